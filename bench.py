@@ -352,6 +352,21 @@ def root_identity_error(ctx, nb, nblb, a, dev):
     return e
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: what the timed path computed in its last step, one DIR/<name>.npy (float64) per array, so that two
+    builds can be compared output for output (every input is seeded: the same arguments give the same inputs in every run)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def timestep_mode(args, dev, world=1, rank=0):
     """1 step = one time step, all operators on the GPU(s), every loop inside librbl; with N > 1 the mobility
     product of every Krylov iteration is tile-pair sharded (one all-reduce per iteration)."""
@@ -414,6 +429,9 @@ def timestep_mode(args, dev, world=1, rank=0):
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
+    if args.dump_outputs and rank == 0:                     # the body configuration the last timed step left
+        X, Q = ctx.get_config(nb)
+        dump_outputs(args.dump_outputs, {"body_positions": X, "body_quaternions": Q})
     phases = phase_block(ctx, args.steps, dev, world)
     ctx.set_timing(False)
     sec_t = torch.tensor([(t1 - t0) / args.steps], dtype=torch.float64, device=dev)
@@ -486,6 +504,8 @@ def brownian_mode(args, dev, world, rank):
         dist.all_reduce(sec, op=dist.ReduceOp.MAX)
     ctx.sync_check()
     its, est = ctx.lanczos_report()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"M_half_W": out.cpu().numpy()})
     if rank == 0:
         sec = float(sec.item())
         pc = args.mhalf == "lanczos_pc"
@@ -1206,6 +1226,8 @@ def main():
                     "default gpurun_out/bench_detail.json")
     ap.add_argument("--notes", action="store_true", help="print the definitions of the line's keys and exit")
     ap.add_argument("--dump-check", default="", help="write a row sample of the result to PATH.rank<r>.npz (tests compare it with the CPU oracle)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy "
+                    "(float64; apply_M: blob_positions, blob_velocities; timestep: body_positions, body_quaternions; brownian: M_half_W)")
     args = ap.parse_args()
 
     if args.notes:
@@ -1306,6 +1328,7 @@ def main():
         return roof
 
     partitionings = None
+    outputs = None          # --dump-outputs: host copies of the last timed step's result
     if not multi:
         # ---- one GPU: blob positions -> U = B M B F, the kernel bracketed by events on its own stream ------------------------
         ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
@@ -1330,6 +1353,8 @@ def main():
         barrier()
         t1 = time.perf_counter()
         ctx.sync_check()
+        if args.dump_outputs:
+            outputs = {"blob_positions": r_all.cpu().numpy(), "blob_velocities": U_full.cpu().numpy()}
         elapsed = t1 - t0
         kern_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps
         # the same K steps twice more: box-to-box and run-to-run spread of this kernel (20.3 - 22.1 ms in round 3) is larger than
@@ -1404,6 +1429,8 @@ def main():
             if split == 0:
                 elapsed, kern_ms, roof = el, k_ms, rf
                 U_check = U_full.clone()
+                if args.dump_outputs:
+                    outputs = {"blob_positions": r_all.cpu().numpy(), "blob_velocities": U_check.cpu().numpy()}
         ctx.set_option("comm_split", 0)
         ctx.set_timing(False)
         repeats = None
@@ -1416,6 +1443,8 @@ def main():
         np.savez("%s.rank%d.npz" % (args.dump_check, rank), row0=b0, values=U_check[3 * b0:3 * b0 + 24].cpu().numpy(), world=world, rank=rank)
 
     phase = os.environ.get("RBL_BENCH_PHASE", "all")       # set by self_launch: main | timestep | all
+    if outputs is not None and rank == 0 and phase != "timestep":
+        dump_outputs(args.dump_outputs, outputs)
     if phase == "timestep":                                  # second job of a self-launched N-rank run: only the time steps
         tstep = timestep_variants(args, ctx, sm, c, nb, nblb, wall, dev, world, stream, barrier, multi)
         if rank == 0:
@@ -1476,7 +1505,7 @@ def main():
     others = None
     dropin = None
     dropin_after = None
-    multi = None
+    mrhs = None
     if world == 1 and args.other_configs and args.config == "cfg3" and phase != "main" and not args.variant and not args.jsplit:
         try:                                                 # (before cfg 5 maps 189 GB: small host-boundary calls measured after it run several times slower)
             dropin = dropin_block(dev)
@@ -1493,11 +1522,11 @@ def main():
             others = {"error": repr(e)}
             failed = failed or "other-configs part failed"
         try:
-            multi = multi_rhs_block(dev, stream)
+            mrhs = multi_rhs_block(dev, stream)
         except Exception as e:
             import traceback
             traceback.print_exc()
-            multi = {"error": repr(e)}
+            mrhs = {"error": repr(e)}
             failed = failed or "multi-RHS part failed"
         try:                                                 # the same small host-boundary calls once more, now that cfg 5 has mapped and freed 189 GB
             dropin_after = dropin_block(dev, names=("cfg2",))
@@ -1517,8 +1546,8 @@ def main():
             line["dropin"] = dropin
         if dropin_after is not None:
             line["dropin_after_cfg5"] = dropin_after
-        if multi is not None:
-            line["multi_rhs"] = multi
+        if mrhs is not None:
+            line["multi_rhs"] = mrhs
         if world == 1 and args.cpu_budget > 0:
             cb = cpu_baseline(c, nb, nblb, wall, args.cpu_budget)
             line["cpu_baseline"] = cb["1core"]

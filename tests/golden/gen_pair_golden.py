@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/pair_kernels.json from the REFERENCE's own compiled
+"""Generate tests/golden/pair_kernels.json, pair_blocks_assembly.json and
+pair_kernels_random.npz from the REFERENCE's own compiled
 pair kernels (oracle/_ref/libref_pair.so, built by oracle/build_ref.sh from
 /root/reference/src/c_rigid_obj.cpp:31-142).
 
@@ -135,6 +136,27 @@ def assembly_cases():
     print("wrote", len(cases), "assembly-level blocks")
 
 
+def random_draws(n=2000):
+    """Third fixture, pair_kernels_random.npz: the first n draws of the seeded argument stream of
+    tests/test_oracle.py::test_live_reference_pair_kernels_if_built (same generator, same order) with the
+    reference's outputs, so that the test checks them where oracle/_ref is not built."""
+    ref = RefPair()
+    rng = np.random.default_rng(7)
+    v = np.zeros((n, 3)); a = np.zeros(n); M = np.zeros((n, 9)); h = np.zeros(n)
+    rpy_out = np.zeros((n, 6)); wall_out = np.zeros((n, 9))
+    for k in range(n):
+        v[k] = rng.uniform(-5, 5, 3)
+        a[k] = float(rng.uniform(0.05, 2.0))
+        M[k] = rng.standard_normal(9)
+        h[k] = float(rng.uniform(0.01, 8))
+        rpy_out[k] = ref.rpy(*v[k], 0, 1, 1 / a[k])
+        wall_out[k] = ref.wall(v[k][0], v[k][1], abs(v[k][2]) + h[k], M[k], 0, 1, h[k])
+    np.savez(os.path.join(os.path.dirname(os.path.abspath(__file__)), "pair_kernels_random.npz"),
+             v=v, a=a, M=M, h=h, rpy_out=rpy_out, wall_out=wall_out)
+    print("wrote", n, "random rpy + wall draws")
+
+
 if __name__ == "__main__":
     main()
     assembly_cases()
+    random_draws()
