@@ -42,6 +42,7 @@ extern "C" {
 #define RBL_ERR_NONFINITE 10  /* result contains inf/nan                                  */
 #define RBL_ERR_ARG 11
 #define RBL_ERR_COMM 12       /* a collective failed (RCCL error, librccl not loadable, callback returned non-zero) */
+#define RBL_ERR_CAPACITY 13   /* a bounded list overflowed (interaction neighbour lists); nothing was truncated silently */
 
 typedef struct rbl_ctx rbl_ctx;
 
@@ -411,7 +412,9 @@ int rbl_comm_allgatherv_dev(rbl_ctx *ctx, double *d_buf, const int64_t *offsets,
 #define RBL_T_COLLECTIVE 3  /* the all-reduce callback of rbl_set_comm                                          */
 #define RBL_T_DENSE 4       /* dense B M B build, Cholesky, L W (RBL_MHALF_CHOLESKY)                            */
 #define RBL_T_TOTAL 5       /* whole solver calls                                                               */
-#define RBL_T_COUNT 6
+#define RBL_T_FORCES 6      /* configuration-dependent forces (section 4): neighbour lists, pair kernel, K^T f.  Nothing is
+                               recorded while interactions are off, and the phase opens no RBL_T_TOTAL bracket           */
+#define RBL_T_COUNT 7
 int rbl_set_timing(rbl_ctx *ctx, int on);
 int rbl_reset_timings(rbl_ctx *ctx);
 int rbl_get_timings(rbl_ctx *ctx, double *ms, int64_t *calls);
@@ -490,12 +493,56 @@ enum {
                                       dependent chain of diagonal solves in one wave, fifteen waves streaming the factor with the next
                                       step's loads already in flight, one barrier a step: k_block_solve_pipe); 0: the two-barrier kernel
                                       of rounds 1-4 (k_block_solve).  Same sums per row in another association                            */
-  RBL_OPT_COUNT = 33
+  RBL_OPT_INTERACTION_CULL = 33,   /* [1] test hook: the interaction kernel walks only the bodies within 2 R_body + r_cut of each body;
+                                      0: every other body is a neighbour (results are bitwise the same: the cull is exact and the pairs
+                                      beyond r_cut are skipped either way)                                                          */
+  RBL_OPT_COUNT = 34
 };
 int rbl_set_option(rbl_ctx *ctx, int option, int64_t value);
 int rbl_get_option(const rbl_ctx *ctx, int option, int64_t *value);
 int rbl_option_info(int option, const char **name, int64_t *min_value, int64_t *max_value, int64_t *default_value);
 int rbl_option_key(const char *name);
+
+/* ===================================================================== */
+/* 4. Configuration-dependent forces (rigid_body_light_amd/csrc/rbl_forces.hip) */
+/* ===================================================================== */
+/* A force model on the blobs, evaluated on the GPU at the context's configuration (the reference has none).  h = z of a
+ * blob centre (wall at z = 0), a = the blob radius of rbl_set_parameters, r_ij = r_i - r_j, r = |r_ij|:
+ *   weight          every blob gets -w z^ (w: buoyant weight per blob);
+ *   wall repulsion  only with the wall (rbl_set_wall_pc): U_w(h) = eps_wall exp(-(h - a) / b_wall) for h >= a, continued by
+ *                   its tangent below h = a (there the force is the constant eps_wall / b_wall along +z^);
+ *   steric          between blobs of DIFFERENT bodies: U_b(r) = eps_blob (2a / r) exp(-(r - 2a) / b_blob) for r >= 2a,
+ *                   continued by its tangent below r = 2a (bounded force; coincident blobs, r = 0, exert none); pairs
+ *                   with r > r_cut are skipped.  Pairs inside one rigid body are left out (their central forces sum to
+ *                   zero force and torque on the body).
+ * Body force / torque about the body centre = K^T f_blob.  The evaluation is deterministic (ordered pairs, no atomics): the
+ * same configuration gives bitwise the same forces on every call and every rank (multi-GPU contexts evaluate the whole
+ * model, replicated).
+ *
+ * rbl_set_interactions: on = 0 switches the model off (the steps are then exactly what they are without it).  Needs
+ * rbl_set_parameters first (RBL_ERR_STATE); b_wall, b_blob > 0, eps_wall, eps_blob >= 0, 2a <= r_cut, all finite, or
+ * RBL_ERR_ARG and the previous model stays in place.  rbl_get_interactions returns it (params: w, eps_wall, b_wall,
+ * eps_blob, b_blob, r_cut; either pointer may be NULL).
+ *
+ * Inside rbl_step_deterministic and rbl_step_brownian, with the model on, its forces at q^n (the configuration the step
+ * starts from -- for the Brownian step the one RHS_and_Midpoint is called on, reference c_rigid_obj.cpp:917-976) are added
+ * to the caller's F_body in the REFERENCE convention before the right-hand side [slip; -F_body] is formed:
+ * U = -N F_body, so physical forces enter as F_body - K^T f_phys.  No lower-level entry point (rbl_RHS_and_Midpoint_dev,
+ * rbl_gmres_saddle_dev, ...) adds them.
+ *
+ * The queries return PHYSICAL forces (a force along +z^ pushes the body up, U = +N K^T f):
+ *   rbl_interaction_forces_dev: d_f_blob[3 N_blobs] device or NULL, d_FT_body[6 N_bod] device (force, torque per body),
+ *       energy: host scalar or NULL (the total potential energy; asking for it synchronises the stream).  Enqueued on the
+ *       context's stream; a neighbour-list overflow is latched in the device error word (rbl_sync_check: RBL_ERR_CAPACITY).
+ *   rbl_interaction_forces: the same into host arrays (synchronous). */
+int rbl_set_interactions(rbl_ctx *ctx, double w, double eps_wall, double b_wall, double eps_blob, double b_blob,
+                         double r_cut, int on);
+int rbl_get_interactions(const rbl_ctx *ctx, double *params6, int *on);
+int rbl_interaction_forces_dev(rbl_ctx *ctx, double *d_f_blob, double *d_FT_body, double *energy);
+int rbl_interaction_forces(rbl_ctx *ctx, double *f_blob, double *FT_body, double *energy);
+/* what the last evaluation walked (reporting, tools/bench_interactions.py): candidate (ordered) body pairs in the neighbour
+ * lists and ordered blob pairs inside r_cut; synchronises the stream */
+int rbl_interaction_stats(rbl_ctx *ctx, int64_t *body_pairs, int64_t *blob_pairs);
 
 #ifdef __cplusplus
 }

@@ -81,6 +81,12 @@ def lib():
         L.rbl_set_timing.argtypes = [vp, C.c_int]
         L.rbl_reset_timings.argtypes = [vp]
         L.rbl_get_timings.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
+        L.rbl_set_interactions.argtypes = [vp, dbl, dbl, dbl, dbl, dbl, dbl, C.c_int]
+        L.rbl_get_interactions.argtypes = [vp, C.POINTER(dbl), C.POINTER(C.c_int)]
+        L.rbl_interaction_forces_dev.argtypes = [vp, vp, vp, C.POINTER(dbl)]
+        L.rbl_interaction_forces.argtypes = [vp, vp, vp, C.POINTER(dbl)]
+        L.rbl_interaction_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+        L.rbl_get_sizes.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         _LIB = L
     return _LIB
 
@@ -100,6 +106,7 @@ class DeviceContext:
             raise RblError("rbl_create failed")
         cfg = np.ascontiguousarray(np.zeros((1, 3)) if cfg is None else cfg, dtype=np.float64)
         self._chk(self.L.rbl_set_parameters(self.h, a, dt, kBT, eta, cfg.ctypes.data, cfg.shape[0]))
+        self._a = float(a)
         self._chk(self.L.rbl_set_wall_pc(self.h, int(bool(wall))))
         self._chk(self.L.rbl_set_stream(self.h, stream_ptr))
         self._stream_ptr = int(stream_ptr or 0)
@@ -219,7 +226,7 @@ class DeviceContext:
         self._chk(self.L.rbl_set_stream(self.h, stream_ptr))
         self._stream_ptr = int(stream_ptr or 0)
 
-    TIMING_PHASES = ("product", "per_body", "factor", "collective", "dense", "total")      # RBL_T_* of include/rbl.h
+    TIMING_PHASES = ("product", "per_body", "factor", "collective", "dense", "total", "forces")   # RBL_T_* of include/rbl.h
 
     def set_timing(self, on=True):
         """hipEvent brackets around the phases of librbl's own solvers (rbl_set_timing)"""
@@ -234,6 +241,58 @@ class DeviceContext:
         ms, calls = (C.c_double * n)(), (C.c_int64 * n)()
         self._chk(self.L.rbl_get_timings(self.h, ms, calls))
         return {k: (ms[i], calls[i]) for i, k in enumerate(self.TIMING_PHASES)}
+
+    # -- configuration-dependent forces (include/rbl.h section 4) ----------------------
+    def set_interactions(self, w=0.0, eps_wall=0.0, b_wall=1.0, eps_blob=0.0, b_blob=1.0, r_cut=None, on=True):
+        """weight w per blob, wall repulsion eps_wall exp(-(h - a)/b_wall), blob-blob repulsion eps_blob (2a/r) exp(-(r - 2a)/b_blob)
+        between bodies, truncated at r_cut (default 2a + 20 b_blob); the whole-step entry points and the krylov.py steppers add
+        these forces at q^n.  on=False switches the model off."""
+        if r_cut is None:
+            r_cut = 2.0 * self._a + 20.0 * b_blob
+        self._chk(self.L.rbl_set_interactions(self.h, float(w), float(eps_wall), float(b_wall), float(eps_blob), float(b_blob),
+                                              float(r_cut), int(bool(on))))
+
+    def interaction_params(self):
+        """{w, eps_wall, b_wall, eps_blob, b_blob, r_cut, on, a} of the context's force model"""
+        v, on = (C.c_double * 6)(), C.c_int(0)
+        self._chk(self.L.rbl_get_interactions(self.h, v, C.byref(on)))
+        return dict(zip(("w", "eps_wall", "b_wall", "eps_blob", "b_blob", "r_cut"), list(v)), on=bool(on.value), a=self._a)
+
+    def interactions_on(self):
+        on = C.c_int(0)
+        self._chk(self.L.rbl_get_interactions(self.h, None, C.byref(on)))
+        return bool(on.value)
+
+    def interaction_forces_dev(self, d_f_blob, d_FT_body, energy=False):
+        """PHYSICAL forces at the current configuration into device buffers (addresses or None); energy=True also returns the
+        total potential energy (synchronises the stream)"""
+        E = C.c_double(0.0)
+        self._chk(self.L.rbl_interaction_forces_dev(self.h, d_f_blob, d_FT_body, C.byref(E) if energy else None))
+        return E.value if energy else None
+
+    def interaction_forces(self):
+        """-> (f_blob (N, 3), FT_body (6 N_bod,)): PHYSICAL blob forces and body force / torque about the centre (U = +N FT)"""
+        import numpy as np
+        nb, nblb = self._sizes()
+        f = np.zeros(3 * nb * nblb); FT = np.zeros(6 * nb)
+        self._chk(self.L.rbl_interaction_forces(self.h, f.ctypes.data, FT.ctypes.data, None))
+        return f.reshape(-1, 3), FT
+
+    def interaction_energy(self):
+        E = C.c_double(0.0)
+        self._chk(self.L.rbl_interaction_forces(self.h, None, None, C.byref(E)))
+        return E.value
+
+    def interaction_stats(self):
+        """(candidate body pairs, ordered blob pairs inside r_cut) of the last evaluation"""
+        bp, pp = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.rbl_interaction_stats(self.h, C.byref(bp), C.byref(pp)))
+        return bp.value, pp.value
+
+    def _sizes(self):
+        nb, nblb = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), C.byref(nblb)))
+        return nb.value, nblb.value
 
     def apply_M(self, dF, dr, n_blobs, row_begin, row_end, dout):
         """dF, dr, dout: integer device addresses (tensor.data_ptr())."""

@@ -416,6 +416,32 @@ struct CManyBodies {
     check(rbl_evolve_X_Q_RFD(ctx, U.data()));
   }
 
+  // configuration-dependent forces (include/rbl.h section 4; the reference has none)
+  void set_interactions(double w, double eps_wall, double b_wall, double eps_blob, double b_blob, double r_cut, bool on)
+  {
+    check(rbl_set_interactions(ctx, w, eps_wall, b_wall, eps_blob, b_blob, r_cut, on ? 1 : 0));
+  }
+  // the model's body forces in the REFERENCE convention, -K^T f_phys (6 N_bod): add them to F in rhs = [0; -F]
+  darr interaction_forces()
+  {
+    darr out(6 * (py::ssize_t)n_bod());
+    int rc;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_interaction_forces(ctx, nullptr, out.mutable_data(), nullptr);
+    }
+    check(rc);
+    double *o = out.mutable_data();
+    for (py::ssize_t i = 0; i < out.size(); ++i) o[i] = -o[i];
+    return out;
+  }
+  double interaction_energy()
+  {
+    double E = 0.0;
+    check(rbl_interaction_forces(ctx, nullptr, nullptr, &E));
+    return E;
+  }
+
   void set_option(const std::string &name, int64_t value)
   {
     const int key = rbl_option_key(name.c_str());
@@ -483,6 +509,10 @@ PYBIND11_MODULE(c_rigid, m)
       .def("M_RFD_from_U", &CManyBodies::M_RFD_from_U, py::arg("U"), py::arg("W"), py::arg("delta") = 1.0e-3)
       .def("KT_RFD_from_U", &CManyBodies::KT_RFD_from_U, py::arg("U"), py::arg("W"), py::arg("delta") = 1.0e-3)
       .def("evolve_X_Q_RFD", &CManyBodies::evolve_X_Q_RFD, py::arg("U"))
+      .def("set_interactions", &CManyBodies::set_interactions, py::arg("w"), py::arg("eps_wall"), py::arg("b_wall"), py::arg("eps_blob"),
+           py::arg("b_blob"), py::arg("r_cut"), py::arg("on") = true)
+      .def("interaction_forces", &CManyBodies::interaction_forces, "force model's body forces/torques, reference convention (-K^T f)")
+      .def("interaction_energy", &CManyBodies::interaction_energy)
       .def("set_option", &CManyBodies::set_option, py::arg("name"), py::arg("value"))
       .def("get_option", &CManyBodies::get_option, py::arg("name"))
       .def("handle", &CManyBodies::handle, "address of the underlying rbl_ctx (for the ctypes device API)")

@@ -7,6 +7,7 @@
 //   rbl_roots.hip     M^{1/2} W: dense Cholesky path and the Lanczos roots
 //   rbl_solvers.hip   GMRES on the saddle operator
 //   rbl_steps.hip     whole time steps, random finite differences
+//   rbl_forces.hip    configuration-dependent forces (weight, wall and steric repulsion)
 // None of these symbols is exported from librbl.so.
 #pragma once
 #include "rbl_internal.hpp"
@@ -69,5 +70,13 @@ int mhalf_dev_multi(rbl_ctx *c, const double *d_r, int64_t nbl, const double *d_
 
 // ---- rbl_steps.hip ------------------------------------------------------------------------------------------------
 int m_rfd_core(rbl_ctx *c, const double *d_W, const double *Wh, double delta, double *d_out, double *d_r, double *d_work);
+
+// ---- rbl_forces.hip -----------------------------------------------------------------------------------------------
+// the model's PHYSICAL forces at the context's configuration: d_f (3 N, may be NULL), d_FT = K^T f (6 N_bod, may be NULL),
+// per-blob energies d_e (N, may be NULL); enqueued on the context's stream under RBL_T_FORCES
+int ia_eval(rbl_ctx *c, double *d_f, double *d_FT, double *d_e);
+// the steps' use of it: d_force (6 N_bod, reference convention) -= K^T f_phys at the current configuration, then the latched
+// device flags are checked (a neighbour-list overflow fails the step).  No-op while the model is off.
+int ia_add_to_step_force(rbl_ctx *c, double *d_force);
 
 #pragma GCC visibility pop

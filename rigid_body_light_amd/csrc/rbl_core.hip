@@ -34,6 +34,8 @@ int rbl_flags_to_status(rbl_ctx *c, unsigned f)
     return rbl_fail(c, RBL_ERR_OVERLAP, "ERROR: TWO BLOBS ARE OVERLAPPING OR TOO CLOSELY POSITIONED.");
   if (f & RBL_FLAG_NOT_SPD)
     return rbl_fail(c, RBL_ERR_NOT_SPD, "Cholesky: matrix is not positive definite");
+  if (f & RBL_FLAG_CAPACITY)
+    return rbl_fail(c, RBL_ERR_CAPACITY, "interactions: a body has more neighbours within 2 R_body + r_cut than its list holds");
   if (f & RBL_FLAG_INTERNAL)
     return rbl_fail(c, RBL_ERR_HIP, "internal: a tile of the per-body factorisation waited for its dependencies longer than the time limit");
   return rbl_fail(c, RBL_ERR_NONFINITE, "mobility product produced a non-finite value");
@@ -278,7 +280,7 @@ void rbl_destroy(rbl_ctx *c)
     if (c->ev_check) (void)hipEventDestroy(c->ev_check);
     RblDevBuf *bufs[] = {&c->d_r, &c->d_F, &c->d_U, &c->d_part, &c->d_W, &c->d_cfg,
                          &c->d_XQ, &c->d_mat, &c->d_tmp, &c->d_tmp2, &c->d_chol,
-                         &c->d_lever, &c->d_pos, &c->d_invM2, &c->d_NL, &c->d_sad, &c->d_blkL, &c->d_blkLinv, &c->d_blkX, &c->d_blkTmp, &c->d_blkXf, &c->d_blkAug, &c->d_commStage, &c->d_tlQ, &c->d_tlCb, &c->d_tlCs, &c->d_tlA, &c->d_tlLinv, &c->d_tlX, &c->d_tlT, &c->d_tlZ, &c->d_ktl, &c->d_bfL, &c->d_bfLinv, &c->d_bfX, &c->d_bfPC, &c->d_pcw, &c->d_pcMK, &c->d_bd, &c->d_bd2, &c->d_gm, &c->d_step, &c->d_hist};
+                         &c->d_lever, &c->d_pos, &c->d_invM2, &c->d_NL, &c->d_sad, &c->d_blkL, &c->d_blkLinv, &c->d_blkX, &c->d_blkTmp, &c->d_blkXf, &c->d_blkAug, &c->d_commStage, &c->d_tlQ, &c->d_tlCb, &c->d_tlCs, &c->d_tlA, &c->d_tlLinv, &c->d_tlX, &c->d_tlT, &c->d_tlZ, &c->d_ktl, &c->d_bfL, &c->d_bfLinv, &c->d_bfX, &c->d_bfPC, &c->d_pcw, &c->d_pcMK, &c->d_bd, &c->d_bd2, &c->d_gm, &c->d_step, &c->d_hist, &c->d_ia};
     for (RblDevBuf *b : bufs)
       if (b->p) (void)hipFree(b->p);
     if (c->chol_aux.stream) {

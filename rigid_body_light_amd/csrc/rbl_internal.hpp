@@ -193,13 +193,19 @@ struct rbl_ctx {
   std::vector<hipEvent_t> ev_pool;
   struct TimedSpan { int phase; hipEvent_t a, b; };
   std::vector<TimedSpan> ev_spans;
-  double t_ms[RBL_T_COUNT] = {0, 0, 0, 0, 0, 0};
-  int64_t t_calls[RBL_T_COUNT] = {0, 0, 0, 0, 0, 0};
+  double t_ms[RBL_T_COUNT] = {0, 0, 0, 0, 0, 0, 0};
+  int64_t t_calls[RBL_T_COUNT] = {0, 0, 0, 0, 0, 0, 0};
   bool gmres_predict = true;    // RBL_OPT_GMRES_PREDICT_CHECKS
   bool gmres_overlap = true;    // RBL_OPT_GMRES_OVERLAP_CHECK: next iteration's preconditioner enqueued before the host reads the Hessenberg column
   bool fused_krylov = true;     // RBL_OPT_FUSED_KRYLOV
   hipEvent_t ev_check = nullptr;   // recorded behind the asynchronous copy of the Hessenberg columns (overlapped convergence test)
   int gmres_last_used = 0;      // iterations of the previous converged solve: where the next one looks first (launch-bound systems)
+  // configuration-dependent forces (rbl_forces.hip; include/rbl.h section 4): the model and the device lists of its last evaluation
+  bool ia_on = false;
+  double ia_w = 0.0, ia_eps_wall = 0.0, ia_b_wall = 1.0, ia_eps_blob = 0.0, ia_b_blob = 1.0, ia_r_cut = 0.0;
+  bool ia_cull = true;                              // RBL_OPT_INTERACTION_CULL
+  RblDevBuf d_ia;                                   // f_blob | energy per blob | neighbour counts | lists | pairs per blob
+  int ia_nb = 0, ia_nblb = 0, ia_cap = 0;           // shape of what d_ia holds (0: nothing evaluated yet)
   // lanczos
   int lanczos_max_iter = 100;
   bool lanczos_out_norm = true;  // preconditioned root: final stopping test in the Euclidean norm of the increment (RBL_OPT_LANCZOS_EUCLID_NORM)

@@ -22,6 +22,7 @@
 #define RBL_FLAG_NONFINITE 4
 #define RBL_FLAG_NOT_SPD 8
 #define RBL_FLAG_INTERNAL 16   // a bounded wait between workgroups ran out (rbl_tilechol.hip): never expected, never a hang
+#define RBL_FLAG_CAPACITY 32   // an interaction neighbour list overflowed its cap (rbl_forces.hip): reported, never truncated silently
 
 struct RblParams {
   double a;        // blob radius

@@ -26,7 +26,8 @@ static int step_buffers(rbl_ctx *c, int64_t n3, int64_t nb6, double **rhs, doubl
 }
 
 // One deterministic time step on the object's own configuration: solve [M -K; K^T 0][lambda; U] = [slip; -F] by
-// right-preconditioned GMRES (rbl_gmres_saddle_dev), then evolve_X_Q(U) (:865-878).  F_body: host, 6 N_bod;
+// right-preconditioned GMRES (rbl_gmres_saddle_dev), then evolve_X_Q(U) (:865-878).  F = F_body - K^T f_phys(q^n) when the
+// force model is on (rbl_set_interactions), F_body otherwise.  F_body: host, 6 N_bod;
 // slip: host, 3 N_blobs, or NULL for zero.  warm_start: 0 cold; 1 start from the previous call's solution x_n; 2 from
 // 2 x_n - x_{n-1}; 3 from 3 x_n - 3 x_{n-1} + x_{n-2} (as far as the history reaches): under a smooth forcing the solution
 // moves smoothly with the configuration, and at cfg 3 GMRES then needs 12 / 6 / 2-3 iterations to 1e-8 instead of 18.
@@ -42,6 +43,7 @@ int rbl_step_deterministic(rbl_ctx *c, const double *F_body, const double *slip,
   if (slip) { if ((rc = copy_h2d(c, rhs, slip, sizeof(double) * (size_t)n3))) return rc; }
   else RBL_HIP(c, hipMemsetAsync(rhs, 0, sizeof(double) * (size_t)n3, c->stream));
   if ((rc = copy_h2d(c, dforce, F_body, sizeof(double) * (size_t)nb6))) return rc;
+  if ((rc = ia_add_to_step_force(c, dforce))) return rc;             // the force model at q^n (include/rbl.h section 4)
   rbl_launch_axpby(c->stream, nb6, -1.0, dforce, 0.0, nullptr, rhs + n3);
   const int64_t nsys = n3 + nb6;
   if ((rc = rbl_dev_reserve(c, c->d_hist, sizeof(double) * (size_t)(3 * nsys)))) return rc;
@@ -82,6 +84,7 @@ int rbl_step_brownian(rbl_ctx *c, const double *F_body, const double *slip, cons
   if (slip) { if ((rc = copy_h2d(c, dslip, slip, sizeof(double) * (size_t)n3))) return rc; }
   else RBL_HIP(c, hipMemsetAsync(dslip, 0, sizeof(double) * (size_t)n3, c->stream));
   if ((rc = copy_h2d(c, dforce, F_body, sizeof(double) * (size_t)nb6))) return rc;
+  if ((rc = ia_add_to_step_force(c, dforce))) return rc;             // the force model at q^n, where RHS_and_Midpoint takes its Force
   double *dW = nullptr;
   if (W) {
     if ((rc = rbl_dev_reserve(c, c->d_W, sizeof(double) * 3 * (size_t)n3))) return rc;

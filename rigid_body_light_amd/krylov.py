@@ -50,8 +50,20 @@ class DeterministicStepper:
         self.remember(x)
         return x[: self.n3], x[self.n3:], m, resid
 
+    def forces_at_qn(self, F_body):
+        """F_body plus the context's force model at the current configuration q^n, in the reference convention
+        (rhs [0; -F], U = -N F): F_body - K^T f_phys -- what rbl_step_deterministic / rbl_step_brownian add.  F_body itself
+        (as a device tensor) while the model is off."""
+        Fb = torch.as_tensor(F_body, dtype=torch.float64, device=self.dev).reshape(-1)
+        if not self.ctx.interactions_on():
+            return Fb
+        FT = torch.empty(6 * self.nb, dtype=torch.float64, device=self.dev)
+        self.ctx.interaction_forces_dev(None, FT.data_ptr())
+        self.ctx.sync_check()                     # a neighbour-list overflow fails the step, as in the C steps
+        return Fb - FT
+
     def step(self, F_body, iters=20, rtol=None):
-        lam, U, m, resid = self.solve(F_body, iters, rtol)
+        lam, U, m, resid = self.solve(self.forces_at_qn(F_body), iters, rtol)
         self.ctx.evolve(U.cpu().numpy())          # O(N_bod) host update, then K/positions rebuilt on the GPU
         self.ctx.sync_check()
         return m, resid
@@ -75,7 +87,7 @@ class BrownianStepper(DeterministicStepper):
     """One stochastic (midpoint) time step, assembled from the pieces the reference leaves unassembled
     (`RHS_and_Midpoint`, c_rigid_obj.cpp:917-976):
 
-      1. at q^n      : rhs = [slip - (kBT M_RFD + BI) ; -F_body]  and the predictor configuration
+      1. at q^n      : rhs = [slip - (kBT M_RFD + BI) ; -F]  and the predictor configuration, F = forces_at_qn(F_body)
                        q^{n+1/2} = q^n displaced by (dt/2) Kinv c1 M^{1/2} W1      (librbl: rbl_RHS_and_Midpoint_dev)
       2. at q^{n+1/2}: right-preconditioned GMRES on the saddle operator -> [lambda ; U]
       3.               q^{n+1} = q^n displaced by dt U                              (evolve_X_Q, :865-878)
@@ -105,7 +117,7 @@ class BrownianStepper(DeterministicStepper):
     def step(self, F_body, slip=None, W=None, seed=0, method=1, iters=20, rtol=None, split_rand=True,
              delta=1.0e-4):
         Xn, Qn = self.ctx.get_config(self.nb)
-        rhs, Xh, Qh = self.rhs_and_midpoint(F_body, slip, W, seed, method, split_rand, delta)
+        rhs, Xh, Qh = self.rhs_and_midpoint(self.forces_at_qn(F_body), slip, W, seed, method, split_rand, delta)
         self.ctx.set_config(Xh, Qh)                      # operators and preconditioner at the predictor configuration
         x, m, resid = self.saddle_solve(rhs, iters, rtol)
         U = x[self.n3:].cpu().numpy()

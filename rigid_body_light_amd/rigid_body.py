@@ -10,7 +10,7 @@ reference src/Rigid.py:54,60,66).
 Beyond the reference surface (its C++ has these, its Python does not): `solve_saddle`, `solve_saddle_multi`,
 `body_mobility_matrix`, `M_half_W`, `M_RFD`,
 `KTinv_RFD`, `M_RFD_cfgs`, `M_RFD_from_U`, `KT_RFD_from_U`, `evolve_rigid_bodies_RFD`, `apply_M_multi`,
-`dense_mobility`.
+`dense_mobility`, and a force model the reference does not have (`set_interactions`, `interaction_forces`).
 """
 import numpy as np
 
@@ -35,6 +35,7 @@ class RigidBody:
         self.cb = _ext.CManyBodies()
         self.precision = self.cb.precision
         self.blobs_per_body = template.size // 3
+        self._a = a                          # (the force model's default cutoff)
         self.cb.setParameters(a, dt, _KBT_IN_WRAPPER, eta, template.reshape(self.blobs_per_body, 3))
         self.cb.setWallPC(bool(wall_PC))
         self.cb.setBlkPC(bool(block_PC))
@@ -201,6 +202,23 @@ class RigidBody:
         W = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1))
         return self.cb.step_brownian(self._require(F_body, "body"), None if slip is None else self._require(slip, "blob"),
                                      W, seed, method, split_rand, delta, max_iter, rtol)
+
+    def set_interactions(self, w=0.0, eps_wall=0.0, b_wall=1.0, eps_blob=0.0, b_blob=1.0, r_cut=None, on=True):
+        """Configuration-dependent forces on the blobs (include/rbl.h section 4): weight w per blob (-w z^), wall repulsion
+        eps_wall exp(-(h - a)/b_wall) (with wall_PC), steric repulsion eps_blob (2a/r) exp(-(r - 2a)/b_blob) between blobs of
+        different bodies, cut off at r_cut (default 2a + 20 b_blob).  step_deterministic / step_brownian then add these forces
+        at the configuration the step starts from; on=False switches the model off."""
+        if r_cut is None:
+            r_cut = 2.0 * self._a + 20.0 * b_blob
+        self.cb.set_interactions(float(w), float(eps_wall), float(b_wall), float(eps_blob), float(b_blob), float(r_cut), bool(on))
+
+    def interaction_forces(self):
+        """The model's body forces and torques at the current configuration, 6 * N_bodies, in the reference convention
+        (-K^T f_phys): add them to F in rhs = [0 ; -F] of a solve over apply_saddle."""
+        return self.cb.interaction_forces()
+
+    def interaction_energy(self):
+        return self.cb.interaction_energy()
 
     def apply_M_multi(self, forces, positions):
         """k right-hand sides at once, forces (k, 3N); k >= 4 runs on the fp64 matrix cores."""
