@@ -544,6 +544,50 @@ int rbl_interaction_forces(rbl_ctx *ctx, double *f_blob, double *FT_body, double
  * lists and ordered blob pairs inside r_cut; synchronises the stream */
 int rbl_interaction_stats(rbl_ctx *ctx, int64_t *body_pairs, int64_t *blob_pairs);
 
+/* ===================================================================== */
+/* 5. Ensembles of independent replicas (rigid_body_light_amd/csrc/rbl_ensemble.hip) */
+/* ===================================================================== */
+/* R independent replicas of one small system, resident on the device: every replica shares the context's structure,
+ * parameters (a, eta, dt, kBT), wall flag and force model (section 4) and has its own X (3 N_bod) and Q (4 N_bod); arrays
+ * over replicas are replica-major (replica r's X at X + 3 N_bod r).  The reference has no such object; its one-system
+ * counterparts are cited per entry.  One step advances every replica with a fixed number of kernel launches whatever R is,
+ * with the scheme of rbl_step_deterministic / rbl_step_brownian (reference c_rigid_obj.cpp:917-976 for the stochastic
+ * midpoint step), and ends in ONE small read-back (iterations, residuals, an error word per replica).  Replicas never
+ * interact, neither hydrodynamically nor through the force model.  Ensemble calls leave the context's own configuration
+ * (rbl_set_config) alone.
+ *
+ * Limits: the sizes of the one-kernel solver (N_bod N_blb <= 256, N_bod <= 64, max_iter <= 255, the LDS must fit) and
+ * 1 <= R <= 65535, else RBL_ERR_SIZE; a context with a communicator gives RBL_ERR_ARG (several GPUs run separate ensembles in
+ * separate processes).  The ensemble's GMRES always uses the diagonal preconditioner (rbl_set_blk_pc is ignored: it changes
+ * iteration counts, not the solution); its Brownian root is the dense Cholesky factor (RBL_MHALF_CHOLESKY).
+ * Errors: RBL_ERR_STATE before rbl_set_parameters / rbl_ensemble_set_config (or after the structure changed), and the codes
+ * of the one-system steps (RBL_ERR_OVERLAP, RBL_ERR_BELOW_WALL, RBL_ERR_NOT_SPD, RBL_ERR_NONFINITE, ...); rbl_last_error names
+ * the first failing replica.  A step commits only if every replica succeeded: on any error no replica's X or Q changes.
+ *
+ *   rbl_ensemble_set_config   setConfig (:201-233) for all replicas: X[R 3 N_bod], Q[R 4 N_bod] (normalised)
+ *   rbl_ensemble_get_config   getConfig (:235-255): X[R 3 N_bod], Q[R 4 N_bod]
+ *   rbl_ensemble_info         R and N_bod (RBL_ERR_STATE, zeros, when none is set)
+ *   rbl_ensemble_config_dev   the resident X and Q (device pointers, valid until the next ensemble call) for observables
+ *                             computed on the device
+ *   rbl_ensemble_step_deterministic  rbl_step_deterministic for every replica (cold start): F_body[R 6 N_bod],
+ *                             slip[R n3] or NULL, iters[R], resid[R] (either may be NULL); n3 = 3 N_bod N_blb
+ *   rbl_ensemble_step_brownian  rbl_step_brownian(method RBL_MHALF_CHOLESKY) for every replica: W = [W1 | W2 | W_rfd] per
+ *                             replica (R 3 n3) or NULL: replica r then draws its 3 n3 normals as
+ *                             rbl_launch_normal(seed, offset r ceil(3 n3 / 2)) would (Philox pairs; replica 0 sees exactly
+ *                             what rbl_step_brownian draws from the same seed).  kBT <= 1e-10: the deterministic step (:967-970)
+ *   rbl_ensemble_interaction_forces  the force model at every replica's configuration: FT_body[R 6 N_bod] in the REFERENCE
+ *                             convention (-K^T f_phys, what the steps add to F_body), energy[R] (either may be NULL)
+ * The force model enters the steps as in the one-system steps: the right-hand side's force is F_body - K^T f_phys at q^n. */
+int rbl_ensemble_set_config(rbl_ctx *ctx, int R, int N_bod, const double *X, const double *Q);
+int rbl_ensemble_get_config(rbl_ctx *ctx, double *X, double *Q);
+int rbl_ensemble_info(const rbl_ctx *ctx, int *R, int *N_bod);
+int rbl_ensemble_config_dev(rbl_ctx *ctx, const double **d_X, const double **d_Q);
+int rbl_ensemble_step_deterministic(rbl_ctx *ctx, const double *F_body, const double *slip, int max_iter, double rtol,
+                                    int *iters, double *resid);
+int rbl_ensemble_step_brownian(rbl_ctx *ctx, const double *F_body, const double *slip, const double *W, uint64_t seed,
+                               int split_rand, double delta, int max_iter, double rtol, int *iters, double *resid);
+int rbl_ensemble_interaction_forces(rbl_ctx *ctx, double *FT_body, double *energy);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ except ImportError as _e:  # fail loudly: the product has no Python/CPU path
     ) from _e
 
 from .rigid_body import RigidBody  # noqa: E402,F401
+from .ensemble import Ensemble  # noqa: E402,F401
 from .synth import load_structure, make_config, STRUCT_DIR  # noqa: E402,F401
 
-__all__ = ["RigidBody", "c_rigid", "load_structure", "make_config", "STRUCT_DIR"]
+__all__ = ["RigidBody", "Ensemble", "c_rigid", "load_structure", "make_config", "STRUCT_DIR"]

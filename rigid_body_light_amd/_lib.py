@@ -87,6 +87,13 @@ def lib():
         L.rbl_interaction_forces.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
         L.rbl_get_sizes.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.rbl_ensemble_set_config.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+        L.rbl_ensemble_get_config.argtypes = [vp, vp, vp]
+        L.rbl_ensemble_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.rbl_ensemble_config_dev.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.rbl_ensemble_step_deterministic.argtypes = [vp, vp, vp, C.c_int, dbl, vp, vp]
+        L.rbl_ensemble_step_brownian.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_int, dbl, C.c_int, dbl, vp, vp]
+        L.rbl_ensemble_interaction_forces.argtypes = [vp, vp, vp]
         _LIB = L
     return _LIB
 
@@ -288,6 +295,82 @@ class DeviceContext:
         bp, pp = C.c_int64(0), C.c_int64(0)
         self._chk(self.L.rbl_interaction_stats(self.h, C.byref(bp), C.byref(pp)))
         return bp.value, pp.value
+
+    # -- ensembles of independent replicas (include/rbl.h section 5) ---------------------
+    def ensemble_set_config(self, X, Q):
+        """X (R, N_bod, 3), Q (R, N_bod, 4): R independent replicas of the context's structure"""
+        import numpy as np
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        self._chk(self.L.rbl_ensemble_set_config(self.h, X.shape[0], X.shape[1], X.ctypes.data, Q.ctypes.data))
+
+    def ensemble_info(self):
+        """(R, N_bod) of the ensemble, (0, 0) when none is set"""
+        r, nb = C.c_int(0), C.c_int(0)
+        self.L.rbl_ensemble_info(self.h, C.byref(r), C.byref(nb))
+        return r.value, nb.value
+
+    def ensemble_get_config(self):
+        """-> X (R, N_bod, 3), Q (R, N_bod, 4)"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        X = np.zeros((R, nb, 3)); Q = np.zeros((R, nb, 4))
+        self._chk(self.L.rbl_ensemble_get_config(self.h, X.ctypes.data, Q.ctypes.data))
+        return X, Q
+
+    def ensemble_config_dev(self):
+        """device addresses of the resident X and Q (valid until the next ensemble call)"""
+        x, q = C.c_void_p(), C.c_void_p()
+        self._chk(self.L.rbl_ensemble_config_dev(self.h, C.byref(x), C.byref(q)))
+        return x.value, q.value
+
+    def _ens_vec(self, v, per, what):
+        import numpy as np
+        R = self.ensemble_info()[0]
+        v = np.asarray(v, dtype=np.float64)
+        if v.size == per:
+            v = np.broadcast_to(v.reshape(1, per), (R, per))
+        if v.size != R * per:
+            raise ValueError("%s must have %d entries per replica (shape (%d,) or (%d, %d)); got shape %s" % (what, per, per, R, per, v.shape))
+        return np.ascontiguousarray(v.reshape(R, per))
+
+    def ensemble_step_deterministic(self, F_body, max_iter=50, rtol=None, slip=None):
+        """one deterministic step of every replica -> (iterations[R], residual estimates[R]); F_body (6 N_bod,) or (R, 6 N_bod)"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        F = self._ens_vec(F_body, 6 * nb, "F_body")
+        sl = None if slip is None else self._ens_vec(slip, 3 * nb * self._sizes()[1], "slip")
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(self.L.rbl_ensemble_step_deterministic(self.h, F.ctypes.data, None if sl is None else sl.ctypes.data, int(max_iter),
+                                                         float(rtol or 0.0), it.ctypes.data, res.ctypes.data))
+        return it, res
+
+    def ensemble_step_brownian(self, F_body, W=None, seed=0, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1e-8, slip=None):
+        """one stochastic midpoint step of every replica (dense Cholesky root) -> (iterations[R], residual estimates[R]);
+        W: (R, 3 n3) standard normals [W1 | W2 | W_rfd] per replica, or None to draw them from `seed`"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        n3 = 3 * nb * self._sizes()[1]
+        F = self._ens_vec(F_body, 6 * nb, "F_body")
+        sl = None if slip is None else self._ens_vec(slip, n3, "slip")
+        Wh = None
+        if W is not None:
+            Wh = np.ascontiguousarray(np.asarray(W, dtype=np.float64))
+            if Wh.size != R * 3 * n3:
+                raise ValueError("W must have shape (%d, %d); got %s" % (R, 3 * n3, Wh.shape))
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(self.L.rbl_ensemble_step_brownian(self.h, F.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                    None if Wh is None else Wh.ctypes.data, int(seed), int(bool(split_rand)),
+                                                    float(delta), int(max_iter), float(rtol or 0.0), it.ctypes.data, res.ctypes.data))
+        return it, res
+
+    def ensemble_interaction_forces(self):
+        """-> (FT (R, 6 N_bod) in the reference convention -K^T f_phys, energy (R,))"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        FT, E = np.zeros((R, 6 * nb)), np.zeros(R)
+        self._chk(self.L.rbl_ensemble_interaction_forces(self.h, FT.ctypes.data, E.ctypes.data))
+        return FT, E
 
     def _sizes(self):
         nb, nblb = C.c_int(0), C.c_int(0)

@@ -8,6 +8,7 @@
 //   rbl_solvers.hip   GMRES on the saddle operator
 //   rbl_steps.hip     whole time steps, random finite differences
 //   rbl_forces.hip    configuration-dependent forces (weight, wall and steric repulsion)
+//   rbl_ensemble.hip  ensembles of independent replicas of one small system
 // None of these symbols is exported from librbl.so.
 #pragma once
 #include "rbl_internal.hpp"
@@ -78,5 +79,11 @@ int ia_eval(rbl_ctx *c, double *d_f, double *d_FT, double *d_e);
 // the steps' use of it: d_force (6 N_bod, reference convention) -= K^T f_phys at the current configuration, then the latched
 // device flags are checked (a neighbour-list overflow fails the step).  No-op while the model is off.
 int ia_add_to_step_force(rbl_ctx *c, double *d_force);
+// the model for `reps` independent copies of N_bod bodies (an ensemble, rbl_ensemble.hip): body centres d_X (3 N_bod reps), blob
+// positions and lever arms of all copies; steric pairs only inside a copy.  d_work: ia_batch_bytes; *d_f -> the blob forces
+// (3 N reps, inside d_work); d_FT (6 N_bod reps) and per-blob energies d_e may be NULL
+size_t ia_batch_bytes(int N_bod, int N_blb, int reps);
+int ia_eval_batch(rbl_ctx *c, const double *d_X, const double *d_pos, const double *d_lever, int N_bod, int reps, void *d_work,
+                  double **d_f, double *d_FT, double *d_e, unsigned *d_err);
 
 #pragma GCC visibility pop

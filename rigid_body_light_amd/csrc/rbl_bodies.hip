@@ -208,7 +208,7 @@ int bf_build(rbl_ctx *c)
   if ((rc = rbl_dev_reserve(c, c->d_bfL, sizeof(double) * (size_t)msz))) return rc;
   if ((rc = rbl_dev_reserve(c, c->d_bfLinv, rbl_cholesky_batched_work_bytes(m, 1)))) return rc;
   double *Lb = (double *)c->d_bfL.p;
-  rbl_launch_build_M_batched(c->stream, rbl_make_params(S.a, S.eta), false, (const double *)c->d_cfg.p, S.N_blb, 1, Lb, msz, c->d_err);
+  rbl_launch_build_M_batched(c->stream, rbl_make_params(S.a, S.eta), false, false, (const double *)c->d_cfg.p, S.N_blb, 1, Lb, msz, c->d_err);
   if ((rc = rbl_launch_cholesky_batched(c->stream, Lb, m, 1, msz, c->d_err, (double *)c->d_bfLinv.p)))
     return rbl_fail(c, rc, "body-frame cholesky launch failed");
   c->bf_inv = false; c->bf_tables = false;
@@ -500,7 +500,7 @@ int pc_block_factors(rbl_ctx *c, int b0, int b1)
   const RblParams P = rbl_make_params(S.a, S.eta);
   double *Lb = (double *)c->d_blkL.p + (size_t)b0 * (size_t)msz;
   for (int q0 = b0; q0 < b1; q0 += 65535)               // bodies ride in gridDim.z
-    rbl_launch_build_M_batched(c->stream, P, S.wall, (const double *)c->d_pos.p + (size_t)q0 * (size_t)m, S.N_blb,
+    rbl_launch_build_M_batched(c->stream, P, S.wall, false, (const double *)c->d_pos.p + (size_t)q0 * (size_t)m, S.N_blb,
                                (b1 - q0 < 65535) ? b1 - q0 : 65535, Lb + (size_t)(q0 - b0) * (size_t)msz, msz, c->d_err,
                                (c->blk_tile && rbl_tile_cholesky_fits(m)) ? 128 : 0);    // (the tile factorisation never reads above its diagonal tiles)
   const bool want_inv = c->blk_explicit && rbl_block_inverse_large_fits(m) && (c->blk_large == 1 || (c->blk_large == 2 && comm_on(c)));

@@ -3,7 +3,8 @@
 // reduced to body forces / torques with K^T.  The reference has no force model; what it would have needed is a host loop.
 //
 // Two kernels:
-//   k_body_neighbours    one wave per body i: the bodies j != i with |X_i - X_j| <= 2 R_body + r_cut, written in increasing j
+//   k_body_neighbours    one wave per body i: the bodies j != i of i's window (an ensemble's replica; one system: all bodies)
+//                        with |X_i - X_j| <= 2 R_body + r_cut, written in increasing j
 //                        by a ballot and a prefix count (no atomics: the lists are the same on every call and every rank).
 //                        Exact cull: a blob lies within R_body of its body's centre, so two blobs of bodies further apart
 //                        than 2 R_body + r_cut are further apart than r_cut.
@@ -30,16 +31,19 @@ struct IaParams {
   int wall;
 };
 
-__global__ __launch_bounds__(64) void k_body_neighbours(const double *__restrict__ X, int N_bod, double cut2, int cull, int cap,
-                                                        int *__restrict__ cnt, int *__restrict__ list, unsigned *__restrict__ err)
+// win: bodies per window -- body i only sees the bodies [i - i % win, i - i % win + win) (the replicas of an ensemble do not
+// interact); win = N_bod: every body
+__global__ __launch_bounds__(64) void k_body_neighbours(const double *__restrict__ X, int N_bod, int win, double cut2, int cull,
+                                                        int cap, int *__restrict__ cnt, int *__restrict__ list, unsigned *__restrict__ err)
 {
   const int i = blockIdx.x, t = threadIdx.x;
   const double xi = X[3 * (size_t)i], yi = X[3 * (size_t)i + 1], zi = X[3 * (size_t)i + 2];
+  const int jb = i - i % win, je = min(jb + win, N_bod);
   int base = 0;
-  for (int j0 = 0; j0 < N_bod; j0 += 64) {
+  for (int j0 = jb; j0 < je; j0 += 64) {
     const int j = j0 + t;
     bool take = false;
-    if (j < N_bod && j != i) {
+    if (j < je && j != i) {
       if (!cull) take = true;
       else {
         const double dx = X[3 * (size_t)j] - xi, dy = X[3 * (size_t)j + 1] - yi, dz = X[3 * (size_t)j + 2] - zi;
@@ -155,16 +159,17 @@ int ia_reserve(rbl_ctx *c, IaLayout &L)
 
 }  // namespace
 
-int ia_eval(rbl_ctx *c, double *d_f, double *d_FT, double *d_e)
+// the model over n_win windows of win bodies each (resident X of the body centres, blob positions and lever arms): neighbour
+// lists inside each window, the pair kernel, K^T f.  d_f (3 N) is required here; d_FT (6 N_bod total) and d_e may be NULL.
+static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_pos, const double *d_lever, int win, int n_win, double *d_cl,
+                     double *d_f, double *d_FT, double *d_e, unsigned *d_err)
 {
-  int rc = sync_bodies(c); if (rc) return rc;            // resident positions and lever arms of the current configuration
   const RblBodyState &S = c->S;
   if (!(c->ia_r_cut >= 2.0 * S.a))
     return rbl_fail(c, RBL_ERR_STATE, "interactions: r_cut is below 2a of the current parameters (call rbl_set_interactions again)");
-  IaLayout L;
-  if ((rc = ia_reserve(c, L))) return rc;
   RblPhase ph(c, RBL_T_FORCES);
-  const int cap = ia_cap(S.N_bod);
+  const int nbod = win * n_win, cap = ia_cap(win);
+  IaLayout L = ia_layout(d_cl, nbod, S.N_blb, cap);
   double R2 = 0.0;                                       // R_body: largest blob distance from the centre, body frame (mean removed)
   for (int k = 0; k < S.N_blb; ++k) {
     const double *q = &S.ref_cfg[3 * (size_t)k];
@@ -173,18 +178,41 @@ int ia_eval(rbl_ctx *c, double *d_f, double *d_FT, double *d_e)
   // a hair of slack for the rounding of the rotated lever arms and of the distances: it can only add candidates, whose
   // pairs beyond r_cut are then skipped one by one
   const double cut = (2.0 * std::sqrt(R2) + c->ia_r_cut) * (1.0 + 1e-12) + 1e-12;
-  hipLaunchKernelGGL(k_body_neighbours, dim3(S.N_bod), dim3(64), 0, c->stream, (const double *)c->d_XQ.p, S.N_bod, cut * cut,
-                     c->ia_cull ? 1 : 0, cap, L.cnt, L.list, c->d_err);
+  hipLaunchKernelGGL(k_body_neighbours, dim3(nbod), dim3(64), 0, c->stream, d_X, nbod, win, cut * cut, c->ia_cull ? 1 : 0, cap,
+                     L.cnt, L.list, d_err);
   IaParams P;
   P.w = c->ia_w; P.a = S.a; P.eps_w = c->ia_eps_wall; P.inv_bw = 1.0 / c->ia_b_wall; P.eps_b = c->ia_eps_blob;
   P.inv_bb = 1.0 / c->ia_b_blob; P.two_a = 2.0 * S.a; P.rc2 = c->ia_r_cut * c->ia_r_cut; P.wall = S.wall ? 1 : 0;
   const int bt = S.N_blb > 128 ? IA_BT : (S.N_blb + 63) / 64 * 64, tiles = (S.N_blb + bt - 1) / bt;
-  double *f = d_f ? d_f : L.f;
-  hipLaunchKernelGGL(k_blob_interactions, dim3((unsigned)(tiles * S.N_bod)), dim3(bt), 0, c->stream, (const double *)c->d_pos.p,
-                     (const int *)L.cnt, (const int *)L.list, cap, S.N_blb, tiles, P, f, d_e, L.np);
-  if (d_FT) rbl_launch_KT_x_Lam(c->stream, (const double *)c->d_lever.p, f, S.N_blb, S.N_bod, d_FT);
-  c->ia_nb = S.N_bod; c->ia_nblb = S.N_blb; c->ia_cap = cap;
+  hipLaunchKernelGGL(k_blob_interactions, dim3((unsigned)(tiles * nbod)), dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt,
+                     (const int *)L.list, cap, S.N_blb, tiles, P, d_f, d_e, L.np);
+  if (d_FT) rbl_launch_KT_x_Lam(c->stream, d_lever, d_f, S.N_blb, nbod, d_FT);
   return RBL_OK;
+}
+
+int ia_eval(rbl_ctx *c, double *d_f, double *d_FT, double *d_e)
+{
+  int rc = sync_bodies(c); if (rc) return rc;            // resident positions and lever arms of the current configuration
+  const RblBodyState &S = c->S;
+  IaLayout L;
+  if ((rc = ia_reserve(c, L))) return rc;
+  if ((rc = ia_launch(c, (const double *)c->d_XQ.p, (const double *)c->d_pos.p, (const double *)c->d_lever.p, S.N_bod, 1,
+                      (double *)c->d_ia.p, d_f ? d_f : L.f, d_FT, d_e, c->d_err))) return rc;
+  c->ia_nb = S.N_bod; c->ia_nblb = S.N_blb; c->ia_cap = ia_cap(S.N_bod);
+  return RBL_OK;
+}
+
+size_t ia_batch_bytes(int N_bod, int N_blb, int reps)
+{
+  return ia_bytes(N_bod * reps, N_blb, ia_cap(N_bod));
+}
+
+int ia_eval_batch(rbl_ctx *c, const double *d_X, const double *d_pos, const double *d_lever, int N_bod, int reps, void *d_work,
+                  double **d_f, double *d_FT, double *d_e, unsigned *d_err)
+{
+  IaLayout L = ia_layout(d_work, N_bod * reps, c->S.N_blb, ia_cap(N_bod));
+  *d_f = L.f;
+  return ia_launch(c, d_X, d_pos, d_lever, N_bod, reps, (double *)d_work, L.f, d_FT, d_e, d_err);
 }
 
 int ia_add_to_step_force(rbl_ctx *c, double *d_force)

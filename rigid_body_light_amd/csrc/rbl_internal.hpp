@@ -206,6 +206,12 @@ struct rbl_ctx {
   bool ia_cull = true;                              // RBL_OPT_INTERACTION_CULL
   RblDevBuf d_ia;                                   // f_blob | energy per blob | neighbour counts | lists | pairs per blob
   int ia_nb = 0, ia_nblb = 0, ia_cap = 0;           // shape of what d_ia holds (0: nothing evaluated yet)
+  // ensemble of independent replicas (rbl_ensemble.hip; include/rbl.h section 5)
+  int ens_R = 0, ens_Nb = 0, ens_Nblb = 0;          // replicas, bodies per replica, blobs per body at rbl_ensemble_set_config (0: none)
+  int ens_cur = 0;                                  // which of the two configuration sets in d_ens is the committed one
+  RblDevBuf d_ens;                                  // [X | Q] x 2 (R 7 N_bod each) | reference configuration
+  RblDevBuf d_ens_w;                                // step workspace
+  std::vector<double> ens_cfg_host;                 // the reference configuration d_ens holds
   // lanczos
   int lanczos_max_iter = 100;
   bool lanczos_out_norm = true;  // preconditioned root: final stopping test in the Euclidean norm of the increment (RBL_OPT_LANCZOS_EUCLID_NORM)
@@ -267,6 +273,9 @@ void rbl_launch_pair_blocks(hipStream_t st, const RblParams &P, bool wall, int m
                             const double *d_ri, const double *d_rj, const int32_t *d_ii,
                             const int32_t *d_jj, int64_t n, double *d_out9, unsigned *d_err);
 void rbl_launch_normal(hipStream_t st, uint64_t seed, uint64_t offset, int64_t n, double *d_out);
+// `batch` draws of n normals in one launch, draw b at d_out + b n from Philox offset b ceil(n / 2): draw b is exactly what
+// rbl_launch_normal(seed, b ceil(n / 2), n) gives
+void rbl_launch_normal_batched(hipStream_t st, uint64_t seed, int64_t n, int batch, double *d_out);
 
 // dense linear algebra (rbl_dense.hip)
 int rbl_launch_cholesky(hipStream_t st, double *d_M, int64_t n, bool zero_upper, unsigned *d_err,
@@ -349,6 +358,12 @@ size_t rbl_gmres_small_work_doubles(int N_blb, int N_bod, int max_iter);
 int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
                            int N_blb, int N_bod, const double *d_rhs, const double *d_x0, double *d_x, int max_iter, double rtol,
                            double fsign, double *d_work, double *d_scal, unsigned *d_err);
+// the same solve for `reps` replicas of one system shape, one workgroup each (rbl_ensemble.hip): X, Q replica-major (3 N_bod,
+// 4 N_bod per replica), rhs / x nsys per replica, d_work reps x rbl_gmres_small_work_doubles, one iteration count, residual and
+// error word per replica; diagonal preconditioner with the force block's sign restored (fsign = +1), cold start
+int rbl_launch_gmres_small_ens(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
+                               int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter, double rtol,
+                               double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err);
 
 // per-body geometric operators on the device (rbl_body_dev.hip)
 void rbl_launch_body_geom(hipStream_t st, const double *dX, const double *dQ, const double *dcfg,
@@ -386,8 +401,11 @@ void rbl_launch_tl_eaddq(hipStream_t st, const double *d_Q, int64_t n3, int N_bl
                          int kind, const double *d_t, int64_t tpitch, const double *d_w, double *d_wo, int64_t wpitch, int nvec);
 void rbl_launch_tl_addq(hipStream_t st, const double *d_Q, int64_t n3, int N_blb, const double *d_s, const double *d_t, int64_t tpitch,
                         const double *d_w, double *d_wo, int64_t wpitch, int nvec);
-void rbl_launch_build_M_batched(hipStream_t st, const RblParams &P, bool wall, const double *d_r,
-                                int64_t n_blobs, int batch, double *d_M, int64_t strideM, unsigned *d_err, int lower_tiles = 0);
+// scale_damp: B M B (the dense root of a whole small system) instead of M (per-body blocks); err_stride: matrix b latches its
+// flags in d_err[b * err_stride] (0: one word for the batch)
+void rbl_launch_build_M_batched(hipStream_t st, const RblParams &P, bool wall, bool scale_damp, const double *d_r,
+                                int64_t n_blobs, int batch, double *d_M, int64_t strideM, unsigned *d_err, int lower_tiles = 0,
+                                int err_stride = 0);
 
 // ---- ONE wave-wide sum of doubles, in ONE order --------------------------------------------------------------------------------
 // The bitwise-equal-everywhere claims of the fused reductions (RblNormFold: every wave of every workgroup must get the SAME |w| from

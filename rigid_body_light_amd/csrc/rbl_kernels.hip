@@ -1346,13 +1346,14 @@ template <bool WALL>
 __global__ __launch_bounds__(256) void k_build_M(const double *__restrict__ r,
                                                  double *__restrict__ M, long N,
                                                  int scale_damp, RblParams P, unsigned *err,
-                                                 long strideR, long strideM, int lower_tiles)
+                                                 long strideR, long strideM, int lower_tiles, int err_stride)
 {
   // lower_tiles > 0 (the per-body matrices a factorisation follows): blocks that lie entirely ABOVE the diagonal tiles of that
   // edge are not written -- a factorisation reads the lower triangle and whole diagonal tiles only: half the bytes
   if (lower_tiles > 0 && 3 * ((long)blockIdx.x * 256 + 256) <= ((3 * (long)blockIdx.y * JB) / lower_tiles) * lower_tiles) return;
   r += (size_t)blockIdx.z * (size_t)strideR;   // batched: one blob set / one matrix per blockIdx.z
   M += (size_t)blockIdx.z * (size_t)strideM;
+  err += (size_t)blockIdx.z * (size_t)err_stride;
   __shared__ double col[3][768];
   const int t = threadIdx.x;
   const long i0 = (long)blockIdx.x * 256;
@@ -1488,7 +1489,8 @@ __global__ void k_normal(uint64_t seed, uint64_t offset, long n, double *__restr
 {
   const long pair = (long)blockIdx.x * blockDim.x + threadIdx.x;  // one pair of outputs
   if (2 * pair >= n) return;
-  const uint64_t ctr = offset + (uint64_t)pair;
+  out += (size_t)blockIdx.y * (size_t)n;                          // batched: draw blockIdx.y, (n + 1) / 2 counters further
+  const uint64_t ctr = offset + (uint64_t)blockIdx.y * (uint64_t)((n + 1) / 2) + (uint64_t)pair;
   uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x52424C31u /* "RBL1" */, 0u};
   philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
   const uint64_t a = ((uint64_t)c[0] << 32) | c[1];
@@ -2227,26 +2229,27 @@ void rbl_launch_build_M(hipStream_t st, const RblParams &P, bool wall, bool scal
   dim3 grid((unsigned)((n_blobs + 255) / 256), (unsigned)((n_blobs + JB - 1) / JB)), block(256);
   if (wall)
     hipLaunchKernelGGL(k_build_M<true>, grid, block, 0, st, d_r, d_M, (long)n_blobs,
-                       scale_damp ? 1 : 0, P, d_err, 0L, 0L, 0);
+                       scale_damp ? 1 : 0, P, d_err, 0L, 0L, 0, 0);
   else
     hipLaunchKernelGGL(k_build_M<false>, grid, block, 0, st, d_r, d_M, (long)n_blobs,
-                       scale_damp ? 1 : 0, P, d_err, 0L, 0L, 0);
+                       scale_damp ? 1 : 0, P, d_err, 0L, 0L, 0, 0);
 }
 
 // `batch` independent blob sets of n_blobs each (one rigid body each), matrices strideM apart
 // lower_tiles: 0 = the whole matrices; t > 0 = only what a factorisation in tiles of t x t reads (the lower triangle and whole
 // diagonal tiles: blocks entirely above them stay unwritten)
-void rbl_launch_build_M_batched(hipStream_t st, const RblParams &P, bool wall, const double *d_r,
-                                int64_t n_blobs, int batch, double *d_M, int64_t strideM, unsigned *d_err, int lower_tiles)
+void rbl_launch_build_M_batched(hipStream_t st, const RblParams &P, bool wall, bool scale_damp, const double *d_r,
+                                int64_t n_blobs, int batch, double *d_M, int64_t strideM, unsigned *d_err, int lower_tiles,
+                                int err_stride)
 {
   if (n_blobs <= 0 || batch <= 0) return;
   dim3 grid((unsigned)((n_blobs + 255) / 256), (unsigned)((n_blobs + JB - 1) / JB), (unsigned)batch), block(256);
   if (wall)
-    hipLaunchKernelGGL(k_build_M<true>, grid, block, 0, st, d_r, d_M, (long)n_blobs, 0, P, d_err,
-                       (long)(3 * n_blobs), (long)strideM, lower_tiles);
+    hipLaunchKernelGGL(k_build_M<true>, grid, block, 0, st, d_r, d_M, (long)n_blobs, scale_damp ? 1 : 0, P, d_err,
+                       (long)(3 * n_blobs), (long)strideM, lower_tiles, err_stride);
   else
-    hipLaunchKernelGGL(k_build_M<false>, grid, block, 0, st, d_r, d_M, (long)n_blobs, 0, P, d_err,
-                       (long)(3 * n_blobs), (long)strideM, lower_tiles);
+    hipLaunchKernelGGL(k_build_M<false>, grid, block, 0, st, d_r, d_M, (long)n_blobs, scale_damp ? 1 : 0, P, d_err,
+                       (long)(3 * n_blobs), (long)strideM, lower_tiles, err_stride);
 }
 
 void rbl_launch_pair_blocks(hipStream_t st, const RblParams &P, bool wall, int mode,
@@ -2264,6 +2267,14 @@ void rbl_launch_normal(hipStream_t st, uint64_t seed, uint64_t offset, int64_t n
   const long pairs = (n + 1) / 2;
   hipLaunchKernelGGL(k_normal, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, seed,
                      offset, (long)n, d_out);
+}
+
+void rbl_launch_normal_batched(hipStream_t st, uint64_t seed, int64_t n, int batch, double *d_out)
+{
+  if (n <= 0 || batch <= 0) return;
+  const long pairs = (n + 1) / 2;
+  hipLaunchKernelGGL(k_normal, dim3((unsigned)((pairs + 255) / 256), (unsigned)batch), dim3(256), 0, st, seed, (uint64_t)0,
+                     (long)n, d_out);
 }
 
 // d_out2 must have room for 2 + 2*DOT_BLOCKS doubles: [0..1] result, rest scratch

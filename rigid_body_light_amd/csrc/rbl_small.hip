@@ -17,11 +17,11 @@
 // memory: thread 0's Givens recurrence then was a chain of dependent L2 round trips, ~10 us per iteration.
 // Every sum has a fixed order: results are bitwise reproducible, like the rest of the library.
 // Limits: N <= 256 blobs, N_bod <= 64, diagonal preconditioner, max_iter <= 255 (checked by the launcher).
-#include "rbl_internal.hpp"
+#include "rbl_small_dev.hpp"
 
 namespace {
 
-constexpr int SGT = 1024;          // threads of the one workgroup
+constexpr int SGT = RBL_SG_THREADS;  // threads of the one workgroup
 constexpr int SG_MAXN = 256;       // blobs
 constexpr int SG_MAXB = 64;        // bodies
 constexpr int SG_MAXIT = 255;
@@ -37,22 +37,12 @@ struct SmallArgs {
   int *iters_out;                  // device scalars
   double *resid_out;
   unsigned *err;
+  size_t work_stride;              // replica r (blockIdx.x) of an ensemble: its X, Q, rhs, x0, x, workspace, iters_out, resid_out
+  int err_stride;                  // and error word lie r strides further (one replica: a grid of one, nothing moves)
   RblParams P;
   int N_blb, N_bod, max_iter;
   double rtol, fsign;
 };
-
-__device__ __forceinline__ void quat_rot9(const double *q, double *R)
-{
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w;
-  const double txx = tx * x, txy = ty * x, txz = tz * x;
-  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
 
 // sum over the wavefront, result in every lane, fixed order.  Inside the 16-lane rows by DPP moves (quad_perm, half-row
 // and row mirrors: a few cycles each; the __shfl_xor butterfly is six dependent ds_bpermute round trips, ~800 cycles, and
@@ -85,6 +75,14 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
   constexpr int NW = SGT / 64;
   const int nbl = A.N_blb, nb = A.N_bod, N = nbl * nb, n3 = 3 * N, nb6 = 6 * nb, nsys = n3 + nb6;
   const int m = A.max_iter;
+  {
+    const int rep = blockIdx.x;
+    A.X += (size_t)rep * 3 * nb; A.Q += (size_t)rep * 4 * nb;
+    A.rhs += (size_t)rep * nsys; A.x += (size_t)rep * nsys;
+    if (A.x0) A.x0 += (size_t)rep * nsys;
+    A.V += (size_t)rep * A.work_stride; A.H += (size_t)rep * A.work_stride;
+    A.iters_out += rep; A.resid_out += rep; A.err += (size_t)rep * A.err_stride;
+  }
   double *pos = sm;                             // 3N  positions / a
   double *lev = pos + n3;                       // 3N  lever arms
   double *iM = lev + n3;                        // 2N  diag_invM: (xx = yy, zz)
@@ -108,14 +106,14 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
   double *Rm = r_lds ? Rl : A.H;
   double *Vb = VLDS ? Rl + (r_lds ? (size_t)m * (m + 1) / 2 : 0) : A.V;   // Krylov basis
   const RblParams P = A.P;
-  const RblParams Pu = {1.0, 1.0, P.nf, 4.0, 1e-24, -0.375, 0.125, 0};
+  const RblParams Pu = rbl_small_unit_params(P);
   unsigned flags = 0;
 
   // ---- geometry + diagonal preconditioner ---------------------------------------------------------------
   if (t < N) {
     const int b = t / nbl, k = t - b * nbl;
     double R[9];
-    quat_rot9(A.Q + 4 * b, R);
+    rbl_quat_rot9(A.Q + 4 * b, R);
     const double c0 = A.cfg[3 * k], c1 = A.cfg[3 * k + 1], c2 = A.cfg[3 * k + 2];
     double l0, l1, l2, p2;
     {
@@ -231,13 +229,9 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
     __syncthreads();
   };
 
-  // out = [M lambda - K U ; K^T lambda]   (src/Rigid.py:73-80; M = B Mob B with the wall term, :641-659)
-  // Every unordered pair once (M_ji = M_ij^T, rbl_pair_sym): step (s, rb) pairs the rows i = 64 rb + lane with the columns
-  // j = i + s (mod N), s = 1 .. N/2 (for even N the offset N/2 only from the lower half), so the 64 lanes of a wavefront
-  // touch 64 different rows and 64 different columns per step; the steps are dealt round-robin to the 16 wavefronts, each
-  // adding into its OWN accumulator set (fixed order inside a wave), and the sets are added in wave order afterwards.
+  // out = [M lambda - K U ; K^T lambda]   (src/Rigid.py:73-80; M = B Mob B with the wall term, :641-659): self blocks here,
+  // every unordered pair once by rbl_small_pair_sweep, the waves' accumulator sets added in wave order afterwards
   auto apply_A = [&](const double *in, double *out) {
-    for (int idx = t; idx < NW * n3; idx += SGT) part[idx] = 0.0;
     if (t < N) {                             // self blocks (:40-46, :98-104) and the per-blob terms of K^T lambda
       const double di = WALL ? dmp[t] : 1.0;
       double ux = 0.0, uy = 0.0, uz = 0.0;
@@ -249,30 +243,7 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
       kt[t] = v0; kt[N + t] = v1; kt[2 * N + t] = v2;
       kt[3 * N + t] = l1 * v2 - l2 * v1; kt[4 * N + t] = l2 * v0 - l0 * v2; kt[5 * N + t] = l0 * v1 - l1 * v0;
     }
-    __syncthreads();
-    {
-      const int RB = (N + 63) / 64, nsteps = (N / 2) * RB;
-      double *acc = part + (size_t)wave * n3;
-      for (int q = wave; q < nsteps; q += NW) {
-        const int s_ = q / RB + 1, i = (q - (s_ - 1) * RB) * 64 + lane;
-        if (i < N && (2 * s_ != N || 2 * i < N)) {
-          int j = i + s_;
-          if (j >= N) j -= N;
-          const double di = WALL ? dmp[i] : 1.0, dj = WALL ? dmp[j] : 1.0;
-          double uix = 0.0, uiy = 0.0, uiz = 0.0, ujx = 0.0, ujy = 0.0, ujz = 0.0;
-          rbl_pair_sym<WALL, true, true>(Pu, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], di * in[3 * i], di * in[3 * i + 1],
-                                         di * in[3 * i + 2], pos[3 * j], pos[3 * j + 1], pos[3 * j + 2], dj * in[3 * j],
-                                         dj * in[3 * j + 1], dj * in[3 * j + 2], uix, uiy, uiz, ujx, ujy, ujz, flags);
-          __hip_atomic_fetch_add(&acc[3 * i], uix, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&acc[3 * i + 1], uiy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&acc[3 * i + 2], uiz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&acc[3 * j], ujx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&acc[3 * j + 1], ujy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&acc[3 * j + 2], ujz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      }
-    }
-    __syncthreads();
+    rbl_small_pair_sweep<WALL>(Pu, pos, dmp, in, N, part, flags);   // one accumulator set per wave in part (rbl_small_dev.hpp)
     if (t < n3) {                            // U_i = nf d_i (self + sum over the waves' sets) - (K U)_i
       double s = su[t];
       for (int w = 0; w < NW; ++w) s += part[(size_t)w * n3 + t];
@@ -474,10 +445,11 @@ size_t rbl_gmres_small_work_doubles(int N_blb, int N_bod, int max_iter)
   return (size_t)(max_iter + 1) * nsys + (size_t)max_iter * (max_iter + 1) / 2 + 8;
 }
 
-// d_work: rbl_gmres_small_work_doubles(...) doubles; d_scal: 2 doubles (iterations as an int in the first, residual in the second)
-int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
-                           int N_blb, int N_bod, const double *d_rhs, const double *d_x0, double *d_x, int max_iter, double rtol,
-                           double fsign, double *d_work, double *d_scal, unsigned *d_err)
+// one workgroup per replica: reps systems of the same shape, replica r's X, Q, rhs, x0, x, workspace, iterations, residual and
+// error word lie r strides further (rbl_launch_gmres_small is the grid of one)
+static int launch_small(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
+                        int N_blb, int N_bod, const double *d_rhs, const double *d_x0, double *d_x, int max_iter, double rtol,
+                        double fsign, double *d_work, int *d_iters, double *d_resid, unsigned *d_err, int reps, int err_stride)
 {
   if (!rbl_gmres_small_fits(N_blb, N_bod, max_iter, false)) return RBL_ERR_SIZE;
   const size_t nsys = (size_t)3 * N_blb * N_bod + (size_t)6 * N_bod;
@@ -486,7 +458,8 @@ int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const 
   SmallArgs A;
   A.X = dX; A.Q = dQ; A.cfg = dcfg; A.rhs = d_rhs; A.x0 = d_x0; A.x = d_x;
   A.V = d_work; A.H = d_work + (size_t)(max_iter + 1) * nsys;
-  A.iters_out = (int *)d_scal; A.resid_out = d_scal + 1; A.err = d_err;
+  A.iters_out = d_iters; A.resid_out = d_resid; A.err = d_err;
+  A.work_stride = rbl_gmres_small_work_doubles(N_blb, N_bod, max_iter); A.err_stride = err_stride;
   A.P = P; A.N_blb = N_blb; A.N_bod = N_bod; A.max_iter = max_iter; A.rtol = rtol; A.fsign = fsign;
   // more than 64 KB of dynamic LDS needs the attribute (gfx950: 160 KB per CU).  If the runtime refuses the basis goes to
   // global memory; if even the vectors do not fit the caller falls back to the general solver (RBL_ERR_SIZE).
@@ -503,12 +476,30 @@ int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const 
     vlds = false;
     if (!allow(false, lds)) return RBL_ERR_SIZE;
   }
+  const dim3 grid((unsigned)reps);
   if (vlds) {
-    if (wall) hipLaunchKernelGGL((k_gmres_small<true, true>), dim3(1), dim3(SGT), lds, st, A);
-    else hipLaunchKernelGGL((k_gmres_small<false, true>), dim3(1), dim3(SGT), lds, st, A);
+    if (wall) hipLaunchKernelGGL((k_gmres_small<true, true>), grid, dim3(SGT), lds, st, A);
+    else hipLaunchKernelGGL((k_gmres_small<false, true>), grid, dim3(SGT), lds, st, A);
   } else {
-    if (wall) hipLaunchKernelGGL((k_gmres_small<true, false>), dim3(1), dim3(SGT), lds, st, A);
-    else hipLaunchKernelGGL((k_gmres_small<false, false>), dim3(1), dim3(SGT), lds, st, A);
+    if (wall) hipLaunchKernelGGL((k_gmres_small<true, false>), grid, dim3(SGT), lds, st, A);
+    else hipLaunchKernelGGL((k_gmres_small<false, false>), grid, dim3(SGT), lds, st, A);
   }
   return RBL_OK;
+}
+
+// d_work: rbl_gmres_small_work_doubles(...) doubles; d_scal: 2 doubles (iterations as an int in the first, residual in the second)
+int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
+                           int N_blb, int N_bod, const double *d_rhs, const double *d_x0, double *d_x, int max_iter, double rtol,
+                           double fsign, double *d_work, double *d_scal, unsigned *d_err)
+{
+  return launch_small(st, P, wall, dX, dQ, dcfg, N_blb, N_bod, d_rhs, d_x0, d_x, max_iter, rtol, fsign, d_work, (int *)d_scal,
+                      d_scal + 1, d_err, 1, 0);
+}
+
+int rbl_launch_gmres_small_ens(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
+                               int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter, double rtol,
+                               double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err)
+{
+  return launch_small(st, P, wall, dX, dQ, dcfg, N_blb, N_bod, d_rhs, nullptr, d_x, max_iter, rtol, 1.0, d_work, d_iters, d_resid,
+                      d_rep_err, reps, 1);
 }

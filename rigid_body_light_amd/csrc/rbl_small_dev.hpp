@@ -1,0 +1,63 @@
+// rbl_small_dev.hpp -- device pieces shared by the one-workgroup kernels of small systems: the one-kernel GMRES solve
+// (rbl_small.hip) and the ensemble's random-finite-difference product (rbl_ensemble.hip).  Both evaluate B M B v of at most
+// 256 blobs held in LDS with one workgroup of RBL_SG_THREADS threads.
+#pragma once
+#include "rbl_internal.hpp"
+
+constexpr int RBL_SG_THREADS = 1024;
+
+// the pair kernels' constants for positions given in units of a (rbl_pair_accum / rbl_pair_sym, scaled by nf afterwards)
+__device__ __forceinline__ RblParams rbl_small_unit_params(const RblParams &P)
+{
+  return {1.0, 1.0, P.nf, 4.0, 1e-24, -0.375, 0.125, 0};
+}
+
+// unit quaternion (scalar-first) -> row-major rotation, the expansion of k_blob_positions / rbl_quat_to_rot
+__device__ __forceinline__ void rbl_quat_rot9(const double *q, double *R)
+{
+  const double w = q[0], x = q[1], y = q[2], z = q[3];
+  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w;
+  const double txx = tx * x, txy = ty * x, txz = tz * x;
+  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
+  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
+}
+
+// The off-diagonal part of the product with the damped vector d v: every unordered pair once (M_ji = M_ij^T, rbl_pair_sym).
+// Step (s, rb) pairs the rows i = 64 rb + lane with the columns j = i + s (mod N), s = 1 .. N/2 (for even N the offset N/2
+// only from the lower half), so the 64 lanes of a wavefront touch 64 different rows and 64 different columns per step; the
+// steps are dealt round-robin to the wavefronts, each adding into its OWN accumulator set part[wave][3N] (fixed order inside
+// a wave).  The caller adds the sets in wave order.  pos: positions / a (3N), dmp: wall damping per blob (WALL only), in: 3N.
+// Every thread of the workgroup calls it (it contains barriers); part holds NW x 3N doubles and is zeroed here.
+template <bool WALL>
+__device__ __forceinline__ void rbl_small_pair_sweep(const RblParams &Pu, const double *pos, const double *dmp, const double *in,
+                                                     int N, double *part, unsigned &flags)
+{
+  constexpr int NW = RBL_SG_THREADS / 64;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, n3 = 3 * N;
+  for (int idx = t; idx < NW * n3; idx += RBL_SG_THREADS) part[idx] = 0.0;
+  __syncthreads();
+  const int RB = (N + 63) / 64, nsteps = (N / 2) * RB;
+  double *acc = part + (size_t)wave * n3;
+  for (int q = wave; q < nsteps; q += NW) {
+    const int s_ = q / RB + 1, i = (q - (s_ - 1) * RB) * 64 + lane;
+    if (i < N && (2 * s_ != N || 2 * i < N)) {
+      int j = i + s_;
+      if (j >= N) j -= N;
+      const double di = WALL ? dmp[i] : 1.0, dj = WALL ? dmp[j] : 1.0;
+      double uix = 0.0, uiy = 0.0, uiz = 0.0, ujx = 0.0, ujy = 0.0, ujz = 0.0;
+      rbl_pair_sym<WALL, true, true>(Pu, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], di * in[3 * i], di * in[3 * i + 1],
+                                     di * in[3 * i + 2], pos[3 * j], pos[3 * j + 1], pos[3 * j + 2], dj * in[3 * j],
+                                     dj * in[3 * j + 1], dj * in[3 * j + 2], uix, uiy, uiz, ujx, ujy, ujz, flags);
+      __hip_atomic_fetch_add(&acc[3 * i], uix, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&acc[3 * i + 1], uiy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&acc[3 * i + 2], uiz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&acc[3 * j], ujx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&acc[3 * j + 1], ujy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&acc[3 * j + 2], ujz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  __syncthreads();
+}
