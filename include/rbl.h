@@ -431,7 +431,7 @@ enum {
                                       kernel, 2 symmetric kernel, 3 MFMA multi-RHS kernel also for few vectors                        */
   RBL_OPT_ORDERED_JSPLIT = 2,      /* [0] j-split of the ordered kernel (0 = heuristic)                                               */
   RBL_OPT_SYM_CHUNK = 3,           /* [0] column tiles per work unit of the symmetric kernels (0 = heuristic)                         */
-  RBL_OPT_SYM_ROWS_PER_LANE = 4,   /* [0] rows per lane of the one-vector symmetric kernel: 0 heuristic, 1, 2 (experiments)            */
+  RBL_OPT_SYM_ROWS_PER_LANE = 4,   /* [0] rows per lane of the one-vector symmetric kernel: 0 heuristic, 1, 2, 4 (experiments)         */
   RBL_OPT_SYM2_ROWS_PER_LANE = 5,  /* [0] the same for the two-vector kernel                                                          */
   RBL_OPT_SYM_WAVES = 6,           /* [0] waves per workgroup of the symmetric kernels: 0 heuristic, 1 or 4 (4 needs two rows per lane; any other
                                       value, or a combination no kernel has, is RBL_ERR_ARG -- at the call or at the product)            */

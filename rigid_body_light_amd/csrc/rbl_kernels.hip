@@ -294,6 +294,10 @@ typedef double double2_t __attribute__((ext_vector_type(2)));
 #define RBL_SYM_WAVES 4
 #endif
 constexpr int SW_LARGE = RBL_SYM_WAVES;
+#ifndef RBL_SYM_NI4_TILES
+#define RBL_SYM_NI4_TILES 1000    // one vector, one GPU: four rows per lane from this many 64-blob tiles on (sym_geometry; measured
+                                  // with tools/bench_rows_per_lane.py, wall: 4 / 2 rows = 1.010 at 642 tiles, 0.982 at 1 004, 0.977 at 2 007)
+#endif
 
 struct SymLayout {
   long Npad;
@@ -356,8 +360,11 @@ __device__ __forceinline__ double sym_first_lane(double v)      // lane 0's valu
 // unasked: no spill, 2 % faster at cfg 3 on one box, A/B gpurun_out/r03k/ab_wpe3.txt; HIP's second launch bound is the
 // minimum number of waves per SIMD.  The other instances are left alone: the relaxed one would spill, the small ones
 // already fit four.)
+// NI = 4 (large single-GPU systems, one vector): the three column reads, the three ds_add_f64 column sums and the loop and
+// address arithmetic of a step are shared by four pair evaluations instead of two, and a lane carries four independent pair
+// chains.  Held to two waves per SIMD (<= 256 VGPRs).
 template <bool WALL, int NI, int SW, int PREC>
-__global__ __launch_bounds__(TS *SW, (WALL && NI == 2 && SW > 1 && PREC == 0) ? 3 : 1) void k_apply_M_sym(const double *__restrict__ r,
+__global__ __launch_bounds__(TS *SW, (WALL && NI == 2 && SW > 1 && PREC == 0) ? 3 : (NI == 4 ? 2 : 1)) void k_apply_M_sym(const double *__restrict__ r,
                                                         const double *__restrict__ F,
                                                         double *__restrict__ slabI,
                                                         double *__restrict__ slabJ, long N, SymLayout L, RblParams P,
@@ -469,9 +476,10 @@ __global__ __launch_bounds__(TS *SW, (WALL && NI == 2 && SW > 1 && PREC == 0) ? 
       uix[0] += (double)ax.x; uiy[0] += (double)ay.x; uiz[0] += (double)az.x;
       uix[NI - 1] += (double)ax.y; uiy[NI - 1] += (double)ay.y; uiz[NI - 1] += (double)az.y;
     } else if (J >= It0 + NI) {  // every owned row tile lies strictly before J: fused symmetric sweep
+      constexpr int kSteps = NI > 2 ? 1 : RBL_SYM_UNROLL;   // steps per trip (four rows: one, or the 239 VGPRs become 256 + spills)
       auto sweep = [&](auto nearchk) {
         unsigned off16 = (unsigned)lane * 16u;       // byte offset of column jj in the 16-B arrays, carried (jj*8 = off16/2)
-#pragma unroll RBL_SYM_UNROLL
+#pragma unroll kSteps
         for (int s = 0; s < TS; ++s) {
           const double2_t pa = *(const double2_t *)((const char *)sP0 + off16), pb = *(const double2_t *)((const char *)sP1 + off16),
                           pd = *(const double2_t *)((const char *)sP2 + off16);
@@ -1945,6 +1953,9 @@ static SymLayout sym_geometry(int64_t n_blobs, int n_cu, int i_first, int i_step
   // rotating column sums between two pairs (43.5 instead of 49 instructions per pair in free space): 8 100 blobs 71 against 74-77 us,
   // cfg 2's Brownian step -2 to -3 % (tools/bench_cfg2_step.py, interleaved); at 4 860 blobs it is the slower one (38 against 34 us)
   if (nrhs == 1 && i_step == 1 && t >= 120) ni = 2;
+  // one vector on one GPU, large: four rows per lane (four-wave workgroups only) -- half the column reads, column-sum atomics and
+  // loop arithmetic per pair of two (no single-precision form: a relaxed product keeps two)
+  if (nrhs == 1 && i_step == 1 && t >= RBL_SYM_NI4_TILES && !tune.relaxed) ni = 4;
   // two vectors: one row per lane a little longer (8 346 wall blobs 175 against 186 us, 8 100 free 110 against 124; 12 960: 259 / 253)
   if (nrhs == 2 && t < 176 * i_step && !tune.relaxed) ni = 1;   // (the relaxed sweep carries the two rows of a lane: it keeps NI = 2)
   if (nrhs == 2 && tune.ni2 > 0) ni = tune.ni2;
@@ -1955,8 +1966,8 @@ static SymLayout sym_geometry(int64_t n_blobs, int n_cu, int i_first, int i_step
   // single-wave workgroups fill the chip a little better (tools/bench_midrange.py, wall, one box, forced shapes back to back:
   // 8 346 / 12 198 / 16 050 blobs 0.142 / 0.244 / 0.384 ms with four waves against 0.132 / 0.232 / 0.371 with one; 23 754: 0.778 /
   // 0.783; 32 742: 1.41 / 1.49; the two-vector product is indifferent below 24 000 blobs and 9 % better with four waves above)
-  int sw = (ni == 2 && tsup >= SW_LARGE * i_step * (i_step > 1 ? 8 : 40)) ? SW_LARGE : 1;
-  if (tune.sw == 1 || (tune.sw == SW_LARGE && ni == 2)) sw = tune.sw;   // (the only workgroup shapes the product build instantiates: 1, or 4 with two rows per lane)
+  int sw = (ni == 4 || (ni == 2 && tsup >= SW_LARGE * i_step * (i_step > 1 ? 8 : 40))) ? SW_LARGE : 1;
+  if (tune.sw == 1 || (tune.sw == SW_LARGE && ni >= 2)) sw = tune.sw;   // (the only workgroup shapes the product build instantiates: 1, or 4 with two or four rows per lane)
   const int tunits = (tsup + sw - 1) / sw;
   const int rowsI = ((tunits + i_step - 1) / i_step) * sw;
   // a unit sweeps <= C column tiles.  Measured (tools/tune_sym_chunk.py): short chunks win -- many
@@ -2012,7 +2023,7 @@ static void launch_sym(hipStream_t st, const RblParams &P, const double *d_F, co
   dim3 g2((unsigned)((n + 63) / 64), (unsigned)nrhs), b2(64 * RG);
   unsigned char *farmap = nullptr;
   unsigned *queue = nullptr;
-  if (NI == 2) {   // large systems only: two more tiny launches, then most tile pairs skip the overlap test
+  if (NI >= 2) {   // large systems only: two more tiny launches, then most tile pairs skip the overlap test
     double *bbox = slabJ + sym_slabJ_blobs(L) * 3 * nrhs;
     farmap = (unsigned char *)(bbox + (size_t)T * 6);
     const int nsup = (T + NI - 1) / NI;
@@ -2028,13 +2039,16 @@ static void launch_sym(hipStream_t st, const RblParams &P, const double *d_F, co
                        (const double *)bbox, T, NI, farmap, queue, gap_ratio);
   }
   constexpr int PR = (NI == 2) ? 1 : 0;      // the relaxed form exists for two rows per lane
-  if (nrhs == 2 && relaxed && NI == 2)
-    hipLaunchKernelGGL((k_apply_M_sym2<WALL, NI, SW, PR>), grid, block, 0, st, d_r, d_F, slabI, slabJ, (long)n_blobs, L, P,
-                       d_err, (const unsigned char *)farmap, queue);
-  else if (nrhs == 2)
-    hipLaunchKernelGGL((k_apply_M_sym2<WALL, NI, SW, 0>), grid, block, 0, st, d_r, d_F, slabI, slabJ, (long)n_blobs, L, P,
-                       d_err, (const unsigned char *)farmap, queue);
-  else if (relaxed && NI == 2)
+  if (nrhs == 2) {
+    if constexpr (NI <= 2) {                 // (four rows per lane: one vector only -- kSymRows never routes two here)
+      if (relaxed && NI == 2)
+        hipLaunchKernelGGL((k_apply_M_sym2<WALL, NI, SW, PR>), grid, block, 0, st, d_r, d_F, slabI, slabJ, (long)n_blobs, L, P,
+                           d_err, (const unsigned char *)farmap, queue);
+      else
+        hipLaunchKernelGGL((k_apply_M_sym2<WALL, NI, SW, 0>), grid, block, 0, st, d_r, d_F, slabI, slabJ, (long)n_blobs, L, P,
+                           d_err, (const unsigned char *)farmap, queue);
+    }
+  } else if (relaxed && NI == 2)
     hipLaunchKernelGGL((k_apply_M_sym<WALL, NI, SW, PR>), grid, block, 0, st, d_r, d_F, slabI, slabJ, (long)n_blobs, L, P,
                        d_err, (const unsigned char *)farmap, queue);
   else
@@ -2097,6 +2111,7 @@ const SymRow kSymRows[] = {
     {"k_apply_M_symw2v<%s,1>", 1, 1, 2, true, false, row_launch_symw<1, 2>},
     {"k_apply_M_symw<%s,2>", 2, 1, 1, true, false, row_launch_symw<2, 1>},
     {"k_apply_M_symw<%s>", 1, 1, 1, true, false, row_launch_symw<1, 1>},
+    {"k_apply_M_sym<%s,4,4>", 4, SW_LARGE, 1, false, false, row_launch_sym<4, SW_LARGE>},
     {"k_apply_M_sym%s<%s,2,4>", 2, SW_LARGE, 0, false, true, row_launch_sym<2, SW_LARGE>},
     {"k_apply_M_sym%s<%s,2,1>", 2, 1, 0, false, true, row_launch_sym<2, 1>},
     {"k_apply_M_sym%s<%s,1,1>", 1, 1, 0, false, false, row_launch_sym<1, 1>},

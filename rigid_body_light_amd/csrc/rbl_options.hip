@@ -27,8 +27,8 @@ const OptRow kOptions[] = {
      [](rbl_ctx *c, int64_t v) { c->tune_jsplit = (int)v; }},
     {RBL_OPT_SYM_CHUNK, "sym_chunk", 0, 4096, 0, [](const rbl_ctx *c) -> int64_t { return c->sym_tune.chunk; },
      [](rbl_ctx *c, int64_t v) { c->sym_tune.chunk = (int)v; }},
-    {RBL_OPT_SYM_ROWS_PER_LANE, "sym_rows_per_lane", 0, 2, 0, [](const rbl_ctx *c) -> int64_t { return c->sym_tune.ni1; },
-     [](rbl_ctx *c, int64_t v) { c->sym_tune.ni1 = (int)v; }},
+    {RBL_OPT_SYM_ROWS_PER_LANE, "sym_rows_per_lane", 0, 4, 0, [](const rbl_ctx *c) -> int64_t { return c->sym_tune.ni1; },
+     [](rbl_ctx *c, int64_t v) { c->sym_tune.ni1 = (int)v; }, [](int64_t v) { return v != 3; }},
     {RBL_OPT_SYM2_ROWS_PER_LANE, "sym2_rows_per_lane", 0, 2, 0, [](const rbl_ctx *c) -> int64_t { return c->sym_tune.ni2; },
      [](rbl_ctx *c, int64_t v) { c->sym_tune.ni2 = (int)v; }},
     {RBL_OPT_SYM_WAVES, "sym_waves", 0, 4, 0, [](const rbl_ctx *c) -> int64_t { return c->sym_tune.sw; },

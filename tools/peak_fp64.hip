@@ -34,6 +34,17 @@ __global__ __launch_bounds__(256) void k_mfma(double *out, int iters)
   out[blockIdx.x * blockDim.x + threadIdx.x] = c0[0] + c1[1] + c2[2] + c3[3];
 }
 
+// v_rsq_f64 alone on eight independent chains (x <- 1/sqrt(x) converges to 1: no denormals, no infinities): its issue cost
+__global__ __launch_bounds__(256) void k_rsq_only(double *out, int iters)
+{
+  double a0 = 1.0 + threadIdx.x * 1e-3, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6, a7 = a0 + 7;
+  for (int i = 0; i < iters; ++i) {
+    a0 = __builtin_amdgcn_rsq(a0); a1 = __builtin_amdgcn_rsq(a1); a2 = __builtin_amdgcn_rsq(a2); a3 = __builtin_amdgcn_rsq(a3);
+    a4 = __builtin_amdgcn_rsq(a4); a5 = __builtin_amdgcn_rsq(a5); a6 = __builtin_amdgcn_rsq(a6); a7 = __builtin_amdgcn_rsq(a7);
+  }
+  out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7;
+}
+
 __global__ __launch_bounds__(256) void k_rsq(double *out, int iters)
 {
   double a0 = 1.0 + threadIdx.x * 1e-3, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3;
@@ -66,11 +77,15 @@ int main()
   double *out; hipMalloc(&out, sizeof(double) * blocks * 256);
   double ms = time_ms([&] { hipLaunchKernelGGL(k_dfma, dim3(blocks), dim3(256), 0, 0, out, iters); });
   printf("v_fma_f64      : %8.2f TFLOP/s\n", 2.0 * 8 * iters * (double)blocks * 256 / (ms * 1e-3) / 1e12);
+  const double ms_per_fma = ms / (8.0 * iters);             // per instruction of every thread: the unit of an issue slot
   ms = time_ms([&] { hipLaunchKernelGGL(k_mfma, dim3(blocks), dim3(256), 0, 0, out, iters / 4); });
   printf("mfma_f64_16x16x4: %7.2f TFLOP/s\n", 2.0 * 16 * 16 * 4 * 4 * (iters / 4) * (double)blocks * 4 / (ms * 1e-3) / 1e12);
+  ms = time_ms([&] { hipLaunchKernelGGL(k_rsq_only, dim3(blocks), dim3(256), 0, 0, out, iters / 4); });
+  printf("v_rsq_f64      : %7.2f Gop/s  (fma-equivalent issue slots per rsq, 8 independent chains: %.2f)\n",
+         8.0 * (iters / 4) * (double)blocks * 256 / (ms * 1e-3) / 1e9, ms / (8.0 * (iters / 4)) / ms_per_fma);
   ms = time_ms([&] { hipLaunchKernelGGL(k_rsq, dim3(blocks), dim3(256), 0, 0, out, iters / 4); });
-  printf("v_rsq_f64 (+add): %7.2f Gop/s  (fma-equivalent issue slots per rsq+add: %.2f)\n",
-         4.0 * (iters / 4) * (double)blocks * 256 / (ms * 1e-3) / 1e9, 0.0);
+  printf("v_rsq_f64 (+add): %7.2f Gop/s  (fma-equivalent issue slots per rsq+add, 4 chains: %.2f)\n",
+         4.0 * (iters / 4) * (double)blocks * 256 / (ms * 1e-3) / 1e9, ms / (4.0 * (iters / 4)) / ms_per_fma);
   const int n = 1 << 20;
   std::vector<double> hx(n), hs(n), hr(n);
   for (int i = 0; i < n; ++i) hx[i] = std::exp(-30.0 + 60.0 * (i + 0.5) / n) * (1.0 + 0.37 * ((i * 2654435761u) % 1000) / 1000.0);
