@@ -496,7 +496,12 @@ enum {
   RBL_OPT_INTERACTION_CULL = 33,   /* [1] test hook: the interaction kernel walks only the bodies within 2 R_body + r_cut of each body;
                                       0: every other body is a neighbour (results are bitwise the same: the cull is exact and the pairs
                                       beyond r_cut are skipped either way)                                                          */
-  RBL_OPT_COUNT = 34
+  RBL_OPT_POISON_WORKSPACE = 34,   /* [0; the environment variable RBL_POISON_WORKSPACE, read by every rbl_create, sets the starting value]
+                                      test hook: every device workspace the library allocates is filled with the 32-bit pattern
+                                      0x7FF87FF8 (NaN as fp64 and as fp32, a large positive int32), and scratch workspaces are
+                                      refilled whenever an entry point reserves them, so a kernel that reads memory nobody wrote
+                                      fails loudly instead of reading zeros.  Costs a fill and a stream synchronise per reserve */
+  RBL_OPT_COUNT = 35
 };
 int rbl_set_option(rbl_ctx *ctx, int option, int64_t value);
 int rbl_get_option(const rbl_ctx *ctx, int option, int64_t *value);

@@ -75,9 +75,94 @@ int rbl_dev_init(rbl_ctx *c)
   return RBL_OK;
 }
 
+// Every device buffer of rbl_ctx, one row each: rbl_destroy frees them all, and RBL_OPT_POISON_WORKSPACE (a test hook) fills
+// them with a pattern that reads as NaN in fp64 and fp32 and as 2 146 992 120 in a 32-bit integer.  A fresh allocation is always
+// filled; a SCRATCH buffer -- contents dead between entry-point calls and at every rbl_dev_reserve of it -- is refilled at every
+// rbl_dev_reserve, so a read of a slot the current call never wrote sees NaN even when the buffer did not grow.  PERSIST buffers
+// (factors, cached tables, resident state, and buffers some nested call reserves again while they are live) are filled once, when
+// allocated.  Each row says why.
+// Integer regions (audit: each is written on the context's stream before any kernel reads it, on every path):
+//   d_part   far map bytes + work-queue counter            k_tile_far, in the same product, before the pair kernel
+//   d_tl*    tile dependency counters                      hipMemsetAsync in rbl_tilechol.hip before the tile kernel
+//   d_ia     neighbour counts / lists, pairs per blob      k_body_neighbours (every count; list entries below min(count, cap),
+//                                                          the only ones read), k_blob_interactions (every blob)
+//   d_ens_w  iters / rerr / gerr read-back block           hipMemsetAsync in ens_begin and the RFD entry point
+//   d_ens_w  ia region                                     as d_ia: ia_eval_batch runs k_body_neighbours first
+enum { RBL_BUF_PERSIST = 0, RBL_BUF_SCRATCH = 1 };
+struct RblBufRow { RblDevBuf rbl_ctx::*buf; int kind; };
+static const RblBufRow kDevBufs[] = {
+    {&rbl_ctx::d_r, RBL_BUF_PERSIST},             // host entry points and the steps stage positions here; not audited for nested reserves
+    {&rbl_ctx::d_F, RBL_BUF_PERSIST},             // host apply_M stages forces; not audited for nested reserves
+    {&rbl_ctx::d_U, RBL_BUF_PERSIST},             // as d_r (the steps keep U here between their phases)
+    {&rbl_ctx::d_part, RBL_BUF_SCRATCH},          // product slabs: reserved right before each product launch, consumed by it
+    {&rbl_ctx::d_W, RBL_BUF_PERSIST},             // as d_r (noise of the Brownian steps)
+    {&rbl_ctx::d_cfg, RBL_BUF_PERSIST},           // reference configuration (dev_cfg_valid)
+    {&rbl_ctx::d_XQ, RBL_BUF_PERSIST},            // resident X | Q (dev_xq_valid)
+    {&rbl_ctx::d_mat, RBL_BUF_PERSIST},           // dense M: built by one entry point, factored in place by the next call of the same path
+    {&rbl_ctx::d_tmp, RBL_BUF_SCRATCH},           // host staging, Lanczos basis, trmv partials: never reserved while live
+    {&rbl_ctx::d_tmp2, RBL_BUF_SCRATCH},          // Lanczos scalars and pair-block debug output, within one call
+    {&rbl_ctx::d_chol, RBL_BUF_PERSIST},          // Cholesky workspace next to d_mat; not audited
+    {&rbl_ctx::d_lever, RBL_BUF_PERSIST},         // resident body geometry
+    {&rbl_ctx::d_pos, RBL_BUF_PERSIST},           // resident blob positions (rbl_positions_dev hands them out)
+    {&rbl_ctx::d_invM2, RBL_BUF_PERSIST},         // diagonal preconditioner, per configuration
+    {&rbl_ctx::d_NL, RBL_BUF_PERSIST},            // per-body N factors of the preconditioner
+    {&rbl_ctx::d_sad, RBL_BUF_SCRATCH},           // saddle product: reserved right before the product that writes it
+    {&rbl_ctx::d_blkL, RBL_BUF_PERSIST},          // per-body factors
+    {&rbl_ctx::d_blkLinv, RBL_BUF_PERSIST},       // inverses of the factors' diagonal blocks
+    {&rbl_ctx::d_pcw, RBL_BUF_PERSIST},           // preconditioner tables built with the factors
+    {&rbl_ctx::d_pcMK, RBL_BUF_PERSIST},          // invM K of the preconditioner
+    {&rbl_ctx::d_blkX, RBL_BUF_PERSIST},          // explicit inverses
+    {&rbl_ctx::d_blkTmp, RBL_BUF_PERSIST},        // apply_A_dev (rbl_roots.hip) hands its product here to blk_solve, which reserves it again
+    {&rbl_ctx::d_commStage, RBL_BUF_SCRATCH},     // all-gather staging: reserved right before the collective
+    {&rbl_ctx::d_blkXf, RBL_BUF_PERSIST},         // single-precision copy of the explicit inverses
+    {&rbl_ctx::d_blkAug, RBL_BUF_SCRATCH},        // tile-factor counters / W tiles, panel-inverse [L ; I]: reserved right before their launch
+    {&rbl_ctx::d_tlQ, RBL_BUF_PERSIST},           // two-level factor: coarse basis
+    {&rbl_ctx::d_tlCb, RBL_BUF_PERSIST},          // two-level factor
+    {&rbl_ctx::d_tlCs, RBL_BUF_PERSIST},          // two-level factor
+    {&rbl_ctx::d_tlA, RBL_BUF_PERSIST},           // two-level factor: coarse operator (kept for RBL_OPT_TWO_LEVEL_REFRESH changes)
+    {&rbl_ctx::d_tlLinv, RBL_BUF_PERSIST},        // two-level factor
+    {&rbl_ctx::d_tlX, RBL_BUF_PERSIST},           // two-level factor: explicit inverse
+    {&rbl_ctx::d_tlT, RBL_BUF_SCRATCH},           // tl_apply's temporaries; reserved only by tl_build, when no tl_apply is under way
+    {&rbl_ctx::d_tlZ, RBL_BUF_SCRATCH},           // tl_build's unit vectors, the block_solve test hook's copy: reserved right before use
+    {&rbl_ctx::d_bfL, RBL_BUF_PERSIST},           // body-frame factor, built once per rbl_set_parameters
+    {&rbl_ctx::d_bfLinv, RBL_BUF_PERSIST},        // body-frame factor
+    {&rbl_ctx::d_bfX, RBL_BUF_PERSIST},           // body-frame explicit inverse
+    {&rbl_ctx::d_bfPC, RBL_BUF_PERSIST},          // body-frame preconditioner tables
+    {&rbl_ctx::d_ktl, RBL_BUF_PERSIST},           // K^T Lambda of the last preconditioner output, read by the next saddle product (ktl_arm)
+    {&rbl_ctx::d_bd, RBL_BUF_SCRATCH},            // RHS_and_Midpoint workspace: reserved at its start
+    {&rbl_ctx::d_bd2, RBL_BUF_SCRATCH},           // host RHS_and_Midpoint staging, GMRES warm-start vectors: within one call, never nested
+    {&rbl_ctx::d_gm, RBL_BUF_SCRATCH},            // GMRES Krylov basis and Hessenberg: reserved at the start of each solve or batch
+    {&rbl_ctx::d_step, RBL_BUF_PERSIST},          // time-step vectors; the previous solution for warm starts
+    {&rbl_ctx::d_hist, RBL_BUF_PERSIST},          // warm-start history ring
+    {&rbl_ctx::d_ia, RBL_BUF_PERSIST},            // force-model lists and forces of the last evaluation (ia_nb, ia_cap)
+    {&rbl_ctx::d_ens, RBL_BUF_PERSIST},           // ensemble configurations
+    {&rbl_ctx::d_ens_w, RBL_BUF_SCRATCH},         // ensemble step workspace: reserved at the start of each ensemble entry point
+};
+
+// the poison pattern, on the context's stream; nothing while the stream is being captured into a graph (a capture may not
+// synchronise, and the buffers it records were filled when the eager warm-up allocated them)
+static int poison_fill(rbl_ctx *c, const RblDevBuf &b)
+{
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  RBL_HIP(c, hipStreamIsCapturing(c->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone) return RBL_OK;
+  const size_t words = b.bytes / 4, tail = b.bytes % 4;
+  if (words) RBL_HIP(c, hipMemsetD32Async((hipDeviceptr_t)b.p, (int)RBL_POISON_WORD, words, c->stream));
+  if (tail) RBL_HIP(c, hipMemsetAsync((char *)b.p + 4 * words, 0xFF, tail, c->stream));
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  return RBL_OK;
+}
+
+static int poison_scratch(rbl_ctx *c, const RblDevBuf &b)
+{
+  for (const RblBufRow &row : kDevBufs)
+    if (&(c->*row.buf) == &b) return row.kind == RBL_BUF_SCRATCH && b.p ? poison_fill(c, b) : RBL_OK;
+  return RBL_OK;
+}
+
 int rbl_dev_reserve(rbl_ctx *c, RblDevBuf &b, size_t bytes)
 {
-  if (bytes <= b.bytes) return RBL_OK;
+  if (bytes <= b.bytes) return c->poison_ws ? poison_scratch(c, b) : RBL_OK;
   if (b.p) {
     RBL_HIP(c, hipStreamSynchronize(c->stream));
     RBL_HIP(c, hipFree(b.p));
@@ -89,7 +174,7 @@ int rbl_dev_reserve(rbl_ctx *c, RblDevBuf &b, size_t bytes)
     return rbl_fail(c, RBL_ERR_ALLOC, std::string("hipMalloc failed: ") + hipGetErrorString(e));
   }
   b.bytes = bytes;
-  return RBL_OK;
+  return c->poison_ws ? poison_fill(c, b) : RBL_OK;
 }
 
 // ---- per-phase timings (include/rbl.h: rbl_set_timing / rbl_get_timings) ----------------------------------------------
@@ -269,7 +354,14 @@ RblParams ctx_params(const rbl_ctx *c)
   return P;
 }
 
-rbl_ctx *rbl_create(void) { return new (std::nothrow) rbl_ctx(); }
+// RBL_POISON_WORKSPACE (read at every call, so a test can set it for one context): starting value of RBL_OPT_POISON_WORKSPACE
+rbl_ctx *rbl_create(void)
+{
+  rbl_ctx *c = new (std::nothrow) rbl_ctx();
+  const char *e = std::getenv("RBL_POISON_WORKSPACE");
+  if (c && e) c->poison_ws = std::strtol(e, nullptr, 10) != 0;
+  return c;
+}
 
 void rbl_destroy(rbl_ctx *c)
 {
@@ -278,11 +370,8 @@ void rbl_destroy(rbl_ctx *c)
     (void)hipStreamSynchronize(c->stream);
     comm_release(c);
     if (c->ev_check) (void)hipEventDestroy(c->ev_check);
-    RblDevBuf *bufs[] = {&c->d_r, &c->d_F, &c->d_U, &c->d_part, &c->d_W, &c->d_cfg,
-                         &c->d_XQ, &c->d_mat, &c->d_tmp, &c->d_tmp2, &c->d_chol,
-                         &c->d_lever, &c->d_pos, &c->d_invM2, &c->d_NL, &c->d_sad, &c->d_blkL, &c->d_blkLinv, &c->d_blkX, &c->d_blkTmp, &c->d_blkXf, &c->d_blkAug, &c->d_commStage, &c->d_tlQ, &c->d_tlCb, &c->d_tlCs, &c->d_tlA, &c->d_tlLinv, &c->d_tlX, &c->d_tlT, &c->d_tlZ, &c->d_ktl, &c->d_bfL, &c->d_bfLinv, &c->d_bfX, &c->d_bfPC, &c->d_pcw, &c->d_pcMK, &c->d_bd, &c->d_bd2, &c->d_gm, &c->d_step, &c->d_hist, &c->d_ia, &c->d_ens, &c->d_ens_w};
-    for (RblDevBuf *b : bufs)
-      if (b->p) (void)hipFree(b->p);
+    for (const RblBufRow &row : kDevBufs)
+      if ((c->*row.buf).p) (void)hipFree((c->*row.buf).p);
     if (c->chol_aux.stream) {
       (void)hipStreamSynchronize(c->chol_aux.stream);
       for (int i = 0; i < 3; ++i)

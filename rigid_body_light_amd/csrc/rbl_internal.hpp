@@ -50,6 +50,8 @@ int rbl_chol6(double *A);  // in-place lower Cholesky of a 6x6 row-major block
 // ----------------------------------------------------------------------------
 // Device buffers + context
 // ----------------------------------------------------------------------------
+constexpr unsigned RBL_POISON_WORD = 0x7FF87FF8u;   // RBL_OPT_POISON_WORKSPACE: NaN as fp64 and fp32, 2 146 992 120 as an int32
+
 struct RblDevBuf {
   void *p = nullptr;
   size_t bytes = 0;
@@ -112,6 +114,7 @@ struct rbl_ctx {
   RblDevBuf d_commStage;                            // padded slots of a ragged in-place all-gather (rbl_comm.hip)
   RblDevBuf d_blkXf, d_blkAug;                      // large bodies: single-precision copy of the inverses; scratch of their inversion
   bool comm_force_staged = false;                   // RBL_OPT_COMM_FORCE_STAGED (test hook)
+  bool poison_ws = false;                           // RBL_OPT_POISON_WORKSPACE (test hook; rbl_core.hip: kDevBufs)
   bool blk_pipe = true;                             // substitution through large bodies' factors: the one-barrier pipeline (k_block_solve_pipe); false: k_block_solve
   bool blk_tile = true;                             // RBL_OPT_BLOCK_TILE_FACTOR: large bodies factored (and inverted) by the dataflow tile kernel
   int blk_large = 2;                                // explicit inverses of bodies with 3 N_blb > 512: 0 never, 1 always, 2 when it pays

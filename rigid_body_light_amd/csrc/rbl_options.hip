@@ -85,6 +85,8 @@ const OptRow kOptions[] = {
      [](rbl_ctx *c, int64_t v) { c->comm_force_staged = v != 0; }},
     {RBL_OPT_INTERACTION_CULL, "interaction_cull", 0, 1, 1, [](const rbl_ctx *c) -> int64_t { return c->ia_cull; },
      [](rbl_ctx *c, int64_t v) { c->ia_cull = v != 0; }},
+    {RBL_OPT_POISON_WORKSPACE, "poison_workspace", 0, 1, 0, [](const rbl_ctx *c) -> int64_t { return c->poison_ws; },
+     [](rbl_ctx *c, int64_t v) { c->poison_ws = v != 0; }},
     {RBL_OPT_FUSED_KRYLOV, "fused_krylov", 0, 1, 1, [](const rbl_ctx *c) -> int64_t { return c->fused_krylov; },
      [](rbl_ctx *c, int64_t v) { c->fused_krylov = v != 0; }},
 };

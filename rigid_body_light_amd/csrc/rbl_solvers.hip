@@ -269,7 +269,9 @@ static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, dou
 // stopping test: exactly the iterates rbl_gmres_saddle_dev would produce one by one), whose k products per iteration are ONE
 // launch of k_apply_M_mrhs (16 right-hand sides per pass through v_mfma_f64_16x16x4: 6.3 ms a vector at cfg 3 against 20.4 for
 // the one-vector kernel) and whose k block-preconditioner applications share passes over the per-body factors.  Columns that
-// have converged stop iterating (their slots ride along in the product, which costs the same for 13 as for 16).
+// have converged stop iterating; their slots ride along in the product (which costs the same for 13 as for 16) as zero vectors:
+// the basis slots such a column never wrote (and the last one, w / |w|, non-finite after an exact breakdown) are cleared once,
+// when it converges, so the preconditioner and the product never read stale or unwritten memory for it.
 static int gmres_multi_batch(rbl_ctx *c, const double *d_rhs, int k, int m, double rtol, double *d_x, int *iters_out, double *resid_out)
 {
   const RblBodyState &S = c->S;
@@ -323,7 +325,7 @@ static int gmres_multi_batch(rbl_ctx *c, const double *d_rhs, int k, int m, doub
   };
   int n_done = 0;
   for (int j = 0; j < m && n_done < k; ++j) {
-    // z_c = P^-1 V_c,j : all columns together (converged ones ride along: their slots are never read again)
+    // z_c = P^-1 V_c,j : all columns together (converged ones ride along on zeroed slots, whose results are never read)
     if ((rc = apply_PC_multi_dev(c, Vc(0, j), Zc(0), Sc(0), k, pitch))) return rc;
     // w_c = [M lambda - K U ; K^T lambda] : ONE multi-vector product, then the O(N) body terms column by column
     if ((rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3 * (size_t)k))) return rc;
@@ -340,7 +342,11 @@ static int gmres_multi_batch(rbl_ctx *c, const double *d_rhs, int k, int m, doub
       for (int col = 0; col < k; ++col) {
         if (done[(size_t)col]) continue;
         resid[(size_t)col] = solve_ls(col, j + 1, ys[(size_t)col]);
-        if (resid[(size_t)col] < rtol) { done[(size_t)col] = 1; ++n_done; }
+        if (resid[(size_t)col] < rtol) {
+          done[(size_t)col] = 1; ++n_done;
+          if (j + 1 < m && n_done < k)                 // V_{j+1} .. V_{m-1}: what the later iterations read for this column
+            RBL_HIP(c, hipMemsetAsync(Vc(col, j + 1), 0, sizeof(double) * (size_t)(m - 1 - j) * (size_t)nsys, c->stream));
+        }
       }
     }
   }

@@ -516,10 +516,17 @@ __global__ __launch_bounds__(256, 2) void k_tile_chol(const TileChol P)
         if (row < n && col < n) Om[(size_t)col * (size_t)ldo + row] = Wb[(size_t)a_ * TC + b_];
       }
     } else if (active && !chol) {
+      // T = -acc, and ZERO in the columns beyond the matrix: with n odd, the lane whose row pair of L starts at n - 1 also loaded
+      // "row n" of the panel (the top of L's next column, above the diagonal and never written when only the lower tiles were
+      // built), and X = T W^T mixes T's columns -- the zero padding of W does not cancel a NaN there (0 x NaN = NaN)
 #pragma unroll
       for (int tj = 0; tj < 4; ++tj)
 #pragma unroll
-        for (int ti = 0; ti < 4; ++ti) acc[tj][ti] = -acc[tj][ti];
+        for (int v = 0; v < 4; ++v) {
+          const bool in = j0 + 16 * tj + l4 + 4 * v < n;
+#pragma unroll
+          for (int ti = 0; ti < 4; ++ti) acc[tj][ti][v] = in ? -acc[tj][ti][v] : 0.0;
+        }
     } else if (active) {
 #pragma unroll
       for (int tp = 0; tp < 4; tp += 2) {

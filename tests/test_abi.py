@@ -51,7 +51,7 @@ def option_keys():
     return {m.group(1): int(m.group(2)) for m in re.finditer(r"\b(RBL_OPT_[A-Z0-9_]+)\s*=\s*(\d+)", text)}
 
 
-def test_every_option_is_named_bounded_and_round_trips():
+def test_every_option_is_named_bounded_and_round_trips(monkeypatch):
     """include/rbl.h's named options (the replacement of the rounds 1-3 switchboard of magic integers): every key 1 .. RBL_OPT_COUNT - 1 has a
     table row (name, range, default), starts at its default, round-trips its extreme values, rejects values outside its range
     and unknown keys with RBL_ERR_ARG leaving the option unchanged; a value inside the range that selects nothing (sym_waves = 2, 3)
@@ -64,6 +64,7 @@ def test_every_option_is_named_bounded_and_round_trips():
     lib.rbl_get_option.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(i64)]
     lib.rbl_option_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p)] + [ctypes.POINTER(i64)] * 3
     lib.rbl_option_key.argtypes = [ctypes.c_char_p]
+    monkeypatch.delenv("RBL_POISON_WORKSPACE", raising=False)      # (it sets poison_workspace's starting value)
     keys = option_keys()
     count = keys.pop("RBL_OPT_COUNT")
     assert sorted(keys.values()) == list(range(1, count)), "RBL_OPT_* keys must be 1 .. RBL_OPT_COUNT - 1 without gaps"

@@ -222,16 +222,19 @@ def test_fused_krylov_iteration_equals_one_kernel_per_operation(nb, nblb, shared
 
 
 @pytest.mark.parametrize("nb,nblb,wall,block", [(10, 12, False, False), (6, 162, True, True), (6, 162, False, True)])
-def test_lock_step_gmres_for_many_right_hand_sides(orc, nb, nblb, wall, block):
+def test_lock_step_gmres_for_many_right_hand_sides(orc, monkeypatch, nb, nblb, wall, block):
     """`solve_saddle_multi` (rbl_gmres_saddle_multi_dev): k right-hand sides of one configuration advance in lock step -- ONE
     multi-vector mobility product per iteration on the fp64 matrix cores, shared passes over the per-body factors -- and every
     column must be the solve `solve_saddle` gives it alone: same iteration count (+-1), same solution to 1e-10, its own residual
     below the tolerance and the TRUE residual through apply_saddle too.  19 columns = two passes (16 + 3) of the product; columns
     of very different scale converge at different iterations.  Then the customer: the body mobility matrix N = (K^T M^-1 K)^-1
     from 6 N_bod unit loads against the oracle's dense M and K (the operator is the reference's
-    src/Rigid.py:69-80)."""
+    src/Rigid.py:69-80).  The context runs with its workspaces poisoned (RBL_POISON_WORKSPACE): columns that converge early
+    stay in the batch, and a slot of theirs that nobody wrote would now read as NaN and fail the batch."""
     from oracle import oracle as O
+    monkeypatch.setenv("RBL_POISON_WORKSPACE", "1")
     c, rb = _body(nb, nblb, wall, block)
+    assert rb.cb.get_option("poison_workspace") == 1
     n3, nsys = 3 * nb * nblb, 3 * nb * nblb + 6 * nb
     rng = np.random.default_rng(21)
     k = 19
@@ -255,6 +258,26 @@ def test_lock_step_gmres_for_many_right_hand_sides(orc, nb, nblb, wall, block):
         assert np.linalg.norm(xf[col] - x1) <= 1e-9 * np.linalg.norm(x1)
     with pytest.raises(RuntimeError):
         rb.solve_saddle_multi(rhs[:, :-1])
+    # converged columns ride along with the rest: 17 columns = a pass of 16 then ONE column on the one-vector product (in the
+    # first batch's Krylov workspace).  Column 0 is all zero: x = 0, residual 0, at most one iteration, and it must not fail the
+    # batch.  Column 1 = [K U; 0] -- P^-1 of it is [0; U] for any saddle preconditioner P, and A [0; U] is the column itself --
+    # converges at iteration 1 while the random ones go on.
+    k2 = 17
+    rhs2 = 0.1 * rng.standard_normal((k2, nsys))
+    rhs2[:, n3:] *= 10.0
+    rhs2[0] = 0.0
+    rhs2[1] = 0.0
+    rhs2[1, :n3] = rb.K_dot(rng.standard_normal(6 * nb)).reshape(-1)
+    x2, its2, res2 = rb.solve_saddle_multi(rhs2, max_iter=200, rtol=1e-10)
+    assert np.all(np.isfinite(x2)) and np.all(np.isfinite(res2))
+    assert not np.any(x2[0]) and res2[0] == 0.0 and int(its2[0]) <= 1, (its2[0], res2[0])
+    assert int(its2[1]) == 1 and res2[1] < 1e-10, (its2[1], res2[1])
+    assert int(its2[2:].min()) > 3 and int(its2[2:].max()) > 10, list(its2)     # columns 0 and 1 ride along for 10+ iterations
+    for col in range(1, k2):
+        xs, it1, res1 = rb.solve_saddle(rhs2[col], max_iter=200, rtol=1e-10)
+        assert abs(int(its2[col]) - it1) <= 1 and res2[col] < 1e-10, (col, its2[col], it1, res2[col])
+        assert np.linalg.norm(x2[col] - xs) <= 1e-9 * np.linalg.norm(xs), col
+        assert np.linalg.norm(rb.apply_saddle(x2[col]) - rhs2[col]) < 1e-9 * np.linalg.norm(rhs2[col]), col
     # the body mobility matrix against dense numpy on the oracle's matrices
     Nmat, itn = rb.body_mobility_matrix(rtol=1e-11)
     cfg = c["cfg"] - c["cfg"].mean(axis=0)
