@@ -593,6 +593,36 @@ int rbl_ensemble_step_brownian(rbl_ctx *ctx, const double *F_body, const double 
                                int split_rand, double delta, int max_iter, double rtol, int *iters, double *resid);
 int rbl_ensemble_interaction_forces(rbl_ctx *ctx, double *FT_body, double *energy);
 
+/* ===================================================================== */
+/* 6. Fluid velocity at arbitrary points (rigid_body_light_amd/csrc/rbl_field.hip) */
+/* ===================================================================== */
+/* The flow the blob forces lambda (e.g. the lambda of a saddle solve [M -K; K^T 0][lambda; U] = [slip; -F]) drive at P points
+ * x_p: the velocity apply_M would give an extra force-free blob of the context's radius a placed at x_p,
+ *     u(x_p) = nf d(z_p) sum_j M(x_p, r_j) d(z_j) lambda_j,     nf = 1 / (8 pi eta a),
+ * with the pair block M of apply_M (free space, or wall-corrected per rbl_set_wall_pc) and its damping d (c_rigid_obj.cpp:618-639;
+ * rbl_set_no_damp is honoured).  A point within 1e-12 a of a blob takes the self block (no RBL_ERR_OVERLAP): a point placed on a
+ * blob returns that blob's apply_M row.  0 < r < 2a takes the overlapping RPY form, as apply_M.  With the wall, a point at z <= 0
+ * gets u = 0 (the fluid is z > 0; the damping already takes u to 0 at z = 0) -- no error.  A blob below the wall is
+ * RBL_ERR_BELOW_WALL as in apply_M; a non-finite result is RBL_ERR_NONFINITE.
+ * The tracer radius is a.  Point probes (radius 0) and other tracer radii are not offered: the free-space RPY tensor of unequal
+ * radii is textbook, but its single-wall correction has nothing in this library or the reference to be checked against.
+ *
+ *   rbl_velocity_field      host arrays: points[3 P], lambda[3 n_src], r_vecs[3 n_src] or NULL, u[3 P] (synchronous).
+ *                           r_vecs == NULL: the context's own blobs at the current configuration (n_src must be N_bod N_blb).
+ *   rbl_velocity_field_dev  the same arguments as device pointers, enqueued on the context's stream; u stays on the device
+ *                           (errors latched in the device word: rbl_sync_check)
+ *   rbl_velocity_field_info the split the product of (n_points, n_src) takes on this context: points per lane (2 or 4), chunks the
+ *                           sources are cut into (their partial sums added in fixed order), device workspace in bytes
+ * Null or negative arguments, or r_vecs == NULL with another n_src, are RBL_ERR_ARG; n_points == 0 does nothing (RBL_OK).
+ * Bitwise reproducible (no float atomics).  Under a communicator every rank evaluates a contiguous share of the points and one
+ * all-gather completes u on every rank; the source split depends on the total point count only, so u is bitwise the same at any
+ * rank count. */
+int rbl_velocity_field(rbl_ctx *ctx, const double *points, int64_t n_points, const double *lambda, const double *r_vecs,
+                       int64_t n_src, double *u);
+int rbl_velocity_field_dev(rbl_ctx *ctx, const double *d_points, int64_t n_points, const double *d_lambda, const double *d_r_vecs,
+                           int64_t n_src, double *d_u);
+int rbl_velocity_field_info(const rbl_ctx *ctx, int64_t n_points, int64_t n_src, int *ni, int *chunks, int64_t *workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,9 @@ def lib():
         L.rbl_ensemble_step_deterministic.argtypes = [vp, vp, vp, C.c_int, dbl, vp, vp]
         L.rbl_ensemble_step_brownian.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_int, dbl, C.c_int, dbl, vp, vp]
         L.rbl_ensemble_interaction_forces.argtypes = [vp, vp, vp]
+        L.rbl_velocity_field.argtypes = [vp, vp, i64, vp, vp, i64, vp]
+        L.rbl_velocity_field_dev.argtypes = [vp, vp, i64, vp, vp, i64, vp]
+        L.rbl_velocity_field_info.argtypes = [vp, i64, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
         _LIB = L
     return _LIB
 
@@ -511,6 +514,29 @@ class DeviceContext:
         buf = C.create_string_buffer(64)
         self._chk(self.L.rbl_apply_M_sym_kernel(self.h, n_blobs, i_step, nrhs, 1 if wall else 0, buf, 64))
         return buf.value.decode()
+
+    # -- fluid velocity at arbitrary points (include/rbl.h section 6) --------------------------------------------------------
+    def velocity_field(self, points, lam, positions=None):
+        """u at points (P, 3) or flat 3P from blob forces lam on blobs `positions` (None: the context's own blobs at its
+        configuration); host arrays in, a flat (3P,) array out"""
+        import numpy as np
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
+        lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(-1)
+        r = None if positions is None else np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
+        u = np.empty_like(pts)
+        self._chk(self.L.rbl_velocity_field(self.h, pts.ctypes.data, pts.size // 3, lam.ctypes.data,
+                                            None if r is None else r.ctypes.data, lam.size // 3, u.ctypes.data))
+        return u
+
+    def velocity_field_dev(self, d_points, n_points, d_lam, d_r, n_src, d_out):
+        """the same on device addresses (d_r = None / 0: the context's own blobs); enqueued on the context's stream"""
+        self._chk(self.L.rbl_velocity_field_dev(self.h, d_points, n_points, d_lam, d_r or None, n_src, d_out))
+
+    def velocity_field_info(self, n_points, n_src):
+        """(points per lane NI, source chunks, workspace bytes) of the product of that size on this context"""
+        ni, ch, wb = C.c_int(0), C.c_int(0), C.c_int64(0)
+        self._chk(self.L.rbl_velocity_field_info(self.h, n_points, n_src, C.byref(ni), C.byref(ch), C.byref(wb)))
+        return ni.value, ch.value, wb.value
 
     def blob_positions(self, body_begin, body_end, dout):
         self._chk(self.L.rbl_blob_positions_dev(self.h, body_begin, body_end, dout))

@@ -417,6 +417,26 @@ struct CManyBodies {
   }
 
   // configuration-dependent forces (include/rbl.h section 4; the reference has none)
+  // fluid velocity at points[3P] from blob forces lambda[3N] on blobs r_vecs[3N] (None: the object's own blobs)
+  darr velocity_field(darr points, darr lambda, py::object r_vecs)
+  {
+    if (points.size() % 3 != 0 || lambda.size() % 3 != 0) throw std::runtime_error("velocity_field: points and lambda must have length 3P, 3N");
+    darr r;
+    const bool own = r_vecs.is_none();
+    if (!own) {
+      r = darr::ensure(r_vecs);
+      if (!r || r.size() != lambda.size()) throw std::runtime_error("velocity_field: r_vecs and lambda must be of the same size");
+    }
+    darr out(points.size());
+    int rc;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_velocity_field(ctx, points.data(), (int64_t)(points.size() / 3), lambda.data(), own ? nullptr : r.data(),
+                              (int64_t)(lambda.size() / 3), out.mutable_data());
+    }
+    check(rc);
+    return out;
+  }
   void set_interactions(double w, double eps_wall, double b_wall, double eps_blob, double b_blob, double r_cut, bool on)
   {
     check(rbl_set_interactions(ctx, w, eps_wall, b_wall, eps_blob, b_blob, r_cut, on ? 1 : 0));
@@ -513,6 +533,8 @@ PYBIND11_MODULE(c_rigid, m)
            py::arg("b_blob"), py::arg("r_cut"), py::arg("on") = true)
       .def("interaction_forces", &CManyBodies::interaction_forces, "force model's body forces/torques, reference convention (-K^T f)")
       .def("interaction_energy", &CManyBodies::interaction_energy)
+      .def("velocity_field", &CManyBodies::velocity_field, "fluid velocity at points from blob forces", py::arg("points"),
+           py::arg("lambda"), py::arg("r_vecs") = py::none())
       .def("set_option", &CManyBodies::set_option, py::arg("name"), py::arg("value"))
       .def("get_option", &CManyBodies::get_option, py::arg("name"))
       .def("handle", &CManyBodies::handle, "address of the underlying rbl_ctx (for the ctypes device API)")

@@ -9,6 +9,7 @@
 //   rbl_steps.hip     whole time steps, random finite differences
 //   rbl_forces.hip    configuration-dependent forces (weight, wall and steric repulsion)
 //   rbl_ensemble.hip  ensembles of independent replicas of one small system
+//   rbl_field.hip     the fluid velocity at arbitrary points from blob forces
 // None of these symbols is exported from librbl.so.
 #pragma once
 #include "rbl_internal.hpp"

@@ -214,6 +214,9 @@ struct rbl_ctx {
   int ens_cur = 0;                                  // which of the two configuration sets in d_ens is the committed one
   RblDevBuf d_ens;                                  // [X | Q] x 2 (R 7 N_bod each) | reference configuration
   RblDevBuf d_ens_w;                                // step workspace
+  // velocity field (rbl_field.hip; include/rbl.h section 6)
+  RblDevBuf d_vf;                                   // host form's staging: points | u | lambda | r
+  RblDevBuf d_vfw;                                  // packed sources | partial-sum slabs of the chunks
   std::vector<double> ens_cfg_host;                 // the reference configuration d_ens holds
   // lanczos
   int lanczos_max_iter = 100;

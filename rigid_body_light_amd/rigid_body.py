@@ -10,7 +10,7 @@ reference src/Rigid.py:54,60,66).
 Beyond the reference surface (its C++ has these, its Python does not): `solve_saddle`, `solve_saddle_multi`,
 `body_mobility_matrix`, `M_half_W`, `M_RFD`,
 `KTinv_RFD`, `M_RFD_cfgs`, `M_RFD_from_U`, `KT_RFD_from_U`, `evolve_rigid_bodies_RFD`, `apply_M_multi`,
-`dense_mobility`, and a force model the reference does not have (`set_interactions`, `interaction_forces`).
+`dense_mobility`, `velocity_field` (the flow at arbitrary points), and a force model the reference does not have (`set_interactions`, `interaction_forces`).
 """
 import numpy as np
 
@@ -219,6 +219,30 @@ class RigidBody:
 
     def interaction_energy(self):
         return self.cb.interaction_energy()
+
+    def velocity_field(self, points, blob_forces, positions=None):
+        """Fluid velocity at arbitrary points from blob forces (include/rbl.h section 6): the velocity `apply_M` would give an
+        extra force-free blob of radius a at each point -- e.g. the flow around the bodies after `solve_saddle`, whose first
+        3 * total_blobs entries are the blob forces.  points: (P, 3) or flat 3P; blob_forces: flat or (N, 3); positions: the
+        blobs' positions (default: this object's blobs at the current configuration, then blob_forces must have 3 * total_blobs
+        entries).  With the wall, points at z <= 0 get u = 0.  Returns (P, 3) or flat, following the shape of `points`."""
+        pts = np.asarray(points, dtype=np.float64)
+        lam = np.asarray(blob_forces, dtype=np.float64)
+        if not (pts.ndim == 2 and pts.shape[1] == 3) and not (pts.ndim == 1 and pts.size % 3 == 0):
+            raise ValueError(f"velocity_field: points must have shape (P, 3) or (3P,). Got shape: {pts.shape}")
+        if not (lam.ndim == 2 and lam.shape[1] == 3) and not (lam.ndim == 1 and lam.size % 3 == 0):
+            raise ValueError(f"velocity_field: blob_forces must have shape (N, 3) or (3N,). Got shape: {lam.shape}")
+        if positions is None:
+            if lam.size != 3 * self.total_blobs:
+                raise ValueError(f"velocity_field: blob_forces must have total size 3*N_blobs = {3 * self.total_blobs}. Got shape: {lam.shape}")
+            r = None
+        else:
+            r = np.asarray(positions, dtype=np.float64)
+            if r.size != lam.size:
+                raise ValueError(f"velocity_field: positions and blob_forces must be of the same size. Got {r.shape} and {lam.shape}")
+            r = r.reshape(-1)
+        u = self.cb.velocity_field(pts.reshape(-1), lam.reshape(-1), r)
+        return u.reshape(pts.shape)
 
     def apply_M_multi(self, forces, positions):
         """k right-hand sides at once, forces (k, 3N); k >= 4 runs on the fp64 matrix cores."""
