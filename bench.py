@@ -14,12 +14,16 @@ process per GPU, torch.distributed / RCCL all-gather), total work fixed -> "stro
     python bench.py --gpus 1 --steps 10 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline`
-(dominant kernel k_apply_M timed with events on its own stream) and `cpu_baseline`
-(the CPU oracle -- a port of the reference algorithm -- on a bounded row sample).
-At N = 1 the line also carries `configs`: every other BASELINE.json configuration timed in the same run (cfg 1 / cfg 2
-products and converged time steps, cfg 5's dense build / Cholesky / L W), each priced against the roofline that bounds it.
-At N > 1 it carries `per_rank`: where each rank's time went (kernel min / max, all-gather, all-reduce, per-body work).
+A plain run sets up, warms up, times the steps and prints ONE JSON line on rank 0: the headline figure with its
+`roofline` (the dominant kernel, bracketed by events inside the timed steps) and, at N > 1, `per_rank`: where each
+rank's time went (kernel min / max, all-gather, all-reduce, per-body work).  Everything else is measured only with
+
+    python bench.py --full
+
+after the timed steps: the time-step variants (`timestep`) at every N; at N = 1 two more passes of the steps (`repeats`),
+`cpu_baseline` (the CPU oracle -- a port of the reference algorithm -- on a bounded row sample), the drop-in and multi-RHS
+solves and `configs`: every other BASELINE.json configuration (cfg 1 / cfg 2 products and converged time steps, cfg 5's
+dense build / Cholesky / L W), each priced against the roofline that bounds it; at N > 1 the row split (`partitionings.rows`).
 """
 import argparse
 import json
@@ -139,7 +143,7 @@ def self_launch(args, argv):
     """`python bench.py --gpus N` without torchrun: start the N-rank job as CHILD processes (one rank per GPU, RCCL)
     before this process has touched the GPU, print the ONE line and exit with the job's status.  Two phases, so that the
     headline line survives whatever happens to the (much longer) time-step part: phase `main` times the hot path and
-    produces the line; phase `timestep` (apply_M mode with --timestep-steps > 0 only) runs the time-step variants as a
+    produces the line; phase `timestep` (apply_M mode with --full and --timestep-steps > 0 only) runs the time-step variants as a
     second job under a time limit and its result -- or the reason it is missing -- is merged into the line; a missing
     time-step part makes the exit status non-zero (the line is still printed).  Every job runs in its own session: on a
     time-out the whole process group is terminated, then killed, so no rank outlives bench.py holding a GPU."""
@@ -1194,7 +1198,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
-    ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of CPU work per cpu_baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure what the headline figure does not need: "
+                    "two more passes of the steps, the CPU baseline, the time-step variants, the other BASELINE configurations, "
+                    "the drop-in and multi-RHS solves, at N > 1 the row split")
+    ap.add_argument("--cpu-budget", type=float, default=None, help="--full: seconds of CPU work per cpu_baseline leg (default 10, 0 = skip)")
     ap.add_argument("--jsplit", type=int, default=0)
     ap.add_argument("--variant", type=int, default=0, help="0 heuristic, 1 ordered-rows kernel, 2 symmetric kernel")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse "
@@ -1203,8 +1210,9 @@ def main():
                     help="apply_M: 1 step = one M.F pass (default).  timestep: 1 step = one time step (SURVEY.md 8d; "
                          "fixed work: 20 GMRES iterations = 21 apply_M + PC + K ops + evolve; --rtol: converged).  brownian: "
                          "1 step = one Brownian increment M^{1/2} W")
-    ap.add_argument("--timestep-steps", type=int, default=10, help="also time this many time steps of every variant (0 = skip)")
-    ap.add_argument("--other-configs", type=int, default=1, help="N = 1, default workload: also time BASELINE configs[0], [1], [4] (0 = skip)")
+    ap.add_argument("--timestep-steps", type=int, default=None, help="--full: also time this many time steps of every variant (default 10, 0 = skip)")
+    ap.add_argument("--other-configs", type=int, default=None, help="--full, N = 1, default workload: also time BASELINE configs[0], [1], [4] "
+                    "(default 1, 0 = skip)")
     ap.add_argument("--kBT", type=float, default=0.0, help="--mode timestep: > 0 runs the stochastic midpoint (Brownian) step")
     ap.add_argument("--mhalf", default="lanczos_pc", choices=["lanczos_pc", "lanczos", "cholesky"],
                     help="square root used by the Brownian step (lanczos_pc: block-Jacobi preconditioned Lanczos)")
@@ -1233,6 +1241,11 @@ def main():
     if args.notes:
         print(json.dumps(NOTES, indent=1))
         return
+    for name, full_default in (("cpu_budget", 10.0), ("timestep_steps", 10), ("other_configs", 1)):   # what only --full measures
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+        elif getattr(args, name) and not args.full:
+            raise SystemExit("bench.py: --%s measures beyond the headline figure: add --full" % name.replace("_", "-"))
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1357,17 +1370,19 @@ def main():
             outputs = {"blob_positions": r_all.cpu().numpy(), "blob_velocities": U_full.cpu().numpy()}
         elapsed = t1 - t0
         kern_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps
-        # the same K steps twice more: box-to-box and run-to-run spread of this kernel (20.3 - 22.1 ms in round 3) is larger than
-        # most kernel changes, so the line carries min / median of three passes; `value` stays the contract's first pass
-        passes = [elapsed / args.steps * 1e3]
-        for _ in range(2):
-            barrier(); ta = time.perf_counter()
-            for k in range(args.steps):
-                step()
-            barrier(); passes.append((time.perf_counter() - ta) / args.steps * 1e3)
-        ctx.sync_check()
-        repeats = {"ms_per_step": [round(x, 4) for x in passes], "min": min(passes), "median": sorted(passes)[1],
-                   "note": "three passes of --steps steps each; `value` / `ms_per_step` are the first (the contract's timed region)"}
+        repeats = None
+        if args.full:
+            # the same K steps twice more: box-to-box and run-to-run spread of this kernel (20.3 - 22.1 ms in round 3) is larger than
+            # most kernel changes, so the line carries min / median of three passes; `value` stays the contract's first pass
+            passes = [elapsed / args.steps * 1e3]
+            for _ in range(2):
+                barrier(); ta = time.perf_counter()
+                for k in range(args.steps):
+                    step()
+                barrier(); passes.append((time.perf_counter() - ta) / args.steps * 1e3)
+            ctx.sync_check()
+            repeats = {"ms_per_step": [round(x, 4) for x in passes], "min": min(passes), "median": sorted(passes)[1],
+                       "note": "three passes of --steps steps each; `value` / `ms_per_step` are the first (the contract's timed region)"}
         if use_sym:
             ni, chunk, wbytes = ctx.apply_M_sym_info(N, 1, 1)
             kname = sym_kernel_name(ctx, wall, N)
@@ -1385,7 +1400,8 @@ def main():
         assert world_ == world and rank_ == rank
         partitionings = {}
         ctx.set_timing(True)
-        for pname, split in (("tile_pairs", 0), ("rows", 1)):
+        splits = (("tile_pairs", 0), ("rows", 1)) if args.full else (("tile_pairs", 0),)   # the headline is the first
+        for pname, split in splits:
             ctx.set_option("comm_split", split)
 
             def step():
@@ -1434,9 +1450,11 @@ def main():
         ctx.set_option("comm_split", 0)
         ctx.set_timing(False)
         repeats = None
-        parallelism = ("tile-pair-sharded x%d, positions replicated, all-reduce(U) [value]; also rows-by-body x%d, all-gather(positions) + "
-                       "all-gather(U) [partitionings.rows]; collectives: %s" % (world, world, "RCCL inside librbl (rbl_comm_init_rccl)" if kind == 2 else
-                                                                               "callbacks into torch.distributed (%s rehearsal)" % args.backend))
+        parallelism = "tile-pair-sharded x%d, positions replicated, all-reduce(U) [value]; " % world
+        if "rows" in partitionings:
+            parallelism += "also rows-by-body x%d, all-gather(positions) + all-gather(U) [partitionings.rows]; " % world
+        parallelism += "collectives: %s" % ("RCCL inside librbl (rbl_comm_init_rccl)" if kind == 2 else
+                                            "callbacks into torch.distributed (%s rehearsal)" % args.backend)
 
     if args.dump_check:   # for tests/: a row sample of what was just timed (the oracle comparison happens in the test)
         b0 = sm.row0 + (nrows // 2)
@@ -1484,8 +1502,8 @@ def main():
             line["per_rank"] = dict(partitionings["tile_pairs"]["per_rank"],
                                     note="GPU milliseconds per step and rank between hipEvents on the context's stream (rbl_get_timings): "
                                          "kernel = this rank's share (pair kernel + slab reduction); collective = the all-reduce / all-gather incl. "
-                                         "the wait for the slowest rank.  Both work splits in `partitionings`; the time-step variants carry the "
-                                         "library's phase timings (`phases`) per rank.")
+                                         "the wait for the slowest rank.  With --full: both work splits in `partitionings`, and the time-step "
+                                         "variants carry the library's phase timings (`phases`) per rank.")
     tstep = None
     failed = None
     if args.timestep_steps > 0 and phase != "main":

@@ -215,6 +215,23 @@ def test_bench_refuses_more_ranks_than_gpus():
     assert not any(l.startswith("{") for l in p.stdout.splitlines())
 
 
+@pytest.mark.parametrize("extra", [["--timestep-steps", "3"], ["--cpu-budget", "5"], ["--other-configs", "1"]])
+def test_bench_measures_beyond_the_headline_only_with_full(extra):
+    """A plain `bench.py` run measures the headline figure alone; the time steps, the CPU baseline and the other configurations
+    run only with --full.  Asking for one of them without --full is refused before the GPU is touched (here: the CPU container)."""
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "0"] + extra, cwd=root, env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode != 0
+    assert "%s measures beyond the headline figure: add --full" % extra[0] in (p.stdout + p.stderr)
+    assert not any(l.startswith("{") for l in p.stdout.splitlines())
+
+
 def test_bench_line_helpers():
     """the pieces of bench.py's line that are pure host logic: the top-level `timesteps_per_sec` / `cpu_baseline_timestep` blocks
     (BASELINE's metric is timesteps/sec + M.F GFLOP/s), the product count of a Brownian step, the --opt parser"""

@@ -37,7 +37,7 @@ def test_two_rank_sharded_apply_M_matches_oracle(orc, tmp_path):
     from rigid_body_light_amd import make_config
     dump = str(tmp_path / "chk")
     p = _torchrun(2, ["bench.py", "--gpus", "2", "--backend", "gloo", "--config", "cfg2", "--steps", "3", "--warmup", "1",
-                      "--dump-check", dump, "--cpu-budget", "0", "--timestep-steps", "1", "--detail", dump + ".json"])
+                      "--dump-check", dump, "--full", "--cpu-budget", "0", "--timestep-steps", "1", "--detail", dump + ".json"])
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     full = json.load(open(dump + ".json"))                 # the sidecar: the full record behind the slim line
@@ -64,7 +64,8 @@ def test_bench_self_launches_two_ranks(timestep_steps, tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RBL_BENCH_PHASE"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--config", "cfg2", "--steps", "3",
-                        "--warmup", "1", "--cpu-budget", "0", "--timestep-steps", timestep_steps, "--detail", str(tmp_path / "d.json")],
+                        "--warmup", "1", "--cpu-budget", "0", "--timestep-steps", timestep_steps, "--detail", str(tmp_path / "d.json")]
+                       + (["--full"] if timestep_steps != "0" else []),
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -73,6 +74,7 @@ def test_bench_self_launches_two_ranks(timestep_steps, tmp_path):
     assert d["n_gpus"] == 2 and "x2" in d["config"]["parallelism"]
     assert 0.0 < d["roofline"]["frac"] <= 1.0
     assert len(lines[0]) < 4500 and list(d)[-1] == "summary"
+    assert set(d["partitionings"]) == ({"tile_pairs", "rows"} if timestep_steps != "0" else {"tile_pairs"})   # the row split: --full only
     if timestep_steps != "0":
         t = json.load(open(str(tmp_path / "d.json")))["timestep"]
         assert d["summary"]["timesteps_per_sec"]["deterministic_fixed_work"] > 0.0
@@ -87,7 +89,7 @@ def test_headline_line_survives_a_failing_time_step_part(monkeypatch, failing_ra
     import json
     monkeypatch.setenv("RBL_BENCH_INJECT_FAILURE", failing_rank)
     p = _torchrun(2, ["bench.py", "--gpus", "2", "--backend", "gloo", "--config", "cfg2", "--steps", "3", "--warmup", "1",
-                      "--cpu-budget", "0", "--timestep-steps", "1"])
+                      "--full", "--cpu-budget", "0", "--timestep-steps", "1"])
     assert p.returncode != 0
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:] + p.stderr[-2000:]
@@ -230,7 +232,7 @@ def test_bench_n_rank_code_path_on_one_rank_over_rccl(orc, tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "RBL_BENCH_PHASE"):
         env.pop(k, None)
     dump = str(tmp_path / "chk")
-    p = subprocess.run([sys.executable, "bench.py", "--force-comm", "--config", "cfg2", "--steps", "3", "--warmup", "1", "--cpu-budget", "0",
+    p = subprocess.run([sys.executable, "bench.py", "--force-comm", "--full", "--config", "cfg2", "--steps", "3", "--warmup", "1", "--cpu-budget", "0",
                         "--timestep-steps", "1", "--dump-check", dump, "--detail", dump + ".json"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]

@@ -13,10 +13,10 @@ BENCH="python3 $R/bench.py --steps 5 --warmup 1 --cpu-budget 0 --timestep-steps 
 for p in $parts; do
 case $p in
 lines)
-  python3 $R/bench.py > $O/bench_line.json 2> $O/bench_line.err || echo "default bench failed"
-  python3 $R/bench.py --force-comm --cpu-budget 0 --timestep-steps 3 > $O/bench_force_comm_line.json 2> $O/bench_force_comm_line.err || echo "force-comm bench failed" ;;
+  python3 $R/bench.py --full > $O/bench_line.json 2> $O/bench_line.err || echo "default bench failed"
+  python3 $R/bench.py --full --force-comm --cpu-budget 0 --timestep-steps 3 > $O/bench_force_comm_line.json 2> $O/bench_force_comm_line.err || echo "force-comm bench failed" ;;
 cfg3)
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/cfg3_stats -- python3 $R/bench.py --steps 5 --warmup 1 --cpu-budget 0 --timestep-steps 2 --other-configs 0 > $O/cfg3_stats.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/cfg3_stats -- python3 $R/bench.py --full --steps 5 --warmup 1 --cpu-budget 0 --timestep-steps 2 --other-configs 0 > $O/cfg3_stats.log 2>&1 || exit 1
   for c in "SQ_INSTS_VALU GRBM_GUI_ACTIVE" "SQ_BUSY_CU_CYCLES SQ_WAVES" "FETCH_SIZE" "WRITE_SIZE"; do
     d=$O/cfg3_pmc_$(echo $c | tr ' ' '_')
     rocprofv3 --kernel-trace --pmc $c --output-format csv -d $d -- $BENCH > $d.log 2>&1 || exit 1

@@ -12,9 +12,9 @@ BENCH="python3 $R/bench.py --steps 5 --warmup 1 --cpu-budget 0 --timestep-steps 
 for p in $parts; do
 case $p in
 line)
-  python3 $R/bench.py --steps 20 --warmup 5 --detail $O/bench_detail.json > $O/bench_line.json 2> $O/bench_line.err || echo "default bench failed" ;;
+  python3 $R/bench.py --full --steps 20 --warmup 5 --detail $O/bench_detail.json > $O/bench_line.json 2> $O/bench_line.err || echo "default bench failed" ;;
 cfg3)
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/cfg3_stats -- python3 $R/bench.py --steps 5 --warmup 1 --cpu-budget 0 --timestep-steps 2 --other-configs 0 > $O/cfg3_stats.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/cfg3_stats -- python3 $R/bench.py --full --steps 5 --warmup 1 --cpu-budget 0 --timestep-steps 2 --other-configs 0 > $O/cfg3_stats.log 2>&1 || exit 1
   for c in "SQ_INSTS_VALU GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do
     d=$O/cfg3_pmc_$(echo $c | tr ' ' '_')
     rocprofv3 --kernel-trace --pmc $c --output-format csv -d $d -- $BENCH > $d.log 2>&1 || exit 1
