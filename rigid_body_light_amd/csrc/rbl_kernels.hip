@@ -1,8 +1,9 @@
 // rbl_kernels.hip -- hand-written gfx950 kernels of the blob-mobility hot path.
 //
-//   k_apply_M_sym<WALL,NI>  matrix-free U = [B] M [B] F, every UNORDERED pair once (default):
-//                           wave-private LDS tile, systolic lane<->column pairing, ds_add_f64
+//   k_apply_M_sym<WALL,NI,SW,PREC,NV>  matrix-free U = [B] M [B] F for NV = 1 or 2 vectors, every UNORDERED pair once
+//                           (default): staged LDS tile, systolic lane<->column pairing, ds_add_f64
 //                           column sums, slabs reduced by k_reduce_sym   (reference :641-659,:413-459)
+//   k_apply_M_symw<WALL,NI,IW,NV>  the same for mid-size systems: a unit per wave, column sums rotating by DPP
 //   k_apply_M<WALL>         the same product by ordered pairs for a ROW RANGE (row sharding,
 //                           very large N): j tiles staged in LDS, lane = row, LDS broadcast;
 //                           j-split partial slabs reduced by k_reduce_parts
@@ -351,20 +352,131 @@ __device__ __forceinline__ double sym_first_lane(double v)      // lane 0's valu
 #define RBL_WT_END(unit)
 #endif
 
+// ---- pieces both symmetric kernel families share (NV = 1 or 2 force vectors) ------------------------------------------------
+// blob idx as the pair arithmetic wants it: position divided by the blob radius, the NV forces damped (vector v of F at F + 3 N v)
+template <bool WALL, int NV>
+__device__ __forceinline__ void sym_load_blob(const double *__restrict__ r, const double *__restrict__ F, long N, const RblParams &P,
+                                              long idx, double &x, double &y, double &z, RblV3 (&f)[NV], unsigned &flags)
+{
+  if (idx < N) {
+    x = r[3 * idx]; y = r[3 * idx + 1]; z = r[3 * idx + 2];
+    double d = 1.0;
+    if (WALL) {
+      if (z < 0.0) flags |= RBL_FLAG_BELOW_WALL;
+      d = damp_of(P, z);
+    }
+    x *= P.inv_a; y *= P.inv_a; z *= P.inv_a;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const double *Fv = F + (size_t)v * (size_t)(3 * N);
+      f[v] = RblV3{d * Fv[3 * idx], d * Fv[3 * idx + 1], d * Fv[3 * idx + 2]};
+    }
+  } else {  // padding blob: zero force, far from everything (and from every other pad)
+    x = 1.0e15 * (double)(2 + (idx - N)); y = 0.0; z = 1.0;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) f[v] = RblV3{0.0, 0.0, 0.0};
+  }
+}
+
+// the column tiles [J0, J1) of chunk c that a unit whose first row tile is It sweeps; false: none (a dead unit)
+__device__ __forceinline__ bool sym_unit_columns(const SymLayout &L, int c, int It, int &J0, int &J1)
+{
+  if (It >= L.T) return false;
+  J0 = c * L.C;
+  J1 = (J0 + L.C < L.T) ? J0 + L.C : L.T;
+  if (J0 < It) J0 = It;
+  return J0 < J1;
+}
+
+// A staged column blob is  x y z f_0 .. f_{NV-1}  in SYM_NP(NV) 16-byte LDS words, word k of every column in an array of its own:
+// (x,y) (z,f0x) (f0y,f0z) [(f1x,f1y) (f1z,-)].  b[k]: that array; a column is addressed by its byte offset 16 jj.
+constexpr int SYM_NP(int NV) { return (3 + 3 * NV + 1) / 2; }
+
+template <int NV> struct SymCol {
+  double x, y, z;
+  RblV3 f[NV];
+};
+
+template <int NV>
+__device__ __forceinline__ void sym_stage_col(char *const *b, int lane, double x, double y, double z, const RblV3 (&f)[NV])
+{
+  double d[2 * SYM_NP(NV)] = {x, y, z};          // (the odd last half stays 0)
+#pragma unroll
+  for (int v = 0; v < NV; ++v) { d[3 + 3 * v] = f[v].x; d[4 + 3 * v] = f[v].y; d[5 + 3 * v] = f[v].z; }
+#pragma unroll
+  for (int k = 0; k < SYM_NP(NV); ++k) ((double2_t *)b[k])[lane] = (double2_t){d[2 * k], d[2 * k + 1]};
+}
+
+template <int NV>
+__device__ __forceinline__ SymCol<NV> sym_read_col(char *const *b, unsigned off16)
+{
+  double d[2 * SYM_NP(NV)];
+#pragma unroll
+  for (int k = 0; k < SYM_NP(NV); ++k) {
+    const double2_t w = *(const double2_t *)(b[k] + off16);
+    d[2 * k] = w.x; d[2 * k + 1] = w.y;
+  }
+  SymCol<NV> c;
+  c.x = d[0]; c.y = d[1]; c.z = d[2];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) c.f[v] = RblV3{d[3 + 3 * v], d[4 + 3 * v], d[5 + 3 * v]};
+  return c;
+}
+
+// the ordered diagonal sweep step: row a of the lane against column blob cj of its own tile, one vector after the other
+template <bool WALL, int NV>
+__device__ __forceinline__ void sym_diag_pair(const RblParams &Pu, double xi, double yi, double zi, const SymCol<NV> &cj, bool is_self,
+                                              RblV3 (&ui)[NV], unsigned &flags)
+{
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+    rbl_pair_accum<WALL, true, true>(Pu, xi, yi, zi, cj.x, cj.y, cj.z, cj.f[v].x, cj.f[v].y, cj.f[v].z, is_self, ui[v].x, ui[v].y, ui[v].z, flags);
+}
+
+// a lane's row sums of chunk c into the chunk's slab (row tiles at or beyond T are padding)
+template <int NI, int NV>
+__device__ __forceinline__ void sym_store_rows(double *__restrict__ slabI, const SymLayout &L, int c, int It0, int lane, const RblV3 (&ui)[NI][NV])
+{
+#pragma unroll
+  for (int a = 0; a < NI; ++a)
+    if (It0 + a < L.T) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        double *p = slabI + sym_idxI(L, c, v, (long)(It0 + a) * TS + lane);
+        p[0] = ui[a][v].x; p[1] = ui[a][v].y; p[2] = ui[a][v].z;
+      }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Workgroup-owned units, NV = 1 or 2 force vectors (F, out: [NV][3N]; the slabs hold the vectors back to back).  Two vectors: the pair
+// coefficients are evaluated once for both (rbl_pair_symv).
 // PREC = 1 (relaxed product, two rows per lane only): tile pairs the far map proves free of overlaps AND safe for single
-// precision (k_tile_far, bit 1) are swept in packed single precision (rbl_pair_sym_pk), coordinates relative to the first
+// precision (k_tile_far, bit 1) are swept in packed single precision (rbl_pk_coef / rbl_pk_apply), coordinates relative to the first
 // blob of the column tile (round 3; one origin per workgroup let the error grow with the extent of the suspension); their
 // per-tile sums are added to the double accumulators, so single precision only ever sums 64 x NI terms.  Diagonal, near
 // and unsafe tiles stay fp64.
-// (the four-wave wall instance is held to 168 VGPRs -- three waves per SIMD instead of two at the 186 the compiler takes
+// (the one-vector four-wave wall instance is held to 168 VGPRs -- three waves per SIMD instead of two at the 186 the compiler takes
 // unasked: no spill, 2 % faster at cfg 3 on one box, A/B gpurun_out/r03k/ab_wpe3.txt; HIP's second launch bound is the
 // minimum number of waves per SIMD.  The other instances are left alone: the relaxed one would spill, the small ones
 // already fit four.)
 // NI = 4 (large single-GPU systems, one vector): the three column reads, the three ds_add_f64 column sums and the loop and
 // address arithmetic of a step are shared by four pair evaluations instead of two, and a lane carries four independent pair
 // chains.  Held to two waves per SIMD (<= 256 VGPRs).
-template <bool WALL, int NI, int SW, int PREC>
-__global__ __launch_bounds__(TS *SW, (WALL && NI == 2 && SW > 1 && PREC == 0) ? 3 : (NI == 4 ? 2 : 1)) void k_apply_M_sym(const double *__restrict__ r,
+// ---------------------------------------------------------------------------
+#ifndef RBL_SYM2_MIN_WAVES
+#define RBL_SYM2_MIN_WAVES 1      // waves per SIMD the two-vector wall instance is held to.  Measured with 3 (tools/build_variant.sh s2w3
+                                  // -DRBL_SYM2_MIN_WAVES=3: 168 VGPRs + 232 B of scratch instead of 235 VGPRs): Brownian step 608.6-609.1 ms
+                                  // against 608.9-609.3 -- no change, left at the compiler's choice
+#endif
+constexpr int sym_min_waves(bool WALL, int NI, int SW, int PREC, int NV)   // minimum waves per SIMD (HIP's second launch bound)
+{
+  if (WALL && NI == 2 && SW > 1 && PREC == 0) return NV == 2 ? RBL_SYM2_MIN_WAVES : 3;
+  return (NV == 1 && NI == 4) ? 2 : 1;
+}
+
+template <bool WALL, int NI, int SW, int PREC, int NV>
+__global__ __launch_bounds__(TS *SW, sym_min_waves(WALL, NI, SW, PREC, NV)) void k_apply_M_sym(const double *__restrict__ r,
                                                         const double *__restrict__ F,
                                                         double *__restrict__ slabI,
                                                         double *__restrict__ slabJ, long N, SymLayout L, RblParams P,
@@ -375,9 +487,13 @@ __global__ __launch_bounds__(TS *SW, (WALL && NI == 2 && SW > 1 && PREC == 0) ? 
   // LDS and the ds_add of M_ji F_i are shared by NI pair evaluations.  The SW waves of the workgroup own SW
   // consecutive owned super-tiles and walk the same column tiles in step: ONE staged j tile, per-wave accumulators.
   static_assert(PREC == 0 || NI == 2, "the packed single-precision sweep carries the two rows of a lane");
-  __shared__ double2_t sP0[TS], sP1[TS], sP2[TS];  // (x,y) (z,fx) (fy,fz) of the j tile
-  __shared__ double sU[SW][3][TS];                  // M_ji F_i sums for the j tile, one set per wave
-  __shared__ float sPf[PREC ? 6 : 1][TS];           // relaxed product: the j tile in single precision, origin-relative
+  static_assert(NV == 1 || (NV == 2 && NI <= 2), "two vectors: at most two rows per lane (kSymRows routes one vector to four)");
+  // the j tile, one array per 16-byte word (sP3, sP4: two vectors only; unreferenced otherwise and not allocated).  ONE array
+  // sP[NP][TS] costs the headline <true,4,4,0> its 239 VGPRs: 256 + 12 B of scratch
+  __shared__ double2_t sP0[TS], sP1[TS], sP2[TS], sP3[NV == 2 ? TS : 1], sP4[NV == 2 ? TS : 1];
+  char *const sP[5] = {(char *)sP0, (char *)sP1, (char *)sP2, (char *)sP3, (char *)sP4};
+  __shared__ double sU[SW][NV][3][TS];              // M_ji F_i sums for the j tile, one set per wave
+  __shared__ float sPf[PREC ? 3 + 3 * NV : 1][TS];  // relaxed product: x y z f_0 .. of the j tile in single precision, origin-relative
   const int lane = threadIdx.x & (TS - 1);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int T = L.T, C = L.C;
@@ -387,113 +503,133 @@ __global__ __launch_bounds__(TS *SW, (WALL && NI == 2 && SW > 1 && PREC == 0) ? 
   // are functions of r/a only): Pu is the a = 1 parameter set, positions are scaled once when loaded.
   const RblParams Pu = unit_params(P);
   const RblWallK WK = rbl_wall_k_resident();
+  // Per-NV differences of the sweeps, each one measured:
+  constexpr int kSteps = NI > 2 ? 1 : RBL_SYM_UNROLL;   // far sweep, steps per trip (four rows: one, or the 239 VGPRs become 256 + spills)
+  constexpr int kDiagSteps = NV == 1 ? 4 : 1;           // diagonal sweep.  Two vectors unrolled by 4: <false,1,1,0> goes from 99 to 171 VGPRs, 4 to 2 waves
   // one work unit: row group g x chunk c (everything below runs once per unit; `return` ends the unit)
   auto sweep_unit = [&](const int c, const int g, const unsigned unit) {
   RBL_WT_BEGIN
   const int It00 = NI * sym_row_of(SW * g, L.i_first, L.i_step, SW);   // first tile of the group (wave 0's)
-  if (It00 >= T) return;
-  int J0 = c * C;
-  const int J1 = (J0 + C < T) ? J0 + C : T;
-  if (J0 < It00) J0 = It00;
-  if (J0 >= J1) return;                                            // workgroup-uniform
+  int J0, J1;
+  if (!sym_unit_columns(L, c, It00, J0, J1)) return;                   // workgroup-uniform
   const int e = SW * g + wave;
   const int I = sym_row_of(e, L.i_first, L.i_step, SW);                // this wave's super-tile
   const bool wlive = e < L.rowsI && NI * I < T;
   const int It0 = wlive ? NI * I : (1 << 30);                      // a wave without rows never sweeps, only keeps step
-  auto load_blob = [&](long idx, double &x, double &y, double &z, double &fx, double &fy, double &fz) {
-    if (idx < N) {
-      x = r[3 * idx]; y = r[3 * idx + 1]; z = r[3 * idx + 2];
-      double d = 1.0;
-      if (WALL) {
-        if (z < 0.0) flags |= RBL_FLAG_BELOW_WALL;
-        d = damp_of(P, z);
-      }
-      x *= P.inv_a; y *= P.inv_a; z *= P.inv_a;
-      fx = d * F[3 * idx]; fy = d * F[3 * idx + 1]; fz = d * F[3 * idx + 2];
-    } else {  // padding blob: zero force, far from everything (and from every other pad)
-      x = 1.0e15 * (double)(2 + (idx - N)); y = 0.0; z = 1.0; fx = 0.0; fy = 0.0; fz = 0.0;
+
+  double xi[NI], yi[NI], zi[NI];
+  RblV3 Fi[NI][NV], ui[NI][NV];
+#pragma unroll
+  for (int a = 0; a < NI; ++a) {
+    sym_load_blob<WALL>(r, F, N, P, wlive ? (long)(It0 + a) * TS + lane : N + 1 + a, xi[a], yi[a], zi[a], Fi[a], flags);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) ui[a][v] = RblV3{0.0, 0.0, 0.0};
+  }
+  rbl_f2 Fi2[NV][3];                                               // relaxed product: the forces on the lane's two rows, packed
+  if constexpr (PREC != 0) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      Fi2[v][0] = (rbl_f2){(float)Fi[0][v].x, (float)Fi[NI - 1][v].x};
+      Fi2[v][1] = (rbl_f2){(float)Fi[0][v].y, (float)Fi[NI - 1][v].y};
+      Fi2[v][2] = (rbl_f2){(float)Fi[0][v].z, (float)Fi[NI - 1][v].z};
+    }
+  }
+  // column sums: the 3 NV contributions of this lane's rows to column jj
+  auto col_add = [&](int jj, const RblV3 (&vj)[NV]) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      __hip_atomic_fetch_add(&sU[wave][v][0][jj], vj[v].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&sU[wave][v][1][jj], vj[v].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&sU[wave][v][2][jj], vj[v].z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
   };
 
-  double xi[NI], yi[NI], zi[NI], Fix[NI], Fiy[NI], Fiz[NI], uix[NI], uiy[NI], uiz[NI];
-#pragma unroll
-  for (int a = 0; a < NI; ++a) {
-    load_blob(wlive ? (long)(It0 + a) * TS + lane : N + 1 + a, xi[a], yi[a], zi[a], Fix[a], Fiy[a], Fiz[a]);
-    uix[a] = 0.0; uiy[a] = 0.0; uiz[a] = 0.0;
-  }
-  rbl_f2 Fx2 = {0, 0}, Fy2 = {0, 0}, Fz2 = {0, 0};
-  if (PREC) {
-    const int a1 = NI - 1;
-    Fx2 = (rbl_f2){(float)Fix[0], (float)Fix[a1]};
-    Fy2 = (rbl_f2){(float)Fiy[0], (float)Fiy[a1]};
-    Fz2 = (rbl_f2){(float)Fiz[0], (float)Fiz[a1]};
-  }
-
   for (int J = J0; J < J1; ++J) {
-    const long j = (long)J * TS + lane;
-    double xj = 0, yj = 0, zj = 0, Fjx = 0, Fjy = 0, Fjz = 0;
-    if (wave == 0) load_blob(j, xj, yj, zj, Fjx, Fjy, Fjz);
+    double xj = 0, yj = 0, zj = 0;
+    RblV3 Fj[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) Fj[v] = RblV3{0, 0, 0};
+    if (wave == 0) sym_load_blob<WALL>(r, F, N, P, (long)J * TS + lane, xj, yj, zj, Fj, flags);
     const bool sweeps = J >= It0;                                  // wave-uniform
     // wave-uniform: every blob of tile J is farther than 2a from every owned row (k_tile_far; bit 1: single precision is safe)
     const int fmap = (sweeps && farmap) ? __builtin_amdgcn_readfirstlane((int)farmap[(size_t)I * (size_t)T + J]) : 0;
     const bool far_tile = fmap != 0;
     __syncthreads();                                               // previous tile consumed, its column sums written
     if (wave == 0) {
-      sP0[lane] = (double2_t){xj, yj};
-      sP1[lane] = (double2_t){zj, Fjx};
-      sP2[lane] = (double2_t){Fjy, Fjz};
-      if (PREC) {
+      sym_stage_col<NV>(sP, lane, xj, yj, zj, Fj);
+      if constexpr (PREC != 0) {
         // coordinates relative to the tile's first blob: what single precision then rounds is a separation-sized number
         const double ox = sym_first_lane(xj), oy = sym_first_lane(yj), oz = sym_first_lane(zj);
         if (lane == 0) { sO[0] = ox; sO[1] = oy; sO[2] = oz; }
-        sPf[0][lane] = (float)(xj - ox); sPf[PREC ? 1 : 0][lane] = (float)(yj - oy); sPf[PREC ? 2 : 0][lane] = (float)(zj - oz);
-        sPf[PREC ? 3 : 0][lane] = (float)Fjx; sPf[PREC ? 4 : 0][lane] = (float)Fjy; sPf[PREC ? 5 : 0][lane] = (float)Fjz;
+        sPf[0][lane] = (float)(xj - ox); sPf[1][lane] = (float)(yj - oy); sPf[2][lane] = (float)(zj - oz);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          sPf[3 + 3 * v][lane] = (float)Fj[v].x; sPf[4 + 3 * v][lane] = (float)Fj[v].y; sPf[5 + 3 * v][lane] = (float)Fj[v].z;
+        }
       }
     }
-    sU[wave][0][lane] = 0.0; sU[wave][1][lane] = 0.0; sU[wave][2][lane] = 0.0;
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+      for (int d = 0; d < 3; ++d) sU[wave][v][d][lane] = 0.0;
     __syncthreads();
     if (!sweeps) {
       // the tile lies before this wave's rows: pairs belong to an earlier wave
-    } else if (PREC && (fmap & 2) && J >= It0 + NI) {   // relaxed product: packed single precision, both rows of the lane at once
-      const double ox = sO[0], oy = sO[1], oz = sO[2];
-      const int a1 = NI - 1;
-      const rbl_f2 xi2 = {(float)(xi[0] - ox), (float)(xi[a1] - ox)}, yi2 = {(float)(yi[0] - oy), (float)(yi[a1] - oy)},
-                   zi2 = {(float)(zi[0] - oz), (float)(zi[a1] - oz)};
-      const float two_z0 = (float)(2.0 * oz);
-      rbl_f2 ax = {0, 0}, ay = {0, 0}, az = {0, 0};
+    } else if (PREC != 0 && (fmap & 2) && J >= It0 + NI) {   // relaxed product: packed single precision, both rows of the lane at once,
+      if constexpr (PREC != 0) {                              // the coefficients once for all vectors
+        const double ox = sO[0], oy = sO[1], oz = sO[2];
+        const int a1 = NI - 1;
+        const rbl_f2 xi2 = {(float)(xi[0] - ox), (float)(xi[a1] - ox)}, yi2 = {(float)(yi[0] - oy), (float)(yi[a1] - oy)},
+                     zi2 = {(float)(zi[0] - oz), (float)(zi[a1] - oz)};
+        const float two_z0 = (float)(2.0 * oz);
+        rbl_f2 acc[NV][3];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) { acc[v][0] = (rbl_f2){0, 0}; acc[v][1] = (rbl_f2){0, 0}; acc[v][2] = (rbl_f2){0, 0}; }
 #pragma unroll 2
-      for (int s = 0; s < TS; ++s) {
-        const int jj = (lane + s) & (TS - 1);
-        rbl_f2 vx = {0, 0}, vy = {0, 0}, vz = {0, 0};
-        rbl_pair_sym_pk<WALL>(xi2, yi2, zi2, Fx2, Fy2, Fz2, sPf[0][jj], sPf[PREC ? 1 : 0][jj], sPf[PREC ? 2 : 0][jj],
-                              sPf[PREC ? 3 : 0][jj], sPf[PREC ? 4 : 0][jj], sPf[PREC ? 5 : 0][jj], two_z0, ax, ay, az, vx, vy, vz);
-        // column sums in double: ds_add_f32 issues ~23x slower than ds_add_f64 on gfx950 (tools/peak_fp32pk.hip: 3.2 vs 74 G
-        // wave-instructions/s), three conversions per step are far cheaper
-        __hip_atomic_fetch_add(&sU[wave][0][jj], (double)(vx.x + vx.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&sU[wave][1][jj], (double)(vy.x + vy.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&sU[wave][2][jj], (double)(vz.x + vz.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        for (int s = 0; s < TS; ++s) {
+          const int jj = (lane + s) & (TS - 1);
+          const RblPkCoef K = rbl_pk_coef<WALL>(xi2, yi2, zi2, sPf[0][jj], sPf[1][jj], sPf[2][jj], two_z0);
+          rbl_f2 vv[NV][3];
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {                                                          // U_i += M F_j
+            vv[v][0] = (rbl_f2){0, 0}; vv[v][1] = (rbl_f2){0, 0}; vv[v][2] = (rbl_f2){0, 0};
+            rbl_pk_apply<WALL, false>(K, rbl_splat(sPf[3 + 3 * v][jj]), rbl_splat(sPf[4 + 3 * v][jj]), rbl_splat(sPf[5 + 3 * v][jj]),
+                                      acc[v][0], acc[v][1], acc[v][2]);
+          }
+#pragma unroll
+          for (int v = 0; v < NV; ++v) rbl_pk_apply<WALL, true>(K, Fi2[v][0], Fi2[v][1], Fi2[v][2], vv[v][0], vv[v][1], vv[v][2]);   // U_j += M^T F_i
+          // column sums in double: ds_add_f32 issues ~23x slower than ds_add_f64 on gfx950 (tools/peak_fp32pk.hip: 3.2 vs 74 G
+          // wave-instructions/s), three conversions per step and vector are far cheaper
+          RblV3 vj[NV];
+#pragma unroll
+          for (int v = 0; v < NV; ++v)
+            vj[v] = RblV3{(double)(vv[v][0].x + vv[v][0].y), (double)(vv[v][1].x + vv[v][1].y), (double)(vv[v][2].x + vv[v][2].y)};
+          col_add(jj, vj);
+        }
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          ui[0][v].x += (double)acc[v][0].x; ui[0][v].y += (double)acc[v][1].x; ui[0][v].z += (double)acc[v][2].x;
+          ui[a1][v].x += (double)acc[v][0].y; ui[a1][v].y += (double)acc[v][1].y; ui[a1][v].z += (double)acc[v][2].y;
+        }
       }
-      uix[0] += (double)ax.x; uiy[0] += (double)ay.x; uiz[0] += (double)az.x;
-      uix[NI - 1] += (double)ax.y; uiy[NI - 1] += (double)ay.y; uiz[NI - 1] += (double)az.y;
     } else if (J >= It0 + NI) {  // every owned row tile lies strictly before J: fused symmetric sweep
-      constexpr int kSteps = NI > 2 ? 1 : RBL_SYM_UNROLL;   // steps per trip (four rows: one, or the 239 VGPRs become 256 + spills)
+      // all rows of the lane meet column jj: their contributions to its sums are added in registers (the pair routine accumulates
+      // onto what it is handed: no instruction more) and go to LDS once -- 3 NV atomics a column instead of 3 NV NI; at two waves a SIMD
+      // the two-vector kernel waits for its LDS 5.7 x as long as the one-vector one (profiles/r05_two_vector_pmc.md)
       auto sweep = [&](auto nearchk) {
         unsigned off16 = (unsigned)lane * 16u;       // byte offset of column jj in the 16-B arrays, carried (jj*8 = off16/2)
 #pragma unroll kSteps
         for (int s = 0; s < TS; ++s) {
-          const double2_t pa = *(const double2_t *)((const char *)sP0 + off16), pb = *(const double2_t *)((const char *)sP1 + off16),
-                          pd = *(const double2_t *)((const char *)sP2 + off16);
+          const SymCol<NV> cj = sym_read_col<NV>(sP, off16);
           const int jj = (int)(off16 >> 4);
           off16 = (off16 + 16u) & (unsigned)(TS * 16 - 16);
-          double vx = 0.0, vy = 0.0, vz = 0.0;
+          RblV3 vj[NV];
+#pragma unroll
+          for (int v = 0; v < NV; ++v) vj[v] = RblV3{0.0, 0.0, 0.0};
 #pragma unroll
           for (int a = 0; a < NI; ++a)
-            rbl_pair_sym<WALL, true, decltype(nearchk)::value>(Pu, xi[a], yi[a], zi[a], Fix[a], Fiy[a], Fiz[a], pa.x,
-                                                               pa.y, pb.x, pb.y, pd.x, pd.y, uix[a], uiy[a], uiz[a],
-                                                               vx, vy, vz, flags, WK);
-          __hip_atomic_fetch_add(&sU[wave][0][jj], vx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&sU[wave][1][jj], vy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&sU[wave][2][jj], vz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            rbl_pair_symv<WALL, true, decltype(nearchk)::value>(Pu, xi[a], yi[a], zi[a], Fi[a], cj.x, cj.y, cj.z, cj.f, ui[a], vj, flags, WK);
+          col_add(jj, vj);
         }
       };
       if (far_tile) sweep(std::false_type{});   // no pair can overlap: sweep without the per-pair test
@@ -501,47 +637,36 @@ __global__ __launch_bounds__(TS *SW, (WALL && NI == 2 && SW > 1 && PREC == 0) ? 
     } else {              // J is one of the owned row tiles: per sub-tile diagonal / symmetric / skip
 #pragma unroll
       for (int a = 0; a < NI; ++a) {
-        if (J == It0 + a) {
-#pragma unroll 4
-          for (int jj = 0; jj < TS; ++jj) {
-            const double2_t pa = sP0[jj], pb = sP1[jj], pd = sP2[jj];
-            rbl_pair_accum<WALL, true, true>(Pu, xi[a], yi[a], zi[a], pa.x, pa.y, pb.x, pb.y, pd.x, pd.y, jj == lane,
-                                       uix[a], uiy[a], uiz[a], flags);
-          }
+        if (J == It0 + a) {       // diagonal tile: ordered pairs with the self term
+#pragma unroll kDiagSteps
+          for (int jj = 0; jj < TS; ++jj)
+            sym_diag_pair<WALL, NV>(Pu, xi[a], yi[a], zi[a], sym_read_col<NV>(sP, (unsigned)jj * 16u), jj == lane, ui[a], flags);
         } else if (J > It0 + a) {
           for (int s = 0; s < TS; ++s) {
             const int jj = (lane + s) & (TS - 1);
-            const double2_t pa = sP0[jj], pb = sP1[jj], pd = sP2[jj];
-            double vx = 0.0, vy = 0.0, vz = 0.0;
-            rbl_pair_sym<WALL, true>(Pu, xi[a], yi[a], zi[a], Fix[a], Fiy[a], Fiz[a], pa.x, pa.y, pb.x, pb.y, pd.x,
-                               pd.y, uix[a], uiy[a], uiz[a], vx, vy, vz, flags, WK);
-            __hip_atomic_fetch_add(&sU[wave][0][jj], vx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_add(&sU[wave][1][jj], vy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_add(&sU[wave][2][jj], vz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const SymCol<NV> cj = sym_read_col<NV>(sP, (unsigned)jj * 16u);
+            RblV3 vj[NV];
+#pragma unroll
+            for (int v = 0; v < NV; ++v) vj[v] = RblV3{0.0, 0.0, 0.0};
+            rbl_pair_symv<WALL, true, true>(Pu, xi[a], yi[a], zi[a], Fi[a], cj.x, cj.y, cj.z, cj.f, ui[a], vj, flags, WK);
+            col_add(jj, vj);
           }
         }
       }
     }
     if (J > It00) {  // some owned row tile of the group precedes J: column sums exist.  Waves added in fixed order.
       __syncthreads();
-      for (int q = threadIdx.x; q < 3 * TS; q += TS * SW) {
-        const int l = q / 3, k = q - 3 * l;
-        double sum = sU[0][k][l];
+      for (int q = threadIdx.x; q < NV * 3 * TS; q += TS * SW) {
+        const int v = NV == 1 ? 0 : q / (3 * TS), rem = q - v * 3 * TS, l = rem / 3, k = rem - 3 * l;
+        double sum = sU[0][v][k][l];
 #pragma unroll
-        for (int w = 1; w < SW; ++w) sum += sU[w][k][l];
-        slabJ[sym_idxJ(L, g, 0, (long)J * TS + l) + k] = sum;
+        for (int w = 1; w < SW; ++w) sum += sU[w][v][k][l];
+        slabJ[sym_idxJ(L, g, v, (long)J * TS + l) + k] = sum;
       }
     }
   }
-  if (wlive && c * C + C > It0) {   // this wave swept at least one tile of the chunk: its row sums (k_reduce_sym reads chunks >= It0 / C)
-#pragma unroll
-    for (int a = 0; a < NI; ++a) {
-      if (It0 + a < T) {
-        double *p = slabI + sym_idxI(L, c, 0, (long)(It0 + a) * TS + lane);
-        p[0] = uix[a]; p[1] = uiy[a]; p[2] = uiz[a];
-      }
-    }
-  }
+  // this wave swept at least one tile of the chunk: its row sums (k_reduce_sym reads chunks >= It0 / C)
+  if (wlive && c * C + C > It0) sym_store_rows<NI, NV>(slabI, L, c, It0, lane, ui);
   RBL_WT_END(unit)
   };
   if (!queue) {
@@ -577,13 +702,16 @@ __global__ __launch_bounds__(TS *SW, (WALL && NI == 2 && SW > 1 && PREC == 0) ? 
 //     hides the staging loads and the fp64 latency chain of a unit that lasts only 5 us of issue;
 //   * the column sums M_ji F_i stay in VGPRs and ROTATE with the column index: at step s lane l pairs its row with column
 //     (l + s) & 63, so the accumulator of that column moves one lane down per step -- `v_mov_b32_dpp wave_rol:1`, six dword
-//     moves, folded into the pair's own FMA chain (the rotated sum is the addend).  The three ds_add_f64 per step of the
-//     LDS form (24 of its 47 LDS clocks, as much LDS time as VALU time at one row per lane) are gone, and after 64 steps
+//     moves per vector, folded into the pair's own FMA chain (the rotated sum is the addend).  The three ds_add_f64 per step and
+//     vector of the LDS form (24 of its 47 LDS clocks, as much LDS time as VALU time at one row per lane; with two vectors the
+//     one-row LDS form is LDS-bound on them: 11 LDS instructions per pair step) are gone, and after 64 steps
 //     every accumulator is back in its own lane: the 64 sums go to the slab straight from registers;
 //   * only the existing units are launched (closed-form index -> (row tile, chunk)), never the dead half of the rectangle.
 // Measured at cfg 2 (tools/bench_midsize.py, one box, alternating): 70.1 us per product against 73.9-75.4 (-6 %); PMC passes of both
 // kernels in profiles/r04_cfg2_kernel_pmc.md.
 // Sums per column are formed in step order, like the LDS atomics before them: bitwise reproducible run to run.
+// (1, 2 or 3 of the three components through ds_add_f64 instead of the rotation -- the DPP moves are VALU work, the atomics LDS work --
+// measured 72.9-74.5 us against 72.3: profiles/r04_midsize_variants.md)
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double wave_rol1(double v)            // lane l takes lane (l + 1) & 63's value
 {
@@ -609,9 +737,6 @@ __host__ __device__ __forceinline__ long symw_prefix(int e, int C, int nch)
 #ifndef RBL_SYMW_UNROLL
 #define RBL_SYMW_UNROLL 2
 #endif
-#ifndef RBL_SYMW_LDSACC
-#define RBL_SYMW_LDSACC 0         // column-sum components kept in LDS (atomics) instead of rotating registers
-#endif
 #ifndef RBL_SYMW_IW
 #define RBL_SYMW_IW 4             // independent waves (= work units in flight) per workgroup
 #endif
@@ -621,6 +746,14 @@ __host__ __device__ __forceinline__ long symw_prefix(int e, int C, int nch)
 #ifndef RBL_SYMW2_WAVES_WALL
 #define RBL_SYMW2_WAVES_WALL 3
 #endif
+#ifndef RBL_SYMW2V_WAVES
+#define RBL_SYMW2V_WAVES(WALL, NI) ((NI) == 2 ? ((WALL) ? 2 : 3) : ((WALL) ? 3 : 4))   // two vectors
+#endif
+constexpr int symw_min_waves(bool WALL, int NI, int NV)
+{
+  if (NV == 2) return RBL_SYMW2V_WAVES(WALL, NI);
+  return NI == 2 ? (WALL ? RBL_SYMW2_WAVES_WALL : RBL_SYMW2_WAVES_FREE) : (WALL ? RBL_SYMW_WAVES_WALL : RBL_SYMW_WAVES_FREE);
+}
 // live units of row super-tile e with NI rows per lane: chunks (NI e) / C .. nch - 1.  Closed form for NI = 1, and for NI = 2 with
 // C = 1 or C even (floor(2 e / C) = floor(e / (C / 2)); sym_geometry keeps C that way for these kernels)
 __host__ __device__ __forceinline__ long symw_prefix_ni(int e, int C, int nch, int ni)
@@ -630,22 +763,19 @@ __host__ __device__ __forceinline__ long symw_prefix_ni(int e, int C, int nch, i
   return symw_prefix(e, C / 2, nch);
 }
 // NI = 2 (round 4, 8 200 - 20 480 blobs and whatever sym_geometry sends here): a lane owns the same two row tiles as in
-// k_apply_M_sym<WALL, 2, 1, 0> and the SAME slabs come out; the column data read from LDS and the three travelling column sums
-// (six DPP moves per step) are shared by the two pair evaluations of a step.
-template <bool WALL, int NI, int IW>
-__global__ __launch_bounds__(TS *IW, NI == 2 ? (WALL ? RBL_SYMW2_WAVES_WALL : RBL_SYMW2_WAVES_FREE) : (WALL ? RBL_SYMW_WAVES_WALL : RBL_SYMW_WAVES_FREE))
-void k_apply_M_symw(const double *__restrict__ r, const double *__restrict__ F,
-                                                        double *__restrict__ slabI, double *__restrict__ slabJ, long N,
-                                                        SymLayout L, RblParams P, unsigned *err, long n_units)
+// k_apply_M_sym<WALL, 2, 1, 0> and the SAME slabs come out; the column data read from LDS and the 3 NV travelling column sums
+// (six DPP moves per step and vector) are shared by the two pair evaluations of a step.
+// NV = 2 (the Lanczos pair of mid-size systems, end of round 4): k_apply_M_sym<WALL, NI, 1, 0, 2>'s decomposition and slabs.
+template <bool WALL, int NI, int IW, int NV>
+__global__ __launch_bounds__(TS *IW, symw_min_waves(WALL, NI, NV))
+void k_apply_M_symw(const double *__restrict__ r, const double *__restrict__ F, double *__restrict__ slabI, double *__restrict__ slabJ,
+                    long N, SymLayout L, RblParams P, unsigned *err, long n_units)
 {
-  __shared__ double2_t sP0[IW][TS], sP1[IW][TS], sP2[IW][TS];   // (x,y) (z,fx) (fy,fz) of a wave's current column tile
-  // RBL_SYMW_LDSACC of the three column-sum components go through LDS atomics instead of the rotating registers: the DPP
-  // moves are VALU work, the atomics LDS work, and the kernel is bound by whichever pipe carries more (measured)
-  constexpr int NL = RBL_SYMW_LDSACC;
-  __shared__ double sU[IW][NL > 0 ? NL : 1][TS];
+  constexpr int NP = SYM_NP(NV);
+  __shared__ double2_t sP[NP][IW][TS];               // a wave's current column tile (sym_stage_col)
   const int lane = threadIdx.x & (TS - 1);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int T = L.T, C = L.C;
+  const int C = L.C;
   unsigned flags = 0;
   const RblParams Pu = unit_params(P);
   const RblWallK WK = rbl_wall_k_resident();
@@ -663,467 +793,74 @@ void k_apply_M_symw(const double *__restrict__ r, const double *__restrict__ F,
     c = (int)(u / L.rowsI);
     e = (int)((u - (long)c * L.rowsI + c) % L.rowsI);
   }
-  const int I = sym_row_of(e, L.i_first, L.i_step, 1);
-  const int It0 = NI * I;            // first row tile of the lane's NI
-  if (It0 >= T) return;
-  int J0 = c * C;
-  const int J1 = (J0 + C < T) ? J0 + C : T;
-  if (J0 < It0) J0 = It0;
-  if (J0 >= J1) return;
-  auto load_blob = [&](long idx, double &x, double &y, double &z, double &fx, double &fy, double &fz) {
-    if (idx < N) {
-      x = r[3 * idx]; y = r[3 * idx + 1]; z = r[3 * idx + 2];
-      double d = 1.0;
-      if (WALL) {
-        if (z < 0.0) flags |= RBL_FLAG_BELOW_WALL;
-        d = damp_of(P, z);
-      }
-      x *= P.inv_a; y *= P.inv_a; z *= P.inv_a;
-      fx = d * F[3 * idx]; fy = d * F[3 * idx + 1]; fz = d * F[3 * idx + 2];
-    } else {  // padding blob: zero force, far from everything (and from every other pad)
-      x = 1.0e15 * (double)(2 + (idx - N)); y = 0.0; z = 1.0; fx = 0.0; fy = 0.0; fz = 0.0;
-    }
-  };
-  double xi[NI], yi[NI], zi[NI], Fix[NI], Fiy[NI], Fiz[NI], uix[NI], uiy[NI], uiz[NI];
+  const int It0 = NI * sym_row_of(e, L.i_first, L.i_step, 1);   // first row tile of the lane's NI
+  int J0, J1;
+  if (!sym_unit_columns(L, c, It0, J0, J1)) return;
+  double xi[NI], yi[NI], zi[NI];
+  RblV3 Fi[NI][NV], ui[NI][NV];
 #pragma unroll
   for (int a = 0; a < NI; ++a) {
-    load_blob((long)(It0 + a) * TS + lane, xi[a], yi[a], zi[a], Fix[a], Fiy[a], Fiz[a]);   // (a row tile beyond T is padding: zero force)
-    uix[a] = 0.0; uiy[a] = 0.0; uiz[a] = 0.0;
+    sym_load_blob<WALL>(r, F, N, P, (long)(It0 + a) * TS + lane, xi[a], yi[a], zi[a], Fi[a], flags);   // (a row tile beyond T is padding: zero force)
+#pragma unroll
+    for (int v = 0; v < NV; ++v) ui[a][v] = RblV3{0.0, 0.0, 0.0};
   }
+  char *b[NP];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) b[k] = (char *)sP[k][wave];
   for (int J = J0; J < J1; ++J) {
     {
-      double xj, yj, zj, Fjx, Fjy, Fjz;
-      load_blob((long)J * TS + lane, xj, yj, zj, Fjx, Fjy, Fjz);
+      double xj, yj, zj;
+      RblV3 Fj[NV];
+      sym_load_blob<WALL>(r, F, N, P, (long)J * TS + lane, xj, yj, zj, Fj, flags);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");         // the previous tile's reads are done (in-order DS queue)
-      sP0[wave][lane] = (double2_t){xj, yj};
-      sP1[wave][lane] = (double2_t){zj, Fjx};
-      sP2[wave][lane] = (double2_t){Fjy, Fjz};
+      sym_stage_col<NV>(b, lane, xj, yj, zj, Fj);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
-    double ax = 0.0, ay = 0.0, az = 0.0;                            // column sums of column (lane + s) & 63, travelling
+    RblV3 acc[NV];                                                   // column sums of column (lane + s) & 63, travelling
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = RblV3{0.0, 0.0, 0.0};
+    auto sym_sweep = [&](auto nrows) {                               // rows 0 .. nrows - 1 of the lane against tile J, column sums rotating
+      unsigned off16 = (unsigned)lane * 16u;
+#pragma unroll RBL_SYMW_UNROLL
+      for (int s = 0; s < TS; ++s) {
+        const SymCol<NV> cj = sym_read_col<NV>(b, off16);
+        off16 = (off16 + 16u) & (unsigned)(TS * 16 - 16);
+        RblV3 vj[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) vj[v] = acc[v];
+#pragma unroll
+        for (int a = 0; a < decltype(nrows)::value; ++a)
+          rbl_pair_symv<WALL, true, true>(Pu, xi[a], yi[a], zi[a], Fi[a], cj.x, cj.y, cj.z, cj.f, ui[a], vj, flags, WK);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) acc[v] = RblV3{wave_rol1(vj[v].x), wave_rol1(vj[v].y), wave_rol1(vj[v].z)};
+      }
+    };
     if (J < It0 + NI) {              // J is one of the lane's own row tiles: the ordered diagonal sweep of that row tile ...
 #pragma unroll
       for (int a = 0; a < NI; ++a)
         if (J == It0 + a) {
 #pragma unroll 2
-          for (int jj = 0; jj < TS; ++jj) {
-            const double2_t pa = sP0[wave][jj], pb = sP1[wave][jj], pd = sP2[wave][jj];
-            rbl_pair_accum<WALL, true, true>(Pu, xi[a], yi[a], zi[a], pa.x, pa.y, pb.x, pb.y, pd.x, pd.y, jj == lane, uix[a], uiy[a], uiz[a], flags);
-          }
+          for (int jj = 0; jj < TS; ++jj)
+            sym_diag_pair<WALL, NV>(Pu, xi[a], yi[a], zi[a], sym_read_col<NV>(b, (unsigned)jj * 16u), jj == lane, ui[a], flags);
         }
       if (NI == 1 || J == It0) continue;                             // (no earlier row tile of the lane: no column sums)
-      // ... and (NI = 2, J = It0 + 1) the symmetric sweep of row tile It0 against it
-      unsigned off16 = (unsigned)lane * 16u;
-      const char *b0 = (const char *)sP0[wave], *b1 = (const char *)sP1[wave], *b2 = (const char *)sP2[wave];
-#pragma unroll 2
-      for (int s = 0; s < TS; ++s) {
-        const double2_t pa = *(const double2_t *)(b0 + off16), pb = *(const double2_t *)(b1 + off16), pd = *(const double2_t *)(b2 + off16);
-        off16 = (off16 + 16u) & (unsigned)(TS * 16 - 16);
-        double vx = ax, vy = ay, vz = az;
-        rbl_pair_sym<WALL, true, true>(Pu, xi[0], yi[0], zi[0], Fix[0], Fiy[0], Fiz[0], pa.x, pa.y, pb.x, pb.y, pd.x, pd.y, uix[0], uiy[0], uiz[0], vx, vy, vz, flags, WK);
-        ax = wave_rol1(vx); ay = wave_rol1(vy); az = wave_rol1(vz);
-      }
-      double *q = slabJ + sym_idxJ(L, e, 0, (long)J * TS + lane);
-      q[0] = ax; q[1] = ay; q[2] = az;
-      continue;
-    }
-    if (NL > 0) {
+      sym_sweep(std::integral_constant<int, 1>{});                   // ... and (NI = 2, J = It0 + 1) the symmetric sweep of row tile It0 against it
+    } else
+      sym_sweep(std::integral_constant<int, NI>{});
 #pragma unroll
-      for (int k = 0; k < NL; ++k) sU[wave][k][lane] = 0.0;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+    for (int v = 0; v < NV; ++v) {                                   // 64 rotations: lane l holds column l again
+      double *q = slabJ + sym_idxJ(L, e, v, (long)J * TS + lane);
+      q[0] = acc[v].x; q[1] = acc[v].y; q[2] = acc[v].z;
     }
-    unsigned off16 = (unsigned)lane * 16u;
-    const char *b0 = (const char *)sP0[wave], *b1 = (const char *)sP1[wave], *b2 = (const char *)sP2[wave];
-#pragma unroll RBL_SYMW_UNROLL
-    for (int s = 0; s < TS; ++s) {
-      const double2_t pa = *(const double2_t *)(b0 + off16), pb = *(const double2_t *)(b1 + off16), pd = *(const double2_t *)(b2 + off16);
-      const int jj = (int)(off16 >> 4);
-      off16 = (off16 + 16u) & (unsigned)(TS * 16 - 16);
-      double vx = (NL > 0) ? 0.0 : ax, vy = (NL > 1) ? 0.0 : ay, vz = (NL > 2) ? 0.0 : az;
-#pragma unroll
-      for (int a = 0; a < NI; ++a)
-        rbl_pair_sym<WALL, true, true>(Pu, xi[a], yi[a], zi[a], Fix[a], Fiy[a], Fiz[a], pa.x, pa.y, pb.x, pb.y, pd.x, pd.y, uix[a], uiy[a], uiz[a], vx, vy, vz, flags, WK);
-      if (NL > 0) __hip_atomic_fetch_add(&sU[wave][0][jj], vx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); else ax = wave_rol1(vx);
-      if (NL > 1) __hip_atomic_fetch_add(&sU[wave][NL > 1 ? 1 : 0][jj], vy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); else ay = wave_rol1(vy);
-      if (NL > 2) __hip_atomic_fetch_add(&sU[wave][NL > 2 ? 2 : 0][jj], vz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); else az = wave_rol1(vz);
-    }
-    if (NL > 0) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      ax = sU[wave][0][lane];
-      if (NL > 1) ay = sU[wave][NL > 1 ? 1 : 0][lane];
-      if (NL > 2) az = sU[wave][NL > 2 ? 2 : 0][lane];
-    }
-    double *q = slabJ + sym_idxJ(L, e, 0, (long)J * TS + lane);     // 64 rotations: lane l holds column l again
-    q[0] = ax; q[1] = ay; q[2] = az;
   }
-#pragma unroll
-  for (int a = 0; a < NI; ++a)
-    if (It0 + a < T) {
-      double *p_ = slabI + sym_idxI(L, c, 0, (long)(It0 + a) * TS + lane);
-      p_[0] = uix[a]; p_[1] = uiy[a]; p_[2] = uiz[a];
-    }
+  sym_store_rows<NI, NV>(slabI, L, c, It0, lane, ui);
   };
   // (A work queue -- a resident set of waves drawing units from one counter, or from eight per-XCD counters -- was measured and
   // dropped: 179 and 119 us per product at cfg 2 against 70 with one unit per wave, gpurun_out/r04f, r04g: a wave that sweeps
   // units back to back pays every unit's staging latency in series.)
   const long u = (long)blockIdx.x * IW + wave;
   if (u < n_units) sweep_unit(u);
-  if (flags) atomicOr(err, flags);
-}
-
-// ---------------------------------------------------------------------------
-// The wave-unit kernel for TWO force vectors (the Lanczos pair of mid-size systems, end of round 4): k_apply_M_sym2<WALL, NI, 1>'s
-// decomposition and slabs, k_apply_M_symw's execution -- a unit per wave, the SIX column sums of a step (three per vector) rotating
-// through the lanes in registers instead of six ds_add_f64 (the one-row form of the round-3 kernel is LDS-bound on them: 11 LDS
-// instructions per pair step).  Vector v of F / the slabs as in k_apply_M_sym2.
-// ---------------------------------------------------------------------------
-#ifndef RBL_SYMW2V_WAVES
-#define RBL_SYMW2V_WAVES(WALL, NI) ((NI) == 2 ? ((WALL) ? 2 : 3) : ((WALL) ? 3 : 4))
-#endif
-template <bool WALL, int NI, int IW>
-__global__ __launch_bounds__(TS *IW, RBL_SYMW2V_WAVES(WALL, NI))
-void k_apply_M_symw2v(const double *__restrict__ r, const double *__restrict__ F, double *__restrict__ slabI, double *__restrict__ slabJ,
-                      long N, SymLayout L, RblParams P, unsigned *err, long n_units)
-{
-  __shared__ double2_t sP0[IW][TS], sP1[IW][TS], sP2[IW][TS], sP3[IW][TS], sP4[IW][TS];   // (x,y) (z,f0x) (f0y,f0z) (f1x,f1y) (f1z,-)
-  const int lane = threadIdx.x & (TS - 1);
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int T = L.T, C = L.C;
-  const long n3 = 3 * N;
-  unsigned flags = 0;
-  const RblParams Pu = unit_params(P);
-  const RblWallK WK = rbl_wall_k_resident();
-  auto sweep_unit = [&](const long u) {
-  int e, c;
-  if (L.tri) {
-    int lo = 0, hi = L.rowsI;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (symw_prefix_ni(mid, C, L.nch, NI) <= u) lo = mid; else hi = mid;
-    }
-    e = lo; c = (NI * e) / C + (int)(u - symw_prefix_ni(e, C, L.nch, NI));
-  } else {
-    c = (int)(u / L.rowsI);
-    e = (int)((u - (long)c * L.rowsI + c) % L.rowsI);
-  }
-  const int I = sym_row_of(e, L.i_first, L.i_step, 1);
-  const int It0 = NI * I;
-  if (It0 >= T) return;
-  int J0 = c * C;
-  const int J1 = (J0 + C < T) ? J0 + C : T;
-  if (J0 < It0) J0 = It0;
-  if (J0 >= J1) return;
-  auto load_blob = [&](long idx, double &x, double &y, double &z, RblV3 &f0, RblV3 &f1) {
-    if (idx < N) {
-      x = r[3 * idx]; y = r[3 * idx + 1]; z = r[3 * idx + 2];
-      double d = 1.0;
-      if (WALL) {
-        if (z < 0.0) flags |= RBL_FLAG_BELOW_WALL;
-        d = damp_of(P, z);
-      }
-      x *= P.inv_a; y *= P.inv_a; z *= P.inv_a;
-      f0 = RblV3{d * F[3 * idx], d * F[3 * idx + 1], d * F[3 * idx + 2]};
-      f1 = RblV3{d * F[n3 + 3 * idx], d * F[n3 + 3 * idx + 1], d * F[n3 + 3 * idx + 2]};
-    } else {
-      x = 1.0e15 * (double)(2 + (idx - N)); y = 0.0; z = 1.0; f0 = RblV3{0.0, 0.0, 0.0}; f1 = RblV3{0.0, 0.0, 0.0};
-    }
-  };
-  double xi[NI], yi[NI], zi[NI];
-  RblV3 Fi0[NI], Fi1[NI], ui0[NI], ui1[NI];
-#pragma unroll
-  for (int a = 0; a < NI; ++a) {
-    load_blob((long)(It0 + a) * TS + lane, xi[a], yi[a], zi[a], Fi0[a], Fi1[a]);
-    ui0[a] = RblV3{0.0, 0.0, 0.0}; ui1[a] = RblV3{0.0, 0.0, 0.0};
-  }
-  for (int J = J0; J < J1; ++J) {
-    {
-      double xj, yj, zj; RblV3 g0, g1;
-      load_blob((long)J * TS + lane, xj, yj, zj, g0, g1);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      sP0[wave][lane] = (double2_t){xj, yj};
-      sP1[wave][lane] = (double2_t){zj, g0.x};
-      sP2[wave][lane] = (double2_t){g0.y, g0.z};
-      sP3[wave][lane] = (double2_t){g1.x, g1.y};
-      sP4[wave][lane] = (double2_t){g1.z, 0.0};
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-    RblV3 a0{0.0, 0.0, 0.0}, a1{0.0, 0.0, 0.0};                    // the six travelling column sums
-    const char *b0 = (const char *)sP0[wave], *b1 = (const char *)sP1[wave], *b2 = (const char *)sP2[wave],
-               *b3 = (const char *)sP3[wave], *b4 = (const char *)sP4[wave];
-    auto sym_sweep = [&](const int alo, const int ahi) {           // rows alo .. ahi - 1 of the lane against tile J, column sums rotating
-      unsigned off16 = (unsigned)lane * 16u;
-#pragma unroll 2
-      for (int s = 0; s < TS; ++s) {
-        const double2_t pa = *(const double2_t *)(b0 + off16), pb = *(const double2_t *)(b1 + off16), pd = *(const double2_t *)(b2 + off16),
-                        pe = *(const double2_t *)(b3 + off16), pf = *(const double2_t *)(b4 + off16);
-        off16 = (off16 + 16u) & (unsigned)(TS * 16 - 16);
-        RblV3 v0 = a0, v1 = a1;
-#pragma unroll
-        for (int a = 0; a < NI; ++a)
-          if (a >= alo && a < ahi)
-            rbl_pair_sym2<WALL, true, true>(Pu, xi[a], yi[a], zi[a], Fi0[a], Fi1[a], pa.x, pa.y, pb.x, RblV3{pb.y, pd.x, pd.y},
-                                            RblV3{pe.x, pe.y, pf.x}, ui0[a], ui1[a], v0, v1, flags, WK);
-        a0 = RblV3{wave_rol1(v0.x), wave_rol1(v0.y), wave_rol1(v0.z)};
-        a1 = RblV3{wave_rol1(v1.x), wave_rol1(v1.y), wave_rol1(v1.z)};
-      }
-    };
-    if (J < It0 + NI) {              // one of the lane's own row tiles: its ordered diagonal sweep, one vector after the other ...
-#pragma unroll
-      for (int a = 0; a < NI; ++a)
-        if (J == It0 + a) {
-#pragma unroll 2
-          for (int jj = 0; jj < TS; ++jj) {
-            const double2_t pa = sP0[wave][jj], pb = sP1[wave][jj], pd = sP2[wave][jj], pe = sP3[wave][jj], pf = sP4[wave][jj];
-            rbl_pair_accum<WALL, true, true>(Pu, xi[a], yi[a], zi[a], pa.x, pa.y, pb.x, pb.y, pd.x, pd.y, jj == lane,
-                                             ui0[a].x, ui0[a].y, ui0[a].z, flags);
-            rbl_pair_accum<WALL, true, true>(Pu, xi[a], yi[a], zi[a], pa.x, pa.y, pb.x, pe.x, pe.y, pf.x, jj == lane,
-                                             ui1[a].x, ui1[a].y, ui1[a].z, flags);
-          }
-        }
-      if (NI == 1 || J == It0) continue;
-      sym_sweep(0, 1);               // ... and (NI = 2, J = It0 + 1) row tile It0 against it
-    } else
-      sym_sweep(0, NI);
-    double *q0 = slabJ + sym_idxJ(L, e, 0, (long)J * TS + lane), *q1 = slabJ + sym_idxJ(L, e, 1, (long)J * TS + lane);
-    q0[0] = a0.x; q0[1] = a0.y; q0[2] = a0.z;
-    q1[0] = a1.x; q1[1] = a1.y; q1[2] = a1.z;
-  }
-#pragma unroll
-  for (int a = 0; a < NI; ++a)
-    if (It0 + a < T) {
-      double *p0 = slabI + sym_idxI(L, c, 0, (long)(It0 + a) * TS + lane), *p1 = slabI + sym_idxI(L, c, 1, (long)(It0 + a) * TS + lane);
-      p0[0] = ui0[a].x; p0[1] = ui0[a].y; p0[2] = ui0[a].z;
-      p1[0] = ui1[a].x; p1[1] = ui1[a].y; p1[2] = ui1[a].z;
-    }
-  };
-  const long u = (long)blockIdx.x * IW + wave;
-  if (u < n_units) sweep_unit(u);
-  if (flags) atomicOr(err, flags);
-}
-
-// ---------------------------------------------------------------------------
-// The symmetric product for TWO force vectors at once (F, out: [2][3N]): same work decomposition, the pair
-// coefficients are evaluated once for both (rbl_pair_sym2).  Slabs hold the two vectors back to back.
-// ---------------------------------------------------------------------------
-#ifndef RBL_SYM2_MIN_WAVES
-#define RBL_SYM2_MIN_WAVES 1      // waves per SIMD the two-vector wall instance is held to.  Measured with 3 (tools/build_variant.sh s2w3
-                                  // -DRBL_SYM2_MIN_WAVES=3: 168 VGPRs + 232 B of scratch instead of 235 VGPRs): Brownian step 608.6-609.1 ms
-                                  // against 608.9-609.3 -- no change, left at the compiler's choice
-#endif
-template <bool WALL, int NI, int SW, int PREC>
-__global__ __launch_bounds__(TS *SW, (WALL && NI == 2 && SW > 1 && PREC == 0) ? RBL_SYM2_MIN_WAVES : 1) void k_apply_M_sym2(const double *__restrict__ r, const double *__restrict__ F,
-                                                         double *__restrict__ slabI, double *__restrict__ slabJ, long N,
-                                                         SymLayout L, RblParams P, unsigned *err,
-                                                         const unsigned char *__restrict__ farmap, unsigned *queue)
-{
-  static_assert(PREC == 0 || NI == 2, "the packed single-precision sweep carries the two rows of a lane");
-  __shared__ double2_t sP0[TS], sP1[TS], sP2[TS], sP3[TS], sP4[TS];  // (x,y) (z,f0x) (f0y,f0z) (f1x,f1y) (f1z,-)
-  __shared__ double sU[SW][2][3][TS];
-  __shared__ float sPf[PREC ? 9 : 1][TS];           // relaxed product: x y z f0 f1 in single precision, origin-relative
-  const int lane = threadIdx.x & (TS - 1);
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int T = L.T, C = L.C;
-  const long n3 = 3 * N;
-  unsigned flags = 0;
-  const RblParams Pu = unit_params(P);
-  const RblWallK WK = rbl_wall_k_resident();
-  __shared__ double sO[3];                          // relaxed product: origin = first blob of the j tile (see k_apply_M_sym)
-  auto sweep_unit = [&](const int c, const int g) {     // one work unit (see k_apply_M_sym)
-  const int It00 = NI * sym_row_of(SW * g, L.i_first, L.i_step, SW);
-  if (It00 >= T) return;
-  int J0 = c * C;
-  const int J1 = (J0 + C < T) ? J0 + C : T;
-  if (J0 < It00) J0 = It00;
-  if (J0 >= J1) return;
-  const int e = SW * g + wave;
-  const int I = sym_row_of(e, L.i_first, L.i_step, SW);
-  const bool wlive = e < L.rowsI && NI * I < T;
-  const int It0 = wlive ? NI * I : (1 << 30);
-  auto load_blob = [&](long idx, double &x, double &y, double &z, RblV3 &f0, RblV3 &f1) {
-    if (idx < N) {
-      x = r[3 * idx]; y = r[3 * idx + 1]; z = r[3 * idx + 2];
-      double d = 1.0;
-      if (WALL) {
-        if (z < 0.0) flags |= RBL_FLAG_BELOW_WALL;
-        d = damp_of(P, z);
-      }
-      x *= P.inv_a; y *= P.inv_a; z *= P.inv_a;
-      f0 = RblV3{d * F[3 * idx], d * F[3 * idx + 1], d * F[3 * idx + 2]};
-      f1 = RblV3{d * F[n3 + 3 * idx], d * F[n3 + 3 * idx + 1], d * F[n3 + 3 * idx + 2]};
-    } else {
-      x = 1.0e15 * (double)(2 + (idx - N)); y = 0.0; z = 1.0;
-      f0 = RblV3{0.0, 0.0, 0.0}; f1 = f0;
-    }
-  };
-  double xi[NI], yi[NI], zi[NI];
-  RblV3 Fi0[NI], Fi1[NI], ui0[NI], ui1[NI];
-#pragma unroll
-  for (int a = 0; a < NI; ++a) {
-    load_blob(wlive ? (long)(It0 + a) * TS + lane : N + 1 + a, xi[a], yi[a], zi[a], Fi0[a], Fi1[a]);
-    ui0[a] = RblV3{0.0, 0.0, 0.0}; ui1[a] = ui0[a];
-  }
-  rbl_f2 F0x = {0, 0}, F0y = {0, 0}, F0z = {0, 0}, F1x = {0, 0}, F1y = {0, 0}, F1z = {0, 0};
-  if (PREC) {
-    const int a1 = NI - 1;
-    F0x = (rbl_f2){(float)Fi0[0].x, (float)Fi0[a1].x}; F0y = (rbl_f2){(float)Fi0[0].y, (float)Fi0[a1].y}; F0z = (rbl_f2){(float)Fi0[0].z, (float)Fi0[a1].z};
-    F1x = (rbl_f2){(float)Fi1[0].x, (float)Fi1[a1].x}; F1y = (rbl_f2){(float)Fi1[0].y, (float)Fi1[a1].y}; F1z = (rbl_f2){(float)Fi1[0].z, (float)Fi1[a1].z};
-  }
-  for (int J = J0; J < J1; ++J) {
-    const long j = (long)J * TS + lane;
-    double xj = 0, yj = 0, zj = 0;
-    RblV3 Fj0{0, 0, 0}, Fj1{0, 0, 0};
-    if (wave == 0) load_blob(j, xj, yj, zj, Fj0, Fj1);
-    const bool sweeps = J >= It0;
-    const int fmap = (sweeps && farmap) ? __builtin_amdgcn_readfirstlane((int)farmap[(size_t)I * (size_t)T + J]) : 0;
-    const bool far_tile = fmap != 0;
-    __syncthreads();
-    double ox = 0.0, oy = 0.0, oz = 0.0;
-    if (PREC && wave == 0) {
-      ox = sym_first_lane(xj); oy = sym_first_lane(yj); oz = sym_first_lane(zj);
-      if (lane == 0) { sO[0] = ox; sO[1] = oy; sO[2] = oz; }
-    }
-    if (wave == 0) {
-      sP0[lane] = (double2_t){xj, yj};
-      sP1[lane] = (double2_t){zj, Fj0.x};
-      sP2[lane] = (double2_t){Fj0.y, Fj0.z};
-      sP3[lane] = (double2_t){Fj1.x, Fj1.y};
-      sP4[lane] = (double2_t){Fj1.z, 0.0};
-      if (PREC) {
-        sPf[0][lane] = (float)(xj - ox); sPf[PREC ? 1 : 0][lane] = (float)(yj - oy); sPf[PREC ? 2 : 0][lane] = (float)(zj - oz);
-        sPf[PREC ? 3 : 0][lane] = (float)Fj0.x; sPf[PREC ? 4 : 0][lane] = (float)Fj0.y; sPf[PREC ? 5 : 0][lane] = (float)Fj0.z;
-        sPf[PREC ? 6 : 0][lane] = (float)Fj1.x; sPf[PREC ? 7 : 0][lane] = (float)Fj1.y; sPf[PREC ? 8 : 0][lane] = (float)Fj1.z;
-      }
-    }
-#pragma unroll
-    for (int v = 0; v < 2; ++v)
-#pragma unroll
-      for (int d = 0; d < 3; ++d) sU[wave][v][d][lane] = 0.0;
-    __syncthreads();
-    auto pair_step = [&](int jj, int a, auto nearchk) {
-      const double2_t pa = sP0[jj], pb = sP1[jj], pd = sP2[jj], pe = sP3[jj], pf = sP4[jj];
-      RblV3 v0{0.0, 0.0, 0.0}, v1{0.0, 0.0, 0.0};
-      rbl_pair_sym2<WALL, true, decltype(nearchk)::value>(Pu, xi[a], yi[a], zi[a], Fi0[a], Fi1[a], pa.x, pa.y, pb.x,
-                                                          RblV3{pb.y, pd.x, pd.y}, RblV3{pe.x, pe.y, pf.x}, ui0[a],
-                                                          ui1[a], v0, v1, flags, WK);
-      __hip_atomic_fetch_add(&sU[wave][0][0][jj], v0.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(&sU[wave][0][1][jj], v0.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(&sU[wave][0][2][jj], v0.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(&sU[wave][1][0][jj], v1.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(&sU[wave][1][1][jj], v1.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(&sU[wave][1][2][jj], v1.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    };
-    if (!sweeps) {
-    } else if (PREC && (fmap & 2) && J >= It0 + NI) {   // relaxed product: packed single precision, coefficients once for both vectors
-      const double qx = sO[0], qy = sO[1], qz = sO[2];
-      const int a1 = NI - 1;
-      const rbl_f2 xi2 = {(float)(xi[0] - qx), (float)(xi[a1] - qx)}, yi2 = {(float)(yi[0] - qy), (float)(yi[a1] - qy)},
-                   zi2 = {(float)(zi[0] - qz), (float)(zi[a1] - qz)};
-      const float two_z0 = (float)(2.0 * qz);
-      rbl_f2 a0x = {0, 0}, a0y = {0, 0}, a0z = {0, 0}, a1x = {0, 0}, a1y = {0, 0}, a1z = {0, 0};
-#pragma unroll 2
-      for (int s = 0; s < TS; ++s) {
-        const int jj = (lane + s) & (TS - 1);
-        const RblPkCoef K = rbl_pk_coef<WALL>(xi2, yi2, zi2, sPf[0][jj], sPf[PREC ? 1 : 0][jj], sPf[PREC ? 2 : 0][jj], two_z0);
-        rbl_f2 v0x = {0, 0}, v0y = {0, 0}, v0z = {0, 0}, v1x = {0, 0}, v1y = {0, 0}, v1z = {0, 0};
-        rbl_pk_apply<WALL, false>(K, rbl_splat(sPf[PREC ? 3 : 0][jj]), rbl_splat(sPf[PREC ? 4 : 0][jj]), rbl_splat(sPf[PREC ? 5 : 0][jj]), a0x, a0y, a0z);
-        rbl_pk_apply<WALL, false>(K, rbl_splat(sPf[PREC ? 6 : 0][jj]), rbl_splat(sPf[PREC ? 7 : 0][jj]), rbl_splat(sPf[PREC ? 8 : 0][jj]), a1x, a1y, a1z);
-        rbl_pk_apply<WALL, true>(K, F0x, F0y, F0z, v0x, v0y, v0z);
-        rbl_pk_apply<WALL, true>(K, F1x, F1y, F1z, v1x, v1y, v1z);
-        __hip_atomic_fetch_add(&sU[wave][0][0][jj], (double)(v0x.x + v0x.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&sU[wave][0][1][jj], (double)(v0y.x + v0y.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&sU[wave][0][2][jj], (double)(v0z.x + v0z.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&sU[wave][1][0][jj], (double)(v1x.x + v1x.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&sU[wave][1][1][jj], (double)(v1y.x + v1y.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&sU[wave][1][2][jj], (double)(v1z.x + v1z.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-      ui0[0].x += (double)a0x.x; ui0[0].y += (double)a0y.x; ui0[0].z += (double)a0z.x;
-      ui0[NI - 1].x += (double)a0x.y; ui0[NI - 1].y += (double)a0y.y; ui0[NI - 1].z += (double)a0z.y;
-      ui1[0].x += (double)a1x.x; ui1[0].y += (double)a1y.x; ui1[0].z += (double)a1z.x;
-      ui1[NI - 1].x += (double)a1x.y; ui1[NI - 1].y += (double)a1y.y; ui1[NI - 1].z += (double)a1z.y;
-    } else if (J >= It0 + NI) {
-      // both rows of the lane meet column jj: their contributions to its sums are added in registers (the pair routine accumulates
-      // onto what it is handed: no instruction more) and go to LDS once -- 6 atomics a column instead of 12; at two waves a SIMD the
-      // two-vector kernel waits for its LDS 5.7 x as long as the one-vector one (profiles/r05_two_vector_pmc.md)
-      auto sweep = [&](auto nearchk) {
-#pragma unroll 2
-        for (int s = 0; s < TS; ++s) {
-          const int jj = (lane + s) & (TS - 1);
-          const double2_t pa = sP0[jj], pb = sP1[jj], pd = sP2[jj], pe = sP3[jj], pf = sP4[jj];
-          RblV3 v0{0.0, 0.0, 0.0}, v1{0.0, 0.0, 0.0};
-#pragma unroll
-          for (int a = 0; a < NI; ++a)
-            rbl_pair_sym2<WALL, true, decltype(nearchk)::value>(Pu, xi[a], yi[a], zi[a], Fi0[a], Fi1[a], pa.x, pa.y, pb.x,
-                                                                RblV3{pb.y, pd.x, pd.y}, RblV3{pe.x, pe.y, pf.x}, ui0[a],
-                                                                ui1[a], v0, v1, flags, WK);
-          __hip_atomic_fetch_add(&sU[wave][0][0][jj], v0.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&sU[wave][0][1][jj], v0.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&sU[wave][0][2][jj], v0.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&sU[wave][1][0][jj], v1.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&sU[wave][1][1][jj], v1.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(&sU[wave][1][2][jj], v1.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      };
-      if (far_tile) sweep(std::false_type{});
-      else sweep(std::true_type{});
-    } else {
-#pragma unroll
-      for (int a = 0; a < NI; ++a) {
-        if (J == It0 + a) {       // diagonal tile: ordered pairs with the self term, one vector after the other
-          for (int jj = 0; jj < TS; ++jj) {
-            const double2_t pa = sP0[jj], pb = sP1[jj], pd = sP2[jj], pe = sP3[jj], pf = sP4[jj];
-            rbl_pair_accum<WALL, true, true>(Pu, xi[a], yi[a], zi[a], pa.x, pa.y, pb.x, pb.y, pd.x, pd.y, jj == lane,
-                                             ui0[a].x, ui0[a].y, ui0[a].z, flags);
-            rbl_pair_accum<WALL, true, true>(Pu, xi[a], yi[a], zi[a], pa.x, pa.y, pb.x, pe.x, pe.y, pf.x, jj == lane,
-                                             ui1[a].x, ui1[a].y, ui1[a].z, flags);
-          }
-        } else if (J > It0 + a) {
-          for (int s = 0; s < TS; ++s) pair_step((lane + s) & (TS - 1), a, std::true_type{});
-        }
-      }
-    }
-    if (J > It00) {
-      __syncthreads();
-      const int t = threadIdx.x;
-      for (int q = t; q < 2 * 3 * TS; q += TS * SW) {
-        const int v = q / (3 * TS), rem = q - v * 3 * TS, l = rem / 3, k = rem - 3 * l;
-        double sum = sU[0][v][k][l];
-#pragma unroll
-        for (int w = 1; w < SW; ++w) sum += sU[w][v][k][l];
-        slabJ[sym_idxJ(L, g, v, (long)J * TS + l) + k] = sum;
-      }
-    }
-  }
-  if (wlive && c * C + C > It0) {
-#pragma unroll
-    for (int a = 0; a < NI; ++a) {
-      if (It0 + a < T) {
-        double *p = slabI + sym_idxI(L, c, 0, (long)(It0 + a) * TS + lane);
-        p[0] = ui0[a].x; p[1] = ui0[a].y; p[2] = ui0[a].z;
-        double *p1 = slabI + sym_idxI(L, c, 1, (long)(It0 + a) * TS + lane);
-        p1[0] = ui1[a].x; p1[1] = ui1[a].y; p1[2] = ui1[a].z;
-      }
-    }
-  }
-  };
-  if (!queue) {
-    sweep_unit((int)blockIdx.y, (int)((blockIdx.x + blockIdx.y) % gridDim.x));
-  } else {                                              // work queue, as in k_apply_M_sym
-    __shared__ unsigned s_unit;
-    const unsigned n_units = (unsigned)L.rowsG * (unsigned)L.nch;
-    for (;;) {
-      __syncthreads();
-      if (threadIdx.x == 0) s_unit = atomicAdd(queue, 1u);
-      __syncthreads();
-      const unsigned u = s_unit;
-      if (u >= n_units) break;
-      const int by = (int)(u / (unsigned)L.rowsG), bx = (int)(u - (unsigned)by * (unsigned)L.rowsG);
-      sweep_unit(L.nch - 1 - by, (bx + by) % L.rowsG);
-    }
-  }
   if (flags) atomicOr(err, flags);
 }
 
@@ -2038,22 +1775,24 @@ static void launch_sym(hipStream_t st, const RblParams &P, const double *d_F, co
     hipLaunchKernelGGL(k_tile_far, dim3((unsigned)((T + 255) / 256), (unsigned)nsup), dim3(256), 0, st,
                        (const double *)bbox, T, NI, farmap, queue, gap_ratio);
   }
-  constexpr int PR = (NI == 2) ? 1 : 0;      // the relaxed form exists for two rows per lane
+  auto launch = [&](auto prec, auto nv) {
+    hipLaunchKernelGGL((k_apply_M_sym<WALL, NI, SW, decltype(prec)::value, decltype(nv)::value>), grid, block, 0, st, d_r, d_F, slabI, slabJ,
+                       (long)n_blobs, L, P, d_err, (const unsigned char *)farmap, queue);
+  };
+  using fp64 = std::integral_constant<int, 0>;
+  using packed = std::integral_constant<int, (NI == 2) ? 1 : 0>;      // the relaxed form exists for two rows per lane
+  const bool rel = relaxed && NI == 2;
   if (nrhs == 2) {
     if constexpr (NI <= 2) {                 // (four rows per lane: one vector only -- kSymRows never routes two here)
-      if (relaxed && NI == 2)
-        hipLaunchKernelGGL((k_apply_M_sym2<WALL, NI, SW, PR>), grid, block, 0, st, d_r, d_F, slabI, slabJ, (long)n_blobs, L, P,
-                           d_err, (const unsigned char *)farmap, queue);
-      else
-        hipLaunchKernelGGL((k_apply_M_sym2<WALL, NI, SW, 0>), grid, block, 0, st, d_r, d_F, slabI, slabJ, (long)n_blobs, L, P,
-                           d_err, (const unsigned char *)farmap, queue);
+      using two = std::integral_constant<int, 2>;
+      if (rel) launch(packed{}, two{});
+      else launch(fp64{}, two{});
     }
-  } else if (relaxed && NI == 2)
-    hipLaunchKernelGGL((k_apply_M_sym<WALL, NI, SW, PR>), grid, block, 0, st, d_r, d_F, slabI, slabJ, (long)n_blobs, L, P,
-                       d_err, (const unsigned char *)farmap, queue);
-  else
-    hipLaunchKernelGGL((k_apply_M_sym<WALL, NI, SW, 0>), grid, block, 0, st, d_r, d_F, slabI, slabJ, (long)n_blobs, L, P,
-                       d_err, (const unsigned char *)farmap, queue);
+  } else {
+    using one = std::integral_constant<int, 1>;
+    if (rel) launch(packed{}, one{});
+    else launch(fp64{}, one{});
+  }
   hipLaunchKernelGGL(k_reduce_sym<WALL>, g2, b2, 0, st, slabI, slabJ, d_r, d_out, (long)n_blobs, L, P, d_err, nrhs == 1 ? fuse : RblSaddleFuse());
 }
 
@@ -2076,20 +1815,15 @@ template <int NI, int SW> void row_launch_sym(const SymArgs &a)
   else launch_sym<false, NI, SW>(a.st, *a.P, a.d_F, a.d_r, a.n_blobs, a.d_out, a.slabI, a.slabJ, *a.L, a.d_err, a.relaxed, a.n_cu, a.use_queue, a.gap_ratio, *a.fuse);
 }
 
-// wave-owned units (k_apply_M_symw / k_apply_M_symw2v): same slabs, same reduction
+// wave-owned units (k_apply_M_symw, NRHS vectors): same slabs, same reduction
 template <int NI, int NRHS> void row_launch_symw(const SymArgs &a)
 {
   constexpr int IW = RBL_SYMW_IW;
   const SymLayout &L = *a.L;
   const long n_units = L.tri ? (NI == 2 || NRHS == 2 ? symw_prefix_ni(L.rowsI, L.C, L.nch, NI) : symw_prefix(L.rowsI, L.C, L.nch)) : (long)L.rowsI * L.nch;
   const dim3 grid((unsigned)((n_units + IW - 1) / IW)), block(TS * IW);
-  if (NRHS == 2) {
-    if (a.wall) hipLaunchKernelGGL((k_apply_M_symw2v<true, NI, IW>), grid, block, 0, a.st, a.d_r, a.d_F, a.slabI, a.slabJ, (long)a.n_blobs, L, *a.P, a.d_err, n_units);
-    else hipLaunchKernelGGL((k_apply_M_symw2v<false, NI, IW>), grid, block, 0, a.st, a.d_r, a.d_F, a.slabI, a.slabJ, (long)a.n_blobs, L, *a.P, a.d_err, n_units);
-  } else {
-    if (a.wall) hipLaunchKernelGGL((k_apply_M_symw<true, NI, IW>), grid, block, 0, a.st, a.d_r, a.d_F, a.slabI, a.slabJ, (long)a.n_blobs, L, *a.P, a.d_err, n_units);
-    else hipLaunchKernelGGL((k_apply_M_symw<false, NI, IW>), grid, block, 0, a.st, a.d_r, a.d_F, a.slabI, a.slabJ, (long)a.n_blobs, L, *a.P, a.d_err, n_units);
-  }
+  if (a.wall) hipLaunchKernelGGL((k_apply_M_symw<true, NI, IW, NRHS>), grid, block, 0, a.st, a.d_r, a.d_F, a.slabI, a.slabJ, (long)a.n_blobs, L, *a.P, a.d_err, n_units);
+  else hipLaunchKernelGGL((k_apply_M_symw<false, NI, IW, NRHS>), grid, block, 0, a.st, a.d_r, a.d_F, a.slabI, a.slabJ, (long)a.n_blobs, L, *a.P, a.d_err, n_units);
   const int64_t n = 3 * a.n_blobs;
   dim3 g2((unsigned)((n + 63) / 64), (unsigned)NRHS), b2(64 * RG);
   const RblSaddleFuse fuse = NRHS == 1 ? *a.fuse : RblSaddleFuse();
@@ -2176,7 +1910,8 @@ void rbl_apply_M_sym_kernel_name(int64_t n_blobs, int n_cu, int i_step, int nrhs
   if (len) out[0] = 0;
   if (!row) return;
   if (row->wave_units) { std::snprintf(out, len, row->name, w); return; }
-  // k_apply_M_sym / k_apply_M_sym2: librbl.isa.json names them <wall, NI> (one or four waves per workgroup: the same sweep)
+  // workgroup-owned units: librbl.isa.json names the one-vector instances <wall, NI> (one or four waves per workgroup: the same
+  // sweep), the two-vector ones with a 2 after `sym` and the waves per workgroup
   if (nrhs == 2) std::snprintf(out, len, "k_apply_M_sym2<%s,%d,%d>", w, L.NI, L.SW);
   else std::snprintf(out, len, "k_apply_M_sym<%s,%d>", w, L.NI);
 }

@@ -8,7 +8,7 @@
 //    oracle.  Used by the dense-build kernel, which is HBM-write bound, so the
 //    extra ALU work is free.
 //
-//  * rbl_pair_accum() / rbl_pair_sym() / rbl_pair_block_fast():  the fast form used by the matvec
+//  * rbl_pair_accum() / rbl_pair_symv() / rbl_pair_block_fast():  the fast form used by the matvec
 //    kernels, which are fp64-VALU bound: ONE v_rsq_f64 + a 3rd-order Newton step per distance, no
 //    division, h_hat eliminated algebraically ( h_hat ez = z_j/R, (1-h_hat) ez = z_i/R ), the wall
 //    "facts" as Horner polynomials (rbl_wall_coeffs) and the block applied in vector form
@@ -192,24 +192,28 @@ __device__ __forceinline__ void rbl_pair_accum(const RblParams &P, double xi, do
 }
 
 // ---------------------------------------------------------------------------
-// Symmetric pair (i != j): evaluates the scalar coefficients ONCE and applies the
-// block in both directions,
-//     U_i += M_ij F_j            (accumulated into uix,uiy,uiz)
-//     U_j += M_ji F_i            (accumulated into ujx,ujy,ujz; caller adds it to j)
+// Symmetric pair (i != j) for NV force vectors at once: evaluates the scalar coefficients ONCE and applies the
+// block in both directions to every vector,
+//     U_i[v] += M_ij F_j[v]      (accumulated into ui[v])
+//     U_j[v] += M_ji F_i[v]      (accumulated into uj[v]; caller adds it to j)
 // M_ji = M_ij^T holds exactly for the RPY part and, for the wall part, through the
 // role swap g <-> k (h = z_i instead of z_j): fact1, fact2, the e_z-part of fact3
 // and the h-free part of fact5 are shared.  ~78 fp64 instructions per unordered wall pair
 // (measured in the ISA of k_apply_M_sym<true,2>) vs 2 x ~68 for two ordered evaluations.
+// NV = 2: the coefficients (~60 of the ~84 fp64 instructions of a wall pair) are shared, only the 20-FMA application
+// is repeated.  Used for the two Brownian increments of the stochastic step (lock-step Lanczos) and for 2-3
+// simultaneous vectors in general.
 // ---------------------------------------------------------------------------
 // NEARCHK = false: the caller has proved (tile bounding boxes) that no pair of this sweep is closer than 2a,
 // the overlap branch and its per-pair compare are compiled out.
-template <bool WALL, bool UNIT = false, bool NEARCHK = true>
-__device__ __forceinline__ void rbl_pair_sym(const RblParams &P, double xi, double yi, double zi,
-                                             double Fix, double Fiy, double Fiz, double xj,
-                                             double yj, double zj, double Fjx, double Fjy,
-                                             double Fjz, double &uix, double &uiy, double &uiz,
-                                             double &ujx, double &ujy, double &ujz,
-                                             unsigned &flags, const RblWallK &K = rbl_wall_k_literal())
+struct RblV3 {
+  double x, y, z;
+};
+
+template <bool WALL, bool UNIT = false, bool NEARCHK = true, int NV = 1>
+__device__ __forceinline__ void rbl_pair_symv(const RblParams &P, double xi, double yi, double zi, const RblV3 (&Fi)[NV],
+                                              double xj, double yj, double zj, const RblV3 (&Fj)[NV], RblV3 (&ui)[NV],
+                                              RblV3 (&uj)[NV], unsigned &flags, const RblWallK &K = rbl_wall_k_literal())
 {
   const double dx = xi - xj, dy = yi - yj, dz = zi - zj;
   const double q = __builtin_fma(dy, dy, dx * dx);
@@ -230,78 +234,21 @@ __device__ __forceinline__ void rbl_pair_sym(const RblParams &P, double xi, doub
     if (r2 < P.tiny2) flags |= RBL_FLAG_OVERLAP;
   }
   if (!WALL) {   // free space: the vector form A F + Bc (d.F) d is cheaper than forming the block
-    const double q2j = __builtin_fma(dy, Fjy, dx * Fjx);
-    const double q2i = __builtin_fma(dy, Fiy, dx * Fix);
-    const double tBj = Bc * __builtin_fma(dz, Fjz, q2j);
-    const double tBi = Bc * __builtin_fma(dz, Fiz, q2i);
-    uix = __builtin_fma(A, Fjx, __builtin_fma(tBj, dx, uix));
-    uiy = __builtin_fma(A, Fjy, __builtin_fma(tBj, dy, uiy));
-    uiz = __builtin_fma(A, Fjz, __builtin_fma(tBj, dz, uiz));
-    ujx = __builtin_fma(A, Fix, __builtin_fma(tBi, dx, ujx));
-    ujy = __builtin_fma(A, Fiy, __builtin_fma(tBi, dy, ujy));
-    ujz = __builtin_fma(A, Fiz, __builtin_fma(tBi, dz, ujz));
-    return;
-  }
-
-  // Wall: coefficients for ONE direction (h = z_j); M_ji = M_ij^T exactly, so U_j += M_ij^T F_i reuses
-  // them.  Vector form: 20 FMAs for both directions instead of forming nine entries.
-  double cF, beta, gxz, gzx, mzz;
-  rbl_wall_coeffs<UNIT>(P, dz, zi, zj, q, r2, A, Bc, cF, beta, gxz, gzx, mzz, K);
-  // U_i += M F_j
-  const double pj = __builtin_fma(dy, Fjy, dx * Fjx);
-  const double lj = __builtin_fma(beta, pj, gxz * Fjz);
-  uix = __builtin_fma(cF, Fjx, __builtin_fma(lj, dx, uix));
-  uiy = __builtin_fma(cF, Fjy, __builtin_fma(lj, dy, uiy));
-  uiz = __builtin_fma(mzz, Fjz, __builtin_fma(gzx, pj, uiz));
-  // U_j += M^T F_i
-  const double pi = __builtin_fma(dy, Fiy, dx * Fix);
-  const double li = __builtin_fma(beta, pi, gzx * Fiz);
-  ujx = __builtin_fma(cF, Fix, __builtin_fma(li, dx, ujx));
-  ujy = __builtin_fma(cF, Fiy, __builtin_fma(li, dy, ujy));
-  ujz = __builtin_fma(mzz, Fiz, __builtin_fma(gxz, pi, ujz));
-}
-
-// ---------------------------------------------------------------------------
-// The same for TWO right-hand sides at once: the scalar coefficients (~60 of the ~84 fp64 instructions of
-// a wall pair) are shared, only the 20-FMA application is repeated.  Used for the two Brownian increments
-// of the stochastic step (lock-step Lanczos) and for 2-3 simultaneous vectors in general.
-// ---------------------------------------------------------------------------
-struct RblV3 {
-  double x, y, z;
-};
-
-template <bool WALL, bool UNIT = false, bool NEARCHK = true>
-__device__ __forceinline__ void rbl_pair_sym2(const RblParams &P, double xi, double yi, double zi, const RblV3 &Fi0,
-                                              const RblV3 &Fi1, double xj, double yj, double zj, const RblV3 &Fj0,
-                                              const RblV3 &Fj1, RblV3 &ui0, RblV3 &ui1, RblV3 &uj0, RblV3 &uj1,
-                                              unsigned &flags, const RblWallK &K = rbl_wall_k_literal())
-{
-  const double dx = xi - xj, dy = yi - yj, dz = zi - zj;
-  const double q = __builtin_fma(dy, dy, dx * dx);
-  const double r2 = __builtin_fma(dz, dz, q);
-  const double invr = rbl_rsqrt(r2);
-  const double invr2 = invr * invr;
-  const double s = UNIT ? invr : P.a * invr;
-  const double s3 = (s * s) * s;
-  double A = __builtin_fma(s3, 2.0 / 3.0, s);
-  double Bc = __builtin_fma(s3, -2.0, s) * invr2;
-  if (NEARCHK && __builtin_expect(__any(r2 < P.four_a2), 0)) {
-    const double rr = r2 * invr;
-    const bool far = r2 >= P.four_a2;
-    A = far ? A : __builtin_fma(rr, P.c_near_A, 4.0 / 3.0);
-    Bc = far ? Bc : invr * P.c_near_B;
-    if (r2 < P.tiny2) flags |= RBL_FLAG_OVERLAP;
-  }
-  if (!WALL) {
     auto app = [&](const RblV3 &F, RblV3 &u) {
       const double tB = Bc * __builtin_fma(dz, F.z, __builtin_fma(dy, F.y, dx * F.x));
       u.x = __builtin_fma(A, F.x, __builtin_fma(tB, dx, u.x));
       u.y = __builtin_fma(A, F.y, __builtin_fma(tB, dy, u.y));
       u.z = __builtin_fma(A, F.z, __builtin_fma(tB, dz, u.z));
     };
-    app(Fj0, ui0); app(Fj1, ui1); app(Fi0, uj0); app(Fi1, uj1);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) app(Fj[v], ui[v]);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) app(Fi[v], uj[v]);
     return;
   }
+
+  // Wall: coefficients for ONE direction (h = z_j); M_ji = M_ij^T exactly, so U_j += M_ij^T F_i reuses
+  // them.  Vector form: 20 FMAs per vector for both directions instead of forming nine entries.
   double cF, beta, gxz, gzx, mzz;
   rbl_wall_coeffs<UNIT>(P, dz, zi, zj, q, r2, A, Bc, cF, beta, gxz, gzx, mzz, K);
   auto app = [&](const RblV3 &F, RblV3 &u, double g_lat, double g_z) {   // M F (g_lat = gxz, g_z = gzx) or M^T F (swapped)
@@ -311,8 +258,10 @@ __device__ __forceinline__ void rbl_pair_sym2(const RblParams &P, double xi, dou
     u.y = __builtin_fma(cF, F.y, __builtin_fma(l, dy, u.y));
     u.z = __builtin_fma(mzz, F.z, __builtin_fma(g_z, p, u.z));
   };
-  app(Fj0, ui0, gxz, gzx); app(Fj1, ui1, gxz, gzx);      // U_i += M F_j
-  app(Fi0, uj0, gzx, gxz); app(Fi1, uj1, gzx, gxz);      // U_j += M^T F_i
+#pragma unroll
+  for (int v = 0; v < NV; ++v) app(Fj[v], ui[v], gxz, gzx);      // U_i += M F_j
+#pragma unroll
+  for (int v = 0; v < NV; ++v) app(Fi[v], uj[v], gzx, gxz);      // U_j += M^T F_i
 }
 
 // ---------------------------------------------------------------------------

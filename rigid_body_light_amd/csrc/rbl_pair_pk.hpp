@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 
 // ---------------------------------------------------------------------------
-// RELAXED-precision form of rbl_pair_sym for far tile pairs (no overlap possible, i != j): the same algebra in packed
+// RELAXED-precision form of rbl_pair_symv for far tile pairs (no overlap possible, i != j): the same algebra in packed
 // single precision -- the two rows a lane owns travel in the two halves of 64-bit registers (v_pk_fma_f32: two pairs per
 // instruction), v_rsq_f32 needs no Newton step.  ~38 VALU instructions per unordered pair instead of ~75.
 // NOT used by default: an inexact Krylov method tolerates a product error of (tolerance / current residual), so the
@@ -65,7 +65,8 @@ __device__ __forceinline__ RblPkCoef rbl_pk_coef(rbl_f2 xi, rbl_f2 yi, rbl_f2 zi
   return K;
 }
 
-// u += M F  (TRANSPOSE = false) or u += M^T F (true) for the two rows' blocks
+// u += M F  (TRANSPOSE = false) or u += M^T F (true) for the two rows' blocks.  A symmetric pair is one rbl_pk_coef, then per force
+// vector U_i += M F_j (F_j splat over the two rows) and U_j += M^T F_i
 template <bool WALL, bool TRANSPOSE>
 __device__ __forceinline__ void rbl_pk_apply(const RblPkCoef &K, rbl_f2 Fx, rbl_f2 Fy, rbl_f2 Fz, rbl_f2 &ux, rbl_f2 &uy, rbl_f2 &uz)
 {
@@ -82,14 +83,4 @@ __device__ __forceinline__ void rbl_pk_apply(const RblPkCoef &K, rbl_f2 Fx, rbl_
   ux = rbl_fma2(K.cF, Fx, rbl_fma2(l, K.dx, ux));
   uy = rbl_fma2(K.cF, Fy, rbl_fma2(l, K.dy, uy));
   uz = rbl_fma2(K.mzz, Fz, rbl_fma2(g_z, p, uz));
-}
-
-template <bool WALL>
-__device__ __forceinline__ void rbl_pair_sym_pk(rbl_f2 xi, rbl_f2 yi, rbl_f2 zi, rbl_f2 Fix, rbl_f2 Fiy, rbl_f2 Fiz, float xj,
-                                                float yj, float zj, float Fjx, float Fjy, float Fjz, float two_z0, rbl_f2 &uix,
-                                                rbl_f2 &uiy, rbl_f2 &uiz, rbl_f2 &ujx, rbl_f2 &ujy, rbl_f2 &ujz)
-{
-  const RblPkCoef K = rbl_pk_coef<WALL>(xi, yi, zi, xj, yj, zj, two_z0);
-  rbl_pk_apply<WALL, false>(K, rbl_splat(Fjx), rbl_splat(Fjy), rbl_splat(Fjz), uix, uiy, uiz);   // U_i += M F_j
-  rbl_pk_apply<WALL, true>(K, Fix, Fiy, Fiz, ujx, ujy, ujz);                                      // U_j += M^T F_i
 }

@@ -6,7 +6,7 @@
 
 constexpr int RBL_SG_THREADS = 1024;
 
-// the pair kernels' constants for positions given in units of a (rbl_pair_accum / rbl_pair_sym, scaled by nf afterwards)
+// the pair kernels' constants for positions given in units of a (rbl_pair_accum / rbl_pair_symv, scaled by nf afterwards)
 __device__ __forceinline__ RblParams rbl_small_unit_params(const RblParams &P)
 {
   return {1.0, 1.0, P.nf, 4.0, 1e-24, -0.375, 0.125, 0};
@@ -25,7 +25,7 @@ __device__ __forceinline__ void rbl_quat_rot9(const double *q, double *R)
   R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
 }
 
-// The off-diagonal part of the product with the damped vector d v: every unordered pair once (M_ji = M_ij^T, rbl_pair_sym).
+// The off-diagonal part of the product with the damped vector d v: every unordered pair once (M_ji = M_ij^T, rbl_pair_symv).
 // Step (s, rb) pairs the rows i = 64 rb + lane with the columns j = i + s (mod N), s = 1 .. N/2 (for even N the offset N/2
 // only from the lower half), so the 64 lanes of a wavefront touch 64 different rows and 64 different columns per step; the
 // steps are dealt round-robin to the wavefronts, each adding into its OWN accumulator set part[wave][3N] (fixed order inside
@@ -47,16 +47,15 @@ __device__ __forceinline__ void rbl_small_pair_sweep(const RblParams &Pu, const 
       int j = i + s_;
       if (j >= N) j -= N;
       const double di = WALL ? dmp[i] : 1.0, dj = WALL ? dmp[j] : 1.0;
-      double uix = 0.0, uiy = 0.0, uiz = 0.0, ujx = 0.0, ujy = 0.0, ujz = 0.0;
-      rbl_pair_sym<WALL, true, true>(Pu, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], di * in[3 * i], di * in[3 * i + 1],
-                                     di * in[3 * i + 2], pos[3 * j], pos[3 * j + 1], pos[3 * j + 2], dj * in[3 * j],
-                                     dj * in[3 * j + 1], dj * in[3 * j + 2], uix, uiy, uiz, ujx, ujy, ujz, flags);
-      __hip_atomic_fetch_add(&acc[3 * i], uix, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(&acc[3 * i + 1], uiy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(&acc[3 * i + 2], uiz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(&acc[3 * j], ujx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(&acc[3 * j + 1], ujy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(&acc[3 * j + 2], ujz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const RblV3 Fi[1] = {{di * in[3 * i], di * in[3 * i + 1], di * in[3 * i + 2]}}, Fj[1] = {{dj * in[3 * j], dj * in[3 * j + 1], dj * in[3 * j + 2]}};
+      RblV3 ui[1] = {{0.0, 0.0, 0.0}}, uj[1] = {{0.0, 0.0, 0.0}};
+      rbl_pair_symv<WALL, true, true>(Pu, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], Fi, pos[3 * j], pos[3 * j + 1], pos[3 * j + 2], Fj, ui, uj, flags);
+      __hip_atomic_fetch_add(&acc[3 * i], ui[0].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&acc[3 * i + 1], ui[0].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&acc[3 * i + 2], ui[0].z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&acc[3 * j], uj[0].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&acc[3 * j + 1], uj[0].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&acc[3 * j + 2], uj[0].z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
   }
   __syncthreads();

@@ -33,15 +33,17 @@ void sym_blocks(const double *ri, const double *rj, double a, int wall, int near
   unsigned flags = 0;
   for (int c = 0; c < 3; ++c) {
     const double fx = c == 0, fy = c == 1, fz = c == 2;
-    double ui[3] = {0, 0, 0}, uj[3] = {0, 0, 0};
+    const RblV3 f[1] = {{fx, fy, fz}};
+    RblV3 ui[1] = {{0, 0, 0}}, uj[1] = {{0, 0, 0}};
     if (wall) {
-      if (nearchk) rbl_pair_sym<true, true, true>(P, xi, yi, zi, fx, fy, fz, xj, yj, zj, fx, fy, fz, ui[0], ui[1], ui[2], uj[0], uj[1], uj[2], flags);
-      else rbl_pair_sym<true, true, false>(P, xi, yi, zi, fx, fy, fz, xj, yj, zj, fx, fy, fz, ui[0], ui[1], ui[2], uj[0], uj[1], uj[2], flags);
+      if (nearchk) rbl_pair_symv<true, true, true>(P, xi, yi, zi, f, xj, yj, zj, f, ui, uj, flags);
+      else rbl_pair_symv<true, true, false>(P, xi, yi, zi, f, xj, yj, zj, f, ui, uj, flags);
     } else {
-      if (nearchk) rbl_pair_sym<false, true, true>(P, xi, yi, zi, fx, fy, fz, xj, yj, zj, fx, fy, fz, ui[0], ui[1], ui[2], uj[0], uj[1], uj[2], flags);
-      else rbl_pair_sym<false, true, false>(P, xi, yi, zi, fx, fy, fz, xj, yj, zj, fx, fy, fz, ui[0], ui[1], ui[2], uj[0], uj[1], uj[2], flags);
+      if (nearchk) rbl_pair_symv<false, true, true>(P, xi, yi, zi, f, xj, yj, zj, f, ui, uj, flags);
+      else rbl_pair_symv<false, true, false>(P, xi, yi, zi, f, xj, yj, zj, f, ui, uj, flags);
     }
-    for (int p = 0; p < 3; ++p) { Mij[3 * p + c] = ui[p]; Mji[3 * p + c] = uj[p]; }
+    const double ui3[3] = {ui[0].x, ui[0].y, ui[0].z}, uj3[3] = {uj[0].x, uj[0].y, uj[0].z};
+    for (int p = 0; p < 3; ++p) { Mij[3 * p + c] = ui3[p]; Mji[3 * p + c] = uj3[p]; }
   }
 }
 }

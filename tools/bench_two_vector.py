@@ -1,4 +1,4 @@
-"""One-vector against two-vector symmetric product at cfg 3 (k_apply_M_sym<true,2,4> / k_apply_M_sym2<true,2,4>): wall time of each and
+"""One-vector against two-vector symmetric product at cfg 3 (k_apply_M_sym<true,2,4,0,NV> with NV = 1 / 2): wall time of each and
 their ratio (the instruction counts of librbl.isa.json say 95 : 75 VALU per pair); the script the counter passes of
 tools/run_profile_two_vector.sh run.  usage: bench_two_vector.py [bodies blobs]"""
 import os, sys

@@ -4,7 +4,8 @@ librbl.so is built from (rigid_body_light_amd/build.py runs this after every ker
 result next to the library: librbl.isa.json).  bench.py prices its roofline with these EXECUTED counts
 (frac <= 1 by construction) instead of the reference-arithmetic 204 flop per ordered pair.
 
-For every k_apply_M_sym / k_apply_M_sym2 / k_apply_M_sym4 instantiation the hot block is the far-tile
+For every k_apply_M_sym<WALL, NI, SW, PREC, NV> instantiation (reported as k_apply_M_sym<...> for one force vector,
+k_apply_M_sym2<...> for two: the names the library's kernel table and bench.py use) the hot block is the far-tile
 systolic sweep: the basic block with the most v_rsq_f64 that has ds_add_f64 column sums and no division.
 Pairs per trip of that block = v_rsq_f64 / (2 with the wall term, 1 without).
 
@@ -67,11 +68,12 @@ def main():
     res = {}
     instances = {}
     for i, l in enumerate(lines):
-        m = re.match(r"^(_ZN\S*?(k_apply_M_sym\d?)ILb([01])ELi(\d)E((?:Li\d+E)*)E\S*):", l)
+        m = re.match(r"^(_ZN\S*?13k_apply_M_symILb([01])ELi(\d)E((?:Li\d+E)*)E\S*):", l)
         if not m:
             continue
-        kern, wall, ni = m.group(2), m.group(3) == "1", int(m.group(4))
-        extra = [int(x) for x in re.findall(r"Li(\d+)E", m.group(5))]      # SW [, PREC]
+        wall, ni = m.group(2) == "1", int(m.group(3))
+        extra = [int(x) for x in re.findall(r"Li(\d+)E", m.group(4))]      # SW, PREC, NV
+        kern = "k_apply_M_sym2" if extra.pop() == 2 else "k_apply_M_sym"
         relaxed = len(extra) >= 2 and extra[1] == 1
         end = next(k for k in range(i, len(lines)) if lines[k].startswith(".Lfunc_end"))
         instances["%s<%s,%d%s>" % (kern, "true" if wall else "false", ni, "".join(",%d" % x for x in extra))] = isa_hash(lines, i, end)
@@ -112,17 +114,20 @@ def main():
         per["flop"] = 2 * per["fma"] + per["mul"] + per["add"] + per["trans"]   # a transcendental counted as ONE flop
         res["%s<%s,%d>" % (kern, "true" if wall else "false", ni)] = {
             "block": best[0], "unordered_pairs_per_trip": pairs, "per_unordered_pair": per}
-    # the wave-unit kernel of mid-size systems, k_apply_M_symw<WALL, IW>: its sweep is a loop of a few basic blocks (the rare overlap
+    # the wave-unit kernel of mid-size systems, k_apply_M_symw<WALL, NI, IW, NV> (two vectors: reported as k_apply_M_symw2v<WALL, NI>): its sweep is a loop of a few basic blocks (the rare overlap
     # branch splits it), column sums rotating through the lanes by v_mov_b32_dpp wave_rol:1 -- summed from the loop header to the
     # block that branches back to it; pair steps per trip = v_rsq_f64 / (2 with the wall term, 1 without)
     for i, l in enumerate(lines):
-        m = re.match(r"^(_ZN\S*?14k_apply_M_symwILb([01])ELi(\d+)ELi(\d+)EE\S*):", l)
+        m = re.match(r"^(_ZN\S*?14k_apply_M_symwILb([01])ELi(\d+)ELi(\d+)ELi(\d+)EE\S*):", l)
         if not m:
             continue
         wall = m.group(2) == "1"
         ni = int(m.group(3))
         end = next(k for k in range(i, len(lines)) if lines[k].startswith(".Lfunc_end"))
-        name_k = ("k_apply_M_symw<%s>" if ni == 1 else "k_apply_M_symw<%%s,%d>" % ni) % ("true" if wall else "false")
+        if int(m.group(5)) == 2:
+            name_k = "k_apply_M_symw2v<%s,%d>" % ("true" if wall else "false", ni)
+        else:
+            name_k = ("k_apply_M_symw<%s>" if ni == 1 else "k_apply_M_symw<%%s,%d>" % ni) % ("true" if wall else "false")
         instances[name_k] = isa_hash(lines, i, end)
         labels, raw = [], []
         for k in range(i + 1, end):

@@ -5,7 +5,7 @@ of the bytes of wide coalesced reads -- MI355X_MICROARCH.md, section HBM), plus 
 The file records the hash of the kernel sources the profiled library was built from; bench.py ignores it when the
 sources have changed since.
 
-usage: pmc_to_json.py <kernel substring, e.g. "k_apply_M_sym<true, 2"> <config> out.json dir1 [dir2 ...]"""
+usage: pmc_to_json.py <kernel substring, e.g. "k_apply_M_sym<true, 2, 4, 0, 1>"> <config> out.json dir1 [dir2 ...]"""
 import collections, csv, glob, hashlib, json, os, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC look at the mid-size product kernel (cfg 2: k_apply_M_sym<false,1,1,0>, 8 128 one-tile-pair units): issue share, waves in flight.
+# PMC look at the mid-size product kernel (cfg 2: k_apply_M_sym<false,1,1,0,1>, 8 128 one-tile-pair units): issue share, waves in flight.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${CFG2_OUT:-r03m}
 mkdir -p $O

@@ -1,6 +1,6 @@
 #!/bin/bash
 # kernel durations + PMC counters of the mid-size product at cfg 2 (8 100 blobs, free space): the round-3 kernel
-# k_apply_M_sym<false,1,1,0> and the wave-unit kernel k_apply_M_symw<false,4> in the same run (tools/bench_midsize.py alternates them)
+# k_apply_M_sym<false,1,1,0,1> and the wave-unit kernel k_apply_M_symw<false,1,4,1> in the same run (tools/bench_midsize.py alternates them)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${1:-r04e}
 mkdir -p $O

@@ -38,7 +38,7 @@ echo "part $p done" >> $O/progress.txt
 done
 cd $R
 python3 tools/pmc_summary.py $O/cfg3_pmc_summary.txt $O/cfg3_pmc_* 2>/dev/null
-python3 tools/pmc_to_json.py "k_apply_M_sym<true, 2, 4, 0" cfg3 $O/cfg3_pmc.json $O/cfg3_pmc_* 2>/dev/null
+python3 tools/pmc_to_json.py "k_apply_M_sym<true, 2, 4, 0, 1>" cfg3 $O/cfg3_pmc.json $O/cfg3_pmc_* 2>/dev/null
 python3 tools/pmc_summary.py $O/mid_pmc_summary.txt $O/mid_pmc_* $O/mid_stats 2>/dev/null
 for f in $(find $O/brownian_cfg2_stats -name "*kernel_trace.csv" | head -1); do python3 tools/step_launches.py $f "cfg 2 converged Brownian step, round 4 (rocprofv3 --kernel-trace)" > $O/cfg2_step_launches.md; done
 for f in $(find $O/brownian_cfg2_unfused -name "*kernel_trace.csv" | head -1); do python3 tools/step_launches.py $f "cfg 2 converged Brownian step, round-3 kernels (fused_krylov=0, sym_wave_units=0)" > $O/cfg2_step_launches_unfused.md; done

@@ -37,7 +37,7 @@ echo "part $p done" >> $O/progress.txt
 done
 cd $R
 python3 tools/pmc_summary.py $O/cfg3_pmc_summary.txt $O/cfg3_pmc_* 2>/dev/null
-python3 tools/pmc_to_json.py "k_apply_M_sym<true, 2, 4, 0" cfg3 $O/cfg3_pmc.json $O/cfg3_pmc_* 2>/dev/null
+python3 tools/pmc_to_json.py "k_apply_M_sym<true, 2, 4, 0, 1>" cfg3 $O/cfg3_pmc.json $O/cfg3_pmc_* 2>/dev/null
 python3 tools/pmc_summary.py $O/tile_pmc_summary.txt $O/tile_pmc_* 2>/dev/null
 python3 tools/pmc_summary.py $O/multi_pmc_summary.txt $O/multi_pmc_* 2>/dev/null
 ls $O | head -40
