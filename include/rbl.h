@@ -623,6 +623,63 @@ int rbl_velocity_field_dev(rbl_ctx *ctx, const double *d_points, int64_t n_point
                            int64_t n_src, double *d_u);
 int rbl_velocity_field_info(const rbl_ctx *ctx, int64_t n_points, int64_t n_src, int *ni, int *chunks, int64_t *workspace_bytes);
 
+/* ===================================================================== */
+/* 7. Prescribed kinematics (rigid_body_light_amd/csrc/rbl_mixed.hip)     */
+/* ===================================================================== */
+/* Every other solver answers "given the loads on all bodies, how do they move?".  Here any subset p of the bodies has its
+ * velocity PRESCRIBED (held: U = 0; driven: U given) while the others (f) stay free; the reference has no such solver.  With
+ * K = [K_f K_p] the blob forces lambda and the free velocities U_f solve
+ *     M lambda - K_f U_f = slip + K_p U_p        (no slip on every blob, prescribed bodies moving as told)
+ *     K_f^T lambda       = -F_f                  (force and torque balance of the free bodies only)
+ * and the by-product is the load the prescribed bodies need, F_p = -K_p^T lambda, in the convention of the F_body argument of
+ * rbl_step_deterministic (rhs = [slip; -F]): if a mobility solve with loads F gives velocities U, prescribing that U on a set p
+ * and keeping F on the rest returns the same lambda, the same U_f and F_p = F on p.  M is what rbl_apply_saddle applies on the
+ * context's configuration.  p empty: the saddle system; f empty: M lambda = slip + K U, the resistance problem.
+ *
+ * The set travels with each call (prescribed[N_bod], 0 = free, 1 = prescribed) and is never context state: no other entry point
+ * changes meaning.  body_in[6 N_bod] holds, body by body, the load F_b of a free body or the velocity U_b (translation, rotation)
+ * of a prescribed one.  Outputs: U[6 N_bod] all body velocities (prescribed ones echoed), F[6 N_bod] all body loads (free ones
+ * echoed, prescribed ones = -K_b^T lambda), lambda[3 N_blobs] (may be NULL) the blob forces -- what rbl_velocity_field takes.
+ *
+ * Cost: an ITERATION costs what an iteration of the unconstrained solve costs; a solve needs more of them the more bodies are
+ * prescribed (nothing but M_b^-1 preconditions M on a prescribed body): 17 / 33 / 60 iterations to 1e-8 for none / a quarter /
+ * all of 200 x 642-blob bodies above the wall with the block preconditioner.
+ * Solver: the right-preconditioned GMRES of rbl_gmres_saddle_dev (no restart, max_iter <= 255, cold start) on
+ *     [M lambda - K (D_f U) ; D_f K^T lambda + D_p U]     (D_f, D_p: 0/1 per body; the slots of prescribed bodies solve to 0)
+ * with the context's preconditioner body by body: a free body as rbl_apply_PC treats it with the force block's sign restored
+ * (the exact inverse of [M_b -K_b; K_b^T 0]), a prescribed one lambda_b = M_b^-1 slip_b with its six body slots passed through.
+ * The residual estimate is relative to |[slip + K_p U_p ; F_f]|.  One iteration costs what an ordinary one costs: one mobility
+ * product, one pass over the per-body factors (two with the free-space body-frame tables when a body is prescribed).
+ *
+ *   rbl_solve_mixed      host arrays, synchronous.
+ *   rbl_solve_mixed_dev  body_in, slip, lambda, U, F are device pointers; `prescribed` stays a HOST array (N_bod bytes, checked
+ *                        before any device work and copied, so it may go after the call); enqueued on the context's stream.
+ *                        The call drains the stream where rbl_gmres_saddle_dev does -- once while the preconditioner of the
+ *                        configuration is made ready (rbl_prepare_dev), at the solver's convergence tests and at its end --
+ *                        and nowhere else; the copies into d_lambda, d_U, d_F are enqueued behind the solve and not waited
+ *                        for.  Errors are latched in the device word (rbl_sync_check).
+ *   rbl_step_mixed       host arrays: the solve at the current configuration, then evolve_X_Q(U) -- prescribed bodies advance by
+ *                        their own velocity (a held body does not move).  F (may be NULL) as above.  With the force model on
+ *                        (section 4) the step adds the model's loads at q^n, -K^T f_phys, to the FREE bodies' slots only: a
+ *                        prescribed body's motion does not depend on the loads on it and its slots hold velocities.  The F
+ *                        returned for a prescribed body is therefore the TOTAL load that everything other than the fluid
+ *                        supplies: the model already supplies its share (rbl_interaction_forces returns it as PHYSICAL forces,
+ *                        i.e. with the opposite sign: share = -FT_body), the outside agent supplies F minus that share.
+ *                        The step clears the warm-start history of rbl_step_deterministic.
+ * slip: 3 N_blobs or NULL for zero.  Status codes as the other solvers.  A NULL prescribed / body_in / U / F (rbl_step_mixed: F
+ * may be NULL), max_iter < 1, rtol < 0 and entries of `prescribed` other than 0 / 1 are RBL_ERR_ARG before any device work; so
+ * is a context with a communicator (as for the ensembles) -- sharding the mixed solve is a follow-up.  Results are bitwise
+ * reproducible call to call (no float atomics).
+ * Not offered: the Brownian midpoint step with prescribed bodies (the scheme carries over with K -> K_f, random displacements
+ * and the RFD direction masked to the free bodies; its check is statistical), ensembles and lock-step multi-right-hand-side
+ * mixed solves, and per-component constraints (only whole bodies are prescribed). */
+int rbl_solve_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
+                    double *lambda, double *U, double *F, int *iters, double *resid);
+int rbl_solve_mixed_dev(rbl_ctx *ctx, const uint8_t *prescribed, const double *d_body_in, const double *d_slip, int max_iter,
+                        double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid);
+int rbl_step_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
+                   double *F, int *iters, double *resid);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,9 @@ def lib():
         L.rbl_velocity_field.argtypes = [vp, vp, i64, vp, vp, i64, vp]
         L.rbl_velocity_field_dev.argtypes = [vp, vp, i64, vp, vp, i64, vp]
         L.rbl_velocity_field_info.argtypes = [vp, i64, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
+        L.rbl_solve_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
+        L.rbl_solve_mixed_dev.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
+        L.rbl_step_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
         _LIB = L
     return _LIB
 
@@ -537,6 +540,37 @@ class DeviceContext:
         ni, ch, wb = C.c_int(0), C.c_int(0), C.c_int64(0)
         self._chk(self.L.rbl_velocity_field_info(self.h, n_points, n_src, C.byref(ni), C.byref(ch), C.byref(wb)))
         return ni.value, ch.value, wb.value
+
+    # -- prescribed kinematics (include/rbl.h section 7) ---------------------------------------------------------------------
+    def solve_mixed(self, prescribed, body_in, max_iter=100, rtol=1.0e-8, slip=None):
+        """bodies with prescribed[b] = 1 move with body_in[b] (a velocity), the others carry body_in[b] as their load; host arrays
+        -> (lambda, U, F, iterations, residual estimate)"""
+        import numpy as np
+        m = np.ascontiguousarray(prescribed, dtype=np.uint8).reshape(-1)
+        bi = np.ascontiguousarray(body_in, dtype=np.float64).reshape(-1)
+        sl = None if slip is None else np.ascontiguousarray(slip, dtype=np.float64).reshape(-1)
+        nb, nl = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), C.byref(nl)))
+        if m.size != nb.value or bi.size != 6 * nb.value or (sl is not None and sl.size != 3 * nb.value * nl.value):
+            raise ValueError("solve_mixed: prescribed (N_bod), body_in (6 N_bod) or slip (3 N_blobs) has the wrong size")
+        lam, U, F = np.empty(3 * nb.value * nl.value), np.empty(6 * nb.value), np.empty(6 * nb.value)
+        it, res = C.c_int(0), C.c_double(0.0)
+        self._chk(self.L.rbl_solve_mixed(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data, int(max_iter),
+                                         float(rtol), lam.ctypes.data, U.ctypes.data, F.ctypes.data, C.byref(it), C.byref(res)))
+        return lam, U, F, it.value, res.value
+
+    def solve_mixed_dev(self, prescribed, d_body_in, d_slip, max_iter, rtol, d_lam, d_U, d_F):
+        """the same on device addresses (prescribed: a host array; d_slip, d_lam may be None / 0) -> (iterations, residual estimate)"""
+        import numpy as np
+        m = np.ascontiguousarray(prescribed, dtype=np.uint8).reshape(-1)
+        nb = C.c_int(0)
+        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), None))
+        if m.size != nb.value:
+            raise ValueError("solve_mixed_dev: prescribed must have N_bod entries")
+        it, res = C.c_int(0), C.c_double(0.0)
+        self._chk(self.L.rbl_solve_mixed_dev(self.h, m.ctypes.data, d_body_in, d_slip or None, int(max_iter), float(rtol), d_lam or None,
+                                             d_U, d_F, C.byref(it), C.byref(res)))
+        return it.value, res.value
 
     def blob_positions(self, body_begin, body_end, dout):
         self._chk(self.L.rbl_blob_positions_dev(self.h, body_begin, body_end, dout))

@@ -437,6 +437,46 @@ struct CManyBodies {
     check(rc);
     return out;
   }
+  // prescribed kinematics (include/rbl.h section 7): mask[N_bod] 0/1, body_in[6 N_bod] loads of the free bodies / velocities of the
+  // prescribed ones -> (lambda, U, F, iterations, residual estimate)
+  using marr = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>;
+  const double *mixed_args(const char *who, const marr &mask, const darr &body_in, const py::object &slip, darr &sl) const
+  {
+    if (mask.size() != (py::ssize_t)n_bod()) throw std::runtime_error(std::string(who) + ": prescribed must have length N_bod");
+    if (body_in.size() != 6 * (py::ssize_t)n_bod()) throw std::runtime_error(std::string(who) + ": body_in must have length 6*N_bod");
+    if (slip.is_none()) return nullptr;
+    sl = slip.cast<darr>();
+    if (sl.size() != n3()) throw std::runtime_error(std::string(who) + ": slip must have length 3*N_blobs");
+    return sl.data();
+  }
+  py::tuple solve_mixed(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
+  {
+    darr sl;
+    const double *sp = mixed_args("solve_mixed", mask, body_in, slip, sl);
+    darr lam(n3()), U(6 * (py::ssize_t)n_bod()), F(6 * (py::ssize_t)n_bod());
+    int it = 0, rc; double res = 0.0;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_solve_mixed(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, lam.mutable_data(), U.mutable_data(), F.mutable_data(),
+                           &it, &res);
+    }
+    check(rc);
+    return py::make_tuple(lam, U, F, it, res);
+  }
+  // the solve, then evolve_X_Q(U) -> (F, iterations, residual estimate)
+  py::tuple step_mixed(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
+  {
+    darr sl;
+    const double *sp = mixed_args("step_mixed", mask, body_in, slip, sl);
+    darr F(6 * (py::ssize_t)n_bod());
+    int it = 0, rc; double res = 0.0;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_step_mixed(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, F.mutable_data(), &it, &res);
+    }
+    check(rc);
+    return py::make_tuple(F, it, res);
+  }
   void set_interactions(double w, double eps_wall, double b_wall, double eps_blob, double b_blob, double r_cut, bool on)
   {
     check(rbl_set_interactions(ctx, w, eps_wall, b_wall, eps_blob, b_blob, r_cut, on ? 1 : 0));
@@ -535,6 +575,10 @@ PYBIND11_MODULE(c_rigid, m)
       .def("interaction_energy", &CManyBodies::interaction_energy)
       .def("velocity_field", &CManyBodies::velocity_field, "fluid velocity at points from blob forces", py::arg("points"),
            py::arg("lambda"), py::arg("r_vecs") = py::none())
+      .def("solve_mixed", &CManyBodies::solve_mixed, "prescribed kinematics: velocities given on some bodies, loads on the others",
+           py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
+      .def("step_mixed", &CManyBodies::step_mixed, py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(),
+           py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
       .def("set_option", &CManyBodies::set_option, py::arg("name"), py::arg("value"))
       .def("get_option", &CManyBodies::get_option, py::arg("name"))
       .def("handle", &CManyBodies::handle, "address of the underlying rbl_ctx (for the ctypes device API)")

@@ -10,6 +10,7 @@
 //   rbl_forces.hip    configuration-dependent forces (weight, wall and steric repulsion)
 //   rbl_ensemble.hip  ensembles of independent replicas of one small system
 //   rbl_field.hip     the fluid velocity at arbitrary points from blob forces
+//   rbl_mixed.hip     prescribed kinematics: held or driven bodies among free ones, the loads that takes
 // None of these symbols is exported from librbl.so.
 #pragma once
 #include "rbl_internal.hpp"
@@ -69,6 +70,19 @@ int blk_trmv_multi(rbl_ctx *c, int b0, int nbo, const double *in, double *out, i
 int tl_build(rbl_ctx *c);
 int tl_apply(rbl_ctx *c, const double *w, double *wo, int nvec, int64_t pitch, int op);
 int mhalf_dev_multi(rbl_ctx *c, const double *d_r, int64_t nbl, const double *d_W, int nvec, int method, double *d_out);
+
+// ---- rbl_solvers.hip ----------------------------------------------------------------------------------------------
+// the library's GMRES (Arnoldi kernels, host Givens solve, overlapped convergence test) on a system of the saddle system's size whose
+// operator and right preconditioner the caller supplies (rbl_mixed.hip).  Every shortcut fused into the ordinary saddle solve
+// (K^T lambda by-product, Gram-Schmidt sums in the product, normalisation folded into the preconditioner, the one-kernel solver,
+// relaxed products, the iteration-count memory) stays off.
+struct RblSolveOps {
+  int (*op)(rbl_ctx *c, void *user, const double *d_x, double *d_out);
+  int (*pc)(rbl_ctx *c, void *user, const double *d_in, double *d_out);
+  void *user;
+};
+int gmres_core_with_ops(rbl_ctx *c, const RblSolveOps *ops, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
+                        double *resid_out);
 
 // ---- rbl_steps.hip ------------------------------------------------------------------------------------------------
 int m_rfd_core(rbl_ctx *c, const double *d_W, const double *Wh, double delta, double *d_out, double *d_r, double *d_work);

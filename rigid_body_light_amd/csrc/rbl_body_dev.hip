@@ -5,6 +5,7 @@
 // everything a GMRES step touches stays in HBM.  All are O(N) and latency-bound; one
 // workgroup per rigid body, deterministic LDS tree reductions (no atomics).
 #include "rbl_internal.hpp"
+#include "rbl_body_dev.hpp"
 
 namespace {
 
@@ -50,10 +51,8 @@ __global__ void k_K_x_U(const double *__restrict__ lever, const double *__restri
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= N) return;
   const int b = (int)(idx / N_blb);
-  const double *u = U + 6 * b, *om = u + 3, *l = lever + 3 * idx;
-  const double k0 = u[0] + l[2] * om[1] - l[1] * om[2];
-  const double k1 = u[1] + l[0] * om[2] - l[2] * om[0];
-  const double k2 = u[2] + l[1] * om[0] - l[0] * om[1];
+  double k0, k1, k2;
+  rbl_KU(lever + 3 * idx, U + 6 * b, k0, k1, k2);
   if (sub) {  // out = sub + alpha * K U   (saddle epilogue: slip = M lambda - K U)
     out[3 * idx] = sub[3 * idx] + alpha * k0; out[3 * idx + 1] = sub[3 * idx + 1] + alpha * k1;
     out[3 * idx + 2] = sub[3 * idx + 2] + alpha * k2;
@@ -65,19 +64,7 @@ __global__ void k_K_x_U(const double *__restrict__ lever, const double *__restri
 template <int NV>
 __device__ __forceinline__ void block_reduce(double (&v)[NV], double (*s)[BT], int t)
 {
-#pragma unroll
-  for (int q = 0; q < NV; ++q) s[q][t] = v[q];
-  __syncthreads();
-  for (int st = BT / 2; st > 0; st >>= 1) {
-    if (t < st) {
-#pragma unroll
-      for (int q = 0; q < NV; ++q) s[q][t] += s[q][t + st];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int q = 0; q < NV; ++q) v[q] = s[q][0];
-  __syncthreads();
+  rbl_block_sum<NV, BT>(v, s, t);
 }
 
 // RblNormFold: |w| and 1 / |w| (0 for a vanishing vector, like k_lz_c) from the partial sums of |w|^2: every wave of every workgroup
@@ -100,11 +87,8 @@ __global__ __launch_bounds__(BT) void k_KT_x_Lam(const double *__restrict__ leve
   double f[6] = {0, 0, 0, 0, 0, 0};
   for (int k = t; k < N_blb; k += BT) {
     const size_t idx = 3 * ((size_t)b * N_blb + k);
-    const double *l = lever + idx, *v = lam + idx;
-    f[0] += v[0]; f[1] += v[1]; f[2] += v[2];
-    f[3] += l[1] * v[2] - l[2] * v[1];
-    f[4] += l[2] * v[0] - l[0] * v[2];
-    f[5] += l[0] * v[1] - l[1] * v[0];
+    const double *v = lam + idx;
+    rbl_KT_acc(lever + idx, v[0], v[1], v[2], f);
   }
   block_reduce<6>(f, s, t);
   if (t < 6) out[6 * b + t] = f[t];
@@ -195,25 +179,13 @@ __global__ __launch_bounds__(BT) void k_pc_diag_apply(const double *__restrict__
     const double *l = lever + 3 * i;
     const double v0 = invM2[2 * i] * (inv * slip[3 * i]), v1 = invM2[2 * i] * (inv * slip[3 * i + 1]),
                  v2 = invM2[2 * i + 1] * (inv * slip[3 * i + 2]);
-    f[0] += v0; f[1] += v1; f[2] += v2;
-    f[3] += l[1] * v2 - l[2] * v1;
-    f[4] += l[2] * v0 - l[0] * v2;
-    f[5] += l[0] * v1 - l[1] * v0;
+    rbl_KT_acc(l, v0, v1, v2, f);
   }
   block_reduce<6>(f, s, t);
   if (t == 0) {  // U = Ninv^-1 (-F - K^T invM slip) through the 6x6 Cholesky factor (:601-608)
-    const double *L = NL + 36 * (size_t)b;
-    double y[6], u[6];
-    for (int p = 0; p < 6; ++p) {
-      double v = fsign * (inv * F[6 * b + p]) - f[p];
-      for (int q = 0; q < p; ++q) v -= L[6 * p + q] * y[q];
-      y[p] = v / L[6 * p + p];
-    }
-    for (int p = 5; p >= 0; --p) {
-      double v = y[p];
-      for (int q = p + 1; q < 6; ++q) v -= L[6 * q + p] * u[q];
-      u[p] = v / L[6 * p + p];
-    }
+    double r[6], u[6];
+    for (int p = 0; p < 6; ++p) r[p] = fsign * (inv * F[6 * b + p]) - f[p];
+    rbl_chol6_solve(NL + 36 * (size_t)b, r, u);
     for (int p = 0; p < 6; ++p) { Ush[p] = u[p]; out[n3 + 6 * b + p] = u[p]; }
   }
   __syncthreads();
@@ -281,26 +253,14 @@ __global__ __launch_bounds__(BT) void k_pc_block_tail(const double *__restrict__
   double f[6] = {0, 0, 0, 0, 0, 0};
   for (int k = t; k < N_blb; k += BT) {
     const size_t idx = 3 * ((size_t)b * N_blb + k);
-    const double *l = lever + idx, *v = y1 + idx;
-    f[0] += v[0]; f[1] += v[1]; f[2] += v[2];
-    f[3] += l[1] * v[2] - l[2] * v[1];
-    f[4] += l[2] * v[0] - l[0] * v[2];
-    f[5] += l[0] * v[1] - l[1] * v[0];
+    const double *v = y1 + idx;
+    rbl_KT_acc(lever + idx, v[0], v[1], v[2], f);
   }
   block_reduce<6>(f, s, t);
   if (t == 0) {
-    const double *L = NL + 36 * (size_t)b;
-    double y[6], u[6];
-    for (int p = 0; p < 6; ++p) {
-      double v = inv * (fsign * F[6 * b + p] - f[p]);
-      for (int q = 0; q < p; ++q) v -= L[6 * p + q] * y[q];
-      y[p] = v / L[6 * p + p];
-    }
-    for (int p = 5; p >= 0; --p) {
-      double v = y[p];
-      for (int q = p + 1; q < 6; ++q) v -= L[6 * q + p] * u[q];
-      u[p] = v / L[6 * p + p];
-    }
+    double r[6], u[6];
+    for (int p = 0; p < 6; ++p) r[p] = inv * (fsign * F[6 * b + p] - f[p]);
+    rbl_chol6_solve(NL + 36 * (size_t)b, r, u);
     for (int p = 0; p < 6; ++p) { U[6 * b + p] = u[p]; us[p] = u[p]; }
   }
   __syncthreads();
@@ -317,11 +277,7 @@ __global__ __launch_bounds__(BT) void k_pc_block_tail(const double *__restrict__
       v[d] = acc;
       lam[idx + d] = acc;
     }
-    const double *l = lever + idx;
-    g[0] += v[0]; g[1] += v[1]; g[2] += v[2];
-    g[3] += l[1] * v[2] - l[2] * v[1];
-    g[4] += l[2] * v[0] - l[0] * v[2];
-    g[5] += l[0] * v[1] - l[1] * v[0];
+    rbl_KT_acc(lever + idx, v[0], v[1], v[2], g);
   }
   if (ktl) {
     block_reduce<6>(g, s, t);
@@ -339,10 +295,8 @@ __global__ void k_saddle_tail(const double *__restrict__ lever, const double *__
   if (idx < nb6) out[3 * N + idx] = ktl[idx];
   if (idx >= N) return;
   const int b = (int)(idx / N_blb);
-  const double *u = U + 6 * b, *om = u + 3, *l = lever + 3 * idx;
-  const double k0 = u[0] + l[2] * om[1] - l[1] * om[2];
-  const double k1 = u[1] + l[0] * om[2] - l[2] * om[0];
-  const double k2 = u[2] + l[1] * om[0] - l[0] * om[1];
+  double k0, k1, k2;
+  rbl_KU(lever + 3 * idx, U + 6 * b, k0, k1, k2);
   out[3 * idx] = sub[3 * idx] - k0; out[3 * idx + 1] = sub[3 * idx + 1] - k1; out[3 * idx + 2] = sub[3 * idx + 2] - k2;
 }
 
@@ -551,19 +505,11 @@ __global__ __launch_bounds__(BFT) void k_pc_bodyframe(const double *__restrict__
   bf_reduce6(f, red, f6, t);
   if (t == 0) {                                      // U' = N_body^-1 (fsign F' - f'), U = (R U'_lin, R U'_ang)
     const double *F = in + n3 + 6 * (size_t)b;
-    double Fb[6], y[6], u[6];
+    double Fb[6], r[6], u[6];
     for (int h = 0; h < 2; ++h)
       for (int d = 0; d < 3; ++d) Fb[3 * h + d] = inv * (R[d] * F[3 * h] + R[3 + d] * F[3 * h + 1] + R[6 + d] * F[3 * h + 2]);   // R^T
-    for (int p = 0; p < 6; ++p) {
-      double v = fsign * Fb[p] - f6[p];
-      for (int q = 0; q < p; ++q) v -= NL[6 * p + q] * y[q];
-      y[p] = v / NL[6 * p + p];
-    }
-    for (int p = 5; p >= 0; --p) {
-      double v = y[p];
-      for (int q = p + 1; q < 6; ++q) v -= NL[6 * q + p] * u[q];
-      u[p] = v / NL[6 * p + p];
-    }
+    for (int p = 0; p < 6; ++p) r[p] = fsign * Fb[p] - f6[p];
+    rbl_chol6_solve(NL, r, u);
     for (int p = 0; p < 6; ++p) us[p] = u[p];
     double *Uo = out + n3 + 6 * (size_t)b;
     for (int h = 0; h < 2; ++h)

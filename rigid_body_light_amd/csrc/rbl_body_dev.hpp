@@ -1,0 +1,58 @@
+// rbl_body_dev.hpp -- device helpers shared by the per-body kernels (rbl_body_dev.hip, rbl_mixed.hip): ONE copy of the K / K^T
+// formulas, of the ordered workgroup sum and of the 6 x 6 substitution, so the kernels that restate a body's operators cannot
+// drift apart.
+#pragma once
+#include <hip/hip_runtime.h>
+
+// (K_b u)_k = u_lin + u_ang x l_k     (reference c_rigid_obj.cpp:368-383, :404)
+__device__ __forceinline__ void rbl_KU(const double *l, const double *u, double &k0, double &k1, double &k2)
+{
+  const double *om = u + 3;
+  k0 = u[0] + l[2] * om[1] - l[1] * om[2];
+  k1 = u[1] + l[0] * om[2] - l[2] * om[0];
+  k2 = u[2] + l[1] * om[0] - l[0] * om[1];
+}
+
+// K_b^T v blob by blob: f += (v, l_k x v)     (:410)
+__device__ __forceinline__ void rbl_KT_acc(const double *l, double v0, double v1, double v2, double (&f)[6])
+{
+  f[0] += v0; f[1] += v1; f[2] += v2;
+  f[3] += l[1] * v2 - l[2] * v1;
+  f[4] += l[2] * v0 - l[0] * v2;
+  f[5] += l[0] * v1 - l[1] * v0;
+}
+
+// sums of NV values over a workgroup of NT threads (NT a power of two) by an LDS tree in one fixed order; every thread gets them
+template <int NV, int NT>
+__device__ __forceinline__ void rbl_block_sum(double (&v)[NV], double (*s)[NT], int t)
+{
+#pragma unroll
+  for (int q = 0; q < NV; ++q) s[q][t] = v[q];
+  __syncthreads();
+  for (int st = NT / 2; st > 0; st >>= 1) {
+    if (t < st) {
+#pragma unroll
+      for (int q = 0; q < NV; ++q) s[q][t] += s[q][t + st];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < NV; ++q) v[q] = s[q][0];
+  __syncthreads();
+}
+
+// u = (L L^T)^-1 g for a 6 x 6 lower Cholesky factor L, row-major (the per-body N = K^T invM K of the preconditioners, :601-608)
+__device__ __forceinline__ void rbl_chol6_solve(const double *L, const double *g, double *u)
+{
+  double y[6];
+  for (int p = 0; p < 6; ++p) {
+    double v = g[p];
+    for (int q = 0; q < p; ++q) v -= L[6 * p + q] * y[q];
+    y[p] = v / L[6 * p + p];
+  }
+  for (int p = 5; p >= 0; --p) {
+    double v = y[p];
+    for (int q = p + 1; q < 6; ++q) v -= L[6 * q + p] * u[q];
+    u[p] = v / L[6 * p + p];
+  }
+}

@@ -139,6 +139,7 @@ static const RblBufRow kDevBufs[] = {
     {&rbl_ctx::d_ens_w, RBL_BUF_SCRATCH},         // ensemble step workspace: reserved at the start of each ensemble entry point
     {&rbl_ctx::d_vf, RBL_BUF_SCRATCH},            // velocity field, host form: reserved at its start, within one call
     {&rbl_ctx::d_vfw, RBL_BUF_SCRATCH},           // velocity field: packed sources and slabs, reserved right before its launches
+    {&rbl_ctx::d_mx, RBL_BUF_SCRATCH},            // mixed solve: reserved once, at the start of each section 7 entry point
 };
 
 // the poison pattern, on the context's stream; nothing while the stream is being captured into a graph (a capture may not

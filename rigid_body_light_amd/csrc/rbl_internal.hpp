@@ -218,6 +218,8 @@ struct rbl_ctx {
   RblDevBuf d_vf;                                   // host form's staging: points | u | lambda | r
   RblDevBuf d_vfw;                                  // packed sources | partial-sum slabs of the chunks
   std::vector<double> ens_cfg_host;                 // the reference configuration d_ens holds
+  // prescribed kinematics (rbl_mixed.hip; include/rbl.h section 7)
+  RblDevBuf d_mx;                                   // rhs | x | invM slip | body_in | slip | U | F | model loads | mask
   // lanczos
   int lanczos_max_iter = 100;
   bool lanczos_out_norm = true;  // preconditioned root: final stopping test in the Euclidean norm of the increment (RBL_OPT_LANCZOS_EUCLID_NORM)

@@ -1,0 +1,387 @@
+// rbl_mixed.hip -- prescribed kinematics (include/rbl.h section 7): any subset of the bodies moves as told, the others stay free;
+// one GMRES solve of the saddle system's size returns the blob forces, the free velocities and the loads the prescribed bodies need.
+// Shared internals are declared in rbl_api_internal.hpp.  Nothing here falls back to a CPU path.
+//
+// The system:  A x = [M lambda - K (D_f U) ; D_f K^T lambda + D_p U] = [slip + K_p U_p ; -F_f on free bodies, 0 on prescribed ones]
+// (D_f, D_p: 0/1 per body).  The six body slots of a prescribed body carry the identity, start at 0 and stay 0 through every
+// Krylov vector, so |rhs| is the norm of the physical right-hand side alone.  The mobility product is the library's own
+// (apply_M_enqueue, untouched); what is new around it -- the masked K / K^T tail, the masked preconditioner tails, the right-hand
+// side and the split of the solution -- are the O(N) kernels below: one workgroup per body, the mask read once per workgroup (the
+// branch on it is uniform), deterministic LDS tree sums, no atomics; the K / K^T formulas, the workgroup sum and the 6 x 6
+// substitution are rbl_body_dev.hpp's, shared with rbl_body_dev.hip.  The Arnoldi recurrence, the Hessenberg solve and the
+// convergence test are gmres_saddle_core_'s (gmres_core_with_ops).
+#include <cstring>
+#include <vector>
+
+#include "rbl_api_internal.hpp"
+#include "rbl_body_dev.hpp"
+
+namespace {
+
+constexpr int MT = 256;
+
+// right-hand side: top = slip + K_p U_p, bottom = -F_b (free body) or 0 (prescribed body)
+__global__ __launch_bounds__(MT) void k_mx_rhs(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
+                                               const double *__restrict__ body_in, const double *__restrict__ slip, int N_blb,
+                                               long n3, double *__restrict__ rhs)
+{
+  const int b = blockIdx.x, t = threadIdx.x;
+  const bool pres = mask[b] != 0;
+  const double *u = body_in + 6 * (size_t)b;
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    double r0 = slip ? slip[idx] : 0.0, r1 = slip ? slip[idx + 1] : 0.0, r2 = slip ? slip[idx + 2] : 0.0;
+    if (pres) {
+      double k0, k1, k2;
+      rbl_KU(lever + idx, u, k0, k1, k2);
+      r0 += k0; r1 += k1; r2 += k2;
+    }
+    rhs[idx] = r0; rhs[idx + 1] = r1; rhs[idx + 2] = r2;
+  }
+  if (t < 6) rhs[n3 + 6 * (size_t)b + t] = pres ? 0.0 : -u[t];
+}
+
+// the operator's tail after sub = M lambda: out = [sub - K (D_f U) ; D_f K^T lambda + D_p U]
+__global__ __launch_bounds__(MT) void k_mx_op_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
+                                                   const double *__restrict__ x, const double *__restrict__ sub, int N_blb, long n3,
+                                                   double *__restrict__ out)
+{
+  __shared__ double s[6][MT];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const double *u = x + n3 + 6 * (size_t)b;
+  if (mask[b]) {                                         // prescribed: no velocity unknown, no balance row
+    for (int k = t; k < N_blb; k += MT) {
+      const size_t idx = 3 * ((size_t)b * N_blb + k);
+      out[idx] = sub[idx]; out[idx + 1] = sub[idx + 1]; out[idx + 2] = sub[idx + 2];
+    }
+    if (t < 6) out[n3 + 6 * (size_t)b + t] = u[t];
+    return;
+  }
+  double f[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    const double *l = lever + idx;
+    double k0, k1, k2;
+    rbl_KU(l, u, k0, k1, k2);
+    out[idx] = sub[idx] - k0; out[idx + 1] = sub[idx + 1] - k1; out[idx + 2] = sub[idx + 2] - k2;
+    rbl_KT_acc(l, x[idx], x[idx + 1], x[idx + 2], f);
+  }
+  rbl_block_sum<6, MT>(f, s, t);
+  if (t < 6) out[n3 + 6 * (size_t)b + t] = f[t];
+}
+
+// block preconditioner after y1 = invM slip (ONE pass over the per-body factors, all bodies).  Free body: what k_pc_block_tail does
+// with the force block's sign restored -- f = K^T y1, U = N^-1 (g - f), lambda = y1 + (invM K) U, the exact inverse of
+// [M_b -K_b; K_b^T 0] on [slip_b; g_b].  Prescribed body: lambda = y1, the six body slots pass through.
+__global__ __launch_bounds__(MT) void k_mx_pc_block_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
+                                                         const double *__restrict__ y1, const double *__restrict__ MK, long stride,
+                                                         const double *__restrict__ NL, const double *__restrict__ in, int N_blb,
+                                                         long n3, double *__restrict__ out)
+{
+  __shared__ double s[6][MT];
+  __shared__ double us[6];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const double *g = in + n3 + 6 * (size_t)b;
+  if (mask[b]) {
+    for (int k = t; k < N_blb; k += MT) {
+      const size_t idx = 3 * ((size_t)b * N_blb + k);
+      out[idx] = y1[idx]; out[idx + 1] = y1[idx + 1]; out[idx + 2] = y1[idx + 2];
+    }
+    if (t < 6) out[n3 + 6 * (size_t)b + t] = g[t];
+    return;
+  }
+  double f[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    rbl_KT_acc(lever + idx, y1[idx], y1[idx + 1], y1[idx + 2], f);
+  }
+  rbl_block_sum<6, MT>(f, s, t);
+  if (t == 0) {
+    double r[6], u[6];
+    for (int p = 0; p < 6; ++p) r[p] = g[p] - f[p];
+    rbl_chol6_solve(NL + 36 * (size_t)b, r, u);
+    for (int p = 0; p < 6; ++p) { us[p] = u[p]; out[n3 + 6 * (size_t)b + p] = u[p]; }
+  }
+  __syncthreads();
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      double acc = y1[idx + d];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) acc = __builtin_fma(MK[(size_t)c * stride + idx + d], us[c], acc);
+      out[idx + d] = acc;
+    }
+  }
+}
+
+// diagonal preconditioner (invM2: the self-block scaling per blob, x/y and z).  Free body: k_pc_diag_apply with the force block's
+// sign restored; prescribed body: lambda = invM slip, the six body slots pass through.
+__global__ __launch_bounds__(MT) void k_mx_pc_diag(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
+                                                   const double *__restrict__ invM2, const double *__restrict__ NL, int N_blb, long n3,
+                                                   const double *__restrict__ in, double *__restrict__ out)
+{
+  __shared__ double s[6][MT];
+  __shared__ double us[6];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const double *g = in + n3 + 6 * (size_t)b;
+  if (mask[b]) {
+    for (int k = t; k < N_blb; k += MT) {
+      const size_t i = (size_t)b * N_blb + k;
+      out[3 * i] = invM2[2 * i] * in[3 * i]; out[3 * i + 1] = invM2[2 * i] * in[3 * i + 1];
+      out[3 * i + 2] = invM2[2 * i + 1] * in[3 * i + 2];
+    }
+    if (t < 6) out[n3 + 6 * (size_t)b + t] = g[t];
+    return;
+  }
+  double f[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = t; k < N_blb; k += MT) {                  // K^T (invM slip)
+    const size_t i = (size_t)b * N_blb + k;
+    rbl_KT_acc(lever + 3 * i, invM2[2 * i] * in[3 * i], invM2[2 * i] * in[3 * i + 1], invM2[2 * i + 1] * in[3 * i + 2], f);
+  }
+  rbl_block_sum<6, MT>(f, s, t);
+  if (t == 0) {
+    double r[6], u[6];
+    for (int p = 0; p < 6; ++p) r[p] = g[p] - f[p];
+    rbl_chol6_solve(NL + 36 * (size_t)b, r, u);
+    for (int p = 0; p < 6; ++p) { us[p] = u[p]; out[n3 + 6 * (size_t)b + p] = u[p]; }
+  }
+  __syncthreads();
+  for (int k = t; k < N_blb; k += MT) {                  // lambda = invM (slip + K U)
+    const size_t i = (size_t)b * N_blb + k;
+    double k0, k1, k2;
+    rbl_KU(lever + 3 * i, us, k0, k1, k2);
+    out[3 * i] = invM2[2 * i] * (in[3 * i] + k0);
+    out[3 * i + 1] = invM2[2 * i] * (in[3 * i + 1] + k1);
+    out[3 * i + 2] = invM2[2 * i + 1] * (in[3 * i + 2] + k2);
+  }
+}
+
+// free-space body-frame tables: `out` holds the ordinary preconditioner's answer for every body; the prescribed ones take
+// lambda = y1 (a second factor application) and their six body slots from the input instead
+__global__ __launch_bounds__(MT) void k_mx_pc_select(const uint8_t *__restrict__ mask, const double *__restrict__ y1,
+                                                     const double *__restrict__ in, int N_blb, long n3, double *__restrict__ out)
+{
+  const int b = blockIdx.x, t = threadIdx.x;
+  if (!mask[b]) return;
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    out[idx] = y1[idx]; out[idx + 1] = y1[idx + 1]; out[idx + 2] = y1[idx + 2];
+  }
+  if (t < 6) out[n3 + 6 * (size_t)b + t] = in[n3 + 6 * (size_t)b + t];
+}
+
+// the solution split: U = the solved velocity (free) or the prescribed one (echoed); F = the given load (free, echoed) or
+// -K_b^T lambda (prescribed)
+__global__ __launch_bounds__(MT) void k_mx_split(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
+                                                 const double *__restrict__ body_in, const double *__restrict__ x, int N_blb, long n3,
+                                                 double *__restrict__ U, double *__restrict__ F)
+{
+  __shared__ double s[6][MT];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const size_t o = 6 * (size_t)b;
+  if (!mask[b]) {
+    if (t < 6) { U[o + t] = x[n3 + o + t]; F[o + t] = body_in[o + t]; }
+    return;
+  }
+  double f[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    rbl_KT_acc(lever + idx, x[idx], x[idx + 1], x[idx + 2], f);
+  }
+  rbl_block_sum<6, MT>(f, s, t);
+  if (t < 6) { U[o + t] = body_in[o + t]; F[o + t] = -f[t]; }
+}
+
+// v += add on the six slots of every free body (the force model's loads enter the free bodies only)
+__global__ void k_mx_add_free(const uint8_t *__restrict__ mask, const double *__restrict__ add, int nb6, double *__restrict__ v)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nb6 && !mask[i / 6]) v[i] += add[i];
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+
+struct MxBuf {           // the one workspace of a section 7 entry point (rbl_ctx::d_mx)
+  double *rhs, *x, *y1, *body_in, *slip, *U, *F, *model;
+  uint8_t *mask;
+};
+
+int mx_reserve(rbl_ctx *c, MxBuf &B)
+{
+  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nsys = n3 + nb6;
+  const int rc = rbl_dev_reserve(c, c->d_mx, sizeof(double) * (2 * nsys + 2 * n3 + 4 * nb6) + (size_t)c->S.N_bod);
+  if (rc) return rc;
+  B.rhs = (double *)c->d_mx.p; B.x = B.rhs + nsys; B.y1 = B.x + nsys; B.slip = B.y1 + n3; B.body_in = B.slip + n3;
+  B.U = B.body_in + nb6; B.F = B.U + nb6; B.model = B.F + nb6;
+  B.mask = (uint8_t *)(B.model + nb6);
+  return RBL_OK;
+}
+
+struct MxSolve {
+  const MxBuf *B;
+  bool any_prescribed;
+};
+
+int mx_op(rbl_ctx *c, void *user, const double *d_x, double *d_out)
+{
+  const MxSolve *m = (const MxSolve *)user;
+  const RblBodyState &S = c->S;
+  const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N;
+  int rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3); if (rc) return rc;
+  if ((rc = apply_M_enqueue(c, S.wall, d_x, (const double *)c->d_pos.p, N, 0, N, (double *)c->d_sad.p))) return rc;
+  hipLaunchKernelGGL(k_mx_op_tail, dim3((unsigned)S.N_bod), dim3(MT), 0, c->stream, (const double *)c->d_lever.p, m->B->mask, d_x,
+                     (const double *)c->d_sad.p, S.N_blb, (long)n3, d_out);
+  return RBL_OK;
+}
+
+int mx_pc(rbl_ctx *c, void *user, const double *d_in, double *d_out)
+{
+  const MxSolve *m = (const MxSolve *)user;
+  const RblBodyState &S = c->S;
+  const long n3 = 3 * (long)S.N_bod * S.N_blb;
+  const double *lev = (const double *)c->d_lever.p;
+  const dim3 grid((unsigned)S.N_bod), block(MT);
+  int rc;
+  if (!S.block_pc) {
+    hipLaunchKernelGGL(k_mx_pc_diag, grid, block, 0, c->stream, lev, m->B->mask, (const double *)c->d_invM2.p, (const double *)c->d_NL.p,
+                       S.N_blb, n3, d_in, d_out);
+    return RBL_OK;
+  }
+  if (bf_on(c) && c->bf_tables) {
+    // free space, small bodies: the one-launch body-frame preconditioner serves the free bodies as it is; the prescribed ones cost
+    // a second application of the shared factor
+    const double keep = c->pc_fsign;
+    c->pc_fsign = 1.0;
+    rc = rbl_apply_PC_dev(c, d_in, d_out);
+    c->pc_fsign = keep;
+    if (rc || !m->any_prescribed) return rc;
+    if ((rc = blk_solve(c, 0, S.N_bod, d_in, m->B->y1, 1, 0, 0))) return rc;
+    hipLaunchKernelGGL(k_mx_pc_select, grid, block, 0, c->stream, m->B->mask, (const double *)m->B->y1, d_in, S.N_blb, n3, d_out);
+    return RBL_OK;
+  }
+  if ((rc = blk_solve(c, 0, S.N_bod, d_in, m->B->y1, 1, 0, 0))) return rc;                   // invM slip, every body: ONE pass
+  RblPhase ph(c, RBL_T_PERBODY);
+  hipLaunchKernelGGL(k_mx_pc_block_tail, grid, block, 0, c->stream, lev, m->B->mask, (const double *)m->B->y1, (const double *)c->d_pcMK.p,
+                     n3, (const double *)c->d_NL.p, d_in, S.N_blb, n3, d_out);
+  return RBL_OK;
+}
+
+// argument checks that need no device
+int mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const void *body_in, int max_iter, double rtol, bool host_form,
+             int *n_prescribed)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (!prescribed || !body_in) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": prescribed or body_in is NULL");
+  if (max_iter < 1 || !(rtol >= 0.0)) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": need max_iter >= 1 and rtol >= 0");
+  if (max_iter + 1 > rbl_gmres_max_vectors()) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": at most 255 iterations (no restart)");
+  int rc = host_form ? need_K(c) : need_config(c); if (rc) return rc;
+  int np = 0;
+  for (int b = 0; b < c->S.N_bod; ++b) {
+    if (prescribed[b] > 1) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": entries of prescribed must be 0 or 1");
+    np += prescribed[b];
+  }
+  if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": not available on a context with a communicator");
+  *n_prescribed = np;
+  return RBL_OK;
+}
+
+// the solve on buffers of B (mask, body_in and slip in place): leaves x = [lambda ; U_f], B.U and B.F; nothing is read back
+// beyond the solver's convergence tests
+int mx_solve(rbl_ctx *c, const MxBuf &B, bool have_slip, int n_prescribed, int max_iter, double rtol, int *iters, double *resid)
+{
+  RblPhase ph_total(c, RBL_T_TOTAL);
+  int rc = rbl_prepare_dev(c); if (rc) return rc;                        // resident geometry, the preconditioner of this configuration
+  const RblBodyState &S = c->S;
+  const long n3 = 3 * (long)S.N_bod * S.N_blb;
+  const double *lev = (const double *)c->d_lever.p;
+  const dim3 grid((unsigned)S.N_bod), block(MT);
+  hipLaunchKernelGGL(k_mx_rhs, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, (const double *)B.body_in,
+                     have_slip ? (const double *)B.slip : nullptr, S.N_blb, n3, B.rhs);
+  MxSolve m{&B, n_prescribed > 0};
+  const RblSolveOps ops{mx_op, mx_pc, &m};
+  if ((rc = gmres_core_with_ops(c, &ops, B.rhs, max_iter, rtol, B.x, iters, resid))) return rc;
+  hipLaunchKernelGGL(k_mx_split, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, (const double *)B.body_in, (const double *)B.x,
+                     S.N_blb, n3, B.U, B.F);
+  RBL_HIP(c, hipGetLastError());
+  return RBL_OK;
+}
+
+// host arrays in, host arrays out; model: add the force model's loads to the free bodies (the step)
+int mx_host(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
+            bool model, double *lambda, double *U, double *F, int *iters, double *resid)
+{
+  int np = 0;
+  int rc = mx_check(c, who, prescribed, body_in, max_iter, rtol, true, &np); if (rc) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
+  MxBuf B;
+  if ((rc = mx_reserve(c, B))) return rc;
+  if ((rc = copy_h2d(c, B.mask, prescribed, (size_t)c->S.N_bod))) return rc;
+  if ((rc = copy_h2d(c, B.body_in, body_in, sizeof(double) * nb6))) return rc;
+  if (slip && (rc = copy_h2d(c, B.slip, slip, sizeof(double) * n3))) return rc;
+  if (model && c->ia_on && np < c->S.N_bod) {            // -K^T f_phys at q^n, free bodies only (no free body: nothing feels the model)
+    RBL_HIP(c, hipMemsetAsync(B.model, 0, sizeof(double) * nb6, c->stream));
+    if ((rc = ia_add_to_step_force(c, B.model))) return rc;
+    hipLaunchKernelGGL(k_mx_add_free, dim3((unsigned)((nb6 + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)B.mask,
+                       (const double *)B.model, (int)nb6, B.body_in);
+  }
+  if ((rc = mx_solve(c, B, slip != nullptr, np, max_iter, rtol, iters, resid))) return rc;
+  if (lambda && (rc = copy_d2h(c, lambda, B.x, sizeof(double) * n3))) return rc;
+  if (U && (rc = copy_d2h(c, U, B.U, sizeof(double) * nb6))) return rc;
+  if (F && (rc = copy_d2h(c, F, B.F, sizeof(double) * nb6))) return rc;
+  return finish_and_check(c);
+}
+
+}  // namespace
+
+// ============================================================================
+// 7. prescribed kinematics (include/rbl.h)
+// ============================================================================
+int rbl_solve_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
+                    double *lambda, double *U, double *F, int *iters, double *resid)
+{
+  if (c && (!U || !F)) return rbl_fail(c, RBL_ERR_ARG, "solve_mixed: U or F is NULL");
+  return mx_host(c, "solve_mixed", prescribed, body_in, slip, max_iter, rtol, false, lambda, U, F, iters, resid);
+}
+
+int rbl_solve_mixed_dev(rbl_ctx *c, const uint8_t *prescribed, const double *d_body_in, const double *d_slip, int max_iter, double rtol,
+                        double *d_lambda, double *d_U, double *d_F, int *iters, double *resid)
+{
+  if (c && (!d_U || !d_F)) return rbl_fail(c, RBL_ERR_ARG, "solve_mixed_dev: U or F is NULL");
+  int np = 0;
+  int rc = mx_check(c, "solve_mixed_dev", prescribed, d_body_in, max_iter, rtol, false, &np); if (rc) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
+  MxBuf B;
+  if ((rc = mx_reserve(c, B))) return rc;
+  // the mask goes up from the context's pinned megabyte (idle between the solver's read-backs, which drain the stream): a true
+  // asynchronous copy, so the caller's array may go after the call and the stream is not drained for it
+  constexpr size_t pin_bytes = (size_t)1 << 20;
+  if ((size_t)c->S.N_bod <= pin_bytes) {
+    if (!c->h_pin) RBL_HIP(c, hipHostMalloc(&c->h_pin, pin_bytes, hipHostMallocDefault));
+    std::memcpy(c->h_pin, prescribed, (size_t)c->S.N_bod);
+    RBL_HIP(c, hipMemcpyAsync(B.mask, c->h_pin, (size_t)c->S.N_bod, hipMemcpyHostToDevice, c->stream));
+  } else {
+    RBL_HIP(c, hipMemcpyAsync(B.mask, prescribed, (size_t)c->S.N_bod, hipMemcpyHostToDevice, c->stream));
+    RBL_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  RBL_HIP(c, hipMemcpyAsync(B.body_in, d_body_in, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
+  if (d_slip) RBL_HIP(c, hipMemcpyAsync(B.slip, d_slip, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
+  if ((rc = mx_solve(c, B, d_slip != nullptr, np, max_iter, rtol, iters, resid))) return rc;
+  if (d_lambda) RBL_HIP(c, hipMemcpyAsync(d_lambda, B.x, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
+  RBL_HIP(c, hipMemcpyAsync(d_U, B.U, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
+  RBL_HIP(c, hipMemcpyAsync(d_F, B.F, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
+  return RBL_OK;
+}
+
+int rbl_step_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol, double *F,
+                   int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  std::vector<double> U((size_t)6 * (size_t)(c->S.N_bod > 0 ? c->S.N_bod : 1));
+  const int rc = mx_host(c, "step_mixed", prescribed, body_in, slip, max_iter, rtol, true, nullptr, U.data(), F, iters, resid);
+  if (rc) return rc;
+  c->step_hist_n = 0;                                    // the warm starts of rbl_step_deterministic extrapolate over ITS steps only
+  return rbl_evolve_X_Q(c, U.data());
+}

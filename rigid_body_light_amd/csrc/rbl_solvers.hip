@@ -88,7 +88,7 @@ int rbl_gmres_saddle_dev(rbl_ctx *c, const double *d_rhs, int max_iter, double r
 }
 
 static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
-                              double *resid_out);
+                              double *resid_out, const RblSolveOps *ops = nullptr);
 
 // any invertible right preconditioner leaves the solution unchanged: inside the solve the force block of apply_PC
 // takes the sign that makes A P^-1 ~ I (see rbl_ctx::pc_fsign); the bound apply_PC keeps the reference's convention
@@ -102,8 +102,16 @@ static int gmres_saddle_core(rbl_ctx *c, const double *d_rhs, int max_iter, doub
   return rc;
 }
 
+int gmres_core_with_ops(rbl_ctx *c, const RblSolveOps *ops, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
+                        double *resid_out)
+{
+  if (!ops || !ops->op || !ops->pc) return rbl_fail(c, RBL_ERR_ARG, "gmres: no operator");
+  return gmres_saddle_core_(c, d_rhs, max_iter, rtol, d_x, iters_out, resid_out, ops);
+}
+
+// ops: the caller's operator and preconditioner instead of rbl_apply_saddle_dev / rbl_apply_PC_dev (RblSolveOps: nothing fused)
 static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
-                              double *resid_out)
+                              double *resid_out, const RblSolveOps *ops)
 {
   int rc = sync_bodies(c); if (rc) return rc;
   if (!d_rhs || !d_x || max_iter < 1) return rbl_fail(c, RBL_ERR_ARG, "gmres: bad arguments");
@@ -128,7 +136,7 @@ static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, dou
   // looks at every iteration since the one before, so the solve still ends at the first iteration that passes.
   const int check_every = ((int64_t)S.N_bod * S.N_blb > 20000) ? 1 : 4;
   int next_check = check_every, last_checked = 0;
-  if (check_every > 1 && c->gmres_predict && c->gmres_last_used > 0) next_check = c->gmres_last_used >= 8 ? c->gmres_last_used - 2 : c->gmres_last_used;
+  if (check_every > 1 && c->gmres_predict && c->gmres_last_used > 0 && !ops) next_check = c->gmres_last_used >= 8 ? c->gmres_last_used - 2 : c->gmres_last_used;
   int used = 0;
   double resid = 1.0;
   // least squares min |beta e1 - H_k y| by Givens rotations on a host copy; returns the residual estimate
@@ -176,6 +184,7 @@ static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, dou
   // falls between the two gets |w| from the same partial sums on the host.  The last possible iteration normalises as before.
   RblNormFold pend;                                    // set: V_j and H[j][j-1] are still to be written, from w
   auto apply_pc = [&](int jv) -> int {                 // z = P^-1 V_jv
+    if (ops) return ops->pc(c, ops->user, V + (size_t)jv * nsys, z);
     c->ktl_arm = true;                                 // the PC's K^T Lambda by-product feeds the product that follows
     const double *src = V + (size_t)jv * nsys;
     if (pend.part) { c->pc_fold = pend; src = w; pend = RblNormFold(); }
@@ -188,17 +197,17 @@ static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, dou
     z_ready = false;
     // inexact Krylov: the j-th product may be in error by ~ rtol / |r_{j-1}| (relative); the relaxed kernel's ~1e-6 is
     // admissible once the residual estimate is below rtol x 1e5 (an order of magnitude in hand)
-    c->sym_tune.relaxed = (c->gmres_relax == 1 && rtol > 0.0 && check_every == 1 && resid <= rtol * 1.0e5) ? 1 : 0;
-    c->fuse_dotV = V; c->fuse_dotK = j + 1; c->fuse_dotPart = part;   // (small systems: the product's last kernel starts the Gram-Schmidt pass)
-    rc = rbl_apply_saddle_dev(c, z, w);
-    const int fused_np = c->fuse_dots_np;
+    c->sym_tune.relaxed = (!ops && c->gmres_relax == 1 && rtol > 0.0 && check_every == 1 && resid <= rtol * 1.0e5) ? 1 : 0;
+    if (!ops) { c->fuse_dotV = V; c->fuse_dotK = j + 1; c->fuse_dotPart = part; }   // (small systems: the product's last kernel starts the Gram-Schmidt pass)
+    rc = ops ? ops->op(c, ops->user, z, w) : rbl_apply_saddle_dev(c, z, w);
+    const int fused_np = ops ? 0 : c->fuse_dots_np;
     c->fuse_dotV = nullptr; c->fuse_dotK = 0; c->fuse_dotPart = nullptr; c->fuse_dots_np = 0;
     c->sym_tune.relaxed = 0;
     c->ktl_arm = false; c->ktl_of = nullptr;
     if (rc) return rc;
     double *Hcol = H + (size_t)j * ldh;
     // classical Gram-Schmidt twice, H[j+1][j] = |w|, V_{j+1} = w / |w|: four launches (three when the product left the first sums)
-    const bool fold = j + 1 < m && pc_can_fold(c);
+    const bool fold = !ops && j + 1 < m && pc_can_fold(c);
     const double *npart = nullptr; int nnp = 0;
     rbl_launch_arnoldi_step(c->stream, V, nsys, j + 1, w, Hcol, V + (size_t)(j + 1) * nsys, part, fused_np, fold, &npart, &nnp);
     if (fold) { pend.part = npart; pend.np = nnp; pend.vnext = V + (size_t)(j + 1) * nsys; pend.hout = Hcol + (j + 1); }
@@ -255,10 +264,10 @@ static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, dou
     if (!std::isfinite(y[k])) return rbl_fail(c, RBL_ERR_NONFINITE, "gmres: non-finite Hessenberg solve");
   if ((rc = upload_coef(c, d_y, y.data(), used, 0))) return rc;
   rbl_launch_lanczos_combine(c->stream, nsys, V, d_y, used, z);                        // z = V y
-  if ((rc = rbl_apply_PC_dev(c, z, d_x))) return rc;                                   // x = P^-1 z
+  if ((rc = ops ? ops->pc(c, ops->user, z, d_x) : rbl_apply_PC_dev(c, z, d_x))) return rc;   // x = P^-1 z
   if (iters_out) *iters_out = used;
   if (resid_out) *resid_out = resid;
-  if (rtol > 0.0) c->gmres_last_used = used;
+  if (rtol > 0.0 && !ops) c->gmres_last_used = used;
   return finish_and_check(c);
 }
 

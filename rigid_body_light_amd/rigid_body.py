@@ -10,7 +10,8 @@ reference src/Rigid.py:54,60,66).
 Beyond the reference surface (its C++ has these, its Python does not): `solve_saddle`, `solve_saddle_multi`,
 `body_mobility_matrix`, `M_half_W`, `M_RFD`,
 `KTinv_RFD`, `M_RFD_cfgs`, `M_RFD_from_U`, `KT_RFD_from_U`, `evolve_rigid_bodies_RFD`, `apply_M_multi`,
-`dense_mobility`, `velocity_field` (the flow at arbitrary points), and a force model the reference does not have (`set_interactions`, `interaction_forces`).
+`dense_mobility`, `velocity_field` (the flow at arbitrary points), prescribed kinematics (`solve_mixed`, `step_mixed`,
+`body_resistance_matrix`: bodies that are held or driven, and the loads that takes), and a force model the reference does not have (`set_interactions`, `interaction_forces`).
 """
 import numpy as np
 
@@ -243,6 +244,77 @@ class RigidBody:
             r = r.reshape(-1)
         u = self.cb.velocity_field(pts.reshape(-1), lam.reshape(-1), r)
         return u.reshape(pts.shape)
+
+    # ------------------------------------------------------------------ prescribed kinematics (include/rbl.h section 7)
+    def _prescribed_mask(self, prescribed):
+        """boolean array of N_bodies (dtype bool: the only form read as a mask), or a list of body indices (any integer array,
+        0/1 values included) -> uint8 mask; ValueError before the library is called"""
+        p = np.asarray(prescribed)
+        nb = self.N_bodies
+        if p.dtype == np.bool_:
+            if p.size != nb:
+                raise ValueError(f"prescribed: a boolean array must have N_bodies = {nb} entries. Got shape: {p.shape}")
+            return np.ascontiguousarray(p.reshape(-1), dtype=np.uint8)
+        if p.size and not np.issubdtype(p.dtype, np.integer):
+            raise ValueError(f"prescribed must be a boolean array of N_bodies or a list of body indices. Got dtype: {p.dtype}")
+        idx = p.reshape(-1).astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= nb):
+            raise ValueError(f"prescribed: body indices must lie in [0, {nb})")
+        if np.unique(idx).size != idx.size:
+            raise ValueError("prescribed: a body index appears twice (integers are body indices; a 0/1 mask must have dtype bool)")
+        mask = np.zeros(nb, dtype=np.uint8)
+        mask[idx] = 1
+        return mask
+
+    def _mixed_args(self, prescribed, body_in, slip):
+        mask = self._prescribed_mask(prescribed)
+        bi = np.asarray(body_in, dtype=np.float64)
+        if bi.size != 6 * self.N_bodies:
+            raise ValueError(f"body_in must have total size 6*N_bodies = {6 * self.N_bodies}. Got shape: {bi.shape}")
+        sl = None
+        if slip is not None:
+            sl = np.asarray(slip, dtype=np.float64)
+            if sl.size != 3 * self.total_blobs:
+                raise ValueError(f"slip must have total size 3*N_blobs = {3 * self.total_blobs}. Got shape: {sl.shape}")
+            sl = sl.reshape(-1)
+        return mask, bi.reshape(-1), sl
+
+    def solve_mixed(self, prescribed, body_in, slip=None, max_iter=100, rtol=1.0e-8):
+        """Prescribed kinematics: the bodies in `prescribed` (boolean array of N_bodies, or a list of body indices) move with the
+        velocity given in their six slots of body_in (translation, rotation; zeros hold a body), the others are free and carry their
+        load F_b there (the convention of step_deterministic's F_body, rhs [slip ; -F]).  ONE GMRES solve on the GPU of the size and
+        per-iteration cost of a mobility solve; it takes 2-3.5 times the iterations when a quarter to all of the bodies are
+        prescribed.  Only an array of dtype bool is read as a mask: integers are ALWAYS body indices ([0, 1] prescribes bodies 0
+        and 1), so convert a 0/1 integer mask with .astype(bool).  -> (lambda, U, F, iterations, residual estimate): blob forces (what velocity_field takes), all
+        body velocities (prescribed ones echoed), all body loads (free ones echoed, prescribed ones -K_b^T lambda: the load it takes
+        to move them as told)."""
+        mask, bi, sl = self._mixed_args(prescribed, body_in, slip)
+        return self.cb.solve_mixed(mask, bi, sl, int(max_iter), float(rtol))
+
+    def step_mixed(self, prescribed, body_in, slip=None, max_iter=50, rtol=1.0e-8):
+        """One deterministic time step with prescribed bodies: solve_mixed at the current configuration, then
+        evolve_rigid_bodies(U) -- a prescribed body advances by its own velocity, a held one stays.  With the force model on its
+        loads are added to the FREE bodies only; the F returned for a prescribed body is the total load everything other than the
+        fluid supplies (the model's share included).  -> (F, iterations, residual estimate)"""
+        mask, bi, sl = self._mixed_args(prescribed, body_in, slip)
+        return self.cb.step_mixed(mask, bi, sl, int(max_iter), float(rtol))
+
+    def body_resistance_matrix(self, max_iter=100, rtol=1.0e-8, columns=None):
+        """The (6 N_bodies) x (6 N_bodies) body resistance matrix R = N^-1 of the current configuration, the inverse of
+        `body_mobility_matrix` (symmetric positive definite): the PHYSICAL loads that move the bodies with velocities U are R U.
+        Every body prescribed, one solve_mixed per unit velocity (one after the other).  The F of solve_mixed follows the reference
+        convention of step_deterministic's F_body (rhs [slip ; -F], U = -N F), so a column here is -F.  columns: only these
+        unit velocities (default all).  -> (R[:, columns], iterations)"""
+        nb6 = 6 * self.N_bodies
+        cols = np.arange(nb6) if columns is None else np.asarray(columns, dtype=int).reshape(-1)
+        everyone = np.ones(self.N_bodies, dtype=bool)
+        R, its = np.zeros((nb6, cols.size)), np.zeros(cols.size, dtype=int)
+        for j, c in enumerate(cols):
+            U = np.zeros(nb6)
+            U[c] = 1.0
+            _, _, F, its[j], _ = self.solve_mixed(everyone, U, max_iter=max_iter, rtol=rtol)
+            R[:, j] = -F
+        return R, its
 
     def apply_M_multi(self, forces, positions):
         """k right-hand sides at once, forces (k, 3N); k >= 4 runs on the fp64 matrix cores."""
