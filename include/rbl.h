@@ -670,15 +670,48 @@ int rbl_velocity_field_info(const rbl_ctx *ctx, int64_t n_points, int64_t n_src,
  * may be NULL), max_iter < 1, rtol < 0 and entries of `prescribed` other than 0 / 1 are RBL_ERR_ARG before any device work; so
  * is a context with a communicator (as for the ensembles) -- sharding the mixed solve is a follow-up.  Results are bitwise
  * reproducible call to call (no float atomics).
- * Not offered: the Brownian midpoint step with prescribed bodies (the scheme carries over with K -> K_f, random displacements
- * and the RFD direction masked to the free bodies; its check is statistical), ensembles and lock-step multi-right-hand-side
- * mixed solves, and per-component constraints (only whole bodies are prescribed). */
+ *
+ * The Brownian midpoint step with prescribed bodies (kBT > 0): rbl_step_brownian with K -> K_f.  With D_f, D_p the 0/1 selectors
+ * of the free and prescribed bodies' six slots and Kinv = (K^T K)^-1 K^T per body, from q^n:
+ *     M^{1/2}W1 (and M^{1/2}W2 with split_rand) at q^n: the blob mobility of ALL blobs, the mask does not enter;
+ *     dq = D_f Kinv W_rfd (prescribed bodies are not displaced),  M_RFD = (1/delta)[M(q + delta/2 dq) - M(q - delta/2 dq)] W_rfd;
+ *     s = slip - kBT M_RFD - BI,  c1, c2, BI as in rbl_RHS_and_Midpoint_dev;
+ *     q^{n+1/2} = q^n displaced by D_f (dt/2) c1 Kinv M^{1/2}W1 + D_p (dt/2) U_p  (a driven body at its own half step, a held
+ *     one stays);
+ *     the mixed solve above at q^{n+1/2} with slip = s and the same body_in (K_p U_p with the midpoint lever arms);
+ *     q^n restored (also on failure), evolve_X_Q(U): a prescribed body advances by exactly dt U_p.
+ * Eliminating lambda, U_f = -Ntilde (F_f + K_f^T M^-1 rhs_top) with Ntilde = (K_f^T M^-1 K_f)^-1: the noise of U_f has covariance
+ * (2 kBT / dt) Ntilde and the midpoint and RFD terms give the drift kBT div_{q_f} Ntilde (the argument of the all-free step with
+ * K_f for K; K_b depends on q_b only); the masks keep the random displacements inside the free coordinates.
+ *
+ *   rbl_RHS_and_Midpoint_mixed      host arrays: s[3 N_blobs], X_half[3 N_bod], Q_half[4 N_bod]; nothing is committed.  Of body_in
+ *                        only the prescribed bodies' velocities are read.  W = [W1 | W2 | W_rfd] (9 N_blobs) or NULL: drawn from
+ *                        `seed` as rbl_step_brownian draws them.  kBT <= 1e-10: s = slip, q^{n+1/2} = q^n.
+ *   rbl_RHS_and_Midpoint_mixed_dev  d_body_in, d_slip (may be NULL), d_W (may be NULL), d_s are device pointers; `prescribed`,
+ *                        X_half and Q_half stay host arrays.  d_s may be d_slip.  One small read-back (12 numbers per body).
+ *   rbl_step_brownian_mixed         host arrays: the whole step; F (may be NULL), iters, resid as rbl_step_mixed -- the F of a held
+ *                        body is its instantaneous load, thermal part included (what a microrheology measurement averages).  The
+ *                        force model enters as in rbl_step_mixed: at q^n, the free bodies only.  kBT <= 1e-10: rbl_step_mixed.
+ *                        s never leaves the device; beyond rbl_step_brownian's and rbl_step_mixed's own traffic the host sees
+ *                        the mask, body_in and 12 numbers per body.
+ * Their refusals are those above plus max_iter > 254 and, when kBT > 1e-10, dt <= 0 or delta <= 0: RBL_ERR_ARG before any device
+ * work.
+ * Not offered: ensembles and lock-step multi-right-hand-side mixed solves, contexts with a communicator, a mask that changes
+ * within a step, and per-component constraints (only whole bodies are prescribed). */
 int rbl_solve_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
                     double *lambda, double *U, double *F, int *iters, double *resid);
 int rbl_solve_mixed_dev(rbl_ctx *ctx, const uint8_t *prescribed, const double *d_body_in, const double *d_slip, int max_iter,
                         double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid);
 int rbl_step_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
                    double *F, int *iters, double *resid);
+int rbl_RHS_and_Midpoint_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
+                               uint64_t seed, int method, int split_rand, double delta, double *s, double *X_half, double *Q_half);
+int rbl_RHS_and_Midpoint_mixed_dev(rbl_ctx *ctx, const uint8_t *prescribed, const double *d_body_in, const double *d_slip,
+                                   const double *d_W, uint64_t seed, int method, int split_rand, double delta, double *d_s,
+                                   double *X_half, double *Q_half);
+int rbl_step_brownian_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
+                            uint64_t seed, int method, int split_rand, double delta, int max_iter, double rtol, double *F,
+                            int *iters, double *resid);
 
 #ifdef __cplusplus
 }

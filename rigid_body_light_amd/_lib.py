@@ -100,6 +100,10 @@ def lib():
         L.rbl_solve_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
         L.rbl_solve_mixed_dev.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
         L.rbl_step_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
+        L.rbl_RHS_and_Midpoint_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, vp, vp, vp]
+        L.rbl_RHS_and_Midpoint_mixed_dev.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, vp, vp, vp]
+        L.rbl_step_brownian_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, C.c_int, dbl, vp, C.POINTER(C.c_int),
+                                              C.POINTER(dbl)]
         _LIB = L
     return _LIB
 
@@ -571,6 +575,42 @@ class DeviceContext:
         self._chk(self.L.rbl_solve_mixed_dev(self.h, m.ctypes.data, d_body_in, d_slip or None, int(max_iter), float(rtol), d_lam or None,
                                              d_U, d_F, C.byref(it), C.byref(res)))
         return it.value, res.value
+
+    def _mixed_sizes(self, who, prescribed):
+        import numpy as np
+        m = np.ascontiguousarray(prescribed, dtype=np.uint8).reshape(-1)
+        nb, nl = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), C.byref(nl)))
+        if m.size != nb.value:
+            raise ValueError(who + ": prescribed must have N_bod entries")
+        return m, nb.value, nl.value
+
+    def RHS_and_Midpoint_mixed_dev(self, prescribed, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s):
+        """right-hand side and predictor of the Brownian step with prescribed bodies on device addresses (prescribed: a host
+        array; d_slip, d_W may be None / 0; d_s: 3 N_blobs) -> (X_half, Q_half) on the host"""
+        import numpy as np
+        m, nb, _ = self._mixed_sizes("RHS_and_Midpoint_mixed_dev", prescribed)
+        X = np.zeros(3 * nb); Q = np.zeros(4 * nb)
+        self._chk(self.L.rbl_RHS_and_Midpoint_mixed_dev(self.h, m.ctypes.data, d_body_in, d_slip or None, d_W or None, int(seed), int(method),
+                                                        int(bool(split_rand)), float(delta), d_s, X.ctypes.data, Q.ctypes.data))
+        return X.reshape(-1, 3), Q.reshape(-1, 4)
+
+    def step_brownian_mixed(self, prescribed, body_in, max_iter=50, rtol=1.0e-8, slip=None, W=None, seed=0, method=2, split_rand=True,
+                            delta=1.0e-4):
+        """one stochastic midpoint step with prescribed bodies inside librbl; host arrays -> (F, iterations, residual estimate)"""
+        import numpy as np
+        m, nb, nl = self._mixed_sizes("step_brownian_mixed", prescribed)
+        bi = np.ascontiguousarray(body_in, dtype=np.float64).reshape(-1)
+        sl = None if slip is None else np.ascontiguousarray(slip, dtype=np.float64).reshape(-1)
+        Wh = None if W is None else np.ascontiguousarray(W, dtype=np.float64).reshape(-1)
+        if bi.size != 6 * nb or (sl is not None and sl.size != 3 * nb * nl) or (Wh is not None and Wh.size != 9 * nb * nl):
+            raise ValueError("step_brownian_mixed: body_in (6 N_bod), slip (3 N_blobs) or W (9 N_blobs) has the wrong size")
+        F = np.empty(6 * nb)
+        it, res = C.c_int(0), C.c_double(0.0)
+        self._chk(self.L.rbl_step_brownian_mixed(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                 None if Wh is None else Wh.ctypes.data, int(seed), int(method), int(bool(split_rand)),
+                                                 float(delta), int(max_iter), float(rtol), F.ctypes.data, C.byref(it), C.byref(res)))
+        return F, it.value, res.value
 
     def blob_positions(self, body_begin, body_end, dout):
         self._chk(self.L.rbl_blob_positions_dev(self.h, body_begin, body_end, dout))

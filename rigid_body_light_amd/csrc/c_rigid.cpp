@@ -477,6 +477,50 @@ struct CManyBodies {
     check(rc);
     return py::make_tuple(F, it, res);
   }
+  // the Brownian midpoint step with prescribed bodies: right-hand side and predictor at q^n -> (s, X_half, Q_half), nothing committed
+  const double *noise_arg(const char *who, const py::object &W, darr &Wa) const
+  {
+    if (W.is_none()) return nullptr;
+    Wa = W.cast<darr>();
+    if (Wa.size() != 3 * n3()) throw std::runtime_error(std::string(who) + ": W must have length 9*N_blobs (W1|W2|W_rfd)");
+    return Wa.data();
+  }
+  py::tuple RHS_and_Midpoint_mixed(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
+                                   bool split_rand, double delta)
+  {
+    darr sl, Wa;
+    const double *sp = mixed_args("RHS_and_Midpoint_mixed", mask, body_in, slip, sl);
+    const double *wp = noise_arg("RHS_and_Midpoint_mixed", W, Wa);
+    const int m = mhalf_method(method);
+    const py::ssize_t nb = n_bod();
+    darr s(n3()), X(3 * nb), Q(4 * nb);
+    int rc;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_RHS_and_Midpoint_mixed(ctx, mask.data(), body_in.data(), sp, wp, seed, m, split_rand ? 1 : 0, delta, s.mutable_data(),
+                                      X.mutable_data(), Q.mutable_data());
+    }
+    check(rc);
+    return py::make_tuple(s, X, Q);
+  }
+  // the whole step -> (F, iterations, residual estimate)
+  py::tuple step_brownian_mixed(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
+                                bool split_rand, double delta, int max_iter, double rtol)
+  {
+    darr sl, Wa;
+    const double *sp = mixed_args("step_brownian_mixed", mask, body_in, slip, sl);
+    const double *wp = noise_arg("step_brownian_mixed", W, Wa);
+    const int m = mhalf_method(method);
+    darr F(6 * (py::ssize_t)n_bod());
+    int it = 0, rc; double res = 0.0;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_step_brownian_mixed(ctx, mask.data(), body_in.data(), sp, wp, seed, m, split_rand ? 1 : 0, delta, max_iter, rtol,
+                                   F.mutable_data(), &it, &res);
+    }
+    check(rc);
+    return py::make_tuple(F, it, res);
+  }
   void set_interactions(double w, double eps_wall, double b_wall, double eps_blob, double b_blob, double r_cut, bool on)
   {
     check(rbl_set_interactions(ctx, w, eps_wall, b_wall, eps_blob, b_blob, r_cut, on ? 1 : 0));
@@ -579,6 +623,12 @@ PYBIND11_MODULE(c_rigid, m)
            py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
       .def("step_mixed", &CManyBodies::step_mixed, py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(),
            py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
+      .def("RHS_and_Midpoint_mixed", &CManyBodies::RHS_and_Midpoint_mixed, py::arg("prescribed"), py::arg("body_in"),
+           py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "cholesky",
+           py::arg("split_rand") = true, py::arg("delta") = 1.0e-4)
+      .def("step_brownian_mixed", &CManyBodies::step_brownian_mixed, py::arg("prescribed"), py::arg("body_in"),
+           py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "lanczos_pc",
+           py::arg("split_rand") = true, py::arg("delta") = 1.0e-4, py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
       .def("set_option", &CManyBodies::set_option, py::arg("name"), py::arg("value"))
       .def("get_option", &CManyBodies::get_option, py::arg("name"))
       .def("handle", &CManyBodies::handle, "address of the underlying rbl_ctx (for the ctypes device API)")

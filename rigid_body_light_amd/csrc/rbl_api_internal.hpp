@@ -10,7 +10,7 @@
 //   rbl_forces.hip    configuration-dependent forces (weight, wall and steric repulsion)
 //   rbl_ensemble.hip  ensembles of independent replicas of one small system
 //   rbl_field.hip     the fluid velocity at arbitrary points from blob forces
-//   rbl_mixed.hip     prescribed kinematics: held or driven bodies among free ones, the loads that takes
+//   rbl_mixed.hip     prescribed kinematics: held or driven bodies among free ones, the loads that takes; their Brownian step
 // None of these symbols is exported from librbl.so.
 #pragma once
 #include "rbl_internal.hpp"
@@ -86,6 +86,8 @@ int gmres_core_with_ops(rbl_ctx *c, const RblSolveOps *ops, const double *d_rhs,
 
 // ---- rbl_steps.hip ------------------------------------------------------------------------------------------------
 int m_rfd_core(rbl_ctx *c, const double *d_W, const double *Wh, double delta, double *d_out, double *d_r, double *d_work);
+// the same along a given direction dq[6 N_bod] (host); rbl_mixed.hip hands it the direction masked to the free bodies
+int m_rfd_dir(rbl_ctx *c, const double *d_W, const double *dq, double delta, double *d_out, double *d_r, double *d_work);
 
 // ---- rbl_forces.hip -----------------------------------------------------------------------------------------------
 // the model's PHYSICAL forces at the context's configuration: d_f (3 N, may be NULL), d_FT = K^T f (6 N_bod, may be NULL),

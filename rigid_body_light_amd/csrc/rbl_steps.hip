@@ -110,7 +110,7 @@ int rbl_step_brownian(rbl_ctx *c, const double *F_body, const double *slip, cons
 
 // d_out = (1/delta)[M(q + delta/2 dq) - M(q - delta/2 dq)] W for a displacement direction dq[6 N_bod] (host): the shared core of
 // M_RFD (:776-794, dq = Kinv W) and M_RFD_from_U (:820-842, dq = the caller's U).  d_r: n3 scratch, d_work: 2 n3 scratch.
-static int m_rfd_dir(rbl_ctx *c, const double *d_W, const double *dq, double delta, double *d_out, double *d_r, double *d_work)
+int m_rfd_dir(rbl_ctx *c, const double *d_W, const double *dq, double delta, double *d_out, double *d_r, double *d_work)
 {
   RblPhase ph_total(c, RBL_T_TOTAL);
   RblBodyState &S = c->S;

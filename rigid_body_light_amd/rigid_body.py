@@ -11,7 +11,8 @@ Beyond the reference surface (its C++ has these, its Python does not): `solve_sa
 `body_mobility_matrix`, `M_half_W`, `M_RFD`,
 `KTinv_RFD`, `M_RFD_cfgs`, `M_RFD_from_U`, `KT_RFD_from_U`, `evolve_rigid_bodies_RFD`, `apply_M_multi`,
 `dense_mobility`, `velocity_field` (the flow at arbitrary points), prescribed kinematics (`solve_mixed`, `step_mixed`,
-`body_resistance_matrix`: bodies that are held or driven, and the loads that takes), and a force model the reference does not have (`set_interactions`, `interaction_forces`).
+`body_resistance_matrix`: bodies that are held or driven, and the loads that takes; `step_brownian_mixed`,
+`RHS_and_Midpoint_mixed`: the same among Brownian bodies), and a force model the reference does not have (`set_interactions`, `interaction_forces`).
 """
 import numpy as np
 
@@ -298,6 +299,36 @@ class RigidBody:
         fluid supplies (the model's share included).  -> (F, iterations, residual estimate)"""
         mask, bi, sl = self._mixed_args(prescribed, body_in, slip)
         return self.cb.step_mixed(mask, bi, sl, int(max_iter), float(rtol))
+
+    def _noise_arg(self, W):
+        if W is None:
+            return None
+        W = np.asarray(W, dtype=np.float64)
+        if W.size != 9 * self.total_blobs:
+            raise ValueError(f"W must have total size 9*N_blobs = {9 * self.total_blobs} (W1 | W2 | W_rfd). Got shape: {W.shape}")
+        return np.ascontiguousarray(W.reshape(-1))
+
+    def RHS_and_Midpoint_mixed(self, prescribed, body_in, slip=None, W=None, seed=0, method="cholesky", split_rand=True, delta=1.0e-4):
+        """Right-hand side and predictor of the Brownian midpoint step with prescribed bodies (include/rbl.h section 7):
+        s = slip - kBT M_RFD - BI with the RFD direction masked to the free bodies, and q^{n+1/2}: a free body displaced by
+        (dt/2) c1 Kinv M^{1/2}W1, a prescribed one by (dt/2) U_p.  Of body_in only the prescribed bodies' velocities are read.
+        Nothing is committed.  -> (s, X_half, Q_half)"""
+        mask, bi, sl = self._mixed_args(prescribed, body_in, slip)
+        W = self._noise_arg(W)
+        return self.cb.RHS_and_Midpoint_mixed(mask, bi, sl, W, int(seed), method, bool(split_rand), float(delta))
+
+    def step_brownian_mixed(self, prescribed, body_in, slip=None, W=None, seed=0, method="lanczos_pc", split_rand=True, delta=1.0e-4,
+                            max_iter=50, rtol=1.0e-8):
+        """One stochastic midpoint step with prescribed bodies: the bodies in `prescribed` (as solve_mixed reads it) are held or
+        driven with the velocity in their slots of body_in, the others are Brownian under their loads: RHS_and_Midpoint_mixed at
+        q^n, solve_mixed at q^{n+1/2}, update from q^n -- a prescribed body advances by exactly dt U_p.  The free bodies' velocity
+        has the covariance (2 kBT/dt) (K_f^T M^-1 K_f)^-1 and the drift kBT div of it.  The force model enters the free bodies
+        only, at q^n.  The F returned for a prescribed body is its instantaneous load, thermal part included: average it over
+        steps for a microrheology measurement.  kBT = 1 as in step_brownian.  -> (F, iterations, residual estimate)"""
+        mask, bi, sl = self._mixed_args(prescribed, body_in, slip)
+        W = self._noise_arg(W)
+        return self.cb.step_brownian_mixed(mask, bi, sl, W, int(seed), method, bool(split_rand), float(delta),
+                                           int(max_iter), float(rtol))
 
     def body_resistance_matrix(self, max_iter=100, rtol=1.0e-8, columns=None):
         """The (6 N_bodies) x (6 N_bodies) body resistance matrix R = N^-1 of the current configuration, the inverse of
