@@ -582,7 +582,30 @@ int rbl_interaction_stats(rbl_ctx *ctx, int64_t *body_pairs, int64_t *blob_pairs
  *                             what rbl_step_brownian draws from the same seed).  kBT <= 1e-10: the deterministic step (:967-970)
  *   rbl_ensemble_interaction_forces  the force model at every replica's configuration: FT_body[R 6 N_bod] in the REFERENCE
  *                             convention (-K^T f_phys, what the steps add to F_body), energy[R] (either may be NULL)
- * The force model enters the steps as in the one-system steps: the right-hand side's force is F_body - K^T f_phys at q^n. */
+ * The force model enters the steps as in the one-system steps: the right-hand side's force is F_body - K^T f_phys at q^n.
+ *
+ * With prescribed bodies (the semantics of section 7, per replica): in every replica any subset of its bodies is held (U = 0) or
+ * driven (U given) while the others stay free, deterministic or Brownian; each call returns, per replica, the loads it takes.
+ * prescribed[R N_bod] (0 = free, 1 = prescribed; replica-major, it may differ from replica to replica and travels with each
+ * call), body_in[R 6 N_bod] (the load of a free body, the velocity of a prescribed one), U[R 6 N_bod] (solved, or echoed for a
+ * prescribed body), F[R 6 N_bod] (echoed for a free body -- with the model's share when a step added it -- or -K_b^T lambda for a
+ * prescribed one: the TOTAL load everything but the fluid supplies, as in rbl_step_mixed), lambda[R n3] the blob forces.
+ *   rbl_ensemble_solve_mixed          rbl_solve_mixed at every replica's configuration; nothing moves, the force model does not
+ *                             enter.  lambda may be NULL; U and F must not.
+ *   rbl_ensemble_step_mixed           rbl_step_mixed for every replica: the solve, then evolve_X_Q(U) -- a driven body advances by
+ *                             exactly dt U_p, a held one does not move.  The force model's loads at q^n enter the free bodies only.
+ *   rbl_ensemble_step_brownian_mixed  rbl_step_brownian_mixed(method RBL_MHALF_CHOLESKY) for every replica: the RFD direction and
+ *                             the random part of the predictor masked to the free bodies, a prescribed body at q^n + (dt/2) U_p in
+ *                             the predictor, s = slip - kBT M_RFD - BI, the masked solve at q^{n+1/2} (K_p U_p with the midpoint's
+ *                             lever arms), the update from q^n by dt U.  W and seed as rbl_ensemble_step_brownian.  kBT <= 1e-10:
+ *                             rbl_ensemble_step_mixed.  F (may be NULL): the instantaneous loads, thermal part included.
+ * One launch of the one-kernel solver assembles K_p U_p, solves every replica's masked system and splits U and F; U and F come
+ * back in the step's one read-back.  Refused before the device is touched: a NULL prescribed or body_in (or U, F of the solve),
+ * max_iter < 1, rtol < 0, an entry of prescribed above 1 and a context with a communicator (RBL_ERR_ARG); max_iter > 255 and a
+ * shape whose masked solve does not fit the LDS (RBL_ERR_SIZE); no ensemble configuration (RBL_ERR_STATE).  Errors during a step
+ * follow the ensemble's policy: the first failing replica is named, nothing is committed unless every replica succeeded.
+ * With nobody prescribed in any replica the configurations and iteration counts are bitwise those of
+ * rbl_ensemble_step_deterministic / rbl_ensemble_step_brownian on the same inputs. */
 int rbl_ensemble_set_config(rbl_ctx *ctx, int R, int N_bod, const double *X, const double *Q);
 int rbl_ensemble_get_config(rbl_ctx *ctx, double *X, double *Q);
 int rbl_ensemble_info(const rbl_ctx *ctx, int *R, int *N_bod);
@@ -592,6 +615,13 @@ int rbl_ensemble_step_deterministic(rbl_ctx *ctx, const double *F_body, const do
 int rbl_ensemble_step_brownian(rbl_ctx *ctx, const double *F_body, const double *slip, const double *W, uint64_t seed,
                                int split_rand, double delta, int max_iter, double rtol, int *iters, double *resid);
 int rbl_ensemble_interaction_forces(rbl_ctx *ctx, double *FT_body, double *energy);
+int rbl_ensemble_solve_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter,
+                             double rtol, double *lambda, double *U, double *F, int *iters, double *resid);
+int rbl_ensemble_step_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter,
+                            double rtol, double *F, int *iters, double *resid);
+int rbl_ensemble_step_brownian_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip,
+                                     const double *W, uint64_t seed, int split_rand, double delta, int max_iter, double rtol,
+                                     double *F, int *iters, double *resid);
 
 /* ===================================================================== */
 /* 6. Fluid velocity at arbitrary points (rigid_body_light_amd/csrc/rbl_field.hip) */
@@ -696,7 +726,8 @@ int rbl_velocity_field_info(const rbl_ctx *ctx, int64_t n_points, int64_t n_src,
  *                        the mask, body_in and 12 numbers per body.
  * Their refusals are those above plus max_iter > 254 and, when kBT > 1e-10, dt <= 0 or delta <= 0: RBL_ERR_ARG before any device
  * work.
- * Not offered: ensembles and lock-step multi-right-hand-side mixed solves, contexts with a communicator, a mask that changes
+ * Ensembles of replicas with prescribed bodies are section 5's rbl_ensemble_*_mixed.
+ * Not offered: lock-step multi-right-hand-side mixed solves, contexts with a communicator, a mask that changes
  * within a step, and per-component constraints (only whole bodies are prescribed). */
 int rbl_solve_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
                     double *lambda, double *U, double *F, int *iters, double *resid);

@@ -94,6 +94,9 @@ def lib():
         L.rbl_ensemble_step_deterministic.argtypes = [vp, vp, vp, C.c_int, dbl, vp, vp]
         L.rbl_ensemble_step_brownian.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_int, dbl, C.c_int, dbl, vp, vp]
         L.rbl_ensemble_interaction_forces.argtypes = [vp, vp, vp]
+        L.rbl_ensemble_solve_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, vp, vp]
+        L.rbl_ensemble_step_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp]
+        L.rbl_ensemble_step_brownian_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, dbl, C.c_int, dbl, vp, vp, vp]
         L.rbl_velocity_field.argtypes = [vp, vp, i64, vp, vp, i64, vp]
         L.rbl_velocity_field_dev.argtypes = [vp, vp, i64, vp, vp, i64, vp]
         L.rbl_velocity_field_info.argtypes = [vp, i64, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
@@ -381,6 +384,63 @@ class DeviceContext:
         FT, E = np.zeros((R, 6 * nb)), np.zeros(R)
         self._chk(self.L.rbl_ensemble_interaction_forces(self.h, FT.ctypes.data, E.ctypes.data))
         return FT, E
+
+    def _ens_mixed_args(self, who, prescribed, body_in, slip):
+        """mask (R, N_bod) uint8 -- (N_bod,) is broadcast over the replicas --, body_in (R, 6 N_bod), slip (R, n3) or None"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        m = np.asarray(prescribed)
+        if m.size == nb:
+            m = np.broadcast_to(m.reshape(1, nb), (R, nb))
+        if m.size != R * nb:
+            raise ValueError("%s: prescribed must have shape (%d,) or (%d, %d); got %s" % (who, nb, R, nb, m.shape))
+        m = np.ascontiguousarray(m.reshape(R, nb), dtype=np.uint8)
+        bi = self._ens_vec(body_in, 6 * nb, "body_in")
+        sl = None if slip is None else self._ens_vec(slip, 3 * nb * self._sizes()[1], "slip")
+        return R, nb, m, bi, sl
+
+    def ensemble_solve_mixed(self, prescribed, body_in, max_iter=100, rtol=1.0e-8, slip=None):
+        """solve_mixed at every replica's configuration (nothing moves) -> (lambda (R, n3), U (R, 6 N_bod), F (R, 6 N_bod),
+        iterations[R], residual estimates[R]); prescribed: 0/1 per body, (N_bod,) or (R, N_bod)"""
+        import numpy as np
+        R, nb, m, bi, sl = self._ens_mixed_args("ensemble_solve_mixed", prescribed, body_in, slip)
+        n3 = 3 * nb * self._sizes()[1]
+        lam, U, F = np.zeros((R, n3)), np.zeros((R, 6 * nb)), np.zeros((R, 6 * nb))
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(self.L.rbl_ensemble_solve_mixed(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                  int(max_iter), float(rtol or 0.0), lam.ctypes.data, U.ctypes.data, F.ctypes.data,
+                                                  it.ctypes.data, res.ctypes.data))
+        return lam, U, F, it, res
+
+    def ensemble_step_mixed(self, prescribed, body_in, max_iter=50, rtol=1.0e-8, slip=None):
+        """one deterministic step of every replica with prescribed bodies -> (F (R, 6 N_bod), iterations[R], residual estimates[R])"""
+        import numpy as np
+        R, nb, m, bi, sl = self._ens_mixed_args("ensemble_step_mixed", prescribed, body_in, slip)
+        F = np.zeros((R, 6 * nb))
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(self.L.rbl_ensemble_step_mixed(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                 int(max_iter), float(rtol or 0.0), F.ctypes.data, it.ctypes.data, res.ctypes.data))
+        return F, it, res
+
+    def ensemble_step_brownian_mixed(self, prescribed, body_in, W=None, seed=0, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8,
+                                     slip=None):
+        """one stochastic midpoint step of every replica with prescribed bodies (dense Cholesky root) -> (F (R, 6 N_bod),
+        iterations[R], residual estimates[R]); W as ensemble_step_brownian"""
+        import numpy as np
+        R, nb, m, bi, sl = self._ens_mixed_args("ensemble_step_brownian_mixed", prescribed, body_in, slip)
+        n3 = 3 * nb * self._sizes()[1]
+        Wh = None
+        if W is not None:
+            Wh = np.ascontiguousarray(np.asarray(W, dtype=np.float64))
+            if Wh.size != R * 3 * n3:
+                raise ValueError("W must have shape (%d, %d); got %s" % (R, 3 * n3, Wh.shape))
+        F = np.zeros((R, 6 * nb))
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(self.L.rbl_ensemble_step_brownian_mixed(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                          None if Wh is None else Wh.ctypes.data, int(seed), int(bool(split_rand)),
+                                                          float(delta), int(max_iter), float(rtol or 0.0), F.ctypes.data,
+                                                          it.ctypes.data, res.ctypes.data))
+        return F, it, res
 
     def _sizes(self):
         nb, nblb = C.c_int(0), C.c_int(0)

@@ -20,6 +20,17 @@
 // followed by ONE read-back (iterations, residuals, one error word per replica).  The step writes the other of two
 // configuration buffers and commits (swaps) only when every replica succeeded: on any error no replica moves.
 // Replicas never interact: the pair sweeps are per replica, the force model's neighbour lists stop at the replica's bodies.
+//
+// With prescribed bodies (rbl_ensemble_solve_mixed / _step_mixed / _step_brownian_mixed; the semantics of include/rbl.h section 7
+// per replica, the restatement of rbl_mixed.hip's mx_solve / mx_step / mx_bd_rhs): a 0/1 mask per body and replica travels with the
+// call.  The same launches with three differences: k_ens_midpoint is followed by k_ens_midpoint_prescribed (dq = 0 and the predictor
+// (dt/2) U_p on a prescribed body; one more launch, so that a free body goes through the very same code), the solve is the
+// masked k_gmres_small (it adds K_p U_p to the right-hand side with the lever arms of the configuration it solves at, zeroes
+// the prescribed bodies' balance rows and splits the solution into U and F per body), and
+// k_ens_evolve reads the U the solver wrote.  The right-hand-side kernels are the unmasked ones: body_in stands where F_body stood,
+// so the model's K^T f reaches the bottom rows of the free bodies and what they write on a prescribed body's rows is overwritten
+// by the solver.  U and F follow the error words in the ONE read-back.  A free body's arithmetic and its order are unchanged: with
+// nobody prescribed the configurations and iteration counts are bitwise those of the unmasked steps.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -128,6 +139,25 @@ __global__ __launch_bounds__(ET) void k_ens_midpoint(int nbod, int Nb, int nbl, 
   double u[6];
   ens_kinv_body(Rm, cfg, nbl, MW + (size_t)r * 3 * n3 + boff, u);
   for (int p = 0; p < 6; ++p) u[p] *= scale;
+  ens_update_body(X + 3 * (size_t)g, Q + 4 * (size_t)g, u, Xh + 3 * (size_t)g, Qh + 4 * (size_t)g);
+}
+
+// k_ens_midpoint with prescribed bodies (mask[nbod], body_in[6 nbod]) is k_ens_midpoint itself on every body, then this kernel
+// on the prescribed ones: such a body takes no random displacement -- dq = 0 -- and sits at q^n + (dt/2) U_p in the predictor
+// (k_mx_bd_sums and the host loop of mx_bd_rhs, rbl_mixed.hip).  One kernel with the two cases as branches was tried: the
+// compiler joins the branches' common tail (the update), scale * u of a free body then no longer fuses into X + u as it does
+// in k_ens_midpoint, and a free body's configuration differs in the last bit from the unmasked step's.  Running the unmasked
+// kernel gives the same bits by construction, for one more small launch per step
+__global__ __launch_bounds__(ET) void k_ens_midpoint_prescribed(int nbod, const double *__restrict__ X, const double *__restrict__ Q,
+                                                                const unsigned char *__restrict__ mask,
+                                                                const double *__restrict__ body_in, double half_dt,
+                                                                double *__restrict__ dq, double *__restrict__ Xh,
+                                                                double *__restrict__ Qh)
+{
+  const int g = blockIdx.x * ET + threadIdx.x;
+  if (g >= nbod || !mask[g]) return;
+  double u[6];
+  for (int p = 0; p < 6; ++p) { dq[6 * (size_t)g + p] = 0.0; u[p] = half_dt * body_in[6 * (size_t)g + p]; }
   ens_update_body(X + 3 * (size_t)g, Q + 4 * (size_t)g, u, Xh + 3 * (size_t)g, Qh + 4 * (size_t)g);
 }
 
@@ -262,6 +292,10 @@ struct EnsWork {
   // read-back block: residuals | iterations | error word per replica | one error word for the batch
   double *resid; int *iters; unsigned *rerr, *gerr;
   size_t rb_bytes;
+  // prescribed bodies: U and F of the masked solve follow the read-back block (rb_mx_bytes reaches their end) and stand in front
+  // of x in one piece [U | F | x], as rbl_launch_gmres_small_ens_mixed wants them; body_in is uploaded where F_body goes (F)
+  double *U, *Fo; unsigned char *mask;
+  size_t rb_mx_bytes;
 };
 
 EnsWork ens_carve(void *base, int R, int Nb, int nbl, int max_iter, size_t *bytes)
@@ -274,13 +308,18 @@ EnsWork ens_carve(void *base, int R, int Nb, int nbl, int max_iter, size_t *byte
   w.rerr = C.take<unsigned>(Rz + 1);
   w.gerr = w.rerr ? w.rerr + Rz : nullptr;
   w.rb_bytes = C.off;
+  w.U = C.take<double>(Rz * (2 * nb6 + nsys));         // [U | F | x]
+  w.Fo = w.U ? w.U + Rz * nb6 : nullptr;
+  w.x = w.U ? w.U + 2 * Rz * nb6 : nullptr;
+  w.rb_mx_bytes = w.rb_bytes + sizeof(double) * 2 * Rz * nb6;
   w.lever = C.take<double>(Rz * n3); w.pos = C.take<double>(Rz * n3);
   w.F = C.take<double>(Rz * nb6); w.FT = C.take<double>(Rz * nb6); w.slip = C.take<double>(Rz * n3);
   w.W = C.take<double>(Rz * 3 * n3); w.MW = C.take<double>(Rz * 3 * n3);
   w.Lm = C.take<double>(Rz * n3 * n3);
   w.Linv = C.take<double>(rbl_cholesky_batched_work_bytes((int64_t)n3, R) / sizeof(double));
   w.dq = C.take<double>(Rz * nb6); w.Xh = C.take<double>(Rz * 3 * Nb); w.Qh = C.take<double>(Rz * 4 * Nb);
-  w.rhs = C.take<double>(Rz * nsys); w.x = C.take<double>(Rz * nsys);
+  w.rhs = C.take<double>(Rz * nsys);
+  w.mask = C.take<unsigned char>(Rz * Nb);
   w.gm = C.take<double>(Rz * rbl_gmres_small_work_doubles(nbl, Nb, max_iter));
   w.e = C.take<double>(Rz * N);
   w.ia = C.take<char>(ia_batch_bytes(Nb, nbl, R));
@@ -310,10 +349,11 @@ int ens_ready(rbl_ctx *c)
 }
 
 // the step's flags: the first failing replica names the error; nothing is committed unless every replica succeeded
-int ens_finish(rbl_ctx *c, const EnsWork &w, int R, int *iters, double *resid, bool commit)
+int ens_finish(rbl_ctx *c, const EnsWork &w, int R, int *iters, double *resid, bool commit, double *U = nullptr, double *F = nullptr)
 {
-  std::vector<char> h(w.rb_bytes);
-  int rc = read_back(c, h.data(), w.resid, w.rb_bytes); if (rc) return rc;
+  const size_t bytes = (U || F) ? w.rb_mx_bytes : w.rb_bytes;
+  std::vector<char> h(bytes);
+  int rc = read_back(c, h.data(), w.resid, bytes); if (rc) return rc;
   const double *hr = (const double *)h.data();
   const int *hi = (const int *)(h.data() + ((char *)w.iters - (char *)w.resid));
   const unsigned *hf = (const unsigned *)(h.data() + ((char *)w.rerr - (char *)w.resid));
@@ -330,13 +370,16 @@ int ens_finish(rbl_ctx *c, const EnsWork &w, int R, int *iters, double *resid, b
     c->last_error = "ensemble: " + c->last_error;
     return rc;
   }
+  const size_t ub = sizeof(double) * (size_t)6 * c->ens_Nb * (size_t)R;       // U and F of the masked solve
+  if (U) std::memcpy(U, h.data() + w.rb_bytes, ub);
+  if (F) std::memcpy(F, h.data() + w.rb_bytes + ub, ub);
   if (commit) c->ens_cur ^= 1;
   return RBL_OK;
 }
 
-// upload F (R 6 N_bod) and slip (R n3 or NULL), clear the read-back block, evaluate the force model at q^n when it is on:
-// *FT -> K^T f_phys of every replica (NULL when the model is off)
-int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *slip, const double **FT)
+// upload F (R 6 N_bod) and slip (R n3 or NULL), clear the read-back block, evaluate the force model at q^n when it is on and
+// the caller wants its loads (model): *FT -> K^T f_phys of every replica (NULL otherwise)
+int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *slip, const double **FT, bool model = true)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
   const size_t n3 = (size_t)3 * Nb * nbl, nb6 = (size_t)6 * Nb;
@@ -346,7 +389,7 @@ int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *
   const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
   rbl_launch_body_geom(c->stream, X, Q, ens_cfg(c), nbl, (int64_t)R * Nb * nbl, w.lever, w.pos);
   *FT = nullptr;
-  if (c->ia_on) {
+  if (model && c->ia_on) {
     double *f = nullptr;
     if ((rc = ia_eval_batch(c, X, w.pos, w.lever, Nb, R, w.ia, &f, w.FT, nullptr, w.gerr))) return rc;
     *FT = w.FT;
@@ -371,18 +414,139 @@ int ens_check_solver(rbl_ctx *c, int max_iter)
   return RBL_OK;
 }
 
-int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const double *Qs, int max_iter, double rtol)
+// mixed: the masked solve (w.mask, body_in in w.F); the update then reads the U it wrote (a prescribed body: dt U_p exactly).
+// evolve = false: the solve alone
+int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const double *Qs, int max_iter, double rtol, bool mixed = false,
+                     bool evolve = true)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
   const long n3 = 3L * Nb * nbl, nsys = n3 + 6L * Nb;
-  int rc = rbl_launch_gmres_small_ens(c->stream, rbl_make_params(c->S.a, c->S.eta), c->S.wall, Xs, Qs, ens_cfg(c), nbl, Nb, R,
-                                      w.rhs, w.x, max_iter, rtol, w.gm, w.iters, w.resid, w.rerr);
+  const RblParams P = rbl_make_params(c->S.a, c->S.eta);
+  int rc = mixed ? rbl_launch_gmres_small_ens_mixed(c->stream, P, c->S.wall, Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.U, max_iter, rtol,
+                                                    w.gm, w.iters, w.resid, w.rerr, w.mask, w.F)
+                 : rbl_launch_gmres_small_ens(c->stream, P, c->S.wall, Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.x, max_iter, rtol, w.gm,
+                                              w.iters, w.resid, w.rerr);
   if (rc) return rbl_fail(c, rc, "ensemble step: the one-kernel solver does not fit this device's LDS");
+  if (!evolve) return RBL_OK;
   const int nbod = R * Nb;
-  hipLaunchKernelGGL(k_ens_evolve, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, nsys, n3, c->S.dt,
-                     (const double *)w.x, (const double *)ens_X(c, c->ens_cur), (const double *)ens_Q(c, c->ens_cur),
-                     ens_X(c, c->ens_cur ^ 1), ens_Q(c, c->ens_cur ^ 1), w.rerr);
+  hipLaunchKernelGGL(k_ens_evolve, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, mixed ? 6L * Nb : nsys,
+                     mixed ? 0L : n3, c->S.dt, mixed ? (const double *)w.U : (const double *)w.x, (const double *)ens_X(c, c->ens_cur),
+                     (const double *)ens_Q(c, c->ens_cur), ens_X(c, c->ens_cur ^ 1), ens_Q(c, c->ens_cur ^ 1), w.rerr);
   return RBL_OK;
+}
+
+// the checks of the entry points with prescribed bodies: none needs a device
+int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *body_in, int max_iter, double rtol)
+{
+  int rc = need_params(c); if (rc) return rc;
+  const std::string w(who);
+  if (!prescribed || !body_in) return rbl_fail(c, RBL_ERR_ARG, w + ": prescribed or body_in is NULL");
+  if (max_iter < 1 || !(rtol >= 0.0)) return rbl_fail(c, RBL_ERR_ARG, w + ": need max_iter >= 1 and rtol >= 0");
+  if (max_iter > 255)
+    return rbl_fail(c, RBL_ERR_SIZE, "ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)");
+  if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, "ensemble: not on a context with a communicator (run one ensemble per process)");
+  if (!c->ens_R) return ens_fail_state(c);
+  if (c->S.N_blb != c->ens_Nblb) return rbl_fail(c, RBL_ERR_STATE, "ensemble: the structure changed since rbl_ensemble_set_config");
+  const size_t nbod = (size_t)c->ens_R * c->ens_Nb;
+  for (size_t g = 0; g < nbod; ++g)
+    if (prescribed[g] > 1) return rbl_fail(c, RBL_ERR_ARG, w + ": entries of prescribed must be 0 or 1 (replica " + std::to_string(g / c->ens_Nb) + ")");
+  if (!rbl_gmres_small_fits(c->S.N_blb, c->ens_Nb, max_iter, false, true))
+    return rbl_fail(c, RBL_ERR_SIZE, rbl_gmres_small_fits(c->S.N_blb, c->ens_Nb, max_iter, false)
+                                         ? w + ": this shape fits the one-kernel solver without prescribed bodies, but not with the mask's 6 N_bod doubles of LDS"
+                                         : std::string("ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)"));
+  return RBL_OK;
+}
+
+// workspace, mask and the step's uploads (ens_begin with body_in where F_body goes)
+int ens_mx_begin(rbl_ctx *c, EnsWork *w, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, bool model,
+                 const double **FT)
+{
+  int rc = ens_ready(c); if (rc) return rc;
+  if ((rc = ens_work(c, max_iter, w))) return rc;
+  if ((rc = copy_h2d(c, w->mask, prescribed, (size_t)c->ens_R * c->ens_Nb))) return rc;
+  return ens_begin(c, *w, body_in, slip, FT, model);     // model = false: the solve at the current configuration takes no model
+                                                         // loads (rbl_solve_mixed)
+}
+
+int ens_mx_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol, bool move,
+                    double *lambda, double *U, double *F, int *iters, double *resid)
+{
+  EnsWork w;
+  const double *FT;
+  int rc = ens_mx_begin(c, &w, prescribed, body_in, slip, max_iter, move, &FT); if (rc) return rc;
+  const int R = c->ens_R, Nb = c->ens_Nb;
+  const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb;
+  const long tot = (long)R * (n3 + nb6);
+  hipLaunchKernelGGL(k_ens_rhs_det, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, n3, nb6,
+                     slip ? (const double *)w.slip : nullptr, (const double *)w.F, FT, w.rhs);
+  if ((rc = ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, true, move))) return rc;
+  std::vector<double> x;
+  if (lambda) {                                          // the blob forces: the top of every replica's solution
+    x.resize((size_t)R * (n3 + nb6));
+    if ((rc = copy_d2h(c, x.data(), w.x, sizeof(double) * x.size()))) return rc;
+  }
+  std::vector<double> Ft;
+  if (!F) { Ft.resize((size_t)R * nb6); F = Ft.data(); }                  // the masked read-back is chosen by U or F
+  if ((rc = ens_finish(c, w, R, iters, resid, move, U, F))) return rc;
+  if (lambda)
+    for (int r = 0; r < R; ++r) std::memcpy(lambda + (size_t)r * n3, x.data() + (size_t)r * (n3 + nb6), sizeof(double) * n3);
+  return RBL_OK;
+}
+
+// the stochastic midpoint step of every replica (checks done by the caller).  prescribed == NULL: rbl_ensemble_step_brownian;
+// otherwise body_in stands where F_body stands, the predictor and the solve are the masked ones and F_out takes the loads
+int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, const double *W, uint64_t seed,
+                int split_rand, double delta, int max_iter, double rtol, double *F_out, int *iters, double *resid)
+{
+  const RblBodyState &S = c->S;
+  const bool mixed = prescribed != nullptr;
+  int rc;
+  EnsWork w;
+  if ((rc = ens_work(c, max_iter, &w))) return rc;
+  if (mixed && (rc = copy_h2d(c, w.mask, prescribed, (size_t)c->ens_R * c->ens_Nb))) return rc;
+  const int R = c->ens_R, Nb = c->ens_Nb, nbl = S.N_blb, N = Nb * nbl;
+  const int64_t n3 = 3 * (int64_t)N;
+  if (W) { if ((rc = copy_h2d(c, w.W, W, sizeof(double) * 3 * (size_t)n3 * R))) return rc; }
+  else rbl_launch_normal_batched(c->stream, seed, 3 * n3, R, w.W);            // rand_vector (:730-741), one draw per replica
+  const double *FT;
+  if ((rc = ens_begin(c, w, F_body, slip, &FT))) return rc;
+  const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
+  // dense root of every replica: B M B (:667-669), lower Cholesky (:670-671), L W1 and L W2 (:672)
+  const RblParams P = rbl_make_params(S.a, S.eta);
+  rbl_launch_build_M_batched(c->stream, P, S.wall, true, w.pos, N, R, w.Lm, n3 * n3, w.rerr, 0, 1);
+  if ((rc = rbl_launch_cholesky_batched(c->stream, w.Lm, n3, R, n3 * n3, w.gerr, w.Linv)))
+    return rbl_fail(c, rc, "ensemble: batched Cholesky launch failed");
+  const int split = split_rand ? 1 : 0;
+  for (int v = 0; v <= split; ++v)
+    rbl_launch_block_trmv(c->stream, w.Lm, n3, R, n3 * n3, w.W + v * n3, w.MW + v * n3, 3 * n3);
+  // Kinv of the RFD noise and the predictor (:776, :955-959), then M_RFD and the right-hand side (:940-963)
+  const double c1 = split_rand ? 2.0 * std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);   // :945-952
+  const double c2 = split_rand ? std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);
+  const int nbod = R * Nb;
+  hipLaunchKernelGGL(k_ens_midpoint, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, nbl, X, Q, ens_cfg(c),
+                     (const double *)w.W, (const double *)w.MW, 0.5 * S.dt * c1, w.dq, w.Xh, w.Qh);
+  if (mixed)                                             // the prescribed bodies: dq = 0, q^n + (dt/2) U_p
+    hipLaunchKernelGGL(k_ens_midpoint_prescribed, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, X, Q,
+                       (const unsigned char *)w.mask, (const double *)w.F, 0.5 * S.dt, w.dq, w.Xh, w.Qh);
+  const size_t lds = rfd_lds_bytes(Nb, nbl);
+  const void *fn = S.wall ? (const void *)k_ens_rfd_rhs<true> : (const void *)k_ens_rfd_rhs<false>;
+  if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return rbl_fail(c, RBL_ERR_SIZE, "ensemble: the RFD product does not fit this device's LDS");
+  }
+  if (S.wall)
+    hipLaunchKernelGGL(k_ens_rfd_rhs<true>, dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
+                       (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
+                       slip ? (const double *)w.slip : nullptr, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
+  else
+    hipLaunchKernelGGL(k_ens_rfd_rhs<false>, dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
+                       (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
+                       slip ? (const double *)w.slip : nullptr, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
+  // saddle solve at q^{n+1/2}, update from q^n
+  if ((rc = ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol, mixed))) return rc;
+  std::vector<double> Ft;
+  if (mixed && !F_out) { Ft.resize((size_t)R * 6 * Nb); F_out = Ft.data(); }   // the masked read-back is chosen by F
+  return ens_finish(c, w, R, iters, resid, true, nullptr, mixed ? F_out : nullptr);
 }
 
 }  // namespace
@@ -482,46 +646,38 @@ int rbl_ensemble_step_brownian(rbl_ctx *c, const double *F_body, const double *s
   if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_brownian: F_body is NULL");
   if (!(S.dt > 0.0) || !(delta > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_brownian: dt and delta must be positive");
   if ((rc = ens_check_solver(c, max_iter))) return rc;
-  EnsWork w;
-  if ((rc = ens_work(c, max_iter, &w))) return rc;
-  const int R = c->ens_R, Nb = c->ens_Nb, nbl = S.N_blb, N = Nb * nbl;
-  const int64_t n3 = 3 * (int64_t)N;
-  if (W) { if ((rc = copy_h2d(c, w.W, W, sizeof(double) * 3 * (size_t)n3 * R))) return rc; }
-  else rbl_launch_normal_batched(c->stream, seed, 3 * n3, R, w.W);            // rand_vector (:730-741), one draw per replica
-  const double *FT;
-  if ((rc = ens_begin(c, w, F_body, slip, &FT))) return rc;
-  const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
-  // dense root of every replica: B M B (:667-669), lower Cholesky (:670-671), L W1 and L W2 (:672)
-  const RblParams P = rbl_make_params(S.a, S.eta);
-  rbl_launch_build_M_batched(c->stream, P, S.wall, true, w.pos, N, R, w.Lm, n3 * n3, w.rerr, 0, 1);
-  if ((rc = rbl_launch_cholesky_batched(c->stream, w.Lm, n3, R, n3 * n3, w.gerr, w.Linv)))
-    return rbl_fail(c, rc, "ensemble: batched Cholesky launch failed");
-  const int split = split_rand ? 1 : 0;
-  for (int v = 0; v <= split; ++v)
-    rbl_launch_block_trmv(c->stream, w.Lm, n3, R, n3 * n3, w.W + v * n3, w.MW + v * n3, 3 * n3);
-  // Kinv of the RFD noise and the predictor (:776, :955-959), then M_RFD and the right-hand side (:940-963)
-  const double c1 = split_rand ? 2.0 * std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);   // :945-952
-  const double c2 = split_rand ? std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);
-  const int nbod = R * Nb;
-  hipLaunchKernelGGL(k_ens_midpoint, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, nbl, X, Q, ens_cfg(c),
-                     (const double *)w.W, (const double *)w.MW, 0.5 * S.dt * c1, w.dq, w.Xh, w.Qh);
-  const size_t lds = rfd_lds_bytes(Nb, nbl);
-  const void *fn = S.wall ? (const void *)k_ens_rfd_rhs<true> : (const void *)k_ens_rfd_rhs<false>;
-  if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return rbl_fail(c, RBL_ERR_SIZE, "ensemble: the RFD product does not fit this device's LDS");
-  }
-  if (S.wall)
-    hipLaunchKernelGGL(k_ens_rfd_rhs<true>, dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
-                       (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
-                       slip ? (const double *)w.slip : nullptr, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
-  else
-    hipLaunchKernelGGL(k_ens_rfd_rhs<false>, dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
-                       (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
-                       slip ? (const double *)w.slip : nullptr, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
-  // saddle solve at q^{n+1/2}, update from q^n
-  if ((rc = ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol))) return rc;
-  return ens_finish(c, w, R, iters, resid, true);
+  return ens_step_bd(c, nullptr, F_body, slip, W, seed, split_rand, delta, max_iter, rtol, nullptr, iters, resid);
+}
+
+int rbl_ensemble_solve_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
+                             double *lambda, double *U, double *F, int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  int rc = ens_mx_check(c, "ensemble_solve_mixed", prescribed, body_in, max_iter, rtol); if (rc) return rc;
+  if (!U || !F) return rbl_fail(c, RBL_ERR_ARG, "ensemble_solve_mixed: U or F is NULL");
+  return ens_mx_step_det(c, prescribed, body_in, slip, max_iter, rtol, false, lambda, U, F, iters, resid);
+}
+
+int rbl_ensemble_step_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
+                            double *F, int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  int rc = ens_mx_check(c, "ensemble_step_mixed", prescribed, body_in, max_iter, rtol); if (rc) return rc;
+  return ens_mx_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
+}
+
+int rbl_ensemble_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
+                                     uint64_t seed, int split_rand, double delta, int max_iter, double rtol, double *F, int *iters,
+                                     double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  int rc = ens_mx_check(c, "ensemble_step_brownian_mixed", prescribed, body_in, max_iter, rtol); if (rc) return rc;
+  const RblBodyState &S = c->S;
+  if (!(S.kBT > 1e-10))                                // no Brownian terms: the deterministic mixed step (as rbl_step_brownian_mixed)
+    return ens_mx_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
+  if (!(S.dt > 0.0) || !(delta > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_brownian_mixed: dt and delta must be positive");
+  if ((rc = ens_ready(c))) return rc;
+  return ens_step_bd(c, prescribed, body_in, slip, W, seed, split_rand, delta, max_iter, rtol, F, iters, resid);
 }
 
 int rbl_ensemble_interaction_forces(rbl_ctx *c, double *FT_body, double *energy)

@@ -361,7 +361,7 @@ void rbl_launch_scale_by_damp(hipStream_t st, const RblParams &P, const double *
                               int64_t n_blobs, const double *in, double *out);
 
 // whole GMRES solve of a small system in one kernel (rbl_small.hip)
-bool rbl_gmres_small_fits(int N_blb, int N_bod, int max_iter, bool block_pc);
+bool rbl_gmres_small_fits(int N_blb, int N_bod, int max_iter, bool block_pc, bool mixed = false);   // mixed: the masked variant
 size_t rbl_gmres_small_work_doubles(int N_blb, int N_bod, int max_iter);
 int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
                            int N_blb, int N_bod, const double *d_rhs, const double *d_x0, double *d_x, int max_iter, double rtol,
@@ -372,6 +372,12 @@ int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const 
 int rbl_launch_gmres_small_ens(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
                                int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter, double rtol,
                                double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err);
+// the same with a 0/1 mask per body and replica (include/rbl.h section 7's system): d_rhs is the all-free right-hand side
+// [slip ; -body_in]; the launch adds K_p U_p, solves and splits.  d_UFx: ONE block [U reps x 6 N_bod | F reps x 6 N_bod | x reps x nsys]
+int rbl_launch_gmres_small_ens_mixed(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ,
+                                     const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_UFx, int max_iter,
+                                     double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err,
+                                     const unsigned char *d_mask, const double *d_body_in);
 
 // per-body geometric operators on the device (rbl_body_dev.hip)
 void rbl_launch_body_geom(hipStream_t st, const double *dX, const double *dQ, const double *dcfg,

@@ -17,6 +17,22 @@
 // memory: thread 0's Givens recurrence then was a chain of dependent L2 round trips, ~10 us per iteration.
 // Every sum has a fixed order: results are bitwise reproducible, like the rest of the library.
 // Limits: N <= 256 blobs, N_bod <= 64, diagonal preconditioner, max_iter <= 255 (checked by the launcher).
+//
+// MIXED (the ensembles with prescribed bodies, include/rbl.h sections 5 and 7): the same solve of
+//   [M lambda - K (D_f U) ; D_f K^T lambda + D_p U] = [slip + K_p U_p ; -F_f | 0]
+// with the replica's 0/1 mask per body.  ONE launch assembles the right-hand side, solves and splits: it takes the all-free
+// right-hand side [slip ; -body_in], adds K_p U_p with the lever arms it has just made and zeroes the bottom of the prescribed
+// bodies (k_mx_rhs of rbl_mixed.hip); the operator and the preconditioner treat the six slots of a prescribed body as
+// k_mx_op_tail / k_mx_pc_diag do, by selects on values outside the pair sweep; the end is k_mx_split's: U and F per body, the
+// K^T sums in blob order.  A free body's arithmetic and its order are those of the unmasked kernel, so with nobody prescribed the
+// solution and the iteration count are bitwise the unmasked ones.  The four unmasked instantiations keep their code (every
+// masked statement is behind `if constexpr (MIXED)`, the extra arguments exist in the masked ones only): 111-128 VGPRs, no
+// scratch, WALL at the 128-register ceiling of a 1024-thread workgroup.  The masked ones fit under the same ceiling without
+// scratch because nothing of theirs stays in a register across the pair sweep: the mask is in LDS where the thread that selects
+// on it reads anyway, 1/|b| waits in LDS, U and F are addressed from x, and the basis in global memory is addressed with
+// 32-bit offsets.
+#include <type_traits>
+
 #include "rbl_small_dev.hpp"
 
 namespace {
@@ -43,6 +59,14 @@ struct SmallArgs {
   int N_blb, N_bod, max_iter;
   double rtol, fsign;
 };
+// The masked variant's outputs U and F (6 N_bod per replica: all body velocities, all body loads) lie in front of x, in ONE block
+// [U of every replica | F of every replica | x of every replica]: their addresses follow from x and the grid, and no pointer of
+// theirs has to stay in registers across the pair sweep (WALL sits at the 128-register ceiling of a 1024-thread workgroup).
+struct SmallArgsMixed : SmallArgs {
+  const unsigned char *mask;       // N_bod per replica: 1 = prescribed
+  const double *body_in;           // 6 N_bod per replica: U_b of a prescribed body (a free body's load is in rhs already)
+  int reps;                        // the grid
+};
 
 // sum over the wavefront, result in every lane, fixed order.  Inside the 16-lane rows by DPP moves (quad_perm, half-row
 // and row mirrors: a few cycles each; the __shfl_xor butterfly is six dependent ds_bpermute round trips, ~800 cycles, and
@@ -67,8 +91,8 @@ __device__ __forceinline__ double wave_sum(double v)
   return ((lane_value(v, 0) + lane_value(v, 16)) + lane_value(v, 32)) + lane_value(v, 48);
 }
 
-template <bool WALL, bool VLDS>
-__global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
+template <bool WALL, bool VLDS, bool MIXED>
+__global__ __launch_bounds__(SGT) void k_gmres_small(std::conditional_t<MIXED, SmallArgsMixed, SmallArgs> A)
 {
   extern __shared__ double sm[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -79,16 +103,23 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
     const int rep = blockIdx.x;
     A.X += (size_t)rep * 3 * nb; A.Q += (size_t)rep * 4 * nb;
     A.rhs += (size_t)rep * nsys; A.x += (size_t)rep * nsys;
-    if (A.x0) A.x0 += (size_t)rep * nsys;
+    if constexpr (MIXED) A.x0 = nullptr;        // cold start only (the ensembles')
+    else if (A.x0) A.x0 += (size_t)rep * nsys;
     A.V += (size_t)rep * A.work_stride; A.H += (size_t)rep * A.work_stride;
     A.iters_out += rep; A.resid_out += rep; A.err += (size_t)rep * A.err_stride;
+    if constexpr (MIXED) {
+      A.mask += (size_t)rep * nb; A.body_in += (size_t)rep * nb6;
+    }
   }
   double *pos = sm;                             // 3N  positions / a
   double *lev = pos + n3;                       // 3N  lever arms
   double *iM = lev + n3;                        // 2N  diag_invM: (xx = yy, zz)
   double *dmp = iM + 2 * N;                     // N   wall damping d_i (1 without the wall term)
-  double *NLs = dmp + N;                        // 36 Nb  (K^T invM K)^-1, row-major 6x6 per body
-  double *vz = NLs + 36 * nb;                   // nsys   z = P^-1 v
+  // MIXED: the mask lives in LDS as a seventh entry of every row of NLs (1.0: the row's body is prescribed), where the thread of a
+  // body slot reads its row anyway: the flag costs no register and no address across the pair sweep
+  constexpr int NS = MIXED ? 42 : 36, RS = MIXED ? 7 : 6;
+  double *NLs = dmp + N;                        // NS Nb  (K^T invM K)^-1, row-major 6x6 per body (rows of RS)
+  double *vz = NLs + NS * nb;                   // nsys   z = P^-1 v
   double *vw = vz + nsys;                       // nsys   w
   double *vv = vw + nsys;                       // nsys   current basis vector / scratch
   double *fb = vv + nsys;                       // 6 Nb   body sums
@@ -105,6 +136,9 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
   const bool r_lds = m <= SG_RLDS;
   double *Rm = r_lds ? Rl : A.H;
   double *Vb = VLDS ? Rl + (r_lds ? (size_t)m * (m + 1) / 2 : 0) : A.V;   // Krylov basis
+  // MIXED with the basis in global memory: 32-bit offsets from the (uniform) base -- the workspace of one replica is a few MB --
+  // so that no 64-bit address per thread is held across the pair sweep
+  constexpr bool V32 = MIXED && !VLDS;
   const RblParams P = A.P;
   const RblParams Pu = rbl_small_unit_params(P);
   unsigned flags = 0;
@@ -186,7 +220,11 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
         for (int q2 = p + 1; q2 < 6; ++q2) v -= L[6 * q2 + p] * u[q2];
         u[p] = v / L[6 * p + p];
       }
-      for (int p = 0; p < 6; ++p) NLs[36 * t + 6 * p + col] = u[p];
+      for (int p = 0; p < 6; ++p) NLs[NS * t + RS * p + col] = u[p];
+    }
+    if constexpr (MIXED) {
+      const double pres = A.mask[t] ? 1.0 : 0.0;
+      for (int p = 0; p < 6; ++p) NLs[NS * t + RS * p + 6] = pres;
     }
   }
   __syncthreads();
@@ -206,15 +244,17 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
       const double *p = part + (size_t)c * N + (size_t)b * nbl;
       double f = 0.0;
       for (int k = 0; k < nbl; ++k) f += p[k];
-      fb[t] = A.fsign * in[n3 + t] - f;
+      if constexpr (MIXED) fb[t] = in[n3 + t] - f;         // the force block's sign restored (fsign = +1), as the ensembles solve
+      else fb[t] = A.fsign * in[n3 + t] - f;
     }
     __syncthreads();
     if (t < nb6) {                           // U = Ninv^-1 (fsign F - f)   (:601-608), explicit 6x6 inverse
       const int b = t / 6, c = t - 6 * b;
-      const double *Nm = NLs + 36 * b + 6 * c, *rh = fb + 6 * b;
+      const double *Nm = NLs + NS * b + RS * c, *rh = fb + 6 * b;
       double u = 0.0;
 #pragma unroll
       for (int d = 0; d < 6; ++d) u = __builtin_fma(Nm[d], rh[d], u);
+      if constexpr (MIXED) u = Nm[6] != 0.0 ? in[n3 + t] : u;   // a prescribed body's six slots pass through
       out[n3 + t] = u;
     }
     __syncthreads();
@@ -222,13 +262,16 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
       const int b = t / nbl;
       const double *u = out + n3 + 6 * b;
       const double l0 = lev[3 * t], l1 = lev[3 * t + 1], l2 = lev[3 * t + 2];
-      out[3 * t] = iM[2 * t] * (in[3 * t] + u[0] + l2 * u[4] - l1 * u[5]);
-      out[3 * t + 1] = iM[2 * t] * (in[3 * t + 1] + u[1] + l0 * u[5] - l2 * u[3]);
+      out[3 * t] = iM[2 * t] * (in[3 * t] + u[0] + l2 * u[4] - l1 * u[5]);       // MIXED, prescribed body: u = 0 (see apply_A),
+      out[3 * t + 1] = iM[2 * t] * (in[3 * t + 1] + u[1] + l0 * u[5] - l2 * u[3]);   // so this is lambda = invM slip
       out[3 * t + 2] = iM[2 * t + 1] * (in[3 * t + 2] + u[2] + l1 * u[3] - l0 * u[4]);
     }
     __syncthreads();
   };
 
+  // MIXED: [M lambda - K (D_f U) ; D_f K^T lambda + D_p U].  The six slots of a prescribed body are 0 in the right-hand side, this
+  // operator is the identity on them and apply_PC passes them through, so they are exactly 0 in every vector either is applied to
+  // (cold start only): K U of such a body is exactly 0 and its rows need no select -- the two selects are on the body slots.
   // out = [M lambda - K U ; K^T lambda]   (src/Rigid.py:73-80; M = B Mob B with the wall term, :641-659): self blocks here,
   // every unordered pair once by rbl_small_pair_sweep, the waves' accumulator sets added in wave order afterwards
   auto apply_A = [&](const double *in, double *out) {
@@ -259,6 +302,7 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
       const double *p = kt + (size_t)c * N + (size_t)b * nbl;
       double f = 0.0;
       for (int k = 0; k < nbl; ++k) f += p[k];
+      if constexpr (MIXED) f = NLs[NS * b + RS * c + 6] != 0.0 ? in[n3 + t] : f;   // D_p U: the identity on a prescribed body's six slots
       out[n3 + t] = f;
     }
     __syncthreads();
@@ -280,7 +324,30 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
   // ---- r0 = b - A x0 (or b), beta, V_0 --------------------------------------------------------------------
   double bnorm;
   {
-    for (int i = t; i < nsys; i += SGT) vw[i] = A.rhs[i];
+    if constexpr (!MIXED) {
+      for (int i = t; i < nsys; i += SGT) vw[i] = A.rhs[i];
+    } else for (int i = t; i < nsys; i += SGT) {
+      double v = A.rhs[i];
+      {                                      // top += K_p U_p (the lever arms of this configuration), bottom = 0 on prescribed bodies
+        if (i < n3) {
+          const int bl = i / 3, c = i - 3 * bl, b = bl / nbl;
+          if (A.mask[b]) {
+            const double *u = A.body_in + 6 * b;
+            const double l0 = lev[3 * bl], l1 = lev[3 * bl + 1], l2 = lev[3 * bl + 2];
+            v += c == 0 ? u[0] + l2 * u[4] - l1 * u[5] : c == 1 ? u[1] + l0 * u[5] - l2 * u[3] : u[2] + l1 * u[3] - l0 * u[4];
+          }
+        } else {                             // what is echoed is written here: rhs and body_in are not needed again
+          // U and F of this replica: the launcher's ONE block [U | F | x] (rbl_launch_gmres_small_ens_mixed: reps x 6 N_bod each,
+          // then reps x nsys), found from A.x, which the prologue moved on by blockIdx.x * nsys; the split at the end forms the
+          // same two addresses -- change the layout there and in both places here together
+          double *Uo = A.x - (size_t)blockIdx.x * nsys - 2 * (size_t)A.reps * nb6 + (size_t)blockIdx.x * nb6, *Fo = Uo + (size_t)A.reps * nb6;
+          const int j = i - n3;
+          if (A.mask[j / 6]) { v = 0.0; Uo[j] = A.body_in[j]; }
+          else Fo[j] = -v;
+        }
+      }
+      vw[i] = v;
+    }
     __syncthreads();
     bnorm = sqrt(norm2(vw));
     if (A.x0) {
@@ -296,9 +363,16 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
   const double ibn = (bnorm > 0.0) ? 1.0 / bnorm : 0.0;
   double resid = (bnorm > 0.0) ? beta / bnorm : 0.0;
   const bool trivial = !(beta > 0.0) || (A.rtol > 0.0 && resid < A.rtol);
+  if constexpr (MIXED) {                       // 1/|b| and the residual wait in LDS, not in registers, across the iterations
+    if (t == 0) { sc[4] = ibn; sc[2] = resid; }
+  }
   if (!trivial) {
     const double ib = 1.0 / beta;
-    for (int i = t; i < nsys; i += SGT) { const double v = vw[i] * ib; vv[i] = v; Vb[i] = v; }
+    if constexpr (V32) {
+      for (int i = t; i < nsys; i += SGT) { const double v = vw[i] * ib; vv[i] = v; Vb[(unsigned)i] = v; }
+    } else {
+      for (int i = t; i < nsys; i += SGT) { const double v = vw[i] * ib; vv[i] = v; Vb[i] = v; }
+    }
     if (t == 0) gg[0] = beta;
     __syncthreads();
 #ifdef RBL_SMALL_PROF
@@ -324,7 +398,8 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
           double a = 0.0, w0 = 0.0;
           for (int i = lane; i < nsys; i += 64) {
             const double wi = vw[i];
-            a = __builtin_fma(vk[i], wi, a);
+            if constexpr (V32) a = __builtin_fma(Vb[(unsigned)(k * nsys + i)], wi, a);
+            else a = __builtin_fma(vk[i], wi, a);
             if (k == 0 && pass == 0) w0 = __builtin_fma(wi, wi, w0);
           }
           a = wave_sum(a);
@@ -335,7 +410,8 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
         double wsq = 0.0;
         for (int i = t; i < nsys; i += SGT) {
           double a = vw[i];
-          for (int k = 0; k <= j; ++k) a = __builtin_fma(-hh[k], Vb[(size_t)k * nsys + i], a);
+          if constexpr (V32) { for (int k = 0; k <= j; ++k) a = __builtin_fma(-hh[k], Vb[(unsigned)(k * nsys + i)], a); }
+          else for (int k = 0; k <= j; ++k) a = __builtin_fma(-hh[k], Vb[(size_t)k * nsys + i], a);
           vw[i] = a;
           wsq = __builtin_fma(a, a, wsq);
         }
@@ -353,7 +429,11 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
       RBL_STAMP(3);
       const double ih = hn > 1e-300 ? 1.0 / hn : 0.0;
       double *vn = Vb + (size_t)(j + 1) * nsys;
-      for (int i = t; i < nsys; i += SGT) { const double v = vw[i] * ih; vv[i] = v; vn[i] = v; }
+      if constexpr (V32) {
+        for (int i = t; i < nsys; i += SGT) { const double v = vw[i] * ih; vv[i] = v; Vb[(unsigned)((j + 1) * nsys + i)] = v; }
+      } else {
+        for (int i = t; i < nsys; i += SGT) { const double v = vw[i] * ih; vv[i] = v; vn[i] = v; }
+      }
       if (t == 0) {   // Givens update of column j (in LDS) and of the rotated right-hand side; residual estimate
         double cur = hc[0];                  // the running entry stays in a register: the chain is two FMAs per rotation,
         for (int i = 0; i < j; ++i) {        // the LDS reads of cs, sn and the next entry do not depend on it
@@ -369,7 +449,8 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
         hc[j] = den;
         gg[j + 1] = -sn[j] * gg[j];
         gg[j] = cs[j] * gg[j];
-        sc[2] = fabs(gg[j + 1]) * ibn;
+        if constexpr (MIXED) sc[2] = fabs(gg[j + 1]) * sc[4];
+        else sc[2] = fabs(gg[j + 1]) * ibn;
         sc[1] = (A.rtol > 0.0 && sc[2] < A.rtol) || !(hn > 1e-300) ? 1.0 : 0.0;
         double *rc = Rm + (size_t)j * (j + 1) / 2;         // column j of R, rows 0..j
         for (int i = 0; i <= j; ++i) rc[i] = hc[i];
@@ -389,7 +470,8 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
     const double *Rs = Rm;
     const int nR = used * (used + 1) / 2;
     if (!r_lds && nR <= NW * n3) {
-      for (int i = t; i < nR; i += SGT) part[i] = Rm[i];
+      if constexpr (V32) { for (int i = t; i < nR; i += SGT) part[i] = Rm[(unsigned)i]; }
+      else for (int i = t; i < nR; i += SGT) part[i] = Rm[i];
       Rs = part;
       __syncthreads();
     }
@@ -405,26 +487,59 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(SmallArgs A)
     __syncthreads();
     for (int i = t; i < nsys; i += SGT) {
       double a = 0.0;
-      for (int k = 0; k < used; ++k) a = __builtin_fma(hh[k], Vb[(size_t)k * nsys + i], a);
+      if constexpr (V32) { for (int k = 0; k < used; ++k) a = __builtin_fma(hh[k], Vb[(unsigned)(k * nsys + i)], a); }
+      else for (int k = 0; k < used; ++k) a = __builtin_fma(hh[k], Vb[(size_t)k * nsys + i], a);
       vw[i] = a;
     }
     __syncthreads();
     apply_PC(vw, vz);
-    for (int i = t; i < nsys; i += SGT) A.x[i] = A.x0 ? A.x0[i] + vz[i] : vz[i];
+    if constexpr (MIXED) {
+      for (int i = t; i < nsys; i += SGT) A.x[i] = vz[i];
+    } else {
+      for (int i = t; i < nsys; i += SGT) A.x[i] = A.x0 ? A.x0[i] + vz[i] : vz[i];
+    }
   } else {
-    for (int i = t; i < nsys; i += SGT) A.x[i] = A.x0 ? A.x0[i] : 0.0;
+    if constexpr (MIXED) {
+      for (int i = t; i < nsys; i += SGT) { A.x[i] = 0.0; vz[i] = 0.0; }
+    } else {
+      for (int i = t; i < nsys; i += SGT) A.x[i] = A.x0 ? A.x0[i] : 0.0;
+    }
   }
-  if (t == 0) { *A.iters_out = used; *A.resid_out = resid; }
+  if constexpr (MIXED) {   // the split: U solved (free) or echoed (prescribed); F echoed (free: the load that entered the right-hand
+    __syncthreads();       // side) or -K_b^T lambda (prescribed), the blobs of the body added in order
+    if (t < N) {
+      const double v0 = vz[3 * t], v1 = vz[3 * t + 1], v2 = vz[3 * t + 2];
+      const double l0 = lev[3 * t], l1 = lev[3 * t + 1], l2 = lev[3 * t + 2];
+      kt[t] = v0; kt[N + t] = v1; kt[2 * N + t] = v2;
+      kt[3 * N + t] = l1 * v2 - l2 * v1; kt[4 * N + t] = l2 * v0 - l0 * v2; kt[5 * N + t] = l0 * v1 - l1 * v0;
+    }
+    __syncthreads();
+    if (t < nb6) {
+      const int b = t / 6, c = t - 6 * b;
+      const double *p = kt + (size_t)c * N + (size_t)b * nbl;
+      double f = 0.0;
+      for (int k = 0; k < nbl; ++k) f += p[k];
+      // [U | F | x] of rbl_launch_gmres_small_ens_mixed, as where the right-hand side is loaded above
+      double *Uo = A.x - (size_t)blockIdx.x * nsys - 2 * (size_t)A.reps * nb6 + (size_t)blockIdx.x * nb6, *Fo = Uo + (size_t)A.reps * nb6;
+      if (NLs[NS * b + RS * c + 6] != 0.0) Fo[t] = -f;
+      else Uo[t] = vz[n3 + t];
+    }
+  }
+  if constexpr (MIXED) {
+    if (t == 0) { *A.iters_out = used; *A.resid_out = sc[2]; }
+  } else {
+    if (t == 0) { *A.iters_out = used; *A.resid_out = resid; }
+  }
   if (flags) atomicOr(A.err, flags);
 }
 
 }  // namespace
 
-static size_t small_lds_base_bytes(int N_blb, int N_bod, int max_iter)
+static size_t small_lds_base_bytes(int N_blb, int N_bod, int max_iter, bool mixed = false)
 {
   const size_t N = (size_t)N_blb * N_bod, n3 = 3 * N, nb6 = 6 * (size_t)N_bod, nsys = n3 + nb6, m = (size_t)max_iter;
   return sizeof(double) * (2 * n3 + 2 * N + N + 36 * (size_t)N_bod + 3 * nsys + nb6 + 3 * (m + 2) + 2 * m + 8 + (SGT / 64) * n3 + n3 + 6 * N +
-                           (max_iter <= SG_RLDS ? m * (m + 1) / 2 : 0));
+                           (max_iter <= SG_RLDS ? m * (m + 1) / 2 : 0) + (mixed ? nb6 : 0));   // mixed: the mask, one flag per row of NLs
 }
 static size_t small_basis_bytes(int N_blb, int N_bod, int max_iter)
 {
@@ -432,11 +547,11 @@ static size_t small_basis_bytes(int N_blb, int N_bod, int max_iter)
 }
 
 // does the one-kernel solver cover this system?
-bool rbl_gmres_small_fits(int N_blb, int N_bod, int max_iter, bool block_pc)
+bool rbl_gmres_small_fits(int N_blb, int N_bod, int max_iter, bool block_pc, bool mixed)
 {
   const long N = (long)N_blb * N_bod;
   if (block_pc || N < 1 || N > SG_MAXN || N_bod > SG_MAXB || max_iter < 1 || max_iter > SG_MAXIT) return false;
-  return small_lds_base_bytes(N_blb, N_bod, max_iter) <= SG_LDS_MAX;
+  return small_lds_base_bytes(N_blb, N_bod, max_iter, mixed) <= SG_LDS_MAX;
 }
 
 size_t rbl_gmres_small_work_doubles(int N_blb, int N_bod, int max_iter)
@@ -446,16 +561,18 @@ size_t rbl_gmres_small_work_doubles(int N_blb, int N_bod, int max_iter)
 }
 
 // one workgroup per replica: reps systems of the same shape, replica r's X, Q, rhs, x0, x, workspace, iterations, residual and
-// error word lie r strides further (rbl_launch_gmres_small is the grid of one)
+// error word lie r strides further (rbl_launch_gmres_small is the grid of one).  MIXED: mask, body_in and reps of A are set by
+// the caller (replica r's r N_bod / 6 N_bod further), d_x is the x of a block [U | F | x]
+template <bool MIXED>
 static int launch_small(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
                         int N_blb, int N_bod, const double *d_rhs, const double *d_x0, double *d_x, int max_iter, double rtol,
-                        double fsign, double *d_work, int *d_iters, double *d_resid, unsigned *d_err, int reps, int err_stride)
+                        double fsign, double *d_work, int *d_iters, double *d_resid, unsigned *d_err, int reps, int err_stride,
+                        std::conditional_t<MIXED, SmallArgsMixed, SmallArgs> A = {})
 {
-  if (!rbl_gmres_small_fits(N_blb, N_bod, max_iter, false)) return RBL_ERR_SIZE;
+  if (!rbl_gmres_small_fits(N_blb, N_bod, max_iter, false, MIXED)) return RBL_ERR_SIZE;
   const size_t nsys = (size_t)3 * N_blb * N_bod + (size_t)6 * N_bod;
-  size_t lds = small_lds_base_bytes(N_blb, N_bod, max_iter);
+  size_t lds = small_lds_base_bytes(N_blb, N_bod, max_iter, MIXED);
   bool vlds = lds + small_basis_bytes(N_blb, N_bod, max_iter) <= SG_LDS_MAX;     // the Krylov basis beside the vectors in LDS?
-  SmallArgs A;
   A.X = dX; A.Q = dQ; A.cfg = dcfg; A.rhs = d_rhs; A.x0 = d_x0; A.x = d_x;
   A.V = d_work; A.H = d_work + (size_t)(max_iter + 1) * nsys;
   A.iters_out = d_iters; A.resid_out = d_resid; A.err = d_err;
@@ -465,8 +582,8 @@ static int launch_small(hipStream_t st, const RblParams &P, bool wall, const dou
   // global memory; if even the vectors do not fit the caller falls back to the general solver (RBL_ERR_SIZE).
   auto allow = [&](bool v, size_t bytes) {
     if (bytes <= 64 * 1024) return true;
-    const void *fn = wall ? (v ? (const void *)k_gmres_small<true, true> : (const void *)k_gmres_small<true, false>)
-                          : (v ? (const void *)k_gmres_small<false, true> : (const void *)k_gmres_small<false, false>);
+    const void *fn = wall ? (v ? (const void *)k_gmres_small<true, true, MIXED> : (const void *)k_gmres_small<true, false, MIXED>)
+                          : (v ? (const void *)k_gmres_small<false, true, MIXED> : (const void *)k_gmres_small<false, false, MIXED>);
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return true;
     (void)hipGetLastError();
     return false;
@@ -478,11 +595,11 @@ static int launch_small(hipStream_t st, const RblParams &P, bool wall, const dou
   }
   const dim3 grid((unsigned)reps);
   if (vlds) {
-    if (wall) hipLaunchKernelGGL((k_gmres_small<true, true>), grid, dim3(SGT), lds, st, A);
-    else hipLaunchKernelGGL((k_gmres_small<false, true>), grid, dim3(SGT), lds, st, A);
+    if (wall) hipLaunchKernelGGL((k_gmres_small<true, true, MIXED>), grid, dim3(SGT), lds, st, A);
+    else hipLaunchKernelGGL((k_gmres_small<false, true, MIXED>), grid, dim3(SGT), lds, st, A);
   } else {
-    if (wall) hipLaunchKernelGGL((k_gmres_small<true, false>), grid, dim3(SGT), lds, st, A);
-    else hipLaunchKernelGGL((k_gmres_small<false, false>), grid, dim3(SGT), lds, st, A);
+    if (wall) hipLaunchKernelGGL((k_gmres_small<true, false, MIXED>), grid, dim3(SGT), lds, st, A);
+    else hipLaunchKernelGGL((k_gmres_small<false, false, MIXED>), grid, dim3(SGT), lds, st, A);
   }
   return RBL_OK;
 }
@@ -492,14 +609,28 @@ int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const 
                            int N_blb, int N_bod, const double *d_rhs, const double *d_x0, double *d_x, int max_iter, double rtol,
                            double fsign, double *d_work, double *d_scal, unsigned *d_err)
 {
-  return launch_small(st, P, wall, dX, dQ, dcfg, N_blb, N_bod, d_rhs, d_x0, d_x, max_iter, rtol, fsign, d_work, (int *)d_scal,
-                      d_scal + 1, d_err, 1, 0);
+  return launch_small<false>(st, P, wall, dX, dQ, dcfg, N_blb, N_bod, d_rhs, d_x0, d_x, max_iter, rtol, fsign, d_work, (int *)d_scal,
+                             d_scal + 1, d_err, 1, 0);
 }
 
 int rbl_launch_gmres_small_ens(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
                                int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter, double rtol,
                                double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err)
 {
-  return launch_small(st, P, wall, dX, dQ, dcfg, N_blb, N_bod, d_rhs, nullptr, d_x, max_iter, rtol, 1.0, d_work, d_iters, d_resid,
-                      d_rep_err, reps, 1);
+  return launch_small<false>(st, P, wall, dX, dQ, dcfg, N_blb, N_bod, d_rhs, nullptr, d_x, max_iter, rtol, 1.0, d_work, d_iters, d_resid,
+                             d_rep_err, reps, 1);
+}
+
+// the masked solve (MIXED above) of every replica: d_rhs is the all-free right-hand side [slip ; -body_in] (the loads of the free
+// bodies), d_mask reps x N_bod bytes, d_body_in reps x 6 N_bod (the prescribed bodies' velocities are read); d_UFx is ONE block
+// [U: reps x 6 N_bod | F: reps x 6 N_bod | x: reps x nsys]
+int rbl_launch_gmres_small_ens_mixed(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ,
+                                     const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_UFx, int max_iter,
+                                     double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err,
+                                     const unsigned char *d_mask, const double *d_body_in)
+{
+  SmallArgsMixed A = {};
+  A.mask = d_mask; A.body_in = d_body_in; A.reps = reps;
+  return launch_small<true>(st, P, wall, dX, dQ, dcfg, N_blb, N_bod, d_rhs, nullptr, d_UFx + (size_t)2 * reps * 6 * N_bod, max_iter, rtol,
+                            1.0, d_work, d_iters, d_resid, d_rep_err, reps, 1, A);
 }

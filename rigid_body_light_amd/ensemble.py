@@ -85,6 +85,87 @@ class Ensemble:
                 _fail("W must have shape (%d, %d); got %s" % (self.R, n, W.shape))
         return self.ctx.ensemble_step_brownian(F, W=W, seed=seed, split_rand=split_rand, delta=delta, max_iter=max_iter, rtol=rtol)
 
+    # ------------------------------------------------------------------ prescribed bodies (include/rbl.h sections 5 and 7)
+    def _prescribed_mask(self, prescribed):
+        """as RigidBody.solve_mixed reads it: a boolean array -- (N_bod,), broadcast over the replicas, or (R, N_bod) -- or a list of
+        body indices (integers are ALWAYS indices, the same bodies in every replica) -> uint8 (R, N_bod); ValueError before the
+        library is called"""
+        p = np.asarray(prescribed)
+        R, nb = self.R, self.N_bodies
+        if p.dtype == np.bool_:
+            if p.shape == (nb,):
+                p = np.broadcast_to(p, (R, nb))
+            if p.shape != (R, nb):
+                _fail("prescribed: a boolean array must have shape (%d,) or (%d, %d); got %s" % (nb, R, nb, p.shape))
+            return np.ascontiguousarray(p, dtype=np.uint8)
+        if p.size and not np.issubdtype(p.dtype, np.integer):
+            _fail("prescribed must be a boolean array or a list of body indices; got dtype %s" % p.dtype)
+        idx = p.reshape(-1).astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= nb):
+            _fail("prescribed: body indices must lie in [0, %d)" % nb)
+        if np.unique(idx).size != idx.size:
+            _fail("prescribed: a body index appears twice (integers are body indices; a 0/1 mask must have dtype bool)")
+        mask = np.zeros((R, nb), dtype=np.uint8)
+        mask[:, idx] = 1
+        return mask
+
+    def _body_in(self, body_in):
+        b = np.asarray(body_in, dtype=np.float64)
+        R, nb = self.R, self.N_bodies
+        if b.shape in ((6 * nb,), (nb, 6)):
+            return np.ascontiguousarray(np.broadcast_to(b.reshape(1, 6 * nb), (R, 6 * nb)))
+        if b.shape in ((R, 6 * nb), (R, nb, 6)):
+            return np.ascontiguousarray(b.reshape(R, 6 * nb))
+        _fail("body_in must have shape (%d,), (%d, 6), (%d, %d) or (%d, %d, 6); got %s" % (6 * nb, nb, R, 6 * nb, R, nb, b.shape))
+
+    def _slip(self, slip):
+        if slip is None:
+            return None
+        s = np.asarray(slip, dtype=np.float64)
+        n3 = 3 * self.N_bodies * self.blobs_per_body
+        if s.shape not in ((n3,), (self.R, n3)):
+            _fail("slip must have shape (%d,) or (%d, %d); got %s" % (n3, self.R, n3, s.shape))
+        return s
+
+    def solve_mixed(self, prescribed, body_in, slip=None, max_iter=100, rtol=1e-8):
+        """RigidBody.solve_mixed at every replica's configuration; nothing moves.  The bodies in `prescribed` move with the velocity
+        in their six slots of body_in, the others carry their load there.  -> (lambda (R, n3), U (R, 6 N_bod), F (R, 6 N_bod),
+        iterations (R,), residual estimates (R,))"""
+        m, b, s = self._prescribed_mask(prescribed), self._body_in(body_in), self._slip(slip)
+        return self.ctx.ensemble_solve_mixed(m, b, max_iter=max_iter, rtol=rtol, slip=s)
+
+    def step_mixed(self, prescribed, body_in, slip=None, max_iter=50, rtol=1e-8):
+        """one deterministic step of every replica with held or driven bodies -> (F (R, 6 N_bod), iterations (R,), residual
+        estimates (R,)): a driven body advances by exactly dt U_p, the force model loads the free bodies only"""
+        m, b, s = self._prescribed_mask(prescribed), self._body_in(body_in), self._slip(slip)
+        return self.ctx.ensemble_step_mixed(m, b, max_iter=max_iter, rtol=rtol, slip=s)
+
+    def step_brownian_mixed(self, prescribed, body_in, slip=None, W=None, seed=0, split_rand=True, delta=1e-4, max_iter=50, rtol=1e-8):
+        """one stochastic midpoint step of every replica with held or driven bodies -> (F (R, 6 N_bod), iterations (R,), residual
+        estimates (R,)).  F of a prescribed body is its instantaneous load, thermal part included: average it over replicas and
+        steps.  W as step_brownian"""
+        m, b, s = self._prescribed_mask(prescribed), self._body_in(body_in), self._slip(slip)
+        if W is not None:
+            W = np.asarray(W, dtype=np.float64)
+            n = 9 * self.N_bodies * self.blobs_per_body
+            if W.shape != (self.R, n):
+                _fail("W must have shape (%d, %d); got %s" % (self.R, n, W.shape))
+        return self.ctx.ensemble_step_brownian_mixed(m, b, W=W, seed=seed, split_rand=split_rand, delta=delta, max_iter=max_iter,
+                                                     rtol=rtol, slip=s)
+
+    def body_resistance_matrix(self, max_iter=100, rtol=1e-8):
+        """the body resistance matrix of every replica's configuration, (R, 6 N_bod, 6 N_bod): every body prescribed, one ensemble
+        solve per unit velocity; sign as RigidBody.body_resistance_matrix (a column is -F: the PHYSICAL loads R U, nothing
+        is symmetrised)"""
+        nb6 = 6 * self.N_bodies
+        everyone = np.ones((self.R, self.N_bodies), dtype=bool)
+        Rm = np.zeros((self.R, nb6, nb6))
+        for j in range(nb6):
+            U = np.zeros(nb6)
+            U[j] = 1.0
+            Rm[:, :, j] = -self.solve_mixed(everyone, U, max_iter=max_iter, rtol=rtol)[2]
+        return Rm
+
     def set_interactions(self, w=0.0, eps_wall=0.0, b_wall=1.0, eps_blob=0.0, b_blob=1.0, r_cut=None, on=True):
         """the force model of RigidBody.set_interactions, for every replica (steric pairs only inside a replica)"""
         self.ctx.set_interactions(w=w, eps_wall=eps_wall, b_wall=b_wall, eps_blob=eps_blob, b_blob=b_blob, r_cut=r_cut, on=on)
