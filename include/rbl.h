@@ -249,6 +249,14 @@ int rbl_apply_M_sym_multi_dev(rbl_ctx *ctx, const double *d_F, const double *d_r
 int rbl_apply_M_sym_info(rbl_ctx *ctx, int64_t n_blobs, int i_step, int nrhs, int *rows_per_lane, int *chunk_tiles,
                          int64_t *workspace_bytes);
 
+/* the work units of that product on a GPU of n_cu compute units under the context's options, in the order they are handed out
+ * (work queue: draw order), no device needed: nine numbers a unit -- index in that order, row group, chunk, first column tile,
+ * column tiles, and the workspace ranges it writes for the first vector, in doubles: row sums (offset, length), column sums
+ * (offset, length).  units holds the first `capacity` of the *n_units units.  info (8 ints, may be NULL): rows per lane, waves
+ * per workgroup, chunk length, short chunk length, short chunks, chunks, 1 = work queue, 1 = that queue draws live units only */
+int rbl_apply_M_sym_units(rbl_ctx *ctx, int64_t n_blobs, int n_cu, int i_step, int nrhs, int64_t *units, int64_t capacity,
+                          int64_t *n_units, int *info, int64_t *workspace_bytes);
+
 /* ... and the kernel instantiation a one- or two-vector symmetric product of that size launches under the context's options
  * ("k_apply_M_sym<true,2>", "k_apply_M_symw<false>", ...; name: >= 40 bytes) */
 int rbl_apply_M_sym_kernel(rbl_ctx *ctx, int64_t n_blobs, int i_step, int nrhs, int wall, char *name, int name_len);
@@ -501,7 +509,13 @@ enum {
                                       0x7FF87FF8 (NaN as fp64 and as fp32, a large positive int32), and scratch workspaces are
                                       refilled whenever an entry point reserves them, so a kernel that reads memory nobody wrote
                                       fails loudly instead of reading zeros.  Costs a fill and a stream synchronise per reserve */
-  RBL_OPT_COUNT = 35
+  RBL_OPT_SYM_TAIL_CHUNK = 35,     /* [0] one GPU, four rows per lane: column tiles per work unit of the SHORT chunks the work queue ends on
+                                      (0 = heuristic, 1 .. 16; the chunk length itself = no short chunks).  Chunk boundaries regroup the
+                                      partial row sums: results differ in the last bits between settings, never run to run            */
+  RBL_OPT_SYM_TAIL_SHARE = 36,     /* [0] per-mille of the column tiles swept at that length (0 = heuristic, 1 .. 1000).  The short length
+                                      set to the chunk length together with 1000 here: the schedule of the one-length kernel, the whole
+                                      (row group x chunk) rectangle in its old order                                                 */
+  RBL_OPT_COUNT = 37
 };
 int rbl_set_option(rbl_ctx *ctx, int option, int64_t value);
 int rbl_get_option(const rbl_ctx *ctx, int option, int64_t *value);

@@ -576,6 +576,21 @@ class DeviceContext:
         self._chk(self.L.rbl_apply_M_sym_info(self.h, n_blobs, i_step, nrhs, C.byref(ni), C.byref(ch), C.byref(wb)))
         return ni.value, ch.value, wb.value
 
+    def apply_M_sym_units(self, n_blobs, n_cu=256, i_step=1, nrhs=1):
+        """work units of the symmetric product of that size on a GPU of n_cu compute units under this context's options, in the
+        order they are handed out (needs no device): (units, info, workspace bytes) with units an (n, 9) int64 array -- index, row
+        group, chunk, first column tile, column tiles, row-sum (offset, length), column-sum (offset, length) in doubles -- and info a
+        dict (include/rbl.h rbl_apply_M_sym_units)"""
+        import numpy as np
+        f = self.L.rbl_apply_M_sym_units
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+        n, wb, info = C.c_int64(0), C.c_int64(0), (C.c_int * 8)()
+        self._chk(f(self.h, n_blobs, n_cu, i_step, nrhs, None, 0, C.byref(n), info, C.byref(wb)))
+        units = np.zeros((n.value, 9), dtype=np.int64)
+        self._chk(f(self.h, n_blobs, n_cu, i_step, nrhs, units.ctypes.data, n.value, C.byref(n), info, C.byref(wb)))
+        keys = ("rows_per_lane", "waves", "chunk", "tail_chunk", "tail_chunks", "chunks", "work_queue", "live_only")
+        return units, dict(zip(keys, list(info))), wb.value
+
     def apply_M_sym_kernel(self, n_blobs, wall, i_step=1, nrhs=1):
         """name of the kernel instantiation a symmetric product of that size launches under this context's options"""
         buf = C.create_string_buffer(64)

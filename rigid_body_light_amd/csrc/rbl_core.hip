@@ -83,6 +83,7 @@ int rbl_dev_init(rbl_ctx *c)
 // allocated.  Each row says why.
 // Integer regions (audit: each is written on the context's stream before any kernel reads it, on every path):
 //   d_part   far map bytes + work-queue counter            k_tile_far, in the same product, before the pair kernel
+//            the work queue's unit table                   k_sym_unit_table (every entry below the queue's limit), likewise
 //   d_tl*    tile dependency counters                      hipMemsetAsync in rbl_tilechol.hip before the tile kernel
 //   d_ia     neighbour counts / lists, pairs per blob      k_body_neighbours (every count; list entries below min(count, cap),
 //                                                          the only ones read), k_blob_interactions (every blob)

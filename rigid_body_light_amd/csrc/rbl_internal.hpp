@@ -89,6 +89,8 @@ struct RblSymTune {        // per-context tuning of the symmetric matvec kernels
   int sw = 0;              // > 0: waves per workgroup (0 = heuristic; experiments)
   int queue = 0;           // < 0: one unit per workgroup in launch order also for large systems (RBL_OPT_SYM_WORK_QUEUE = 0); 0: work queue there
   int gap_ratio = 0;       // relaxed product: a tile pair is swept in single precision when (d_I + 2 d_J) <= gap_ratio x gap (0 = default; RBL_OPT_RELAXED_GAP_RATIO)
+  int tail_chunk = 0;      // > 0: length of the short chunks the work queue ends on (0 = heuristic; the chunk length itself: no short chunks; RBL_OPT_SYM_TAIL_CHUNK)
+  int tail_share = 0;      // > 0: per-mille of the column tiles swept at that length (0 = heuristic; RBL_OPT_SYM_TAIL_SHARE)
   int wave_units = 0;      // < 0: mid-size systems on the round-3 kernel (one workgroup per unit, column sums by LDS atomics); 0: wave-owned units (RBL_OPT_SYM_WAVE_UNITS)
   RblSaddleFuse fuse;      // transient: see RblSaddleFuse
   int relaxed = 0;         // transient: far tile pairs in packed single precision (inexact Krylov iterations only)
@@ -263,6 +265,7 @@ void rbl_launch_apply_M(hipStream_t st, const RblParams &P, bool wall, const dou
                         int variant, unsigned *d_err);
 size_t rbl_apply_M_sym_bytes(int64_t n_blobs, int n_cu, int i_step, int nrhs, const RblSymTune &tune,
                              int *NI_out = nullptr, int *C_out = nullptr);
+long rbl_apply_M_sym_units(int64_t n_blobs, int n_cu, int i_step, int nrhs, const RblSymTune &tune, int64_t *out, long cap, int *info);
 void rbl_apply_M_sym_kernel_name(int64_t n_blobs, int n_cu, int i_step, int nrhs, const RblSymTune &tune, bool wall, char *out, size_t len);
 // nrhs = 1 or 2 vectors ([nrhs][3 n_blobs]); workspace rbl_apply_M_sym_bytes(..., nrhs)
 int rbl_launch_apply_M_sym(hipStream_t st, const RblParams &P, bool wall, const double *d_F,

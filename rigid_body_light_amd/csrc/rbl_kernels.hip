@@ -183,18 +183,18 @@ constexpr int TS = 64;
 // owned unit is taken from the ge-th block of i_step consecutive units, offset i_first in even blocks and
 // i_step - 1 - i_first in odd ones: two consecutive blocks give every rank the same work.  Increasing in e (the
 // column-sum slabs rely on it).  sw = 1 or i_step = 1: the plain maps.
-__device__ __forceinline__ int sym_unit_of(int ge, int i_first, int i_step)
+__host__ __device__ __forceinline__ int sym_unit_of(int ge, int i_first, int i_step)
 {
   return ge * i_step + ((ge & 1) ? i_step - 1 - i_first : i_first);
 }
-__device__ __forceinline__ int sym_row_of(int e, int i_first, int i_step, int sw)
+__host__ __device__ __forceinline__ int sym_row_of(int e, int i_first, int i_step, int sw)
 {
   const int ge = e / sw;
   return sym_unit_of(ge, i_first, i_step) * sw + (e - ge * sw);
 }
-__device__ __forceinline__ bool sym_unit_owned(int G, int i_first, int i_step) { return sym_unit_of(G / i_step, i_first, i_step) == G; }
-__device__ __forceinline__ bool sym_row_owned(int I, int i_first, int i_step, int sw) { return sym_unit_owned(I / sw, i_first, i_step); }
-__device__ __forceinline__ int sym_rows_below(int Ilim, int i_first, int i_step, int sw)   // owned rows I < Ilim
+__host__ __device__ __forceinline__ bool sym_unit_owned(int G, int i_first, int i_step) { return sym_unit_of(G / i_step, i_first, i_step) == G; }
+__host__ __device__ __forceinline__ bool sym_row_owned(int I, int i_first, int i_step, int sw) { return sym_unit_owned(I / sw, i_first, i_step); }
+__host__ __device__ __forceinline__ int sym_rows_below(int Ilim, int i_first, int i_step, int sw)   // owned rows I < Ilim
 {
   const int Gl = Ilim / sw, rem = Ilim - Gl * sw;                     // units 0 .. Gl-1 lie wholly below Ilim
   const int eb = Gl / i_step;                                         // blocks 0 .. eb-1 lie wholly below unit Gl
@@ -229,6 +229,9 @@ __global__ __launch_bounds__(TS) void k_tile_bbox(const double *__restrict__ r, 
     b[0] = lo[0]; b[1] = lo[1]; b[2] = lo[2]; b[3] = hi[0]; b[4] = hi[1]; b[5] = hi[2];
   }
 }
+
+// what sym_unit_of_index needs beside the layout: whole units / all units of the long chunks, whole units of the short ones
+struct SymSched { unsigned nAc, nUc, nAf; };
 
 // farmap[S][J] = 1 when every blob of tile J is farther than 2a from every blob of row super-tile S
 // (NI consecutive tiles): one byte per (super-tile, tile), read as a wave-uniform value by the matvec kernel.
@@ -283,7 +286,8 @@ typedef double double2_t __attribute__((ext_vector_type(2)));
 //   column sums  slabJ[g]  : ONE set per row group (the SW waves' LDS accumulators are added in wave order before the
 //                            write), for the column blobs at or after the group's first row, [RJ(g), Npad)
 // With one rank (i_step == 1) both are stored as triangles (tri = 1): prefix offsets in closed form,
-//   offI(c) = 64 [C c (c+1) / 2 + (NI-1) c],      offJ(g) = g Npad - RJ1 g (g-1) / 2,   RJ(g) = RJ1 g,   RJ1 = 64 NI SW;
+//   offI(c) = 64 [C c (c+1) / 2 + (NI-1) c],      offJ(g) = g Npad - RJ1 g (g-1) / 2,   RJ(g) = RJ1 g,   RJ1 = 64 NI SW
+// (one chunk length; with nf short chunks of Cf tiles in front of the long ones the same sums in two pieces, sym_offI);
 // row shards of a multi-GPU launch own every i_step-th super-tile, their slabs stay rectangular (and are 1/i_step of
 // the single-rank size anyway).  nrhs vectors lie back to back inside a slab.  All in units of blobs (x 3 doubles).
 // SW = 4 for large systems (two rows per lane), 1 otherwise: with few tiles the lock-step of a multi-wave workgroup and
@@ -295,25 +299,55 @@ typedef double double2_t __attribute__((ext_vector_type(2)));
 #define RBL_SYM_WAVES 4
 #endif
 constexpr int SW_LARGE = RBL_SYM_WAVES;
+// SYM_TAIL_RULE: short chunks at the end of the work queue (four rows per lane; sym_geometry) -- length in tiles and the per-mille of
+// the column tiles they cover.  tools/bench_unit_schedule.py, one box, interleaved, minimum of 4 rounds of 5 products against the
+// old rectangle draw at C = 15 (2 007 tiles, 20.32 ms): live units only 0.995; C_f = 4 over 20 / 30 / 40 / 50 % of the tiles 0.989 /
+// 0.989 / 0.986 / 0.991; C_f = 3 and 5 and C = 8 and 12 within the 0.5 % the rounds scatter by.  30 % of the tiles is the last 9 % of
+// the pairs: the tail idle share falls from 0.034 to 0.010.  Applied where the chunk is longer than C_f (below ~1 600 tiles it is not).
+#ifndef RBL_SYM_TAIL_CHUNK
+#define RBL_SYM_TAIL_CHUNK 4
+#endif
+#ifndef RBL_SYM_TAIL_SHARE
+#define RBL_SYM_TAIL_SHARE 300
+#endif
 #ifndef RBL_SYM_NI4_TILES
 #define RBL_SYM_NI4_TILES 1000    // one vector, one GPU: four rows per lane from this many 64-blob tiles on (sym_geometry; measured
                                   // with tools/bench_rows_per_lane.py, wall: 4 / 2 rows = 1.010 at 642 tiles, 0.982 at 1 004, 0.977 at 2 007)
 #endif
 
+// Two chunk lengths (one GPU, multi-wave workgroups; sym_geometry): the chunks 0 .. nf-1 are Cf tiles long and cover the column tiles
+// [0, nf Cf), the chunks nf .. nch-1 are C tiles long and follow them.  The work queue hands the long chunks out first, so the
+// kernel ends on short units.  nf = 0 is the one-length layout (every wave-unit kernel, every multi-GPU shard).
+// nU > 0: the work queue enumerates the nU live units in the order of sym_unit_of_index; 0: the whole rowsG x nch rectangle.
 struct SymLayout {
   long Npad;
   int T, NI, C, nch, rowsI, rowsG, tri, nrhs, i_first, i_step, SW;
+  int fine;                        // nf and Cf in one word (32 nf + Cf, Cf <= 16: one scalar register less through the sweeps); sym_nf, sym_Cf
+  unsigned nU;
 };
+__host__ __device__ __forceinline__ int sym_nf(const SymLayout &L) { return L.fine >> 5; }
+__host__ __device__ __forceinline__ int sym_Cf(const SymLayout &L) { return L.fine & 31; }
 
+__host__ __device__ __forceinline__ int sym_chunk_first(const SymLayout &L, int c) { return c < sym_nf(L) ? c * sym_Cf(L) : sym_nf(L) * sym_Cf(L) + (c - sym_nf(L)) * L.C; }
+__host__ __device__ __forceinline__ int sym_chunk_len(const SymLayout &L, int c) { return c < sym_nf(L) ? sym_Cf(L) : L.C; }
+__host__ __device__ __forceinline__ int sym_chunk_of(const SymLayout &L, int t)      // the chunk column tile t lies in
+{
+  const int S = sym_nf(L) * sym_Cf(L);
+  return t < S ? t / sym_Cf(L) : sym_nf(L) + (t - S) / L.C;
+}
 __host__ __device__ __forceinline__ long sym_HI(const SymLayout &L, int c)
 {
   if (!L.tri) return L.Npad;
-  const long h = (long)(c + 1) * L.C + (L.NI - 1);
+  const long h = (long)sym_chunk_first(L, c) + sym_chunk_len(L, c) + (L.NI - 1);
   return (h < L.T ? h : (long)L.T) * TS;
 }
+// (tri: the sum of the uncapped HI of the chunks before c -- short ones 64 (Cf (k+1) + NI-1), long ones 64 (S + C (k+1) + NI-1))
 __host__ __device__ __forceinline__ long sym_offI(const SymLayout &L, int c)
 {
-  return L.tri ? (long)TS * ((long)L.C * ((long)c * (c + 1) / 2) + (long)(L.NI - 1) * c) : (long)c * L.Npad;
+  if (!L.tri) return (long)c * L.Npad;
+  const long cf = c < sym_nf(L) ? c : sym_nf(L), m = c - cf;
+  return (long)TS * ((long)sym_Cf(L) * (cf * (cf + 1) / 2) + (long)(L.NI - 1) * cf +
+                     m * ((long)sym_nf(L) * sym_Cf(L) + (L.NI - 1)) + (long)L.C * (m * (m + 1) / 2));
 }
 __host__ __device__ __forceinline__ long sym_RJ(const SymLayout &L, int g) { return L.tri ? (long)TS * L.NI * L.SW * g : 0; }
 __host__ __device__ __forceinline__ long sym_offJ(const SymLayout &L, int g)
@@ -321,11 +355,11 @@ __host__ __device__ __forceinline__ long sym_offJ(const SymLayout &L, int g)
   return L.tri ? (long)g * L.Npad - (long)TS * L.NI * L.SW * ((long)g * (g - 1) / 2) : (long)g * L.Npad;
 }
 // doubles: address of (vector v, blob b) in chunk c's row-sum slab / group g's column-sum slab
-__device__ __forceinline__ size_t sym_idxI(const SymLayout &L, int c, int v, long b)
+__host__ __device__ __forceinline__ size_t sym_idxI(const SymLayout &L, int c, int v, long b)
 {
   return ((size_t)sym_offI(L, c) * L.nrhs + (size_t)v * sym_HI(L, c) + (size_t)b) * 3;
 }
-__device__ __forceinline__ size_t sym_idxJ(const SymLayout &L, int g, int v, long b)
+__host__ __device__ __forceinline__ size_t sym_idxJ(const SymLayout &L, int g, int v, long b)
 {
   const long rj = sym_RJ(L, g);
   return ((size_t)sym_offJ(L, g) * L.nrhs + (size_t)v * (L.Npad - rj) + (size_t)(b - rj)) * 3;
@@ -351,6 +385,122 @@ __device__ __forceinline__ double sym_first_lane(double v)      // lane 0's valu
 #define RBL_WT_BEGIN
 #define RBL_WT_END(unit)
 #endif
+
+// ---- the work queue's units (one GPU, multi-wave workgroups, sched = 1) -------------------------------------------------------
+// A unit = row group g (first row tile g G, G = NI SW) x chunk c; it is live when g G lies before the chunk's end, WHOLE when
+// g G <= the chunk's first tile (it sweeps every tile of the chunk) and CUT by the diagonal otherwise (it starts at g G).  Only live
+// units are drawn, the long chunks' before the short ones', and within a length: the whole units of the full-length chunks (last
+// chunk first), then everything shorter by falling tile count -- units the diagonal cuts, and the units of a last chunk that the
+// matrix edge cuts short -- so that the units a resident workgroup still holds when the queue runs dry are the shortest there are.
+// Index -> (g, c) in closed form: sum_{i<n} floor((a i + b) / m) by the Euclid-like descent.
+__host__ __device__ __forceinline__ unsigned sym_floor_sum(unsigned n, unsigned m, unsigned a, unsigned b)
+{
+  unsigned ans = 0;
+  for (;;) {
+    if (a >= m) { ans += (n - 1) * n / 2 * (a / m); a %= m; }
+    if (b >= m) { ans += n * (b / m); b %= m; }
+    const unsigned y = a * n + b;
+    if (y < m) break;
+    n = y / m; b = y % m;
+    const unsigned t = m; m = a; a = t;
+  }
+  return ans;
+}
+struct SymClass { int a, len, n, cbase; };      // the n chunks cbase .. of one length: first tiles a, a + len, ...
+__host__ __device__ __forceinline__ SymClass sym_class(const SymLayout &L, bool fine)
+{
+  return fine ? SymClass{0, sym_Cf(L), sym_nf(L), 0} : SymClass{sym_nf(L) * sym_Cf(L), L.C, L.nch - sym_nf(L), sym_nf(L)};
+}
+__host__ __device__ __forceinline__ int sym_class_full(const SymLayout &L, const SymClass &k)   // its chunks of full length (all but a last one the matrix edge cuts)
+{
+  return (k.n > 0 && k.a + k.n * k.len > L.T) ? k.n - 1 : k.n;
+}
+// whole units of the class's first k full-length chunks: chunk i has floor((a + i len) / G) + 1
+__host__ __device__ __forceinline__ unsigned sym_class_whole(const SymLayout &L, const SymClass &k, int nk)
+{
+  return nk <= 0 ? 0u : (unsigned)nk + sym_floor_sum((unsigned)nk, (unsigned)(L.NI * L.SW), (unsigned)k.len, (unsigned)k.a);
+}
+static unsigned sym_class_live(const SymLayout &L, const SymClass &k)      // live units of the class: chunk by chunk, the groups before its end
+{
+  const int G = L.NI * L.SW;
+  unsigned n = 0;
+  for (int i = 0; i < k.n; ++i) { const int e = std::min(k.a + (i + 1) * k.len, L.T); n += (unsigned)((e + G - 1) / G); }
+  return n;
+}
+// unit p of the class (nA: its whole units of full-length chunks) -> (g, c); false: p is past the class's last unit
+__host__ __device__ inline bool sym_class_unit(const SymLayout &L, const SymClass &k, unsigned nA, unsigned p, int &g, int &c)
+{
+  const int G = L.NI * L.SW, nfull = sym_class_full(L, k);
+  if (p < nA) {                                   // whole units, last chunk first: chunk i holds the positions [nA - W(i+1), nA - W(i))
+    const unsigned q = nA - p;                    // smallest i + 1 with W(i + 1) >= q
+    int lo = 0, hi = nfull;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (sym_class_whole(L, k, mid) >= q) hi = mid; else lo = mid;
+    }
+    c = k.cbase + hi - 1;
+    g = (int)(p - (nA - sym_class_whole(L, k, hi)));
+    return true;
+  }
+  p -= nA;
+  const int end_full = k.a + nfull * k.len;       // first tile behind the full-length chunks
+  const int g_lo = k.a / G + 1, g_hi = end_full > 0 ? (end_full - 1) / G : -1;   // groups whose first tile lies inside them, behind a
+  int P = 1;                                      // (g G - a) mod len repeats with this period in g
+  while ((P * G) % k.len) ++P;
+  const bool edge = nfull < k.n;
+  const int rem = L.T - end_full;                 // edge: tiles of the last chunk
+  for (int m = k.len - 1; m >= 1; --m) {
+    // cut units of m tiles: g G = (chunk's end) - m, i.e. (g G - a) mod len = len - m -- an arithmetic progression in g
+    for (int t = 0; t < P; ++t) {
+      const int g0 = g_lo + t;
+      if ((g0 * G - k.a) % k.len != k.len - m) continue;
+      if (g0 > g_hi) break;
+      const unsigned n = (unsigned)((g_hi - g0) / P + 1);
+      if (p < n) { g = g0 + (int)p * P; c = k.cbase + (g * G - k.a) / k.len; return true; }
+      p -= n;
+      break;
+    }
+    if (edge) {
+      const int nw = end_full / G + 1;            // the last chunk's whole units have rem tiles, the group behind them T - g G
+      if (rem == m) {
+        if (p < (unsigned)nw) { g = (int)p; c = k.cbase + nfull; return true; }
+        p -= (unsigned)nw;
+      }
+      for (int g0 = nw; g0 * G < L.T; ++g0)
+        if (L.T - g0 * G == m) {
+          if (p == 0) { g = g0; c = k.cbase + nfull; return true; }
+          --p;
+        }
+    }
+  }
+  return false;
+}
+__host__ __device__ __forceinline__ void sym_unit_of_index(const SymLayout &L, const SymSched &S, unsigned u, int &g, int &c)
+{
+  if (u < S.nUc) sym_class_unit(L, sym_class(L, false), S.nAc, u, g, c);
+  else sym_class_unit(L, sym_class(L, true), S.nAf, u - S.nUc, g, c);
+}
+// The queue in the workspace: word 0 the counter (k_tile_far zeroes it), word 1 the number of units, and from word SYM_QUEUE_WORDS on
+// the units themselves, index -> (row group, chunk), written out once per product: the closed form costs a lane microseconds (two
+// dozen integer divisions in a binary search) that a workgroup would otherwise spend, all its waves waiting, at every draw -- 6 % of
+// the product at 642 tiles with one-tile chunks (tools/bench_unit_schedule.py) -- and read from memory the schedule keeps no
+// scalar register of the pair kernel busy through its sweeps.  nU = 0: the rectangle, long chunks first, row groups rotated.
+constexpr int SYM_QUEUE_WORDS = 32;
+__host__ __device__ __forceinline__ unsigned sym_queue_units(const SymLayout &L) { return L.nU ? L.nU : (unsigned)L.rowsG * (unsigned)L.nch; }
+__global__ __launch_bounds__(256) void k_sym_unit_table(SymLayout L, SymSched S, unsigned *__restrict__ queue)
+{
+  const unsigned u = blockIdx.x * 256u + threadIdx.x, n = sym_queue_units(L);
+  if (u == 0) queue[1] = n;
+  if (u >= n) return;
+  int g = 0, c = 0;
+  if (L.nU) sym_unit_of_index(L, S, u, g, c);
+  else {
+    const int by = (int)(u / (unsigned)L.rowsG), bx = (int)(u - (unsigned)by * (unsigned)L.rowsG);
+    c = L.nch - 1 - by; g = (bx + by) % L.rowsG;
+  }
+  unsigned *table = queue + SYM_QUEUE_WORDS;
+  table[2 * u] = (unsigned)g; table[2 * u + 1] = (unsigned)c;
+}
 
 // ---- pieces both symmetric kernel families share (NV = 1 or 2 force vectors) ------------------------------------------------
 // blob idx as the pair arithmetic wants it: position divided by the blob radius, the NV forces damped (vector v of F at F + 3 N v)
@@ -379,11 +529,12 @@ __device__ __forceinline__ void sym_load_blob(const double *__restrict__ r, cons
 }
 
 // the column tiles [J0, J1) of chunk c that a unit whose first row tile is It sweeps; false: none (a dead unit)
-__device__ __forceinline__ bool sym_unit_columns(const SymLayout &L, int c, int It, int &J0, int &J1)
+__host__ __device__ __forceinline__ bool sym_unit_columns(const SymLayout &L, int c, int It, int &J0, int &J1)
 {
   if (It >= L.T) return false;
-  J0 = c * L.C;
-  J1 = (J0 + L.C < L.T) ? J0 + L.C : L.T;
+  J0 = sym_chunk_first(L, c);
+  J1 = J0 + sym_chunk_len(L, c);
+  if (J1 > L.T) J1 = L.T;
   if (J0 < It) J0 = It;
   return J0 < J1;
 }
@@ -472,6 +623,7 @@ __device__ __forceinline__ void sym_store_rows(double *__restrict__ slabI, const
 constexpr int sym_min_waves(bool WALL, int NI, int SW, int PREC, int NV)   // minimum waves per SIMD (HIP's second launch bound)
 {
   if (WALL && NI == 2 && SW > 1 && PREC == 0) return NV == 2 ? RBL_SYM2_MIN_WAVES : 3;
+  if (!WALL && NI == 2 && SW > 1 && PREC == 0 && NV == 1) return 4;   // (the 128 VGPRs it took unasked until the layout grew by the short chunks' word: 129)
   return (NV == 1 && NI == 4) ? 2 : 1;
 }
 
@@ -496,7 +648,7 @@ __global__ __launch_bounds__(TS *SW, sym_min_waves(WALL, NI, SW, PREC, NV)) void
   __shared__ float sPf[PREC ? 3 + 3 * NV : 1][TS];  // relaxed product: x y z f_0 .. of the j tile in single precision, origin-relative
   const int lane = threadIdx.x & (TS - 1);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int T = L.T, C = L.C;
+  const int T = L.T;
   unsigned flags = 0;
   __shared__ double sO[3];                          // relaxed product: origin of the single-precision coordinates = first blob of the j tile
   // All pair arithmetic of this kernel runs in coordinates divided by the blob radius (the mobility entries
@@ -665,29 +817,49 @@ __global__ __launch_bounds__(TS *SW, sym_min_waves(WALL, NI, SW, PREC, NV)) void
       }
     }
   }
-  // this wave swept at least one tile of the chunk: its row sums (k_reduce_sym reads chunks >= It0 / C)
-  if (wlive && c * C + C > It0) sym_store_rows<NI, NV>(slabI, L, c, It0, lane, ui);
+  // this wave swept at least one tile of the chunk (J1 = its end, or T; It0 < T): its row sums (k_reduce_sym reads the chunks from It0's on)
+  if (wlive && J1 > It0) sym_store_rows<NI, NV>(slabI, L, c, It0, lane, ui);
   RBL_WT_END(unit)
   };
-  if (!queue) {
-    // one unit per workgroup.  Workgroups go to the 8 XCDs round-robin in launch order: rotate the row group with the chunk,
+  if (SW == 1 || !queue) {
+    // one unit per workgroup (single-wave workgroups always).  Workgroups go to the 8 XCDs round-robin in launch order: rotate the row group with the chunk,
     // or a group count that is a multiple of 8 pins every group (and its triangular share of the work) to one XCD
     sweep_unit((int)blockIdx.y, (int)((blockIdx.x + blockIdx.y) % gridDim.x), blockIdx.y * gridDim.x + blockIdx.x);
   } else {
     // WORK QUEUE (large systems): a fixed set of resident workgroups draws units from one counter until it runs dry, so an
     // XCD that runs faster -- they differ by up to 5 % under fp64 load, and launch-order dispatch deals every XCD the same
     // number of workgroups -- simply takes more units, and nobody idles for longer than one unit at the end.  The slabs are
-    // addressed by unit, not by workgroup: results do not depend on who swept what.  Long chunks first.
+    // addressed by unit, not by workgroup: results do not depend on who swept what.  Long chunks first; four rows per lane: only the
+    // live units, the shortest last (sym_unit_of_index), otherwise the whole rectangle, whose dead half leaves at once.
     __shared__ unsigned s_unit;
-    const unsigned n_units = (unsigned)L.rowsG * (unsigned)L.nch;
-    for (;;) {
-      __syncthreads();                                   // the previous unit's LDS is dead
-      if (threadIdx.x == 0) s_unit = atomicAdd(queue, 1u);
-      __syncthreads();
-      const unsigned u = s_unit;
-      if (u >= n_units) break;
-      const int by = (int)(u / (unsigned)L.rowsG), bx = (int)(u - (unsigned)by * (unsigned)L.rowsG);
-      sweep_unit(L.nch - 1 - by, (bx + by) % L.rowsG, u);
+    if constexpr (NI == 4) {                             // the units come from the table (k_sym_unit_table): live ones only, shortest last
+      __shared__ int s_gc[2];
+      for (;;) {
+        __syncthreads();                                 // the previous unit's LDS is dead
+        if (threadIdx.x == 0) {                          // one lane draws the unit and looks it up
+          unsigned u = atomicAdd(queue, 1u);
+          if (u < queue[1]) {
+            const unsigned *tab = queue + SYM_QUEUE_WORDS + 2 * (size_t)u;
+            s_gc[0] = (int)tab[0]; s_gc[1] = (int)tab[1];
+          } else u = ~0u;
+          s_unit = u;
+        }
+        __syncthreads();
+        const unsigned u = s_unit;
+        if (u == ~0u) break;
+        sweep_unit(__builtin_amdgcn_readfirstlane(s_gc[1]), __builtin_amdgcn_readfirstlane(s_gc[0]), u);
+      }
+    } else {                                             // two rows per lane: the whole rectangle, long chunks first, row groups rotated
+      const unsigned n_units = (unsigned)L.rowsG * (unsigned)L.nch;
+      for (;;) {
+        __syncthreads();                                 // the previous unit's LDS is dead
+        if (threadIdx.x == 0) s_unit = atomicAdd(queue, 1u);
+        __syncthreads();
+        const unsigned u = s_unit;
+        if (u >= n_units) break;
+        const int by = (int)(u / (unsigned)L.rowsG), bx = (int)(u - (unsigned)by * (unsigned)L.rowsG);
+        sweep_unit(L.nch - 1 - by, (bx + by) % L.rowsG, u);
+      }
     }
   }
   if (flags) atomicOr(err, flags);
@@ -893,10 +1065,10 @@ __global__ __launch_bounds__(64 * RG) void k_reduce_sym(const double *__restrict
   const long j = idc / 3;
   const int k = (int)(idc - 3 * j);
   const int J = (int)(j / TS);
-  const int NI = L.NI, C = L.C;
+  const int NI = L.NI;
   const int Is = J / NI;                                 // super-tile owning row tile J
   const bool owned = sym_row_owned(Is, L.i_first, L.i_step, L.SW);   // this launch owned the rows of tile J
-  const int c0 = (NI * Is) / C;
+  const int c0 = sym_chunk_of(L, NI * Is);                // the first chunk that holds row sums of this row
   const int nI = owned ? L.nch - c0 : 0;
   const int Ilim = (J + NI - 1) / NI;                    // super-tiles I with NI*I < J
   const int nE = sym_rows_below(Ilim, L.i_first, L.i_step, L.SW);   // owned ones among them
@@ -1709,8 +1881,13 @@ static SymLayout sym_geometry(int64_t n_blobs, int n_cu, int i_first, int i_step
   const int rowsI = ((tunits + i_step - 1) / i_step) * sw;
   // a unit sweeps <= C column tiles.  Measured (tools/tune_sym_chunk.py): short chunks win -- many
   // wave-units balance the triangular work and hide tile-boundary latency; C = 4..16 is flat at
-  // 128 400 blobs (29.8-29.9 ms vs 30.8 at C = 64), C = 2 best at 8 100.  Aim for ~8 rounds of
-  // (4 waves/SIMD x 4 SIMD x CUs) wave-units, capped at 16 tiles.
+  // 128 400 blobs (29.8-29.9 ms vs 30.8 at C = 64), C = 2 best at 8 100.  The rule, from the one-row kernel: ~8 rounds of
+  // (4 waves/SIMD x 4 SIMD x CUs) wave-units, capped at 16 tiles.  For the four-row kernel, which keeps TWO four-wave
+  // workgroups on a compute unit (one wave per SIMD each), not sixteen single waves, the same rule reads: target_units / (2 n_cu)
+  // = 64 draws per resident workgroup over the whole rectangle, half of them dead -- at cfg 3 (2 007 tiles) C = 15, 8 541 live
+  // units of <= 3 840 pair evaluations per lane, 16.7 per slot.  Of the two workgroups of a compute unit the older one gets nearly
+  // every issue slot: its units take 0.66 ms, the other's 3.9 ms (tools/wave_trace.hip), so when the queue ran dry the slots still held
+  // up to a whole long unit each and the compute units stood wholly idle for 3.0 % of the kernel (profiles/sym_unit_schedule.md).
   const double pairs = 0.5 * (double)rowsI * (double)t;
   const double target_units = (double)(n_cu > 0 ? n_cu : 256) * 16.0 * 8.0;
   int c = (int)(pairs / target_units);
@@ -1730,7 +1907,31 @@ static SymLayout sym_geometry(int64_t n_blobs, int n_cu, int i_first, int i_step
   L.Npad = (long)t * TS; L.T = t; L.NI = ni; L.C = c; L.nch = (t + c - 1) / c; L.rowsI = rowsI;
   L.SW = sw;
   L.rowsG = (rowsI + L.SW - 1) / L.SW; L.tri = (i_step == 1) ? 1 : 0; L.nrhs = nrhs; L.i_first = i_first; L.i_step = i_step;
+  L.fine = 1; L.nU = 0;                                  // (no short chunks: their length is never looked at)
+  // One GPU, multi-wave workgroups (the work queue's layouts): live units only, the shortest last, and short chunks over the first
+  // column tiles -- the last the queue hands out (SYM_TAIL_RULE below).  RBL_OPT_SYM_TAIL_CHUNK = C together with
+  // RBL_OPT_SYM_TAIL_SHARE = 1000 ("every tile at the short length C") is the schedule before there were two lengths: the rectangle.
+  // Four rows per lane only: the two-row kernels keep the rectangle (their 642-tile product measured 1 % slower with the live schedule).
+  if (L.tri && sw > 1 && ni == 4 && !(tune.tail_chunk == c && tune.tail_share == 1000)) {
+    int cf = c, share = 0;
+    if (c > RBL_SYM_TAIL_CHUNK) { cf = RBL_SYM_TAIL_CHUNK; share = RBL_SYM_TAIL_SHARE; }
+    if (tune.tail_chunk > 0) cf = tune.tail_chunk;
+    if (tune.tail_share > 0) share = tune.tail_share;
+    if (cf != c && share > 0) {
+      int nf = (int)(((long)t * share / 1000 + cf - 1) / cf);
+      if (nf * cf >= t) nf = (t + cf - 1) / cf;                           // every tile at the short length
+      const int S = nf * cf;
+      L.fine = 32 * nf + cf;
+      L.nch = nf + (S < t ? (t - S + c - 1) / c : 0);
+    }
+    L.nU = sym_class_live(L, sym_class(L, false)) + sym_class_live(L, sym_class(L, true));
+  }
   return L;
+}
+static SymSched sym_sched(const SymLayout &L)
+{
+  const SymClass kc = sym_class(L, false), kf = sym_class(L, true);
+  return SymSched{sym_class_whole(L, kc, sym_class_full(L, kc)), sym_class_live(L, kc), sym_class_whole(L, kf, sym_class_full(L, kf))};
 }
 
 static size_t sym_slabI_blobs(const SymLayout &L) { return (size_t)(sym_offI(L, L.nch - 1) + sym_HI(L, L.nch - 1)); }
@@ -1746,7 +1947,8 @@ size_t rbl_apply_M_sym_bytes(int64_t n_blobs, int n_cu, int i_step, int nrhs, co
   if (C_out) *C_out = L.C;
   // slabs + tile bounding boxes + far map (one byte per (row super-tile, tile))
   return ((sym_slabI_blobs(L) + sym_slabJ_blobs(L)) * 3 * nrhs + (size_t)L.T * 6) * sizeof(double) +
-         (size_t)((L.T + L.NI - 1) / L.NI) * (size_t)L.T + 64 + 128;      // (+ the work-queue counter, 64-byte aligned, behind the far map)
+         (size_t)((L.T + L.NI - 1) / L.NI) * (size_t)L.T + 64 + 128 +      // (+ the work-queue counter, 64-byte aligned, behind the far map,
+         (L.NI == 4 ? (size_t)sym_queue_units(L) * 8 : 0);                   //    and the queue's unit table behind it)
 }
 
 template <bool WALL, int NI, int SW>
@@ -1768,12 +1970,14 @@ static void launch_sym(hipStream_t st, const RblParams &P, const double *d_F, co
     if (use_queue && SW > 1) {
       queue = (unsigned *)(((uintptr_t)(farmap + (size_t)nsup * (size_t)T) + 63) & ~(uintptr_t)63);
       // more workgroups than can be resident do no harm (late ones find the queue empty); fewer would leave CUs idle
-      const unsigned want = (unsigned)(n_cu > 0 ? n_cu : 256) * 4u, have = (unsigned)L.rowsG * (unsigned)L.nch;
+      const unsigned want = (unsigned)(n_cu > 0 ? n_cu : 256) * 4u, have = sym_queue_units(L);
       grid = dim3(want < have ? want : have, 1);
     }
     hipLaunchKernelGGL(k_tile_bbox, dim3((unsigned)T), dim3(TS), 0, st, d_r, (long)n_blobs, P.inv_a, bbox);
     hipLaunchKernelGGL(k_tile_far, dim3((unsigned)((T + 255) / 256), (unsigned)nsup), dim3(256), 0, st,
                        (const double *)bbox, T, NI, farmap, queue, gap_ratio);
+    if (queue && NI == 4)
+      hipLaunchKernelGGL(k_sym_unit_table, dim3((sym_queue_units(L) + 255) / 256), dim3(256), 0, st, L, L.nU ? sym_sched(L) : SymSched{0, 0, 0}, queue);
   }
   auto launch = [&](auto prec, auto nv) {
     hipLaunchKernelGGL((k_apply_M_sym<WALL, NI, SW, decltype(prec)::value, decltype(nv)::value>), grid, block, 0, st, d_r, d_F, slabI, slabJ,
@@ -1879,6 +2083,65 @@ bool sym_forced_ok(const SymLayout &L, int nrhs, const RblSymTune &tune)
 }
 
 }  // namespace
+
+// Every work unit of the product rbl_launch_apply_M_sym would launch, in the order the units are handed out (work queue: draw order;
+// otherwise launch order), dead units of a rectangle left out.  Nine numbers a unit: its index in that order, row group (wave-unit
+// kernels: row super-tile), chunk, first column tile, tiles, and the ranges it writes in the workspace, in doubles from its start,
+// for the first vector: row sums (offset, length), column sums (offset, length).  No device needed.
+// Returns the number of units (out holds the first cap of them), -1 when the options force a shape no kernel has.
+// info: {rows per lane, waves per workgroup, C, C_f, short chunks, chunks, 1 = work queue, 1 = live units only}.
+long rbl_apply_M_sym_units(int64_t n_blobs, int n_cu, int i_step, int nrhs, const RblSymTune &tune, int64_t *out, long cap, int *info)
+{
+  const SymLayout L = sym_geometry(n_blobs, n_cu, 0, i_step, nrhs, tune);
+  const SymRow *row = sym_forced_ok(L, nrhs, tune) ? sym_pick(L, nrhs, tune.relaxed != 0, tune) : nullptr;
+  if (!row) return -1;
+  const bool queue = !row->wave_units && tune.queue >= 0 && L.SW > 1 && L.NI >= 2;
+  if (info) { info[0] = L.NI; info[1] = L.SW; info[2] = L.C; info[3] = sym_nf(L) ? sym_Cf(L) : L.C; info[4] = sym_nf(L); info[5] = L.nch; info[6] = queue; info[7] = queue && L.nU; }
+  const int SWu = row->wave_units ? 1 : L.SW;
+  const size_t baseJ = sym_slabI_blobs(L) * 3 * (size_t)nrhs;
+  long n_idx, n = 0;
+  if (row->wave_units) n_idx = L.tri ? symw_prefix_ni(L.rowsI, L.C, L.nch, L.NI) : (long)L.rowsI * L.nch;
+  else n_idx = (queue && L.nU) ? (long)L.nU : (long)L.rowsG * L.nch;
+  const SymSched S = sym_sched(L);
+  for (long u = 0; u < n_idx; ++u) {
+    int g, c;
+    if (row->wave_units) {
+      if (L.tri) {
+        const int pni = L.NI;
+        int lo = 0, hi = L.rowsI;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (symw_prefix_ni(mid, L.C, L.nch, pni) <= u) lo = mid; else hi = mid; }
+        g = lo; c = (L.NI * g) / L.C + (int)(u - symw_prefix_ni(g, L.C, L.nch, pni));
+      } else { c = (int)(u / L.rowsI); g = (int)((u - (long)c * L.rowsI + c) % L.rowsI); }
+    } else if (queue && L.nU) sym_unit_of_index(L, S, (unsigned)u, g, c);
+    else {
+      const int by = (int)(u / L.rowsG), bx = (int)(u - (long)by * L.rowsG);
+      c = queue ? L.nch - 1 - by : by; g = (bx + by) % L.rowsG;
+    }
+    const int It00 = L.NI * sym_row_of(SWu * g, L.i_first, L.i_step, SWu);
+    int J0, J1;
+    if (!sym_unit_columns(L, c, It00, J0, J1)) continue;
+    if (n < cap) {
+      int64_t *o = out + 9 * n;
+      o[0] = u; o[1] = g; o[2] = c; o[3] = J0; o[4] = J1 - J0;
+      // row sums: the waves whose first row tile lies before the chunk's end store their NI row tiles (those below T)
+      const int cend = sym_chunk_first(L, c) + sym_chunk_len(L, c);
+      long lenI = 0; size_t offI = 0; bool first = true;
+      for (int w = 0; w < SWu; ++w) {
+        const int e = SWu * g + w;
+        if (e >= L.rowsI) break;
+        const int It0 = L.NI * sym_row_of(e, L.i_first, L.i_step, SWu);
+        if (It0 >= L.T || cend <= It0) continue;
+        if (first) { offI = sym_idxI(L, c, 0, (long)It0 * TS); first = false; }
+        lenI += 3L * TS * (std::min(It0 + L.NI, L.T) - It0);
+      }
+      o[5] = (int64_t)offI; o[6] = lenI;
+      const int Jw = std::max(J0, It00 + 1);          // column sums exist for the tiles behind the group's first row tile
+      o[7] = Jw < J1 ? (int64_t)(baseJ + sym_idxJ(L, g, 0, (long)Jw * TS)) : (int64_t)baseJ; o[8] = Jw < J1 ? 3L * TS * (J1 - Jw) : 0;
+    }
+    ++n;
+  }
+  return n;
+}
 
 // nrhs = 1 or 2 force vectors (d_F, d_out: [nrhs][3 n_blobs]); d_work from rbl_apply_M_sym_bytes(...).
 // RBL_ERR_ARG (nothing launched): the options force a shape no instantiation has.

@@ -375,6 +375,18 @@ int rbl_apply_M_sym_info(rbl_ctx *c, int64_t n_blobs, int i_step, int nrhs, int 
   return RBL_OK;
 }
 
+int rbl_apply_M_sym_units(rbl_ctx *c, int64_t n_blobs, int n_cu, int i_step, int nrhs, int64_t *units, int64_t capacity, int64_t *n_units,
+                          int *info, int64_t *workspace_bytes)
+{
+  if (!c || n_blobs <= 0 || n_cu < 1 || i_step < 1 || nrhs < 1 || nrhs > 2 || capacity < 0 || (capacity > 0 && !units) || !n_units)
+    return rbl_fail(c, RBL_ERR_ARG, "apply_M_sym_units: bad arguments");
+  const long n = rbl_apply_M_sym_units(n_blobs, n_cu, i_step, nrhs, c->sym_tune, units, (long)capacity, info);
+  if (n < 0) return rbl_fail(c, RBL_ERR_ARG, SYM_SHAPE_MSG);
+  *n_units = n;
+  if (workspace_bytes) *workspace_bytes = (int64_t)rbl_apply_M_sym_bytes(n_blobs, n_cu, i_step, nrhs, c->sym_tune);
+  return RBL_OK;
+}
+
 int rbl_apply_M_sym_kernel(rbl_ctx *c, int64_t n_blobs, int i_step, int nrhs, int wall, char *name, int name_len)
 {
   if (!c || n_blobs <= 0 || i_step < 1 || nrhs < 1 || nrhs > 2 || !name || name_len < 40)

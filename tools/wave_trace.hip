@@ -2,7 +2,12 @@
 // workgroup's wave started and ended (100 MHz constant clock) and on which XCD / SE / CU / SIMD it ran.  Compiles the
 // product's own kernel source with -DRBL_WAVE_TRACE (the hooks are empty in the library build).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -w -DRBL_WAVE_TRACE -Irigid_body_light_amd/csrc tools/wave_trace.hip -o tools/wave_trace
-//   tools/wave_trace [n_blobs [wall [rows_per_lane [chunk [waves_per_workgroup [queue: -1 off]]]]]] > gpurun_out/wave_trace.csv       (summary on stderr)
+//   tools/wave_trace [n_blobs [wall [rows_per_lane [chunk [waves_per_workgroup [queue: -1 off [lattice [tail_chunk [tail_share]]]]]]]]] > wave_trace.csv       (summary on stderr)
+// lattice = 1: blobs on a cubic lattice 2.5 radii apart, x fastest, so a 64-blob tile is compact and nearly every tile pair is
+// "far" as in cfg 3 (uniformly random blobs make every tile span the box and every sweep carry the overlap test).
+// With the work queue a workgroup is a resident SLOT that draws units until the queue is dry: the summary then gives when the
+// last unit was drawn, when each slot ended and the idle share of the tail, sum over slots of (kernel end - slot end) / (slots x kernel time)
+// (profiles/sym_unit_schedule.md).
 #include <hip/hip_runtime.h>
 __device__ unsigned long long *g_wave_trace = nullptr;
 #include "rbl_kernels.hip"
@@ -19,6 +24,12 @@ int main(int argc, char **argv)
   std::uniform_real_distribution<double> U(0.0, 1.0);
   const double a = 0.12, box = 14.0;                       // cfg 2's blob radius, ~its extent
   std::vector<double> r(3 * N), F(3 * N);
+  const bool lattice = argc > 7 && atoi(argv[7]) != 0;
+  if (lattice) {
+    long m = 1; while (m * m * m < N) ++m;
+    const double h = 2.5 * a;
+    for (long i = 0; i < N; ++i) { r[3 * i] = h * (i % m); r[3 * i + 1] = h * ((i / m) % m); r[3 * i + 2] = 1.0 + h * (i / (m * m)); }
+  } else
   for (long i = 0; i < N; ++i) { r[3 * i] = box * U(gen); r[3 * i + 1] = box * U(gen); r[3 * i + 2] = 1.0 + box * U(gen); }
   for (auto &f : F) f = U(gen) - 0.5;
   hipStream_t st; hipStreamCreate(&st);
@@ -29,6 +40,8 @@ int main(int argc, char **argv)
   if (argc > 4) tune.chunk = atoi(argv[4]);
   if (argc > 5) tune.sw = atoi(argv[5]);
   if (argc > 6) tune.queue = atoi(argv[6]);
+  if (argc > 8) tune.tail_chunk = atoi(argv[8]);
+  if (argc > 9) tune.tail_share = atoi(argv[9]);
   const size_t wb = rbl_apply_M_sym_bytes(N, ncu, 1, 1, tune);
   double *dr, *dF, *dU, *dW; unsigned *derr;
   hipMalloc((void **)&dr, 24 * N); hipMalloc((void **)&dF, 24 * N); hipMalloc((void **)&dU, 24 * N); hipMalloc((void **)&dW, wb);
@@ -70,12 +83,14 @@ int main(int argc, char **argv)
   fprintf(stderr, "traced launch: %zu workgroups with rows, first start -> last end %.1f us, mean wave life %.1f us, SIMDs used %zu\n", live,
           span / 1e3, life / live / 1e3, per_simd.size());
   // start-time histogram (5 us bins), units per SIMD, mean concurrency
+  if (span < 500e3) {                                        // (a cfg 3 launch lasts 20 ms: 4 000 bins say nothing)
   std::vector<int> hist((size_t)(span / 5000.0) + 1, 0), endh(hist.size(), 0);
   for (size_t w = 0; w < nwg; ++w) if (h[4 * w]) { ++hist[(size_t)((h[4 * w] - t0) * 10.0 / 5000.0)]; ++endh[(size_t)((h[4 * w + 1] - t0) * 10.0 / 5000.0)]; }
   fprintf(stderr, "starts per 5 us:");
   for (int v : hist) fprintf(stderr, " %d", v);
   fprintf(stderr, "\nends   per 5 us:");
   for (int v : endh) fprintf(stderr, " %d", v);
+  }
   std::map<size_t, int> cnt;
   double last_min = 1e30, last_max = 0;
   for (auto &kv : per_simd) {
@@ -86,5 +101,37 @@ int main(int argc, char **argv)
   fprintf(stderr, "\nunits per SIMD (count of SIMDs):");
   for (auto &kv : cnt) fprintf(stderr, " %zu:%d", kv.first, kv.second);
   fprintf(stderr, "\nlast end per SIMD: earliest %.1f us, latest %.1f us\n", last_min / 1e3, last_max / 1e3);
+  // resident slots (a slot = the hardware wave slot the workgroup's first wave sits in): tail of the work queue
+  std::map<unsigned, std::pair<double, int>> slot;          // last end, units
+  double dry = 0.0, longest = 0.0;
+  for (size_t w = 0; w < nwg; ++w) {
+    if (!h[4 * w]) continue;
+    const unsigned hw = (unsigned)h[4 * w + 2], xcc = (unsigned)h[4 * w + 3] & 15u;
+    const unsigned key = (xcc << 20) | (((hw >> 13) & 7u) << 16) | (((hw >> 8) & 15u) << 8) | (((hw >> 4) & 3u) << 4) | (hw & 15u);
+    const double s = (h[4 * w] - t0) * 10.0, e = (h[4 * w + 1] - t0) * 10.0;
+    auto &sl = slot[key];
+    sl.first = std::max(sl.first, e); ++sl.second;
+    dry = std::max(dry, s); longest = std::max(longest, e - s);
+  }
+  double idle = 0.0, first_end = 1e30;
+  for (auto &kv : slot) { idle += span - kv.second.first; first_end = std::min(first_end, kv.second.first); }
+  fprintf(stderr, "slots %zu, units per slot %.2f, longest unit %.1f us, last unit drawn at %.1f us, first slot ended at %.1f us, kernel end %.1f us\n",
+          slot.size(), (double)live / slot.size(), longest / 1e3, dry / 1e3, first_end / 1e3, span / 1e3);
+  fprintf(stderr, "tail idle share = sum(kernel end - slot end) / (slots x kernel time) = %.4f\n", idle / (slot.size() * span));
+  std::map<unsigned, std::pair<double, double>> cus;        // compute unit -> (first, last) end of its slots
+  for (auto &kv : slot) {
+    auto it = cus.find(kv.first >> 8);
+    if (it == cus.end()) cus[kv.first >> 8] = {kv.second.first, kv.second.first};
+    else { it->second.first = std::min(it->second.first, kv.second.first); it->second.second = std::max(it->second.second, kv.second.first); }
+  }
+  double cu_idle = 0.0, cu_half = 0.0;
+  for (auto &kv : cus) { cu_idle += span - kv.second.second; cu_half += kv.second.second - kv.second.first; }
+  fprintf(stderr, "compute units %zu: wholly idle share %.4f, share with one of their slots ended %.4f\n", cus.size(), cu_idle / (cus.size() * span),
+          cu_half / (cus.size() * span));
+  std::vector<int> sh(21, 0);
+  for (auto &kv : slot) ++sh[std::min((size_t)20, (size_t)((span - kv.second.first) / 50000.0))];
+  fprintf(stderr, "slots by (kernel end - slot end), 50 us bins:");
+  for (int v : sh) fprintf(stderr, " %d", v);
+  fprintf(stderr, "\n");
   return 0;
 }
