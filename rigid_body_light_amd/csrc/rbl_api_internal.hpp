@@ -17,6 +17,32 @@
 
 #pragma GCC visibility push(hidden)
 
+// ---- requests -----------------------------------------------------------------------------------------------------
+// What a solver asks of one product, preconditioner application or saddle product beyond the plain operator, and what that call
+// did about it, travel in these structs: a default-constructed one is the plain operator, and no call leaves anything behind in
+// rbl_ctx for the next one.  Fields marked "answer" are written by the callee.
+struct RblProductReq {                   // apply_M_enqueue, apply_M_multi_enqueue
+  bool relaxed = false;                  // far tile pairs in packed single precision (inexact Krylov iterations only)
+  bool undamped = false;                 // skip the damping B in this product even while RBL_OPT_NO_DAMP is off (preconditioned root)
+  const RblSaddleFuse *fuse = nullptr;   // the slab reduction of a symmetric product also writes the saddle epilogue
+  bool fused = false;                    // answer: it did (ordered kernel, sharded product: it did not)
+};
+constexpr double RBL_PC_FSIGN_REFERENCE = -1.0;   // apply_PC as the reference defines it (see rbl_ctx::gmres_pc_sign_fix)
+struct RblPcReq {                        // apply_PC_dev
+  double fsign = RBL_PC_FSIGN_REFERENCE; // sign of the force block
+  const RblNormFold *fold = nullptr;     // d_in is an un-normalised Arnoldi vector (refused unless pc_can_fold)
+  bool leave_ktl = false;                // also leave K^T Lambda of the output ...
+  const double *ktl = nullptr;           // answer: ... here; NULL: this form does not produce it (diagonal, sharded context)
+};
+struct RblSaddleReq {                    // apply_saddle_dev
+  const double *ktl = nullptr;           // K^T Lambda of d_x as the preconditioner left it (RblPcReq::ktl), or NULL
+  bool relaxed = false;                  // see RblProductReq
+  const double *dotV = nullptr;          // first Gram-Schmidt pass of the Arnoldi step that follows: the basis, ...
+  int dotK = 0;                          // ... its vectors so far ...
+  double *dotPart = nullptr;             // ... and where their partial sums go (see RblSaddleFuse)
+  int dots_np = 0;                       // answer: partial sums per vector (0: not done)
+};
+
 // ---- rbl_core.hip -------------------------------------------------------------------------------------------------
 int need_params(rbl_ctx *c);
 int need_config(rbl_ctx *c);
@@ -27,7 +53,7 @@ int copy_h2d(rbl_ctx *c, void *dst, const void *src, size_t bytes);   // synchro
 int copy_d2h(rbl_ctx *c, void *dst, const void *src, size_t bytes);
 int read_back(rbl_ctx *c, void *dst, const void *d_src, size_t bytes);   // small device -> host read the host needs NOW
 int finish_and_check(rbl_ctx *c);             // drain the stream, read + clear the latched device flags
-RblParams ctx_params(const rbl_ctx *c);
+RblParams ctx_params(const rbl_ctx *c, bool force_no_damp);   // undamped when RBL_OPT_NO_DAMP or the caller asks
 
 // ---- rbl_comm.hip -------------------------------------------------------------------------------------------------
 bool comm_on(const rbl_ctx *c);
@@ -48,10 +74,9 @@ void comm_release(rbl_ctx *c);                // destroy a native communicator (
 
 // ---- rbl_products.hip ---------------------------------------------------------------------------------------------
 int apply_M_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double *d_r, int64_t nbl, int64_t row_begin, int64_t row_end,
-                    double *d_out);
+                    double *d_out, RblProductReq *rq = nullptr);
 int apply_M_multi_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double *d_r, int64_t nbl, int nrhs, double *d_out,
-                          int64_t ldF = 0, int64_t ldO = 0);
-int apply_PC_multi_dev(rbl_ctx *c, const double *d_in, double *d_out, double *d_scratch, int nv, int64_t pitch);
+                          int64_t ldF = 0, int64_t ldO = 0, RblProductReq *rq = nullptr);
 int ensure_xq_dev(rbl_ctx *c);
 int positions_dev(rbl_ctx *c, int b0, int b1, double *d_out);
 
@@ -64,6 +89,10 @@ int blk_prepare(rbl_ctx *c, int b0, int b1);
 int blk_solve(rbl_ctx *c, int b0, int nbo, const double *in, double *out, int nv, int64_t pitch, int mode, bool allow_f32 = true);
 int blk_trmv(rbl_ctx *c, int b0, int nbo, const double *in, double *out);
 bool pc_can_fold(rbl_ctx *c);
+// the workers behind rbl_apply_PC_dev / rbl_apply_saddle_dev (which pass default requests)
+int apply_PC_dev(rbl_ctx *c, const double *d_in, double *d_out, RblPcReq &rq);
+int apply_PC_multi_dev(rbl_ctx *c, const double *d_in, double *d_out, double *d_scratch, int nv, int64_t pitch, double fsign);
+int apply_saddle_dev(rbl_ctx *c, const double *d_x, double *d_out, RblSaddleReq &rq);
 int blk_trmv_multi(rbl_ctx *c, int b0, int nbo, const double *in, double *out, int nv, int64_t pitch);
 
 // ---- rbl_roots.hip ------------------------------------------------------------------------------------------------
@@ -73,9 +102,10 @@ int mhalf_dev_multi(rbl_ctx *c, const double *d_r, int64_t nbl, const double *d_
 
 // ---- rbl_solvers.hip ----------------------------------------------------------------------------------------------
 // the library's GMRES (Arnoldi kernels, host Givens solve, overlapped convergence test) on a system of the saddle system's size whose
-// operator and right preconditioner the caller supplies (rbl_mixed.hip).  Every shortcut fused into the ordinary saddle solve
-// (K^T lambda by-product, Gram-Schmidt sums in the product, normalisation folded into the preconditioner, the one-kernel solver,
-// relaxed products, the iteration-count memory) stays off.
+// operator and right preconditioner the caller supplies (rbl_mixed.hip).  The shortcuts fused into the ordinary saddle solve
+// (K^T lambda by-product, Gram-Schmidt sums in the product, normalisation folded into the preconditioner, relaxed products) are
+// requests to the library's own operators (RblPcReq, RblSaddleReq): such a solve makes none; the one-kernel solver and the
+// iteration-count memory stay off too.
 struct RblSolveOps {
   int (*op)(rbl_ctx *c, void *user, const double *d_x, double *d_out);
   int (*pc)(rbl_ctx *c, void *user, const double *d_in, double *d_out);

@@ -568,8 +568,7 @@ static int pc_block_build(rbl_ctx *c)
   if ((rc = rbl_dev_reserve(c, c->d_pcMK, sizeof(double) * 6 * (size_t)n3))) return rc;
   // Ninv_b = K_b^T invM_b K_b, column by column (bodies do not couple), then its 6x6 Cholesky; the six
   // solved columns invM_b K_b are kept (d_pcMK): every application needs invM K U
-  double *w1 = (double *)c->d_pcw.p, *cols = w1 + 2 * n3, *Uunit = cols + 36 * (size_t)S.N_bod;
-  (void)w1;
+  double *cols = (double *)c->d_pcw.p + 2 * n3, *Uunit = cols + 36 * (size_t)S.N_bod;
   double *MK = (double *)c->d_pcMK.p;
   for (int cc = 0; cc < 6; ++cc) {                       // the six columns of K ...
     rbl_launch_unit_U(c->stream, S.N_bod, cc, Uunit);
@@ -586,67 +585,54 @@ static int pc_block_build(rbl_ctx *c)
   return RBL_OK;
 }
 
-static int pc_block_apply_local(rbl_ctx *c, const double *d_in, double *d_out, bool shard)
+static int pc_block_apply_local(rbl_ctx *c, const double *d_in, double *d_out, bool shard, RblPcReq &rq)
 {
   RblPhase ph(c, RBL_T_PERBODY);
   const RblBodyState &S = c->S;
   const int64_t m = 3 * (int64_t)S.N_blb, N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N;
-  double *w1 = (double *)c->d_pcw.p, *w2 = w1 + n3, *f6 = w2 + n3 + 36 * (size_t)S.N_bod + 6 * (size_t)S.N_bod;
+  double *w1 = (double *)c->d_pcw.p;
   const double *lev = (const double *)c->d_lever.p;
   int b0 = 0, b1 = S.N_bod;
   if (shard) comm_body_range(c, &b0, &b1);
   const int nbo = b1 - b0;
-  const size_t off = (size_t)b0 * (size_t)m;
   int rc;
   if (shard && comm_gather_needs_zero(c)) RBL_HIP(c, hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)(n3 + 6 * S.N_bod), c->stream));
-  c->ktl_of = nullptr;
-  if (bf_on(c) && c->bf_tables) {                        // the whole application in the body frame, one launch
-    if ((rc = ensure_xq_dev(c))) return rc;
-    if (nbo > 0) {
-      double *ktl = nullptr;
-      if (c->ktl_arm && !shard) {
-        if ((rc = rbl_dev_reserve(c, c->d_ktl, sizeof(double) * 6 * (size_t)S.N_bod))) return rc;
-        ktl = (double *)c->d_ktl.p;
-      }
-      const double *T = (const double *)c->d_bfPC.p;
-      if ((rc = rbl_dev_reserve(c, c->d_blkTmp, sizeof(double) * 3 * (size_t)n3))) return rc;
-      if ((rc = rbl_launch_pc_bodyframe(c->stream, T, T + (size_t)(m * m), T + (size_t)(m * m) + 6 * (size_t)m, (const double *)c->d_cfg.p,
-                                        (const double *)c->d_XQ.p + 3 * (size_t)S.N_bod, m, b0, nbo, d_in, n3, c->pc_fsign, d_out, ktl,
-                                        (double *)c->d_blkTmp.p, c->shared_gemm ? 1 : 0, c->pc_fold.part ? &c->pc_fold : nullptr)))
-        return rbl_fail(c, rc, "body-frame preconditioner launch failed");
-      c->pc_fold = RblNormFold();
-      if (ktl) c->ktl_of = d_out;
-    }
-    return RBL_OK;
+  const bool bodyframe = bf_on(c) && c->bf_tables;
+  if (bodyframe && (rc = ensure_xq_dev(c))) return rc;
+  if (nbo <= 0) return RBL_OK;
+  double *ktl = nullptr;                                 // K^T Lambda on the side, for the saddle product that follows (a shard's is partial)
+  if (rq.leave_ktl && !shard) {
+    if ((rc = rbl_dev_reserve(c, c->d_ktl, sizeof(double) * 6 * (size_t)S.N_bod))) return rc;
+    ktl = (double *)c->d_ktl.p;
   }
-  if (nbo > 0) {
+  if (bodyframe) {                                       // the whole application in the body frame, one launch
+    const double *T = (const double *)c->d_bfPC.p;
+    if ((rc = rbl_dev_reserve(c, c->d_blkTmp, sizeof(double) * 3 * (size_t)n3))) return rc;
+    if ((rc = rbl_launch_pc_bodyframe(c->stream, T, T + (size_t)(m * m), T + (size_t)(m * m) + 6 * (size_t)m, (const double *)c->d_cfg.p,
+                                      (const double *)c->d_XQ.p + 3 * (size_t)S.N_bod, m, b0, nbo, d_in, n3, rq.fsign, d_out, ktl,
+                                      (double *)c->d_blkTmp.p, c->shared_gemm ? 1 : 0, rq.fold)))
+      return rbl_fail(c, rc, "body-frame preconditioner launch failed");
+  } else {
     if ((rc = blk_solve(c, b0, nbo, d_in, w1, 1, 0, 0))) return rc;                                      // invM slip
     // K^T (invM slip);  U (:601-608);  Lambda = invM (slip + K U) (:610) = invM slip + (invM K) U: no second pass over
-    // the factors -- one launch (k_pc_block_tail); inside GMRES it also leaves K^T Lambda for the saddle product
-    double *ktl = nullptr;
-    if (c->ktl_arm && !shard) {
-      if ((rc = rbl_dev_reserve(c, c->d_ktl, sizeof(double) * 6 * (size_t)S.N_bod))) return rc;
-      ktl = (double *)c->d_ktl.p;
-    }
+    // the factors -- one launch (k_pc_block_tail)
     rbl_launch_pc_block_tail(c->stream, lev, w1, (const double *)c->d_pcMK.p, n3, (const double *)c->d_NL.p, d_in + n3, S.N_blb,
-                             b0, nbo, c->pc_fsign, d_out + n3, d_out, ktl, c->pc_fold.part ? &c->pc_fold : nullptr, d_in);
-    c->pc_fold = RblNormFold();
-    if (ktl) c->ktl_of = d_out;
+                             b0, nbo, rq.fsign, d_out + n3, d_out, ktl, rq.fold, d_in);
   }
-  (void)f6; (void)off;
+  rq.ktl = ktl;
   return RBL_OK;
 }
 
-static int pc_block_apply(rbl_ctx *c, const double *d_in, double *d_out)
+static int pc_block_apply(rbl_ctx *c, const double *d_in, double *d_out, RblPcReq &rq)
 {
   const bool shard = comm_on(c);                         // own bodies only, completed by ONE all-gather of the owners' [lambda | U] segments
-  int rc = pc_block_apply_local(c, d_in, d_out, shard);
+  int rc = pc_block_apply_local(c, d_in, d_out, shard, rq);
   if (rc || !shard) return rc;
   const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb;
   return comm_allgather_bodies2(c, d_out, 0, 3 * (int64_t)c->S.N_blb, d_out, n3, 6);
 }
 
-// may the next rbl_apply_PC_dev be handed an un-normalised Arnoldi vector (rbl_ctx::pc_fold)?  On one GPU, once the preconditioner
+// may apply_PC_dev be handed an un-normalised Arnoldi vector (RblPcReq::fold)?  On one GPU, once the preconditioner
 // has been built (its first application builds it): the diagonal one, the per-body factors' tail kernel, and the free-space
 // body-frame tables in their matrix-vector form
 bool pc_can_fold(rbl_ctx *c)
@@ -657,22 +643,18 @@ bool pc_can_fold(rbl_ctx *c)
   return true;
 }
 
-int rbl_apply_PC_dev(rbl_ctx *c, const double *d_in, double *d_out)
+int apply_PC_dev(rbl_ctx *c, const double *d_in, double *d_out, RblPcReq &rq)
 {
-  struct FoldGuard {                                     // whatever happens, the request to fold a normalisation dies with this call
-    rbl_ctx *c;
-    explicit FoldGuard(rbl_ctx *c_) : c(c_) {}
-    ~FoldGuard() { c->pc_fold = RblNormFold(); }
-  } guard(c);
   int rc = sync_bodies(c); if (rc) return rc;
   const RblBodyState &S = c->S;
-  if (c->pc_fold.part && !pc_can_fold(c)) { c->pc_fold = RblNormFold(); return rbl_fail(c, RBL_ERR_ARG, "apply_PC: this preconditioner does not normalise its input"); }
+  rq.ktl = nullptr;
+  if (rq.fold && rq.fold->part && !pc_can_fold(c)) return rbl_fail(c, RBL_ERR_ARG, "apply_PC: this preconditioner does not normalise its input");
   if (S.block_pc) {
     if (!c->dev_pc_valid) {
       if ((rc = pc_block_build(c))) return rc;
       c->dev_pc_valid = true;
     }
-    return pc_block_apply(c, d_in, d_out);
+    return pc_block_apply(c, d_in, d_out, rq);
   }
   if (!c->dev_pc_valid) {
     const size_t N = (size_t)S.N_bod * S.N_blb;
@@ -684,16 +666,21 @@ int rbl_apply_PC_dev(rbl_ctx *c, const double *d_in, double *d_out)
     c->dev_pc_valid = true;
   }
   rbl_launch_pc_diag_apply(c->stream, (const double *)c->d_lever.p, (const double *)c->d_invM2.p, (const double *)c->d_NL.p,
-                           S.N_blb, S.N_bod, d_in, d_out, c->pc_fsign, c->pc_fold.part ? &c->pc_fold : nullptr);
-  c->pc_fold = RblNormFold();
+                           S.N_blb, S.N_bod, d_in, d_out, rq.fsign, rq.fold);
   return RBL_OK;
+}
+
+int rbl_apply_PC_dev(rbl_ctx *c, const double *d_in, double *d_out)
+{
+  RblPcReq plain;
+  return apply_PC_dev(c, d_in, d_out, plain);
 }
 
 // out_v = P^-1 in_v for nv saddle vectors `pitch` doubles apart (in, out and the scratch vectors all laid out alike).  The block
 // preconditioner of per-configuration factors on one GPU sends all vectors through the factors together -- three share one pass
 // over the 5.9 GB of cfg 3 (rbl_launch_block_solve_multi), so 16 vectors cost six passes, not sixteen; every other
 // preconditioner (diagonal, body frame, sharded) is applied vector by vector.  d_scratch: nv vectors of >= n3 doubles.
-int apply_PC_multi_dev(rbl_ctx *c, const double *d_in, double *d_out, double *d_scratch, int nv, int64_t pitch)
+int apply_PC_multi_dev(rbl_ctx *c, const double *d_in, double *d_out, double *d_scratch, int nv, int64_t pitch, double fsign)
 {
   int rc = sync_bodies(c); if (rc) return rc;
   const RblBodyState &S = c->S;
@@ -703,19 +690,20 @@ int apply_PC_multi_dev(rbl_ctx *c, const double *d_in, double *d_out, double *d_
   }
   const bool together = S.block_pc && !comm_on(c) && !(bf_on(c) && c->bf_tables) && nv > 1 && d_scratch;
   if (!together) {
+    RblPcReq rq;
+    rq.fsign = fsign;
     for (int v = 0; v < nv; ++v)
-      if ((rc = rbl_apply_PC_dev(c, d_in + (size_t)v * (size_t)pitch, d_out + (size_t)v * (size_t)pitch))) return rc;
+      if ((rc = apply_PC_dev(c, d_in + (size_t)v * (size_t)pitch, d_out + (size_t)v * (size_t)pitch, rq))) return rc;
     return RBL_OK;
   }
   RblPhase ph(c, RBL_T_PERBODY);
   const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N;
-  c->ktl_of = nullptr;
   if ((rc = blk_solve(c, 0, S.N_bod, d_in, d_scratch, nv, pitch, 0))) return rc;                              // invM slip, all vectors
   for (int v = 0; v < nv; ++v) {
     const double *in = d_in + (size_t)v * (size_t)pitch;
     double *out = d_out + (size_t)v * (size_t)pitch;
     rbl_launch_pc_block_tail(c->stream, (const double *)c->d_lever.p, d_scratch + (size_t)v * (size_t)pitch, (const double *)c->d_pcMK.p, n3,
-                             (const double *)c->d_NL.p, in + n3, S.N_blb, 0, S.N_bod, c->pc_fsign, out + n3, out, nullptr, nullptr, in);
+                             (const double *)c->d_NL.p, in + n3, S.N_blb, 0, S.N_bod, fsign, out + n3, out, nullptr, nullptr, in);
   }
   return RBL_OK;
 }
@@ -740,39 +728,42 @@ int rbl_prepare_dev(rbl_ctx *c)
 }
 
 // [M lambda - K U ; K^T lambda] on the object's own configuration (src/Rigid.py:73-80)
-int rbl_apply_saddle_dev(rbl_ctx *c, const double *d_x, double *d_out)
+int apply_saddle_dev(rbl_ctx *c, const double *d_x, double *d_out, RblSaddleReq &rq)
 {
   int rc = sync_bodies(c); if (rc) return rc;
   const RblBodyState &S = c->S;
   const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N;
   if ((rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3))) return rc;
-  const bool have_ktl = c->ktl_arm && c->ktl_of == d_x;   // GMRES: d_x came out of the block preconditioner together with its K^T Lambda
-  c->fuse_done = false;
-  if (have_ktl && c->fused_krylov && !comm_on(c)) {
+  rq.dots_np = 0;
+  RblProductReq prod;
+  prod.relaxed = rq.relaxed;
+  RblSaddleFuse f;
+  if (rq.ktl && c->fused_krylov && !comm_on(c)) {        // (GMRES: d_x came out of the block preconditioner together with its K^T Lambda)
     // one launch fewer per iteration: the slab reduction of the product writes  out = [M lambda - K U ; K^T lambda]  itself
-    RblSaddleFuse f;
-    f.lever = (const double *)c->d_lever.p; f.U = d_x + n3; f.ktl = (const double *)c->d_ktl.p; f.w = d_out;
+    f.lever = (const double *)c->d_lever.p; f.U = d_x + n3; f.ktl = rq.ktl; f.w = d_out;
     f.N_blb = S.N_blb; f.nb6 = 6 * S.N_bod;
     const int64_t np = (n3 + 63) / 64 + 1;              // one partial per block of the reduction + the body rows
-    if (c->fuse_dotK > 0 && c->fuse_dotV && c->fuse_dotPart && np <= rbl_gmres_p1_capacity()) {
-      f.dotV = c->fuse_dotV; f.dotStride = (long)(n3 + 6 * S.N_bod); f.dotK = c->fuse_dotK; f.dotNp = (int)np; f.dotPart = c->fuse_dotPart;
+    if (rq.dotK > 0 && rq.dotV && rq.dotPart && np <= rbl_gmres_p1_capacity()) {
+      f.dotV = rq.dotV; f.dotStride = (long)(n3 + 6 * S.N_bod); f.dotK = rq.dotK; f.dotNp = (int)np; f.dotPart = rq.dotPart;
     }
-    c->sym_tune.fuse = f;
+    prod.fuse = &f;
   }
-  c->fuse_dots_np = 0;
-  const int dots_np = c->sym_tune.fuse.dotK > 0 ? c->sym_tune.fuse.dotNp : 0;
-  rc = apply_M_enqueue(c, S.wall, d_x, (const double *)c->d_pos.p, N, 0, N, (double *)c->d_sad.p);
-  c->sym_tune.fuse = RblSaddleFuse();
-  if (rc) return rc;
-  if (c->fuse_done) { c->fuse_done = false; c->fuse_dots_np = dots_np; return RBL_OK; }
-  if (have_ktl) {
+  if ((rc = apply_M_enqueue(c, S.wall, d_x, (const double *)c->d_pos.p, N, 0, N, (double *)c->d_sad.p, &prod))) return rc;
+  if (prod.fused) { rq.dots_np = f.dotK > 0 ? f.dotNp : 0; return RBL_OK; }
+  if (rq.ktl) {
     rbl_launch_saddle_tail(c->stream, (const double *)c->d_lever.p, d_x + n3, S.N_blb, N, S.N_bod, d_out,
-                           (const double *)c->d_sad.p, (const double *)c->d_ktl.p);
+                           (const double *)c->d_sad.p, rq.ktl);
     return RBL_OK;
   }
   rbl_launch_K_x_U(c->stream, (const double *)c->d_lever.p, d_x + n3, S.N_blb, N, d_out, (const double *)c->d_sad.p, -1.0);
   rbl_launch_KT_x_Lam(c->stream, (const double *)c->d_lever.p, d_x, S.N_blb, S.N_bod, d_out + n3);
   return RBL_OK;
+}
+
+int rbl_apply_saddle_dev(rbl_ctx *c, const double *d_x, double *d_out)
+{
+  RblSaddleReq plain;
+  return apply_saddle_dev(c, d_x, d_out, plain);
 }
 
 // [M lambda - K U ; K^T lambda] for host vectors (src/Rigid.py:73-80): one upload, the device operator, one download

@@ -129,7 +129,7 @@ static const RblBufRow kDevBufs[] = {
     {&rbl_ctx::d_bfLinv, RBL_BUF_PERSIST},        // body-frame factor
     {&rbl_ctx::d_bfX, RBL_BUF_PERSIST},           // body-frame explicit inverse
     {&rbl_ctx::d_bfPC, RBL_BUF_PERSIST},          // body-frame preconditioner tables
-    {&rbl_ctx::d_ktl, RBL_BUF_PERSIST},           // K^T Lambda of the last preconditioner output, read by the next saddle product (ktl_arm)
+    {&rbl_ctx::d_ktl, RBL_BUF_PERSIST},           // K^T Lambda of the last preconditioner output, handed to the saddle product that follows (RblPcReq::ktl)
     {&rbl_ctx::d_bd, RBL_BUF_SCRATCH},            // RHS_and_Midpoint workspace: reserved at its start
     {&rbl_ctx::d_bd2, RBL_BUF_SCRATCH},           // host RHS_and_Midpoint staging, GMRES warm-start vectors: within one call, never nested
     {&rbl_ctx::d_gm, RBL_BUF_SCRATCH},            // GMRES Krylov basis and Hessenberg: reserved at the start of each solve or batch
@@ -351,10 +351,10 @@ int finish_and_check(rbl_ctx *c)
 // Enqueue rows [row_begin,row_end) of U = [B] M [B] F on the context stream, choosing the
 // kernel variant: 1 = symmetric (unordered pairs, needs the full row range), 0 = ordered rows.
 // tune_variant: 0 = heuristic, 1 = force ordered, 2 = force symmetric.
-RblParams ctx_params(const rbl_ctx *c)
+RblParams ctx_params(const rbl_ctx *c, bool force_no_damp)
 {
   RblParams P = rbl_make_params(c->S.a, c->S.eta);
-  P.no_damp = c->no_damp ? 1 : 0;
+  P.no_damp = (c->no_damp || force_no_damp) ? 1 : 0;
   return P;
 }
 

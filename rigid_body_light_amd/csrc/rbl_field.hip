@@ -295,7 +295,7 @@ int vf_enqueue(rbl_ctx *c, const double *d_pts, int64_t n_points, const double *
   if (comm && comm_gather_needs_zero(c)) RBL_HIP(c, hipMemsetAsync(d_u, 0, sizeof(double) * 3 * (size_t)n_points, c->stream));
   {
     RblPhase ph(c, RBL_T_PRODUCT);
-    const RblParams P = ctx_params(c);
+    const RblParams P = ctx_params(c, false);
     if (c->S.wall)
       vf_launch<true>(c->stream, P, g, d_lam, d_r, n_src, d_pts + 3 * p0, p1 - p0, d_u + 3 * p0, c->d_vfw.p, c->d_err);
     else

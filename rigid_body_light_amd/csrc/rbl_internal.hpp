@@ -92,8 +92,9 @@ struct RblSymTune {        // per-context tuning of the symmetric matvec kernels
   int tail_chunk = 0;      // > 0: length of the short chunks the work queue ends on (0 = heuristic; the chunk length itself: no short chunks; RBL_OPT_SYM_TAIL_CHUNK)
   int tail_share = 0;      // > 0: per-mille of the column tiles swept at that length (0 = heuristic; RBL_OPT_SYM_TAIL_SHARE)
   int wave_units = 0;      // < 0: mid-size systems on the round-3 kernel (one workgroup per unit, column sums by LDS atomics); 0: wave-owned units (RBL_OPT_SYM_WAVE_UNITS)
-  RblSaddleFuse fuse;      // transient: see RblSaddleFuse
-  int relaxed = 0;         // transient: far tile pairs in packed single precision (inexact Krylov iterations only)
+  // per launch: filled in from the product's request (RblProductReq, rbl_products.hip: launch_tune); off in rbl_ctx::sym_tune
+  RblSaddleFuse fuse;      // see RblSaddleFuse
+  int relaxed = 0;         // far tile pairs in packed single precision (inexact Krylov iterations only)
 };
 
 struct RblCholAux {        // second stream + events for the one-panel lookahead
@@ -136,8 +137,7 @@ struct rbl_ctx {
   RblDevBuf d_bfPC;                                 // small bodies: M_body^-1 (n^2) | M_body^-1 K_body (6 n) | chol(N_body) (36)
   bool blk_bodyframe = true, bf_valid = false, bf_inv = false;   // RBL_OPT_BODYFRAME_FACTOR
   bool bf_wall_approx = false;                                   // RBL_OPT_BODYFRAME_WALL_APPROX (experiment)
-  RblDevBuf d_ktl;                                  // K^T Lambda of the last block-PC output (GMRES: the saddle product re-uses it)
-  bool ktl_arm = false; const double *ktl_of = nullptr;   // armed by the GMRES loop only; ktl_of = the vector d_ktl belongs to
+  RblDevBuf d_ktl;                                  // K^T Lambda of a block-PC output whose caller asked for it (RblPcReq::leave_ktl)
   bool shared_gemm = true;                          // RBL_OPT_SHARED_GEMM: the ONE body-frame matrix of free space applied to all bodies' vectors as a matrix-matrix product (MFMA)
   bool blk_explicit = true, blk_inv_valid = false;  // RBL_OPT_BLOCK_EXPLICIT_SMALL; d_blkX matches d_blkL for bodies blk_b0 .. blk_b1
   RblDevBuf d_bd, d_bd2;                            // RHS_and_Midpoint workspaces
@@ -161,8 +161,7 @@ struct rbl_ctx {
   RblCholAux chol_aux;
   // apply_PC as the reference defines it (:601-608) answers [M -K; K^T 0] x = [slip; -F]: with the saddle operator of
   // src/Rigid.py:73-80 the preconditioned operator then has its 6 N_bod body eigenvalues at -1 and the rest at +1.  The
-  // library's own GMRES may apply the preconditioner with the force block's sign restored (pc_fsign = +1: one cluster).
-  double pc_fsign = -1.0;
+  // library's own GMRES may apply the preconditioner with the force block's sign restored (RblPcReq::fsign = +1: one cluster).
   bool gmres_pc_sign_fix = true;
   bool gmres_small = true;
   // inexact-Krylov relaxation (off by default): once GMRES's residual estimate is below rtol x 1e5 its products may carry
@@ -179,12 +178,8 @@ struct rbl_ctx {
   void *comm_nccl = nullptr;                        // ncclComm_t of the native communicator
   int comm_split = 0;                               // RBL_OPT_COMM_SPLIT: 0 unordered tile pairs + all-reduce(U), 1 rows by body index + all-gather (north_star)
   std::vector<int64_t> comm_offs, comm_cnts;        // scratch of the all-gather calls
-  bool fuse_done = false; // the last full product honoured sym_tune.fuse (rbl_apply_saddle_dev)
-  RblNormFold pc_fold;              // transient, GMRES -> the next rbl_apply_PC_dev (body-frame tables only; see pc_can_fold)
-  bool gmres_fold_norm = true;      // ... unless switched off with RBL_OPT_FUSED_KRYLOV = 0
-  const double *fuse_dotV = nullptr; double *fuse_dotPart = nullptr;   // GMRES -> rbl_apply_saddle_dev: also leave the partials of V^T w ...
-  int fuse_dotK = 0, fuse_dots_np = 0;                                  // ... for dotK basis vectors; answer: partials per vector (0 = not done)
-  bool no_damp = false;   // transient: matvec kernels skip the damping B (preconditioned square root)
+  bool gmres_fold_norm = true;      // GMRES hands its next preconditioner an RblNormFold where pc_can_fold; off with RBL_OPT_FUSED_KRYLOV = 0
+  bool no_damp = false;   // RBL_OPT_NO_DAMP: matvec kernels skip the damping B (a product may also be asked to: RblProductReq::undamped)
   // tuning
   size_t sym_workspace_budget = (size_t)24 << 30;   // bytes the symmetric kernel may use for its slabs
   int tune_jsplit = 0;

@@ -9,7 +9,7 @@
 // side and the split of the solution -- are the O(N) kernels below: one workgroup per body, the mask read once per workgroup (the
 // branch on it is uniform), deterministic LDS tree sums, no atomics; the K / K^T formulas, the workgroup sum and the 6 x 6
 // substitution are rbl_body_dev.hpp's, shared with rbl_body_dev.hip.  The Arnoldi recurrence, the Hessenberg solve and the
-// convergence test are gmres_saddle_core_'s (gmres_core_with_ops).
+// convergence test are gmres_core's (gmres_core_with_ops).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -278,10 +278,9 @@ int mx_pc(rbl_ctx *c, void *user, const double *d_in, double *d_out)
   if (bf_on(c) && c->bf_tables) {
     // free space, small bodies: the one-launch body-frame preconditioner serves the free bodies as it is; the prescribed ones cost
     // a second application of the shared factor
-    const double keep = c->pc_fsign;
-    c->pc_fsign = 1.0;
-    rc = rbl_apply_PC_dev(c, d_in, d_out);
-    c->pc_fsign = keep;
+    RblPcReq rq;
+    rq.fsign = 1.0;
+    rc = apply_PC_dev(c, d_in, d_out, rq);
     if (rc || !m->any_prescribed) return rc;
     if ((rc = blk_solve(c, 0, S.N_bod, d_in, m->B->y1, 1, 0, 0))) return rc;
     hipLaunchKernelGGL(k_mx_pc_select, grid, block, 0, c->stream, m->B->mask, (const double *)m->B->y1, d_in, S.N_blb, n3, d_out);

@@ -14,15 +14,29 @@
 
 #define SYM_SHAPE_MSG "symmetric product: the options (sym_rows_per_lane / sym2_rows_per_lane / sym_waves / sym_chunk) force a kernel shape that does not exist"
 
-int apply_M_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double *d_r, int64_t nbl,
-                           int64_t row_begin, int64_t row_end, double *d_out)
+// the tune of one launch of the symmetric kernels: the context's persistent one with the request's switches (and the
+// RBL_OPT_RELAXED_ALWAYS hook) filled in
+static RblSymTune launch_tune(const rbl_ctx *c, const RblProductReq &rq)
 {
-  const RblParams P = ctx_params(c);
+  RblSymTune tune = c->sym_tune;
+  tune.relaxed = (rq.relaxed || c->force_relaxed) ? 1 : 0;
+  if (rq.fuse) tune.fuse = *rq.fuse;
+  return tune;
+}
+
+int apply_M_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double *d_r, int64_t nbl,
+                           int64_t row_begin, int64_t row_end, double *d_out, RblProductReq *rq)
+{
+  RblProductReq plain;
+  if (!rq) rq = &plain;
+  rq->fused = false;
+  const RblParams P = ctx_params(c, rq->undamped);
+  RblSymTune tune = launch_tune(c, *rq);
   const bool full = (row_begin == 0 && row_end == nbl);
   bool sym = full;   // measured faster at every size, N = 120 ... 128 400 (profiles/r01_apply_M_all_configs.md)
   // its row/column-sum slabs grow like N^2/128 * 24 B (1.7 GB at 128 400 blobs, ~100 GB at 10^6):
   // beyond a budget the ordered kernel (O(N) workspace, ~1.6x the time) takes over
-  if (sym && rbl_apply_M_sym_bytes(nbl, c->n_cu, 1, 1, c->sym_tune) > c->sym_workspace_budget) sym = false;
+  if (sym && rbl_apply_M_sym_bytes(nbl, c->n_cu, 1, 1, tune) > c->sym_workspace_budget) sym = false;
   if (c->tune_variant == 1) sym = false;
   if (c->tune_variant == 2) sym = full;
   int rc;
@@ -47,10 +61,8 @@ int apply_M_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double *d_r,
     return comm_allgather_rows(c, d_out, bounds.data(), 3);
   }
   if (full && comm_on(c)) {   // multi-GPU: this rank's tile pairs, then the sum over the ranks
-    RblSymTune tune = c->sym_tune;
     tune.fuse = RblSaddleFuse();                      // (a shard's sum is partial: the epilogue waits for the all-reduce)
-    if (c->force_relaxed) tune.relaxed = 1;
-    if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_sym_bytes(nbl, c->n_cu, c->comm_world, 1, tune)))) return rc;   // (the geometry follows the transient switches)
+    if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_sym_bytes(nbl, c->n_cu, c->comm_world, 1, tune)))) return rc;   // (the geometry follows the request's switches)
     {
       RblPhase ph(c, RBL_T_PRODUCT);
       if ((rc = rbl_launch_apply_M_sym(c->stream, P, wall, d_F, d_r, nbl, c->comm_rank, c->comm_world, d_out, (double *)c->d_part.p,
@@ -61,13 +73,11 @@ int apply_M_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double *d_r,
   }
   RblPhase ph(c, RBL_T_PRODUCT);
   if (sym) {
-    RblSymTune tune = c->sym_tune;
-    if (c->force_relaxed) tune.relaxed = 1;
-    if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_sym_bytes(nbl, c->n_cu, 1, 1, tune)))) return rc;   // (the geometry follows the transient switches)
+    if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_sym_bytes(nbl, c->n_cu, 1, 1, tune)))) return rc;   // (the geometry follows the request's switches)
     if ((rc = rbl_launch_apply_M_sym(c->stream, P, wall, d_F, d_r, nbl, 0, 1, d_out, (double *)c->d_part.p, c->n_cu,
                                      c->d_err, 1, tune)))
       return rbl_fail(c, rc, SYM_SHAPE_MSG);
-    c->fuse_done = tune.fuse.lever != nullptr;        // the slab reduction also wrote the saddle epilogue (rbl_apply_saddle_dev)
+    rq->fused = tune.fuse.lever != nullptr;       // the slab reduction also wrote the saddle epilogue (apply_saddle_dev)
   } else {
     int js = 1;
     const size_t pb = rbl_apply_M_part_bytes(nbl, row_end - row_begin, c->n_cu, c->tune_jsplit, &js);
@@ -82,8 +92,12 @@ int apply_M_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double *d_r,
 // fp64-MFMA kernel in passes of 16; fewer are cheaper one by one on the symmetric kernel.
 // tune_variant 3 forces the MFMA kernel, 1/2 force the single-RHS kernels.
 int apply_M_multi_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double *d_r, int64_t nbl,
-                                 int nrhs, double *d_out, int64_t ldF, int64_t ldO)
+                                 int nrhs, double *d_out, int64_t ldF, int64_t ldO, RblProductReq *rq)
 {
+  RblProductReq plain;
+  if (!rq) rq = &plain;
+  const RblParams P = ctx_params(c, rq->undamped);
+  const RblSymTune tune = launch_tune(c, *rq);
   const int64_t n3 = 3 * nbl;
   if (ldF <= 0) ldF = n3;                               // doubles between consecutive vectors (default: packed)
   if (ldO <= 0) ldO = n3;
@@ -93,7 +107,7 @@ int apply_M_multi_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double
     if (c->tune_variant == 1 || c->tune_variant == 2) mf = false;
     if (comm_on(c) || !mf) {
       for (int k = 0; k < nrhs; ++k) {
-        const int rc1 = apply_M_enqueue(c, wall, d_F + (size_t)k * (size_t)ldF, d_r, nbl, 0, nbl, d_out + (size_t)k * (size_t)ldO);
+        const int rc1 = apply_M_enqueue(c, wall, d_F + (size_t)k * (size_t)ldF, d_r, nbl, 0, nbl, d_out + (size_t)k * (size_t)ldO, rq);
         if (rc1) return rc1;
       }
       return RBL_OK;
@@ -101,10 +115,9 @@ int apply_M_multi_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double
     int rc2;
     RblPhase ph2(c, RBL_T_PRODUCT);
     if ((rc2 = rbl_dev_reserve(c, c->d_part, rbl_apply_M_mrhs_bytes(nbl, c->n_cu)))) return rc2;
-    const RblParams P2 = ctx_params(c);
     for (int k = 0; k < nrhs; k += 16) {
       const int nb = (nrhs - k < 16) ? nrhs - k : 16;
-      rbl_launch_apply_M_mrhs(c->stream, P2, wall, d_F + (size_t)k * (size_t)ldF, d_r, nbl, nb, d_out + (size_t)k * (size_t)ldO,
+      rbl_launch_apply_M_mrhs(c->stream, P, wall, d_F + (size_t)k * (size_t)ldF, d_r, nbl, nb, d_out + (size_t)k * (size_t)ldO,
                               (double *)c->d_part.p, c->n_cu, c->d_err, ldF, ldO);
     }
     return RBL_OK;
@@ -117,43 +130,38 @@ int apply_M_multi_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double
     int k = 0;
     if (c->comm_split == 1) {   // (the row split has no two-vector kernel: one ordered-pair pass per vector)
       for (; k < nrhs; ++k)
-        if ((rc = apply_M_enqueue(c, wall, d_F + (size_t)k * n3, d_r, nbl, 0, nbl, d_out + (size_t)k * n3))) return rc;
+        if ((rc = apply_M_enqueue(c, wall, d_F + (size_t)k * n3, d_r, nbl, 0, nbl, d_out + (size_t)k * n3, rq))) return rc;
       return RBL_OK;
     }
     for (; k + 2 <= nrhs; k += 2) {
-      RblSymTune tune = c->sym_tune;
-      if (c->force_relaxed) tune.relaxed = 1;
-      if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_sym_bytes(nbl, c->n_cu, c->comm_world, 2, tune)))) return rc;   // (the geometry follows the transient switches)
+      if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_sym_bytes(nbl, c->n_cu, c->comm_world, 2, tune)))) return rc;   // (the geometry follows the request's switches)
       {
         RblPhase ph(c, RBL_T_PRODUCT);
-        if ((rc = rbl_launch_apply_M_sym(c->stream, ctx_params(c), wall, d_F + (size_t)k * n3, d_r, nbl, c->comm_rank, c->comm_world,
+        if ((rc = rbl_launch_apply_M_sym(c->stream, P, wall, d_F + (size_t)k * n3, d_r, nbl, c->comm_rank, c->comm_world,
                                          d_out + (size_t)k * n3, (double *)c->d_part.p, c->n_cu, c->d_err, 2, tune)))
           return rbl_fail(c, rc, SYM_SHAPE_MSG);
       }
       if ((rc = comm_allreduce(c, d_out + (size_t)k * n3, 2 * n3))) return rc;
     }
     for (; k < nrhs; ++k)
-      if ((rc = apply_M_enqueue(c, wall, d_F + (size_t)k * n3, d_r, nbl, 0, nbl, d_out + (size_t)k * n3))) return rc;
+      if ((rc = apply_M_enqueue(c, wall, d_F + (size_t)k * n3, d_r, nbl, 0, nbl, d_out + (size_t)k * n3, rq))) return rc;
     return RBL_OK;
   }
   RblPhase ph(c, RBL_T_PRODUCT);
   if (!mfma) {   // 1-3 vectors: pairs of vectors through the two-vector symmetric kernel, a single one alone
     int k = 0;
-    const bool sym2 = c->tune_variant != 1 && rbl_apply_M_sym_bytes(nbl, c->n_cu, 1, 2, c->sym_tune) <= c->sym_workspace_budget;
+    const bool sym2 = c->tune_variant != 1 && rbl_apply_M_sym_bytes(nbl, c->n_cu, 1, 2, tune) <= c->sym_workspace_budget;
     for (; sym2 && k + 2 <= nrhs; k += 2) {
-      RblSymTune tune = c->sym_tune;
-      if (c->force_relaxed) tune.relaxed = 1;
-      if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_sym_bytes(nbl, c->n_cu, 1, 2, tune)))) return rc;   // (the geometry follows the transient switches)
-      if ((rc = rbl_launch_apply_M_sym(c->stream, ctx_params(c), wall, d_F + (size_t)k * n3, d_r, nbl, 0, 1,
+      if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_sym_bytes(nbl, c->n_cu, 1, 2, tune)))) return rc;   // (the geometry follows the request's switches)
+      if ((rc = rbl_launch_apply_M_sym(c->stream, P, wall, d_F + (size_t)k * n3, d_r, nbl, 0, 1,
                                        d_out + (size_t)k * n3, (double *)c->d_part.p, c->n_cu, c->d_err, 2, tune)))
         return rbl_fail(c, rc, SYM_SHAPE_MSG);
     }
     for (; k < nrhs; ++k)
-      if ((rc = apply_M_enqueue(c, wall, d_F + (size_t)k * n3, d_r, nbl, 0, nbl, d_out + (size_t)k * n3))) return rc;
+      if ((rc = apply_M_enqueue(c, wall, d_F + (size_t)k * n3, d_r, nbl, 0, nbl, d_out + (size_t)k * n3, rq))) return rc;
     return RBL_OK;
   }
   if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_mrhs_bytes(nbl, c->n_cu)))) return rc;
-  const RblParams P = ctx_params(c);
   for (int k = 0; k < nrhs; k += 16) {
     const int nb = (nrhs - k < 16) ? nrhs - k : 16;
     rbl_launch_apply_M_mrhs(c->stream, P, wall, d_F + (size_t)k * n3, d_r, nbl, nb, d_out + (size_t)k * n3,
@@ -340,7 +348,7 @@ int rbl_apply_M_sym_multi_dev(rbl_ctx *c, const double *d_F, const double *d_r, 
   if (n_blobs <= 0 || i_step < 1 || i_first < 0 || i_first >= i_step || nrhs < 1 || nrhs > 2)
     return rbl_fail(c, RBL_ERR_SIZE, "apply_M_sym_multi_dev: need n_blobs > 0, 0 <= i_first < i_step, nrhs 1 or 2");
   if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_sym_bytes(n_blobs, c->n_cu, i_step, nrhs, c->sym_tune)))) return rc;
-  if ((rc = rbl_launch_apply_M_sym(c->stream, ctx_params(c), c->S.wall, d_F, d_r, n_blobs, i_first,
+  if ((rc = rbl_launch_apply_M_sym(c->stream, ctx_params(c, false), c->S.wall, d_F, d_r, n_blobs, i_first,
                                    i_step, d_out, (double *)c->d_part.p, c->n_cu, c->d_err, nrhs, c->sym_tune)))
     return rbl_fail(c, rc, SYM_SHAPE_MSG);
   return RBL_OK;
@@ -353,10 +361,9 @@ int rbl_apply_M_sym_dev(rbl_ctx *c, const double *d_F, const double *d_r, int64_
   if ((rc = rbl_dev_init(c))) return rc;
   if (n_blobs <= 0 || i_step < 1 || i_first < 0 || i_first >= i_step)
     return rbl_fail(c, RBL_ERR_SIZE, "apply_M_sym_dev: need n_blobs > 0 and 0 <= i_first < i_step");
-  RblSymTune tune = c->sym_tune;
-  if (c->force_relaxed) tune.relaxed = 1;
-  if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_sym_bytes(n_blobs, c->n_cu, i_step, 1, tune)))) return rc;   // (the geometry follows the transient switches)
-  if ((rc = rbl_launch_apply_M_sym(c->stream, ctx_params(c), c->S.wall, d_F, d_r, n_blobs, i_first,
+  const RblSymTune tune = launch_tune(c, RblProductReq());
+  if ((rc = rbl_dev_reserve(c, c->d_part, rbl_apply_M_sym_bytes(n_blobs, c->n_cu, i_step, 1, tune)))) return rc;   // (the geometry follows RBL_OPT_RELAXED_ALWAYS)
+  if ((rc = rbl_launch_apply_M_sym(c->stream, ctx_params(c, false), c->S.wall, d_F, d_r, n_blobs, i_first,
                                    i_step, d_out, (double *)c->d_part.p, c->n_cu, c->d_err, 1, tune)))
     return rbl_fail(c, rc, SYM_SHAPE_MSG);
   return RBL_OK;

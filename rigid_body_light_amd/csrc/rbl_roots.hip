@@ -171,11 +171,14 @@ int tl_apply(rbl_ctx *c, const double *w, double *wo, int nvec, int64_t pitch, i
 // y_v = (B M B) x_v for nvec (1 or 2) vectors stored back to back; two vectors share the pair coefficients
 // precond: y_v = L^-1 M L^-T x_v with the per-body Cholesky factors L L^T = M_body (block Jacobi), M undamped
 static int apply_A_dev(rbl_ctx *c, const RblParams &P, const double *d_r, int64_t nbl,
-                       const double *d_x, double *d_y, double *d_tmp, int nvec = 1, bool precond = false)
+                       const double *d_x, double *d_y, double *d_tmp, int nvec, bool precond, bool relaxed)
 {
   const int64_t n = 3 * nbl;
+  RblProductReq rq;
+  rq.relaxed = relaxed;
   if (precond) {
     int rc;
+    rq.undamped = true;                                 // M itself between the factors, whatever RBL_OPT_NO_DAMP says
     // B G (G^-1 M G^-T)^{1/2} W is an exact root for any invertible G applied CONSISTENTLY; the single-precision copy of L^-1
     // and the fp64 L of the final product agree to 6e-8 only, so it serves the loose tolerances (>= 1e-5) and no others
     const bool lz32 = c->lanczos_tol >= 1.0e-5;
@@ -193,10 +196,7 @@ static int apply_A_dev(rbl_ctx *c, const RblParams &P, const double *d_r, int64_
       if ((rc = blk_solve(c, b0, b1 - b0, src, d_tmp, nvec, n, 2, lz32)))
         return rbl_fail(c, rc, "preconditioned square root: the per-body factor application failed");
       if ((rc = comm_allgather_bodies(c, d_tmp, 0, mb, nvec, n))) return rc;
-      c->no_damp = true;
-      rc = apply_M_multi_enqueue(c, c->S.wall, d_tmp, d_r, nbl, nvec, d_y);
-      c->no_damp = false;
-      if (rc) return rc;
+      if ((rc = apply_M_multi_enqueue(c, c->S.wall, d_tmp, d_r, nbl, nvec, d_y, 0, 0, &rq))) return rc;
       if (comm_gather_needs_zero(c)) RBL_HIP(c, hipMemsetAsync(d_tmp, 0, vbytes, c->stream));
       if ((rc = blk_solve(c, b0, b1 - b0, d_y, d_tmp, nvec, n, 1, lz32))) return rc;
       if ((rc = comm_allgather_bodies(c, d_tmp, 0, mb, nvec, n))) return rc;
@@ -213,17 +213,14 @@ static int apply_A_dev(rbl_ctx *c, const RblParams &P, const double *d_r, int64_
       if ((rc = rbl_dev_reserve(c, c->d_blkTmp, sizeof(double) * 3 * (size_t)n))) return rc;
       prod = (double *)c->d_blkTmp.p;
     }
-    c->no_damp = true;
-    rc = apply_M_multi_enqueue(c, c->S.wall, d_tmp, d_r, nbl, nvec, prod);
-    c->no_damp = false;
-    if (rc) return rc;
+    if ((rc = apply_M_multi_enqueue(c, c->S.wall, d_tmp, d_r, nbl, nvec, prod, 0, 0, &rq))) return rc;
     if ((rc = blk_solve(c, 0, c->S.N_bod, prod, d_y, nvec, n, 1, lz32))) return rc;
     return tl ? tl_apply(c, d_y, d_y, nvec, n, 1) : RBL_OK;
   }
-  if (c->S.wall) return apply_M_multi_enqueue(c, true, d_x, d_r, nbl, nvec, d_y);   // kernel applies B M B itself
+  if (c->S.wall) return apply_M_multi_enqueue(c, true, d_x, d_r, nbl, nvec, d_y, 0, 0, &rq);   // kernel applies B M B itself
   for (int v = 0; v < nvec; ++v)                                                     // free-space M, damping around it
     rbl_launch_scale_by_damp(c->stream, P, d_r, nbl, d_x + (size_t)v * n, d_tmp + (size_t)v * n);
-  int rc = apply_M_multi_enqueue(c, false, d_tmp, d_r, nbl, nvec, d_y);
+  int rc = apply_M_multi_enqueue(c, false, d_tmp, d_r, nbl, nvec, d_y, 0, 0, &rq);
   for (int v = 0; v < nvec; ++v)
     rbl_launch_scale_by_damp(c->stream, P, d_r, nbl, d_y + (size_t)v * n, d_y + (size_t)v * n);
   return rc;
@@ -313,10 +310,7 @@ static int mhalf_lanczos_dev(rbl_ctx *c, const double *d_r, int64_t nbl, const d
   static const bool trace = std::getenv("RBL_LANCZOS_TRACE") != nullptr;      // diagnostic: the estimate's history on stderr
   for (int it = 0; it < maxit && !done; ++it) {
     // inexact Krylov: an estimate wanted to lanczos_tol >= 1e-4 does not notice a product error of ~1e-6
-    c->sym_tune.relaxed = (c->gmres_relax && c->lanczos_tol >= 1.0e-4) ? 1 : 0;
-    rc = apply_A_dev(c, P, d_r, nbl, Vp(it, 0), u, tmp, nvec, precond);
-    c->sym_tune.relaxed = 0;
-    if (rc) return rc;
+    if ((rc = apply_A_dev(c, P, d_r, nbl, Vp(it, 0), u, tmp, nvec, precond, c->gmres_relax && c->lanczos_tol >= 1.0e-4))) return rc;
     // both recurrences of a pair in the same launches (vectors n apart, their scalars nsc apart)
     if (reorth)
       rbl_launch_lanczos_step_reorth(c->stream, n, it + 1, u, V, Vp(it + 1, 0), d_alpha(0) + it, d_beta(0) + it, (int64_t)nsc, d_hcol,

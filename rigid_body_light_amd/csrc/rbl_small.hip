@@ -230,7 +230,7 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(std::conditional_t<MIXED, S
   __syncthreads();
 
   // ---- operators on LDS vectors (every thread calls them: they contain barriers) ----------------------------
-  // out = P^-1 in   (apply_PC with the diagonal invM, :589-616; fsign: see rbl_ctx::pc_fsign)
+  // out = P^-1 in   (apply_PC with the diagonal invM, :589-616; fsign: see rbl_ctx::gmres_pc_sign_fix)
   auto apply_PC = [&](const double *in, double *out) {
     if (t < N) {                             // per-blob terms of K^T (invM slip) -> part[c][blob]
       const double v0 = iM[2 * t] * in[3 * t], v1 = iM[2 * t] * in[3 * t + 1], v2 = iM[2 * t + 1] * in[3 * t + 2];

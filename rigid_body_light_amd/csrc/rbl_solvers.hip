@@ -17,8 +17,44 @@
 // once at the end (fixed work, rtol <= 0) or, for the convergence test, every iteration (large systems) /
 // every 4th (small, launch-bound ones).
 
-static int gmres_saddle_core(rbl_ctx *c, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
-                             double *resid_out);
+// ops: the caller's operator and preconditioner instead of apply_saddle_dev / apply_PC_dev (RblSolveOps); NULL: the library's own
+static int gmres_core(rbl_ctx *c, const RblSolveOps *ops, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
+                      double *resid_out);
+
+// any invertible right preconditioner leaves the solution unchanged: inside the library's solves the force block of apply_PC takes
+// the sign that makes A P^-1 ~ I (rbl_ctx::gmres_pc_sign_fix); the bound apply_PC keeps the reference's convention
+static double gmres_fsign(const rbl_ctx *c) { return c->gmres_pc_sign_fix ? 1.0 : RBL_PC_FSIGN_REFERENCE; }
+
+// least squares min |beta e1 - H_k y| by Givens rotations on a host copy hc = [beta | H column-major, ldh rows]; returns the
+// residual estimate
+static double hessenberg_ls(const double *hc, int ldh, int k, std::vector<double> &yout)
+{
+  std::vector<double> R(hc + 1, hc + 1 + (size_t)ldh * k), g((size_t)k + 1, 0.0), cs((size_t)k), sn((size_t)k);
+  const double beta = hc[0];
+  g[0] = beta;
+  for (int j = 0; j < k; ++j) {
+    double *col = R.data() + (size_t)j * ldh;
+    for (int i = 0; i < j; ++i) {
+      const double t = cs[i] * col[i] + sn[i] * col[i + 1];
+      col[i + 1] = -sn[i] * col[i] + cs[i] * col[i + 1];
+      col[i] = t;
+    }
+    const double den = std::hypot(col[j], col[j + 1]);
+    cs[j] = den > 0.0 ? col[j] / den : 1.0;
+    sn[j] = den > 0.0 ? col[j + 1] / den : 0.0;
+    col[j] = den; col[j + 1] = 0.0;
+    g[j + 1] = -sn[j] * g[j];
+    g[j] = cs[j] * g[j];
+  }
+  yout.assign((size_t)k, 0.0);
+  for (int i = k - 1; i >= 0; --i) {
+    double v = g[i];
+    for (int j = i + 1; j < k; ++j) v -= R[(size_t)j * ldh + i] * yout[j];
+    const double d = R[(size_t)i * ldh + i];
+    yout[i] = d != 0.0 ? v / d : 0.0;
+  }
+  return beta > 0.0 ? std::fabs(g[k]) / beta : 0.0;
+}
 
 // Small systems (<= 256 blobs, diagonal PC): geometry, preconditioner build and the whole Arnoldi / Givens loop in ONE
 // kernel launch on one CU (rbl_small.hip) -- launch-bound otherwise (cfg 1: ~6 launches per iteration).
@@ -32,7 +68,7 @@ static int gmres_small(rbl_ctx *c, const double *d_rhs, const double *d_x0, int 
   double *work = (double *)c->d_gm.p, *scal = work + wd;
   const double *dX = (const double *)c->d_XQ.p, *dQ = dX + 3 * (size_t)S.N_bod;
   rc = rbl_launch_gmres_small(c->stream, rbl_make_params(S.a, S.eta), S.wall, dX, dQ, (const double *)c->d_cfg.p, S.N_blb,
-                              S.N_bod, d_rhs, d_x0, d_x, max_iter, rtol, c->gmres_pc_sign_fix ? 1.0 : c->pc_fsign, work, scal,
+                              S.N_bod, d_rhs, d_x0, d_x, max_iter, rtol, gmres_fsign(c), work, scal,
                               c->d_err);
   if (rc == RBL_ERR_SIZE) return rc;       // the caller falls back to the general solver
   if (rc) return rbl_fail(c, rc, "gmres (one-kernel solver): launch failed");
@@ -62,9 +98,8 @@ int rbl_gmres_saddle_dev(rbl_ctx *c, const double *d_rhs, int max_iter, double r
       c->gmres_small = false;                // this runtime does not grant the LDS the one-kernel solver needs
     }
   }
-  if (!use_x0) return gmres_saddle_core(c, d_rhs, max_iter, rtol, d_x, iters_out, resid_out);
+  if (!use_x0) return gmres_core(c, nullptr, d_rhs, max_iter, rtol, d_x, iters_out, resid_out);
   int rc = sync_bodies(c); if (rc) return rc;
-  if (!d_rhs || !d_x) return rbl_fail(c, RBL_ERR_ARG, "gmres: bad arguments");
   const int64_t nsys = (int64_t)3 * c->S.N_bod * c->S.N_blb + (int64_t)6 * c->S.N_bod;
   const size_t vb = sizeof(double) * (size_t)nsys;
   if ((rc = rbl_dev_reserve(c, c->d_bd2, 3 * vb + sizeof(double) * (2 + 2 * 512)))) return rc;   // + dot2 scratch
@@ -81,42 +116,29 @@ int rbl_gmres_saddle_dev(rbl_ctx *c, const double *d_rhs, int max_iter, double r
   const double scale = (nb2 > 0.0 && nr2 > 0.0) ? std::sqrt(nb2 / nr2) : 1.0;          // |b| / |r0|
   if (nr2 == 0.0) { if (iters_out) *iters_out = 0; if (resid_out) *resid_out = 0.0; return RBL_OK; }   // x0 already solves it
   double resid = 0.0;
-  if ((rc = gmres_saddle_core(c, r0, max_iter, rtol > 0.0 ? rtol * scale : rtol, dx, iters_out, &resid))) return rc;
+  if ((rc = gmres_core(c, nullptr, r0, max_iter, rtol > 0.0 ? rtol * scale : rtol, dx, iters_out, &resid))) return rc;
   rbl_launch_axpby(c->stream, nsys, 1.0, x0, 1.0, dx, d_x);                             // x = x0 + dx
   if (resid_out) *resid_out = resid / scale;
   return finish_and_check(c);
-}
-
-static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
-                              double *resid_out, const RblSolveOps *ops = nullptr);
-
-// any invertible right preconditioner leaves the solution unchanged: inside the solve the force block of apply_PC
-// takes the sign that makes A P^-1 ~ I (see rbl_ctx::pc_fsign); the bound apply_PC keeps the reference's convention
-static int gmres_saddle_core(rbl_ctx *c, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
-                             double *resid_out)
-{
-  const double keep = c->pc_fsign;
-  if (c->gmres_pc_sign_fix) c->pc_fsign = 1.0;
-  const int rc = gmres_saddle_core_(c, d_rhs, max_iter, rtol, d_x, iters_out, resid_out);
-  c->pc_fsign = keep;
-  return rc;
 }
 
 int gmres_core_with_ops(rbl_ctx *c, const RblSolveOps *ops, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
                         double *resid_out)
 {
   if (!ops || !ops->op || !ops->pc) return rbl_fail(c, RBL_ERR_ARG, "gmres: no operator");
-  return gmres_saddle_core_(c, d_rhs, max_iter, rtol, d_x, iters_out, resid_out, ops);
+  return gmres_core(c, ops, d_rhs, max_iter, rtol, d_x, iters_out, resid_out);
 }
 
-// ops: the caller's operator and preconditioner instead of rbl_apply_saddle_dev / rbl_apply_PC_dev (RblSolveOps: nothing fused)
-static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
-                              double *resid_out, const RblSolveOps *ops)
+static int gmres_core(rbl_ctx *c, const RblSolveOps *ops, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
+                      double *resid_out)
 {
   int rc = sync_bodies(c); if (rc) return rc;
   if (!d_rhs || !d_x || max_iter < 1) return rbl_fail(c, RBL_ERR_ARG, "gmres: bad arguments");
   if (max_iter + 1 > rbl_gmres_max_vectors()) return rbl_fail(c, RBL_ERR_ARG, "gmres: at most 255 iterations (no restart)");
   const RblBodyState &S = c->S;
+  // the library's own operators take requests (RblPcReq, RblSaddleReq) and the iteration-count memory is theirs; a caller's take none
+  const bool own = !ops;
+  const double fsign = gmres_fsign(c);
   const int64_t nsys = (int64_t)3 * S.N_bod * S.N_blb + (int64_t)6 * S.N_bod;
   const int m = max_iter, ldh = m + 1;
   const size_t vb = sizeof(double) * (size_t)nsys;
@@ -136,38 +158,9 @@ static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, dou
   // looks at every iteration since the one before, so the solve still ends at the first iteration that passes.
   const int check_every = ((int64_t)S.N_bod * S.N_blb > 20000) ? 1 : 4;
   int next_check = check_every, last_checked = 0;
-  if (check_every > 1 && c->gmres_predict && c->gmres_last_used > 0 && !ops) next_check = c->gmres_last_used >= 8 ? c->gmres_last_used - 2 : c->gmres_last_used;
+  if (check_every > 1 && c->gmres_predict && c->gmres_last_used > 0 && own) next_check = c->gmres_last_used >= 8 ? c->gmres_last_used - 2 : c->gmres_last_used;
   int used = 0;
   double resid = 1.0;
-  // least squares min |beta e1 - H_k y| by Givens rotations on a host copy; returns the residual estimate
-  auto solve_ls = [&](int k, std::vector<double> &yout) -> double {
-    std::vector<double> R(Hh.begin() + 1, Hh.begin() + 1 + (size_t)ldh * k), g((size_t)k + 1, 0.0);
-    const double beta = Hh[0];
-    g[0] = beta;
-    std::vector<double> cs((size_t)k), sn((size_t)k);
-    for (int j = 0; j < k; ++j) {
-      double *col = R.data() + (size_t)j * ldh;
-      for (int i = 0; i < j; ++i) {
-        const double t = cs[i] * col[i] + sn[i] * col[i + 1];
-        col[i + 1] = -sn[i] * col[i] + cs[i] * col[i + 1];
-        col[i] = t;
-      }
-      const double den = std::hypot(col[j], col[j + 1]);
-      cs[j] = den > 0.0 ? col[j] / den : 1.0;
-      sn[j] = den > 0.0 ? col[j + 1] / den : 0.0;
-      col[j] = den; col[j + 1] = 0.0;
-      g[j + 1] = -sn[j] * g[j];
-      g[j] = cs[j] * g[j];
-    }
-    yout.assign((size_t)k, 0.0);
-    for (int i = k - 1; i >= 0; --i) {
-      double v = g[i];
-      for (int j = i + 1; j < k; ++j) v -= R[(size_t)j * ldh + i] * yout[j];
-      const double d = R[(size_t)i * ldh + i];
-      yout[i] = d != 0.0 ? v / d : 0.0;
-    }
-    return beta > 0.0 ? std::fabs(g[k]) / beta : 0.0;
-  };
   // Overlapped convergence test (large systems, RBL_OPT_GMRES_OVERLAP_CHECK): the Hessenberg columns of iteration j go to the
   // host by an asynchronous copy; the preconditioner of iteration j + 1 is enqueued BEFORE the host waits for that copy, so
   // the stream never runs dry at a test -- on N GPUs no rank drains per iteration.  A solve that ends at j has applied one
@@ -183,13 +176,16 @@ static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, dou
   // 1 / |w| themselves and store V_{j+1} and H[j+1][j] on the side -- one launch fewer per iteration.  A convergence test that
   // falls between the two gets |w| from the same partial sums on the host.  The last possible iteration normalises as before.
   RblNormFold pend;                                    // set: V_j and H[j][j-1] are still to be written, from w
+  const double *ktl_z = nullptr;                       // K^T Lambda of z where the preconditioner left it: feeds the product that follows
   auto apply_pc = [&](int jv) -> int {                 // z = P^-1 V_jv
     if (ops) return ops->pc(c, ops->user, V + (size_t)jv * nsys, z);
-    c->ktl_arm = true;                                 // the PC's K^T Lambda by-product feeds the product that follows
+    RblPcReq rq;
+    rq.fsign = fsign; rq.leave_ktl = true;
+    const RblNormFold fold = pend;
     const double *src = V + (size_t)jv * nsys;
-    if (pend.part) { c->pc_fold = pend; src = w; pend = RblNormFold(); }
-    const int r = rbl_apply_PC_dev(c, src, z);
-    if (r) c->ktl_arm = false;
+    if (fold.part) { rq.fold = &fold; src = w; pend = RblNormFold(); }
+    const int r = apply_PC_dev(c, src, z, rq);
+    ktl_z = rq.ktl;
     return r;
   };
   for (int j = 0; j < m; ++j) {
@@ -197,17 +193,15 @@ static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, dou
     z_ready = false;
     // inexact Krylov: the j-th product may be in error by ~ rtol / |r_{j-1}| (relative); the relaxed kernel's ~1e-6 is
     // admissible once the residual estimate is below rtol x 1e5 (an order of magnitude in hand)
-    c->sym_tune.relaxed = (!ops && c->gmres_relax == 1 && rtol > 0.0 && check_every == 1 && resid <= rtol * 1.0e5) ? 1 : 0;
-    if (!ops) { c->fuse_dotV = V; c->fuse_dotK = j + 1; c->fuse_dotPart = part; }   // (small systems: the product's last kernel starts the Gram-Schmidt pass)
-    rc = ops ? ops->op(c, ops->user, z, w) : rbl_apply_saddle_dev(c, z, w);
-    const int fused_np = ops ? 0 : c->fuse_dots_np;
-    c->fuse_dotV = nullptr; c->fuse_dotK = 0; c->fuse_dotPart = nullptr; c->fuse_dots_np = 0;
-    c->sym_tune.relaxed = 0;
-    c->ktl_arm = false; c->ktl_of = nullptr;
-    if (rc) return rc;
+    RblSaddleReq sq;
+    sq.ktl = ktl_z;
+    sq.relaxed = c->gmres_relax == 1 && rtol > 0.0 && check_every == 1 && resid <= rtol * 1.0e5;
+    sq.dotV = V; sq.dotK = j + 1; sq.dotPart = part;   // (small systems: the product's last kernel starts the Gram-Schmidt pass)
+    if ((rc = ops ? ops->op(c, ops->user, z, w) : apply_saddle_dev(c, z, w, sq))) return rc;
+    const int fused_np = sq.dots_np;
     double *Hcol = H + (size_t)j * ldh;
     // classical Gram-Schmidt twice, H[j+1][j] = |w|, V_{j+1} = w / |w|: four launches (three when the product left the first sums)
-    const bool fold = !ops && j + 1 < m && pc_can_fold(c);
+    const bool fold = own && j + 1 < m && pc_can_fold(c);
     const double *npart = nullptr; int nnp = 0;
     rbl_launch_arnoldi_step(c->stream, V, nsys, j + 1, w, Hcol, V + (size_t)(j + 1) * nsys, part, fused_np, fold, &npart, &nnp);
     if (fold) { pend.part = npart; pend.np = nnp; pend.vnext = V + (size_t)(j + 1) * nsys; pend.hout = Hcol + (j + 1); }
@@ -239,10 +233,10 @@ static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, dou
       double r_before = resid;
       for (int k = last_checked + 1; k <= used; ++k) {
         r_before = resid;
-        resid = solve_ls(k, y);
+        resid = hessenberg_ls(Hh.data(), ldh, k, y);
         if (resid < rtol) { hit = k; break; }
       }
-      if (hit) { used = hit; c->ktl_arm = false; c->ktl_of = nullptr; break; }
+      if (hit) { used = hit; break; }
       last_checked = used;
       int ahead = 1;
       if (check_every > 1 && !c->gmres_predict) ahead = check_every - (used % check_every);
@@ -258,16 +252,18 @@ static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, dou
   }
   if (!(rtol > 0.0) || y.size() != (size_t)used) {
     if ((rc = read_back(c, Hh.data(), d_beta, sizeof(double) * (1 + (size_t)ldh * used)))) return rc;
-    resid = solve_ls(used, y);
+    resid = hessenberg_ls(Hh.data(), ldh, used, y);
   }
   for (int k = 0; k < used; ++k)
     if (!std::isfinite(y[k])) return rbl_fail(c, RBL_ERR_NONFINITE, "gmres: non-finite Hessenberg solve");
   if ((rc = upload_coef(c, d_y, y.data(), used, 0))) return rc;
   rbl_launch_lanczos_combine(c->stream, nsys, V, d_y, used, z);                        // z = V y
-  if ((rc = ops ? ops->pc(c, ops->user, z, d_x) : rbl_apply_PC_dev(c, z, d_x))) return rc;   // x = P^-1 z
+  RblPcReq last;
+  last.fsign = fsign;
+  if ((rc = ops ? ops->pc(c, ops->user, z, d_x) : apply_PC_dev(c, z, d_x, last))) return rc;   // x = P^-1 z
   if (iters_out) *iters_out = used;
   if (resid_out) *resid_out = resid;
-  if (rtol > 0.0 && !ops) c->gmres_last_used = used;
+  if (rtol > 0.0 && own) c->gmres_last_used = used;
   return finish_and_check(c);
 }
 
@@ -283,6 +279,7 @@ static int gmres_saddle_core_(rbl_ctx *c, const double *d_rhs, int max_iter, dou
 // when it converges, so the preconditioner and the product never read stale or unwritten memory for it.
 static int gmres_multi_batch(rbl_ctx *c, const double *d_rhs, int k, int m, double rtol, double *d_x, int *iters_out, double *resid_out)
 {
+  const double fsign = gmres_fsign(c);              // one eigenvalue cluster instead of two, as in the one-vector solver
   const RblBodyState &S = c->S;
   const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N, nsys = n3 + (int64_t)6 * S.N_bod;
   const int ldh = m + 1;
@@ -304,38 +301,10 @@ static int gmres_multi_batch(rbl_ctx *c, const double *d_rhs, int k, int m, doub
   std::vector<std::vector<double>> ys((size_t)k);
   std::vector<int> used((size_t)k, 0), done((size_t)k, 0);
   std::vector<double> resid((size_t)k, 1.0);
-  auto solve_ls = [&](int col, int kk, std::vector<double> &yout) -> double {       // Givens on a host copy, as in the one-vector solver
-    const double *hc = Hh.data() + hcol * (size_t)col;
-    std::vector<double> R(hc + 1, hc + 1 + (size_t)ldh * kk), g((size_t)kk + 1, 0.0), cs((size_t)kk), sn((size_t)kk);
-    const double beta = hc[0];
-    g[0] = beta;
-    for (int j = 0; j < kk; ++j) {
-      double *cl = R.data() + (size_t)j * ldh;
-      for (int i = 0; i < j; ++i) {
-        const double t = cs[i] * cl[i] + sn[i] * cl[i + 1];
-        cl[i + 1] = -sn[i] * cl[i] + cs[i] * cl[i + 1];
-        cl[i] = t;
-      }
-      const double den = std::hypot(cl[j], cl[j + 1]);
-      cs[j] = den > 0.0 ? cl[j] / den : 1.0;
-      sn[j] = den > 0.0 ? cl[j + 1] / den : 0.0;
-      cl[j] = den; cl[j + 1] = 0.0;
-      g[j + 1] = -sn[j] * g[j];
-      g[j] = cs[j] * g[j];
-    }
-    yout.assign((size_t)kk, 0.0);
-    for (int i = kk - 1; i >= 0; --i) {
-      double v = g[i];
-      for (int j = i + 1; j < kk; ++j) v -= R[(size_t)j * ldh + i] * yout[j];
-      const double d = R[(size_t)i * ldh + i];
-      yout[i] = d != 0.0 ? v / d : 0.0;
-    }
-    return beta > 0.0 ? std::fabs(g[kk]) / beta : 0.0;
-  };
   int n_done = 0;
   for (int j = 0; j < m && n_done < k; ++j) {
     // z_c = P^-1 V_c,j : all columns together (converged ones ride along on zeroed slots, whose results are never read)
-    if ((rc = apply_PC_multi_dev(c, Vc(0, j), Zc(0), Sc(0), k, pitch))) return rc;
+    if ((rc = apply_PC_multi_dev(c, Vc(0, j), Zc(0), Sc(0), k, pitch, fsign))) return rc;
     // w_c = [M lambda - K U ; K^T lambda] : ONE multi-vector product, then the O(N) body terms column by column
     if ((rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3 * (size_t)k))) return rc;
     if ((rc = apply_M_multi_enqueue(c, S.wall, Zc(0), (const double *)c->d_pos.p, N, k, (double *)c->d_sad.p, pitch, n3))) return rc;
@@ -350,7 +319,7 @@ static int gmres_multi_batch(rbl_ctx *c, const double *d_rhs, int k, int m, doub
       if ((rc = read_back(c, Hh.data(), Hall, sizeof(double) * hcol * (size_t)k))) return rc;
       for (int col = 0; col < k; ++col) {
         if (done[(size_t)col]) continue;
-        resid[(size_t)col] = solve_ls(col, j + 1, ys[(size_t)col]);
+        resid[(size_t)col] = hessenberg_ls(Hh.data() + hcol * (size_t)col, ldh, j + 1, ys[(size_t)col]);
         if (resid[(size_t)col] < rtol) {
           done[(size_t)col] = 1; ++n_done;
           if (j + 1 < m && n_done < k)                 // V_{j+1} .. V_{m-1}: what the later iterations read for this column
@@ -362,7 +331,7 @@ static int gmres_multi_batch(rbl_ctx *c, const double *d_rhs, int k, int m, doub
   if (!(rtol > 0.0) || n_done < k) {
     if ((rc = read_back(c, Hh.data(), Hall, sizeof(double) * hcol * (size_t)k))) return rc;
     for (int col = 0; col < k; ++col)
-      if (!done[(size_t)col]) resid[(size_t)col] = solve_ls(col, used[(size_t)col], ys[(size_t)col]);
+      if (!done[(size_t)col]) resid[(size_t)col] = hessenberg_ls(Hh.data() + hcol * (size_t)col, ldh, used[(size_t)col], ys[(size_t)col]);
   }
   for (int col = 0; col < k; ++col) {
     const int u = used[(size_t)col];
@@ -373,7 +342,7 @@ static int gmres_multi_batch(rbl_ctx *c, const double *d_rhs, int k, int m, doub
     if (iters_out) iters_out[col] = u;
     if (resid_out) resid_out[col] = resid[(size_t)col];
   }
-  if ((rc = apply_PC_multi_dev(c, Zc(0), Wc(0), Sc(0), k, pitch))) return rc;                        // x = P^-1 z
+  if ((rc = apply_PC_multi_dev(c, Zc(0), Wc(0), Sc(0), k, pitch, fsign))) return rc;                        // x = P^-1 z
   for (int col = 0; col < k; ++col)
     RBL_HIP(c, hipMemcpyAsync(d_x + (size_t)col * (size_t)nsys, Wc(col), sizeof(double) * (size_t)nsys, hipMemcpyDeviceToDevice, c->stream));
   return RBL_OK;
@@ -389,14 +358,11 @@ int rbl_gmres_saddle_multi_dev(rbl_ctx *c, const double *d_rhs, int nrhs, int ma
   if (max_iter + 1 > rbl_gmres_max_vectors()) return rbl_fail(c, RBL_ERR_ARG, "gmres: at most 255 iterations (no restart)");
   if ((rc = sync_bodies(c))) return rc;
   const int64_t nsys = (int64_t)3 * c->S.N_bod * c->S.N_blb + (int64_t)6 * c->S.N_bod;
-  const double keep = c->pc_fsign;
-  if (c->gmres_pc_sign_fix) c->pc_fsign = 1.0;          // one eigenvalue cluster instead of two, as in the one-vector solver
   for (int k0 = 0; k0 < nrhs && !rc; k0 += 16) {
     const int kb = nrhs - k0 < 16 ? nrhs - k0 : 16;
     rc = gmres_multi_batch(c, d_rhs + (size_t)k0 * (size_t)nsys, kb, max_iter, rtol, d_x + (size_t)k0 * (size_t)nsys,
                            iters_out ? iters_out + k0 : nullptr, resid_out ? resid_out + k0 : nullptr);
   }
-  c->pc_fsign = keep;
   if (rc) return rc;
   return finish_and_check(c);
 }

@@ -291,3 +291,92 @@ def test_lock_step_gmres_for_many_right_hand_sides(orc, monkeypatch, nb, nblb, w
     assert Nmat.shape == (6 * nb, 6 * nb) and np.all(itn > 0)
     assert np.linalg.norm(Nmat - Nref) <= 1e-8 * np.linalg.norm(Nref)
     assert np.linalg.norm(Nmat - Nmat.T) <= 1e-8 * np.linalg.norm(Nmat)            # symmetric positive definite, as a mobility must be
+
+
+def _ctx_4x12(wall, block):
+    """4 x shell_N_12 = 48 blobs on the general solver: the smallest system on which every fused Krylov shortcut is live (four
+    partial sums per vector in the product's slab reduction, several bodies)"""
+    import torch
+    from rigid_body_light_amd import make_config
+    from rigid_body_light_amd._lib import DeviceContext, lib
+    c = make_config(4, 12, wall)
+    ctx = DeviceContext(c["a"], c["eta"], wall, cfg=c["cfg"], dt=c["dt"], stream_ptr=torch.cuda.current_stream().cuda_stream)
+    lib().rbl_set_blk_pc(ctx.h, 1 if block else 0)
+    ctx.set_config(c["X"], c["Q"])
+    ctx.set_option("gmres_one_kernel", 0)
+    return ctx
+
+
+@pytest.mark.parametrize("wall", [False, True])
+@pytest.mark.parametrize("block", [False, True])
+def test_a_solve_leaves_nothing_behind_for_the_bound_operators(wall, block):
+    """What a solver asks of the preconditioner and the saddle product (the force block's sign, K^T Lambda on the side, a folded
+    normalisation, Gram-Schmidt sums, relaxed or undamped products) is an argument of that one call: after a converged solve, a
+    fixed-work one, a lock-step solve and a preconditioned root, the bound apply_PC (the reference's sign convention) and
+    apply_saddle give bitwise what a fresh context gives, and a repeated fixed-work solve repeats itself bitwise."""
+    import torch
+    nb, nblb = 4, 12
+    N = nb * nblb; n3 = 3 * N; nsys = n3 + 6 * nb
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(48)
+    rhs = torch.from_numpy(np.concatenate([0.1 * rng.standard_normal((3, n3)), rng.standard_normal((3, 6 * nb))], axis=1)).to(dev)
+    v = torch.from_numpy(rng.standard_normal(nsys)).to(dev)
+    W = torch.from_numpy(rng.standard_normal(n3)).to(dev)
+    used = _ctx_4x12(wall, block)
+    x = torch.empty(nsys, dtype=torch.float64, device=dev)
+    m, res = used.gmres_saddle(rhs[0].data_ptr(), 200, 1e-9, x.data_ptr()); used.sync_check()
+    assert 3 < m < 200 and res < 1e-9
+    x7 = torch.empty_like(x)
+    m7, _ = used.gmres_saddle(rhs[0].data_ptr(), 7, 0.0, x7.data_ptr()); used.sync_check()
+    assert m7 == 7
+    xm = torch.empty_like(rhs)
+    its, _ = used.gmres_saddle_multi(rhs.data_ptr(), 3, 200, 1e-9, xm.data_ptr()); used.sync_check()
+    assert all(3 < i < 200 for i in its)
+    if block:
+        r = torch.empty(n3, dtype=torch.float64, device=dev)
+        used.blob_positions(0, nb, r.data_ptr())
+        hw = torch.empty_like(W)
+        used.M_half_W(r.data_ptr(), N, W.data_ptr(), "lanczos_pc", hw.data_ptr()); used.sync_check()
+        assert bool(torch.isfinite(hw).all())
+    fresh = _ctx_4x12(wall, block)
+    got = {}
+    for name, ctx in (("used", used), ("fresh", fresh)):
+        pc, sad = torch.empty_like(v), torch.empty_like(v)
+        ctx.apply_PC(v.data_ptr(), pc.data_ptr()); ctx.sync_check()
+        ctx.apply_saddle(v.data_ptr(), sad.data_ptr()); ctx.sync_check()
+        got[name] = (pc, sad)
+    fresh.close()
+    assert torch.equal(got["used"][0], got["fresh"][0])
+    assert torch.equal(got["used"][1], got["fresh"][1])
+    x7b = torch.empty_like(x)
+    m7b, _ = used.gmres_saddle(rhs[0].data_ptr(), 7, 0.0, x7b.data_ptr()); used.sync_check()
+    used.close()
+    assert m7b == m7 and torch.equal(x7b, x7)
+
+
+def test_no_damp_option_survives_a_preconditioned_root():
+    """RBL_OPT_NO_DAMP belongs to the caller: the preconditioned Lanczos root asks for its undamped products itself and leaves the
+    option as it found it"""
+    import torch
+    nb, nblb = 4, 12
+    N = nb * nblb; n3 = 3 * N
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(49)
+    F = torch.from_numpy(rng.standard_normal(n3)).to(dev)
+    W = torch.from_numpy(rng.standard_normal(n3)).to(dev)
+    out = {}
+    for name in ("used", "fresh"):
+        ctx = _ctx_4x12(True, True)
+        r = torch.empty(n3, dtype=torch.float64, device=dev)
+        ctx.blob_positions(0, nb, r.data_ptr())
+        ctx.set_no_damp(True)
+        if name == "used":
+            hw = torch.empty_like(W)
+            ctx.M_half_W(r.data_ptr(), N, W.data_ptr(), "lanczos_pc", hw.data_ptr()); ctx.sync_check()
+            assert bool(torch.isfinite(hw).all())
+        assert ctx.get_option("no_damp") == 1
+        U = torch.empty_like(F)
+        ctx.apply_M(F.data_ptr(), r.data_ptr(), N, 0, N, U.data_ptr()); ctx.sync_check()
+        out[name] = U
+        ctx.close()
+    assert torch.equal(out["used"], out["fresh"])
