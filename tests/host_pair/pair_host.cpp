@@ -24,12 +24,38 @@ void fast_block(const double *ri, const double *rj, int i, int j, double a, int 
     out9[c] = ux; out9[3 + c] = uy; out9[6 + c] = uz;
   }
 }
+// the same form in radius-scaled coordinates (UNIT = true: what k_apply_M and the velocity-field kernel run)
+void fast_block_unit(const double *ri, const double *rj, int i, int j, double a, int wall, double *out9)
+{
+  const RblParams P = make_params(1.0);
+  const double inv_a = 1.0 / a;
+  const double xi = ri[0] * inv_a, yi = ri[1] * inv_a, zi = ri[2] * inv_a, xj = rj[0] * inv_a, yj = rj[1] * inv_a, zj = rj[2] * inv_a;
+  unsigned flags = 0;
+  for (int c = 0; c < 3; ++c) {
+    double ux = 0, uy = 0, uz = 0;
+    const double fx = c == 0, fy = c == 1, fz = c == 2;
+    if (wall) rbl_pair_accum<true, true, true>(P, xi, yi, zi, xj, yj, zj, fx, fy, fz, i == j, ux, uy, uz, flags);
+    else rbl_pair_accum<false, true, true>(P, xi, yi, zi, xj, yj, zj, fx, fy, fz, i == j, ux, uy, uz, flags);
+    out9[c] = ux; out9[3 + c] = uy; out9[6 + c] = uz;
+  }
+}
+// full ordered block (i <- j, h = z_j) in radius-scaled coordinates (what the MFMA kernel k_apply_M_mrhs forms), row-major, unscaled
+void block_fast_unit(const double *ri, const double *rj, int i, int j, double a, int wall, double *out9)
+{
+  const RblParams P = make_params(1.0);
+  const double inv_a = 1.0 / a;
+  const double xi = ri[0] * inv_a, yi = ri[1] * inv_a, zi = ri[2] * inv_a, xj = rj[0] * inv_a, yj = rj[1] * inv_a, zj = rj[2] * inv_a;
+  unsigned flags = 0;
+  if (wall) rbl_pair_block_fast<true, true, true>(P, xi, yi, zi, xj, yj, zj, i == j, out9, flags);
+  else rbl_pair_block_fast<false, true, true>(P, xi, yi, zi, xj, yj, zj, i == j, out9, flags);
+}
 // symmetric form in radius-scaled coordinates (what k_apply_M_sym runs): M_ij (from U_i += M F_j) and M_ji
 // (from U_j += M^T F_i), both row-major, unscaled
 void sym_blocks(const double *ri, const double *rj, double a, int wall, int nearchk, double *Mij, double *Mji)
 {
   RblParams P = make_params(1.0);
-  const double xi = ri[0] / a, yi = ri[1] / a, zi = ri[2] / a, xj = rj[0] / a, yj = rj[1] / a, zj = rj[2] / a;
+  const double inv_a = 1.0 / a;   // the kernels multiply by P.inv_a
+  const double xi = ri[0] * inv_a, yi = ri[1] * inv_a, zi = ri[2] * inv_a, xj = rj[0] * inv_a, yj = rj[1] * inv_a, zj = rj[2] * inv_a;
   unsigned flags = 0;
   for (int c = 0; c < 3; ++c) {
     const double fx = c == 0, fy = c == 1, fz = c == 2;
