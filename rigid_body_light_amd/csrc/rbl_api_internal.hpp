@@ -6,13 +6,15 @@
 //   rbl_bodies.hip    K operators, preconditioners, per-body factors, saddle operator
 //   rbl_roots.hip     M^{1/2} W: dense Cholesky path and the Lanczos roots
 //   rbl_solvers.hip   GMRES on the saddle operator
-//   rbl_steps.hip     whole time steps, random finite differences
+//   rbl_steps.hip     whole time steps, the stochastic midpoint scheme (free and mixed), random finite differences
 //   rbl_forces.hip    configuration-dependent forces (weight, wall and steric repulsion)
 //   rbl_ensemble.hip  ensembles of independent replicas of one small system
 //   rbl_field.hip     the fluid velocity at arbitrary points from blob forces
-//   rbl_mixed.hip     prescribed kinematics: held or driven bodies among free ones, the loads that takes; their Brownian step
+//   rbl_mixed.hip     prescribed kinematics: held or driven bodies among free ones, the loads that takes; the entry points of their Brownian step
 // None of these symbols is exported from librbl.so.
 #pragma once
+#include <functional>
+
 #include "rbl_internal.hpp"
 
 #pragma GCC visibility push(hidden)
@@ -115,9 +117,15 @@ int gmres_core_with_ops(rbl_ctx *c, const RblSolveOps *ops, const double *d_rhs,
                         double *resid_out);
 
 // ---- rbl_steps.hip ------------------------------------------------------------------------------------------------
-int m_rfd_core(rbl_ctx *c, const double *d_W, const double *Wh, double delta, double *d_out, double *d_r, double *d_work);
-// the same along a given direction dq[6 N_bod] (host); rbl_mixed.hip hands it the direction masked to the free bodies
-int m_rfd_dir(rbl_ctx *c, const double *d_W, const double *dq, double delta, double *d_out, double *d_r, double *d_work);
+// The stochastic midpoint scheme, once for rbl_step_brownian and rbl_step_brownian_mixed (rbl_mixed.hip): the all-free step is the
+// mixed one with no mask (h_mask, d_mask, d_body_in all NULL).  d_s = slip - kBT M_RFD - BI may alias d_slip; d_slip NULL: zero
+int rhs_and_midpoint_core(rbl_ctx *c, const uint8_t *h_mask, const uint8_t *d_mask, const double *d_body_in, const double *d_slip,
+                          const double *d_W, uint64_t seed, int method, int split_rand, double delta, double *d_s, double *X_half,
+                          double *Q_half);
+// the host's noise W (9 N_blobs) into d_W; *d_W = NULL when W is NULL
+int step_upload_W(rbl_ctx *c, const double *W, double **d_W);
+// save q^n, rhs(X_half, Q_half), operators at q^{n+1/2}, solve(U: 6 N_bod, host), back to q^n (also on failure), evolve by dt U
+int step_midpoint(rbl_ctx *c, const std::function<int(double *, double *)> &rhs, const std::function<int(double *)> &solve);
 
 // ---- rbl_forces.hip -----------------------------------------------------------------------------------------------
 // the model's PHYSICAL forces at the context's configuration: d_f (3 N, may be NULL), d_FT = K^T f (6 N_bod, may be NULL),

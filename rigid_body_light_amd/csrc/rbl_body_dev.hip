@@ -94,6 +94,33 @@ __global__ __launch_bounds__(BT) void k_KT_x_Lam(const double *__restrict__ leve
   if (t < 6) out[6 * b + t] = f[t];
 }
 
+// the Brownian step's two body displacements where the blob vectors live: out[0 .. nb6) = K_b^T W_rfd and out[nb6 .. 2 nb6) =
+// K_b^T (M^{1/2}W1), the sums Kinv needs (k_KT_x_Lam's, term for term).  mask (NULL: nobody) marks the prescribed bodies: such a
+// body takes no random displacement -- its RFD slots are 0, its blobs are not read -- and its predictor slots carry its own
+// velocity U_p = body_in
+__global__ __launch_bounds__(BT) void k_mx_bd_sums(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
+                                                   const double *__restrict__ body_in, const double *__restrict__ Wrfd,
+                                                   const double *__restrict__ MW1, int N_blb, long nb6, double *__restrict__ out)
+{
+  __shared__ double s[6][BT];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const size_t o = 6 * (size_t)b;
+  if (mask && mask[b]) {
+    if (t < 6) { out[o + t] = 0.0; out[nb6 + o + t] = body_in[o + t]; }
+    return;
+  }
+  double f[6] = {0, 0, 0, 0, 0, 0}, g[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = t; k < N_blb; k += BT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    const double *l = lever + idx;
+    rbl_KT_acc(l, Wrfd[idx], Wrfd[idx + 1], Wrfd[idx + 2], f);
+    rbl_KT_acc(l, MW1[idx], MW1[idx + 1], MW1[idx + 2], g);
+  }
+  block_reduce<6>(f, s, t);
+  block_reduce<6>(g, s, t);
+  if (t < 6) { out[o + t] = f[t]; out[nb6 + o + t] = g[t]; }
+}
+
 // diag_invM (:489-543) + Ninv = K^T invM K per body and its Cholesky (:593-594, :554-567)
 template <bool WALL>
 __global__ __launch_bounds__(BT) void k_pc_diag_build(const double *__restrict__ lever,
@@ -796,6 +823,13 @@ void rbl_launch_KT_x_Lam(hipStream_t st, const double *d_lever, const double *d_
 {
   if (N_bod <= 0) return;
   hipLaunchKernelGGL(k_KT_x_Lam, dim3(N_bod), dim3(BT), 0, st, d_lever, d_lam, N_blb, d_out);
+}
+
+void rbl_launch_mx_bd_sums(hipStream_t st, const double *d_lever, const uint8_t *d_mask, const double *d_body_in, const double *d_Wrfd,
+                           const double *d_MW1, int N_blb, int N_bod, double *d_out)
+{
+  if (N_bod <= 0) return;
+  hipLaunchKernelGGL(k_mx_bd_sums, dim3(N_bod), dim3(BT), 0, st, d_lever, d_mask, d_body_in, d_Wrfd, d_MW1, N_blb, 6L * N_bod, d_out);
 }
 
 void rbl_launch_pc_diag_build(hipStream_t st, const RblParams &P, bool wall, const double *d_lever,

@@ -22,8 +22,9 @@
 // Replicas never interact: the pair sweeps are per replica, the force model's neighbour lists stop at the replica's bodies.
 //
 // With prescribed bodies (rbl_ensemble_solve_mixed / _step_mixed / _step_brownian_mixed; the semantics of include/rbl.h section 7
-// per replica, the restatement of rbl_mixed.hip's mx_solve / mx_step / mx_bd_rhs): a 0/1 mask per body and replica travels with the
-// call.  The same launches with three differences: k_ens_midpoint is followed by k_ens_midpoint_prescribed (dq = 0 and the predictor
+// per replica, the restatement of rbl_mixed.hip's mx_solve / mx_step and of rbl_steps.hip's rhs_and_midpoint_core): a 0/1 mask per
+// body and replica travels with the call, and NULL for it is the unmasked step: ens_step_det and ens_step_bd serve both.
+// The same launches with three differences: k_ens_midpoint is followed by k_ens_midpoint_prescribed (dq = 0 and the predictor
 // (dt/2) U_p on a prescribed body; one more launch, so that a free body goes through the very same code), the solve is the
 // masked k_gmres_small (it adds K_p U_p to the right-hand side with the lever arms of the configuration it solves at, zeroes
 // the prescribed bodies' balance rows and splits the solution into U and F per body), and
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(ET) void k_ens_midpoint(int nbod, int Nb, int nbl, 
 
 // k_ens_midpoint with prescribed bodies (mask[nbod], body_in[6 nbod]) is k_ens_midpoint itself on every body, then this kernel
 // on the prescribed ones: such a body takes no random displacement -- dq = 0 -- and sits at q^n + (dt/2) U_p in the predictor
-// (k_mx_bd_sums and the host loop of mx_bd_rhs, rbl_mixed.hip).  One kernel with the two cases as branches was tried: the
+// (k_mx_bd_sums, rbl_body_dev.hip, and the host loop of rhs_and_midpoint_core, rbl_steps.hip).  One kernel with the two cases as branches was tried: the
 // compiler joins the branches' common tail (the update), scale * u of a free body then no longer fuses into X + u as it does
 // in k_ens_midpoint, and a free body's configuration differs in the last bit from the unmasked step's.  Running the unmasked
 // kernel gives the same bits by construction, for one more small launch per step
@@ -457,37 +458,33 @@ int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const d
   return RBL_OK;
 }
 
-// workspace, mask and the step's uploads (ens_begin with body_in where F_body goes)
-int ens_mx_begin(rbl_ctx *c, EnsWork *w, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, bool model,
-                 const double **FT)
+// the deterministic step of every replica (checks and ens_ready done by the caller).  prescribed == NULL:
+// rbl_ensemble_step_deterministic -- the unmasked solver, lambda, U and F NULL; otherwise body_in stands where F_body stands and
+// the solve is the masked one.  move = false: the solve alone, at the current configuration and without the model's loads
+// (rbl_ensemble_solve_mixed)
+int ens_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, int max_iter, double rtol, bool move,
+                 double *lambda, double *U, double *F, int *iters, double *resid)
 {
-  int rc = ens_ready(c); if (rc) return rc;
-  if ((rc = ens_work(c, max_iter, w))) return rc;
-  if ((rc = copy_h2d(c, w->mask, prescribed, (size_t)c->ens_R * c->ens_Nb))) return rc;
-  return ens_begin(c, *w, body_in, slip, FT, model);     // model = false: the solve at the current configuration takes no model
-                                                         // loads (rbl_solve_mixed)
-}
-
-int ens_mx_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol, bool move,
-                    double *lambda, double *U, double *F, int *iters, double *resid)
-{
+  const bool mixed = prescribed != nullptr;
   EnsWork w;
   const double *FT;
-  int rc = ens_mx_begin(c, &w, prescribed, body_in, slip, max_iter, move, &FT); if (rc) return rc;
+  int rc = ens_work(c, max_iter, &w); if (rc) return rc;
+  if (mixed && (rc = copy_h2d(c, w.mask, prescribed, (size_t)c->ens_R * c->ens_Nb))) return rc;
+  if ((rc = ens_begin(c, w, F_body, slip, &FT, move))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb;
   const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb;
   const long tot = (long)R * (n3 + nb6);
   hipLaunchKernelGGL(k_ens_rhs_det, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, n3, nb6,
                      slip ? (const double *)w.slip : nullptr, (const double *)w.F, FT, w.rhs);
-  if ((rc = ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, true, move))) return rc;
+  if ((rc = ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, mixed, move))) return rc;
   std::vector<double> x;
   if (lambda) {                                          // the blob forces: the top of every replica's solution
     x.resize((size_t)R * (n3 + nb6));
     if ((rc = copy_d2h(c, x.data(), w.x, sizeof(double) * x.size()))) return rc;
   }
   std::vector<double> Ft;
-  if (!F) { Ft.resize((size_t)R * nb6); F = Ft.data(); }                  // the masked read-back is chosen by U or F
-  if ((rc = ens_finish(c, w, R, iters, resid, move, U, F))) return rc;
+  if (mixed && !F) { Ft.resize((size_t)R * nb6); F = Ft.data(); }         // the masked read-back is chosen by U or F
+  if ((rc = ens_finish(c, w, R, iters, resid, move, mixed ? U : nullptr, mixed ? F : nullptr))) return rc;
   if (lambda)
     for (int r = 0; r < R; ++r) std::memcpy(lambda + (size_t)r * n3, x.data() + (size_t)r * (n3 + nb6), sizeof(double) * n3);
   return RBL_OK;
@@ -622,17 +619,7 @@ int rbl_ensemble_step_deterministic(rbl_ctx *c, const double *F_body, const doub
   int rc = ens_ready(c); if (rc) return rc;
   if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_deterministic: F_body is NULL");
   if ((rc = ens_check_solver(c, max_iter))) return rc;
-  EnsWork w;
-  if ((rc = ens_work(c, max_iter, &w))) return rc;
-  const int R = c->ens_R, Nb = c->ens_Nb;
-  const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb;
-  const double *FT;
-  if ((rc = ens_begin(c, w, F_body, slip, &FT))) return rc;
-  const long tot = (long)R * (n3 + nb6);
-  hipLaunchKernelGGL(k_ens_rhs_det, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, n3, nb6,
-                     slip ? (const double *)w.slip : nullptr, (const double *)w.F, FT, w.rhs);
-  if ((rc = ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol))) return rc;
-  return ens_finish(c, w, R, iters, resid, true);
+  return ens_step_det(c, nullptr, F_body, slip, max_iter, rtol, true, nullptr, nullptr, nullptr, iters, resid);
 }
 
 int rbl_ensemble_step_brownian(rbl_ctx *c, const double *F_body, const double *slip, const double *W, uint64_t seed,
@@ -655,7 +642,8 @@ int rbl_ensemble_solve_mixed(rbl_ctx *c, const uint8_t *prescribed, const double
   if (!c) return RBL_ERR_ARG;
   int rc = ens_mx_check(c, "ensemble_solve_mixed", prescribed, body_in, max_iter, rtol); if (rc) return rc;
   if (!U || !F) return rbl_fail(c, RBL_ERR_ARG, "ensemble_solve_mixed: U or F is NULL");
-  return ens_mx_step_det(c, prescribed, body_in, slip, max_iter, rtol, false, lambda, U, F, iters, resid);
+  if ((rc = ens_ready(c))) return rc;
+  return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, false, lambda, U, F, iters, resid);
 }
 
 int rbl_ensemble_step_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
@@ -663,7 +651,8 @@ int rbl_ensemble_step_mixed(rbl_ctx *c, const uint8_t *prescribed, const double 
 {
   if (!c) return RBL_ERR_ARG;
   int rc = ens_mx_check(c, "ensemble_step_mixed", prescribed, body_in, max_iter, rtol); if (rc) return rc;
-  return ens_mx_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
+  if ((rc = ens_ready(c))) return rc;
+  return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
 }
 
 int rbl_ensemble_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
@@ -673,10 +662,11 @@ int rbl_ensemble_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, cons
   if (!c) return RBL_ERR_ARG;
   int rc = ens_mx_check(c, "ensemble_step_brownian_mixed", prescribed, body_in, max_iter, rtol); if (rc) return rc;
   const RblBodyState &S = c->S;
-  if (!(S.kBT > 1e-10))                                // no Brownian terms: the deterministic mixed step (as rbl_step_brownian_mixed)
-    return ens_mx_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
-  if (!(S.dt > 0.0) || !(delta > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_brownian_mixed: dt and delta must be positive");
+  const bool brownian = S.kBT > 1e-10;                 // no Brownian terms: the deterministic mixed step (as rbl_step_brownian_mixed)
+  if (brownian && (!(S.dt > 0.0) || !(delta > 0.0)))
+    return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_brownian_mixed: dt and delta must be positive");
   if ((rc = ens_ready(c))) return rc;
+  if (!brownian) return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
   return ens_step_bd(c, prescribed, body_in, slip, W, seed, split_rand, delta, max_iter, rtol, F, iters, resid);
 }
 

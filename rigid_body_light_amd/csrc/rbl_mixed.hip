@@ -10,7 +10,10 @@
 // branch on it is uniform), deterministic LDS tree sums, no atomics; the K / K^T formulas, the workgroup sum and the 6 x 6
 // substitution are rbl_body_dev.hpp's, shared with rbl_body_dev.hip.  The Arnoldi recurrence, the Hessenberg solve and the
 // convergence test are gmres_core's (gmres_core_with_ops).
-#include <cmath>
+//
+// The Brownian midpoint step with prescribed bodies has its entry points here and nothing of the scheme: right-hand side, predictor
+// and the sequence of the step are rbl_steps.hip's (rhs_and_midpoint_core, step_midpoint), which the all-free step goes through with
+// no mask; this file hands them the mask and mx_solve.
 #include <cstring>
 #include <vector>
 
@@ -201,32 +204,6 @@ __global__ void k_mx_add_free(const uint8_t *__restrict__ mask, const double *__
   if (i < nb6 && !mask[i / 6]) v[i] += add[i];
 }
 
-// the Brownian step's two body displacements, masked where the blob vectors live: out[0 .. nb6) = K_b^T W_rfd and
-// out[nb6 .. 2 nb6) = K_b^T (M^{1/2}W1) on a free body (the sums Kinv needs); a prescribed body takes no random displacement -- its
-// RFD slots are 0, its blobs are not read -- and its predictor slots carry its own velocity U_p
-__global__ __launch_bounds__(MT) void k_mx_bd_sums(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
-                                                   const double *__restrict__ body_in, const double *__restrict__ Wrfd,
-                                                   const double *__restrict__ MW1, int N_blb, long nb6, double *__restrict__ out)
-{
-  __shared__ double s[6][MT];
-  const int b = blockIdx.x, t = threadIdx.x;
-  const size_t o = 6 * (size_t)b;
-  if (mask[b]) {
-    if (t < 6) { out[o + t] = 0.0; out[nb6 + o + t] = body_in[o + t]; }
-    return;
-  }
-  double f[6] = {0, 0, 0, 0, 0, 0}, g[6] = {0, 0, 0, 0, 0, 0};
-  for (int k = t; k < N_blb; k += MT) {
-    const size_t idx = 3 * ((size_t)b * N_blb + k);
-    const double *l = lever + idx;
-    rbl_KT_acc(l, Wrfd[idx], Wrfd[idx + 1], Wrfd[idx + 2], f);
-    rbl_KT_acc(l, MW1[idx], MW1[idx + 1], MW1[idx + 2], g);
-  }
-  rbl_block_sum<6, MT>(f, s, t);
-  rbl_block_sum<6, MT>(g, s, t);
-  if (t < 6) { out[o + t] = f[t]; out[nb6 + o + t] = g[t]; }
-}
-
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 
 struct MxBuf {           // the one workspace of a section 7 entry point (rbl_ctx::d_mx)
@@ -378,56 +355,7 @@ int mx_step(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double
   return rbl_evolve_X_Q(c, U.data());
 }
 
-// ---- the Brownian midpoint step with prescribed bodies ------------------------------------------------------------------------------
-
-// Right-hand side and predictor at q^n (kBT > 1e-10, dt > 0, delta > 0 checked by the caller): rbl_RHS_and_Midpoint_dev with the
-// RFD direction and the random part of the predictor masked to the free bodies, a prescribed body displaced by (dt/2) U_p.
-// d_mask, d_body_in, d_slip (NULL: zero) and d_W ([W1 | W2 | W_rfd], NULL: drawn from seed) are device vectors, h_mask the host's
-// copy of the mask; d_s (3 N_blobs, may be d_slip) = slip - kBT M_RFD - BI.  The square roots, the RFD products and the combined
-// right-hand side are the all-free step's own; one read-back of 12 numbers per body.
-int mx_bd_rhs(rbl_ctx *c, const uint8_t *h_mask, const uint8_t *d_mask, const double *d_body_in, const double *d_slip, const double *d_W,
-              uint64_t seed, int method, int split_rand, double delta, double *d_s, double *X_half, double *Q_half)
-{
-  RblBodyState &S = c->S;
-  const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N, nb6 = (int64_t)6 * S.N_bod;
-  const size_t vb = sizeof(double) * (size_t)n3;
-  // workspace as rbl_RHS_and_Midpoint_dev: [W1 | W2 | W_rfd] (when drawn here), M^{1/2}W1, M^{1/2}W2, M_RFD, positions, 2 scratch
-  int rc = rbl_dev_reserve(c, c->d_bd, 9 * vb + 2 * sizeof(double) * (size_t)nb6); if (rc) return rc;
-  double *base = (double *)c->d_bd.p;
-  double *dWown = base, *dMW = base + 3 * n3, *dRFD = base + 5 * n3, *dr = base + 6 * n3, *dwork = base + 7 * n3, *dt12 = base + 9 * n3;
-  if (!d_W) {
-    rbl_launch_normal(c->stream, seed, 0, 3 * n3, dWown);
-    d_W = dWown;
-  }
-  if ((rc = positions_dev(c, 0, S.N_bod, dr))) return rc;
-  if ((rc = mhalf_dev_multi(c, dr, N, d_W, split_rand ? 2 : 1, method, dMW))) return rc;    // M is all blobs': the mask does not enter
-  if ((rc = sync_bodies(c))) return rc;                                                    // lever arms of q^n
-  hipLaunchKernelGGL(k_mx_bd_sums, dim3((unsigned)S.N_bod), dim3(MT), 0, c->stream, (const double *)c->d_lever.p, d_mask, d_body_in,
-                     d_W + 2 * n3, (const double *)dMW, S.N_blb, (long)nb6, dt12);
-  std::vector<double> t((size_t)(2 * nb6)), dq((size_t)nb6), pre((size_t)nb6), Xo, Qo;
-  if ((rc = read_back(c, t.data(), dt12, sizeof(double) * t.size()))) return rc;
-  const double c1 = split_rand ? 2.0 * std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);
-  const double c2 = split_rand ? std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);
-  for (int b = 0; b < S.N_bod; ++b) {
-    const double *Kb = &S.KTKinv[(size_t)36 * b], *tr = t.data() + 6 * (size_t)b, *tp = tr + nb6;
-    for (int p = 0; p < 6; ++p) {
-      double sr = 0.0, sp = 0.0;
-      for (int q = 0; q < 6; ++q) { sr += Kb[6 * p + q] * tr[q]; sp += Kb[6 * p + q] * tp[q]; }
-      dq[6 * (size_t)b + p] = h_mask[b] ? 0.0 : sr;                                        // D_f Kinv W_rfd
-      pre[6 * (size_t)b + p] = 0.5 * S.dt * (h_mask[b] ? tp[p] : c1 * sp);                 // D_p (dt/2) U_p + D_f (dt/2) c1 Kinv M^{1/2}W1
-    }
-  }
-  if ((rc = m_rfd_dir(c, d_W + 2 * n3, dq.data(), delta, dRFD, dr, dwork))) return rc;
-  if (!d_slip) {
-    RBL_HIP(c, hipMemsetAsync(d_s, 0, vb, c->stream));
-    d_slip = d_s;
-  }
-  rbl_launch_rhs_combine(c->stream, n3, d_slip, S.kBT, dRFD, c2, dMW, split_rand ? dMW + n3 : nullptr, d_s);
-  rbl_body_update_X_Q(S, pre.data(), Xo, Qo);
-  std::memcpy(X_half, Xo.data(), sizeof(double) * Xo.size());
-  std::memcpy(Q_half, Qo.data(), sizeof(double) * Qo.size());
-  return finish_and_check(c);                                                              // as rbl_RHS_and_Midpoint_dev ends
-}
+// ---- the Brownian midpoint step with prescribed bodies: the scheme is rbl_steps.hip's (rhs_and_midpoint_core, step_midpoint) ---------
 
 // the checks of the two right-hand-side forms and of the step, none of which needs a device
 int mx_bd_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const void *body_in, int max_iter, double rtol, double delta,
@@ -497,19 +425,14 @@ int rbl_RHS_and_Midpoint_mixed_dev(rbl_ctx *c, const uint8_t *prescribed, const 
   int np = 0;
   int rc = mx_bd_check(c, "RHS_and_Midpoint_mixed_dev", prescribed, d_body_in, 1, 0.0, delta, &np); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
-  RblBodyState &S = c->S;
-  const size_t vb = sizeof(double) * 3 * (size_t)S.N_bod * (size_t)S.N_blb;
-  if (!(S.kBT > 1e-10)) {                                // no Brownian terms, as rbl_RHS_and_Midpoint_dev
-    if (!d_slip) RBL_HIP(c, hipMemsetAsync(d_s, 0, vb, c->stream));
-    else if (d_slip != d_s) RBL_HIP(c, hipMemcpyAsync(d_s, d_slip, vb, hipMemcpyDeviceToDevice, c->stream));
-    std::memcpy(X_half, S.X.data(), sizeof(double) * S.X.size());
-    std::memcpy(Q_half, S.Q.data(), sizeof(double) * S.Q.size());
-    return finish_and_check(c);
+  const uint8_t *d_mask = nullptr;
+  if (c->S.kBT > 1e-10) {                                // without Brownian terms the mask is not read: no workspace for it
+    MxBuf B;
+    if ((rc = mx_reserve(c, B))) return rc;
+    if ((rc = copy_h2d(c, B.mask, prescribed, (size_t)c->S.N_bod))) return rc;
+    d_mask = B.mask;
   }
-  MxBuf B;
-  if ((rc = mx_reserve(c, B))) return rc;
-  if ((rc = copy_h2d(c, B.mask, prescribed, (size_t)S.N_bod))) return rc;
-  return mx_bd_rhs(c, prescribed, B.mask, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s, X_half, Q_half);
+  return rhs_and_midpoint_core(c, prescribed, d_mask, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s, X_half, Q_half);
 }
 
 int rbl_RHS_and_Midpoint_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
@@ -542,29 +465,21 @@ int rbl_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, const double 
   if (!(c->S.kBT > 1e-10))                               // no Brownian terms: the deterministic step (as rbl_step_brownian, :967-970)
     return mx_step(c, "step_brownian_mixed", prescribed, body_in, slip, max_iter, rtol, F, iters, resid);
   if ((rc = rbl_dev_init(c))) return rc;
-  const int Nb = c->S.N_bod;
-  const size_t nb6 = 6 * (size_t)Nb, n3 = 3 * (size_t)Nb * (size_t)c->S.N_blb;
+  const size_t nb6 = 6 * (size_t)c->S.N_bod;
   MxBuf B;
+  double *dW;
   if ((rc = mx_upload(c, B, prescribed, body_in, slip, true, np))) return rc;      // the force model at q^n, free bodies only
-  double *dW = nullptr;
-  if (W) {
-    if ((rc = rbl_dev_reserve(c, c->d_W, sizeof(double) * 3 * n3))) return rc;
-    dW = (double *)c->d_W.p;
-    if ((rc = copy_h2d(c, dW, W, sizeof(double) * 3 * n3))) return rc;
-  }
-  c->step_hist_n = 0;
-  const std::vector<double> Xn = c->S.X, Qn = c->S.Q;
-  std::vector<double> Xh((size_t)3 * Nb), Qh((size_t)4 * Nb), U(nb6);
-  // s takes the slip's place in the solve's workspace: it never leaves the device
-  if ((rc = mx_bd_rhs(c, prescribed, B.mask, B.body_in, slip ? B.slip : nullptr, dW, seed, method, split_rand, delta, B.slip, Xh.data(),
-                      Qh.data()))) return rc;
-  if ((rc = rbl_set_config(c, Xh.data(), Qh.data(), Nb))) return rc;               // operators and lever arms at q^{n+1/2}
-  rc = mx_solve(c, B, true, np, max_iter, rtol, iters, resid);
-  if (!rc) rc = copy_d2h(c, U.data(), B.U, sizeof(double) * nb6);
-  if (!rc && F) rc = copy_d2h(c, F, B.F, sizeof(double) * nb6);
-  if (!rc) rc = finish_and_check(c);
-  const int rc2 = rbl_set_config(c, Xn.data(), Qn.data(), Nb);                     // the update starts from q^n (also on failure)
-  if (rc) return rc;
-  if (rc2) return rc2;
-  return rbl_evolve_X_Q(c, U.data());
+  if ((rc = step_upload_W(c, W, &dW))) return rc;
+  return step_midpoint(
+      c,
+      [&](double *Xh, double *Qh) {                       // s takes the slip's place in the solve's workspace: it never leaves the device
+        return rhs_and_midpoint_core(c, prescribed, B.mask, B.body_in, slip ? B.slip : nullptr, dW, seed, method, split_rand, delta, B.slip,
+                                     Xh, Qh);
+      },
+      [&](double *U) {
+        int r = mx_solve(c, B, true, np, max_iter, rtol, iters, resid);
+        if (!r) r = copy_d2h(c, U, B.U, sizeof(double) * nb6);
+        if (!r && F) r = copy_d2h(c, F, B.F, sizeof(double) * nb6);
+        return r ? r : finish_and_check(c);
+      });
 }

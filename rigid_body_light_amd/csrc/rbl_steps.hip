@@ -1,6 +1,11 @@
 // rbl_steps.hip -- whole time steps and the random-finite-difference family (reference C++-only members).
 // Part of the implementation of the C ABI in include/rbl.h (split from the former rbl_api.hip along its sections);
 // shared internals are declared in rbl_api_internal.hpp.  Nothing here falls back to a CPU path.
+//
+// The stochastic midpoint scheme stands here once, for the all-free step and for the one with prescribed bodies (rbl_mixed.hip,
+// which passes its mask and its solver): rhs_and_midpoint_core (right-hand side and predictor at q^n) and step_midpoint (save q^n,
+// operators at q^{n+1/2}, solve, back to q^n, evolve).  So do the two ways of displacing by +- (delta/2) dq that the RFD family
+// needs: at_displaced_config (the context's own configuration, restored afterwards) and on_displaced_copies (a copy of the body state).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -67,129 +72,158 @@ int rbl_step_deterministic(rbl_ctx *c, const double *F_body, const double *slip,
   return rbl_evolve_X_Q(c, U.data());
 }
 
-// One stochastic midpoint step: right-hand side and predictor configuration at q^n (rbl_RHS_and_Midpoint_dev,
-// reference :917-976), saddle solve at q^{n+1/2}, update from q^n with dt U.  W: host, [W1 | W2 | W_rfd] = 9 N_blobs
-// standard normals, or NULL to draw them from `seed`.
-int rbl_step_brownian(rbl_ctx *c, const double *F_body, const double *slip, const double *W, uint64_t seed, int method,
-                      int split_rand, double delta, int max_iter, double rtol, int *iters, double *resid)
+// the noise of a stochastic step on the device: *d_W = the host's W = [W1 | W2 | W_rfd] (9 N_blobs) uploaded into d_W, or NULL
+// when W is NULL (the right-hand side then draws it from the seed)
+int step_upload_W(rbl_ctx *c, const double *W, double **d_W)
 {
-  int rc = need_K(c); if (rc) return rc;
-  if ((rc = rbl_dev_init(c))) return rc;
-  if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "step_brownian: F_body is NULL");
+  *d_W = nullptr;
+  if (!W) return RBL_OK;
+  const size_t bytes = sizeof(double) * 9 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
+  int rc = rbl_dev_reserve(c, c->d_W, bytes); if (rc) return rc;
+  *d_W = (double *)c->d_W.p;
+  return copy_h2d(c, *d_W, W, bytes);
+}
+
+// The stochastic midpoint scheme around its two solver-specific parts (reference :917-976): rhs(X_half, Q_half) leaves the
+// right-hand side of q^n on the device and returns the predictor configuration; solve(U) solves at q^{n+1/2} and brings the body
+// velocities (6 N_bod) to the host.  The update starts from q^n with dt U.
+int step_midpoint(rbl_ctx *c, const std::function<int(double *, double *)> &rhs, const std::function<int(double *)> &solve)
+{
   const int Nb = c->S.N_bod;
-  const int64_t n3 = (int64_t)3 * Nb * c->S.N_blb, nb6 = (int64_t)6 * Nb;
-  double *rhs, *x, *dslip, *dforce;
-  if ((rc = step_buffers(c, n3, nb6, &rhs, &x, &dslip, &dforce))) return rc;
   c->step_hist_n = 0;                                       // the random part of the solution does not carry over
-  if (slip) { if ((rc = copy_h2d(c, dslip, slip, sizeof(double) * (size_t)n3))) return rc; }
-  else RBL_HIP(c, hipMemsetAsync(dslip, 0, sizeof(double) * (size_t)n3, c->stream));
-  if ((rc = copy_h2d(c, dforce, F_body, sizeof(double) * (size_t)nb6))) return rc;
-  if ((rc = ia_add_to_step_force(c, dforce))) return rc;             // the force model at q^n, where RHS_and_Midpoint takes its Force
-  double *dW = nullptr;
-  if (W) {
-    if ((rc = rbl_dev_reserve(c, c->d_W, sizeof(double) * 3 * (size_t)n3))) return rc;
-    dW = (double *)c->d_W.p;
-    if ((rc = copy_h2d(c, dW, W, sizeof(double) * 3 * (size_t)n3))) return rc;
-  }
   const std::vector<double> Xn = c->S.X, Qn = c->S.Q;
-  std::vector<double> Xh((size_t)3 * Nb), Qh((size_t)4 * Nb);
-  if ((rc = rbl_RHS_and_Midpoint_dev(c, dslip, dforce, dW, seed, method, split_rand, delta, rhs, Xh.data(), Qh.data())))
-    return rc;
-  if ((rc = rbl_set_config(c, Xh.data(), Qh.data(), Nb))) return rc;       // operators at the predictor configuration
-  rc = rbl_gmres_saddle_dev(c, rhs, max_iter, rtol, x, 0, iters, resid);
-  std::vector<double> U((size_t)nb6);
-  if (!rc) rc = copy_d2h(c, U.data(), x + n3, sizeof(double) * (size_t)nb6);
-  if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = RBL_ERR_HIP;
+  std::vector<double> Xh((size_t)3 * Nb), Qh((size_t)4 * Nb), U((size_t)6 * Nb);
+  int rc = rhs(Xh.data(), Qh.data()); if (rc) return rc;
+  if ((rc = rbl_set_config(c, Xh.data(), Qh.data(), Nb))) return rc;       // operators and lever arms at q^{n+1/2}
+  rc = solve(U.data());
   const int rc2 = rbl_set_config(c, Xn.data(), Qn.data(), Nb);              // the update starts from q^n (also on failure)
   if (rc) return rc;
   if (rc2) return rc2;
   return rbl_evolve_X_Q(c, U.data());
 }
 
+// One stochastic midpoint step: right-hand side and predictor configuration at q^n (rbl_RHS_and_Midpoint_dev), saddle solve at
+// q^{n+1/2} (step_midpoint).  W: host, [W1 | W2 | W_rfd] = 9 N_blobs standard normals, or NULL to draw them from `seed`.
+int rbl_step_brownian(rbl_ctx *c, const double *F_body, const double *slip, const double *W, uint64_t seed, int method,
+                      int split_rand, double delta, int max_iter, double rtol, int *iters, double *resid)
+{
+  int rc = need_K(c); if (rc) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "step_brownian: F_body is NULL");
+  const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb, nb6 = (int64_t)6 * c->S.N_bod;
+  double *rhs, *x, *dslip, *dforce, *dW;
+  if ((rc = step_buffers(c, n3, nb6, &rhs, &x, &dslip, &dforce))) return rc;
+  if (slip) { if ((rc = copy_h2d(c, dslip, slip, sizeof(double) * (size_t)n3))) return rc; }
+  else RBL_HIP(c, hipMemsetAsync(dslip, 0, sizeof(double) * (size_t)n3, c->stream));
+  if ((rc = copy_h2d(c, dforce, F_body, sizeof(double) * (size_t)nb6))) return rc;
+  if ((rc = ia_add_to_step_force(c, dforce))) return rc;             // the force model at q^n, where RHS_and_Midpoint takes its Force
+  if ((rc = step_upload_W(c, W, &dW))) return rc;
+  return step_midpoint(
+      c,
+      [&](double *Xh, double *Qh) { return rbl_RHS_and_Midpoint_dev(c, dslip, dforce, dW, seed, method, split_rand, delta, rhs, Xh, Qh); },
+      [&](double *U) {
+        int r = rbl_gmres_saddle_dev(c, rhs, max_iter, rtol, x, 0, iters, resid);
+        if (!r) r = copy_d2h(c, U, x + n3, sizeof(double) * (size_t)nb6);
+        if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = RBL_ERR_HIP;
+        return r;
+      });
+}
+
 // ---- random finite differences (reference C++-only members) ---------------
 
-// d_out = (1/delta)[M(q + delta/2 dq) - M(q - delta/2 dq)] W for a displacement direction dq[6 N_bod] (host): the shared core of
-// M_RFD (:776-794, dq = Kinv W) and M_RFD_from_U (:820-842, dq = the caller's U).  d_r: n3 scratch, d_work: 2 n3 scratch.
-int m_rfd_dir(rbl_ctx *c, const double *d_W, const double *dq, double delta, double *d_out, double *d_r, double *d_work)
+// f(0) with the context's configuration at q + (delta/2) dq, then f(1) at q - (delta/2) dq (dq[6 N_bod], host; :783-788); q and
+// the validity of its device copy are restored after each, whatever f returns.  The first failure ends it.
+template <class Fn>
+static int at_displaced_config(rbl_ctx *c, const double *dq, double delta, Fn &&f)
 {
-  RblPhase ph_total(c, RBL_T_TOTAL);
   RblBodyState &S = c->S;
-  const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N;
   std::vector<double> win((size_t)6 * S.N_bod), Xs, Qs;
   const std::vector<double> X0 = S.X, Q0 = S.Q;
-  double *dM[2] = {d_work, d_work + n3};
-  int rc = RBL_OK;
-  for (int sgn = 0; sgn < 2; ++sgn) {                                 // q +- delta/2 dq (:783-788)
-    const double f = (sgn == 0 ? 0.5 : -0.5) * delta;
-    for (size_t i = 0; i < win.size(); ++i) win[i] = f * dq[i];
+  for (int sgn = 0; sgn < 2; ++sgn) {
+    const double h = (sgn == 0 ? 0.5 : -0.5) * delta;
+    for (size_t i = 0; i < win.size(); ++i) win[i] = h * dq[i];
     rbl_body_update_X_Q(S, win.data(), Xs, Qs);
     S.X = Xs; S.Q = Qs; c->dev_xq_valid = false;                      // displaced configuration, temporarily
-    rc = positions_dev(c, 0, S.N_bod, d_r);
-    if (!rc) rc = apply_M_enqueue(c, S.wall, d_W, d_r, N, 0, N, dM[sgn]);   // :790-791
+    const int rc = f(sgn);
     S.X = X0; S.Q = Q0; c->dev_xq_valid = false;
     if (rc) return rc;
   }
+  return RBL_OK;
+}
+
+// The same on a copy of the body state with its K built (the host-side differences, :755-761, :853-859): f(T, w) with T at
+// q + (delta/2) dq and w = 1/delta, then at q - (delta/2) dq with w = -1/delta.  The context is not touched.
+template <class Fn>
+static int on_displaced_copies(rbl_ctx *c, const double *dq, double delta, Fn &&f)
+{
+  const RblBodyState &S = c->S;
+  std::vector<double> win((size_t)6 * S.N_bod);
+  for (int sgn = 0; sgn < 2; ++sgn) {
+    const double h = (sgn == 0 ? 0.5 : -0.5) * delta;
+    for (size_t i = 0; i < win.size(); ++i) win[i] = h * dq[i];
+    RblBodyState T = S;
+    rbl_body_update_X_Q(S, win.data(), T.X, T.Q);
+    const int rc = rbl_body_set_K(T, c->last_error); if (rc) return rc;
+    f(T, (sgn == 0 ? 1.0 : -1.0) / delta);
+  }
+  return RBL_OK;
+}
+
+// d_out = (1/delta)[M(q + delta/2 dq) - M(q - delta/2 dq)] W for a displacement direction dq[6 N_bod] (host): the shared core of
+// M_RFD (:776-794, dq = Kinv W), M_RFD_from_U (:820-842, dq = the caller's U) and the stochastic right-hand side (dq masked to
+// the free bodies).  d_r: n3 scratch, d_work: 2 n3 scratch.
+static int m_rfd_dir(rbl_ctx *c, const double *d_W, const double *dq, double delta, double *d_out, double *d_r, double *d_work)
+{
+  RblPhase ph_total(c, RBL_T_TOTAL);
+  const int64_t N = (int64_t)c->S.N_bod * c->S.N_blb, n3 = 3 * N;
+  double *dM[2] = {d_work, d_work + n3};
+  const int rc = at_displaced_config(c, dq, delta, [&](int sgn) {
+    const int r = positions_dev(c, 0, c->S.N_bod, d_r);
+    return r ? r : apply_M_enqueue(c, c->S.wall, d_W, d_r, N, 0, N, dM[sgn]);          // :790-791
+  });
+  if (rc) return rc;
   rbl_launch_axpby(c->stream, n3, 1.0 / delta, dM[0], -1.0 / delta, dM[1], d_out);   // :793
   return RBL_OK;
 }
 
-// core of M_RFD(), c_rigid_obj.cpp:776-794: dq = Kinv W.  Wh = host copy of W (Kinv is O(N) host work)
-int m_rfd_core(rbl_ctx *c, const double *d_W, const double *Wh, double delta, double *d_out, double *d_r, double *d_work)
+// M_RFD (U == NULL: along Kinv W; W == NULL: drawn from the seed) and M_RFD_from_U (along the caller's U), checks done: W up, the two
+// products on the GPU at the two displaced configurations, the quotient down
+static int m_rfd_host(rbl_ctx *c, const double *W, uint64_t seed, const double *U, double delta, double *out)
 {
-  std::vector<double> uom((size_t)6 * c->S.N_bod);
-  rbl_body_Kinv_x_V(c->S, Wh, uom.data());                            // UOM = Kinv W (:776)
-  return m_rfd_dir(c, d_W, uom.data(), delta, d_out, d_r, d_work);
-}
-
-// uom_v = Kinv V_v = (K^T K)^-1 K^T V_v for nv device vectors: the sums over the blobs on the device (one launch each), the
-// 6 x 6 blocks on the host after ONE small read-back -- instead of bringing the 3 N-vectors to the host (reference :408)
-static int kinv_dev(rbl_ctx *c, const double *const *d_V, int nv, double *d_t, std::vector<double> *uom)
-{
-  int rc = sync_bodies(c); if (rc) return rc;
-  const RblBodyState &S = c->S;
-  const size_t nb6 = (size_t)6 * S.N_bod;
-  for (int v = 0; v < nv; ++v) rbl_launch_KT_x_Lam(c->stream, (const double *)c->d_lever.p, d_V[v], S.N_blb, S.N_bod, d_t + (size_t)v * nb6);
-  std::vector<double> t(nb6 * (size_t)nv);
-  if ((rc = read_back(c, t.data(), d_t, sizeof(double) * t.size()))) return rc;
-  for (int v = 0; v < nv; ++v) {
-    uom[v].assign(nb6, 0.0);
-    for (int b = 0; b < S.N_bod; ++b) {
-      const double *B = &S.KTKinv[(size_t)36 * b], *tb = t.data() + (size_t)v * nb6 + 6 * (size_t)b;
-      for (int p = 0; p < 6; ++p) {
-        double s = 0.0;
-        for (int q = 0; q < 6; ++q) s += B[6 * p + q] * tb[q];
-        uom[v][6 * (size_t)b + p] = s;
-      }
-    }
+  const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb;
+  const size_t vb = sizeof(double) * (size_t)n3;
+  int rc;
+  if ((rc = rbl_dev_reserve(c, c->d_W, vb))) return rc;
+  if ((rc = rbl_dev_reserve(c, c->d_r, vb))) return rc;
+  if ((rc = rbl_dev_reserve(c, c->d_U, 2 * vb))) return rc;
+  std::vector<double> Wh, uom;
+  if (W) {
+    if ((rc = copy_h2d(c, c->d_W.p, W, vb))) return rc;
+  } else {  // rand_vector (:730-741) replaced by the seeded device generator
+    Wh.resize((size_t)n3);
+    rbl_launch_normal(c->stream, seed, 0, n3, (double *)c->d_W.p);
+    if ((rc = copy_d2h(c, Wh.data(), c->d_W.p, vb))) return rc;
+    RBL_HIP(c, hipStreamSynchronize(c->stream));
+    W = Wh.data();
   }
-  return RBL_OK;
+  if (!U) {
+    uom.resize((size_t)6 * c->S.N_bod);
+    rbl_body_Kinv_x_V(c->S, W, uom.data());                          // UOM = Kinv W (:776), O(N) host work
+    U = uom.data();
+  }
+  double *dU = (double *)c->d_U.p;
+  if ((rc = m_rfd_dir(c, (const double *)c->d_W.p, U, delta, dU, (double *)c->d_r.p, dU))) return rc;
+  if ((rc = copy_d2h(c, out, dU, vb))) return rc;
+  return finish_and_check(c);
 }
 
-// M_RFD(), c_rigid_obj.cpp:769-796.  The two products run on the GPU at the two displaced configurations.
+// M_RFD(), c_rigid_obj.cpp:769-796
 int rbl_M_RFD(rbl_ctx *c, const double *W, uint64_t seed, double delta, double *out)
 {
   int rc = need_K(c); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (!(delta > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "M_RFD: delta must be positive");
-  RblBodyState &S = c->S;
-  const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N;
-  const size_t vb = sizeof(double) * (size_t)n3;
-  if ((rc = rbl_dev_reserve(c, c->d_W, vb))) return rc;
-  if ((rc = rbl_dev_reserve(c, c->d_r, vb))) return rc;
-  if ((rc = rbl_dev_reserve(c, c->d_U, 2 * vb))) return rc;
-  std::vector<double> Wh((size_t)n3);
-  if (W) {
-    std::memcpy(Wh.data(), W, vb);
-    if ((rc = copy_h2d(c, c->d_W.p, W, vb))) return rc;
-  } else {  // rand_vector (:730-741) replaced by the seeded device generator
-    rbl_launch_normal(c->stream, seed, 0, n3, (double *)c->d_W.p);
-    if ((rc = copy_d2h(c, Wh.data(), c->d_W.p, vb))) return rc;
-    RBL_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  double *dU = (double *)c->d_U.p;
-  if ((rc = m_rfd_core(c, (const double *)c->d_W.p, Wh.data(), delta, dU, (double *)c->d_r.p, dU))) return rc;
-  if ((rc = copy_d2h(c, out, dU, vb))) return rc;
-  return finish_and_check(c);
+  return m_rfd_host(c, W, seed, nullptr, delta, out);
 }
 
 // update_X_Q(U), c_rigid_obj.cpp:798-863: the configuration displaced by U (displacement units: translation
@@ -205,6 +239,71 @@ int rbl_update_X_Q(rbl_ctx *c, const double *U, double *X_out, double *Q_out)
   return RBL_OK;
 }
 
+// Right-hand side and predictor of the stochastic midpoint step at q^n (c_rigid_obj.cpp:917-976), with any subset of the bodies
+// prescribed (include/rbl.h section 7); the all-free scheme is the one with no mask.  Checks done by the caller, dt and delta
+// positive when kBT > 1e-10 among them.  h_mask / d_mask: the 0/1 mask per body on the host and on the device, d_body_in: the
+// prescribed bodies' velocities in their six slots -- all three NULL: every body is free.  d_slip: 3 N_blobs or NULL for zero;
+// d_W: [W1 | W2 | W_rfd] (3 n3) or NULL (drawn from `seed`).
+//   d_s (3 N_blobs, may be d_slip) = slip - kBT M_RFD - BI,  M_RFD along dq = D_f Kinv W_rfd,
+//   q^{n+1/2} = q^n displaced by D_f (dt/2 c1) Kinv M^{1/2}W1 + D_p (dt/2) U_p.
+// M is all blobs': the mask does not enter the square roots.  One read-back of 12 numbers per body.
+int rhs_and_midpoint_core(rbl_ctx *c, const uint8_t *h_mask, const uint8_t *d_mask, const double *d_body_in, const double *d_slip,
+                          const double *d_W, uint64_t seed, int method, int split_rand, double delta, double *d_s, double *X_half,
+                          double *Q_half)
+{
+  RblBodyState &S = c->S;
+  const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N, nb6 = (int64_t)6 * S.N_bod;
+  const size_t vb = sizeof(double) * (size_t)n3;
+  int rc;
+  if (!d_slip) {
+    RBL_HIP(c, hipMemsetAsync(d_s, 0, vb, c->stream));
+    d_slip = d_s;
+  }
+  if (!(S.kBT > 1e-10)) {                                                              // no Brownian terms (:967-970)
+    if (d_slip != d_s) RBL_HIP(c, hipMemcpyAsync(d_s, d_slip, vb, hipMemcpyDeviceToDevice, c->stream));
+    std::memcpy(X_half, S.X.data(), sizeof(double) * S.X.size());
+    std::memcpy(Q_half, S.Q.data(), sizeof(double) * S.Q.size());
+    return finish_and_check(c);
+  }
+  // workspace: [W1 | W2 | W_rfd] (when drawn here), M^{1/2}W1, M^{1/2}W2, M_RFD, positions, 2 scratch, the sums per body
+  if ((rc = rbl_dev_reserve(c, c->d_bd, 9 * vb + 2 * sizeof(double) * (size_t)nb6))) return rc;
+  double *base = (double *)c->d_bd.p;
+  double *dWown = base, *dMW = base + 3 * n3 /* 2 vectors */, *dRFD = base + 5 * n3, *dr = base + 6 * n3,
+         *dwork = base + 7 * n3, *dt12 = base + 9 * n3;
+  if (!d_W) {                                                                          // rand_vector (:730-741)
+    rbl_launch_normal(c->stream, seed, 0, 3 * n3, dWown);
+    d_W = dWown;
+  }
+  if ((rc = positions_dev(c, 0, S.N_bod, dr))) return rc;                              // multi_body_pos (:662)
+  if ((rc = mhalf_dev_multi(c, dr, N, d_W, split_rand ? 2 : 1, method, dMW))) return rc;   // M_half_W1/2 (:927-936)
+  // Kinv of the RFD noise (M_RFD's direction, :776) and of M^{1/2}W1 (the predictor, :955): the sums over the blobs on the device
+  // with the lever arms of q^n, the 6 x 6 blocks on the host after one small read-back (the reference brings the 3 N-vectors, :408)
+  if ((rc = sync_bodies(c))) return rc;
+  rbl_launch_mx_bd_sums(c->stream, (const double *)c->d_lever.p, d_mask, d_body_in, d_W + 2 * n3, dMW, S.N_blb, S.N_bod, dt12);
+  std::vector<double> t((size_t)(2 * nb6)), dq((size_t)nb6), pre((size_t)nb6), Xo, Qo;
+  if ((rc = read_back(c, t.data(), dt12, sizeof(double) * t.size()))) return rc;
+  const double c1 = split_rand ? 2.0 * std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);   // :945-952
+  const double c2 = split_rand ? std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);
+  const double half_dt = 0.5 * S.dt, scale = half_dt * c1;
+  for (int b = 0; b < S.N_bod; ++b) {
+    const double *Kb = &S.KTKinv[(size_t)36 * b], *tr = t.data() + 6 * (size_t)b, *tp = tr + nb6;
+    const bool prescribed = h_mask && h_mask[b];
+    for (int p = 0; p < 6; ++p) {
+      double sr = 0.0, sp = 0.0;
+      for (int q = 0; q < 6; ++q) { sr += Kb[6 * p + q] * tr[q]; sp += Kb[6 * p + q] * tp[q]; }
+      dq[6 * (size_t)b + p] = prescribed ? 0.0 : sr;                                    // D_f Kinv W_rfd
+      pre[6 * (size_t)b + p] = prescribed ? half_dt * tp[p] : scale * sp;               // (:955-959) and D_p (dt/2) U_p
+    }
+  }
+  if ((rc = m_rfd_dir(c, d_W + 2 * n3, dq.data(), delta, dRFD, dr, dwork))) return rc;  // M_RFD (:940)
+  // Slip -= kBT M_RFD + BI,  BI = c2 (M^{1/2}W1 - M^{1/2}W2)  or  c2 M^{1/2}W1   (:948,953,963)
+  rbl_launch_rhs_combine(c->stream, n3, d_slip, S.kBT, dRFD, c2, dMW, split_rand ? dMW + n3 : nullptr, d_s);
+  rbl_body_update_X_Q(S, pre.data(), Xo, Qo);
+  std::memcpy(X_half, Xo.data(), sizeof(double) * Xo.size());
+  std::memcpy(Q_half, Qo.data(), sizeof(double) * Qo.size());
+  return finish_and_check(c);
+}
+
 // RHS_and_Midpoint(Slip, Force), c_rigid_obj.cpp:917-976 -- device-resident form.  d_W = [W1 | W2 | W_rfd]
 // (3 n3) or NULL (drawn from `seed`).  d_RHS = [Slip - (kBT M_RFD + BI) ; -Force]  (n3 + 6 N_bod).
 int rbl_RHS_and_Midpoint_dev(rbl_ctx *c, const double *d_Slip, const double *d_Force, const double *d_W,
@@ -214,45 +313,12 @@ int rbl_RHS_and_Midpoint_dev(rbl_ctx *c, const double *d_Slip, const double *d_F
   int rc = need_K(c); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (!d_Slip || !d_Force || !d_RHS || !X_half || !Q_half) return rbl_fail(c, RBL_ERR_ARG, "RHS_and_Midpoint: null argument");
-  RblBodyState &S = c->S;
-  const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N, nb6 = (int64_t)6 * S.N_bod;
-  const size_t vb = sizeof(double) * (size_t)n3;
+  const RblBodyState &S = c->S;
+  const int64_t n3 = (int64_t)3 * S.N_bod * S.N_blb, nb6 = (int64_t)6 * S.N_bod;
   rbl_launch_axpby(c->stream, nb6, -1.0, d_Force, 0.0, nullptr, d_RHS + n3);          // Force *= -1 (:972)
-  if (!(S.kBT > 1e-10)) {                                                              // no Brownian terms (:967-970)
-    RBL_HIP(c, hipMemcpyAsync(d_RHS, d_Slip, vb, hipMemcpyDeviceToDevice, c->stream));
-    std::memcpy(X_half, S.X.data(), sizeof(double) * S.X.size());
-    std::memcpy(Q_half, S.Q.data(), sizeof(double) * S.Q.size());
-    return finish_and_check(c);
-  }
-  if (!(S.dt > 0.0) || !(delta > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "RHS_and_Midpoint: dt and delta must be positive");
-  // workspace: [W1 | W2 | W_rfd] (when drawn here), M^{1/2}W1, M^{1/2}W2, M_RFD, positions, 2 scratch
-  if ((rc = rbl_dev_reserve(c, c->d_bd, 9 * vb + 2 * sizeof(double) * (size_t)nb6))) return rc;
-  double *base = (double *)c->d_bd.p;
-  double *dWown = base, *dMW = base + 3 * n3 /* 2 vectors */, *dRFD = base + 5 * n3, *dr = base + 6 * n3,
-         *dwork = base + 7 * n3, *dt6 = base + 9 * n3;
-  if (!d_W) {                                                                          // rand_vector (:730-741)
-    rbl_launch_normal(c->stream, seed, 0, 3 * n3, dWown);
-    d_W = dWown;
-  }
-  const int nvec = split_rand ? 2 : 1;
-  if ((rc = positions_dev(c, 0, S.N_bod, dr))) return rc;                              // multi_body_pos (:662)
-  if ((rc = mhalf_dev_multi(c, dr, N, d_W, nvec, method, dMW))) return rc;             // M_half_W1/2 (:927-936)
-  // Kinv of the RFD noise (M_RFD's direction, :776) and of M^{1/2}W1 (the predictor, :955): blob sums on the device, one read-back
-  const double *kv[2] = {d_W + 2 * n3, dMW};
-  std::vector<double> uoms[2];
-  if ((rc = kinv_dev(c, kv, 2, dt6, uoms))) return rc;
-  if ((rc = m_rfd_dir(c, d_W + 2 * n3, uoms[0].data(), delta, dRFD, dr, dwork))) return rc;  // M_RFD (:940)
-  const double c1 = split_rand ? 2.0 * std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);   // :945-952
-  const double c2 = split_rand ? std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);
-  // Slip -= kBT M_RFD + BI,  BI = c2 (M^{1/2}W1 - M^{1/2}W2)  or  c2 M^{1/2}W1   (:948,953,963)
-  rbl_launch_rhs_combine(c->stream, n3, d_Slip, S.kBT, dRFD, c2, dMW, split_rand ? dMW + n3 : nullptr, d_RHS);
-  // predictor: q^{n+1/2} = q^n displaced by (dt/2) Kinv (c1 M^{1/2}W1)   (:955-959)
-  std::vector<double> &uom = uoms[1], Xo, Qo;
-  for (double &u : uom) u *= 0.5 * S.dt * c1;
-  rbl_body_update_X_Q(S, uom.data(), Xo, Qo);
-  std::memcpy(X_half, Xo.data(), sizeof(double) * Xo.size());
-  std::memcpy(Q_half, Qo.data(), sizeof(double) * Qo.size());
-  return finish_and_check(c);
+  if (S.kBT > 1e-10 && (!(S.dt > 0.0) || !(delta > 0.0)))
+    return rbl_fail(c, RBL_ERR_ARG, "RHS_and_Midpoint: dt and delta must be positive");
+  return rhs_and_midpoint_core(c, nullptr, nullptr, nullptr, d_Slip, d_W, seed, method, split_rand, delta, d_RHS, X_half, Q_half);
 }
 
 // host-pointer form of the same
@@ -280,20 +346,14 @@ int rbl_KTinv_RFD(rbl_ctx *c, const double *W, double delta, double *out)
 {
   int rc = need_K(c); if (rc) return rc;
   if (!W || !(delta > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "KTinv_RFD: need W and delta > 0");
-  const RblBodyState &S = c->S;
-  const size_t n3 = (size_t)3 * S.N_bod * S.N_blb;
-  std::vector<double> win((size_t)6 * S.N_bod), acc(n3, 0.0), tmp(n3);
-  for (int sgn = 0; sgn < 2; ++sgn) {
-    const double f = (sgn == 0 ? 0.5 : -0.5) * delta;
-    for (size_t i = 0; i < win.size(); ++i) win[i] = f * W[i];
-    RblBodyState T = S;                                              // displaced copy (:755-761)
-    rbl_body_update_X_Q(S, win.data(), T.X, T.Q);
-    if ((rc = rbl_body_set_K(T, c->last_error))) return rc;
+  const size_t n3 = (size_t)3 * c->S.N_bod * c->S.N_blb;
+  std::vector<double> acc(n3, 0.0), tmp(n3);
+  rc = on_displaced_copies(c, W, delta, [&](const RblBodyState &T, double w) {
     rbl_body_KTinv_x_F(T, W, tmp.data());
-    const double w = (sgn == 0 ? 1.0 : -1.0) / delta;
     for (size_t i = 0; i < n3; ++i) acc[i] += w * tmp[i];            // :763-764
-  }
-  rbl_body_KT_x_Lam(S, acc.data(), out);                             // :766
+  });
+  if (rc) return rc;
+  rbl_body_KT_x_Lam(c->S, acc.data(), out);                          // :766
   return RBL_OK;
 }
 
@@ -303,16 +363,7 @@ int rbl_M_RFD_from_U(rbl_ctx *c, const double *U, const double *W, double delta,
   int rc = need_config(c); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (!U || !W || !out || !(delta > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "M_RFD_from_U: need U, W, out and delta > 0");
-  const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb;
-  const size_t vb = sizeof(double) * (size_t)n3;
-  if ((rc = rbl_dev_reserve(c, c->d_W, vb))) return rc;
-  if ((rc = rbl_dev_reserve(c, c->d_r, vb))) return rc;
-  if ((rc = rbl_dev_reserve(c, c->d_U, 2 * vb))) return rc;
-  if ((rc = copy_h2d(c, c->d_W.p, W, vb))) return rc;
-  double *dU = (double *)c->d_U.p;
-  if ((rc = m_rfd_dir(c, (const double *)c->d_W.p, U, delta, dU, (double *)c->d_r.p, dU))) return rc;
-  if ((rc = copy_d2h(c, out, dU, vb))) return rc;
-  return finish_and_check(c);
+  return m_rfd_host(c, W, 0, U, delta, out);
 }
 
 // M_RFD_cfgs(U, delta), c_rigid_obj.cpp:798-818: blob positions at q +- (delta/2) U
@@ -321,23 +372,14 @@ int rbl_M_RFD_cfgs(rbl_ctx *c, const double *U, double delta, double *r_plus, do
   int rc = need_config(c); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (!U || !r_plus || !r_minus) return rbl_fail(c, RBL_ERR_ARG, "M_RFD_cfgs: null argument");
-  RblBodyState &S = c->S;
-  const size_t vb = sizeof(double) * 3 * (size_t)S.N_bod * S.N_blb;
+  const size_t vb = sizeof(double) * 3 * (size_t)c->S.N_bod * c->S.N_blb;
   if ((rc = rbl_dev_reserve(c, c->d_r, vb))) return rc;
-  std::vector<double> win((size_t)6 * S.N_bod), Xs, Qs;
-  const std::vector<double> X0 = S.X, Q0 = S.Q;
-  for (int sgn = 0; sgn < 2; ++sgn) {
-    const double f = (sgn == 0 ? 0.5 : -0.5) * delta;                 // :808, :811
-    for (size_t i = 0; i < win.size(); ++i) win[i] = f * U[i];
-    rbl_body_update_X_Q(S, win.data(), Xs, Qs);
-    S.X = Xs; S.Q = Qs; c->dev_xq_valid = false;
-    rc = positions_dev(c, 0, S.N_bod, (double *)c->d_r.p);
-    if (!rc) rc = copy_d2h(c, sgn == 0 ? r_plus : r_minus, c->d_r.p, vb);
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = RBL_ERR_HIP;
-    S.X = X0; S.Q = Q0; c->dev_xq_valid = false;
-    if (rc) return rc;
-  }
-  return RBL_OK;
+  return at_displaced_config(c, U, delta, [&](int sgn) {               // :808, :811
+    int r = positions_dev(c, 0, c->S.N_bod, (double *)c->d_r.p);
+    if (!r) r = copy_d2h(c, sgn == 0 ? r_plus : r_minus, c->d_r.p, vb);
+    if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = RBL_ERR_HIP;
+    return r;
+  });
 }
 
 // KT_RFD_from_U(U, W), c_rigid_obj.cpp:844-863: (1/delta) [K(q+)^T - K(q-)^T] W, W[3N] -> out[6 N_bod] (O(N) host work)
@@ -345,21 +387,13 @@ int rbl_KT_RFD_from_U(rbl_ctx *c, const double *U, const double *W, double delta
 {
   int rc = need_K(c); if (rc) return rc;
   if (!U || !W || !out || !(delta > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "KT_RFD_from_U: need U, W, out and delta > 0");
-  const RblBodyState &S = c->S;
-  const size_t nb6 = (size_t)6 * S.N_bod;
-  std::vector<double> win(nb6), tmp(nb6);
+  const size_t nb6 = (size_t)6 * c->S.N_bod;
+  std::vector<double> tmp(nb6);
   for (size_t i = 0; i < nb6; ++i) out[i] = 0.0;
-  for (int sgn = 0; sgn < 2; ++sgn) {
-    const double f = (sgn == 0 ? 0.5 : -0.5) * delta;
-    for (size_t i = 0; i < nb6; ++i) win[i] = f * U[i];
-    RblBodyState T = S;                                              // displaced copy (:853-859)
-    rbl_body_update_X_Q(S, win.data(), T.X, T.Q);
-    if ((rc = rbl_body_set_K(T, c->last_error))) return rc;
+  return on_displaced_copies(c, U, delta, [&](const RblBodyState &T, double w) {
     rbl_body_KT_x_Lam(T, W, tmp.data());
-    const double w = (sgn == 0 ? 1.0 : -1.0) / delta;
     for (size_t i = 0; i < nb6; ++i) out[i] += w * tmp[i];           // :861
-  }
-  return RBL_OK;
+  });
 }
 
 // evolve_X_Q_RFD(U), c_rigid_obj.cpp:880-893: commit q displaced by U (displacement units), rebuild K, KEEP the

@@ -231,6 +231,24 @@ def test_nothing_prescribed_is_step_brownian(shell12, wall):
     assert np.array_equal(Fo, F.reshape(-1)) and np.linalg.norm(Xa - X) > 1e-4
 
 
+@pytest.mark.parametrize("split_rand", [False, True])
+@pytest.mark.parametrize("wall", [False, True])
+def test_nothing_prescribed_is_RHS_and_Midpoint_bitwise(shell12, wall, split_rand):
+    """The all-free right-hand side is the mixed one with no mask, stated once in the library: with nobody prescribed s, X_half and
+    Q_half are the bits of RHS_and_Midpoint's top block and predictor.  (The whole steps of the neighbouring test go through two
+    GMRES drivers and keep their atol.)"""
+    X, Q, W, slip, F, _ = _case(wall, seed=250)
+    a, b = _solver(shell12, X, Q, wall, True), _solver(shell12, X, Q, wall, True)
+    s, Xh, Qh = a.RHS_and_Midpoint_mixed([], F, slip=slip, W=W, method="cholesky", split_rand=split_rand)
+    rhs, Xr, Qr = b.RHS_and_Midpoint(slip, F.reshape(-1), W=W, method="cholesky", split_rand=split_rand)
+    Xh, Qh, Xr, Qr = (np.asarray(v).reshape(-1) for v in (Xh, Qh, Xr, Qr))
+    print("nobody prescribed wall=%s split=%s: |ds| %.2e |dX_half| %.2e |dQ_half| %.2e"
+          % (wall, split_rand, np.abs(s - rhs[:s.size]).max(), np.abs(Xh - Xr).max(), np.abs(Qh - Qr).max()))
+    assert np.array_equal(s, rhs[:s.size]) and np.array_equal(rhs[s.size:], -F.reshape(-1))
+    assert np.array_equal(Xh, Xr) and np.array_equal(Qh, Qr)
+    assert np.linalg.norm(Xh - X.reshape(-1)) > 1e-4                                  # a predictor that moved
+
+
 def test_seeded_noise_is_reproducible(shell12):
     X, Q, _, slip, F, Up = _case(True, seed=260)
     p, bi = _mask_and_body_in("one held, one driven", F, Up)
