@@ -741,14 +741,56 @@ int rbl_velocity_field_info(const rbl_ctx *ctx, int64_t n_points, int64_t n_src,
  * Their refusals are those above plus max_iter > 254 and, when kBT > 1e-10, dt <= 0 or delta <= 0: RBL_ERR_ARG before any device
  * work.
  * Ensembles of replicas with prescribed bodies are section 5's rbl_ensemble_*_mixed.
- * Not offered: lock-step multi-right-hand-side mixed solves, contexts with a communicator, a mask that changes
- * within a step, and per-component constraints (only whole bodies are prescribed). */
+ *
+ * Prescribed kinematics per velocity component (per-component constraints: the _dof entry points).  A microroller has its
+ * angular velocity about a lab axis imposed and translates freely; a trapped particle is held in place and rotates freely; a
+ * quasi-2D suspension has U_z = 0.  Here D_p and D_f = I - D_p are diagonal 0/1 selectors on each body's six LAB-frame components, in the order of body_in (translation
+ * x, y, z, then rotation x, y, z):
+ *     M lambda - K D_f U    = slip + K D_p U_in
+ *     D_f K^T lambda + D_p U = -D_f F_in          (a prescribed slot: the identity, right-hand side 0)
+ * prescribed6[6 N_bod] (0 = free, 1 = prescribed, component by component); body_in[6 N_bod] holds the load of a free component or
+ * the velocity of a prescribed one; U = D_f U_solved + D_p U_in (prescribed components echoed), F = D_f F_in + D_p (-K^T lambda)
+ * (free components echoed; a prescribed component: the force or torque along it that holds the motion), lambda as above.  Signs,
+ * the residual (relative to the physical right-hand side; prescribed slots stay 0 in every Krylov vector) and the solver are
+ * those above, and with all six entries of every body equal the system, the iteration count and the results are rbl_solve_mixed's.
+ * The preconditioner stays the exact inverse of a body's own block in all three modes: with y1 = M_b^-1 slip_b, f = K_b^T y1 and
+ * R_b = K_b^T M_b^-1 K_b (its diagonal-mobility stand-in under the diagonal preconditioner),
+ *     (D_f R_b D_f + D_p) u = D_f (g - f) + D_p g,    lambda_b = y1 + (M_b^-1 K_b) D_f u,    the body slots take u.
+ * The masked 6 x 6 Cholesky factors are made once per solve by one small launch (from the context's own factors; with the
+ * free-space body-frame tables the one shared factor is first taken to each body's lab frame) and an iteration launches what an
+ * iteration of rbl_solve_mixed launches: one mobility product and one pass over the per-body factors, two with the free-space
+ * body-frame tables when anything is prescribed.  Its time per iteration and the iteration counts per mask have not been
+ * measured yet (tools/bench_prescribed_dof.py).
+ *
+ *   rbl_solve_mixed_dof      host arrays, synchronous.
+ *   rbl_solve_mixed_dof_dev  device pointers as rbl_solve_mixed_dev; prescribed6 stays a HOST array (6 N_bod bytes, checked
+ *                            before any device work and copied); stream drains and error latching as there.
+ *   rbl_step_mixed_dof       the solve, then evolve_X_Q(U): a body with its three translations held keeps its position exactly
+ *                            while it turns.  The force model's loads at q^n are added to the FREE COMPONENTS only, so the F of
+ *                            a prescribed component is the TOTAL load along it, as in rbl_step_mixed.  Clears the warm-start
+ *                            history.
+ * Refused with RBL_ERR_ARG before any device work: a NULL prescribed6 / body_in / U / F (rbl_step_mixed_dof: F may be NULL),
+ * max_iter < 1, rtol < 0, more than 255 iterations, an entry of prescribed6 above 1, a context with a communicator.
+ *
+ * Not offered: lock-step multi-right-hand-side mixed solves, contexts with a communicator, a mask that changes within a step;
+ * and with masks per component:
+ *   - the Brownian step (rbl_step_brownian_mixed takes whole bodies only): its drift argument rests on whole bodies being
+ *     undisplaced, a partly prescribed rotation is not a subset of the coordinates, and nobody has derived the scheme for it;
+ *   - ensembles (rbl_ensemble_*_mixed take whole bodies only);
+ *   - constraint axes fixed in the body frame (the six components are the lab frame's);
+ *   - lock-step multi-right-hand-side solves. */
 int rbl_solve_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
                     double *lambda, double *U, double *F, int *iters, double *resid);
 int rbl_solve_mixed_dev(rbl_ctx *ctx, const uint8_t *prescribed, const double *d_body_in, const double *d_slip, int max_iter,
                         double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid);
 int rbl_step_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
                    double *F, int *iters, double *resid);
+int rbl_solve_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter, double rtol,
+                        double *lambda, double *U, double *F, int *iters, double *resid);
+int rbl_solve_mixed_dof_dev(rbl_ctx *ctx, const uint8_t *prescribed6, const double *d_body_in, const double *d_slip, int max_iter,
+                            double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid);
+int rbl_step_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter, double rtol,
+                       double *F, int *iters, double *resid);
 int rbl_RHS_and_Midpoint_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
                                uint64_t seed, int method, int split_rand, double delta, double *s, double *X_half, double *Q_half);
 int rbl_RHS_and_Midpoint_mixed_dev(rbl_ctx *ctx, const uint8_t *prescribed, const double *d_body_in, const double *d_slip,

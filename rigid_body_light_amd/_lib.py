@@ -103,6 +103,8 @@ def lib():
         L.rbl_solve_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
         L.rbl_solve_mixed_dev.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
         L.rbl_step_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
+        L.rbl_solve_mixed_dof.argtypes = L.rbl_solve_mixed_dof_dev.argtypes = L.rbl_solve_mixed.argtypes
+        L.rbl_step_mixed_dof.argtypes = L.rbl_step_mixed.argtypes
         L.rbl_RHS_and_Midpoint_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, vp, vp, vp]
         L.rbl_RHS_and_Midpoint_mixed_dev.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, vp, vp, vp]
         L.rbl_step_brownian_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, C.c_int, dbl, vp, C.POINTER(C.c_int),
@@ -649,6 +651,20 @@ class DeviceContext:
         it, res = C.c_int(0), C.c_double(0.0)
         self._chk(self.L.rbl_solve_mixed_dev(self.h, m.ctypes.data, d_body_in, d_slip or None, int(max_iter), float(rtol), d_lam or None,
                                              d_U, d_F, C.byref(it), C.byref(res)))
+        return it.value, res.value
+
+    def solve_mixed_dof_dev(self, prescribed6, d_body_in, d_slip, max_iter, rtol, d_lam, d_U, d_F):
+        """solve_mixed_dev with a mask per velocity component (prescribed6: a host array of 6 N_bod entries) -> (iterations,
+        residual estimate)"""
+        import numpy as np
+        m = np.ascontiguousarray(prescribed6, dtype=np.uint8).reshape(-1)
+        nb = C.c_int(0)
+        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), None))
+        if m.size != 6 * nb.value:
+            raise ValueError("solve_mixed_dof_dev: prescribed6 must have 6 N_bod entries")
+        it, res = C.c_int(0), C.c_double(0.0)
+        self._chk(self.L.rbl_solve_mixed_dof_dev(self.h, m.ctypes.data, d_body_in, d_slip or None, int(max_iter), float(rtol),
+                                                 d_lam or None, d_U, d_F, C.byref(it), C.byref(res)))
         return it.value, res.value
 
     def _mixed_sizes(self, who, prescribed):

@@ -477,6 +477,43 @@ struct CManyBodies {
     check(rc);
     return py::make_tuple(F, it, res);
   }
+  // a mask per velocity component (rbl_solve_mixed_dof, rbl_step_mixed_dof): mask[6 N_bod] in body_in's order
+  const double *mixed_dof_args(const char *who, const marr &mask, const darr &body_in, const py::object &slip, darr &sl) const
+  {
+    if (mask.size() != 6 * (py::ssize_t)n_bod()) throw py::value_error(std::string(who) + ": prescribed must have length 6*N_bod");
+    if (body_in.size() != 6 * (py::ssize_t)n_bod()) throw py::value_error(std::string(who) + ": body_in must have length 6*N_bod");
+    if (slip.is_none()) return nullptr;
+    sl = slip.cast<darr>();
+    if (sl.size() != n3()) throw py::value_error(std::string(who) + ": slip must have length 3*N_blobs");
+    return sl.data();
+  }
+  py::tuple solve_mixed_dof(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
+  {
+    darr sl;
+    const double *sp = mixed_dof_args("solve_mixed_dof", mask, body_in, slip, sl);
+    darr lam(n3()), U(6 * (py::ssize_t)n_bod()), F(6 * (py::ssize_t)n_bod());
+    int it = 0, rc; double res = 0.0;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_solve_mixed_dof(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, lam.mutable_data(), U.mutable_data(), F.mutable_data(),
+                               &it, &res);
+    }
+    check(rc);
+    return py::make_tuple(lam, U, F, it, res);
+  }
+  py::tuple step_mixed_dof(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
+  {
+    darr sl;
+    const double *sp = mixed_dof_args("step_mixed_dof", mask, body_in, slip, sl);
+    darr F(6 * (py::ssize_t)n_bod());
+    int it = 0, rc; double res = 0.0;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_step_mixed_dof(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, F.mutable_data(), &it, &res);
+    }
+    check(rc);
+    return py::make_tuple(F, it, res);
+  }
   // the Brownian midpoint step with prescribed bodies: right-hand side and predictor at q^n -> (s, X_half, Q_half), nothing committed
   const double *noise_arg(const char *who, const py::object &W, darr &Wa) const
   {
@@ -622,6 +659,10 @@ PYBIND11_MODULE(c_rigid, m)
       .def("solve_mixed", &CManyBodies::solve_mixed, "prescribed kinematics: velocities given on some bodies, loads on the others",
            py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
       .def("step_mixed", &CManyBodies::step_mixed, py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(),
+           py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
+      .def("solve_mixed_dof", &CManyBodies::solve_mixed_dof, "prescribed kinematics per velocity component: prescribed has 6 N_bod entries",
+           py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
+      .def("step_mixed_dof", &CManyBodies::step_mixed_dof, py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(),
            py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
       .def("RHS_and_Midpoint_mixed", &CManyBodies::RHS_and_Midpoint_mixed, py::arg("prescribed"), py::arg("body_in"),
            py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "cholesky",

@@ -11,18 +11,6 @@ namespace {
 
 constexpr int BT = 256;
 
-__device__ __forceinline__ void quat_rot(const double *q, double *R)
-{
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w;
-  const double txx = tx * x, txy = ty * x, txz = tz * x;
-  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-
 // lever arms l_k = R(Q_b) c_k (:374) and positions r_k = l_k + X_b (:257-265)
 __global__ void k_body_geom(const double *__restrict__ X, const double *__restrict__ Q,
                             const double *__restrict__ cfg, int N_blb, long N,

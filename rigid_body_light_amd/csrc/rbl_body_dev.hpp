@@ -1,8 +1,21 @@
 // rbl_body_dev.hpp -- device helpers shared by the per-body kernels (rbl_body_dev.hip, rbl_mixed.hip): ONE copy of the K / K^T
-// formulas, of the ordered workgroup sum and of the 6 x 6 substitution, so the kernels that restate a body's operators cannot
+// formulas, of the quaternion's rotation, of the ordered workgroup sum and of the 6 x 6 substitution, so the kernels that restate a body's operators cannot
 // drift apart.
 #pragma once
 #include <hip/hip_runtime.h>
+
+// rotation matrix (row-major) of a unit quaternion (w, x, y, z): lab = R body
+__device__ __forceinline__ void quat_rot(const double *q, double *R)
+{
+  const double w = q[0], x = q[1], y = q[2], z = q[3];
+  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w;
+  const double txx = tx * x, txy = ty * x, txz = tz * x;
+  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
+  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
+}
 
 // (K_b u)_k = u_lin + u_ang x l_k     (reference c_rigid_obj.cpp:368-383, :404)
 __device__ __forceinline__ void rbl_KU(const double *l, const double *u, double &k0, double &k1, double &k2)

@@ -3,8 +3,9 @@
 // Shared internals are declared in rbl_api_internal.hpp.  Nothing here falls back to a CPU path.
 //
 // The system:  A x = [M lambda - K (D_f U) ; D_f K^T lambda + D_p U] = [slip + K_p U_p ; -F_f on free bodies, 0 on prescribed ones]
-// (D_f, D_p: 0/1 per body).  The six body slots of a prescribed body carry the identity, start at 0 and stay 0 through every
-// Krylov vector, so |rhs| is the norm of the physical right-hand side alone.  The mobility product is the library's own
+// (D_f, D_p: 0/1 per body, or per velocity component in the _dof entry points: the k_mxd_ kernels, whose body-row solves go
+// through 6 x 6 factors masked once per solve).  The body slots that are prescribed carry the identity, start at 0 and stay 0
+// through every Krylov vector, so |rhs| is the norm of the physical right-hand side alone.  The mobility product is the library's own
 // (apply_M_enqueue, untouched); what is new around it -- the masked K / K^T tail, the masked preconditioner tails, the right-hand
 // side and the split of the solution -- are the O(N) kernels below: one workgroup per body, the mask read once per workgroup (the
 // branch on it is uniform), deterministic LDS tree sums, no atomics; the K / K^T formulas, the workgroup sum and the 6 x 6
@@ -204,21 +205,349 @@ __global__ void k_mx_add_free(const uint8_t *__restrict__ mask, const double *__
   if (i < nb6 && !mask[i / 6]) v[i] += add[i];
 }
 
+// ---- masks per velocity component (rbl_solve_mixed_dof): the kernels above with D_f, D_p diagonal 0/1 on a body's six lab-frame
+// components.  The six mask bytes of the workgroup's body become one scalar bit set (bit c: component c prescribed), so every branch
+// on it is uniform; a body with no bit set or all six takes the arithmetic of the kernels above in the same order.
+
+__device__ __forceinline__ unsigned mxd_bits(const uint8_t *__restrict__ mask6, int b)
+{
+  const uint8_t *m = mask6 + 6 * (size_t)b;
+  unsigned pm = 0;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) pm |= (m[c] != 0 ? 1u : 0u) << c;
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)pm);
+}
+
+// right-hand side: top = slip + K D_p U_in, bottom = -F_in on the free components, 0 on the prescribed ones
+__global__ __launch_bounds__(MT) void k_mxd_rhs(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
+                                                const double *__restrict__ body_in, const double *__restrict__ slip, int N_blb,
+                                                long n3, double *__restrict__ rhs)
+{
+  const int b = blockIdx.x, t = threadIdx.x;
+  const unsigned pm = mxd_bits(mask6, b);
+  const double *u = body_in + 6 * (size_t)b;
+  double up[6];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) up[c] = (pm >> c & 1u) ? u[c] : 0.0;
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    double r0 = slip ? slip[idx] : 0.0, r1 = slip ? slip[idx + 1] : 0.0, r2 = slip ? slip[idx + 2] : 0.0;
+    if (pm) {
+      double k0, k1, k2;
+      rbl_KU(lever + idx, up, k0, k1, k2);
+      r0 += k0; r1 += k1; r2 += k2;
+    }
+    rhs[idx] = r0; rhs[idx + 1] = r1; rhs[idx + 2] = r2;
+  }
+  if (t < 6) rhs[n3 + 6 * (size_t)b + t] = (pm >> t & 1u) ? 0.0 : -u[t];
+}
+
+// the operator's tail after sub = M lambda: out = [sub - K (D_f U) ; D_f K^T lambda + D_p U]
+__global__ __launch_bounds__(MT) void k_mxd_op_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
+                                                    const double *__restrict__ x, const double *__restrict__ sub, int N_blb, long n3,
+                                                    double *__restrict__ out)
+{
+  __shared__ double s[6][MT];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const unsigned pm = mxd_bits(mask6, b);
+  const double *u = x + n3 + 6 * (size_t)b;
+  if (pm == 63u) {                                       // no velocity unknown, no balance row
+    for (int k = t; k < N_blb; k += MT) {
+      const size_t idx = 3 * ((size_t)b * N_blb + k);
+      out[idx] = sub[idx]; out[idx + 1] = sub[idx + 1]; out[idx + 2] = sub[idx + 2];
+    }
+    if (t < 6) out[n3 + 6 * (size_t)b + t] = u[t];
+    return;
+  }
+  double uf[6];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) uf[c] = (pm >> c & 1u) ? 0.0 : u[c];
+  double f[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    const double *l = lever + idx;
+    double k0, k1, k2;
+    rbl_KU(l, uf, k0, k1, k2);
+    out[idx] = sub[idx] - k0; out[idx + 1] = sub[idx + 1] - k1; out[idx + 2] = sub[idx + 2] - k2;
+    rbl_KT_acc(l, x[idx], x[idx + 1], x[idx + 2], f);
+  }
+  rbl_block_sum<6, MT>(f, s, t);
+  if (t < 6) {
+    double ft = f[0];
+#pragma unroll
+    for (int c = 1; c < 6; ++c) ft = t == c ? f[c] : ft;   // (selects: a register array indexed by the lane goes to scratch here)
+    out[n3 + 6 * (size_t)b + t] = (pm >> t & 1u) ? u[t] : ft;
+  }
+}
+
+// The masked 6 x 6 factors, once per solve, one thread per body: R_b = L L^T from the context's factor (NL: per body, or with
+// `Q` the ONE body-frame factor of the free-space tables, taken to the lab frame first: R_lab = (I2 x Rot) R_body (I2 x Rot)^T),
+// rows and columns of the prescribed components replaced by the identity's, factored again -- a principal submatrix's Cholesky
+// factor is not a sub-block of NL.  A body with no bit set copies its own factor (Q NULL); with the shared factor nothing is
+// written for it, as no tail reads it there (the body-frame preconditioner's answer stands).  Not positive definite: the flag
+// k_pc_block_ninv latches.
+__global__ void k_mxd_factors(const double *__restrict__ NL, const double *__restrict__ Q, const uint8_t *__restrict__ mask6, int N_bod,
+                              double *__restrict__ NLm, unsigned *err)
+{
+  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (b >= N_bod) return;
+  unsigned pm = 0;
+  for (int c = 0; c < 6; ++c) pm |= (mask6[6 * (size_t)b + c] != 0 ? 1u : 0u) << c;
+  const double *L0 = Q ? NL : NL + 36 * (size_t)b;
+  double *Lo = NLm + 36 * (size_t)b;
+  if (pm == 0) {
+    if (!Q)
+      for (int e = 0; e < 36; ++e) Lo[e] = L0[e];
+    return;
+  }
+  double A[36], L[36];
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double v = 0.0;
+      for (int k = 0; k <= j; ++k) v += L0[6 * i + k] * L0[6 * j + k];
+      A[6 * i + j] = v; A[6 * j + i] = v;
+    }
+  if (Q) {
+    double R[9], T[9];
+    quat_rot(Q + 4 * (size_t)b, R);
+    for (int hi = 0; hi < 2; ++hi)
+      for (int hj = 0; hj <= hi; ++hj) {                 // block (hi, hj): R A R^T; the upper block is the lower one's transpose
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) {
+            double v = 0.0;
+            for (int k = 0; k < 3; ++k) v += R[3 * i + k] * A[6 * (3 * hi + k) + 3 * hj + j];
+            T[3 * i + j] = v;
+          }
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) {
+            double v = 0.0;
+            for (int k = 0; k < 3; ++k) v += T[3 * i + k] * R[3 * j + k];
+            L[6 * (3 * hi + i) + 3 * hj + j] = v;
+          }
+      }
+    for (int i = 0; i < 6; ++i)
+      for (int j = 0; j <= i; ++j) {
+        // the diagonal blocks are symmetric up to rounding: the lower triangle is what the factorisation reads
+        A[6 * i + j] = L[6 * i + j];
+      }
+  }
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j <= i; ++j) {
+      const bool cut = ((pm >> i) | (pm >> j)) & 1u;
+      L[6 * i + j] = cut ? (i == j ? 1.0 : 0.0) : A[6 * i + j];
+    }
+  bool ok = true;
+  for (int j = 0; j < 6; ++j) {
+    double d = L[6 * j + j];
+    for (int k = 0; k < j; ++k) d -= L[6 * j + k] * L[6 * j + k];
+    if (!(d > 0.0)) ok = false;
+    d = sqrt(d);
+    L[6 * j + j] = d;
+    for (int i = j + 1; i < 6; ++i) {
+      double v = L[6 * i + j];
+      for (int k = 0; k < j; ++k) v -= L[6 * i + k] * L[6 * j + k];
+      L[6 * i + j] = v / d;
+    }
+    for (int i = 0; i < j; ++i) L[6 * i + j] = 0.0;
+  }
+  if (!ok) atomicOr(err, (unsigned)RBL_FLAG_NOT_SPD);
+  for (int e = 0; e < 36; ++e) Lo[e] = L[e];
+}
+
+// the six body rows of a preconditioner application from f = K_b^T y1 and the masked factor: (D_f R_b D_f + D_p) u = D_f (g - f) +
+// D_p g; the body slots take u (a prescribed slot: g, passed through), uf = D_f u goes on into lambda
+__device__ __forceinline__ void mxd_body_rows(const double *NLm_b, unsigned pm, const double *g, const double (&f)[6], double *out_b, double *uf)
+{
+  double r[6], u[6];
+  for (int p = 0; p < 6; ++p) r[p] = (pm >> p & 1u) ? g[p] : g[p] - f[p];
+  rbl_chol6_solve(NLm_b, r, u);
+  for (int p = 0; p < 6; ++p) {
+    const bool pres = pm >> p & 1u;
+    out_b[p] = pres ? g[p] : u[p];
+    uf[p] = pres ? 0.0 : u[p];
+  }
+}
+
+// block preconditioner after y1 = invM slip: k_mx_pc_block_tail with the masked factor; lambda = y1 + (invM K) D_f u
+__global__ __launch_bounds__(MT) void k_mxd_pc_block_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
+                                                          const double *__restrict__ y1, const double *__restrict__ MK, long stride,
+                                                          const double *__restrict__ NLm, const double *__restrict__ in, int N_blb,
+                                                          long n3, double *__restrict__ out)
+{
+  __shared__ double s[6][MT];
+  __shared__ double us[6];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const unsigned pm = mxd_bits(mask6, b);
+  const double *g = in + n3 + 6 * (size_t)b;
+  if (pm == 63u) {
+    for (int k = t; k < N_blb; k += MT) {
+      const size_t idx = 3 * ((size_t)b * N_blb + k);
+      out[idx] = y1[idx]; out[idx + 1] = y1[idx + 1]; out[idx + 2] = y1[idx + 2];
+    }
+    if (t < 6) out[n3 + 6 * (size_t)b + t] = g[t];
+    return;
+  }
+  double f[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    rbl_KT_acc(lever + idx, y1[idx], y1[idx + 1], y1[idx + 2], f);
+  }
+  rbl_block_sum<6, MT>(f, s, t);
+  if (t == 0) mxd_body_rows(NLm + 36 * (size_t)b, pm, g, f, out + n3 + 6 * (size_t)b, us);
+  __syncthreads();
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      double acc = y1[idx + d];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) acc = __builtin_fma(MK[(size_t)c * stride + idx + d], us[c], acc);
+      out[idx + d] = acc;
+    }
+  }
+}
+
+// diagonal preconditioner: k_mx_pc_diag with the masked factor; lambda = invM (slip + K D_f u)
+__global__ __launch_bounds__(MT) void k_mxd_pc_diag(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
+                                                    const double *__restrict__ invM2, const double *__restrict__ NLm, int N_blb, long n3,
+                                                    const double *__restrict__ in, double *__restrict__ out)
+{
+  __shared__ double s[6][MT];
+  __shared__ double us[6];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const unsigned pm = mxd_bits(mask6, b);
+  const double *g = in + n3 + 6 * (size_t)b;
+  if (pm == 63u) {
+    for (int k = t; k < N_blb; k += MT) {
+      const size_t i = (size_t)b * N_blb + k;
+      out[3 * i] = invM2[2 * i] * in[3 * i]; out[3 * i + 1] = invM2[2 * i] * in[3 * i + 1];
+      out[3 * i + 2] = invM2[2 * i + 1] * in[3 * i + 2];
+    }
+    if (t < 6) out[n3 + 6 * (size_t)b + t] = g[t];
+    return;
+  }
+  double f[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = t; k < N_blb; k += MT) {                  // K^T (invM slip)
+    const size_t i = (size_t)b * N_blb + k;
+    rbl_KT_acc(lever + 3 * i, invM2[2 * i] * in[3 * i], invM2[2 * i] * in[3 * i + 1], invM2[2 * i + 1] * in[3 * i + 2], f);
+  }
+  rbl_block_sum<6, MT>(f, s, t);
+  if (t == 0) mxd_body_rows(NLm + 36 * (size_t)b, pm, g, f, out + n3 + 6 * (size_t)b, us);
+  __syncthreads();
+  for (int k = t; k < N_blb; k += MT) {                  // lambda = invM (slip + K D_f u)
+    const size_t i = (size_t)b * N_blb + k;
+    double k0, k1, k2;
+    rbl_KU(lever + 3 * i, us, k0, k1, k2);
+    out[3 * i] = invM2[2 * i] * (in[3 * i] + k0);
+    out[3 * i + 1] = invM2[2 * i] * (in[3 * i + 1] + k1);
+    out[3 * i + 2] = invM2[2 * i + 1] * (in[3 * i + 2] + k2);
+  }
+}
+
+// free-space body-frame tables: `out` holds the ordinary preconditioner's answer for every body, which stands for a body with no
+// bit set; the others are redone from y1 = M_b^-1 slip_b (a second factor application, lab frame) with the masked lab-frame factor.
+// The table MKb = M_body^-1 K_body ([6][3 N_blb], one for all bodies) is in the body frame: M_b^-1 K_b D_f u = Rot MKb (I2 x Rot)^T D_f u
+__global__ __launch_bounds__(MT) void k_mxd_pc_bodyframe_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
+                                                              const double *__restrict__ y1, const double *__restrict__ MKb,
+                                                              const double *__restrict__ Q, const double *__restrict__ NLm,
+                                                              const double *__restrict__ in, int N_blb, long n3, double *__restrict__ out)
+{
+  __shared__ double s[6][MT];
+  __shared__ double us[6];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const unsigned pm = mxd_bits(mask6, b);
+  if (pm == 0u) return;
+  const double *g = in + n3 + 6 * (size_t)b;
+  if (pm == 63u) {
+    for (int k = t; k < N_blb; k += MT) {
+      const size_t idx = 3 * ((size_t)b * N_blb + k);
+      out[idx] = y1[idx]; out[idx + 1] = y1[idx + 1]; out[idx + 2] = y1[idx + 2];
+    }
+    if (t < 6) out[n3 + 6 * (size_t)b + t] = g[t];
+    return;
+  }
+  double R[9];
+  quat_rot(Q + 4 * (size_t)b, R);
+  double f[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    rbl_KT_acc(lever + idx, y1[idx], y1[idx + 1], y1[idx + 2], f);
+  }
+  rbl_block_sum<6, MT>(f, s, t);
+  if (t == 0) {
+    double uf[6];
+    mxd_body_rows(NLm + 36 * (size_t)b, pm, g, f, out + n3 + 6 * (size_t)b, uf);
+    for (int h = 0; h < 2; ++h)                          // (I2 x Rot)^T D_f u
+      for (int d = 0; d < 3; ++d) us[3 * h + d] = R[d] * uf[3 * h] + R[3 + d] * uf[3 * h + 1] + R[6 + d] * uf[3 * h + 2];
+  }
+  __syncthreads();
+  const long n = 3L * N_blb;
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    double w[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      double acc = 0.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) acc = __builtin_fma(MKb[(size_t)c * n + 3 * k + d], us[c], acc);
+      w[d] = acc;
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) out[idx + d] = y1[idx + d] + (R[3 * d] * w[0] + R[3 * d + 1] * w[1] + R[3 * d + 2] * w[2]);
+  }
+}
+
+// v += add on the free components (the force model's loads enter the free components only)
+__global__ void k_mxd_add_free(const uint8_t *__restrict__ mask6, const double *__restrict__ add, int nb6, double *__restrict__ v)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nb6 && !mask6[i]) v[i] += add[i];
+}
+
+// the solution split: U = D_f U_solved + D_p U_in (echoed), F = D_f F_in (echoed) + D_p (-K_b^T lambda)
+__global__ __launch_bounds__(MT) void k_mxd_split(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
+                                                  const double *__restrict__ body_in, const double *__restrict__ x, int N_blb, long n3,
+                                                  double *__restrict__ U, double *__restrict__ F)
+{
+  __shared__ double s[6][MT];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const unsigned pm = mxd_bits(mask6, b);
+  const size_t o = 6 * (size_t)b;
+  if (pm == 0u) {
+    if (t < 6) { U[o + t] = x[n3 + o + t]; F[o + t] = body_in[o + t]; }
+    return;
+  }
+  double f[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    rbl_KT_acc(lever + idx, x[idx], x[idx + 1], x[idx + 2], f);
+  }
+  rbl_block_sum<6, MT>(f, s, t);
+  if (t < 6) {
+    const bool pres = pm >> t & 1u;
+    U[o + t] = pres ? body_in[o + t] : x[n3 + o + t];
+    F[o + t] = pres ? -f[t] : body_in[o + t];
+  }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 
 struct MxBuf {           // the one workspace of a section 7 entry point (rbl_ctx::d_mx)
   double *rhs, *x, *y1, *body_in, *slip, *U, *F, *model;
-  uint8_t *mask;
+  double *NLm;           // the masked 6 x 6 factors of a solve with a mask per component (k_mxd_factors)
+  uint8_t *mask;         // per * N_bod entries
+  int per = 1;           // mask entries per body: 1 (whole bodies) or 6 (velocity components, the _dof entry points)
 };
 
 int mx_reserve(rbl_ctx *c, MxBuf &B)
 {
   const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nsys = n3 + nb6;
-  const int rc = rbl_dev_reserve(c, c->d_mx, sizeof(double) * (2 * nsys + 2 * n3 + 4 * nb6) + (size_t)c->S.N_bod);
+  const size_t nlm = B.per == 6 ? 6 * nb6 : 0;           // the masked factors: solves with a mask per component only
+  const int rc = rbl_dev_reserve(c, c->d_mx, sizeof(double) * (2 * nsys + 2 * n3 + 4 * nb6 + nlm) + (size_t)B.per * (size_t)c->S.N_bod);
   if (rc) return rc;
   B.rhs = (double *)c->d_mx.p; B.x = B.rhs + nsys; B.y1 = B.x + nsys; B.slip = B.y1 + n3; B.body_in = B.slip + n3;
-  B.U = B.body_in + nb6; B.F = B.U + nb6; B.model = B.F + nb6;
-  B.mask = (uint8_t *)(B.model + nb6);
+  B.U = B.body_in + nb6; B.F = B.U + nb6; B.model = B.F + nb6; B.NLm = nlm ? B.model + nb6 : nullptr;
+  B.mask = (uint8_t *)(B.model + nb6 + nlm);
   return RBL_OK;
 }
 
@@ -234,9 +563,17 @@ int mx_op(rbl_ctx *c, void *user, const double *d_x, double *d_out)
   const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N;
   int rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3); if (rc) return rc;
   if ((rc = apply_M_enqueue(c, S.wall, d_x, (const double *)c->d_pos.p, N, 0, N, (double *)c->d_sad.p))) return rc;
-  hipLaunchKernelGGL(k_mx_op_tail, dim3((unsigned)S.N_bod), dim3(MT), 0, c->stream, (const double *)c->d_lever.p, m->B->mask, d_x,
+  const auto k_tail = m->B->per == 6 ? k_mxd_op_tail : k_mx_op_tail;
+  hipLaunchKernelGGL(k_tail, dim3((unsigned)S.N_bod), dim3(MT), 0, c->stream, (const double *)c->d_lever.p, (const uint8_t *)m->B->mask, d_x,
                      (const double *)c->d_sad.p, S.N_blb, (long)n3, d_out);
   return RBL_OK;
+}
+
+// the tables of the free-space body-frame preconditioner (bf_build: M_body^-1 | M_body^-1 K_body | the 6 x 6 factor)
+const double *bf_table_MK(const rbl_ctx *c)
+{
+  const size_t m = 3 * (size_t)c->S.N_blb;
+  return (const double *)c->d_bfPC.p + m * m;
 }
 
 int mx_pc(rbl_ctx *c, void *user, const double *d_in, double *d_out)
@@ -246,10 +583,16 @@ int mx_pc(rbl_ctx *c, void *user, const double *d_in, double *d_out)
   const long n3 = 3 * (long)S.N_bod * S.N_blb;
   const double *lev = (const double *)c->d_lever.p;
   const dim3 grid((unsigned)S.N_bod), block(MT);
+  const bool dof = m->B->per == 6;                       // a mask per component: the same three paths with the masked factors
+  const uint8_t *mask = m->B->mask;
   int rc;
   if (!S.block_pc) {
-    hipLaunchKernelGGL(k_mx_pc_diag, grid, block, 0, c->stream, lev, m->B->mask, (const double *)c->d_invM2.p, (const double *)c->d_NL.p,
-                       S.N_blb, n3, d_in, d_out);
+    if (dof)
+      hipLaunchKernelGGL(k_mxd_pc_diag, grid, block, 0, c->stream, lev, mask, (const double *)c->d_invM2.p, (const double *)m->B->NLm,
+                         S.N_blb, n3, d_in, d_out);
+    else
+      hipLaunchKernelGGL(k_mx_pc_diag, grid, block, 0, c->stream, lev, mask, (const double *)c->d_invM2.p, (const double *)c->d_NL.p,
+                         S.N_blb, n3, d_in, d_out);
     return RBL_OK;
   }
   if (bf_on(c) && c->bf_tables) {
@@ -260,19 +603,27 @@ int mx_pc(rbl_ctx *c, void *user, const double *d_in, double *d_out)
     rc = apply_PC_dev(c, d_in, d_out, rq);
     if (rc || !m->any_prescribed) return rc;
     if ((rc = blk_solve(c, 0, S.N_bod, d_in, m->B->y1, 1, 0, 0))) return rc;
-    hipLaunchKernelGGL(k_mx_pc_select, grid, block, 0, c->stream, m->B->mask, (const double *)m->B->y1, d_in, S.N_blb, n3, d_out);
+    if (dof)
+      hipLaunchKernelGGL(k_mxd_pc_bodyframe_tail, grid, block, 0, c->stream, lev, mask, (const double *)m->B->y1, bf_table_MK(c),
+                         (const double *)c->d_XQ.p + 3 * (size_t)S.N_bod, (const double *)m->B->NLm, d_in, S.N_blb, n3, d_out);
+    else
+      hipLaunchKernelGGL(k_mx_pc_select, grid, block, 0, c->stream, mask, (const double *)m->B->y1, d_in, S.N_blb, n3, d_out);
     return RBL_OK;
   }
   if ((rc = blk_solve(c, 0, S.N_bod, d_in, m->B->y1, 1, 0, 0))) return rc;                   // invM slip, every body: ONE pass
   RblPhase ph(c, RBL_T_PERBODY);
-  hipLaunchKernelGGL(k_mx_pc_block_tail, grid, block, 0, c->stream, lev, m->B->mask, (const double *)m->B->y1, (const double *)c->d_pcMK.p,
-                     n3, (const double *)c->d_NL.p, d_in, S.N_blb, n3, d_out);
+  if (dof)
+    hipLaunchKernelGGL(k_mxd_pc_block_tail, grid, block, 0, c->stream, lev, mask, (const double *)m->B->y1, (const double *)c->d_pcMK.p,
+                       n3, (const double *)m->B->NLm, d_in, S.N_blb, n3, d_out);
+  else
+    hipLaunchKernelGGL(k_mx_pc_block_tail, grid, block, 0, c->stream, lev, mask, (const double *)m->B->y1, (const double *)c->d_pcMK.p,
+                       n3, (const double *)c->d_NL.p, d_in, S.N_blb, n3, d_out);
   return RBL_OK;
 }
 
 // argument checks that need no device
 int mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const void *body_in, int max_iter, double rtol, bool host_form,
-             int *n_prescribed)
+             int *n_prescribed, int per = 1)
 {
   if (!c) return RBL_ERR_ARG;
   if (!prescribed || !body_in) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": prescribed or body_in is NULL");
@@ -280,7 +631,7 @@ int mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const void 
   if (max_iter + 1 > rbl_gmres_max_vectors()) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": at most 255 iterations (no restart)");
   int rc = host_form ? need_K(c) : need_config(c); if (rc) return rc;
   int np = 0;
-  for (int b = 0; b < c->S.N_bod; ++b) {
+  for (size_t b = 0; b < (size_t)per * (size_t)c->S.N_bod; ++b) {
     if (prescribed[b] > 1) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": entries of prescribed must be 0 or 1");
     np += prescribed[b];
   }
@@ -299,44 +650,55 @@ int mx_solve(rbl_ctx *c, const MxBuf &B, bool have_slip, int n_prescribed, int m
   const long n3 = 3 * (long)S.N_bod * S.N_blb;
   const double *lev = (const double *)c->d_lever.p;
   const dim3 grid((unsigned)S.N_bod), block(MT);
-  hipLaunchKernelGGL(k_mx_rhs, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, (const double *)B.body_in,
+  const bool dof = B.per == 6;
+  const auto k_rhs = dof ? k_mxd_rhs : k_mx_rhs;
+  const auto k_split = dof ? k_mxd_split : k_mx_split;
+  hipLaunchKernelGGL(k_rhs, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, (const double *)B.body_in,
                      have_slip ? (const double *)B.slip : nullptr, S.N_blb, n3, B.rhs);
+  if (dof) {                                             // the masked 6 x 6 factors: once per solve
+    const bool shared = S.block_pc && bf_on(c) && c->bf_tables;          // one body-frame factor for all bodies, behind the tables
+    if (shared && (rc = ensure_xq_dev(c))) return rc;
+    hipLaunchKernelGGL(k_mxd_factors, dim3((unsigned)((S.N_bod + 63) / 64)), dim3(64), 0, c->stream,
+                       shared ? bf_table_MK(c) + 18 * (size_t)S.N_blb : (const double *)c->d_NL.p,
+                       shared ? (const double *)c->d_XQ.p + 3 * (size_t)S.N_bod : nullptr, (const uint8_t *)B.mask, S.N_bod, B.NLm, c->d_err);
+  }
   MxSolve m{&B, n_prescribed > 0};
   const RblSolveOps ops{mx_op, mx_pc, &m};
   if ((rc = gmres_core_with_ops(c, &ops, B.rhs, max_iter, rtol, B.x, iters, resid))) return rc;
-  hipLaunchKernelGGL(k_mx_split, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, (const double *)B.body_in, (const double *)B.x,
+  hipLaunchKernelGGL(k_split, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, (const double *)B.body_in, (const double *)B.x,
                      S.N_blb, n3, B.U, B.F);
   RBL_HIP(c, hipGetLastError());
   return RBL_OK;
 }
 
-// the workspace with the host's mask, body_in and slip in place; model: the force model's loads at the current configuration added
-// to the free bodies' slots of body_in (the steps)
+// the workspace with the host's mask (B.per entries per body), body_in and slip in place; model: the force model's loads at the
+// current configuration added to the free slots of body_in (the steps)
 int mx_upload(rbl_ctx *c, MxBuf &B, const uint8_t *prescribed, const double *body_in, const double *slip, bool model, int np)
 {
   const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
   int rc = mx_reserve(c, B); if (rc) return rc;
-  if ((rc = copy_h2d(c, B.mask, prescribed, (size_t)c->S.N_bod))) return rc;
+  if ((rc = copy_h2d(c, B.mask, prescribed, (size_t)B.per * (size_t)c->S.N_bod))) return rc;
   if ((rc = copy_h2d(c, B.body_in, body_in, sizeof(double) * nb6))) return rc;
   if (slip && (rc = copy_h2d(c, B.slip, slip, sizeof(double) * n3))) return rc;
-  if (model && c->ia_on && np < c->S.N_bod) {            // -K^T f_phys at q^n, free bodies only (no free body: nothing feels the model)
+  if (model && c->ia_on && np < B.per * c->S.N_bod) {    // -K^T f_phys at q^n, free slots only (none free: nothing feels the model)
     RBL_HIP(c, hipMemsetAsync(B.model, 0, sizeof(double) * nb6, c->stream));
     if ((rc = ia_add_to_step_force(c, B.model))) return rc;
-    hipLaunchKernelGGL(k_mx_add_free, dim3((unsigned)((nb6 + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)B.mask,
-                       (const double *)B.model, (int)nb6, B.body_in);
+    hipLaunchKernelGGL(B.per == 6 ? k_mxd_add_free : k_mx_add_free, dim3((unsigned)((nb6 + 255) / 256)), dim3(256), 0, c->stream,
+                       (const uint8_t *)B.mask, (const double *)B.model, (int)nb6, B.body_in);
   }
   return RBL_OK;
 }
 
 // host arrays in, host arrays out; model: add the force model's loads to the free bodies (the step)
 int mx_host(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
-            bool model, double *lambda, double *U, double *F, int *iters, double *resid)
+            bool model, double *lambda, double *U, double *F, int *iters, double *resid, int per = 1)
 {
   int np = 0;
-  int rc = mx_check(c, who, prescribed, body_in, max_iter, rtol, true, &np); if (rc) return rc;
+  int rc = mx_check(c, who, prescribed, body_in, max_iter, rtol, true, &np, per); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
   MxBuf B;
+  B.per = per;
   if ((rc = mx_upload(c, B, prescribed, body_in, slip, model, np))) return rc;
   if ((rc = mx_solve(c, B, slip != nullptr, np, max_iter, rtol, iters, resid))) return rc;
   if (lambda && (rc = copy_d2h(c, lambda, B.x, sizeof(double) * n3))) return rc;
@@ -345,11 +707,43 @@ int mx_host(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double
   return finish_and_check(c);
 }
 
+// device arrays in, device arrays out, the mask (per entries per body) from the host; the stream is drained where the solver drains it
+int mx_dev(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *d_body_in, const double *d_slip, int max_iter, double rtol,
+           double *d_lambda, double *d_U, double *d_F, int *iters, double *resid, int per)
+{
+  if (c && (!d_U || !d_F)) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": U or F is NULL");
+  int np = 0;
+  int rc = mx_check(c, who, prescribed, d_body_in, max_iter, rtol, false, &np, per); if (rc) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nmask = (size_t)per * (size_t)c->S.N_bod;
+  MxBuf B;
+  B.per = per;
+  if ((rc = mx_reserve(c, B))) return rc;
+  // the mask goes up from the context's pinned megabyte (idle between the solver's read-backs, which drain the stream): a true
+  // asynchronous copy, so the caller's array may go after the call and the stream is not drained for it
+  constexpr size_t pin_bytes = (size_t)1 << 20;
+  if (nmask <= pin_bytes) {
+    if (!c->h_pin) RBL_HIP(c, hipHostMalloc(&c->h_pin, pin_bytes, hipHostMallocDefault));
+    std::memcpy(c->h_pin, prescribed, nmask);
+    RBL_HIP(c, hipMemcpyAsync(B.mask, c->h_pin, nmask, hipMemcpyHostToDevice, c->stream));
+  } else {
+    RBL_HIP(c, hipMemcpyAsync(B.mask, prescribed, nmask, hipMemcpyHostToDevice, c->stream));
+    RBL_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  RBL_HIP(c, hipMemcpyAsync(B.body_in, d_body_in, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
+  if (d_slip) RBL_HIP(c, hipMemcpyAsync(B.slip, d_slip, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
+  if ((rc = mx_solve(c, B, d_slip != nullptr, np, max_iter, rtol, iters, resid))) return rc;
+  if (d_lambda) RBL_HIP(c, hipMemcpyAsync(d_lambda, B.x, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
+  RBL_HIP(c, hipMemcpyAsync(d_U, B.U, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
+  RBL_HIP(c, hipMemcpyAsync(d_F, B.F, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
+  return RBL_OK;
+}
+
 int mx_step(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
-            double *F, int *iters, double *resid)
+            double *F, int *iters, double *resid, int per = 1)
 {
   std::vector<double> U((size_t)6 * (size_t)(c->S.N_bod > 0 ? c->S.N_bod : 1));
-  const int rc = mx_host(c, who, prescribed, body_in, slip, max_iter, rtol, true, nullptr, U.data(), F, iters, resid);
+  const int rc = mx_host(c, who, prescribed, body_in, slip, max_iter, rtol, true, nullptr, U.data(), F, iters, resid, per);
   if (rc) return rc;
   c->step_hist_n = 0;                                    // the warm starts of rbl_step_deterministic extrapolate over ITS steps only
   return rbl_evolve_X_Q(c, U.data());
@@ -383,31 +777,7 @@ int rbl_solve_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in
 int rbl_solve_mixed_dev(rbl_ctx *c, const uint8_t *prescribed, const double *d_body_in, const double *d_slip, int max_iter, double rtol,
                         double *d_lambda, double *d_U, double *d_F, int *iters, double *resid)
 {
-  if (c && (!d_U || !d_F)) return rbl_fail(c, RBL_ERR_ARG, "solve_mixed_dev: U or F is NULL");
-  int np = 0;
-  int rc = mx_check(c, "solve_mixed_dev", prescribed, d_body_in, max_iter, rtol, false, &np); if (rc) return rc;
-  if ((rc = rbl_dev_init(c))) return rc;
-  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
-  MxBuf B;
-  if ((rc = mx_reserve(c, B))) return rc;
-  // the mask goes up from the context's pinned megabyte (idle between the solver's read-backs, which drain the stream): a true
-  // asynchronous copy, so the caller's array may go after the call and the stream is not drained for it
-  constexpr size_t pin_bytes = (size_t)1 << 20;
-  if ((size_t)c->S.N_bod <= pin_bytes) {
-    if (!c->h_pin) RBL_HIP(c, hipHostMalloc(&c->h_pin, pin_bytes, hipHostMallocDefault));
-    std::memcpy(c->h_pin, prescribed, (size_t)c->S.N_bod);
-    RBL_HIP(c, hipMemcpyAsync(B.mask, c->h_pin, (size_t)c->S.N_bod, hipMemcpyHostToDevice, c->stream));
-  } else {
-    RBL_HIP(c, hipMemcpyAsync(B.mask, prescribed, (size_t)c->S.N_bod, hipMemcpyHostToDevice, c->stream));
-    RBL_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  RBL_HIP(c, hipMemcpyAsync(B.body_in, d_body_in, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
-  if (d_slip) RBL_HIP(c, hipMemcpyAsync(B.slip, d_slip, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
-  if ((rc = mx_solve(c, B, d_slip != nullptr, np, max_iter, rtol, iters, resid))) return rc;
-  if (d_lambda) RBL_HIP(c, hipMemcpyAsync(d_lambda, B.x, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
-  RBL_HIP(c, hipMemcpyAsync(d_U, B.U, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
-  RBL_HIP(c, hipMemcpyAsync(d_F, B.F, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
-  return RBL_OK;
+  return mx_dev(c, "solve_mixed_dev", prescribed, d_body_in, d_slip, max_iter, rtol, d_lambda, d_U, d_F, iters, resid, 1);
 }
 
 int rbl_step_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol, double *F,
@@ -415,6 +785,27 @@ int rbl_step_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in,
 {
   if (!c) return RBL_ERR_ARG;
   return mx_step(c, "step_mixed", prescribed, body_in, slip, max_iter, rtol, F, iters, resid);
+}
+
+// ---- a mask per velocity component: prescribed6[6 N_bod], the same workers with six mask entries per body ----------------------------
+int rbl_solve_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter, double rtol,
+                        double *lambda, double *U, double *F, int *iters, double *resid)
+{
+  if (c && (!U || !F)) return rbl_fail(c, RBL_ERR_ARG, "solve_mixed_dof: U or F is NULL");
+  return mx_host(c, "solve_mixed_dof", prescribed6, body_in, slip, max_iter, rtol, false, lambda, U, F, iters, resid, 6);
+}
+
+int rbl_solve_mixed_dof_dev(rbl_ctx *c, const uint8_t *prescribed6, const double *d_body_in, const double *d_slip, int max_iter,
+                            double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid)
+{
+  return mx_dev(c, "solve_mixed_dof_dev", prescribed6, d_body_in, d_slip, max_iter, rtol, d_lambda, d_U, d_F, iters, resid, 6);
+}
+
+int rbl_step_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter, double rtol,
+                       double *F, int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  return mx_step(c, "step_mixed_dof", prescribed6, body_in, slip, max_iter, rtol, F, iters, resid, 6);
 }
 
 int rbl_RHS_and_Midpoint_mixed_dev(rbl_ctx *c, const uint8_t *prescribed, const double *d_body_in, const double *d_slip,

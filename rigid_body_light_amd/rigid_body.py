@@ -11,7 +11,8 @@ Beyond the reference surface (its C++ has these, its Python does not): `solve_sa
 `body_mobility_matrix`, `M_half_W`, `M_RFD`,
 `KTinv_RFD`, `M_RFD_cfgs`, `M_RFD_from_U`, `KT_RFD_from_U`, `evolve_rigid_bodies_RFD`, `apply_M_multi`,
 `dense_mobility`, `velocity_field` (the flow at arbitrary points), prescribed kinematics (`solve_mixed`, `step_mixed`,
-`body_resistance_matrix`: bodies that are held or driven, and the loads that takes; `step_brownian_mixed`,
+`body_resistance_matrix`: bodies that are held or driven, and the loads that takes; `solve_mixed_dof`, `step_mixed_dof`: the same for
+single velocity components; `step_brownian_mixed`,
 `RHS_and_Midpoint_mixed`: the same among Brownian bodies), and a force model the reference does not have (`set_interactions`, `interaction_forces`).
 """
 import numpy as np
@@ -268,7 +269,9 @@ class RigidBody:
         return mask
 
     def _mixed_args(self, prescribed, body_in, slip):
-        mask = self._prescribed_mask(prescribed)
+        return (self._prescribed_mask(prescribed),) + self._body_in_and_slip(body_in, slip)
+
+    def _body_in_and_slip(self, body_in, slip):
         bi = np.asarray(body_in, dtype=np.float64)
         if bi.size != 6 * self.N_bodies:
             raise ValueError(f"body_in must have total size 6*N_bodies = {6 * self.N_bodies}. Got shape: {bi.shape}")
@@ -278,7 +281,7 @@ class RigidBody:
             if sl.size != 3 * self.total_blobs:
                 raise ValueError(f"slip must have total size 3*N_blobs = {3 * self.total_blobs}. Got shape: {sl.shape}")
             sl = sl.reshape(-1)
-        return mask, bi.reshape(-1), sl
+        return bi.reshape(-1), sl
 
     def solve_mixed(self, prescribed, body_in, slip=None, max_iter=100, rtol=1.0e-8):
         """Prescribed kinematics: the bodies in `prescribed` (boolean array of N_bodies, or a list of body indices) move with the
@@ -299,6 +302,31 @@ class RigidBody:
         fluid supplies (the model's share included).  -> (F, iterations, residual estimate)"""
         mask, bi, sl = self._mixed_args(prescribed, body_in, slip)
         return self.cb.step_mixed(mask, bi, sl, int(max_iter), float(rtol))
+
+    def _mixed_dof_args(self, prescribed, body_in, slip):
+        p = np.asarray(prescribed)
+        if p.dtype != np.bool_ or p.shape != (self.N_bodies, 6):
+            raise ValueError(f"prescribed must be a boolean array of shape (N_bodies, 6) = ({self.N_bodies}, 6): one entry per velocity "
+                             f"component (translation x, y, z, rotation x, y, z). Got dtype {p.dtype}, shape {p.shape}")
+        return (np.ascontiguousarray(p, dtype=np.uint8).reshape(-1),) + self._body_in_and_slip(body_in, slip)
+
+    def solve_mixed_dof(self, prescribed, body_in, slip=None, max_iter=100, rtol=1.0e-8):
+        """Prescribed kinematics per velocity component: `prescribed` is a boolean array of shape (N_bodies, 6) over each body's
+        lab-frame components (translation x, y, z, then rotation x, y, z, the order of body_in).  A prescribed component moves with
+        the velocity in its slot of body_in (zero holds it), a free one carries its load there: a microroller has its rotation
+        prescribed and its translation free, a trapped particle the reverse, a quasi-2D suspension only U_z = 0.  The solver is
+        solve_mixed's (the cost has not been measured yet), and with whole rows set the results are solve_mixed's.  -> (lambda, U, F, iterations, residual estimate): U
+        with the prescribed components echoed, F with the free components echoed and -K^T lambda on the prescribed ones (the force
+        or torque along that component that it takes)."""
+        mask, bi, sl = self._mixed_dof_args(prescribed, body_in, slip)
+        return self.cb.solve_mixed_dof(mask, bi, sl, int(max_iter), float(rtol))
+
+    def step_mixed_dof(self, prescribed, body_in, slip=None, max_iter=50, rtol=1.0e-8):
+        """One deterministic time step with a mask per velocity component: solve_mixed_dof at the current configuration, then
+        evolve_rigid_bodies(U).  With the force model on its loads are added to the FREE components only; the F of a prescribed
+        component is the total load along it that everything other than the fluid supplies.  -> (F, iterations, residual estimate)"""
+        mask, bi, sl = self._mixed_dof_args(prescribed, body_in, slip)
+        return self.cb.step_mixed_dof(mask, bi, sl, int(max_iter), float(rtol))
 
     def _noise_arg(self, W):
         if W is None:
