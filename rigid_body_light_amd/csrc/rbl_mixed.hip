@@ -3,14 +3,15 @@
 // Shared internals are declared in rbl_api_internal.hpp.  Nothing here falls back to a CPU path.
 //
 // The system:  A x = [M lambda - K (D_f U) ; D_f K^T lambda + D_p U] = [slip + K_p U_p ; -F_f on free bodies, 0 on prescribed ones]
-// (D_f, D_p: 0/1 per body, or per velocity component in the _dof entry points: the k_mxd_ kernels, whose body-row solves go
-// through 6 x 6 factors masked once per solve).  The body slots that are prescribed carry the identity, start at 0 and stay 0
-// through every Krylov vector, so |rhs| is the norm of the physical right-hand side alone.  The mobility product is the library's own
-// (apply_M_enqueue, untouched); what is new around it -- the masked K / K^T tail, the masked preconditioner tails, the right-hand
-// side and the split of the solution -- are the O(N) kernels below: one workgroup per body, the mask read once per workgroup (the
-// branch on it is uniform), deterministic LDS tree sums, no atomics; the K / K^T formulas, the workgroup sum and the 6 x 6
-// substitution are rbl_body_dev.hpp's, shared with rbl_body_dev.hip.  The Arnoldi recurrence, the Hessenberg solve and the
-// convergence test are gmres_core's (gmres_core_with_ops).
+// (D_f, D_p: diagonal 0/1 on a body's six lab-frame velocity components.  The mask has one entry per body, or six in the _dof entry
+// points: one kernel family serves both, a whole-body mask being the component mask with none or all six of a body's bits set; the
+// body-row solves of a component mask go through 6 x 6 factors masked once per solve).  The body slots that are prescribed carry the
+// identity, start at 0 and stay 0 through every Krylov vector, so |rhs| is the norm of the physical right-hand side alone.  The
+// mobility product is the library's own (apply_M_enqueue, untouched); what is new around it -- the masked K / K^T tail, the masked
+// preconditioner tails, the right-hand side and the split of the solution -- are the O(N) kernels below: one workgroup per body, the
+// mask read once per workgroup (the branch on it is uniform), deterministic LDS tree sums, no atomics; the K / K^T formulas, the
+// workgroup sum and the 6 x 6 substitution are rbl_body_dev.hpp's, shared with rbl_body_dev.hip.  The Arnoldi recurrence, the
+// Hessenberg solve and the convergence test are gmres_core's (gmres_core_with_ops).
 //
 // The Brownian midpoint step with prescribed bodies has its entry points here and nothing of the scheme: right-hand side, predictor
 // and the sequence of the step are rbl_steps.hip's (rhs_and_midpoint_core, step_midpoint), which the all-free step goes through with
@@ -25,206 +26,39 @@ namespace {
 
 constexpr int MT = 256;
 
-// right-hand side: top = slip + K_p U_p, bottom = -F_b (free body) or 0 (prescribed body)
-__global__ __launch_bounds__(MT) void k_mx_rhs(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
+// The mask of the workgroup's body as one scalar bit set (bit c: component c prescribed), so every branch on it is uniform.
+// per = mask entries per body: 6 (one per velocity component), or 1 (whole bodies: no bit or all six).
+__device__ __forceinline__ unsigned mx_bits(const uint8_t *__restrict__ mask, int per, int b)
+{
+  unsigned pm = 0;
+  if (per == 6) {
+    const uint8_t *m = mask + 6 * (size_t)b;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) pm |= (m[c] != 0 ? 1u : 0u) << c;
+  } else {
+    pm = mask[b] != 0 ? 63u : 0u;
+  }
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)pm);
+}
+
+// a fully prescribed body (pm == 63) in the operator and the preconditioners: lambda_b = v_b, the six body slots pass through
+__device__ __forceinline__ void mx_pass_through(const double *__restrict__ v, const double *g, int b, int t, int N_blb, long n3,
+                                                double *__restrict__ out)
+{
+  for (int k = t; k < N_blb; k += MT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    out[idx] = v[idx]; out[idx + 1] = v[idx + 1]; out[idx + 2] = v[idx + 2];
+  }
+  if (t < 6) out[n3 + 6 * (size_t)b + t] = g[t];
+}
+
+// right-hand side: top = slip + K D_p U_in, bottom = -F_in on the free components, 0 on the prescribed ones
+__global__ __launch_bounds__(MT) void k_mx_rhs(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
                                                const double *__restrict__ body_in, const double *__restrict__ slip, int N_blb,
                                                long n3, double *__restrict__ rhs)
 {
   const int b = blockIdx.x, t = threadIdx.x;
-  const bool pres = mask[b] != 0;
-  const double *u = body_in + 6 * (size_t)b;
-  for (int k = t; k < N_blb; k += MT) {
-    const size_t idx = 3 * ((size_t)b * N_blb + k);
-    double r0 = slip ? slip[idx] : 0.0, r1 = slip ? slip[idx + 1] : 0.0, r2 = slip ? slip[idx + 2] : 0.0;
-    if (pres) {
-      double k0, k1, k2;
-      rbl_KU(lever + idx, u, k0, k1, k2);
-      r0 += k0; r1 += k1; r2 += k2;
-    }
-    rhs[idx] = r0; rhs[idx + 1] = r1; rhs[idx + 2] = r2;
-  }
-  if (t < 6) rhs[n3 + 6 * (size_t)b + t] = pres ? 0.0 : -u[t];
-}
-
-// the operator's tail after sub = M lambda: out = [sub - K (D_f U) ; D_f K^T lambda + D_p U]
-__global__ __launch_bounds__(MT) void k_mx_op_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
-                                                   const double *__restrict__ x, const double *__restrict__ sub, int N_blb, long n3,
-                                                   double *__restrict__ out)
-{
-  __shared__ double s[6][MT];
-  const int b = blockIdx.x, t = threadIdx.x;
-  const double *u = x + n3 + 6 * (size_t)b;
-  if (mask[b]) {                                         // prescribed: no velocity unknown, no balance row
-    for (int k = t; k < N_blb; k += MT) {
-      const size_t idx = 3 * ((size_t)b * N_blb + k);
-      out[idx] = sub[idx]; out[idx + 1] = sub[idx + 1]; out[idx + 2] = sub[idx + 2];
-    }
-    if (t < 6) out[n3 + 6 * (size_t)b + t] = u[t];
-    return;
-  }
-  double f[6] = {0, 0, 0, 0, 0, 0};
-  for (int k = t; k < N_blb; k += MT) {
-    const size_t idx = 3 * ((size_t)b * N_blb + k);
-    const double *l = lever + idx;
-    double k0, k1, k2;
-    rbl_KU(l, u, k0, k1, k2);
-    out[idx] = sub[idx] - k0; out[idx + 1] = sub[idx + 1] - k1; out[idx + 2] = sub[idx + 2] - k2;
-    rbl_KT_acc(l, x[idx], x[idx + 1], x[idx + 2], f);
-  }
-  rbl_block_sum<6, MT>(f, s, t);
-  if (t < 6) out[n3 + 6 * (size_t)b + t] = f[t];
-}
-
-// block preconditioner after y1 = invM slip (ONE pass over the per-body factors, all bodies).  Free body: what k_pc_block_tail does
-// with the force block's sign restored -- f = K^T y1, U = N^-1 (g - f), lambda = y1 + (invM K) U, the exact inverse of
-// [M_b -K_b; K_b^T 0] on [slip_b; g_b].  Prescribed body: lambda = y1, the six body slots pass through.
-__global__ __launch_bounds__(MT) void k_mx_pc_block_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
-                                                         const double *__restrict__ y1, const double *__restrict__ MK, long stride,
-                                                         const double *__restrict__ NL, const double *__restrict__ in, int N_blb,
-                                                         long n3, double *__restrict__ out)
-{
-  __shared__ double s[6][MT];
-  __shared__ double us[6];
-  const int b = blockIdx.x, t = threadIdx.x;
-  const double *g = in + n3 + 6 * (size_t)b;
-  if (mask[b]) {
-    for (int k = t; k < N_blb; k += MT) {
-      const size_t idx = 3 * ((size_t)b * N_blb + k);
-      out[idx] = y1[idx]; out[idx + 1] = y1[idx + 1]; out[idx + 2] = y1[idx + 2];
-    }
-    if (t < 6) out[n3 + 6 * (size_t)b + t] = g[t];
-    return;
-  }
-  double f[6] = {0, 0, 0, 0, 0, 0};
-  for (int k = t; k < N_blb; k += MT) {
-    const size_t idx = 3 * ((size_t)b * N_blb + k);
-    rbl_KT_acc(lever + idx, y1[idx], y1[idx + 1], y1[idx + 2], f);
-  }
-  rbl_block_sum<6, MT>(f, s, t);
-  if (t == 0) {
-    double r[6], u[6];
-    for (int p = 0; p < 6; ++p) r[p] = g[p] - f[p];
-    rbl_chol6_solve(NL + 36 * (size_t)b, r, u);
-    for (int p = 0; p < 6; ++p) { us[p] = u[p]; out[n3 + 6 * (size_t)b + p] = u[p]; }
-  }
-  __syncthreads();
-  for (int k = t; k < N_blb; k += MT) {
-    const size_t idx = 3 * ((size_t)b * N_blb + k);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      double acc = y1[idx + d];
-#pragma unroll
-      for (int c = 0; c < 6; ++c) acc = __builtin_fma(MK[(size_t)c * stride + idx + d], us[c], acc);
-      out[idx + d] = acc;
-    }
-  }
-}
-
-// diagonal preconditioner (invM2: the self-block scaling per blob, x/y and z).  Free body: k_pc_diag_apply with the force block's
-// sign restored; prescribed body: lambda = invM slip, the six body slots pass through.
-__global__ __launch_bounds__(MT) void k_mx_pc_diag(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
-                                                   const double *__restrict__ invM2, const double *__restrict__ NL, int N_blb, long n3,
-                                                   const double *__restrict__ in, double *__restrict__ out)
-{
-  __shared__ double s[6][MT];
-  __shared__ double us[6];
-  const int b = blockIdx.x, t = threadIdx.x;
-  const double *g = in + n3 + 6 * (size_t)b;
-  if (mask[b]) {
-    for (int k = t; k < N_blb; k += MT) {
-      const size_t i = (size_t)b * N_blb + k;
-      out[3 * i] = invM2[2 * i] * in[3 * i]; out[3 * i + 1] = invM2[2 * i] * in[3 * i + 1];
-      out[3 * i + 2] = invM2[2 * i + 1] * in[3 * i + 2];
-    }
-    if (t < 6) out[n3 + 6 * (size_t)b + t] = g[t];
-    return;
-  }
-  double f[6] = {0, 0, 0, 0, 0, 0};
-  for (int k = t; k < N_blb; k += MT) {                  // K^T (invM slip)
-    const size_t i = (size_t)b * N_blb + k;
-    rbl_KT_acc(lever + 3 * i, invM2[2 * i] * in[3 * i], invM2[2 * i] * in[3 * i + 1], invM2[2 * i + 1] * in[3 * i + 2], f);
-  }
-  rbl_block_sum<6, MT>(f, s, t);
-  if (t == 0) {
-    double r[6], u[6];
-    for (int p = 0; p < 6; ++p) r[p] = g[p] - f[p];
-    rbl_chol6_solve(NL + 36 * (size_t)b, r, u);
-    for (int p = 0; p < 6; ++p) { us[p] = u[p]; out[n3 + 6 * (size_t)b + p] = u[p]; }
-  }
-  __syncthreads();
-  for (int k = t; k < N_blb; k += MT) {                  // lambda = invM (slip + K U)
-    const size_t i = (size_t)b * N_blb + k;
-    double k0, k1, k2;
-    rbl_KU(lever + 3 * i, us, k0, k1, k2);
-    out[3 * i] = invM2[2 * i] * (in[3 * i] + k0);
-    out[3 * i + 1] = invM2[2 * i] * (in[3 * i + 1] + k1);
-    out[3 * i + 2] = invM2[2 * i + 1] * (in[3 * i + 2] + k2);
-  }
-}
-
-// free-space body-frame tables: `out` holds the ordinary preconditioner's answer for every body; the prescribed ones take
-// lambda = y1 (a second factor application) and their six body slots from the input instead
-__global__ __launch_bounds__(MT) void k_mx_pc_select(const uint8_t *__restrict__ mask, const double *__restrict__ y1,
-                                                     const double *__restrict__ in, int N_blb, long n3, double *__restrict__ out)
-{
-  const int b = blockIdx.x, t = threadIdx.x;
-  if (!mask[b]) return;
-  for (int k = t; k < N_blb; k += MT) {
-    const size_t idx = 3 * ((size_t)b * N_blb + k);
-    out[idx] = y1[idx]; out[idx + 1] = y1[idx + 1]; out[idx + 2] = y1[idx + 2];
-  }
-  if (t < 6) out[n3 + 6 * (size_t)b + t] = in[n3 + 6 * (size_t)b + t];
-}
-
-// the solution split: U = the solved velocity (free) or the prescribed one (echoed); F = the given load (free, echoed) or
-// -K_b^T lambda (prescribed)
-__global__ __launch_bounds__(MT) void k_mx_split(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
-                                                 const double *__restrict__ body_in, const double *__restrict__ x, int N_blb, long n3,
-                                                 double *__restrict__ U, double *__restrict__ F)
-{
-  __shared__ double s[6][MT];
-  const int b = blockIdx.x, t = threadIdx.x;
-  const size_t o = 6 * (size_t)b;
-  if (!mask[b]) {
-    if (t < 6) { U[o + t] = x[n3 + o + t]; F[o + t] = body_in[o + t]; }
-    return;
-  }
-  double f[6] = {0, 0, 0, 0, 0, 0};
-  for (int k = t; k < N_blb; k += MT) {
-    const size_t idx = 3 * ((size_t)b * N_blb + k);
-    rbl_KT_acc(lever + idx, x[idx], x[idx + 1], x[idx + 2], f);
-  }
-  rbl_block_sum<6, MT>(f, s, t);
-  if (t < 6) { U[o + t] = body_in[o + t]; F[o + t] = -f[t]; }
-}
-
-// v += add on the six slots of every free body (the force model's loads enter the free bodies only)
-__global__ void k_mx_add_free(const uint8_t *__restrict__ mask, const double *__restrict__ add, int nb6, double *__restrict__ v)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nb6 && !mask[i / 6]) v[i] += add[i];
-}
-
-// ---- masks per velocity component (rbl_solve_mixed_dof): the kernels above with D_f, D_p diagonal 0/1 on a body's six lab-frame
-// components.  The six mask bytes of the workgroup's body become one scalar bit set (bit c: component c prescribed), so every branch
-// on it is uniform; a body with no bit set or all six takes the arithmetic of the kernels above in the same order.
-
-__device__ __forceinline__ unsigned mxd_bits(const uint8_t *__restrict__ mask6, int b)
-{
-  const uint8_t *m = mask6 + 6 * (size_t)b;
-  unsigned pm = 0;
-#pragma unroll
-  for (int c = 0; c < 6; ++c) pm |= (m[c] != 0 ? 1u : 0u) << c;
-  return (unsigned)__builtin_amdgcn_readfirstlane((int)pm);
-}
-
-// right-hand side: top = slip + K D_p U_in, bottom = -F_in on the free components, 0 on the prescribed ones
-__global__ __launch_bounds__(MT) void k_mxd_rhs(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
-                                                const double *__restrict__ body_in, const double *__restrict__ slip, int N_blb,
-                                                long n3, double *__restrict__ rhs)
-{
-  const int b = blockIdx.x, t = threadIdx.x;
-  const unsigned pm = mxd_bits(mask6, b);
+  const unsigned pm = mx_bits(mask, per, b);
   const double *u = body_in + 6 * (size_t)b;
   double up[6];
 #pragma unroll
@@ -243,22 +77,15 @@ __global__ __launch_bounds__(MT) void k_mxd_rhs(const double *__restrict__ lever
 }
 
 // the operator's tail after sub = M lambda: out = [sub - K (D_f U) ; D_f K^T lambda + D_p U]
-__global__ __launch_bounds__(MT) void k_mxd_op_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
-                                                    const double *__restrict__ x, const double *__restrict__ sub, int N_blb, long n3,
-                                                    double *__restrict__ out)
+__global__ __launch_bounds__(MT) void k_mx_op_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
+                                                   const double *__restrict__ x, const double *__restrict__ sub, int N_blb, long n3,
+                                                   double *__restrict__ out)
 {
   __shared__ double s[6][MT];
   const int b = blockIdx.x, t = threadIdx.x;
-  const unsigned pm = mxd_bits(mask6, b);
+  const unsigned pm = mx_bits(mask, per, b);
   const double *u = x + n3 + 6 * (size_t)b;
-  if (pm == 63u) {                                       // no velocity unknown, no balance row
-    for (int k = t; k < N_blb; k += MT) {
-      const size_t idx = 3 * ((size_t)b * N_blb + k);
-      out[idx] = sub[idx]; out[idx + 1] = sub[idx + 1]; out[idx + 2] = sub[idx + 2];
-    }
-    if (t < 6) out[n3 + 6 * (size_t)b + t] = u[t];
-    return;
-  }
+  if (pm == 63u) { mx_pass_through(sub, u, b, t, N_blb, n3, out); return; }      // no velocity unknown, no balance row
   double uf[6];
 #pragma unroll
   for (int c = 0; c < 6; ++c) uf[c] = (pm >> c & 1u) ? 0.0 : u[c];
@@ -280,14 +107,15 @@ __global__ __launch_bounds__(MT) void k_mxd_op_tail(const double *__restrict__ l
   }
 }
 
-// The masked 6 x 6 factors, once per solve, one thread per body: R_b = L L^T from the context's factor (NL: per body, or with
-// `Q` the ONE body-frame factor of the free-space tables, taken to the lab frame first: R_lab = (I2 x Rot) R_body (I2 x Rot)^T),
-// rows and columns of the prescribed components replaced by the identity's, factored again -- a principal submatrix's Cholesky
-// factor is not a sub-block of NL.  A body with no bit set copies its own factor (Q NULL); with the shared factor nothing is
-// written for it, as no tail reads it there (the body-frame preconditioner's answer stands).  Not positive definite: the flag
-// k_pc_block_ninv latches.
-__global__ void k_mxd_factors(const double *__restrict__ NL, const double *__restrict__ Q, const uint8_t *__restrict__ mask6, int N_bod,
-                              double *__restrict__ NLm, unsigned *err)
+// The masked 6 x 6 factors of a solve with a mask per component, once per solve, one thread per body: R_b = L L^T from the context's
+// factor (NL: per body, or with `Q` the ONE body-frame factor of the free-space tables, taken to the lab frame first: R_lab =
+// (I2 x Rot) R_body (I2 x Rot)^T), rows and columns of the prescribed components replaced by the identity's, factored again -- a
+// principal submatrix's Cholesky factor is not a sub-block of NL.  A body with no bit set copies its own factor (Q NULL); with the
+// shared factor nothing is written for it, as no tail reads it there (the body-frame preconditioner's answer stands).  Not positive
+// definite: the flag k_pc_block_ninv latches.  Whole-body masks need none of this: a free body's factor is the context's own, a
+// prescribed body reads none.
+__global__ void k_mx_factors(const double *__restrict__ NL, const double *__restrict__ Q, const uint8_t *__restrict__ mask6, int N_bod,
+                             double *__restrict__ NLm, unsigned *err)
 {
   const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (b >= N_bod) return;
@@ -356,7 +184,7 @@ __global__ void k_mxd_factors(const double *__restrict__ NL, const double *__res
 
 // the six body rows of a preconditioner application from f = K_b^T y1 and the masked factor: (D_f R_b D_f + D_p) u = D_f (g - f) +
 // D_p g; the body slots take u (a prescribed slot: g, passed through), uf = D_f u goes on into lambda
-__device__ __forceinline__ void mxd_body_rows(const double *NLm_b, unsigned pm, const double *g, const double (&f)[6], double *out_b, double *uf)
+__device__ __forceinline__ void mx_body_rows(const double *NLm_b, unsigned pm, const double *g, const double (&f)[6], double *out_b, double *uf)
 {
   double r[6], u[6];
   for (int p = 0; p < 6; ++p) r[p] = (pm >> p & 1u) ? g[p] : g[p] - f[p];
@@ -368,32 +196,28 @@ __device__ __forceinline__ void mxd_body_rows(const double *NLm_b, unsigned pm, 
   }
 }
 
-// block preconditioner after y1 = invM slip: k_mx_pc_block_tail with the masked factor; lambda = y1 + (invM K) D_f u
-__global__ __launch_bounds__(MT) void k_mxd_pc_block_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
-                                                          const double *__restrict__ y1, const double *__restrict__ MK, long stride,
-                                                          const double *__restrict__ NLm, const double *__restrict__ in, int N_blb,
-                                                          long n3, double *__restrict__ out)
+// block preconditioner after y1 = invM slip (ONE pass over the per-body factors, all bodies).  A body with a free component: what
+// k_pc_block_tail does with the force block's sign restored and the masked factor -- f = K^T y1, the body rows of mx_body_rows,
+// lambda = y1 + (invM K) D_f u, the exact inverse of [M_b -K_b D_f; D_f K_b^T D_p] on [slip_b; g_b].  Fully prescribed body:
+// lambda = y1, the six body slots pass through.  NLm: the masked factors, or with a whole-body mask the context's own.
+__global__ __launch_bounds__(MT) void k_mx_pc_block_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
+                                                         const double *__restrict__ y1, const double *__restrict__ MK, long stride,
+                                                         const double *__restrict__ NLm, const double *__restrict__ in, int N_blb,
+                                                         long n3, double *__restrict__ out)
 {
   __shared__ double s[6][MT];
   __shared__ double us[6];
   const int b = blockIdx.x, t = threadIdx.x;
-  const unsigned pm = mxd_bits(mask6, b);
+  const unsigned pm = mx_bits(mask, per, b);
   const double *g = in + n3 + 6 * (size_t)b;
-  if (pm == 63u) {
-    for (int k = t; k < N_blb; k += MT) {
-      const size_t idx = 3 * ((size_t)b * N_blb + k);
-      out[idx] = y1[idx]; out[idx + 1] = y1[idx + 1]; out[idx + 2] = y1[idx + 2];
-    }
-    if (t < 6) out[n3 + 6 * (size_t)b + t] = g[t];
-    return;
-  }
+  if (pm == 63u) { mx_pass_through(y1, g, b, t, N_blb, n3, out); return; }
   double f[6] = {0, 0, 0, 0, 0, 0};
   for (int k = t; k < N_blb; k += MT) {
     const size_t idx = 3 * ((size_t)b * N_blb + k);
     rbl_KT_acc(lever + idx, y1[idx], y1[idx + 1], y1[idx + 2], f);
   }
   rbl_block_sum<6, MT>(f, s, t);
-  if (t == 0) mxd_body_rows(NLm + 36 * (size_t)b, pm, g, f, out + n3 + 6 * (size_t)b, us);
+  if (t == 0) mx_body_rows(NLm + 36 * (size_t)b, pm, g, f, out + n3 + 6 * (size_t)b, us);
   __syncthreads();
   for (int k = t; k < N_blb; k += MT) {
     const size_t idx = 3 * ((size_t)b * N_blb + k);
@@ -407,15 +231,17 @@ __global__ __launch_bounds__(MT) void k_mxd_pc_block_tail(const double *__restri
   }
 }
 
-// diagonal preconditioner: k_mx_pc_diag with the masked factor; lambda = invM (slip + K D_f u)
-__global__ __launch_bounds__(MT) void k_mxd_pc_diag(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
-                                                    const double *__restrict__ invM2, const double *__restrict__ NLm, int N_blb, long n3,
-                                                    const double *__restrict__ in, double *__restrict__ out)
+// diagonal preconditioner (invM2: the self-block scaling per blob, x/y and z).  A body with a free component: k_pc_diag_apply with
+// the force block's sign restored and the masked factor, lambda = invM (slip + K D_f u); fully prescribed body: lambda = invM slip,
+// the six body slots pass through.  NLm as in k_mx_pc_block_tail.
+__global__ __launch_bounds__(MT) void k_mx_pc_diag(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
+                                                   const double *__restrict__ invM2, const double *__restrict__ NLm, int N_blb, long n3,
+                                                   const double *__restrict__ in, double *__restrict__ out)
 {
   __shared__ double s[6][MT];
   __shared__ double us[6];
   const int b = blockIdx.x, t = threadIdx.x;
-  const unsigned pm = mxd_bits(mask6, b);
+  const unsigned pm = mx_bits(mask, per, b);
   const double *g = in + n3 + 6 * (size_t)b;
   if (pm == 63u) {
     for (int k = t; k < N_blb; k += MT) {
@@ -432,7 +258,7 @@ __global__ __launch_bounds__(MT) void k_mxd_pc_diag(const double *__restrict__ l
     rbl_KT_acc(lever + 3 * i, invM2[2 * i] * in[3 * i], invM2[2 * i] * in[3 * i + 1], invM2[2 * i + 1] * in[3 * i + 2], f);
   }
   rbl_block_sum<6, MT>(f, s, t);
-  if (t == 0) mxd_body_rows(NLm + 36 * (size_t)b, pm, g, f, out + n3 + 6 * (size_t)b, us);
+  if (t == 0) mx_body_rows(NLm + 36 * (size_t)b, pm, g, f, out + n3 + 6 * (size_t)b, us);
   __syncthreads();
   for (int k = t; k < N_blb; k += MT) {                  // lambda = invM (slip + K D_f u)
     const size_t i = (size_t)b * N_blb + k;
@@ -445,27 +271,22 @@ __global__ __launch_bounds__(MT) void k_mxd_pc_diag(const double *__restrict__ l
 }
 
 // free-space body-frame tables: `out` holds the ordinary preconditioner's answer for every body, which stands for a body with no
-// bit set; the others are redone from y1 = M_b^-1 slip_b (a second factor application, lab frame) with the masked lab-frame factor.
-// The table MKb = M_body^-1 K_body ([6][3 N_blb], one for all bodies) is in the body frame: M_b^-1 K_b D_f u = Rot MKb (I2 x Rot)^T D_f u
-__global__ __launch_bounds__(MT) void k_mxd_pc_bodyframe_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
-                                                              const double *__restrict__ y1, const double *__restrict__ MKb,
-                                                              const double *__restrict__ Q, const double *__restrict__ NLm,
-                                                              const double *__restrict__ in, int N_blb, long n3, double *__restrict__ out)
+// bit set; a fully prescribed body takes lambda = y1 = M_b^-1 slip_b (a second factor application, lab frame) and its six body
+// slots from the input; a partly prescribed one is redone from y1 with the masked lab-frame factor.
+// The table MKb = M_body^-1 K_body ([6][3 N_blb], one for all bodies) is in the body frame: M_b^-1 K_b D_f u = Rot MKb (I2 x Rot)^T D_f u.
+// Only a partial mask reads lever, MKb, Q and NLm: with a whole-body mask (per == 1) Q and NLm are NULL.
+__global__ __launch_bounds__(MT) void k_mx_pc_bodyframe_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
+                                                             const double *__restrict__ y1, const double *__restrict__ MKb,
+                                                             const double *__restrict__ Q, const double *__restrict__ NLm,
+                                                             const double *__restrict__ in, int N_blb, long n3, double *__restrict__ out)
 {
   __shared__ double s[6][MT];
   __shared__ double us[6];
   const int b = blockIdx.x, t = threadIdx.x;
-  const unsigned pm = mxd_bits(mask6, b);
+  const unsigned pm = mx_bits(mask, per, b);
   if (pm == 0u) return;
   const double *g = in + n3 + 6 * (size_t)b;
-  if (pm == 63u) {
-    for (int k = t; k < N_blb; k += MT) {
-      const size_t idx = 3 * ((size_t)b * N_blb + k);
-      out[idx] = y1[idx]; out[idx + 1] = y1[idx + 1]; out[idx + 2] = y1[idx + 2];
-    }
-    if (t < 6) out[n3 + 6 * (size_t)b + t] = g[t];
-    return;
-  }
+  if (pm == 63u) { mx_pass_through(y1, g, b, t, N_blb, n3, out); return; }
   double R[9];
   quat_rot(Q + 4 * (size_t)b, R);
   double f[6] = {0, 0, 0, 0, 0, 0};
@@ -476,7 +297,7 @@ __global__ __launch_bounds__(MT) void k_mxd_pc_bodyframe_tail(const double *__re
   rbl_block_sum<6, MT>(f, s, t);
   if (t == 0) {
     double uf[6];
-    mxd_body_rows(NLm + 36 * (size_t)b, pm, g, f, out + n3 + 6 * (size_t)b, uf);
+    mx_body_rows(NLm + 36 * (size_t)b, pm, g, f, out + n3 + 6 * (size_t)b, uf);
     for (int h = 0; h < 2; ++h)                          // (I2 x Rot)^T D_f u
       for (int d = 0; d < 3; ++d) us[3 * h + d] = R[d] * uf[3 * h] + R[3 + d] * uf[3 * h + 1] + R[6 + d] * uf[3 * h + 2];
   }
@@ -498,20 +319,20 @@ __global__ __launch_bounds__(MT) void k_mxd_pc_bodyframe_tail(const double *__re
 }
 
 // v += add on the free components (the force model's loads enter the free components only)
-__global__ void k_mxd_add_free(const uint8_t *__restrict__ mask6, const double *__restrict__ add, int nb6, double *__restrict__ v)
+__global__ void k_mx_add_free(const uint8_t *__restrict__ mask, int per, const double *__restrict__ add, int nb6, double *__restrict__ v)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nb6 && !mask6[i]) v[i] += add[i];
+  if (i < nb6 && !mask[per == 6 ? i : i / 6]) v[i] += add[i];
 }
 
 // the solution split: U = D_f U_solved + D_p U_in (echoed), F = D_f F_in (echoed) + D_p (-K_b^T lambda)
-__global__ __launch_bounds__(MT) void k_mxd_split(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
-                                                  const double *__restrict__ body_in, const double *__restrict__ x, int N_blb, long n3,
-                                                  double *__restrict__ U, double *__restrict__ F)
+__global__ __launch_bounds__(MT) void k_mx_split(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
+                                                 const double *__restrict__ body_in, const double *__restrict__ x, int N_blb, long n3,
+                                                 double *__restrict__ U, double *__restrict__ F)
 {
   __shared__ double s[6][MT];
   const int b = blockIdx.x, t = threadIdx.x;
-  const unsigned pm = mxd_bits(mask6, b);
+  const unsigned pm = mx_bits(mask, per, b);
   const size_t o = 6 * (size_t)b;
   if (pm == 0u) {
     if (t < 6) { U[o + t] = x[n3 + o + t]; F[o + t] = body_in[o + t]; }
@@ -534,7 +355,7 @@ __global__ __launch_bounds__(MT) void k_mxd_split(const double *__restrict__ lev
 
 struct MxBuf {           // the one workspace of a section 7 entry point (rbl_ctx::d_mx)
   double *rhs, *x, *y1, *body_in, *slip, *U, *F, *model;
-  double *NLm;           // the masked 6 x 6 factors of a solve with a mask per component (k_mxd_factors)
+  double *NLm;           // the masked 6 x 6 factors of a solve with a mask per component (k_mx_factors); NULL with per == 1
   uint8_t *mask;         // per * N_bod entries
   int per = 1;           // mask entries per body: 1 (whole bodies) or 6 (velocity components, the _dof entry points)
 };
@@ -563,9 +384,8 @@ int mx_op(rbl_ctx *c, void *user, const double *d_x, double *d_out)
   const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N;
   int rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3); if (rc) return rc;
   if ((rc = apply_M_enqueue(c, S.wall, d_x, (const double *)c->d_pos.p, N, 0, N, (double *)c->d_sad.p))) return rc;
-  const auto k_tail = m->B->per == 6 ? k_mxd_op_tail : k_mx_op_tail;
-  hipLaunchKernelGGL(k_tail, dim3((unsigned)S.N_bod), dim3(MT), 0, c->stream, (const double *)c->d_lever.p, (const uint8_t *)m->B->mask, d_x,
-                     (const double *)c->d_sad.p, S.N_blb, (long)n3, d_out);
+  hipLaunchKernelGGL(k_mx_op_tail, dim3((unsigned)S.N_bod), dim3(MT), 0, c->stream, (const double *)c->d_lever.p,
+                     (const uint8_t *)m->B->mask, m->B->per, d_x, (const double *)c->d_sad.p, S.N_blb, (long)n3, d_out);
   return RBL_OK;
 }
 
@@ -583,41 +403,33 @@ int mx_pc(rbl_ctx *c, void *user, const double *d_in, double *d_out)
   const long n3 = 3 * (long)S.N_bod * S.N_blb;
   const double *lev = (const double *)c->d_lever.p;
   const dim3 grid((unsigned)S.N_bod), block(MT);
-  const bool dof = m->B->per == 6;                       // a mask per component: the same three paths with the masked factors
+  const int per = m->B->per;
   const uint8_t *mask = m->B->mask;
+  // the 6 x 6 factors of the tails: masked once per solve for a mask per component; whole bodies read the context's own (a free
+  // body) or none (a prescribed one)
+  const double *NL = per == 6 ? (const double *)m->B->NLm : (const double *)c->d_NL.p;
   int rc;
   if (!S.block_pc) {
-    if (dof)
-      hipLaunchKernelGGL(k_mxd_pc_diag, grid, block, 0, c->stream, lev, mask, (const double *)c->d_invM2.p, (const double *)m->B->NLm,
-                         S.N_blb, n3, d_in, d_out);
-    else
-      hipLaunchKernelGGL(k_mx_pc_diag, grid, block, 0, c->stream, lev, mask, (const double *)c->d_invM2.p, (const double *)c->d_NL.p,
-                         S.N_blb, n3, d_in, d_out);
+    hipLaunchKernelGGL(k_mx_pc_diag, grid, block, 0, c->stream, lev, mask, per, (const double *)c->d_invM2.p, NL, S.N_blb, n3, d_in, d_out);
     return RBL_OK;
   }
   if (bf_on(c) && c->bf_tables) {
     // free space, small bodies: the one-launch body-frame preconditioner serves the free bodies as it is; the prescribed ones cost
-    // a second application of the shared factor
+    // a second application of the shared factor.  Whole bodies: the tail reads neither the orientations nor a masked factor
     RblPcReq rq;
     rq.fsign = 1.0;
     rc = apply_PC_dev(c, d_in, d_out, rq);
     if (rc || !m->any_prescribed) return rc;
     if ((rc = blk_solve(c, 0, S.N_bod, d_in, m->B->y1, 1, 0, 0))) return rc;
-    if (dof)
-      hipLaunchKernelGGL(k_mxd_pc_bodyframe_tail, grid, block, 0, c->stream, lev, mask, (const double *)m->B->y1, bf_table_MK(c),
-                         (const double *)c->d_XQ.p + 3 * (size_t)S.N_bod, (const double *)m->B->NLm, d_in, S.N_blb, n3, d_out);
-    else
-      hipLaunchKernelGGL(k_mx_pc_select, grid, block, 0, c->stream, mask, (const double *)m->B->y1, d_in, S.N_blb, n3, d_out);
+    hipLaunchKernelGGL(k_mx_pc_bodyframe_tail, grid, block, 0, c->stream, lev, mask, per, (const double *)m->B->y1, bf_table_MK(c),
+                       per == 6 ? (const double *)c->d_XQ.p + 3 * (size_t)S.N_bod : nullptr, (const double *)m->B->NLm, d_in, S.N_blb, n3,
+                       d_out);
     return RBL_OK;
   }
   if ((rc = blk_solve(c, 0, S.N_bod, d_in, m->B->y1, 1, 0, 0))) return rc;                   // invM slip, every body: ONE pass
   RblPhase ph(c, RBL_T_PERBODY);
-  if (dof)
-    hipLaunchKernelGGL(k_mxd_pc_block_tail, grid, block, 0, c->stream, lev, mask, (const double *)m->B->y1, (const double *)c->d_pcMK.p,
-                       n3, (const double *)m->B->NLm, d_in, S.N_blb, n3, d_out);
-  else
-    hipLaunchKernelGGL(k_mx_pc_block_tail, grid, block, 0, c->stream, lev, mask, (const double *)m->B->y1, (const double *)c->d_pcMK.p,
-                       n3, (const double *)c->d_NL.p, d_in, S.N_blb, n3, d_out);
+  hipLaunchKernelGGL(k_mx_pc_block_tail, grid, block, 0, c->stream, lev, mask, per, (const double *)m->B->y1, (const double *)c->d_pcMK.p,
+                     n3, NL, d_in, S.N_blb, n3, d_out);
   return RBL_OK;
 }
 
@@ -650,23 +462,20 @@ int mx_solve(rbl_ctx *c, const MxBuf &B, bool have_slip, int n_prescribed, int m
   const long n3 = 3 * (long)S.N_bod * S.N_blb;
   const double *lev = (const double *)c->d_lever.p;
   const dim3 grid((unsigned)S.N_bod), block(MT);
-  const bool dof = B.per == 6;
-  const auto k_rhs = dof ? k_mxd_rhs : k_mx_rhs;
-  const auto k_split = dof ? k_mxd_split : k_mx_split;
-  hipLaunchKernelGGL(k_rhs, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, (const double *)B.body_in,
+  hipLaunchKernelGGL(k_mx_rhs, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, B.per, (const double *)B.body_in,
                      have_slip ? (const double *)B.slip : nullptr, S.N_blb, n3, B.rhs);
-  if (dof) {                                             // the masked 6 x 6 factors: once per solve
+  if (B.per == 6) {                                      // the masked 6 x 6 factors: once per solve (whole bodies need none: mx_pc)
     const bool shared = S.block_pc && bf_on(c) && c->bf_tables;          // one body-frame factor for all bodies, behind the tables
     if (shared && (rc = ensure_xq_dev(c))) return rc;
-    hipLaunchKernelGGL(k_mxd_factors, dim3((unsigned)((S.N_bod + 63) / 64)), dim3(64), 0, c->stream,
+    hipLaunchKernelGGL(k_mx_factors, dim3((unsigned)((S.N_bod + 63) / 64)), dim3(64), 0, c->stream,
                        shared ? bf_table_MK(c) + 18 * (size_t)S.N_blb : (const double *)c->d_NL.p,
                        shared ? (const double *)c->d_XQ.p + 3 * (size_t)S.N_bod : nullptr, (const uint8_t *)B.mask, S.N_bod, B.NLm, c->d_err);
   }
   MxSolve m{&B, n_prescribed > 0};
   const RblSolveOps ops{mx_op, mx_pc, &m};
   if ((rc = gmres_core_with_ops(c, &ops, B.rhs, max_iter, rtol, B.x, iters, resid))) return rc;
-  hipLaunchKernelGGL(k_split, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, (const double *)B.body_in, (const double *)B.x,
-                     S.N_blb, n3, B.U, B.F);
+  hipLaunchKernelGGL(k_mx_split, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, B.per, (const double *)B.body_in,
+                     (const double *)B.x, S.N_blb, n3, B.U, B.F);
   RBL_HIP(c, hipGetLastError());
   return RBL_OK;
 }
@@ -683,8 +492,8 @@ int mx_upload(rbl_ctx *c, MxBuf &B, const uint8_t *prescribed, const double *bod
   if (model && c->ia_on && np < B.per * c->S.N_bod) {    // -K^T f_phys at q^n, free slots only (none free: nothing feels the model)
     RBL_HIP(c, hipMemsetAsync(B.model, 0, sizeof(double) * nb6, c->stream));
     if ((rc = ia_add_to_step_force(c, B.model))) return rc;
-    hipLaunchKernelGGL(B.per == 6 ? k_mxd_add_free : k_mx_add_free, dim3((unsigned)((nb6 + 255) / 256)), dim3(256), 0, c->stream,
-                       (const uint8_t *)B.mask, (const double *)B.model, (int)nb6, B.body_in);
+    hipLaunchKernelGGL(k_mx_add_free, dim3((unsigned)((nb6 + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)B.mask, B.per,
+                       (const double *)B.model, (int)nb6, B.body_in);
   }
   return RBL_OK;
 }

@@ -22,8 +22,8 @@
 //   [M lambda - K (D_f U) ; D_f K^T lambda + D_p U] = [slip + K_p U_p ; -F_f | 0]
 // with the replica's 0/1 mask per body.  ONE launch assembles the right-hand side, solves and splits: it takes the all-free
 // right-hand side [slip ; -body_in], adds K_p U_p with the lever arms it has just made and zeroes the bottom of the prescribed
-// bodies (k_mx_rhs of rbl_mixed.hip); the operator and the preconditioner treat the six slots of a prescribed body as
-// k_mx_op_tail / k_mx_pc_diag do, by selects on values outside the pair sweep; the end is k_mx_split's: U and F per body, the
+// bodies (k_mx_rhs of rbl_mixed.hip, given a mask per body); the operator and the preconditioner treat the six slots of a
+// prescribed body as k_mx_op_tail / k_mx_pc_diag do, by selects on values outside the pair sweep; the end is k_mx_split's: U, F per body, the
 // K^T sums in blob order.  A free body's arithmetic and its order are those of the unmasked kernel, so with nobody prescribed the
 // solution and the iteration count are bitwise the unmasked ones.  The four unmasked instantiations keep their code (every
 // masked statement is behind `if constexpr (MIXED)`, the extra arguments exist in the masked ones only): 111-128 VGPRs, no

@@ -174,6 +174,8 @@ def test_one_irregular_body_converges_in_two_iterations():
 # ---- 4. reduction to what exists ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("wall,block", WALL_BLOCK)
 def test_whole_body_masks_reduce_to_solve_mixed(wall, block):
+    """whole rows of the mask: the same kernels on the same bit sets and the same factor values (the masked factor of an all-free
+    body is a copy of the context's, a fully prescribed body reads none), so solve_mixed's results bit for bit"""
     c, rb = t._body(NB, NBLB, wall, block)
     F, Up, slip = t._inputs(NB, NBLB, seed=26)
     for name, p in t._sets(NB).items():                    # none, bodies 1 4 7, all
@@ -186,6 +188,7 @@ def test_whole_body_masks_reduce_to_solve_mixed(wall, block):
               % (wall, block, name, got[3], want[3], diffs[0], diffs[1], diffs[2], bitwise))
         assert 0 < got[3] < 200 and got[3] == want[3]
         assert max(diffs) <= 1e-12
+        assert bitwise
 
 
 # ---- 5. round trip through a mobility solve ----------------------------------------------------------------------------------------
