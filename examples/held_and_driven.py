@@ -6,7 +6,8 @@ included, by the end -- and the remaining seven are free and sediment under the 
 RigidBody.set_interactions).  Every step is one `step_mixed`: a single GMRES solve on the GPU returns the velocities of the free
 shells and the loads on the two prescribed ones.  Prints, per step, the physical force it takes to drag the driven shell and the
 one that holds the obstacle in place -- the total that the outside world supplies together with the model, whose own share on
-those two shells (`interaction_forces`) is printed once at the start.
+those two shells (`interaction_forces`) is printed once at the start.  At the end: the 54 x 54 body resistance matrix of the final
+configuration, its unit velocities solved in lock step (`body_resistance_matrix(lock_step=True)`, 16 columns advancing together).
 
 python examples/held_and_driven.py [--steps 160] [--speed 1.0]"""
 import argparse, os, sys
@@ -45,3 +46,8 @@ Xn = Xn.reshape(-1, 3)
 print("driven shell moved %.4f along x (speed x time = %.4f); held shell moved %.1e; mean height of the free shells %.4f"
       % (Xn[driven, 0] - X[driven, 0], args.speed * args.steps * dt, np.abs(Xn[held] - X[held]).max(),
          np.delete(Xn[:, 2], [held, driven]).mean()))
+# the resistance matrix of where they ended up: R U = the physical loads that move all nine shells with velocities U
+R, its = rb.body_resistance_matrix(rtol=1e-8, lock_step=True)
+print("resistance matrix in lock step: %d columns, iterations %d..%d, asymmetry %.1e; drag coefficient of the held shell along x, y, z: %s"
+      % (R.shape[1], its.min(), its.max(), np.linalg.norm(R - R.T) / np.linalg.norm(R),
+         np.array2string(np.diag(R)[6 * held:6 * held + 3], precision=4)))

@@ -772,13 +772,32 @@ int rbl_velocity_field_info(const rbl_ctx *ctx, int64_t n_points, int64_t n_src,
  * Refused with RBL_ERR_ARG before any device work: a NULL prescribed6 / body_in / U / F (rbl_step_mixed_dof: F may be NULL),
  * max_iter < 1, rtol < 0, more than 255 iterations, an entry of prescribed6 above 1, a context with a communicator.
  *
- * Not offered: lock-step multi-right-hand-side mixed solves, contexts with a communicator, a mask that changes within a step;
- * and with masks per component:
+ * Many right-hand sides under ONE mask, in lock step (the _multi entry points): the 6 N_bod unit velocities of the body resistance
+ * matrix, a handful of imposed rotations or trap displacements under one component mask, several noise realisations against fixed
+ * obstacles.  nrhs independent recurrences of the solver above -- each column with its own Krylov basis, Hessenberg matrix and
+ * stopping test, so its iterates are those of the one-vector call on it alone up to the rounding of the multi-vector product --
+ * advance together, 16 columns a batch as rbl_gmres_saddle_multi_dev: ONE launch of the multi-vector mobility product per
+ * iteration (the fp64 matrix cores from 4 columns on), the per-body factor passes shared by the columns (three vectors a pass),
+ * and the masked tails above with the column on the grid's second axis: one launch per iteration for all live columns.  The masked
+ * 6 x 6 factors are made once per call.  A column that has converged stops iterating; a column whose right-hand side is exactly
+ * zero returns zeros after one iteration.
+ *     prescribed / prescribed6     ONE mask for all columns (N_bod / 6 N_bod bytes, a HOST array in the _dev forms too)
+ *     body_in[nrhs][6 N_bod], slip[nrhs][3 N_blobs] or NULL        one vector after the other
+ *     lambda[nrhs][3 N_blobs] (may be NULL), U[nrhs][6 N_bod], F[nrhs][6 N_bod]      column by column, each as above
+ *     iters[nrhs], resid[nrhs]     (may be NULL)
+ *   rbl_solve_mixed_multi, rbl_solve_mixed_dof_multi          host arrays, synchronous.
+ *   rbl_solve_mixed_multi_dev, rbl_solve_mixed_dof_multi_dev  device pointers, stream drains and error latching as
+ *                        rbl_solve_mixed_dev (the lock-step solver tests convergence every iteration).
+ * Refused with RBL_ERR_ARG before any device work: what the one-vector calls refuse, and nrhs < 1.  Results are bitwise reproducible
+ * call to call.  16 unit-velocity columns at cfg 3 take 0.34 (every body prescribed) and 0.32 (the rotations of all bodies) of the
+ * sequential loop's time (tools/bench_prescribed_multi.py, profiles/prescribed_multi.jsonl).
+ *
+ * Not offered: contexts with a communicator, a mask that changes within a step, lock-step solves whose mask differs from column to
+ * column, the Brownian steps in lock step; and with masks per component:
  *   - the Brownian step (rbl_step_brownian_mixed takes whole bodies only): its drift argument rests on whole bodies being
  *     undisplaced, a partly prescribed rotation is not a subset of the coordinates, and nobody has derived the scheme for it;
  *   - ensembles (rbl_ensemble_*_mixed take whole bodies only);
- *   - constraint axes fixed in the body frame (the six components are the lab frame's);
- *   - lock-step multi-right-hand-side solves. */
+ *   - constraint axes fixed in the body frame (the six components are the lab frame's). */
 int rbl_solve_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
                     double *lambda, double *U, double *F, int *iters, double *resid);
 int rbl_solve_mixed_dev(rbl_ctx *ctx, const uint8_t *prescribed, const double *d_body_in, const double *d_slip, int max_iter,
@@ -791,6 +810,14 @@ int rbl_solve_mixed_dof_dev(rbl_ctx *ctx, const uint8_t *prescribed6, const doub
                             double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid);
 int rbl_step_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter, double rtol,
                        double *F, int *iters, double *resid);
+int rbl_solve_mixed_multi(rbl_ctx *ctx, const uint8_t *prescribed, int nrhs, const double *body_in, const double *slip, int max_iter,
+                          double rtol, double *lambda, double *U, double *F, int *iters, double *resid);
+int rbl_solve_mixed_multi_dev(rbl_ctx *ctx, const uint8_t *prescribed, int nrhs, const double *d_body_in, const double *d_slip,
+                              int max_iter, double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid);
+int rbl_solve_mixed_dof_multi(rbl_ctx *ctx, const uint8_t *prescribed6, int nrhs, const double *body_in, const double *slip, int max_iter,
+                              double rtol, double *lambda, double *U, double *F, int *iters, double *resid);
+int rbl_solve_mixed_dof_multi_dev(rbl_ctx *ctx, const uint8_t *prescribed6, int nrhs, const double *d_body_in, const double *d_slip,
+                                  int max_iter, double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid);
 int rbl_RHS_and_Midpoint_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
                                uint64_t seed, int method, int split_rand, double delta, double *s, double *X_half, double *Q_half);
 int rbl_RHS_and_Midpoint_mixed_dev(rbl_ctx *ctx, const uint8_t *prescribed, const double *d_body_in, const double *d_slip,

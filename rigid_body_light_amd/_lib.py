@@ -105,6 +105,9 @@ def lib():
         L.rbl_step_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
         L.rbl_solve_mixed_dof.argtypes = L.rbl_solve_mixed_dof_dev.argtypes = L.rbl_solve_mixed.argtypes
         L.rbl_step_mixed_dof.argtypes = L.rbl_step_mixed.argtypes
+        L.rbl_solve_mixed_multi.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, dbl, vp, vp, vp, vp, vp]
+        L.rbl_solve_mixed_multi_dev.argtypes = L.rbl_solve_mixed_dof_multi.argtypes = L.rbl_solve_mixed_multi.argtypes
+        L.rbl_solve_mixed_dof_multi_dev.argtypes = L.rbl_solve_mixed_multi.argtypes
         L.rbl_RHS_and_Midpoint_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, vp, vp, vp]
         L.rbl_RHS_and_Midpoint_mixed_dev.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, vp, vp, vp]
         L.rbl_step_brownian_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, C.c_int, dbl, vp, C.POINTER(C.c_int),
@@ -666,6 +669,30 @@ class DeviceContext:
         self._chk(self.L.rbl_solve_mixed_dof_dev(self.h, m.ctypes.data, d_body_in, d_slip or None, int(max_iter), float(rtol),
                                                  d_lam or None, d_U, d_F, C.byref(it), C.byref(res)))
         return it.value, res.value
+
+    def _mixed_multi_dev(self, who, per, prescribed, nrhs, d_body_in, d_slip, max_iter, rtol, d_lam, d_U, d_F):
+        import numpy as np
+        m = np.ascontiguousarray(prescribed, dtype=np.uint8).reshape(-1)
+        nb = C.c_int(0)
+        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), None))
+        if m.size != per * nb.value:
+            raise ValueError("%s: prescribed must have %sN_bod entries" % (who, "6 " if per == 6 else ""))
+        if int(nrhs) < 1:
+            raise ValueError("%s: need nrhs >= 1" % who)
+        it, res = np.zeros(int(nrhs), dtype=np.int32), np.zeros(int(nrhs))
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, int(nrhs), d_body_in, d_slip or None, int(max_iter), float(rtol),
+                                                d_lam or None, d_U, d_F, it.ctypes.data, res.ctypes.data))
+        return it, res
+
+    def solve_mixed_multi_dev(self, prescribed, nrhs, d_body_in, d_slip, max_iter, rtol, d_lam, d_U, d_F):
+        """nrhs right-hand sides under ONE mask in lock step, on device addresses: d_body_in nrhs vectors of 6 N_bod, d_slip (None / 0
+        or nrhs vectors of 3 N_blobs), d_lam (may be None / 0), d_U, d_F likewise, one vector after the other; prescribed: a host array
+        of N_bod entries -> (iterations (nrhs,), residual estimates (nrhs,))"""
+        return self._mixed_multi_dev("solve_mixed_multi_dev", 1, prescribed, nrhs, d_body_in, d_slip, max_iter, rtol, d_lam, d_U, d_F)
+
+    def solve_mixed_dof_multi_dev(self, prescribed6, nrhs, d_body_in, d_slip, max_iter, rtol, d_lam, d_U, d_F):
+        """solve_mixed_multi_dev with a mask per velocity component (prescribed6: a host array of 6 N_bod entries)"""
+        return self._mixed_multi_dev("solve_mixed_dof_multi_dev", 6, prescribed6, nrhs, d_body_in, d_slip, max_iter, rtol, d_lam, d_U, d_F)
 
     def _mixed_sizes(self, who, prescribed):
         import numpy as np

@@ -514,6 +514,44 @@ struct CManyBodies {
     check(rc);
     return py::make_tuple(F, it, res);
   }
+  // k right-hand sides under one mask in lock step (rbl_solve_mixed_multi, rbl_solve_mixed_dof_multi): body_in (k, 6 N_bod), slip None
+  // or (k, 3 N_blobs) -> (lambda (k, 3 N_blobs), U (k, 6 N_bod), F (k, 6 N_bod), iterations (k,), residual estimates (k,))
+  py::tuple solve_mixed_multi_any(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip, int max_iter,
+                                  double rtol)
+  {
+    const py::ssize_t nb6 = 6 * (py::ssize_t)n_bod();
+    if (mask.size() != per * (py::ssize_t)n_bod())
+      throw py::value_error(std::string(who) + (per == 6 ? ": prescribed must have length 6*N_bod" : ": prescribed must have length N_bod"));
+    if (body_in.ndim() != 2 || body_in.shape(0) < 1 || body_in.shape(1) != nb6)
+      throw py::value_error(std::string(who) + ": body_in must have shape (k, 6*N_bod), k >= 1");
+    const py::ssize_t k = body_in.shape(0);
+    darr sl;
+    const double *sp = nullptr;
+    if (!slip.is_none()) {
+      sl = slip.cast<darr>();
+      if (sl.ndim() != 2 || sl.shape(0) != k || sl.shape(1) != n3()) throw py::value_error(std::string(who) + ": slip must have shape (k, 3*N_blobs)");
+      sp = sl.data();
+    }
+    darr lam({k, (py::ssize_t)n3()}), U({k, nb6}), F({k, nb6}), res(k);
+    py::array_t<int> it(k);
+    int rc;
+    {
+      py::gil_scoped_release rel;
+      rc = (per == 6 ? rbl_solve_mixed_dof_multi : rbl_solve_mixed_multi)(ctx, mask.data(), (int)k, body_in.data(), sp, max_iter, rtol,
+                                                                          lam.mutable_data(), U.mutable_data(), F.mutable_data(),
+                                                                          it.mutable_data(), res.mutable_data());
+    }
+    check(rc);
+    return py::make_tuple(lam, U, F, it, res);
+  }
+  py::tuple solve_mixed_multi(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
+  {
+    return solve_mixed_multi_any("solve_mixed_multi", 1, mask, body_in, slip, max_iter, rtol);
+  }
+  py::tuple solve_mixed_dof_multi(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
+  {
+    return solve_mixed_multi_any("solve_mixed_dof_multi", 6, mask, body_in, slip, max_iter, rtol);
+  }
   // the Brownian midpoint step with prescribed bodies: right-hand side and predictor at q^n -> (s, X_half, Q_half), nothing committed
   const double *noise_arg(const char *who, const py::object &W, darr &Wa) const
   {
@@ -664,6 +702,10 @@ PYBIND11_MODULE(c_rigid, m)
            py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
       .def("step_mixed_dof", &CManyBodies::step_mixed_dof, py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(),
            py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
+      .def("solve_mixed_multi", &CManyBodies::solve_mixed_multi, "prescribed kinematics, k right-hand sides under one mask in lock step",
+           py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
+      .def("solve_mixed_dof_multi", &CManyBodies::solve_mixed_dof_multi, "the same with a mask per velocity component (6 N_bod entries)",
+           py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
       .def("RHS_and_Midpoint_mixed", &CManyBodies::RHS_and_Midpoint_mixed, py::arg("prescribed"), py::arg("body_in"),
            py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "cholesky",
            py::arg("split_rand") = true, py::arg("delta") = 1.0e-4)

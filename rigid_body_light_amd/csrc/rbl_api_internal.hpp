@@ -115,6 +115,18 @@ struct RblSolveOps {
 };
 int gmres_core_with_ops(rbl_ctx *c, const RblSolveOps *ops, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
                         double *resid_out);
+// The lock-step analogue: k <= 16 right-hand sides (d_rhs, d_x: k vectors of the system's size one after the other), each with its
+// own recurrence and stopping test, whose operator and preconditioner are ONE call per iteration for all of them.  The vectors a
+// callback reads and writes are `pitch` doubles apart; `live` has bit c set while column c iterates: a callback need not touch a
+// column whose bit is clear (its input slot is zeroed, its output is never read).  d_scratch: room for one vector per column,
+// `pitch` apart too.
+struct RblMultiOps {
+  int (*op)(rbl_ctx *c, void *user, const double *d_x, double *d_out, int k, int64_t pitch, unsigned live);
+  int (*pc)(rbl_ctx *c, void *user, const double *d_in, double *d_out, double *d_scratch, int k, int64_t pitch, unsigned live);
+  void *user;
+};
+int gmres_multi_with_ops(rbl_ctx *c, const RblMultiOps *ops, const double *d_rhs, int k, int max_iter, double rtol, double *d_x,
+                         int *iters_out, double *resid_out);
 
 // ---- rbl_steps.hip ------------------------------------------------------------------------------------------------
 // The stochastic midpoint scheme, once for rbl_step_brownian and rbl_step_brownian_mixed (rbl_mixed.hip): the all-free step is the

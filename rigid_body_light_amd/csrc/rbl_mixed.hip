@@ -13,6 +13,11 @@
 // workgroup sum and the 6 x 6 substitution are rbl_body_dev.hpp's, shared with rbl_body_dev.hip.  The Arnoldi recurrence, the
 // Hessenberg solve and the convergence test are gmres_core's (gmres_core_with_ops).
 //
+// Many right-hand sides under ONE mask (the _multi entry points) advance in lock step through gmres_multi_with_ops: the same kernels
+// with the column on the grid's second axis -- one workgroup per (body, column), the vectors of a batch `pitch` doubles apart, a bit
+// set `live` of the columns still iterating (a converged column's workgroups return at once).  One vector is a grid of height 1 with
+// pitch 0 and live = 1: the arithmetic per vector is the same either way.
+//
 // The Brownian midpoint step with prescribed bodies has its entry points here and nothing of the scheme: right-hand side, predictor
 // and the sequence of the step are rbl_steps.hip's (rhs_and_midpoint_core, step_midpoint), which the all-free step goes through with
 // no mask; this file hands them the mask and mx_solve.
@@ -41,6 +46,13 @@ __device__ __forceinline__ unsigned mx_bits(const uint8_t *__restrict__ mask, in
   return (unsigned)__builtin_amdgcn_readfirstlane((int)pm);
 }
 
+// the workgroup's column of a lock-step batch; false: that column has converged, nothing to do
+__device__ __forceinline__ bool mx_live(unsigned live, int &col)
+{
+  col = (int)blockIdx.y;
+  return (live >> col) & 1u;
+}
+
 // a fully prescribed body (pm == 63) in the operator and the preconditioners: lambda_b = v_b, the six body slots pass through
 __device__ __forceinline__ void mx_pass_through(const double *__restrict__ v, const double *g, int b, int t, int N_blb, long n3,
                                                 double *__restrict__ out)
@@ -55,9 +67,12 @@ __device__ __forceinline__ void mx_pass_through(const double *__restrict__ v, co
 // right-hand side: top = slip + K D_p U_in, bottom = -F_in on the free components, 0 on the prescribed ones
 __global__ __launch_bounds__(MT) void k_mx_rhs(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
                                                const double *__restrict__ body_in, const double *__restrict__ slip, int N_blb,
-                                               long n3, double *__restrict__ rhs)
+                                               long n3, double *__restrict__ rhs, long pb, long ps, long pr)
 {
   const int b = blockIdx.x, t = threadIdx.x;
+  const size_t col = blockIdx.y;                         // column: body_in pb, slip ps, rhs pr doubles apart
+  body_in += col * (size_t)pb; rhs += col * (size_t)pr;
+  if (slip) slip += col * (size_t)ps;
   const unsigned pm = mx_bits(mask, per, b);
   const double *u = body_in + 6 * (size_t)b;
   double up[6];
@@ -79,10 +94,13 @@ __global__ __launch_bounds__(MT) void k_mx_rhs(const double *__restrict__ lever,
 // the operator's tail after sub = M lambda: out = [sub - K (D_f U) ; D_f K^T lambda + D_p U]
 __global__ __launch_bounds__(MT) void k_mx_op_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
                                                    const double *__restrict__ x, const double *__restrict__ sub, int N_blb, long n3,
-                                                   double *__restrict__ out)
+                                                   double *__restrict__ out, long pitch, long spitch, unsigned live)
 {
   __shared__ double s[6][MT];
   const int b = blockIdx.x, t = threadIdx.x;
+  int col;
+  if (!mx_live(live, col)) return;
+  x += (size_t)col * (size_t)pitch; out += (size_t)col * (size_t)pitch; sub += (size_t)col * (size_t)spitch;
   const unsigned pm = mx_bits(mask, per, b);
   const double *u = x + n3 + 6 * (size_t)b;
   if (pm == 63u) { mx_pass_through(sub, u, b, t, N_blb, n3, out); return; }      // no velocity unknown, no balance row
@@ -203,11 +221,14 @@ __device__ __forceinline__ void mx_body_rows(const double *NLm_b, unsigned pm, c
 __global__ __launch_bounds__(MT) void k_mx_pc_block_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
                                                          const double *__restrict__ y1, const double *__restrict__ MK, long stride,
                                                          const double *__restrict__ NLm, const double *__restrict__ in, int N_blb,
-                                                         long n3, double *__restrict__ out)
+                                                         long n3, double *__restrict__ out, long pitch, unsigned live)
 {
   __shared__ double s[6][MT];
   __shared__ double us[6];
   const int b = blockIdx.x, t = threadIdx.x;
+  int col;
+  if (!mx_live(live, col)) return;
+  y1 += (size_t)col * (size_t)pitch; in += (size_t)col * (size_t)pitch; out += (size_t)col * (size_t)pitch;
   const unsigned pm = mx_bits(mask, per, b);
   const double *g = in + n3 + 6 * (size_t)b;
   if (pm == 63u) { mx_pass_through(y1, g, b, t, N_blb, n3, out); return; }
@@ -236,11 +257,14 @@ __global__ __launch_bounds__(MT) void k_mx_pc_block_tail(const double *__restric
 // the six body slots pass through.  NLm as in k_mx_pc_block_tail.
 __global__ __launch_bounds__(MT) void k_mx_pc_diag(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
                                                    const double *__restrict__ invM2, const double *__restrict__ NLm, int N_blb, long n3,
-                                                   const double *__restrict__ in, double *__restrict__ out)
+                                                   const double *__restrict__ in, double *__restrict__ out, long pitch, unsigned live)
 {
   __shared__ double s[6][MT];
   __shared__ double us[6];
   const int b = blockIdx.x, t = threadIdx.x;
+  int col;
+  if (!mx_live(live, col)) return;
+  in += (size_t)col * (size_t)pitch; out += (size_t)col * (size_t)pitch;
   const unsigned pm = mx_bits(mask, per, b);
   const double *g = in + n3 + 6 * (size_t)b;
   if (pm == 63u) {
@@ -278,11 +302,15 @@ __global__ __launch_bounds__(MT) void k_mx_pc_diag(const double *__restrict__ le
 __global__ __launch_bounds__(MT) void k_mx_pc_bodyframe_tail(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
                                                              const double *__restrict__ y1, const double *__restrict__ MKb,
                                                              const double *__restrict__ Q, const double *__restrict__ NLm,
-                                                             const double *__restrict__ in, int N_blb, long n3, double *__restrict__ out)
+                                                             const double *__restrict__ in, int N_blb, long n3, double *__restrict__ out,
+                                                             long pitch, unsigned live)
 {
   __shared__ double s[6][MT];
   __shared__ double us[6];
   const int b = blockIdx.x, t = threadIdx.x;
+  int col;
+  if (!mx_live(live, col)) return;
+  y1 += (size_t)col * (size_t)pitch; in += (size_t)col * (size_t)pitch; out += (size_t)col * (size_t)pitch;
   const unsigned pm = mx_bits(mask, per, b);
   if (pm == 0u) return;
   const double *g = in + n3 + 6 * (size_t)b;
@@ -328,10 +356,12 @@ __global__ void k_mx_add_free(const uint8_t *__restrict__ mask, int per, const d
 // the solution split: U = D_f U_solved + D_p U_in (echoed), F = D_f F_in (echoed) + D_p (-K_b^T lambda)
 __global__ __launch_bounds__(MT) void k_mx_split(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
                                                  const double *__restrict__ body_in, const double *__restrict__ x, int N_blb, long n3,
-                                                 double *__restrict__ U, double *__restrict__ F)
+                                                 double *__restrict__ U, double *__restrict__ F, long pb, long px)
 {
   __shared__ double s[6][MT];
   const int b = blockIdx.x, t = threadIdx.x;
+  const size_t col = blockIdx.y;                         // column: body_in, U and F pb, x px doubles apart
+  body_in += col * (size_t)pb; U += col * (size_t)pb; F += col * (size_t)pb; x += col * (size_t)px;
   const unsigned pm = mx_bits(mask, per, b);
   const size_t o = 6 * (size_t)b;
   if (pm == 0u) {
@@ -358,16 +388,18 @@ struct MxBuf {           // the one workspace of a section 7 entry point (rbl_ct
   double *NLm;           // the masked 6 x 6 factors of a solve with a mask per component (k_mx_factors); NULL with per == 1
   uint8_t *mask;         // per * N_bod entries
   int per = 1;           // mask entries per body: 1 (whole bodies) or 6 (velocity components, the _dof entry points)
+  int k = 1;             // columns: rhs, x, slip, body_in, U and F hold k vectors one after the other (the _multi entry points: <= 16)
 };
 
 int mx_reserve(rbl_ctx *c, MxBuf &B)
 {
   const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nsys = n3 + nb6;
   const size_t nlm = B.per == 6 ? 6 * nb6 : 0;           // the masked factors: solves with a mask per component only
-  const int rc = rbl_dev_reserve(c, c->d_mx, sizeof(double) * (2 * nsys + 2 * n3 + 4 * nb6 + nlm) + (size_t)B.per * (size_t)c->S.N_bod);
+  const size_t k = (size_t)B.k;                          // (y1, model, the factors and the mask are shared by the columns)
+  const int rc = rbl_dev_reserve(c, c->d_mx, sizeof(double) * (k * (2 * nsys + n3 + 3 * nb6) + n3 + nb6 + nlm) + (size_t)B.per * (size_t)c->S.N_bod);
   if (rc) return rc;
-  B.rhs = (double *)c->d_mx.p; B.x = B.rhs + nsys; B.y1 = B.x + nsys; B.slip = B.y1 + n3; B.body_in = B.slip + n3;
-  B.U = B.body_in + nb6; B.F = B.U + nb6; B.model = B.F + nb6; B.NLm = nlm ? B.model + nb6 : nullptr;
+  B.rhs = (double *)c->d_mx.p; B.x = B.rhs + k * nsys; B.y1 = B.x + k * nsys; B.slip = B.y1 + n3; B.body_in = B.slip + k * n3;
+  B.U = B.body_in + k * nb6; B.F = B.U + k * nb6; B.model = B.F + k * nb6; B.NLm = nlm ? B.model + nb6 : nullptr;
   B.mask = (uint8_t *)(B.model + nb6 + nlm);
   return RBL_OK;
 }
@@ -385,7 +417,21 @@ int mx_op(rbl_ctx *c, void *user, const double *d_x, double *d_out)
   int rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3); if (rc) return rc;
   if ((rc = apply_M_enqueue(c, S.wall, d_x, (const double *)c->d_pos.p, N, 0, N, (double *)c->d_sad.p))) return rc;
   hipLaunchKernelGGL(k_mx_op_tail, dim3((unsigned)S.N_bod), dim3(MT), 0, c->stream, (const double *)c->d_lever.p,
-                     (const uint8_t *)m->B->mask, m->B->per, d_x, (const double *)c->d_sad.p, S.N_blb, (long)n3, d_out);
+                     (const uint8_t *)m->B->mask, m->B->per, d_x, (const double *)c->d_sad.p, S.N_blb, (long)n3, d_out, 0L, 0L, 1u);
+  return RBL_OK;
+}
+
+// k columns `pitch` doubles apart: ONE multi-vector product (the fp64 matrix cores from 4 columns on), ONE masked tail for the live ones
+int mx_op_multi(rbl_ctx *c, void *user, const double *d_x, double *d_out, int k, int64_t pitch, unsigned live)
+{
+  const MxSolve *m = (const MxSolve *)user;
+  const RblBodyState &S = c->S;
+  const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N;
+  int rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3 * (size_t)k); if (rc) return rc;
+  if ((rc = apply_M_multi_enqueue(c, S.wall, d_x, (const double *)c->d_pos.p, N, k, (double *)c->d_sad.p, pitch, n3))) return rc;
+  hipLaunchKernelGGL(k_mx_op_tail, dim3((unsigned)S.N_bod, (unsigned)k), dim3(MT), 0, c->stream, (const double *)c->d_lever.p,
+                     (const uint8_t *)m->B->mask, m->B->per, d_x, (const double *)c->d_sad.p, S.N_blb, (long)n3, d_out, (long)pitch, (long)n3,
+                     live);
   return RBL_OK;
 }
 
@@ -396,13 +442,15 @@ const double *bf_table_MK(const rbl_ctx *c)
   return (const double *)c->d_bfPC.p + m * m;
 }
 
-int mx_pc(rbl_ctx *c, void *user, const double *d_in, double *d_out)
+// the masked preconditioner on k vectors `pitch` doubles apart (one vector: k = 1, pitch 0, live = 1); y1: room for invM slip of
+// every vector, `pitch` apart too.  The per-body factor passes take all k vectors at once (three share a pass); a converged
+// column rides along there on its zeroed slot and is skipped by the tails
+int mx_pc_cols(rbl_ctx *c, const MxSolve *m, const double *d_in, double *d_out, double *y1, int k, int64_t pitch, unsigned live)
 {
-  const MxSolve *m = (const MxSolve *)user;
   const RblBodyState &S = c->S;
   const long n3 = 3 * (long)S.N_bod * S.N_blb;
   const double *lev = (const double *)c->d_lever.p;
-  const dim3 grid((unsigned)S.N_bod), block(MT);
+  const dim3 grid((unsigned)S.N_bod, (unsigned)k), block(MT);
   const int per = m->B->per;
   const uint8_t *mask = m->B->mask;
   // the 6 x 6 factors of the tails: masked once per solve for a mask per component; whole bodies read the context's own (a free
@@ -410,35 +458,51 @@ int mx_pc(rbl_ctx *c, void *user, const double *d_in, double *d_out)
   const double *NL = per == 6 ? (const double *)m->B->NLm : (const double *)c->d_NL.p;
   int rc;
   if (!S.block_pc) {
-    hipLaunchKernelGGL(k_mx_pc_diag, grid, block, 0, c->stream, lev, mask, per, (const double *)c->d_invM2.p, NL, S.N_blb, n3, d_in, d_out);
+    hipLaunchKernelGGL(k_mx_pc_diag, grid, block, 0, c->stream, lev, mask, per, (const double *)c->d_invM2.p, NL, S.N_blb, n3, d_in, d_out,
+                       (long)pitch, live);
     return RBL_OK;
   }
   if (bf_on(c) && c->bf_tables) {
     // free space, small bodies: the one-launch body-frame preconditioner serves the free bodies as it is; the prescribed ones cost
     // a second application of the shared factor.  Whole bodies: the tail reads neither the orientations nor a masked factor
-    RblPcReq rq;
-    rq.fsign = 1.0;
-    rc = apply_PC_dev(c, d_in, d_out, rq);
-    if (rc || !m->any_prescribed) return rc;
-    if ((rc = blk_solve(c, 0, S.N_bod, d_in, m->B->y1, 1, 0, 0))) return rc;
-    hipLaunchKernelGGL(k_mx_pc_bodyframe_tail, grid, block, 0, c->stream, lev, mask, per, (const double *)m->B->y1, bf_table_MK(c),
+    for (int col = 0; col < k; ++col) {
+      if (!(live >> col & 1u)) continue;
+      RblPcReq rq;
+      rq.fsign = 1.0;
+      if ((rc = apply_PC_dev(c, d_in + (size_t)col * (size_t)pitch, d_out + (size_t)col * (size_t)pitch, rq))) return rc;
+    }
+    if (!m->any_prescribed) return RBL_OK;
+    if ((rc = blk_solve(c, 0, S.N_bod, d_in, y1, k, pitch, 0))) return rc;
+    hipLaunchKernelGGL(k_mx_pc_bodyframe_tail, grid, block, 0, c->stream, lev, mask, per, (const double *)y1, bf_table_MK(c),
                        per == 6 ? (const double *)c->d_XQ.p + 3 * (size_t)S.N_bod : nullptr, (const double *)m->B->NLm, d_in, S.N_blb, n3,
-                       d_out);
+                       d_out, (long)pitch, live);
     return RBL_OK;
   }
-  if ((rc = blk_solve(c, 0, S.N_bod, d_in, m->B->y1, 1, 0, 0))) return rc;                   // invM slip, every body: ONE pass
+  if ((rc = blk_solve(c, 0, S.N_bod, d_in, y1, k, pitch, 0))) return rc;                     // invM slip, every body: ONE pass
   RblPhase ph(c, RBL_T_PERBODY);
-  hipLaunchKernelGGL(k_mx_pc_block_tail, grid, block, 0, c->stream, lev, mask, per, (const double *)m->B->y1, (const double *)c->d_pcMK.p,
-                     n3, NL, d_in, S.N_blb, n3, d_out);
+  hipLaunchKernelGGL(k_mx_pc_block_tail, grid, block, 0, c->stream, lev, mask, per, (const double *)y1, (const double *)c->d_pcMK.p,
+                     n3, NL, d_in, S.N_blb, n3, d_out, (long)pitch, live);
   return RBL_OK;
+}
+
+int mx_pc(rbl_ctx *c, void *user, const double *d_in, double *d_out)
+{
+  const MxSolve *m = (const MxSolve *)user;
+  return mx_pc_cols(c, m, d_in, d_out, m->B->y1, 1, 0, 1u);
+}
+
+int mx_pc_multi(rbl_ctx *c, void *user, const double *d_in, double *d_out, double *d_scratch, int k, int64_t pitch, unsigned live)
+{
+  return mx_pc_cols(c, (const MxSolve *)user, d_in, d_out, d_scratch, k, pitch, live);
 }
 
 // argument checks that need no device
 int mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const void *body_in, int max_iter, double rtol, bool host_form,
-             int *n_prescribed, int per = 1)
+             int *n_prescribed, int per = 1, int nrhs = 1)
 {
   if (!c) return RBL_ERR_ARG;
   if (!prescribed || !body_in) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": prescribed or body_in is NULL");
+  if (nrhs < 1) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": need nrhs >= 1");
   if (max_iter < 1 || !(rtol >= 0.0)) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": need max_iter >= 1 and rtol >= 0");
   if (max_iter + 1 > rbl_gmres_max_vectors()) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": at most 255 iterations (no restart)");
   int rc = host_form ? need_K(c) : need_config(c); if (rc) return rc;
@@ -463,7 +527,7 @@ int mx_solve(rbl_ctx *c, const MxBuf &B, bool have_slip, int n_prescribed, int m
   const double *lev = (const double *)c->d_lever.p;
   const dim3 grid((unsigned)S.N_bod), block(MT);
   hipLaunchKernelGGL(k_mx_rhs, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, B.per, (const double *)B.body_in,
-                     have_slip ? (const double *)B.slip : nullptr, S.N_blb, n3, B.rhs);
+                     have_slip ? (const double *)B.slip : nullptr, S.N_blb, n3, B.rhs, 0L, 0L, 0L);
   if (B.per == 6) {                                      // the masked 6 x 6 factors: once per solve (whole bodies need none: mx_pc)
     const bool shared = S.block_pc && bf_on(c) && c->bf_tables;          // one body-frame factor for all bodies, behind the tables
     if (shared && (rc = ensure_xq_dev(c))) return rc;
@@ -475,7 +539,43 @@ int mx_solve(rbl_ctx *c, const MxBuf &B, bool have_slip, int n_prescribed, int m
   const RblSolveOps ops{mx_op, mx_pc, &m};
   if ((rc = gmres_core_with_ops(c, &ops, B.rhs, max_iter, rtol, B.x, iters, resid))) return rc;
   hipLaunchKernelGGL(k_mx_split, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, B.per, (const double *)B.body_in,
-                     (const double *)B.x, S.N_blb, n3, B.U, B.F);
+                     (const double *)B.x, S.N_blb, n3, B.U, B.F, 0L, 0L);
+  RBL_HIP(c, hipGetLastError());
+  return RBL_OK;
+}
+
+// what a _multi call does once, the mask (shared by all columns) in place: the resident geometry and the preconditioner of this
+// configuration, the masked 6 x 6 factors
+int mx_multi_prepare(rbl_ctx *c, const MxBuf &B)
+{
+  int rc = rbl_prepare_dev(c); if (rc) return rc;
+  const RblBodyState &S = c->S;
+  if (B.per == 6) {
+    const bool shared = S.block_pc && bf_on(c) && c->bf_tables;
+    if (shared && (rc = ensure_xq_dev(c))) return rc;
+    hipLaunchKernelGGL(k_mx_factors, dim3((unsigned)((S.N_bod + 63) / 64)), dim3(64), 0, c->stream,
+                       shared ? bf_table_MK(c) + 18 * (size_t)S.N_blb : (const double *)c->d_NL.p,
+                       shared ? (const double *)c->d_XQ.p + 3 * (size_t)S.N_bod : nullptr, (const uint8_t *)B.mask, S.N_bod, B.NLm, c->d_err);
+  }
+  return RBL_OK;
+}
+
+// one batch of kb <= B.k columns in lock step on the buffers of B (body_in and slip of the batch in place): leaves x = [lambda ;
+// U_f], B.U and B.F column by column
+int mx_solve_batch(rbl_ctx *c, const MxBuf &B, bool have_slip, int n_prescribed, int kb, int max_iter, double rtol, int *iters, double *resid)
+{
+  const RblBodyState &S = c->S;
+  const long nb6 = 6 * (long)S.N_bod, n3 = 3 * (long)S.N_bod * S.N_blb, nsys = n3 + nb6;
+  const double *lev = (const double *)c->d_lever.p;
+  const dim3 grid((unsigned)S.N_bod, (unsigned)kb), block(MT);
+  hipLaunchKernelGGL(k_mx_rhs, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, B.per, (const double *)B.body_in,
+                     have_slip ? (const double *)B.slip : nullptr, S.N_blb, n3, B.rhs, nb6, n3, nsys);
+  MxSolve m{&B, n_prescribed > 0};
+  const RblMultiOps ops{mx_op_multi, mx_pc_multi, &m};
+  int rc;
+  if ((rc = gmres_multi_with_ops(c, &ops, B.rhs, kb, max_iter, rtol, B.x, iters, resid))) return rc;
+  hipLaunchKernelGGL(k_mx_split, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, B.per, (const double *)B.body_in,
+                     (const double *)B.x, S.N_blb, n3, B.U, B.F, nb6, nsys);
   RBL_HIP(c, hipGetLastError());
   return RBL_OK;
 }
@@ -516,20 +616,12 @@ int mx_host(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double
   return finish_and_check(c);
 }
 
-// device arrays in, device arrays out, the mask (per entries per body) from the host; the stream is drained where the solver drains it
-int mx_dev(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *d_body_in, const double *d_slip, int max_iter, double rtol,
-           double *d_lambda, double *d_U, double *d_F, int *iters, double *resid, int per)
+// the host's mask into the workspace of a _dev form.  It goes up from the context's pinned megabyte (idle between the solver's
+// read-backs, which drain the stream): a true asynchronous copy, so the caller's array may go after the call and the stream is not
+// drained for it
+int mx_mask_async(rbl_ctx *c, const MxBuf &B, const uint8_t *prescribed)
 {
-  if (c && (!d_U || !d_F)) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": U or F is NULL");
-  int np = 0;
-  int rc = mx_check(c, who, prescribed, d_body_in, max_iter, rtol, false, &np, per); if (rc) return rc;
-  if ((rc = rbl_dev_init(c))) return rc;
-  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nmask = (size_t)per * (size_t)c->S.N_bod;
-  MxBuf B;
-  B.per = per;
-  if ((rc = mx_reserve(c, B))) return rc;
-  // the mask goes up from the context's pinned megabyte (idle between the solver's read-backs, which drain the stream): a true
-  // asynchronous copy, so the caller's array may go after the call and the stream is not drained for it
+  const size_t nmask = (size_t)B.per * (size_t)c->S.N_bod;
   constexpr size_t pin_bytes = (size_t)1 << 20;
   if (nmask <= pin_bytes) {
     if (!c->h_pin) RBL_HIP(c, hipHostMalloc(&c->h_pin, pin_bytes, hipHostMallocDefault));
@@ -539,12 +631,77 @@ int mx_dev(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double 
     RBL_HIP(c, hipMemcpyAsync(B.mask, prescribed, nmask, hipMemcpyHostToDevice, c->stream));
     RBL_HIP(c, hipStreamSynchronize(c->stream));
   }
+  return RBL_OK;
+}
+
+// device arrays in, device arrays out, the mask (per entries per body) from the host; the stream is drained where the solver drains it
+int mx_dev(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *d_body_in, const double *d_slip, int max_iter, double rtol,
+           double *d_lambda, double *d_U, double *d_F, int *iters, double *resid, int per)
+{
+  if (c && (!d_U || !d_F)) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": U or F is NULL");
+  int np = 0;
+  int rc = mx_check(c, who, prescribed, d_body_in, max_iter, rtol, false, &np, per); if (rc) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
+  MxBuf B;
+  B.per = per;
+  if ((rc = mx_reserve(c, B))) return rc;
+  if ((rc = mx_mask_async(c, B, prescribed))) return rc;
   RBL_HIP(c, hipMemcpyAsync(B.body_in, d_body_in, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
   if (d_slip) RBL_HIP(c, hipMemcpyAsync(B.slip, d_slip, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
   if ((rc = mx_solve(c, B, d_slip != nullptr, np, max_iter, rtol, iters, resid))) return rc;
   if (d_lambda) RBL_HIP(c, hipMemcpyAsync(d_lambda, B.x, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
   RBL_HIP(c, hipMemcpyAsync(d_U, B.U, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
   RBL_HIP(c, hipMemcpyAsync(d_F, B.F, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
+  return RBL_OK;
+}
+
+// ---- nrhs right-hand sides under one mask, in lock step, 16 columns a batch (the workspace holds one batch) -------------------------
+// body_in: nrhs vectors of 6 N_bod, slip: NULL or nrhs vectors of 3 N, one after the other; lambda (may be NULL), U, F likewise
+int mx_multi(rbl_ctx *c, const char *who, bool host_form, const uint8_t *prescribed, int nrhs, const double *body_in, const double *slip,
+             int max_iter, double rtol, double *lambda, double *U, double *F, int *iters, double *resid, int per)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (!U || !F) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": U or F is NULL");
+  int np = 0;
+  int rc = mx_check(c, who, prescribed, body_in, max_iter, rtol, host_form, &np, per, nrhs); if (rc) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nsys = n3 + nb6;
+  MxBuf B;
+  B.per = per;
+  B.k = nrhs < 16 ? nrhs : 16;
+  if ((rc = mx_reserve(c, B))) return rc;
+  if (host_form) rc = copy_h2d(c, B.mask, prescribed, (size_t)per * (size_t)c->S.N_bod);
+  else rc = mx_mask_async(c, B, prescribed);
+  if (rc) return rc;
+  RblPhase ph_total(c, RBL_T_TOTAL);
+  if ((rc = mx_multi_prepare(c, B))) return rc;
+  const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
+  for (int k0 = 0; k0 < nrhs; k0 += 16) {
+    const int kb = nrhs - k0 < 16 ? nrhs - k0 : 16;
+    const double *bi = body_in + (size_t)k0 * nb6, *sl = slip ? slip + (size_t)k0 * n3 : nullptr;
+    if (host_form) {
+      if ((rc = copy_h2d(c, B.body_in, bi, sizeof(double) * nb6 * (size_t)kb))) return rc;
+      if (sl && (rc = copy_h2d(c, B.slip, sl, sizeof(double) * n3 * (size_t)kb))) return rc;
+    } else {
+      RBL_HIP(c, hipMemcpyAsync(B.body_in, bi, sizeof(double) * nb6 * (size_t)kb, d2d, c->stream));
+      if (sl) RBL_HIP(c, hipMemcpyAsync(B.slip, sl, sizeof(double) * n3 * (size_t)kb, d2d, c->stream));
+    }
+    if ((rc = mx_solve_batch(c, B, slip != nullptr, np, kb, max_iter, rtol, iters ? iters + k0 : nullptr, resid ? resid + k0 : nullptr)))
+      return rc;
+    if (host_form) {
+      for (int col = 0; lambda && col < kb; ++col)
+        if ((rc = copy_d2h(c, lambda + (size_t)(k0 + col) * n3, B.x + (size_t)col * nsys, sizeof(double) * n3))) return rc;
+      if ((rc = copy_d2h(c, U + (size_t)k0 * nb6, B.U, sizeof(double) * nb6 * (size_t)kb))) return rc;
+      if ((rc = copy_d2h(c, F + (size_t)k0 * nb6, B.F, sizeof(double) * nb6 * (size_t)kb))) return rc;
+    } else {
+      for (int col = 0; lambda && col < kb; ++col)
+        RBL_HIP(c, hipMemcpyAsync(lambda + (size_t)(k0 + col) * n3, B.x + (size_t)col * nsys, sizeof(double) * n3, d2d, c->stream));
+      RBL_HIP(c, hipMemcpyAsync(U + (size_t)k0 * nb6, B.U, sizeof(double) * nb6 * (size_t)kb, d2d, c->stream));
+      RBL_HIP(c, hipMemcpyAsync(F + (size_t)k0 * nb6, B.F, sizeof(double) * nb6 * (size_t)kb, d2d, c->stream));
+    }
+    if ((rc = finish_and_check(c))) return rc;           // the latched device flags, batch by batch
+  }
   return RBL_OK;
 }
 
@@ -615,6 +772,32 @@ int rbl_step_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *bod
 {
   if (!c) return RBL_ERR_ARG;
   return mx_step(c, "step_mixed_dof", prescribed6, body_in, slip, max_iter, rtol, F, iters, resid, 6);
+}
+
+// ---- many right-hand sides under one mask, in lock step ------------------------------------------------------------------------------
+int rbl_solve_mixed_multi(rbl_ctx *c, const uint8_t *prescribed, int nrhs, const double *body_in, const double *slip, int max_iter,
+                          double rtol, double *lambda, double *U, double *F, int *iters, double *resid)
+{
+  return mx_multi(c, "solve_mixed_multi", true, prescribed, nrhs, body_in, slip, max_iter, rtol, lambda, U, F, iters, resid, 1);
+}
+
+int rbl_solve_mixed_multi_dev(rbl_ctx *c, const uint8_t *prescribed, int nrhs, const double *d_body_in, const double *d_slip, int max_iter,
+                              double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid)
+{
+  return mx_multi(c, "solve_mixed_multi_dev", false, prescribed, nrhs, d_body_in, d_slip, max_iter, rtol, d_lambda, d_U, d_F, iters, resid, 1);
+}
+
+int rbl_solve_mixed_dof_multi(rbl_ctx *c, const uint8_t *prescribed6, int nrhs, const double *body_in, const double *slip, int max_iter,
+                              double rtol, double *lambda, double *U, double *F, int *iters, double *resid)
+{
+  return mx_multi(c, "solve_mixed_dof_multi", true, prescribed6, nrhs, body_in, slip, max_iter, rtol, lambda, U, F, iters, resid, 6);
+}
+
+int rbl_solve_mixed_dof_multi_dev(rbl_ctx *c, const uint8_t *prescribed6, int nrhs, const double *d_body_in, const double *d_slip,
+                                  int max_iter, double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid)
+{
+  return mx_multi(c, "solve_mixed_dof_multi_dev", false, prescribed6, nrhs, d_body_in, d_slip, max_iter, rtol, d_lambda, d_U, d_F, iters,
+                  resid, 6);
 }
 
 int rbl_RHS_and_Midpoint_mixed_dev(rbl_ctx *c, const uint8_t *prescribed, const double *d_body_in, const double *d_slip,

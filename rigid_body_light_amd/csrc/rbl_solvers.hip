@@ -277,7 +277,11 @@ static int gmres_core(rbl_ctx *c, const RblSolveOps *ops, const double *d_rhs, i
 // have converged stop iterating; their slots ride along in the product (which costs the same for 13 as for 16) as zero vectors:
 // the basis slots such a column never wrote (and the last one, w / |w|, non-finite after an exact breakdown) are cleared once,
 // when it converges, so the preconditioner and the product never read stale or unwritten memory for it.
-static int gmres_multi_batch(rbl_ctx *c, const double *d_rhs, int k, int m, double rtol, double *d_x, int *iters_out, double *resid_out)
+// ops: the caller's multi-vector operator and preconditioner (RblMultiOps) instead of the saddle operator's; they get the bit set of
+// the columns still iterating and leave the others' outputs alone (written at iteration 0, when every column is live, and never
+// read after the column has converged).  NULL: the library's own, launch for launch what this function has always enqueued.
+static int gmres_multi_batch(rbl_ctx *c, const RblMultiOps *ops, const double *d_rhs, int k, int m, double rtol, double *d_x, int *iters_out,
+                             double *resid_out)
 {
   const double fsign = gmres_fsign(c);              // one eigenvalue cluster instead of two, as in the one-vector solver
   const RblBodyState &S = c->S;
@@ -302,16 +306,26 @@ static int gmres_multi_batch(rbl_ctx *c, const double *d_rhs, int k, int m, doub
   std::vector<int> used((size_t)k, 0), done((size_t)k, 0);
   std::vector<double> resid((size_t)k, 1.0);
   int n_done = 0;
+  const unsigned all = k >= 32 ? ~0u : (1u << k) - 1u;
   for (int j = 0; j < m && n_done < k; ++j) {
+    unsigned live = 0;
+    for (int col = 0; col < k; ++col) live |= done[(size_t)col] ? 0u : 1u << col;
     // z_c = P^-1 V_c,j : all columns together (converged ones ride along on zeroed slots, whose results are never read)
-    if ((rc = apply_PC_multi_dev(c, Vc(0, j), Zc(0), Sc(0), k, pitch, fsign))) return rc;
-    // w_c = [M lambda - K U ; K^T lambda] : ONE multi-vector product, then the O(N) body terms column by column
-    if ((rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3 * (size_t)k))) return rc;
-    if ((rc = apply_M_multi_enqueue(c, S.wall, Zc(0), (const double *)c->d_pos.p, N, k, (double *)c->d_sad.p, pitch, n3))) return rc;
+    if ((rc = ops ? ops->pc(c, ops->user, Vc(0, j), Zc(0), Sc(0), k, pitch, live) : apply_PC_multi_dev(c, Vc(0, j), Zc(0), Sc(0), k, pitch, fsign)))
+      return rc;
+    if (ops) {                                           // w_c = A z_c : the caller's product and its tail, ONE call for the live columns
+      if ((rc = ops->op(c, ops->user, Zc(0), Wc(0), k, pitch, live))) return rc;
+    } else {
+      // w_c = [M lambda - K U ; K^T lambda] : ONE multi-vector product, then the O(N) body terms column by column
+      if ((rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3 * (size_t)k))) return rc;
+      if ((rc = apply_M_multi_enqueue(c, S.wall, Zc(0), (const double *)c->d_pos.p, N, k, (double *)c->d_sad.p, pitch, n3))) return rc;
+    }
     for (int col = 0; col < k; ++col) {
       if (done[(size_t)col]) continue;
-      rbl_launch_K_x_U(c->stream, (const double *)c->d_lever.p, Zc(col) + n3, S.N_blb, N, Wc(col), (const double *)c->d_sad.p + (size_t)col * (size_t)n3, -1.0);
-      rbl_launch_KT_x_Lam(c->stream, (const double *)c->d_lever.p, Zc(col), S.N_blb, S.N_bod, Wc(col) + n3);
+      if (!ops) {
+        rbl_launch_K_x_U(c->stream, (const double *)c->d_lever.p, Zc(col) + n3, S.N_blb, N, Wc(col), (const double *)c->d_sad.p + (size_t)col * (size_t)n3, -1.0);
+        rbl_launch_KT_x_Lam(c->stream, (const double *)c->d_lever.p, Zc(col), S.N_blb, S.N_bod, Wc(col) + n3);
+      }
       rbl_launch_arnoldi_step(c->stream, Vc(col, 0), nsys, j + 1, Wc(col), Hall + hcol * col + 1 + (size_t)j * ldh, Vc(col, j + 1), part);
       used[(size_t)col] = j + 1;
     }
@@ -342,10 +356,21 @@ static int gmres_multi_batch(rbl_ctx *c, const double *d_rhs, int k, int m, doub
     if (iters_out) iters_out[col] = u;
     if (resid_out) resid_out[col] = resid[(size_t)col];
   }
-  if ((rc = apply_PC_multi_dev(c, Zc(0), Wc(0), Sc(0), k, pitch, fsign))) return rc;                        // x = P^-1 z
+  if ((rc = ops ? ops->pc(c, ops->user, Zc(0), Wc(0), Sc(0), k, pitch, all) : apply_PC_multi_dev(c, Zc(0), Wc(0), Sc(0), k, pitch, fsign)))
+    return rc;                                           // x = P^-1 z
   for (int col = 0; col < k; ++col)
     RBL_HIP(c, hipMemcpyAsync(d_x + (size_t)col * (size_t)nsys, Wc(col), sizeof(double) * (size_t)nsys, hipMemcpyDeviceToDevice, c->stream));
   return RBL_OK;
+}
+
+int gmres_multi_with_ops(rbl_ctx *c, const RblMultiOps *ops, const double *d_rhs, int k, int max_iter, double rtol, double *d_x,
+                         int *iters_out, double *resid_out)
+{
+  if (!ops || !ops->op || !ops->pc) return rbl_fail(c, RBL_ERR_ARG, "gmres (multi): no operator");
+  if (!d_rhs || !d_x || k < 1 || k > 16 || max_iter < 1) return rbl_fail(c, RBL_ERR_ARG, "gmres (multi): bad arguments");
+  if (max_iter + 1 > rbl_gmres_max_vectors()) return rbl_fail(c, RBL_ERR_ARG, "gmres: at most 255 iterations (no restart)");
+  const int rc = sync_bodies(c); if (rc) return rc;
+  return gmres_multi_batch(c, ops, d_rhs, k, max_iter, rtol, d_x, iters_out, resid_out);
 }
 
 int rbl_gmres_saddle_multi_dev(rbl_ctx *c, const double *d_rhs, int nrhs, int max_iter, double rtol, double *d_x, int *iters_out,
@@ -360,7 +385,7 @@ int rbl_gmres_saddle_multi_dev(rbl_ctx *c, const double *d_rhs, int nrhs, int ma
   const int64_t nsys = (int64_t)3 * c->S.N_bod * c->S.N_blb + (int64_t)6 * c->S.N_bod;
   for (int k0 = 0; k0 < nrhs && !rc; k0 += 16) {
     const int kb = nrhs - k0 < 16 ? nrhs - k0 : 16;
-    rc = gmres_multi_batch(c, d_rhs + (size_t)k0 * (size_t)nsys, kb, max_iter, rtol, d_x + (size_t)k0 * (size_t)nsys,
+    rc = gmres_multi_batch(c, nullptr, d_rhs + (size_t)k0 * (size_t)nsys, kb, max_iter, rtol, d_x + (size_t)k0 * (size_t)nsys,
                            iters_out ? iters_out + k0 : nullptr, resid_out ? resid_out + k0 : nullptr);
   }
   if (rc) return rc;

@@ -12,7 +12,7 @@ Beyond the reference surface (its C++ has these, its Python does not): `solve_sa
 `KTinv_RFD`, `M_RFD_cfgs`, `M_RFD_from_U`, `KT_RFD_from_U`, `evolve_rigid_bodies_RFD`, `apply_M_multi`,
 `dense_mobility`, `velocity_field` (the flow at arbitrary points), prescribed kinematics (`solve_mixed`, `step_mixed`,
 `body_resistance_matrix`: bodies that are held or driven, and the loads that takes; `solve_mixed_dof`, `step_mixed_dof`: the same for
-single velocity components; `step_brownian_mixed`,
+single velocity components; `solve_mixed_multi`, `solve_mixed_dof_multi`: many right-hand sides under one mask in lock step; `step_brownian_mixed`,
 `RHS_and_Midpoint_mixed`: the same among Brownian bodies), and a force model the reference does not have (`set_interactions`, `interaction_forces`).
 """
 import numpy as np
@@ -328,6 +328,39 @@ class RigidBody:
         mask, bi, sl = self._mixed_dof_args(prescribed, body_in, slip)
         return self.cb.step_mixed_dof(mask, bi, sl, int(max_iter), float(rtol))
 
+    def _multi_body_in_and_slip(self, body_in, slip):
+        bi = np.asarray(body_in)
+        if bi.dtype.kind not in "fiu" or bi.ndim != 2 or bi.shape[0] < 1 or bi.shape[1] != 6 * self.N_bodies:
+            raise ValueError(f"body_in must be a real array of shape (k, 6*N_bodies) = (k, {6 * self.N_bodies}) with k >= 1: one row per "
+                             f"right-hand side. Got dtype {bi.dtype}, shape {bi.shape}")
+        sl = None
+        if slip is not None:
+            sl = np.asarray(slip)
+            if sl.dtype.kind not in "fiu" or sl.shape != (bi.shape[0], 3 * self.total_blobs):
+                raise ValueError(f"slip must be a real array of shape (k, 3*N_blobs) = ({bi.shape[0]}, {3 * self.total_blobs}). "
+                                 f"Got dtype {sl.dtype}, shape {sl.shape}")
+            sl = np.ascontiguousarray(sl, dtype=np.float64)
+        return np.ascontiguousarray(bi, dtype=np.float64), sl
+
+    def solve_mixed_multi(self, prescribed, body_in, slip=None, max_iter=100, rtol=1.0e-8):
+        """solve_mixed for k right-hand sides under ONE mask, in lock step: body_in has shape (k, 6 N_bodies), slip is None or
+        (k, 3 N_blobs), `prescribed` is read exactly as solve_mixed reads it.  The k GMRES recurrences advance together (16 a batch):
+        one multi-vector mobility product per iteration on the fp64 matrix cores, shared passes over the per-body factors, one launch
+        of each masked kernel for all columns; a column stops when it has converged, and each column's iterates are those of
+        solve_mixed on it alone up to the rounding of the product (16 columns at cfg 3: a third of the sequential loop's time).
+        -> (lambda (k, 3 N_blobs), U (k, 6 N_bodies), F (k, 6 N_bodies), iterations (k,), residual estimates (k,))"""
+        mask = self._prescribed_mask(prescribed)
+        bi, sl = self._multi_body_in_and_slip(body_in, slip)
+        return self.cb.solve_mixed_multi(mask, bi, sl, int(max_iter), float(rtol))
+
+    def solve_mixed_dof_multi(self, prescribed, body_in, slip=None, max_iter=100, rtol=1.0e-8):
+        """solve_mixed_dof for k right-hand sides under ONE mask per velocity component (a boolean array of shape (N_bodies, 6)), in
+        lock step as solve_mixed_multi: body_in (k, 6 N_bodies), slip None or (k, 3 N_blobs).
+        -> (lambda (k, 3 N_blobs), U (k, 6 N_bodies), F (k, 6 N_bodies), iterations (k,), residual estimates (k,))"""
+        mask = self._mixed_dof_args(prescribed, np.zeros(6 * self.N_bodies), None)[0]
+        bi, sl = self._multi_body_in_and_slip(body_in, slip)
+        return self.cb.solve_mixed_dof_multi(mask, bi, sl, int(max_iter), float(rtol))
+
     def _noise_arg(self, W):
         if W is None:
             return None
@@ -358,15 +391,23 @@ class RigidBody:
         return self.cb.step_brownian_mixed(mask, bi, sl, W, int(seed), method, bool(split_rand), float(delta),
                                            int(max_iter), float(rtol))
 
-    def body_resistance_matrix(self, max_iter=100, rtol=1.0e-8, columns=None):
+    def body_resistance_matrix(self, max_iter=100, rtol=1.0e-8, columns=None, lock_step=False):
         """The (6 N_bodies) x (6 N_bodies) body resistance matrix R = N^-1 of the current configuration, the inverse of
         `body_mobility_matrix` (symmetric positive definite): the PHYSICAL loads that move the bodies with velocities U are R U.
         Every body prescribed, one solve_mixed per unit velocity (one after the other).  The F of solve_mixed follows the reference
         convention of step_deterministic's F_body (rhs [slip ; -F], U = -N F), so a column here is -F.  columns: only these
-        unit velocities (default all).  -> (R[:, columns], iterations)"""
+        unit velocities (default all).  lock_step=True: the unit velocities go through solve_mixed_multi, 16 columns advancing
+        together; the columns agree with the default's to the solves' tolerance, not bit for bit.  -> (R[:, columns], iterations)"""
         nb6 = 6 * self.N_bodies
         cols = np.arange(nb6) if columns is None else np.asarray(columns, dtype=int).reshape(-1)
         everyone = np.ones(self.N_bodies, dtype=bool)
+        if lock_step:
+            if cols.size == 0:
+                return np.zeros((nb6, 0)), np.zeros(0, dtype=int)
+            U = np.zeros((cols.size, nb6))
+            U[np.arange(cols.size), cols] = 1.0
+            _, _, F, its, _ = self.solve_mixed_multi(everyone, U, max_iter=max_iter, rtol=rtol)
+            return -np.ascontiguousarray(F.T), np.asarray(its, dtype=int)
         R, its = np.zeros((nb6, cols.size)), np.zeros(cols.size, dtype=int)
         for j, c in enumerate(cols):
             U = np.zeros(nb6)
