@@ -515,7 +515,10 @@ enum {
   RBL_OPT_SYM_TAIL_SHARE = 36,     /* [0] per-mille of the column tiles swept at that length (0 = heuristic, 1 .. 1000).  The short length
                                       set to the chunk length together with 1000 here: the schedule of the one-length kernel, the whole
                                       (row group x chunk) rectangle in its old order                                                 */
-  RBL_OPT_COUNT = 37
+  RBL_OPT_RECORD_MOMENTS = 37,     /* [0] every whole-step entry point also leaves the first moments D_b = sum (r_i - X_b) lambda_i^T of its
+                                      solve's blob forces on the device (section 8: rbl_step_moments, rbl_ensemble_step_moments); one small
+                                      launch per step.  Setting the option (to either value) discards what was recorded              */
+  RBL_OPT_COUNT = 38
 };
 int rbl_set_option(rbl_ctx *ctx, int option, int64_t value);
 int rbl_get_option(const rbl_ctx *ctx, int option, int64_t *value);
@@ -826,6 +829,73 @@ int rbl_RHS_and_Midpoint_mixed_dev(rbl_ctx *ctx, const uint8_t *prescribed, cons
 int rbl_step_brownian_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
                             uint64_t seed, int method, int split_rand, double delta, int max_iter, double rtol, double *F,
                             int *iters, double *resid);
+
+/* ===================================================================== */
+/* 8. Imposed flow and active slip (rigid_body_light_amd/csrc/rbl_flow.hip) */
+/* ===================================================================== */
+/* The other half of the right-hand side, kept in the context and evaluated on the device as the force model (section 4) is: a
+ * background flow that is linear in space and a slip pattern carried by the bodies (the reference has neither; its only handle
+ * is a lab-frame slip vector per call).  Sign convention of the `slip` argument throughout: the saddle system is
+ * M lambda - K U = slip, so a blob that must move with the fluid velocity u_inf gets slip = -u_inf(r_i).  Per blob i of body b:
+ *     t_i = scale_b R(q_b) s_body,i - (u0 + G r_i)
+ * with the blob positions r_i and rotations R(q_b) of the configuration (what rbl_multi_body_pos returns).  No sums over blobs, no
+ * atomics: bitwise the same on every call, every rank (a context with a communicator evaluates the whole term, replicated) and
+ * for every replica of an ensemble.
+ *
+ *   rbl_set_background_flow  u_inf(r) = u0 + G r, G row-major, G[3 i + j] = d u_i / d x_j.  on = 0 switches the flow off.  NULL or
+ *                            non-finite entries: RBL_ERR_ARG, the previous model stays in place.
+ *   rbl_set_body_slip        slip_body[3 N_blb]: a pattern in the BODY frame, one vector per blob of the shared structure, in the
+ *                            units and the sign of the `slip` argument; slip_scale[n_scale]: a factor per body (NULL: 1 for every
+ *                            body; 0: a passive body).  Needs rbl_set_parameters first (RBL_ERR_STATE).  n_scale must equal the
+ *                            body count of whatever configuration later uses the model -- the context's, or an ensemble's, where
+ *                            slip_scale[b] serves body b of every replica; a mismatch is RBL_ERR_ARG at that use, not here.  The
+ *                            pattern belongs to the structure: after any later rbl_set_parameters call a pattern that is still
+ *                            switched on is RBL_ERR_STATE at the use, until rbl_set_body_slip is called again.
+ *   rbl_get_flow_model       u0G12 = [u0 (3) | G (9)], the two switches; any pointer may be NULL.
+ *
+ * With the wall (rbl_set_wall_pc) the mobility assumes no slip at z = 0, so a flow that does not vanish there is refused: u0 != 0
+ * or any of G[.][0], G[.][1], G[2][2] non-zero -- only u = (G02 z, G12 z, 0) passes -- is RBL_ERR_ARG at every use, a step or a
+ * query, before the device is touched.  In free space any G is accepted.
+ *
+ * Where it enters: the term is added to the slip at q^n -- the configuration the step starts from, where the force model is
+ * evaluated; for the Brownian steps the one RHS_and_Midpoint is called on -- in every whole-step entry point and nowhere else:
+ * rbl_step_deterministic, rbl_step_brownian, rbl_step_mixed, rbl_step_mixed_dof, rbl_step_brownian_mixed,
+ * rbl_ensemble_step_deterministic, rbl_ensemble_step_brownian, rbl_ensemble_step_mixed, rbl_ensemble_step_brownian_mixed.  When
+ * the caller also passes `slip` the right-hand side holds slip + t, added in that order.  No lower-level entry point adds it
+ * (rbl_solve_mixed*, rbl_gmres_saddle*, rbl_RHS_and_Midpoint*, the ensemble solves): for those there are the queries.  With both
+ * parts off every entry point does exactly what it does without this section: no launch, no allocation.
+ * Left out on purpose: flows that are not linear in r, evaluation at q^{n+1/2}, a flow per replica.
+ *
+ *   rbl_flow_slip_dev        the term at the context's configuration into device memory, 3 N_blobs doubles (enqueued, not
+ *                            synchronised); zeros with both parts off
+ *   rbl_flow_slip            the same into a host array (synchronous)
+ *   rbl_ensemble_flow_slip   the term at every replica's configuration, R n3 doubles, host
+ *
+ * First moments of the blob forces.  For each body b, with the lever arms l_i = r_i - X_b the K operators use,
+ *     D_b = sum_{i in b} l_i lambda_i^T      (3 x 3 row-major, 9 N_bod doubles in all)
+ * one workgroup per body, fixed-order reduction, no atomics: bitwise reproducible.  The antisymmetric part of D_b is the torque of
+ * rbl_KT_x_Lam, its symmetric traceless part the stresslet.  Any 3 N_blobs vector may be passed: the lambda of a solve, or the
+ * f_blob of rbl_interaction_forces for the interparticle contribution.
+ *   rbl_first_moments_dev    device pointers, enqueued on the context's stream
+ *   rbl_first_moments        host arrays, synchronous
+ * With the option RBL_OPT_RECORD_MOMENTS switched on every whole-step entry point listed above also computes D_b from the lambda of its solve, with
+ * the lever arms of the configuration it solved at (q^n for the deterministic steps, q^{n+1/2} for the midpoint steps), into a
+ * device buffer: one small launch per step, one launch over R N_bod bodies for an ensemble.
+ *   rbl_step_moments           the last recorded set, 9 N_bod doubles
+ *   rbl_ensemble_step_moments  the same of the last ensemble step, R 9 N_bod doubles
+ * Both return RBL_ERR_STATE when no step has recorded since the option was set or since the configuration's size changed.
+ * What is recorded is the first moment of that step's lambda, thermal part included in a Brownian step.  The Brownian drift's
+ * contribution to the stress is NOT added: the recorded moments of Brownian steps do not average to the full Brownian stress. */
+int rbl_set_background_flow(rbl_ctx *ctx, const double u0[3], const double G[9], int on);
+int rbl_set_body_slip(rbl_ctx *ctx, const double *slip_body, const double *slip_scale, int n_scale, int on);
+int rbl_get_flow_model(const rbl_ctx *ctx, double *u0G12, int *flow_on, int *body_slip_on);
+int rbl_flow_slip_dev(rbl_ctx *ctx, double *d_out);
+int rbl_flow_slip(rbl_ctx *ctx, double *out);
+int rbl_ensemble_flow_slip(rbl_ctx *ctx, double *out);
+int rbl_first_moments_dev(rbl_ctx *ctx, const double *d_lambda, double *d_D);
+int rbl_first_moments(rbl_ctx *ctx, const double *lambda, double *D);
+int rbl_step_moments(rbl_ctx *ctx, double *D);
+int rbl_ensemble_step_moments(rbl_ctx *ctx, double *D);
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,12 @@ def lib():
         L.rbl_RHS_and_Midpoint_mixed_dev.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, vp, vp, vp]
         L.rbl_step_brownian_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, C.c_int, dbl, vp, C.POINTER(C.c_int),
                                               C.POINTER(dbl)]
+        L.rbl_set_background_flow.argtypes = [vp, vp, vp, C.c_int]
+        L.rbl_set_body_slip.argtypes = [vp, vp, vp, C.c_int, C.c_int]
+        L.rbl_get_flow_model.argtypes = [vp, C.POINTER(dbl), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.rbl_flow_slip_dev.argtypes = L.rbl_flow_slip.argtypes = L.rbl_ensemble_flow_slip.argtypes = [vp, vp]
+        L.rbl_first_moments_dev.argtypes = L.rbl_first_moments.argtypes = [vp, vp, vp]
+        L.rbl_step_moments.argtypes = L.rbl_ensemble_step_moments.argtypes = [vp, vp]
         _LIB = L
     return _LIB
 
@@ -313,6 +319,91 @@ class DeviceContext:
         bp, pp = C.c_int64(0), C.c_int64(0)
         self._chk(self.L.rbl_interaction_stats(self.h, C.byref(bp), C.byref(pp)))
         return bp.value, pp.value
+
+    # -- imposed flow, active slip, first moments (include/rbl.h section 8) --------------
+    def set_background_flow(self, u0=None, G=None, on=True):
+        """u_inf(r) = u0 + G r, G[i, j] = d u_i / d x_j (None: zeros); the whole-step entry points and the krylov.py steppers add
+        -u_inf at the blobs of q^n to their slip.  on=False switches the flow off."""
+        import numpy as np
+        u0 = np.zeros(3) if u0 is None else np.asarray(u0, dtype=np.float64)
+        G = np.zeros((3, 3)) if G is None else np.asarray(G, dtype=np.float64)
+        if u0.shape != (3,) or G.shape != (3, 3):
+            raise ValueError("set_background_flow: u0 must have shape (3,) and G (3, 3); got %s and %s" % (u0.shape, G.shape))
+        u0, G = np.ascontiguousarray(u0), np.ascontiguousarray(G)
+        self._chk(self.L.rbl_set_background_flow(self.h, u0.ctypes.data, G.ctypes.data, int(bool(on))))
+
+    def set_body_slip(self, slip_body, scale=None, on=True):
+        """slip_body: the body-frame pattern, 3 N_blb numbers; scale: a factor per body (None: 1), one per body of the context's
+        configuration or of an ensemble's replica"""
+        import numpy as np
+        sb = np.ascontiguousarray(np.asarray(slip_body, dtype=np.float64).reshape(-1))
+        if sb.size != 3 * self._sizes()[1]:
+            raise ValueError("set_body_slip: slip_body must have 3 N_blb = %d entries; got shape %s" % (3 * self._sizes()[1], np.shape(slip_body)))
+        sc = None if scale is None else np.ascontiguousarray(np.asarray(scale, dtype=np.float64).reshape(-1))
+        self._chk(self.L.rbl_set_body_slip(self.h, sb.ctypes.data, None if sc is None else sc.ctypes.data, 0 if sc is None else sc.size,
+                                           int(bool(on))))
+
+    def flow_model(self):
+        """{u0 (3,), G (3, 3), flow_on, body_slip_on}"""
+        import numpy as np
+        v, f, b = (C.c_double * 12)(), C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_flow_model(self.h, v, C.byref(f), C.byref(b)))
+        return {"u0": np.array(v[:3]), "G": np.array(v[3:]).reshape(3, 3), "flow_on": bool(f.value), "body_slip_on": bool(b.value)}
+
+    def flow_model_on(self):
+        f, b = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_flow_model(self.h, None, C.byref(f), C.byref(b)))
+        return bool(f.value or b.value)
+
+    def flow_slip_dev(self, d_out):
+        """the model's term at the current configuration into a device buffer of 3 N_blobs doubles (enqueued)"""
+        self._chk(self.L.rbl_flow_slip_dev(self.h, d_out))
+
+    def flow_slip(self):
+        import numpy as np
+        nb, nblb = self._sizes()
+        out = np.zeros(3 * nb * nblb)
+        self._chk(self.L.rbl_flow_slip(self.h, out.ctypes.data))
+        return out
+
+    def first_moments_dev(self, d_lambda, d_D):
+        """D_b = sum (r_i - X_b) lambda_i^T per body: device buffers of 3 N_blobs and 9 N_bod doubles (enqueued)"""
+        self._chk(self.L.rbl_first_moments_dev(self.h, d_lambda, d_D))
+
+    def first_moments(self, lam):
+        import numpy as np
+        nb, nblb = self._sizes()
+        lam = np.ascontiguousarray(np.asarray(lam, dtype=np.float64).reshape(-1))
+        if lam.size != 3 * nb * nblb:
+            raise ValueError("first_moments: lam must have 3 N_blobs = %d entries; got %d" % (3 * nb * nblb, lam.size))
+        D = np.zeros((nb, 3, 3))
+        self._chk(self.L.rbl_first_moments(self.h, lam.ctypes.data, D.ctypes.data))
+        return D
+
+    def record_moments(self, on=True):
+        self.set_option("record_moments", int(bool(on)))
+
+    def step_moments(self):
+        import numpy as np
+        D = np.zeros((self._sizes()[0], 3, 3))
+        self._chk(self.L.rbl_step_moments(self.h, D.ctypes.data))
+        return D
+
+    def ensemble_flow_slip(self):
+        """-> (R, n3): the model's term at every replica's configuration"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        out = np.zeros((R, 3 * nb * self._sizes()[1]))
+        self._chk(self.L.rbl_ensemble_flow_slip(self.h, out.ctypes.data))
+        return out
+
+    def ensemble_step_moments(self):
+        """-> (R, N_bod, 3, 3): first moments recorded by the last ensemble step"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        D = np.zeros((R, nb, 3, 3))
+        self._chk(self.L.rbl_ensemble_step_moments(self.h, D.ctypes.data))
+        return D
 
     # -- ensembles of independent replicas (include/rbl.h section 5) ---------------------
     def ensemble_set_config(self, X, Q):

@@ -621,6 +621,56 @@ struct CManyBodies {
     return E;
   }
 
+  // ---- imposed flow and active slip, first moments (include/rbl.h section 8) ----
+  void set_background_flow(darr u0, darr G, bool on)
+  {
+    if (u0.size() != 3 || G.size() != 9) throw std::runtime_error("set_background_flow: u0 must have 3 entries, G 9");
+    check(rbl_set_background_flow(ctx, u0.data(), G.data(), on ? 1 : 0));
+  }
+  void set_body_slip(darr slip_body, py::object scale, bool on)
+  {
+    if (slip_body.size() != (py::ssize_t)3 * n_blb()) throw std::runtime_error("set_body_slip: slip_body must have 3 N_blb entries");
+    darr sc;
+    if (!scale.is_none()) sc = scale.cast<darr>();
+    check(rbl_set_body_slip(ctx, slip_body.data(), scale.is_none() ? nullptr : sc.data(), scale.is_none() ? 0 : (int)sc.size(), on ? 1 : 0));
+  }
+  py::tuple flow_model() const
+  {
+    darr v(12);
+    int f = 0, b = 0;
+    check(rbl_get_flow_model(ctx, v.mutable_data(), &f, &b));
+    return py::make_tuple(v, f != 0, b != 0);
+  }
+  darr flow_slip()
+  {
+    darr out(n3());
+    int rc;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_flow_slip(ctx, out.mutable_data());
+    }
+    check(rc);
+    return out;
+  }
+  darr first_moments(darr lam)
+  {
+    if (lam.size() != n3()) throw std::runtime_error("first_moments: lambda must have 3 N_blobs entries");
+    darr out(9 * (py::ssize_t)n_bod());
+    int rc;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_first_moments(ctx, lam.data(), out.mutable_data());
+    }
+    check(rc);
+    return out;
+  }
+  darr step_moments()
+  {
+    darr out(9 * (py::ssize_t)n_bod());
+    check(rbl_step_moments(ctx, out.mutable_data()));
+    return out;
+  }
+
   void set_option(const std::string &name, int64_t value)
   {
     const int key = rbl_option_key(name.c_str());
@@ -712,6 +762,14 @@ PYBIND11_MODULE(c_rigid, m)
       .def("step_brownian_mixed", &CManyBodies::step_brownian_mixed, py::arg("prescribed"), py::arg("body_in"),
            py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "lanczos_pc",
            py::arg("split_rand") = true, py::arg("delta") = 1.0e-4, py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
+      .def("set_background_flow", &CManyBodies::set_background_flow, "u_inf(r) = u0 + G r added to every step's slip as -u_inf",
+           py::arg("u0"), py::arg("G"), py::arg("on") = true)
+      .def("set_body_slip", &CManyBodies::set_body_slip, "slip pattern in the body frame, a factor per body", py::arg("slip_body"),
+           py::arg("scale") = py::none(), py::arg("on") = true)
+      .def("flow_model", &CManyBodies::flow_model, "([u0 | G], flow on, body slip on)")
+      .def("flow_slip", &CManyBodies::flow_slip, "the flow model's term at the current configuration, 3 N_blobs")
+      .def("first_moments", &CManyBodies::first_moments, "D_b = sum (r_i - X_b) lambda_i^T per body, 9 N_bod", py::arg("lambda"))
+      .def("step_moments", &CManyBodies::step_moments, "first moments recorded by the last step (option record_moments)")
       .def("set_option", &CManyBodies::set_option, py::arg("name"), py::arg("value"))
       .def("get_option", &CManyBodies::get_option, py::arg("name"))
       .def("handle", &CManyBodies::handle, "address of the underlying rbl_ctx (for the ctypes device API)")

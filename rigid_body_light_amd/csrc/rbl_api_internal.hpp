@@ -11,6 +11,7 @@
 //   rbl_ensemble.hip  ensembles of independent replicas of one small system
 //   rbl_field.hip     the fluid velocity at arbitrary points from blob forces
 //   rbl_mixed.hip     prescribed kinematics: held or driven bodies among free ones, the loads that takes; the entry points of their Brownian step
+//   rbl_flow.hip      imposed linear flow and body-frame slip added to every step's slip, first moments of the blob forces
 // None of these symbols is exported from librbl.so.
 #pragma once
 #include <functional>
@@ -152,5 +153,23 @@ int ia_add_to_step_force(rbl_ctx *c, double *d_force);
 size_t ia_batch_bytes(int N_bod, int N_blb, int reps);
 int ia_eval_batch(rbl_ctx *c, const double *d_X, const double *d_pos, const double *d_lever, int N_bod, int reps, void *d_work,
                   double **d_f, double *d_FT, double *d_e, unsigned *d_err);
+
+// ---- rbl_flow.hip -------------------------------------------------------------------------------------------------
+// the model's checks that need no device (wall consistency, the pattern's structure, n_scale against n_bod bodies); RBL_OK while
+// both parts are off
+int flow_check(rbl_ctx *c, int n_bod);
+// the steps' use of the term t = scale R s_body - u_inf at the context's configuration: d_slip (3 N) becomes slip + t when
+// *have_slip, t otherwise, and *have_slip becomes true.  While both parts are off: nothing (no launch, no allocation)
+int flow_add_to_step_slip(rbl_ctx *c, double *d_slip, bool *have_slip);
+// the same for `reps` replicas of N_bod bodies in one launch (positions and orientations of all of them)
+int flow_add_batch(rbl_ctx *c, const double *d_pos, const double *d_Q, int N_bod, int reps, double *d_slip, bool *have_slip);
+// D_b = sum l lambda^T of n_bodies bodies, Nb a replica; d_lever, or NULL and (d_Q, d_cfg) to rebuild the lever arms
+void flow_launch_moments(rbl_ctx *c, const double *d_lever, const double *d_Q, const double *d_cfg, const double *d_lam, int Nb,
+                         int n_bodies, int64_t rep_stride, double *d_D);
+// a whole-step entry point begins: with RBL_OPT_RECORD_MOMENTS on the previous record is dropped, so a step whose solve fails
+// leaves nothing to read
+void flow_begin_step(rbl_ctx *c);
+// RBL_OPT_RECORD_MOMENTS: the moments of d_lambda at the configuration the context is at; no-op while the option is off
+int flow_record_moments(rbl_ctx *c, const double *d_lambda);
 
 #pragma GCC visibility pop

@@ -141,6 +141,10 @@ static const RblBufRow kDevBufs[] = {
     {&rbl_ctx::d_vf, RBL_BUF_SCRATCH},            // velocity field, host form: reserved at its start, within one call
     {&rbl_ctx::d_vfw, RBL_BUF_SCRATCH},           // velocity field: packed sources and slabs, reserved right before its launches
     {&rbl_ctx::d_mx, RBL_BUF_SCRATCH},            // mixed solve: reserved once, at the start of each section 7 entry point
+    {&rbl_ctx::d_flow, RBL_BUF_PERSIST},          // slip pattern and scales of the flow model (fl_dev_valid)
+    {&rbl_ctx::d_flow_w, RBL_BUF_SCRATCH},        // host forms of section 8: reserved at their start, within one call
+    {&rbl_ctx::d_mom, RBL_BUF_PERSIST},           // first moments of the last recording step (mom_nb)
+    {&rbl_ctx::d_ens_mom, RBL_BUF_PERSIST},       // the same of the last recording ensemble step (ens_mom_R)
 };
 
 // the poison pattern, on the context's stream; nothing while the stream is being captured into a graph (a capture may not
@@ -420,6 +424,7 @@ int rbl_set_parameters(rbl_ctx *c, double a, double dt, double kBT, double eta, 
   c->tl_valid = false; c->pc_keep_once = false;
   S.N_blb = N_blb;
   S.params_set = true;
+  ++c->params_gen;                                     // a body-frame slip pattern set before this call is stale (rbl_flow.hip)
   S.M_scale = 1.0;
   c->dev_bodies_valid = false; c->dev_pc_valid = false; c->dev_blk_valid = false; c->dev_xq_valid = false;
   c->bf_valid = false;                                 // the body-frame factor belongs to (a, eta, cfg)

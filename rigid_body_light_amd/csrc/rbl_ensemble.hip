@@ -328,6 +328,10 @@ EnsWork ens_carve(void *base, int R, int Nb, int nbl, int max_iter, size_t *byte
   return w;
 }
 
+// the flow model's host-side refusals (wall consistency, n_scale) for the ensemble's body count, made by the step entry points
+// and the query before ens_ready touches the device; without an ensemble there is nothing to check (ens_ready says so)
+int ens_flow_check(rbl_ctx *c) { return c->ens_R ? flow_check(c, c->ens_Nb) : RBL_OK; }
+
 int ens_fail_state(rbl_ctx *c) { return rbl_fail(c, RBL_ERR_STATE, "ensemble: no ensemble configuration (rbl_ensemble_set_config)"); }
 
 double *ens_X(rbl_ctx *c, int which) { return (double *)c->d_ens.p + (size_t)which * 7 * c->ens_R * c->ens_Nb; }
@@ -375,12 +379,16 @@ int ens_finish(rbl_ctx *c, const EnsWork &w, int R, int *iters, double *resid, b
   if (U) std::memcpy(U, h.data() + w.rb_bytes, ub);
   if (F) std::memcpy(F, h.data() + w.rb_bytes + ub, ub);
   if (commit) c->ens_cur ^= 1;
+  if (commit && c->record_mom) { c->ens_mom_R = R; c->ens_mom_nb = c->ens_Nb; }
   return RBL_OK;
 }
 
 // upload F (R 6 N_bod) and slip (R n3 or NULL), clear the read-back block, evaluate the force model at q^n when it is on and
-// the caller wants its loads (model): *FT -> K^T f_phys of every replica (NULL otherwise)
-int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *slip, const double **FT, bool model = true)
+// the caller wants its loads (model): *FT -> K^T f_phys of every replica (NULL otherwise).  The flow model (include/rbl.h
+// section 8) goes the same way: one launch adds its term at q^n to every replica's slip.  *SL -> the slip the right-hand side
+// takes: the caller's, the term, their sum, or NULL for zero
+int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *slip, const double **FT, const double **SL,
+              bool model = true)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
   const size_t n3 = (size_t)3 * Nb * nbl, nb6 = (size_t)6 * Nb;
@@ -395,6 +403,9 @@ int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *
     if ((rc = ia_eval_batch(c, X, w.pos, w.lever, Nb, R, w.ia, &f, w.FT, nullptr, w.gerr))) return rc;
     *FT = w.FT;
   }
+  bool have_slip = slip != nullptr;
+  if (model && (rc = flow_add_batch(c, w.pos, Q, Nb, R, w.slip, &have_slip))) return rc;
+  *SL = have_slip ? w.slip : nullptr;
   return RBL_OK;
 }
 
@@ -430,6 +441,11 @@ int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const doubl
   if (rc) return rbl_fail(c, rc, "ensemble step: the one-kernel solver does not fit this device's LDS");
   if (!evolve) return RBL_OK;
   const int nbod = R * Nb;
+  if (c->record_mom) {                                   // RBL_OPT_RECORD_MOMENTS: lambda is the top of every replica's x, the lever
+    c->ens_mom_R = 0;                                    // arms those of the configuration solved at; valid once the step committed
+    if ((rc = rbl_dev_reserve(c, c->d_ens_mom, sizeof(double) * 9 * (size_t)nbod))) return rc;
+    flow_launch_moments(c, nullptr, Qs, ens_cfg(c), w.x, Nb, nbod, nsys, (double *)c->d_ens_mom.p);
+  }
   hipLaunchKernelGGL(k_ens_evolve, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, mixed ? 6L * Nb : nsys,
                      mixed ? 0L : n3, c->S.dt, mixed ? (const double *)w.U : (const double *)w.x, (const double *)ens_X(c, c->ens_cur),
                      (const double *)ens_Q(c, c->ens_cur), ens_X(c, c->ens_cur ^ 1), ens_Q(c, c->ens_cur ^ 1), w.rerr);
@@ -467,15 +483,16 @@ int ens_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, co
 {
   const bool mixed = prescribed != nullptr;
   EnsWork w;
-  const double *FT;
-  int rc = ens_work(c, max_iter, &w); if (rc) return rc;
+  const double *FT, *SL;
+  int rc;
+  if ((rc = ens_work(c, max_iter, &w))) return rc;
   if (mixed && (rc = copy_h2d(c, w.mask, prescribed, (size_t)c->ens_R * c->ens_Nb))) return rc;
-  if ((rc = ens_begin(c, w, F_body, slip, &FT, move))) return rc;
+  if ((rc = ens_begin(c, w, F_body, slip, &FT, &SL, move))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb;
   const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb;
   const long tot = (long)R * (n3 + nb6);
-  hipLaunchKernelGGL(k_ens_rhs_det, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, n3, nb6,
-                     slip ? (const double *)w.slip : nullptr, (const double *)w.F, FT, w.rhs);
+  hipLaunchKernelGGL(k_ens_rhs_det, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, n3, nb6, SL,
+                     (const double *)w.F, FT, w.rhs);
   if ((rc = ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, mixed, move))) return rc;
   std::vector<double> x;
   if (lambda) {                                          // the blob forces: the top of every replica's solution
@@ -505,8 +522,8 @@ int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, con
   const int64_t n3 = 3 * (int64_t)N;
   if (W) { if ((rc = copy_h2d(c, w.W, W, sizeof(double) * 3 * (size_t)n3 * R))) return rc; }
   else rbl_launch_normal_batched(c->stream, seed, 3 * n3, R, w.W);            // rand_vector (:730-741), one draw per replica
-  const double *FT;
-  if ((rc = ens_begin(c, w, F_body, slip, &FT))) return rc;
+  const double *FT, *SL;
+  if ((rc = ens_begin(c, w, F_body, slip, &FT, &SL))) return rc;
   const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
   // dense root of every replica: B M B (:667-669), lower Cholesky (:670-671), L W1 and L W2 (:672)
   const RblParams P = rbl_make_params(S.a, S.eta);
@@ -534,11 +551,11 @@ int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, con
   if (S.wall)
     hipLaunchKernelGGL(k_ens_rfd_rhs<true>, dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
                        (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
-                       slip ? (const double *)w.slip : nullptr, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
+                       SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
   else
     hipLaunchKernelGGL(k_ens_rfd_rhs<false>, dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
                        (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
-                       slip ? (const double *)w.slip : nullptr, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
+                       SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
   // saddle solve at q^{n+1/2}, update from q^n
   if ((rc = ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol, mixed))) return rc;
   std::vector<double> Ft;
@@ -616,7 +633,8 @@ int rbl_ensemble_step_deterministic(rbl_ctx *c, const double *F_body, const doub
                                     double *resid)
 {
   if (!c) return RBL_ERR_ARG;
-  int rc = ens_ready(c); if (rc) return rc;
+  int rc = ens_flow_check(c); if (rc) return rc;
+  if ((rc = ens_ready(c))) return rc;
   if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_deterministic: F_body is NULL");
   if ((rc = ens_check_solver(c, max_iter))) return rc;
   return ens_step_det(c, nullptr, F_body, slip, max_iter, rtol, true, nullptr, nullptr, nullptr, iters, resid);
@@ -626,7 +644,8 @@ int rbl_ensemble_step_brownian(rbl_ctx *c, const double *F_body, const double *s
                                int split_rand, double delta, int max_iter, double rtol, int *iters, double *resid)
 {
   if (!c) return RBL_ERR_ARG;
-  int rc = ens_ready(c); if (rc) return rc;
+  int rc = ens_flow_check(c); if (rc) return rc;
+  if ((rc = ens_ready(c))) return rc;
   const RblBodyState &S = c->S;
   if (!(S.kBT > 1e-10))                                // no Brownian terms (:967-970): the deterministic midpoint
     return rbl_ensemble_step_deterministic(c, F_body, slip, max_iter, rtol, iters, resid);
@@ -651,6 +670,7 @@ int rbl_ensemble_step_mixed(rbl_ctx *c, const uint8_t *prescribed, const double 
 {
   if (!c) return RBL_ERR_ARG;
   int rc = ens_mx_check(c, "ensemble_step_mixed", prescribed, body_in, max_iter, rtol); if (rc) return rc;
+  if ((rc = ens_flow_check(c))) return rc;
   if ((rc = ens_ready(c))) return rc;
   return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
 }
@@ -661,6 +681,7 @@ int rbl_ensemble_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, cons
 {
   if (!c) return RBL_ERR_ARG;
   int rc = ens_mx_check(c, "ensemble_step_brownian_mixed", prescribed, body_in, max_iter, rtol); if (rc) return rc;
+  if ((rc = ens_flow_check(c))) return rc;
   const RblBodyState &S = c->S;
   const bool brownian = S.kBT > 1e-10;                 // no Brownian terms: the deterministic mixed step (as rbl_step_brownian_mixed)
   if (brownian && (!(S.dt > 0.0) || !(delta > 0.0)))
@@ -696,5 +717,26 @@ int rbl_ensemble_interaction_forces(rbl_ctx *c, double *FT_body, double *energy)
       for (size_t i = 0; i < N; ++i) E += e[(size_t)r * N + i];
       energy[r] = E;
     }
+  return RBL_OK;
+}
+
+// the flow model's term at every replica's configuration (include/rbl.h section 8): R n3 doubles, zeros with both parts off
+int rbl_ensemble_flow_slip(rbl_ctx *c, double *out)
+{
+  if (!c) return RBL_ERR_ARG;
+  int rc = ens_flow_check(c); if (rc) return rc;
+  if ((rc = ens_ready(c))) return rc;
+  if (!out) return rbl_fail(c, RBL_ERR_ARG, "ensemble_flow_slip: out is NULL");
+  EnsWork w;
+  if ((rc = ens_work(c, 1, &w))) return rc;
+  const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
+  const size_t vb = sizeof(double) * 3 * (size_t)R * Nb * nbl;
+  const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
+  rbl_launch_body_geom(c->stream, X, Q, ens_cfg(c), nbl, (int64_t)R * Nb * nbl, w.lever, w.pos);
+  bool have = false;
+  if ((rc = flow_add_batch(c, w.pos, Q, Nb, R, w.slip, &have))) return rc;
+  if (!have) RBL_HIP(c, hipMemsetAsync(w.slip, 0, vb, c->stream));
+  if ((rc = copy_d2h(c, out, w.slip, vb))) return rc;
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
   return RBL_OK;
 }

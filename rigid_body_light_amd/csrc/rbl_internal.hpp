@@ -217,6 +217,18 @@ struct rbl_ctx {
   std::vector<double> ens_cfg_host;                 // the reference configuration d_ens holds
   // prescribed kinematics (rbl_mixed.hip; include/rbl.h section 7)
   RblDevBuf d_mx;                                   // rhs | x | invM slip | body_in | slip | U | F | model loads | mask
+  // imposed flow and active slip, recorded first moments (rbl_flow.hip; include/rbl.h section 8)
+  bool fl_flow_on = false, fl_slip_on = false;
+  double fl_u0[3] = {0, 0, 0}, fl_G[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // u_inf(r) = u0 + G r, G row-major
+  std::vector<double> fl_slip_body;                 // the body-frame pattern, 3 N_blb
+  std::vector<double> fl_scale;                     // its factor per body (empty: 1 for every body)
+  bool fl_dev_valid = false;                        // d_flow holds the pattern and the scales
+  int params_gen = 0, fl_slip_gen = 0;              // rbl_set_parameters calls so far; the count at rbl_set_body_slip (the pattern belongs to that structure)
+  RblDevBuf d_flow;                                 // pattern | scales
+  RblDevBuf d_flow_w;                               // host forms' staging: the term, or lambda | D
+  bool record_mom = false;                          // RBL_OPT_RECORD_MOMENTS
+  RblDevBuf d_mom, d_ens_mom;                       // D_b of the last recording step: 9 N_bod; R 9 N_bod
+  int mom_nb = 0, ens_mom_R = 0, ens_mom_nb = 0;    // shapes of what they hold (0: nothing recorded)
   // lanczos
   int lanczos_max_iter = 100;
   bool lanczos_out_norm = true;  // preconditioned root: final stopping test in the Euclidean norm of the increment (RBL_OPT_LANCZOS_EUCLID_NORM)

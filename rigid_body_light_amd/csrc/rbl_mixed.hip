@@ -581,14 +581,18 @@ int mx_solve_batch(rbl_ctx *c, const MxBuf &B, bool have_slip, int n_prescribed,
 }
 
 // the workspace with the host's mask (B.per entries per body), body_in and slip in place; model: the force model's loads at the
-// current configuration added to the free slots of body_in (the steps)
-int mx_upload(rbl_ctx *c, MxBuf &B, const uint8_t *prescribed, const double *body_in, const double *slip, bool model, int np)
+// current configuration added to the free slots of body_in and the flow model's term added to the slip (the steps).
+// *have_slip: B.slip holds something (the caller's slip, the term, or their sum)
+int mx_upload(rbl_ctx *c, MxBuf &B, const uint8_t *prescribed, const double *body_in, const double *slip, bool model, int np,
+              bool *have_slip)
 {
   const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
   int rc = mx_reserve(c, B); if (rc) return rc;
   if ((rc = copy_h2d(c, B.mask, prescribed, (size_t)B.per * (size_t)c->S.N_bod))) return rc;
   if ((rc = copy_h2d(c, B.body_in, body_in, sizeof(double) * nb6))) return rc;
   if (slip && (rc = copy_h2d(c, B.slip, slip, sizeof(double) * n3))) return rc;
+  *have_slip = slip != nullptr;
+  if (model && (rc = flow_add_to_step_slip(c, B.slip, have_slip))) return rc;   // imposed flow and body slip at q^n (section 8)
   if (model && c->ia_on && np < B.per * c->S.N_bod) {    // -K^T f_phys at q^n, free slots only (none free: nothing feels the model)
     RBL_HIP(c, hipMemsetAsync(B.model, 0, sizeof(double) * nb6, c->stream));
     if ((rc = ia_add_to_step_force(c, B.model))) return rc;
@@ -604,12 +608,16 @@ int mx_host(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double
 {
   int np = 0;
   int rc = mx_check(c, who, prescribed, body_in, max_iter, rtol, true, &np, per); if (rc) return rc;
+  if (model && (rc = flow_check(c, c->S.N_bod))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
+  if (model) flow_begin_step(c);
   const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
   MxBuf B;
   B.per = per;
-  if ((rc = mx_upload(c, B, prescribed, body_in, slip, model, np))) return rc;
-  if ((rc = mx_solve(c, B, slip != nullptr, np, max_iter, rtol, iters, resid))) return rc;
+  bool have_slip;
+  if ((rc = mx_upload(c, B, prescribed, body_in, slip, model, np, &have_slip))) return rc;
+  if ((rc = mx_solve(c, B, have_slip, np, max_iter, rtol, iters, resid))) return rc;
+  if (model && (rc = flow_record_moments(c, B.x))) return rc;          // the steps: RBL_OPT_RECORD_MOMENTS, lever arms of q^n
   if (lambda && (rc = copy_d2h(c, lambda, B.x, sizeof(double) * n3))) return rc;
   if (U && (rc = copy_d2h(c, U, B.U, sizeof(double) * nb6))) return rc;
   if (F && (rc = copy_d2h(c, F, B.F, sizeof(double) * nb6))) return rc;
@@ -847,20 +855,24 @@ int rbl_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, const double 
   int rc = mx_bd_check(c, "step_brownian_mixed", prescribed, body_in, max_iter, rtol, delta, &np); if (rc) return rc;
   if (!(c->S.kBT > 1e-10))                               // no Brownian terms: the deterministic step (as rbl_step_brownian, :967-970)
     return mx_step(c, "step_brownian_mixed", prescribed, body_in, slip, max_iter, rtol, F, iters, resid);
+  if ((rc = flow_check(c, c->S.N_bod))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
+  flow_begin_step(c);
   const size_t nb6 = 6 * (size_t)c->S.N_bod;
   MxBuf B;
   double *dW;
-  if ((rc = mx_upload(c, B, prescribed, body_in, slip, true, np))) return rc;      // the force model at q^n, free bodies only
+  bool have_slip;
+  if ((rc = mx_upload(c, B, prescribed, body_in, slip, true, np, &have_slip))) return rc;   // the models at q^n; forces: free bodies only
   if ((rc = step_upload_W(c, W, &dW))) return rc;
   return step_midpoint(
       c,
       [&](double *Xh, double *Qh) {                       // s takes the slip's place in the solve's workspace: it never leaves the device
-        return rhs_and_midpoint_core(c, prescribed, B.mask, B.body_in, slip ? B.slip : nullptr, dW, seed, method, split_rand, delta, B.slip,
+        return rhs_and_midpoint_core(c, prescribed, B.mask, B.body_in, have_slip ? B.slip : nullptr, dW, seed, method, split_rand, delta, B.slip,
                                      Xh, Qh);
       },
       [&](double *U) {
         int r = mx_solve(c, B, true, np, max_iter, rtol, iters, resid);
+        if (!r) r = flow_record_moments(c, B.x);                          // RBL_OPT_RECORD_MOMENTS: lever arms of q^{n+1/2}
         if (!r) r = copy_d2h(c, U, B.U, sizeof(double) * nb6);
         if (!r && F) r = copy_d2h(c, F, B.F, sizeof(double) * nb6);
         return r ? r : finish_and_check(c);

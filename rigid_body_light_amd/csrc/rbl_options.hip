@@ -93,6 +93,8 @@ const OptRow kOptions[] = {
      [](rbl_ctx *c, int64_t v) { c->poison_ws = v != 0; }},
     {RBL_OPT_FUSED_KRYLOV, "fused_krylov", 0, 1, 1, [](const rbl_ctx *c) -> int64_t { return c->fused_krylov; },
      [](rbl_ctx *c, int64_t v) { c->fused_krylov = v != 0; }},
+    {RBL_OPT_RECORD_MOMENTS, "record_moments", 0, 1, 0, [](const rbl_ctx *c) -> int64_t { return c->record_mom; },
+     [](rbl_ctx *c, int64_t v) { c->record_mom = v != 0; c->mom_nb = 0; c->ens_mom_R = 0; }},
 };
 
 const OptRow *find_option(int key)

@@ -40,13 +40,17 @@ int rbl_step_deterministic(rbl_ctx *c, const double *F_body, const double *slip,
                            int warm_start, int *iters, double *resid)
 {
   int rc = need_K(c); if (rc) return rc;
+  if ((rc = flow_check(c, c->S.N_bod))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "step_deterministic: F_body is NULL");
+  flow_begin_step(c);
   const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb, nb6 = (int64_t)6 * c->S.N_bod;
   double *rhs, *x, *dslip, *dforce;
   if ((rc = step_buffers(c, n3, nb6, &rhs, &x, &dslip, &dforce))) return rc;
-  if (slip) { if ((rc = copy_h2d(c, rhs, slip, sizeof(double) * (size_t)n3))) return rc; }
-  else RBL_HIP(c, hipMemsetAsync(rhs, 0, sizeof(double) * (size_t)n3, c->stream));
+  bool have_slip = slip != nullptr;
+  if (slip && (rc = copy_h2d(c, rhs, slip, sizeof(double) * (size_t)n3))) return rc;
+  if ((rc = flow_add_to_step_slip(c, rhs, &have_slip))) return rc;   // imposed flow and body slip at q^n (include/rbl.h section 8)
+  if (!have_slip) RBL_HIP(c, hipMemsetAsync(rhs, 0, sizeof(double) * (size_t)n3, c->stream));
   if ((rc = copy_h2d(c, dforce, F_body, sizeof(double) * (size_t)nb6))) return rc;
   if ((rc = ia_add_to_step_force(c, dforce))) return rc;             // the force model at q^n (include/rbl.h section 4)
   rbl_launch_axpby(c->stream, nb6, -1.0, dforce, 0.0, nullptr, rhs + n3);
@@ -66,6 +70,7 @@ int rbl_step_deterministic(rbl_ctx *c, const double *F_body, const double *slip,
   c->step_hist_head = (c->step_hist_head + 2) % 3;                     // the oldest slot becomes the newest
   RBL_HIP(c, hipMemcpyAsync(slot(0), x, sizeof(double) * (size_t)nsys, hipMemcpyDeviceToDevice, c->stream));
   if (c->step_hist_n < 3) ++c->step_hist_n;
+  if ((rc = flow_record_moments(c, x))) return rc;                     // RBL_OPT_RECORD_MOMENTS: lever arms of q^n
   std::vector<double> U((size_t)nb6);
   if ((rc = copy_d2h(c, U.data(), x + n3, sizeof(double) * (size_t)nb6))) return rc;
   RBL_HIP(c, hipStreamSynchronize(c->stream));
@@ -108,13 +113,17 @@ int rbl_step_brownian(rbl_ctx *c, const double *F_body, const double *slip, cons
                       int split_rand, double delta, int max_iter, double rtol, int *iters, double *resid)
 {
   int rc = need_K(c); if (rc) return rc;
+  if ((rc = flow_check(c, c->S.N_bod))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "step_brownian: F_body is NULL");
+  flow_begin_step(c);
   const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb, nb6 = (int64_t)6 * c->S.N_bod;
   double *rhs, *x, *dslip, *dforce, *dW;
   if ((rc = step_buffers(c, n3, nb6, &rhs, &x, &dslip, &dforce))) return rc;
-  if (slip) { if ((rc = copy_h2d(c, dslip, slip, sizeof(double) * (size_t)n3))) return rc; }
-  else RBL_HIP(c, hipMemsetAsync(dslip, 0, sizeof(double) * (size_t)n3, c->stream));
+  bool have_slip = slip != nullptr;
+  if (slip && (rc = copy_h2d(c, dslip, slip, sizeof(double) * (size_t)n3))) return rc;
+  if ((rc = flow_add_to_step_slip(c, dslip, &have_slip))) return rc;   // imposed flow and body slip at q^n, where RHS_and_Midpoint takes its Slip
+  if (!have_slip) RBL_HIP(c, hipMemsetAsync(dslip, 0, sizeof(double) * (size_t)n3, c->stream));
   if ((rc = copy_h2d(c, dforce, F_body, sizeof(double) * (size_t)nb6))) return rc;
   if ((rc = ia_add_to_step_force(c, dforce))) return rc;             // the force model at q^n, where RHS_and_Midpoint takes its Force
   if ((rc = step_upload_W(c, W, &dW))) return rc;
@@ -123,6 +132,7 @@ int rbl_step_brownian(rbl_ctx *c, const double *F_body, const double *slip, cons
       [&](double *Xh, double *Qh) { return rbl_RHS_and_Midpoint_dev(c, dslip, dforce, dW, seed, method, split_rand, delta, rhs, Xh, Qh); },
       [&](double *U) {
         int r = rbl_gmres_saddle_dev(c, rhs, max_iter, rtol, x, 0, iters, resid);
+        if (!r) r = flow_record_moments(c, x);                          // RBL_OPT_RECORD_MOMENTS: lever arms of q^{n+1/2}
         if (!r) r = copy_d2h(c, U, x + n3, sizeof(double) * (size_t)nb6);
         if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = RBL_ERR_HIP;
         return r;

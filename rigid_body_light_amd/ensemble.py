@@ -70,20 +70,22 @@ class Ensemble:
             return F
         _fail("F must have shape (%d,) or (%d, %d); got %s" % (per, self.R, per, F.shape))
 
-    def step_deterministic(self, F, max_iter=50, rtol=1e-8):
-        """one deterministic step of every replica -> (iterations (R,), residual estimates (R,))"""
-        return self.ctx.ensemble_step_deterministic(self._forces(F), max_iter=max_iter, rtol=rtol)
+    def step_deterministic(self, F, max_iter=50, rtol=1e-8, slip=None):
+        """one deterministic step of every replica -> (iterations (R,), residual estimates (R,)).  slip: (n3,) or (R, n3)"""
+        return self.ctx.ensemble_step_deterministic(self._forces(F), max_iter=max_iter, rtol=rtol, slip=self._slip(slip))
 
-    def step_brownian(self, F, W=None, seed=0, split_rand=True, delta=1e-4, max_iter=50, rtol=1e-8):
+    def step_brownian(self, F, W=None, seed=0, split_rand=True, delta=1e-4, max_iter=50, rtol=1e-8, slip=None):
         """one stochastic midpoint step of every replica -> (iterations (R,), residual estimates (R,)).  W: (R, 9 N_bod N_blb)
-        standard normals [W1 | W2 | W_rfd] per replica, or None to draw them from `seed` (replica r from its own counters)"""
+        standard normals [W1 | W2 | W_rfd] per replica, or None to draw them from `seed` (replica r from its own counters);
+        slip: (n3,) or (R, n3)"""
         F = self._forces(F)
         if W is not None:
             W = np.asarray(W, dtype=np.float64)
             n = 9 * self.N_bodies * self.blobs_per_body
             if W.shape != (self.R, n):
                 _fail("W must have shape (%d, %d); got %s" % (self.R, n, W.shape))
-        return self.ctx.ensemble_step_brownian(F, W=W, seed=seed, split_rand=split_rand, delta=delta, max_iter=max_iter, rtol=rtol)
+        return self.ctx.ensemble_step_brownian(F, W=W, seed=seed, split_rand=split_rand, delta=delta, max_iter=max_iter, rtol=rtol,
+                                               slip=self._slip(slip))
 
     # ------------------------------------------------------------------ prescribed bodies (include/rbl.h sections 5 and 7)
     def _prescribed_mask(self, prescribed):
@@ -177,6 +179,41 @@ class Ensemble:
     def interaction_energy(self):
         """total potential energy of every replica, (R,)"""
         return self.ctx.ensemble_interaction_forces()[1]
+
+    # ------------------------------------------------------------------ imposed flow, active slip, stresslets (include/rbl.h section 8)
+    def set_background_flow(self, u0=None, G=None, on=True):
+        """the background flow of RigidBody.set_background_flow, one for all replicas: every step adds -(u0 + G r) at the blobs of
+        q^n to its slip, in one launch over all replicas"""
+        u0 = np.zeros(3) if u0 is None else np.asarray(u0, dtype=np.float64)
+        G = np.zeros((3, 3)) if G is None else np.asarray(G, dtype=np.float64)
+        if u0.shape != (3,):
+            _fail("u0 must have shape (3,); got %s" % (u0.shape,))
+        if G.shape != (3, 3):
+            _fail("G must have shape (3, 3); got %s" % (G.shape,))
+        self.ctx.set_background_flow(u0, G, on=on)
+
+    def set_body_slip(self, slip_body, scale=None, on=True):
+        """the body-frame slip pattern of RigidBody.set_body_slip; scale (N_bod,): scale[b] serves body b of every replica"""
+        sb = np.asarray(slip_body, dtype=np.float64)
+        if sb.size != 3 * self.blobs_per_body or not (sb.ndim == 1 or (sb.ndim == 2 and sb.shape[1] == 3)):
+            _fail("slip_body must have shape (%d, 3) or (%d,); got %s" % (self.blobs_per_body, 3 * self.blobs_per_body, sb.shape))
+        if scale is not None:
+            scale = np.asarray(scale, dtype=np.float64)
+            if scale.shape != (self.N_bodies,):
+                _fail("scale must have shape (%d,); got %s" % (self.N_bodies, scale.shape))
+        self.ctx.set_body_slip(sb, scale, on=on)
+
+    def flow_slip(self):
+        """the flow model's term at every replica's configuration, (R, n3)"""
+        return self.ctx.ensemble_flow_slip()
+
+    def record_moments(self, on=True):
+        """every step from now on leaves the first moments of its lambda on the device (one launch over R N_bod bodies)"""
+        self.ctx.record_moments(on)
+
+    def step_moments(self):
+        """first moments D_b = sum (r_i - X_b) lambda_i^T recorded by the last step, (R, N_bod, 3, 3)"""
+        return self.ctx.ensemble_step_moments()
 
     def close(self):
         self.ctx.close()

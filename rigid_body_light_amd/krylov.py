@@ -39,11 +39,13 @@ class DeterministicStepper:
         if self.warm_start:
             self._x_hist = [x] + self._x_hist[:2]
 
-    def solve(self, F_body, iters=20, rtol=None):
-        """Solve the saddle system for rhs = [0 ; -F_body]; returns (lambda, U, iterations, residual)."""
+    def solve(self, F_body, iters=20, rtol=None, slip=None):
+        """Solve the saddle system for rhs = [slip (None: 0) ; -F_body]; returns (lambda, U, iterations, residual)."""
         Fb = torch.as_tensor(F_body, dtype=torch.float64, device=self.dev).reshape(-1)
         x0 = self.initial_guess(rtol)
         b = torch.zeros(self.size, dtype=torch.float64, device=self.dev)
+        if slip is not None:
+            b[: self.n3] = slip
         b[self.n3:] = -Fb
         x = x0 if x0 is not None else torch.empty_like(b)
         m, resid = self.ctx.gmres_saddle(b.data_ptr(), iters, rtol, x.data_ptr(), use_x0=x0 is not None)
@@ -62,8 +64,20 @@ class DeterministicStepper:
         self.ctx.sync_check()                     # a neighbour-list overflow fails the step, as in the C steps
         return Fb - FT
 
+    def slip_at_qn(self, slip=None):
+        """slip plus the context's flow model (include/rbl.h section 8) at the current configuration q^n, slip + t in that
+        order -- what the C steps add.  slip itself (None stays None) while both parts of the model are off."""
+        sl = None if slip is None else torch.as_tensor(slip, dtype=torch.float64, device=self.dev).reshape(-1)
+        if not self.ctx.flow_model_on():
+            return sl
+        t = torch.empty(self.n3, dtype=torch.float64, device=self.dev)
+        self.ctx.flow_slip_dev(t.data_ptr())
+        return t if sl is None else sl + t
+
     def step(self, F_body, iters=20, rtol=None):
-        lam, U, m, resid = self.solve(self.forces_at_qn(F_body), iters, rtol)
+        sl = self.slip_at_qn()                    # None while the flow model is off: solve() is then called as it always was
+        F = self.forces_at_qn(F_body)
+        lam, U, m, resid = self.solve(F, iters, rtol) if sl is None else self.solve(F, iters, rtol, slip=sl)
         self.ctx.evolve(U.cpu().numpy())          # O(N_bod) host update, then K/positions rebuilt on the GPU
         self.ctx.sync_check()
         return m, resid
@@ -117,7 +131,7 @@ class BrownianStepper(DeterministicStepper):
     def step(self, F_body, slip=None, W=None, seed=0, method=1, iters=20, rtol=None, split_rand=True,
              delta=1.0e-4):
         Xn, Qn = self.ctx.get_config(self.nb)
-        rhs, Xh, Qh = self.rhs_and_midpoint(self.forces_at_qn(F_body), slip, W, seed, method, split_rand, delta)
+        rhs, Xh, Qh = self.rhs_and_midpoint(self.forces_at_qn(F_body), self.slip_at_qn(slip), W, seed, method, split_rand, delta)
         self.ctx.set_config(Xh, Qh)                      # operators and preconditioner at the predictor configuration
         x, m, resid = self.saddle_solve(rhs, iters, rtol)
         U = x[self.n3:].cpu().numpy()

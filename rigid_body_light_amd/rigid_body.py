@@ -13,7 +13,9 @@ Beyond the reference surface (its C++ has these, its Python does not): `solve_sa
 `dense_mobility`, `velocity_field` (the flow at arbitrary points), prescribed kinematics (`solve_mixed`, `step_mixed`,
 `body_resistance_matrix`: bodies that are held or driven, and the loads that takes; `solve_mixed_dof`, `step_mixed_dof`: the same for
 single velocity components; `solve_mixed_multi`, `solve_mixed_dof_multi`: many right-hand sides under one mask in lock step; `step_brownian_mixed`,
-`RHS_and_Midpoint_mixed`: the same among Brownian bodies), and a force model the reference does not have (`set_interactions`, `interaction_forces`).
+`RHS_and_Midpoint_mixed`: the same among Brownian bodies), a force model the reference does not have (`set_interactions`, `interaction_forces`),
+and an imposed flow, a body-frame slip and stresslets (`set_background_flow`, `set_body_slip`, `flow_slip`, `first_moments`, `stresslets`,
+`record_moments`, `step_moments`).
 """
 import numpy as np
 
@@ -39,6 +41,7 @@ class RigidBody:
         self.precision = self.cb.precision
         self.blobs_per_body = template.size // 3
         self._a = a                          # (the force model's default cutoff)
+        self._wall = bool(wall_PC)
         self.cb.setParameters(a, dt, _KBT_IN_WRAPPER, eta, template.reshape(self.blobs_per_body, 3))
         self.cb.setWallPC(bool(wall_PC))
         self.cb.setBlkPC(bool(block_PC))
@@ -223,12 +226,13 @@ class RigidBody:
     def interaction_energy(self):
         return self.cb.interaction_energy()
 
-    def velocity_field(self, points, blob_forces, positions=None):
+    def velocity_field(self, points, blob_forces, positions=None, with_flow=False):
         """Fluid velocity at arbitrary points from blob forces (include/rbl.h section 6): the velocity `apply_M` would give an
         extra force-free blob of radius a at each point -- e.g. the flow around the bodies after `solve_saddle`, whose first
         3 * total_blobs entries are the blob forces.  points: (P, 3) or flat 3P; blob_forces: flat or (N, 3); positions: the
         blobs' positions (default: this object's blobs at the current configuration, then blob_forces must have 3 * total_blobs
-        entries).  With the wall, points at z <= 0 get u = 0.  Returns (P, 3) or flat, following the shape of `points`."""
+        entries).  With the wall, points at z <= 0 get u = 0.  with_flow=True adds the background flow u0 + G p of set_background_flow
+        (while it is on; with the wall only at points above it), on the host.  Returns (P, 3) or flat, following the shape of `points`."""
         pts = np.asarray(points, dtype=np.float64)
         lam = np.asarray(blob_forces, dtype=np.float64)
         if not (pts.ndim == 2 and pts.shape[1] == 3) and not (pts.ndim == 1 and pts.size % 3 == 0):
@@ -245,7 +249,78 @@ class RigidBody:
                 raise ValueError(f"velocity_field: positions and blob_forces must be of the same size. Got {r.shape} and {lam.shape}")
             r = r.reshape(-1)
         u = self.cb.velocity_field(pts.reshape(-1), lam.reshape(-1), r)
+        if with_flow:
+            m = self.flow_model()
+            if m["flow_on"]:
+                p = pts.reshape(-1, 3)
+                uinf = m["u0"] + p @ m["G"].T
+                if self._wall:
+                    uinf[p[:, 2] <= 0.0] = 0.0
+                u = u + uinf.reshape(-1)
         return u.reshape(pts.shape)
+
+    # ------------------------------------------------------------------ imposed flow, active slip, stresslets (include/rbl.h section 8)
+    def set_background_flow(self, u0=None, G=None, on=True):
+        """Background flow u_inf(r) = u0 + G r, G[i, j] = d u_i / d x_j (None: zeros).  Every step entry point (step_deterministic,
+        step_brownian, step_mixed, step_mixed_dof, step_brownian_mixed) then adds -u_inf at the blobs of q^n to its slip; the bare
+        solves do not: pass them slip=flow_slip().  With wall_PC only u = (G[0, 2] z, G[1, 2] z, 0) is accepted -- at the use, not
+        here.  on=False switches the flow off."""
+        u0 = np.zeros(3) if u0 is None else np.asarray(u0, dtype=np.float64)
+        G = np.zeros((3, 3)) if G is None else np.asarray(G, dtype=np.float64)
+        if u0.shape != (3,):
+            raise ValueError(f"set_background_flow: u0 must have shape (3,). Got shape: {u0.shape}")
+        if G.shape != (3, 3):
+            raise ValueError(f"set_background_flow: G must have shape (3, 3). Got shape: {G.shape}")
+        self.cb.set_background_flow(u0, np.ascontiguousarray(G).reshape(-1), bool(on))
+
+    def set_body_slip(self, slip_body, scale=None, on=True):
+        """Active slip carried by the bodies: slip_body (blobs_per_body, 3) or flat, a pattern in the BODY frame in the units and
+        sign of the `slip` argument; scale: a factor per body, (N_bodies,) (None: 1; 0: a passive body).  The steps add
+        scale_b R(q_b) slip_body to their slip at q^n.  on=False switches it off."""
+        sb = np.asarray(slip_body, dtype=np.float64)
+        if sb.size != 3 * self.blobs_per_body or not (sb.ndim == 1 or (sb.ndim == 2 and sb.shape[1] == 3)):
+            raise ValueError(f"set_body_slip: slip_body must have shape ({self.blobs_per_body}, 3) or ({3 * self.blobs_per_body},). Got shape: {sb.shape}")
+        sc = None
+        if scale is not None:
+            sc = np.asarray(scale, dtype=np.float64)
+            if sc.shape != (self.N_bodies,):
+                raise ValueError(f"set_body_slip: scale must have shape (N_bodies,) = ({self.N_bodies},). Got shape: {sc.shape}")
+            sc = np.ascontiguousarray(sc)
+        self.cb.set_body_slip(np.ascontiguousarray(sb).reshape(-1), sc, bool(on))
+
+    def flow_model(self):
+        """{u0 (3,), G (3, 3), flow_on, body_slip_on} of the context's flow model"""
+        v, f, b = self.cb.flow_model()
+        return {"u0": np.array(v[:3]), "G": np.array(v[3:]).reshape(3, 3), "flow_on": bool(f), "body_slip_on": bool(b)}
+
+    def flow_slip(self):
+        """The flow model's term at the current configuration, t_i = scale_b R(q_b) slip_body_i - (u0 + G r_i): what the steps add
+        to their slip, and what a bare solve takes as slip=.  Zeros with both parts off.  Shaped like the blob positions."""
+        return self._like_X(self.cb.flow_slip())
+
+    def first_moments(self, lam):
+        """D_b = sum_i (r_i - X_b) lambda_i^T over the blobs of each body -> (N_bodies, 3, 3).  lam: any blob vector -- the lambda
+        of a solve, or the model's blob forces for the interparticle contribution."""
+        lam = np.asarray(lam, dtype=np.float64)
+        if lam.size != 3 * self.total_blobs:
+            raise ValueError(f"first_moments: lam must have total size 3*N_blobs = {3 * self.total_blobs}. Got shape: {lam.shape}")
+        return self.cb.first_moments(np.ascontiguousarray(lam).reshape(-1)).reshape(self.N_bodies, 3, 3)
+
+    def stresslets(self, lam):
+        """The symmetric traceless part of first_moments(lam) -> (N_bodies, 3, 3)"""
+        D = self.first_moments(lam)
+        S = 0.5 * (D + D.transpose(0, 2, 1))
+        return S - np.trace(S, axis1=1, axis2=2)[:, None, None] * np.eye(3) / 3.0
+
+    def record_moments(self, on=True):
+        """Every step from now on also leaves the first moments of its solve's lambda on the device (one small launch): read them
+        with step_moments().  Switching discards what was recorded."""
+        self.cb.set_option("record_moments", int(bool(on)))
+
+    def step_moments(self):
+        """first moments recorded by the last step, (N_bodies, 3, 3), with the lever arms of the configuration it solved at (q^n
+        for the deterministic steps, q^{n+1/2} for the midpoint steps).  The Brownian drift's share of the stress is not in it."""
+        return self.cb.step_moments().reshape(self.N_bodies, 3, 3)
 
     # ------------------------------------------------------------------ prescribed kinematics (include/rbl.h section 7)
     def _prescribed_mask(self, prescribed):
