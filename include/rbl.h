@@ -640,6 +640,95 @@ int rbl_ensemble_step_brownian_mixed(rbl_ctx *ctx, const uint8_t *prescribed, co
                                      const double *W, uint64_t seed, int split_rand, double delta, int max_iter, double rtol,
                                      double *F, int *iters, double *resid);
 
+/* A run: n_steps ensemble steps in ONE call.  The inputs are uploaded once, every step's verdict and commit are taken per
+ * replica on the device, the records accumulate there, and the host reads back once at the end (plus the optional status polls
+ * of check_every).  The one-step calls above are unchanged; a run enqueues their very launch sequence once per step, followed by
+ * two small launches (the verdict of every replica, then the commit), and flips the two configuration buffers on the host
+ * without a synchronisation.  The four step families are chosen by the options: brownian 0/1, and either F_body (all bodies
+ * free) or prescribed with body_in (held or driven bodies, as rbl_ensemble_step_[brownian_]mixed).  Everything in the options is
+ * constant over the run; the force model (section 4) and the flow model (section 8) enter every step at that step's q^n.
+ *
+ * Noise: drawn on the device.  Step n of the run (n = 0, 1, ... counts the run's steps, rejected ones included) draws what
+ * rbl_ensemble_step_brownian(W = NULL, seed + n) draws; injected noise is not offered.  kBT <= 1e-10: the deterministic step.
+ *
+ * on_error
+ *   RBL_RUN_STOP (0, the default): the policy of the one-step calls.  At the first step s in which any replica's error word or
+ *     the batch word is set no replica commits, and a sticky device flag makes every later step of the run commit nothing: the
+ *     final configuration is bitwise what a loop of one-step calls leaves when it fails at step s.  The call returns that step's
+ *     status code, rbl_last_error names the step and the first failing replica, and the outputs are still filled.
+ *   RBL_RUN_REJECT (1): a replica whose error word is set at step n keeps q^n, its rejected count goes up, and it tries again at
+ *     step n + 1 with that step's fresh noise; the others commit.  Here the NEW configuration is validated before it commits (a
+ *     replica that landed below the wall would otherwise be accepted and fail every later step): every component of X and Q
+ *     finite and, with the wall, every blob of q^{n+1} at z >= 0, the height computed with the arithmetic the next step's
+ *     kernels use, so the verdict is the one they would reach.  A replica that fails validation is rejected like any other.  A
+ *     non-SPD mobility of one replica is that replica's rejection (in a run the batched Cholesky reports per matrix).  What
+ *     cannot be pinned to a replica -- a neighbour-list overflow of the force model -- stops the run as under RBL_RUN_STOP.
+ *     A rejected Brownian move is REDRAWN.  That is the customary treatment in rigid-multiblob codes, not an unbiased one: the
+ *     accepted moves are conditioned on staying valid.  rejected[] is returned so that the caller can see how much it matters.
+ *     Under RBL_RUN_REJECT the replicas no longer share a clock: replica r's physical time is dt accepted[r].
+ * STOP does not validate the new configuration, by design: it reproduces the loop, which meets a bad q^{n+1} one step later.
+ *
+ * stride > 0 records n_frames = n_steps / stride frames: frame k is the committed configuration after step (k + 1) stride - 1,
+ * X[R 3 N_bod], Q[R 4 N_bod], accepted_at[R] (the replica's accepted count then) and, for runs with prescribed bodies, that
+ * step's F[R 6 N_bod] (a replica rejected in that very step: its last accepted F, zeros before any).  The frames are written on
+ * the device and downloaded once.  Frames after a stop repeat the stopped configuration where their steps were still enqueued;
+ * where a status poll ended the enqueuing first, the caller's arrays are left as they were from there on.  Stresslet frames are not recorded, and rbl_ensemble_step_moments is RBL_ERR_STATE after a
+ * run until a one-step call has recorded again.
+ *
+ * check_every = k > 0: after every k steps the host reads the status block (a few bytes, one stream drain) and stops enqueuing
+ * once the run has stopped; 0: never before the end -- a stopped run then still enqueues its remaining steps, which meet the
+ * flagged configuration again, set flags and commit nothing.  RBL_RUN_CHECK_DEFAULT is 64: a drain every 64 steps is a fraction
+ * of a percent of their time, and it bounds what a stopped run wastes to 64 steps; results do not depend on it.
+ *
+ * Outputs (any per-replica pointer may be NULL): accepted[R], rejected[R]; first_flags[R], the error word (internal bits) of the
+ * replica's first rejected step, and first_status[R], the same as an RBL_ERR_* code (0: never rejected); iters_sum[R] and
+ * resid_max[R] over the replica's accepted steps; F_sum[R 6 N_bod] (runs with prescribed bodies) the sum over the replica's
+ * ACCEPTED steps of the load F the one-step call returns, added in step order by one thread per entry (bitwise reproducible): its
+ * mean is the microrheology measurement.  steps_done: steps before the run stopped (n_steps if it never did); stopped_at: the
+ * step that stopped it or -1; stop_replica: its first failing replica, -1 for a batch-level failure or none.  Under
+ * RBL_RUN_STOP a replica whose word is set at the stopping step counts one rejection; nothing counts after a stop.
+ *
+ * Refused before the device is touched, rbl_last_error naming the argument -- RBL_ERR_ARG: NULL structs or a wrong size,
+ * n_steps < 1, stride < 0, check_every < 0, on_error outside {0, 1}, both or neither of F_body and (prescribed, body_in),
+ * entries of prescribed above 1, max_iter < 1, rtol < 0, dt or delta not positive for a Brownian run, frame arrays NULL while
+ * stride > 0 and n_frames > 0, a context with a communicator; RBL_ERR_SIZE: the solver's size refusals; RBL_ERR_STATE: no
+ * ensemble configuration.  After a run rbl_ensemble_get_config and the one-step calls go on from its final configuration. */
+#define RBL_RUN_STOP 0
+#define RBL_RUN_REJECT 1
+#define RBL_RUN_CHECK_DEFAULT 64
+typedef struct rbl_run_opts {
+  int64_t size;               /* sizeof(rbl_run_opts) */
+  int32_t n_steps;            /* >= 1 */
+  int32_t brownian;           /* 0: deterministic steps, else the stochastic midpoint step */
+  int32_t split_rand;         /* as rbl_ensemble_step_brownian */
+  int32_t max_iter;           /* >= 1 */
+  int32_t stride;             /* >= 0; 0 records no frames */
+  int32_t on_error;           /* RBL_RUN_STOP or RBL_RUN_REJECT */
+  int32_t check_every;        /* >= 0 */
+  int32_t reserved;           /* 0 */
+  uint64_t seed;              /* step n draws from seed + n */
+  double delta;               /* RFD step, as rbl_ensemble_step_brownian */
+  double rtol;                /* >= 0 */
+  const double *F_body;       /* [R 6 N_bod], or NULL with prescribed and body_in */
+  const uint8_t *prescribed;  /* [R N_bod] 0/1, or NULL with F_body */
+  const double *body_in;      /* [R 6 N_bod] */
+  const double *slip;         /* [R n3] or NULL */
+} rbl_run_opts;
+typedef struct rbl_run_out {
+  int64_t size;               /* sizeof(rbl_run_out) */
+  int32_t *accepted, *rejected;          /* [R] */
+  uint32_t *first_flags;                 /* [R] */
+  int32_t *first_status;                 /* [R] */
+  int64_t *iters_sum;                    /* [R] */
+  double *resid_max;                     /* [R] */
+  double *F_sum;                         /* [R 6 N_bod], runs with prescribed bodies */
+  double *frame_X, *frame_Q;             /* [n_frames R 3 N_bod], [n_frames R 4 N_bod] */
+  int32_t *frame_accepted_at;            /* [n_frames R] */
+  double *frame_F;                       /* [n_frames R 6 N_bod], runs with prescribed bodies */
+  int32_t steps_done, stopped_at, stop_replica, reserved;   /* written by the call */
+} rbl_run_out;
+int rbl_ensemble_run(rbl_ctx *ctx, const rbl_run_opts *opts, rbl_run_out *out);
+
 /* ===================================================================== */
 /* 6. Fluid velocity at arbitrary points (rigid_body_light_amd/csrc/rbl_field.hip) */
 /* ===================================================================== */

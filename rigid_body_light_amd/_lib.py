@@ -97,6 +97,7 @@ def lib():
         L.rbl_ensemble_solve_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, vp, vp]
         L.rbl_ensemble_step_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp]
         L.rbl_ensemble_step_brownian_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, dbl, C.c_int, dbl, vp, vp, vp]
+        L.rbl_ensemble_run.argtypes = [vp, C.POINTER(RunOpts), C.POINTER(RunOut)]
         L.rbl_velocity_field.argtypes = [vp, vp, i64, vp, vp, i64, vp]
         L.rbl_velocity_field_dev.argtypes = [vp, vp, i64, vp, vp, i64, vp]
         L.rbl_velocity_field_info.argtypes = [vp, i64, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
@@ -124,6 +125,38 @@ def lib():
 
 class RblError(RuntimeError):
     pass
+
+
+class RunOpts(C.Structure):
+    """rbl_run_opts (include/rbl.h section 5)"""
+    _fields_ = [("size", C.c_int64), ("n_steps", C.c_int32), ("brownian", C.c_int32), ("split_rand", C.c_int32),
+                ("max_iter", C.c_int32), ("stride", C.c_int32), ("on_error", C.c_int32), ("check_every", C.c_int32),
+                ("reserved", C.c_int32), ("seed", C.c_uint64), ("delta", C.c_double), ("rtol", C.c_double),
+                ("F_body", C.c_void_p), ("prescribed", C.c_void_p), ("body_in", C.c_void_p), ("slip", C.c_void_p)]
+
+
+class RunOut(C.Structure):
+    """rbl_run_out (include/rbl.h section 5)"""
+    _fields_ = [("size", C.c_int64), ("accepted", C.c_void_p), ("rejected", C.c_void_p), ("first_flags", C.c_void_p),
+                ("first_status", C.c_void_p), ("iters_sum", C.c_void_p), ("resid_max", C.c_void_p), ("F_sum", C.c_void_p),
+                ("frame_X", C.c_void_p), ("frame_Q", C.c_void_p), ("frame_accepted_at", C.c_void_p), ("frame_F", C.c_void_p),
+                ("steps_done", C.c_int32), ("stopped_at", C.c_int32), ("stop_replica", C.c_int32), ("reserved", C.c_int32)]
+
+
+RUN_STOP, RUN_REJECT, RUN_CHECK_DEFAULT = 0, 1, 64
+
+
+class RunResult:
+    """what a run of ensemble steps leaves (DeviceContext.ensemble_run, Ensemble.run): per replica accepted, rejected,
+    first_flags / first_status (the error word / the status code of the first rejected step, 0: none), iters_sum and resid_max over
+    the accepted steps; F_sum and F_mean (R, 6 N_bod) for runs with prescribed bodies (F_mean = F_sum / accepted, NaN where nothing
+    was accepted), else None; steps_done, stopped_at (-1: never), stop_replica; the frames X (n_frames, R, N_bod, 3), Q (n_frames,
+    R, N_bod, 4), accepted_at (n_frames, R) and, with prescribed bodies, F (n_frames, R, 6 N_bod); status and error: the call's
+    status code and message (0, None for a run that did not stop)"""
+
+    def __repr__(self):
+        return "RunResult(steps_done=%d, stopped_at=%d, accepted=%d..%d, rejected=%d)" % (
+            self.steps_done, self.stopped_at, int(self.accepted.min()), int(self.accepted.max()), int(self.rejected.sum()))
 
 
 class DeviceContext:
@@ -537,6 +570,70 @@ class DeviceContext:
                                                           float(delta), int(max_iter), float(rtol or 0.0), F.ctypes.data,
                                                           it.ctypes.data, res.ctypes.data))
         return F, it, res
+
+    def ensemble_run(self, n_steps, F_body=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error=RUN_STOP,
+                     check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8):
+        """n_steps steps of every replica in one call (rbl_ensemble_run): the inputs are uploaded once, the verdict, the commit
+        and the records are kept per replica on the device -> (RunResult, status): the result is filled for a stopped run too,
+        whose status and message it carries; nothing is raised here for such a run (Ensemble.run does).  F_body (6 N_bod,) or
+        (R, 6 N_bod) for free bodies, or prescribed (N_bod,) / (R, N_bod) with body_in; on_error: RUN_STOP or RUN_REJECT"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        if R == 0:
+            self._chk(self.L.rbl_ensemble_get_config(self.h, None, None))       # the state error, as every ensemble call gives it
+        if (F_body is None) == (prescribed is None and body_in is None):
+            raise ValueError("ensemble_run: give either F_body or prescribed with body_in")
+        if F_body is None and (prescribed is None or body_in is None):
+            raise ValueError("ensemble_run: prescribed and body_in go together")
+        n_steps, stride = int(n_steps), int(stride)
+        if n_steps < 1 or stride < 0:
+            raise ValueError("ensemble_run: need n_steps >= 1 and stride >= 0; got %d and %d" % (n_steps, stride))
+        masked = F_body is None
+        sl = None
+        if masked:
+            _, _, m, bi, sl = self._ens_mixed_args("ensemble_run", prescribed, body_in, slip)
+        else:
+            F = self._ens_vec(F_body, 6 * nb, "F_body")
+            sl = None if slip is None else self._ens_vec(slip, 3 * nb * self._sizes()[1], "slip")
+        o = RunOpts()
+        o.size = C.sizeof(RunOpts)
+        o.n_steps, o.brownian, o.split_rand, o.max_iter = n_steps, int(bool(brownian)), int(bool(split_rand)), int(max_iter)
+        o.stride, o.on_error, o.check_every, o.seed = stride, int(on_error), int(check_every), int(seed)
+        o.delta, o.rtol = float(delta), float(rtol or 0.0)
+        o.F_body = None if masked else F.ctypes.data
+        o.prescribed = m.ctypes.data if masked else None
+        o.body_in = bi.ctypes.data if masked else None
+        o.slip = None if sl is None else sl.ctypes.data
+        nf = n_steps // stride if stride > 0 else 0
+        res = RunResult()
+        res.accepted, res.rejected = np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32)
+        res.first_flags, res.first_status = np.zeros(R, dtype=np.uint32), np.zeros(R, dtype=np.int32)
+        res.iters_sum, res.resid_max = np.zeros(R, dtype=np.int64), np.zeros(R)
+        res.F_sum = np.zeros((R, 6 * nb)) if masked else None
+        res.X, res.Q = np.zeros((nf, R, nb, 3)), np.zeros((nf, R, nb, 4))
+        res.accepted_at = np.zeros((nf, R), dtype=np.int32)
+        res.F = np.zeros((nf, R, 6 * nb)) if masked else None
+        out = RunOut()
+        out.size = C.sizeof(RunOut)
+        out.accepted, out.rejected = res.accepted.ctypes.data, res.rejected.ctypes.data
+        out.first_flags, out.first_status = res.first_flags.ctypes.data, res.first_status.ctypes.data
+        out.iters_sum, out.resid_max = res.iters_sum.ctypes.data, res.resid_max.ctypes.data
+        out.F_sum = res.F_sum.ctypes.data if masked else None
+        out.frame_X, out.frame_Q, out.frame_accepted_at = res.X.ctypes.data, res.Q.ctypes.data, res.accepted_at.ctypes.data
+        out.frame_F = res.F.ctypes.data if masked else None
+        out.stopped_at = out.stop_replica = -1       # a refused call leaves them so
+        rc = self.L.rbl_ensemble_run(self.h, C.byref(o), C.byref(out))
+        res.steps_done, res.stopped_at, res.stop_replica = out.steps_done, out.stopped_at, out.stop_replica
+        res.status, res.error = rc, None
+        if rc != 0:
+            res.error = "%s [rbl status %d]" % (self.L.rbl_last_error(self.h).decode(), rc)
+            if out.stopped_at < 0:                    # refused, or failed outside the steps: there is no result
+                raise RblError(res.error)
+        res.F_mean = None
+        if masked:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                res.F_mean = np.where(res.accepted[:, None] > 0, res.F_sum / res.accepted[:, None], np.nan)
+        return res, rc
 
     def _sizes(self):
         nb, nblb = C.c_int(0), C.c_int(0)

@@ -161,8 +161,11 @@ int flow_check(rbl_ctx *c, int n_bod);
 // the steps' use of the term t = scale R s_body - u_inf at the context's configuration: d_slip (3 N) becomes slip + t when
 // *have_slip, t otherwise, and *have_slip becomes true.  While both parts are off: nothing (no launch, no allocation)
 int flow_add_to_step_slip(rbl_ctx *c, double *d_slip, bool *have_slip);
-// the same for `reps` replicas of N_bod bodies in one launch (positions and orientations of all of them)
-int flow_add_batch(rbl_ctx *c, const double *d_pos, const double *d_Q, int N_bod, int reps, double *d_slip, bool *have_slip);
+// the same for `reps` replicas of N_bod bodies in one launch (positions and orientations of all of them).  d_caller (a run's
+// resident slip, uploaded once): the caller's slip is read there and d_slip is only written, so it is never added to twice
+int flow_add_batch(rbl_ctx *c, const double *d_pos, const double *d_Q, int N_bod, int reps, double *d_slip, bool *have_slip,
+                   const double *d_caller = nullptr);
+bool flow_on(const rbl_ctx *c);               // either part of the model is switched on
 // D_b = sum l lambda^T of n_bodies bodies, Nb a replica; d_lever, or NULL and (d_Q, d_cfg) to rebuild the lever arms
 void flow_launch_moments(rbl_ctx *c, const double *d_lever, const double *d_Q, const double *d_cfg, const double *d_lam, int Nb,
                          int n_bodies, int64_t rep_stride, double *d_D);

@@ -21,10 +21,11 @@ constexpr int PBW = 8;   // waves of k_potrf_block
 
 __global__ __launch_bounds__(64 * PBW) void k_potrf_block(double *__restrict__ A, long ld, long k, int pw,
                                                           double *__restrict__ LinvAll, unsigned *err,
-                                                          long strideA, long strideL)
+                                                          long strideA, long strideL, long strideE)
 {
   A += (size_t)blockIdx.y * (size_t)strideA;        // batched: one matrix per blockIdx.y
   LinvAll += (size_t)blockIdx.y * (size_t)strideL;
+  err += (size_t)blockIdx.y * (size_t)strideE;      // its error word (0: one word for the batch)
   __shared__ double Y[IB][IB + 1];   // L_kk^-1 of the current step, row-major [c][m]
   potrf_block_body<PBW>(A, ld, k, pw, LinvAll, err, Y);
 }
@@ -476,7 +477,7 @@ int rbl_launch_cholesky(hipStream_t st, double *d_M, int64_t n, bool zero_upper,
     }
     // the NB x NB diagonal block: one 16-wave workgroup, barriers instead of launches
     hipLaunchKernelGGL(k_potrf_block, dim3(1), dim3(64 * PBW), 0, sp, d_M, (long)n, (long)k, (int)pw, Linv, d_err,
-                       0L, 0L);
+                       0L, 0L, 0L);
     if (pend < n)            // rows below the block: X = A21 L11^-T, all NB/IB column blocks in one launch
       hipLaunchKernelGGL(k_trsm_tall, dim3((unsigned)((n - pend + 127) / 128)), dim3(256), 0, sp, d_M, (long)n,
                          (long)n, (long)k, (int)(pw / IB), (long)pend, Linv, 0L, 0L);
@@ -528,15 +529,15 @@ size_t rbl_cholesky_batched_work_bytes(int64_t n, int batch)
 }
 
 int rbl_launch_cholesky_batched(hipStream_t st, double *d_M, int64_t n, int batch, int64_t strideA,
-                                unsigned *d_err, double *d_Linv)
+                                unsigned *d_err, double *d_Linv, int64_t err_stride)
 {
   constexpr int GRID_YZ_MAX = 65535;                 // bodies ride in gridDim.y / .z: more than that go in several rounds
   if (batch > GRID_YZ_MAX) {
     const size_t lstride = rbl_cholesky_batched_work_bytes(n, 1) / sizeof(double);
     for (int b0 = 0; b0 < batch; b0 += GRID_YZ_MAX) {
       const int nb = batch - b0 < GRID_YZ_MAX ? batch - b0 : GRID_YZ_MAX;
-      const int rc = rbl_launch_cholesky_batched(st, d_M + (size_t)b0 * (size_t)strideA, n, nb, strideA, d_err,
-                                                 d_Linv + (size_t)b0 * lstride);
+      const int rc = rbl_launch_cholesky_batched(st, d_M + (size_t)b0 * (size_t)strideA, n, nb, strideA,
+                                                 d_err + (size_t)b0 * (size_t)err_stride, d_Linv + (size_t)b0 * lstride, err_stride);
       if (rc) return rc;
     }
     return RBL_OK;
@@ -550,7 +551,7 @@ int rbl_launch_cholesky_batched(hipStream_t st, double *d_M, int64_t n, int batc
     double *Lk = d_Linv + (size_t)(k / IB) * IB * IB;   // this panel's L_kk^-1 blocks (all are kept)
     // diagonal block of every matrix: one workgroup each; then the rows below it, all column steps fused
     hipLaunchKernelGGL(k_potrf_block, dim3(1, batch), dim3(64 * PBW), 0, st, d_M, (long)n, (long)k, (int)pw, Lk, d_err,
-                       (long)strideA, strideL);
+                       (long)strideA, strideL, (long)err_stride);
     if (pend < n)
       hipLaunchKernelGGL(k_trsm_tall, dim3((unsigned)((n - pend + 127) / 128), 1, batch), dim3(256), 0, st, d_M, (long)n,
                          (long)n, (long)k, (int)(pw / IB), (long)pend, (const double *)Lk, (long)strideA, strideL);

@@ -32,6 +32,15 @@
 // so the model's K^T f reaches the bottom rows of the free bodies and what they write on a prescribed body's rows is overwritten
 // by the solver.  U and F follow the error words in the ONE read-back.  A free body's arithmetic and its order are unchanged: with
 // nobody prescribed the configurations and iteration counts are bitwise those of the unmasked steps.
+//
+// A run (rbl_ensemble_run): n steps in one call.  Each step function is an enqueueing part (ens_enqueue_det / ens_enqueue_bd) and
+// a finish (ens_finish: the read-back, the host's verdict, the swap); the one-step calls are the two in a row.  A run uploads its
+// inputs once, enqueues the first part per step with them resident, and lets two kernels of its own stand where the finish stood:
+//   k_ens_verdict             per replica (one workgroup): its error word, and under the reject policy the wall check of q^{n+1};
+//                             one compare-and-swap latches the step that stops the run
+//   k_ens_commit              per replica, a second launch (so `stopped` is final without any wait between workgroups): commit, or
+//                             q^n copied into the new buffer; counters, sums over accepted steps, the frame
+// The host swaps the two configuration buffers after every step without a synchronisation and reads back once at the end.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -270,6 +279,111 @@ __global__ __launch_bounds__(ET) void k_ens_evolve(int nbod, int Nb, long nsys, 
   if (!ok) atomicOr(rerr + r, (unsigned)RBL_FLAG_NONFINITE);
 }
 
+// ---- a run of steps (rbl_ensemble_run): the verdict and the commit of every step, per replica, on the device ----------------
+// The few bytes the host polls.  stopped: 1 + the step that stopped the run (0: never; written once, by the first verdict that
+// finds a reason); stop_rep: R - r of the first failing replica r of that step (0: none, a batch-level failure); batch: the batch
+// word of that step
+struct EnsRunStatus { int stopped, stop_rep; unsigned batch; int pad; };
+
+// what the commit kernel reads and writes (device pointers; the frame slots are NULL in a step that records none)
+struct EnsRunDev {
+  const double *Xo, *Qo;                 // q^n
+  double *Xn, *Qn;                       // q^{n+1} as k_ens_evolve left it; q^n again where the replica does not commit
+  const unsigned *vflag, *gerr;
+  const int *iters; const double *resid;
+  const double *Fo;                      // the masked solve's loads (NULL: nobody prescribed)
+  EnsRunStatus *st;
+  int *accepted, *rejected; unsigned *first_flags; long long *iters_sum; double *resid_max, *F_sum, *F_last;
+  double *fX, *fQ; int *fA; double *fF;
+};
+
+// One workgroup per replica: the replica's verdict on step `step`, vflag[r] = its error word as the step's kernels left it and,
+// with reject, the validation of q^{n+1} (Xn, Qn) BEFORE it commits: a blob of the new configuration below the wall is
+// RBL_FLAG_BELOW_WALL, its height computed term for term as k_body_geom does (lever arm with contraction off, then + X), so this
+// is the verdict the next step's k_build_M or pair sweep would reach.  Non-finite components of Xn, Qn are in the word already
+// (k_ens_evolve).  Lanes that find something OR it into one LDS word.  Then the run-level decision: the batch word, or under
+// the stop policy any replica's word, stops the run at this step unless it stopped before -- one compare-and-swap, nobody waits
+template <bool WALL>
+__global__ __launch_bounds__(ET) void k_ens_verdict(int Nb, int nbl, int step, int reject, const double *__restrict__ Xn,
+                                                    const double *__restrict__ Qn, const double *__restrict__ cfg,
+                                                    const unsigned *__restrict__ rerr, const unsigned *__restrict__ gerr,
+                                                    unsigned *__restrict__ vflag, EnsRunStatus *st)
+{
+  __shared__ unsigned s_flags;
+  const int r = blockIdx.x, t = threadIdx.x;
+  if (t == 0) s_flags = rerr[r];
+  __syncthreads();
+  if (WALL && reject && t < Nb * nbl) {
+    const int b = t / nbl, k = t - b * nbl;
+    const size_t g = (size_t)r * Nb + b;
+    double Rm[9];
+    rbl_quat_rot9(Qn + 4 * g, Rm);
+    const double c0 = cfg[3 * k], c1 = cfg[3 * k + 1], c2 = cfg[3 * k + 2];
+    double p2;
+    {
+#pragma clang fp contract(off)
+      const double l2 = c0 * Rm[6] + c1 * Rm[7] + c2 * Rm[8];
+      p2 = l2 + Xn[3 * g + 2];
+    }
+    if (p2 < 0.0) atomicOr(&s_flags, (unsigned)RBL_FLAG_BELOW_WALL);
+  }
+  __syncthreads();
+  if (t == 0) {
+    const unsigned f = s_flags;
+    vflag[r] = f;
+    if (gerr[0] || (!reject && f)) atomicCAS(&st->stopped, 0, step + 1);
+  }
+}
+
+// One workgroup per replica, after k_ens_verdict has finished for all of them (st->stopped is final for this step): the replica
+// commits when the run has not stopped and its word is clear; otherwise q^n is copied into the new buffer, which the host
+// makes the current one without looking.  Counters, the sums over accepted steps and the frame follow the same decision; every
+// entry of F_sum is added to by one thread, in step order.  Nothing counts after the stopping step
+__global__ __launch_bounds__(ET) void k_ens_commit(int R, int Nb, int step, EnsRunDev D)
+{
+  const int r = blockIdx.x, t = threadIdx.x;
+  const int stopped = D.st->stopped;
+  const unsigned f = D.vflag[r];
+  const bool ok = stopped == 0 && f == 0;
+  const int acc = D.accepted[r] + (ok ? 1 : 0);
+  __syncthreads();                                     // every thread has read accepted[r]
+  if (t == 0) {
+    if (ok) {
+      D.accepted[r] = acc;
+      D.iters_sum[r] += D.iters[r];
+      if (D.resid[r] > D.resid_max[r]) D.resid_max[r] = D.resid[r];
+    } else if (f && (stopped == 0 || stopped == step + 1)) {
+      if (D.rejected[r] == 0) D.first_flags[r] = f;
+      D.rejected[r] += 1;
+    }
+    if (stopped == step + 1) {                         // the stopping step names its first failing replica and keeps the batch word
+      if (f) atomicMax(&D.st->stop_rep, R - r);
+      if (r == 0) D.st->batch = D.gerr[0];
+    }
+    if (D.fA) D.fA[r] = acc;
+  }
+  const int nx = 3 * Nb, nq = 4 * Nb, nf = 6 * Nb;
+  for (int j = t; j < nx; j += ET) {
+    const size_t i = (size_t)r * nx + j;
+    double v = D.Xn[i];
+    if (!ok) { v = D.Xo[i]; D.Xn[i] = v; }
+    if (D.fX) D.fX[i] = v;
+  }
+  for (int j = t; j < nq; j += ET) {
+    const size_t i = (size_t)r * nq + j;
+    double v = D.Qn[i];
+    if (!ok) { v = D.Qo[i]; D.Qn[i] = v; }
+    if (D.fQ) D.fQ[i] = v;
+  }
+  if (D.Fo)
+    for (int j = t; j < nf; j += ET) {
+      const size_t i = (size_t)r * nf + j;
+      double v = D.F_last[i];
+      if (ok) { v = D.Fo[i]; D.F_last[i] = v; D.F_sum[i] += v; }
+      if (D.fF) D.fF[i] = v;
+    }
+}
+
 size_t rfd_lds_bytes(int Nb, int nbl)
 {
   const size_t N = (size_t)Nb * nbl;
@@ -386,14 +500,19 @@ int ens_finish(rbl_ctx *c, const EnsWork &w, int R, int *iters, double *resid, b
 // upload F (R 6 N_bod) and slip (R n3 or NULL), clear the read-back block, evaluate the force model at q^n when it is on and
 // the caller wants its loads (model): *FT -> K^T f_phys of every replica (NULL otherwise).  The flow model (include/rbl.h
 // section 8) goes the same way: one launch adds its term at q^n to every replica's slip.  *SL -> the slip the right-hand side
-// takes: the caller's, the term, their sum, or NULL for zero
+// takes: the caller's, the term, their sum, or NULL for zero.  resident (a run, rbl_ensemble_run): nothing is uploaded -- w.F
+// holds F_body since the run began and slip is the DEVICE copy made then, which the flow model's term is added to into w.slip
+// (never in place: the copy serves every step)
 int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *slip, const double **FT, const double **SL,
-              bool model = true)
+              bool model = true, bool resident = false)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
   const size_t n3 = (size_t)3 * Nb * nbl, nb6 = (size_t)6 * Nb;
-  int rc = copy_h2d(c, w.F, F_body, sizeof(double) * nb6 * R); if (rc) return rc;
-  if (slip && (rc = copy_h2d(c, w.slip, slip, sizeof(double) * n3 * R))) return rc;
+  int rc;
+  if (!resident) {
+    if ((rc = copy_h2d(c, w.F, F_body, sizeof(double) * nb6 * R))) return rc;
+    if (slip && (rc = copy_h2d(c, w.slip, slip, sizeof(double) * n3 * R))) return rc;
+  }
   RBL_HIP(c, hipMemsetAsync(w.resid, 0, w.rb_bytes, c->stream));
   const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
   rbl_launch_body_geom(c->stream, X, Q, ens_cfg(c), nbl, (int64_t)R * Nb * nbl, w.lever, w.pos);
@@ -404,8 +523,9 @@ int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *
     *FT = w.FT;
   }
   bool have_slip = slip != nullptr;
-  if (model && (rc = flow_add_batch(c, w.pos, Q, Nb, R, w.slip, &have_slip))) return rc;
-  *SL = have_slip ? w.slip : nullptr;
+  const bool flow = model && flow_on(c);
+  if (flow && (rc = flow_add_batch(c, w.pos, Q, Nb, R, w.slip, &have_slip, resident ? slip : nullptr))) return rc;
+  *SL = !have_slip ? nullptr : (resident && !flow) ? slip : w.slip;
   return RBL_OK;
 }
 
@@ -429,7 +549,7 @@ int ens_check_solver(rbl_ctx *c, int max_iter)
 // mixed: the masked solve (w.mask, body_in in w.F); the update then reads the U it wrote (a prescribed body: dt U_p exactly).
 // evolve = false: the solve alone
 int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const double *Qs, int max_iter, double rtol, bool mixed = false,
-                     bool evolve = true)
+                     bool evolve = true, bool record = true)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
   const long n3 = 3L * Nb * nbl, nsys = n3 + 6L * Nb;
@@ -441,8 +561,9 @@ int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const doubl
   if (rc) return rbl_fail(c, rc, "ensemble step: the one-kernel solver does not fit this device's LDS");
   if (!evolve) return RBL_OK;
   const int nbod = R * Nb;
-  if (c->record_mom) {                                   // RBL_OPT_RECORD_MOMENTS: lambda is the top of every replica's x, the lever
-    c->ens_mom_R = 0;                                    // arms those of the configuration solved at; valid once the step committed
+  if (c->record_mom) c->ens_mom_R = 0;                   // valid once a step committed; a run (record = false) leaves nothing to read
+  if (c->record_mom && record) {                         // RBL_OPT_RECORD_MOMENTS: lambda is the top of every replica's x, the lever
+                                                         // arms those of the configuration solved at
     if ((rc = rbl_dev_reserve(c, c->d_ens_mom, sizeof(double) * 9 * (size_t)nbod))) return rc;
     flow_launch_moments(c, nullptr, Qs, ens_cfg(c), w.x, Nb, nbod, nsys, (double *)c->d_ens_mom.p);
   }
@@ -478,22 +599,44 @@ int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const d
 // rbl_ensemble_step_deterministic -- the unmasked solver, lambda, U and F NULL; otherwise body_in stands where F_body stands and
 // the solve is the masked one.  move = false: the solve alone, at the current configuration and without the model's loads
 // (rbl_ensemble_solve_mixed)
-int ens_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, int max_iter, double rtol, bool move,
-                 double *lambda, double *U, double *F, int *iters, double *resid)
+// What one step reads.  A one-step call passes host arrays, which the enqueueing part uploads; a run (rbl_ensemble_run) has uploaded
+// them once: resident -- prescribed then only says that the step is the masked one (w.mask is filled), F_body is unused (w.F is
+// filled), slip is the run's device copy, W is NULL.  chol_err: the batched Cholesky's error stride (0: the batch word)
+struct EnsStepIn {
+  const uint8_t *prescribed = nullptr;
+  const double *F_body = nullptr, *slip = nullptr, *W = nullptr;
+  bool resident = false;
+  int64_t chol_err = 0;
+};
+
+// everything the deterministic step enqueues, from the uploads to the update: the one-step calls and the run share it
+int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_iter, double rtol, bool move)
 {
-  const bool mixed = prescribed != nullptr;
-  EnsWork w;
+  const bool mixed = in.prescribed != nullptr;
   const double *FT, *SL;
   int rc;
-  if ((rc = ens_work(c, max_iter, &w))) return rc;
-  if (mixed && (rc = copy_h2d(c, w.mask, prescribed, (size_t)c->ens_R * c->ens_Nb))) return rc;
-  if ((rc = ens_begin(c, w, F_body, slip, &FT, &SL, move))) return rc;
+  if (mixed && !in.resident && (rc = copy_h2d(c, w.mask, in.prescribed, (size_t)c->ens_R * c->ens_Nb))) return rc;
+  if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, move, in.resident))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb;
   const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb;
   const long tot = (long)R * (n3 + nb6);
   hipLaunchKernelGGL(k_ens_rhs_det, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, n3, nb6, SL,
                      (const double *)w.F, FT, w.rhs);
-  if ((rc = ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, mixed, move))) return rc;
+  return ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, mixed, move, !in.resident);
+}
+
+int ens_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, int max_iter, double rtol, bool move,
+                 double *lambda, double *U, double *F, int *iters, double *resid)
+{
+  const bool mixed = prescribed != nullptr;
+  EnsWork w;
+  int rc;
+  if ((rc = ens_work(c, max_iter, &w))) return rc;
+  EnsStepIn in;
+  in.prescribed = prescribed; in.F_body = F_body; in.slip = slip;
+  if ((rc = ens_enqueue_det(c, w, in, max_iter, rtol, move))) return rc;
+  const int R = c->ens_R, Nb = c->ens_Nb;
+  const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb;
   std::vector<double> x;
   if (lambda) {                                          // the blob forces: the top of every replica's solution
     x.resize((size_t)R * (n3 + nb6));
@@ -509,26 +652,25 @@ int ens_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, co
 
 // the stochastic midpoint step of every replica (checks done by the caller).  prescribed == NULL: rbl_ensemble_step_brownian;
 // otherwise body_in stands where F_body stands, the predictor and the solve are the masked ones and F_out takes the loads
-int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, const double *W, uint64_t seed,
-                int split_rand, double delta, int max_iter, double rtol, double *F_out, int *iters, double *resid)
+// everything the stochastic step enqueues, from the uploads and the noise to the update: shared as ens_enqueue_det is
+int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t seed, int split_rand, double delta, int max_iter,
+                   double rtol)
 {
   const RblBodyState &S = c->S;
-  const bool mixed = prescribed != nullptr;
+  const bool mixed = in.prescribed != nullptr;
   int rc;
-  EnsWork w;
-  if ((rc = ens_work(c, max_iter, &w))) return rc;
-  if (mixed && (rc = copy_h2d(c, w.mask, prescribed, (size_t)c->ens_R * c->ens_Nb))) return rc;
+  if (mixed && !in.resident && (rc = copy_h2d(c, w.mask, in.prescribed, (size_t)c->ens_R * c->ens_Nb))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = S.N_blb, N = Nb * nbl;
   const int64_t n3 = 3 * (int64_t)N;
-  if (W) { if ((rc = copy_h2d(c, w.W, W, sizeof(double) * 3 * (size_t)n3 * R))) return rc; }
+  if (in.W) { if ((rc = copy_h2d(c, w.W, in.W, sizeof(double) * 3 * (size_t)n3 * R))) return rc; }
   else rbl_launch_normal_batched(c->stream, seed, 3 * n3, R, w.W);            // rand_vector (:730-741), one draw per replica
   const double *FT, *SL;
-  if ((rc = ens_begin(c, w, F_body, slip, &FT, &SL))) return rc;
+  if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, true, in.resident))) return rc;
   const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
   // dense root of every replica: B M B (:667-669), lower Cholesky (:670-671), L W1 and L W2 (:672)
   const RblParams P = rbl_make_params(S.a, S.eta);
   rbl_launch_build_M_batched(c->stream, P, S.wall, true, w.pos, N, R, w.Lm, n3 * n3, w.rerr, 0, 1);
-  if ((rc = rbl_launch_cholesky_batched(c->stream, w.Lm, n3, R, n3 * n3, w.gerr, w.Linv)))
+  if ((rc = rbl_launch_cholesky_batched(c->stream, w.Lm, n3, R, n3 * n3, in.chol_err ? w.rerr : w.gerr, w.Linv, in.chol_err)))
     return rbl_fail(c, rc, "ensemble: batched Cholesky launch failed");
   const int split = split_rand ? 1 : 0;
   for (int v = 0; v <= split; ++v)
@@ -557,10 +699,151 @@ int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, con
                        (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
                        SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
   // saddle solve at q^{n+1/2}, update from q^n
-  if ((rc = ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol, mixed))) return rc;
+  return ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol, mixed, true, !in.resident);
+}
+
+int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, const double *W, uint64_t seed,
+                int split_rand, double delta, int max_iter, double rtol, double *F_out, int *iters, double *resid)
+{
+  const bool mixed = prescribed != nullptr;
+  int rc;
+  EnsWork w;
+  if ((rc = ens_work(c, max_iter, &w))) return rc;
+  EnsStepIn in;
+  in.prescribed = prescribed; in.F_body = F_body; in.slip = slip; in.W = W;
+  if ((rc = ens_enqueue_bd(c, w, in, seed, split_rand, delta, max_iter, rtol))) return rc;
+  const int R = c->ens_R, Nb = c->ens_Nb;
   std::vector<double> Ft;
   if (mixed && !F_out) { Ft.resize((size_t)R * 6 * Nb); F_out = Ft.data(); }   // the masked read-back is chosen by F
   return ens_finish(c, w, R, iters, resid, true, nullptr, mixed ? F_out : nullptr);
+}
+
+// the run's own device buffer: [slip copy] | read-back block (status, counters, sums) | verdict words, last loads | frames
+struct EnsRunBuf {
+  double *slip;
+  EnsRunStatus *st; int *accepted, *rejected; unsigned *first_flags; long long *iters_sum; double *resid_max, *F_sum;
+  size_t rb_off, rb_bytes;                 // the read-back block: from st to the end of F_sum
+  unsigned *vflag; double *F_last;
+  double *fX, *fQ; int *fA; double *fF;
+};
+
+EnsRunBuf ens_run_carve(void *base, int R, int Nb, int nbl, bool slip, bool mixed, size_t n_frames, size_t *bytes)
+{
+  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, n3 = (size_t)3 * Nb * nbl;
+  Carve C{(char *)base};
+  EnsRunBuf b;
+  b.slip = C.take<double>(slip ? Rz * n3 : 0);
+  b.rb_off = C.off;
+  b.st = C.take<EnsRunStatus>(1);
+  b.accepted = C.take<int>(Rz); b.rejected = C.take<int>(Rz); b.first_flags = C.take<unsigned>(Rz);
+  b.iters_sum = C.take<long long>(Rz); b.resid_max = C.take<double>(Rz);
+  b.F_sum = C.take<double>(mixed ? Rz * nb6 : 0);
+  b.rb_bytes = C.off - b.rb_off;
+  b.vflag = C.take<unsigned>(Rz);
+  b.F_last = C.take<double>(mixed ? Rz * nb6 : 0);
+  b.fX = C.take<double>(n_frames * Rz * 3 * Nb); b.fQ = C.take<double>(n_frames * Rz * 4 * Nb);
+  b.fA = C.take<int>(n_frames * Rz);
+  b.fF = C.take<double>(mixed ? n_frames * Rz * nb6 : 0);
+  *bytes = C.off;
+  return b;
+}
+
+// n_steps steps of every replica (checks and ens_ready done by the caller): the inputs go up once, every step is the one-step
+// calls' enqueue sequence followed by the verdict and the commit, the buffers flip on the host, ONE read-back ends it
+int ens_run(rbl_ctx *c, const rbl_run_opts &o, bool brownian, rbl_run_out *out)
+{
+  const RblBodyState &S = c->S;
+  const bool mixed = o.prescribed != nullptr, reject = o.on_error == RBL_RUN_REJECT;
+  const int R = c->ens_R, Nb = c->ens_Nb, nbl = S.N_blb;
+  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, n3 = (size_t)3 * Nb * nbl;
+  const size_t n_frames = o.stride > 0 ? (size_t)(o.n_steps / o.stride) : 0;
+  int rc;
+  EnsWork w;
+  if ((rc = ens_work(c, o.max_iter, &w))) return rc;
+  size_t bytes = 0;
+  ens_run_carve(nullptr, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
+  if ((rc = rbl_dev_reserve(c, c->d_ens_run, bytes))) return rc;
+  const EnsRunBuf b = ens_run_carve(c->d_ens_run.p, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
+  // the uploads, once
+  if (mixed && (rc = copy_h2d(c, w.mask, o.prescribed, Rz * Nb))) return rc;
+  if ((rc = copy_h2d(c, w.F, mixed ? o.body_in : o.F_body, sizeof(double) * nb6 * Rz))) return rc;
+  if (o.slip && (rc = copy_h2d(c, b.slip, o.slip, sizeof(double) * n3 * Rz))) return rc;
+  RBL_HIP(c, hipMemsetAsync(b.st, 0, b.rb_bytes, c->stream));
+  if (mixed) RBL_HIP(c, hipMemsetAsync(b.F_last, 0, sizeof(double) * nb6 * Rz, c->stream));
+  EnsStepIn in;
+  in.prescribed = o.prescribed; in.slip = o.slip ? b.slip : nullptr; in.resident = true; in.chol_err = 1;
+  EnsRunStatus hs = {0, 0, 0u, 0};
+  int enq = 0;
+  for (int n = 0; n < o.n_steps; ++n) {
+    rc = brownian ? ens_enqueue_bd(c, w, in, o.seed + (uint64_t)n, o.split_rand, o.delta, o.max_iter, o.rtol)
+                  : ens_enqueue_det(c, w, in, o.max_iter, o.rtol, true);
+    if (rc) return rc;
+    const int cur = c->ens_cur;
+    if (S.wall)
+      hipLaunchKernelGGL(k_ens_verdict<true>, dim3((unsigned)R), dim3(ET), 0, c->stream, Nb, nbl, n, reject ? 1 : 0,
+                         (const double *)ens_X(c, cur ^ 1), (const double *)ens_Q(c, cur ^ 1), (const double *)ens_cfg(c),
+                         (const unsigned *)w.rerr, (const unsigned *)w.gerr, b.vflag, b.st);
+    else
+      hipLaunchKernelGGL(k_ens_verdict<false>, dim3((unsigned)R), dim3(ET), 0, c->stream, Nb, nbl, n, reject ? 1 : 0,
+                         (const double *)ens_X(c, cur ^ 1), (const double *)ens_Q(c, cur ^ 1), (const double *)ens_cfg(c),
+                         (const unsigned *)w.rerr, (const unsigned *)w.gerr, b.vflag, b.st);
+    EnsRunDev D;
+    D.Xo = ens_X(c, cur); D.Qo = ens_Q(c, cur); D.Xn = ens_X(c, cur ^ 1); D.Qn = ens_Q(c, cur ^ 1);
+    D.vflag = b.vflag; D.gerr = w.gerr; D.iters = w.iters; D.resid = w.resid; D.Fo = mixed ? w.Fo : nullptr; D.st = b.st;
+    D.accepted = b.accepted; D.rejected = b.rejected; D.first_flags = b.first_flags; D.iters_sum = b.iters_sum;
+    D.resid_max = b.resid_max; D.F_sum = b.F_sum; D.F_last = b.F_last;
+    D.fX = D.fQ = D.fF = nullptr; D.fA = nullptr;
+    if (o.stride > 0 && (n + 1) % o.stride == 0) {
+      const size_t k = (size_t)((n + 1) / o.stride - 1);
+      D.fX = b.fX + k * Rz * 3 * Nb; D.fQ = b.fQ + k * Rz * 4 * Nb; D.fA = b.fA + k * Rz;
+      if (mixed) D.fF = b.fF + k * Rz * nb6;
+    }
+    hipLaunchKernelGGL(k_ens_commit, dim3((unsigned)R), dim3(ET), 0, c->stream, R, Nb, n, D);
+    c->ens_cur ^= 1;                                     // the new buffer holds every replica's configuration, moved or not
+    ++enq;
+    if (o.check_every > 0 && enq % o.check_every == 0 && n + 1 < o.n_steps) {
+      if ((rc = read_back(c, &hs, b.st, sizeof(hs)))) return rc;
+      if (hs.stopped) break;
+    }
+  }
+  RBL_HIP(c, hipGetLastError());
+  // the one read-back: status, counters, sums; then the frames the run completed, straight into the caller's arrays
+  std::vector<char> h(b.rb_bytes);
+  if ((rc = copy_d2h(c, h.data(), b.st, b.rb_bytes))) return rc;
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  auto at = [&](const void *p) { return h.data() + ((const char *)p - (const char *)b.st); };
+  std::memcpy(&hs, at(b.st), sizeof(hs));
+  const int *hacc = (const int *)at(b.accepted), *hrej = (const int *)at(b.rejected);
+  const unsigned *hff = (const unsigned *)at(b.first_flags);
+  if (out->accepted) std::memcpy(out->accepted, hacc, sizeof(int) * Rz);
+  if (out->rejected) std::memcpy(out->rejected, hrej, sizeof(int) * Rz);
+  if (out->first_flags) std::memcpy(out->first_flags, hff, sizeof(unsigned) * Rz);
+  if (out->first_status)
+    for (int r = 0; r < R; ++r) out->first_status[r] = hrej[r] ? rbl_flags_to_status(c, hff[r]) : RBL_OK;
+  if (out->iters_sum) std::memcpy(out->iters_sum, at(b.iters_sum), sizeof(int64_t) * Rz);
+  if (out->resid_max) std::memcpy(out->resid_max, at(b.resid_max), sizeof(double) * Rz);
+  if (mixed && out->F_sum) std::memcpy(out->F_sum, at(b.F_sum), sizeof(double) * nb6 * Rz);
+  const size_t nfr = o.stride > 0 ? (size_t)(enq / o.stride) : 0;   // frames of the steps that were enqueued (a polled stop: fewer)
+  if (nfr) {
+    if ((rc = copy_d2h(c, out->frame_X, b.fX, sizeof(double) * nfr * Rz * 3 * Nb))) return rc;
+    if ((rc = copy_d2h(c, out->frame_Q, b.fQ, sizeof(double) * nfr * Rz * 4 * Nb))) return rc;
+    if ((rc = copy_d2h(c, out->frame_accepted_at, b.fA, sizeof(int) * nfr * Rz))) return rc;
+    if (mixed && (rc = copy_d2h(c, out->frame_F, b.fF, sizeof(double) * nfr * Rz * nb6))) return rc;
+    RBL_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  out->stopped_at = hs.stopped ? hs.stopped - 1 : -1;
+  out->steps_done = hs.stopped ? hs.stopped - 1 : o.n_steps;
+  out->stop_replica = hs.stopped && hs.stop_rep ? R - hs.stop_rep : -1;
+  if (!hs.stopped) return RBL_OK;
+  const std::string at_step = "ensemble_run step " + std::to_string(hs.stopped - 1);
+  if (hs.stop_rep) {
+    rc = rbl_flags_to_status(c, hff[R - hs.stop_rep]);
+    c->last_error = at_step + ", replica " + std::to_string(R - hs.stop_rep) + ": " + c->last_error;
+  } else {
+    rc = rbl_flags_to_status(c, hs.batch);
+    c->last_error = at_step + ": " + c->last_error;
+  }
+  return rc;
 }
 
 }  // namespace
@@ -689,6 +972,45 @@ int rbl_ensemble_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, cons
   if ((rc = ens_ready(c))) return rc;
   if (!brownian) return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
   return ens_step_bd(c, prescribed, body_in, slip, W, seed, split_rand, delta, max_iter, rtol, F, iters, resid);
+}
+
+int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (!o || !out) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: opts or out is NULL");
+  if (o->size != (int64_t)sizeof(rbl_run_opts)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: opts.size is not sizeof(rbl_run_opts)");
+  if (out->size != (int64_t)sizeof(rbl_run_out)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: out.size is not sizeof(rbl_run_out)");
+  out->steps_done = 0; out->stopped_at = -1; out->stop_replica = -1; out->reserved = 0;   // what a refused call leaves
+  if (o->n_steps < 1) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: n_steps must be >= 1");
+  if (o->stride < 0) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: stride must be >= 0");
+  if (o->check_every < 0) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: check_every must be >= 0");
+  if (o->on_error != RBL_RUN_STOP && o->on_error != RBL_RUN_REJECT)
+    return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: on_error must be RBL_RUN_STOP (0) or RBL_RUN_REJECT (1)");
+  const bool free_run = o->F_body != nullptr, masked = o->prescribed || o->body_in;
+  if (free_run == masked)
+    return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: give either F_body or prescribed with body_in (both or neither were given)");
+  if (o->max_iter < 1) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: max_iter must be >= 1");
+  if (!(o->rtol >= 0.0)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: rtol must be >= 0");
+  const size_t n_frames = o->stride > 0 ? (size_t)(o->n_steps / o->stride) : 0;
+  if (n_frames && (!out->frame_X || !out->frame_Q || !out->frame_accepted_at || (masked && !out->frame_F)))
+    return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: frame_X, frame_Q, frame_accepted_at (and frame_F with prescribed bodies) must not be NULL while stride > 0 records frames");
+  int rc;
+  if (masked) {                                        // NULL halves, max_iter > 255, communicator, state, entries, the LDS
+    if ((rc = ens_mx_check(c, "ensemble_run", o->prescribed, o->body_in, o->max_iter, o->rtol))) return rc;
+  } else {
+    if ((rc = need_params(c))) return rc;
+    if (o->max_iter > 255)
+      return rbl_fail(c, RBL_ERR_SIZE, "ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)");
+    if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, "ensemble: not on a context with a communicator (run one ensemble per process)");
+    if (!c->ens_R) return ens_fail_state(c);
+    if (c->S.N_blb != c->ens_Nblb) return rbl_fail(c, RBL_ERR_STATE, "ensemble: the structure changed since rbl_ensemble_set_config");
+    if ((rc = ens_check_solver(c, o->max_iter))) return rc;
+  }
+  const bool brownian = o->brownian && c->S.kBT > 1e-10;   // no Brownian terms (:967-970): the deterministic step
+  if (brownian && (!(c->S.dt > 0.0) || !(o->delta > 0.0))) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: dt and delta must be positive");
+  if ((rc = ens_flow_check(c))) return rc;
+  if ((rc = ens_ready(c))) return rc;
+  return ens_run(c, *o, brownian, out);
 }
 
 int rbl_ensemble_interaction_forces(rbl_ctx *c, double *FT_body, double *energy)

@@ -157,11 +157,14 @@ int flow_add_to_step_slip(rbl_ctx *c, double *d_slip, bool *have_slip)
 }
 
 // the same for `reps` replicas of N_bod bodies (rbl_ensemble.hip): positions and orientations of all of them, one launch
-int flow_add_batch(rbl_ctx *c, const double *d_pos, const double *d_Q, int N_bod, int reps, double *d_slip, bool *have_slip)
+bool flow_on(const rbl_ctx *c) { return fl_on(c); }
+
+int flow_add_batch(rbl_ctx *c, const double *d_pos, const double *d_Q, int N_bod, int reps, double *d_slip, bool *have_slip,
+                   const double *d_caller)
 {
   if (!fl_on(c)) return RBL_OK;
   int rc = fl_upload(c); if (rc) return rc;
-  fl_launch(c, d_pos, d_Q, N_bod, (int64_t)reps * N_bod * c->S.N_blb, *have_slip ? d_slip : nullptr, d_slip);
+  fl_launch(c, d_pos, d_Q, N_bod, (int64_t)reps * N_bod * c->S.N_blb, *have_slip ? (d_caller ? d_caller : d_slip) : nullptr, d_slip);
   *have_slip = true;
   return RBL_OK;
 }

@@ -211,6 +211,7 @@ struct rbl_ctx {
   int ens_cur = 0;                                  // which of the two configuration sets in d_ens is the committed one
   RblDevBuf d_ens;                                  // [X | Q] x 2 (R 7 N_bod each) | reference configuration
   RblDevBuf d_ens_w;                                // step workspace
+  RblDevBuf d_ens_run;                              // rbl_ensemble_run: resident inputs, counters, status block, frames
   // velocity field (rbl_field.hip; include/rbl.h section 6)
   RblDevBuf d_vf;                                   // host form's staging: points | u | lambda | r
   RblDevBuf d_vfw;                                  // packed sources | partial-sum slabs of the chunks
@@ -300,8 +301,9 @@ int rbl_launch_cholesky(hipStream_t st, double *d_M, int64_t n, bool zero_upper,
                         double *d_work, size_t work_bytes, const RblCholAux *aux);
 size_t rbl_cholesky_work_bytes(int64_t n);
 size_t rbl_cholesky_batched_work_bytes(int64_t n, int batch);
+// err_stride: matrix b reports into d_err[b err_stride] (0, the default: all into the one word; as rbl_launch_build_M_batched)
 int rbl_launch_cholesky_batched(hipStream_t st, double *d_M, int64_t n, int batch, int64_t strideA,
-                                unsigned *d_err, double *d_Linv);
+                                unsigned *d_err, double *d_Linv, int64_t err_stride = 0);
 int rbl_launch_block_solve_multi(hipStream_t st, const double *d_L, int64_t n, int batch, int64_t strideA,
                                  const double *d_Linv, const double *d_in, double *d_out, int64_t vec_stride, int nv,
                                  int64_t rhs_pitch, int mode, const double *d_Q = nullptr);

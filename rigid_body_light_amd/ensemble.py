@@ -11,7 +11,7 @@ the GPU.  Replicas never interact.  Sizes are those of the one-kernel solver (N_
 """
 import numpy as np
 
-from ._lib import DeviceContext
+from ._lib import RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError
 
 
 def _fail(message):
@@ -36,6 +36,7 @@ class Ensemble:
         self.ctx = DeviceContext(a, eta, wall, cfg=template.reshape(-1, 3), dt=dt, kBT=kBT, stream_ptr=stream)
         self.ctx.ensemble_set_config(X, Q)
         self.R, self.N_bodies = X.shape[0], X.shape[1]
+        self.last_run = None
 
     @staticmethod
     def _shapes(X, Q):
@@ -154,6 +155,46 @@ class Ensemble:
                 _fail("W must have shape (%d, %d); got %s" % (self.R, n, W.shape))
         return self.ctx.ensemble_step_brownian_mixed(m, b, W=W, seed=seed, split_rand=split_rand, delta=delta, max_iter=max_iter,
                                                      rtol=rtol, slip=s)
+
+    # ------------------------------------------------------------------ a run of steps (include/rbl.h section 5, rbl_ensemble_run)
+    def run(self, n_steps, F=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error="stop",
+            check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1e-4, max_iter=50, rtol=1e-8):
+        """n_steps steps of every replica in ONE call: the inputs go to the device once, each step's verdict and commit are taken
+        per replica on the device, one read-back ends the run -> RunResult (accepted, rejected, first_status, iters_sum, resid_max,
+        F_mean for runs with prescribed bodies, steps_done, stopped_at, and with stride > 0 the frames X, Q, accepted_at, F after
+        every stride-th step).  F as step_brownian takes it, or prescribed with body_in as step_brownian_mixed; step n draws its
+        noise from seed + n; brownian=False: deterministic steps.
+        on_error="stop": the first failing step commits nothing, nor does any later one; RblError is raised as the step methods
+        raise it, the partial result stays on self.last_run.  on_error="reject": a failing replica keeps its configuration and
+        tries again with the next step's noise (the customary redraw, not an unbiased one: see rejected), the others go on; the
+        new configuration is validated before it commits; only a failure of the whole batch raises.  check_every: steps between
+        the host's looks at the run's status (0: none before the end)"""
+        modes = {"stop": RUN_STOP, "reject": RUN_REJECT}
+        if on_error not in modes:
+            _fail("on_error must be 'stop' or 'reject'; got %r" % (on_error,))
+        n_steps, stride, check_every = int(n_steps), int(stride), int(check_every)
+        if n_steps < 1:
+            _fail("n_steps must be >= 1; got %d" % n_steps)
+        if stride < 0 or check_every < 0:
+            _fail("stride and check_every must be >= 0; got %d and %d" % (stride, check_every))
+        if (F is None) == (prescribed is None and body_in is None):
+            _fail("give either F or prescribed with body_in")
+        if F is None and (prescribed is None or body_in is None):
+            _fail("prescribed and body_in go together")
+        m = b = None
+        if F is not None:
+            F = self._forces(F)
+        else:
+            m, b = self._prescribed_mask(prescribed), self._body_in(body_in)
+        s = self._slip(slip)
+        self.last_run = None
+        res, rc = self.ctx.ensemble_run(n_steps, F_body=F, prescribed=m, body_in=b, brownian=brownian, seed=seed, stride=stride,
+                                        on_error=modes[on_error], check_every=check_every, slip=s, split_rand=split_rand,
+                                        delta=delta, max_iter=max_iter, rtol=rtol)
+        self.last_run = res
+        if rc != 0:
+            raise RblError(res.error)
+        return res
 
     def body_resistance_matrix(self, max_iter=100, rtol=1e-8):
         """the body resistance matrix of every replica's configuration, (R, 6 N_bod, 6 N_bod): every body prescribed, one ensemble
