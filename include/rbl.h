@@ -622,7 +622,21 @@ int rbl_interaction_stats(rbl_ctx *ctx, int64_t *body_pairs, int64_t *blob_pairs
  * shape whose masked solve does not fit the LDS (RBL_ERR_SIZE); no ensemble configuration (RBL_ERR_STATE).  Errors during a step
  * follow the ensemble's policy: the first failing replica is named, nothing is committed unless every replica succeeded.
  * With nobody prescribed in any replica the configurations and iteration counts are bitwise those of
- * rbl_ensemble_step_deterministic / rbl_ensemble_step_brownian on the same inputs. */
+ * rbl_ensemble_step_deterministic / rbl_ensemble_step_brownian on the same inputs.
+ *
+ * With a mask per velocity component (the _dof semantics of section 7, per replica: a roller with its rotation imposed and its
+ * translation free, a trapped probe free to turn, a layer with U_z = 0): prescribed6[R 6 N_bod], component by component in the lab
+ * frame (translation x, y, z, then rotation x, y, z); body_in, U and F as above, read component by component.
+ *   rbl_ensemble_solve_mixed_dof      rbl_solve_mixed_dof at every replica's configuration; lambda may be NULL, U and F must not.
+ *   rbl_ensemble_step_mixed_dof       rbl_step_mixed_dof for every replica: the solve, then evolve_X_Q(U); a body with its three
+ *                             translations held keeps X exactly while it turns.  The force model's loads and the flow model's
+ *                             term enter at q^n as in rbl_ensemble_step_mixed; the model's load counts on the free components
+ *                             only, so the F of a prescribed component is the TOTAL load along it.
+ * The same launch of the same kernel family: a whole body is the mask with none or all six of its entries set, and the launch is
+ * told whether its mask holds one entry per body or six.  A partly prescribed body's 6 x 6 preconditioner block is K^T invM K with the rows and columns of its prescribed components replaced
+ * by the identity's, factored again inside the launch (RBL_ERR_NOT_SPD when that fails).  Masks whose six entries per body are
+ * equal give bitwise the results, iteration counts and configurations of rbl_ensemble_solve_mixed / _step_mixed.  Refusals and the
+ * error policy are those above, with prescribed6 for prescribed.  There is no Brownian step with component masks (section 7). */
 int rbl_ensemble_set_config(rbl_ctx *ctx, int R, int N_bod, const double *X, const double *Q);
 int rbl_ensemble_get_config(rbl_ctx *ctx, double *X, double *Q);
 int rbl_ensemble_info(const rbl_ctx *ctx, int *R, int *N_bod);
@@ -636,6 +650,10 @@ int rbl_ensemble_solve_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const doub
                              double rtol, double *lambda, double *U, double *F, int *iters, double *resid);
 int rbl_ensemble_step_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter,
                             double rtol, double *F, int *iters, double *resid);
+int rbl_ensemble_solve_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter,
+                                 double rtol, double *lambda, double *U, double *F, int *iters, double *resid);
+int rbl_ensemble_step_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter,
+                                double rtol, double *F, int *iters, double *resid);
 int rbl_ensemble_step_brownian_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip,
                                      const double *W, uint64_t seed, int split_rand, double delta, int max_iter, double rtol,
                                      double *F, int *iters, double *resid);
@@ -645,7 +663,9 @@ int rbl_ensemble_step_brownian_mixed(rbl_ctx *ctx, const uint8_t *prescribed, co
  * of check_every).  The one-step calls above are unchanged; a run enqueues their very launch sequence once per step, followed by
  * two small launches (the verdict of every replica, then the commit), and flips the two configuration buffers on the host
  * without a synchronisation.  The four step families are chosen by the options: brownian 0/1, and either F_body (all bodies
- * free) or prescribed with body_in (held or driven bodies, as rbl_ensemble_step_[brownian_]mixed).  Everything in the options is
+ * free) or prescribed with body_in (held or driven bodies, as rbl_ensemble_step_[brownian_]mixed).  prescribed_per = 6 makes the
+ * mask one entry per velocity component (prescribed[R 6 N_bod], the steps of rbl_ensemble_step_mixed_dof; 0 and 1: whole bodies);
+ * such a run is deterministic only: with brownian != 0 and kBT > 1e-10 it is refused, that step's drift term is not derived.  Everything in the options is
  * constant over the run; the force model (section 4) and the flow model (section 8) enter every step at that step's q^n.
  *
  * Noise: drawn on the device.  Step n of the run (n = 0, 1, ... counts the run's steps, rejected ones included) draws what
@@ -690,7 +710,7 @@ int rbl_ensemble_step_brownian_mixed(rbl_ctx *ctx, const uint8_t *prescribed, co
  *
  * Refused before the device is touched, rbl_last_error naming the argument -- RBL_ERR_ARG: NULL structs or a wrong size,
  * n_steps < 1, stride < 0, check_every < 0, on_error outside {0, 1}, both or neither of F_body and (prescribed, body_in),
- * entries of prescribed above 1, max_iter < 1, rtol < 0, dt or delta not positive for a Brownian run, frame arrays NULL while
+ * entries of prescribed above 1, prescribed_per outside {0, 1, 6}, a Brownian run with prescribed_per = 6, max_iter < 1, rtol < 0, dt or delta not positive for a Brownian run, frame arrays NULL while
  * stride > 0 and n_frames > 0, a context with a communicator; RBL_ERR_SIZE: the solver's size refusals; RBL_ERR_STATE: no
  * ensemble configuration.  After a run rbl_ensemble_get_config and the one-step calls go on from its final configuration. */
 #define RBL_RUN_STOP 0
@@ -705,12 +725,12 @@ typedef struct rbl_run_opts {
   int32_t stride;             /* >= 0; 0 records no frames */
   int32_t on_error;           /* RBL_RUN_STOP or RBL_RUN_REJECT */
   int32_t check_every;        /* >= 0 */
-  int32_t reserved;           /* 0 */
+  int32_t prescribed_per;     /* mask entries per body: 0 or 1 whole bodies, 6 velocity components (deterministic runs only) */
   uint64_t seed;              /* step n draws from seed + n */
   double delta;               /* RFD step, as rbl_ensemble_step_brownian */
   double rtol;                /* >= 0 */
   const double *F_body;       /* [R 6 N_bod], or NULL with prescribed and body_in */
-  const uint8_t *prescribed;  /* [R N_bod] 0/1, or NULL with F_body */
+  const uint8_t *prescribed;  /* [R N_bod] 0/1 ([R 6 N_bod] with prescribed_per = 6), or NULL with F_body */
   const double *body_in;      /* [R 6 N_bod] */
   const double *slip;         /* [R n3] or NULL */
 } rbl_run_opts;
@@ -851,8 +871,8 @@ int rbl_velocity_field_info(const rbl_ctx *ctx, int64_t n_points, int64_t n_src,
  * The masked 6 x 6 Cholesky factors are made once per solve by one small launch (from the context's own factors; with the
  * free-space body-frame tables the one shared factor is first taken to each body's lab frame) and an iteration launches what an
  * iteration of rbl_solve_mixed launches: one mobility product and one pass over the per-body factors, two with the free-space
- * body-frame tables when anything is prescribed.  Its time per iteration and the iteration counts per mask have not been
- * measured yet (tools/bench_prescribed_dof.py).
+ * body-frame tables when anything is prescribed.  Its time per iteration over rbl_solve_mixed's with every body
+ * prescribed: 1.03-1.05 at cfg 2, 1.001-1.004 at cfg 3, wall (tools/bench_prescribed_dof.py, profiles/prescribed_dof.jsonl).
  *
  *   rbl_solve_mixed_dof      host arrays, synchronous.
  *   rbl_solve_mixed_dof_dev  device pointers as rbl_solve_mixed_dev; prescribed6 stays a HOST array (6 N_bod bytes, checked
@@ -888,7 +908,8 @@ int rbl_velocity_field_info(const rbl_ctx *ctx, int64_t n_points, int64_t n_src,
  * column, the Brownian steps in lock step; and with masks per component:
  *   - the Brownian step (rbl_step_brownian_mixed takes whole bodies only): its drift argument rests on whole bodies being
  *     undisplaced, a partly prescribed rotation is not a subset of the coordinates, and nobody has derived the scheme for it;
- *   - ensembles (rbl_ensemble_*_mixed take whole bodies only);
+ *   - for ensembles, the Brownian step as well (rbl_ensemble_step_brownian_mixed and Brownian runs take whole bodies only; the
+ *     deterministic rbl_ensemble_solve_mixed_dof / _step_mixed_dof and runs with prescribed_per = 6 are in section 5);
  *   - constraint axes fixed in the body frame (the six components are the lab frame's). */
 int rbl_solve_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
                     double *lambda, double *U, double *F, int *iters, double *resid);

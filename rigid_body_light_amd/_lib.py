@@ -96,6 +96,8 @@ def lib():
         L.rbl_ensemble_interaction_forces.argtypes = [vp, vp, vp]
         L.rbl_ensemble_solve_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, vp, vp]
         L.rbl_ensemble_step_mixed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp]
+        L.rbl_ensemble_solve_mixed_dof.argtypes = L.rbl_ensemble_solve_mixed.argtypes
+        L.rbl_ensemble_step_mixed_dof.argtypes = L.rbl_ensemble_step_mixed.argtypes
         L.rbl_ensemble_step_brownian_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, dbl, C.c_int, dbl, vp, vp, vp]
         L.rbl_ensemble_run.argtypes = [vp, C.POINTER(RunOpts), C.POINTER(RunOut)]
         L.rbl_velocity_field.argtypes = [vp, vp, i64, vp, vp, i64, vp]
@@ -131,7 +133,7 @@ class RunOpts(C.Structure):
     """rbl_run_opts (include/rbl.h section 5)"""
     _fields_ = [("size", C.c_int64), ("n_steps", C.c_int32), ("brownian", C.c_int32), ("split_rand", C.c_int32),
                 ("max_iter", C.c_int32), ("stride", C.c_int32), ("on_error", C.c_int32), ("check_every", C.c_int32),
-                ("reserved", C.c_int32), ("seed", C.c_uint64), ("delta", C.c_double), ("rtol", C.c_double),
+                ("prescribed_per", C.c_int32), ("seed", C.c_uint64), ("delta", C.c_double), ("rtol", C.c_double),
                 ("F_body", C.c_void_p), ("prescribed", C.c_void_p), ("body_in", C.c_void_p), ("slip", C.c_void_p)]
 
 
@@ -514,16 +516,24 @@ class DeviceContext:
         self._chk(self.L.rbl_ensemble_interaction_forces(self.h, FT.ctypes.data, E.ctypes.data))
         return FT, E
 
-    def _ens_mixed_args(self, who, prescribed, body_in, slip):
-        """mask (R, N_bod) uint8 -- (N_bod,) is broadcast over the replicas --, body_in (R, 6 N_bod), slip (R, n3) or None"""
+    def _ens_mixed_args(self, who, prescribed, body_in, slip, per=1):
+        """mask (R, N_bod) uint8 -- (N_bod,) is broadcast over the replicas --, body_in (R, 6 N_bod), slip (R, n3) or None.
+        per=6: a mask per velocity component, (R, 6 N_bod) from (N_bod, 6) or (R, N_bod, 6)"""
         import numpy as np
         R, nb = self.ensemble_info()
         m = np.asarray(prescribed)
-        if m.size == nb:
-            m = np.broadcast_to(m.reshape(1, nb), (R, nb))
-        if m.size != R * nb:
-            raise ValueError("%s: prescribed must have shape (%d,) or (%d, %d); got %s" % (who, nb, R, nb, m.shape))
-        m = np.ascontiguousarray(m.reshape(R, nb), dtype=np.uint8)
+        if per == 6:
+            if m.shape == (nb, 6):
+                m = np.broadcast_to(m.reshape(1, nb, 6), (R, nb, 6))
+            if m.shape != (R, nb, 6):
+                raise ValueError("%s: prescribed6 must have shape (%d, 6) or (%d, %d, 6); got %s" % (who, nb, R, nb, m.shape))
+            m = np.ascontiguousarray(m.reshape(R, 6 * nb), dtype=np.uint8)
+        else:
+            if m.size == nb:
+                m = np.broadcast_to(m.reshape(1, nb), (R, nb))
+            if m.size != R * nb:
+                raise ValueError("%s: prescribed must have shape (%d,) or (%d, %d); got %s" % (who, nb, R, nb, m.shape))
+            m = np.ascontiguousarray(m.reshape(R, nb), dtype=np.uint8)
         bi = self._ens_vec(body_in, 6 * nb, "body_in")
         sl = None if slip is None else self._ens_vec(slip, 3 * nb * self._sizes()[1], "slip")
         return R, nb, m, bi, sl
@@ -551,6 +561,30 @@ class DeviceContext:
                                                  int(max_iter), float(rtol or 0.0), F.ctypes.data, it.ctypes.data, res.ctypes.data))
         return F, it, res
 
+    def ensemble_solve_mixed_dof(self, prescribed6, body_in, max_iter=100, rtol=1.0e-8, slip=None):
+        """solve_mixed_dof at every replica's configuration (nothing moves) -> (lambda (R, n3), U (R, 6 N_bod), F (R, 6 N_bod),
+        iterations[R], residual estimates[R]); prescribed6: 0/1 per velocity component, (N_bod, 6) or (R, N_bod, 6)"""
+        import numpy as np
+        R, nb, m, bi, sl = self._ens_mixed_args("ensemble_solve_mixed_dof", prescribed6, body_in, slip, per=6)
+        n3 = 3 * nb * self._sizes()[1]
+        lam, U, F = np.zeros((R, n3)), np.zeros((R, 6 * nb)), np.zeros((R, 6 * nb))
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(self.L.rbl_ensemble_solve_mixed_dof(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                      int(max_iter), float(rtol or 0.0), lam.ctypes.data, U.ctypes.data, F.ctypes.data,
+                                                      it.ctypes.data, res.ctypes.data))
+        return lam, U, F, it, res
+
+    def ensemble_step_mixed_dof(self, prescribed6, body_in, max_iter=50, rtol=1.0e-8, slip=None):
+        """one deterministic step of every replica with prescribed velocity components -> (F (R, 6 N_bod), iterations[R],
+        residual estimates[R])"""
+        import numpy as np
+        R, nb, m, bi, sl = self._ens_mixed_args("ensemble_step_mixed_dof", prescribed6, body_in, slip, per=6)
+        F = np.zeros((R, 6 * nb))
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(self.L.rbl_ensemble_step_mixed_dof(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                     int(max_iter), float(rtol or 0.0), F.ctypes.data, it.ctypes.data, res.ctypes.data))
+        return F, it, res
+
     def ensemble_step_brownian_mixed(self, prescribed, body_in, W=None, seed=0, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8,
                                      slip=None):
         """one stochastic midpoint step of every replica with prescribed bodies (dense Cholesky root) -> (F (R, 6 N_bod),
@@ -572,11 +606,12 @@ class DeviceContext:
         return F, it, res
 
     def ensemble_run(self, n_steps, F_body=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error=RUN_STOP,
-                     check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8):
+                     check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8, per=1):
         """n_steps steps of every replica in one call (rbl_ensemble_run): the inputs are uploaded once, the verdict, the commit
         and the records are kept per replica on the device -> (RunResult, status): the result is filled for a stopped run too,
         whose status and message it carries; nothing is raised here for such a run (Ensemble.run does).  F_body (6 N_bod,) or
-        (R, 6 N_bod) for free bodies, or prescribed (N_bod,) / (R, N_bod) with body_in; on_error: RUN_STOP or RUN_REJECT"""
+        (R, 6 N_bod) for free bodies, or prescribed (N_bod,) / (R, N_bod) with body_in -- per=6: a mask per velocity component,
+        (N_bod, 6) / (R, N_bod, 6), deterministic runs only --; on_error: RUN_STOP or RUN_REJECT"""
         import numpy as np
         R, nb = self.ensemble_info()
         if R == 0:
@@ -591,7 +626,7 @@ class DeviceContext:
         masked = F_body is None
         sl = None
         if masked:
-            _, _, m, bi, sl = self._ens_mixed_args("ensemble_run", prescribed, body_in, slip)
+            _, _, m, bi, sl = self._ens_mixed_args("ensemble_run", prescribed, body_in, slip, per=per)
         else:
             F = self._ens_vec(F_body, 6 * nb, "F_body")
             sl = None if slip is None else self._ens_vec(slip, 3 * nb * self._sizes()[1], "slip")
@@ -600,6 +635,7 @@ class DeviceContext:
         o.n_steps, o.brownian, o.split_rand, o.max_iter = n_steps, int(bool(brownian)), int(bool(split_rand)), int(max_iter)
         o.stride, o.on_error, o.check_every, o.seed = stride, int(on_error), int(check_every), int(seed)
         o.delta, o.rtol = float(delta), float(rtol or 0.0)
+        o.prescribed_per = int(per)
         o.F_body = None if masked else F.ctypes.data
         o.prescribed = m.ctypes.data if masked else None
         o.body_in = bi.ctypes.data if masked else None

@@ -24,6 +24,8 @@
 // With prescribed bodies (rbl_ensemble_solve_mixed / _step_mixed / _step_brownian_mixed; the semantics of include/rbl.h section 7
 // per replica, the restatement of rbl_mixed.hip's mx_solve / mx_step and of rbl_steps.hip's rhs_and_midpoint_core): a 0/1 mask per
 // body and replica travels with the call, and NULL for it is the unmasked step: ens_step_det and ens_step_bd serve both.
+// The deterministic calls also take a mask per velocity component (rbl_ensemble_solve_mixed_dof / _step_mixed_dof, runs with
+// prescribed_per = 6): the mask goes up as the caller gave it and the solver is told how many entries a body has.
 // The same launches with three differences: k_ens_midpoint is followed by k_ens_midpoint_prescribed (dq = 0 and the predictor
 // (dt/2) U_p on a prescribed body; one more launch, so that a free body goes through the very same code), the solve is the
 // masked k_gmres_small (it adds K_p U_p to the right-hand side with the lever arms of the configuration it solves at, zeroes
@@ -434,7 +436,7 @@ EnsWork ens_carve(void *base, int R, int Nb, int nbl, int max_iter, size_t *byte
   w.Linv = C.take<double>(rbl_cholesky_batched_work_bytes((int64_t)n3, R) / sizeof(double));
   w.dq = C.take<double>(Rz * nb6); w.Xh = C.take<double>(Rz * 3 * Nb); w.Qh = C.take<double>(Rz * 4 * Nb);
   w.rhs = C.take<double>(Rz * nsys);
-  w.mask = C.take<unsigned char>(Rz * Nb);
+  w.mask = C.take<unsigned char>(Rz * nb6);             // room for one entry per velocity component (whole bodies use Rz * Nb of it)
   w.gm = C.take<double>(Rz * rbl_gmres_small_work_doubles(nbl, Nb, max_iter));
   w.e = C.take<double>(Rz * N);
   w.ia = C.take<char>(ia_batch_bytes(Nb, nbl, R));
@@ -549,13 +551,13 @@ int ens_check_solver(rbl_ctx *c, int max_iter)
 // mixed: the masked solve (w.mask, body_in in w.F); the update then reads the U it wrote (a prescribed body: dt U_p exactly).
 // evolve = false: the solve alone
 int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const double *Qs, int max_iter, double rtol, bool mixed = false,
-                     bool evolve = true, bool record = true)
+                     bool evolve = true, bool record = true, int per = 1)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
   const long n3 = 3L * Nb * nbl, nsys = n3 + 6L * Nb;
   const RblParams P = rbl_make_params(c->S.a, c->S.eta);
   int rc = mixed ? rbl_launch_gmres_small_ens_mixed(c->stream, P, c->S.wall, Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.U, max_iter, rtol,
-                                                    w.gm, w.iters, w.resid, w.rerr, w.mask, w.F)
+                                                    w.gm, w.iters, w.resid, w.rerr, w.mask, w.F, per)
                  : rbl_launch_gmres_small_ens(c->stream, P, c->S.wall, Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.x, max_iter, rtol, w.gm,
                                               w.iters, w.resid, w.rerr);
   if (rc) return rbl_fail(c, rc, "ensemble step: the one-kernel solver does not fit this device's LDS");
@@ -574,24 +576,27 @@ int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const doubl
 }
 
 // the checks of the entry points with prescribed bodies: none needs a device
-int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *body_in, int max_iter, double rtol)
+// per: mask entries per body, 1 (whole bodies) or 6 (velocity components, the _dof entry points)
+int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *body_in, int max_iter, double rtol, int per = 1)
 {
   int rc = need_params(c); if (rc) return rc;
   const std::string w(who);
-  if (!prescribed || !body_in) return rbl_fail(c, RBL_ERR_ARG, w + ": prescribed or body_in is NULL");
+  const char *pn = per == 6 ? "prescribed6" : "prescribed";
+  if (!prescribed || !body_in) return rbl_fail(c, RBL_ERR_ARG, w + ": " + pn + " or body_in is NULL");
   if (max_iter < 1 || !(rtol >= 0.0)) return rbl_fail(c, RBL_ERR_ARG, w + ": need max_iter >= 1 and rtol >= 0");
-  if (max_iter > 255)
-    return rbl_fail(c, RBL_ERR_SIZE, "ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)");
-  if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, "ensemble: not on a context with a communicator (run one ensemble per process)");
-  if (!c->ens_R) return ens_fail_state(c);
-  if (c->S.N_blb != c->ens_Nblb) return rbl_fail(c, RBL_ERR_STATE, "ensemble: the structure changed since rbl_ensemble_set_config");
-  const size_t nbod = (size_t)c->ens_R * c->ens_Nb;
-  for (size_t g = 0; g < nbod; ++g)
-    if (prescribed[g] > 1) return rbl_fail(c, RBL_ERR_ARG, w + ": entries of prescribed must be 0 or 1 (replica " + std::to_string(g / c->ens_Nb) + ")");
+  const std::string beyond = w + ": ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)";
+  if (max_iter > 255) return rbl_fail(c, RBL_ERR_SIZE, beyond);
+  if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, w + ": ensemble: not on a context with a communicator (run one ensemble per process)");
+  if (!c->ens_R) return rbl_fail(c, RBL_ERR_STATE, w + ": ensemble: no ensemble configuration (rbl_ensemble_set_config)");
+  if (c->S.N_blb != c->ens_Nblb) return rbl_fail(c, RBL_ERR_STATE, w + ": ensemble: the structure changed since rbl_ensemble_set_config");
+  const size_t nent = (size_t)c->ens_R * c->ens_Nb * (size_t)per;
+  for (size_t g = 0; g < nent; ++g)
+    if (prescribed[g] > 1)
+      return rbl_fail(c, RBL_ERR_ARG, w + ": entries of " + pn + " must be 0 or 1 (replica " + std::to_string(g / ((size_t)c->ens_Nb * per)) + ")");
   if (!rbl_gmres_small_fits(c->S.N_blb, c->ens_Nb, max_iter, false, true))
     return rbl_fail(c, RBL_ERR_SIZE, rbl_gmres_small_fits(c->S.N_blb, c->ens_Nb, max_iter, false)
                                          ? w + ": this shape fits the one-kernel solver without prescribed bodies, but not with the mask's 6 N_bod doubles of LDS"
-                                         : std::string("ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)"));
+                                         : beyond);
   return RBL_OK;
 }
 
@@ -604,10 +609,17 @@ int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const d
 // filled), slip is the run's device copy, W is NULL.  chol_err: the batched Cholesky's error stride (0: the batch word)
 struct EnsStepIn {
   const uint8_t *prescribed = nullptr;
+  int per = 1;                              // entries of prescribed per body: 1 (whole bodies) or 6 (velocity components)
   const double *F_body = nullptr, *slip = nullptr, *W = nullptr;
   bool resident = false;
   int64_t chol_err = 0;
 };
+
+// the mask as the caller gave it: per entries per body (the solver is told which, k_gmres_small's `per`)
+int ens_upload_mask(rbl_ctx *c, const EnsWork &w, const uint8_t *prescribed, int per)
+{
+  return copy_h2d(c, w.mask, prescribed, (size_t)c->ens_R * c->ens_Nb * (size_t)per);
+}
 
 // everything the deterministic step enqueues, from the uploads to the update: the one-step calls and the run share it
 int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_iter, double rtol, bool move)
@@ -615,25 +627,25 @@ int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_i
   const bool mixed = in.prescribed != nullptr;
   const double *FT, *SL;
   int rc;
-  if (mixed && !in.resident && (rc = copy_h2d(c, w.mask, in.prescribed, (size_t)c->ens_R * c->ens_Nb))) return rc;
+  if (mixed && !in.resident && (rc = ens_upload_mask(c, w, in.prescribed, in.per))) return rc;
   if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, move, in.resident))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb;
   const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb;
   const long tot = (long)R * (n3 + nb6);
   hipLaunchKernelGGL(k_ens_rhs_det, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, n3, nb6, SL,
                      (const double *)w.F, FT, w.rhs);
-  return ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, mixed, move, !in.resident);
+  return ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, mixed, move, !in.resident, in.per);
 }
 
 int ens_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, int max_iter, double rtol, bool move,
-                 double *lambda, double *U, double *F, int *iters, double *resid)
+                 double *lambda, double *U, double *F, int *iters, double *resid, int per = 1)
 {
   const bool mixed = prescribed != nullptr;
   EnsWork w;
   int rc;
   if ((rc = ens_work(c, max_iter, &w))) return rc;
   EnsStepIn in;
-  in.prescribed = prescribed; in.F_body = F_body; in.slip = slip;
+  in.prescribed = prescribed; in.per = per; in.F_body = F_body; in.slip = slip;
   if ((rc = ens_enqueue_det(c, w, in, max_iter, rtol, move))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb;
   const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb;
@@ -659,7 +671,7 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
   const RblBodyState &S = c->S;
   const bool mixed = in.prescribed != nullptr;
   int rc;
-  if (mixed && !in.resident && (rc = copy_h2d(c, w.mask, in.prescribed, (size_t)c->ens_R * c->ens_Nb))) return rc;
+  if (mixed && !in.resident && (rc = ens_upload_mask(c, w, in.prescribed, in.per))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = S.N_blb, N = Nb * nbl;
   const int64_t n3 = 3 * (int64_t)N;
   if (in.W) { if ((rc = copy_h2d(c, w.W, in.W, sizeof(double) * 3 * (size_t)n3 * R))) return rc; }
@@ -765,13 +777,14 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, bool brownian, rbl_run_out *out)
   if ((rc = rbl_dev_reserve(c, c->d_ens_run, bytes))) return rc;
   const EnsRunBuf b = ens_run_carve(c->d_ens_run.p, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
   // the uploads, once
-  if (mixed && (rc = copy_h2d(c, w.mask, o.prescribed, Rz * Nb))) return rc;
+  if (mixed && (rc = ens_upload_mask(c, w, o.prescribed, o.prescribed_per == 6 ? 6 : 1))) return rc;
   if ((rc = copy_h2d(c, w.F, mixed ? o.body_in : o.F_body, sizeof(double) * nb6 * Rz))) return rc;
   if (o.slip && (rc = copy_h2d(c, b.slip, o.slip, sizeof(double) * n3 * Rz))) return rc;
   RBL_HIP(c, hipMemsetAsync(b.st, 0, b.rb_bytes, c->stream));
   if (mixed) RBL_HIP(c, hipMemsetAsync(b.F_last, 0, sizeof(double) * nb6 * Rz, c->stream));
   EnsStepIn in;
-  in.prescribed = o.prescribed; in.slip = o.slip ? b.slip : nullptr; in.resident = true; in.chol_err = 1;
+  in.prescribed = o.prescribed; in.per = o.prescribed_per == 6 ? 6 : 1;
+  in.slip = o.slip ? b.slip : nullptr; in.resident = true; in.chol_err = 1;
   EnsRunStatus hs = {0, 0, 0u, 0};
   int enq = 0;
   for (int n = 0; n < o.n_steps; ++n) {
@@ -958,6 +971,28 @@ int rbl_ensemble_step_mixed(rbl_ctx *c, const uint8_t *prescribed, const double 
   return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
 }
 
+// the masks per velocity component (include/rbl.h section 7's _dof semantics, per replica): the whole-body calls with six mask
+// entries per body -- the same checks, the same enqueue sequence, the same kernel
+int rbl_ensemble_solve_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter,
+                                 double rtol, double *lambda, double *U, double *F, int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (!U || !F) return rbl_fail(c, RBL_ERR_ARG, "ensemble_solve_mixed_dof: U or F is NULL");
+  int rc = ens_mx_check(c, "ensemble_solve_mixed_dof", prescribed6, body_in, max_iter, rtol, 6); if (rc) return rc;
+  if ((rc = ens_ready(c))) return rc;
+  return ens_step_det(c, prescribed6, body_in, slip, max_iter, rtol, false, lambda, U, F, iters, resid, 6);
+}
+
+int rbl_ensemble_step_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter,
+                                double rtol, double *F, int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  int rc = ens_mx_check(c, "ensemble_step_mixed_dof", prescribed6, body_in, max_iter, rtol, 6); if (rc) return rc;
+  if ((rc = ens_flow_check(c))) return rc;
+  if ((rc = ens_ready(c))) return rc;
+  return ens_step_det(c, prescribed6, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid, 6);
+}
+
 int rbl_ensemble_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
                                      uint64_t seed, int split_rand, double delta, int max_iter, double rtol, double *F, int *iters,
                                      double *resid)
@@ -986,9 +1021,15 @@ int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)
   if (o->check_every < 0) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: check_every must be >= 0");
   if (o->on_error != RBL_RUN_STOP && o->on_error != RBL_RUN_REJECT)
     return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: on_error must be RBL_RUN_STOP (0) or RBL_RUN_REJECT (1)");
+  if (o->prescribed_per != 0 && o->prescribed_per != 1 && o->prescribed_per != 6)
+    return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: prescribed_per must be 0 or 1 (a mask entry per body) or 6 (one per velocity component)");
+  const int per = o->prescribed_per == 6 ? 6 : 1;
   const bool free_run = o->F_body != nullptr, masked = o->prescribed || o->body_in;
   if (free_run == masked)
     return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: give either F_body or prescribed with body_in (both or neither were given)");
+  if (masked && per == 6 && o->brownian && c->S.kBT > 1e-10)   // kBT <= 1e-10 runs the deterministic step, as elsewhere
+    return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: the Brownian step takes whole-body masks only (prescribed_per = 6 with brownian != 0 and "
+                                    "kBT > 1e-10): the drift term of a partly prescribed body has not been derived");
   if (o->max_iter < 1) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: max_iter must be >= 1");
   if (!(o->rtol >= 0.0)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: rtol must be >= 0");
   const size_t n_frames = o->stride > 0 ? (size_t)(o->n_steps / o->stride) : 0;
@@ -996,7 +1037,7 @@ int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)
     return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: frame_X, frame_Q, frame_accepted_at (and frame_F with prescribed bodies) must not be NULL while stride > 0 records frames");
   int rc;
   if (masked) {                                        // NULL halves, max_iter > 255, communicator, state, entries, the LDS
-    if ((rc = ens_mx_check(c, "ensemble_run", o->prescribed, o->body_in, o->max_iter, o->rtol))) return rc;
+    if ((rc = ens_mx_check(c, "ensemble_run", o->prescribed, o->body_in, o->max_iter, o->rtol, per))) return rc;
   } else {
     if ((rc = need_params(c))) return rc;
     if (o->max_iter > 255)

@@ -384,12 +384,12 @@ int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const 
 int rbl_launch_gmres_small_ens(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
                                int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter, double rtol,
                                double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err);
-// the same with a 0/1 mask per body and replica (include/rbl.h section 7's system): d_rhs is the all-free right-hand side
+// the same with a 0/1 mask per body (per = 1) or per velocity component (per = 6) and replica (include/rbl.h section 7's system): d_rhs is the all-free right-hand side
 // [slip ; -body_in]; the launch adds K_p U_p, solves and splits.  d_UFx: ONE block [U reps x 6 N_bod | F reps x 6 N_bod | x reps x nsys]
 int rbl_launch_gmres_small_ens_mixed(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ,
                                      const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_UFx, int max_iter,
                                      double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err,
-                                     const unsigned char *d_mask, const double *d_body_in);
+                                     const unsigned char *d_mask, const double *d_body_in, int per);
 
 // per-body geometric operators on the device (rbl_body_dev.hip)
 void rbl_launch_body_geom(hipStream_t st, const double *dX, const double *dQ, const double *dcfg,

@@ -20,10 +20,12 @@
 //
 // MIXED (the ensembles with prescribed bodies, include/rbl.h sections 5 and 7): the same solve of
 //   [M lambda - K (D_f U) ; D_f K^T lambda + D_p U] = [slip + K_p U_p ; -F_f | 0]
-// with the replica's 0/1 mask per body.  ONE launch assembles the right-hand side, solves and splits: it takes the all-free
-// right-hand side [slip ; -body_in], adds K_p U_p with the lever arms it has just made and zeroes the bottom of the prescribed
-// bodies (k_mx_rhs of rbl_mixed.hip, given a mask per body); the operator and the preconditioner treat the six slots of a
-// prescribed body as k_mx_op_tail / k_mx_pc_diag do, by selects on values outside the pair sweep; the end is k_mx_split's: U, F per body, the
+// with the replica's 0/1 mask per velocity component (six per body, lab frame; a whole body: none or all six set -- `per` says
+// whether the mask holds one entry per body or six, and is read once, where the flags are filled).  ONE launch assembles the right-hand side, solves and splits: it takes the all-free
+// right-hand side [slip ; -body_in], adds K (D_p U_in) with the lever arms it has just made and zeroes the bottom of the prescribed
+// components (k_mx_rhs of rbl_mixed.hip); the operator and the preconditioner treat a prescribed slot as k_mx_op_tail /
+// k_mx_pc_diag do, by selects on values outside the pair sweep, the 6 x 6 block of a partly prescribed body being factored with
+// the identity's rows and columns on its prescribed components (k_mx_factors); the end is k_mx_split's: U, F per component, the
 // K^T sums in blob order.  A free body's arithmetic and its order are those of the unmasked kernel, so with nobody prescribed the
 // solution and the iteration count are bitwise the unmasked ones.  The four unmasked instantiations keep their code (every
 // masked statement is behind `if constexpr (MIXED)`, the extra arguments exist in the masked ones only): 111-128 VGPRs, no
@@ -63,9 +65,10 @@ struct SmallArgs {
 // [U of every replica | F of every replica | x of every replica]: their addresses follow from x and the grid, and no pointer of
 // theirs has to stay in registers across the pair sweep (WALL sits at the 128-register ceiling of a 1024-thread workgroup).
 struct SmallArgsMixed : SmallArgs {
-  const unsigned char *mask;       // N_bod per replica: 1 = prescribed
-  const double *body_in;           // 6 N_bod per replica: U_b of a prescribed body (a free body's load is in rhs already)
+  const unsigned char *mask;       // per N_bod per replica: 1 = prescribed -- the body (per = 1) or this velocity component of it (per = 6)
+  const double *body_in;           // 6 N_bod per replica: U of a prescribed component (a free component's load is in rhs already)
   int reps;                        // the grid
+  int per;                         // mask entries per body: 1 or 6 (read in the prologue only: the flags in LDS serve afterwards)
 };
 
 // sum over the wavefront, result in every lane, fixed order.  Inside the 16-lane rows by DPP moves (quad_perm, half-row
@@ -108,14 +111,14 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(std::conditional_t<MIXED, S
     A.V += (size_t)rep * A.work_stride; A.H += (size_t)rep * A.work_stride;
     A.iters_out += rep; A.resid_out += rep; A.err += (size_t)rep * A.err_stride;
     if constexpr (MIXED) {
-      A.mask += (size_t)rep * nb; A.body_in += (size_t)rep * nb6;
+      A.mask += (size_t)rep * nb * A.per; A.body_in += (size_t)rep * nb6;
     }
   }
   double *pos = sm;                             // 3N  positions / a
   double *lev = pos + n3;                       // 3N  lever arms
   double *iM = lev + n3;                        // 2N  diag_invM: (xx = yy, zz)
   double *dmp = iM + 2 * N;                     // N   wall damping d_i (1 without the wall term)
-  // MIXED: the mask lives in LDS as a seventh entry of every row of NLs (1.0: the row's body is prescribed), where the thread of a
+  // MIXED: the mask lives in LDS as a seventh entry of every row of NLs (1.0: the row's velocity component is prescribed), where the thread of a
   // body slot reads its row anyway: the flag costs no register and no address across the pair sweep
   constexpr int NS = MIXED ? 42 : 36, RS = MIXED ? 7 : 6;
   double *NLs = dmp + N;                        // NS Nb  (K^T invM K)^-1, row-major 6x6 per body (rows of RS)
@@ -192,6 +195,21 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(std::conditional_t<MIXED, S
     int q = 0;
     for (int r = 0; r < 6; ++r)
       for (int c = 0; c <= r; ++c) { L[6 * r + c] = acc[q]; if (c < r) L[6 * c + r] = 0.0; ++q; }
+    if constexpr (MIXED) {
+      // the flags (the seventh entry of every row of NLs; the inverse below writes the first six), from one mask entry per body
+      // or six.  A partly prescribed body: the rows and columns of its prescribed components become the identity's BEFORE the
+      // factorisation (k_mx_factors' rule: a principal submatrix's factor is no sub-block of the full one); the selects leave
+      // a body with no bit set its matrix, factor and inverse bit for bit.  The inverse then has the identity's rows and columns
+      // there too, so apply_PC's 6x6 product takes nothing from a prescribed slot into a free one
+      unsigned pm = 0;                         // bit p = component p of this body is prescribed
+      for (int p = 0; p < 6; ++p) pm |= (A.mask[A.per == 6 ? 6 * t + p : t] ? 1u : 0u) << p;
+      for (int p = 0; p < 6; ++p) NLs[NS * t + RS * p + 6] = (pm >> p & 1u) ? 1.0 : 0.0;
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c <= r; ++c) {
+          const bool cut = ((pm >> r) | (pm >> c)) & 1u;
+          L[6 * r + c] = cut ? (r == c ? 1.0 : 0.0) : L[6 * r + c];
+        }
+    }
     bool ok = true;
     for (int j = 0; j < 6; ++j) {
       double dd = L[6 * j + j];
@@ -222,10 +240,6 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(std::conditional_t<MIXED, S
       }
       for (int p = 0; p < 6; ++p) NLs[NS * t + RS * p + col] = u[p];
     }
-    if constexpr (MIXED) {
-      const double pres = A.mask[t] ? 1.0 : 0.0;
-      for (int p = 0; p < 6; ++p) NLs[NS * t + RS * p + 6] = pres;
-    }
   }
   __syncthreads();
 
@@ -254,7 +268,7 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(std::conditional_t<MIXED, S
       double u = 0.0;
 #pragma unroll
       for (int d = 0; d < 6; ++d) u = __builtin_fma(Nm[d], rh[d], u);
-      if constexpr (MIXED) u = Nm[6] != 0.0 ? in[n3 + t] : u;   // a prescribed body's six slots pass through
+      if constexpr (MIXED) u = Nm[6] != 0.0 ? in[n3 + t] : u;   // a prescribed component's slot passes through
       out[n3 + t] = u;
     }
     __syncthreads();
@@ -262,14 +276,14 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(std::conditional_t<MIXED, S
       const int b = t / nbl;
       const double *u = out + n3 + 6 * b;
       const double l0 = lev[3 * t], l1 = lev[3 * t + 1], l2 = lev[3 * t + 2];
-      out[3 * t] = iM[2 * t] * (in[3 * t] + u[0] + l2 * u[4] - l1 * u[5]);       // MIXED, prescribed body: u = 0 (see apply_A),
+      out[3 * t] = iM[2 * t] * (in[3 * t] + u[0] + l2 * u[4] - l1 * u[5]);       // MIXED, all six prescribed: u = 0 (see apply_A),
       out[3 * t + 1] = iM[2 * t] * (in[3 * t + 1] + u[1] + l0 * u[5] - l2 * u[3]);   // so this is lambda = invM slip
       out[3 * t + 2] = iM[2 * t + 1] * (in[3 * t + 2] + u[2] + l1 * u[3] - l0 * u[4]);
     }
     __syncthreads();
   };
 
-  // MIXED: [M lambda - K (D_f U) ; D_f K^T lambda + D_p U].  The six slots of a prescribed body are 0 in the right-hand side, this
+  // MIXED: [M lambda - K (D_f U) ; D_f K^T lambda + D_p U].  The slots of prescribed components are 0 in the right-hand side, this
   // operator is the identity on them and apply_PC passes them through, so they are exactly 0 in every vector either is applied to
   // (cold start only): K U of such a body is exactly 0 and its rows need no select -- the two selects are on the body slots.
   // out = [M lambda - K U ; K^T lambda]   (src/Rigid.py:73-80; M = B Mob B with the wall term, :641-659): self blocks here,
@@ -302,7 +316,7 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(std::conditional_t<MIXED, S
       const double *p = kt + (size_t)c * N + (size_t)b * nbl;
       double f = 0.0;
       for (int k = 0; k < nbl; ++k) f += p[k];
-      if constexpr (MIXED) f = NLs[NS * b + RS * c + 6] != 0.0 ? in[n3 + t] : f;   // D_p U: the identity on a prescribed body's six slots
+      if constexpr (MIXED) f = NLs[NS * b + RS * c + 6] != 0.0 ? in[n3 + t] : f;   // D_p U: the identity on a prescribed component's slot
       out[n3 + t] = f;
     }
     __syncthreads();
@@ -328,11 +342,15 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(std::conditional_t<MIXED, S
       for (int i = t; i < nsys; i += SGT) vw[i] = A.rhs[i];
     } else for (int i = t; i < nsys; i += SGT) {
       double v = A.rhs[i];
-      {                                      // top += K_p U_p (the lever arms of this configuration), bottom = 0 on prescribed bodies
+      {                                      // top += K (D_p U_in) (the lever arms of this configuration), bottom = 0 on prescribed components
         if (i < n3) {
           const int bl = i / 3, c = i - 3 * bl, b = bl / nbl;
-          if (A.mask[b]) {
-            const double *u = A.body_in + 6 * b;
+          const double *fl = NLs + NS * b + 6;         // the six flags of the body (filled above)
+          bool any = false;
+          for (int p = 0; p < 6; ++p) any = any || fl[RS * p] != 0.0;
+          if (any) {                               // K (D_p U_in): the prescribed components only; all six: the whole-body sum
+            double u[6];
+            for (int p = 0; p < 6; ++p) u[p] = fl[RS * p] != 0.0 ? A.body_in[6 * b + p] : 0.0;
             const double l0 = lev[3 * bl], l1 = lev[3 * bl + 1], l2 = lev[3 * bl + 2];
             v += c == 0 ? u[0] + l2 * u[4] - l1 * u[5] : c == 1 ? u[1] + l0 * u[5] - l2 * u[3] : u[2] + l1 * u[3] - l0 * u[4];
           }
@@ -342,7 +360,7 @@ __global__ __launch_bounds__(SGT) void k_gmres_small(std::conditional_t<MIXED, S
           // same two addresses -- change the layout there and in both places here together
           double *Uo = A.x - (size_t)blockIdx.x * nsys - 2 * (size_t)A.reps * nb6 + (size_t)blockIdx.x * nb6, *Fo = Uo + (size_t)A.reps * nb6;
           const int j = i - n3;
-          if (A.mask[j / 6]) { v = 0.0; Uo[j] = A.body_in[j]; }
+          if (NLs[NS * (j / 6) + RS * (j % 6) + 6] != 0.0) { v = 0.0; Uo[j] = A.body_in[j]; }
           else Fo[j] = -v;
         }
       }
@@ -622,15 +640,16 @@ int rbl_launch_gmres_small_ens(hipStream_t st, const RblParams &P, bool wall, co
 }
 
 // the masked solve (MIXED above) of every replica: d_rhs is the all-free right-hand side [slip ; -body_in] (the loads of the free
-// bodies), d_mask reps x N_bod bytes, d_body_in reps x 6 N_bod (the prescribed bodies' velocities are read); d_UFx is ONE block
+// components), d_mask reps x per N_bod bytes (per = 1: one per body, 6: one per velocity component), d_body_in reps x 6 N_bod (the prescribed components'
+// velocities are read); d_UFx is ONE block
 // [U: reps x 6 N_bod | F: reps x 6 N_bod | x: reps x nsys]
 int rbl_launch_gmres_small_ens_mixed(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ,
                                      const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_UFx, int max_iter,
                                      double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err,
-                                     const unsigned char *d_mask, const double *d_body_in)
+                                     const unsigned char *d_mask, const double *d_body_in, int per)
 {
   SmallArgsMixed A = {};
-  A.mask = d_mask; A.body_in = d_body_in; A.reps = reps;
+  A.mask = d_mask; A.body_in = d_body_in; A.reps = reps; A.per = per;
   return launch_small<true>(st, P, wall, dX, dQ, dcfg, N_blb, N_bod, d_rhs, nullptr, d_UFx + (size_t)2 * reps * 6 * N_bod, max_iter, rtol,
                             1.0, d_work, d_iters, d_resid, d_rep_err, reps, 1, A);
 }

@@ -156,14 +156,45 @@ class Ensemble:
         return self.ctx.ensemble_step_brownian_mixed(m, b, W=W, seed=seed, split_rand=split_rand, delta=delta, max_iter=max_iter,
                                                      rtol=rtol, slip=s)
 
+    # ------------------------------------------------------------------ prescribed velocity components (the _dof entry points)
+    def _prescribed_dof_mask(self, prescribed):
+        """as RigidBody.solve_mixed_dof reads it: a boolean array (N_bod, 6) -- translation x, y, z, then rotation x, y, z in the lab
+        frame; broadcast over the replicas -- or (R, N_bod, 6) -> uint8 (R, N_bod, 6); ValueError before the library is called.
+        Nothing else is read: with R = N_bod = 6 a whole-body mask (R, N_bod) has the shape of (N_bod, 6), hence the separate
+        methods and keyword"""
+        p = np.asarray(prescribed)
+        R, nb = self.R, self.N_bodies
+        if p.dtype != np.bool_:
+            _fail("prescribed (per component) must be a boolean array; got dtype %s" % p.dtype)
+        if p.shape == (nb, 6):
+            p = np.broadcast_to(p, (R, nb, 6))
+        if p.shape != (R, nb, 6):
+            _fail("prescribed (per component) must have shape (%d, 6) or (%d, %d, 6); got %s" % (nb, R, nb, p.shape))
+        return np.ascontiguousarray(p, dtype=np.uint8)
+
+    def solve_mixed_dof(self, prescribed, body_in, slip=None, max_iter=100, rtol=1e-8):
+        """RigidBody.solve_mixed_dof at every replica's configuration; nothing moves.  prescribed: bool (N_bod, 6) or
+        (R, N_bod, 6); a prescribed component moves with its entry of body_in, a free one carries its load there.
+        -> (lambda (R, n3), U (R, 6 N_bod), F (R, 6 N_bod), iterations (R,), residual estimates (R,))"""
+        m, b, s = self._prescribed_dof_mask(prescribed), self._body_in(body_in), self._slip(slip)
+        return self.ctx.ensemble_solve_mixed_dof(m, b, max_iter=max_iter, rtol=rtol, slip=s)
+
+    def step_mixed_dof(self, prescribed, body_in, slip=None, max_iter=50, rtol=1e-8):
+        """one deterministic step of every replica with prescribed velocity components -> (F (R, 6 N_bod), iterations (R,),
+        residual estimates (R,)): a body with its three translations held keeps X exactly while it turns; the force model loads
+        the free components only, so F of a prescribed component is the total load along it"""
+        m, b, s = self._prescribed_dof_mask(prescribed), self._body_in(body_in), self._slip(slip)
+        return self.ctx.ensemble_step_mixed_dof(m, b, max_iter=max_iter, rtol=rtol, slip=s)
+
     # ------------------------------------------------------------------ a run of steps (include/rbl.h section 5, rbl_ensemble_run)
     def run(self, n_steps, F=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error="stop",
-            check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1e-4, max_iter=50, rtol=1e-8):
+            check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1e-4, max_iter=50, rtol=1e-8, prescribed_dof=None):
         """n_steps steps of every replica in ONE call: the inputs go to the device once, each step's verdict and commit are taken
         per replica on the device, one read-back ends the run -> RunResult (accepted, rejected, first_status, iters_sum, resid_max,
         F_mean for runs with prescribed bodies, steps_done, stopped_at, and with stride > 0 the frames X, Q, accepted_at, F after
         every stride-th step).  F as step_brownian takes it, or prescribed with body_in as step_brownian_mixed; step n draws its
-        noise from seed + n; brownian=False: deterministic steps.
+        noise from seed + n; brownian=False: deterministic steps.  prescribed_dof with body_in (instead of F or prescribed): a mask
+        per velocity component as step_mixed_dof takes it, deterministic steps only (a Brownian run at kBT > 0 is refused).
         on_error="stop": the first failing step commits nothing, nor does any later one; RblError is raised as the step methods
         raise it, the partial result stays on self.last_run.  on_error="reject": a failing replica keeps its configuration and
         tries again with the next step's noise (the customary redraw, not an unbiased one: see rejected), the others go on; the
@@ -177,20 +208,29 @@ class Ensemble:
             _fail("n_steps must be >= 1; got %d" % n_steps)
         if stride < 0 or check_every < 0:
             _fail("stride and check_every must be >= 0; got %d and %d" % (stride, check_every))
-        if (F is None) == (prescribed is None and body_in is None):
-            _fail("give either F or prescribed with body_in")
-        if F is None and (prescribed is None or body_in is None):
-            _fail("prescribed and body_in go together")
+        if prescribed_dof is not None and (F is not None or prescribed is not None):
+            _fail("prescribed_dof excludes F and prescribed")
+        per = 6 if prescribed_dof is not None else 1
+        if per == 6:
+            if body_in is None:
+                _fail("prescribed_dof and body_in go together")
+        else:
+            if (F is None) == (prescribed is None and body_in is None):
+                _fail("give either F or prescribed with body_in")
+            if F is None and (prescribed is None or body_in is None):
+                _fail("prescribed and body_in go together")
         m = b = None
         if F is not None:
             F = self._forces(F)
+        elif per == 6:
+            m, b = self._prescribed_dof_mask(prescribed_dof), self._body_in(body_in)
         else:
             m, b = self._prescribed_mask(prescribed), self._body_in(body_in)
         s = self._slip(slip)
         self.last_run = None
         res, rc = self.ctx.ensemble_run(n_steps, F_body=F, prescribed=m, body_in=b, brownian=brownian, seed=seed, stride=stride,
                                         on_error=modes[on_error], check_every=check_every, slip=s, split_rand=split_rand,
-                                        delta=delta, max_iter=max_iter, rtol=rtol)
+                                        delta=delta, max_iter=max_iter, rtol=rtol, per=per)
         self.last_run = res
         if rc != 0:
             raise RblError(res.error)

@@ -390,7 +390,7 @@ class RigidBody:
         lab-frame components (translation x, y, z, then rotation x, y, z, the order of body_in).  A prescribed component moves with
         the velocity in its slot of body_in (zero holds it), a free one carries its load there: a microroller has its rotation
         prescribed and its translation free, a trapped particle the reverse, a quasi-2D suspension only U_z = 0.  The solver is
-        solve_mixed's (the cost has not been measured yet), and with whole rows set the results are solve_mixed's.  -> (lambda, U, F, iterations, residual estimate): U
+        solve_mixed's (1.00-1.05 of its time per iteration at cfg 2 and cfg 3: profiles/prescribed_dof.jsonl), and with whole rows set the results are solve_mixed's.  -> (lambda, U, F, iterations, residual estimate): U
         with the prescribed components echoed, F with the free components echoed and -K^T lambda on the prescribed ones (the force
         or torque along that component that it takes)."""
         mask, bi, sl = self._mixed_dof_args(prescribed, body_in, slip)
