@@ -537,16 +537,37 @@ int rbl_option_key(const char *name);
  *                   continued by its tangent below r = 2a (bounded force; coincident blobs, r = 0, exert none); pairs
  *                   with r > r_cut are skipped.  Pairs inside one rigid body are left out (their central forces sum to
  *                   zero force and torque on the body).
- * Body force / torque about the body centre = K^T f_blob.  The evaluation is deterministic (ordered pairs, no atomics): the
- * same configuration gives bitwise the same forces on every call and every rank (multi-GPU contexts evaluate the whole
- * model, replicated).
+ * Three further terms, each with its own switch (none changes anything while it is off); they add to the ones above:
+ *   pair table      between blobs of DIFFERENT bodies: a radial potential given by its values U[k] and derivatives dU[k] =
+ *                   dU/dr on the uniform grid r_k = r_min + k h, h = (r_cut - r_min) / (n - 1), 0 <= r_min < r_cut,
+ *                   2 <= n <= 65537.  Inside the grid U is the cubic Hermite interpolant of (U, dU) and the force is the exact
+ *                   derivative of that interpolant: with D_k = h dU_k and t = (r - r_k) / h in [0, 1],
+ *                     c0 = U_k, c1 = D_k, c2 = 3 (U_{k+1} - U_k) - 2 D_k - D_{k+1}, c3 = 2 (U_k - U_{k+1}) + D_k + D_{k+1},
+ *                     U = c0 + t (c1 + t (c2 + t c3)),   dU/dr = (c1 + t (2 c2 + 3 c3 t)) / h
+ *                   (energy and force consistent by construction, the force continuous; the interval index is clamped to
+ *                   [0, n - 2]).  Below r_min the potential continues along its tangent at r_min (the constant force -dU_0;
+ *                   coincident blobs, r = 0, exert none, as in the steric term); pairs with r > r_cut are skipped.  The
+ *                   table is NOT shifted: U(r_cut) != 0 is a jump in the energy (the force stays finite; tabulate a shifted
+ *                   potential where the energy matters).  It adds to the steric term, each with its own cutoff; the
+ *                   neighbour cull uses the larger cutoff of the pair terms that are on;
+ *   height table    the same construction in the blob height z over (h_min, h_cut), any finite h_min < h_cut: tangent
+ *                   continued below h_min, nothing above h_cut; applied WITH OR WITHOUT the wall of the mobility (a soft
+ *                   confinement in free space), beside the wall repulsion;
+ *   traps           on the body centres: stiffness k (3 lab-frame components per body, 0: no trap along that axis) and
+ *                   centre X0 (3 per body), E = 1/2 sum_c k_c (X_c - X0_c)^2, force -k_c (X_c - X0_c), no torque.  The
+ *                   traps enter the BODY forces and the energy; the blob-level array f_blob does not contain them.
+ *                   n_bodies must be N_bod when the model is evaluated; in an ensemble (section 5) N_bod entries shared by
+ *                   every replica or R N_bod entries, replica-major (anything else at evaluation time: RBL_ERR_STATE).
+ * Body force / torque about the body centre = K^T f_blob (+ the traps).  The evaluation is deterministic (ordered pairs, no
+ * atomics): the same configuration gives bitwise the same forces on every call and every rank (multi-GPU contexts evaluate
+ * the whole model, replicated).
  *
- * rbl_set_interactions: on = 0 switches the model off (the steps are then exactly what they are without it).  Needs
- * rbl_set_parameters first (RBL_ERR_STATE); b_wall, b_blob > 0, eps_wall, eps_blob >= 0, 2a <= r_cut, all finite, or
+ * rbl_set_interactions: on = 0 switches the built-in terms off (with every term off the steps are exactly what they are
+ * without a model).  Needs rbl_set_parameters first (RBL_ERR_STATE); b_wall, b_blob > 0, eps_wall, eps_blob >= 0, 2a <= r_cut, all finite, or
  * RBL_ERR_ARG and the previous model stays in place.  rbl_get_interactions returns it (params: w, eps_wall, b_wall,
  * eps_blob, b_blob, r_cut; either pointer may be NULL).
  *
- * Inside rbl_step_deterministic and rbl_step_brownian, with the model on, its forces at q^n (the configuration the step
+ * Inside rbl_step_deterministic and rbl_step_brownian, with any term on, the model's forces at q^n (the configuration the step
  * starts from -- for the Brownian step the one RHS_and_Midpoint is called on, reference c_rigid_obj.cpp:917-976) are added
  * to the caller's F_body in the REFERENCE convention before the right-hand side [slip; -F_body] is formed:
  * U = -N F_body, so physical forces enter as F_body - K^T f_phys.  No lower-level entry point (rbl_RHS_and_Midpoint_dev,
@@ -560,10 +581,24 @@ int rbl_option_key(const char *name);
 int rbl_set_interactions(rbl_ctx *ctx, double w, double eps_wall, double b_wall, double eps_blob, double b_blob,
                          double r_cut, int on);
 int rbl_get_interactions(const rbl_ctx *ctx, double *params6, int *on);
+/* The tabulated terms and the traps (host arrays, copied; the coefficients are built once here).  Invalid arguments return
+ * RBL_ERR_ARG and leave the previous table / traps in place.  on = 0 stores the arguments and switches the term off; U = dU =
+ * NULL (k = X0 = NULL) with on = 0 only switches it off.  rbl_set_parameters is not needed first.  The getters take NULL for
+ * what is not wanted; coef: 4 (n - 1) doubles (c0 c1 c2 c3 per interval), k3 / X0: 3 n_bodies each; n = 0: never set.
+ * rbl_get_interactions keeps reporting the built-in term only; rbl_interactions_active: bit 0 built-in term, bit 1 pair
+ * table, bit 2 height table, bit 3 traps.  The steps, the queries below and the ensembles evaluate every term that is on. */
+int rbl_set_pair_table(rbl_ctx *ctx, const double *U, const double *dU, int n, double r_min, double r_cut, int on);
+int rbl_get_pair_table(const rbl_ctx *ctx, int *n, double *r_min, double *r_cut, int *on, double *coef);
+int rbl_set_height_table(rbl_ctx *ctx, const double *U, const double *dU, int n, double h_min, double h_cut, int on);
+int rbl_get_height_table(const rbl_ctx *ctx, int *n, double *h_min, double *h_cut, int *on, double *coef);
+int rbl_set_traps(rbl_ctx *ctx, const double *k3, const double *X0, int n_bodies, int on);
+int rbl_get_traps(const rbl_ctx *ctx, int *n_bodies, int *on, double *k3, double *X0);
+int rbl_interactions_active(const rbl_ctx *ctx, int *mask);
 int rbl_interaction_forces_dev(rbl_ctx *ctx, double *d_f_blob, double *d_FT_body, double *energy);
 int rbl_interaction_forces(rbl_ctx *ctx, double *f_blob, double *FT_body, double *energy);
 /* what the last evaluation walked (reporting, tools/bench_interactions.py): candidate (ordered) body pairs in the neighbour
- * lists and ordered blob pairs inside r_cut; synchronises the stream */
+ * lists and ordered blob pairs inside the cutoff of a pair term that is on (a pair inside both counts once); synchronises the
+ * stream */
 int rbl_interaction_stats(rbl_ctx *ctx, int64_t *body_pairs, int64_t *blob_pairs);
 
 /* ===================================================================== */

@@ -83,6 +83,12 @@ def lib():
         L.rbl_get_timings.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
         L.rbl_set_interactions.argtypes = [vp, dbl, dbl, dbl, dbl, dbl, dbl, C.c_int]
         L.rbl_get_interactions.argtypes = [vp, C.POINTER(dbl), C.POINTER(C.c_int)]
+        L.rbl_set_pair_table.argtypes = L.rbl_set_height_table.argtypes = [vp, vp, vp, C.c_int, dbl, dbl, C.c_int]
+        L.rbl_get_pair_table.argtypes = L.rbl_get_height_table.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(dbl), C.POINTER(dbl),
+                                                                           C.POINTER(C.c_int), vp]
+        L.rbl_set_traps.argtypes = [vp, vp, vp, C.c_int, C.c_int]
+        L.rbl_get_traps.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp]
+        L.rbl_interactions_active.argtypes = [vp, C.POINTER(C.c_int)]
         L.rbl_interaction_forces_dev.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_forces.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
@@ -127,6 +133,24 @@ def lib():
 
 class RblError(RuntimeError):
     pass
+
+
+def tabulate(U, dU, lo, hi, n):
+    """values of the callables U(x) and dU(x) = dU/dx on the uniform grid lo + k (hi - lo) / (n - 1), k = 0 .. n - 1: the two
+    arrays set_pair_table / set_height_table take"""
+    import numpy as np
+    x = np.linspace(float(lo), float(hi), int(n))
+    return (np.ascontiguousarray(np.broadcast_to(np.asarray(U(x), dtype=np.float64), x.shape)),
+            np.ascontiguousarray(np.broadcast_to(np.asarray(dU(x), dtype=np.float64), x.shape)))
+
+
+def table_arrays(who, U, dU):
+    """the checks a table's arrays can fail before the library is called -> contiguous float64 U, dU"""
+    import numpy as np
+    U, dU = np.ascontiguousarray(U, dtype=np.float64), np.ascontiguousarray(dU, dtype=np.float64)
+    if U.ndim != 1 or U.shape != dU.shape:
+        raise ValueError("%s: U and dU must be one-dimensional and of one length; got %s and %s" % (who, U.shape, dU.shape))
+    return U, dU
 
 
 class RunOpts(C.Structure):
@@ -325,9 +349,69 @@ class DeviceContext:
         return dict(zip(("w", "eps_wall", "b_wall", "eps_blob", "b_blob", "r_cut"), list(v)), on=bool(on.value), a=self._a)
 
     def interactions_on(self):
-        on = C.c_int(0)
-        self._chk(self.L.rbl_get_interactions(self.h, None, C.byref(on)))
-        return bool(on.value)
+        """any term of the model is on: the built-in one, a pair table, a height table or the traps"""
+        return self.interactions_active() != 0
+
+    def interactions_active(self):
+        """bit 0 built-in terms, bit 1 pair table, bit 2 height table, bit 3 traps"""
+        m = C.c_int(0)
+        self._chk(self.L.rbl_interactions_active(self.h, C.byref(m)))
+        return m.value
+
+    def set_pair_table(self, U, dU, r_min, r_cut, on=True):
+        """a radial potential between blobs of different bodies from its values U and derivatives dU = dU/dr on the uniform grid
+        r_min .. r_cut (see `tabulate`): cubic Hermite inside, the tangent at r_min below it, nothing beyond r_cut (the table is
+        not shifted: U(r_cut) != 0 is a jump in the energy).  Adds to the built-in steric term.  on=False stores it switched off; U = dU = None
+        with on=False only switches the stored table off."""
+        if U is None and dU is None and not on:       # only the switch: the stored table stays
+            return self._chk(self.L.rbl_set_pair_table(self.h, None, None, 0, 0.0, 0.0, 0))
+        U, dU = table_arrays("set_pair_table", U, dU)
+        self._chk(self.L.rbl_set_pair_table(self.h, U.ctypes.data, dU.ctypes.data, U.size, float(r_min), float(r_cut), int(bool(on))))
+
+    def set_height_table(self, U, dU, h_min, h_cut, on=True):
+        """the same construction in the blob height z over h_min .. h_cut, with or without the wall"""
+        if U is None and dU is None and not on:
+            return self._chk(self.L.rbl_set_height_table(self.h, None, None, 0, 0.0, 0.0, 0))
+        U, dU = table_arrays("set_height_table", U, dU)
+        self._chk(self.L.rbl_set_height_table(self.h, U.ctypes.data, dU.ctypes.data, U.size, float(h_min), float(h_cut), int(bool(on))))
+
+    def _get_table(self, fn):
+        import numpy as np
+        n, lo, hi, on = C.c_int(0), C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+        self._chk(fn(self.h, C.byref(n), C.byref(lo), C.byref(hi), C.byref(on), None))
+        coef = np.zeros((max(n.value - 1, 0), 4))
+        if n.value:
+            self._chk(fn(self.h, None, None, None, None, coef.ctypes.data))
+        return dict(n=n.value, lo=lo.value, hi=hi.value, on=bool(on.value), coef=coef)
+
+    def pair_table(self):
+        """{n, lo, hi, on, coef (n - 1, 4)} of the pair table (n = 0: never set)"""
+        return self._get_table(self.L.rbl_get_pair_table)
+
+    def height_table(self):
+        return self._get_table(self.L.rbl_get_height_table)
+
+    def set_traps(self, k, X0, on=True):
+        """harmonic traps on the body centres: stiffness k and centre X0, (n, 3) each (a component of k that is 0: no trap along
+        that axis); force -k (X - X0) on the body, no torque.  n: the bodies -- of an ensemble: those of one replica (shared by
+        all) or R N_bod entries, replica-major"""
+        import numpy as np
+        if k is None and X0 is None and not on:
+            return self._chk(self.L.rbl_set_traps(self.h, None, None, 0, 0))
+        k, X0 = np.ascontiguousarray(k, dtype=np.float64), np.ascontiguousarray(X0, dtype=np.float64)
+        if k.ndim != 2 or k.shape[1] != 3 or k.shape != X0.shape:
+            raise ValueError("set_traps: k and X0 must both have shape (n, 3); got %s and %s" % (k.shape, X0.shape))
+        self._chk(self.L.rbl_set_traps(self.h, k.ctypes.data, X0.ctypes.data, k.shape[0], int(bool(on))))
+
+    def traps(self):
+        """{on, k (n, 3), X0 (n, 3)}"""
+        import numpy as np
+        n, on = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_traps(self.h, C.byref(n), C.byref(on), None, None))
+        k, X0 = np.zeros((n.value, 3)), np.zeros((n.value, 3))
+        if n.value:
+            self._chk(self.L.rbl_get_traps(self.h, None, None, k.ctypes.data, X0.ctypes.data))
+        return dict(on=bool(on.value), k=k, X0=X0)
 
     def interaction_forces_dev(self, d_f_blob, d_FT_body, energy=False):
         """PHYSICAL forces at the current configuration into device buffers (addresses or None); energy=True also returns the

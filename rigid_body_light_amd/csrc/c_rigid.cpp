@@ -600,6 +600,27 @@ struct CManyBodies {
   {
     check(rbl_set_interactions(ctx, w, eps_wall, b_wall, eps_blob, b_blob, r_cut, on ? 1 : 0));
   }
+  void set_pair_table(darr U, darr dU, double r_min, double r_cut, bool on)
+  {
+    if (U.ndim() != 1 || dU.ndim() != 1 || U.size() != dU.size()) throw std::runtime_error("set_pair_table: U and dU must be one-dimensional and of one length");
+    check(rbl_set_pair_table(ctx, U.data(), dU.data(), (int)U.size(), r_min, r_cut, on ? 1 : 0));
+  }
+  void set_height_table(darr U, darr dU, double h_min, double h_cut, bool on)
+  {
+    if (U.ndim() != 1 || dU.ndim() != 1 || U.size() != dU.size()) throw std::runtime_error("set_height_table: U and dU must be one-dimensional and of one length");
+    check(rbl_set_height_table(ctx, U.data(), dU.data(), (int)U.size(), h_min, h_cut, on ? 1 : 0));
+  }
+  void set_traps(darr k, darr X0, bool on)
+  {
+    if (k.size() != X0.size() || k.size() % 3 || !k.size()) throw std::runtime_error("set_traps: k and X0 must both hold 3 entries per body");
+    check(rbl_set_traps(ctx, k.data(), X0.data(), (int)(k.size() / 3), on ? 1 : 0));
+  }
+  int interactions_active() const
+  {
+    int m = 0;
+    rbl_interactions_active(ctx, &m);
+    return m;
+  }
   // the model's body forces in the REFERENCE convention, -K^T f_phys (6 N_bod): add them to F in rhs = [0; -F]
   darr interaction_forces()
   {
@@ -740,6 +761,11 @@ PYBIND11_MODULE(c_rigid, m)
       .def("evolve_X_Q_RFD", &CManyBodies::evolve_X_Q_RFD, py::arg("U"))
       .def("set_interactions", &CManyBodies::set_interactions, py::arg("w"), py::arg("eps_wall"), py::arg("b_wall"), py::arg("eps_blob"),
            py::arg("b_blob"), py::arg("r_cut"), py::arg("on") = true)
+      .def("set_pair_table", &CManyBodies::set_pair_table, py::arg("U"), py::arg("dU"), py::arg("r_min"), py::arg("r_cut"), py::arg("on") = true)
+      .def("set_height_table", &CManyBodies::set_height_table, py::arg("U"), py::arg("dU"), py::arg("h_min"), py::arg("h_cut"),
+           py::arg("on") = true)
+      .def("set_traps", &CManyBodies::set_traps, py::arg("k"), py::arg("X0"), py::arg("on") = true)
+      .def("interactions_active", &CManyBodies::interactions_active, "bit 0 built-in terms, 1 pair table, 2 height table, 3 traps")
       .def("interaction_forces", &CManyBodies::interaction_forces, "force model's body forces/torques, reference convention (-K^T f)")
       .def("interaction_energy", &CManyBodies::interaction_energy)
       .def("velocity_field", &CManyBodies::velocity_field, "fluid velocity at points from blob forces", py::arg("points"),

@@ -7,7 +7,7 @@
 //   rbl_roots.hip     M^{1/2} W: dense Cholesky path and the Lanczos roots
 //   rbl_solvers.hip   GMRES on the saddle operator
 //   rbl_steps.hip     whole time steps, the stochastic midpoint scheme (free and mixed), random finite differences
-//   rbl_forces.hip    configuration-dependent forces (weight, wall and steric repulsion)
+//   rbl_forces.hip    configuration-dependent forces (weight, wall and steric repulsion, tabulated potentials, traps)
 //   rbl_ensemble.hip  ensembles of independent replicas of one small system
 //   rbl_field.hip     the fluid velocity at arbitrary points from blob forces
 //   rbl_mixed.hip     prescribed kinematics: held or driven bodies among free ones, the loads that takes; the entry points of their Brownian step
@@ -141,6 +141,8 @@ int step_upload_W(rbl_ctx *c, const double *W, double **d_W);
 int step_midpoint(rbl_ctx *c, const std::function<int(double *, double *)> &rhs, const std::function<int(double *)> &solve);
 
 // ---- rbl_forces.hip -----------------------------------------------------------------------------------------------
+// any term of the model is switched on: the built-in one, a pair table, a height table or the traps
+bool ia_any(const rbl_ctx *c);
 // the model's PHYSICAL forces at the context's configuration: d_f (3 N, may be NULL), d_FT = K^T f (6 N_bod, may be NULL),
 // per-blob energies d_e (N, may be NULL); enqueued on the context's stream under RBL_T_FORCES
 int ia_eval(rbl_ctx *c, double *d_f, double *d_FT, double *d_e);

@@ -519,7 +519,7 @@ int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *
   const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
   rbl_launch_body_geom(c->stream, X, Q, ens_cfg(c), nbl, (int64_t)R * Nb * nbl, w.lever, w.pos);
   *FT = nullptr;
-  if (model && c->ia_on) {
+  if (model && ia_any(c)) {
     double *f = nullptr;
     if ((rc = ia_eval_batch(c, X, w.pos, w.lever, Nb, R, w.ia, &f, w.FT, nullptr, w.gerr))) return rc;
     *FT = w.FT;
@@ -1058,7 +1058,7 @@ int rbl_ensemble_interaction_forces(rbl_ctx *c, double *FT_body, double *energy)
 {
   if (!c) return RBL_ERR_ARG;
   int rc = ens_ready(c); if (rc) return rc;
-  if (!c->ia_on) return rbl_fail(c, RBL_ERR_STATE, "ensemble_interaction_forces: no force model is switched on (rbl_set_interactions)");
+  if (!ia_any(c)) return rbl_fail(c, RBL_ERR_STATE, "ensemble_interaction_forces: no force model is switched on (rbl_set_interactions)");
   EnsWork w;
   if ((rc = ens_work(c, 1, &w))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;

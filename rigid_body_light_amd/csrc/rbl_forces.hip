@@ -13,9 +13,19 @@
 //                        (i <- j; the pair j <- i is evaluated by j's workgroup), weight and wall are added in the epilogue.
 //                        No fp64 atomics, one summation order: bitwise reproducible.  The software exp and the division are
 //                        taken only inside r_cut.
+//   k_blob_interactions_tab<TAB>  the same body compiled with the tabulated terms (bit 0 of TAB: pair table, bit 1: height
+//                        table): per pair inside the table's cutoff one interval index, one 32-byte coefficient read and two
+//                        Horner evaluations.  The coefficients stay in global memory and are read through L1 / L2: a lane's
+//                        interval follows ITS pair distance, so the read is a gather either way; in LDS a gather of 32 bytes
+//                        per lane at unrelated intervals pays bank conflicts, and only tables below a few thousand intervals
+//                        would fit beside the position chunk at all (the largest table is 2 MB).  An LDS-staged variant has
+//                        not been built.  k_blob_interactions itself is the TAB = 0 instantiation with the argument list it
+//                        always had.
+//   k_body_traps         harmonic traps on the body centres, after K^T f: one lane per body.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "rbl_api_internal.hpp"
@@ -61,12 +71,39 @@ __global__ __launch_bounds__(64) void k_body_neighbours(const double *__restrict
   }
 }
 
-__global__ __launch_bounds__(IA_BT) void k_blob_interactions(const double *__restrict__ pos, const int *__restrict__ cnt,
-                                                             const int *__restrict__ list, int cap, int N_blb, int tiles,
-                                                             IaParams p, double *__restrict__ f, double *__restrict__ e,
-                                                             int *__restrict__ npairs)
+// a tabulated potential on the device: coef[k] = (c0, c1, c2, c3) of interval k, U = c0 + t (c1 + t (c2 + t c3)),
+// dU/dx = (c1 + t (2 c2 + 3 c3 t)) / h with t = (x - lo) / h - k
+struct IaTab {
+  const double4 *coef;
+  double lo, hi, inv_h, U0, dU0, hi2;                    // U0, dU0: value and slope at lo (the tangent below it); hi2: hi^2 rounded up
+  int last;                                              // n - 2, the last interval
+};
+
+// (U, dU/dx) at x <= T.hi
+__device__ __forceinline__ void ia_tab_eval(const IaTab &T, double x, double &U, double &dU)
 {
-  __shared__ double s[IA_CHUNK][4];
+  if (x >= T.lo) {
+    const double sx = (x - T.lo) * T.inv_h;
+    const int k = min((int)sx, T.last);
+    const double t = sx - (double)k;
+    const double4 c = T.coef[k];
+    U = c.x + t * (c.y + t * (c.z + t * c.w));
+    dU = (c.y + t * (2.0 * c.z + 3.0 * c.w * t)) * T.inv_h;
+  } else {                                               // the tangent at lo continued downwards
+    U = T.U0 + T.dU0 * (x - T.lo);
+    dU = T.dU0;
+  }
+}
+
+// TAB: bit 0 pair table PT, bit 1 height table HT (both ignored in the TAB = 0 instantiation, the model of weight, wall and
+// steric repulsion alone).  A pair is counted once when it lies inside the cutoff of a pair term that is on; the built-in
+// term is switched off by p.rc2 < 0
+template <int TAB>
+__device__ __forceinline__ void ia_blob_interactions(double (*s)[4], const double *__restrict__ pos, const int *__restrict__ cnt,
+                                                     const int *__restrict__ list, int cap, int N_blb, int tiles, const IaParams &p,
+                                                     const IaTab &PT, const IaTab &HT, double *__restrict__ f,
+                                                     double *__restrict__ e, int *__restrict__ npairs)
+{
   const int i = blockIdx.x / tiles, k = (blockIdx.x - i * tiles) * blockDim.x + threadIdx.x;
   const bool own = k < N_blb;
   const size_t gi = (size_t)i * N_blb + (own ? k : 0);
@@ -89,16 +126,32 @@ __global__ __launch_bounds__(IA_BT) void k_blob_interactions(const double *__res
       for (int u = 0; u < m; ++u) {
         const double dx = xi - s[u][0], dy = yi - s[u][1], dz = zi - s[u][2];
         const double r2 = dx * dx + dy * dy + dz * dz;
-        if (r2 > p.rc2) continue;                        // beyond the cutoff: skipped, not multiplied by zero
+        if constexpr (TAB & 1) {
+          if (r2 > p.rc2 && r2 > PT.hi2) continue;       // beyond both cutoffs (hi2: a hair above hi^2, r <= hi decides)
+        } else {
+          if (r2 > p.rc2) continue;                      // beyond the cutoff: skipped, not multiplied by zero
+        }
         const double r = sqrt(r2);
+        const bool in_t = (TAB & 1) && r <= PT.hi;       // each term has its own cutoff
         double U, g;                                     // energy of the pair, -U'(r) / r
-        if (r >= p.two_a) {
+        if ((TAB & 1) && r2 > p.rc2) {                   // only the table can reach this far
+          if (!in_t) continue;
+          U = 0.0; g = 0.0;
+        } else if (r >= p.two_a) {
           U = p.eps_b * (p.two_a / r) * exp(-(r - p.two_a) * p.inv_bb);
           g = U * (1.0 / r + p.inv_bb) / r;
         } else {                                         // the tangent at r = 2a continued inwards
           const double slope = p.eps_b * (1.0 / p.two_a + p.inv_bb);
           U = p.eps_b + slope * (p.two_a - r);
           g = r > 0.0 ? slope / r : 0.0;
+        }
+        if constexpr (TAB & 1) {
+          if (in_t) {
+            double Ut, dUt;
+            ia_tab_eval(PT, r, Ut, dUt);
+            U += Ut;
+            if (r > 0.0) g -= dUt / r;                   // coincident blobs exert no force
+          }
         }
         fx += g * dx; fy += g * dy; fz += g * dz;
         en += 0.5 * U;
@@ -116,9 +169,59 @@ __global__ __launch_bounds__(IA_BT) void k_blob_interactions(const double *__res
     fz += Fw;
     en += Uw;
   }
+  if constexpr (TAB & 2) {
+    if (zi <= HT.hi) {                                   // with or without the wall; nothing above h_cut
+      double Uh, dUh;
+      ia_tab_eval(HT, zi, Uh, dUh);
+      fz -= dUh;
+      en += Uh;
+    }
+  }
   f[3 * gi] = fx; f[3 * gi + 1] = fy; f[3 * gi + 2] = fz;
   if (e) e[gi] = en;
   npairs[gi] = np;
+}
+
+__global__ __launch_bounds__(IA_BT) void k_blob_interactions(const double *__restrict__ pos, const int *__restrict__ cnt,
+                                                             const int *__restrict__ list, int cap, int N_blb, int tiles,
+                                                             IaParams p, double *__restrict__ f, double *__restrict__ e,
+                                                             int *__restrict__ npairs)
+{
+  __shared__ double s[IA_CHUNK][4];
+  const IaTab none = {};
+  ia_blob_interactions<0>(s, pos, cnt, list, cap, N_blb, tiles, p, none, none, f, e, npairs);
+}
+
+template <int TAB>
+__global__ __launch_bounds__(IA_BT) void k_blob_interactions_tab(const double *__restrict__ pos, const int *__restrict__ cnt,
+                                                                 const int *__restrict__ list, int cap, int N_blb, int tiles,
+                                                                 IaParams p, IaTab PT, IaTab HT, double *__restrict__ f,
+                                                                 double *__restrict__ e, int *__restrict__ npairs)
+{
+  static_assert(TAB >= 1 && TAB <= 3, "bit 0: pair table, bit 1: height table");
+  __shared__ double s[IA_CHUNK][4];
+  ia_blob_interactions<TAB>(s, pos, cnt, list, cap, N_blb, tiles, p, PT, HT, f, e, npairs);
+}
+
+// harmonic traps on the body centres: FT[6 i + c] -= k_c (X_c - X0_c), the energy added to the entry of the body's first blob
+// (after the pair kernel on the same stream: one order).  per: entries of k / X0 -- body i reads entry i % per (an ensemble's
+// shared layout: per = bodies of a replica; one entry per body otherwise)
+__global__ __launch_bounds__(256) void k_body_traps(const double *__restrict__ X, const double *__restrict__ k3,
+                                                    const double *__restrict__ X0, int nbod, int per, int N_blb,
+                                                    double *__restrict__ FT, double *__restrict__ e)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nbod) return;
+  const size_t j = (size_t)(i % per);
+  double E = 0.0;
+  for (int c = 0; c < 3; ++c) {
+    const double k = k3[3 * j + c], d = X[3 * (size_t)i + c] - X0[3 * j + c];
+    if (k != 0.0) {                                      // a component of 0: no trap along that axis
+      if (FT) FT[6 * (size_t)i + c] -= k * d;
+      E += 0.5 * k * d * d;
+    }
+  }
+  if (e) e[(size_t)i * N_blb] += E;
 }
 
 struct IaLayout {
@@ -159,34 +262,93 @@ int ia_reserve(rbl_ctx *c, IaLayout &L)
 
 }  // namespace
 
+bool ia_any(const rbl_ctx *c) { return c->ia_on || c->ia_pt.on || c->ia_ht.on || c->ia_tr_on; }
+
+// the tables' coefficients and the traps on the device (once per rbl_set_pair_table / rbl_set_height_table / rbl_set_traps):
+// pair coefficients | height coefficients | trap k | trap X0.  4 (n - 1) doubles per table: every interval starts 32-byte aligned
+static int ia_upload(rbl_ctx *c)
+{
+  if (c->ia_tab_valid) return RBL_OK;
+  const std::vector<double> *part[4] = {&c->ia_pt.coef, &c->ia_ht.coef, &c->ia_tr_k, &c->ia_tr_X0};
+  size_t n = 0;
+  for (const std::vector<double> *v : part) n += v->size();
+  if (n) {
+    int rc = rbl_dev_reserve(c, c->d_iat, sizeof(double) * n); if (rc) return rc;
+    double *d = (double *)c->d_iat.p;
+    for (const std::vector<double> *v : part) {
+      if (!v->empty() && (rc = copy_h2d(c, d, v->data(), sizeof(double) * v->size()))) return rc;
+      d += v->size();
+    }
+    RBL_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  c->ia_tab_valid = true;
+  return RBL_OK;
+}
+
+static IaTab ia_tab_args(const rbl_ctx::IaTable &t, const double *d_coef)
+{
+  IaTab T = {};
+  if (!t.on) return T;
+  T.coef = (const double4 *)d_coef;
+  T.lo = t.lo; T.hi = t.hi;
+  T.inv_h = (double)(t.n - 1) / (t.hi - t.lo);
+  T.U0 = t.coef[0]; T.dU0 = t.dU0;
+  T.hi2 = t.hi * t.hi * (1.0 + 1e-15);
+  T.last = t.n - 2;
+  return T;
+}
+
 // the model over n_win windows of win bodies each (resident X of the body centres, blob positions and lever arms): neighbour
 // lists inside each window, the pair kernel, K^T f.  d_f (3 N) is required here; d_FT (6 N_bod total) and d_e may be NULL.
 static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_pos, const double *d_lever, int win, int n_win, double *d_cl,
                      double *d_f, double *d_FT, double *d_e, unsigned *d_err)
 {
   const RblBodyState &S = c->S;
-  if (!(c->ia_r_cut >= 2.0 * S.a))
+  if (c->ia_on && !(c->ia_r_cut >= 2.0 * S.a))           // the built-in term's own check: a context with only a table on has r_cut = 0
     return rbl_fail(c, RBL_ERR_STATE, "interactions: r_cut is below 2a of the current parameters (call rbl_set_interactions again)");
-  RblPhase ph(c, RBL_T_FORCES);
   const int nbod = win * n_win, cap = ia_cap(win);
+  const size_t ntr = c->ia_tr_k.size() / 3;
+  if (c->ia_tr_on && ntr != (size_t)win && ntr != (size_t)nbod)
+    return rbl_fail(c, RBL_ERR_STATE, "interactions: the traps hold neither one entry per body nor one per body of every replica (rbl_set_traps)");
+  int rc = ia_upload(c); if (rc) return rc;
+  RblPhase ph(c, RBL_T_FORCES);
   IaLayout L = ia_layout(d_cl, nbod, S.N_blb, cap);
   double R2 = 0.0;                                       // R_body: largest blob distance from the centre, body frame (mean removed)
   for (int k = 0; k < S.N_blb; ++k) {
     const double *q = &S.ref_cfg[3 * (size_t)k];
     R2 = std::max(R2, q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
   }
-  // a hair of slack for the rounding of the rotated lever arms and of the distances: it can only add candidates, whose
-  // pairs beyond r_cut are then skipped one by one
-  const double cut = (2.0 * std::sqrt(R2) + c->ia_r_cut) * (1.0 + 1e-12) + 1e-12;
+  // the larger cutoff of the pair terms that are on.  A hair of slack for the rounding of the rotated lever arms and of the
+  // distances: it can only add candidates, whose pairs beyond the cutoffs are then skipped one by one
+  const double rc_max = std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0);
+  const double cut = (2.0 * std::sqrt(R2) + rc_max) * (1.0 + 1e-12) + 1e-12;
   hipLaunchKernelGGL(k_body_neighbours, dim3(nbod), dim3(64), 0, c->stream, d_X, nbod, win, cut * cut, c->ia_cull ? 1 : 0, cap,
                      L.cnt, L.list, d_err);
   IaParams P;
   P.w = c->ia_w; P.a = S.a; P.eps_w = c->ia_eps_wall; P.inv_bw = 1.0 / c->ia_b_wall; P.eps_b = c->ia_eps_blob;
   P.inv_bb = 1.0 / c->ia_b_blob; P.two_a = 2.0 * S.a; P.rc2 = c->ia_r_cut * c->ia_r_cut; P.wall = S.wall ? 1 : 0;
+  if (!c->ia_on) { P.w = 0.0; P.wall = 0; P.eps_b = 0.0; P.rc2 = -1.0; }   // no pair is inside a negative cutoff
   const int bt = S.N_blb > 128 ? IA_BT : (S.N_blb + 63) / 64 * 64, tiles = (S.N_blb + bt - 1) / bt;
-  hipLaunchKernelGGL(k_blob_interactions, dim3((unsigned)(tiles * nbod)), dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt,
-                     (const int *)L.list, cap, S.N_blb, tiles, P, d_f, d_e, L.np);
+  const dim3 grid((unsigned)(tiles * nbod));
+  const int tab = (c->ia_pt.on ? 1 : 0) | (c->ia_ht.on ? 2 : 0);
+  const double *T = (const double *)c->d_iat.p;
+  const IaTab PT = ia_tab_args(c->ia_pt, T), HT = ia_tab_args(c->ia_ht, T + c->ia_pt.coef.size());
+#define RBL_IA_TAB(K)                                                                                                              \
+  hipLaunchKernelGGL(k_blob_interactions_tab<K>, grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt, (const int *)L.list, cap, \
+                     S.N_blb, tiles, P, PT, HT, d_f, d_e, L.np)
+  if (tab == 0)
+    hipLaunchKernelGGL(k_blob_interactions, grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt, (const int *)L.list, cap,
+                       S.N_blb, tiles, P, d_f, d_e, L.np);
+  else if (tab == 1) RBL_IA_TAB(1);
+  else if (tab == 2) RBL_IA_TAB(2);
+  else RBL_IA_TAB(3);
+#undef RBL_IA_TAB
   if (d_FT) rbl_launch_KT_x_Lam(c->stream, d_lever, d_f, S.N_blb, nbod, d_FT);
+  if (c->ia_tr_on && (d_FT || d_e)) {
+    const double *k3 = T + c->ia_pt.coef.size() + c->ia_ht.coef.size();
+    hipLaunchKernelGGL(k_body_traps, dim3((unsigned)((nbod + 255) / 256)), dim3(256), 0, c->stream, d_X, k3, k3 + 3 * ntr, nbod,
+                       (int)ntr, S.N_blb, d_FT, d_e);
+  }
   return RBL_OK;
 }
 
@@ -217,7 +379,7 @@ int ia_eval_batch(rbl_ctx *c, const double *d_X, const double *d_pos, const doub
 
 int ia_add_to_step_force(rbl_ctx *c, double *d_force)
 {
-  if (!c->ia_on) return RBL_OK;
+  if (!ia_any(c)) return RBL_OK;
   IaLayout L;
   int rc = ia_reserve(c, L); if (rc) return rc;
   if ((rc = ia_eval(c, nullptr, L.ft, nullptr))) return rc;
@@ -253,11 +415,106 @@ int rbl_get_interactions(const rbl_ctx *c, double *params6, int *on)
   return RBL_OK;
 }
 
+// one tabulated term: checks, then the four Hermite coefficients per interval (include/rbl.h section 4).  Nothing is stored
+// unless every check passes.  U = dU = NULL with on = 0 only switches the term off and keeps its table
+static int ia_set_table(rbl_ctx *c, const char *who, rbl_ctx::IaTable &t, const double *U, const double *dU, int n, double lo, double hi,
+                        bool lo_nonneg, int on)
+{
+  if (!U && !dU && !on) { t.on = false; return RBL_OK; }
+  if (!U || !dU) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": U and dU must not be NULL");
+  if (n < 2 || n > 65537) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": n must lie in [2, 65537]");
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi) || (lo_nonneg && lo < 0.0))
+    return rbl_fail(c, RBL_ERR_ARG, std::string(who) + (lo_nonneg ? ": needs finite 0 <= r_min < r_cut" : ": needs finite h_min < h_cut"));
+  for (int k = 0; k < n; ++k)
+    if (!std::isfinite(U[k]) || !std::isfinite(dU[k])) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": every value of U and dU must be finite");
+  const double h = (hi - lo) / (double)(n - 1);
+  std::vector<double> coef(4 * (size_t)(n - 1));
+  for (int k = 0; k + 1 < n; ++k) {
+    const double D0 = h * dU[k], D1 = h * dU[k + 1];
+    double *q = &coef[4 * (size_t)k];
+    q[0] = U[k];
+    q[1] = D0;
+    q[2] = 3.0 * (U[k + 1] - U[k]) - 2.0 * D0 - D1;
+    q[3] = 2.0 * (U[k] - U[k + 1]) + D0 + D1;
+  }
+  t.coef.swap(coef);
+  t.n = n; t.lo = lo; t.hi = hi; t.dU0 = dU[0];
+  t.on = on != 0;
+  c->ia_tab_valid = false;
+  return RBL_OK;
+}
+
+static int ia_get_table(const rbl_ctx::IaTable &t, int *n, double *lo, double *hi, int *on, double *coef)
+{
+  if (n) *n = t.n;
+  if (lo) *lo = t.lo;
+  if (hi) *hi = t.hi;
+  if (on) *on = t.on ? 1 : 0;
+  if (coef && !t.coef.empty()) std::memcpy(coef, t.coef.data(), sizeof(double) * t.coef.size());
+  return RBL_OK;
+}
+
+int rbl_set_pair_table(rbl_ctx *c, const double *U, const double *dU, int n, double r_min, double r_cut, int on)
+{
+  if (!c) return RBL_ERR_ARG;
+  return ia_set_table(c, "set_pair_table", c->ia_pt, U, dU, n, r_min, r_cut, true, on);
+}
+
+int rbl_get_pair_table(const rbl_ctx *c, int *n, double *r_min, double *r_cut, int *on, double *coef)
+{
+  if (!c) return RBL_ERR_ARG;
+  return ia_get_table(c->ia_pt, n, r_min, r_cut, on, coef);
+}
+
+int rbl_set_height_table(rbl_ctx *c, const double *U, const double *dU, int n, double h_min, double h_cut, int on)
+{
+  if (!c) return RBL_ERR_ARG;
+  return ia_set_table(c, "set_height_table", c->ia_ht, U, dU, n, h_min, h_cut, false, on);
+}
+
+int rbl_get_height_table(const rbl_ctx *c, int *n, double *h_min, double *h_cut, int *on, double *coef)
+{
+  if (!c) return RBL_ERR_ARG;
+  return ia_get_table(c->ia_ht, n, h_min, h_cut, on, coef);
+}
+
+int rbl_set_traps(rbl_ctx *c, const double *k3, const double *X0, int n_bodies, int on)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (!k3 && !X0 && !on) { c->ia_tr_on = false; return RBL_OK; }
+  if (!k3 || !X0) return rbl_fail(c, RBL_ERR_ARG, "set_traps: k and X0 must not be NULL");
+  if (n_bodies < 1) return rbl_fail(c, RBL_ERR_ARG, "set_traps: n_bodies must be >= 1");
+  for (size_t i = 0; i < 3 * (size_t)n_bodies; ++i)
+    if (!std::isfinite(k3[i]) || !std::isfinite(X0[i])) return rbl_fail(c, RBL_ERR_ARG, "set_traps: every value of k and X0 must be finite");
+  c->ia_tr_k.assign(k3, k3 + 3 * (size_t)n_bodies);
+  c->ia_tr_X0.assign(X0, X0 + 3 * (size_t)n_bodies);
+  c->ia_tr_on = on != 0;
+  c->ia_tab_valid = false;
+  return RBL_OK;
+}
+
+int rbl_get_traps(const rbl_ctx *c, int *n_bodies, int *on, double *k3, double *X0)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (n_bodies) *n_bodies = (int)(c->ia_tr_k.size() / 3);
+  if (on) *on = c->ia_tr_on ? 1 : 0;
+  if (k3 && !c->ia_tr_k.empty()) std::memcpy(k3, c->ia_tr_k.data(), sizeof(double) * c->ia_tr_k.size());
+  if (X0 && !c->ia_tr_X0.empty()) std::memcpy(X0, c->ia_tr_X0.data(), sizeof(double) * c->ia_tr_X0.size());
+  return RBL_OK;
+}
+
+int rbl_interactions_active(const rbl_ctx *c, int *mask)
+{
+  if (!c || !mask) return RBL_ERR_ARG;
+  *mask = (c->ia_on ? 1 : 0) | (c->ia_pt.on ? 2 : 0) | (c->ia_ht.on ? 4 : 0) | (c->ia_tr_on ? 8 : 0);
+  return RBL_OK;
+}
+
 int rbl_interaction_forces_dev(rbl_ctx *c, double *d_f_blob, double *d_FT_body, double *energy)
 {
   int rc = need_config(c); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
-  if (!c->ia_on) return rbl_fail(c, RBL_ERR_STATE, "interaction_forces: no force model is switched on (rbl_set_interactions)");
+  if (!ia_any(c)) return rbl_fail(c, RBL_ERR_STATE, "interaction_forces: no force model is switched on (rbl_set_interactions)");
   if (!energy) return ia_eval(c, d_f_blob, d_FT_body, nullptr);
   IaLayout L;
   if ((rc = ia_reserve(c, L))) return rc;
@@ -276,7 +533,7 @@ int rbl_interaction_forces(rbl_ctx *c, double *f_blob, double *FT_body, double *
 {
   int rc = need_config(c); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
-  if (!c->ia_on) return rbl_fail(c, RBL_ERR_STATE, "interaction_forces: no force model is switched on (rbl_set_interactions)");
+  if (!ia_any(c)) return rbl_fail(c, RBL_ERR_STATE, "interaction_forces: no force model is switched on (rbl_set_interactions)");
   const size_t N = (size_t)c->S.N_bod * c->S.N_blb, nb6 = (size_t)6 * c->S.N_bod;
   IaLayout L;
   if ((rc = ia_reserve(c, L))) return rc;

@@ -204,6 +204,18 @@ struct rbl_ctx {
   bool ia_on = false;
   double ia_w = 0.0, ia_eps_wall = 0.0, ia_b_wall = 1.0, ia_eps_blob = 0.0, ia_b_blob = 1.0, ia_r_cut = 0.0;
   bool ia_cull = true;                              // RBL_OPT_INTERACTION_CULL
+  // tabulated terms: a potential on the uniform grid lo + k (hi - lo) / (n - 1) as four Hermite coefficients per interval
+  struct IaTable {
+    bool on = false;
+    int n = 0;                                      // grid points (0: never set)
+    double lo = 0.0, hi = 0.0, dU0 = 0.0;           // dU0: the caller's dU/dx at lo, the slope of the tangent continued below it
+    std::vector<double> coef;                       // 4 (n - 1)
+  };
+  IaTable ia_pt, ia_ht;                             // pair table in r, height table in z
+  bool ia_tr_on = false;                            // harmonic traps on the body centres
+  std::vector<double> ia_tr_k, ia_tr_X0;            // 3 per body, ia_tr_k.size() / 3 bodies
+  RblDevBuf d_iat;                                  // pair coefficients | height coefficients | trap k | trap X0 (ia_tab_valid)
+  bool ia_tab_valid = false;
   RblDevBuf d_ia;                                   // f_blob | energy per blob | neighbour counts | lists | pairs per blob
   int ia_nb = 0, ia_nblb = 0, ia_cap = 0;           // shape of what d_ia holds (0: nothing evaluated yet)
   // ensemble of independent replicas (rbl_ensemble.hip; include/rbl.h section 5)

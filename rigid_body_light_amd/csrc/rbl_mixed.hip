@@ -593,7 +593,7 @@ int mx_upload(rbl_ctx *c, MxBuf &B, const uint8_t *prescribed, const double *bod
   if (slip && (rc = copy_h2d(c, B.slip, slip, sizeof(double) * n3))) return rc;
   *have_slip = slip != nullptr;
   if (model && (rc = flow_add_to_step_slip(c, B.slip, have_slip))) return rc;   // imposed flow and body slip at q^n (section 8)
-  if (model && c->ia_on && np < B.per * c->S.N_bod) {    // -K^T f_phys at q^n, free slots only (none free: nothing feels the model)
+  if (model && ia_any(c) && np < B.per * c->S.N_bod) {    // -K^T f_phys at q^n, free slots only (none free: nothing feels the model)
     RBL_HIP(c, hipMemsetAsync(B.model, 0, sizeof(double) * nb6, c->stream));
     if ((rc = ia_add_to_step_force(c, B.model))) return rc;
     hipLaunchKernelGGL(k_mx_add_free, dim3((unsigned)((nb6 + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)B.mask, B.per,

@@ -253,6 +253,22 @@ class Ensemble:
         """the force model of RigidBody.set_interactions, for every replica (steric pairs only inside a replica)"""
         self.ctx.set_interactions(w=w, eps_wall=eps_wall, b_wall=b_wall, eps_blob=eps_blob, b_blob=b_blob, r_cut=r_cut, on=on)
 
+    def set_pair_table(self, U, dU, r_min, r_cut, on=True):
+        """the tabulated pair potential of RigidBody.set_pair_table, for every replica (pairs only inside a replica)"""
+        self.ctx.set_pair_table(U, dU, r_min, r_cut, on=on)
+
+    def set_height_table(self, U, dU, h_min, h_cut, on=True):
+        """the tabulated potential in the blob height of RigidBody.set_height_table, for every replica"""
+        self.ctx.set_height_table(U, dU, h_min, h_cut, on=on)
+
+    def set_traps(self, k, X0, on=True):
+        """harmonic traps on the body centres: k and X0 of shape (N_bod, 3), shared by every replica, or (R, N_bod, 3)"""
+        k, X0 = np.asarray(k, dtype=np.float64), np.asarray(X0, dtype=np.float64)
+        nb = self.N_bodies
+        if k.shape != X0.shape or k.shape not in ((nb, 3), (self.R, nb, 3)):
+            _fail("k and X0 must both have shape (%d, 3) or (%d, %d, 3); got %s and %s" % (nb, self.R, nb, k.shape, X0.shape))
+        self.ctx.set_traps(k.reshape(-1, 3), X0.reshape(-1, 3), on=on)
+
     def interaction_forces(self):
         """body forces and torques of the model, (R, 6 N_bod), reference convention (-K^T f_phys)"""
         return self.ctx.ensemble_interaction_forces()[0]

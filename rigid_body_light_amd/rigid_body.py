@@ -20,6 +20,7 @@ and an imposed flow, a body-frame slip and stresslets (`set_background_flow`, `s
 import numpy as np
 
 from . import c_rigid as _ext
+from ._lib import table_arrays, tabulate  # noqa: F401
 
 _KBT_IN_WRAPPER = 1.0   # the reference wrapper passes kBT = 1 whatever the caller wants (src/Rigid.py:23)
 
@@ -217,6 +218,27 @@ class RigidBody:
         if r_cut is None:
             r_cut = 2.0 * self._a + 20.0 * b_blob
         self.cb.set_interactions(float(w), float(eps_wall), float(b_wall), float(eps_blob), float(b_blob), float(r_cut), bool(on))
+
+    def set_pair_table(self, U, dU, r_min, r_cut, on=True):
+        """A tabulated radial potential between blobs of different bodies (include/rbl.h section 4): values U and derivatives
+        dU = dU/dr on the uniform grid r_min .. r_cut (`tabulate(U, dU, r_min, r_cut, n)` makes them from callables).  Cubic
+        Hermite inside the grid, the tangent at r_min below it, nothing beyond r_cut; the table is not shifted, so
+        U(r_cut) != 0 is a jump in the energy.  Adds to the steric term of set_interactions."""
+        U, dU = table_arrays("set_pair_table", U, dU)
+        self.cb.set_pair_table(U, dU, float(r_min), float(r_cut), bool(on))
+
+    def set_height_table(self, U, dU, h_min, h_cut, on=True):
+        """The same construction in the blob height z over h_min .. h_cut, with or without the wall."""
+        U, dU = table_arrays("set_height_table", U, dU)
+        self.cb.set_height_table(U, dU, float(h_min), float(h_cut), bool(on))
+
+    def set_traps(self, k, X0, on=True):
+        """Harmonic traps on the body centres: k and X0 of shape (N_bodies, 3), lab frame; a component of k that is 0 leaves
+        that axis free.  The body feels -k (X - X0) and no torque."""
+        k, X0 = np.ascontiguousarray(k, dtype=np.float64), np.ascontiguousarray(X0, dtype=np.float64)
+        if k.ndim != 2 or k.shape[1] != 3 or k.shape != X0.shape:
+            raise ValueError(f"set_traps: k and X0 must both have shape (N_bodies, 3). Got shapes: {k.shape} and {X0.shape}")
+        self.cb.set_traps(k.reshape(-1), X0.reshape(-1), bool(on))
 
     def interaction_forces(self):
         """The model's body forces and torques at the current configuration, 6 * N_bodies, in the reference convention
