@@ -558,9 +558,41 @@ int rbl_option_key(const char *name);
  *                   traps enter the BODY forces and the energy; the blob-level array f_blob does not contain them.
  *                   n_bodies must be N_bod when the model is evaluated; in an ensemble (section 5) N_bod entries shared by
  *                   every replica or R N_bod entries, replica-major (anything else at evaluation time: RBL_ERR_STATE).
- * Body force / torque about the body centre = K^T f_blob (+ the traps).  The evaluation is deterministic (ordered pairs, no
- * atomics): the same configuration gives bitwise the same forces on every call and every rank (multi-GPU contexts evaluate
- * the whole model, replicated).
+ * Permanent magnetic dipoles, fixed in the bodies, with two terms of their own (each with its own switch, nothing changes while
+ * they are off).  Body i carries the body-frame moment m_body,i; its lab-frame moment is m_i = R(Q_i) m_body,i with the rotation
+ * matrix of the blob positions (Q scalar-first, normalised):
+ *   field           a uniform field B(t) = B0 + B1 cos(omega t) + B2 sin(omega t) (three lab-frame vectors: static, rotating,
+ *                   oscillating, elliptical, precessing), t the context's FIELD TIME (below).  Energy -sum_i m_i . B, torque
+ *                   m_i x B on body i, no force;
+ *   dipole pairs    between the centres of DIFFERENT bodies of the same system (never between the replicas of an ensemble):
+ *                   with r = X_i - X_j, d = |r|, s = max(d, r_core), a = m_i . r, b = m_j . r,
+ *                     U_ij = c_dd [ m_i . m_j / s^3 - 3 a b / s^5 ]         (the caller puts mu_0 / 4 pi into c_dd),
+ *                     force on i, d >= r_core:  3 c_dd [ a m_j + b m_i + (m_i . m_j) r - 5 a b r / d^2 ] / s^5,
+ *                     force on i, d <  r_core:  3 c_dd [ a m_j + b m_i ] / s^5,
+ *                     torque on i:              m_i x c_dd [ 3 b r / s^5 - m_j / s^3 ],
+ *                   the exact derivatives of U: below the core s is constant and U a quadratic form in r, so the energy is
+ *                   continuous and the force bounded (it jumps at r_core); d = 0 gives no force.  Pairs with d > r_cut are
+ *                   skipped, r_cut = +inf takes every pair; the energy is NOT shifted at r_cut (as the tables are not).  All
+ *                   pairs of a system are visited with the cutoff test: there is no neighbour list for this term.
+ * Like the traps, both enter the BODY forces / torques and the energy (each body carries half of every pair energy); f_blob
+ * does not contain them.  m_body: 3 n_bodies doubles, n_bodies = 1 (every body alike), N_bod, or in an ensemble R N_bod
+ * replica-major, read as the traps are (entry i % n_bodies); a count that fits neither at evaluation time: RBL_ERR_STATE.
+ * Bit 4 of rbl_interactions_active: dipole pairs (dipoles on and c_dd > 0); bit 5: field torque (dipoles on and field on).
+ * Field time: rbl_set_field_time takes n = 1 entry (shared) or n = R (one per replica of an ensemble; a single context uses
+ * entry 0; anything else at an ensemble evaluation: RBL_ERR_STATE); the default is t = 0.  NO call advances it: the one-step
+ * entry points and the queries evaluate B at the time that was set.  Inside rbl_ensemble_run (section 5) replica r evaluates
+ * step by step at t_r = t0_r + dt accepted[r], accepted[r] the run's own count of the replica's accepted steps at the start
+ * of the step and dt the context's: under RBL_RUN_REJECT a rejected replica's field waits for it.  The run leaves the
+ * context's field time as it was; continue with t0_r + dt accepted[r] from the returned counts.  The product and the sum are
+ * rounded separately on the device, so a run is bitwise the loop of one-step calls with rbl_set_field_time(t0 + dt n) before
+ * step n.
+ * RBL_ERR_ARG, with the argument named, the previous model in place and no device touched: NULL where an array is needed
+ * with on != 0; non-finite moments, field vectors, omega or t; c_dd < 0 or non-finite; with c_dd > 0: r_core <= 0 or
+ * non-finite, r_cut <= r_core or NaN (+inf is accepted); n_bodies < 1 or n < 1.  on = 0 with NULL arrays only switches the
+ * term off.  The getters take NULL for what is not wanted (m_body: 3 n_bodies doubles, B9: B0 | B1 | B2, t: n doubles).
+ * Body force / torque about the body centre = K^T f_blob (+ the traps, the dipole pairs and the field torque).  The
+ * evaluation is deterministic (ordered pairs, no atomics): the same configuration gives bitwise the same forces on every
+ * call and every rank (multi-GPU contexts evaluate the whole model, replicated -- the dipole terms included).
  *
  * rbl_set_interactions: on = 0 switches the built-in terms off (with every term off the steps are exactly what they are
  * without a model).  Needs rbl_set_parameters first (RBL_ERR_STATE); b_wall, b_blob > 0, eps_wall, eps_blob >= 0, 2a <= r_cut, all finite, or
@@ -586,13 +618,20 @@ int rbl_get_interactions(const rbl_ctx *ctx, double *params6, int *on);
  * NULL (k = X0 = NULL) with on = 0 only switches it off.  rbl_set_parameters is not needed first.  The getters take NULL for
  * what is not wanted; coef: 4 (n - 1) doubles (c0 c1 c2 c3 per interval), k3 / X0: 3 n_bodies each; n = 0: never set.
  * rbl_get_interactions keeps reporting the built-in term only; rbl_interactions_active: bit 0 built-in term, bit 1 pair
- * table, bit 2 height table, bit 3 traps.  The steps, the queries below and the ensembles evaluate every term that is on. */
+ * table, bit 2 height table, bit 3 traps, bit 4 dipole pairs, bit 5 field torque.  The steps, the queries below and the
+ * ensembles evaluate every term that is on. */
 int rbl_set_pair_table(rbl_ctx *ctx, const double *U, const double *dU, int n, double r_min, double r_cut, int on);
 int rbl_get_pair_table(const rbl_ctx *ctx, int *n, double *r_min, double *r_cut, int *on, double *coef);
 int rbl_set_height_table(rbl_ctx *ctx, const double *U, const double *dU, int n, double h_min, double h_cut, int on);
 int rbl_get_height_table(const rbl_ctx *ctx, int *n, double *h_min, double *h_cut, int *on, double *coef);
 int rbl_set_traps(rbl_ctx *ctx, const double *k3, const double *X0, int n_bodies, int on);
 int rbl_get_traps(const rbl_ctx *ctx, int *n_bodies, int *on, double *k3, double *X0);
+int rbl_set_dipoles(rbl_ctx *ctx, const double *m_body, int n_bodies, double c_dd, double r_core, double r_cut, int on);
+int rbl_get_dipoles(const rbl_ctx *ctx, int *n_bodies, double *c_dd, double *r_core, double *r_cut, int *on, double *m_body);
+int rbl_set_magnetic_field(rbl_ctx *ctx, const double B0[3], const double B1[3], const double B2[3], double omega, int on);
+int rbl_get_magnetic_field(const rbl_ctx *ctx, double *B9, double *omega, int *on);
+int rbl_set_field_time(rbl_ctx *ctx, const double *t, int n);
+int rbl_get_field_time(const rbl_ctx *ctx, int *n, double *t);
 int rbl_interactions_active(const rbl_ctx *ctx, int *mask);
 int rbl_interaction_forces_dev(rbl_ctx *ctx, double *d_f_blob, double *d_FT_body, double *energy);
 int rbl_interaction_forces(rbl_ctx *ctx, double *f_blob, double *FT_body, double *energy);
@@ -702,6 +741,8 @@ int rbl_ensemble_step_brownian_mixed(rbl_ctx *ctx, const uint8_t *prescribed, co
  * mask one entry per velocity component (prescribed[R 6 N_bod], the steps of rbl_ensemble_step_mixed_dof; 0 and 1: whole bodies);
  * such a run is deterministic only: with brownian != 0 and kBT > 1e-10 it is refused, that step's drift term is not derived.  Everything in the options is
  * constant over the run; the force model (section 4) and the flow model (section 8) enter every step at that step's q^n.
+ * The one input that moves is the magnetic field's clock (section 4): replica r evaluates B at its field time + dt accepted[r],
+ * and the context's field time itself is left as it was.
  *
  * Noise: drawn on the device.  Step n of the run (n = 0, 1, ... counts the run's steps, rejected ones included) draws what
  * rbl_ensemble_step_brownian(W = NULL, seed + n) draws; injected noise is not offered.  kBT <= 1e-10: the deterministic step.

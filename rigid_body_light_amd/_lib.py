@@ -89,6 +89,12 @@ def lib():
         L.rbl_set_traps.argtypes = [vp, vp, vp, C.c_int, C.c_int]
         L.rbl_get_traps.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp]
         L.rbl_interactions_active.argtypes = [vp, C.POINTER(C.c_int)]
+        L.rbl_set_dipoles.argtypes = [vp, vp, C.c_int, dbl, dbl, dbl, C.c_int]
+        L.rbl_get_dipoles.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int), vp]
+        L.rbl_set_magnetic_field.argtypes = [vp, vp, vp, vp, dbl, C.c_int]
+        L.rbl_get_magnetic_field.argtypes = [vp, vp, C.POINTER(dbl), C.POINTER(C.c_int)]
+        L.rbl_set_field_time.argtypes = [vp, vp, C.c_int]
+        L.rbl_get_field_time.argtypes = [vp, C.POINTER(C.c_int), vp]
         L.rbl_interaction_forces_dev.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_forces.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
@@ -142,6 +148,34 @@ def tabulate(U, dU, lo, hi, n):
     x = np.linspace(float(lo), float(hi), int(n))
     return (np.ascontiguousarray(np.broadcast_to(np.asarray(U(x), dtype=np.float64), x.shape)),
             np.ascontiguousarray(np.broadcast_to(np.asarray(dU(x), dtype=np.float64), x.shape)))
+
+
+def dipole_args(who, m_body, c_dd, r_core):
+    """the checks set_dipoles can make before the library is called -> contiguous float64 m_body (n, 3), r_core as a float.
+    r_core=None is accepted only without the pair term (c_dd == 0), where no core is needed"""
+    import numpy as np
+    m = np.ascontiguousarray(m_body, dtype=np.float64)
+    if m.shape == (3,):
+        m = m.reshape(1, 3)
+    if m.ndim != 2 or m.shape[1] != 3 or not m.shape[0]:
+        raise ValueError("%s: m_body must have shape (3,) or (n, 3); got %s" % (who, m.shape))
+    if r_core is None:
+        if float(c_dd) != 0.0:
+            raise ValueError("%s: r_core is needed with c_dd != 0 (below it the pair energy is a quadratic form)" % who)
+        r_core = 0.0
+    return m, float(r_core)
+
+
+def field_args(who, B0, B1, B2):
+    """-> three contiguous float64 vectors of 3 (None: zeros)"""
+    import numpy as np
+    out = []
+    for name, B in (("B0", B0), ("B1", B1), ("B2", B2)):
+        B = np.zeros(3) if B is None else np.ascontiguousarray(B, dtype=np.float64)
+        if B.shape != (3,):
+            raise ValueError("%s: %s must have shape (3,); got %s" % (who, name, B.shape))
+        out.append(B)
+    return out
 
 
 def table_arrays(who, U, dU):
@@ -349,11 +383,11 @@ class DeviceContext:
         return dict(zip(("w", "eps_wall", "b_wall", "eps_blob", "b_blob", "r_cut"), list(v)), on=bool(on.value), a=self._a)
 
     def interactions_on(self):
-        """any term of the model is on: the built-in one, a pair table, a height table or the traps"""
+        """any term of the model is on: the built-in one, a pair table, a height table, the traps, dipole pairs, the field torque"""
         return self.interactions_active() != 0
 
     def interactions_active(self):
-        """bit 0 built-in terms, bit 1 pair table, bit 2 height table, bit 3 traps"""
+        """bit 0 built-in terms, bit 1 pair table, bit 2 height table, bit 3 traps, bit 4 dipole pairs, bit 5 field torque"""
         m = C.c_int(0)
         self._chk(self.L.rbl_interactions_active(self.h, C.byref(m)))
         return m.value
@@ -412,6 +446,62 @@ class DeviceContext:
         if n.value:
             self._chk(self.L.rbl_get_traps(self.h, None, None, k.ctypes.data, X0.ctypes.data))
         return dict(on=bool(on.value), k=k, X0=X0)
+
+    def set_dipoles(self, m_body, c_dd=0.0, r_core=None, r_cut=float("inf"), on=True):
+        """permanent magnetic moments fixed in the bodies: m_body (3,) -- every body alike -- or (n, 3), body frame, n the bodies
+        as set_traps counts them.  c_dd > 0 switches the dipole pairs between body centres on (c_dd: mu_0 / 4 pi in the caller's
+        units; r_core: below it the pair energy is a quadratic form, the force bounded; pairs beyond r_cut are skipped, the
+        energy is not shifted); the torque of set_magnetic_field needs the moments too.  m_body=None with on=False only switches
+        the dipoles off."""
+        if m_body is None and not on:
+            return self._chk(self.L.rbl_set_dipoles(self.h, None, 0, 0.0, 0.0, 0.0, 0))
+        m, r_core = dipole_args("set_dipoles", m_body, c_dd, r_core)
+        self._chk(self.L.rbl_set_dipoles(self.h, m.ctypes.data, m.shape[0], float(c_dd), r_core, float(r_cut), int(bool(on))))
+
+    def dipoles(self):
+        """{on, c_dd, r_core, r_cut, m_body (n, 3)} (n = 0: never set)"""
+        import numpy as np
+        n, on = C.c_int(0), C.c_int(0)
+        c_dd, r_core, r_cut = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        self._chk(self.L.rbl_get_dipoles(self.h, C.byref(n), C.byref(c_dd), C.byref(r_core), C.byref(r_cut), C.byref(on), None))
+        m = np.zeros((n.value, 3))
+        if n.value:
+            self._chk(self.L.rbl_get_dipoles(self.h, None, None, None, None, None, m.ctypes.data))
+        return dict(on=bool(on.value), c_dd=c_dd.value, r_core=r_core.value, r_cut=r_cut.value, m_body=m)
+
+    def set_magnetic_field(self, B0=None, B1=None, B2=None, omega=0.0, on=True):
+        """the uniform field B(t) = B0 + B1 cos(omega t) + B2 sin(omega t), lab frame (None: zeros), t the field time of
+        set_field_time: torque m x B on every body that carries a moment (set_dipoles), no force.  B0 = B1 = B2 = None with
+        on=False only switches the field off."""
+        if B0 is None and B1 is None and B2 is None and not on:
+            return self._chk(self.L.rbl_set_magnetic_field(self.h, None, None, None, 0.0, 0))
+        B0, B1, B2 = field_args("set_magnetic_field", B0, B1, B2)
+        self._chk(self.L.rbl_set_magnetic_field(self.h, B0.ctypes.data, B1.ctypes.data, B2.ctypes.data, float(omega), int(bool(on))))
+
+    def magnetic_field(self):
+        """{on, omega, B0, B1, B2}"""
+        import numpy as np
+        B, om, on = np.zeros((3, 3)), C.c_double(0.0), C.c_int(0)
+        self._chk(self.L.rbl_get_magnetic_field(self.h, B.ctypes.data, C.byref(om), C.byref(on)))
+        return dict(on=bool(on.value), omega=om.value, B0=B[0].copy(), B1=B[1].copy(), B2=B[2].copy())
+
+    def set_field_time(self, t):
+        """the time the field is evaluated at: a number, or one per replica of an ensemble.  No step advances it; inside
+        ensemble_run replica r's clock runs as t[r] + dt * (its accepted steps) and the value set here stays"""
+        import numpy as np
+        t = np.ascontiguousarray(np.atleast_1d(np.asarray(t, dtype=np.float64)))
+        if t.ndim != 1:
+            raise ValueError("set_field_time: t must be a number or one-dimensional; got shape %s" % (t.shape,))
+        self._chk(self.L.rbl_set_field_time(self.h, t.ctypes.data, t.size))
+
+    def field_time(self):
+        """the field time(s) as set, (n,)"""
+        import numpy as np
+        n = C.c_int(0)
+        self._chk(self.L.rbl_get_field_time(self.h, C.byref(n), None))
+        t = np.zeros(n.value)
+        self._chk(self.L.rbl_get_field_time(self.h, None, t.ctypes.data))
+        return t
 
     def interaction_forces_dev(self, d_f_blob, d_FT_body, energy=False):
         """PHYSICAL forces at the current configuration into device buffers (addresses or None); energy=True also returns the

@@ -615,6 +615,52 @@ struct CManyBodies {
     if (k.size() != X0.size() || k.size() % 3 || !k.size()) throw std::runtime_error("set_traps: k and X0 must both hold 3 entries per body");
     check(rbl_set_traps(ctx, k.data(), X0.data(), (int)(k.size() / 3), on ? 1 : 0));
   }
+  // m: 3 entries per body; None with on = false only switches the dipoles off
+  void set_dipoles(py::object m, double c_dd, double r_core, double r_cut, bool on)
+  {
+    if (m.is_none()) { check(rbl_set_dipoles(ctx, nullptr, 0, c_dd, r_core, r_cut, on ? 1 : 0)); return; }
+    darr ma = m.cast<darr>();
+    if (ma.size() % 3 || !ma.size()) throw std::runtime_error("set_dipoles: m_body must hold 3 entries per body");
+    check(rbl_set_dipoles(ctx, ma.data(), (int)(ma.size() / 3), c_dd, r_core, r_cut, on ? 1 : 0));
+  }
+  py::dict dipoles() const
+  {
+    int n = 0, on = 0;
+    double c_dd = 0.0, r_core = 0.0, r_cut = 0.0;
+    rbl_get_dipoles(ctx, &n, &c_dd, &r_core, &r_cut, &on, nullptr);
+    darr m(std::vector<py::ssize_t>{(py::ssize_t)n, 3});
+    if (n) rbl_get_dipoles(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, m.mutable_data());
+    py::dict d;
+    d["on"] = on != 0; d["c_dd"] = c_dd; d["r_core"] = r_core; d["r_cut"] = r_cut; d["m_body"] = m;
+    return d;
+  }
+  void set_magnetic_field(py::object B0, py::object B1, py::object B2, double omega, bool on)
+  {
+    if (B0.is_none() && B1.is_none() && B2.is_none()) { check(rbl_set_magnetic_field(ctx, nullptr, nullptr, nullptr, omega, on ? 1 : 0)); return; }
+    darr b[3] = {B0.cast<darr>(), B1.cast<darr>(), B2.cast<darr>()};
+    for (const darr &v : b)
+      if (v.size() != 3) throw std::runtime_error("set_magnetic_field: B0, B1 and B2 must have 3 entries each");
+    check(rbl_set_magnetic_field(ctx, b[0].data(), b[1].data(), b[2].data(), omega, on ? 1 : 0));
+  }
+  py::dict magnetic_field() const
+  {
+    darr B(std::vector<py::ssize_t>{3, 3});
+    double omega = 0.0;
+    int on = 0;
+    rbl_get_magnetic_field(ctx, B.mutable_data(), &omega, &on);
+    py::dict d;
+    d["on"] = on != 0; d["omega"] = omega; d["B"] = B;
+    return d;
+  }
+  void set_field_time(darr t) { check(rbl_set_field_time(ctx, t.data(), (int)t.size())); }
+  darr field_time() const
+  {
+    int n = 0;
+    rbl_get_field_time(ctx, &n, nullptr);
+    darr t(n);
+    rbl_get_field_time(ctx, nullptr, t.mutable_data());
+    return t;
+  }
   int interactions_active() const
   {
     int m = 0;
@@ -765,7 +811,16 @@ PYBIND11_MODULE(c_rigid, m)
       .def("set_height_table", &CManyBodies::set_height_table, py::arg("U"), py::arg("dU"), py::arg("h_min"), py::arg("h_cut"),
            py::arg("on") = true)
       .def("set_traps", &CManyBodies::set_traps, py::arg("k"), py::arg("X0"), py::arg("on") = true)
-      .def("interactions_active", &CManyBodies::interactions_active, "bit 0 built-in terms, 1 pair table, 2 height table, 3 traps")
+      .def("set_dipoles", &CManyBodies::set_dipoles, py::arg("m_body"), py::arg("c_dd"), py::arg("r_core"), py::arg("r_cut"),
+           py::arg("on") = true)
+      .def("dipoles", &CManyBodies::dipoles)
+      .def("set_magnetic_field", &CManyBodies::set_magnetic_field, py::arg("B0"), py::arg("B1"), py::arg("B2"), py::arg("omega"),
+           py::arg("on") = true)
+      .def("magnetic_field", &CManyBodies::magnetic_field)
+      .def("set_field_time", &CManyBodies::set_field_time, py::arg("t"))
+      .def("field_time", &CManyBodies::field_time)
+      .def("interactions_active", &CManyBodies::interactions_active,
+           "bit 0 built-in terms, 1 pair table, 2 height table, 3 traps, 4 dipole pairs, 5 field torque")
       .def("interaction_forces", &CManyBodies::interaction_forces, "force model's body forces/torques, reference convention (-K^T f)")
       .def("interaction_energy", &CManyBodies::interaction_energy)
       .def("velocity_field", &CManyBodies::velocity_field, "fluid velocity at points from blob forces", py::arg("points"),

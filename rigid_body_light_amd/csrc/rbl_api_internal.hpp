@@ -141,7 +141,7 @@ int step_upload_W(rbl_ctx *c, const double *W, double **d_W);
 int step_midpoint(rbl_ctx *c, const std::function<int(double *, double *)> &rhs, const std::function<int(double *)> &solve);
 
 // ---- rbl_forces.hip -----------------------------------------------------------------------------------------------
-// any term of the model is switched on: the built-in one, a pair table, a height table or the traps
+// any term of the model is switched on: the built-in one, a pair table, a height table, the traps, dipole pairs or the field torque
 bool ia_any(const rbl_ctx *c);
 // the model's PHYSICAL forces at the context's configuration: d_f (3 N, may be NULL), d_FT = K^T f (6 N_bod, may be NULL),
 // per-blob energies d_e (N, may be NULL); enqueued on the context's stream under RBL_T_FORCES
@@ -150,11 +150,12 @@ int ia_eval(rbl_ctx *c, double *d_f, double *d_FT, double *d_e);
 // device flags are checked (a neighbour-list overflow fails the step).  No-op while the model is off.
 int ia_add_to_step_force(rbl_ctx *c, double *d_force);
 // the model for `reps` independent copies of N_bod bodies (an ensemble, rbl_ensemble.hip): body centres d_X (3 N_bod reps), blob
-// positions and lever arms of all copies; steric pairs only inside a copy.  d_work: ia_batch_bytes; *d_f -> the blob forces
-// (3 N reps, inside d_work); d_FT (6 N_bod reps) and per-blob energies d_e may be NULL
+// positions and lever arms of all copies; steric and dipole pairs only inside a copy.  d_Q (4 N_bod reps): the orientations, for
+// the dipoles.  d_work: ia_batch_bytes; *d_f -> the blob forces (3 N reps, inside d_work); d_FT (6 N_bod reps) and per-blob
+// energies d_e may be NULL.  d_accepted (a run): copy r evaluates the field at its field time + dt * d_accepted[r]
 size_t ia_batch_bytes(int N_bod, int N_blb, int reps);
-int ia_eval_batch(rbl_ctx *c, const double *d_X, const double *d_pos, const double *d_lever, int N_bod, int reps, void *d_work,
-                  double **d_f, double *d_FT, double *d_e, unsigned *d_err);
+int ia_eval_batch(rbl_ctx *c, const double *d_X, const double *d_Q, const double *d_pos, const double *d_lever, int N_bod, int reps,
+                  void *d_work, double **d_f, double *d_FT, double *d_e, unsigned *d_err, const int *d_accepted = nullptr);
 
 // ---- rbl_flow.hip -------------------------------------------------------------------------------------------------
 // the model's checks that need no device (wall consistency, the pattern's structure, n_scale against n_bod bodies); RBL_OK while

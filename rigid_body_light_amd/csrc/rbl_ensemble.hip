@@ -504,9 +504,9 @@ int ens_finish(rbl_ctx *c, const EnsWork &w, int R, int *iters, double *resid, b
 // section 8) goes the same way: one launch adds its term at q^n to every replica's slip.  *SL -> the slip the right-hand side
 // takes: the caller's, the term, their sum, or NULL for zero.  resident (a run, rbl_ensemble_run): nothing is uploaded -- w.F
 // holds F_body since the run began and slip is the DEVICE copy made then, which the flow model's term is added to into w.slip
-// (never in place: the copy serves every step)
+// (never in place: the copy serves every step).  accepted (a run): the replicas' step counters, the clock of the magnetic field
 int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *slip, const double **FT, const double **SL,
-              bool model = true, bool resident = false)
+              bool model = true, bool resident = false, const int *accepted = nullptr)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
   const size_t n3 = (size_t)3 * Nb * nbl, nb6 = (size_t)6 * Nb;
@@ -521,7 +521,7 @@ int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *
   *FT = nullptr;
   if (model && ia_any(c)) {
     double *f = nullptr;
-    if ((rc = ia_eval_batch(c, X, w.pos, w.lever, Nb, R, w.ia, &f, w.FT, nullptr, w.gerr))) return rc;
+    if ((rc = ia_eval_batch(c, X, Q, w.pos, w.lever, Nb, R, w.ia, &f, w.FT, nullptr, w.gerr, accepted))) return rc;
     *FT = w.FT;
   }
   bool have_slip = slip != nullptr;
@@ -613,6 +613,7 @@ struct EnsStepIn {
   const double *F_body = nullptr, *slip = nullptr, *W = nullptr;
   bool resident = false;
   int64_t chol_err = 0;
+  const int *accepted = nullptr;            // a run: the device counters of accepted steps, the field's clock (section 4)
 };
 
 // the mask as the caller gave it: per entries per body (the solver is told which, k_gmres_small's `per`)
@@ -628,7 +629,7 @@ int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_i
   const double *FT, *SL;
   int rc;
   if (mixed && !in.resident && (rc = ens_upload_mask(c, w, in.prescribed, in.per))) return rc;
-  if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, move, in.resident))) return rc;
+  if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, move, in.resident, in.accepted))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb;
   const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb;
   const long tot = (long)R * (n3 + nb6);
@@ -677,7 +678,7 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
   if (in.W) { if ((rc = copy_h2d(c, w.W, in.W, sizeof(double) * 3 * (size_t)n3 * R))) return rc; }
   else rbl_launch_normal_batched(c->stream, seed, 3 * n3, R, w.W);            // rand_vector (:730-741), one draw per replica
   const double *FT, *SL;
-  if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, true, in.resident))) return rc;
+  if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, true, in.resident, in.accepted))) return rc;
   const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
   // dense root of every replica: B M B (:667-669), lower Cholesky (:670-671), L W1 and L W2 (:672)
   const RblParams P = rbl_make_params(S.a, S.eta);
@@ -785,6 +786,7 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, bool brownian, rbl_run_out *out)
   EnsStepIn in;
   in.prescribed = o.prescribed; in.per = o.prescribed_per == 6 ? 6 : 1;
   in.slip = o.slip ? b.slip : nullptr; in.resident = true; in.chol_err = 1;
+  in.accepted = b.accepted;
   EnsRunStatus hs = {0, 0, 0u, 0};
   int enq = 0;
   for (int n = 0; n < o.n_steps; ++n) {
@@ -1067,7 +1069,7 @@ int rbl_ensemble_interaction_forces(rbl_ctx *c, double *FT_body, double *energy)
   const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
   rbl_launch_body_geom(c->stream, X, Q, ens_cfg(c), nbl, (int64_t)R * N, w.lever, w.pos);
   double *f = nullptr;
-  if ((rc = ia_eval_batch(c, X, w.pos, w.lever, Nb, R, w.ia, &f, w.FT, w.e, w.gerr))) return rc;
+  if ((rc = ia_eval_batch(c, X, Q, w.pos, w.lever, Nb, R, w.ia, &f, w.FT, w.e, w.gerr))) return rc;
   std::vector<double> FT(nb6 * R), e(N * R);
   if ((rc = copy_d2h(c, FT.data(), w.FT, sizeof(double) * FT.size()))) return rc;
   if ((rc = copy_d2h(c, e.data(), w.e, sizeof(double) * e.size()))) return rc;

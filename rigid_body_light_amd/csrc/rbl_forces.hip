@@ -22,6 +22,14 @@
 //                        not been built.  k_blob_interactions itself is the TAB = 0 instantiation with the argument list it
 //                        always had.
 //   k_body_traps         harmonic traps on the body centres, after K^T f: one lane per body.
+//   k_body_dipoles<NT>   permanent dipoles fixed in the bodies, after the traps: one workgroup of NT lanes per body i (one wave
+//                        for windows of up to 512 bodies, four beyond).  Lane t takes the partners j = t, t + NT, ... of i's
+//                        window by their window-local index, rotates the partner's body-frame moment with its quaternion and
+//                        accumulates force, torque and pair energy on i in fp64 registers; rbl_block_sum adds the lanes in one
+//                        fixed tree and lane 0 adds the result, and the torque and energy of the uniform field B(t), to
+//                        FT[6 i ..] and to the energy entry of the body's first blob.  No atomics; the order depends on the
+//                        window-local indices alone, so a replica of an ensemble is bitwise the single context.  Every
+//                        partner is read once per workgroup, so nothing is staged: the only LDS is the reduction's.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -29,6 +37,7 @@
 #include <vector>
 
 #include "rbl_api_internal.hpp"
+#include "rbl_body_dev.hpp"
 
 namespace {
 
@@ -224,6 +233,96 @@ __global__ __launch_bounds__(256) void k_body_traps(const double *__restrict__ X
   if (e) e[(size_t)i * N_blb] += E;
 }
 
+// the dipole model as the kernel takes it (by value).  B: B0 | B1 | B2
+struct IaMag {
+  double B[9], omega, dt, c_dd, r_core, r_cut;
+  int pairs, field;                                      // the pair term (c_dd > 0) / the field torque is on
+  int per_m, per_t;                                      // entries of the moment array (body i reads i % per_m) and of the field times
+};
+
+// B at replica r's field time t = t0 + dt * n, n = the replica's accepted steps so far inside a run (accepted == NULL, the
+// one-step calls: 0).  The product and the sum are rounded separately, as the host's t0 + dt * n is: a run is bitwise the loop
+__device__ __forceinline__ void ia_field_B(const IaMag &M, const double *__restrict__ tf, const int *__restrict__ accepted, int r,
+                                           double (&B)[3])
+{
+  const double n = accepted ? (double)accepted[r] : 0.0;
+  const double t = __dadd_rn(tf[M.per_t == 1 ? 0 : r], __dmul_rn(M.dt, n));
+  double sn, cs;
+  sincos(__dmul_rn(M.omega, t), &sn, &cs);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) B[c] = M.B[c] + M.B[3 + c] * cs + M.B[6 + c] * sn;
+}
+
+// lab-frame moment of body j: R(Q_j) m_body
+__device__ __forceinline__ void ia_lab_moment(const double *__restrict__ Q, const double *__restrict__ mb, int j, int per_m,
+                                              double (&m)[3])
+{
+  double R[9];
+  quat_rot(Q + 4 * (size_t)j, R);
+  const double *b = mb + 3 * (size_t)(j % per_m);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) m[c] = R[3 * c] * b[0] + R[3 * c + 1] * b[1] + R[3 * c + 2] * b[2];
+}
+
+// dipole pairs between the centres of the bodies of one window and the field torque (include/rbl.h section 4), added to FT and
+// to the energy entry of the body's first blob after the traps on the same stream: one order
+template <int NT>
+__global__ __launch_bounds__(NT) void k_body_dipoles(const double *__restrict__ X, const double *__restrict__ Q,
+                                                     const double *__restrict__ mb, const double *__restrict__ tf,
+                                                     const int *__restrict__ accepted, int win, int N_blb, IaMag M,
+                                                     double *__restrict__ FT, double *__restrict__ e)
+{
+  __shared__ double red[7][NT];
+  const int i = blockIdx.x, t = threadIdx.x;
+  const int jb = i - i % win;
+  double mi[3];
+  ia_lab_moment(Q, mb, i, M.per_m, mi);
+  const double xi = X[3 * (size_t)i], yi = X[3 * (size_t)i + 1], zi = X[3 * (size_t)i + 2];
+  double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // force, torque, sum of the pair energies
+  if (M.pairs) {
+    for (int j = jb + t; j < jb + win; j += NT) {
+      if (j == i) continue;
+      const double rx = xi - X[3 * (size_t)j], ry = yi - X[3 * (size_t)j + 1], rz = zi - X[3 * (size_t)j + 2];
+      const double d2 = rx * rx + ry * ry + rz * rz;
+      const double d = sqrt(d2);
+      if (d > M.r_cut) continue;                         // skipped, not multiplied by zero (r_cut = +inf: every pair)
+      double mj[3];
+      ia_lab_moment(Q, mb, j, M.per_m, mj);
+      const bool core = d < M.r_core;                    // below the core s is the constant r_core: U is a quadratic form in r
+      const double is = 1.0 / (core ? M.r_core : d), is2 = is * is, is3 = is2 * is, is5 = is3 * is2;
+      const double a = mi[0] * rx + mi[1] * ry + mi[2] * rz, b = mj[0] * rx + mj[1] * ry + mj[2] * rz;
+      const double mm = mi[0] * mj[0] + mi[1] * mj[1] + mi[2] * mj[2];
+      const double k5 = 3.0 * M.c_dd * is5;
+      const double kr = core ? 0.0 : mm - 5.0 * a * b * is2;       // d >= r_core > 0: 1 / d^2 = is2
+      acc[0] += k5 * (a * mj[0] + b * mi[0] + kr * rx);
+      acc[1] += k5 * (a * mj[1] + b * mi[1] + kr * ry);
+      acc[2] += k5 * (a * mj[2] + b * mi[2] + kr * rz);
+      const double gb = k5 * b, g3 = M.c_dd * is3;               // the partner's field at i: gb r - g3 m_j
+      const double hx = gb * rx - g3 * mj[0], hy = gb * ry - g3 * mj[1], hz = gb * rz - g3 * mj[2];
+      acc[3] += mi[1] * hz - mi[2] * hy;
+      acc[4] += mi[2] * hx - mi[0] * hz;
+      acc[5] += mi[0] * hy - mi[1] * hx;
+      acc[6] += M.c_dd * (mm * is3 - 3.0 * a * b * is5);
+    }
+    rbl_block_sum<7, NT>(acc, red, t);
+  }
+  if (t != 0) return;
+  double E = 0.5 * acc[6];                               // every body carries half of each of its pair energies
+  if (M.field) {
+    double B[3];
+    ia_field_B(M, tf, accepted, i / win, B);
+    acc[3] += mi[1] * B[2] - mi[2] * B[1];
+    acc[4] += mi[2] * B[0] - mi[0] * B[2];
+    acc[5] += mi[0] * B[1] - mi[1] * B[0];
+    E -= mi[0] * B[0] + mi[1] * B[1] + mi[2] * B[2];
+  }
+  if (FT) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) FT[6 * (size_t)i + c] += acc[c];
+  }
+  if (e) e[(size_t)i * N_blb] += E;
+}
+
 struct IaLayout {
   double *f, *e, *ft;
   int *cnt, *list, *np;
@@ -262,7 +361,10 @@ int ia_reserve(rbl_ctx *c, IaLayout &L)
 
 }  // namespace
 
-bool ia_any(const rbl_ctx *c) { return c->ia_on || c->ia_pt.on || c->ia_ht.on || c->ia_tr_on; }
+static bool ia_dp_pairs(const rbl_ctx *c) { return c->ia_dp_on && c->ia_dp_c > 0.0; }
+static bool ia_dp_field(const rbl_ctx *c) { return c->ia_dp_on && c->ia_mf_on; }
+
+bool ia_any(const rbl_ctx *c) { return c->ia_on || c->ia_pt.on || c->ia_ht.on || c->ia_tr_on || ia_dp_pairs(c) || ia_dp_field(c); }
 
 // the tables' coefficients and the traps on the device (once per rbl_set_pair_table / rbl_set_height_table / rbl_set_traps):
 // pair coefficients | height coefficients | trap k | trap X0.  4 (n - 1) doubles per table: every interval starts 32-byte aligned
@@ -285,6 +387,22 @@ static int ia_upload(rbl_ctx *c)
   return RBL_OK;
 }
 
+// the body-frame moments and the field times on the device: moments | times.  rbl_set_dipoles invalidates both, rbl_set_field_time
+// the times alone, so the loop that sets the time before every step uploads n doubles per step and not the moments again
+static int ia_mag_upload(rbl_ctx *c)
+{
+  if (c->ia_mag_valid && c->ia_ft_valid) return RBL_OK;
+  const size_t nm = c->ia_dp_m.size(), nt = c->ia_ft.size(), need = sizeof(double) * (nm + nt);
+  const bool moments = !c->ia_mag_valid || need > c->d_iam.bytes;     // a buffer that has to grow loses what it held
+  int rc = rbl_dev_reserve(c, c->d_iam, need); if (rc) return rc;
+  double *d = (double *)c->d_iam.p;
+  if (moments && nm && (rc = copy_h2d(c, d, c->ia_dp_m.data(), sizeof(double) * nm))) return rc;
+  if ((rc = copy_h2d(c, d + nm, c->ia_ft.data(), sizeof(double) * nt))) return rc;
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  c->ia_mag_valid = c->ia_ft_valid = true;
+  return RBL_OK;
+}
+
 static IaTab ia_tab_args(const rbl_ctx::IaTable &t, const double *d_coef)
 {
   IaTab T = {};
@@ -300,8 +418,10 @@ static IaTab ia_tab_args(const rbl_ctx::IaTable &t, const double *d_coef)
 
 // the model over n_win windows of win bodies each (resident X of the body centres, blob positions and lever arms): neighbour
 // lists inside each window, the pair kernel, K^T f.  d_f (3 N) is required here; d_FT (6 N_bod total) and d_e may be NULL.
-static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_pos, const double *d_lever, int win, int n_win, double *d_cl,
-                     double *d_f, double *d_FT, double *d_e, unsigned *d_err)
+// d_Q: the orientations beside d_X (the dipoles); d_accepted: a run's per-replica step counters, the field's clock (NULL: the
+// field time as set)
+static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const double *d_pos, const double *d_lever, int win, int n_win,
+                     double *d_cl, double *d_f, double *d_FT, double *d_e, unsigned *d_err, const int *d_accepted = nullptr)
 {
   const RblBodyState &S = c->S;
   if (c->ia_on && !(c->ia_r_cut >= 2.0 * S.a))           // the built-in term's own check: a context with only a table on has r_cut = 0
@@ -310,7 +430,14 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_pos, const d
   const size_t ntr = c->ia_tr_k.size() / 3;
   if (c->ia_tr_on && ntr != (size_t)win && ntr != (size_t)nbod)
     return rbl_fail(c, RBL_ERR_STATE, "interactions: the traps hold neither one entry per body nor one per body of every replica (rbl_set_traps)");
+  const bool dp_pairs = ia_dp_pairs(c), dp_field = ia_dp_field(c), dp = dp_pairs || dp_field;
+  const size_t ndm = c->ia_dp_m.size() / 3, nft = c->ia_ft.size();
+  if (dp && ndm != 1 && ndm != (size_t)win && ndm != (size_t)nbod)
+    return rbl_fail(c, RBL_ERR_STATE, "interactions: the dipole moments hold neither one entry, nor one per body, nor one per body of every replica (rbl_set_dipoles)");
+  if (dp_field && n_win > 1 && nft != 1 && nft != (size_t)n_win)
+    return rbl_fail(c, RBL_ERR_STATE, "interactions: the field time holds neither one entry nor one per replica (rbl_set_field_time)");
   int rc = ia_upload(c); if (rc) return rc;
+  if (dp && (rc = ia_mag_upload(c))) return rc;
   RblPhase ph(c, RBL_T_FORCES);
   IaLayout L = ia_layout(d_cl, nbod, S.N_blb, cap);
   double R2 = 0.0;                                       // R_body: largest blob distance from the centre, body frame (mean removed)
@@ -349,6 +476,20 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_pos, const d
     hipLaunchKernelGGL(k_body_traps, dim3((unsigned)((nbod + 255) / 256)), dim3(256), 0, c->stream, d_X, k3, k3 + 3 * ntr, nbod,
                        (int)ntr, S.N_blb, d_FT, d_e);
   }
+  if (dp && (d_FT || d_e)) {
+    IaMag M;
+    std::memcpy(M.B, c->ia_mf_B, sizeof(M.B));
+    M.omega = c->ia_mf_omega; M.dt = S.dt; M.c_dd = c->ia_dp_c; M.r_core = c->ia_dp_rcore; M.r_cut = c->ia_dp_rcut;
+    M.pairs = dp_pairs ? 1 : 0; M.field = dp_field ? 1 : 0;
+    M.per_m = (int)ndm; M.per_t = n_win > 1 ? (int)nft : 1;  // a single context uses entry 0
+    const double *mb = (const double *)c->d_iam.p, *tf = mb + 3 * ndm;
+    if (win > 512)
+      hipLaunchKernelGGL(k_body_dipoles<256>, dim3((unsigned)nbod), dim3(256), 0, c->stream, d_X, d_Q, mb, tf, d_accepted, win,
+                         S.N_blb, M, d_FT, d_e);
+    else
+      hipLaunchKernelGGL(k_body_dipoles<64>, dim3((unsigned)nbod), dim3(64), 0, c->stream, d_X, d_Q, mb, tf, d_accepted, win,
+                         S.N_blb, M, d_FT, d_e);
+  }
   return RBL_OK;
 }
 
@@ -358,7 +499,8 @@ int ia_eval(rbl_ctx *c, double *d_f, double *d_FT, double *d_e)
   const RblBodyState &S = c->S;
   IaLayout L;
   if ((rc = ia_reserve(c, L))) return rc;
-  if ((rc = ia_launch(c, (const double *)c->d_XQ.p, (const double *)c->d_pos.p, (const double *)c->d_lever.p, S.N_bod, 1,
+  const double *dX = (const double *)c->d_XQ.p;
+  if ((rc = ia_launch(c, dX, dX + 3 * (size_t)S.N_bod, (const double *)c->d_pos.p, (const double *)c->d_lever.p, S.N_bod, 1,
                       (double *)c->d_ia.p, d_f ? d_f : L.f, d_FT, d_e, c->d_err))) return rc;
   c->ia_nb = S.N_bod; c->ia_nblb = S.N_blb; c->ia_cap = ia_cap(S.N_bod);
   return RBL_OK;
@@ -369,12 +511,12 @@ size_t ia_batch_bytes(int N_bod, int N_blb, int reps)
   return ia_bytes(N_bod * reps, N_blb, ia_cap(N_bod));
 }
 
-int ia_eval_batch(rbl_ctx *c, const double *d_X, const double *d_pos, const double *d_lever, int N_bod, int reps, void *d_work,
-                  double **d_f, double *d_FT, double *d_e, unsigned *d_err)
+int ia_eval_batch(rbl_ctx *c, const double *d_X, const double *d_Q, const double *d_pos, const double *d_lever, int N_bod, int reps,
+                  void *d_work, double **d_f, double *d_FT, double *d_e, unsigned *d_err, const int *d_accepted)
 {
   IaLayout L = ia_layout(d_work, N_bod * reps, c->S.N_blb, ia_cap(N_bod));
   *d_f = L.f;
-  return ia_launch(c, d_X, d_pos, d_lever, N_bod, reps, (double *)d_work, L.f, d_FT, d_e, d_err);
+  return ia_launch(c, d_X, d_Q, d_pos, d_lever, N_bod, reps, (double *)d_work, L.f, d_FT, d_e, d_err, d_accepted);
 }
 
 int ia_add_to_step_force(rbl_ctx *c, double *d_force)
@@ -503,10 +645,90 @@ int rbl_get_traps(const rbl_ctx *c, int *n_bodies, int *on, double *k3, double *
   return RBL_OK;
 }
 
+// the dipoles: checks first, nothing is stored unless every one passes (include/rbl.h section 4)
+int rbl_set_dipoles(rbl_ctx *c, const double *m_body, int n_bodies, double c_dd, double r_core, double r_cut, int on)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (!m_body && !on) { c->ia_dp_on = false; return RBL_OK; }
+  if (!m_body) return rbl_fail(c, RBL_ERR_ARG, "set_dipoles: m_body must not be NULL");
+  if (n_bodies < 1) return rbl_fail(c, RBL_ERR_ARG, "set_dipoles: n_bodies must be >= 1");
+  for (size_t i = 0; i < 3 * (size_t)n_bodies; ++i)
+    if (!std::isfinite(m_body[i])) return rbl_fail(c, RBL_ERR_ARG, "set_dipoles: every value of m_body must be finite");
+  if (!std::isfinite(c_dd) || c_dd < 0.0) return rbl_fail(c, RBL_ERR_ARG, "set_dipoles: c_dd must be finite and >= 0");
+  if (c_dd > 0.0) {
+    if (!std::isfinite(r_core) || !(r_core > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "set_dipoles: r_core must be finite and positive while c_dd > 0");
+    if (std::isnan(r_cut) || !(r_cut > r_core)) return rbl_fail(c, RBL_ERR_ARG, "set_dipoles: r_cut must be larger than r_core (+inf: every pair) while c_dd > 0");
+  }
+  c->ia_dp_m.assign(m_body, m_body + 3 * (size_t)n_bodies);
+  c->ia_dp_c = c_dd; c->ia_dp_rcore = r_core; c->ia_dp_rcut = r_cut;
+  c->ia_dp_on = on != 0;
+  c->ia_mag_valid = c->ia_ft_valid = false;
+  return RBL_OK;
+}
+
+int rbl_get_dipoles(const rbl_ctx *c, int *n_bodies, double *c_dd, double *r_core, double *r_cut, int *on, double *m_body)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (n_bodies) *n_bodies = (int)(c->ia_dp_m.size() / 3);
+  if (c_dd) *c_dd = c->ia_dp_c;
+  if (r_core) *r_core = c->ia_dp_rcore;
+  if (r_cut) *r_cut = c->ia_dp_rcut;
+  if (on) *on = c->ia_dp_on ? 1 : 0;
+  if (m_body && !c->ia_dp_m.empty()) std::memcpy(m_body, c->ia_dp_m.data(), sizeof(double) * c->ia_dp_m.size());
+  return RBL_OK;
+}
+
+int rbl_set_magnetic_field(rbl_ctx *c, const double B0[3], const double B1[3], const double B2[3], double omega, int on)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (!B0 && !B1 && !B2 && !on) { c->ia_mf_on = false; return RBL_OK; }
+  if (!B0 || !B1 || !B2) return rbl_fail(c, RBL_ERR_ARG, "set_magnetic_field: B0, B1 and B2 must not be NULL");
+  const double *B[3] = {B0, B1, B2};
+  static const char *const name[3] = {"B0", "B1", "B2"};
+  for (int k = 0; k < 3; ++k)
+    for (int q = 0; q < 3; ++q)
+      if (!std::isfinite(B[k][q])) return rbl_fail(c, RBL_ERR_ARG, std::string("set_magnetic_field: every value of ") + name[k] + " must be finite");
+  if (!std::isfinite(omega)) return rbl_fail(c, RBL_ERR_ARG, "set_magnetic_field: omega must be finite");
+  for (int k = 0; k < 3; ++k) std::memcpy(c->ia_mf_B + 3 * k, B[k], 3 * sizeof(double));
+  c->ia_mf_omega = omega;
+  c->ia_mf_on = on != 0;
+  return RBL_OK;
+}
+
+int rbl_get_magnetic_field(const rbl_ctx *c, double *B9, double *omega, int *on)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (B9) std::memcpy(B9, c->ia_mf_B, sizeof(c->ia_mf_B));
+  if (omega) *omega = c->ia_mf_omega;
+  if (on) *on = c->ia_mf_on ? 1 : 0;
+  return RBL_OK;
+}
+
+int rbl_set_field_time(rbl_ctx *c, const double *t, int n)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (!t) return rbl_fail(c, RBL_ERR_ARG, "set_field_time: t must not be NULL");
+  if (n < 1) return rbl_fail(c, RBL_ERR_ARG, "set_field_time: n must be >= 1");
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(t[i])) return rbl_fail(c, RBL_ERR_ARG, "set_field_time: every value of t must be finite");
+  c->ia_ft.assign(t, t + n);
+  c->ia_ft_valid = false;
+  return RBL_OK;
+}
+
+int rbl_get_field_time(const rbl_ctx *c, int *n, double *t)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (n) *n = (int)c->ia_ft.size();
+  if (t) std::memcpy(t, c->ia_ft.data(), sizeof(double) * c->ia_ft.size());
+  return RBL_OK;
+}
+
 int rbl_interactions_active(const rbl_ctx *c, int *mask)
 {
   if (!c || !mask) return RBL_ERR_ARG;
-  *mask = (c->ia_on ? 1 : 0) | (c->ia_pt.on ? 2 : 0) | (c->ia_ht.on ? 4 : 0) | (c->ia_tr_on ? 8 : 0);
+  *mask = (c->ia_on ? 1 : 0) | (c->ia_pt.on ? 2 : 0) | (c->ia_ht.on ? 4 : 0) | (c->ia_tr_on ? 8 : 0) |
+          (ia_dp_pairs(c) ? 16 : 0) | (ia_dp_field(c) ? 32 : 0);
   return RBL_OK;
 }
 

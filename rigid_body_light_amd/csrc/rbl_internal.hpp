@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -216,6 +217,15 @@ struct rbl_ctx {
   std::vector<double> ia_tr_k, ia_tr_X0;            // 3 per body, ia_tr_k.size() / 3 bodies
   RblDevBuf d_iat;                                  // pair coefficients | height coefficients | trap k | trap X0 (ia_tab_valid)
   bool ia_tab_valid = false;
+  // permanent dipoles fixed in the bodies, a uniform field B(t) = B0 + B1 cos(omega t) + B2 sin(omega t) and its clock
+  bool ia_dp_on = false;
+  std::vector<double> ia_dp_m;                      // body-frame moments, 3 per entry (1, N_bod or R N_bod entries)
+  double ia_dp_c = 0.0, ia_dp_rcore = 0.0, ia_dp_rcut = std::numeric_limits<double>::infinity();   // c_dd (0: no pair term), core and cutoff of the pair term
+  bool ia_mf_on = false;
+  double ia_mf_B[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ia_mf_omega = 0.0;   // B0 | B1 | B2
+  std::vector<double> ia_ft = std::vector<double>(1, 0.0);   // field time: one entry, or one per replica
+  RblDevBuf d_iam;                                  // body-frame moments | field times
+  bool ia_mag_valid = false, ia_ft_valid = false;   // d_iam holds the current moments / the current field times
   RblDevBuf d_ia;                                   // f_blob | energy per blob | neighbour counts | lists | pairs per blob
   int ia_nb = 0, ia_nblb = 0, ia_cap = 0;           // shape of what d_ia holds (0: nothing evaluated yet)
   // ensemble of independent replicas (rbl_ensemble.hip; include/rbl.h section 5)

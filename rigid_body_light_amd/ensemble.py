@@ -269,6 +269,39 @@ class Ensemble:
             _fail("k and X0 must both have shape (%d, 3) or (%d, %d, 3); got %s and %s" % (nb, self.R, nb, k.shape, X0.shape))
         self.ctx.set_traps(k.reshape(-1, 3), X0.reshape(-1, 3), on=on)
 
+    def set_dipoles(self, m_body, c_dd=0.0, r_core=None, r_cut=np.inf, on=True):
+        """the permanent moments of RigidBody.set_dipoles: m_body of shape (3,) -- every body of every replica alike --,
+        (N_bod, 3), shared by every replica, or (R, N_bod, 3); dipole pairs only inside a replica"""
+        if m_body is None and not on:
+            return self.ctx.set_dipoles(None, on=False)
+        m = np.asarray(m_body, dtype=np.float64)
+        nb = self.N_bodies
+        if m.shape not in ((3,), (nb, 3), (self.R, nb, 3)):
+            _fail("m_body must have shape (3,), (%d, 3) or (%d, %d, 3); got %s" % (nb, self.R, nb, m.shape))
+        self.ctx.set_dipoles(m.reshape(-1, 3), c_dd=c_dd, r_core=r_core, r_cut=r_cut, on=on)
+
+    def dipoles(self):
+        return self.ctx.dipoles()
+
+    def set_magnetic_field(self, B0=None, B1=None, B2=None, omega=0.0, on=True):
+        """the uniform field of RigidBody.set_magnetic_field, one for all replicas"""
+        self.ctx.set_magnetic_field(B0, B1, B2, omega=omega, on=on)
+
+    def magnetic_field(self):
+        return self.ctx.magnetic_field()
+
+    def set_field_time(self, t):
+        """the field's clock: a number for all replicas or (R,), one per replica.  The one-step methods evaluate the field at
+        this time and do not advance it.  run() evaluates step by step at t[r] + dt * (replica r's accepted steps so far) and
+        leaves the value set here as it was: continue with t + dt * result.accepted"""
+        t = np.asarray(t, dtype=np.float64)
+        if t.shape not in ((), (1,), (self.R,)):
+            _fail("t must be a number or have shape (%d,); got %s" % (self.R, t.shape))
+        self.ctx.set_field_time(t)
+
+    def field_time(self):
+        return self.ctx.field_time()
+
     def interaction_forces(self):
         """body forces and torques of the model, (R, 6 N_bod), reference convention (-K^T f_phys)"""
         return self.ctx.ensemble_interaction_forces()[0]

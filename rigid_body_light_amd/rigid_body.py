@@ -20,7 +20,7 @@ and an imposed flow, a body-frame slip and stresslets (`set_background_flow`, `s
 import numpy as np
 
 from . import c_rigid as _ext
-from ._lib import table_arrays, tabulate  # noqa: F401
+from ._lib import dipole_args, field_args, table_arrays, tabulate  # noqa: F401
 
 _KBT_IN_WRAPPER = 1.0   # the reference wrapper passes kBT = 1 whatever the caller wants (src/Rigid.py:23)
 
@@ -239,6 +239,44 @@ class RigidBody:
         if k.ndim != 2 or k.shape[1] != 3 or k.shape != X0.shape:
             raise ValueError(f"set_traps: k and X0 must both have shape (N_bodies, 3). Got shapes: {k.shape} and {X0.shape}")
         self.cb.set_traps(k.reshape(-1), X0.reshape(-1), bool(on))
+
+    def set_dipoles(self, m_body, c_dd=0.0, r_core=None, r_cut=np.inf, on=True):
+        """Permanent magnetic moments fixed in the bodies (include/rbl.h section 4): m_body of shape (3,) -- every body alike --
+        or (N_bodies, 3), body frame; the lab-frame moment is R(Q) m_body.  c_dd > 0 adds the dipole pairs between the body
+        centres, U = c_dd [m_i.m_j / s^3 - 3 (m_i.r)(m_j.r) / s^5], s = max(|r|, r_core), skipped beyond r_cut (not shifted);
+        set_magnetic_field adds the torque m x B(t).  Both enter the body forces and torques of every step at q^n."""
+        if m_body is None and not on:
+            return self.cb.set_dipoles(None, 0.0, 0.0, 0.0, False)
+        m, r_core = dipole_args("set_dipoles", m_body, c_dd, r_core)
+        if m.shape[0] not in (1, self.N_bodies):
+            raise ValueError(f"set_dipoles: m_body must have shape (3,) or (N_bodies, 3). Got shape: {m.shape}")
+        self.cb.set_dipoles(m.reshape(-1), float(c_dd), r_core, float(r_cut), bool(on))
+
+    def dipoles(self):
+        """{on, c_dd, r_core, r_cut, m_body (n, 3)}"""
+        return dict(self.cb.dipoles())
+
+    def set_magnetic_field(self, B0=None, B1=None, B2=None, omega=0.0, on=True):
+        """The uniform field B(t) = B0 + B1 cos(omega t) + B2 sin(omega t), lab frame (None: zeros), evaluated at the field
+        time of set_field_time -- no step advances that clock.  Torque m x B on every body with a moment, no force."""
+        if B0 is None and B1 is None and B2 is None and not on:
+            return self.cb.set_magnetic_field(None, None, None, 0.0, False)
+        B0, B1, B2 = field_args("set_magnetic_field", B0, B1, B2)
+        self.cb.set_magnetic_field(B0, B1, B2, float(omega), bool(on))
+
+    def magnetic_field(self):
+        """{on, omega, B0, B1, B2}"""
+        d = dict(self.cb.magnetic_field())
+        B = d.pop("B")
+        d.update(B0=B[0].copy(), B1=B[1].copy(), B2=B[2].copy())
+        return d
+
+    def set_field_time(self, t):
+        """The time the field is evaluated at by the next steps and queries (default 0); the caller advances it."""
+        self.cb.set_field_time(np.atleast_1d(np.asarray(t, dtype=np.float64)))
+
+    def field_time(self):
+        return float(self.cb.field_time()[0])
 
     def interaction_forces(self):
         """The model's body forces and torques at the current configuration, 6 * N_bodies, in the reference convention

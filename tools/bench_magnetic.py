@@ -1,0 +1,166 @@
+"""What the dipole terms of the force model cost (include/rbl.h section 4: permanent moments, dipole pairs, field torque).
+
+  (a) eval        rbl_interaction_forces_dev at cfg 3 (200 x shell_N_642 above the wall): the built-in model alone and with
+                  dipoles, a rotating field and ALL pairs (r_cut = +inf) added; ms per evaluation.
+  (b) run         per-step time of a Brownian Ensemble.run at R = 256 replicas of 10 x shell_N_12 above the wall (dt = 1e-3), with the built-in
+                  model alone and with the dipole terms added.
+  (c) run_parent  the step of (b) with the new terms off, on THIS build and, with --parent-root, on a build of the parent commit
+                  (a checkout of it, built, anywhere on this machine).  The two alternate, visit by visit, each visit a fresh
+                  process that imports the package from its own root; the windows of all visits of a build are pooled.  The verdict
+                  line compares this build's median with the parent's against the PARENT's own window spread.
+
+Every window is timed by the host clock around its work and ends in a device synchronise; every line carries its windows and
+their spread (max - min) / median.  One JSON line per measurement, appended to --out.
+
+    python tools/bench_magnetic.py [--parent-root DIR] [--steps 200] [--rounds 5] [--visits 2] [--out profiles/magnetic.jsonl]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+R_RUN, NB, DT_RUN = 256, 10, 1e-3                            # dt as tools/bench_interaction_tables.py: no overlaps within a window
+BUILTIN = dict(w=0.3, eps_wall=1.0, b_wall=0.1, eps_blob=1.0, b_blob=0.05)
+
+
+def worker(args):
+    sys.path.insert(0, args.worker)
+    import torch
+    from rigid_body_light_amd import make_config
+    from rigid_body_light_amd._lib import DeviceContext
+    import rigid_body_light_amd
+    assert os.path.dirname(os.path.dirname(os.path.abspath(rigid_body_light_amd.__file__))) == os.path.abspath(args.worker)
+    assert torch.cuda.is_available(), "this benchmark needs a GPU"
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def line(mode, terms, ts, per, **more):
+        med = float(np.median(ts))
+        d = {"build": args.label, "mode": mode, "terms": terms, "windows_ms": [round(1e3 * t, 5) for t in ts],
+             "ms_per_" + per: round(1e3 * med, 5), "window_spread": round((max(ts) - min(ts)) / med, 4)}
+        d.update(more)
+        print("JSON " + json.dumps(d), flush=True)
+
+    def magnetic(ctx, n):
+        rng = np.random.default_rng(3)
+        ctx.set_dipoles(rng.standard_normal((n, 3)), c_dd=0.05, r_core=2.0, r_cut=np.inf)
+        ctx.set_magnetic_field(B1=[1.0, 0.0, 0.0], B2=[0.0, 0.0, -1.0], omega=3.0)
+        ctx.set_field_time(0.4)
+
+    for kind in args.kinds.split(","):
+        if kind == "eval":
+            c = make_config(200, 642, True)
+            nb = c["X"].shape[0]
+            ctx = DeviceContext(c["a"], c["eta"], True, cfg=c["cfg"], dt=c["dt"], stream_ptr=stream)
+            ctx.set_config(c["X"], c["Q"])
+            ctx.set_interactions(**BUILTIN)
+            FT = torch.empty(6 * nb, dtype=torch.float64, device="cuda:0")
+            for terms in ("builtin", "builtin+dipoles+field"):
+                if terms != "builtin":
+                    magnetic(ctx, nb)
+                for _ in range(args.warmup):
+                    ctx.interaction_forces_dev(None, FT.data_ptr())
+                ts = []
+                for _ in range(args.rounds):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(args.evals):
+                        ctx.interaction_forces_dev(None, FT.data_ptr())
+                    torch.cuda.synchronize()
+                    ts.append((time.perf_counter() - t0) / args.evals)
+                ctx.sync_check()
+                line("eval", terms, ts, "eval", workload="cfg3_200x642_wall", evals_per_window=args.evals,
+                     active=ctx.interactions_active(), dipole_pairs=nb * (nb - 1))
+            ctx.close()
+        else:                                                   # "run": both variants; "run_off": the new terms off only
+            c = make_config(NB, 12, True)
+            X, Q = np.repeat(c["X"][None], R_RUN, axis=0), np.repeat(c["Q"][None], R_RUN, axis=0)
+            for terms in (("builtin",) if kind == "run_off" else ("builtin", "builtin+dipoles+field")):
+                e = DeviceContext(c["a"], 1.0, True, cfg=c["cfg"], dt=DT_RUN, kBT=1.0, stream_ptr=stream)
+                e.ensemble_set_config(X, Q)
+                e.set_interactions(**BUILTIN)
+                if terms != "builtin":
+                    magnetic(e, NB)
+                F = np.zeros((R_RUN, 6 * NB))
+
+                def run(n, seed):
+                    res, rc = e.ensemble_run(n, F_body=F, brownian=True, seed=seed, max_iter=50, rtol=1e-8)
+                    assert rc == 0, res.error
+                    return res
+                run(args.warmup, 1)
+                ts, acc = [], 0
+                for w in range(args.rounds):
+                    e.ensemble_set_config(X, Q)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    res = run(args.steps, 100 + 1000 * w)
+                    torch.cuda.synchronize()
+                    ts.append((time.perf_counter() - t0) / args.steps)
+                    acc += int(res.accepted.sum())
+                active = e.interactions_active()
+                e.close()
+                line("run_brownian", terms, ts, "step", workload="cfg1_10x12_wall", R=R_RUN, steps_per_window=args.steps,
+                     accepted=acc, active=active)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--evals", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--visits", type=int, default=2)
+    ap.add_argument("--parent-root", default=None, help="a built checkout of the parent commit")
+    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "magnetic.jsonl"))
+    ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--label", default="this", help=argparse.SUPPRESS)
+    ap.add_argument("--kinds", default="eval,run", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.worker:
+        return worker(args)
+
+    def visit(root, label, kinds):
+        cmd = [sys.executable, os.path.abspath(__file__), "--worker", root, "--label", label, "--kinds", kinds, "--steps", str(args.steps),
+               "--evals", str(args.evals), "--warmup", str(args.warmup), "--rounds", str(args.rounds)]
+        env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
+        print("visit: %s build, %s" % (label, kinds), file=sys.stderr, flush=True)
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:
+            sys.exit("the %s build's worker failed (exit %d):\n%s" % (label, p.returncode, (p.stdout + p.stderr)[-3000:]))
+        return [json.loads(l[5:]) for l in p.stdout.splitlines() if l.startswith("JSON ")]
+
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+
+    def emit(d):                                              # as it is measured: a later failure loses nothing
+        print(json.dumps(d), flush=True)
+        with open(args.out, "a") as f:
+            f.write(json.dumps(d) + "\n")
+
+    for d in visit(HERE, "this", "eval,run"):                 # (a) and (b)
+        emit(d)
+    pooled = {}                                               # (c): parent, this, parent, this, ...
+    builds = ([("parent", os.path.abspath(args.parent_root))] if args.parent_root else []) + [("this", HERE)]
+    for v in range(args.visits):
+        for label, root in builds:
+            for d in visit(root, label, "run_off"):
+                d["visit"] = v
+                emit(d)
+                pooled.setdefault(label, []).extend(d["windows_ms"])
+    t = pooled["this"]
+    d = {"workload": "cfg1_10x12_wall", "mode": "terms_off_check", "R": R_RUN, "this_ms_per_step": round(float(np.median(t)), 5),
+         "this_window_spread": round((max(t) - min(t)) / float(np.median(t)), 4), "windows": len(t)}
+    if "parent" in pooled:
+        p = pooled["parent"]
+        mp = float(np.median(p))
+        d.update({"parent_ms_per_step": round(mp, 5), "parent_window_spread": round((max(p) - min(p)) / mp, 4),
+                  "this_over_parent": round(float(np.median(t)) / mp, 4)})
+        d["within_parent_spread"] = bool(float(np.median(t)) <= mp * (1.0 + d["parent_window_spread"]))
+    emit(d)
+
+
+if __name__ == "__main__":
+    main()
