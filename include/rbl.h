@@ -710,7 +710,18 @@ int rbl_interaction_stats(rbl_ctx *ctx, int64_t *body_pairs, int64_t *blob_pairs
  * told whether its mask holds one entry per body or six.  A partly prescribed body's 6 x 6 preconditioner block is K^T invM K with the rows and columns of its prescribed components replaced
  * by the identity's, factored again inside the launch (RBL_ERR_NOT_SPD when that fails).  Masks whose six entries per body are
  * equal give bitwise the results, iteration counts and configurations of rbl_ensemble_solve_mixed / _step_mixed.  Refusals and the
- * error policy are those above, with prescribed6 for prescribed.  There is no Brownian step with component masks (section 7). */
+ * error policy are those above, with prescribed6 for prescribed.
+ *   rbl_ensemble_step_brownian_mixed_dof  rbl_step_brownian_mixed_dof(method RBL_MHALF_CHOLESKY) for every replica, for the masks
+ *                             section 7 admits: in every body of every replica the three rotation entries are all 0 or all 1
+ *                             (translation entries as the caller likes).  rbl_ensemble_step_brownian_mixed's launch sequence with
+ *                             one kernel exchanged: after the unmasked predictor kernel a per-component companion sets dq = 0 and
+ *                             the predictor displacement (dt/2) U_p on the prescribed components of the bodies that have any
+ *                             (a partly prescribed body's scale Kinv M^{1/2}W1 is computed again there; free bodies are not
+ *                             touched), and the solver is told that the mask has six entries per body.  Whole rows in every
+ *                             replica give bitwise rbl_ensemble_step_brownian_mixed.  kBT <= 1e-10: rbl_ensemble_step_mixed_dof.
+ *                             A mask with a partly prescribed rotation is RBL_ERR_ARG before the device is touched; the message
+ *                             names the replica and the body.  The other refusals are rbl_ensemble_step_brownian_mixed's.
+ * A Brownian RUN with prescribed_per = 6 stays refused (below): it is the follow-up and needs only this kernel in its sequence. */
 int rbl_ensemble_set_config(rbl_ctx *ctx, int R, int N_bod, const double *X, const double *Q);
 int rbl_ensemble_get_config(rbl_ctx *ctx, double *X, double *Q);
 int rbl_ensemble_info(const rbl_ctx *ctx, int *R, int *N_bod);
@@ -731,6 +742,9 @@ int rbl_ensemble_step_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed6, const 
 int rbl_ensemble_step_brownian_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip,
                                      const double *W, uint64_t seed, int split_rand, double delta, int max_iter, double rtol,
                                      double *F, int *iters, double *resid);
+int rbl_ensemble_step_brownian_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed6, const double *body_in, const double *slip,
+                                         const double *W, uint64_t seed, int split_rand, double delta, int max_iter, double rtol,
+                                         double *F, int *iters, double *resid);
 
 /* A run: n_steps ensemble steps in ONE call.  The inputs are uploaded once, every step's verdict and commit are taken per
  * replica on the device, the records accumulate there, and the host reads back once at the end (plus the optional status polls
@@ -960,6 +974,32 @@ int rbl_velocity_field_info(const rbl_ctx *ctx, int64_t n_points, int64_t n_src,
  * Refused with RBL_ERR_ARG before any device work: a NULL prescribed6 / body_in / U / F (rbl_step_mixed_dof: F may be NULL),
  * max_iter < 1, rtol < 0, more than 255 iterations, an entry of prescribed6 above 1, a context with a communicator.
  *
+ * The Brownian midpoint step with a mask per velocity component (kBT > 0), for the masks in which every body's three ROTATION
+ * entries (3..5 of its row) are all 0 or all 1; the translation entries are free to choose.  That covers a quasi-2D layer
+ * (U_z = 0), a trapped probe held in place and free to turn, and a roller with Omega imposed whose translation diffuses.  For such
+ * a mask the free velocity components ARE a subset of the coordinates: translation components are Cartesian coordinates, and a
+ * whole rotation is either untouched or treated as the all-free step treats it.  The reference configuration has its mean removed,
+ * so each body's K^T K is block diagonal -- n I for the translation, no translation-rotation coupling -- and (K D_f)^+ = D_f Kinv:
+ * the random displacements D_f Kinv W stay inside the free coordinates.  The whole-body argument above then carries over with
+ * K_f = K D_f: the free components' velocity has covariance (2 kBT / dt) Ntilde, Ntilde = ((K D_f)^T M^-1 K D_f)^-1 on the free
+ * slots, and the drift kBT div_{q_f} Ntilde.  The scheme is the one above with D_f, D_p diagonal over the 6 N_bod slots:
+ *     dq = D_f Kinv W_rfd;  q^{n+1/2} = q^n displaced by D_f (dt/2) c1 Kinv M^{1/2}W1 + D_p (dt/2) U_p, component by component in ONE
+ *     update_X_Q;  the rbl_solve_mixed_dof system at q^{n+1/2} with slip = s and the same body_in (K D_p U_in with the midpoint
+ *     lever arms);  q^n restored (also on failure), evolve_X_Q(U): a prescribed component advances by exactly dt U_p.
+ *   rbl_RHS_and_Midpoint_mixed_dof, rbl_RHS_and_Midpoint_mixed_dof_dev, rbl_step_brownian_mixed_dof
+ *                        the argument lists and conventions of the three whole-body calls above with prescribed6[6 N_bod] for
+ *                        prescribed; the _dev form reads back 18 numbers per body.  The force model and the flow model enter at
+ *                        q^n as in rbl_step_mixed_dof (free components only), RBL_OPT_RECORD_MOMENTS as in rbl_step_brownian_mixed.
+ *                        kBT <= 1e-10: rbl_step_mixed_dof.  Rows all 0 or all 1 give bitwise the whole-body calls' results.  With no
+ *                        entry set the step IS rbl_step_brownian (the call is handed to it: its bits and its iteration count; F
+ *                        echoes the loads it solved with), from which rbl_step_brownian_mixed with nobody prescribed differs in
+ *                        the last digits, the masked solve being another GMRES driver.
+ * Refused with RBL_ERR_ARG before any device work: what the whole-body Brownian calls and the _dof calls refuse, and a mask with a
+ * partly prescribed rotation (one or two of a body's entries 3..5 set) -- the message names the entry point and the first such
+ * body.  A partly prescribed rotation is not a subset of the coordinates and nobody has derived its drift; sampling cannot tell
+ * either, a shell's rotational drift being below one standard error of any affordable sample.
+ * Cost: tools/bench_brownian_dof.py, profiles/brownian_dof.jsonl.
+ *
  * Many right-hand sides under ONE mask, in lock step (the _multi entry points): the 6 N_bod unit velocities of the body resistance
  * matrix, a handful of imposed rotations or trap displacements under one component mask, several noise realisations against fixed
  * obstacles.  nrhs independent recurrences of the solver above -- each column with its own Krylov basis, Hessenberg matrix and
@@ -982,10 +1022,11 @@ int rbl_velocity_field_info(const rbl_ctx *ctx, int64_t n_points, int64_t n_src,
  *
  * Not offered: contexts with a communicator, a mask that changes within a step, lock-step solves whose mask differs from column to
  * column, the Brownian steps in lock step; and with masks per component:
- *   - the Brownian step (rbl_step_brownian_mixed takes whole bodies only): its drift argument rests on whole bodies being
- *     undisplaced, a partly prescribed rotation is not a subset of the coordinates, and nobody has derived the scheme for it;
- *   - for ensembles, the Brownian step as well (rbl_ensemble_step_brownian_mixed and Brownian runs take whole bodies only; the
- *     deterministic rbl_ensemble_solve_mixed_dof / _step_mixed_dof and runs with prescribed_per = 6 are in section 5);
+ *   - the Brownian step with a partly prescribed rotation (one or two of a body's three rotation components): that is not a
+ *     subset of the coordinates and nobody has derived the scheme for it; single contexts and ensembles refuse such a mask;
+ *   - for ensembles, Brownian RUNS with component masks (rbl_ensemble_run with prescribed_per = 6, brownian != 0 and kBT > 1e-10
+ *     stays refused: the follow-up, which needs only the per-component midpoint kernel in the run's step sequence; the one-step
+ *     rbl_ensemble_step_brownian_mixed_dof and the deterministic runs with prescribed_per = 6 are in section 5);
  *   - constraint axes fixed in the body frame (the six components are the lab frame's). */
 int rbl_solve_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
                     double *lambda, double *U, double *F, int *iters, double *resid);
@@ -1015,6 +1056,14 @@ int rbl_RHS_and_Midpoint_mixed_dev(rbl_ctx *ctx, const uint8_t *prescribed, cons
 int rbl_step_brownian_mixed(rbl_ctx *ctx, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
                             uint64_t seed, int method, int split_rand, double delta, int max_iter, double rtol, double *F,
                             int *iters, double *resid);
+int rbl_RHS_and_Midpoint_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed6, const double *body_in, const double *slip, const double *W,
+                                   uint64_t seed, int method, int split_rand, double delta, double *s, double *X_half, double *Q_half);
+int rbl_RHS_and_Midpoint_mixed_dof_dev(rbl_ctx *ctx, const uint8_t *prescribed6, const double *d_body_in, const double *d_slip,
+                                       const double *d_W, uint64_t seed, int method, int split_rand, double delta, double *d_s,
+                                       double *X_half, double *Q_half);
+int rbl_step_brownian_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed6, const double *body_in, const double *slip, const double *W,
+                                uint64_t seed, int method, int split_rand, double delta, int max_iter, double rtol, double *F,
+                                int *iters, double *resid);
 
 /* ===================================================================== */
 /* 8. Imposed flow and active slip (rigid_body_light_amd/csrc/rbl_flow.hip) */

@@ -127,6 +127,9 @@ def lib():
         L.rbl_RHS_and_Midpoint_mixed_dev.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, vp, vp, vp]
         L.rbl_step_brownian_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, dbl, C.c_int, dbl, vp, C.POINTER(C.c_int),
                                               C.POINTER(dbl)]
+        L.rbl_RHS_and_Midpoint_mixed_dof.argtypes = L.rbl_RHS_and_Midpoint_mixed_dof_dev.argtypes = L.rbl_RHS_and_Midpoint_mixed.argtypes
+        L.rbl_step_brownian_mixed_dof.argtypes = L.rbl_step_brownian_mixed.argtypes
+        L.rbl_ensemble_step_brownian_mixed_dof.argtypes = L.rbl_ensemble_step_brownian_mixed.argtypes
         L.rbl_set_background_flow.argtypes = [vp, vp, vp, C.c_int]
         L.rbl_set_body_slip.argtypes = [vp, vp, vp, C.c_int, C.c_int]
         L.rbl_get_flow_model.argtypes = [vp, C.POINTER(dbl), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -185,6 +188,21 @@ def table_arrays(who, U, dU):
     if U.ndim != 1 or U.shape != dU.shape:
         raise ValueError("%s: U and dU must be one-dimensional and of one length; got %s and %s" % (who, U.shape, dU.shape))
     return U, dU
+
+
+def check_brownian_mask6(who, mask6, n_bod, replicas=1):
+    """The masks per velocity component that the Brownian midpoint step takes (include/rbl.h section 7): in every body's row the
+    three rotation entries (3..5) are all 0 or all 1 -- only then are the free components a subset of the coordinates.  The
+    library's own refusal, worded as it words it, raised as ValueError before the library is called.  mask6: replicas * n_bod
+    rows of six entries, in any shape"""
+    import numpy as np
+    rot = (np.asarray(mask6).reshape(-1, 6)[:, 3:] != 0).sum(axis=1)
+    bad = np.flatnonzero((rot != 0) & (rot != 3))
+    if bad.size:
+        g = int(bad[0])
+        where = "replica %d, body %d" % (g // n_bod, g % n_bod) if replicas > 1 else "body %d" % g
+        raise ValueError("%s: %s: the rotation is partly prescribed (entries 3..5 of a body's row of prescribed6 must be all 0 or all "
+                         "1 in the Brownian step: the drift of a partly prescribed rotation has not been derived)" % (who, where))
 
 
 class RunOpts(C.Structure):
@@ -779,6 +797,29 @@ class DeviceContext:
                                                           it.ctypes.data, res.ctypes.data))
         return F, it, res
 
+    def ensemble_step_brownian_mixed_dof(self, prescribed6, body_in, W=None, seed=0, split_rand=True, delta=1.0e-4, max_iter=50,
+                                         rtol=1.0e-8, slip=None):
+        """one stochastic midpoint step of every replica with prescribed velocity components (dense Cholesky root); prescribed6:
+        (N_bod, 6) or (R, N_bod, 6), every body's rotation entries all 0 or all 1 (check_brownian_mask6) -> (F (R, 6 N_bod),
+        iterations[R], residual estimates[R]); W as ensemble_step_brownian"""
+        import numpy as np
+        who = "ensemble_step_brownian_mixed_dof"
+        R, nb, m, bi, sl = self._ens_mixed_args(who, prescribed6, body_in, slip, per=6)
+        check_brownian_mask6(who, m, nb, R)
+        n3 = 3 * nb * self._sizes()[1]
+        Wh = None
+        if W is not None:
+            Wh = np.ascontiguousarray(np.asarray(W, dtype=np.float64))
+            if Wh.size != R * 3 * n3:
+                raise ValueError("W must have shape (%d, %d); got %s" % (R, 3 * n3, Wh.shape))
+        F = np.zeros((R, 6 * nb))
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(self.L.rbl_ensemble_step_brownian_mixed_dof(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                              None if Wh is None else Wh.ctypes.data, int(seed), int(bool(split_rand)),
+                                                              float(delta), int(max_iter), float(rtol or 0.0), F.ctypes.data,
+                                                              it.ctypes.data, res.ctypes.data))
+        return F, it, res
+
     def ensemble_run(self, n_steps, F_body=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error=RUN_STOP,
                      check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8, per=1):
         """n_steps steps of every replica in one call (rbl_ensemble_run): the inputs are uploaded once, the verdict, the commit
@@ -1126,6 +1167,46 @@ class DeviceContext:
         self._chk(self.L.rbl_step_brownian_mixed(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
                                                  None if Wh is None else Wh.ctypes.data, int(seed), int(method), int(bool(split_rand)),
                                                  float(delta), int(max_iter), float(rtol), F.ctypes.data, C.byref(it), C.byref(res)))
+        return F, it.value, res.value
+
+    def _mixed_dof_sizes(self, who, prescribed6):
+        """the mask per velocity component of a Brownian call: 6 N_bod entries, every body's rotation entries all 0 or all 1"""
+        import numpy as np
+        m = np.ascontiguousarray(prescribed6, dtype=np.uint8).reshape(-1)
+        nb, nl = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), C.byref(nl)))
+        if m.size != 6 * nb.value:
+            raise ValueError(who + ": prescribed6 must have 6 N_bod entries")
+        check_brownian_mask6(who, m, nb.value)
+        return m, nb.value, nl.value
+
+    def RHS_and_Midpoint_mixed_dof_dev(self, prescribed6, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s):
+        """RHS_and_Midpoint_mixed_dev with a mask per velocity component (prescribed6: a host array of 6 N_bod entries, every
+        body's rotation entries all 0 or all 1) -> (X_half, Q_half) on the host"""
+        import numpy as np
+        m, nb, _ = self._mixed_dof_sizes("RHS_and_Midpoint_mixed_dof_dev", prescribed6)
+        X = np.zeros(3 * nb); Q = np.zeros(4 * nb)
+        self._chk(self.L.rbl_RHS_and_Midpoint_mixed_dof_dev(self.h, m.ctypes.data, d_body_in, d_slip or None, d_W or None, int(seed),
+                                                            int(method), int(bool(split_rand)), float(delta), d_s, X.ctypes.data,
+                                                            Q.ctypes.data))
+        return X.reshape(-1, 3), Q.reshape(-1, 4)
+
+    def step_brownian_mixed_dof(self, prescribed6, body_in, max_iter=50, rtol=1.0e-8, slip=None, W=None, seed=0, method=2, split_rand=True,
+                                delta=1.0e-4):
+        """one stochastic midpoint step with prescribed velocity components inside librbl; host arrays -> (F, iterations, residual
+        estimate)"""
+        import numpy as np
+        m, nb, nl = self._mixed_dof_sizes("step_brownian_mixed_dof", prescribed6)
+        bi = np.ascontiguousarray(body_in, dtype=np.float64).reshape(-1)
+        sl = None if slip is None else np.ascontiguousarray(slip, dtype=np.float64).reshape(-1)
+        Wh = None if W is None else np.ascontiguousarray(W, dtype=np.float64).reshape(-1)
+        if bi.size != 6 * nb or (sl is not None and sl.size != 3 * nb * nl) or (Wh is not None and Wh.size != 9 * nb * nl):
+            raise ValueError("step_brownian_mixed_dof: body_in (6 N_bod), slip (3 N_blobs) or W (9 N_blobs) has the wrong size")
+        F = np.empty(6 * nb)
+        it, res = C.c_int(0), C.c_double(0.0)
+        self._chk(self.L.rbl_step_brownian_mixed_dof(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                     None if Wh is None else Wh.ctypes.data, int(seed), int(method), int(bool(split_rand)),
+                                                     float(delta), int(max_iter), float(rtol), F.ctypes.data, C.byref(it), C.byref(res)))
         return F, it.value, res.value
 
     def blob_positions(self, body_begin, body_end, dout):

@@ -596,6 +596,42 @@ struct CManyBodies {
     check(rc);
     return py::make_tuple(F, it, res);
   }
+  // the same with a mask per velocity component (rbl_RHS_and_Midpoint_mixed_dof, rbl_step_brownian_mixed_dof): mask[6 N_bod]
+  py::tuple RHS_and_Midpoint_mixed_dof(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
+                                       bool split_rand, double delta)
+  {
+    darr sl, Wa;
+    const double *sp = mixed_dof_args("RHS_and_Midpoint_mixed_dof", mask, body_in, slip, sl);
+    const double *wp = noise_arg("RHS_and_Midpoint_mixed_dof", W, Wa);
+    const int m = mhalf_method(method);
+    const py::ssize_t nb = n_bod();
+    darr s(n3()), X(3 * nb), Q(4 * nb);
+    int rc;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_RHS_and_Midpoint_mixed_dof(ctx, mask.data(), body_in.data(), sp, wp, seed, m, split_rand ? 1 : 0, delta, s.mutable_data(),
+                                          X.mutable_data(), Q.mutable_data());
+    }
+    check(rc);
+    return py::make_tuple(s, X, Q);
+  }
+  py::tuple step_brownian_mixed_dof(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
+                                    bool split_rand, double delta, int max_iter, double rtol)
+  {
+    darr sl, Wa;
+    const double *sp = mixed_dof_args("step_brownian_mixed_dof", mask, body_in, slip, sl);
+    const double *wp = noise_arg("step_brownian_mixed_dof", W, Wa);
+    const int m = mhalf_method(method);
+    darr F(6 * (py::ssize_t)n_bod());
+    int it = 0, rc; double res = 0.0;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_step_brownian_mixed_dof(ctx, mask.data(), body_in.data(), sp, wp, seed, m, split_rand ? 1 : 0, delta, max_iter, rtol,
+                                       F.mutable_data(), &it, &res);
+    }
+    check(rc);
+    return py::make_tuple(F, it, res);
+  }
   void set_interactions(double w, double eps_wall, double b_wall, double eps_blob, double b_blob, double r_cut, bool on)
   {
     check(rbl_set_interactions(ctx, w, eps_wall, b_wall, eps_blob, b_blob, r_cut, on ? 1 : 0));
@@ -841,6 +877,12 @@ PYBIND11_MODULE(c_rigid, m)
            py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "cholesky",
            py::arg("split_rand") = true, py::arg("delta") = 1.0e-4)
       .def("step_brownian_mixed", &CManyBodies::step_brownian_mixed, py::arg("prescribed"), py::arg("body_in"),
+           py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "lanczos_pc",
+           py::arg("split_rand") = true, py::arg("delta") = 1.0e-4, py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
+      .def("RHS_and_Midpoint_mixed_dof", &CManyBodies::RHS_and_Midpoint_mixed_dof, py::arg("prescribed"), py::arg("body_in"),
+           py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "cholesky",
+           py::arg("split_rand") = true, py::arg("delta") = 1.0e-4)
+      .def("step_brownian_mixed_dof", &CManyBodies::step_brownian_mixed_dof, py::arg("prescribed"), py::arg("body_in"),
            py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "lanczos_pc",
            py::arg("split_rand") = true, py::arg("delta") = 1.0e-4, py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
       .def("set_background_flow", &CManyBodies::set_background_flow, "u_inf(r) = u0 + G r added to every step's slip as -u_inf",

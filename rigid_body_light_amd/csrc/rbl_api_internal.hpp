@@ -131,10 +131,16 @@ int gmres_multi_with_ops(rbl_ctx *c, const RblMultiOps *ops, const double *d_rhs
 
 // ---- rbl_steps.hip ------------------------------------------------------------------------------------------------
 // The stochastic midpoint scheme, once for rbl_step_brownian and rbl_step_brownian_mixed (rbl_mixed.hip): the all-free step is the
-// mixed one with no mask (h_mask, d_mask, d_body_in all NULL).  d_s = slip - kBT M_RFD - BI may alias d_slip; d_slip NULL: zero
+// mixed one with no mask (h_mask, d_mask, d_body_in all NULL).  d_s = slip - kBT M_RFD - BI may alias d_slip; d_slip NULL: zero.
+// per: mask entries per body, 1 or 6 (a mask per velocity component whose rotation entries are all equal within a body)
 int rhs_and_midpoint_core(rbl_ctx *c, const uint8_t *h_mask, const uint8_t *d_mask, const double *d_body_in, const double *d_slip,
                           const double *d_W, uint64_t seed, int method, int split_rand, double delta, double *d_s, double *X_half,
-                          double *Q_half);
+                          double *Q_half, int per = 1);
+// rbl_mixed.hip: the masks per velocity component that the Brownian step takes (every body's rotation entries all equal), for
+// prescribed6[R 6 N_bod]; RBL_ERR_ARG names `who`, the first offending body and, with R > 1, its replica.  Touches no device
+int rbl_bd_mask6_check(rbl_ctx *c, const char *who, const uint8_t *prescribed6, int R, int N_bod);
+// the body loads the last rbl_step_deterministic / rbl_step_brownian solved with, on the device (6 N_bod; step_buffers' layout)
+const double *step_force_dev(const rbl_ctx *c);
 // the host's noise W (9 N_blobs) into d_W; *d_W = NULL when W is NULL
 int step_upload_W(rbl_ctx *c, const double *W, double **d_W);
 // save q^n, rhs(X_half, Q_half), operators at q^{n+1/2}, solve(U: 6 N_bod, host), back to q^n (also on failure), evolve by dt U

@@ -109,6 +109,35 @@ __global__ __launch_bounds__(BT) void k_mx_bd_sums(const double *__restrict__ le
   if (t < 6) { out[o + t] = f[t]; out[nb6 + o + t] = g[t]; }
 }
 
+// the same with a mask per velocity component (mask6[6 N_bod]): a body with some components prescribed and others free needs both
+// its sums and the velocities of its prescribed components, so body_in travels in a third block, out[2 nb6 .. 3 nb6), and the
+// host picks per component.  The sums are k_mx_bd_sums', term for term; a body with all six prescribed reads no blob and gets 0
+__global__ __launch_bounds__(BT) void k_mx_bd_sums6(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
+                                                    const double *__restrict__ body_in, const double *__restrict__ Wrfd,
+                                                    const double *__restrict__ MW1, int N_blb, long nb6, double *__restrict__ out)
+{
+  __shared__ double s[6][BT];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const size_t o = 6 * (size_t)b;
+  if (t < 6) out[2 * nb6 + o + t] = body_in[o + t];
+  bool all = true;
+  for (int c = 0; c < 6; ++c) all = all && mask6[o + c] != 0;   // (the same six bytes in every lane: the branch is uniform)
+  if (all) {
+    if (t < 6) { out[o + t] = 0.0; out[nb6 + o + t] = 0.0; }
+    return;
+  }
+  double f[6] = {0, 0, 0, 0, 0, 0}, g[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = t; k < N_blb; k += BT) {
+    const size_t idx = 3 * ((size_t)b * N_blb + k);
+    const double *l = lever + idx;
+    rbl_KT_acc(l, Wrfd[idx], Wrfd[idx + 1], Wrfd[idx + 2], f);
+    rbl_KT_acc(l, MW1[idx], MW1[idx + 1], MW1[idx + 2], g);
+  }
+  block_reduce<6>(f, s, t);
+  block_reduce<6>(g, s, t);
+  if (t < 6) { out[o + t] = f[t]; out[nb6 + o + t] = g[t]; }
+}
+
 // diag_invM (:489-543) + Ninv = K^T invM K per body and its Cholesky (:593-594, :554-567)
 template <bool WALL>
 __global__ __launch_bounds__(BT) void k_pc_diag_build(const double *__restrict__ lever,
@@ -818,6 +847,13 @@ void rbl_launch_mx_bd_sums(hipStream_t st, const double *d_lever, const uint8_t 
 {
   if (N_bod <= 0) return;
   hipLaunchKernelGGL(k_mx_bd_sums, dim3(N_bod), dim3(BT), 0, st, d_lever, d_mask, d_body_in, d_Wrfd, d_MW1, N_blb, 6L * N_bod, d_out);
+}
+
+void rbl_launch_mx_bd_sums6(hipStream_t st, const double *d_lever, const uint8_t *d_mask6, const double *d_body_in, const double *d_Wrfd,
+                            const double *d_MW1, int N_blb, int N_bod, double *d_out)
+{
+  if (N_bod <= 0) return;
+  hipLaunchKernelGGL(k_mx_bd_sums6, dim3(N_bod), dim3(BT), 0, st, d_lever, d_mask6, d_body_in, d_Wrfd, d_MW1, N_blb, 6L * N_bod, d_out);
 }
 
 void rbl_launch_pc_diag_build(hipStream_t st, const RblParams &P, bool wall, const double *d_lever,

@@ -26,6 +26,8 @@
 // body and replica travels with the call, and NULL for it is the unmasked step: ens_step_det and ens_step_bd serve both.
 // The deterministic calls also take a mask per velocity component (rbl_ensemble_solve_mixed_dof / _step_mixed_dof, runs with
 // prescribed_per = 6): the mask goes up as the caller gave it and the solver is told how many entries a body has.
+// The one-step Brownian call takes one too (rbl_ensemble_step_brownian_mixed_dof: every body's rotation entries all equal), with
+// k_ens_midpoint_dof where k_ens_midpoint_prescribed stands below; a Brownian RUN with such a mask stays refused.
 // The same launches with three differences: k_ens_midpoint is followed by k_ens_midpoint_prescribed (dq = 0 and the predictor
 // (dt/2) U_p on a prescribed body; one more launch, so that a free body goes through the very same code), the solve is the
 // masked k_gmres_small (it adds K_p U_p to the right-hand side with the lever arms of the configuration it solves at, zeroes
@@ -170,6 +172,50 @@ __global__ __launch_bounds__(ET) void k_ens_midpoint_prescribed(int nbod, const 
   if (g >= nbod || !mask[g]) return;
   double u[6];
   for (int p = 0; p < 6; ++p) { dq[6 * (size_t)g + p] = 0.0; u[p] = half_dt * body_in[6 * (size_t)g + p]; }
+  ens_update_body(X + 3 * (size_t)g, Q + 4 * (size_t)g, u, Xh + 3 * (size_t)g, Qh + 4 * (size_t)g);
+}
+
+// The companion with a mask per velocity component (mask6[6 nbod], every body's rotation entries all equal: the entry point has
+// checked it), run after k_ens_midpoint on the bodies with any component prescribed.  A body with all six prescribed is
+// k_ens_midpoint_prescribed's case, statement for statement and in a function of its own, so that the compiler contracts it as it
+// does there and whole rows give the whole-body step's bits.  A partly prescribed body keeps k_ens_midpoint's dq on its free
+// components (D_f Kinv W_rfd: (K^T K)^-1 has no translation-rotation coupling) and gets 0 on the prescribed ones; its predictor
+// displacement is (dt/2) U_p on the prescribed components and scale Kinv M^1/2 W1, computed again here, on the free ones, taken
+// in ONE update_X_Q.  The free bodies are not touched, for the reason given above.
+__device__ __noinline__ void ens_midpoint_whole_body(const double *X, const double *Q, const double *body_in, double half_dt, double *dq,
+                                                     double *Xh, double *Qh)
+{
+  double u[6];
+  for (int p = 0; p < 6; ++p) { dq[p] = 0.0; u[p] = half_dt * body_in[p]; }
+  ens_update_body(X, Q, u, Xh, Qh);
+}
+
+__global__ __launch_bounds__(ET) void k_ens_midpoint_dof(int nbod, int Nb, int nbl, const double *__restrict__ X,
+                                                         const double *__restrict__ Q, const double *__restrict__ cfg,
+                                                         const unsigned char *__restrict__ mask6, const double *__restrict__ body_in,
+                                                         const double *__restrict__ MW, double scale, double half_dt,
+                                                         double *__restrict__ dq, double *__restrict__ Xh, double *__restrict__ Qh)
+{
+  const int g = blockIdx.x * ET + threadIdx.x;
+  if (g >= nbod) return;
+  unsigned pm = 0;
+  for (int p = 0; p < 6; ++p) pm |= (mask6[6 * (size_t)g + p] != 0 ? 1u : 0u) << p;
+  if (!pm) return;
+  if (pm == 63u) {
+    ens_midpoint_whole_body(X + 3 * (size_t)g, Q + 4 * (size_t)g, body_in + 6 * (size_t)g, half_dt, dq + 6 * (size_t)g, Xh + 3 * (size_t)g,
+                            Qh + 4 * (size_t)g);
+    return;
+  }
+  const int r = g / Nb, b = g - r * Nb;
+  const size_t n3 = (size_t)3 * Nb * nbl, boff = (size_t)3 * b * nbl;
+  double Rm[9], u[6];
+  rbl_quat_rot9(Q + 4 * (size_t)g, Rm);
+  ens_kinv_body(Rm, cfg, nbl, MW + (size_t)r * 3 * n3 + boff, u);
+  for (int p = 0; p < 6; ++p) {
+    const bool pres = pm >> p & 1u;
+    if (pres) dq[6 * (size_t)g + p] = 0.0;
+    u[p] = pres ? half_dt * body_in[6 * (size_t)g + p] : scale * u[p];
+  }
   ens_update_body(X + 3 * (size_t)g, Q + 4 * (size_t)g, u, Xh + 3 * (size_t)g, Qh + 4 * (size_t)g);
 }
 
@@ -694,7 +740,11 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
   const int nbod = R * Nb;
   hipLaunchKernelGGL(k_ens_midpoint, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, nbl, X, Q, ens_cfg(c),
                      (const double *)w.W, (const double *)w.MW, 0.5 * S.dt * c1, w.dq, w.Xh, w.Qh);
-  if (mixed)                                             // the prescribed bodies: dq = 0, q^n + (dt/2) U_p
+  if (mixed && in.per == 6)                              // the prescribed components: dq = 0, (dt/2) U_p in the predictor displacement
+    hipLaunchKernelGGL(k_ens_midpoint_dof, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, nbl, X, Q, ens_cfg(c),
+                       (const unsigned char *)w.mask, (const double *)w.F, (const double *)w.MW, 0.5 * S.dt * c1, 0.5 * S.dt, w.dq, w.Xh,
+                       w.Qh);
+  else if (mixed)                                        // the prescribed bodies: dq = 0, q^n + (dt/2) U_p
     hipLaunchKernelGGL(k_ens_midpoint_prescribed, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, X, Q,
                        (const unsigned char *)w.mask, (const double *)w.F, 0.5 * S.dt, w.dq, w.Xh, w.Qh);
   const size_t lds = rfd_lds_bytes(Nb, nbl);
@@ -712,18 +762,18 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
                        (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
                        SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
   // saddle solve at q^{n+1/2}, update from q^n
-  return ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol, mixed, true, !in.resident);
+  return ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol, mixed, true, !in.resident, in.per);
 }
 
 int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, const double *W, uint64_t seed,
-                int split_rand, double delta, int max_iter, double rtol, double *F_out, int *iters, double *resid)
+                int split_rand, double delta, int max_iter, double rtol, double *F_out, int *iters, double *resid, int per = 1)
 {
   const bool mixed = prescribed != nullptr;
   int rc;
   EnsWork w;
   if ((rc = ens_work(c, max_iter, &w))) return rc;
   EnsStepIn in;
-  in.prescribed = prescribed; in.F_body = F_body; in.slip = slip; in.W = W;
+  in.prescribed = prescribed; in.per = per; in.F_body = F_body; in.slip = slip; in.W = W;
   if ((rc = ens_enqueue_bd(c, w, in, seed, split_rand, delta, max_iter, rtol))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb;
   std::vector<double> Ft;
@@ -1009,6 +1059,25 @@ int rbl_ensemble_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, cons
   if ((rc = ens_ready(c))) return rc;
   if (!brownian) return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
   return ens_step_bd(c, prescribed, body_in, slip, W, seed, split_rand, delta, max_iter, rtol, F, iters, resid);
+}
+
+// the Brownian step with a mask per velocity component (include/rbl.h section 7's admissible class, per replica): the whole-body
+// call's checks and launch sequence, k_ens_midpoint_dof where k_ens_midpoint_prescribed stood and the solver told per = 6
+int rbl_ensemble_step_brownian_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *body_in, const double *slip, const double *W,
+                                         uint64_t seed, int split_rand, double delta, int max_iter, double rtol, double *F, int *iters,
+                                         double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  int rc = ens_mx_check(c, "ensemble_step_brownian_mixed_dof", prescribed6, body_in, max_iter, rtol, 6); if (rc) return rc;
+  if ((rc = rbl_bd_mask6_check(c, "ensemble_step_brownian_mixed_dof", prescribed6, c->ens_R, c->ens_Nb))) return rc;
+  if ((rc = ens_flow_check(c))) return rc;
+  const RblBodyState &S = c->S;
+  const bool brownian = S.kBT > 1e-10;                 // no Brownian terms: the deterministic step with this mask
+  if (brownian && (!(S.dt > 0.0) || !(delta > 0.0)))
+    return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_brownian_mixed_dof: dt and delta must be positive");
+  if ((rc = ens_ready(c))) return rc;
+  if (!brownian) return ens_step_det(c, prescribed6, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid, 6);
+  return ens_step_bd(c, prescribed6, body_in, slip, W, seed, split_rand, delta, max_iter, rtol, F, iters, resid, 6);
 }
 
 int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)

@@ -424,6 +424,10 @@ void rbl_launch_KT_x_Lam(hipStream_t st, const double *d_lever, const double *d_
 // none) gets 0 and its six entries of d_body_in instead (the stochastic midpoint step, rbl_steps.hip)
 void rbl_launch_mx_bd_sums(hipStream_t st, const double *d_lever, const uint8_t *d_mask, const double *d_body_in, const double *d_Wrfd,
                            const double *d_MW1, int N_blb, int N_bod, double *d_out);
+// the same with a mask per velocity component (d_mask6[6 N_bod], d_body_in: neither NULL): d_out has a third block,
+// d_out[12 N_bod .. 18 N_bod) = d_body_in; a body with all six components prescribed gets 0 in the first two
+void rbl_launch_mx_bd_sums6(hipStream_t st, const double *d_lever, const uint8_t *d_mask6, const double *d_body_in, const double *d_Wrfd,
+                            const double *d_MW1, int N_blb, int N_bod, double *d_out);
 void rbl_launch_pc_diag_build(hipStream_t st, const RblParams &P, bool wall, const double *d_lever,
                               const double *d_pos, int N_blb, int N_bod, double *d_invM2, double *d_NL,
                               unsigned *d_err);

@@ -20,7 +20,8 @@
 //
 // The Brownian midpoint step with prescribed bodies has its entry points here and nothing of the scheme: right-hand side, predictor
 // and the sequence of the step are rbl_steps.hip's (rhs_and_midpoint_core, step_midpoint), which the all-free step goes through with
-// no mask; this file hands them the mask and mx_solve.
+// no mask; this file hands them the mask and mx_solve.  With a mask per velocity component (the _dof forms of the three entry
+// points) the mask must make the free components a subset of the coordinates: rbl_bd_mask6_check.
 #include <cstring>
 #include <vector>
 
@@ -727,16 +728,106 @@ int mx_step(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double
 
 // the checks of the two right-hand-side forms and of the step, none of which needs a device
 int mx_bd_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const void *body_in, int max_iter, double rtol, double delta,
-                int *n_prescribed)
+                int *n_prescribed, int per = 1)
 {
-  const int rc = mx_check(c, who, prescribed, body_in, max_iter, rtol, true, n_prescribed); if (rc) return rc;
+  int rc = mx_check(c, who, prescribed, body_in, max_iter, rtol, true, n_prescribed, per); if (rc) return rc;
+  if (per == 6 && (rc = rbl_bd_mask6_check(c, who, prescribed, 1, c->S.N_bod))) return rc;
   if (max_iter > 254) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": at most 254 iterations (no restart)");
   if (c->S.kBT > 1e-10 && (!(c->S.dt > 0.0) || !(delta > 0.0)))
     return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": dt and delta must be positive");
   return RBL_OK;
 }
 
+// right-hand side and predictor, device arrays in and out (who: the entry point's name; per: mask entries per body)
+int mx_bd_rhs_dev(rbl_ctx *c, const char *who, const uint8_t *prescribed, int per, const double *d_body_in, const double *d_slip,
+                  const double *d_W, uint64_t seed, int method, int split_rand, double delta, double *d_s, double *X_half, double *Q_half)
+{
+  if (c && (!d_s || !X_half || !Q_half)) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": s, X_half or Q_half is NULL");
+  int np = 0;
+  int rc = mx_bd_check(c, who, prescribed, d_body_in, 1, 0.0, delta, &np, per); if (rc) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  const uint8_t *d_mask = nullptr;
+  if (c->S.kBT > 1e-10) {                                // without Brownian terms the mask is not read: no workspace for it
+    MxBuf B;
+    B.per = per;
+    if ((rc = mx_reserve(c, B))) return rc;
+    if ((rc = copy_h2d(c, B.mask, prescribed, (size_t)per * (size_t)c->S.N_bod))) return rc;
+    d_mask = B.mask;
+  }
+  return rhs_and_midpoint_core(c, prescribed, d_mask, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s, X_half, Q_half, per);
+}
+
+// the same with host arrays (who: the host entry point's name; the refusals name it)
+int mx_bd_rhs_host(rbl_ctx *c, const char *who, const uint8_t *prescribed, int per, const double *body_in, const double *slip,
+                   const double *W, uint64_t seed, int method, int split_rand, double delta, double *s, double *X_half, double *Q_half)
+{
+  if (c && (!s || !X_half || !Q_half)) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": s, X_half or Q_half is NULL");
+  int np = 0;
+  int rc = mx_bd_check(c, who, prescribed, body_in, 1, 0.0, delta, &np, per); if (rc) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
+  const size_t vb = sizeof(double) * n3, fb = sizeof(double) * nb6;
+  if ((rc = rbl_dev_reserve(c, c->d_bd2, (W ? 4 : 1) * vb + fb))) return rc;
+  double *dS = (double *)c->d_bd2.p, *dBody = dS + n3, *dW = dBody + nb6;
+  if (slip && (rc = copy_h2d(c, dS, slip, vb))) return rc;
+  if ((rc = copy_h2d(c, dBody, body_in, fb))) return rc;
+  if (W && (rc = copy_h2d(c, dW, W, 3 * vb))) return rc;
+  if ((rc = mx_bd_rhs_dev(c, who, prescribed, per, dBody, slip ? dS : nullptr, W ? dW : nullptr, seed, method, split_rand, delta, dS, X_half,
+                          Q_half))) return rc;
+  if ((rc = copy_d2h(c, s, dS, vb))) return rc;
+  return finish_and_check(c);
+}
+
+// the Brownian step with prescribed bodies (per = 1) or velocity components (per = 6), the checks done and kBT > 1e-10: with six
+// mask entries per body the predictor picks per component (k_mx_bd_sums6) and the solve at q^{n+1/2} is mx_step's _dof solve
+int mx_bd_step(rbl_ctx *c, const uint8_t *prescribed, int per, int np, const double *body_in, const double *slip, const double *W,
+               uint64_t seed, int method, int split_rand, double delta, int max_iter, double rtol, double *F, int *iters, double *resid)
+{
+  int rc;
+  if ((rc = flow_check(c, c->S.N_bod))) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  flow_begin_step(c);
+  const size_t nb6 = 6 * (size_t)c->S.N_bod;
+  MxBuf B;
+  B.per = per;
+  double *dW;
+  bool have_slip;
+  if ((rc = mx_upload(c, B, prescribed, body_in, slip, true, np, &have_slip))) return rc;   // the models at q^n; forces: free components only
+  if ((rc = step_upload_W(c, W, &dW))) return rc;
+  return step_midpoint(
+      c,
+      [&](double *Xh, double *Qh) {                       // s takes the slip's place in the solve's workspace: it never leaves the device
+        return rhs_and_midpoint_core(c, prescribed, B.mask, B.body_in, have_slip ? B.slip : nullptr, dW, seed, method, split_rand, delta, B.slip,
+                                     Xh, Qh, per);
+      },
+      [&](double *U) {
+        int r = mx_solve(c, B, true, np, max_iter, rtol, iters, resid);
+        if (!r) r = flow_record_moments(c, B.x);                          // RBL_OPT_RECORD_MOMENTS: lever arms of q^{n+1/2}
+        if (!r) r = copy_d2h(c, U, B.U, sizeof(double) * nb6);
+        if (!r && F) r = copy_d2h(c, F, B.F, sizeof(double) * nb6);
+        return r ? r : finish_and_check(c);
+      });
+}
+
 }  // namespace
+
+// The masks the Brownian midpoint step takes per velocity component (include/rbl.h section 7): every body's three rotation entries
+// all 0 or all 1, the translation entries as the caller likes -- then the free coordinates are a subset of the coordinates.
+// prescribed6[R 6 N_bod] (R = 1: a single context; the replica is named otherwise).  No device is touched.
+int rbl_bd_mask6_check(rbl_ctx *c, const char *who, const uint8_t *prescribed6, int R, int N_bod)
+{
+  for (size_t g = 0; g < (size_t)R * (size_t)N_bod; ++g) {
+    const uint8_t *m = prescribed6 + 6 * g;
+    const int nrot = (m[3] != 0) + (m[4] != 0) + (m[5] != 0);
+    if (nrot == 0 || nrot == 3) continue;
+    const std::string where = R > 1 ? "replica " + std::to_string(g / (size_t)N_bod) + ", body " + std::to_string(g % (size_t)N_bod)
+                                    : "body " + std::to_string(g);
+    return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": " + where + ": the rotation is partly prescribed (entries 3..5 of a body's row of "
+                                    "prescribed6 must be all 0 or all 1 in the Brownian step: the drift of a partly prescribed rotation "
+                                    "has not been derived)");
+  }
+  return RBL_OK;
+}
 
 // ============================================================================
 // 7. prescribed kinematics (include/rbl.h)
@@ -812,38 +903,14 @@ int rbl_RHS_and_Midpoint_mixed_dev(rbl_ctx *c, const uint8_t *prescribed, const 
                                    const double *d_W, uint64_t seed, int method, int split_rand, double delta, double *d_s,
                                    double *X_half, double *Q_half)
 {
-  if (c && (!d_s || !X_half || !Q_half)) return rbl_fail(c, RBL_ERR_ARG, "RHS_and_Midpoint_mixed_dev: s, X_half or Q_half is NULL");
-  int np = 0;
-  int rc = mx_bd_check(c, "RHS_and_Midpoint_mixed_dev", prescribed, d_body_in, 1, 0.0, delta, &np); if (rc) return rc;
-  if ((rc = rbl_dev_init(c))) return rc;
-  const uint8_t *d_mask = nullptr;
-  if (c->S.kBT > 1e-10) {                                // without Brownian terms the mask is not read: no workspace for it
-    MxBuf B;
-    if ((rc = mx_reserve(c, B))) return rc;
-    if ((rc = copy_h2d(c, B.mask, prescribed, (size_t)c->S.N_bod))) return rc;
-    d_mask = B.mask;
-  }
-  return rhs_and_midpoint_core(c, prescribed, d_mask, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s, X_half, Q_half);
+  return mx_bd_rhs_dev(c, "RHS_and_Midpoint_mixed_dev", prescribed, 1, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s, X_half,
+                       Q_half);
 }
 
 int rbl_RHS_and_Midpoint_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
                                uint64_t seed, int method, int split_rand, double delta, double *s, double *X_half, double *Q_half)
 {
-  if (c && (!s || !X_half || !Q_half)) return rbl_fail(c, RBL_ERR_ARG, "RHS_and_Midpoint_mixed: s, X_half or Q_half is NULL");
-  int np = 0;
-  int rc = mx_bd_check(c, "RHS_and_Midpoint_mixed", prescribed, body_in, 1, 0.0, delta, &np); if (rc) return rc;
-  if ((rc = rbl_dev_init(c))) return rc;
-  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
-  const size_t vb = sizeof(double) * n3, fb = sizeof(double) * nb6;
-  if ((rc = rbl_dev_reserve(c, c->d_bd2, (W ? 4 : 1) * vb + fb))) return rc;
-  double *dS = (double *)c->d_bd2.p, *dBody = dS + n3, *dW = dBody + nb6;
-  if (slip && (rc = copy_h2d(c, dS, slip, vb))) return rc;
-  if ((rc = copy_h2d(c, dBody, body_in, fb))) return rc;
-  if (W && (rc = copy_h2d(c, dW, W, 3 * vb))) return rc;
-  if ((rc = rbl_RHS_and_Midpoint_mixed_dev(c, prescribed, dBody, slip ? dS : nullptr, W ? dW : nullptr, seed, method, split_rand, delta,
-                                           dS, X_half, Q_half))) return rc;
-  if ((rc = copy_d2h(c, s, dS, vb))) return rc;
-  return finish_and_check(c);
+  return mx_bd_rhs_host(c, "RHS_and_Midpoint_mixed", prescribed, 1, body_in, slip, W, seed, method, split_rand, delta, s, X_half, Q_half);
 }
 
 int rbl_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
@@ -852,29 +919,42 @@ int rbl_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, const double 
 {
   if (!c) return RBL_ERR_ARG;
   int np = 0;
-  int rc = mx_bd_check(c, "step_brownian_mixed", prescribed, body_in, max_iter, rtol, delta, &np); if (rc) return rc;
+  const int rc = mx_bd_check(c, "step_brownian_mixed", prescribed, body_in, max_iter, rtol, delta, &np); if (rc) return rc;
   if (!(c->S.kBT > 1e-10))                               // no Brownian terms: the deterministic step (as rbl_step_brownian, :967-970)
     return mx_step(c, "step_brownian_mixed", prescribed, body_in, slip, max_iter, rtol, F, iters, resid);
-  if ((rc = flow_check(c, c->S.N_bod))) return rc;
-  if ((rc = rbl_dev_init(c))) return rc;
-  flow_begin_step(c);
-  const size_t nb6 = 6 * (size_t)c->S.N_bod;
-  MxBuf B;
-  double *dW;
-  bool have_slip;
-  if ((rc = mx_upload(c, B, prescribed, body_in, slip, true, np, &have_slip))) return rc;   // the models at q^n; forces: free bodies only
-  if ((rc = step_upload_W(c, W, &dW))) return rc;
-  return step_midpoint(
-      c,
-      [&](double *Xh, double *Qh) {                       // s takes the slip's place in the solve's workspace: it never leaves the device
-        return rhs_and_midpoint_core(c, prescribed, B.mask, B.body_in, have_slip ? B.slip : nullptr, dW, seed, method, split_rand, delta, B.slip,
-                                     Xh, Qh);
-      },
-      [&](double *U) {
-        int r = mx_solve(c, B, true, np, max_iter, rtol, iters, resid);
-        if (!r) r = flow_record_moments(c, B.x);                          // RBL_OPT_RECORD_MOMENTS: lever arms of q^{n+1/2}
-        if (!r) r = copy_d2h(c, U, B.U, sizeof(double) * nb6);
-        if (!r && F) r = copy_d2h(c, F, B.F, sizeof(double) * nb6);
-        return r ? r : finish_and_check(c);
-      });
+  return mx_bd_step(c, prescribed, 1, np, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, F, iters, resid);
+}
+
+// ---- the Brownian midpoint step with a mask per velocity component: prescribed6[6 N_bod], every body's rotation entries all equal ----
+int rbl_RHS_and_Midpoint_mixed_dof_dev(rbl_ctx *c, const uint8_t *prescribed6, const double *d_body_in, const double *d_slip,
+                                       const double *d_W, uint64_t seed, int method, int split_rand, double delta, double *d_s,
+                                       double *X_half, double *Q_half)
+{
+  return mx_bd_rhs_dev(c, "RHS_and_Midpoint_mixed_dof_dev", prescribed6, 6, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s,
+                       X_half, Q_half);
+}
+
+int rbl_RHS_and_Midpoint_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *body_in, const double *slip, const double *W,
+                                   uint64_t seed, int method, int split_rand, double delta, double *s, double *X_half, double *Q_half)
+{
+  return mx_bd_rhs_host(c, "RHS_and_Midpoint_mixed_dof", prescribed6, 6, body_in, slip, W, seed, method, split_rand, delta, s, X_half,
+                        Q_half);
+}
+
+int rbl_step_brownian_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *body_in, const double *slip, const double *W,
+                                uint64_t seed, int method, int split_rand, double delta, int max_iter, double rtol, double *F,
+                                int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  int np = 0;
+  const int rc = mx_bd_check(c, "step_brownian_mixed_dof", prescribed6, body_in, max_iter, rtol, delta, &np, 6); if (rc) return rc;
+  if (!(c->S.kBT > 1e-10))                               // no Brownian terms: the deterministic step with this mask
+    return mx_step(c, "step_brownian_mixed_dof", prescribed6, body_in, slip, max_iter, rtol, F, iters, resid, 6);
+  if (np == 0) {                                         // nothing prescribed: rbl_step_brownian itself, hence its bits (the masked
+    // solve goes through another GMRES driver and would differ from it in the last digits); F: the loads it solved with, echoed
+    int r = rbl_step_brownian(c, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, iters, resid);
+    if (!r && F && !(r = copy_d2h(c, F, step_force_dev(c), sizeof(double) * 6 * (size_t)c->S.N_bod))) r = finish_and_check(c);
+    return r;
+  }
+  return mx_bd_step(c, prescribed6, 6, np, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, F, iters, resid);
 }

@@ -11,7 +11,7 @@ the GPU.  Replicas never interact.  Sizes are those of the one-kernel solver (N_
 """
 import numpy as np
 
-from ._lib import RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError
+from ._lib import RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError, check_brownian_mask6
 
 
 def _fail(message):
@@ -186,6 +186,24 @@ class Ensemble:
         m, b, s = self._prescribed_dof_mask(prescribed), self._body_in(body_in), self._slip(slip)
         return self.ctx.ensemble_step_mixed_dof(m, b, max_iter=max_iter, rtol=rtol, slip=s)
 
+    def step_brownian_mixed_dof(self, prescribed, body_in, slip=None, W=None, seed=0, split_rand=True, delta=1e-4, max_iter=50,
+                                rtol=1e-8):
+        """one stochastic midpoint step of every replica with prescribed velocity components: a quasi-2D Brownian layer (U_z = 0),
+        a trapped probe held in place and free to turn, a roller with Omega imposed whose translation diffuses.  prescribed: bool
+        (N_bod, 6) or (R, N_bod, 6) in which every body's three rotation entries are all False or all True -- anything else is a
+        ValueError naming the replica and the body: a partly prescribed rotation is not a subset of the coordinates and its drift
+        has not been derived.  -> (F (R, 6 N_bod), iterations (R,), residual estimates (R,)); F of a prescribed component is the
+        instantaneous load along it, thermal part included.  W as step_brownian"""
+        m, b, s = self._prescribed_dof_mask(prescribed), self._body_in(body_in), self._slip(slip)
+        check_brownian_mask6("ensemble_step_brownian_mixed_dof", m, self.N_bodies, self.R)
+        if W is not None:
+            W = np.asarray(W, dtype=np.float64)
+            n = 9 * self.N_bodies * self.blobs_per_body
+            if W.shape != (self.R, n):
+                _fail("W must have shape (%d, %d); got %s" % (self.R, n, W.shape))
+        return self.ctx.ensemble_step_brownian_mixed_dof(m, b, W=W, seed=seed, split_rand=split_rand, delta=delta, max_iter=max_iter,
+                                                         rtol=rtol, slip=s)
+
     # ------------------------------------------------------------------ a run of steps (include/rbl.h section 5, rbl_ensemble_run)
     def run(self, n_steps, F=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error="stop",
             check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1e-4, max_iter=50, rtol=1e-8, prescribed_dof=None):
@@ -194,7 +212,8 @@ class Ensemble:
         F_mean for runs with prescribed bodies, steps_done, stopped_at, and with stride > 0 the frames X, Q, accepted_at, F after
         every stride-th step).  F as step_brownian takes it, or prescribed with body_in as step_brownian_mixed; step n draws its
         noise from seed + n; brownian=False: deterministic steps.  prescribed_dof with body_in (instead of F or prescribed): a mask
-        per velocity component as step_mixed_dof takes it, deterministic steps only (a Brownian run at kBT > 0 is refused).
+        per velocity component as step_mixed_dof takes it, deterministic steps only (a Brownian run at kBT > 0 is refused: loop over
+        step_brownian_mixed_dof instead).
         on_error="stop": the first failing step commits nothing, nor does any later one; RblError is raised as the step methods
         raise it, the partial result stays on self.last_run.  on_error="reject": a failing replica keeps its configuration and
         tries again with the next step's noise (the customary redraw, not an unbiased one: see rejected), the others go on; the

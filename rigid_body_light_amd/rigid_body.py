@@ -13,14 +13,15 @@ Beyond the reference surface (its C++ has these, its Python does not): `solve_sa
 `dense_mobility`, `velocity_field` (the flow at arbitrary points), prescribed kinematics (`solve_mixed`, `step_mixed`,
 `body_resistance_matrix`: bodies that are held or driven, and the loads that takes; `solve_mixed_dof`, `step_mixed_dof`: the same for
 single velocity components; `solve_mixed_multi`, `solve_mixed_dof_multi`: many right-hand sides under one mask in lock step; `step_brownian_mixed`,
-`RHS_and_Midpoint_mixed`: the same among Brownian bodies), a force model the reference does not have (`set_interactions`, `interaction_forces`),
+`RHS_and_Midpoint_mixed`: the same among Brownian bodies; `step_brownian_mixed_dof`, `RHS_and_Midpoint_mixed_dof`: Brownian steps with single
+velocity components prescribed, a body's rotation wholly or not at all), a force model the reference does not have (`set_interactions`, `interaction_forces`),
 and an imposed flow, a body-frame slip and stresslets (`set_background_flow`, `set_body_slip`, `flow_slip`, `first_moments`, `stresslets`,
 `record_moments`, `step_moments`).
 """
 import numpy as np
 
 from . import c_rigid as _ext
-from ._lib import dipole_args, field_args, table_arrays, tabulate  # noqa: F401
+from ._lib import check_brownian_mask6, dipole_args, field_args, table_arrays, tabulate  # noqa: F401
 
 _KBT_IN_WRAPPER = 1.0   # the reference wrapper passes kBT = 1 whatever the caller wants (src/Rigid.py:23)
 
@@ -525,6 +526,37 @@ class RigidBody:
         W = self._noise_arg(W)
         return self.cb.step_brownian_mixed(mask, bi, sl, W, int(seed), method, bool(split_rand), float(delta),
                                            int(max_iter), float(rtol))
+
+    def _brownian_dof_args(self, who, prescribed, body_in, slip):
+        mask, bi, sl = self._mixed_dof_args(prescribed, body_in, slip)
+        check_brownian_mask6(who, mask, self.N_bodies)
+        return mask, bi, sl
+
+    def RHS_and_Midpoint_mixed_dof(self, prescribed, body_in, slip=None, W=None, seed=0, method="cholesky", split_rand=True, delta=1.0e-4):
+        """RHS_and_Midpoint_mixed with a mask per velocity component (boolean, shape (N_bodies, 6), as solve_mixed_dof takes it) in
+        which every body's three rotation entries are all False or all True: s = slip - kBT M_RFD - BI with the RFD direction
+        D_f Kinv W_rfd, and q^{n+1/2} = q^n displaced by D_f (dt/2) c1 Kinv M^{1/2}W1 + D_p (dt/2) U_p, component by component.
+        Nothing is committed.  -> (s, X_half, Q_half)"""
+        mask, bi, sl = self._brownian_dof_args("RHS_and_Midpoint_mixed_dof", prescribed, body_in, slip)
+        W = self._noise_arg(W)
+        return self.cb.RHS_and_Midpoint_mixed_dof(mask, bi, sl, W, int(seed), method, bool(split_rand), float(delta))
+
+    def step_brownian_mixed_dof(self, prescribed, body_in, slip=None, W=None, seed=0, method="lanczos_pc", split_rand=True, delta=1.0e-4,
+                                max_iter=50, rtol=1.0e-8):
+        """One stochastic midpoint step with prescribed velocity components: a quasi-2D Brownian layer (U_z = 0 for every body), a
+        trapped probe held in place and free to turn, a microroller with Omega imposed whose translation diffuses.  `prescribed` is
+        a boolean array of shape (N_bodies, 6) as step_mixed_dof takes it, with ONE restriction: a body's three rotation entries
+        are all False or all True.  Then the free components are a subset of the coordinates (translations are Cartesian, a whole
+        rotation is treated as the all-free step treats it, and K^T K has no translation-rotation coupling), and the argument of
+        step_brownian_mixed carries over: the free components' velocity has the covariance (2 kBT/dt) Ntilde with
+        Ntilde = ((K D_f)^T M^-1 K D_f)^-1 and the drift kBT div Ntilde over the free coordinates.  A partly prescribed rotation
+        is a ValueError naming the body: nobody has derived its drift.  RHS_and_Midpoint_mixed_dof at q^n, solve_mixed_dof at
+        q^{n+1/2}, update from q^n -- a prescribed component advances by exactly dt U_p.  The force model loads the free components
+        only, at q^n.  With whole rows the results are step_brownian_mixed's, bit for bit.  -> (F, iterations, residual estimate)"""
+        mask, bi, sl = self._brownian_dof_args("step_brownian_mixed_dof", prescribed, body_in, slip)
+        W = self._noise_arg(W)
+        return self.cb.step_brownian_mixed_dof(mask, bi, sl, W, int(seed), method, bool(split_rand), float(delta),
+                                               int(max_iter), float(rtol))
 
     def body_resistance_matrix(self, max_iter=100, rtol=1.0e-8, columns=None, lock_step=False):
         """The (6 N_bodies) x (6 N_bodies) body resistance matrix R = N^-1 of the current configuration, the inverse of
