@@ -336,7 +336,8 @@ __global__ void k_saddle_tail(const double *__restrict__ lever, const double *__
                               int nb6)
 {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx < nb6) out[3 * N + idx] = ktl[idx];
+  // the grid is sized by the blobs: bodies of fewer than six blobs have more body rows than it has threads, so stride over them
+  for (long i = idx; i < nb6; i += (long)gridDim.x * blockDim.x) out[3 * N + i] = ktl[i];
   if (idx >= N) return;
   const int b = (int)(idx / N_blb);
   double k0, k1, k2;

@@ -922,7 +922,7 @@ int rbl_ensemble_set_config(rbl_ctx *c, int R, int N_bod, const double *X, const
   if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, "ensemble: not on a context with a communicator (run one ensemble per process)");
   if (R < 1 || R > ENS_R_MAX) return rbl_fail(c, RBL_ERR_SIZE, "ensemble: R must be 1 .. 65535");
   if (!rbl_gmres_small_fits(c->S.N_blb, N_bod, 1, false))
-    return rbl_fail(c, RBL_ERR_SIZE, "ensemble: N_bod * N_blb must be <= 256 and N_bod <= 64 (the one-kernel solver)");
+    return rbl_fail(c, RBL_ERR_SIZE, "ensemble: the system is beyond the one-kernel solver (N_bod * N_blb <= 256, N_bod <= 64 and its vectors within 150 KB of LDS: about 75 N_blobs + 60 N_bod doubles)");
   if (!X || !Q) return rbl_fail(c, RBL_ERR_ARG, "ensemble_set_config: null argument");
   {                                                    // K^T K of the structure (rotation invariant) must be invertible (:312-316)
     RblBodyState T = c->S;

@@ -16,7 +16,11 @@
 // otherwise it goes to a global workspace (L2-resident).  A first version kept basis and Hessenberg matrix in global
 // memory: thread 0's Givens recurrence then was a chain of dependent L2 round trips, ~10 us per iteration.
 // Every sum has a fixed order: results are bitwise reproducible, like the rest of the library.
-// Limits: N <= 256 blobs, N_bod <= 64, diagonal preconditioner, max_iter <= 255 (checked by the launcher).
+// Limits: N <= 256 blobs, N_bod <= 64, diagonal preconditioner, max_iter <= 255, AND the vectors below within SG_LDS_MAX = 150 KB
+// (rbl_gmres_small_fits; checked by the launcher).  The LDS bound is the one that binds: the sixteen accumulator sets of the pair
+// sweep alone are 384 N bytes, so about 75 N + 60 N_bod doubles in all -- one body of 238 blobs, 49 tetrahedra (196 blobs) or 62
+// trimers at max_iter = 255; 64 x 4 and 1 x 256 blobs do NOT fit, and since the triangular factor is kept in LDS up to 64
+// iterations the bound is not monotonic in max_iter (64 trimers fit at max_iter <= 38 and at 65 .. 189).
 //
 // MIXED (the ensembles with prescribed bodies, include/rbl.h sections 5 and 7): the same solve of
 //   [M lambda - K (D_f U) ; D_f K^T lambda + D_p U] = [slip + K_p U_p ; -F_f | 0]

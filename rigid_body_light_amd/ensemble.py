@@ -7,7 +7,9 @@
     X, Q = ens.get_config()
 
 All replicas share the structure, the parameters, the wall flag and the force model; each has its own configuration, resident on
-the GPU.  Replicas never interact.  Sizes are those of the one-kernel solver (N_bod N_blb <= 256, N_bod <= 64) and 1 <= R <= 65535.
+the GPU.  Replicas never interact.  Sizes are those of the one-kernel solver (N_bod N_blb <= 256, N_bod <= 64 and its
+vectors within 150 KB of LDS, about 75 N_blobs + 60 N_bod doubles: 49 tetrahedra or one body of 238 blobs at max_iter = 255) and
+1 <= R <= 65535.
 """
 import numpy as np
 
