@@ -681,6 +681,17 @@ class DeviceContext:
                                                          float(rtol or 0.0), it.ctypes.data, res.ctypes.data))
         return it, res
 
+    @staticmethod
+    def _ens_noise(W, R, n3):
+        """W (R, 3 n3) as a contiguous array, or None"""
+        import numpy as np
+        if W is None:
+            return None
+        Wh = np.ascontiguousarray(np.asarray(W, dtype=np.float64))
+        if Wh.size != R * 3 * n3:
+            raise ValueError("W must have shape (%d, %d); got %s" % (R, 3 * n3, Wh.shape))
+        return Wh
+
     def ensemble_step_brownian(self, F_body, W=None, seed=0, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1e-8, slip=None):
         """one stochastic midpoint step of every replica (dense Cholesky root) -> (iterations[R], residual estimates[R]);
         W: (R, 3 n3) standard normals [W1 | W2 | W_rfd] per replica, or None to draw them from `seed`"""
@@ -689,11 +700,7 @@ class DeviceContext:
         n3 = 3 * nb * self._sizes()[1]
         F = self._ens_vec(F_body, 6 * nb, "F_body")
         sl = None if slip is None else self._ens_vec(slip, n3, "slip")
-        Wh = None
-        if W is not None:
-            Wh = np.ascontiguousarray(np.asarray(W, dtype=np.float64))
-            if Wh.size != R * 3 * n3:
-                raise ValueError("W must have shape (%d, %d); got %s" % (R, 3 * n3, Wh.shape))
+        Wh = self._ens_noise(W, R, n3)
         it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
         self._chk(self.L.rbl_ensemble_step_brownian(self.h, F.ctypes.data, None if sl is None else sl.ctypes.data,
                                                     None if Wh is None else Wh.ctypes.data, int(seed), int(bool(split_rand)),
@@ -730,95 +737,72 @@ class DeviceContext:
         sl = None if slip is None else self._ens_vec(slip, 3 * nb * self._sizes()[1], "slip")
         return R, nb, m, bi, sl
 
-    def ensemble_solve_mixed(self, prescribed, body_in, max_iter=100, rtol=1.0e-8, slip=None):
-        """solve_mixed at every replica's configuration (nothing moves) -> (lambda (R, n3), U (R, 6 N_bod), F (R, 6 N_bod),
-        iterations[R], residual estimates[R]); prescribed: 0/1 per body, (N_bod,) or (R, N_bod)"""
+    def _ens_solve_mixed(self, who, per, prescribed, body_in, max_iter, rtol, slip):
         import numpy as np
-        R, nb, m, bi, sl = self._ens_mixed_args("ensemble_solve_mixed", prescribed, body_in, slip)
+        R, nb, m, bi, sl = self._ens_mixed_args(who, prescribed, body_in, slip, per=per)
         n3 = 3 * nb * self._sizes()[1]
         lam, U, F = np.zeros((R, n3)), np.zeros((R, 6 * nb)), np.zeros((R, 6 * nb))
         it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
-        self._chk(self.L.rbl_ensemble_solve_mixed(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
-                                                  int(max_iter), float(rtol or 0.0), lam.ctypes.data, U.ctypes.data, F.ctypes.data,
-                                                  it.ctypes.data, res.ctypes.data))
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                int(max_iter), float(rtol or 0.0), lam.ctypes.data, U.ctypes.data, F.ctypes.data,
+                                                it.ctypes.data, res.ctypes.data))
         return lam, U, F, it, res
+
+    def _ens_step_mixed(self, who, per, prescribed, body_in, max_iter, rtol, slip):
+        import numpy as np
+        R, nb, m, bi, sl = self._ens_mixed_args(who, prescribed, body_in, slip, per=per)
+        F = np.zeros((R, 6 * nb))
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                int(max_iter), float(rtol or 0.0), F.ctypes.data, it.ctypes.data, res.ctypes.data))
+        return F, it, res
+
+    def _ens_step_brownian_mixed(self, who, per, prescribed, body_in, W, seed, split_rand, delta, max_iter, rtol, slip):
+        import numpy as np
+        R, nb, m, bi, sl = self._ens_mixed_args(who, prescribed, body_in, slip, per=per)
+        if per == 6:
+            check_brownian_mask6(who, m, nb, R)
+        Wh = self._ens_noise(W, R, 3 * nb * self._sizes()[1])
+        F = np.zeros((R, 6 * nb))
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                None if Wh is None else Wh.ctypes.data, int(seed), int(bool(split_rand)), float(delta),
+                                                int(max_iter), float(rtol or 0.0), F.ctypes.data, it.ctypes.data, res.ctypes.data))
+        return F, it, res
+
+    def ensemble_solve_mixed(self, prescribed, body_in, max_iter=100, rtol=1.0e-8, slip=None):
+        """solve_mixed at every replica's configuration (nothing moves) -> (lambda (R, n3), U (R, 6 N_bod), F (R, 6 N_bod),
+        iterations[R], residual estimates[R]); prescribed: 0/1 per body, (N_bod,) or (R, N_bod)"""
+        return self._ens_solve_mixed("ensemble_solve_mixed", 1, prescribed, body_in, max_iter, rtol, slip)
 
     def ensemble_step_mixed(self, prescribed, body_in, max_iter=50, rtol=1.0e-8, slip=None):
         """one deterministic step of every replica with prescribed bodies -> (F (R, 6 N_bod), iterations[R], residual estimates[R])"""
-        import numpy as np
-        R, nb, m, bi, sl = self._ens_mixed_args("ensemble_step_mixed", prescribed, body_in, slip)
-        F = np.zeros((R, 6 * nb))
-        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
-        self._chk(self.L.rbl_ensemble_step_mixed(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
-                                                 int(max_iter), float(rtol or 0.0), F.ctypes.data, it.ctypes.data, res.ctypes.data))
-        return F, it, res
+        return self._ens_step_mixed("ensemble_step_mixed", 1, prescribed, body_in, max_iter, rtol, slip)
 
     def ensemble_solve_mixed_dof(self, prescribed6, body_in, max_iter=100, rtol=1.0e-8, slip=None):
         """solve_mixed_dof at every replica's configuration (nothing moves) -> (lambda (R, n3), U (R, 6 N_bod), F (R, 6 N_bod),
         iterations[R], residual estimates[R]); prescribed6: 0/1 per velocity component, (N_bod, 6) or (R, N_bod, 6)"""
-        import numpy as np
-        R, nb, m, bi, sl = self._ens_mixed_args("ensemble_solve_mixed_dof", prescribed6, body_in, slip, per=6)
-        n3 = 3 * nb * self._sizes()[1]
-        lam, U, F = np.zeros((R, n3)), np.zeros((R, 6 * nb)), np.zeros((R, 6 * nb))
-        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
-        self._chk(self.L.rbl_ensemble_solve_mixed_dof(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
-                                                      int(max_iter), float(rtol or 0.0), lam.ctypes.data, U.ctypes.data, F.ctypes.data,
-                                                      it.ctypes.data, res.ctypes.data))
-        return lam, U, F, it, res
+        return self._ens_solve_mixed("ensemble_solve_mixed_dof", 6, prescribed6, body_in, max_iter, rtol, slip)
 
     def ensemble_step_mixed_dof(self, prescribed6, body_in, max_iter=50, rtol=1.0e-8, slip=None):
         """one deterministic step of every replica with prescribed velocity components -> (F (R, 6 N_bod), iterations[R],
         residual estimates[R])"""
-        import numpy as np
-        R, nb, m, bi, sl = self._ens_mixed_args("ensemble_step_mixed_dof", prescribed6, body_in, slip, per=6)
-        F = np.zeros((R, 6 * nb))
-        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
-        self._chk(self.L.rbl_ensemble_step_mixed_dof(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
-                                                     int(max_iter), float(rtol or 0.0), F.ctypes.data, it.ctypes.data, res.ctypes.data))
-        return F, it, res
+        return self._ens_step_mixed("ensemble_step_mixed_dof", 6, prescribed6, body_in, max_iter, rtol, slip)
 
     def ensemble_step_brownian_mixed(self, prescribed, body_in, W=None, seed=0, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8,
                                      slip=None):
         """one stochastic midpoint step of every replica with prescribed bodies (dense Cholesky root) -> (F (R, 6 N_bod),
         iterations[R], residual estimates[R]); W as ensemble_step_brownian"""
-        import numpy as np
-        R, nb, m, bi, sl = self._ens_mixed_args("ensemble_step_brownian_mixed", prescribed, body_in, slip)
-        n3 = 3 * nb * self._sizes()[1]
-        Wh = None
-        if W is not None:
-            Wh = np.ascontiguousarray(np.asarray(W, dtype=np.float64))
-            if Wh.size != R * 3 * n3:
-                raise ValueError("W must have shape (%d, %d); got %s" % (R, 3 * n3, Wh.shape))
-        F = np.zeros((R, 6 * nb))
-        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
-        self._chk(self.L.rbl_ensemble_step_brownian_mixed(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
-                                                          None if Wh is None else Wh.ctypes.data, int(seed), int(bool(split_rand)),
-                                                          float(delta), int(max_iter), float(rtol or 0.0), F.ctypes.data,
-                                                          it.ctypes.data, res.ctypes.data))
-        return F, it, res
+        return self._ens_step_brownian_mixed("ensemble_step_brownian_mixed", 1, prescribed, body_in, W, seed, split_rand, delta, max_iter,
+                                             rtol, slip)
 
     def ensemble_step_brownian_mixed_dof(self, prescribed6, body_in, W=None, seed=0, split_rand=True, delta=1.0e-4, max_iter=50,
                                          rtol=1.0e-8, slip=None):
         """one stochastic midpoint step of every replica with prescribed velocity components (dense Cholesky root); prescribed6:
         (N_bod, 6) or (R, N_bod, 6), every body's rotation entries all 0 or all 1 (check_brownian_mask6) -> (F (R, 6 N_bod),
         iterations[R], residual estimates[R]); W as ensemble_step_brownian"""
-        import numpy as np
-        who = "ensemble_step_brownian_mixed_dof"
-        R, nb, m, bi, sl = self._ens_mixed_args(who, prescribed6, body_in, slip, per=6)
-        check_brownian_mask6(who, m, nb, R)
-        n3 = 3 * nb * self._sizes()[1]
-        Wh = None
-        if W is not None:
-            Wh = np.ascontiguousarray(np.asarray(W, dtype=np.float64))
-            if Wh.size != R * 3 * n3:
-                raise ValueError("W must have shape (%d, %d); got %s" % (R, 3 * n3, Wh.shape))
-        F = np.zeros((R, 6 * nb))
-        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
-        self._chk(self.L.rbl_ensemble_step_brownian_mixed_dof(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
-                                                              None if Wh is None else Wh.ctypes.data, int(seed), int(bool(split_rand)),
-                                                              float(delta), int(max_iter), float(rtol or 0.0), F.ctypes.data,
-                                                              it.ctypes.data, res.ctypes.data))
-        return F, it, res
+        return self._ens_step_brownian_mixed("ensemble_step_brownian_mixed_dof", 6, prescribed6, body_in, W, seed, split_rand, delta,
+                                             max_iter, rtol, slip)
 
     def ensemble_run(self, n_steps, F_body=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error=RUN_STOP,
                      check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8, per=1):
@@ -1133,81 +1117,66 @@ class DeviceContext:
         """solve_mixed_multi_dev with a mask per velocity component (prescribed6: a host array of 6 N_bod entries)"""
         return self._mixed_multi_dev("solve_mixed_dof_multi_dev", 6, prescribed6, nrhs, d_body_in, d_slip, max_iter, rtol, d_lam, d_U, d_F)
 
-    def _mixed_sizes(self, who, prescribed):
+    def _mixed_sizes(self, who, per, prescribed):
+        """the mask of a Brownian call -> (mask, N_bod, N_blb).  per = 6: a mask per velocity component, 6 N_bod entries, every
+        body's rotation entries all 0 or all 1"""
         import numpy as np
         m = np.ascontiguousarray(prescribed, dtype=np.uint8).reshape(-1)
         nb, nl = C.c_int(0), C.c_int(0)
         self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), C.byref(nl)))
-        if m.size != nb.value:
-            raise ValueError(who + ": prescribed must have N_bod entries")
+        if m.size != per * nb.value:
+            raise ValueError(who + (": prescribed6 must have 6 N_bod entries" if per == 6 else ": prescribed must have N_bod entries"))
+        if per == 6:
+            check_brownian_mask6(who, m, nb.value)
         return m, nb.value, nl.value
 
-    def RHS_and_Midpoint_mixed_dev(self, prescribed, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s):
-        """right-hand side and predictor of the Brownian step with prescribed bodies on device addresses (prescribed: a host
-        array; d_slip, d_W may be None / 0; d_s: 3 N_blobs) -> (X_half, Q_half) on the host"""
+    def _rhs_and_midpoint_mixed_dev(self, who, per, prescribed, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s):
         import numpy as np
-        m, nb, _ = self._mixed_sizes("RHS_and_Midpoint_mixed_dev", prescribed)
+        m, nb, _ = self._mixed_sizes(who, per, prescribed)
         X = np.zeros(3 * nb); Q = np.zeros(4 * nb)
-        self._chk(self.L.rbl_RHS_and_Midpoint_mixed_dev(self.h, m.ctypes.data, d_body_in, d_slip or None, d_W or None, int(seed), int(method),
-                                                        int(bool(split_rand)), float(delta), d_s, X.ctypes.data, Q.ctypes.data))
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, d_body_in, d_slip or None, d_W or None, int(seed), int(method),
+                                                int(bool(split_rand)), float(delta), d_s, X.ctypes.data, Q.ctypes.data))
         return X.reshape(-1, 3), Q.reshape(-1, 4)
 
-    def step_brownian_mixed(self, prescribed, body_in, max_iter=50, rtol=1.0e-8, slip=None, W=None, seed=0, method=2, split_rand=True,
-                            delta=1.0e-4):
-        """one stochastic midpoint step with prescribed bodies inside librbl; host arrays -> (F, iterations, residual estimate)"""
+    def _step_brownian_mixed(self, who, per, prescribed, body_in, max_iter, rtol, slip, W, seed, method, split_rand, delta):
         import numpy as np
-        m, nb, nl = self._mixed_sizes("step_brownian_mixed", prescribed)
+        m, nb, nl = self._mixed_sizes(who, per, prescribed)
         bi = np.ascontiguousarray(body_in, dtype=np.float64).reshape(-1)
         sl = None if slip is None else np.ascontiguousarray(slip, dtype=np.float64).reshape(-1)
         Wh = None if W is None else np.ascontiguousarray(W, dtype=np.float64).reshape(-1)
         if bi.size != 6 * nb or (sl is not None and sl.size != 3 * nb * nl) or (Wh is not None and Wh.size != 9 * nb * nl):
-            raise ValueError("step_brownian_mixed: body_in (6 N_bod), slip (3 N_blobs) or W (9 N_blobs) has the wrong size")
+            raise ValueError(who + ": body_in (6 N_bod), slip (3 N_blobs) or W (9 N_blobs) has the wrong size")
         F = np.empty(6 * nb)
         it, res = C.c_int(0), C.c_double(0.0)
-        self._chk(self.L.rbl_step_brownian_mixed(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
-                                                 None if Wh is None else Wh.ctypes.data, int(seed), int(method), int(bool(split_rand)),
-                                                 float(delta), int(max_iter), float(rtol), F.ctypes.data, C.byref(it), C.byref(res)))
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                None if Wh is None else Wh.ctypes.data, int(seed), int(method), int(bool(split_rand)),
+                                                float(delta), int(max_iter), float(rtol), F.ctypes.data, C.byref(it), C.byref(res)))
         return F, it.value, res.value
 
-    def _mixed_dof_sizes(self, who, prescribed6):
-        """the mask per velocity component of a Brownian call: 6 N_bod entries, every body's rotation entries all 0 or all 1"""
-        import numpy as np
-        m = np.ascontiguousarray(prescribed6, dtype=np.uint8).reshape(-1)
-        nb, nl = C.c_int(0), C.c_int(0)
-        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), C.byref(nl)))
-        if m.size != 6 * nb.value:
-            raise ValueError(who + ": prescribed6 must have 6 N_bod entries")
-        check_brownian_mask6(who, m, nb.value)
-        return m, nb.value, nl.value
+    def RHS_and_Midpoint_mixed_dev(self, prescribed, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s):
+        """right-hand side and predictor of the Brownian step with prescribed bodies on device addresses (prescribed: a host
+        array; d_slip, d_W may be None / 0; d_s: 3 N_blobs) -> (X_half, Q_half) on the host"""
+        return self._rhs_and_midpoint_mixed_dev("RHS_and_Midpoint_mixed_dev", 1, prescribed, d_body_in, d_slip, d_W, seed, method,
+                                                split_rand, delta, d_s)
+
+    def step_brownian_mixed(self, prescribed, body_in, max_iter=50, rtol=1.0e-8, slip=None, W=None, seed=0, method=2, split_rand=True,
+                            delta=1.0e-4):
+        """one stochastic midpoint step with prescribed bodies inside librbl; host arrays -> (F, iterations, residual estimate)"""
+        return self._step_brownian_mixed("step_brownian_mixed", 1, prescribed, body_in, max_iter, rtol, slip, W, seed, method, split_rand,
+                                         delta)
 
     def RHS_and_Midpoint_mixed_dof_dev(self, prescribed6, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s):
         """RHS_and_Midpoint_mixed_dev with a mask per velocity component (prescribed6: a host array of 6 N_bod entries, every
         body's rotation entries all 0 or all 1) -> (X_half, Q_half) on the host"""
-        import numpy as np
-        m, nb, _ = self._mixed_dof_sizes("RHS_and_Midpoint_mixed_dof_dev", prescribed6)
-        X = np.zeros(3 * nb); Q = np.zeros(4 * nb)
-        self._chk(self.L.rbl_RHS_and_Midpoint_mixed_dof_dev(self.h, m.ctypes.data, d_body_in, d_slip or None, d_W or None, int(seed),
-                                                            int(method), int(bool(split_rand)), float(delta), d_s, X.ctypes.data,
-                                                            Q.ctypes.data))
-        return X.reshape(-1, 3), Q.reshape(-1, 4)
+        return self._rhs_and_midpoint_mixed_dev("RHS_and_Midpoint_mixed_dof_dev", 6, prescribed6, d_body_in, d_slip, d_W, seed, method,
+                                                split_rand, delta, d_s)
 
     def step_brownian_mixed_dof(self, prescribed6, body_in, max_iter=50, rtol=1.0e-8, slip=None, W=None, seed=0, method=2, split_rand=True,
                                 delta=1.0e-4):
         """one stochastic midpoint step with prescribed velocity components inside librbl; host arrays -> (F, iterations, residual
         estimate)"""
-        import numpy as np
-        m, nb, nl = self._mixed_dof_sizes("step_brownian_mixed_dof", prescribed6)
-        bi = np.ascontiguousarray(body_in, dtype=np.float64).reshape(-1)
-        sl = None if slip is None else np.ascontiguousarray(slip, dtype=np.float64).reshape(-1)
-        Wh = None if W is None else np.ascontiguousarray(W, dtype=np.float64).reshape(-1)
-        if bi.size != 6 * nb or (sl is not None and sl.size != 3 * nb * nl) or (Wh is not None and Wh.size != 9 * nb * nl):
-            raise ValueError("step_brownian_mixed_dof: body_in (6 N_bod), slip (3 N_blobs) or W (9 N_blobs) has the wrong size")
-        F = np.empty(6 * nb)
-        it, res = C.c_int(0), C.c_double(0.0)
-        self._chk(self.L.rbl_step_brownian_mixed_dof(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
-                                                     None if Wh is None else Wh.ctypes.data, int(seed), int(method), int(bool(split_rand)),
-                                                     float(delta), int(max_iter), float(rtol), F.ctypes.data, C.byref(it), C.byref(res)))
-        return F, it.value, res.value
+        return self._step_brownian_mixed("step_brownian_mixed_dof", 6, prescribed6, body_in, max_iter, rtol, slip, W, seed, method,
+                                         split_rand, delta)
 
     def blob_positions(self, body_begin, body_end, dout):
         self._chk(self.L.rbl_blob_positions_dev(self.h, body_begin, body_end, dout))

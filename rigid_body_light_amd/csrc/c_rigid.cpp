@@ -438,81 +438,67 @@ struct CManyBodies {
     return out;
   }
   // prescribed kinematics (include/rbl.h section 7): mask[N_bod] 0/1, body_in[6 N_bod] loads of the free bodies / velocities of the
-  // prescribed ones -> (lambda, U, F, iterations, residual estimate)
+  // prescribed ones -> (lambda, U, F, iterations, residual estimate).  per: mask entries per body, 1, or 6 for a mask per velocity
+  // component in body_in's order (the _dof methods, which call the _dof entry points); one body serves each pair of methods
   using marr = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>;
-  const double *mixed_args(const char *who, const marr &mask, const darr &body_in, const py::object &slip, darr &sl) const
+  [[noreturn]] static void bad_mixed_arg(int per, const std::string &msg)   // the whole-body methods raise RuntimeError, the _dof ones ValueError
   {
-    if (mask.size() != (py::ssize_t)n_bod()) throw std::runtime_error(std::string(who) + ": prescribed must have length N_bod");
-    if (body_in.size() != 6 * (py::ssize_t)n_bod()) throw std::runtime_error(std::string(who) + ": body_in must have length 6*N_bod");
+    if (per == 6) throw py::value_error(msg);
+    throw std::runtime_error(msg);
+  }
+  const double *mixed_args(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip, darr &sl) const
+  {
+    if (mask.size() != per * (py::ssize_t)n_bod())
+      bad_mixed_arg(per, std::string(who) + (per == 6 ? ": prescribed must have length 6*N_bod" : ": prescribed must have length N_bod"));
+    if (body_in.size() != 6 * (py::ssize_t)n_bod()) bad_mixed_arg(per, std::string(who) + ": body_in must have length 6*N_bod");
     if (slip.is_none()) return nullptr;
     sl = slip.cast<darr>();
-    if (sl.size() != n3()) throw std::runtime_error(std::string(who) + ": slip must have length 3*N_blobs");
+    if (sl.size() != n3()) bad_mixed_arg(per, std::string(who) + ": slip must have length 3*N_blobs");
     return sl.data();
   }
-  py::tuple solve_mixed(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
+  py::tuple solve_mixed_any(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip, int max_iter, double rtol)
   {
     darr sl;
-    const double *sp = mixed_args("solve_mixed", mask, body_in, slip, sl);
+    const double *sp = mixed_args(who, per, mask, body_in, slip, sl);
     darr lam(n3()), U(6 * (py::ssize_t)n_bod()), F(6 * (py::ssize_t)n_bod());
     int it = 0, rc; double res = 0.0;
     {
       py::gil_scoped_release rel;
-      rc = rbl_solve_mixed(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, lam.mutable_data(), U.mutable_data(), F.mutable_data(),
-                           &it, &res);
+      rc = (per == 6 ? rbl_solve_mixed_dof : rbl_solve_mixed)(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, lam.mutable_data(),
+                                                              U.mutable_data(), F.mutable_data(), &it, &res);
     }
     check(rc);
     return py::make_tuple(lam, U, F, it, res);
   }
   // the solve, then evolve_X_Q(U) -> (F, iterations, residual estimate)
-  py::tuple step_mixed(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
+  py::tuple step_mixed_any(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip, int max_iter, double rtol)
   {
     darr sl;
-    const double *sp = mixed_args("step_mixed", mask, body_in, slip, sl);
+    const double *sp = mixed_args(who, per, mask, body_in, slip, sl);
     darr F(6 * (py::ssize_t)n_bod());
     int it = 0, rc; double res = 0.0;
     {
       py::gil_scoped_release rel;
-      rc = rbl_step_mixed(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, F.mutable_data(), &it, &res);
+      rc = (per == 6 ? rbl_step_mixed_dof : rbl_step_mixed)(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, F.mutable_data(), &it, &res);
     }
     check(rc);
     return py::make_tuple(F, it, res);
   }
-  // a mask per velocity component (rbl_solve_mixed_dof, rbl_step_mixed_dof): mask[6 N_bod] in body_in's order
-  const double *mixed_dof_args(const char *who, const marr &mask, const darr &body_in, const py::object &slip, darr &sl) const
+  py::tuple solve_mixed(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
   {
-    if (mask.size() != 6 * (py::ssize_t)n_bod()) throw py::value_error(std::string(who) + ": prescribed must have length 6*N_bod");
-    if (body_in.size() != 6 * (py::ssize_t)n_bod()) throw py::value_error(std::string(who) + ": body_in must have length 6*N_bod");
-    if (slip.is_none()) return nullptr;
-    sl = slip.cast<darr>();
-    if (sl.size() != n3()) throw py::value_error(std::string(who) + ": slip must have length 3*N_blobs");
-    return sl.data();
+    return solve_mixed_any("solve_mixed", 1, mask, body_in, slip, max_iter, rtol);
+  }
+  py::tuple step_mixed(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
+  {
+    return step_mixed_any("step_mixed", 1, mask, body_in, slip, max_iter, rtol);
   }
   py::tuple solve_mixed_dof(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
   {
-    darr sl;
-    const double *sp = mixed_dof_args("solve_mixed_dof", mask, body_in, slip, sl);
-    darr lam(n3()), U(6 * (py::ssize_t)n_bod()), F(6 * (py::ssize_t)n_bod());
-    int it = 0, rc; double res = 0.0;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_solve_mixed_dof(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, lam.mutable_data(), U.mutable_data(), F.mutable_data(),
-                               &it, &res);
-    }
-    check(rc);
-    return py::make_tuple(lam, U, F, it, res);
+    return solve_mixed_any("solve_mixed_dof", 6, mask, body_in, slip, max_iter, rtol);
   }
   py::tuple step_mixed_dof(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
   {
-    darr sl;
-    const double *sp = mixed_dof_args("step_mixed_dof", mask, body_in, slip, sl);
-    darr F(6 * (py::ssize_t)n_bod());
-    int it = 0, rc; double res = 0.0;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_step_mixed_dof(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, F.mutable_data(), &it, &res);
-    }
-    check(rc);
-    return py::make_tuple(F, it, res);
+    return step_mixed_any("step_mixed_dof", 6, mask, body_in, slip, max_iter, rtol);
   }
   // k right-hand sides under one mask in lock step (rbl_solve_mixed_multi, rbl_solve_mixed_dof_multi): body_in (k, 6 N_bod), slip None
   // or (k, 3 N_blobs) -> (lambda (k, 3 N_blobs), U (k, 6 N_bod), F (k, 6 N_bod), iterations (k,), residual estimates (k,))
@@ -560,77 +546,64 @@ struct CManyBodies {
     if (Wa.size() != 3 * n3()) throw std::runtime_error(std::string(who) + ": W must have length 9*N_blobs (W1|W2|W_rfd)");
     return Wa.data();
   }
-  py::tuple RHS_and_Midpoint_mixed(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
-                                   bool split_rand, double delta)
+  py::tuple RHS_and_Midpoint_mixed_any(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip,
+                                       const py::object &W, uint64_t seed, const std::string &method, bool split_rand, double delta)
   {
     darr sl, Wa;
-    const double *sp = mixed_args("RHS_and_Midpoint_mixed", mask, body_in, slip, sl);
-    const double *wp = noise_arg("RHS_and_Midpoint_mixed", W, Wa);
+    const double *sp = mixed_args(who, per, mask, body_in, slip, sl);
+    const double *wp = noise_arg(who, W, Wa);
     const int m = mhalf_method(method);
     const py::ssize_t nb = n_bod();
     darr s(n3()), X(3 * nb), Q(4 * nb);
     int rc;
     {
       py::gil_scoped_release rel;
-      rc = rbl_RHS_and_Midpoint_mixed(ctx, mask.data(), body_in.data(), sp, wp, seed, m, split_rand ? 1 : 0, delta, s.mutable_data(),
-                                      X.mutable_data(), Q.mutable_data());
+      rc = (per == 6 ? rbl_RHS_and_Midpoint_mixed_dof : rbl_RHS_and_Midpoint_mixed)(ctx, mask.data(), body_in.data(), sp, wp, seed, m,
+                                                                                    split_rand ? 1 : 0, delta, s.mutable_data(),
+                                                                                    X.mutable_data(), Q.mutable_data());
     }
     check(rc);
     return py::make_tuple(s, X, Q);
   }
   // the whole step -> (F, iterations, residual estimate)
-  py::tuple step_brownian_mixed(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
-                                bool split_rand, double delta, int max_iter, double rtol)
+  py::tuple step_brownian_mixed_any(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip,
+                                    const py::object &W, uint64_t seed, const std::string &method, bool split_rand, double delta,
+                                    int max_iter, double rtol)
   {
     darr sl, Wa;
-    const double *sp = mixed_args("step_brownian_mixed", mask, body_in, slip, sl);
-    const double *wp = noise_arg("step_brownian_mixed", W, Wa);
+    const double *sp = mixed_args(who, per, mask, body_in, slip, sl);
+    const double *wp = noise_arg(who, W, Wa);
     const int m = mhalf_method(method);
     darr F(6 * (py::ssize_t)n_bod());
     int it = 0, rc; double res = 0.0;
     {
       py::gil_scoped_release rel;
-      rc = rbl_step_brownian_mixed(ctx, mask.data(), body_in.data(), sp, wp, seed, m, split_rand ? 1 : 0, delta, max_iter, rtol,
-                                   F.mutable_data(), &it, &res);
+      rc = (per == 6 ? rbl_step_brownian_mixed_dof : rbl_step_brownian_mixed)(ctx, mask.data(), body_in.data(), sp, wp, seed, m,
+                                                                              split_rand ? 1 : 0, delta, max_iter, rtol, F.mutable_data(),
+                                                                              &it, &res);
     }
     check(rc);
     return py::make_tuple(F, it, res);
   }
-  // the same with a mask per velocity component (rbl_RHS_and_Midpoint_mixed_dof, rbl_step_brownian_mixed_dof): mask[6 N_bod]
+  py::tuple RHS_and_Midpoint_mixed(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
+                                   bool split_rand, double delta)
+  {
+    return RHS_and_Midpoint_mixed_any("RHS_and_Midpoint_mixed", 1, mask, body_in, slip, W, seed, method, split_rand, delta);
+  }
+  py::tuple step_brownian_mixed(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
+                                bool split_rand, double delta, int max_iter, double rtol)
+  {
+    return step_brownian_mixed_any("step_brownian_mixed", 1, mask, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol);
+  }
   py::tuple RHS_and_Midpoint_mixed_dof(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
                                        bool split_rand, double delta)
   {
-    darr sl, Wa;
-    const double *sp = mixed_dof_args("RHS_and_Midpoint_mixed_dof", mask, body_in, slip, sl);
-    const double *wp = noise_arg("RHS_and_Midpoint_mixed_dof", W, Wa);
-    const int m = mhalf_method(method);
-    const py::ssize_t nb = n_bod();
-    darr s(n3()), X(3 * nb), Q(4 * nb);
-    int rc;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_RHS_and_Midpoint_mixed_dof(ctx, mask.data(), body_in.data(), sp, wp, seed, m, split_rand ? 1 : 0, delta, s.mutable_data(),
-                                          X.mutable_data(), Q.mutable_data());
-    }
-    check(rc);
-    return py::make_tuple(s, X, Q);
+    return RHS_and_Midpoint_mixed_any("RHS_and_Midpoint_mixed_dof", 6, mask, body_in, slip, W, seed, method, split_rand, delta);
   }
   py::tuple step_brownian_mixed_dof(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
                                     bool split_rand, double delta, int max_iter, double rtol)
   {
-    darr sl, Wa;
-    const double *sp = mixed_dof_args("step_brownian_mixed_dof", mask, body_in, slip, sl);
-    const double *wp = noise_arg("step_brownian_mixed_dof", W, Wa);
-    const int m = mhalf_method(method);
-    darr F(6 * (py::ssize_t)n_bod());
-    int it = 0, rc; double res = 0.0;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_step_brownian_mixed_dof(ctx, mask.data(), body_in.data(), sp, wp, seed, m, split_rand ? 1 : 0, delta, max_iter, rtol,
-                                       F.mutable_data(), &it, &res);
-    }
-    check(rc);
-    return py::make_tuple(F, it, res);
+    return step_brownian_mixed_any("step_brownian_mixed_dof", 6, mask, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol);
   }
   void set_interactions(double w, double eps_wall, double b_wall, double eps_blob, double b_blob, double r_cut, bool on)
   {

@@ -82,49 +82,25 @@ __global__ __launch_bounds__(BT) void k_KT_x_Lam(const double *__restrict__ leve
   if (t < 6) out[6 * b + t] = f[t];
 }
 
-// the Brownian step's two body displacements where the blob vectors live: out[0 .. nb6) = K_b^T W_rfd and out[nb6 .. 2 nb6) =
-// K_b^T (M^{1/2}W1), the sums Kinv needs (k_KT_x_Lam's, term for term).  mask (NULL: nobody) marks the prescribed bodies: such a
-// body takes no random displacement -- its RFD slots are 0, its blobs are not read -- and its predictor slots carry its own
-// velocity U_p = body_in
-__global__ __launch_bounds__(BT) void k_mx_bd_sums(const double *__restrict__ lever, const uint8_t *__restrict__ mask,
+// the Brownian step's two body displacements where the blob vectors live, k_KT_x_Lam's sums term for term.  ONE layout for
+// every mask: three blocks of nb6, out[0 .. nb6) = K_b^T W_rfd, out[nb6 .. 2 nb6) = K_b^T (M^{1/2}W1), the sums Kinv needs, and
+// out[2 nb6 .. 3 nb6) = body_in, echoed, where the host finds the velocity U_p of every prescribed component.  mask (NULL: every
+// body free -- body_in is not read and the third block is not written) has per entries per body (mx_bits).  A body with some
+// components prescribed needs both its sums and its velocities: the host picks per component.  A body with all six prescribed
+// takes no random displacement: it reads no blob and its sums are 0
+__global__ __launch_bounds__(BT) void k_mx_bd_sums(const double *__restrict__ lever, const uint8_t *__restrict__ mask, int per,
                                                    const double *__restrict__ body_in, const double *__restrict__ Wrfd,
                                                    const double *__restrict__ MW1, int N_blb, long nb6, double *__restrict__ out)
 {
   __shared__ double s[6][BT];
   const int b = blockIdx.x, t = threadIdx.x;
   const size_t o = 6 * (size_t)b;
-  if (mask && mask[b]) {
-    if (t < 6) { out[o + t] = 0.0; out[nb6 + o + t] = body_in[o + t]; }
-    return;
-  }
-  double f[6] = {0, 0, 0, 0, 0, 0}, g[6] = {0, 0, 0, 0, 0, 0};
-  for (int k = t; k < N_blb; k += BT) {
-    const size_t idx = 3 * ((size_t)b * N_blb + k);
-    const double *l = lever + idx;
-    rbl_KT_acc(l, Wrfd[idx], Wrfd[idx + 1], Wrfd[idx + 2], f);
-    rbl_KT_acc(l, MW1[idx], MW1[idx + 1], MW1[idx + 2], g);
-  }
-  block_reduce<6>(f, s, t);
-  block_reduce<6>(g, s, t);
-  if (t < 6) { out[o + t] = f[t]; out[nb6 + o + t] = g[t]; }
-}
-
-// the same with a mask per velocity component (mask6[6 N_bod]): a body with some components prescribed and others free needs both
-// its sums and the velocities of its prescribed components, so body_in travels in a third block, out[2 nb6 .. 3 nb6), and the
-// host picks per component.  The sums are k_mx_bd_sums', term for term; a body with all six prescribed reads no blob and gets 0
-__global__ __launch_bounds__(BT) void k_mx_bd_sums6(const double *__restrict__ lever, const uint8_t *__restrict__ mask6,
-                                                    const double *__restrict__ body_in, const double *__restrict__ Wrfd,
-                                                    const double *__restrict__ MW1, int N_blb, long nb6, double *__restrict__ out)
-{
-  __shared__ double s[6][BT];
-  const int b = blockIdx.x, t = threadIdx.x;
-  const size_t o = 6 * (size_t)b;
-  if (t < 6) out[2 * nb6 + o + t] = body_in[o + t];
-  bool all = true;
-  for (int c = 0; c < 6; ++c) all = all && mask6[o + c] != 0;   // (the same six bytes in every lane: the branch is uniform)
-  if (all) {
-    if (t < 6) { out[o + t] = 0.0; out[nb6 + o + t] = 0.0; }
-    return;
+  if (mask) {
+    if (t < 6) out[2 * nb6 + o + t] = body_in[o + t];
+    if (mx_bits(mask, per, b) == 63u) {
+      if (t < 6) { out[o + t] = 0.0; out[nb6 + o + t] = 0.0; }
+      return;
+    }
   }
   double f[6] = {0, 0, 0, 0, 0, 0}, g[6] = {0, 0, 0, 0, 0, 0};
   for (int k = t; k < N_blb; k += BT) {
@@ -843,18 +819,11 @@ void rbl_launch_KT_x_Lam(hipStream_t st, const double *d_lever, const double *d_
   hipLaunchKernelGGL(k_KT_x_Lam, dim3(N_bod), dim3(BT), 0, st, d_lever, d_lam, N_blb, d_out);
 }
 
-void rbl_launch_mx_bd_sums(hipStream_t st, const double *d_lever, const uint8_t *d_mask, const double *d_body_in, const double *d_Wrfd,
-                           const double *d_MW1, int N_blb, int N_bod, double *d_out)
+void rbl_launch_mx_bd_sums(hipStream_t st, const double *d_lever, const uint8_t *d_mask, int per, const double *d_body_in,
+                           const double *d_Wrfd, const double *d_MW1, int N_blb, int N_bod, double *d_out)
 {
   if (N_bod <= 0) return;
-  hipLaunchKernelGGL(k_mx_bd_sums, dim3(N_bod), dim3(BT), 0, st, d_lever, d_mask, d_body_in, d_Wrfd, d_MW1, N_blb, 6L * N_bod, d_out);
-}
-
-void rbl_launch_mx_bd_sums6(hipStream_t st, const double *d_lever, const uint8_t *d_mask6, const double *d_body_in, const double *d_Wrfd,
-                            const double *d_MW1, int N_blb, int N_bod, double *d_out)
-{
-  if (N_bod <= 0) return;
-  hipLaunchKernelGGL(k_mx_bd_sums6, dim3(N_bod), dim3(BT), 0, st, d_lever, d_mask6, d_body_in, d_Wrfd, d_MW1, N_blb, 6L * N_bod, d_out);
+  hipLaunchKernelGGL(k_mx_bd_sums, dim3(N_bod), dim3(BT), 0, st, d_lever, d_mask, per, d_body_in, d_Wrfd, d_MW1, N_blb, 6L * N_bod, d_out);
 }
 
 void rbl_launch_pc_diag_build(hipStream_t st, const RblParams &P, bool wall, const double *d_lever,

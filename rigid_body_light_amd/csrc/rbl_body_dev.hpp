@@ -1,8 +1,9 @@
-// rbl_body_dev.hpp -- device helpers shared by the per-body kernels (rbl_body_dev.hip, rbl_mixed.hip): ONE copy of the K / K^T
-// formulas, of the quaternion's rotation, of the ordered workgroup sum and of the 6 x 6 substitution, so the kernels that restate a body's operators cannot
-// drift apart.
+// rbl_body_dev.hpp -- device helpers shared by the per-body kernels (rbl_body_dev.hip, rbl_mixed.hip, rbl_ensemble.hip): ONE copy
+// of the K / K^T formulas, of the prescribed-mask decoding, of the quaternion's rotation, of the ordered workgroup sum and of the
+// 6 x 6 substitution, so the kernels that restate a body's operators cannot drift apart.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdint>
 
 // rotation matrix (row-major) of a unit quaternion (w, x, y, z): lab = R body
 __device__ __forceinline__ void quat_rot(const double *q, double *R)
@@ -52,6 +53,28 @@ __device__ __forceinline__ void rbl_block_sum(double (&v)[NV], double (*s)[NT], 
 #pragma unroll
   for (int q = 0; q < NV; ++q) v[q] = s[q][0];
   __syncthreads();
+}
+
+// A body's prescribed-mask as a bit set (bit c: velocity component c prescribed), the ONE decoding every kernel uses.
+// per = mask entries per body: 6 (one per component), or 1 (whole bodies: no bit or all six).  This form is per lane: for the
+// kernels with one thread per body, whose lanes hold different bodies (never broadcast its result)
+__device__ __forceinline__ unsigned mx_lane_bits(const uint8_t *__restrict__ mask, int per, size_t b)
+{
+  unsigned pm = 0;
+  if (per == 6) {
+    const uint8_t *m = mask + 6 * b;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) pm |= (m[c] != 0 ? 1u : 0u) << c;
+  } else {
+    pm = mask[b] != 0 ? 63u : 0u;
+  }
+  return pm;
+}
+
+// the same for the kernels with one workgroup per body b: one scalar, so every branch on it is uniform
+__device__ __forceinline__ unsigned mx_bits(const uint8_t *__restrict__ mask, int per, int b)
+{
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)mx_lane_bits(mask, per, (size_t)b));
 }
 
 // u = (L L^T)^-1 g for a 6 x 6 lower Cholesky factor L, row-major (the per-body N = K^T invM K of the preconditioners, :601-608)

@@ -21,16 +21,16 @@
 // configuration buffers and commits (swaps) only when every replica succeeded: on any error no replica moves.
 // Replicas never interact: the pair sweeps are per replica, the force model's neighbour lists stop at the replica's bodies.
 //
-// With prescribed bodies (rbl_ensemble_solve_mixed / _step_mixed / _step_brownian_mixed; the semantics of include/rbl.h section 7
-// per replica, the restatement of rbl_mixed.hip's mx_solve / mx_step and of rbl_steps.hip's rhs_and_midpoint_core): a 0/1 mask per
-// body and replica travels with the call, and NULL for it is the unmasked step: ens_step_det and ens_step_bd serve both.
-// The deterministic calls also take a mask per velocity component (rbl_ensemble_solve_mixed_dof / _step_mixed_dof, runs with
-// prescribed_per = 6): the mask goes up as the caller gave it and the solver is told how many entries a body has.
-// The one-step Brownian call takes one too (rbl_ensemble_step_brownian_mixed_dof: every body's rotation entries all equal), with
-// k_ens_midpoint_dof where k_ens_midpoint_prescribed stands below; a Brownian RUN with such a mask stays refused.
-// The same launches with three differences: k_ens_midpoint is followed by k_ens_midpoint_prescribed (dq = 0 and the predictor
-// (dt/2) U_p on a prescribed body; one more launch, so that a free body goes through the very same code), the solve is the
-// masked k_gmres_small (it adds K_p U_p to the right-hand side with the lever arms of the configuration it solves at, zeroes
+// With prescribed bodies (rbl_ensemble_solve_mixed / _step_mixed / _step_brownian_mixed and their _dof forms; the semantics of
+// include/rbl.h section 7 per replica, the restatement of rbl_mixed.hip's mx_solve / mx_step and of rbl_steps.hip's
+// rhs_and_midpoint_core): a 0/1 mask travels with the call, one entry per body and replica or (the _dof forms, runs with
+// prescribed_per = 6) one per velocity component, and NULL for it is the unmasked step: ens_step_det and ens_step_bd serve all.
+// `per`, the entries per body, is decided once at the exported function; the mask goes up as the caller gave it and every kernel
+// that reads it is told per (mx_lane_bits / mx_bits, rbl_body_dev.hpp).  In the Brownian step a mask per component must have every
+// body's rotation entries all equal; a Brownian RUN with such a mask stays refused.
+// The same launches with three differences: k_ens_midpoint is followed by k_ens_midpoint_masked (dq = 0 and the predictor
+// displacement (dt/2) U_p on a prescribed component; one more launch, so that a free body goes through the very same code), the
+// solve is the masked k_gmres_small (it adds K_p U_p to the right-hand side with the lever arms of the configuration it solves at, zeroes
 // the prescribed bodies' balance rows and splits the solution into U and F per body), and
 // k_ens_evolve reads the U the solver wrote.  The right-hand-side kernels are the unmasked ones: body_in stands where F_body stood,
 // so the model's K^T f reaches the bottom rows of the free bodies and what they write on a prescribed body's rows is overwritten
@@ -52,6 +52,7 @@
 #include <vector>
 
 #include "rbl_api_internal.hpp"
+#include "rbl_body_dev.hpp"
 #include "rbl_small_dev.hpp"
 
 namespace {
@@ -156,32 +157,17 @@ __global__ __launch_bounds__(ET) void k_ens_midpoint(int nbod, int Nb, int nbl, 
   ens_update_body(X + 3 * (size_t)g, Q + 4 * (size_t)g, u, Xh + 3 * (size_t)g, Qh + 4 * (size_t)g);
 }
 
-// k_ens_midpoint with prescribed bodies (mask[nbod], body_in[6 nbod]) is k_ens_midpoint itself on every body, then this kernel
-// on the prescribed ones: such a body takes no random displacement -- dq = 0 -- and sits at q^n + (dt/2) U_p in the predictor
-// (k_mx_bd_sums, rbl_body_dev.hip, and the host loop of rhs_and_midpoint_core, rbl_steps.hip).  One kernel with the two cases as branches was tried: the
-// compiler joins the branches' common tail (the update), scale * u of a free body then no longer fuses into X + u as it does
-// in k_ens_midpoint, and a free body's configuration differs in the last bit from the unmasked step's.  Running the unmasked
-// kernel gives the same bits by construction, for one more small launch per step
-__global__ __launch_bounds__(ET) void k_ens_midpoint_prescribed(int nbod, const double *__restrict__ X, const double *__restrict__ Q,
-                                                                const unsigned char *__restrict__ mask,
-                                                                const double *__restrict__ body_in, double half_dt,
-                                                                double *__restrict__ dq, double *__restrict__ Xh,
-                                                                double *__restrict__ Qh)
-{
-  const int g = blockIdx.x * ET + threadIdx.x;
-  if (g >= nbod || !mask[g]) return;
-  double u[6];
-  for (int p = 0; p < 6; ++p) { dq[6 * (size_t)g + p] = 0.0; u[p] = half_dt * body_in[6 * (size_t)g + p]; }
-  ens_update_body(X + 3 * (size_t)g, Q + 4 * (size_t)g, u, Xh + 3 * (size_t)g, Qh + 4 * (size_t)g);
-}
-
-// The companion with a mask per velocity component (mask6[6 nbod], every body's rotation entries all equal: the entry point has
-// checked it), run after k_ens_midpoint on the bodies with any component prescribed.  A body with all six prescribed is
-// k_ens_midpoint_prescribed's case, statement for statement and in a function of its own, so that the compiler contracts it as it
-// does there and whole rows give the whole-body step's bits.  A partly prescribed body keeps k_ens_midpoint's dq on its free
-// components (D_f Kinv W_rfd: (K^T K)^-1 has no translation-rotation coupling) and gets 0 on the prescribed ones; its predictor
-// displacement is (dt/2) U_p on the prescribed components and scale Kinv M^1/2 W1, computed again here, on the free ones, taken
-// in ONE update_X_Q.  The free bodies are not touched, for the reason given above.
+// k_ens_midpoint with a mask (per entries per body, body_in[6 nbod]) is k_ens_midpoint itself on every body, then
+// k_ens_midpoint_masked on the bodies with any component prescribed: a prescribed component takes no random displacement -- dq = 0
+// -- and moves by (dt/2) U_p in the predictor (k_mx_bd_sums, rbl_body_dev.hip, and the host loop of rhs_and_midpoint_core,
+// rbl_steps.hip).  One kernel with the free and the prescribed case as branches was tried: the compiler joins the branches' common
+// tail (the update), scale * u of a free body then no longer fuses into X + u as it does in k_ens_midpoint, and a free body's
+// configuration differs in the last bit from the unmasked step's.  Running the unmasked kernel first and leaving the free bodies
+// alone here gives the same bits by construction, for one more small launch per step.
+//
+// A body with all six components prescribed (every prescribed body of a whole-body mask) sits at q^n + (dt/2) U_p.  Its
+// statements stand in a function of their own, out of line, so that the compiler contracts them the same way whatever surrounds
+// the call: whole rows of a component mask give the whole-body step's bits.
 __device__ __noinline__ void ens_midpoint_whole_body(const double *X, const double *Q, const double *body_in, double half_dt, double *dq,
                                                      double *Xh, double *Qh)
 {
@@ -190,16 +176,20 @@ __device__ __noinline__ void ens_midpoint_whole_body(const double *X, const doub
   ens_update_body(X, Q, u, Xh, Qh);
 }
 
-__global__ __launch_bounds__(ET) void k_ens_midpoint_dof(int nbod, int Nb, int nbl, const double *__restrict__ X,
-                                                         const double *__restrict__ Q, const double *__restrict__ cfg,
-                                                         const unsigned char *__restrict__ mask6, const double *__restrict__ body_in,
-                                                         const double *__restrict__ MW, double scale, double half_dt,
-                                                         double *__restrict__ dq, double *__restrict__ Xh, double *__restrict__ Qh)
+// A partly prescribed body (per = 6 only; its rotation entries all equal: the entry point has checked it) keeps k_ens_midpoint's dq
+// on its free components (D_f Kinv W_rfd: (K^T K)^-1 has no translation-rotation coupling) and gets 0 on the prescribed ones; its
+// predictor displacement is (dt/2) U_p on the prescribed components and scale Kinv M^1/2 W1, computed again here, on the free
+// ones, taken in ONE update_X_Q.  One thread per body: the bit set differs lane by lane (mx_lane_bits, nothing broadcast)
+__global__ __launch_bounds__(ET) void k_ens_midpoint_masked(int nbod, int Nb, int nbl, const double *__restrict__ X,
+                                                            const double *__restrict__ Q, const double *__restrict__ cfg,
+                                                            const unsigned char *__restrict__ mask, int per,
+                                                            const double *__restrict__ body_in, const double *__restrict__ MW,
+                                                            double scale, double half_dt, double *__restrict__ dq,
+                                                            double *__restrict__ Xh, double *__restrict__ Qh)
 {
   const int g = blockIdx.x * ET + threadIdx.x;
   if (g >= nbod) return;
-  unsigned pm = 0;
-  for (int p = 0; p < 6; ++p) pm |= (mask6[6 * (size_t)g + p] != 0 ? 1u : 0u) << p;
+  const unsigned pm = mx_lane_bits(mask, per, (size_t)g);
   if (!pm) return;
   if (pm == 63u) {
     ens_midpoint_whole_body(X + 3 * (size_t)g, Q + 4 * (size_t)g, body_in + 6 * (size_t)g, half_dt, dq + 6 * (size_t)g, Xh + 3 * (size_t)g,
@@ -740,13 +730,10 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
   const int nbod = R * Nb;
   hipLaunchKernelGGL(k_ens_midpoint, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, nbl, X, Q, ens_cfg(c),
                      (const double *)w.W, (const double *)w.MW, 0.5 * S.dt * c1, w.dq, w.Xh, w.Qh);
-  if (mixed && in.per == 6)                              // the prescribed components: dq = 0, (dt/2) U_p in the predictor displacement
-    hipLaunchKernelGGL(k_ens_midpoint_dof, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, nbl, X, Q, ens_cfg(c),
-                       (const unsigned char *)w.mask, (const double *)w.F, (const double *)w.MW, 0.5 * S.dt * c1, 0.5 * S.dt, w.dq, w.Xh,
-                       w.Qh);
-  else if (mixed)                                        // the prescribed bodies: dq = 0, q^n + (dt/2) U_p
-    hipLaunchKernelGGL(k_ens_midpoint_prescribed, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, X, Q,
-                       (const unsigned char *)w.mask, (const double *)w.F, 0.5 * S.dt, w.dq, w.Xh, w.Qh);
+  if (mixed)                                             // the prescribed components: dq = 0, (dt/2) U_p in the predictor displacement
+    hipLaunchKernelGGL(k_ens_midpoint_masked, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, nbl, X, Q, ens_cfg(c),
+                       (const unsigned char *)w.mask, in.per, (const double *)w.F, (const double *)w.MW, 0.5 * S.dt * c1, 0.5 * S.dt, w.dq,
+                       w.Xh, w.Qh);
   const size_t lds = rfd_lds_bytes(Nb, nbl);
   const void *fn = S.wall ? (const void *)k_ens_rfd_rhs<true> : (const void *)k_ens_rfd_rhs<false>;
   if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
@@ -811,9 +798,10 @@ EnsRunBuf ens_run_carve(void *base, int R, int Nb, int nbl, bool slip, bool mixe
   return b;
 }
 
-// n_steps steps of every replica (checks and ens_ready done by the caller): the inputs go up once, every step is the one-step
-// calls' enqueue sequence followed by the verdict and the commit, the buffers flip on the host, ONE read-back ends it
-int ens_run(rbl_ctx *c, const rbl_run_opts &o, bool brownian, rbl_run_out *out)
+// n_steps steps of every replica (checks and ens_ready done by the caller; per: the mask's entries per body): the inputs go up
+// once, every step is the one-step calls' enqueue sequence followed by the verdict and the commit, the buffers flip on the host,
+// ONE read-back ends it
+int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_out *out)
 {
   const RblBodyState &S = c->S;
   const bool mixed = o.prescribed != nullptr, reject = o.on_error == RBL_RUN_REJECT;
@@ -828,13 +816,13 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, bool brownian, rbl_run_out *out)
   if ((rc = rbl_dev_reserve(c, c->d_ens_run, bytes))) return rc;
   const EnsRunBuf b = ens_run_carve(c->d_ens_run.p, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
   // the uploads, once
-  if (mixed && (rc = ens_upload_mask(c, w, o.prescribed, o.prescribed_per == 6 ? 6 : 1))) return rc;
+  if (mixed && (rc = ens_upload_mask(c, w, o.prescribed, per))) return rc;
   if ((rc = copy_h2d(c, w.F, mixed ? o.body_in : o.F_body, sizeof(double) * nb6 * Rz))) return rc;
   if (o.slip && (rc = copy_h2d(c, b.slip, o.slip, sizeof(double) * n3 * Rz))) return rc;
   RBL_HIP(c, hipMemsetAsync(b.st, 0, b.rb_bytes, c->stream));
   if (mixed) RBL_HIP(c, hipMemsetAsync(b.F_last, 0, sizeof(double) * nb6 * Rz, c->stream));
   EnsStepIn in;
-  in.prescribed = o.prescribed; in.per = o.prescribed_per == 6 ? 6 : 1;
+  in.prescribed = o.prescribed; in.per = per;
   in.slip = o.slip ? b.slip : nullptr; in.resident = true; in.chol_err = 1;
   in.accepted = b.accepted;
   EnsRunStatus hs = {0, 0, 0u, 0};
@@ -909,6 +897,49 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, bool brownian, rbl_run_out *out)
     c->last_error = at_step + ": " + c->last_error;
   }
   return rc;
+}
+
+// ---- the entry points with a mask: one worker per operation, per decided by the exported function (1: whole bodies, who's plain
+// name; 6: velocity components, the _dof name) -------------------------------------------------------------------------------------------
+
+int ens_mx_solve(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter,
+                 double rtol, double *lambda, double *U, double *F, int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  const std::string no_out = std::string(who) + ": U or F is NULL";
+  if (per == 6 && (!U || !F)) return rbl_fail(c, RBL_ERR_ARG, no_out);   // the _dof call refuses NULL outputs before it reads the mask,
+  int rc = ens_mx_check(c, who, prescribed, body_in, max_iter, rtol, per); if (rc) return rc;
+  if (!U || !F) return rbl_fail(c, RBL_ERR_ARG, no_out);                 // the whole-body call after: a caller sees the first refusal
+  if ((rc = ens_ready(c))) return rc;
+  return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, false, lambda, U, F, iters, resid, per);
+}
+
+int ens_mx_step(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter,
+                double rtol, double *F, int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  int rc = ens_mx_check(c, who, prescribed, body_in, max_iter, rtol, per); if (rc) return rc;
+  if ((rc = ens_flow_check(c))) return rc;
+  if ((rc = ens_ready(c))) return rc;
+  return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid, per);
+}
+
+// the Brownian step: the deterministic one's checks and launch sequence plus the predictor's masked kernel.  A mask per velocity
+// component must be in include/rbl.h section 7's admissible class, per replica
+int ens_mx_step_bd(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed, const double *body_in, const double *slip,
+                   const double *W, uint64_t seed, int split_rand, double delta, int max_iter, double rtol, double *F, int *iters,
+                   double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  int rc = ens_mx_check(c, who, prescribed, body_in, max_iter, rtol, per); if (rc) return rc;
+  if (per == 6 && (rc = rbl_bd_mask6_check(c, who, prescribed, c->ens_R, c->ens_Nb))) return rc;   // whole bodies: nothing to check
+  if ((rc = ens_flow_check(c))) return rc;
+  const RblBodyState &S = c->S;
+  const bool brownian = S.kBT > 1e-10;                 // no Brownian terms: the deterministic mixed step (as rbl_step_brownian_mixed)
+  if (brownian && (!(S.dt > 0.0) || !(delta > 0.0))) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": dt and delta must be positive");
+  if ((rc = ens_ready(c))) return rc;
+  if (!brownian) return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid, per);
+  return ens_step_bd(c, prescribed, body_in, slip, W, seed, split_rand, delta, max_iter, rtol, F, iters, resid, per);
 }
 
 }  // namespace
@@ -1003,81 +1034,46 @@ int rbl_ensemble_step_brownian(rbl_ctx *c, const double *F_body, const double *s
   return ens_step_bd(c, nullptr, F_body, slip, W, seed, split_rand, delta, max_iter, rtol, nullptr, iters, resid);
 }
 
+// the masked entry points: a mask entry per body, or (the _dof forms; include/rbl.h section 7's _dof semantics, per replica) one per
+// velocity component -- the same worker, the same enqueue sequence, the same kernels, told how many entries a body has
 int rbl_ensemble_solve_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
                              double *lambda, double *U, double *F, int *iters, double *resid)
 {
-  if (!c) return RBL_ERR_ARG;
-  int rc = ens_mx_check(c, "ensemble_solve_mixed", prescribed, body_in, max_iter, rtol); if (rc) return rc;
-  if (!U || !F) return rbl_fail(c, RBL_ERR_ARG, "ensemble_solve_mixed: U or F is NULL");
-  if ((rc = ens_ready(c))) return rc;
-  return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, false, lambda, U, F, iters, resid);
+  return ens_mx_solve(c, "ensemble_solve_mixed", 1, prescribed, body_in, slip, max_iter, rtol, lambda, U, F, iters, resid);
+}
+
+int rbl_ensemble_solve_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter,
+                                 double rtol, double *lambda, double *U, double *F, int *iters, double *resid)
+{
+  return ens_mx_solve(c, "ensemble_solve_mixed_dof", 6, prescribed6, body_in, slip, max_iter, rtol, lambda, U, F, iters, resid);
 }
 
 int rbl_ensemble_step_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
                             double *F, int *iters, double *resid)
 {
-  if (!c) return RBL_ERR_ARG;
-  int rc = ens_mx_check(c, "ensemble_step_mixed", prescribed, body_in, max_iter, rtol); if (rc) return rc;
-  if ((rc = ens_flow_check(c))) return rc;
-  if ((rc = ens_ready(c))) return rc;
-  return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
-}
-
-// the masks per velocity component (include/rbl.h section 7's _dof semantics, per replica): the whole-body calls with six mask
-// entries per body -- the same checks, the same enqueue sequence, the same kernel
-int rbl_ensemble_solve_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter,
-                                 double rtol, double *lambda, double *U, double *F, int *iters, double *resid)
-{
-  if (!c) return RBL_ERR_ARG;
-  if (!U || !F) return rbl_fail(c, RBL_ERR_ARG, "ensemble_solve_mixed_dof: U or F is NULL");
-  int rc = ens_mx_check(c, "ensemble_solve_mixed_dof", prescribed6, body_in, max_iter, rtol, 6); if (rc) return rc;
-  if ((rc = ens_ready(c))) return rc;
-  return ens_step_det(c, prescribed6, body_in, slip, max_iter, rtol, false, lambda, U, F, iters, resid, 6);
+  return ens_mx_step(c, "ensemble_step_mixed", 1, prescribed, body_in, slip, max_iter, rtol, F, iters, resid);
 }
 
 int rbl_ensemble_step_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *body_in, const double *slip, int max_iter,
                                 double rtol, double *F, int *iters, double *resid)
 {
-  if (!c) return RBL_ERR_ARG;
-  int rc = ens_mx_check(c, "ensemble_step_mixed_dof", prescribed6, body_in, max_iter, rtol, 6); if (rc) return rc;
-  if ((rc = ens_flow_check(c))) return rc;
-  if ((rc = ens_ready(c))) return rc;
-  return ens_step_det(c, prescribed6, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid, 6);
+  return ens_mx_step(c, "ensemble_step_mixed_dof", 6, prescribed6, body_in, slip, max_iter, rtol, F, iters, resid);
 }
 
 int rbl_ensemble_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, const double *body_in, const double *slip, const double *W,
                                      uint64_t seed, int split_rand, double delta, int max_iter, double rtol, double *F, int *iters,
                                      double *resid)
 {
-  if (!c) return RBL_ERR_ARG;
-  int rc = ens_mx_check(c, "ensemble_step_brownian_mixed", prescribed, body_in, max_iter, rtol); if (rc) return rc;
-  if ((rc = ens_flow_check(c))) return rc;
-  const RblBodyState &S = c->S;
-  const bool brownian = S.kBT > 1e-10;                 // no Brownian terms: the deterministic mixed step (as rbl_step_brownian_mixed)
-  if (brownian && (!(S.dt > 0.0) || !(delta > 0.0)))
-    return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_brownian_mixed: dt and delta must be positive");
-  if ((rc = ens_ready(c))) return rc;
-  if (!brownian) return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid);
-  return ens_step_bd(c, prescribed, body_in, slip, W, seed, split_rand, delta, max_iter, rtol, F, iters, resid);
+  return ens_mx_step_bd(c, "ensemble_step_brownian_mixed", 1, prescribed, body_in, slip, W, seed, split_rand, delta, max_iter, rtol, F,
+                        iters, resid);
 }
 
-// the Brownian step with a mask per velocity component (include/rbl.h section 7's admissible class, per replica): the whole-body
-// call's checks and launch sequence, k_ens_midpoint_dof where k_ens_midpoint_prescribed stood and the solver told per = 6
 int rbl_ensemble_step_brownian_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *body_in, const double *slip, const double *W,
                                          uint64_t seed, int split_rand, double delta, int max_iter, double rtol, double *F, int *iters,
                                          double *resid)
 {
-  if (!c) return RBL_ERR_ARG;
-  int rc = ens_mx_check(c, "ensemble_step_brownian_mixed_dof", prescribed6, body_in, max_iter, rtol, 6); if (rc) return rc;
-  if ((rc = rbl_bd_mask6_check(c, "ensemble_step_brownian_mixed_dof", prescribed6, c->ens_R, c->ens_Nb))) return rc;
-  if ((rc = ens_flow_check(c))) return rc;
-  const RblBodyState &S = c->S;
-  const bool brownian = S.kBT > 1e-10;                 // no Brownian terms: the deterministic step with this mask
-  if (brownian && (!(S.dt > 0.0) || !(delta > 0.0)))
-    return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_brownian_mixed_dof: dt and delta must be positive");
-  if ((rc = ens_ready(c))) return rc;
-  if (!brownian) return ens_step_det(c, prescribed6, body_in, slip, max_iter, rtol, true, nullptr, nullptr, F, iters, resid, 6);
-  return ens_step_bd(c, prescribed6, body_in, slip, W, seed, split_rand, delta, max_iter, rtol, F, iters, resid, 6);
+  return ens_mx_step_bd(c, "ensemble_step_brownian_mixed_dof", 6, prescribed6, body_in, slip, W, seed, split_rand, delta, max_iter, rtol, F,
+                        iters, resid);
 }
 
 int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)
@@ -1122,7 +1118,7 @@ int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)
   if (brownian && (!(c->S.dt > 0.0) || !(o->delta > 0.0))) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: dt and delta must be positive");
   if ((rc = ens_flow_check(c))) return rc;
   if ((rc = ens_ready(c))) return rc;
-  return ens_run(c, *o, brownian, out);
+  return ens_run(c, *o, per, brownian, out);
 }
 
 int rbl_ensemble_interaction_forces(rbl_ctx *c, double *FT_body, double *energy)

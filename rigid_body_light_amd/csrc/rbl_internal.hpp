@@ -420,14 +420,11 @@ void rbl_launch_K_x_U(hipStream_t st, const double *d_lever, const double *d_U, 
                       double *d_out, const double *d_sub, double alpha);
 void rbl_launch_KT_x_Lam(hipStream_t st, const double *d_lever, const double *d_lam, int N_blb, int N_bod,
                          double *d_out);
-// d_out[0 .. 6 N_bod) = K^T d_Wrfd, d_out[6 N_bod .. 12 N_bod) = K^T d_MW1 per body in one launch; a body marked in d_mask (NULL:
-// none) gets 0 and its six entries of d_body_in instead (the stochastic midpoint step, rbl_steps.hip)
-void rbl_launch_mx_bd_sums(hipStream_t st, const double *d_lever, const uint8_t *d_mask, const double *d_body_in, const double *d_Wrfd,
-                           const double *d_MW1, int N_blb, int N_bod, double *d_out);
-// the same with a mask per velocity component (d_mask6[6 N_bod], d_body_in: neither NULL): d_out has a third block,
-// d_out[12 N_bod .. 18 N_bod) = d_body_in; a body with all six components prescribed gets 0 in the first two
-void rbl_launch_mx_bd_sums6(hipStream_t st, const double *d_lever, const uint8_t *d_mask6, const double *d_body_in, const double *d_Wrfd,
-                            const double *d_MW1, int N_blb, int N_bod, double *d_out);
+// per body in one launch: d_out[0 .. 6 N_bod) = K^T d_Wrfd, d_out[6 N_bod .. 12 N_bod) = K^T d_MW1 (both 0 on a body with all six
+// components prescribed) and, with a mask, d_out[12 N_bod .. 18 N_bod) = d_body_in.  d_mask: per entries per body (1 or 6), or NULL:
+// every body free, d_body_in not read, 12 N_bod written (the stochastic midpoint step, rbl_steps.hip)
+void rbl_launch_mx_bd_sums(hipStream_t st, const double *d_lever, const uint8_t *d_mask, int per, const double *d_body_in,
+                           const double *d_Wrfd, const double *d_MW1, int N_blb, int N_bod, double *d_out);
 void rbl_launch_pc_diag_build(hipStream_t st, const RblParams &P, bool wall, const double *d_lever,
                               const double *d_pos, int N_blb, int N_bod, double *d_invM2, double *d_NL,
                               unsigned *d_err);

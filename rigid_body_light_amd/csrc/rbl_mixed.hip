@@ -10,7 +10,7 @@
 // mobility product is the library's own (apply_M_enqueue, untouched); what is new around it -- the masked K / K^T tail, the masked
 // preconditioner tails, the right-hand side and the split of the solution -- are the O(N) kernels below: one workgroup per body, the
 // mask read once per workgroup (the branch on it is uniform), deterministic LDS tree sums, no atomics; the K / K^T formulas, the
-// workgroup sum and the 6 x 6 substitution are rbl_body_dev.hpp's, shared with rbl_body_dev.hip.  The Arnoldi recurrence, the
+// mask decoding (mx_bits), the workgroup sum and the 6 x 6 substitution are rbl_body_dev.hpp's, shared with rbl_body_dev.hip.  The Arnoldi recurrence, the
 // Hessenberg solve and the convergence test are gmres_core's (gmres_core_with_ops).
 //
 // Many right-hand sides under ONE mask (the _multi entry points) advance in lock step through gmres_multi_with_ops: the same kernels
@@ -31,21 +31,6 @@
 namespace {
 
 constexpr int MT = 256;
-
-// The mask of the workgroup's body as one scalar bit set (bit c: component c prescribed), so every branch on it is uniform.
-// per = mask entries per body: 6 (one per velocity component), or 1 (whole bodies: no bit or all six).
-__device__ __forceinline__ unsigned mx_bits(const uint8_t *__restrict__ mask, int per, int b)
-{
-  unsigned pm = 0;
-  if (per == 6) {
-    const uint8_t *m = mask + 6 * (size_t)b;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) pm |= (m[c] != 0 ? 1u : 0u) << c;
-  } else {
-    pm = mask[b] != 0 ? 63u : 0u;
-  }
-  return (unsigned)__builtin_amdgcn_readfirstlane((int)pm);
-}
 
 // the workgroup's column of a lock-step batch; false: that column has converged, nothing to do
 __device__ __forceinline__ bool mx_live(unsigned live, int &col)
@@ -778,8 +763,8 @@ int mx_bd_rhs_host(rbl_ctx *c, const char *who, const uint8_t *prescribed, int p
   return finish_and_check(c);
 }
 
-// the Brownian step with prescribed bodies (per = 1) or velocity components (per = 6), the checks done and kBT > 1e-10: with six
-// mask entries per body the predictor picks per component (k_mx_bd_sums6) and the solve at q^{n+1/2} is mx_step's _dof solve
+// the Brownian step with prescribed bodies (per = 1) or velocity components (per = 6), the checks done and kBT > 1e-10: the
+// predictor picks per component (k_mx_bd_sums and rhs_and_midpoint_core's loop) and the solve at q^{n+1/2} is mx_step's solve
 int mx_bd_step(rbl_ctx *c, const uint8_t *prescribed, int per, int np, const double *body_in, const double *slip, const double *W,
                uint64_t seed, int method, int split_rand, double delta, int max_iter, double rtol, double *F, int *iters, double *resid)
 {
@@ -807,6 +792,26 @@ int mx_bd_step(rbl_ctx *c, const uint8_t *prescribed, int per, int np, const dou
         if (!r && F) r = copy_d2h(c, F, B.F, sizeof(double) * nb6);
         return r ? r : finish_and_check(c);
       });
+}
+
+// rbl_step_brownian_mixed (per = 1) and its _dof form (per = 6): checks, then the deterministic step, the all-free step or mx_bd_step
+int mx_bd_step_entry(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed, const double *body_in, const double *slip,
+                     const double *W, uint64_t seed, int method, int split_rand, double delta, int max_iter, double rtol, double *F,
+                     int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  int np = 0;
+  const int rc = mx_bd_check(c, who, prescribed, body_in, max_iter, rtol, delta, &np, per); if (rc) return rc;
+  if (!(c->S.kBT > 1e-10))                               // no Brownian terms: the deterministic step (as rbl_step_brownian, :967-970)
+    return mx_step(c, who, prescribed, body_in, slip, max_iter, rtol, F, iters, resid, per);
+  if (per == 6 && np == 0) {                             // the _dof step with nothing prescribed: rbl_step_brownian itself, hence its
+    // bits (the masked solve goes through another GMRES driver and would differ from it in the last digits); F: the loads it solved
+    // with, echoed.  The whole-body step with nobody prescribed goes through the masked solve, as it always has: its bits stay too
+    int r = rbl_step_brownian(c, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, iters, resid);
+    if (!r && F && !(r = copy_d2h(c, F, step_force_dev(c), sizeof(double) * 6 * (size_t)c->S.N_bod))) r = finish_and_check(c);
+    return r;
+  }
+  return mx_bd_step(c, prescribed, per, np, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, F, iters, resid);
 }
 
 }  // namespace
@@ -917,12 +922,8 @@ int rbl_step_brownian_mixed(rbl_ctx *c, const uint8_t *prescribed, const double 
                             uint64_t seed, int method, int split_rand, double delta, int max_iter, double rtol, double *F,
                             int *iters, double *resid)
 {
-  if (!c) return RBL_ERR_ARG;
-  int np = 0;
-  const int rc = mx_bd_check(c, "step_brownian_mixed", prescribed, body_in, max_iter, rtol, delta, &np); if (rc) return rc;
-  if (!(c->S.kBT > 1e-10))                               // no Brownian terms: the deterministic step (as rbl_step_brownian, :967-970)
-    return mx_step(c, "step_brownian_mixed", prescribed, body_in, slip, max_iter, rtol, F, iters, resid);
-  return mx_bd_step(c, prescribed, 1, np, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, F, iters, resid);
+  return mx_bd_step_entry(c, "step_brownian_mixed", 1, prescribed, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, F, iters,
+                          resid);
 }
 
 // ---- the Brownian midpoint step with a mask per velocity component: prescribed6[6 N_bod], every body's rotation entries all equal ----
@@ -945,16 +946,6 @@ int rbl_step_brownian_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const do
                                 uint64_t seed, int method, int split_rand, double delta, int max_iter, double rtol, double *F,
                                 int *iters, double *resid)
 {
-  if (!c) return RBL_ERR_ARG;
-  int np = 0;
-  const int rc = mx_bd_check(c, "step_brownian_mixed_dof", prescribed6, body_in, max_iter, rtol, delta, &np, 6); if (rc) return rc;
-  if (!(c->S.kBT > 1e-10))                               // no Brownian terms: the deterministic step with this mask
-    return mx_step(c, "step_brownian_mixed_dof", prescribed6, body_in, slip, max_iter, rtol, F, iters, resid, 6);
-  if (np == 0) {                                         // nothing prescribed: rbl_step_brownian itself, hence its bits (the masked
-    // solve goes through another GMRES driver and would differ from it in the last digits); F: the loads it solved with, echoed
-    int r = rbl_step_brownian(c, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, iters, resid);
-    if (!r && F && !(r = copy_d2h(c, F, step_force_dev(c), sizeof(double) * 6 * (size_t)c->S.N_bod))) r = finish_and_check(c);
-    return r;
-  }
-  return mx_bd_step(c, prescribed6, 6, np, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, F, iters, resid);
+  return mx_bd_step_entry(c, "step_brownian_mixed_dof", 6, prescribed6, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, F,
+                          iters, resid);
 }

@@ -257,16 +257,17 @@ int rbl_update_X_Q(rbl_ctx *c, const double *U, double *X_out, double *Q_out)
   return RBL_OK;
 }
 
-// Right-hand side and predictor of the stochastic midpoint step at q^n (c_rigid_obj.cpp:917-976), with any subset of the bodies
-// prescribed (include/rbl.h section 7); the all-free scheme is the one with no mask.  Checks done by the caller, dt and delta
-// positive when kBT > 1e-10 among them.  h_mask / d_mask: the 0/1 mask per body on the host and on the device, d_body_in: the
-// prescribed bodies' velocities in their six slots -- all three NULL: every body is free.  per: mask entries per body, 1 (whole
-// bodies) or 6 (one per lab-frame velocity component, every body's rotation entries all equal: the caller has checked it) -- D_f
-// and D_p below are then diagonal over the 6 N_bod slots and the sums come from k_mx_bd_sums6.  d_slip: 3 N_blobs or NULL for zero;
-// d_W: [W1 | W2 | W_rfd] (3 n3) or NULL (drawn from `seed`).
+// Right-hand side and predictor of the stochastic midpoint step at q^n (c_rigid_obj.cpp:917-976), with any subset of the velocity
+// components prescribed (include/rbl.h section 7); the all-free scheme is the one with no mask.  Checks done by the caller, dt and
+// delta positive when kBT > 1e-10 among them.  h_mask / d_mask: the 0/1 mask on the host and on the device, d_body_in: the
+// prescribed components' velocities in their slots -- all three NULL: every body is free.  per: mask entries per body, 1 (whole
+// bodies: none or all six of a body's components) or 6 (one per lab-frame velocity component, every body's rotation entries all
+// equal: the caller has checked it).  ONE path for both: k_mx_bd_sums decodes the mask on the device, the loop below on the host;
+// D_f and D_p are diagonal 0/1 over the 6 N_bod slots.  d_slip: 3 N_blobs or NULL for zero; d_W: [W1 | W2 | W_rfd] (3 n3) or NULL
+// (drawn from `seed`).
 //   d_s (3 N_blobs, may be d_slip) = slip - kBT M_RFD - BI,  M_RFD along dq = D_f Kinv W_rfd,
 //   q^{n+1/2} = q^n displaced by D_f (dt/2 c1) Kinv M^{1/2}W1 + D_p (dt/2) U_p.
-// M is all blobs': the mask does not enter the square roots.  One read-back of 12 numbers per body (18 with per = 6).
+// M is all blobs': the mask does not enter the square roots.  One read-back of 12 numbers per body (18 with a mask: U_p echoed).
 int rhs_and_midpoint_core(rbl_ctx *c, const uint8_t *h_mask, const uint8_t *d_mask, const double *d_body_in, const double *d_slip,
                           const double *d_W, uint64_t seed, int method, int split_rand, double delta, double *d_s, double *X_half,
                           double *Q_half, int per)
@@ -286,7 +287,7 @@ int rhs_and_midpoint_core(rbl_ctx *c, const uint8_t *h_mask, const uint8_t *d_ma
     return finish_and_check(c);
   }
   // workspace: [W1 | W2 | W_rfd] (when drawn here), M^{1/2}W1, M^{1/2}W2, M_RFD, positions, 2 scratch, the sums per body
-  if ((rc = rbl_dev_reserve(c, c->d_bd, 9 * vb + (per == 6 ? 3 : 2) * sizeof(double) * (size_t)nb6))) return rc;
+  if ((rc = rbl_dev_reserve(c, c->d_bd, 9 * vb + (d_mask ? 3 : 2) * sizeof(double) * (size_t)nb6))) return rc;
   double *base = (double *)c->d_bd.p;
   double *dWown = base, *dMW = base + 3 * n3 /* 2 vectors */, *dRFD = base + 5 * n3, *dr = base + 6 * n3,
          *dwork = base + 7 * n3, *dt12 = base + 9 * n3;
@@ -299,27 +300,21 @@ int rhs_and_midpoint_core(rbl_ctx *c, const uint8_t *h_mask, const uint8_t *d_ma
   // Kinv of the RFD noise (M_RFD's direction, :776) and of M^{1/2}W1 (the predictor, :955): the sums over the blobs on the device
   // with the lever arms of q^n, the 6 x 6 blocks on the host after one small read-back (the reference brings the 3 N-vectors, :408)
   if ((rc = sync_bodies(c))) return rc;
-  if (per == 6) rbl_launch_mx_bd_sums6(c->stream, (const double *)c->d_lever.p, d_mask, d_body_in, d_W + 2 * n3, dMW, S.N_blb, S.N_bod, dt12);
-  else rbl_launch_mx_bd_sums(c->stream, (const double *)c->d_lever.p, d_mask, d_body_in, d_W + 2 * n3, dMW, S.N_blb, S.N_bod, dt12);
-  std::vector<double> t((size_t)((per == 6 ? 3 : 2) * nb6)), dq((size_t)nb6), pre((size_t)nb6), Xo, Qo;
+  rbl_launch_mx_bd_sums(c->stream, (const double *)c->d_lever.p, d_mask, per, d_body_in, d_W + 2 * n3, dMW, S.N_blb, S.N_bod, dt12);
+  std::vector<double> t((size_t)((d_mask ? 3 : 2) * nb6)), dq((size_t)nb6), pre((size_t)nb6), Xo, Qo;
   if ((rc = read_back(c, t.data(), dt12, sizeof(double) * t.size()))) return rc;
   const double c1 = split_rand ? 2.0 * std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);   // :945-952
   const double c2 = split_rand ? std::sqrt(S.kBT / S.dt) : std::sqrt(2.0 * S.kBT / S.dt);
   const double half_dt = 0.5 * S.dt, scale = half_dt * c1;
   for (int b = 0; b < S.N_bod; ++b) {
     const double *Kb = &S.KTKinv[(size_t)36 * b], *tr = t.data() + 6 * (size_t)b, *tp = tr + nb6;
-    const bool prescribed = per == 1 && h_mask && h_mask[b];
+    const uint8_t *hm = h_mask ? h_mask + (size_t)per * b : nullptr;                    // the body's per mask entries
     for (int p = 0; p < 6; ++p) {
       double sr = 0.0, sp = 0.0;
       for (int q = 0; q < 6; ++q) { sr += Kb[6 * p + q] * tr[q]; sp += Kb[6 * p + q] * tp[q]; }
-      if (per == 6) {                                                                   // component by component; U_p: the third block
-        const bool pres = h_mask[6 * (size_t)b + p] != 0;
-        dq[6 * (size_t)b + p] = pres ? 0.0 : sr;
-        pre[6 * (size_t)b + p] = pres ? half_dt * tp[nb6 + p] : scale * sp;
-        continue;
-      }
-      dq[6 * (size_t)b + p] = prescribed ? 0.0 : sr;                                    // D_f Kinv W_rfd
-      pre[6 * (size_t)b + p] = prescribed ? half_dt * tp[p] : scale * sp;               // (:955-959) and D_p (dt/2) U_p
+      const bool pres = hm && hm[p % per] != 0;                                         // component p: its own entry of six, or the body's one
+      dq[6 * (size_t)b + p] = pres ? 0.0 : sr;                                          // D_f Kinv W_rfd
+      pre[6 * (size_t)b + p] = pres ? half_dt * tp[nb6 + p] : scale * sp;               // (:955-959) and D_p (dt/2) U_p: the third block
     }
   }
   if ((rc = m_rfd_dir(c, d_W + 2 * n3, dq.data(), delta, dRFD, dr, dwork))) return rc;  // M_RFD (:940)

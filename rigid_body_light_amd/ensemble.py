@@ -82,11 +82,7 @@ class Ensemble:
         standard normals [W1 | W2 | W_rfd] per replica, or None to draw them from `seed` (replica r from its own counters);
         slip: (n3,) or (R, n3)"""
         F = self._forces(F)
-        if W is not None:
-            W = np.asarray(W, dtype=np.float64)
-            n = 9 * self.N_bodies * self.blobs_per_body
-            if W.shape != (self.R, n):
-                _fail("W must have shape (%d, %d); got %s" % (self.R, n, W.shape))
+        W = self._noise(W)
         return self.ctx.ensemble_step_brownian(F, W=W, seed=seed, split_rand=split_rand, delta=delta, max_iter=max_iter, rtol=rtol,
                                                slip=self._slip(slip))
 
@@ -132,6 +128,15 @@ class Ensemble:
             _fail("slip must have shape (%d,) or (%d, %d); got %s" % (n3, self.R, n3, s.shape))
         return s
 
+    def _noise(self, W):
+        if W is None:
+            return None
+        W = np.asarray(W, dtype=np.float64)
+        n = 9 * self.N_bodies * self.blobs_per_body
+        if W.shape != (self.R, n):
+            _fail("W must have shape (%d, %d); got %s" % (self.R, n, W.shape))
+        return W
+
     def solve_mixed(self, prescribed, body_in, slip=None, max_iter=100, rtol=1e-8):
         """RigidBody.solve_mixed at every replica's configuration; nothing moves.  The bodies in `prescribed` move with the velocity
         in their six slots of body_in, the others carry their load there.  -> (lambda (R, n3), U (R, 6 N_bod), F (R, 6 N_bod),
@@ -150,11 +155,7 @@ class Ensemble:
         estimates (R,)).  F of a prescribed body is its instantaneous load, thermal part included: average it over replicas and
         steps.  W as step_brownian"""
         m, b, s = self._prescribed_mask(prescribed), self._body_in(body_in), self._slip(slip)
-        if W is not None:
-            W = np.asarray(W, dtype=np.float64)
-            n = 9 * self.N_bodies * self.blobs_per_body
-            if W.shape != (self.R, n):
-                _fail("W must have shape (%d, %d); got %s" % (self.R, n, W.shape))
+        W = self._noise(W)
         return self.ctx.ensemble_step_brownian_mixed(m, b, W=W, seed=seed, split_rand=split_rand, delta=delta, max_iter=max_iter,
                                                      rtol=rtol, slip=s)
 
@@ -198,11 +199,7 @@ class Ensemble:
         instantaneous load along it, thermal part included.  W as step_brownian"""
         m, b, s = self._prescribed_dof_mask(prescribed), self._body_in(body_in), self._slip(slip)
         check_brownian_mask6("ensemble_step_brownian_mixed_dof", m, self.N_bodies, self.R)
-        if W is not None:
-            W = np.asarray(W, dtype=np.float64)
-            n = 9 * self.N_bodies * self.blobs_per_body
-            if W.shape != (self.R, n):
-                _fail("W must have shape (%d, %d); got %s" % (self.R, n, W.shape))
+        W = self._noise(W)
         return self.ctx.ensemble_step_brownian_mixed_dof(m, b, W=W, seed=seed, split_rand=split_rand, delta=delta, max_iter=max_iter,
                                                          rtol=rtol, slip=s)
 

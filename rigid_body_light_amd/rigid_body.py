@@ -404,8 +404,17 @@ class RigidBody:
         mask[idx] = 1
         return mask
 
-    def _mixed_args(self, prescribed, body_in, slip):
-        return (self._prescribed_mask(prescribed),) + self._body_in_and_slip(body_in, slip)
+    def _prescribed_mask6(self, prescribed):
+        p = np.asarray(prescribed)
+        if p.dtype != np.bool_ or p.shape != (self.N_bodies, 6):
+            raise ValueError(f"prescribed must be a boolean array of shape (N_bodies, 6) = ({self.N_bodies}, 6): one entry per velocity "
+                             f"component (translation x, y, z, rotation x, y, z). Got dtype {p.dtype}, shape {p.shape}")
+        return np.ascontiguousarray(p, dtype=np.uint8).reshape(-1)
+
+    def _mixed_args(self, prescribed, body_in, slip, per=1):
+        """per: mask entries per body, 1 (bodies) or 6 (velocity components, the _dof methods)"""
+        mask = self._prescribed_mask6(prescribed) if per == 6 else self._prescribed_mask(prescribed)
+        return (mask,) + self._body_in_and_slip(body_in, slip)
 
     def _body_in_and_slip(self, body_in, slip):
         bi = np.asarray(body_in, dtype=np.float64)
@@ -439,13 +448,6 @@ class RigidBody:
         mask, bi, sl = self._mixed_args(prescribed, body_in, slip)
         return self.cb.step_mixed(mask, bi, sl, int(max_iter), float(rtol))
 
-    def _mixed_dof_args(self, prescribed, body_in, slip):
-        p = np.asarray(prescribed)
-        if p.dtype != np.bool_ or p.shape != (self.N_bodies, 6):
-            raise ValueError(f"prescribed must be a boolean array of shape (N_bodies, 6) = ({self.N_bodies}, 6): one entry per velocity "
-                             f"component (translation x, y, z, rotation x, y, z). Got dtype {p.dtype}, shape {p.shape}")
-        return (np.ascontiguousarray(p, dtype=np.uint8).reshape(-1),) + self._body_in_and_slip(body_in, slip)
-
     def solve_mixed_dof(self, prescribed, body_in, slip=None, max_iter=100, rtol=1.0e-8):
         """Prescribed kinematics per velocity component: `prescribed` is a boolean array of shape (N_bodies, 6) over each body's
         lab-frame components (translation x, y, z, then rotation x, y, z, the order of body_in).  A prescribed component moves with
@@ -454,14 +456,14 @@ class RigidBody:
         solve_mixed's (1.00-1.05 of its time per iteration at cfg 2 and cfg 3: profiles/prescribed_dof.jsonl), and with whole rows set the results are solve_mixed's.  -> (lambda, U, F, iterations, residual estimate): U
         with the prescribed components echoed, F with the free components echoed and -K^T lambda on the prescribed ones (the force
         or torque along that component that it takes)."""
-        mask, bi, sl = self._mixed_dof_args(prescribed, body_in, slip)
+        mask, bi, sl = self._mixed_args(prescribed, body_in, slip, per=6)
         return self.cb.solve_mixed_dof(mask, bi, sl, int(max_iter), float(rtol))
 
     def step_mixed_dof(self, prescribed, body_in, slip=None, max_iter=50, rtol=1.0e-8):
         """One deterministic time step with a mask per velocity component: solve_mixed_dof at the current configuration, then
         evolve_rigid_bodies(U).  With the force model on its loads are added to the FREE components only; the F of a prescribed
         component is the total load along it that everything other than the fluid supplies.  -> (F, iterations, residual estimate)"""
-        mask, bi, sl = self._mixed_dof_args(prescribed, body_in, slip)
+        mask, bi, sl = self._mixed_args(prescribed, body_in, slip, per=6)
         return self.cb.step_mixed_dof(mask, bi, sl, int(max_iter), float(rtol))
 
     def _multi_body_in_and_slip(self, body_in, slip):
@@ -493,7 +495,7 @@ class RigidBody:
         """solve_mixed_dof for k right-hand sides under ONE mask per velocity component (a boolean array of shape (N_bodies, 6)), in
         lock step as solve_mixed_multi: body_in (k, 6 N_bodies), slip None or (k, 3 N_blobs).
         -> (lambda (k, 3 N_blobs), U (k, 6 N_bodies), F (k, 6 N_bodies), iterations (k,), residual estimates (k,))"""
-        mask = self._mixed_dof_args(prescribed, np.zeros(6 * self.N_bodies), None)[0]
+        mask = self._prescribed_mask6(prescribed)
         bi, sl = self._multi_body_in_and_slip(body_in, slip)
         return self.cb.solve_mixed_dof_multi(mask, bi, sl, int(max_iter), float(rtol))
 
@@ -528,7 +530,7 @@ class RigidBody:
                                            int(max_iter), float(rtol))
 
     def _brownian_dof_args(self, who, prescribed, body_in, slip):
-        mask, bi, sl = self._mixed_dof_args(prescribed, body_in, slip)
+        mask, bi, sl = self._mixed_args(prescribed, body_in, slip, per=6)
         check_brownian_mask6(who, mask, self.N_bodies)
         return mask, bi, sl
 

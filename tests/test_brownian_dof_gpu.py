@@ -106,22 +106,27 @@ def _np_step6(orc, cfg, X, Qn, a, eta, wall, dt, kBT, P, body_in, slip, W, split
 
 # ---- 1. right-hand side, predictor and whole step against the restatement ------------------------------------------------------------
 
-def _rhs_case6(orc, shell12, wall, split_rand, which):
+def _rhs_compare(orc, cfg, a, X, Q, W, slip, P, held, F, Up, wall, split_rand, tag, whole_body=False):
+    """RHS_and_Midpoint_mixed_dof (whole_body: RHS_and_Midpoint_mixed with the bodies whose rows of P are set) against the
+    restatement -> what the call returned"""
     from oracle import oracle as O
-    nb, dt = 4, 0.01
-    X, Q, W, slip, F, Up = _case(wall)
-    P, held = _mask6(which, nb)
+    dt = 0.01
     bi = _body_in6(P, held, F, Up)
-    rb = _solver(shell12, X, Q, wall, False, dt=dt)
+    rb = _solver(cfg, X, Q, wall, False, dt=dt, a=a)
     args0 = [v.copy() for v in (P, bi, slip, W)]
-    s, Xh, Qh = rb.RHS_and_Midpoint_mixed_dof(P, bi, slip=slip, W=W, method="cholesky", split_rand=split_rand)
+    if whole_body:
+        assert np.array_equal(P, np.repeat(P[:, :1], 6, axis=1))
+        got = rb.RHS_and_Midpoint_mixed(P[:, 0].copy(), bi, slip=slip, W=W, method="cholesky", split_rand=split_rand)
+    else:
+        got = rb.RHS_and_Midpoint_mixed_dof(P, bi, slip=slip, W=W, method="cholesky", split_rand=split_rand)
+    s, Xh, Qh = got
     for v, v0 in zip((P, bi, slip, W), args0):
         assert np.array_equal(v, v0)                                                   # arguments untouched
     Qn = O.normalize_quats(Q)
-    s_r, Xr, Qr = _np_rhs_mid6(orc, O.remove_mean(shell12), X, Qn, 1.0, 1.0, wall, dt, KBT, P, bi, slip, W, split_rand)
+    s_r, Xr, Qr = _np_rhs_mid6(orc, O.remove_mean(cfg), X, Qn, a, 1.0, wall, dt, KBT, P, bi, slip, W, split_rand)
     Xh, Qh = Xh.reshape(-1, 3), Qh.reshape(-1, 4)
-    print("rhs wall=%s split=%s mask=%s: rel. error of s %.2e, |X_half - ref| %.2e, |Q_half - ref| %.2e"
-          % (wall, split_rand, which, _rel(s, s_r), np.abs(Xh - Xr).max(), np.abs(Qh - Qr).max()))
+    print("rhs wall=%s split=%s %s: rel. error of s %.2e, |X_half - ref| %.2e, |Q_half - ref| %.2e"
+          % (wall, split_rand, tag, _rel(s, s_r), np.abs(Xh - Xr).max(), np.abs(Qh - Qr).max()))
     assert _rel(s, s_r) < 1e-8                      # the difference quotient carries 1e-15/delta of product rounding
     np.testing.assert_allclose(Xh, Xr, rtol=0, atol=1e-11)
     np.testing.assert_allclose(Qh, Qr, rtol=0, atol=1e-11)
@@ -134,6 +139,13 @@ def _rhs_case6(orc, shell12, wall, split_rand, which):
         assert np.linalg.norm(Xh - X) > 1e-4                                           # the free ones did move
     X1, Q1 = rb.get_config()
     assert np.array_equal(X1.reshape(-1, 3), X) and np.allclose(Q1.reshape(-1, 4), Qn, rtol=0, atol=1e-15)   # nothing committed
+    return got
+
+
+def _rhs_case6(orc, shell12, wall, split_rand, which):
+    X, Q, W, slip, F, Up = _case(wall)
+    P, held = _mask6(which, 4)
+    _rhs_compare(orc, shell12, 1.0, X, Q, W, slip, P, held, F, Up, wall, split_rand, "mask=%s" % which)
 
 
 @pytest.mark.parametrize("which", MASKS)
@@ -141,6 +153,33 @@ def _rhs_case6(orc, shell12, wall, split_rand, which):
 @pytest.mark.parametrize("wall", [False, True])
 def test_rhs_and_predictor_against_the_numpy_restatement(orc, shell12, wall, split_rand, which):
     _rhs_case6(orc, shell12, wall, split_rand, which)
+
+
+@pytest.mark.parametrize("shape,nb", [("fib257", 2), ("fib7", 3)])
+@pytest.mark.parametrize("wall", [False, True])
+def test_rhs_and_predictor_at_bodies_of_257_and_of_7_blobs(orc, wall, shape, nb):
+    """The comparison above where the sums kernel's loop over a body's blobs is not the 12-blob one: 257 blobs are one past the
+    workgroup's 256 threads (a second pass with one live lane), 7 are fewer than the threads and odd.  At each structure a
+    whole-body mask (body 0, driven) through the whole-body call and a component mask (z of every body held, the rotation of
+    body 1 driven) through the _dof call; and whole rows through _dof are the whole-body call's bits."""
+    import body_shapes as bs
+    cfg = bs.shape(shape)
+    X, Q = bs.lattice(nb, cfg, wall, seed=3)
+    n3 = 3 * nb * cfg.shape[0]
+    rng = np.random.default_rng(257)
+    W, slip, F, Up = rng.standard_normal(3 * n3), 0.1 * rng.standard_normal(n3), rng.standard_normal((nb, 6)), 0.5 * rng.standard_normal((nb, 6))
+    none = np.zeros((nb, 6), dtype=bool)
+    Pw = none.copy()
+    Pw[0] = True
+    tag = "%d x %s " % (nb, shape)
+    whole = _rhs_compare(orc, cfg, bs.A, X, Q, W, slip, Pw, none, F, Up, wall, True, tag + "body 0, whole-body call", whole_body=True)
+    rows = _rhs_compare(orc, cfg, bs.A, X, Q, W, slip, Pw, none, F, Up, wall, True, tag + "body 0, whole rows")
+    for x, y in zip(rows, whole):
+        assert np.array_equal(x, y)
+    P, held = none.copy(), none.copy()
+    P[:, 2] = held[:, 2] = True
+    P[1, 3:] = True
+    _rhs_compare(orc, cfg, bs.A, X, Q, W, slip, P, held, F, Up, wall, True, tag + "z of all, rotation of body 1")
 
 
 def _check_step(tag, nb, dt, X, Qn, P, held, bi, Up, Xg, Qg, Fo, its, res, ref):
@@ -465,6 +504,56 @@ def test_every_replica_is_the_single_context_step(R, nb, steps, sample, split_ra
         if (~Pt).any():
             assert np.linalg.norm(Xe[r][~Pt] - X0[r][~Pt]) > 1e-5
     s.close()
+
+
+@pytest.mark.parametrize("per", [6, 1])
+def test_258_trimers_with_masks_that_differ_lane_by_lane(per):
+    """43 replicas of 6 trimers: 258 bodies, so the second workgroup of the one-thread-per-body kernels has two live lanes, and 3
+    blobs a body.  Replica r holds z of the bodies in r's bits and drives the whole of body r % 6: neighbouring lanes of the masked
+    predictor kernel hold free bodies, bodies with z alone, whole bodies -- a mask decoded for one lane and used by another gives
+    another configuration.  per = 6: that mask through ensemble_step_brownian_mixed_dof; per = 1: its whole-body part alone through
+    ensemble_step_brownian_mixed.  One step, injected noise; every replica against the single-context step at its configuration
+    within the 1e-7 of test_every_replica_is_the_single_context_step."""
+    import body_shapes as bs
+    R, nb, wall = 43, 6, True
+    cfg = bs.trimer()
+    c = {"cfg": cfg, "a": bs.A, "eta": bs.ETA, "dt": 0.01}
+    X0, Q0 = (np.stack(v) for v in zip(*(bs.lattice(nb, cfg, wall, seed=bs.replica_seed(r)) for r in range(R))))
+    whole = np.arange(nb)[None, :] == (np.arange(R) % nb)[:, None]
+    P = np.zeros((R, nb, 6), dtype=bool)
+    if per == 6:
+        P[:, :, 2] = ((np.arange(R)[:, None] >> np.arange(nb)[None, :]) & 1).astype(bool)
+    P[whole] = True
+    kinds = {int(k) for k in np.unique((P * (1 << np.arange(6))).sum(axis=2))}
+    assert kinds == ({0, 4, 63} if per == 6 else {0, 63}) and len({m.tobytes() for m in P}) == (R if per == 6 else nb)
+    bi, slip = _ens_inputs(P, 92, nblb=3)
+    W = np.random.default_rng(93).standard_normal((R, 9 * 3 * nb))
+    ens = _ensemble(c, X0, Q0, wall)
+    if per == 6:
+        F, its, res = ens.ensemble_step_brownian_mixed_dof(P, bi, W=W, max_iter=IT, rtol=RTOL, slip=slip)
+    else:
+        F, its, res = ens.ensemble_step_brownian_mixed(whole, bi, W=W, max_iter=IT, rtol=RTOL, slip=slip)
+    assert np.all(its > 0) and np.all(its < IT) and np.all(res < RTOL)
+    Xe, Qe = ens.ensemble_get_config()
+    ens.close()
+    s = _single(c, X0[0], Q0[0], wall)
+    worst = np.zeros(3)
+    for r in range(R):
+        s.set_config(X0[r], Q0[r])
+        if per == 6:
+            Fs, it, _ = s.step_brownian_mixed_dof(P[r], bi[r], max_iter=IT, rtol=RTOL, slip=slip[r], W=W[r], method=0)
+        else:
+            Fs, it, _ = s.step_brownian_mixed(whole[r], bi[r], max_iter=IT, rtol=RTOL, slip=slip[r], W=W[r], method=0)
+        assert 0 < it < IT
+        Xs, Qs = s.get_config(nb)
+        worst = np.maximum(worst, [np.abs(Xe[r] - Xs).max(), np.abs(Qe[r] - Qs).max(), _rel(F[r], Fs)])
+        assert np.abs(Xe[r] - Xs).max() <= 1e-7 and np.abs(Qe[r] - Qs).max() <= 1e-7, r
+        assert _rel(F[r], Fs) <= 1e-7, r
+        Pt, Up = P[r][:, :3], bi[r].reshape(nb, 6)[:, :3]
+        assert np.abs((Xe[r][Pt] - X0[r][Pt]) - c["dt"] * Up[Pt]).max() <= 1e-15 * np.abs(Xe[r]).max()   # X += dt U_p: one rounding
+        assert np.linalg.norm(Xe[r][~Pt] - X0[r][~Pt]) > 1e-5
+    s.close()
+    print("258 trimers, per=%d: worst |X - single| %.2e |Q - single| %.2e, rel. diff F %.2e" % (per, *worst))
 
 
 @pytest.mark.parametrize("R,nb", [(5, 3), (200, 2)])
