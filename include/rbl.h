@@ -590,7 +590,36 @@ int rbl_option_key(const char *name);
  * with on != 0; non-finite moments, field vectors, omega or t; c_dd < 0 or non-finite; with c_dd > 0: r_core <= 0 or
  * non-finite, r_cut <= r_core or NaN (+inf is accepted); n_bodies < 1 or n < 1.  on = 0 with NULL arrays only switches the
  * term off.  The getters take NULL for what is not wanted (m_body: 3 n_bodies doubles, B9: B0 | B1 | B2, t: n doubles).
- * Body force / torque about the body centre = K^T f_blob (+ the traps, the dipole pairs and the field torque).  The
+ * Bonds and tethers between anchor points fixed in the bodies (their own switch, nothing changes while they are off).  Bond b
+ * joins end A, the point p_A = X_i + R(Q_i) s_A of body i, to end B, the same kind of point of a DIFFERENT body j -- or, with
+ * j = -1, the fixed lab-frame point P (a tether).  s is a body-frame vector relative to the body's tracking point, in the frame
+ * of the structure after its mean was removed (s = 0: the centre; a blob's body-frame position: the bond ends on that blob).
+ * With r = p_A - p_B and d = |r|:
+ *   kind 0, harmonic    U = 1/2 k (d - l0)^2, k >= 0, l0 >= 0;
+ *   kind 1, tabulated   U = k T(d), T the BOND TABLE of rbl_set_bond_table: the construction, limits and coefficient layout of
+ *                       the pair table (0 <= r_min < r_cut, 2 <= n <= 65537, cubic Hermite in (U, dU)), but continued along
+ *                       its tangent at BOTH ends of the grid -- below r_min with the slope dU_0, above r_cut with the slope
+ *                       dU_{n-1}: a bond never breaks, nothing is skipped beyond r_cut.  FENE, worm-like chain, Morse, ...
+ *                       Evaluating a kind-1 bond while no bond table is set, or while it is off: RBL_ERR_STATE.
+ * Force on end A: f = -(dU/dd) r / d, on end B: -f; d = 0 exerts no force for either kind (as in the steric term) and has the
+ * energy U(0).  Body i gets the force f and the torque (R(Q_i) s_A) x f, body j gets -f and (R(Q_j) s_B) x (-f), a lab point
+ * nothing.  Each body carries half of a body-body bond's energy, the one body of a tether all of it.  Like the traps and the
+ * dipoles the term enters the BODY forces / torques and the energy, not f_blob.  One bond is a ball joint, two are a hinge, three
+ * non-collinear ones a stiff joint with bending and torsional stiffness: there are no angle or dihedral terms.  Bit 6 of
+ * rbl_interactions_active: bonds on and n_bonds > 0.
+ * rbl_set_bonds: body[2 n_bonds] (body[2b] >= 0; body[2b+1] >= 0 and different, or -1), anchor[6 n_bonds] (s_A, then s_B or
+ * P), kind[n_bonds] or NULL (all harmonic), param[n_sets 2 n_bonds] ((k, l0) per bond, set-major), n_sets = 1, or R for a
+ * stiffness or rest-length sweep with one set per replica of an ensemble (a single context uses set 0; any other count at an
+ * ensemble evaluation: RBL_ERR_STATE).  In an ensemble the topology and the anchors are shared by all replicas, indices are
+ * local to a replica and replicas never bond to each other.  It may be called before rbl_set_config: a body index >= N_bod is
+ * found when the model is evaluated (RBL_ERR_STATE, the bond named).  RBL_ERR_ARG, with the argument named, the previous model
+ * in place and no device touched: NULL where an array is needed; n_bonds < 1 or > 2^24; n_sets < 1 (or n_sets n_bonds >
+ * 2^30); a first index < 0; a second index < -1; both ends on one body; a kind other than 0 or 1; non-finite anchors or
+ * parameters; k < 0; l0 < 0.  on = 0 with NULL arrays only switches the term off; on = 0 with arrays stores them switched off.
+ * rbl_get_bonds takes NULL for what is not wanted.  rbl_bond_state / rbl_ensemble_bond_state: length d, tension dU/dd and
+ * energy U of every stored bond (on or off) at the context's / every replica's configuration, n_bonds / R n_bonds doubles
+ * each (replica-major), host arrays, any may be NULL; synchronous.  RBL_ERR_STATE before any bonds were set.
+ * Body force / torque about the body centre = K^T f_blob (+ the traps, the dipole pairs, the field torque and the bonds).  The
  * evaluation is deterministic (ordered pairs, no atomics): the same configuration gives bitwise the same forces on every
  * call and every rank (multi-GPU contexts evaluate the whole model, replicated -- the dipole terms included).
  *
@@ -618,8 +647,8 @@ int rbl_get_interactions(const rbl_ctx *ctx, double *params6, int *on);
  * NULL (k = X0 = NULL) with on = 0 only switches it off.  rbl_set_parameters is not needed first.  The getters take NULL for
  * what is not wanted; coef: 4 (n - 1) doubles (c0 c1 c2 c3 per interval), k3 / X0: 3 n_bodies each; n = 0: never set.
  * rbl_get_interactions keeps reporting the built-in term only; rbl_interactions_active: bit 0 built-in term, bit 1 pair
- * table, bit 2 height table, bit 3 traps, bit 4 dipole pairs, bit 5 field torque.  The steps, the queries below and the
- * ensembles evaluate every term that is on. */
+ * table, bit 2 height table, bit 3 traps, bit 4 dipole pairs, bit 5 field torque, bit 6 bonds.  The steps, the queries below
+ * and the ensembles evaluate every term that is on. */
 int rbl_set_pair_table(rbl_ctx *ctx, const double *U, const double *dU, int n, double r_min, double r_cut, int on);
 int rbl_get_pair_table(const rbl_ctx *ctx, int *n, double *r_min, double *r_cut, int *on, double *coef);
 int rbl_set_height_table(rbl_ctx *ctx, const double *U, const double *dU, int n, double h_min, double h_cut, int on);
@@ -632,6 +661,13 @@ int rbl_set_magnetic_field(rbl_ctx *ctx, const double B0[3], const double B1[3],
 int rbl_get_magnetic_field(const rbl_ctx *ctx, double *B9, double *omega, int *on);
 int rbl_set_field_time(rbl_ctx *ctx, const double *t, int n);
 int rbl_get_field_time(const rbl_ctx *ctx, int *n, double *t);
+int rbl_set_bonds(rbl_ctx *ctx, int n_bonds, const int *body, const double *anchor, const int *kind, const double *param,
+                  int n_sets, int on);
+int rbl_get_bonds(const rbl_ctx *ctx, int *n_bonds, int *n_sets, int *on, int *body, double *anchor, int *kind, double *param);
+int rbl_set_bond_table(rbl_ctx *ctx, const double *U, const double *dU, int n, double r_min, double r_cut, int on);
+int rbl_get_bond_table(const rbl_ctx *ctx, int *n, double *r_min, double *r_cut, int *on, double *coef);
+int rbl_bond_state(rbl_ctx *ctx, double *length, double *tension, double *energy);
+int rbl_ensemble_bond_state(rbl_ctx *ctx, double *length, double *tension, double *energy);
 int rbl_interactions_active(const rbl_ctx *ctx, int *mask);
 int rbl_interaction_forces_dev(rbl_ctx *ctx, double *d_f_blob, double *d_FT_body, double *energy);
 int rbl_interaction_forces(rbl_ctx *ctx, double *f_blob, double *FT_body, double *energy);

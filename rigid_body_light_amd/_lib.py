@@ -95,6 +95,11 @@ def lib():
         L.rbl_get_magnetic_field.argtypes = [vp, vp, C.POINTER(dbl), C.POINTER(C.c_int)]
         L.rbl_set_field_time.argtypes = [vp, vp, C.c_int]
         L.rbl_get_field_time.argtypes = [vp, C.POINTER(C.c_int), vp]
+        L.rbl_set_bonds.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int]
+        L.rbl_get_bonds.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, vp, vp]
+        L.rbl_set_bond_table.argtypes = L.rbl_set_pair_table.argtypes
+        L.rbl_get_bond_table.argtypes = L.rbl_get_pair_table.argtypes
+        L.rbl_bond_state.argtypes = L.rbl_ensemble_bond_state.argtypes = [vp, vp, vp, vp]
         L.rbl_interaction_forces_dev.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_forces.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
@@ -167,6 +172,60 @@ def dipole_args(who, m_body, c_dd, r_core):
             raise ValueError("%s: r_core is needed with c_dd != 0 (below it the pair energy is a quadratic form)" % who)
         r_core = 0.0
     return m, float(r_core)
+
+
+def bond_args(who, body, anchor_a, anchor_b, k, l0, kind, sets=(1,)):
+    """the checks set_bonds can make before the library is called -> contiguous body int32 (n, 2), anchor float64 (n, 6), kind
+    int32 (n,) or None, param float64 (n_sets, n, 2).  body: (n, 2) integers (or (2,) for one bond), the second -1 for a lab
+    point; anchor_a, anchor_b: (3,) -- every bond alike -- or (n, 3); k, l0: a number, (n,) or (n_sets, n) with n_sets in `sets`
+    (None: any count); kind: None (all harmonic) or (n,) integers"""
+    import numpy as np
+    b = np.asarray(body)
+    if b.shape == (2,):
+        b = b.reshape(1, 2)
+    if b.ndim != 2 or b.shape[1] != 2 or not b.shape[0] or not np.issubdtype(b.dtype, np.integer):
+        raise ValueError("%s: body must be an integer array of shape (n, 2); got %s of dtype %s" % (who, b.shape, b.dtype))
+    n = b.shape[0]
+    anchors = []
+    for name, v in (("anchor_a", anchor_a), ("anchor_b", anchor_b)):
+        v = np.asarray(v, dtype=np.float64)
+        if v.shape == (3,):
+            v = np.broadcast_to(v, (n, 3))
+        if v.shape != (n, 3):
+            raise ValueError("%s: %s must have shape (3,) or (%d, 3); got %s" % (who, name, n, v.shape))
+        anchors.append(v)
+    par = []
+    for name, v in (("k", k), ("l0", l0)):
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim == 0:
+            v = np.broadcast_to(v, (n,))
+        if v.ndim == 1 and v.shape == (n,):
+            v = v.reshape(1, n)
+        if v.ndim != 2 or v.shape[1] != n or not v.shape[0] or (sets is not None and v.shape[0] not in sets):
+            want = "(n_sets, %d)" % n if sets is None else " or ".join("(%d, %d)" % (q, n) for q in sets if q != 1)
+            raise ValueError("%s: %s must be a number or have shape (%d,)%s; got %s" % (who, name, n, " or " + want if want else "", v.shape))
+        par.append(v)
+    n_sets = max(par[0].shape[0], par[1].shape[0])
+    if any(v.shape[0] not in (1, n_sets) for v in par):
+        raise ValueError("%s: k and l0 hold different numbers of sets; got %s and %s" % (who, par[0].shape, par[1].shape))
+    param = np.ascontiguousarray(np.stack([np.broadcast_to(v, (n_sets, n)) for v in par], axis=2))
+    if kind is not None:
+        kind = np.asarray(kind)
+        if kind.shape != (n,) or not np.issubdtype(kind.dtype, np.integer):
+            raise ValueError("%s: kind must be None or an integer array of shape (%d,); got %s of dtype %s" % (who, n, kind.shape, kind.dtype))
+        kind = np.ascontiguousarray(kind, dtype=np.int32)
+    return (np.ascontiguousarray(b, dtype=np.int32), np.ascontiguousarray(np.concatenate(anchors, axis=1)), kind, param)
+
+
+def blob_anchor(cfg, k):
+    """body-frame position of blob k of the structure cfg (N_blb, 3) with the structure's mean removed, as the library removes
+    it: the anchor of a bond that ends on that blob"""
+    import numpy as np
+    cfg = np.asarray(cfg, dtype=np.float64).reshape(-1, 3)
+    mean = np.zeros(3)
+    for row in cfg:                                    # the library's own order of summation
+        mean = mean + row
+    return cfg[int(k)] - mean / float(cfg.shape[0])
 
 
 def field_args(who, B0, B1, B2):
@@ -249,6 +308,7 @@ class DeviceContext:
         cfg = np.ascontiguousarray(np.zeros((1, 3)) if cfg is None else cfg, dtype=np.float64)
         self._chk(self.L.rbl_set_parameters(self.h, a, dt, kBT, eta, cfg.ctypes.data, cfg.shape[0]))
         self._a = float(a)
+        self._cfg = cfg.reshape(-1, 3).copy()
         self._chk(self.L.rbl_set_wall_pc(self.h, int(bool(wall))))
         self._chk(self.L.rbl_set_stream(self.h, stream_ptr))
         self._stream_ptr = int(stream_ptr or 0)
@@ -401,11 +461,13 @@ class DeviceContext:
         return dict(zip(("w", "eps_wall", "b_wall", "eps_blob", "b_blob", "r_cut"), list(v)), on=bool(on.value), a=self._a)
 
     def interactions_on(self):
-        """any term of the model is on: the built-in one, a pair table, a height table, the traps, dipole pairs, the field torque"""
+        """any term of the model is on: the built-in one, a pair table, a height table, the traps, dipole pairs, the field torque,
+        bonds"""
         return self.interactions_active() != 0
 
     def interactions_active(self):
-        """bit 0 built-in terms, bit 1 pair table, bit 2 height table, bit 3 traps, bit 4 dipole pairs, bit 5 field torque"""
+        """bit 0 built-in terms, bit 1 pair table, bit 2 height table, bit 3 traps, bit 4 dipole pairs, bit 5 field torque,
+        bit 6 bonds"""
         m = C.c_int(0)
         self._chk(self.L.rbl_interactions_active(self.h, C.byref(m)))
         return m.value
@@ -520,6 +582,65 @@ class DeviceContext:
         t = np.zeros(n.value)
         self._chk(self.L.rbl_get_field_time(self.h, None, t.ctypes.data))
         return t
+
+    def set_bonds(self, body, anchor_a, anchor_b, k, l0=0.0, kind=None, on=True):
+        """bonds and tethers between anchor points fixed in the bodies (include/rbl.h section 4): bond b joins the point
+        X_i + R(Q_i) anchor_a[b] of body i = body[b, 0] to the same kind of point of body j = body[b, 1] != i, or, with j = -1, to
+        the lab point anchor_b[b].  kind 0 (the default): U = k (d - l0)^2 / 2; kind 1: U = k T(d), T the bond table of
+        set_bond_table.  k, l0: a number, (n,) or (n_sets, n), n_sets = 1 or the replicas of an ensemble.  body=None with
+        on=False only switches the bonds off."""
+        if body is None and not on:
+            return self._chk(self.L.rbl_set_bonds(self.h, 0, None, None, None, None, 0, 0))
+        b, anchor, kind, param = bond_args("set_bonds", body, anchor_a, anchor_b, k, l0, kind, sets=None)
+        self._chk(self.L.rbl_set_bonds(self.h, b.shape[0], b.ctypes.data, anchor.ctypes.data, None if kind is None else kind.ctypes.data,
+                                       param.ctypes.data, param.shape[0], int(bool(on))))
+
+    def bonds(self):
+        """{on, body (n, 2), anchor_a (n, 3), anchor_b (n, 3), kind (n,), k (n_sets, n), l0 (n_sets, n)} (n = 0: never set)"""
+        import numpy as np
+        n, ns, on = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_bonds(self.h, C.byref(n), C.byref(ns), C.byref(on), None, None, None, None))
+        body, anchor = np.zeros((n.value, 2), dtype=np.int32), np.zeros((n.value, 6))
+        kind, param = np.zeros(n.value, dtype=np.int32), np.zeros((ns.value, n.value, 2))
+        if n.value:
+            self._chk(self.L.rbl_get_bonds(self.h, None, None, None, body.ctypes.data, anchor.ctypes.data, kind.ctypes.data, param.ctypes.data))
+        return dict(on=bool(on.value), body=body, anchor_a=anchor[:, :3].copy(), anchor_b=anchor[:, 3:].copy(), kind=kind,
+                    k=param[:, :, 0].copy(), l0=param[:, :, 1].copy())
+
+    def set_bond_table(self, U, dU, r_min, r_cut, on=True):
+        """the potential T(d) of the kind-1 bonds from its values U and derivatives dU = dU/dd on the uniform grid r_min .. r_cut
+        (see `tabulate`): cubic Hermite inside, continued along its tangent at BOTH ends (a bond never breaks).  U = dU = None with
+        on=False only switches the stored table off."""
+        if U is None and dU is None and not on:
+            return self._chk(self.L.rbl_set_bond_table(self.h, None, None, 0, 0.0, 0.0, 0))
+        U, dU = table_arrays("set_bond_table", U, dU)
+        self._chk(self.L.rbl_set_bond_table(self.h, U.ctypes.data, dU.ctypes.data, U.size, float(r_min), float(r_cut), int(bool(on))))
+
+    def bond_table(self):
+        return self._get_table(self.L.rbl_get_bond_table)
+
+    def blob_anchor(self, k):
+        """body-frame position of blob k with the structure's mean removed: the anchor of a bond that ends on that blob"""
+        return blob_anchor(self._cfg, k)
+
+    def bond_state(self):
+        """-> (length, tension dU/dd, energy) of every bond at the context's configuration, (n_bonds,) each"""
+        import numpy as np
+        n = C.c_int(0)
+        self._chk(self.L.rbl_get_bonds(self.h, C.byref(n), None, None, None, None, None, None))
+        out = np.zeros((3, max(n.value, 1)))
+        self._chk(self.L.rbl_bond_state(self.h, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
+        return out[0, :n.value], out[1, :n.value], out[2, :n.value]
+
+    def ensemble_bond_state(self):
+        """-> (length, tension, energy) of every bond of every replica, (R, n_bonds) each"""
+        import numpy as np
+        n = C.c_int(0)
+        self._chk(self.L.rbl_get_bonds(self.h, C.byref(n), None, None, None, None, None, None))
+        R = self.ensemble_info()[0]
+        out = np.zeros((3, max(R * n.value, 1)))
+        self._chk(self.L.rbl_ensemble_bond_state(self.h, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
+        return tuple(out[q, :R * n.value].reshape(R, n.value) for q in range(3))
 
     def interaction_forces_dev(self, d_f_blob, d_FT_body, energy=False):
         """PHYSICAL forces at the current configuration into device buffers (addresses or None); energy=True also returns the

@@ -670,6 +670,42 @@ struct CManyBodies {
     rbl_get_field_time(ctx, nullptr, t.mutable_data());
     return t;
   }
+  // body: 2 per bond, anchor: 6 per bond, kind: 1 per bond or None, param: (k, l0) per bond; body None only switches the bonds off
+  void set_bonds(py::object body, py::object anchor, py::object kind, py::object param, bool on)
+  {
+    if (body.is_none()) { check(rbl_set_bonds(ctx, 0, nullptr, nullptr, nullptr, nullptr, 0, on ? 1 : 0)); return; }
+    typedef py::array_t<int, py::array::c_style | py::array::forcecast> iarr;
+    iarr b = body.cast<iarr>();
+    darr an = anchor.cast<darr>(), pa = param.cast<darr>();
+    const py::ssize_t n = b.size() / 2;
+    if (b.size() % 2 || !n || an.size() != 6 * n || pa.size() != 2 * n)
+      throw std::runtime_error("set_bonds: body must hold 2, anchor 6 and param 2 entries per bond");
+    iarr ki;
+    if (!kind.is_none()) {
+      ki = kind.cast<iarr>();
+      if (ki.size() != n) throw std::runtime_error("set_bonds: kind must hold one entry per bond");
+    }
+    check(rbl_set_bonds(ctx, (int)n, b.data(), an.data(), kind.is_none() ? nullptr : ki.data(), pa.data(), 1, on ? 1 : 0));
+  }
+  void set_bond_table(darr U, darr dU, double r_min, double r_cut, bool on)
+  {
+    if (U.ndim() != 1 || dU.ndim() != 1 || U.size() != dU.size()) throw std::runtime_error("set_bond_table: U and dU must be one-dimensional and of one length");
+    check(rbl_set_bond_table(ctx, U.data(), dU.data(), (int)U.size(), r_min, r_cut, on ? 1 : 0));
+  }
+  // (length, tension, energy) of every bond
+  py::tuple bond_state()
+  {
+    int n = 0;
+    rbl_get_bonds(ctx, &n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    darr len(n), ten(n), en(n);
+    int rc;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_bond_state(ctx, len.mutable_data(), ten.mutable_data(), en.mutable_data());
+    }
+    check(rc);
+    return py::make_tuple(len, ten, en);
+  }
   int interactions_active() const
   {
     int m = 0;
@@ -828,8 +864,11 @@ PYBIND11_MODULE(c_rigid, m)
       .def("magnetic_field", &CManyBodies::magnetic_field)
       .def("set_field_time", &CManyBodies::set_field_time, py::arg("t"))
       .def("field_time", &CManyBodies::field_time)
+      .def("set_bonds", &CManyBodies::set_bonds, py::arg("body"), py::arg("anchor"), py::arg("kind"), py::arg("param"), py::arg("on") = true)
+      .def("set_bond_table", &CManyBodies::set_bond_table, py::arg("U"), py::arg("dU"), py::arg("r_min"), py::arg("r_cut"), py::arg("on") = true)
+      .def("bond_state", &CManyBodies::bond_state, "(length, tension dU/dd, energy) of every bond")
       .def("interactions_active", &CManyBodies::interactions_active,
-           "bit 0 built-in terms, 1 pair table, 2 height table, 3 traps, 4 dipole pairs, 5 field torque")
+           "bit 0 built-in terms, 1 pair table, 2 height table, 3 traps, 4 dipole pairs, 5 field torque, 6 bonds")
       .def("interaction_forces", &CManyBodies::interaction_forces, "force model's body forces/torques, reference convention (-K^T f)")
       .def("interaction_energy", &CManyBodies::interaction_energy)
       .def("velocity_field", &CManyBodies::velocity_field, "fluid velocity at points from blob forces", py::arg("points"),

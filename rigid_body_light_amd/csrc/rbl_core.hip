@@ -141,6 +141,8 @@ static const RblBufRow kDevBufs[] = {
     {&rbl_ctx::d_ia, RBL_BUF_PERSIST},            // force-model lists and forces of the last evaluation (ia_nb, ia_cap)
     {&rbl_ctx::d_iat, RBL_BUF_PERSIST},           // force-model tables and traps (ia_tab_valid)
     {&rbl_ctx::d_iam, RBL_BUF_PERSIST},           // dipole moments and field times (ia_mag_valid, ia_ft_valid)
+    {&rbl_ctx::d_iab, RBL_BUF_PERSIST},           // bonds: anchors, parameters, topology (ia_bd_valid)
+    {&rbl_ctx::d_iabs, RBL_BUF_SCRATCH},          // bond state queries: reserved at their start, within one call
     {&rbl_ctx::d_ens, RBL_BUF_PERSIST},           // ensemble configurations
     {&rbl_ctx::d_ens_w, RBL_BUF_SCRATCH},         // ensemble step workspace: reserved at the start of each ensemble entry point
     {&rbl_ctx::d_ens_run, RBL_BUF_SCRATCH},       // ensemble run: inputs, counters and frames, reserved at the start of rbl_ensemble_run

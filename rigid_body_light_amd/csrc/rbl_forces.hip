@@ -30,6 +30,16 @@
 //                        FT[6 i ..] and to the energy entry of the body's first blob.  No atomics; the order depends on the
 //                        window-local indices alone, so a replica of an ensemble is bitwise the single context.  Every
 //                        partner is read once per workgroup, so nothing is staged: the only LDS is the reduction's.
+//   k_body_bonds         bonds and tethers between anchor points fixed in the bodies, after the dipoles: one wave per (bonded
+//                        body, window).  The host keeps a CSR of bond ENDS by body, in increasing bond index (built once per
+//                        rbl_set_bonds); lane t takes the ends t, t + 64, ... of its body, rotates both anchors with the two
+//                        quaternions, evaluates the bond (harmonic, or the bond table continued along its tangent at both ends
+//                        of the grid) and accumulates force, torque and its share of the energy in fp64 registers;
+//                        rbl_block_sum adds the lanes in one fixed tree and lane 0 adds to FT[6 i ..] and to the energy entry
+//                        of the body's first blob.  Both ends of a bond evaluate the same r = p_A - p_B with the same
+//                        operations, so the two forces are bitwise opposite.  No atomics; the order depends on replica-local
+//                        indices alone.  The grid covers the compact list of bonded bodies, not all bodies.
+//   k_bond_state         one lane per (window, bond): length, tension dU/dd and energy, for the state queries.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -323,6 +333,121 @@ __global__ __launch_bounds__(NT) void k_body_dipoles(const double *__restrict__ 
   if (e) e[(size_t)i * N_blb] += E;
 }
 
+// the bond table on the device: the pair table's construction, continued along its tangent above hi as well as below lo
+struct IaBondTab {
+  IaTab T;
+  double U1, dU1;                                        // value and slope at hi
+};
+
+// the bonds as the kernels take them (by value).  anchor: s_A | s_B (or the lab point P) per bond; param: (k, l0) per bond,
+// set-major; ends: (partner or -1, bond, which end) per entry of the CSR
+struct IaBonds {
+  const double *anchor, *param;
+  const int *kind, *body, *rows, *ptr, *ends;
+  IaBondTab BT;
+  int n, n_rows, per_set;                                // per_set: window w reads parameter set w (0: every window reads set 0)
+};
+
+// R(Q_b) s
+__device__ __forceinline__ void ia_lab_anchor(const double *__restrict__ Q, const double *__restrict__ s, int b, double (&l)[3])
+{
+  double R[9];
+  quat_rot(Q + 4 * (size_t)b, R);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) l[c] = R[3 * c] * s[0] + R[3 * c + 1] * s[1] + R[3 * c + 2] * s[2];
+}
+
+// bond b of window w between the bodies ia and ib (global indices; ib < 0: the lab point): the lever arms of both ends,
+// r = p_A - p_B, its length, the energy U(d) and the tension dU/dd.  ONE sequence of operations for both ends of a bond and
+// for the state query
+__device__ __forceinline__ void ia_bond_eval(const IaBonds &B, const double *__restrict__ X, const double *__restrict__ Q, int b,
+                                             int w, int ia, int ib, double (&lA)[3], double (&lB)[3], double (&r)[3], double &d,
+                                             double &U, double &dU)
+{
+  const double *s = B.anchor + 6 * (size_t)b;
+  ia_lab_anchor(Q, s, ia, lA);
+  double pB[3];
+  if (ib >= 0) {
+    ia_lab_anchor(Q, s + 3, ib, lB);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pB[c] = X[3 * (size_t)ib + c] + lB[c];
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { lB[c] = 0.0; pB[c] = s[3 + c]; }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) r[c] = (X[3 * (size_t)ia + c] + lA[c]) - pB[c];
+  d = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  const double *q = B.param + 2 * ((size_t)(B.per_set ? w : 0) * B.n + b);
+  const double k = q[0], l0 = q[1];
+  if (B.kind[b] == 0) {
+    const double x = d - l0;
+    dU = k * x;
+    U = 0.5 * k * x * x;
+  } else {
+    double Ut, dUt;
+    if (d > B.BT.T.hi) {                                 // a bond never breaks: the tangent at hi continued upwards
+      Ut = B.BT.U1 + B.BT.dU1 * (d - B.BT.T.hi);
+      dUt = B.BT.dU1;
+    } else {
+      ia_tab_eval(B.BT.T, d, Ut, dUt);
+    }
+    U = k * Ut;
+    dU = k * dUt;
+  }
+}
+
+// bonds and tethers (include/rbl.h section 4), added to FT and to the energy entry of the body's first blob after the dipoles on
+// the same stream: one order.  One wave per (bonded body, window): blockIdx.x = window * n_rows + row
+__global__ __launch_bounds__(64) void k_body_bonds(const double *__restrict__ X, const double *__restrict__ Q, int win, int N_blb,
+                                                   IaBonds B, double *__restrict__ FT, double *__restrict__ e)
+{
+  __shared__ double red[7][64];
+  const int w = blockIdx.x / B.n_rows, row = blockIdx.x - w * B.n_rows, t = threadIdx.x;
+  const int i = w * win + B.rows[row];
+  double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // force, torque, the body's share of the energies
+  for (int q = B.ptr[row] + t; q < B.ptr[row + 1]; q += 64) {
+    const int partner = B.ends[3 * (size_t)q], b = B.ends[3 * (size_t)q + 1], end = B.ends[3 * (size_t)q + 2];
+    const int other = partner >= 0 ? w * win + partner : -1;
+    double lA[3], lB[3], r[3], d, U, dU;
+    ia_bond_eval(B, X, Q, b, w, end ? other : i, end ? i : other, lA, lB, r, d, U, dU);
+    const double g = d > 0.0 ? -dU / d : 0.0;              // coincident ends exert no force
+    double f[3] = {g * r[0], g * r[1], g * r[2]};          // on end A
+    const double *l = lA;
+    if (end) {
+      f[0] = -f[0]; f[1] = -f[1]; f[2] = -f[2];
+      l = lB;
+    }
+    acc[0] += f[0]; acc[1] += f[1]; acc[2] += f[2];
+    acc[3] += l[1] * f[2] - l[2] * f[1];
+    acc[4] += l[2] * f[0] - l[0] * f[2];
+    acc[5] += l[0] * f[1] - l[1] * f[0];
+    acc[6] += partner >= 0 ? 0.5 * U : U;                  // half of a body-body bond, all of a tether
+  }
+  rbl_block_sum<7, 64>(acc, red, t);
+  if (t != 0) return;
+  if (FT) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) FT[6 * (size_t)i + c] += acc[c];
+  }
+  if (e) e[(size_t)i * N_blb] += acc[6];
+}
+
+// length, tension dU/dd and energy of every bond of every window: out = length [n_win n] | tension | energy
+__global__ __launch_bounds__(256) void k_bond_state(const double *__restrict__ X, const double *__restrict__ Q, int win, int n_win,
+                                                    IaBonds B, double *__restrict__ out)
+{
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x, tot = (size_t)n_win * B.n;
+  if (g >= tot) return;
+  const int w = (int)(g / B.n), b = (int)(g - (size_t)w * B.n);
+  const int jb = B.body[2 * (size_t)b + 1];
+  double lA[3], lB[3], r[3], d, U, dU;
+  ia_bond_eval(B, X, Q, b, w, w * win + B.body[2 * (size_t)b], jb >= 0 ? w * win + jb : -1, lA, lB, r, d, U, dU);
+  out[g] = d;
+  out[tot + g] = dU;
+  out[2 * tot + g] = U;
+}
+
 struct IaLayout {
   double *f, *e, *ft;
   int *cnt, *list, *np;
@@ -363,15 +488,21 @@ int ia_reserve(rbl_ctx *c, IaLayout &L)
 
 static bool ia_dp_pairs(const rbl_ctx *c) { return c->ia_dp_on && c->ia_dp_c > 0.0; }
 static bool ia_dp_field(const rbl_ctx *c) { return c->ia_dp_on && c->ia_mf_on; }
+static bool ia_bonds(const rbl_ctx *c) { return c->ia_bd_on && c->ia_bd_n > 0; }
 
-bool ia_any(const rbl_ctx *c) { return c->ia_on || c->ia_pt.on || c->ia_ht.on || c->ia_tr_on || ia_dp_pairs(c) || ia_dp_field(c); }
+bool ia_any(const rbl_ctx *c)
+{
+  return c->ia_on || c->ia_pt.on || c->ia_ht.on || c->ia_tr_on || ia_dp_pairs(c) || ia_dp_field(c) || ia_bonds(c);
+}
 
-// the tables' coefficients and the traps on the device (once per rbl_set_pair_table / rbl_set_height_table / rbl_set_traps):
-// pair coefficients | height coefficients | trap k | trap X0.  4 (n - 1) doubles per table: every interval starts 32-byte aligned
+// the tables' coefficients and the traps on the device (once per rbl_set_pair_table / rbl_set_height_table / rbl_set_bond_table /
+// rbl_set_traps):
+// pair coefficients | height coefficients | bond coefficients | trap k | trap X0.  4 (n - 1) doubles per table: every interval
+// starts 32-byte aligned
 static int ia_upload(rbl_ctx *c)
 {
   if (c->ia_tab_valid) return RBL_OK;
-  const std::vector<double> *part[4] = {&c->ia_pt.coef, &c->ia_ht.coef, &c->ia_tr_k, &c->ia_tr_X0};
+  const std::vector<double> *part[5] = {&c->ia_pt.coef, &c->ia_ht.coef, &c->ia_bt.coef, &c->ia_tr_k, &c->ia_tr_X0};
   size_t n = 0;
   for (const std::vector<double> *v : part) n += v->size();
   if (n) {
@@ -416,6 +547,66 @@ static IaTab ia_tab_args(const rbl_ctx::IaTable &t, const double *d_coef)
   return T;
 }
 
+// what an evaluation over windows of `win` bodies needs of the bonds (no device touched)
+static int ia_bond_check(rbl_ctx *c, const char *who, int win, int n_win)
+{
+  if (c->ia_bd_top >= win)
+    for (int b = 0; b < c->ia_bd_n; ++b) {
+      const int m = std::max(c->ia_bd_body[2 * (size_t)b], c->ia_bd_body[2 * (size_t)b + 1]);
+      if (m >= win)
+        return rbl_fail(c, RBL_ERR_STATE, std::string(who) + ": bond " + std::to_string(b) + " names body " + std::to_string(m) +
+                                              ", the system has " + std::to_string(win) + " bodies (rbl_set_bonds)");
+    }
+  if (n_win > 1 && c->ia_bd_sets != 1 && c->ia_bd_sets != n_win)
+    return rbl_fail(c, RBL_ERR_STATE, std::string(who) + ": the bonds hold neither one parameter set nor one per replica (rbl_set_bonds)");
+  if (!c->ia_bt.on && c->ia_bd_tab >= 0)
+    return rbl_fail(c, RBL_ERR_STATE, std::string(who) + ": bond " + std::to_string(c->ia_bd_tab) + " is tabulated (kind 1) and no bond table is on (rbl_set_bond_table)");
+  return RBL_OK;
+}
+
+// the bonds on the device, once per rbl_set_bonds: anchors | parameters | kinds | bodies | rows | row starts | ends
+static int ia_bond_upload(rbl_ctx *c)
+{
+  if (c->ia_bd_valid) return RBL_OK;
+  const std::vector<double> *dpart[2] = {&c->ia_bd_anchor, &c->ia_bd_param};
+  const std::vector<int> *ipart[5] = {&c->ia_bd_kind, &c->ia_bd_body, &c->ia_bd_rows, &c->ia_bd_ptr, &c->ia_bd_ends};
+  size_t nd = 0, ni = 0;
+  for (const std::vector<double> *v : dpart) nd += v->size();
+  for (const std::vector<int> *v : ipart) ni += v->size();
+  int rc = rbl_dev_reserve(c, c->d_iab, sizeof(double) * nd + sizeof(int) * ni); if (rc) return rc;
+  double *d = (double *)c->d_iab.p;
+  for (const std::vector<double> *v : dpart) {
+    if (!v->empty() && (rc = copy_h2d(c, d, v->data(), sizeof(double) * v->size()))) return rc;
+    d += v->size();
+  }
+  int *q = (int *)d;
+  for (const std::vector<int> *v : ipart) {
+    if (!v->empty() && (rc = copy_h2d(c, q, v->data(), sizeof(int) * v->size()))) return rc;
+    q += v->size();
+  }
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  c->ia_bd_valid = true;
+  return RBL_OK;
+}
+
+// after ia_upload and ia_bond_upload
+static IaBonds ia_bond_args(const rbl_ctx *c, int n_win)
+{
+  IaBonds B = {};
+  B.anchor = (const double *)c->d_iab.p;
+  B.param = B.anchor + c->ia_bd_anchor.size();
+  B.kind = (const int *)(B.param + c->ia_bd_param.size());
+  B.body = B.kind + c->ia_bd_kind.size();
+  B.rows = B.body + c->ia_bd_body.size();
+  B.ptr = B.rows + c->ia_bd_rows.size();
+  B.ends = B.ptr + c->ia_bd_ptr.size();
+  B.BT.T = ia_tab_args(c->ia_bt, (const double *)c->d_iat.p + c->ia_pt.coef.size() + c->ia_ht.coef.size());
+  B.BT.U1 = c->ia_bt.U1; B.BT.dU1 = c->ia_bt.dU1;
+  B.n = c->ia_bd_n; B.n_rows = (int)c->ia_bd_rows.size();
+  B.per_set = n_win > 1 && c->ia_bd_sets != 1 ? 1 : 0;     // a single context uses set 0
+  return B;
+}
+
 // the model over n_win windows of win bodies each (resident X of the body centres, blob positions and lever arms): neighbour
 // lists inside each window, the pair kernel, K^T f.  d_f (3 N) is required here; d_FT (6 N_bod total) and d_e may be NULL.
 // d_Q: the orientations beside d_X (the dipoles); d_accepted: a run's per-replica step counters, the field's clock (NULL: the
@@ -436,8 +627,12 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
     return rbl_fail(c, RBL_ERR_STATE, "interactions: the dipole moments hold neither one entry, nor one per body, nor one per body of every replica (rbl_set_dipoles)");
   if (dp_field && n_win > 1 && nft != 1 && nft != (size_t)n_win)
     return rbl_fail(c, RBL_ERR_STATE, "interactions: the field time holds neither one entry nor one per replica (rbl_set_field_time)");
-  int rc = ia_upload(c); if (rc) return rc;
+  const bool bonds = ia_bonds(c);
+  int rc;
+  if (bonds && (rc = ia_bond_check(c, "interactions", win, n_win))) return rc;
+  if ((rc = ia_upload(c))) return rc;
   if (dp && (rc = ia_mag_upload(c))) return rc;
+  if (bonds && (rc = ia_bond_upload(c))) return rc;
   RblPhase ph(c, RBL_T_FORCES);
   IaLayout L = ia_layout(d_cl, nbod, S.N_blb, cap);
   double R2 = 0.0;                                       // R_body: largest blob distance from the centre, body frame (mean removed)
@@ -472,7 +667,7 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
 #undef RBL_IA_TAB
   if (d_FT) rbl_launch_KT_x_Lam(c->stream, d_lever, d_f, S.N_blb, nbod, d_FT);
   if (c->ia_tr_on && (d_FT || d_e)) {
-    const double *k3 = T + c->ia_pt.coef.size() + c->ia_ht.coef.size();
+    const double *k3 = T + c->ia_pt.coef.size() + c->ia_ht.coef.size() + c->ia_bt.coef.size();
     hipLaunchKernelGGL(k_body_traps, dim3((unsigned)((nbod + 255) / 256)), dim3(256), 0, c->stream, d_X, k3, k3 + 3 * ntr, nbod,
                        (int)ntr, S.N_blb, d_FT, d_e);
   }
@@ -489,6 +684,11 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
     else
       hipLaunchKernelGGL(k_body_dipoles<64>, dim3((unsigned)nbod), dim3(64), 0, c->stream, d_X, d_Q, mb, tf, d_accepted, win,
                          S.N_blb, M, d_FT, d_e);
+  }
+  if (bonds && (d_FT || d_e)) {
+    const IaBonds B = ia_bond_args(c, n_win);
+    hipLaunchKernelGGL(k_body_bonds, dim3((unsigned)((size_t)B.n_rows * n_win)), dim3(64), 0, c->stream, d_X, d_Q, win, S.N_blb, B,
+                       d_FT, d_e);
   }
   return RBL_OK;
 }
@@ -581,6 +781,7 @@ static int ia_set_table(rbl_ctx *c, const char *who, rbl_ctx::IaTable &t, const 
   }
   t.coef.swap(coef);
   t.n = n; t.lo = lo; t.hi = hi; t.dU0 = dU[0];
+  t.U1 = U[n - 1]; t.dU1 = dU[n - 1];
   t.on = on != 0;
   c->ia_tab_valid = false;
   return RBL_OK;
@@ -678,6 +879,132 @@ int rbl_get_dipoles(const rbl_ctx *c, int *n_bodies, double *c_dd, double *r_cor
   return RBL_OK;
 }
 
+int rbl_set_bond_table(rbl_ctx *c, const double *U, const double *dU, int n, double r_min, double r_cut, int on)
+{
+  if (!c) return RBL_ERR_ARG;
+  return ia_set_table(c, "set_bond_table", c->ia_bt, U, dU, n, r_min, r_cut, true, on);
+}
+
+int rbl_get_bond_table(const rbl_ctx *c, int *n, double *r_min, double *r_cut, int *on, double *coef)
+{
+  if (!c) return RBL_ERR_ARG;
+  return ia_get_table(c->ia_bt, n, r_min, r_cut, on, coef);
+}
+
+// the bonds: checks first, nothing is stored unless every one passes; then the CSR of bond ends by body (include/rbl.h section 4)
+int rbl_set_bonds(rbl_ctx *c, int n_bonds, const int *body, const double *anchor, const int *kind, const double *param, int n_sets, int on)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (!body && !anchor && !param && !on) { c->ia_bd_on = false; return RBL_OK; }
+  if (!body) return rbl_fail(c, RBL_ERR_ARG, "set_bonds: body must not be NULL");
+  if (!anchor) return rbl_fail(c, RBL_ERR_ARG, "set_bonds: anchor must not be NULL");
+  if (!param) return rbl_fail(c, RBL_ERR_ARG, "set_bonds: param must not be NULL");
+  if (n_bonds < 1 || n_bonds > (1 << 24)) return rbl_fail(c, RBL_ERR_ARG, "set_bonds: n_bonds must lie in [1, 2^24]");
+  if (n_sets < 1) return rbl_fail(c, RBL_ERR_ARG, "set_bonds: n_sets must be >= 1");
+  if ((size_t)n_sets * (size_t)n_bonds > ((size_t)1 << 30)) return rbl_fail(c, RBL_ERR_ARG, "set_bonds: n_sets * n_bonds must not exceed 2^30");
+  int top = -1;
+  for (int b = 0; b < n_bonds; ++b) {
+    const int i = body[2 * (size_t)b], j = body[2 * (size_t)b + 1];
+    const std::string at = "set_bonds: bond " + std::to_string(b) + ": ";
+    if (i < 0) return rbl_fail(c, RBL_ERR_ARG, at + "body[2 b], the first body index, must be >= 0");
+    if (j < -1) return rbl_fail(c, RBL_ERR_ARG, at + "body[2 b + 1], the second body index, must be >= 0 or -1 (a lab point)");
+    if (i == j) return rbl_fail(c, RBL_ERR_ARG, at + "body: both ends lie on one body (a bond inside a rigid body does nothing)");
+    if (kind && kind[b] != 0 && kind[b] != 1) return rbl_fail(c, RBL_ERR_ARG, at + "kind must be 0 (harmonic) or 1 (tabulated)");
+    for (int q = 0; q < 6; ++q)
+      if (!std::isfinite(anchor[6 * (size_t)b + q])) return rbl_fail(c, RBL_ERR_ARG, at + "every value of anchor must be finite");
+    top = std::max(top, std::max(i, j));
+  }
+  for (int s = 0; s < n_sets; ++s)
+    for (int b = 0; b < n_bonds; ++b) {
+      const double k = param[2 * ((size_t)s * n_bonds + b)], l0 = param[2 * ((size_t)s * n_bonds + b) + 1];
+      const std::string at = "set_bonds: bond " + std::to_string(b) + ", set " + std::to_string(s) + ": ";
+      if (!std::isfinite(k) || !std::isfinite(l0)) return rbl_fail(c, RBL_ERR_ARG, at + "every value of param (k, l0) must be finite");
+      if (k < 0.0) return rbl_fail(c, RBL_ERR_ARG, at + "param: k must be >= 0");
+      if (l0 < 0.0) return rbl_fail(c, RBL_ERR_ARG, at + "param: l0 must be >= 0");
+    }
+  c->ia_bd_n = n_bonds; c->ia_bd_sets = n_sets; c->ia_bd_top = top;
+  c->ia_bd_body.assign(body, body + 2 * (size_t)n_bonds);
+  c->ia_bd_anchor.assign(anchor, anchor + 6 * (size_t)n_bonds);
+  if (kind) c->ia_bd_kind.assign(kind, kind + n_bonds);
+  else c->ia_bd_kind.assign((size_t)n_bonds, 0);
+  const auto tab = std::find(c->ia_bd_kind.begin(), c->ia_bd_kind.end(), 1);
+  c->ia_bd_tab = tab == c->ia_bd_kind.end() ? -1 : (int)(tab - c->ia_bd_kind.begin());
+  c->ia_bd_param.assign(param, param + 2 * (size_t)n_sets * n_bonds);
+  // bond ends by body, in increasing bond index: the ends in bond order, sorted by body with a stable sort (a body index may
+  // be anything up to INT_MAX here, so nothing is sized by it)
+  struct End { int body, partner, bond, end; };
+  std::vector<End> ends;
+  ends.reserve(2 * (size_t)n_bonds);
+  for (int b = 0; b < n_bonds; ++b)
+    for (int q = 0; q < 2; ++q)
+      if (body[2 * (size_t)b + q] >= 0) ends.push_back({body[2 * (size_t)b + q], body[2 * (size_t)b + 1 - q], b, q});
+  std::stable_sort(ends.begin(), ends.end(), [](const End &x, const End &y) { return x.body < y.body; });
+  c->ia_bd_rows.clear(); c->ia_bd_ptr.clear();
+  c->ia_bd_ends.resize(3 * ends.size());
+  for (size_t q = 0; q < ends.size(); ++q) {
+    if (!q || ends[q].body != ends[q - 1].body) {
+      c->ia_bd_rows.push_back(ends[q].body);
+      c->ia_bd_ptr.push_back((int)q);
+    }
+    c->ia_bd_ends[3 * q] = ends[q].partner; c->ia_bd_ends[3 * q + 1] = ends[q].bond; c->ia_bd_ends[3 * q + 2] = ends[q].end;
+  }
+  c->ia_bd_ptr.push_back((int)ends.size());
+  c->ia_bd_on = on != 0;
+  c->ia_bd_valid = false;
+  return RBL_OK;
+}
+
+int rbl_get_bonds(const rbl_ctx *c, int *n_bonds, int *n_sets, int *on, int *body, double *anchor, int *kind, double *param)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (n_bonds) *n_bonds = c->ia_bd_n;
+  if (n_sets) *n_sets = c->ia_bd_sets;
+  if (on) *on = c->ia_bd_on ? 1 : 0;
+  if (body && c->ia_bd_n) std::memcpy(body, c->ia_bd_body.data(), sizeof(int) * c->ia_bd_body.size());
+  if (anchor && c->ia_bd_n) std::memcpy(anchor, c->ia_bd_anchor.data(), sizeof(double) * c->ia_bd_anchor.size());
+  if (kind && c->ia_bd_n) std::memcpy(kind, c->ia_bd_kind.data(), sizeof(int) * c->ia_bd_kind.size());
+  if (param && c->ia_bd_n) std::memcpy(param, c->ia_bd_param.data(), sizeof(double) * c->ia_bd_param.size());
+  return RBL_OK;
+}
+
+// length | tension | energy of the stored bonds (on or off) over n_win windows of win bodies into host arrays (any may be NULL)
+static int ia_bond_state(rbl_ctx *c, const char *who, const double *d_X, const double *d_Q, int win, int n_win, double *length,
+                         double *tension, double *energy)
+{
+  if (c->ia_bd_n < 1) return rbl_fail(c, RBL_ERR_STATE, std::string(who) + ": no bonds have been set (rbl_set_bonds)");
+  int rc = ia_bond_check(c, who, win, n_win); if (rc) return rc;
+  if ((rc = ia_upload(c))) return rc;
+  if ((rc = ia_bond_upload(c))) return rc;
+  const size_t tot = (size_t)n_win * c->ia_bd_n;
+  if ((rc = rbl_dev_reserve(c, c->d_iabs, sizeof(double) * 3 * tot))) return rc;
+  double *out = (double *)c->d_iabs.p;
+  hipLaunchKernelGGL(k_bond_state, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, d_X, d_Q, win, n_win,
+                     ia_bond_args(c, n_win), out);
+  double *host[3] = {length, tension, energy};
+  for (int q = 0; q < 3; ++q)
+    if (host[q] && (rc = copy_d2h(c, host[q], out + q * tot, sizeof(double) * tot))) return rc;
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  return RBL_OK;
+}
+
+int rbl_bond_state(rbl_ctx *c, double *length, double *tension, double *energy)
+{
+  int rc = need_config(c); if (rc) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  if ((rc = sync_bodies(c))) return rc;
+  const double *dX = (const double *)c->d_XQ.p;
+  return ia_bond_state(c, "bond_state", dX, dX + 3 * (size_t)c->S.N_bod, c->S.N_bod, 1, length, tension, energy);
+}
+
+int rbl_ensemble_bond_state(rbl_ctx *c, double *length, double *tension, double *energy)
+{
+  if (!c) return RBL_ERR_ARG;
+  const double *dX = nullptr, *dQ = nullptr;
+  int rc = rbl_ensemble_config_dev(c, &dX, &dQ); if (rc) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  return ia_bond_state(c, "ensemble_bond_state", dX, dQ, c->ens_Nb, c->ens_R, length, tension, energy);
+}
+
 int rbl_set_magnetic_field(rbl_ctx *c, const double B0[3], const double B1[3], const double B2[3], double omega, int on)
 {
   if (!c) return RBL_ERR_ARG;
@@ -728,7 +1055,7 @@ int rbl_interactions_active(const rbl_ctx *c, int *mask)
 {
   if (!c || !mask) return RBL_ERR_ARG;
   *mask = (c->ia_on ? 1 : 0) | (c->ia_pt.on ? 2 : 0) | (c->ia_ht.on ? 4 : 0) | (c->ia_tr_on ? 8 : 0) |
-          (ia_dp_pairs(c) ? 16 : 0) | (ia_dp_field(c) ? 32 : 0);
+          (ia_dp_pairs(c) ? 16 : 0) | (ia_dp_field(c) ? 32 : 0) | (ia_bonds(c) ? 64 : 0);
   return RBL_OK;
 }
 

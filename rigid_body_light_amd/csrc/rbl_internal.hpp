@@ -210,12 +210,14 @@ struct rbl_ctx {
     bool on = false;
     int n = 0;                                      // grid points (0: never set)
     double lo = 0.0, hi = 0.0, dU0 = 0.0;           // dU0: the caller's dU/dx at lo, the slope of the tangent continued below it
+    double U1 = 0.0, dU1 = 0.0;                     // the caller's U and dU/dx at hi (the bond table continues along this tangent too)
     std::vector<double> coef;                       // 4 (n - 1)
   };
   IaTable ia_pt, ia_ht;                             // pair table in r, height table in z
+  IaTable ia_bt;                                    // bond table in the bond length d (kind-1 bonds)
   bool ia_tr_on = false;                            // harmonic traps on the body centres
   std::vector<double> ia_tr_k, ia_tr_X0;            // 3 per body, ia_tr_k.size() / 3 bodies
-  RblDevBuf d_iat;                                  // pair coefficients | height coefficients | trap k | trap X0 (ia_tab_valid)
+  RblDevBuf d_iat;                                  // pair | height | bond coefficients | trap k | trap X0 (ia_tab_valid)
   bool ia_tab_valid = false;
   // permanent dipoles fixed in the bodies, a uniform field B(t) = B0 + B1 cos(omega t) + B2 sin(omega t) and its clock
   bool ia_dp_on = false;
@@ -226,6 +228,17 @@ struct rbl_ctx {
   std::vector<double> ia_ft = std::vector<double>(1, 0.0);   // field time: one entry, or one per replica
   RblDevBuf d_iam;                                  // body-frame moments | field times
   bool ia_mag_valid = false, ia_ft_valid = false;   // d_iam holds the current moments / the current field times
+  // bonds and tethers between anchor points fixed in the bodies (topology and anchors shared by the replicas of an ensemble)
+  bool ia_bd_on = false;
+  int ia_bd_n = 0, ia_bd_sets = 0;                  // bonds (0: never set), parameter sets (1, or one per replica)
+  int ia_bd_top = -1;                               // the largest body index a bond names (checked against N_bod at evaluation)
+  int ia_bd_tab = -1;                               // the first tabulated (kind 1) bond, -1: none (it needs a bond table that is on)
+  std::vector<int> ia_bd_body, ia_bd_kind;          // 2 per bond (second -1: a lab point) / 1 per bond (0 harmonic, 1 tabulated)
+  std::vector<double> ia_bd_anchor, ia_bd_param;    // 6 per bond (s_A | s_B or P) / (k, l0) per bond, set-major
+  std::vector<int> ia_bd_rows, ia_bd_ptr, ia_bd_ends;   // CSR of bond ends by body: bonded bodies, row starts, (partner, bond, end) per entry
+  RblDevBuf d_iab;                                  // anchors | parameters | kinds | bodies | rows | row starts | ends (ia_bd_valid)
+  bool ia_bd_valid = false;
+  RblDevBuf d_iabs;                                 // the state queries' length | tension | energy
   RblDevBuf d_ia;                                   // f_blob | energy per blob | neighbour counts | lists | pairs per blob
   int ia_nb = 0, ia_nblb = 0, ia_cap = 0;           // shape of what d_ia holds (0: nothing evaluated yet)
   // ensemble of independent replicas (rbl_ensemble.hip; include/rbl.h section 5)

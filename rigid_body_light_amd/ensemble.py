@@ -13,7 +13,7 @@ vectors within 150 KB of LDS, about 75 N_blobs + 60 N_bod doubles: 49 tetrahedra
 """
 import numpy as np
 
-from ._lib import RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError, check_brownian_mask6
+from ._lib import RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError, blob_anchor, bond_args, check_brownian_mask6
 
 
 def _fail(message):
@@ -26,6 +26,7 @@ class Ensemble:
         if template.size % 3:
             _fail("rigid_config must have length 3 N_blb; got shape %s" % (template.shape,))
         self.blobs_per_body = template.size // 3
+        self._cfg = template.reshape(-1, 3).copy()
         self._a = float(a)
         stream = None
         try:
@@ -319,6 +320,30 @@ class Ensemble:
 
     def field_time(self):
         return self.ctx.field_time()
+
+    def set_bonds(self, body, anchor_a, anchor_b, k, l0=0.0, kind=None, on=True):
+        """the bonds and tethers of RigidBody.set_bonds, for every replica: the topology (body, kind) and the anchors are shared,
+        indices are local to a replica and replicas never bond to each other.  k, l0: a number or (n_bonds,), shared, or
+        (R, n_bonds): a stiffness or rest-length sweep with one set per replica"""
+        if body is None and not on:
+            return self.ctx.set_bonds(None, None, None, None, on=False)
+        b, anchor, kind, param = bond_args("set_bonds", body, anchor_a, anchor_b, k, l0, kind, sets=(1, self.R))
+        self.ctx.set_bonds(b, anchor[:, :3], anchor[:, 3:], param[:, :, 0], param[:, :, 1], kind=kind, on=on)
+
+    def bonds(self):
+        return self.ctx.bonds()
+
+    def set_bond_table(self, U, dU, r_min, r_cut, on=True):
+        """the potential of the kind-1 bonds of RigidBody.set_bond_table, one for all replicas"""
+        self.ctx.set_bond_table(U, dU, r_min, r_cut, on=on)
+
+    def bond_state(self):
+        """-> (length, tension dU/dd, energy) of every bond of every replica, (R, n_bonds) each"""
+        return self.ctx.ensemble_bond_state()
+
+    def blob_anchor(self, k):
+        """body-frame position of blob k with the structure's mean removed: the anchor of a bond that ends on that blob"""
+        return blob_anchor(self._cfg, k)
 
     def interaction_forces(self):
         """body forces and torques of the model, (R, 6 N_bod), reference convention (-K^T f_phys)"""

@@ -21,7 +21,7 @@ and an imposed flow, a body-frame slip and stresslets (`set_background_flow`, `s
 import numpy as np
 
 from . import c_rigid as _ext
-from ._lib import check_brownian_mask6, dipole_args, field_args, table_arrays, tabulate  # noqa: F401
+from ._lib import blob_anchor, bond_args, check_brownian_mask6, dipole_args, field_args, table_arrays, tabulate  # noqa: F401
 
 _KBT_IN_WRAPPER = 1.0   # the reference wrapper passes kBT = 1 whatever the caller wants (src/Rigid.py:23)
 
@@ -42,6 +42,7 @@ class RigidBody:
         self.cb = _ext.CManyBodies()
         self.precision = self.cb.precision
         self.blobs_per_body = template.size // 3
+        self._cfg = np.array(template, dtype=np.float64).reshape(-1, 3)
         self._a = a                          # (the force model's default cutoff)
         self._wall = bool(wall_PC)
         self.cb.setParameters(a, dt, _KBT_IN_WRAPPER, eta, template.reshape(self.blobs_per_body, 3))
@@ -278,6 +279,34 @@ class RigidBody:
 
     def field_time(self):
         return float(self.cb.field_time()[0])
+
+    def set_bonds(self, body, anchor_a, anchor_b, k, l0=0.0, kind=None, on=True):
+        """Bonds and tethers between anchor points fixed in the bodies (include/rbl.h section 4).  body: (n_bonds, 2) integers;
+        bond b joins the point X_i + R(Q_i) anchor_a[b] of body i = body[b, 0] to the same kind of point of body j = body[b, 1]
+        != i or, with j = -1, to the lab-frame point anchor_b[b] (a tether).  Anchors are body-frame vectors from the body's
+        centre ((3,): every bond alike, or (n_bonds, 3); `blob_anchor(k)` ends a bond on blob k).  kind 0 (default): harmonic,
+        U = k (d - l0)^2 / 2; kind 1: U = k T(d) with the table of set_bond_table.  k, l0: a number or (n_bonds,).  One bond is a
+        ball joint, two a hinge, three non-collinear ones a stiff joint.  The bonds enter the body forces and torques of every
+        step at q^n.  body=None with on=False only switches them off."""
+        if body is None and not on:
+            return self.cb.set_bonds(None, None, None, None, False)
+        b, anchor, kind, param = bond_args("set_bonds", body, anchor_a, anchor_b, k, l0, kind, sets=(1,))
+        self.cb.set_bonds(b.reshape(-1), anchor.reshape(-1), kind, param.reshape(-1), bool(on))
+
+    def set_bond_table(self, U, dU, r_min, r_cut, on=True):
+        """The potential T(d) of the kind-1 bonds: values U and derivatives dU = dU/dd on the uniform grid r_min .. r_cut
+        (`tabulate` makes them from callables).  Cubic Hermite inside the grid, continued along its tangent at BOTH ends: a bond
+        never breaks.  FENE, worm-like chain, Morse, ..."""
+        U, dU = table_arrays("set_bond_table", U, dU)
+        self.cb.set_bond_table(U, dU, float(r_min), float(r_cut), bool(on))
+
+    def bond_state(self):
+        """-> (length, tension dU/dd, energy) of every bond at the current configuration, (n_bonds,) each"""
+        return tuple(self.cb.bond_state())
+
+    def blob_anchor(self, k):
+        """Body-frame position of blob k with the structure's mean removed: the anchor of a bond that ends on that blob."""
+        return blob_anchor(self._cfg, k)
 
     def interaction_forces(self):
         """The model's body forces and torques at the current configuration, 6 * N_bodies, in the reference convention
