@@ -348,7 +348,9 @@ int rbl_gmres_saddle_multi(rbl_ctx *ctx, const double *rhs, int nrhs, int max_it
  *       of the last two / three solutions), then evolve_X_Q(U).
  *   rbl_step_brownian: stochastic midpoint step -- RHS_and_Midpoint at q^n (W = [W1|W2|W_rfd] host, or NULL for
  *       seeded device noise; method RBL_MHALF_*), saddle solve at q^{n+1/2}, update from q^n.
- * F_body: host, 6 N_bod; slip: host, 3 N_blobs.  iters / resid report the GMRES run. */
+ * F_body: host, 6 N_bod; slip: host, 3 N_blobs.  iters / resid report the GMRES run.
+ * Joints set with rbl_set_joints (section 9) are IGNORED by both, as by every entry point outside section 9: only
+ * rbl_solve_jointed / rbl_step_jointed impose them. */
 int rbl_step_deterministic(rbl_ctx *ctx, const double *F_body, const double *slip, int max_iter, double rtol,
                            int warm_start, int *iters, double *resid);
 int rbl_step_brownian(rbl_ctx *ctx, const double *F_body, const double *slip, const double *W, uint64_t seed,
@@ -1130,7 +1132,7 @@ int rbl_step_brownian_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed6, const 
  *
  * Where it enters: the term is added to the slip at q^n -- the configuration the step starts from, where the force model is
  * evaluated; for the Brownian steps the one RHS_and_Midpoint is called on -- in every whole-step entry point and nowhere else:
- * rbl_step_deterministic, rbl_step_brownian, rbl_step_mixed, rbl_step_mixed_dof, rbl_step_brownian_mixed,
+ * rbl_step_deterministic, rbl_step_brownian, rbl_step_mixed, rbl_step_mixed_dof, rbl_step_brownian_mixed, rbl_step_jointed,
  * rbl_ensemble_step_deterministic, rbl_ensemble_step_brownian, rbl_ensemble_step_mixed, rbl_ensemble_step_brownian_mixed.  When
  * the caller also passes `slip` the right-hand side holds slip + t, added in that order.  No lower-level entry point adds it
  * (rbl_solve_mixed*, rbl_gmres_saddle*, rbl_RHS_and_Midpoint*, the ensemble solves): for those there are the queries.  With both
@@ -1167,6 +1169,107 @@ int rbl_first_moments_dev(rbl_ctx *ctx, const double *d_lambda, double *d_D);
 int rbl_first_moments(rbl_ctx *ctx, const double *lambda, double *D);
 int rbl_step_moments(rbl_ctx *ctx, double *D);
 int rbl_ensemble_step_moments(rbl_ctx *ctx, double *D);
+
+/* ===================================================================== */
+/* 9. Hard joints (rigid_body_light_amd/csrc/rbl_joints.hip)             */
+/* ===================================================================== */
+/* Ball joints between anchor points fixed in two bodies, or in a body and the lab (a pivot), imposed as CONSTRAINTS of the saddle
+ * solve: the joint forces are unknowns of the same linear system and the constraint holds to the solver's tolerance at any dt.
+ * (The bonds of section 4 are springs: they hold two points together as well as their stiffness allows, and a stiff one limits
+ * dt like any explicit spring.)  The reference has no counterpart.
+ *
+ * Joint j joins the point p_A = X_A + R(Q_A) s_A of body A to the point p_B = X_B + R(Q_B) s_B of body B, or to the lab point P:
+ * the description rbl_set_bonds takes.  body[2 j] = A >= 0, body[2 j + 1] = B >= 0 and different, or -1 for a pivot;
+ * anchor[6 j .. 6 j + 5] = s_A, then s_B or P; s = 0 is the body centre, a blob's body-frame position ends the joint on that
+ * blob.  Each joint has
+ *     its gap          g_j = p_A - p_B,
+ *     three rows       (J U)_j = (u_A + w_A x l_A) - (u_B + w_B x l_B),   l = R(Q) s the lever arms, no B term for a pivot,
+ *     one unknown      phi_j, three components: the joint's force.
+ * In the convention of rbl_step_deterministic (rhs = [slip; -F_body]) the jointed solve is
+ *     M lambda - K U             = slip
+ *     K^T lambda       + J^T phi = -F_body
+ *                    J U         = c
+ * phi is reported in the convention of the F_body argument (that of the F rbl_solve_mixed returns): the load the joints put on
+ * the bodies is J^T phi -- on body A of joint j the force phi_j and the torque l_A x phi_j, on body B the opposite force at l_B --
+ * and rbl_gmres_saddle on [slip; -(F_body + J^T phi)] returns the same lambda and U.  That statement defines the sign.
+ *
+ * One ball joint leaves the two bodies their three relative rotations; two between the same bodies are a hinge about the line
+ * through them, two pivots on one body a hinge to the lab.  A closed hinge carries one redundant row -- both joints hold the
+ * distance between the two anchors, which either body fixes by itself -- and the solver expects it (see "redundant" below).
+ *
+ *   rbl_set_joints   context state, like the bonds: checks first, nothing is stored unless all pass, no device touched.
+ *                    RBL_ERR_ARG with the joint named in rbl_last_error and the previous joints in place for: NULL where an array
+ *                    is needed; n_joints < 1 or > 2048; a body index out of range (body[2 j] < 0, body[2 j + 1] < -1, or, once a
+ *                    configuration is set, either >= N_bod; a set made before any configuration is checked at the solve,
+ *                    RBL_ERR_STATE there); a pivot in the first slot (body[2 j] = -1); both ends on one body; non-finite
+ *                    anchors; more than two joints between the same pair of bodies or more than two pivots on one body (three
+ *                    would constrain nine of six relative coordinates).  on = 0 stores the joints switched off; body = anchor =
+ *                    NULL with on = 0 only switches them off.
+ *   rbl_get_joints   reads them back; any pointer may be NULL.
+ *   rbl_solve_jointed      host arrays, synchronous.  F_body[6 N_bod]; slip[3 N_blobs] or NULL (zero); joint_rhs[3 n_joints], the
+ *                    c above, or NULL (zero); lambda[3 N_blobs], U[6 N_bod], phi[3 n_joints], any may be NULL.  No-restart
+ *                    right-preconditioned GMRES as rbl_gmres_saddle_dev (max_iter <= 255), the vectors longer by 3 n_joints;
+ *                    iters / resid report the run, resid relative to |[slip; -F_body; c]|.
+ *   rbl_solve_jointed_dev  the same with device vectors, on the conditions of rbl_solve_mixed_dev: enqueued on the context's
+ *                    stream, which is drained where the solver drains it (its convergence tests, the check of the factorisation);
+ *                    d_slip, d_joint_rhs and d_lambda may be NULL; no force or flow model is added.
+ *   rbl_step_jointed one deterministic time step: the force model's loads (bonds included, section 4) and the flow model's slip
+ *                    (section 8) at q^n exactly as rbl_step_deterministic adds them, the solve above with
+ *                        c = -(gamma / dt) g(q^n) + joint_velocity,
+ *                    then evolve_X_Q(U).  gamma in [0, 1] (RBL_ERR_ARG otherwise) relaxes the gap: with gamma = 1 the O(dt^2) gap
+ *                    the explicit rotation update leaves is taken out by the next step and does not accumulate, with gamma = 0
+ *                    only the velocities are constrained and the gaps drift.  joint_velocity[3 n_joints] or NULL (zero): the
+ *                    rate at which p_A - p_B is to change -- a pivot that moves with velocity v takes -v, a joint that is pulled
+ *                    apart its opening rate.  phi[3 n_joints] may be NULL.  The step clears the warm-start history of
+ *                    rbl_step_deterministic, as rbl_step_mixed does.
+ *   rbl_joint_state  gap[3 n_joints]: the gaps of the stored joints (on or off) at the context's configuration; phi[3 n_joints]:
+ *                    the joint forces of the last rbl_solve_jointed* / rbl_step_jointed that succeeded with this joint set,
+ *                    RBL_ERR_STATE if there is none.  Host arrays, either may be NULL; synchronous.
+ *
+ * The preconditioner is the exact inverse of the system with M replaced by the context's preconditioner M~ (diagonal or per-body
+ * blocks, with the wall term or the free-space body-frame tables: whatever rbl_set_blk_pc / rbl_set_wall_pc select).  One
+ * application: apply_PC on the (slip, body) part; phi from the joint Schur complement S = J N~^-1 J^T, N~_b^-1 = (NL_b NL_b^T)^-1
+ * the per-body 6 x 6 blocks every preconditioner keeps; apply_PC a second time on (0, J^T phi); the difference.  S has
+ * 3 n_joints rows and couples only joints that share a body; it is stored dense, assembled, factored (the device Cholesky of
+ * rbl_cholesky_lower_dev) and inverted once per solve -- the configuration cannot change inside one -- and applied as one
+ * matrix-vector product per iteration.  Cost beyond the plain solve, per iteration: the second preconditioner application and
+ * three launches over the joints; per solve: O(n_joints^3) for the inverse (profiles/joints.jsonl has the times).
+ * No floating-point atomics anywhere: two calls on the same input give the same bits.
+ *
+ * Redundant joints.  A loop of joints that constrains a relative coordinate twice leaves S singular.  One such row is expected
+ * and dealt with: that of a hinge.  Of two joints between one pair of bodies the combination d . (J U)_1 - d . (J U)_2, d the
+ * unit vector between the two anchors, is the rate of change of |A_1 - A_2|^2 - |B_1 - B_2|^2, which vanishes identically once the
+ * hinge is closed (||A_1 - A_2| - |B_1 - B_2|| <= 1e-6 |A_1 - A_2| is taken as closed; two pivots on one body are always: the lab
+ * points do not move).  For a closed hinge the preconditioner gives that direction of S an eigenvalue of the size of the
+ * others, i.e. applies the pseudo-inverse there; the operator is untouched, GMRES solves the consistent singular system, lambda
+ * and U are the constrained motion and the two phi are determined up to equal and opposite forces along the hinge's axis, which
+ * load neither body (the step's gamma = 1 drives every hinge there: its gaps stay at the O(dt^2) of the rotation update).  A
+ * hinge that is open takes part as it is: its S has an eigenvalue of the order (gap / distance between the anchors)^2 relative
+ * to the others and phi along the axis is determined that badly; a joint_rhs that asks the two anchors' distances to change
+ * differently on the two bodies has no bounded answer.
+ * Any OTHER redundancy -- a closed ring of joints, a joint between two bodies that hinges to the lab already hold, two joints
+ * on one point -- makes the factorisation fail: a pivot d with d^2 <= 1e-14 S_ii counts as lost (two orders above what rounding
+ * leaves of an exactly redundant row), and the call returns RBL_ERR_NOT_SPD with "redundant" in rbl_last_error, no answer, the
+ * configuration untouched (a step does not advance); the context serves a valid joint set afterwards.
+ *
+ * The joints act in the section 9 calls only.  No other entry point changes meaning, launches or results: on a context with
+ * joints set rbl_step_deterministic, rbl_solve_mixed and the rest ignore them.  With the joints switched off, or never set,
+ * rbl_solve_jointed is the plain solve (rbl_gmres_saddle_dev on [slip; -F_body], cold start; joint_rhs and phi are not touched)
+ * and rbl_step_jointed is rbl_step_deterministic with a cold start.
+ *
+ * Not offered, each refused before any device work: contexts with a communicator (RBL_ERR_ARG); contexts that hold an ensemble
+ * (RBL_ERR_STATE; the ensemble entry points of section 5 ignore the joints like every other); and, having no entry point at
+ * all: the jointed solve together with prescribed masks (section 7), lock-step right-hand sides, Brownian steps (the drift of a
+ * constrained suspension has not been derived here), joint kinds other than the ball joint. */
+int rbl_set_joints(rbl_ctx *ctx, int n_joints, const int *body, const double *anchor, int on);
+int rbl_get_joints(const rbl_ctx *ctx, int *n_joints, int *on, int *body, double *anchor);
+int rbl_solve_jointed(rbl_ctx *ctx, const double *F_body, const double *slip, const double *joint_rhs, int max_iter, double rtol,
+                      double *lambda, double *U, double *phi, int *iters, double *resid);
+int rbl_solve_jointed_dev(rbl_ctx *ctx, const double *d_F_body, const double *d_slip, const double *d_joint_rhs, int max_iter,
+                          double rtol, double *d_lambda, double *d_U, double *d_phi, int *iters, double *resid);
+int rbl_step_jointed(rbl_ctx *ctx, const double *F_body, const double *slip, const double *joint_velocity, double gamma, int max_iter,
+                     double rtol, double *phi, int *iters, double *resid);
+int rbl_joint_state(rbl_ctx *ctx, double *gap, double *phi);
 
 #ifdef __cplusplus
 }

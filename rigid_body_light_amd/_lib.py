@@ -100,6 +100,12 @@ def lib():
         L.rbl_set_bond_table.argtypes = L.rbl_set_pair_table.argtypes
         L.rbl_get_bond_table.argtypes = L.rbl_get_pair_table.argtypes
         L.rbl_bond_state.argtypes = L.rbl_ensemble_bond_state.argtypes = [vp, vp, vp, vp]
+        L.rbl_set_joints.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+        L.rbl_get_joints.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp]
+        L.rbl_solve_jointed.argtypes = L.rbl_solve_jointed_dev.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, C.POINTER(C.c_int),
+                                                                         C.POINTER(dbl)]
+        L.rbl_step_jointed.argtypes = [vp, vp, vp, vp, dbl, C.c_int, dbl, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
+        L.rbl_joint_state.argtypes = [vp, vp, vp]
         L.rbl_interaction_forces_dev.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_forces.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
@@ -215,6 +221,14 @@ def bond_args(who, body, anchor_a, anchor_b, k, l0, kind, sets=(1,)):
             raise ValueError("%s: kind must be None or an integer array of shape (%d,); got %s of dtype %s" % (who, n, kind.shape, kind.dtype))
         kind = np.ascontiguousarray(kind, dtype=np.int32)
     return (np.ascontiguousarray(b, dtype=np.int32), np.ascontiguousarray(np.concatenate(anchors, axis=1)), kind, param)
+
+
+def joint_args(who, body, anchor_a, anchor_b):
+    """the checks set_joints can make before the library is called -> contiguous body int32 (n, 2), anchor float64 (n, 6).
+    body: (n, 2) integers (or (2,) for one joint), the second -1 for a lab point; anchor_a, anchor_b: (3,) -- every joint alike --
+    or (n, 3)"""
+    b, anchor, _, _ = bond_args(who, body, anchor_a, anchor_b, 0.0, 0.0, None)
+    return b, anchor
 
 
 def blob_anchor(cfg, k):
@@ -606,6 +620,84 @@ class DeviceContext:
             self._chk(self.L.rbl_get_bonds(self.h, None, None, None, body.ctypes.data, anchor.ctypes.data, kind.ctypes.data, param.ctypes.data))
         return dict(on=bool(on.value), body=body, anchor_a=anchor[:, :3].copy(), anchor_b=anchor[:, 3:].copy(), kind=kind,
                     k=param[:, :, 0].copy(), l0=param[:, :, 1].copy())
+
+    # -- hard joints (include/rbl.h section 9) ---------------------------------------------------------------------------------
+    def set_joints(self, body, anchor_a, anchor_b, on=True):
+        """ball joints between the point X_i + R(Q_i) anchor_a[j] of body i = body[j, 0] and the same kind of point of body
+        body[j, 1] != i, or, with body[j, 1] = -1, the lab point anchor_b[j] (a pivot): constraints of solve_jointed /
+        step_jointed, ignored by every other call.  body=None with on=False only switches them off."""
+        if body is None and not on:
+            return self._chk(self.L.rbl_set_joints(self.h, 0, None, None, 0))
+        b, anchor = joint_args("set_joints", body, anchor_a, anchor_b)
+        self._chk(self.L.rbl_set_joints(self.h, b.shape[0], b.ctypes.data, anchor.ctypes.data, int(bool(on))))
+
+    def joints(self):
+        """{on, body (n, 2), anchor_a (n, 3), anchor_b (n, 3)} (n = 0: never set)"""
+        import numpy as np
+        n, on = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_joints(self.h, C.byref(n), C.byref(on), None, None))
+        body, anchor = np.zeros((n.value, 2), dtype=np.int32), np.zeros((n.value, 6))
+        if n.value:
+            self._chk(self.L.rbl_get_joints(self.h, None, None, body.ctypes.data, anchor.ctypes.data))
+        return dict(on=bool(on.value), body=body, anchor_a=anchor[:, :3].copy(), anchor_b=anchor[:, 3:].copy())
+
+    def _joints_active(self):
+        n, on = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_joints(self.h, C.byref(n), C.byref(on), None, None))
+        return n.value if on.value else 0
+
+    def _jointed_args(self, who, F_body, slip, jv, jname):
+        import numpy as np
+        nb, nl = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), C.byref(nl)))
+        nj = self._joints_active()
+        F = np.ascontiguousarray(F_body, dtype=np.float64).reshape(-1)
+        sl = None if slip is None else np.ascontiguousarray(slip, dtype=np.float64).reshape(-1)
+        jr = None if jv is None else np.ascontiguousarray(jv, dtype=np.float64).reshape(-1)
+        if F.size != 6 * nb.value or (sl is not None and sl.size != 3 * nb.value * nl.value) or (jr is not None and jr.size != 3 * nj):
+            raise ValueError("%s: F_body (6 N_bod), slip (3 N_blobs) or %s (3 n_joints) has the wrong size" % (who, jname))
+        return nb.value, nl.value, nj, F, sl, jr
+
+    def solve_jointed(self, F_body, slip=None, joint_rhs=None, max_iter=100, rtol=1.0e-8):
+        """the saddle solve with the joints as constraints J U = joint_rhs (None: zero); host arrays -> (lambda, U, phi, iterations,
+        residual estimate), phi (3 n_joints) in the convention of F_body: F_body + J^T phi in the plain solve gives the same
+        lambda and U.  Joints off or never set: the plain solve, phi empty."""
+        import numpy as np
+        nb, nl, nj, F, sl, jr = self._jointed_args("solve_jointed", F_body, slip, joint_rhs, "joint_rhs")
+        lam, U, phi = np.empty(3 * nb * nl), np.empty(6 * nb), np.empty(3 * nj)
+        it, res = C.c_int(0), C.c_double(0.0)
+        self._chk(self.L.rbl_solve_jointed(self.h, F.ctypes.data, None if sl is None else sl.ctypes.data,
+                                           None if jr is None or not nj else jr.ctypes.data, int(max_iter), float(rtol), lam.ctypes.data,
+                                           U.ctypes.data, phi.ctypes.data if nj else None, C.byref(it), C.byref(res)))
+        return lam, U, phi, it.value, res.value
+
+    def solve_jointed_dev(self, d_F_body, d_slip, d_joint_rhs, max_iter, rtol, d_lam, d_U, d_phi):
+        """the same on device addresses (d_slip, d_joint_rhs, d_lam may be None / 0) -> (iterations, residual estimate)"""
+        it, res = C.c_int(0), C.c_double(0.0)
+        self._chk(self.L.rbl_solve_jointed_dev(self.h, d_F_body, d_slip or None, d_joint_rhs or None, int(max_iter), float(rtol),
+                                               d_lam or None, d_U, d_phi or None, C.byref(it), C.byref(res)))
+        return it.value, res.value
+
+    def step_jointed(self, F_body, slip=None, joint_velocity=None, gamma=1.0, max_iter=50, rtol=1.0e-8):
+        """one deterministic time step with the joints: J U = -(gamma / dt) gap + joint_velocity -> (phi, iterations, residual
+        estimate)"""
+        import numpy as np
+        nb, nl, nj, F, sl, jr = self._jointed_args("step_jointed", F_body, slip, joint_velocity, "joint_velocity")
+        phi = np.empty(3 * nj)
+        it, res = C.c_int(0), C.c_double(0.0)
+        self._chk(self.L.rbl_step_jointed(self.h, F.ctypes.data, None if sl is None else sl.ctypes.data,
+                                          None if jr is None or not nj else jr.ctypes.data, float(gamma), int(max_iter), float(rtol),
+                                          phi.ctypes.data if nj else None, C.byref(it), C.byref(res)))
+        return phi, it.value, res.value
+
+    def joint_state(self):
+        """-> (gaps p_A - p_B at the context's configuration (n_joints, 3), phi of the last jointed solve or step (n_joints, 3))"""
+        import numpy as np
+        n = C.c_int(0)
+        self._chk(self.L.rbl_get_joints(self.h, C.byref(n), None, None, None))
+        gap, phi = np.zeros((max(n.value, 1), 3)), np.zeros((max(n.value, 1), 3))
+        self._chk(self.L.rbl_joint_state(self.h, gap.ctypes.data, phi.ctypes.data))
+        return gap[:n.value], phi[:n.value]
 
     def set_bond_table(self, U, dU, r_min, r_cut, on=True):
         """the potential T(d) of the kind-1 bonds from its values U and derivatives dU = dU/dd on the uniform grid r_min .. r_cut

@@ -706,6 +706,92 @@ struct CManyBodies {
     check(rc);
     return py::make_tuple(len, ten, en);
   }
+  // hard joints (include/rbl.h section 9).  body: 2 per joint, anchor: 6 per joint; body None only switches the joints off
+  void set_joints(py::object body, py::object anchor, bool on)
+  {
+    if (body.is_none()) { check(rbl_set_joints(ctx, 0, nullptr, nullptr, on ? 1 : 0)); return; }
+    typedef py::array_t<int, py::array::c_style | py::array::forcecast> iarr;
+    iarr b = body.cast<iarr>();
+    darr an = anchor.cast<darr>();
+    const py::ssize_t n = b.size() / 2;
+    if (b.size() % 2 || !n || an.size() != 6 * n) throw std::runtime_error("set_joints: body must hold 2 and anchor 6 entries per joint");
+    check(rbl_set_joints(ctx, (int)n, b.data(), an.data(), on ? 1 : 0));
+  }
+  // -> (on, body (2 n,), anchor (6 n,))
+  py::tuple joints() const
+  {
+    int n = 0, on = 0;
+    rbl_get_joints(ctx, &n, &on, nullptr, nullptr);
+    py::array_t<int> b(2 * (py::ssize_t)n);
+    darr an(6 * (py::ssize_t)n);
+    rbl_get_joints(ctx, nullptr, nullptr, b.mutable_data(), an.mutable_data());
+    return py::make_tuple(on != 0, b, an);
+  }
+  py::ssize_t joints_active() const
+  {
+    int n = 0, on = 0;
+    rbl_get_joints(ctx, &n, &on, nullptr, nullptr);
+    return on ? n : 0;
+  }
+  const double *jointed_args(const char *who, const darr &F, const py::object &slip, const py::object &jv, const char *jname, darr &sl,
+                             darr &jr, const double **jp) const
+  {
+    if (F.size() != 6 * (py::ssize_t)n_bod()) throw std::runtime_error(std::string(who) + ": F_body must have length 6*N_bod");
+    *jp = nullptr;
+    if (!jv.is_none()) {
+      jr = jv.cast<darr>();
+      if (jr.size() != 3 * joints_active()) throw std::runtime_error(std::string(who) + ": " + jname + " must have length 3*n_joints (of the joints that are on)");
+      *jp = jr.size() ? jr.data() : nullptr;
+    }
+    if (slip.is_none()) return nullptr;
+    sl = slip.cast<darr>();
+    if (sl.size() != n3()) throw std::runtime_error(std::string(who) + ": slip must have length 3*N_blobs");
+    return sl.data();
+  }
+  // -> (lambda, U, phi, iterations, residual estimate); phi is empty while the joints are off
+  py::tuple solve_jointed(darr F, py::object slip, py::object joint_rhs, int max_iter, double rtol)
+  {
+    darr sl, jr;
+    const double *jp = nullptr;
+    const double *sp = jointed_args("solve_jointed", F, slip, joint_rhs, "joint_rhs", sl, jr, &jp);
+    darr lam(n3()), U(6 * (py::ssize_t)n_bod()), phi(3 * joints_active());
+    int it = 0, rc; double res = 0.0;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_solve_jointed(ctx, F.data(), sp, jp, max_iter, rtol, lam.mutable_data(), U.mutable_data(), phi.mutable_data(), &it, &res);
+    }
+    check(rc);
+    return py::make_tuple(lam, U, phi, it, res);
+  }
+  // the step -> (phi, iterations, residual estimate)
+  py::tuple step_jointed(darr F, py::object slip, py::object joint_velocity, double gamma, int max_iter, double rtol)
+  {
+    darr sl, jr;
+    const double *jp = nullptr;
+    const double *sp = jointed_args("step_jointed", F, slip, joint_velocity, "joint_velocity", sl, jr, &jp);
+    darr phi(3 * joints_active());
+    int it = 0, rc; double res = 0.0;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_step_jointed(ctx, F.data(), sp, jp, gamma, max_iter, rtol, phi.mutable_data(), &it, &res);
+    }
+    check(rc);
+    return py::make_tuple(phi, it, res);
+  }
+  // (gaps (3 n,), phi of the last jointed solve or step (3 n,))
+  py::tuple joint_state()
+  {
+    int n = 0;
+    rbl_get_joints(ctx, &n, nullptr, nullptr, nullptr);
+    darr gap(3 * (py::ssize_t)n), phi(3 * (py::ssize_t)n);
+    int rc;
+    {
+      py::gil_scoped_release rel;
+      rc = rbl_joint_state(ctx, gap.mutable_data(), phi.mutable_data());
+    }
+    check(rc);
+    return py::make_tuple(gap, phi);
+  }
   int interactions_active() const
   {
     int m = 0;
@@ -867,6 +953,15 @@ PYBIND11_MODULE(c_rigid, m)
       .def("set_bonds", &CManyBodies::set_bonds, py::arg("body"), py::arg("anchor"), py::arg("kind"), py::arg("param"), py::arg("on") = true)
       .def("set_bond_table", &CManyBodies::set_bond_table, py::arg("U"), py::arg("dU"), py::arg("r_min"), py::arg("r_cut"), py::arg("on") = true)
       .def("bond_state", &CManyBodies::bond_state, "(length, tension dU/dd, energy) of every bond")
+      .def("set_joints", &CManyBodies::set_joints, "hard joints: ball joints and pivots imposed by solve_jointed / step_jointed", py::arg("body"),
+           py::arg("anchor"), py::arg("on") = true)
+      .def("joints", &CManyBodies::joints, "(on, body, anchor) of the stored joints")
+      .def("solve_jointed", &CManyBodies::solve_jointed, "the saddle solve with the joints as constraints -> (lambda, U, phi, iterations, residual)",
+           py::arg("F_body"), py::arg("slip") = py::none(), py::arg("joint_rhs") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
+      .def("step_jointed", &CManyBodies::step_jointed, "one deterministic time step with the joints -> (phi, iterations, residual)",
+           py::arg("F_body"), py::arg("slip") = py::none(), py::arg("joint_velocity") = py::none(), py::arg("gamma") = 1.0,
+           py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
+      .def("joint_state", &CManyBodies::joint_state, "(gaps at the current configuration, phi of the last jointed solve or step)")
       .def("interactions_active", &CManyBodies::interactions_active,
            "bit 0 built-in terms, 1 pair table, 2 height table, 3 traps, 4 dipole pairs, 5 field torque, 6 bonds")
       .def("interaction_forces", &CManyBodies::interaction_forces, "force model's body forces/torques, reference convention (-K^T f)")

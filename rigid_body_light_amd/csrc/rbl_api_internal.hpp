@@ -108,11 +108,13 @@ int mhalf_dev_multi(rbl_ctx *c, const double *d_r, int64_t nbl, const double *d_
 // operator and right preconditioner the caller supplies (rbl_mixed.hip).  The shortcuts fused into the ordinary saddle solve
 // (K^T lambda by-product, Gram-Schmidt sums in the product, normalisation folded into the preconditioner, relaxed products) are
 // requests to the library's own operators (RblPcReq, RblSaddleReq): such a solve makes none; the one-kernel solver and the
-// iteration-count memory stay off too.
+// iteration-count memory stay off too.  extra: unknowns the caller's system has behind the 3 N + 6 N_bod of the saddle system (the
+// joint forces of rbl_joints.hip); every vector the callbacks see is that much longer.
 struct RblSolveOps {
   int (*op)(rbl_ctx *c, void *user, const double *d_x, double *d_out);
   int (*pc)(rbl_ctx *c, void *user, const double *d_in, double *d_out);
   void *user;
+  int64_t extra = 0;
 };
 int gmres_core_with_ops(rbl_ctx *c, const RblSolveOps *ops, const double *d_rhs, int max_iter, double rtol, double *d_x, int *iters_out,
                         double *resid_out);

@@ -153,6 +153,10 @@ static const RblBufRow kDevBufs[] = {
     {&rbl_ctx::d_flow_w, RBL_BUF_SCRATCH},        // host forms of section 8: reserved at their start, within one call
     {&rbl_ctx::d_mom, RBL_BUF_PERSIST},           // first moments of the last recording step (mom_nb)
     {&rbl_ctx::d_ens_mom, RBL_BUF_PERSIST},       // the same of the last recording ensemble step (ens_mom_R)
+    {&rbl_ctx::d_jt, RBL_BUF_PERSIST},            // joints: anchors and topology (jt_valid)
+    {&rbl_ctx::d_jtS, RBL_BUF_SCRATCH},           // joint Schur complement and its inverse: reserved once per jointed solve, before it is assembled
+    {&rbl_ctx::d_jtw, RBL_BUF_SCRATCH},           // jointed solve's vectors: reserved once, at the start of each section 9 entry point
+    {&rbl_ctx::d_jtphi, RBL_BUF_PERSIST},         // joint forces of the last jointed solve (jt_phi_valid)
 };
 
 // the poison pattern, on the context's stream; nothing while the stream is being captured into a graph (a capture may not

@@ -265,6 +265,20 @@ struct rbl_ctx {
   bool record_mom = false;                          // RBL_OPT_RECORD_MOMENTS
   RblDevBuf d_mom, d_ens_mom;                       // D_b of the last recording step: 9 N_bod; R 9 N_bod
   int mom_nb = 0, ens_mom_R = 0, ens_mom_nb = 0;    // shapes of what they hold (0: nothing recorded)
+  // hard joints (rbl_joints.hip; include/rbl.h section 9): ball joints between anchor points fixed in two bodies, or a body and the lab
+  bool jt_on = false;
+  int jt_n = 0;                                     // joints (0: never set)
+  int jt_top = -1;                                  // the largest body index a joint names (checked against N_bod at the solve)
+  std::vector<int> jt_body;                         // 2 per joint (second -1: a lab point, a pivot)
+  std::vector<double> jt_anchor;                    // 6 per joint (s_A | s_B or P)
+  std::vector<int> jt_rows, jt_ptr, jt_ends;        // CSR of joint ends by body: jointed bodies, row starts, (joint, end) per entry
+  std::vector<int> jt_mate;                         // 2 per joint: the other joint between the same two bodies (a hinge) or -1, its ends swapped?
+  RblDevBuf d_jt;                                   // anchors | bodies | rows | row starts | ends | mates (jt_valid)
+  bool jt_valid = false;
+  RblDevBuf d_jtS;                                  // per-body N^-1 | joint Schur complement, its factor | its inverse | its diagonal
+  RblDevBuf d_jtw;                                  // a jointed solve's vectors: rhs | x | (0, J^T phi) | its preconditioned image | lever arms and gaps
+  RblDevBuf d_jtphi;                                // phi of the last jointed solve or step (jt_phi_valid), the state query's gaps
+  bool jt_phi_valid = false;
   // lanczos
   int lanczos_max_iter = 100;
   bool lanczos_out_norm = true;  // preconditioned root: final stopping test in the Euclidean norm of the increment (RBL_OPT_LANCZOS_EUCLID_NORM)

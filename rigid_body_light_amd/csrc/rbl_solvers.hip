@@ -139,7 +139,7 @@ static int gmres_core(rbl_ctx *c, const RblSolveOps *ops, const double *d_rhs, i
   // the library's own operators take requests (RblPcReq, RblSaddleReq) and the iteration-count memory is theirs; a caller's take none
   const bool own = !ops;
   const double fsign = gmres_fsign(c);
-  const int64_t nsys = (int64_t)3 * S.N_bod * S.N_blb + (int64_t)6 * S.N_bod;
+  const int64_t nsys = (int64_t)3 * S.N_bod * S.N_blb + (int64_t)6 * S.N_bod + (ops ? ops->extra : 0);   // (a caller's system may be longer)
   const int m = max_iter, ldh = m + 1;
   const size_t vb = sizeof(double) * (size_t)nsys;
   // workspace: V[(m+1)][nsys] | w | z | H[(m+1) x m] column-major | beta | y[m] | partial sums

@@ -21,7 +21,7 @@ and an imposed flow, a body-frame slip and stresslets (`set_background_flow`, `s
 import numpy as np
 
 from . import c_rigid as _ext
-from ._lib import blob_anchor, bond_args, check_brownian_mask6, dipole_args, field_args, table_arrays, tabulate  # noqa: F401
+from ._lib import blob_anchor, bond_args, check_brownian_mask6, dipole_args, field_args, joint_args, table_arrays, tabulate  # noqa: F401
 
 _KBT_IN_WRAPPER = 1.0   # the reference wrapper passes kBT = 1 whatever the caller wants (src/Rigid.py:23)
 
@@ -307,6 +307,59 @@ class RigidBody:
     def blob_anchor(self, k):
         """Body-frame position of blob k with the structure's mean removed: the anchor of a bond that ends on that blob."""
         return blob_anchor(self._cfg, k)
+
+    # -- hard joints (include/rbl.h section 9) -----------------------------------------------------------------------------------
+    def set_joints(self, body, anchor_a, anchor_b, on=True):
+        """Hard joints: ball joints between anchor points fixed in the bodies, imposed as constraints of the saddle solve (the
+        bonds of set_bonds are springs).  The description is set_bonds': body (n_joints, 2) integers; joint j joins the point
+        X_i + R(Q_i) anchor_a[j] of body i = body[j, 0] to the same kind of point of body body[j, 1] != i or, with body[j, 1] = -1,
+        to the lab-frame point anchor_b[j] (a pivot).  Anchors: (3,) -- every joint alike -- or (n_joints, 3); zeros are the body
+        centre, `blob_anchor(k)` is blob k.  One joint leaves the relative rotation free, two between the same bodies are a hinge.
+        Refused (RuntimeError naming the joint): a body index out of range, both ends on one body, a pivot in the first slot,
+        non-finite anchors, a third joint between one pair of bodies or a third pivot on one body.  Only solve_jointed and
+        step_jointed use the joints; every other method ignores them.  body=None with on=False only switches them off."""
+        if body is None and not on:
+            return self.cb.set_joints(None, None, False)
+        b, anchor = joint_args("set_joints", body, anchor_a, anchor_b)
+        self.cb.set_joints(b.reshape(-1), anchor.reshape(-1), bool(on))
+
+    def joints(self):
+        """-> {on, body (n_joints, 2), anchor_a (n_joints, 3), anchor_b (n_joints, 3)} (n_joints = 0: never set)"""
+        on, b, an = self.cb.joints()
+        an = np.asarray(an).reshape(-1, 6)
+        return dict(on=bool(on), body=np.asarray(b).reshape(-1, 2), anchor_a=an[:, :3].copy(), anchor_b=an[:, 3:].copy())
+
+    def _jointed_args(self, F_body, slip, jv, name):
+        F, sl = self._body_in_and_slip(F_body, slip)
+        if jv is not None:
+            jv = np.ascontiguousarray(jv, dtype=np.float64).reshape(-1)
+        return F, sl, jv
+
+    def solve_jointed(self, F_body, slip=None, joint_rhs=None, max_iter=100, rtol=1.0e-8):
+        """The saddle solve with the joints as constraints:  M lambda - K U = slip,  K^T lambda + J^T phi = -F_body,  J U = joint_rhs
+        (None: zero; (n_joints, 3) or flat), (J U)_j the velocity of joint j's point on body A minus that of its point on body B.
+        ONE GMRES solve on the GPU, longer by 3 n_joints unknowns, whose preconditioner inverts the jointed system exactly for
+        the context's block or diagonal M.  -> (lambda, U, phi, iterations, residual estimate).  phi (3 n_joints) is in the
+        convention of F_body: the joints load the bodies with J^T phi, and solve_saddle with F_body + J^T phi returns the same
+        lambda and U.  A joint set whose constraints are redundant raises RuntimeError ("redundant").  With the joints off or
+        never set this is the plain solve and phi is empty."""
+        F, sl, jr = self._jointed_args(F_body, slip, joint_rhs, "joint_rhs")
+        return self.cb.solve_jointed(F, sl, jr, int(max_iter), float(rtol))
+
+    def step_jointed(self, F_body, slip=None, joint_velocity=None, gamma=1.0, max_iter=50, rtol=1.0e-8):
+        """One deterministic time step with the joints: the force model (bonds included) and the flow model at q^n as in
+        step_deterministic, solve_jointed with joint_rhs = -(gamma / dt) gap(q^n) + joint_velocity, then evolve_rigid_bodies(U).
+        gamma in [0, 1]: 1 (default) takes the O(dt^2) gap of the explicit rotation update out in the next step, 0 constrains the
+        velocities only.  joint_velocity (n_joints, 3) or None: the rate of change asked of p_A - p_B (a pivot moving with v: -v).
+        -> (phi, iterations, residual estimate)."""
+        F, sl, jv = self._jointed_args(F_body, slip, joint_velocity, "joint_velocity")
+        return self.cb.step_jointed(F, sl, jv, float(gamma), int(max_iter), float(rtol))
+
+    def joint_state(self):
+        """-> (gaps p_A - p_B of every stored joint at the current configuration (n_joints, 3), phi of the last solve_jointed /
+        step_jointed (n_joints, 3); RuntimeError if there has been none with this joint set)"""
+        gap, phi = self.cb.joint_state()
+        return np.asarray(gap).reshape(-1, 3), np.asarray(phi).reshape(-1, 3)
 
     def interaction_forces(self):
         """The model's body forces and torques at the current configuration, 6 * N_bodies, in the reference convention
