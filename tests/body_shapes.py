@@ -220,3 +220,24 @@ COND_A = {
     ("E4", False): 184,
     ("E4", True): 153,
 }
+
+
+# ---- condition numbers of the JOINTED matrix [M -K 0; K^T 0 J^T; 0 J 0] of tests/joint_oracle.SHAPE_CASES, cond_2, measured by
+# tests/test_joints_shapes_cpu.py (joint_oracle.cond_jointed) and rounded up: the solution bounds 10 cond(A) rtol of
+# tests/test_joints_shapes_gpu.py rest on them.  The cap on these inputs is 1e5
+COND_JOINTED = {
+    "J1w": 319,
+    "J1f": 394,
+    "J2": 720,
+    "J3": 461,
+    "J4": 218,
+    "J5f": 6.07e+03,
+    "J5w": 5.03e+03,
+    "J6f": 715,
+    "J6w": 850,
+    "J7a": 5.82e+04,
+    "J7b": 3.67e+04,
+    "J7c": 1.95e+04,
+    "J7d": 2.36e+04,
+    "J1s": 3.24e+03,            # joint_oracle.step_case: the largest over the three configurations its reference steps solve at
+}
