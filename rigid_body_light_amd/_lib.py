@@ -1,6 +1,9 @@
-"""ctypes view of librbl.so's device-pointer API (include/rbl.h section 3) for callers
-that keep data resident on the GPU (bench.py, dist.py).  torch is used only as the
-owner of device memory and streams; the pointers handed over are raw HIP pointers."""
+"""ctypes binding of librbl.so (include/rbl.h): `DeviceContext` is the ONE Python binding of everything the library has beyond
+the reference's surface -- the force model, tables, traps, dipoles, bonds, joints, the imposed flow and moments, the velocity
+field, prescribed kinematics, ensembles -- in host-array methods, and of the device-pointer API (section 3) for callers that keep
+data resident on the GPU (bench.py, dist.py).  It owns its rbl_ctx, or borrows the one of a `c_rigid.CManyBodies`
+(`DeviceContext.borrow`: how `RigidBody` reaches these methods).  torch is used only as the owner of device memory and
+streams; the pointers handed over are raw HIP pointers."""
 import ctypes as C
 import os
 
@@ -10,13 +13,17 @@ except ImportError:
     _torch = None
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
+IN_PACKAGE_LIB = os.path.join(_HERE, "librbl.so")   # the file c_rigid is linked against (rpath $ORIGIN)
+_LIBS = {}                                          # path -> loaded library
 
 
-def lib():
-    global _LIB
-    if _LIB is None:
-        path = os.environ.get("RBL_LIBRARY") or os.path.join(_HERE, "librbl.so")   # override: A/B kernel builds
+def lib(path=None):
+    """the library at `path` with its argument types declared, loaded once per path.  None: RBL_LIBRARY (A/B kernel builds),
+    else the in-package file"""
+    if path is None:
+        path = os.environ.get("RBL_LIBRARY") or IN_PACKAGE_LIB
+    L = _LIBS.get(path)
+    if L is None:
         if not os.path.exists(path):
             raise ImportError("librbl.so not built; run `python rigid_body_light_amd/build.py`")
         L = C.CDLL(path)
@@ -147,12 +154,29 @@ def lib():
         L.rbl_flow_slip_dev.argtypes = L.rbl_flow_slip.argtypes = L.rbl_ensemble_flow_slip.argtypes = [vp, vp]
         L.rbl_first_moments_dev.argtypes = L.rbl_first_moments.argtypes = [vp, vp, vp]
         L.rbl_step_moments.argtypes = L.rbl_ensemble_step_moments.argtypes = [vp, vp]
-        _LIB = L
-    return _LIB
+        _LIBS[path] = L
+    return L
 
 
 class RblError(RuntimeError):
     pass
+
+
+def _ptr(a):
+    """address of a numpy array, None for None (an argument left out)"""
+    return None if a is None else a.ctypes.data
+
+
+MHALF_METHODS = {"cholesky": 0, "lanczos": 1, "lanczos_pc": 2}   # RBL_MHALF_* of include/rbl.h
+
+
+def mhalf_code(method):
+    """the root method's code from its name; an integer passes through"""
+    if not isinstance(method, str):
+        return int(method)
+    if method not in MHALF_METHODS:
+        raise RuntimeError("M_half_W: method must be 'cholesky', 'lanczos' or 'lanczos_pc'")
+    return MHALF_METHODS[method]
 
 
 def tabulate(U, dU, lo, hi, n):
@@ -311,7 +335,10 @@ class RunResult:
 
 
 class DeviceContext:
-    """Owns one rbl_ctx bound to the current HIP device and a stream."""
+    """One rbl_ctx bound to the current HIP device and a stream: its own, or (`borrow`) somebody else's."""
+
+    _owner = None       # a borrowed view: whoever owns the rbl_ctx, kept alive; the view never destroys the context
+    _borrowed = False
 
     def __init__(self, a, eta, wall, cfg=None, dt=0.0, kBT=1.0, stream_ptr=None):
         import numpy as np
@@ -326,6 +353,22 @@ class DeviceContext:
         self._chk(self.L.rbl_set_wall_pc(self.h, int(bool(wall))))
         self._chk(self.L.rbl_set_stream(self.h, stream_ptr))
         self._stream_ptr = int(stream_ptr or 0)
+
+    @classmethod
+    def borrow(cls, handle, a, cfg, owner=None):
+        """A view of an existing rbl_ctx (handle: its address, `c_rigid.CManyBodies.handle()`) that calls nothing on it: the
+        owner's parameters, wall flag and stream stand, and the owner destroys it.  a, cfg: the blob radius and the structure the
+        owner was given (the default cutoff, blob_anchor).  owner: kept referenced, so the context outlives the view.  The view
+        calls into the in-package library, the one c_rigid is linked against, whatever RBL_LIBRARY says."""
+        import numpy as np
+        self = cls.__new__(cls)
+        self.L = lib(IN_PACKAGE_LIB)
+        self.h = int(handle)
+        self._owner, self._borrowed = owner, True
+        self._a = float(a)
+        self._cfg = np.array(cfg, dtype=np.float64).reshape(-1, 3)
+        self._stream_ptr = 0
+        return self
 
     def _chk(self, rc):
         if rc != 0:
@@ -1151,7 +1194,7 @@ class DeviceContext:
         Wh = None if W is None else np.ascontiguousarray(W, dtype=np.float64).reshape(-1)
         it, res = C.c_int(0), C.c_double(0.0)
         self._chk(self.L.rbl_step_brownian(self.h, F.ctypes.data, None if sl is None else sl.ctypes.data,
-                                           None if Wh is None else Wh.ctypes.data, int(seed), int(method), int(bool(split_rand)),
+                                           None if Wh is None else Wh.ctypes.data, int(seed), mhalf_code(method), int(bool(split_rand)),
                                            float(delta), int(max_iter), float(rtol or 0.0), C.byref(it), C.byref(res)))
         return it.value, res.value
 
@@ -1189,7 +1232,7 @@ class DeviceContext:
         """device-vector form of the reference's RHS_and_Midpoint -> (X_half, Q_half) on the host"""
         import numpy as np
         X = np.zeros(3 * n_bodies); Q = np.zeros(4 * n_bodies)
-        self._chk(self.L.rbl_RHS_and_Midpoint_dev(self.h, dSlip, dForce, dW, seed, method, int(split_rand), delta,
+        self._chk(self.L.rbl_RHS_and_Midpoint_dev(self.h, dSlip, dForce, dW, seed, mhalf_code(method), int(split_rand), delta,
                                                   dRHS, X.ctypes.data, Q.ctypes.data))
         return X.reshape(-1, 3), Q.reshape(-1, 4)
 
@@ -1262,22 +1305,94 @@ class DeviceContext:
         return ni.value, ch.value, wb.value
 
     # -- prescribed kinematics (include/rbl.h section 7) ---------------------------------------------------------------------
+    # The host-array methods: each whole-body / _dof pair is one body that takes `who`, the entry point's name without rbl_, and
+    # `per`, the mask entries per body -- 1, or 6 for a mask per velocity component.
+    def _mixed_host_args(self, who, per, prescribed, body_in, slip, W=None, brownian=False):
+        """-> (mask, N_bod, N_blb, body_in, slip or None, W or None), flat and contiguous"""
+        import numpy as np
+        m, nb, nl = self._mixed_sizes(who, per, prescribed, brownian)
+        bi = np.ascontiguousarray(body_in, dtype=np.float64).reshape(-1)
+        sl = None if slip is None else np.ascontiguousarray(slip, dtype=np.float64).reshape(-1)
+        Wh = None if W is None else np.ascontiguousarray(W, dtype=np.float64).reshape(-1)
+        if bi.size != 6 * nb or (sl is not None and sl.size != 3 * nb * nl) or (Wh is not None and Wh.size != 9 * nb * nl):
+            raise ValueError(who + ": body_in (6 N_bod), slip (3 N_blobs) or W (9 N_blobs) has the wrong size")
+        return m, nb, nl, bi, sl, Wh
+
+    def _solve_mixed(self, who, per, prescribed, body_in, max_iter, rtol, slip):
+        import numpy as np
+        m, nb, nl, bi, sl, _ = self._mixed_host_args(who, per, prescribed, body_in, slip)
+        lam, U, F = np.empty(3 * nb * nl), np.empty(6 * nb), np.empty(6 * nb)
+        it, res = C.c_int(0), C.c_double(0.0)
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, bi.ctypes.data, _ptr(sl), int(max_iter), float(rtol),
+                                                lam.ctypes.data, U.ctypes.data, F.ctypes.data, C.byref(it), C.byref(res)))
+        return lam, U, F, it.value, res.value
+
+    def _step_mixed(self, who, per, prescribed, body_in, max_iter, rtol, slip):
+        import numpy as np
+        m, nb, _, bi, sl, _ = self._mixed_host_args(who, per, prescribed, body_in, slip)
+        F = np.empty(6 * nb)
+        it, res = C.c_int(0), C.c_double(0.0)
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, bi.ctypes.data, _ptr(sl), int(max_iter), float(rtol),
+                                                F.ctypes.data, C.byref(it), C.byref(res)))
+        return F, it.value, res.value
+
+    def _solve_mixed_multi(self, who, per, prescribed, body_in, max_iter, rtol, slip):
+        import numpy as np
+        m, nb, nl = self._mixed_sizes(who, per, prescribed, brownian=False)
+        bi = np.ascontiguousarray(body_in, dtype=np.float64)
+        if bi.ndim != 2 or bi.shape[0] < 1 or bi.shape[1] != 6 * nb:
+            raise ValueError("%s: body_in must have shape (k, 6 N_bod), k >= 1; got %s" % (who, bi.shape))
+        k = bi.shape[0]
+        sl = None if slip is None else np.ascontiguousarray(slip, dtype=np.float64)
+        if sl is not None and sl.shape != (k, 3 * nb * nl):
+            raise ValueError("%s: slip must have shape (k, 3 N_blobs) = (%d, %d); got %s" % (who, k, 3 * nb * nl, sl.shape))
+        lam, U, F = np.empty((k, 3 * nb * nl)), np.empty((k, 6 * nb)), np.empty((k, 6 * nb))
+        it, res = np.zeros(k, dtype=np.int32), np.zeros(k)
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, k, bi.ctypes.data, _ptr(sl), int(max_iter), float(rtol),
+                                                lam.ctypes.data, U.ctypes.data, F.ctypes.data, it.ctypes.data, res.ctypes.data))
+        return lam, U, F, it, res
+
+    def _rhs_and_midpoint_mixed(self, who, per, prescribed, body_in, slip, W, seed, method, split_rand, delta):
+        import numpy as np
+        m, nb, nl, bi, sl, Wh = self._mixed_host_args(who, per, prescribed, body_in, slip, W, brownian=True)
+        s, X, Q = np.empty(3 * nb * nl), np.empty(3 * nb), np.empty(4 * nb)
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, bi.ctypes.data, _ptr(sl), _ptr(Wh), int(seed), mhalf_code(method),
+                                                int(bool(split_rand)), float(delta), s.ctypes.data, X.ctypes.data, Q.ctypes.data))
+        return s, X, Q
+
     def solve_mixed(self, prescribed, body_in, max_iter=100, rtol=1.0e-8, slip=None):
         """bodies with prescribed[b] = 1 move with body_in[b] (a velocity), the others carry body_in[b] as their load; host arrays
         -> (lambda, U, F, iterations, residual estimate)"""
-        import numpy as np
-        m = np.ascontiguousarray(prescribed, dtype=np.uint8).reshape(-1)
-        bi = np.ascontiguousarray(body_in, dtype=np.float64).reshape(-1)
-        sl = None if slip is None else np.ascontiguousarray(slip, dtype=np.float64).reshape(-1)
-        nb, nl = C.c_int(0), C.c_int(0)
-        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), C.byref(nl)))
-        if m.size != nb.value or bi.size != 6 * nb.value or (sl is not None and sl.size != 3 * nb.value * nl.value):
-            raise ValueError("solve_mixed: prescribed (N_bod), body_in (6 N_bod) or slip (3 N_blobs) has the wrong size")
-        lam, U, F = np.empty(3 * nb.value * nl.value), np.empty(6 * nb.value), np.empty(6 * nb.value)
-        it, res = C.c_int(0), C.c_double(0.0)
-        self._chk(self.L.rbl_solve_mixed(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data, int(max_iter),
-                                         float(rtol), lam.ctypes.data, U.ctypes.data, F.ctypes.data, C.byref(it), C.byref(res)))
-        return lam, U, F, it.value, res.value
+        return self._solve_mixed("solve_mixed", 1, prescribed, body_in, max_iter, rtol, slip)
+
+    def solve_mixed_dof(self, prescribed6, body_in, max_iter=100, rtol=1.0e-8, slip=None):
+        """solve_mixed with a mask per velocity component (prescribed6: 6 N_bod entries, in body_in's order)"""
+        return self._solve_mixed("solve_mixed_dof", 6, prescribed6, body_in, max_iter, rtol, slip)
+
+    def step_mixed(self, prescribed, body_in, max_iter=50, rtol=1.0e-8, slip=None):
+        """the solve, then evolve_X_Q(U) -> (F, iterations, residual estimate)"""
+        return self._step_mixed("step_mixed", 1, prescribed, body_in, max_iter, rtol, slip)
+
+    def step_mixed_dof(self, prescribed6, body_in, max_iter=50, rtol=1.0e-8, slip=None):
+        return self._step_mixed("step_mixed_dof", 6, prescribed6, body_in, max_iter, rtol, slip)
+
+    def solve_mixed_multi(self, prescribed, body_in, max_iter=100, rtol=1.0e-8, slip=None):
+        """k right-hand sides under ONE mask in lock step: body_in (k, 6 N_bod), slip None or (k, 3 N_blobs); host arrays
+        -> (lambda (k, 3 N_blobs), U (k, 6 N_bod), F (k, 6 N_bod), iterations (k,), residual estimates (k,))"""
+        return self._solve_mixed_multi("solve_mixed_multi", 1, prescribed, body_in, max_iter, rtol, slip)
+
+    def solve_mixed_dof_multi(self, prescribed6, body_in, max_iter=100, rtol=1.0e-8, slip=None):
+        return self._solve_mixed_multi("solve_mixed_dof_multi", 6, prescribed6, body_in, max_iter, rtol, slip)
+
+    def RHS_and_Midpoint_mixed(self, prescribed, body_in, slip=None, W=None, seed=0, method="cholesky", split_rand=True, delta=1.0e-4):
+        """right-hand side and predictor of the Brownian step with prescribed bodies at q^n, nothing committed; host arrays, W
+        (9 N_blobs: W1 | W2 | W_rfd) or None for seeded device noise -> (s (3 N_blobs), X_half (3 N_bod), Q_half (4 N_bod))"""
+        return self._rhs_and_midpoint_mixed("RHS_and_Midpoint_mixed", 1, prescribed, body_in, slip, W, seed, method, split_rand, delta)
+
+    def RHS_and_Midpoint_mixed_dof(self, prescribed6, body_in, slip=None, W=None, seed=0, method="cholesky", split_rand=True, delta=1.0e-4):
+        """the same with a mask per velocity component, every body's rotation entries all 0 or all 1"""
+        return self._rhs_and_midpoint_mixed("RHS_and_Midpoint_mixed_dof", 6, prescribed6, body_in, slip, W, seed, method, split_rand,
+                                            delta)
 
     def solve_mixed_dev(self, prescribed, d_body_in, d_slip, max_iter, rtol, d_lam, d_U, d_F):
         """the same on device addresses (prescribed: a host array; d_slip, d_lam may be None / 0) -> (iterations, residual estimate)"""
@@ -1330,40 +1445,34 @@ class DeviceContext:
         """solve_mixed_multi_dev with a mask per velocity component (prescribed6: a host array of 6 N_bod entries)"""
         return self._mixed_multi_dev("solve_mixed_dof_multi_dev", 6, prescribed6, nrhs, d_body_in, d_slip, max_iter, rtol, d_lam, d_U, d_F)
 
-    def _mixed_sizes(self, who, per, prescribed):
-        """the mask of a Brownian call -> (mask, N_bod, N_blb).  per = 6: a mask per velocity component, 6 N_bod entries, every
-        body's rotation entries all 0 or all 1"""
+    def _mixed_sizes(self, who, per, prescribed, brownian=True):
+        """the mask of a call -> (mask, N_bod, N_blb).  per = 6: a mask per velocity component, 6 N_bod entries, in a Brownian
+        call every body's rotation entries all 0 or all 1"""
         import numpy as np
         m = np.ascontiguousarray(prescribed, dtype=np.uint8).reshape(-1)
-        nb, nl = C.c_int(0), C.c_int(0)
-        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), C.byref(nl)))
-        if m.size != per * nb.value:
+        nb, nl = self._sizes()
+        if m.size != per * nb:
             raise ValueError(who + (": prescribed6 must have 6 N_bod entries" if per == 6 else ": prescribed must have N_bod entries"))
-        if per == 6:
-            check_brownian_mask6(who, m, nb.value)
-        return m, nb.value, nl.value
+        if per == 6 and brownian:
+            check_brownian_mask6(who, m, nb)
+        return m, nb, nl
 
     def _rhs_and_midpoint_mixed_dev(self, who, per, prescribed, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s):
         import numpy as np
         m, nb, _ = self._mixed_sizes(who, per, prescribed)
         X = np.zeros(3 * nb); Q = np.zeros(4 * nb)
-        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, d_body_in, d_slip or None, d_W or None, int(seed), int(method),
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, d_body_in, d_slip or None, d_W or None, int(seed), mhalf_code(method),
                                                 int(bool(split_rand)), float(delta), d_s, X.ctypes.data, Q.ctypes.data))
         return X.reshape(-1, 3), Q.reshape(-1, 4)
 
     def _step_brownian_mixed(self, who, per, prescribed, body_in, max_iter, rtol, slip, W, seed, method, split_rand, delta):
         import numpy as np
-        m, nb, nl = self._mixed_sizes(who, per, prescribed)
-        bi = np.ascontiguousarray(body_in, dtype=np.float64).reshape(-1)
-        sl = None if slip is None else np.ascontiguousarray(slip, dtype=np.float64).reshape(-1)
-        Wh = None if W is None else np.ascontiguousarray(W, dtype=np.float64).reshape(-1)
-        if bi.size != 6 * nb or (sl is not None and sl.size != 3 * nb * nl) or (Wh is not None and Wh.size != 9 * nb * nl):
-            raise ValueError(who + ": body_in (6 N_bod), slip (3 N_blobs) or W (9 N_blobs) has the wrong size")
+        m, nb, _, bi, sl, Wh = self._mixed_host_args(who, per, prescribed, body_in, slip, W, brownian=True)
         F = np.empty(6 * nb)
         it, res = C.c_int(0), C.c_double(0.0)
-        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, bi.ctypes.data, None if sl is None else sl.ctypes.data,
-                                                None if Wh is None else Wh.ctypes.data, int(seed), int(method), int(bool(split_rand)),
-                                                float(delta), int(max_iter), float(rtol), F.ctypes.data, C.byref(it), C.byref(res)))
+        self._chk(getattr(self.L, "rbl_" + who)(self.h, m.ctypes.data, bi.ctypes.data, _ptr(sl), _ptr(Wh), int(seed), mhalf_code(method),
+                                                int(bool(split_rand)), float(delta), int(max_iter), float(rtol), F.ctypes.data,
+                                                C.byref(it), C.byref(res)))
         return F, it.value, res.value
 
     def RHS_and_Midpoint_mixed_dev(self, prescribed, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s):
@@ -1408,7 +1517,7 @@ class DeviceContext:
         self._chk(self.L.rbl_trmv_lower_dev(self.h, dL, n, dW, dout))
 
     def M_half_W(self, dr, n_blobs, dW, method, dout):
-        self._chk(self.L.rbl_M_half_W_dev(self.h, dr, n_blobs, dW, {"cholesky": 0, "lanczos": 1, "lanczos_pc": 2}[method], dout))
+        self._chk(self.L.rbl_M_half_W_dev(self.h, dr, n_blobs, dW, mhalf_code(method), dout))
 
     def set_lanczos(self, max_iter, tol):
         self._chk(self.L.rbl_set_lanczos(self.h, max_iter, tol))
@@ -1422,9 +1531,9 @@ class DeviceContext:
         self._chk(self.L.rbl_sync_check(self.h))
 
     def close(self):
-        if self.h:
+        if self.h and not self._borrowed:
             self.L.rbl_destroy(self.h)
-            self.h = None
+        self.h = self._owner = None
 
     def __del__(self):
         try:

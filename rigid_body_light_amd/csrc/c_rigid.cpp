@@ -2,6 +2,9 @@
 // same Python-visible names as the reference's nanobind module
 // (reference src/c_rigid_obj.cpp:997-1027).  It is a thin shim: every method
 // calls one extern "C" entry point of include/rbl.h (librbl.so) and nothing else.
+// It binds what the reference binds plus the solver and stepping methods below; everything
+// newer (include/rbl.h sections 4, 6-9) is bound ONCE, in ctypes, by _lib.DeviceContext, which
+// borrows this object's context through handle().  Add no method here for a new capability.
 //
 // Differences a caller can observe (all listed in DESIGN.md):
 //   * multi_body_pos() returns a numpy array instead of a Python list (the
@@ -416,459 +419,6 @@ struct CManyBodies {
     check(rbl_evolve_X_Q_RFD(ctx, U.data()));
   }
 
-  // configuration-dependent forces (include/rbl.h section 4; the reference has none)
-  // fluid velocity at points[3P] from blob forces lambda[3N] on blobs r_vecs[3N] (None: the object's own blobs)
-  darr velocity_field(darr points, darr lambda, py::object r_vecs)
-  {
-    if (points.size() % 3 != 0 || lambda.size() % 3 != 0) throw std::runtime_error("velocity_field: points and lambda must have length 3P, 3N");
-    darr r;
-    const bool own = r_vecs.is_none();
-    if (!own) {
-      r = darr::ensure(r_vecs);
-      if (!r || r.size() != lambda.size()) throw std::runtime_error("velocity_field: r_vecs and lambda must be of the same size");
-    }
-    darr out(points.size());
-    int rc;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_velocity_field(ctx, points.data(), (int64_t)(points.size() / 3), lambda.data(), own ? nullptr : r.data(),
-                              (int64_t)(lambda.size() / 3), out.mutable_data());
-    }
-    check(rc);
-    return out;
-  }
-  // prescribed kinematics (include/rbl.h section 7): mask[N_bod] 0/1, body_in[6 N_bod] loads of the free bodies / velocities of the
-  // prescribed ones -> (lambda, U, F, iterations, residual estimate).  per: mask entries per body, 1, or 6 for a mask per velocity
-  // component in body_in's order (the _dof methods, which call the _dof entry points); one body serves each pair of methods
-  using marr = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>;
-  [[noreturn]] static void bad_mixed_arg(int per, const std::string &msg)   // the whole-body methods raise RuntimeError, the _dof ones ValueError
-  {
-    if (per == 6) throw py::value_error(msg);
-    throw std::runtime_error(msg);
-  }
-  const double *mixed_args(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip, darr &sl) const
-  {
-    if (mask.size() != per * (py::ssize_t)n_bod())
-      bad_mixed_arg(per, std::string(who) + (per == 6 ? ": prescribed must have length 6*N_bod" : ": prescribed must have length N_bod"));
-    if (body_in.size() != 6 * (py::ssize_t)n_bod()) bad_mixed_arg(per, std::string(who) + ": body_in must have length 6*N_bod");
-    if (slip.is_none()) return nullptr;
-    sl = slip.cast<darr>();
-    if (sl.size() != n3()) bad_mixed_arg(per, std::string(who) + ": slip must have length 3*N_blobs");
-    return sl.data();
-  }
-  py::tuple solve_mixed_any(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip, int max_iter, double rtol)
-  {
-    darr sl;
-    const double *sp = mixed_args(who, per, mask, body_in, slip, sl);
-    darr lam(n3()), U(6 * (py::ssize_t)n_bod()), F(6 * (py::ssize_t)n_bod());
-    int it = 0, rc; double res = 0.0;
-    {
-      py::gil_scoped_release rel;
-      rc = (per == 6 ? rbl_solve_mixed_dof : rbl_solve_mixed)(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, lam.mutable_data(),
-                                                              U.mutable_data(), F.mutable_data(), &it, &res);
-    }
-    check(rc);
-    return py::make_tuple(lam, U, F, it, res);
-  }
-  // the solve, then evolve_X_Q(U) -> (F, iterations, residual estimate)
-  py::tuple step_mixed_any(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip, int max_iter, double rtol)
-  {
-    darr sl;
-    const double *sp = mixed_args(who, per, mask, body_in, slip, sl);
-    darr F(6 * (py::ssize_t)n_bod());
-    int it = 0, rc; double res = 0.0;
-    {
-      py::gil_scoped_release rel;
-      rc = (per == 6 ? rbl_step_mixed_dof : rbl_step_mixed)(ctx, mask.data(), body_in.data(), sp, max_iter, rtol, F.mutable_data(), &it, &res);
-    }
-    check(rc);
-    return py::make_tuple(F, it, res);
-  }
-  py::tuple solve_mixed(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
-  {
-    return solve_mixed_any("solve_mixed", 1, mask, body_in, slip, max_iter, rtol);
-  }
-  py::tuple step_mixed(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
-  {
-    return step_mixed_any("step_mixed", 1, mask, body_in, slip, max_iter, rtol);
-  }
-  py::tuple solve_mixed_dof(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
-  {
-    return solve_mixed_any("solve_mixed_dof", 6, mask, body_in, slip, max_iter, rtol);
-  }
-  py::tuple step_mixed_dof(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
-  {
-    return step_mixed_any("step_mixed_dof", 6, mask, body_in, slip, max_iter, rtol);
-  }
-  // k right-hand sides under one mask in lock step (rbl_solve_mixed_multi, rbl_solve_mixed_dof_multi): body_in (k, 6 N_bod), slip None
-  // or (k, 3 N_blobs) -> (lambda (k, 3 N_blobs), U (k, 6 N_bod), F (k, 6 N_bod), iterations (k,), residual estimates (k,))
-  py::tuple solve_mixed_multi_any(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip, int max_iter,
-                                  double rtol)
-  {
-    const py::ssize_t nb6 = 6 * (py::ssize_t)n_bod();
-    if (mask.size() != per * (py::ssize_t)n_bod())
-      throw py::value_error(std::string(who) + (per == 6 ? ": prescribed must have length 6*N_bod" : ": prescribed must have length N_bod"));
-    if (body_in.ndim() != 2 || body_in.shape(0) < 1 || body_in.shape(1) != nb6)
-      throw py::value_error(std::string(who) + ": body_in must have shape (k, 6*N_bod), k >= 1");
-    const py::ssize_t k = body_in.shape(0);
-    darr sl;
-    const double *sp = nullptr;
-    if (!slip.is_none()) {
-      sl = slip.cast<darr>();
-      if (sl.ndim() != 2 || sl.shape(0) != k || sl.shape(1) != n3()) throw py::value_error(std::string(who) + ": slip must have shape (k, 3*N_blobs)");
-      sp = sl.data();
-    }
-    darr lam({k, (py::ssize_t)n3()}), U({k, nb6}), F({k, nb6}), res(k);
-    py::array_t<int> it(k);
-    int rc;
-    {
-      py::gil_scoped_release rel;
-      rc = (per == 6 ? rbl_solve_mixed_dof_multi : rbl_solve_mixed_multi)(ctx, mask.data(), (int)k, body_in.data(), sp, max_iter, rtol,
-                                                                          lam.mutable_data(), U.mutable_data(), F.mutable_data(),
-                                                                          it.mutable_data(), res.mutable_data());
-    }
-    check(rc);
-    return py::make_tuple(lam, U, F, it, res);
-  }
-  py::tuple solve_mixed_multi(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
-  {
-    return solve_mixed_multi_any("solve_mixed_multi", 1, mask, body_in, slip, max_iter, rtol);
-  }
-  py::tuple solve_mixed_dof_multi(marr mask, darr body_in, py::object slip, int max_iter, double rtol)
-  {
-    return solve_mixed_multi_any("solve_mixed_dof_multi", 6, mask, body_in, slip, max_iter, rtol);
-  }
-  // the Brownian midpoint step with prescribed bodies: right-hand side and predictor at q^n -> (s, X_half, Q_half), nothing committed
-  const double *noise_arg(const char *who, const py::object &W, darr &Wa) const
-  {
-    if (W.is_none()) return nullptr;
-    Wa = W.cast<darr>();
-    if (Wa.size() != 3 * n3()) throw std::runtime_error(std::string(who) + ": W must have length 9*N_blobs (W1|W2|W_rfd)");
-    return Wa.data();
-  }
-  py::tuple RHS_and_Midpoint_mixed_any(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip,
-                                       const py::object &W, uint64_t seed, const std::string &method, bool split_rand, double delta)
-  {
-    darr sl, Wa;
-    const double *sp = mixed_args(who, per, mask, body_in, slip, sl);
-    const double *wp = noise_arg(who, W, Wa);
-    const int m = mhalf_method(method);
-    const py::ssize_t nb = n_bod();
-    darr s(n3()), X(3 * nb), Q(4 * nb);
-    int rc;
-    {
-      py::gil_scoped_release rel;
-      rc = (per == 6 ? rbl_RHS_and_Midpoint_mixed_dof : rbl_RHS_and_Midpoint_mixed)(ctx, mask.data(), body_in.data(), sp, wp, seed, m,
-                                                                                    split_rand ? 1 : 0, delta, s.mutable_data(),
-                                                                                    X.mutable_data(), Q.mutable_data());
-    }
-    check(rc);
-    return py::make_tuple(s, X, Q);
-  }
-  // the whole step -> (F, iterations, residual estimate)
-  py::tuple step_brownian_mixed_any(const char *who, int per, const marr &mask, const darr &body_in, const py::object &slip,
-                                    const py::object &W, uint64_t seed, const std::string &method, bool split_rand, double delta,
-                                    int max_iter, double rtol)
-  {
-    darr sl, Wa;
-    const double *sp = mixed_args(who, per, mask, body_in, slip, sl);
-    const double *wp = noise_arg(who, W, Wa);
-    const int m = mhalf_method(method);
-    darr F(6 * (py::ssize_t)n_bod());
-    int it = 0, rc; double res = 0.0;
-    {
-      py::gil_scoped_release rel;
-      rc = (per == 6 ? rbl_step_brownian_mixed_dof : rbl_step_brownian_mixed)(ctx, mask.data(), body_in.data(), sp, wp, seed, m,
-                                                                              split_rand ? 1 : 0, delta, max_iter, rtol, F.mutable_data(),
-                                                                              &it, &res);
-    }
-    check(rc);
-    return py::make_tuple(F, it, res);
-  }
-  py::tuple RHS_and_Midpoint_mixed(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
-                                   bool split_rand, double delta)
-  {
-    return RHS_and_Midpoint_mixed_any("RHS_and_Midpoint_mixed", 1, mask, body_in, slip, W, seed, method, split_rand, delta);
-  }
-  py::tuple step_brownian_mixed(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
-                                bool split_rand, double delta, int max_iter, double rtol)
-  {
-    return step_brownian_mixed_any("step_brownian_mixed", 1, mask, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol);
-  }
-  py::tuple RHS_and_Midpoint_mixed_dof(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
-                                       bool split_rand, double delta)
-  {
-    return RHS_and_Midpoint_mixed_any("RHS_and_Midpoint_mixed_dof", 6, mask, body_in, slip, W, seed, method, split_rand, delta);
-  }
-  py::tuple step_brownian_mixed_dof(marr mask, darr body_in, py::object slip, py::object W, uint64_t seed, const std::string &method,
-                                    bool split_rand, double delta, int max_iter, double rtol)
-  {
-    return step_brownian_mixed_any("step_brownian_mixed_dof", 6, mask, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol);
-  }
-  void set_interactions(double w, double eps_wall, double b_wall, double eps_blob, double b_blob, double r_cut, bool on)
-  {
-    check(rbl_set_interactions(ctx, w, eps_wall, b_wall, eps_blob, b_blob, r_cut, on ? 1 : 0));
-  }
-  void set_pair_table(darr U, darr dU, double r_min, double r_cut, bool on)
-  {
-    if (U.ndim() != 1 || dU.ndim() != 1 || U.size() != dU.size()) throw std::runtime_error("set_pair_table: U and dU must be one-dimensional and of one length");
-    check(rbl_set_pair_table(ctx, U.data(), dU.data(), (int)U.size(), r_min, r_cut, on ? 1 : 0));
-  }
-  void set_height_table(darr U, darr dU, double h_min, double h_cut, bool on)
-  {
-    if (U.ndim() != 1 || dU.ndim() != 1 || U.size() != dU.size()) throw std::runtime_error("set_height_table: U and dU must be one-dimensional and of one length");
-    check(rbl_set_height_table(ctx, U.data(), dU.data(), (int)U.size(), h_min, h_cut, on ? 1 : 0));
-  }
-  void set_traps(darr k, darr X0, bool on)
-  {
-    if (k.size() != X0.size() || k.size() % 3 || !k.size()) throw std::runtime_error("set_traps: k and X0 must both hold 3 entries per body");
-    check(rbl_set_traps(ctx, k.data(), X0.data(), (int)(k.size() / 3), on ? 1 : 0));
-  }
-  // m: 3 entries per body; None with on = false only switches the dipoles off
-  void set_dipoles(py::object m, double c_dd, double r_core, double r_cut, bool on)
-  {
-    if (m.is_none()) { check(rbl_set_dipoles(ctx, nullptr, 0, c_dd, r_core, r_cut, on ? 1 : 0)); return; }
-    darr ma = m.cast<darr>();
-    if (ma.size() % 3 || !ma.size()) throw std::runtime_error("set_dipoles: m_body must hold 3 entries per body");
-    check(rbl_set_dipoles(ctx, ma.data(), (int)(ma.size() / 3), c_dd, r_core, r_cut, on ? 1 : 0));
-  }
-  py::dict dipoles() const
-  {
-    int n = 0, on = 0;
-    double c_dd = 0.0, r_core = 0.0, r_cut = 0.0;
-    rbl_get_dipoles(ctx, &n, &c_dd, &r_core, &r_cut, &on, nullptr);
-    darr m(std::vector<py::ssize_t>{(py::ssize_t)n, 3});
-    if (n) rbl_get_dipoles(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, m.mutable_data());
-    py::dict d;
-    d["on"] = on != 0; d["c_dd"] = c_dd; d["r_core"] = r_core; d["r_cut"] = r_cut; d["m_body"] = m;
-    return d;
-  }
-  void set_magnetic_field(py::object B0, py::object B1, py::object B2, double omega, bool on)
-  {
-    if (B0.is_none() && B1.is_none() && B2.is_none()) { check(rbl_set_magnetic_field(ctx, nullptr, nullptr, nullptr, omega, on ? 1 : 0)); return; }
-    darr b[3] = {B0.cast<darr>(), B1.cast<darr>(), B2.cast<darr>()};
-    for (const darr &v : b)
-      if (v.size() != 3) throw std::runtime_error("set_magnetic_field: B0, B1 and B2 must have 3 entries each");
-    check(rbl_set_magnetic_field(ctx, b[0].data(), b[1].data(), b[2].data(), omega, on ? 1 : 0));
-  }
-  py::dict magnetic_field() const
-  {
-    darr B(std::vector<py::ssize_t>{3, 3});
-    double omega = 0.0;
-    int on = 0;
-    rbl_get_magnetic_field(ctx, B.mutable_data(), &omega, &on);
-    py::dict d;
-    d["on"] = on != 0; d["omega"] = omega; d["B"] = B;
-    return d;
-  }
-  void set_field_time(darr t) { check(rbl_set_field_time(ctx, t.data(), (int)t.size())); }
-  darr field_time() const
-  {
-    int n = 0;
-    rbl_get_field_time(ctx, &n, nullptr);
-    darr t(n);
-    rbl_get_field_time(ctx, nullptr, t.mutable_data());
-    return t;
-  }
-  // body: 2 per bond, anchor: 6 per bond, kind: 1 per bond or None, param: (k, l0) per bond; body None only switches the bonds off
-  void set_bonds(py::object body, py::object anchor, py::object kind, py::object param, bool on)
-  {
-    if (body.is_none()) { check(rbl_set_bonds(ctx, 0, nullptr, nullptr, nullptr, nullptr, 0, on ? 1 : 0)); return; }
-    typedef py::array_t<int, py::array::c_style | py::array::forcecast> iarr;
-    iarr b = body.cast<iarr>();
-    darr an = anchor.cast<darr>(), pa = param.cast<darr>();
-    const py::ssize_t n = b.size() / 2;
-    if (b.size() % 2 || !n || an.size() != 6 * n || pa.size() != 2 * n)
-      throw std::runtime_error("set_bonds: body must hold 2, anchor 6 and param 2 entries per bond");
-    iarr ki;
-    if (!kind.is_none()) {
-      ki = kind.cast<iarr>();
-      if (ki.size() != n) throw std::runtime_error("set_bonds: kind must hold one entry per bond");
-    }
-    check(rbl_set_bonds(ctx, (int)n, b.data(), an.data(), kind.is_none() ? nullptr : ki.data(), pa.data(), 1, on ? 1 : 0));
-  }
-  void set_bond_table(darr U, darr dU, double r_min, double r_cut, bool on)
-  {
-    if (U.ndim() != 1 || dU.ndim() != 1 || U.size() != dU.size()) throw std::runtime_error("set_bond_table: U and dU must be one-dimensional and of one length");
-    check(rbl_set_bond_table(ctx, U.data(), dU.data(), (int)U.size(), r_min, r_cut, on ? 1 : 0));
-  }
-  // (length, tension, energy) of every bond
-  py::tuple bond_state()
-  {
-    int n = 0;
-    rbl_get_bonds(ctx, &n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    darr len(n), ten(n), en(n);
-    int rc;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_bond_state(ctx, len.mutable_data(), ten.mutable_data(), en.mutable_data());
-    }
-    check(rc);
-    return py::make_tuple(len, ten, en);
-  }
-  // hard joints (include/rbl.h section 9).  body: 2 per joint, anchor: 6 per joint; body None only switches the joints off
-  void set_joints(py::object body, py::object anchor, bool on)
-  {
-    if (body.is_none()) { check(rbl_set_joints(ctx, 0, nullptr, nullptr, on ? 1 : 0)); return; }
-    typedef py::array_t<int, py::array::c_style | py::array::forcecast> iarr;
-    iarr b = body.cast<iarr>();
-    darr an = anchor.cast<darr>();
-    const py::ssize_t n = b.size() / 2;
-    if (b.size() % 2 || !n || an.size() != 6 * n) throw std::runtime_error("set_joints: body must hold 2 and anchor 6 entries per joint");
-    check(rbl_set_joints(ctx, (int)n, b.data(), an.data(), on ? 1 : 0));
-  }
-  // -> (on, body (2 n,), anchor (6 n,))
-  py::tuple joints() const
-  {
-    int n = 0, on = 0;
-    rbl_get_joints(ctx, &n, &on, nullptr, nullptr);
-    py::array_t<int> b(2 * (py::ssize_t)n);
-    darr an(6 * (py::ssize_t)n);
-    rbl_get_joints(ctx, nullptr, nullptr, b.mutable_data(), an.mutable_data());
-    return py::make_tuple(on != 0, b, an);
-  }
-  py::ssize_t joints_active() const
-  {
-    int n = 0, on = 0;
-    rbl_get_joints(ctx, &n, &on, nullptr, nullptr);
-    return on ? n : 0;
-  }
-  const double *jointed_args(const char *who, const darr &F, const py::object &slip, const py::object &jv, const char *jname, darr &sl,
-                             darr &jr, const double **jp) const
-  {
-    if (F.size() != 6 * (py::ssize_t)n_bod()) throw std::runtime_error(std::string(who) + ": F_body must have length 6*N_bod");
-    *jp = nullptr;
-    if (!jv.is_none()) {
-      jr = jv.cast<darr>();
-      if (jr.size() != 3 * joints_active()) throw std::runtime_error(std::string(who) + ": " + jname + " must have length 3*n_joints (of the joints that are on)");
-      *jp = jr.size() ? jr.data() : nullptr;
-    }
-    if (slip.is_none()) return nullptr;
-    sl = slip.cast<darr>();
-    if (sl.size() != n3()) throw std::runtime_error(std::string(who) + ": slip must have length 3*N_blobs");
-    return sl.data();
-  }
-  // -> (lambda, U, phi, iterations, residual estimate); phi is empty while the joints are off
-  py::tuple solve_jointed(darr F, py::object slip, py::object joint_rhs, int max_iter, double rtol)
-  {
-    darr sl, jr;
-    const double *jp = nullptr;
-    const double *sp = jointed_args("solve_jointed", F, slip, joint_rhs, "joint_rhs", sl, jr, &jp);
-    darr lam(n3()), U(6 * (py::ssize_t)n_bod()), phi(3 * joints_active());
-    int it = 0, rc; double res = 0.0;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_solve_jointed(ctx, F.data(), sp, jp, max_iter, rtol, lam.mutable_data(), U.mutable_data(), phi.mutable_data(), &it, &res);
-    }
-    check(rc);
-    return py::make_tuple(lam, U, phi, it, res);
-  }
-  // the step -> (phi, iterations, residual estimate)
-  py::tuple step_jointed(darr F, py::object slip, py::object joint_velocity, double gamma, int max_iter, double rtol)
-  {
-    darr sl, jr;
-    const double *jp = nullptr;
-    const double *sp = jointed_args("step_jointed", F, slip, joint_velocity, "joint_velocity", sl, jr, &jp);
-    darr phi(3 * joints_active());
-    int it = 0, rc; double res = 0.0;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_step_jointed(ctx, F.data(), sp, jp, gamma, max_iter, rtol, phi.mutable_data(), &it, &res);
-    }
-    check(rc);
-    return py::make_tuple(phi, it, res);
-  }
-  // (gaps (3 n,), phi of the last jointed solve or step (3 n,))
-  py::tuple joint_state()
-  {
-    int n = 0;
-    rbl_get_joints(ctx, &n, nullptr, nullptr, nullptr);
-    darr gap(3 * (py::ssize_t)n), phi(3 * (py::ssize_t)n);
-    int rc;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_joint_state(ctx, gap.mutable_data(), phi.mutable_data());
-    }
-    check(rc);
-    return py::make_tuple(gap, phi);
-  }
-  int interactions_active() const
-  {
-    int m = 0;
-    rbl_interactions_active(ctx, &m);
-    return m;
-  }
-  // the model's body forces in the REFERENCE convention, -K^T f_phys (6 N_bod): add them to F in rhs = [0; -F]
-  darr interaction_forces()
-  {
-    darr out(6 * (py::ssize_t)n_bod());
-    int rc;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_interaction_forces(ctx, nullptr, out.mutable_data(), nullptr);
-    }
-    check(rc);
-    double *o = out.mutable_data();
-    for (py::ssize_t i = 0; i < out.size(); ++i) o[i] = -o[i];
-    return out;
-  }
-  double interaction_energy()
-  {
-    double E = 0.0;
-    check(rbl_interaction_forces(ctx, nullptr, nullptr, &E));
-    return E;
-  }
-
-  // ---- imposed flow and active slip, first moments (include/rbl.h section 8) ----
-  void set_background_flow(darr u0, darr G, bool on)
-  {
-    if (u0.size() != 3 || G.size() != 9) throw std::runtime_error("set_background_flow: u0 must have 3 entries, G 9");
-    check(rbl_set_background_flow(ctx, u0.data(), G.data(), on ? 1 : 0));
-  }
-  void set_body_slip(darr slip_body, py::object scale, bool on)
-  {
-    if (slip_body.size() != (py::ssize_t)3 * n_blb()) throw std::runtime_error("set_body_slip: slip_body must have 3 N_blb entries");
-    darr sc;
-    if (!scale.is_none()) sc = scale.cast<darr>();
-    check(rbl_set_body_slip(ctx, slip_body.data(), scale.is_none() ? nullptr : sc.data(), scale.is_none() ? 0 : (int)sc.size(), on ? 1 : 0));
-  }
-  py::tuple flow_model() const
-  {
-    darr v(12);
-    int f = 0, b = 0;
-    check(rbl_get_flow_model(ctx, v.mutable_data(), &f, &b));
-    return py::make_tuple(v, f != 0, b != 0);
-  }
-  darr flow_slip()
-  {
-    darr out(n3());
-    int rc;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_flow_slip(ctx, out.mutable_data());
-    }
-    check(rc);
-    return out;
-  }
-  darr first_moments(darr lam)
-  {
-    if (lam.size() != n3()) throw std::runtime_error("first_moments: lambda must have 3 N_blobs entries");
-    darr out(9 * (py::ssize_t)n_bod());
-    int rc;
-    {
-      py::gil_scoped_release rel;
-      rc = rbl_first_moments(ctx, lam.data(), out.mutable_data());
-    }
-    check(rc);
-    return out;
-  }
-  darr step_moments()
-  {
-    darr out(9 * (py::ssize_t)n_bod());
-    check(rbl_step_moments(ctx, out.mutable_data()));
-    return out;
-  }
-
   void set_option(const std::string &name, int64_t value)
   {
     const int key = rbl_option_key(name.c_str());
@@ -936,70 +486,6 @@ PYBIND11_MODULE(c_rigid, m)
       .def("M_RFD_from_U", &CManyBodies::M_RFD_from_U, py::arg("U"), py::arg("W"), py::arg("delta") = 1.0e-3)
       .def("KT_RFD_from_U", &CManyBodies::KT_RFD_from_U, py::arg("U"), py::arg("W"), py::arg("delta") = 1.0e-3)
       .def("evolve_X_Q_RFD", &CManyBodies::evolve_X_Q_RFD, py::arg("U"))
-      .def("set_interactions", &CManyBodies::set_interactions, py::arg("w"), py::arg("eps_wall"), py::arg("b_wall"), py::arg("eps_blob"),
-           py::arg("b_blob"), py::arg("r_cut"), py::arg("on") = true)
-      .def("set_pair_table", &CManyBodies::set_pair_table, py::arg("U"), py::arg("dU"), py::arg("r_min"), py::arg("r_cut"), py::arg("on") = true)
-      .def("set_height_table", &CManyBodies::set_height_table, py::arg("U"), py::arg("dU"), py::arg("h_min"), py::arg("h_cut"),
-           py::arg("on") = true)
-      .def("set_traps", &CManyBodies::set_traps, py::arg("k"), py::arg("X0"), py::arg("on") = true)
-      .def("set_dipoles", &CManyBodies::set_dipoles, py::arg("m_body"), py::arg("c_dd"), py::arg("r_core"), py::arg("r_cut"),
-           py::arg("on") = true)
-      .def("dipoles", &CManyBodies::dipoles)
-      .def("set_magnetic_field", &CManyBodies::set_magnetic_field, py::arg("B0"), py::arg("B1"), py::arg("B2"), py::arg("omega"),
-           py::arg("on") = true)
-      .def("magnetic_field", &CManyBodies::magnetic_field)
-      .def("set_field_time", &CManyBodies::set_field_time, py::arg("t"))
-      .def("field_time", &CManyBodies::field_time)
-      .def("set_bonds", &CManyBodies::set_bonds, py::arg("body"), py::arg("anchor"), py::arg("kind"), py::arg("param"), py::arg("on") = true)
-      .def("set_bond_table", &CManyBodies::set_bond_table, py::arg("U"), py::arg("dU"), py::arg("r_min"), py::arg("r_cut"), py::arg("on") = true)
-      .def("bond_state", &CManyBodies::bond_state, "(length, tension dU/dd, energy) of every bond")
-      .def("set_joints", &CManyBodies::set_joints, "hard joints: ball joints and pivots imposed by solve_jointed / step_jointed", py::arg("body"),
-           py::arg("anchor"), py::arg("on") = true)
-      .def("joints", &CManyBodies::joints, "(on, body, anchor) of the stored joints")
-      .def("solve_jointed", &CManyBodies::solve_jointed, "the saddle solve with the joints as constraints -> (lambda, U, phi, iterations, residual)",
-           py::arg("F_body"), py::arg("slip") = py::none(), py::arg("joint_rhs") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
-      .def("step_jointed", &CManyBodies::step_jointed, "one deterministic time step with the joints -> (phi, iterations, residual)",
-           py::arg("F_body"), py::arg("slip") = py::none(), py::arg("joint_velocity") = py::none(), py::arg("gamma") = 1.0,
-           py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
-      .def("joint_state", &CManyBodies::joint_state, "(gaps at the current configuration, phi of the last jointed solve or step)")
-      .def("interactions_active", &CManyBodies::interactions_active,
-           "bit 0 built-in terms, 1 pair table, 2 height table, 3 traps, 4 dipole pairs, 5 field torque, 6 bonds")
-      .def("interaction_forces", &CManyBodies::interaction_forces, "force model's body forces/torques, reference convention (-K^T f)")
-      .def("interaction_energy", &CManyBodies::interaction_energy)
-      .def("velocity_field", &CManyBodies::velocity_field, "fluid velocity at points from blob forces", py::arg("points"),
-           py::arg("lambda"), py::arg("r_vecs") = py::none())
-      .def("solve_mixed", &CManyBodies::solve_mixed, "prescribed kinematics: velocities given on some bodies, loads on the others",
-           py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
-      .def("step_mixed", &CManyBodies::step_mixed, py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(),
-           py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
-      .def("solve_mixed_dof", &CManyBodies::solve_mixed_dof, "prescribed kinematics per velocity component: prescribed has 6 N_bod entries",
-           py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
-      .def("step_mixed_dof", &CManyBodies::step_mixed_dof, py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(),
-           py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
-      .def("solve_mixed_multi", &CManyBodies::solve_mixed_multi, "prescribed kinematics, k right-hand sides under one mask in lock step",
-           py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
-      .def("solve_mixed_dof_multi", &CManyBodies::solve_mixed_dof_multi, "the same with a mask per velocity component (6 N_bod entries)",
-           py::arg("prescribed"), py::arg("body_in"), py::arg("slip") = py::none(), py::arg("max_iter") = 100, py::arg("rtol") = 1.0e-8)
-      .def("RHS_and_Midpoint_mixed", &CManyBodies::RHS_and_Midpoint_mixed, py::arg("prescribed"), py::arg("body_in"),
-           py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "cholesky",
-           py::arg("split_rand") = true, py::arg("delta") = 1.0e-4)
-      .def("step_brownian_mixed", &CManyBodies::step_brownian_mixed, py::arg("prescribed"), py::arg("body_in"),
-           py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "lanczos_pc",
-           py::arg("split_rand") = true, py::arg("delta") = 1.0e-4, py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
-      .def("RHS_and_Midpoint_mixed_dof", &CManyBodies::RHS_and_Midpoint_mixed_dof, py::arg("prescribed"), py::arg("body_in"),
-           py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "cholesky",
-           py::arg("split_rand") = true, py::arg("delta") = 1.0e-4)
-      .def("step_brownian_mixed_dof", &CManyBodies::step_brownian_mixed_dof, py::arg("prescribed"), py::arg("body_in"),
-           py::arg("slip") = py::none(), py::arg("W") = py::none(), py::arg("seed") = 0, py::arg("method") = "lanczos_pc",
-           py::arg("split_rand") = true, py::arg("delta") = 1.0e-4, py::arg("max_iter") = 50, py::arg("rtol") = 1.0e-8)
-      .def("set_background_flow", &CManyBodies::set_background_flow, "u_inf(r) = u0 + G r added to every step's slip as -u_inf",
-           py::arg("u0"), py::arg("G"), py::arg("on") = true)
-      .def("set_body_slip", &CManyBodies::set_body_slip, "slip pattern in the body frame, a factor per body", py::arg("slip_body"),
-           py::arg("scale") = py::none(), py::arg("on") = true)
-      .def("flow_model", &CManyBodies::flow_model, "([u0 | G], flow on, body slip on)")
-      .def("flow_slip", &CManyBodies::flow_slip, "the flow model's term at the current configuration, 3 N_blobs")
-      .def("first_moments", &CManyBodies::first_moments, "D_b = sum (r_i - X_b) lambda_i^T per body, 9 N_bod", py::arg("lambda"))
-      .def("step_moments", &CManyBodies::step_moments, "first moments recorded by the last step (option record_moments)")
       .def("set_option", &CManyBodies::set_option, py::arg("name"), py::arg("value"))
       .def("get_option", &CManyBodies::get_option, py::arg("name"))
       .def("handle", &CManyBodies::handle, "address of the underlying rbl_ctx (for the ctypes device API)")

@@ -2,8 +2,9 @@
 
 `RigidBody` presents the constructor, attributes, methods, output shapes and RuntimeError
 behaviour of the reference's Python wrapper (reference src/Rigid.py:5-135) so that user code written
-against `from Rigid import RigidBody` runs unchanged, but every call lands in librbl.so through the
-pybind11 class `c_rigid.CManyBodies`.  Size rules are kept in one table (`_expected_size`) instead
+against `from Rigid import RigidBody` runs unchanged, but every call lands in librbl.so: the reference's
+surface and the solver and stepping methods through the pybind11 class `c_rigid.CManyBodies` (`self.cb`), everything
+newer through `self.ctx`, a `_lib.DeviceContext` that borrows the same rbl_ctx.  Size rules are kept in one table (`_expected_size`) instead
 of per-method checks; shapes follow the shape X was given in (2-D in -> (-1, 3) out, flat in -> flat out,
 reference src/Rigid.py:54,60,66).
 
@@ -21,7 +22,7 @@ and an imposed flow, a body-frame slip and stresslets (`set_background_flow`, `s
 import numpy as np
 
 from . import c_rigid as _ext
-from ._lib import blob_anchor, bond_args, check_brownian_mask6, dipole_args, field_args, joint_args, table_arrays, tabulate  # noqa: F401
+from ._lib import DeviceContext, blob_anchor, bond_args, check_brownian_mask6, dipole_args, field_args, joint_args, table_arrays, tabulate  # noqa: F401
 
 _KBT_IN_WRAPPER = 1.0   # the reference wrapper passes kBT = 1 whatever the caller wants (src/Rigid.py:23)
 
@@ -46,6 +47,7 @@ class RigidBody:
         self._a = a                          # (the force model's default cutoff)
         self._wall = bool(wall_PC)
         self.cb.setParameters(a, dt, _KBT_IN_WRAPPER, eta, template.reshape(self.blobs_per_body, 3))
+        self.ctx = DeviceContext.borrow(self.cb.handle(), a, template.reshape(self.blobs_per_body, 3), owner=self.cb)
         self.cb.setWallPC(bool(wall_PC))
         self.cb.setBlkPC(bool(block_PC))
         self.set_config(X, Q)
@@ -219,7 +221,7 @@ class RigidBody:
         at the configuration the step starts from; on=False switches the model off."""
         if r_cut is None:
             r_cut = 2.0 * self._a + 20.0 * b_blob
-        self.cb.set_interactions(float(w), float(eps_wall), float(b_wall), float(eps_blob), float(b_blob), float(r_cut), bool(on))
+        self.ctx.set_interactions(w, eps_wall, b_wall, eps_blob, b_blob, r_cut, on)
 
     def set_pair_table(self, U, dU, r_min, r_cut, on=True):
         """A tabulated radial potential between blobs of different bodies (include/rbl.h section 4): values U and derivatives
@@ -227,12 +229,12 @@ class RigidBody:
         Hermite inside the grid, the tangent at r_min below it, nothing beyond r_cut; the table is not shifted, so
         U(r_cut) != 0 is a jump in the energy.  Adds to the steric term of set_interactions."""
         U, dU = table_arrays("set_pair_table", U, dU)
-        self.cb.set_pair_table(U, dU, float(r_min), float(r_cut), bool(on))
+        self.ctx.set_pair_table(U, dU, r_min, r_cut, on)
 
     def set_height_table(self, U, dU, h_min, h_cut, on=True):
         """The same construction in the blob height z over h_min .. h_cut, with or without the wall."""
         U, dU = table_arrays("set_height_table", U, dU)
-        self.cb.set_height_table(U, dU, float(h_min), float(h_cut), bool(on))
+        self.ctx.set_height_table(U, dU, h_min, h_cut, on)
 
     def set_traps(self, k, X0, on=True):
         """Harmonic traps on the body centres: k and X0 of shape (N_bodies, 3), lab frame; a component of k that is 0 leaves
@@ -240,7 +242,7 @@ class RigidBody:
         k, X0 = np.ascontiguousarray(k, dtype=np.float64), np.ascontiguousarray(X0, dtype=np.float64)
         if k.ndim != 2 or k.shape[1] != 3 or k.shape != X0.shape:
             raise ValueError(f"set_traps: k and X0 must both have shape (N_bodies, 3). Got shapes: {k.shape} and {X0.shape}")
-        self.cb.set_traps(k.reshape(-1), X0.reshape(-1), bool(on))
+        self.ctx.set_traps(k, X0, on)
 
     def set_dipoles(self, m_body, c_dd=0.0, r_core=None, r_cut=np.inf, on=True):
         """Permanent magnetic moments fixed in the bodies (include/rbl.h section 4): m_body of shape (3,) -- every body alike --
@@ -248,37 +250,34 @@ class RigidBody:
         centres, U = c_dd [m_i.m_j / s^3 - 3 (m_i.r)(m_j.r) / s^5], s = max(|r|, r_core), skipped beyond r_cut (not shifted);
         set_magnetic_field adds the torque m x B(t).  Both enter the body forces and torques of every step at q^n."""
         if m_body is None and not on:
-            return self.cb.set_dipoles(None, 0.0, 0.0, 0.0, False)
+            return self.ctx.set_dipoles(None, on=False)
         m, r_core = dipole_args("set_dipoles", m_body, c_dd, r_core)
         if m.shape[0] not in (1, self.N_bodies):
             raise ValueError(f"set_dipoles: m_body must have shape (3,) or (N_bodies, 3). Got shape: {m.shape}")
-        self.cb.set_dipoles(m.reshape(-1), float(c_dd), r_core, float(r_cut), bool(on))
+        self.ctx.set_dipoles(m, c_dd, r_core, r_cut, on)
 
     def dipoles(self):
         """{on, c_dd, r_core, r_cut, m_body (n, 3)}"""
-        return dict(self.cb.dipoles())
+        return self.ctx.dipoles()
 
     def set_magnetic_field(self, B0=None, B1=None, B2=None, omega=0.0, on=True):
         """The uniform field B(t) = B0 + B1 cos(omega t) + B2 sin(omega t), lab frame (None: zeros), evaluated at the field
         time of set_field_time -- no step advances that clock.  Torque m x B on every body with a moment, no force."""
         if B0 is None and B1 is None and B2 is None and not on:
-            return self.cb.set_magnetic_field(None, None, None, 0.0, False)
+            return self.ctx.set_magnetic_field(on=False)
         B0, B1, B2 = field_args("set_magnetic_field", B0, B1, B2)
-        self.cb.set_magnetic_field(B0, B1, B2, float(omega), bool(on))
+        self.ctx.set_magnetic_field(B0, B1, B2, float(omega), bool(on))
 
     def magnetic_field(self):
         """{on, omega, B0, B1, B2}"""
-        d = dict(self.cb.magnetic_field())
-        B = d.pop("B")
-        d.update(B0=B[0].copy(), B1=B[1].copy(), B2=B[2].copy())
-        return d
+        return self.ctx.magnetic_field()
 
     def set_field_time(self, t):
         """The time the field is evaluated at by the next steps and queries (default 0); the caller advances it."""
-        self.cb.set_field_time(np.atleast_1d(np.asarray(t, dtype=np.float64)))
+        self.ctx.set_field_time(t)
 
     def field_time(self):
-        return float(self.cb.field_time()[0])
+        return float(self.ctx.field_time()[0])
 
     def set_bonds(self, body, anchor_a, anchor_b, k, l0=0.0, kind=None, on=True):
         """Bonds and tethers between anchor points fixed in the bodies (include/rbl.h section 4).  body: (n_bonds, 2) integers;
@@ -289,20 +288,20 @@ class RigidBody:
         ball joint, two a hinge, three non-collinear ones a stiff joint.  The bonds enter the body forces and torques of every
         step at q^n.  body=None with on=False only switches them off."""
         if body is None and not on:
-            return self.cb.set_bonds(None, None, None, None, False)
+            return self.ctx.set_bonds(None, None, None, None, on=False)
         b, anchor, kind, param = bond_args("set_bonds", body, anchor_a, anchor_b, k, l0, kind, sets=(1,))
-        self.cb.set_bonds(b.reshape(-1), anchor.reshape(-1), kind, param.reshape(-1), bool(on))
+        self.ctx.set_bonds(b, anchor[:, :3], anchor[:, 3:], param[0, :, 0], param[0, :, 1], kind, bool(on))
 
     def set_bond_table(self, U, dU, r_min, r_cut, on=True):
         """The potential T(d) of the kind-1 bonds: values U and derivatives dU = dU/dd on the uniform grid r_min .. r_cut
         (`tabulate` makes them from callables).  Cubic Hermite inside the grid, continued along its tangent at BOTH ends: a bond
         never breaks.  FENE, worm-like chain, Morse, ..."""
         U, dU = table_arrays("set_bond_table", U, dU)
-        self.cb.set_bond_table(U, dU, float(r_min), float(r_cut), bool(on))
+        self.ctx.set_bond_table(U, dU, r_min, r_cut, on)
 
     def bond_state(self):
         """-> (length, tension dU/dd, energy) of every bond at the current configuration, (n_bonds,) each"""
-        return tuple(self.cb.bond_state())
+        return self.ctx.bond_state()
 
     def blob_anchor(self, k):
         """Body-frame position of blob k with the structure's mean removed: the anchor of a bond that ends on that blob."""
@@ -319,20 +318,20 @@ class RigidBody:
         non-finite anchors, a third joint between one pair of bodies or a third pivot on one body.  Only solve_jointed and
         step_jointed use the joints; every other method ignores them.  body=None with on=False only switches them off."""
         if body is None and not on:
-            return self.cb.set_joints(None, None, False)
+            return self.ctx.set_joints(None, None, None, on=False)
         b, anchor = joint_args("set_joints", body, anchor_a, anchor_b)
-        self.cb.set_joints(b.reshape(-1), anchor.reshape(-1), bool(on))
+        self.ctx.set_joints(b, anchor[:, :3], anchor[:, 3:], bool(on))
 
     def joints(self):
         """-> {on, body (n_joints, 2), anchor_a (n_joints, 3), anchor_b (n_joints, 3)} (n_joints = 0: never set)"""
-        on, b, an = self.cb.joints()
-        an = np.asarray(an).reshape(-1, 6)
-        return dict(on=bool(on), body=np.asarray(b).reshape(-1, 2), anchor_a=an[:, :3].copy(), anchor_b=an[:, 3:].copy())
+        return self.ctx.joints()
 
-    def _jointed_args(self, F_body, slip, jv, name):
+    def _jointed_args(self, who, F_body, slip, jv, name):
         F, sl = self._body_in_and_slip(F_body, slip)
         if jv is not None:
             jv = np.ascontiguousarray(jv, dtype=np.float64).reshape(-1)
+            if jv.size != 3 * self.ctx._joints_active():
+                _fail(f"{who}: {name} must have length 3*n_joints (of the joints that are on)")
         return F, sl, jv
 
     def solve_jointed(self, F_body, slip=None, joint_rhs=None, max_iter=100, rtol=1.0e-8):
@@ -343,8 +342,8 @@ class RigidBody:
         convention of F_body: the joints load the bodies with J^T phi, and solve_saddle with F_body + J^T phi returns the same
         lambda and U.  A joint set whose constraints are redundant raises RuntimeError ("redundant").  With the joints off or
         never set this is the plain solve and phi is empty."""
-        F, sl, jr = self._jointed_args(F_body, slip, joint_rhs, "joint_rhs")
-        return self.cb.solve_jointed(F, sl, jr, int(max_iter), float(rtol))
+        F, sl, jr = self._jointed_args("solve_jointed", F_body, slip, joint_rhs, "joint_rhs")
+        return self.ctx.solve_jointed(F, slip=sl, joint_rhs=jr, max_iter=int(max_iter), rtol=float(rtol))
 
     def step_jointed(self, F_body, slip=None, joint_velocity=None, gamma=1.0, max_iter=50, rtol=1.0e-8):
         """One deterministic time step with the joints: the force model (bonds included) and the flow model at q^n as in
@@ -352,22 +351,21 @@ class RigidBody:
         gamma in [0, 1]: 1 (default) takes the O(dt^2) gap of the explicit rotation update out in the next step, 0 constrains the
         velocities only.  joint_velocity (n_joints, 3) or None: the rate of change asked of p_A - p_B (a pivot moving with v: -v).
         -> (phi, iterations, residual estimate)."""
-        F, sl, jv = self._jointed_args(F_body, slip, joint_velocity, "joint_velocity")
-        return self.cb.step_jointed(F, sl, jv, float(gamma), int(max_iter), float(rtol))
+        F, sl, jv = self._jointed_args("step_jointed", F_body, slip, joint_velocity, "joint_velocity")
+        return self.ctx.step_jointed(F, slip=sl, joint_velocity=jv, gamma=float(gamma), max_iter=int(max_iter), rtol=float(rtol))
 
     def joint_state(self):
         """-> (gaps p_A - p_B of every stored joint at the current configuration (n_joints, 3), phi of the last solve_jointed /
         step_jointed (n_joints, 3); RuntimeError if there has been none with this joint set)"""
-        gap, phi = self.cb.joint_state()
-        return np.asarray(gap).reshape(-1, 3), np.asarray(phi).reshape(-1, 3)
+        return self.ctx.joint_state()
 
     def interaction_forces(self):
         """The model's body forces and torques at the current configuration, 6 * N_bodies, in the reference convention
         (-K^T f_phys): add them to F in rhs = [0 ; -F] of a solve over apply_saddle."""
-        return self.cb.interaction_forces()
+        return -self.ctx.interaction_forces()[1]      # the library's are the physical ones, +K^T f
 
     def interaction_energy(self):
-        return self.cb.interaction_energy()
+        return self.ctx.interaction_energy()
 
     def velocity_field(self, points, blob_forces, positions=None, with_flow=False):
         """Fluid velocity at arbitrary points from blob forces (include/rbl.h section 6): the velocity `apply_M` would give an
@@ -391,7 +389,7 @@ class RigidBody:
             if r.size != lam.size:
                 raise ValueError(f"velocity_field: positions and blob_forces must be of the same size. Got {r.shape} and {lam.shape}")
             r = r.reshape(-1)
-        u = self.cb.velocity_field(pts.reshape(-1), lam.reshape(-1), r)
+        u = self.ctx.velocity_field(pts.reshape(-1), lam.reshape(-1), r)
         if with_flow:
             m = self.flow_model()
             if m["flow_on"]:
@@ -414,7 +412,7 @@ class RigidBody:
             raise ValueError(f"set_background_flow: u0 must have shape (3,). Got shape: {u0.shape}")
         if G.shape != (3, 3):
             raise ValueError(f"set_background_flow: G must have shape (3, 3). Got shape: {G.shape}")
-        self.cb.set_background_flow(u0, np.ascontiguousarray(G).reshape(-1), bool(on))
+        self.ctx.set_background_flow(u0, np.ascontiguousarray(G), bool(on))
 
     def set_body_slip(self, slip_body, scale=None, on=True):
         """Active slip carried by the bodies: slip_body (blobs_per_body, 3) or flat, a pattern in the BODY frame in the units and
@@ -429,17 +427,16 @@ class RigidBody:
             if sc.shape != (self.N_bodies,):
                 raise ValueError(f"set_body_slip: scale must have shape (N_bodies,) = ({self.N_bodies},). Got shape: {sc.shape}")
             sc = np.ascontiguousarray(sc)
-        self.cb.set_body_slip(np.ascontiguousarray(sb).reshape(-1), sc, bool(on))
+        self.ctx.set_body_slip(np.ascontiguousarray(sb).reshape(-1), sc, bool(on))
 
     def flow_model(self):
         """{u0 (3,), G (3, 3), flow_on, body_slip_on} of the context's flow model"""
-        v, f, b = self.cb.flow_model()
-        return {"u0": np.array(v[:3]), "G": np.array(v[3:]).reshape(3, 3), "flow_on": bool(f), "body_slip_on": bool(b)}
+        return self.ctx.flow_model()
 
     def flow_slip(self):
         """The flow model's term at the current configuration, t_i = scale_b R(q_b) slip_body_i - (u0 + G r_i): what the steps add
         to their slip, and what a bare solve takes as slip=.  Zeros with both parts off.  Shaped like the blob positions."""
-        return self._like_X(self.cb.flow_slip())
+        return self._like_X(self.ctx.flow_slip())
 
     def first_moments(self, lam):
         """D_b = sum_i (r_i - X_b) lambda_i^T over the blobs of each body -> (N_bodies, 3, 3).  lam: any blob vector -- the lambda
@@ -447,7 +444,7 @@ class RigidBody:
         lam = np.asarray(lam, dtype=np.float64)
         if lam.size != 3 * self.total_blobs:
             raise ValueError(f"first_moments: lam must have total size 3*N_blobs = {3 * self.total_blobs}. Got shape: {lam.shape}")
-        return self.cb.first_moments(np.ascontiguousarray(lam).reshape(-1)).reshape(self.N_bodies, 3, 3)
+        return self.ctx.first_moments(np.ascontiguousarray(lam).reshape(-1)).reshape(self.N_bodies, 3, 3)
 
     def stresslets(self, lam):
         """The symmetric traceless part of first_moments(lam) -> (N_bodies, 3, 3)"""
@@ -463,7 +460,7 @@ class RigidBody:
     def step_moments(self):
         """first moments recorded by the last step, (N_bodies, 3, 3), with the lever arms of the configuration it solved at (q^n
         for the deterministic steps, q^{n+1/2} for the midpoint steps).  The Brownian drift's share of the stress is not in it."""
-        return self.cb.step_moments().reshape(self.N_bodies, 3, 3)
+        return self.ctx.step_moments().reshape(self.N_bodies, 3, 3)
 
     # ------------------------------------------------------------------ prescribed kinematics (include/rbl.h section 7)
     def _prescribed_mask(self, prescribed):
@@ -520,7 +517,7 @@ class RigidBody:
         body velocities (prescribed ones echoed), all body loads (free ones echoed, prescribed ones -K_b^T lambda: the load it takes
         to move them as told)."""
         mask, bi, sl = self._mixed_args(prescribed, body_in, slip)
-        return self.cb.solve_mixed(mask, bi, sl, int(max_iter), float(rtol))
+        return self.ctx.solve_mixed(mask, bi, slip=sl, max_iter=int(max_iter), rtol=float(rtol))
 
     def step_mixed(self, prescribed, body_in, slip=None, max_iter=50, rtol=1.0e-8):
         """One deterministic time step with prescribed bodies: solve_mixed at the current configuration, then
@@ -528,7 +525,7 @@ class RigidBody:
         loads are added to the FREE bodies only; the F returned for a prescribed body is the total load everything other than the
         fluid supplies (the model's share included).  -> (F, iterations, residual estimate)"""
         mask, bi, sl = self._mixed_args(prescribed, body_in, slip)
-        return self.cb.step_mixed(mask, bi, sl, int(max_iter), float(rtol))
+        return self.ctx.step_mixed(mask, bi, slip=sl, max_iter=int(max_iter), rtol=float(rtol))
 
     def solve_mixed_dof(self, prescribed, body_in, slip=None, max_iter=100, rtol=1.0e-8):
         """Prescribed kinematics per velocity component: `prescribed` is a boolean array of shape (N_bodies, 6) over each body's
@@ -539,14 +536,14 @@ class RigidBody:
         with the prescribed components echoed, F with the free components echoed and -K^T lambda on the prescribed ones (the force
         or torque along that component that it takes)."""
         mask, bi, sl = self._mixed_args(prescribed, body_in, slip, per=6)
-        return self.cb.solve_mixed_dof(mask, bi, sl, int(max_iter), float(rtol))
+        return self.ctx.solve_mixed_dof(mask, bi, slip=sl, max_iter=int(max_iter), rtol=float(rtol))
 
     def step_mixed_dof(self, prescribed, body_in, slip=None, max_iter=50, rtol=1.0e-8):
         """One deterministic time step with a mask per velocity component: solve_mixed_dof at the current configuration, then
         evolve_rigid_bodies(U).  With the force model on its loads are added to the FREE components only; the F of a prescribed
         component is the total load along it that everything other than the fluid supplies.  -> (F, iterations, residual estimate)"""
         mask, bi, sl = self._mixed_args(prescribed, body_in, slip, per=6)
-        return self.cb.step_mixed_dof(mask, bi, sl, int(max_iter), float(rtol))
+        return self.ctx.step_mixed_dof(mask, bi, slip=sl, max_iter=int(max_iter), rtol=float(rtol))
 
     def _multi_body_in_and_slip(self, body_in, slip):
         bi = np.asarray(body_in)
@@ -571,7 +568,7 @@ class RigidBody:
         -> (lambda (k, 3 N_blobs), U (k, 6 N_bodies), F (k, 6 N_bodies), iterations (k,), residual estimates (k,))"""
         mask = self._prescribed_mask(prescribed)
         bi, sl = self._multi_body_in_and_slip(body_in, slip)
-        return self.cb.solve_mixed_multi(mask, bi, sl, int(max_iter), float(rtol))
+        return self.ctx.solve_mixed_multi(mask, bi, slip=sl, max_iter=int(max_iter), rtol=float(rtol))
 
     def solve_mixed_dof_multi(self, prescribed, body_in, slip=None, max_iter=100, rtol=1.0e-8):
         """solve_mixed_dof for k right-hand sides under ONE mask per velocity component (a boolean array of shape (N_bodies, 6)), in
@@ -579,7 +576,7 @@ class RigidBody:
         -> (lambda (k, 3 N_blobs), U (k, 6 N_bodies), F (k, 6 N_bodies), iterations (k,), residual estimates (k,))"""
         mask = self._prescribed_mask6(prescribed)
         bi, sl = self._multi_body_in_and_slip(body_in, slip)
-        return self.cb.solve_mixed_dof_multi(mask, bi, sl, int(max_iter), float(rtol))
+        return self.ctx.solve_mixed_dof_multi(mask, bi, slip=sl, max_iter=int(max_iter), rtol=float(rtol))
 
     def _noise_arg(self, W):
         if W is None:
@@ -596,7 +593,7 @@ class RigidBody:
         Nothing is committed.  -> (s, X_half, Q_half)"""
         mask, bi, sl = self._mixed_args(prescribed, body_in, slip)
         W = self._noise_arg(W)
-        return self.cb.RHS_and_Midpoint_mixed(mask, bi, sl, W, int(seed), method, bool(split_rand), float(delta))
+        return self.ctx.RHS_and_Midpoint_mixed(mask, bi, slip=sl, W=W, seed=int(seed), method=method, split_rand=bool(split_rand), delta=float(delta))
 
     def step_brownian_mixed(self, prescribed, body_in, slip=None, W=None, seed=0, method="lanczos_pc", split_rand=True, delta=1.0e-4,
                             max_iter=50, rtol=1.0e-8):
@@ -608,8 +605,8 @@ class RigidBody:
         steps for a microrheology measurement.  kBT = 1 as in step_brownian.  -> (F, iterations, residual estimate)"""
         mask, bi, sl = self._mixed_args(prescribed, body_in, slip)
         W = self._noise_arg(W)
-        return self.cb.step_brownian_mixed(mask, bi, sl, W, int(seed), method, bool(split_rand), float(delta),
-                                           int(max_iter), float(rtol))
+        return self.ctx.step_brownian_mixed(mask, bi, slip=sl, W=W, seed=int(seed), method=method, split_rand=bool(split_rand),
+                                            delta=float(delta), max_iter=int(max_iter), rtol=float(rtol))
 
     def _brownian_dof_args(self, who, prescribed, body_in, slip):
         mask, bi, sl = self._mixed_args(prescribed, body_in, slip, per=6)
@@ -623,7 +620,7 @@ class RigidBody:
         Nothing is committed.  -> (s, X_half, Q_half)"""
         mask, bi, sl = self._brownian_dof_args("RHS_and_Midpoint_mixed_dof", prescribed, body_in, slip)
         W = self._noise_arg(W)
-        return self.cb.RHS_and_Midpoint_mixed_dof(mask, bi, sl, W, int(seed), method, bool(split_rand), float(delta))
+        return self.ctx.RHS_and_Midpoint_mixed_dof(mask, bi, slip=sl, W=W, seed=int(seed), method=method, split_rand=bool(split_rand), delta=float(delta))
 
     def step_brownian_mixed_dof(self, prescribed, body_in, slip=None, W=None, seed=0, method="lanczos_pc", split_rand=True, delta=1.0e-4,
                                 max_iter=50, rtol=1.0e-8):
@@ -639,8 +636,8 @@ class RigidBody:
         only, at q^n.  With whole rows the results are step_brownian_mixed's, bit for bit.  -> (F, iterations, residual estimate)"""
         mask, bi, sl = self._brownian_dof_args("step_brownian_mixed_dof", prescribed, body_in, slip)
         W = self._noise_arg(W)
-        return self.cb.step_brownian_mixed_dof(mask, bi, sl, W, int(seed), method, bool(split_rand), float(delta),
-                                               int(max_iter), float(rtol))
+        return self.ctx.step_brownian_mixed_dof(mask, bi, slip=sl, W=W, seed=int(seed), method=method, split_rand=bool(split_rand),
+                                                delta=float(delta), max_iter=int(max_iter), rtol=float(rtol))
 
     def body_resistance_matrix(self, max_iter=100, rtol=1.0e-8, columns=None, lock_step=False):
         """The (6 N_bodies) x (6 N_bodies) body resistance matrix R = N^-1 of the current configuration, the inverse of

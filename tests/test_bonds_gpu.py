@@ -407,7 +407,7 @@ def test_only_the_free_slots_of_a_mask_feel_the_bonds():
         Xs, Qs = (np.array(v) for v in rb.get_config())
         if with_model:
             body, anchor, kind, k, l0 = _set_ring(rb, c)
-            assert rb.cb.interactions_active() == 64
+            assert rb.ctx.interactions_active() == 64
             assert np.array_equal(rb.blob_anchor(4), anchor[1, 3:])
             loads = rb.interaction_forces()                    # reference convention, -K^T f_phys
             assert np.abs(loads[:6]).max() > 0.1 and np.abs(loads[6:]).max() > 0.1

@@ -254,7 +254,7 @@ class _NoLibrary:
 def _wrapper(nb=5, nblb=2):
     from rigid_body_light_amd import RigidBody
     rb = RigidBody.__new__(RigidBody)
-    rb.cb = _NoLibrary()
+    rb.cb = rb.ctx = _NoLibrary()          # the extension object and the view of its context
     rb.N_bodies, rb.blobs_per_body, rb.total_blobs = nb, nblb, nb * nblb
     rb.X_shape, rb.Q_shape = (nb, 3), (nb, 4)
     return rb
@@ -309,14 +309,14 @@ def test_wrapper_rejects_bad_shapes_and_passes_admissible_masks_on():
     seen = {}
 
     class _Record:
-        def step_brownian_mixed_dof(self, *args):
-            seen["step"] = args
+        def step_brownian_mixed_dof(self, mask, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol):
+            seen["step"] = (mask, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol)
             return "stepped"
 
-        def RHS_and_Midpoint_mixed_dof(self, *args):
-            seen["rhs"] = args
+        def RHS_and_Midpoint_mixed_dof(self, mask, body_in, slip, W, seed, method, split_rand, delta):
+            seen["rhs"] = (mask, body_in, slip, W, seed, method, split_rand, delta)
             return "rhs"
-    rb.cb = _Record()
+    rb.ctx = _Record()
     assert rb.step_brownian_mixed_dof(good, bi.reshape(5, 6), W=np.zeros((3, 30)), seed=5, max_iter=7) == "stepped"
     mask, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol = seen["step"]
     assert mask.dtype == np.uint8 and mask.shape == (30,) and np.array_equal(mask.reshape(5, 6), good) and body_in.shape == (30,)

@@ -315,18 +315,21 @@ def test_nothing_prescribed_is_step_brownian_bitwise(shell12, wall, split_rand):
 
 @pytest.mark.parametrize("wall", [False, True])
 def test_zero_temperature_is_step_mixed_dof_bitwise(shell12, wall):
+    from rigid_body_light_amd._lib import DeviceContext
     nb = 4
     X, Q, W, slip, F, Up = _case(wall, seed=240)
     P, held = _mask6("mixed", nb)
     bi = _body_in6(P, held, F, Up).reshape(-1)
     mask = P.astype(np.uint8).reshape(-1)
     a, b = _raw(shell12, X, Q, 0.0, wall, True), _raw(shell12, X, Q, 0.0, wall, True)
-    Fa, ita, resa = a.step_brownian_mixed_dof(mask, bi, slip, W, 0, "cholesky", True, 1e-4, 200, 1e-10)
-    Fb, itb, resb = b.step_mixed_dof(mask, bi, slip, 200, 1e-10)
+    va, vb = (DeviceContext.borrow(cm.handle(), 1.0, shell12) for cm in (a, b))       # the views' methods; a and b own the contexts
+    Fa, ita, resa = va.step_brownian_mixed_dof(mask, bi, slip=slip, W=W, seed=0, method="cholesky", split_rand=True, delta=1e-4,
+                                               max_iter=200, rtol=1e-10)
+    Fb, itb, resb = vb.step_mixed_dof(mask, bi, slip=slip, max_iter=200, rtol=1e-10)
     (Xa, Qa), (Xb, Qb) = a.getConfig(), b.getConfig()
     assert ita == itb and 0 < ita < 200 and resa == resb
     assert np.array_equal(Xa, Xb) and np.array_equal(Qa, Qb) and np.array_equal(Fa, Fb)
-    s, Xh, Qh = a.RHS_and_Midpoint_mixed_dof(mask, bi, slip, W)
+    s, Xh, Qh = va.RHS_and_Midpoint_mixed_dof(mask, bi, slip, W)
     assert np.array_equal(s, slip) and np.array_equal(Xh, Xa) and np.array_equal(Qh, Qa)
 
 

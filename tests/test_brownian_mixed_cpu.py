@@ -141,7 +141,7 @@ class _NoLibrary:
 def _wrapper(nb=4, nblb=2):
     from rigid_body_light_amd import RigidBody
     rb = RigidBody.__new__(RigidBody)
-    rb.cb = _NoLibrary()
+    rb.cb = rb.ctx = _NoLibrary()          # the extension object and the view of its context
     rb.N_bodies, rb.blobs_per_body, rb.total_blobs = nb, nblb, nb * nblb
     rb.X_shape, rb.Q_shape = (nb, 3), (nb, 4)
     return rb
@@ -168,14 +168,14 @@ def test_wrapper_rejects_bad_sets_and_shapes_before_calling_the_library():
     seen = {}
 
     class _Record:
-        def step_brownian_mixed(self, *args):
-            seen["step"] = args
+        def step_brownian_mixed(self, mask, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol):
+            seen["step"] = (mask, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol)
             return "stepped"
 
-        def RHS_and_Midpoint_mixed(self, *args):
-            seen["rhs"] = args
+        def RHS_and_Midpoint_mixed(self, mask, body_in, slip, W, seed, method, split_rand, delta):
+            seen["rhs"] = (mask, body_in, slip, W, seed, method, split_rand, delta)
             return "rhs"
-    rb.cb = _Record()
+    rb.ctx = _Record()
     assert rb.step_brownian_mixed([3, 1], bi.reshape(4, 6), W=np.zeros((3, 24)), seed=5, max_iter=7) == "stepped"
     mask, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol = seen["step"]
     assert mask.dtype == np.uint8 and mask.tolist() == [0, 1, 0, 1] and body_in.shape == (24,) and slip is None

@@ -203,16 +203,19 @@ def _raw(shell12, X, Q, kBT, wall, block, dt=0.01):
 
 @pytest.mark.parametrize("wall", [False, True])
 def test_zero_temperature_is_step_mixed(shell12, wall):
+    from rigid_body_light_amd._lib import DeviceContext
     X, Q, W, slip, F, Up = _case(wall, seed=240)
     p, bi = _mask_and_body_in("one held, one driven", F, Up)
     mask = p.astype(np.uint8)
     a, b = _raw(shell12, X, Q, 0.0, wall, True), _raw(shell12, X, Q, 0.0, wall, True)
-    Fa, ita, _ = a.step_brownian_mixed(mask, bi.reshape(-1), slip, W, 0, "cholesky", True, 1e-4, 200, 1e-10)
-    Fb, itb, _ = b.step_mixed(mask, bi.reshape(-1), slip, 200, 1e-10)
+    va, vb = (DeviceContext.borrow(cm.handle(), 1.0, shell12) for cm in (a, b))       # the views' methods; a and b own the contexts
+    Fa, ita, _ = va.step_brownian_mixed(mask, bi.reshape(-1), slip=slip, W=W, seed=0, method="cholesky", split_rand=True, delta=1e-4,
+                                        max_iter=200, rtol=1e-10)
+    Fb, itb, _ = vb.step_mixed(mask, bi.reshape(-1), slip=slip, max_iter=200, rtol=1e-10)
     (Xa, Qa), (Xb, Qb) = a.getConfig(), b.getConfig()
     assert ita == itb and 0 < ita < 200
     assert np.abs(Xa - Xb).max() <= 1e-14 and np.abs(Qa - Qb).max() <= 1e-14 and np.abs(Fa - Fb).max() <= 1e-14 * np.abs(Fb).max()
-    s, Xh, Qh = a.RHS_and_Midpoint_mixed(mask, bi.reshape(-1), slip, W)
+    s, Xh, Qh = va.RHS_and_Midpoint_mixed(mask, bi.reshape(-1), slip, W)
     assert np.array_equal(s, slip) and np.array_equal(Xh, Xa) and np.array_equal(Qh, Qa)
 
 

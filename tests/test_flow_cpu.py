@@ -282,7 +282,7 @@ class _NoLibrary:
 def _wrapper(nb=4, nblb=2):
     from rigid_body_light_amd import RigidBody
     rb = RigidBody.__new__(RigidBody)
-    rb.cb = _NoLibrary()
+    rb.cb = rb.ctx = _NoLibrary()          # the extension object and the view of its context
     rb.N_bodies, rb.blobs_per_body, rb.total_blobs = nb, nblb, nb * nblb
     rb.X_shape, rb.Q_shape = (nb, 3), (nb, 4)
     rb._wall = False
@@ -318,9 +318,9 @@ def test_rigid_body_shape_errors_raise_before_the_library():
         def first_moments(self, lam):
             seen["lam"] = lam
             return np.arange(36.0)
-    rb.cb = _Record()
+    rb.ctx = _Record()
     rb.set_background_flow(G=np.arange(9.0).reshape(3, 3), on=False)
-    assert seen["flow"][0].tolist() == [0, 0, 0] and seen["flow"][1].tolist() == list(range(9)) and seen["flow"][2] is False
+    assert seen["flow"][0].tolist() == [0, 0, 0] and seen["flow"][1].reshape(-1).tolist() == list(range(9)) and seen["flow"][1].flags.c_contiguous and seen["flow"][2] is False
     rb.set_body_slip(np.arange(6.0).reshape(2, 3), scale=[1, 0, 2, 3])
     assert seen["slip"][0].shape == (6,) and seen["slip"][1].tolist() == [1, 0, 2, 3] and seen["slip"][2] is True
     D = rb.first_moments(np.zeros((8, 3)))

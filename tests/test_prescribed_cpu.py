@@ -117,7 +117,7 @@ class _NoLibrary:
 def _wrapper(nb=4, nblb=2):
     from rigid_body_light_amd import RigidBody
     rb = RigidBody.__new__(RigidBody)
-    rb.cb = _NoLibrary()
+    rb.cb = rb.ctx = _NoLibrary()          # the extension object and the view of its context
     rb.N_bodies, rb.blobs_per_body, rb.total_blobs = nb, nblb, nb * nblb
     rb.X_shape, rb.Q_shape = (nb, 3), (nb, 4)
     return rb
@@ -144,7 +144,7 @@ def test_wrapper_rejects_bad_sets_and_shapes_before_calling_the_library():
         def solve_mixed(self, mask, body_in, slip, max_iter, rtol):
             seen["args"] = (mask, body_in, slip, max_iter, rtol)
             return "solved"
-    rb.cb = _Record()
+    rb.ctx = _Record()
     assert rb.solve_mixed([3, 1], bi.reshape(4, 6), max_iter=7) == "solved"
     mask, body_in, slip, max_iter, rtol = seen["args"]
     assert mask.dtype == np.uint8 and mask.tolist() == [0, 1, 0, 1] and body_in.shape == (24,) and slip is None and max_iter == 7

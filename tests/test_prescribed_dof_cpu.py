@@ -127,7 +127,7 @@ class _NoLibrary:
 def _wrapper(nb=4, nblb=2):
     from rigid_body_light_amd import RigidBody
     rb = RigidBody.__new__(RigidBody)
-    rb.cb = _NoLibrary()
+    rb.cb = rb.ctx = _NoLibrary()          # the extension object and the view of its context
     rb.N_bodies, rb.blobs_per_body, rb.total_blobs = nb, nblb, nb * nblb
     rb.X_shape, rb.Q_shape = (nb, 3), (nb, 4)
     return rb
@@ -163,7 +163,7 @@ def test_wrapper_takes_a_bool_array_of_shape_nbodies_by_6_and_nothing_else():
         def step_mixed_dof(self, mask, body_in, slip, max_iter, rtol):
             seen["args"] = (mask, body_in, slip, max_iter, rtol)
             return "stepped"
-    rb.cb = _Record()
+    rb.ctx = _Record()
     assert rb.solve_mixed_dof(good, bi.reshape(4, 6), max_iter=7) == "solved"
     mask, body_in, slip, max_iter, rtol = seen["args"]
     assert mask.dtype == np.uint8 and mask.shape == (24,) and mask.tolist() == good.reshape(-1).astype(int).tolist()

@@ -119,7 +119,7 @@ class _NoLibrary:
 def _wrapper(nb=4, nblb=2):
     from rigid_body_light_amd import RigidBody
     rb = RigidBody.__new__(RigidBody)
-    rb.cb = _NoLibrary()
+    rb.cb = rb.ctx = _NoLibrary()          # the extension object and the view of its context
     rb.N_bodies, rb.blobs_per_body, rb.total_blobs = nb, nblb, nb * nblb
     rb.X_shape, rb.Q_shape = (nb, 3), (nb, 4)
     return rb
@@ -149,14 +149,14 @@ def test_wrappers_reject_wrong_shapes_and_dtypes_before_calling_down():
     seen = {}
 
     class _Record:
-        def solve_mixed_multi(self, *args):
-            seen["args"] = args
+        def solve_mixed_multi(self, mask, body_in, slip, max_iter, rtol):
+            seen["args"] = (mask, body_in, slip, max_iter, rtol)
             return "multi"
 
-        def solve_mixed_dof_multi(self, *args):
-            seen["args"] = args
+        def solve_mixed_dof_multi(self, mask, body_in, slip, max_iter, rtol):
+            seen["args"] = (mask, body_in, slip, max_iter, rtol)
             return "dof_multi"
-    rb.cb = _Record()
+    rb.ctx = _Record()
     assert rb.solve_mixed_multi([1, 3], np.asfortranarray(bi), max_iter=7) == "multi"
     mask, body_in, slip, max_iter, rtol = seen["args"]
     assert mask.dtype == np.uint8 and mask.tolist() == [0, 1, 0, 1]
@@ -176,7 +176,7 @@ def test_wrappers_reject_wrong_shapes_and_dtypes_before_calling_down():
         def solve_mixed_multi(self, mask, body_in, slip, max_iter, rtol):
             calls.append(("multi", body_in.copy()))
             return None, None, np.arange(body_in.size, dtype=float).reshape(body_in.shape), np.ones(body_in.shape[0], dtype=np.int32), None
-    rb.cb = _Count()
+    rb.ctx = _Count()
     R, its = rb.body_resistance_matrix(columns=[2, 17])
     assert calls == ["one", "one"] and R.shape == (24, 2)
     del calls[:]
