@@ -113,6 +113,8 @@ def lib(path=None):
                                                                          C.POINTER(dbl)]
         L.rbl_step_jointed.argtypes = [vp, vp, vp, vp, dbl, C.c_int, dbl, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
         L.rbl_joint_state.argtypes = [vp, vp, vp]
+        L.rbl_set_periodic.argtypes = [vp, dbl, dbl, C.c_int, C.c_int, C.c_int]
+        L.rbl_get_periodic.argtypes = [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.rbl_interaction_forces_dev.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_forces.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
@@ -332,6 +334,24 @@ class RunResult:
     def __repr__(self):
         return "RunResult(steps_done=%d, stopped_at=%d, accepted=%d..%d, rejected=%d)" % (
             self.steps_done, self.stopped_at, int(self.accepted.min()), int(self.accepted.max()), int(self.rejected.sum()))
+
+
+def periodic_args(who, Lx, Ly, images):
+    """the checks set_periodic can make before the library is called -> (Lx, Ly, nx, ny)"""
+    import numbers
+    for name, v in (("Lx", Lx), ("Ly", Ly)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise TypeError("%s: %s must be a real number, got %r" % (who, name, v))
+    try:
+        n = tuple(images)
+    except TypeError:
+        raise TypeError("%s: images must be a pair of integers (nx, ny), got %r" % (who, images)) from None
+    if len(n) != 2:
+        raise ValueError("%s: images must be a pair (nx, ny), got %d entries" % (who, len(n)))
+    for v in n:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError("%s: images must be integers, got %r" % (who, v))
+    return float(Lx), float(Ly), int(n[0]), int(n[1])
 
 
 class DeviceContext:
@@ -741,6 +761,20 @@ class DeviceContext:
         gap, phi = np.zeros((max(n.value, 1), 3)), np.zeros((max(n.value, 1), 3))
         self._chk(self.L.rbl_joint_state(self.h, gap.ctypes.data, phi.ctypes.data))
         return gap[:n.value], phi[:n.value]
+
+    # -- periodic cell in x and y (include/rbl.h section 10) ---------------------------------------------------------------------
+    def set_periodic(self, Lx, Ly, images=(1, 1), on=True):
+        """the periodic cell: lengths Lx, Ly (0: that axis is open) and the image counts (nx, ny) of the truncated lattice sum,
+        |p| <= nx and |q| <= ny images about the nearest one of every pair (1 ... 16 on a periodic axis).  With the cell on every
+        mobility product of the library is the periodic one and the pair forces use the minimum image; coordinates stay unwrapped."""
+        Lx, Ly, nx, ny = periodic_args("set_periodic", Lx, Ly, images)
+        self._chk(self.L.rbl_set_periodic(self.h, Lx, Ly, nx, ny, int(bool(on))))
+
+    def periodic(self):
+        """{on, Lx, Ly, images (nx, ny)} (both lengths 0: never set)"""
+        Lx, Ly, nx, ny, on = C.c_double(0.0), C.c_double(0.0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_periodic(self.h, C.byref(Lx), C.byref(Ly), C.byref(nx), C.byref(ny), C.byref(on)))
+        return dict(on=bool(on.value), Lx=Lx.value, Ly=Ly.value, images=(nx.value, ny.value))
 
     def set_bond_table(self, U, dU, r_min, r_cut, on=True):
         """the potential T(d) of the kind-1 bonds from its values U and derivatives dU = dU/dd on the uniform grid r_min .. r_cut

@@ -12,6 +12,7 @@
 //   rbl_field.hip     the fluid velocity at arbitrary points from blob forces
 //   rbl_mixed.hip     prescribed kinematics: held or driven bodies among free ones, the loads that takes; the entry points of their Brownian step
 //   rbl_flow.hip      imposed linear flow and body-frame slip added to every step's slip, first moments of the blob forces
+//   rbl_periodic.hip  the periodic cell in x and y: its state, and the refusals of what it is not offered with
 // None of these symbols is exported from librbl.so.
 #pragma once
 #include <functional>
@@ -185,5 +186,10 @@ void flow_launch_moments(rbl_ctx *c, const double *d_lever, const double *d_Q, c
 void flow_begin_step(rbl_ctx *c);
 // RBL_OPT_RECORD_MOMENTS: the moments of d_lambda at the configuration the context is at; no-op while the option is off
 int flow_record_moments(rbl_ctx *c, const double *d_lambda);
+
+// ---- rbl_periodic.hip ---------------------------------------------------------------------------------------------
+bool periodic_on(const rbl_ctx *c);           // a cell is set and switched on
+// RBL_ERR_STATE "<who>: not offered with a periodic cell ..." while the cell is on, RBL_OK otherwise; touches no device
+int periodic_refuse(rbl_ctx *c, const char *who);
 
 #pragma GCC visibility pop

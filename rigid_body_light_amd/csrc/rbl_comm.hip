@@ -278,6 +278,7 @@ static void comm_invalidate(rbl_ctx *c)
 int rbl_set_comm_ops(rbl_ctx *c, int rank, int world, rbl_allreduce_fn allreduce, rbl_allgatherv_fn allgatherv, void *user)
 {
   if (!c || world < 1 || rank < 0 || rank >= world) return rbl_fail(c, RBL_ERR_ARG, "set_comm: need 0 <= rank < world");
+  if (allreduce && periodic_on(c)) return periodic_refuse(c, "set_comm");   // (detaching one stays possible)
   if (c->dev_ready) (void)hipStreamSynchronize(c->stream);
   comm_release(c);
   comm_invalidate(c);
@@ -306,6 +307,7 @@ int rbl_comm_unique_id(void *id_out)
 int rbl_comm_init_rccl(rbl_ctx *c, const void *unique_id, int rank, int world)
 {
   if (!c || !unique_id || world < 1 || rank < 0 || rank >= world) return rbl_fail(c, RBL_ERR_ARG, "comm_init_rccl: need an id and 0 <= rank < world");
+  if (periodic_on(c)) return periodic_refuse(c, "comm_init_rccl");
   int rc = rbl_dev_init(c); if (rc) return rc;
   const RcclApi *R = rccl();
   if (!R) return rbl_fail(c, RBL_ERR_COMM, g_rccl.error);

@@ -906,6 +906,7 @@ int ens_mx_solve(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed
                  double rtol, double *lambda, double *U, double *F, int *iters, double *resid)
 {
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, who);
   const std::string no_out = std::string(who) + ": U or F is NULL";
   if (per == 6 && (!U || !F)) return rbl_fail(c, RBL_ERR_ARG, no_out);   // the _dof call refuses NULL outputs before it reads the mask,
   int rc = ens_mx_check(c, who, prescribed, body_in, max_iter, rtol, per); if (rc) return rc;
@@ -918,6 +919,7 @@ int ens_mx_step(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed,
                 double rtol, double *F, int *iters, double *resid)
 {
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, who);
   int rc = ens_mx_check(c, who, prescribed, body_in, max_iter, rtol, per); if (rc) return rc;
   if ((rc = ens_flow_check(c))) return rc;
   if ((rc = ens_ready(c))) return rc;
@@ -931,6 +933,7 @@ int ens_mx_step_bd(rbl_ctx *c, const char *who, int per, const uint8_t *prescrib
                    double *resid)
 {
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, who);
   int rc = ens_mx_check(c, who, prescribed, body_in, max_iter, rtol, per); if (rc) return rc;
   if (per == 6 && (rc = rbl_bd_mask6_check(c, who, prescribed, c->ens_R, c->ens_Nb))) return rc;   // whole bodies: nothing to check
   if ((rc = ens_flow_check(c))) return rc;
@@ -949,6 +952,7 @@ int ens_mx_step_bd(rbl_ctx *c, const char *who, int per, const uint8_t *prescrib
 int rbl_ensemble_set_config(rbl_ctx *c, int R, int N_bod, const double *X, const double *Q)
 {
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_set_config");
   int rc = need_params(c); if (rc) return rc;
   if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, "ensemble: not on a context with a communicator (run one ensemble per process)");
   if (R < 1 || R > ENS_R_MAX) return rbl_fail(c, RBL_ERR_SIZE, "ensemble: R must be 1 .. 65535");
@@ -982,6 +986,7 @@ int rbl_ensemble_set_config(rbl_ctx *c, int R, int N_bod, const double *X, const
 int rbl_ensemble_get_config(rbl_ctx *c, double *X, double *Q)
 {
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_get_config");
   if (!c->ens_R) return ens_fail_state(c);
   if (!X || !Q) return rbl_fail(c, RBL_ERR_ARG, "ensemble_get_config: null argument");
   const size_t nb = (size_t)c->ens_R * c->ens_Nb;
@@ -1002,6 +1007,7 @@ int rbl_ensemble_info(const rbl_ctx *c, int *R, int *N_bod)
 int rbl_ensemble_config_dev(rbl_ctx *c, const double **d_X, const double **d_Q)
 {
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_config_dev");
   if (!c->ens_R) return ens_fail_state(c);
   if (d_X) *d_X = ens_X(c, c->ens_cur);
   if (d_Q) *d_Q = ens_Q(c, c->ens_cur);
@@ -1012,6 +1018,7 @@ int rbl_ensemble_step_deterministic(rbl_ctx *c, const double *F_body, const doub
                                     double *resid)
 {
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_step_deterministic");
   int rc = ens_flow_check(c); if (rc) return rc;
   if ((rc = ens_ready(c))) return rc;
   if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_deterministic: F_body is NULL");
@@ -1023,6 +1030,7 @@ int rbl_ensemble_step_brownian(rbl_ctx *c, const double *F_body, const double *s
                                int split_rand, double delta, int max_iter, double rtol, int *iters, double *resid)
 {
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_step_brownian");
   int rc = ens_flow_check(c); if (rc) return rc;
   if ((rc = ens_ready(c))) return rc;
   const RblBodyState &S = c->S;
@@ -1083,6 +1091,7 @@ int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)
   if (o->size != (int64_t)sizeof(rbl_run_opts)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: opts.size is not sizeof(rbl_run_opts)");
   if (out->size != (int64_t)sizeof(rbl_run_out)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: out.size is not sizeof(rbl_run_out)");
   out->steps_done = 0; out->stopped_at = -1; out->stop_replica = -1; out->reserved = 0;   // what a refused call leaves
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_run");
   if (o->n_steps < 1) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: n_steps must be >= 1");
   if (o->stride < 0) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: stride must be >= 0");
   if (o->check_every < 0) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: check_every must be >= 0");
@@ -1124,6 +1133,7 @@ int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)
 int rbl_ensemble_interaction_forces(rbl_ctx *c, double *FT_body, double *energy)
 {
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_interaction_forces");
   int rc = ens_ready(c); if (rc) return rc;
   if (!ia_any(c)) return rbl_fail(c, RBL_ERR_STATE, "ensemble_interaction_forces: no force model is switched on (rbl_set_interactions)");
   EnsWork w;
@@ -1154,6 +1164,7 @@ int rbl_ensemble_interaction_forces(rbl_ctx *c, double *FT_body, double *energy)
 int rbl_ensemble_flow_slip(rbl_ctx *c, double *out)
 {
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_flow_slip");
   int rc = ens_flow_check(c); if (rc) return rc;
   if ((rc = ens_ready(c))) return rc;
   if (!out) return rbl_fail(c, RBL_ERR_ARG, "ensemble_flow_slip: out is NULL");

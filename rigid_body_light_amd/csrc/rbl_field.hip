@@ -312,6 +312,7 @@ int vf_check_args(rbl_ctx *c, const double *points, int64_t n_points, const doub
 {
   *noop = false;
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "velocity_field");
   if (n_points < 0 || n_src < 0) return rbl_fail(c, RBL_ERR_ARG, "velocity_field: negative size");
   if (n_points == 0) { *noop = true; return RBL_OK; }
   if (!points || !u || !lambda) return rbl_fail(c, RBL_ERR_ARG, "velocity_field: null points, lambda or output");

@@ -304,6 +304,7 @@ int rbl_step_moments(rbl_ctx *c, double *D)
 int rbl_ensemble_step_moments(rbl_ctx *c, double *D)
 {
   if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_step_moments");
   if (!D) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_moments: D is NULL");
   if (!c->ens_mom_R || c->ens_mom_R != c->ens_R || c->ens_mom_nb != c->ens_Nb)
     return rbl_fail(c, RBL_ERR_STATE, "ensemble_step_moments: no ensemble step has recorded first moments for this ensemble (rbl_set_option record_moments, then a step)");

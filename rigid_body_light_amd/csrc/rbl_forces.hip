@@ -40,6 +40,10 @@
 //                        operations, so the two forces are bitwise opposite.  No atomics; the order depends on replica-local
 //                        indices alone.  The grid covers the compact list of bonded bodies, not all bodies.
 //   k_bond_state         one lane per (window, bond): length, tension dU/dd and energy, for the state queries.
+//   k_body_neighbours_per, k_blob_interactions_per<TAB>, k_body_dipoles_per<NT>   the same three with the pair displacement by
+//                        minimum image in a periodic cell (include/rbl.h section 10), selected by ia_launch while the cell is on.
+//                        The pair kernel shares its body with the open one through a template flag; the other two repeat theirs
+//                        (see k_body_neighbours_per).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -60,6 +64,20 @@ struct IaParams {
   int wall;
 };
 
+// the periodic cell of include/rbl.h section 10 as the minimum-image kernels take it (by value): lengths and reciprocals, 0 on an
+// open axis, whose reduction is then skipped (no 1 / 0)
+struct IaCell {
+  double Lx, Ly, iLx, iLy;
+  int px, py;
+};
+
+// minimum-image convention on a displacement: d - L rint(d / L) on every periodic axis
+__device__ __forceinline__ void ia_min_image(const IaCell &C, double &dx, double &dy)
+{
+  if (C.px) dx = __builtin_fma(-C.Lx, rint(dx * C.iLx), dx);
+  if (C.py) dy = __builtin_fma(-C.Ly, rint(dy * C.iLy), dy);
+}
+
 // win: bodies per window -- body i only sees the bodies [i - i % win, i - i % win + win) (the replicas of an ensemble do not
 // interact); win = N_bod: every body
 __global__ __launch_bounds__(64) void k_body_neighbours(const double *__restrict__ X, int N_bod, int win, double cut2, int cull,
@@ -76,6 +94,40 @@ __global__ __launch_bounds__(64) void k_body_neighbours(const double *__restrict
       if (!cull) take = true;
       else {
         const double dx = X[3 * (size_t)j] - xi, dy = X[3 * (size_t)j + 1] - yi, dz = X[3 * (size_t)j + 2] - zi;
+        take = dx * dx + dy * dy + dz * dz <= cut2;
+      }
+    }
+    const unsigned long long m = __ballot(take);
+    const int below = __popcll(m & ((1ull << t) - 1ull));
+    if (take && base + below < cap) list[(size_t)i * cap + base + below] = j;
+    base += __popcll(m);
+  }
+  if (t == 0) {
+    cnt[i] = base;                                       // may exceed cap: the pair kernel walks min(cnt, cap) and the overflow is reported
+    if (base > cap) atomicOr(err, (unsigned)RBL_FLAG_CAPACITY);
+  }
+}
+
+// the same with the centre distance by minimum image (a periodic cell).  Its own kernel, the body repeated: k_body_neighbours
+// as an instantiation of a shared template came out of the compiler with its registers permuted, and the existing kernels keep
+// their code instruction for instruction
+__global__ __launch_bounds__(64) void k_body_neighbours_per(const double *__restrict__ X, int N_bod, int win, double cut2, int cull,
+                                                            int cap, IaCell C, int *__restrict__ cnt, int *__restrict__ list,
+                                                            unsigned *__restrict__ err)
+{
+  const int i = blockIdx.x, t = threadIdx.x;
+  const double xi = X[3 * (size_t)i], yi = X[3 * (size_t)i + 1], zi = X[3 * (size_t)i + 2];
+  const int jb = i - i % win, je = min(jb + win, N_bod);
+  int base = 0;
+  for (int j0 = jb; j0 < je; j0 += 64) {
+    const int j = j0 + t;
+    bool take = false;
+    if (j < je && j != i) {
+      if (!cull) take = true;
+      else {
+        double dx = X[3 * (size_t)j] - xi, dy = X[3 * (size_t)j + 1] - yi;
+        const double dz = X[3 * (size_t)j + 2] - zi;
+        ia_min_image(C, dx, dy);
         take = dx * dx + dy * dy + dz * dz <= cut2;
       }
     }
@@ -117,11 +169,13 @@ __device__ __forceinline__ void ia_tab_eval(const IaTab &T, double x, double &U,
 // TAB: bit 0 pair table PT, bit 1 height table HT (both ignored in the TAB = 0 instantiation, the model of weight, wall and
 // steric repulsion alone).  A pair is counted once when it lies inside the cutoff of a pair term that is on; the built-in
 // term is switched off by p.rc2 < 0
-template <int TAB>
+// PER: the pair displacement by minimum image in the cell C (every blob pair on its own: the check at the evaluation makes
+// the convention unique inside the cutoff)
+template <int TAB, bool PER = false>
 __device__ __forceinline__ void ia_blob_interactions(double (*s)[4], const double *__restrict__ pos, const int *__restrict__ cnt,
                                                      const int *__restrict__ list, int cap, int N_blb, int tiles, const IaParams &p,
                                                      const IaTab &PT, const IaTab &HT, double *__restrict__ f,
-                                                     double *__restrict__ e, int *__restrict__ npairs)
+                                                     double *__restrict__ e, int *__restrict__ npairs, const IaCell &C = IaCell{})
 {
   const int i = blockIdx.x / tiles, k = (blockIdx.x - i * tiles) * blockDim.x + threadIdx.x;
   const bool own = k < N_blb;
@@ -143,7 +197,9 @@ __device__ __forceinline__ void ia_blob_interactions(double (*s)[4], const doubl
       __syncthreads();
       if (!own) continue;
       for (int u = 0; u < m; ++u) {
-        const double dx = xi - s[u][0], dy = yi - s[u][1], dz = zi - s[u][2];
+        double dx = xi - s[u][0], dy = yi - s[u][1];
+        const double dz = zi - s[u][2];
+        if constexpr (PER) ia_min_image(C, dx, dy);
         const double r2 = dx * dx + dy * dy + dz * dz;
         if constexpr (TAB & 1) {
           if (r2 > p.rc2 && r2 > PT.hi2) continue;       // beyond both cutoffs (hi2: a hair above hi^2, r <= hi decides)
@@ -220,6 +276,18 @@ __global__ __launch_bounds__(IA_BT) void k_blob_interactions_tab(const double *_
   static_assert(TAB >= 1 && TAB <= 3, "bit 0: pair table, bit 1: height table");
   __shared__ double s[IA_CHUNK][4];
   ia_blob_interactions<TAB>(s, pos, cnt, list, cap, N_blb, tiles, p, PT, HT, f, e, npairs);
+}
+
+// the pair kernel of a periodic cell, TAB = 0 ... 3 as above
+template <int TAB>
+__global__ __launch_bounds__(IA_BT) void k_blob_interactions_per(const double *__restrict__ pos, const int *__restrict__ cnt,
+                                                                 const int *__restrict__ list, int cap, int N_blb, int tiles,
+                                                                 IaParams p, IaTab PT, IaTab HT, IaCell C, double *__restrict__ f,
+                                                                 double *__restrict__ e, int *__restrict__ npairs)
+{
+  static_assert(TAB >= 0 && TAB <= 3, "bit 0: pair table, bit 1: height table");
+  __shared__ double s[IA_CHUNK][4];
+  ia_blob_interactions<TAB, true>(s, pos, cnt, list, cap, N_blb, tiles, p, PT, HT, f, e, npairs, C);
 }
 
 // harmonic traps on the body centres: FT[6 i + c] -= k_c (X_c - X0_c), the energy added to the entry of the body's first blob
@@ -448,6 +516,67 @@ __global__ __launch_bounds__(256) void k_bond_state(const double *__restrict__ X
   out[2 * tot + g] = U;
 }
 
+// the same with the pair displacement by minimum image (a periodic cell): its own kernel for the reason given at
+// k_body_neighbours_per
+template <int NT>
+__global__ __launch_bounds__(NT) void k_body_dipoles_per(const double *__restrict__ X, const double *__restrict__ Q,
+                                                     const double *__restrict__ mb, const double *__restrict__ tf,
+                                                     const int *__restrict__ accepted, int win, int N_blb, IaMag M, IaCell C,
+                                                     double *__restrict__ FT, double *__restrict__ e)
+{
+  __shared__ double red[7][NT];
+  const int i = blockIdx.x, t = threadIdx.x;
+  const int jb = i - i % win;
+  double mi[3];
+  ia_lab_moment(Q, mb, i, M.per_m, mi);
+  const double xi = X[3 * (size_t)i], yi = X[3 * (size_t)i + 1], zi = X[3 * (size_t)i + 2];
+  double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // force, torque, sum of the pair energies
+  if (M.pairs) {
+    for (int j = jb + t; j < jb + win; j += NT) {
+      if (j == i) continue;
+      double rx = xi - X[3 * (size_t)j], ry = yi - X[3 * (size_t)j + 1];
+      const double rz = zi - X[3 * (size_t)j + 2];
+      ia_min_image(C, rx, ry);
+      const double d2 = rx * rx + ry * ry + rz * rz;
+      const double d = sqrt(d2);
+      if (d > M.r_cut) continue;                         // skipped, not multiplied by zero (r_cut = +inf: every pair)
+      double mj[3];
+      ia_lab_moment(Q, mb, j, M.per_m, mj);
+      const bool core = d < M.r_core;                    // below the core s is the constant r_core: U is a quadratic form in r
+      const double is = 1.0 / (core ? M.r_core : d), is2 = is * is, is3 = is2 * is, is5 = is3 * is2;
+      const double a = mi[0] * rx + mi[1] * ry + mi[2] * rz, b = mj[0] * rx + mj[1] * ry + mj[2] * rz;
+      const double mm = mi[0] * mj[0] + mi[1] * mj[1] + mi[2] * mj[2];
+      const double k5 = 3.0 * M.c_dd * is5;
+      const double kr = core ? 0.0 : mm - 5.0 * a * b * is2;       // d >= r_core > 0: 1 / d^2 = is2
+      acc[0] += k5 * (a * mj[0] + b * mi[0] + kr * rx);
+      acc[1] += k5 * (a * mj[1] + b * mi[1] + kr * ry);
+      acc[2] += k5 * (a * mj[2] + b * mi[2] + kr * rz);
+      const double gb = k5 * b, g3 = M.c_dd * is3;               // the partner's field at i: gb r - g3 m_j
+      const double hx = gb * rx - g3 * mj[0], hy = gb * ry - g3 * mj[1], hz = gb * rz - g3 * mj[2];
+      acc[3] += mi[1] * hz - mi[2] * hy;
+      acc[4] += mi[2] * hx - mi[0] * hz;
+      acc[5] += mi[0] * hy - mi[1] * hx;
+      acc[6] += M.c_dd * (mm * is3 - 3.0 * a * b * is5);
+    }
+    rbl_block_sum<7, NT>(acc, red, t);
+  }
+  if (t != 0) return;
+  double E = 0.5 * acc[6];                               // every body carries half of each of its pair energies
+  if (M.field) {
+    double B[3];
+    ia_field_B(M, tf, accepted, i / win, B);
+    acc[3] += mi[1] * B[2] - mi[2] * B[1];
+    acc[4] += mi[2] * B[0] - mi[0] * B[2];
+    acc[5] += mi[0] * B[1] - mi[1] * B[0];
+    E -= mi[0] * B[0] + mi[1] * B[1] + mi[2] * B[2];
+  }
+  if (FT) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) FT[6 * (size_t)i + c] += acc[c];
+  }
+  if (e) e[(size_t)i * N_blb] += E;
+}
+
 struct IaLayout {
   double *f, *e, *ft;
   int *cnt, *list, *np;
@@ -630,6 +759,34 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   const bool bonds = ia_bonds(c);
   int rc;
   if (bonds && (rc = ia_bond_check(c, "interactions", win, n_win))) return rc;
+  // a periodic cell (include/rbl.h section 10): minimum image in the neighbour search, the blob pair terms and the dipole pairs.
+  // The convention is unique only while no pair inside a cutoff has a second image inside it: blobs of two bodies lie within
+  // 2 R_body + r_cut of each other's centres, dipoles sit on the centres themselves
+  IaCell C = {};
+  if (periodic_on(c)) {
+    double R2b = 0.0;
+    for (int k = 0; k < S.N_blb; ++k) {
+      const double *q = &S.ref_cfg[3 * (size_t)k];
+      R2b = std::max(R2b, q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+    }
+    const double rc_pair = std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0);
+    const double need_pair = (c->ia_on || c->ia_pt.on) ? 2.0 * std::sqrt(R2b) + rc_pair : 0.0;
+    const double need_dp = dp_pairs ? c->ia_dp_rcut : 0.0;
+    for (int k = 0; k < 2; ++k) {
+      const double Lk = c->per_L[k];
+      if (!(Lk > 0.0)) continue;
+      const std::string Ln = std::string("L") + (k ? "y" : "x") + " = " + std::to_string(Lk);
+      if (need_pair > 0.5 * Lk)
+        return rbl_fail(c, RBL_ERR_ARG, "interactions: periodic cell too small: " + Ln + " needs 2 R_body + r_cut = " + std::to_string(need_pair) +
+                                            " <= L / 2 = " + std::to_string(0.5 * Lk) + " for a unique minimum image");
+      if (need_dp > 0.5 * Lk)
+        return rbl_fail(c, RBL_ERR_ARG, "interactions: periodic cell too small: " + Ln + " needs the dipole r_cut = " + std::to_string(need_dp) +
+                                            " <= L / 2 = " + std::to_string(0.5 * Lk) + " for a unique minimum image");
+    }
+    C.Lx = c->per_L[0]; C.Ly = c->per_L[1];
+    C.px = C.Lx > 0.0 ? 1 : 0; C.py = C.Ly > 0.0 ? 1 : 0;
+    C.iLx = C.px ? 1.0 / C.Lx : 0.0; C.iLy = C.py ? 1.0 / C.Ly : 0.0;
+  }
   if ((rc = ia_upload(c))) return rc;
   if (dp && (rc = ia_mag_upload(c))) return rc;
   if (bonds && (rc = ia_bond_upload(c))) return rc;
@@ -644,8 +801,13 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   // distances: it can only add candidates, whose pairs beyond the cutoffs are then skipped one by one
   const double rc_max = std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0);
   const double cut = (2.0 * std::sqrt(R2) + rc_max) * (1.0 + 1e-12) + 1e-12;
-  hipLaunchKernelGGL(k_body_neighbours, dim3(nbod), dim3(64), 0, c->stream, d_X, nbod, win, cut * cut, c->ia_cull ? 1 : 0, cap,
-                     L.cnt, L.list, d_err);
+  const bool per = periodic_on(c);
+  if (per)
+    hipLaunchKernelGGL(k_body_neighbours_per, dim3(nbod), dim3(64), 0, c->stream, d_X, nbod, win, cut * cut, c->ia_cull ? 1 : 0, cap,
+                       C, L.cnt, L.list, d_err);
+  else
+    hipLaunchKernelGGL(k_body_neighbours, dim3(nbod), dim3(64), 0, c->stream, d_X, nbod, win, cut * cut, c->ia_cull ? 1 : 0, cap,
+                       L.cnt, L.list, d_err);
   IaParams P;
   P.w = c->ia_w; P.a = S.a; P.eps_w = c->ia_eps_wall; P.inv_bw = 1.0 / c->ia_b_wall; P.eps_b = c->ia_eps_blob;
   P.inv_bb = 1.0 / c->ia_b_blob; P.two_a = 2.0 * S.a; P.rc2 = c->ia_r_cut * c->ia_r_cut; P.wall = S.wall ? 1 : 0;
@@ -658,13 +820,22 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
 #define RBL_IA_TAB(K)                                                                                                              \
   hipLaunchKernelGGL(k_blob_interactions_tab<K>, grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt, (const int *)L.list, cap, \
                      S.N_blb, tiles, P, PT, HT, d_f, d_e, L.np)
-  if (tab == 0)
+#define RBL_IA_PER(K)                                                                                                              \
+  hipLaunchKernelGGL(k_blob_interactions_per<K>, grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt, (const int *)L.list, cap, \
+                     S.N_blb, tiles, P, PT, HT, C, d_f, d_e, L.np)
+  if (per) {
+    if (tab == 0) RBL_IA_PER(0);
+    else if (tab == 1) RBL_IA_PER(1);
+    else if (tab == 2) RBL_IA_PER(2);
+    else RBL_IA_PER(3);
+  } else if (tab == 0)
     hipLaunchKernelGGL(k_blob_interactions, grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt, (const int *)L.list, cap,
                        S.N_blb, tiles, P, d_f, d_e, L.np);
   else if (tab == 1) RBL_IA_TAB(1);
   else if (tab == 2) RBL_IA_TAB(2);
   else RBL_IA_TAB(3);
 #undef RBL_IA_TAB
+#undef RBL_IA_PER
   if (d_FT) rbl_launch_KT_x_Lam(c->stream, d_lever, d_f, S.N_blb, nbod, d_FT);
   if (c->ia_tr_on && (d_FT || d_e)) {
     const double *k3 = T + c->ia_pt.coef.size() + c->ia_ht.coef.size() + c->ia_bt.coef.size();
@@ -678,12 +849,18 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
     M.pairs = dp_pairs ? 1 : 0; M.field = dp_field ? 1 : 0;
     M.per_m = (int)ndm; M.per_t = n_win > 1 ? (int)nft : 1;  // a single context uses entry 0
     const double *mb = (const double *)c->d_iam.p, *tf = mb + 3 * ndm;
-    if (win > 512)
+    if (!per && win > 512)
       hipLaunchKernelGGL(k_body_dipoles<256>, dim3((unsigned)nbod), dim3(256), 0, c->stream, d_X, d_Q, mb, tf, d_accepted, win,
                          S.N_blb, M, d_FT, d_e);
-    else
+    else if (!per)
       hipLaunchKernelGGL(k_body_dipoles<64>, dim3((unsigned)nbod), dim3(64), 0, c->stream, d_X, d_Q, mb, tf, d_accepted, win,
                          S.N_blb, M, d_FT, d_e);
+    else if (win > 512)
+      hipLaunchKernelGGL(k_body_dipoles_per<256>, dim3((unsigned)nbod), dim3(256), 0, c->stream, d_X, d_Q, mb, tf, d_accepted, win,
+                         S.N_blb, M, C, d_FT, d_e);
+    else
+      hipLaunchKernelGGL(k_body_dipoles_per<64>, dim3((unsigned)nbod), dim3(64), 0, c->stream, d_X, d_Q, mb, tf, d_accepted, win,
+                         S.N_blb, M, C, d_FT, d_e);
   }
   if (bonds && (d_FT || d_e)) {
     const IaBonds B = ia_bond_args(c, n_win);

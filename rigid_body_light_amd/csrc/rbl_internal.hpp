@@ -279,6 +279,11 @@ struct rbl_ctx {
   RblDevBuf d_jtw;                                  // a jointed solve's vectors: rhs | x | (0, J^T phi) | its preconditioned image | lever arms and gaps
   RblDevBuf d_jtphi;                                // phi of the last jointed solve or step (jt_phi_valid), the state query's gaps
   bool jt_phi_valid = false;
+  // periodic cell in x and y (rbl_periodic.hip; include/rbl.h section 10): explicit image sums of the wall-corrected product,
+  // minimum image in the pair forces.  A length of 0: that axis is open (its image count is stored as 0)
+  bool per_on = false;
+  double per_L[2] = {0.0, 0.0};
+  int per_n[2] = {0, 0};
   // lanczos
   int lanczos_max_iter = 100;
   bool lanczos_out_norm = true;  // preconditioned root: final stopping test in the Euclidean norm of the increment (RBL_OPT_LANCZOS_EUCLID_NORM)
@@ -320,6 +325,11 @@ void rbl_launch_apply_M(hipStream_t st, const RblParams &P, bool wall, const dou
                         const double *d_r, int64_t n_blobs, int64_t row_begin,
                         int64_t row_end, double *d_out, double *d_part, int jsplit,
                         int variant, unsigned *d_err);
+// the ordered-pair product of a periodic cell (wall only): every pair summed over its (2 nx + 1)(2 ny + 1) images about the
+// nearest one.  Lx, Ly in physical units (0: that axis is open, its n is 0); grid, j-split and d_part as rbl_launch_apply_M
+void rbl_launch_apply_M_per(hipStream_t st, const RblParams &P, const double *d_F, const double *d_r, int64_t n_blobs,
+                            int64_t row_begin, int64_t row_end, double *d_out, double *d_part, int jsplit, double Lx, double Ly,
+                            int nx, int ny, unsigned *d_err);
 size_t rbl_apply_M_sym_bytes(int64_t n_blobs, int n_cu, int i_step, int nrhs, const RblSymTune &tune,
                              int *NI_out = nullptr, int *C_out = nullptr);
 long rbl_apply_M_sym_units(int64_t n_blobs, int n_cu, int i_step, int nrhs, const RblSymTune &tune, int64_t *out, long cap, int *info);

@@ -7,6 +7,8 @@
 //   k_apply_M<WALL>         the same product by ordered pairs for a ROW RANGE (row sharding,
 //                           very large N): j tiles staged in LDS, lane = row, LDS broadcast;
 //                           j-split partial slabs reduced by k_reduce_parts
+//   k_apply_M_per<PX,PY>    the ordered-pair product of a periodic cell in x and / or y (wall only): nearest-image reduction
+//                           once per pair, the image loop innermost, k_apply_M's grid, j-split and epilogue
 //   k_apply_M_mrhs<WALL>    16 right-hand sides: pair blocks on the VALU, nine v_mfma_f64_16x16x4
 //                           per step apply them (k_pack_rhs / k_unpack_rhs transpose the vectors)
 //   k_build_M<WALL>         dense column-major assembly (reference :413-459), HBM-write bound,
@@ -157,6 +159,106 @@ __global__ __launch_bounds__(256) void k_reduce_parts(const double *__restrict__
   if (WALL) sc *= damp_of(P, r[3 * (row_begin + idx / 3) + 2]);
   out[idx] = sc * s;
   if (!isfinite(s)) atomicOr(err, (unsigned)RBL_FLAG_NONFINITE);
+}
+
+// ---------------------------------------------------------------------------
+// The ordered-pair product of a periodic cell in x and / or y (include/rbl.h section 10), wall only:
+//     U_i = sum_j sum_{|p| <= nx} sum_{|q| <= ny}  B(d0_ij + (p Lx, q Ly, 0); z_i, z_j) F_j,
+// d0 the nearest-image displacement.  Grid, j-split, LDS tile and epilogue are k_apply_M's (k_reduce_parts adds the slabs).
+// Per pair: ONE LDS read of the j blob, the nearest-image reduction in radius-scaled coordinates (a multiply, a rint and an fma
+// per periodic axis; PX / PY = false compiles an open axis' reduction out: no 1 / 0), then the image loop innermost.
+// The self term is (p, q) = (0, 0) of the pair with equal indices and nothing else: a blob's own images are ordinary pairs of two
+// blobs at one height.  Ragged tiles end the j loop early instead of padding it: a padded slot "far away" would be folded into
+// the cell by the reduction and land on somebody.  One summation order (j, then p, then q), no atomics on doubles.
+// ---------------------------------------------------------------------------
+struct PerCell {
+  double Lx, Ly, iLx, iLy;   // radius-scaled lengths and their reciprocals (0 on an open axis)
+  int nx, ny;
+};
+
+template <bool SELF, bool PX, bool PY>
+__device__ __forceinline__ void sweep_tile_per(const RblParams &P, const JBlob *sj, int njj, double xi, double yi, double zi,
+                                               int self_jj, const PerCell &C, double &ux, double &uy, double &uz, unsigned &flags,
+                                               const RblWallK &K)
+{
+  for (int jj = 0; jj < njj; ++jj) {
+    const JBlob b = sj[jj];
+    double dx = xi - b.x, dy = yi - b.y;
+    if (PX) dx = __builtin_fma(-C.Lx, rint(dx * C.iLx), dx);
+    if (PY) dy = __builtin_fma(-C.Ly, rint(dy * C.iLy), dy);
+    for (int p = -C.nx; p <= C.nx; ++p) {
+      const double x = PX ? __builtin_fma((double)p, C.Lx, dx) : dx;
+      for (int q = -C.ny; q <= C.ny; ++q) {
+        const double y = PY ? __builtin_fma((double)q, C.Ly, dy) : dy;
+        if (SELF && p == 0 && q == 0)   // wave-uniform
+          rbl_pair_accum<true, true, true>(P, x, y, zi, 0.0, 0.0, b.z, b.fx, b.fy, b.fz, jj == self_jj, ux, uy, uz, flags, K);
+        else
+          rbl_pair_accum<true, false, true>(P, x, y, zi, 0.0, 0.0, b.z, b.fx, b.fy, b.fz, false, ux, uy, uz, flags, K);
+      }
+    }
+  }
+}
+
+template <bool PX, bool PY>
+__global__ __launch_bounds__(TB) void k_apply_M_per(const double *__restrict__ r, const double *__restrict__ F,
+                                                    double *__restrict__ out, double *__restrict__ part, long N, long row_begin,
+                                                    long row_end, long jchunk, int jsplit, RblParams P, PerCell C, unsigned *err)
+{
+  __shared__ JBlob sj[TB];
+  const int t = threadIdx.x;
+  const long i_tile0 = row_begin + (long)blockIdx.x * TB;
+  const long i = i_tile0 + t;
+  const bool valid = i < row_end;
+  const long ic = valid ? i : row_end - 1;
+  const double zi_phys = r[3 * ic + 2];
+  const double xi = r[3 * ic] * P.inv_a, yi = r[3 * ic + 1] * P.inv_a, zi = zi_phys * P.inv_a;   // radius-scaled
+  const RblParams Pu = unit_params(P);
+  const RblWallK WK = rbl_wall_k_resident();
+  unsigned flags = 0;
+  if (zi < 0.0) flags |= RBL_FLAG_BELOW_WALL;
+
+  const long j_begin = (long)blockIdx.y * jchunk;
+  const long j_end = (j_begin + jchunk < N) ? j_begin + jchunk : N;
+  double ux = 0.0, uy = 0.0, uz = 0.0;
+
+  for (long j0 = j_begin; j0 < j_end; j0 += TB) {
+    const long j = j0 + t;
+    const int njj = (int)((j_end - j0 < TB) ? j_end - j0 : TB);   // block-uniform: the slots beyond are never read
+    JBlob b = {0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+    if (j < j_end) {
+      b.x = r[3 * j]; b.y = r[3 * j + 1]; b.z = r[3 * j + 2];
+      if (b.z < 0.0) flags |= RBL_FLAG_BELOW_WALL;
+      const double d = damp_of(P, b.z);
+      b.x *= P.inv_a; b.y *= P.inv_a; b.z *= P.inv_a;
+      b.fx = d * F[3 * j]; b.fy = d * F[3 * j + 1]; b.fz = d * F[3 * j + 2];
+    }
+    __syncthreads();  // previous tile fully consumed
+    sj[t] = b;
+    __syncthreads();
+    const bool diag = (j0 < i_tile0 + TB) && (j0 + TB > i_tile0);  // block-uniform
+    if (diag) {
+      const long sjj = i - j0;
+      const int self_jj = (valid && sjj >= 0 && sjj < TB) ? (int)sjj : -1;
+      sweep_tile_per<true, PX, PY>(Pu, sj, njj, xi, yi, zi, self_jj, C, ux, uy, uz, flags, WK);
+    } else {
+      sweep_tile_per<false, PX, PY>(Pu, sj, njj, xi, yi, zi, -1, C, ux, uy, uz, flags, WK);
+    }
+  }
+
+  if (valid) {
+    const long o = 3 * (i - row_begin);
+    if (jsplit == 1) {
+      const double sc = P.nf * damp_of(P, zi_phys);
+      out[o] = sc * ux; out[o + 1] = sc * uy; out[o + 2] = sc * uz;
+      if (!(isfinite(ux) && isfinite(uy) && isfinite(uz))) flags |= RBL_FLAG_NONFINITE;
+    } else {
+      double *p = part + (size_t)blockIdx.y * (size_t)(3 * (row_end - row_begin)) + o;
+      p[0] = ux; p[1] = uy; p[2] = uz;
+    }
+  } else {
+    flags &= ~RBL_FLAG_OVERLAP;  // clamped duplicate row: ignore its pair checks
+  }
+  if (flags) atomicOr(err, flags);
 }
 
 
@@ -1846,6 +1948,36 @@ void rbl_launch_apply_M(hipStream_t st, const RblParams &P, bool wall, const dou
     else
       hipLaunchKernelGGL(k_reduce_parts<false>, g2, b2, 0, st, d_part, d_r, d_out,
                          (long)row_begin, (long)nrows, js_eff, P, d_err);
+  }
+}
+
+void rbl_launch_apply_M_per(hipStream_t st, const RblParams &P, const double *d_F, const double *d_r, int64_t n_blobs,
+                            int64_t row_begin, int64_t row_end, double *d_out, double *d_part, int jsplit, double Lx, double Ly,
+                            int nx, int ny, unsigned *d_err)
+{
+  const int64_t nrows = row_end - row_begin;
+  if (nrows <= 0 || n_blobs <= 0) return;
+  const int64_t itiles = (nrows + TB - 1) / TB;
+  const int64_t jtiles = (n_blobs + TB - 1) / TB;
+  const int64_t jchunk = ((jtiles + jsplit - 1) / jsplit) * TB;
+  const int js_eff = (int)((n_blobs + jchunk - 1) / jchunk);
+  const bool px = Lx > 0.0, py = Ly > 0.0;
+  PerCell C;
+  C.Lx = px ? Lx * P.inv_a : 0.0; C.Ly = py ? Ly * P.inv_a : 0.0;
+  C.iLx = px ? 1.0 / C.Lx : 0.0; C.iLy = py ? 1.0 / C.Ly : 0.0;
+  C.nx = px ? nx : 0; C.ny = py ? ny : 0;
+  dim3 grid((unsigned)itiles, (unsigned)js_eff), block(TB);
+#define RBL_PER_LAUNCH(PX, PY)                                                                                                  \
+  hipLaunchKernelGGL((k_apply_M_per<PX, PY>), grid, block, 0, st, d_r, d_F, d_out, d_part, (long)n_blobs, (long)row_begin,       \
+                     (long)row_end, (long)jchunk, js_eff, P, C, d_err)
+  if (px && py) RBL_PER_LAUNCH(true, true);
+  else if (px) RBL_PER_LAUNCH(true, false);
+  else RBL_PER_LAUNCH(false, true);
+#undef RBL_PER_LAUNCH
+  if (js_eff > 1) {
+    const int64_t n = 3 * nrows;
+    dim3 g2((unsigned)((n + 255) / 256)), b2(256);
+    hipLaunchKernelGGL(k_reduce_parts<true>, g2, b2, 0, st, d_part, d_r, d_out, (long)row_begin, (long)nrows, js_eff, P, d_err);
   }
 }
 

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <string>
 
 #include <vector>
 
@@ -24,12 +25,32 @@ static RblSymTune launch_tune(const rbl_ctx *c, const RblProductReq &rq)
   return tune;
 }
 
+// the product of a periodic cell (include/rbl.h section 10): the ordered image-sum kernel for every call, fp64 only (a relaxed
+// request is ignored), never fused: callers run their separate saddle epilogue as after the ordered kernel
+static int apply_M_per_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double *d_r, int64_t nbl, int64_t row_begin,
+                               int64_t row_end, double *d_out, const RblProductReq &rq)
+{
+  if (!wall) return rbl_fail(c, RBL_ERR_STATE, "periodic cell: the wall term is off, and the free-space lattice sum diverges (rbl_set_wall_pc)");
+  for (int k = 0; k < 2; ++k)
+    if (c->per_L[k] > 0.0 && !(c->per_L[k] > 4.0 * c->S.a))
+      return rbl_fail(c, RBL_ERR_STATE, std::string("periodic cell: L") + (k ? "y" : "x") + " = " + std::to_string(c->per_L[k]) +
+                                            " no longer exceeds 4a of the current parameters (call rbl_set_periodic again)");
+  int js = 1, rc;
+  const size_t pb = rbl_apply_M_part_bytes(nbl, row_end - row_begin, c->n_cu, c->tune_jsplit, &js);
+  if ((rc = rbl_dev_reserve(c, c->d_part, pb))) return rc;
+  RblPhase ph(c, RBL_T_PRODUCT);
+  rbl_launch_apply_M_per(c->stream, ctx_params(c, rq.undamped), d_F, d_r, nbl, row_begin, row_end, d_out, (double *)c->d_part.p, js,
+                         c->per_L[0], c->per_L[1], c->per_n[0], c->per_n[1], c->d_err);
+  return RBL_OK;
+}
+
 int apply_M_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double *d_r, int64_t nbl,
                            int64_t row_begin, int64_t row_end, double *d_out, RblProductReq *rq)
 {
   RblProductReq plain;
   if (!rq) rq = &plain;
   rq->fused = false;
+  if (periodic_on(c)) return apply_M_per_enqueue(c, wall, d_F, d_r, nbl, row_begin, row_end, d_out, *rq);
   const RblParams P = ctx_params(c, rq->undamped);
   RblSymTune tune = launch_tune(c, *rq);
   const bool full = (row_begin == 0 && row_end == nbl);
@@ -101,6 +122,13 @@ int apply_M_multi_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double
   const int64_t n3 = 3 * nbl;
   if (ldF <= 0) ldF = n3;                               // doubles between consecutive vectors (default: packed)
   if (ldO <= 0) ldO = n3;
+  if (periodic_on(c)) {                                  // a periodic cell: the vectors one at a time through its kernel
+    for (int k = 0; k < nrhs; ++k) {
+      const int rc1 = apply_M_enqueue(c, wall, d_F + (size_t)k * (size_t)ldF, d_r, nbl, 0, nbl, d_out + (size_t)k * (size_t)ldO, rq);
+      if (rc1) return rc1;
+    }
+    return RBL_OK;
+  }
   if (ldF != n3 || ldO != n3) {                          // strided vectors (the lock-step GMRES): one at a time unless the MFMA kernel takes them
     bool mf = nrhs >= 4;
     if (c->tune_variant == 3) mf = true;
@@ -275,6 +303,7 @@ int rbl_apply_M_multi(rbl_ctx *c, const double *F, const double *r_vecs, int64_t
 int rbl_rotne_prager_tensor(rbl_ctx *c, const double *r, int64_t n3, int scale_damp, double *out)
 {
   int rc = need_params(c); if (rc) return rc;
+  if ((rc = periodic_refuse(c, "rotne_prager_tensor"))) return rc;
   if (n3 <= 0 || n3 % 3 != 0) return rbl_fail(c, RBL_ERR_SIZE, "r_vecs must have length 3N");
   rc = rbl_dev_init(c); if (rc) return rc;
   const size_t mb = sizeof(double) * (size_t)n3 * (size_t)n3;
@@ -344,6 +373,7 @@ int rbl_apply_M_sym_multi_dev(rbl_ctx *c, const double *d_F, const double *d_r, 
                               int i_first, int i_step, double *d_out)
 {
   int rc = need_params(c); if (rc) return rc;
+  if ((rc = periodic_refuse(c, "apply_M_sym_multi_dev"))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (n_blobs <= 0 || i_step < 1 || i_first < 0 || i_first >= i_step || nrhs < 1 || nrhs > 2)
     return rbl_fail(c, RBL_ERR_SIZE, "apply_M_sym_multi_dev: need n_blobs > 0, 0 <= i_first < i_step, nrhs 1 or 2");
@@ -358,6 +388,7 @@ int rbl_apply_M_sym_dev(rbl_ctx *c, const double *d_F, const double *d_r, int64_
                         int i_step, double *d_out)
 {
   int rc = need_params(c); if (rc) return rc;
+  if ((rc = periodic_refuse(c, "apply_M_sym_dev"))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (n_blobs <= 0 || i_step < 1 || i_first < 0 || i_first >= i_step)
     return rbl_fail(c, RBL_ERR_SIZE, "apply_M_sym_dev: need n_blobs > 0 and 0 <= i_first < i_step");
@@ -408,6 +439,7 @@ int rbl_rotne_prager_tensor_dev(rbl_ctx *c, const double *d_r, int64_t n_blobs, 
                                 double *d_out)
 {
   int rc = need_params(c); if (rc) return rc;
+  if ((rc = periodic_refuse(c, "rotne_prager_tensor_dev"))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   rbl_launch_build_M(c->stream, rbl_make_params(c->S.a, c->S.eta), c->S.wall, scale_damp != 0, d_r,
                      n_blobs, d_out, c->d_err);

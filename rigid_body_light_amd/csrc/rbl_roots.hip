@@ -439,6 +439,7 @@ int mhalf_dev_multi(rbl_ctx *c, const double *d_r, int64_t nbl, const double *d_
 {
   const int64_t n = 3 * nbl;
   int rc;
+  if (method == RBL_MHALF_CHOLESKY && (rc = periodic_refuse(c, "M_half_W (dense Cholesky method)"))) return rc;
   RblPhase ph_total(c, RBL_T_TOTAL);
   if (method == RBL_MHALF_LANCZOS || method == RBL_MHALF_LANCZOS_PC) {
     const bool pc = method == RBL_MHALF_LANCZOS_PC;
@@ -483,6 +484,7 @@ int rbl_M_half_W_dev(rbl_ctx *c, const double *d_r, int64_t n_blobs, const doubl
                      double *d_out)
 {
   int rc = need_params(c); if (rc) return rc;
+  if (method == RBL_MHALF_CHOLESKY && (rc = periodic_refuse(c, "M_half_W_dev (dense Cholesky method)"))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (n_blobs <= 0) return rbl_fail(c, RBL_ERR_SIZE, "M_half_W_dev: n_blobs must be positive");
   return mhalf_dev(c, d_r, n_blobs, d_W, method, d_out);
@@ -493,6 +495,7 @@ int rbl_M_half_W_r(rbl_ctx *c, const double *r, int64_t n3, const double *W, uin
 {
   int rc = need_params(c); if (rc) return rc;
   if (n3 <= 0 || n3 % 3 != 0) return rbl_fail(c, RBL_ERR_SIZE, "r_vecs must have length 3N");
+  if (method == RBL_MHALF_CHOLESKY && (rc = periodic_refuse(c, "M_half_W_r (dense Cholesky method)"))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   const size_t vb = sizeof(double) * (size_t)n3;
   if ((rc = rbl_dev_reserve(c, c->d_r, vb))) return rc;
@@ -509,6 +512,7 @@ int rbl_M_half_W_r(rbl_ctx *c, const double *r, int64_t n3, const double *W, uin
 int rbl_M_half_W(rbl_ctx *c, const double *W, uint64_t seed, int method, double *out)
 {
   int rc = need_config(c); if (rc) return rc;
+  if (method == RBL_MHALF_CHOLESKY && (rc = periodic_refuse(c, "M_half_W (dense Cholesky method)"))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb;  // :663
   const size_t vb = sizeof(double) * (size_t)n3;

@@ -92,7 +92,7 @@ int rbl_gmres_saddle_dev(rbl_ctx *c, const double *d_rhs, int max_iter, double r
     int rc = need_config(c); if (rc) return rc;
     if ((rc = rbl_dev_init(c))) return rc;
     if (!d_rhs || !d_x || max_iter < 1) return rbl_fail(c, RBL_ERR_ARG, "gmres: bad arguments");
-    if (c->gmres_small && !comm_on(c) && rbl_gmres_small_fits(c->S.N_blb, c->S.N_bod, max_iter, c->S.block_pc)) {
+    if (c->gmres_small && !comm_on(c) && !periodic_on(c) && rbl_gmres_small_fits(c->S.N_blb, c->S.N_bod, max_iter, c->S.block_pc)) {
       rc = gmres_small(c, d_rhs, use_x0 ? d_x : nullptr, max_iter, rtol, d_x, iters_out, resid_out);
       if (rc != RBL_ERR_SIZE) return rc;
       c->gmres_small = false;                // this runtime does not grant the LDS the one-kernel solver needs

@@ -286,6 +286,7 @@ int rhs_and_midpoint_core(rbl_ctx *c, const uint8_t *h_mask, const uint8_t *d_ma
     std::memcpy(Q_half, S.Q.data(), sizeof(double) * S.Q.size());
     return finish_and_check(c);
   }
+  if (method == RBL_MHALF_CHOLESKY && (rc = periodic_refuse(c, "Brownian step with the dense Cholesky root"))) return rc;
   // workspace: [W1 | W2 | W_rfd] (when drawn here), M^{1/2}W1, M^{1/2}W2, M_RFD, positions, 2 scratch, the sums per body
   if ((rc = rbl_dev_reserve(c, c->d_bd, 9 * vb + (d_mask ? 3 : 2) * sizeof(double) * (size_t)nb6))) return rc;
   double *base = (double *)c->d_bd.p;

@@ -338,6 +338,11 @@ class Ensemble:
         rows.  Hold replicas together with set_bonds"""
         raise ValueError("set_joints: hard joints are not offered for ensembles (include/rbl.h section 9); bonds are (set_bonds)")
 
+    def set_periodic(self, *args, **kwargs):
+        """a periodic cell (RigidBody.set_periodic) is not offered for ensembles: the one-kernel solver of the replicas has no
+        image sum"""
+        raise ValueError("set_periodic: a periodic cell is not offered for ensembles (include/rbl.h section 10)")
+
     def set_bond_table(self, U, dU, r_min, r_cut, on=True):
         """the potential of the kind-1 bonds of RigidBody.set_bond_table, one for all replicas"""
         self.ctx.set_bond_table(U, dU, r_min, r_cut, on=on)

@@ -22,7 +22,7 @@ and an imposed flow, a body-frame slip and stresslets (`set_background_flow`, `s
 import numpy as np
 
 from . import c_rigid as _ext
-from ._lib import DeviceContext, blob_anchor, bond_args, check_brownian_mask6, dipole_args, field_args, joint_args, table_arrays, tabulate  # noqa: F401
+from ._lib import DeviceContext, blob_anchor, bond_args, check_brownian_mask6, dipole_args, field_args, joint_args, periodic_args, table_arrays, tabulate  # noqa: F401
 
 _KBT_IN_WRAPPER = 1.0   # the reference wrapper passes kBT = 1 whatever the caller wants (src/Rigid.py:23)
 
@@ -325,6 +325,23 @@ class RigidBody:
     def joints(self):
         """-> {on, body (n_joints, 2), anchor_a (n_joints, 3), anchor_b (n_joints, 3)} (n_joints = 0: never set)"""
         return self.ctx.joints()
+
+    # -- periodic cell in x and y (include/rbl.h section 10) -----------------------------------------------------------------------
+    def set_periodic(self, Lx, Ly, images=(1, 1), on=True):
+        """A periodic cell of lengths Lx, Ly along x and y above the wall (0: that axis stays open): every mobility product --
+        apply_M, the solves, the Brownian roots and drift, every step -- sums the wall-corrected pair mobility over
+        images = (nx, ny) periodic images on either side of every pair's nearest one, and the pair forces (steric, pair table,
+        dipole pairs) use the minimum image.  Positions stay unwrapped.  The sum is truncated: its remainder falls like 1 / n, and
+        the nearest image alone (n = 0) is not positive definite, so a periodic axis takes 1 <= n <= 16.  Needs the wall; L must
+        exceed 4a; the force model needs 2 R_body + r_cut <= L / 2.  Bonds and joints join bodies at their unwrapped positions.
+        Not offered with the cell on (RuntimeError, "periodic"): the dense mobility and the dense Cholesky root, the velocity
+        field, ensembles, several GPUs."""
+        Lx, Ly, nx, ny = periodic_args("set_periodic", Lx, Ly, images)
+        self.ctx.set_periodic(Lx, Ly, images=(nx, ny), on=bool(on))
+
+    def periodic(self):
+        """-> {on, Lx, Ly, images (nx, ny)} (both lengths 0: never set)"""
+        return self.ctx.periodic()
 
     def _jointed_args(self, who, F_body, slip, jv, name):
         F, sl = self._body_in_and_slip(F_body, slip)
