@@ -1260,7 +1260,52 @@ int rbl_ensemble_step_moments(rbl_ctx *ctx, double *D);
  * Not offered, each refused before any device work: contexts with a communicator (RBL_ERR_ARG); contexts that hold an ensemble
  * (RBL_ERR_STATE; the ensemble entry points of section 5 ignore the joints like every other); and, having no entry point at
  * all: the jointed solve together with prescribed masks (section 7), lock-step right-hand sides, Brownian steps (the drift of a
- * constrained suspension has not been derived here), joint kinds other than the ball joint. */
+ * constrained suspension has not been derived here), joint kinds other than those below (no slider, no universal joint).
+ *
+ * Joint kinds.  rbl_set_joint_kinds is a superset of rbl_set_joints: one kind per joint, every joint keeps three rows and three
+ * unknowns, so every vector of this section keeps its length 3 n_joints.  With dw = w_A - w_B (w_B = 0 and Q_B = identity for
+ * body B = -1, the lab) and ah = R(Q_A) a the lab-frame image of a unit axis a fixed in body A:
+ *
+ *     kind                 rows (J U)_j                          load J^T phi of joint j
+ *     RBL_JOINT_BALL  0    (u_A + w_A x l_A) - (u_B + w_B x l_B)  as above
+ *     RBL_JOINT_LOCK  1    dw                                    torque +phi_j on A, -phi_j on B, no force
+ *     RBL_JOINT_AXIS  2    P dw,  P = I - ah ah^T                torque +P phi_j on A, -P phi_j on B, no force
+ *
+ * An axis joint leaves the relative rotation about ah free.  Its row along ah constrains nothing; so that the system stays
+ * regular without a pseudo-inverse, the operator's rows of that joint are P dw - sigma ah (ah . phi_j) and S gets sigma ah ah^T
+ * on that diagonal block (the minus sign makes the preconditioner's S = J N~^-1 J^T + sigma ah ah^T the exact Schur complement),
+ * sigma = the mean rotational diagonal entry of N~_A^-1.  The component of joint_rhs / joint_velocity along ah is IGNORED (the
+ * rows are projected with P before the solve) and the returned phi_j is P phi_j: its component along ah is zero to the rounding
+ * of that one projection, exactly zero when ah is a coordinate axis.  The answer does not depend on sigma.
+ * Compositions are the caller's: BALL + AXIS on one pair of bodies is a five-row hinge (no redundant row, unlike the two-ball
+ * hinge, which stays as it is), BALL + LOCK a weld, BALL + LOCK with a rate a motor or driven hinge.
+ *
+ * Orientation gap.  An angular joint stores q_rel (scalar first, normalised on entry) and, a lock, the axis a and a motor angle
+ * theta (0 when set).  The target orientation of body B is Q_B* = Q_A rot(theta a) q_rel (an axis joint: theta = 0), and the
+ * angular gap e is the lab-frame rotation vector of Q_B* Q_B^-1, the short way round (the quaternion's sign is flipped on a
+ * negative scalar part), so that de/dt = w_A - w_B to first order, as dg/dt = J U for a ball joint.  An axis joint uses P e.
+ * rbl_step_jointed sets c = -(gamma / dt) e + w on those rows, w the caller's joint_velocity rows plus, for a lock with the rate
+ * Omega_j, -Omega_j ah: body B turns relative to body A at +Omega_j about ah.  After an accepted step theta_j += Omega_j dt; a
+ * refused step changes nothing.
+ *
+ *   rbl_set_joint_kinds   body and anchor as rbl_set_joints; kind[n_joints]; axis[3 n_joints] (read for LOCK and AXIS,
+ *                    normalised); q_rel[4 n_joints] (read for LOCK and AXIS); anchor is read for BALL only (an angular joint's
+ *                    anchors read back as zeros).  Checks first, nothing stored unless all pass, no device touched.  RBL_ERR_ARG
+ *                    with the joint named for: an unknown kind; an axis that is not finite or of norm < 1e-12 where one is
+ *                    read; a q_rel of zero norm; a second angular joint on a pair of bodies (or on a body and the lab); an
+ *                    angular joint together with two ball joints on that pair; both ends on one body; and every refusal of
+ *                    rbl_set_joints.  At most 2048 joints.  Every pointer NULL with on = 0 only switches the joints off.
+ *   rbl_get_joint_kinds   reads everything back, theta and the rates included; any pointer may be NULL.  by_kinds: 1 when the
+ *                    stored set came through rbl_set_joint_kinds.  A set from rbl_set_joints reads back as BALL throughout.
+ *   rbl_set_joint_rates   rate[n_joints], context state read by rbl_step_jointed: a lock's Omega_j; must be 0 for every other
+ *                    kind (RBL_ERR_ARG, the joint named) and is 0 after rbl_set_joint_kinds.  May change from step to step.
+ *   rbl_joint_state_kinds rbl_joint_state and theta[n_joints] (may be NULL).  The gap rows of an angular joint hold e (P e for
+ *                    an axis joint); rbl_joint_state returns the same rows.
+ * rbl_solve_jointed[_dev], rbl_step_jointed and rbl_joint_state serve whichever joint set is stored.  A set without a lock or
+ * axis joint launches the kernels of the ball joint unchanged: the same bits whichever entry point stored it. */
+#define RBL_JOINT_BALL 0
+#define RBL_JOINT_LOCK 1
+#define RBL_JOINT_AXIS 2
 int rbl_set_joints(rbl_ctx *ctx, int n_joints, const int *body, const double *anchor, int on);
 int rbl_get_joints(const rbl_ctx *ctx, int *n_joints, int *on, int *body, double *anchor);
 int rbl_solve_jointed(rbl_ctx *ctx, const double *F_body, const double *slip, const double *joint_rhs, int max_iter, double rtol,
@@ -1270,6 +1315,12 @@ int rbl_solve_jointed_dev(rbl_ctx *ctx, const double *d_F_body, const double *d_
 int rbl_step_jointed(rbl_ctx *ctx, const double *F_body, const double *slip, const double *joint_velocity, double gamma, int max_iter,
                      double rtol, double *phi, int *iters, double *resid);
 int rbl_joint_state(rbl_ctx *ctx, double *gap, double *phi);
+int rbl_set_joint_kinds(rbl_ctx *ctx, int n_joints, const int *body, const double *anchor, const int *kind, const double *axis,
+                        const double *q_rel, int on);
+int rbl_get_joint_kinds(const rbl_ctx *ctx, int *n_joints, int *on, int *by_kinds, int *body, double *anchor, int *kind, double *axis,
+                        double *q_rel, double *theta, double *rate);
+int rbl_set_joint_rates(rbl_ctx *ctx, const double *rate);
+int rbl_joint_state_kinds(rbl_ctx *ctx, double *gap, double *phi, double *theta);
 
 /* ===================================================================== */
 /* 10. Periodic cell in x and y (rigid_body_light_amd/csrc/rbl_periodic.hip) */

@@ -113,6 +113,10 @@ def lib(path=None):
                                                                          C.POINTER(dbl)]
         L.rbl_step_jointed.argtypes = [vp, vp, vp, vp, dbl, C.c_int, dbl, vp, C.POINTER(C.c_int), C.POINTER(dbl)]
         L.rbl_joint_state.argtypes = [vp, vp, vp]
+        L.rbl_set_joint_kinds.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int]
+        L.rbl_get_joint_kinds.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, vp, vp, vp, vp, vp]
+        L.rbl_set_joint_rates.argtypes = [vp, vp]
+        L.rbl_joint_state_kinds.argtypes = [vp, vp, vp, vp]
         L.rbl_set_periodic.argtypes = [vp, dbl, dbl, C.c_int, C.c_int, C.c_int]
         L.rbl_get_periodic.argtypes = [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.rbl_interaction_forces_dev.argtypes = [vp, vp, vp, C.POINTER(dbl)]
@@ -255,6 +259,143 @@ def joint_args(who, body, anchor_a, anchor_b):
     or (n, 3)"""
     b, anchor, _, _ = bond_args(who, body, anchor_a, anchor_b, 0.0, 0.0, None)
     return b, anchor
+
+
+JOINT_BALL, JOINT_LOCK, JOINT_AXIS = 0, 1, 2          # RBL_JOINT_* of include/rbl.h section 9
+
+
+def quat_mul(p, q):
+    """Hamilton product of two quaternions (w, x, y, z): R(p q) = R(p) R(q)"""
+    import numpy as np
+    p, q = np.asarray(p, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    return np.concatenate([[p[0] * q[0] - p[1:] @ q[1:]], p[0] * q[1:] + q[0] * p[1:] + np.cross(p[1:], q[1:])])
+
+
+def quat_matrix(q):
+    """rotation matrix of a quaternion (w, x, y, z), normalised here: lab = R body"""
+    import numpy as np
+    w, x, y, z = np.asarray(q, dtype=np.float64) / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def relative_quat(Q, a, b):
+    """Q_A^-1 Q_B of the bodies a and b of the configuration's quaternions Q (N_bod, 4); b = -1, the lab: Q_B is the identity"""
+    import numpy as np
+    Q = np.asarray(Q, dtype=np.float64).reshape(-1, 4)
+    qa = Q[a] / np.linalg.norm(Q[a])
+    qb = np.array([1.0, 0.0, 0.0, 0.0]) if b < 0 else Q[b] / np.linalg.norm(Q[b])
+    return quat_mul(qa * [1.0, -1.0, -1.0, -1.0], qb)
+
+
+def joint_kind_args(who, body, kind, anchor_a=None, anchor_b=None, axis=None, q_rel=None):
+    """the checks set_joint_kinds can make before the library is called -> contiguous body int32 (n, 2), kind int32 (n,), anchor
+    float64 (n, 6), axis float64 (n, 3), q_rel float64 (n, 4).  kind: (n,) integers, JOINT_BALL, JOINT_LOCK or JOINT_AXIS;
+    anchors as set_joints takes them, needed when there is a ball joint; axis (3,) or (n, 3), in body A's frame, needed when
+    there is a lock or axis joint, finite and of norm >= 1e-12 on their rows; q_rel (4,) or (n, 4), of non-zero norm on those rows,
+    or None: the identity here, which the caller replaces by that of the configuration (default_q_rel) once every check has passed"""
+    import numpy as np
+    b = np.asarray(body)
+    if b.shape == (2,):
+        b = b.reshape(1, 2)
+    if b.ndim != 2 or b.shape[1] != 2 or not b.shape[0] or not np.issubdtype(b.dtype, np.integer):
+        raise ValueError("%s: body must be an integer array of shape (n, 2); got %s of dtype %s" % (who, b.shape, b.dtype))
+    n = b.shape[0]
+    k = np.asarray(kind)
+    if k.ndim == 0 and np.issubdtype(k.dtype, np.integer):
+        k = np.broadcast_to(k, (n,))
+    if k.shape != (n,) or not np.issubdtype(k.dtype, np.integer):
+        raise ValueError("%s: kind must be an integer array of shape (%d,); got %s of dtype %s" % (who, n, k.shape, k.dtype))
+    for j in range(n):
+        if k[j] not in (JOINT_BALL, JOINT_LOCK, JOINT_AXIS):
+            raise ValueError("%s: joint %d: unknown kind %d (JOINT_BALL 0, JOINT_LOCK 1, JOINT_AXIS 2)" % (who, j, k[j]))
+    ball, ang = k == JOINT_BALL, k != JOINT_BALL
+    if ball.any() and (anchor_a is None or anchor_b is None):
+        raise ValueError("%s: joint %d is a ball joint: anchor_a and anchor_b are needed" % (who, int(np.argmax(ball))))
+    if ang.any() and axis is None:
+        raise ValueError("%s: joint %d is a lock or axis joint: axis is needed" % (who, int(np.argmax(ang))))
+    out = []
+    for name, v, w in (("anchor_a", anchor_a, 3), ("anchor_b", anchor_b, 3), ("axis", axis, 3), ("q_rel", q_rel, 4)):
+        if v is None:
+            v = np.zeros((n, w))
+            if name == "q_rel":
+                v[:, 0] = 1.0
+        v = np.asarray(v, dtype=np.float64)
+        if v.shape == (w,):
+            v = np.broadcast_to(v, (n, w))
+        if v.shape != (n, w):
+            raise ValueError("%s: %s must have shape (%d,) or (%d, %d); got %s" % (who, name, w, n, w, v.shape))
+        out.append(np.array(v))
+    anchor = np.concatenate(out[:2], axis=1)
+    anchor[ang] = 0.0                                     # not read for an angular joint
+    for j in np.flatnonzero(ball):
+        if not np.isfinite(anchor[j]).all():
+            raise ValueError("%s: joint %d: every value of the anchors must be finite" % (who, j))
+    for j in np.flatnonzero(ang):
+        na = np.linalg.norm(out[2][j])
+        if not np.isfinite(na) or na < 1e-12:
+            raise ValueError("%s: joint %d: axis must be finite and of norm >= 1e-12" % (who, j))
+        nq = np.linalg.norm(out[3][j])
+        if not np.isfinite(nq) or not nq > 0.0:
+            raise ValueError("%s: joint %d: q_rel must be finite and of non-zero norm" % (who, j))
+    return (np.ascontiguousarray(b, dtype=np.int32), np.ascontiguousarray(k, dtype=np.int32), np.ascontiguousarray(anchor),
+            np.ascontiguousarray(out[2]), np.ascontiguousarray(out[3]))
+
+
+def default_q_rel(who, body, kind, q_rel, Q):
+    """q_rel = Q_A^-1 Q_B of the configuration's quaternions Q on the rows of the lock and axis joints, in place"""
+    import numpy as np
+    nb = np.asarray(Q).reshape(-1, 4).shape[0]
+    for j in np.flatnonzero(kind != JOINT_BALL):
+        if not 0 <= body[j, 0] < nb or not -1 <= body[j, 1] < nb:
+            raise ValueError("%s: joint %d: body index out of range of the %d bodies of the configuration" % (who, j, nb))
+        q_rel[j] = relative_quat(Q, body[j, 0], body[j, 1])
+
+
+def _joint_rows(X, Q, a, b, point, axis, kinds):
+    """the rows of a composed joint between the bodies a and b (b = -1: the lab) of the configuration X, Q: a ball joint at the
+    lab-frame point `point` first, then one angular joint per further entry of kinds about the lab-frame direction `axis`"""
+    import numpy as np
+    X, Q = np.asarray(X, dtype=np.float64).reshape(-1, 3), np.asarray(Q, dtype=np.float64).reshape(-1, 4)
+    a, b = int(a), int(b)
+    if not 0 <= a < X.shape[0] or not -1 <= b < X.shape[0] or a == b:
+        raise ValueError("joint builder: bodies (%d, %d): the first must be a body of the configuration, the second another or -1" % (a, b))
+    point, axis = np.asarray(point, dtype=np.float64), np.asarray(axis, dtype=np.float64)
+    if point.shape != (3,) or axis.shape != (3,) or not np.isfinite(point).all() or not np.isfinite(axis).all() or np.linalg.norm(axis) < 1e-12:
+        raise ValueError("joint builder: point and axis must be finite vectors of 3, the axis of norm >= 1e-12")
+    n = len(kinds)
+    RA = quat_matrix(Q[a])
+    rows = dict(body=np.tile([a, b], (n, 1)), kind=np.array(kinds, dtype=np.int32), anchor_a=np.zeros((n, 3)), anchor_b=np.zeros((n, 3)),
+                axis=np.tile(RA.T @ (axis / np.linalg.norm(axis)), (n, 1)), q_rel=np.tile(relative_quat(Q, a, b), (n, 1)))
+    rows["anchor_a"][0] = RA.T @ (point - X[a])
+    rows["anchor_b"][0] = point if b < 0 else quat_matrix(Q[b]).T @ (point - X[b])
+    return rows
+
+
+def hinge(X, Q, a, b, point, axis):
+    """a five-row hinge between the bodies a and b (b = -1: the lab) at the configuration X, Q: a ball joint at the lab-frame
+    point and an axis joint about the lab-frame direction axis -> rows for joint_rows / set_joint_kinds"""
+    return _joint_rows(X, Q, a, b, point, axis, [JOINT_BALL, JOINT_AXIS])
+
+
+def weld(X, Q, a, b, point):
+    """the two bodies move as one: a ball joint at the lab-frame point and a lock joint (its rate stays 0)"""
+    return _joint_rows(X, Q, a, b, point, [0.0, 0.0, 1.0], [JOINT_BALL, JOINT_LOCK])
+
+
+def motor(X, Q, a, b, point, axis):
+    """a driven hinge: a ball joint at the lab-frame point and a lock joint whose rate (set_joint_rates) turns body b relative
+    to body a about the lab-frame direction axis, fixed in body a"""
+    return _joint_rows(X, Q, a, b, point, axis, [JOINT_BALL, JOINT_LOCK])
+
+
+def joint_rows(*rows):
+    """the rows of several builders (hinge, weld, motor, or dicts of the same keys) concatenated -> the keyword arguments of
+    set_joint_kinds"""
+    import numpy as np
+    keys = ("body", "kind", "anchor_a", "anchor_b", "axis", "q_rel")
+    return {k: np.concatenate([np.atleast_2d(r[k]) if k != "kind" else np.atleast_1d(r[k]) for r in rows]) for k in keys}
 
 
 def blob_anchor(cfg, k):
@@ -754,13 +895,76 @@ class DeviceContext:
         return phi, it.value, res.value
 
     def joint_state(self):
-        """-> (gaps p_A - p_B at the context's configuration (n_joints, 3), phi of the last jointed solve or step (n_joints, 3))"""
+        """-> (gaps p_A - p_B at the context's configuration (n_joints, 3), phi of the last jointed solve or step (n_joints, 3));
+        for a set given through set_joint_kinds -> (gap, phi, theta (n_joints,)), the gap rows of a lock or axis joint its angular
+        gap e"""
+        import numpy as np
+        n, kinds = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_joint_kinds(self.h, C.byref(n), None, C.byref(kinds), None, None, None, None, None, None, None))
+        gap, phi = np.zeros((max(n.value, 1), 3)), np.zeros((max(n.value, 1), 3))
+        if not kinds.value:
+            self._chk(self.L.rbl_joint_state(self.h, gap.ctypes.data, phi.ctypes.data))
+            return gap[:n.value], phi[:n.value]
+        theta = np.zeros(max(n.value, 1))
+        self._chk(self.L.rbl_joint_state_kinds(self.h, gap.ctypes.data, phi.ctypes.data, theta.ctypes.data))
+        return gap[:n.value], phi[:n.value], theta[:n.value]
+
+    def set_joint_kinds(self, body, kind, anchor_a=None, anchor_b=None, axis=None, q_rel=None, on=True):
+        """joints of every kind (include/rbl.h section 9): kind[j] JOINT_BALL (anchors as set_joints), JOINT_LOCK (w_A = w_B; with
+        a rate, a motor about axis) or JOINT_AXIS (relative rotation free about axis only); axis in body A's frame; q_rel the
+        target Q_A^-1 Q_B, None: that of the current configuration.  body=None with on=False only switches the joints off."""
+        if body is None and not on:
+            return self._chk(self.L.rbl_set_joint_kinds(self.h, 0, None, None, None, None, None, 0))
+        b, k, anchor, ax, qr = joint_kind_args("set_joint_kinds", body, kind, anchor_a, anchor_b, axis, q_rel)
+        if q_rel is None and (k != JOINT_BALL).any():
+            default_q_rel("set_joint_kinds", b, k, qr, self._config()[1])
+        self._chk(self.L.rbl_set_joint_kinds(self.h, b.shape[0], b.ctypes.data, anchor.ctypes.data, k.ctypes.data, ax.ctypes.data,
+                                             qr.ctypes.data, int(bool(on))))
+
+    def joint_kinds(self):
+        """{on, by_kinds, body, anchor_a, anchor_b, kind, axis, q_rel, theta, rate} of the stored joints (n = 0: never set); a set
+        given through set_joints reads back as ball joints throughout"""
+        import numpy as np
+        n, on, kinds = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_joint_kinds(self.h, C.byref(n), C.byref(on), C.byref(kinds), None, None, None, None, None, None, None))
+        m = n.value
+        body, anchor, kind = np.zeros((m, 2), dtype=np.int32), np.zeros((m, 6)), np.zeros(m, dtype=np.int32)
+        axis, q_rel, theta, rate = np.zeros((m, 3)), np.zeros((m, 4)), np.zeros(m), np.zeros(m)
+        if m:
+            self._chk(self.L.rbl_get_joint_kinds(self.h, None, None, None, body.ctypes.data, anchor.ctypes.data, kind.ctypes.data,
+                                                 axis.ctypes.data, q_rel.ctypes.data, theta.ctypes.data, rate.ctypes.data))
+        return dict(on=bool(on.value), by_kinds=bool(kinds.value), body=body, anchor_a=anchor[:, :3].copy(), anchor_b=anchor[:, 3:].copy(),
+                    kind=kind, axis=axis, q_rel=q_rel, theta=theta, rate=rate)
+
+    def set_joint_rates(self, rates):
+        """the motors' rates, one per stored joint (a number: every lock joint alike is NOT assumed -- give (n_joints,)): body B of
+        a lock joint turns relative to body A at +rate about the joint's axis; 0 for every other kind"""
         import numpy as np
         n = C.c_int(0)
         self._chk(self.L.rbl_get_joints(self.h, C.byref(n), None, None, None))
-        gap, phi = np.zeros((max(n.value, 1), 3)), np.zeros((max(n.value, 1), 3))
-        self._chk(self.L.rbl_joint_state(self.h, gap.ctypes.data, phi.ctypes.data))
-        return gap[:n.value], phi[:n.value]
+        r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+        if r.size != n.value or not n.value:
+            raise ValueError("set_joint_rates: rates must have one value per stored joint (%d); got %d" % (n.value, r.size))
+        if not np.isfinite(r).all():
+            raise ValueError("set_joint_rates: joint %d: the rate must be finite" % int(np.argmin(np.isfinite(r))))
+        self._chk(self.L.rbl_set_joint_rates(self.h, r.ctypes.data))
+
+    def _config(self):
+        nb, nl = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_sizes(self.h, C.byref(nb), C.byref(nl)))
+        return self.get_config(nb.value)
+
+    def hinge(self, a, b, point, axis):
+        """rows of a five-row hinge (ball + axis joint) at the current configuration; point and axis in the lab frame"""
+        return hinge(*self._config(), a, b, point, axis)
+
+    def weld(self, a, b, point):
+        """rows of a weld (ball + lock joint) at the current configuration; point in the lab frame"""
+        return weld(*self._config(), a, b, point)
+
+    def motor(self, a, b, point, axis):
+        """rows of a motor (ball + lock joint, driven by set_joint_rates) at the current configuration"""
+        return motor(*self._config(), a, b, point, axis)
 
     # -- periodic cell in x and y (include/rbl.h section 10) ---------------------------------------------------------------------
     def set_periodic(self, Lx, Ly, images=(1, 1), on=True):

@@ -273,7 +273,11 @@ struct rbl_ctx {
   std::vector<double> jt_anchor;                    // 6 per joint (s_A | s_B or P)
   std::vector<int> jt_rows, jt_ptr, jt_ends;        // CSR of joint ends by body: jointed bodies, row starts, (joint, end) per entry
   std::vector<int> jt_mate;                         // 2 per joint: the other joint between the same two bodies (a hinge) or -1, its ends swapped?
-  RblDevBuf d_jt;                                   // anchors | bodies | rows | row starts | ends | mates (jt_valid)
+  bool jt_by_kinds = false, jt_angular = false;     // set through rbl_set_joint_kinds; holds a lock or axis joint (the kernels' KINDS forms)
+  std::vector<int> jt_kind;                         // 1 per joint (RBL_JOINT_*)
+  std::vector<double> jt_ang;                       // 7 per joint: the axis, unit, in A's frame | q_rel, unit (a ball joint: 0 | identity)
+  std::vector<double> jt_theta, jt_rate;            // 1 per joint: a lock's motor angle and its rate (a change clears jt_valid)
+  RblDevBuf d_jt;                                   // anchors | bodies | rows | row starts | ends | mates (jt_valid); jt_angular: see jt_upload
   bool jt_valid = false;
   RblDevBuf d_jtS;                                  // per-body N^-1 | joint Schur complement, its factor | its inverse | its diagonal
   RblDevBuf d_jtw;                                  // a jointed solve's vectors: rhs | x | (0, J^T phi) | its preconditioned image | lever arms and gaps

@@ -36,6 +36,18 @@
 //   k_jt_inverse   one workgroup per column of S^-1: forward and backward substitution with the column in LDS, one barrier a step
 //   k_jt_sinv      phi = S^-1 t: 64 rows a workgroup, four waves a quarter of the sum each, added in wave order
 //   k_jt_step_rhs  c = -(gamma / dt) g + v of the time step
+//
+// Joint kinds (rbl_set_joint_kinds): every joint keeps three rows; the kind selects G of a joint end -- [I W] for a ball end, [0 I]
+// for a lock end (w_A - w_B = c: a weld, or a motor), [0 P] for an axis end, P = I - ah ah^T (the relative rotation about ah =
+// R(Q_A) a stays free).  k_jt_geom, k_jt_tail and k_jt_schur are templated on KINDS: a set without a lock or axis joint launches
+// the <false> instantiations, the ball joint's code unchanged (the same bits whichever entry point stored the set), a set with
+// one the <true> ones, which read the kind from the joint table.  An axis joint's row along ah constrains nothing: the operator's
+// rows of that joint are P (w_A - w_B) - sigma ah (ah . phi_j) and S gets sigma ah ah^T on that diagonal block -- with the minus
+// sign S = J N^-1 J^T + sigma ah ah^T is the exact Schur complement, so the preconditioner stays the exact inverse and no
+// pseudo-inverse is involved.  The right-hand side's component along ah is projected out before the solve and phi's after it:
+//   k_jt_across          x_j <- P x_j for every axis joint
+//   k_jt_step_rhs_kinds  k_jt_step_rhs and a motor's - rate_j ah on its lock joint's rows
+// The motor angles advance on the host after an accepted step and travel to the device with the rates (jt_upload).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -63,7 +75,13 @@ struct JtDev {
   const double *anchor;
   const int *body, *rows, *ptr, *ends, *mate;            // mate: (the other joint of the same pair of bodies or -1, its ends swapped?)
   int n, n_rows;
+  // a set with angular joints (the KINDS instantiations; NULL otherwise).  ang: axis a (unit, in A's frame) | q_rel per joint;
+  // ninv: the per-body N^-1 of the solve under way (k_jt_ninv), for an axis joint's sigma
+  const int *kind;
+  const double *ang, *theta, *rate, *ninv;
 };
+
+constexpr int JT_BALL = RBL_JOINT_BALL, JT_LOCK = RBL_JOINT_LOCK, JT_AXIS = RBL_JOINT_AXIS;
 
 // two joints between one pair of bodies (a hinge) count as closed when the two anchors are as far apart on one body as on the
 // other to within this, relative: |dA - dB| <= JT_HINGE_CLOSED |dA|.  Their common row -- the distance between the anchors,
@@ -89,12 +107,64 @@ __device__ __forceinline__ void jt_levers(const double *__restrict__ Q, const Jt
   else lB[0] = lB[1] = lB[2] = 0.0;
 }
 
+// Hamilton product of two quaternions (w, x, y, z): R(p q) = R(p) R(q)
+__device__ __forceinline__ void jt_qmul(const double (&p)[4], const double (&q)[4], double (&o)[4])
+{
+  o[0] = p[0] * q[0] - p[1] * q[1] - p[2] * q[2] - p[3] * q[3];
+  o[1] = p[0] * q[1] + p[1] * q[0] + p[2] * q[3] - p[3] * q[2];
+  o[2] = p[0] * q[2] - p[1] * q[3] + p[2] * q[0] + p[3] * q[1];
+  o[3] = p[0] * q[3] + p[1] * q[2] - p[2] * q[1] + p[3] * q[0];
+}
+
+// v -= ah (ah . v): the part of v across the unit vector ah
+__device__ __forceinline__ void jt_across(const double *__restrict__ ah, double &v0, double &v1, double &v2)
+{
+  const double d = ah[0] * v0 + ah[1] * v1 + ah[2] * v2;
+  v0 -= ah[0] * d; v1 -= ah[1] * d; v2 -= ah[2] * d;
+}
+
+// sigma of an axis joint: the eigenvalue its free row gets in the operator and in S -- the mean rotational entry of N^-1 of its body A
+__device__ __forceinline__ double jt_sigma(const double *__restrict__ Ninv, int a)
+{
+  const double *Nb = Ninv + 36 * (size_t)a;
+  return (Nb[21] + Nb[28] + Nb[35]) * (1.0 / 3.0);
+}
+
+// An angular joint (lock or axis): ah = R(Q_A) a, its axis in the lab frame, and the angular gap e, the lab-frame rotation vector
+// of Q_B* Q_B^-1 with the target Q_B* = Q_A rot(theta a) q_rel (theta: a lock's motor angle, 0 for an axis joint), the short way
+// round, so that de/dt = w_A - w_B to first order.  An axis joint keeps the part of e across ah.  Q_B = identity for the lab
+__device__ __forceinline__ void jt_angular(const double *__restrict__ Q, const JtDev &J, int j, int a, int b, double (&ah)[3], double (&e)[3])
+{
+  const double *g = J.ang + 7 * (size_t)j;
+  const int kind = J.kind[j];
+  jt_lab(Q, g, a, ah);
+  const double half = kind == JT_LOCK ? 0.5 * J.theta[j] : 0.0, sn = sin(half);
+  const double r[4] = {cos(half), sn * g[0], sn * g[1], sn * g[2]};
+  const double qa[4] = {Q[4 * (size_t)a], Q[4 * (size_t)a + 1], Q[4 * (size_t)a + 2], Q[4 * (size_t)a + 3]};
+  const double qr[4] = {g[3], g[4], g[5], g[6]};
+  double qbc[4] = {1.0, 0.0, 0.0, 0.0}, t1[4], t2[4], d[4];
+  if (b >= 0) {
+    qbc[0] = Q[4 * (size_t)b]; qbc[1] = -Q[4 * (size_t)b + 1]; qbc[2] = -Q[4 * (size_t)b + 2]; qbc[3] = -Q[4 * (size_t)b + 3];
+  }
+  jt_qmul(qa, r, t1);
+  jt_qmul(t1, qr, t2);
+  jt_qmul(t2, qbc, d);
+  const double sg = d[0] < 0.0 ? -1.0 : 1.0;
+  const double vn = sqrt(d[1] * d[1] + d[2] * d[2] + d[3] * d[3]);
+  const double sc = vn > 0.0 ? sg * 2.0 * atan2(vn, sg * d[0]) / vn : 0.0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) e[c] = sc * d[1 + c];
+  if (kind == JT_AXIS) jt_across(ah, e[0], e[1], e[2]);
+}
+
 // lev = l_A | l_B per joint, gap = p_A - p_B, and gau = the joint's three entries of its hinge's redundant row (zero: none).
 // Two joints lo < hi between one pair of bodies hold the points A1, A2 of one body on the points B1, B2 of the other; when the
 // hinge is closed (JT_HINGE_CLOSED; two pivots on one body: always, the lab points do not move) the combination
 // d . (rows of lo) - d . (rows of hi), d the unit vector from A2 to A1, is the rate of |A1 - A2|^2 - |B1 - B2|^2: zero whatever
 // the bodies do.  gau_lo = d, gau_hi = -d (+d when hi names the two bodies in the other order): k_jt_schur takes this direction
-// out of the null space of S
+// out of the null space of S.
+// KINDS (a set with angular joints): a lock or axis joint leaves lev = ah | 0, gap = e (jt_angular) and gau = 0
+template <bool KINDS>
 __global__ __launch_bounds__(64) void k_jt_geom(const double *__restrict__ X, const double *__restrict__ Q, JtDev J,
                                                 double *__restrict__ lev, double *__restrict__ gap, double *__restrict__ gau)
 {
@@ -103,6 +173,17 @@ __global__ __launch_bounds__(64) void k_jt_geom(const double *__restrict__ X, co
   const int a = J.body[2 * (size_t)j], b = J.body[2 * (size_t)j + 1];
   const double *s = J.anchor + 6 * (size_t)j;
   double lA[3], lB[3], pB[3];
+  if (KINDS && J.kind[j] != JT_BALL) {
+    jt_angular(Q, J, j, a, b, lA, pB);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      lev[6 * (size_t)j + c] = lA[c];
+      lev[6 * (size_t)j + 3 + c] = 0.0;
+      gap[3 * (size_t)j + c] = pB[c];
+      if (gau) gau[3 * (size_t)j + c] = 0.0;
+    }
+    return;
+  }
   jt_levers(Q, J, j, lA, lB);
 #pragma unroll
   for (int c = 0; c < 3; ++c) pB[c] = b >= 0 ? X[3 * (size_t)b + c] + lB[c] : s[3 + c];
@@ -144,6 +225,9 @@ __global__ __launch_bounds__(64) void k_jt_geom(const double *__restrict__ X, co
 // Workgroups [0, n_rows): body rows[w] takes J^T phi -- the force s phi_j and the torque l x (s phi_j) of every joint end on it,
 // s = +1 at end A and -1 at end B -- added to body_out (add != 0) or stored there.  Workgroups behind them: one lane per joint,
 // joint_out_j = (J U)_j - sub_j (sub NULL: zero).  Either half is skipped when its output is NULL.
+// KINDS: a lock end loads its body with the torque s phi_j and no force, an axis end with s P phi_j, P = I - ah ah^T; their rows of
+// J U are w_A - w_B and P (w_A - w_B), and with phi given an axis joint's rows are those of the operator, less sigma ah (ah . phi_j)
+template <bool KINDS>
 __global__ __launch_bounds__(64) void k_jt_tail(JtDev J, const double *__restrict__ lev, const double *__restrict__ phi, int add,
                                                 double *__restrict__ body_out, const double *__restrict__ U,
                                                 const double *__restrict__ sub, double *__restrict__ joint_out)
@@ -158,6 +242,12 @@ __global__ __launch_bounds__(64) void k_jt_tail(JtDev J, const double *__restric
       const int j = J.ends[2 * (size_t)q], end = J.ends[2 * (size_t)q + 1];
       const double s = end ? -1.0 : 1.0;
       const double *p = phi + 3 * (size_t)j;
+      if (KINDS && J.kind[j] != JT_BALL) {
+        double p0 = s * p[0], p1 = s * p[1], p2 = s * p[2];
+        if (J.kind[j] == JT_AXIS) jt_across(lev + 6 * (size_t)j, p0, p1, p2);
+        acc[3] += p0; acc[4] += p1; acc[5] += p2;
+        continue;
+      }
       rbl_KT_acc(lev + 6 * (size_t)j + 3 * end, s * p[0], s * p[1], s * p[2], acc);
     }
     rbl_block_sum<6, 64>(acc, red, t);
@@ -176,11 +266,28 @@ __global__ __launch_bounds__(64) void k_jt_tail(JtDev J, const double *__restric
   const int a = J.body[2 * (size_t)j], b = J.body[2 * (size_t)j + 1];
   const double *l = lev + 6 * (size_t)j;
   double o0, o1, o2;
-  rbl_KU(l, U + 6 * (size_t)a, o0, o1, o2);
-  if (b >= 0) {
-    double q0, q1, q2;
-    rbl_KU(l + 3, U + 6 * (size_t)b, q0, q1, q2);
-    o0 -= q0; o1 -= q1; o2 -= q2;
+  if (KINDS && J.kind[j] != JT_BALL) {
+    const double *wa = U + 6 * (size_t)a + 3;
+    o0 = wa[0]; o1 = wa[1]; o2 = wa[2];
+    if (b >= 0) {
+      const double *wb = U + 6 * (size_t)b + 3;
+      o0 -= wb[0]; o1 -= wb[1]; o2 -= wb[2];
+    }
+    if (J.kind[j] == JT_AXIS) {
+      jt_across(l, o0, o1, o2);
+      if (phi) {
+        const double *p = phi + 3 * (size_t)j;
+        const double d = jt_sigma(J.ninv, a) * (l[0] * p[0] + l[1] * p[1] + l[2] * p[2]);
+        o0 -= l[0] * d; o1 -= l[1] * d; o2 -= l[2] * d;
+      }
+    }
+  } else {
+    rbl_KU(l, U + 6 * (size_t)a, o0, o1, o2);
+    if (b >= 0) {
+      double q0, q1, q2;
+      rbl_KU(l + 3, U + 6 * (size_t)b, q0, q1, q2);
+      o0 -= q0; o1 -= q1; o2 -= q2;
+    }
   }
   if (sub) { o0 -= sub[3 * (size_t)j]; o1 -= sub[3 * (size_t)j + 1]; o2 -= sub[3 * (size_t)j + 2]; }
   joint_out[3 * (size_t)j] = o0; joint_out[3 * (size_t)j + 1] = o1; joint_out[3 * (size_t)j + 2] = o2;
@@ -255,12 +362,27 @@ __device__ __forceinline__ void jt_W(const double *__restrict__ l, double (&W)[3
   W[2][0] = l[1];  W[2][1] = -l[0]; W[2][2] = 0.0;
 }
 
+// the rotation half W of G = [a I  W] of a joint's end (lv: the joint's six values of lev) -> a: a ball end 1 and -[l]x, a lock
+// end 0 and I, an axis end 0 and P = I - ah ah^T
+__device__ __forceinline__ double jt_G(int kind, const double *__restrict__ lv, int end, double (&W)[3][3])
+{
+  if (kind == JT_BALL) { jt_W(lv + 3 * end, W); return 1.0; }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) W[r][c] = (r == c ? 1.0 : 0.0) - (kind == JT_AXIS ? lv[r] * lv[c] : 0.0);
+  return 0.0;
+}
+
 // S = J N^-1 J^T, dense column-major of order np >= 3 n (the rows behind 3 n: the identity), the caller has cleared it.  Work item
 // g = j n + k owns the block of the joints j and k: for each pair of their ends that lies on ONE body b the term
 // s_j s_k G_j N_b^-1 G_k^T with G = [I  W] of that end -- two ends of one joint lie on different bodies, so at most two terms.
 // A closed hinge (gau != 0 on both its joints, k_jt_geom) adds sigma / 2 gau_j gau_k^T to its four blocks: its redundant row, which S
 // annihilates, gets the eigenvalue sigma = the mean translational entry of N^-1 of the lower joint's body A, and S^-1 acts as the
-// pseudo-inverse there.  diag0: the diagonal of S, kept for k_jt_pivots
+// pseudo-inverse there.  diag0: the diagonal of S, kept for k_jt_pivots.
+// KINDS: G = [0 I] for a lock end and [0 P] for an axis end, P = I - ah ah^T, and an axis joint's diagonal block gets
+// sigma ah ah^T (jt_sigma): the row along its axis, which constrains nothing, has the eigenvalue the operator gives it
+template <bool KINDS>
 __global__ __launch_bounds__(256) void k_jt_schur(JtDev J, const double *__restrict__ lev, const double *__restrict__ gau,
                                                   const double *__restrict__ Ninv, long np, double *__restrict__ A,
                                                   double *__restrict__ diag0)
@@ -283,19 +405,33 @@ __global__ __launch_bounds__(256) void k_jt_schur(JtDev J, const double *__restr
       const double sgn = e == f ? 1.0 : -1.0;
       const double *Nb = Ninv + 36 * (size_t)bj;
       double Wj[3][3], Wk[3][3], T[6][3];
-      jt_W(lev + 6 * (size_t)j + 3 * e, Wj);
-      jt_W(lev + 6 * (size_t)k + 3 * f, Wk);
+      double aj = 1.0, ak = 1.0;                         // G = [a I  W]
+      if (KINDS) {
+        aj = jt_G(J.kind[j], lev + 6 * (size_t)j, e, Wj);
+        ak = jt_G(J.kind[k], lev + 6 * (size_t)k, f, Wk);
+      } else {
+        jt_W(lev + 6 * (size_t)j + 3 * e, Wj);
+        jt_W(lev + 6 * (size_t)k + 3 * f, Wk);
+      }
 #pragma unroll
       for (int p = 0; p < 6; ++p)
 #pragma unroll
         for (int c = 0; c < 3; ++c)                      // T = N_b^-1 G_k^T
-          T[p][c] = Nb[6 * p + c] + Nb[6 * p + 3] * Wk[c][0] + Nb[6 * p + 4] * Wk[c][1] + Nb[6 * p + 5] * Wk[c][2];
+          T[p][c] = (KINDS ? ak * Nb[6 * p + c] : Nb[6 * p + c]) + Nb[6 * p + 3] * Wk[c][0] + Nb[6 * p + 4] * Wk[c][1] + Nb[6 * p + 5] * Wk[c][2];
 #pragma unroll
       for (int r = 0; r < 3; ++r)
 #pragma unroll
         for (int c = 0; c < 3; ++c)
-          B[r][c] += sgn * (T[r][c] + Wj[r][0] * T[3][c] + Wj[r][1] * T[4][c] + Wj[r][2] * T[5][c]);
+          B[r][c] += sgn * ((KINDS ? aj * T[r][c] : T[r][c]) + Wj[r][0] * T[3][c] + Wj[r][1] * T[4][c] + Wj[r][2] * T[5][c]);
     }
+  if (KINDS && j == k && J.kind[j] == JT_AXIS) {
+    const double sg = jt_sigma(Ninv, J.body[2 * (size_t)j]);
+    const double *ah = lev + 6 * (size_t)j;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) B[r][c] += sg * ah[r] * ah[c];
+  }
   const int mate = J.mate[2 * (size_t)j];
   if (mate >= 0 && (k == j || k == mate)) {
     const double *Nb = Ninv + 36 * (size_t)J.body[2 * (size_t)(j < mate ? j : mate)];
@@ -382,6 +518,30 @@ __global__ __launch_bounds__(256) void k_jt_step_rhs(const double *__restrict__ 
   if (i < m) out[i] = coef * gap[i] + (v ? v[i] : 0.0);
 }
 
+// the same for a set with angular joints: a lock's row takes its motor's rate, - rate_j ah (body B turns at + rate_j about ah
+// relative to body A); lev holds ah
+__global__ __launch_bounds__(256) void k_jt_step_rhs_kinds(const double *__restrict__ gap, const double *__restrict__ v, double coef, int m,
+                                                           JtDev J, const double *__restrict__ lev, double *__restrict__ out)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const int j = i / 3, r = i - 3 * j;
+  double o = coef * gap[i] + (v ? v[i] : 0.0);
+  if (J.kind[j] == JT_LOCK) o -= J.rate[j] * lev[6 * (size_t)j + r];
+  out[i] = o;
+}
+
+// x_j <- P x_j for every axis joint, one lane a joint: the right-hand side's rows before the solve (the component along the
+// axis is ignored) and phi after it (its component along the axis is zero; GMRES leaves rounding there)
+__global__ __launch_bounds__(64) void k_jt_across(JtDev J, const double *__restrict__ lev, double *__restrict__ x)
+{
+  const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (j >= J.n || J.kind[j] != JT_AXIS) return;
+  double v0 = x[3 * (size_t)j], v1 = x[3 * (size_t)j + 1], v2 = x[3 * (size_t)j + 2];
+  jt_across(lev + 6 * (size_t)j, v0, v1, v2);
+  x[3 * (size_t)j] = v0; x[3 * (size_t)j + 1] = v1; x[3 * (size_t)j + 2] = v2;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 
 bool jt_active(const rbl_ctx *c) { return c->jt_on && c->jt_n > 0; }
@@ -402,17 +562,27 @@ int jt_reserve(rbl_ctx *c, JtBuf &B)
   return RBL_OK;
 }
 
-// the joints on the device, once per rbl_set_joints: anchors | bodies | rows | row starts | ends | mates
+// the joints on the device, once per rbl_set_joints: anchors | bodies | rows | row starts | ends | mates.  A set with angular
+// joints (jt_angular): anchors | axes and q_rel | theta | rates | the same integers | kinds, and again after every change of theta
+// or of the rates
 int jt_upload(rbl_ctx *c)
 {
   if (c->jt_valid) return RBL_OK;
-  const std::vector<int> *ipart[5] = {&c->jt_body, &c->jt_rows, &c->jt_ptr, &c->jt_ends, &c->jt_mate};
-  size_t ni = 0;
-  for (const std::vector<int> *v : ipart) ni += v->size();
-  int rc = rbl_dev_reserve(c, c->d_jt, sizeof(double) * c->jt_anchor.size() + sizeof(int) * ni); if (rc) return rc;
-  if ((rc = copy_h2d(c, c->d_jt.p, c->jt_anchor.data(), sizeof(double) * c->jt_anchor.size()))) return rc;
-  int *q = (int *)((double *)c->d_jt.p + c->jt_anchor.size());
-  for (const std::vector<int> *v : ipart) {
+  const std::vector<double> *dpart[4] = {&c->jt_anchor, &c->jt_ang, &c->jt_theta, &c->jt_rate};
+  const std::vector<int> *ipart[6] = {&c->jt_body, &c->jt_rows, &c->jt_ptr, &c->jt_ends, &c->jt_mate, &c->jt_kind};
+  const int nd = c->jt_angular ? 4 : 1, nip = c->jt_angular ? 6 : 5;
+  size_t ndbl = 0, ni = 0;
+  for (int k = 0; k < nd; ++k) ndbl += dpart[k]->size();
+  for (int k = 0; k < nip; ++k) ni += ipart[k]->size();
+  int rc = rbl_dev_reserve(c, c->d_jt, sizeof(double) * ndbl + sizeof(int) * ni); if (rc) return rc;
+  double *dq = (double *)c->d_jt.p;
+  for (int k = 0; k < nd; ++k) {
+    if ((rc = copy_h2d(c, dq, dpart[k]->data(), sizeof(double) * dpart[k]->size()))) return rc;
+    dq += dpart[k]->size();
+  }
+  int *q = (int *)dq;
+  for (int k = 0; k < nip; ++k) {
+    const std::vector<int> *v = ipart[k];
     if ((rc = copy_h2d(c, q, v->data(), sizeof(int) * v->size()))) return rc;
     q += v->size();
   }
@@ -425,11 +595,19 @@ JtDev jt_args(const rbl_ctx *c)
 {
   JtDev J = {};
   J.anchor = (const double *)c->d_jt.p;
-  J.body = (const int *)(J.anchor + c->jt_anchor.size());
+  const double *dend = J.anchor + c->jt_anchor.size();
+  if (c->jt_angular) {
+    J.ang = dend;
+    J.theta = J.ang + c->jt_ang.size();
+    J.rate = J.theta + c->jt_theta.size();
+    dend = J.rate + c->jt_rate.size();
+  }
+  J.body = (const int *)dend;
   J.rows = J.body + c->jt_body.size();
   J.ptr = J.rows + c->jt_rows.size();
   J.ends = J.ptr + c->jt_ptr.size();
   J.mate = J.ends + c->jt_ends.size();
+  if (c->jt_angular) J.kind = J.mate + c->jt_mate.size();
   J.n = c->jt_n; J.n_rows = (int)c->jt_rows.size();
   return J;
 }
@@ -463,8 +641,11 @@ int jt_geom(rbl_ctx *c, double *lev, double *gap, double *gau)
   int rc = jt_upload(c); if (rc) return rc;
   if ((rc = ensure_xq_dev(c))) return rc;
   const double *dX = (const double *)c->d_XQ.p;
-  hipLaunchKernelGGL(k_jt_geom, dim3((unsigned)((c->jt_n + 63) / 64)), dim3(64), 0, c->stream, dX, dX + 3 * (size_t)c->S.N_bod, jt_args(c),
-                     lev, gap, gau);
+  const dim3 grid((unsigned)((c->jt_n + 63) / 64));
+  if (c->jt_angular)
+    hipLaunchKernelGGL(k_jt_geom<true>, grid, dim3(64), 0, c->stream, dX, dX + 3 * (size_t)c->S.N_bod, jt_args(c), lev, gap, gau);
+  else
+    hipLaunchKernelGGL(k_jt_geom<false>, grid, dim3(64), 0, c->stream, dX, dX + 3 * (size_t)c->S.N_bod, jt_args(c), lev, gap, gau);
   return RBL_OK;
 }
 
@@ -478,8 +659,11 @@ struct JtSolve {
 void jt_launch_tail(rbl_ctx *c, const JtSolve *m, const double *phi, int add, double *body_out, const double *U, const double *sub,
                     double *joint_out)
 {
-  hipLaunchKernelGGL(k_jt_tail, dim3((unsigned)(m->J.n_rows + (m->J.n + 63) / 64)), dim3(64), 0, c->stream, m->J, (const double *)m->B->lev,
-                     phi, add, body_out, U, sub, joint_out);
+  const dim3 grid((unsigned)(m->J.n_rows + (m->J.n + 63) / 64));
+  if (m->J.kind)
+    hipLaunchKernelGGL(k_jt_tail<true>, grid, dim3(64), 0, c->stream, m->J, (const double *)m->B->lev, phi, add, body_out, U, sub, joint_out);
+  else
+    hipLaunchKernelGGL(k_jt_tail<false>, grid, dim3(64), 0, c->stream, m->J, (const double *)m->B->lev, phi, add, body_out, U, sub, joint_out);
 }
 
 int jt_op(rbl_ctx *c, void *user, const double *d_x, double *d_out)
@@ -513,7 +697,7 @@ int jt_pc(rbl_ctx *c, void *user, const double *d_in, double *d_out)
 
 // S of the context's configuration, its factor and its inverse; the preconditioner must be built (rbl_prepare_dev) and the latched
 // flags clean.  A singular S: RBL_ERR_NOT_SPD with the message below
-int jt_factor(rbl_ctx *c, const char *who, const JtBuf &B, const double **Sinv)
+int jt_factor(rbl_ctx *c, const char *who, const JtBuf &B, const double **Sinv, const double **Ninv_out)
 {
   const RblBodyState &S = c->S;
   const long np = jt_np(c);
@@ -529,8 +713,12 @@ int jt_factor(rbl_ctx *c, const char *who, const JtBuf &B, const double **Sinv)
   RBL_HIP(c, hipMemsetAsync(A, 0, sizeof(double) * sq, c->stream));
   const JtDev J = jt_args(c);
   const size_t items = std::max((size_t)J.n * (size_t)J.n, (size_t)np);
-  hipLaunchKernelGGL(k_jt_schur, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, c->stream, J, (const double *)B.lev,
-                     (const double *)B.gau, (const double *)Ninv, np, A, diag0);
+  if (c->jt_angular)
+    hipLaunchKernelGGL(k_jt_schur<true>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, c->stream, J, (const double *)B.lev,
+                       (const double *)B.gau, (const double *)Ninv, np, A, diag0);
+  else
+    hipLaunchKernelGGL(k_jt_schur<false>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, c->stream, J, (const double *)B.lev,
+                       (const double *)B.gau, (const double *)Ninv, np, A, diag0);
   if ((rc = rbl_dev_reserve(c, c->d_chol, rbl_cholesky_work_bytes(np)))) return rc;
   rc = rbl_launch_cholesky(c->stream, A, np, false, c->d_err, (double *)c->d_chol.p, c->d_chol.bytes, &c->chol_aux);
   if (rc) return rbl_fail(c, rc, std::string(who) + ": cholesky launch failed");
@@ -546,6 +734,7 @@ int jt_factor(rbl_ctx *c, const char *who, const JtBuf &B, const double **Sinv)
   hipLaunchKernelGGL(k_jt_inverse, dim3((unsigned)np), dim3(256), sizeof(double) * (size_t)np, c->stream, (const double *)A, (int)np, Si);
   RBL_HIP(c, hipGetLastError());
   *Sinv = Si;
+  *Ninv_out = Ninv;
   return RBL_OK;
 }
 
@@ -558,11 +747,15 @@ int jt_solve(rbl_ctx *c, const char *who, const JtBuf &B, int max_iter, double r
   int rc = rbl_prepare_dev(c); if (rc) return rc;                        // resident geometry, the preconditioner of this configuration
   const size_t n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nsys = n3 + 6 * (size_t)c->S.N_bod, nj3 = 3 * (size_t)c->jt_n;
   JtSolve m{&B, jt_args(c), nullptr, jt_np(c)};
-  if ((rc = jt_factor(c, who, B, &m.Sinv))) return rc;
+  if ((rc = jt_factor(c, who, B, &m.Sinv, &m.J.ninv))) return rc;
   RBL_HIP(c, hipMemsetAsync(B.v, 0, sizeof(double) * nsys, c->stream));
+  const dim3 jgrid((unsigned)((c->jt_n + 63) / 64));
+  if (c->jt_angular)                                     // an axis joint's right-hand side counts across its axis only
+    hipLaunchKernelGGL(k_jt_across, jgrid, dim3(64), 0, c->stream, m.J, (const double *)B.lev, B.rhs + nsys);
   RblSolveOps ops{jt_op, jt_pc, &m};
   ops.extra = (int64_t)nj3;
   if ((rc = gmres_core_with_ops(c, &ops, B.rhs, max_iter, rtol, B.x, iters, resid))) return rc;
+  if (c->jt_angular) hipLaunchKernelGGL(k_jt_across, jgrid, dim3(64), 0, c->stream, m.J, (const double *)B.lev, B.x + nsys);
   if ((rc = rbl_dev_reserve(c, c->d_jtphi, sizeof(double) * 4 * nj3))) return rc;
   RBL_HIP(c, hipMemcpyAsync(c->d_jtphi.p, B.x + nsys, sizeof(double) * nj3, hipMemcpyDeviceToDevice, c->stream));
   c->jt_phi_valid = true;
@@ -610,6 +803,8 @@ int jt_plain_solve(rbl_ctx *c, const double *F_body, const double *slip, bool ho
 
 // ---- the C ABI (include/rbl.h section 9) -------------------------------------------------------------------------------------------
 
+static void jt_store(rbl_ctx *c, int n_joints, const int *body, const double *anchor, const int *kind, int on, int top);
+
 // the joints: checks first, nothing is stored unless every one passes; then the CSR of joint ends by body
 int rbl_set_joints(rbl_ctx *c, int n_joints, const int *body, const double *anchor, int on)
 {
@@ -636,11 +831,29 @@ int rbl_set_joints(rbl_ctx *c, int n_joints, const int *body, const double *anch
                                           ": three ball joints would constrain nine of six relative coordinates");
     top = std::max(top, std::max(a, b));
   }
+  jt_store(c, n_joints, body, anchor, nullptr, on, top);
+  return RBL_OK;
+}
+
+// the checked joints into the context: the mates, the CSR of joint ends by body.  kind NULL: ball joints only
+static void jt_store(rbl_ctx *c, int n_joints, const int *body, const double *anchor, const int *kind, int on, int top)
+{
   c->jt_n = n_joints; c->jt_top = top;
-  // the two joints of a pair of bodies name each other (at most two: checked above)
+  c->jt_by_kinds = kind != nullptr;
+  c->jt_angular = false;
+  c->jt_kind.assign((size_t)n_joints, JT_BALL);
+  c->jt_ang.assign(7 * (size_t)n_joints, 0.0);
+  c->jt_theta.assign((size_t)n_joints, 0.0);
+  c->jt_rate.assign((size_t)n_joints, 0.0);
+  for (int j = 0; j < n_joints; ++j) {
+    c->jt_ang[7 * (size_t)j + 3] = 1.0;                  // q_rel of a ball joint reads back as the identity
+    if (kind && kind[j] != JT_BALL) { c->jt_kind[j] = kind[j]; c->jt_angular = true; }
+  }
+  // the two ball joints of a pair of bodies name each other (at most two: checked by the caller)
   c->jt_mate.assign(2 * (size_t)n_joints, -1);
   std::map<std::pair<int, int>, int> first;
   for (int j = 0; j < n_joints; ++j) {
+    if (c->jt_kind[j] != JT_BALL) continue;
     const int a = body[2 * (size_t)j], b = body[2 * (size_t)j + 1];
     const auto hit = first.emplace(std::make_pair(std::min(a, b), std::max(a, b)), j);
     if (hit.second) continue;
@@ -651,7 +864,9 @@ int rbl_set_joints(rbl_ctx *c, int n_joints, const int *body, const double *anch
   for (int j = 0; j < n_joints; ++j)
     if (c->jt_mate[2 * (size_t)j] < 0) c->jt_mate[2 * (size_t)j + 1] = 0;
   c->jt_body.assign(body, body + 2 * (size_t)n_joints);
-  c->jt_anchor.assign(anchor, anchor + 6 * (size_t)n_joints);
+  c->jt_anchor.assign(6 * (size_t)n_joints, 0.0);        // an angular joint has no anchors: zeros
+  for (int j = 0; j < n_joints; ++j)
+    if (c->jt_kind[j] == JT_BALL) std::copy(anchor + 6 * (size_t)j, anchor + 6 * (size_t)j + 6, c->jt_anchor.begin() + 6 * (size_t)j);
   // joint ends by body, in increasing joint index: the ends in joint order, sorted by body with a stable sort
   struct End { int body, joint, end; };
   std::vector<End> ends;
@@ -673,7 +888,6 @@ int rbl_set_joints(rbl_ctx *c, int n_joints, const int *body, const double *anch
   c->jt_on = on != 0;
   c->jt_valid = false;
   c->jt_phi_valid = false;
-  return RBL_OK;
 }
 
 int rbl_get_joints(const rbl_ctx *c, int *n_joints, int *on, int *body, double *anchor)
@@ -683,6 +897,102 @@ int rbl_get_joints(const rbl_ctx *c, int *n_joints, int *on, int *body, double *
   if (on) *on = c->jt_on ? 1 : 0;
   if (body && c->jt_n) std::memcpy(body, c->jt_body.data(), sizeof(int) * c->jt_body.size());
   if (anchor && c->jt_n) std::memcpy(anchor, c->jt_anchor.data(), sizeof(double) * c->jt_anchor.size());
+  return RBL_OK;
+}
+
+// joints of every kind: rbl_set_joints' checks and those of the angular joints, then the same storing
+int rbl_set_joint_kinds(rbl_ctx *c, int n_joints, const int *body, const double *anchor, const int *kind, const double *axis,
+                        const double *q_rel, int on)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (!body && !anchor && !kind && !axis && !q_rel && !on) { c->jt_on = false; return RBL_OK; }
+  if (!body) return rbl_fail(c, RBL_ERR_ARG, "set_joint_kinds: body must not be NULL");
+  if (!kind) return rbl_fail(c, RBL_ERR_ARG, "set_joint_kinds: kind must not be NULL");
+  if (n_joints < 1 || n_joints > JT_MAX)
+    return rbl_fail(c, RBL_ERR_ARG, "set_joint_kinds: n_joints must lie in [1, " + std::to_string(JT_MAX) + "]");
+  int top = -1;
+  std::map<std::pair<int, int>, std::pair<int, int>> count;        // balls, angular joints of a pair of bodies
+  std::vector<double> ang(7 * (size_t)n_joints, 0.0);
+  for (int j = 0; j < n_joints; ++j) {
+    const int a = body[2 * (size_t)j], b = body[2 * (size_t)j + 1], k = kind[j];
+    const std::string at = "set_joint_kinds: joint " + std::to_string(j) + ": ";
+    if (k != JT_BALL && k != JT_LOCK && k != JT_AXIS)
+      return rbl_fail(c, RBL_ERR_ARG, at + "unknown kind " + std::to_string(k) + " (RBL_JOINT_BALL 0, RBL_JOINT_LOCK 1, RBL_JOINT_AXIS 2)");
+    if (a == -1) return rbl_fail(c, RBL_ERR_ARG, at + "body[2 j] is -1: the lab goes in the second slot, the body in the first");
+    if (a < 0 || b < -1 || (c->S.cfg_set && std::max(a, b) >= c->S.N_bod))
+      return rbl_fail(c, RBL_ERR_ARG, at + "body index out of range (the first >= 0, the second >= 0 or -1 for the lab" +
+                                          (c->S.cfg_set ? ", both below the " + std::to_string(c->S.N_bod) + " bodies of the configuration)" : ")"));
+    if (a == b) return rbl_fail(c, RBL_ERR_ARG, at + "body: both ends lie on one body (a joint inside a rigid body constrains nothing)");
+    ang[7 * (size_t)j + 3] = 1.0;
+    if (k == JT_BALL) {
+      if (!anchor) return rbl_fail(c, RBL_ERR_ARG, at + "a ball joint needs anchor, which is NULL");
+      for (int q = 0; q < 6; ++q)
+        if (!std::isfinite(anchor[6 * (size_t)j + q])) return rbl_fail(c, RBL_ERR_ARG, at + "every value of anchor must be finite");
+    } else {
+      if (!axis || !q_rel) return rbl_fail(c, RBL_ERR_ARG, at + "a lock or axis joint needs axis and q_rel, one of which is NULL");
+      double na = 0.0, nq = 0.0;
+      for (int q = 0; q < 3; ++q) na += axis[3 * (size_t)j + q] * axis[3 * (size_t)j + q];
+      for (int q = 0; q < 4; ++q) nq += q_rel[4 * (size_t)j + q] * q_rel[4 * (size_t)j + q];
+      na = std::sqrt(na); nq = std::sqrt(nq);
+      if (!std::isfinite(na) || na < 1e-12) return rbl_fail(c, RBL_ERR_ARG, at + "axis must be finite and of norm >= 1e-12");
+      if (!std::isfinite(nq) || !(nq > 0.0)) return rbl_fail(c, RBL_ERR_ARG, at + "q_rel must be finite and of non-zero norm");
+      for (int q = 0; q < 3; ++q) ang[7 * (size_t)j + q] = axis[3 * (size_t)j + q] / na;
+      for (int q = 0; q < 4; ++q) ang[7 * (size_t)j + 3 + q] = q_rel[4 * (size_t)j + q] / nq;
+    }
+    std::pair<int, int> &n = count[std::make_pair(std::min(a, b), std::max(a, b))];
+    const std::string pair = b < 0 ? "body " + std::to_string(a) + " and the lab"
+                                   : "the bodies " + std::to_string(std::min(a, b)) + " and " + std::to_string(std::max(a, b));
+    if (k == JT_BALL && ++n.first > 2)
+      return rbl_fail(c, RBL_ERR_ARG, at + (b < 0 ? "a third pivot on body " + std::to_string(a) : "a third joint between " + pair) +
+                                          ": three ball joints would constrain nine of six relative coordinates");
+    if (k != JT_BALL && ++n.second > 1)
+      return rbl_fail(c, RBL_ERR_ARG, at + "a second angular joint between " + pair + ": one lock or axis joint a pair");
+    if (n.first > 1 && n.second > 0)
+      return rbl_fail(c, RBL_ERR_ARG, at + "an angular joint together with two ball joints between " + pair +
+                                          ": the second ball joint would constrain what the angular joint already holds");
+    top = std::max(top, std::max(a, b));
+  }
+  jt_store(c, n_joints, body, anchor, kind, on, top);
+  for (int j = 0; j < n_joints; ++j)
+    if (kind[j] != JT_BALL) std::copy(ang.begin() + 7 * (size_t)j, ang.begin() + 7 * (size_t)j + 7, c->jt_ang.begin() + 7 * (size_t)j);
+  return RBL_OK;
+}
+
+int rbl_get_joint_kinds(const rbl_ctx *c, int *n_joints, int *on, int *by_kinds, int *body, double *anchor, int *kind, double *axis,
+                        double *q_rel, double *theta, double *rate)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (n_joints) *n_joints = c->jt_n;
+  if (on) *on = c->jt_on ? 1 : 0;
+  if (by_kinds) *by_kinds = c->jt_n > 0 && c->jt_by_kinds ? 1 : 0;
+  if (!c->jt_n) return RBL_OK;
+  if (body) std::memcpy(body, c->jt_body.data(), sizeof(int) * c->jt_body.size());
+  if (anchor) std::memcpy(anchor, c->jt_anchor.data(), sizeof(double) * c->jt_anchor.size());
+  if (kind) std::memcpy(kind, c->jt_kind.data(), sizeof(int) * c->jt_kind.size());
+  for (int j = 0; j < c->jt_n; ++j) {
+    if (axis) std::copy(c->jt_ang.begin() + 7 * (size_t)j, c->jt_ang.begin() + 7 * (size_t)j + 3, axis + 3 * (size_t)j);
+    if (q_rel) std::copy(c->jt_ang.begin() + 7 * (size_t)j + 3, c->jt_ang.begin() + 7 * (size_t)j + 7, q_rel + 4 * (size_t)j);
+  }
+  if (theta) std::memcpy(theta, c->jt_theta.data(), sizeof(double) * c->jt_theta.size());
+  if (rate) std::memcpy(rate, c->jt_rate.data(), sizeof(double) * c->jt_rate.size());
+  return RBL_OK;
+}
+
+// the motors' rates: context state, read by rbl_step_jointed; nothing is stored unless every value passes
+int rbl_set_joint_rates(rbl_ctx *c, const double *rate)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (c->jt_n < 1) return rbl_fail(c, RBL_ERR_STATE, "set_joint_rates: no joints have been set (rbl_set_joint_kinds)");
+  if (!rate) return rbl_fail(c, RBL_ERR_ARG, "set_joint_rates: rate must not be NULL");
+  for (int j = 0; j < c->jt_n; ++j) {
+    const std::string at = "set_joint_rates: joint " + std::to_string(j) + ": ";
+    if (!std::isfinite(rate[j])) return rbl_fail(c, RBL_ERR_ARG, at + "the rate must be finite");
+    if (rate[j] != 0.0 && c->jt_kind[j] != JT_LOCK)
+      return rbl_fail(c, RBL_ERR_ARG, at + "only a lock joint (RBL_JOINT_LOCK) takes a rate; it must be 0 here");
+  }
+  if (std::memcmp(c->jt_rate.data(), rate, sizeof(double) * (size_t)c->jt_n) == 0) return RBL_OK;
+  c->jt_rate.assign(rate, rate + c->jt_n);
+  c->jt_valid = false;
   return RBL_OK;
 }
 
@@ -765,8 +1075,12 @@ int rbl_step_jointed(rbl_ctx *c, const double *F_body, const double *slip, const
   if ((rc = copy_h2d(c, B.v, F_body, sizeof(double) * nb6))) return rc;
   if ((rc = ia_add_to_step_force(c, B.v))) return rc;                   // the force model at q^n, bonds included (section 4)
   if (joint_velocity && (rc = copy_h2d(c, B.t, joint_velocity, sizeof(double) * nj3))) return rc;
-  hipLaunchKernelGGL(k_jt_step_rhs, dim3((unsigned)((nj3 + 255) / 256)), dim3(256), 0, c->stream, (const double *)B.gap,
-                     joint_velocity ? (const double *)B.t : nullptr, -gamma / c->S.dt, (int)nj3, B.c);
+  if (c->jt_angular)
+    hipLaunchKernelGGL(k_jt_step_rhs_kinds, dim3((unsigned)((nj3 + 255) / 256)), dim3(256), 0, c->stream, (const double *)B.gap,
+                       joint_velocity ? (const double *)B.t : nullptr, -gamma / c->S.dt, (int)nj3, jt_args(c), (const double *)B.lev, B.c);
+  else
+    hipLaunchKernelGGL(k_jt_step_rhs, dim3((unsigned)((nj3 + 255) / 256)), dim3(256), 0, c->stream, (const double *)B.gap,
+                       joint_velocity ? (const double *)B.t : nullptr, -gamma / c->S.dt, (int)nj3, B.c);
   jt_rhs(c, B, B.v, have_slip, B.c);
   c->step_hist_n = 0;                                    // the warm starts of rbl_step_deterministic extrapolate over ITS steps only
   if ((rc = jt_solve(c, "step_jointed", B, max_iter, rtol, iters, resid))) return rc;
@@ -775,7 +1089,17 @@ int rbl_step_jointed(rbl_ctx *c, const double *F_body, const double *slip, const
   if ((rc = copy_d2h(c, U.data(), B.x + n3, sizeof(double) * nb6))) return rc;
   if (phi && (rc = copy_d2h(c, phi, B.x + nsys, sizeof(double) * nj3))) return rc;
   if ((rc = finish_and_check(c))) return rc;
-  return rbl_evolve_X_Q(c, U.data());
+  if ((rc = rbl_evolve_X_Q(c, U.data()))) return rc;
+  // the step is accepted: every motor's angle advances, theta_j += rate_j dt (product and sum rounded one after the other)
+  bool moved = false;
+  for (int j = 0; j < c->jt_n && c->jt_angular; ++j)
+    if (c->jt_rate[j] != 0.0) {
+      volatile double d = c->jt_rate[j] * c->S.dt;
+      c->jt_theta[j] += d;
+      moved = true;
+    }
+  if (moved) c->jt_valid = false;
+  return RBL_OK;
 }
 
 // the gaps g_j = p_A - p_B of the stored joints (on or off) at the context's configuration and the phi of the last jointed solve
@@ -798,5 +1122,14 @@ int rbl_joint_state(rbl_ctx *c, double *gap, double *phi)
   }
   if (phi && (rc = copy_d2h(c, phi, d_phi, sizeof(double) * nj3))) return rc;
   RBL_HIP(c, hipStreamSynchronize(c->stream));
+  return RBL_OK;
+}
+
+// the same with the motor angles: gap rows of an angular joint hold e (P e for an axis joint); theta[n_joints] may be NULL
+int rbl_joint_state_kinds(rbl_ctx *c, double *gap, double *phi, double *theta)
+{
+  const int rc = rbl_joint_state(c, gap, phi);
+  if (rc) return rc;
+  if (theta) std::memcpy(theta, c->jt_theta.data(), sizeof(double) * c->jt_theta.size());
   return RBL_OK;
 }

@@ -22,7 +22,7 @@ and an imposed flow, a body-frame slip and stresslets (`set_background_flow`, `s
 import numpy as np
 
 from . import c_rigid as _ext
-from ._lib import DeviceContext, blob_anchor, bond_args, check_brownian_mask6, dipole_args, field_args, joint_args, periodic_args, table_arrays, tabulate  # noqa: F401
+from ._lib import JOINT_AXIS, JOINT_BALL, JOINT_LOCK, DeviceContext, default_q_rel, hinge, joint_kind_args, joint_rows, motor, weld, blob_anchor, bond_args, check_brownian_mask6, dipole_args, field_args, joint_args, periodic_args, table_arrays, tabulate  # noqa: F401
 
 _KBT_IN_WRAPPER = 1.0   # the reference wrapper passes kBT = 1 whatever the caller wants (src/Rigid.py:23)
 
@@ -326,6 +326,47 @@ class RigidBody:
         """-> {on, body (n_joints, 2), anchor_a (n_joints, 3), anchor_b (n_joints, 3)} (n_joints = 0: never set)"""
         return self.ctx.joints()
 
+    def set_joint_kinds(self, body, kind, anchor_a=None, anchor_b=None, axis=None, q_rel=None, on=True):
+        """Hard joints of every kind, a superset of set_joints: kind[j] is JOINT_BALL (0; three translational rows, anchors as in
+        set_joints), JOINT_LOCK (1; w_A = w_B) or JOINT_AXIS (2; w_A - w_B free about axis only).  axis (3,) or (n_joints, 3) is
+        fixed in body A's frame; q_rel (4,) or (n_joints, 4), scalar first, is the target Q_A^-1 Q_B, None: that of the current
+        configuration.  Body B = -1 is the lab.  Compose them: ball + axis on one pair is a five-row hinge, ball + lock a weld,
+        ball + lock with a rate (set_joint_rates) a motor -- `hinge`, `weld`, `motor` build the rows, `joint_rows` concatenates
+        them.  Refused with the joint named: an unknown kind, a bad axis or q_rel, a second angular joint on a pair, an angular
+        joint next to two ball joints on a pair, and what set_joints refuses."""
+        if body is None and not on:
+            return self.ctx.set_joint_kinds(None, None, on=False)
+        b, k, anchor, ax, qr = joint_kind_args("set_joint_kinds", body, kind, anchor_a, anchor_b, axis, q_rel)
+        if q_rel is None and (k != JOINT_BALL).any():
+            default_q_rel("set_joint_kinds", b, k, qr, self.cb.getConfig()[1])
+        self.ctx.set_joint_kinds(b, k, anchor[:, :3], anchor[:, 3:], ax, qr, bool(on))
+
+    def set_joint_rates(self, rates):
+        """The motors' rates (n_joints,): body B of a lock joint turns relative to body A at +rate about the joint's axis (fixed
+        in A); 0 for every other kind.  Read by step_jointed; the motor angle theta advances by rate dt per accepted step."""
+        r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+        if not np.isfinite(r).all():
+            _fail("set_joint_rates: joint %d: the rate must be finite" % int(np.argmin(np.isfinite(r))))
+        self.ctx.set_joint_rates(r)
+
+    def joint_kinds(self):
+        """-> {on, by_kinds, body, anchor_a, anchor_b, kind, axis, q_rel, theta, rate} of the stored joints"""
+        return self.ctx.joint_kinds()
+
+    def hinge(self, a, b, point, axis):
+        """Rows of a five-row hinge between the bodies a and b (b = -1: the lab) at the current configuration: a ball joint at
+        the lab-frame point and an axis joint about the lab-frame direction axis."""
+        return hinge(*self.cb.getConfig(), a, b, point, axis)
+
+    def weld(self, a, b, point):
+        """Rows of a weld: a ball joint at the lab-frame point and a lock joint; the two bodies move as one."""
+        return weld(*self.cb.getConfig(), a, b, point)
+
+    def motor(self, a, b, point, axis):
+        """Rows of a motor or driven hinge: a ball joint at the lab-frame point and a lock joint about axis, driven by
+        set_joint_rates."""
+        return motor(*self.cb.getConfig(), a, b, point, axis)
+
     # -- periodic cell in x and y (include/rbl.h section 10) -----------------------------------------------------------------------
     def set_periodic(self, Lx, Ly, images=(1, 1), on=True):
         """A periodic cell of lengths Lx, Ly along x and y above the wall (0: that axis stays open): every mobility product --
@@ -373,7 +414,8 @@ class RigidBody:
 
     def joint_state(self):
         """-> (gaps p_A - p_B of every stored joint at the current configuration (n_joints, 3), phi of the last solve_jointed /
-        step_jointed (n_joints, 3); RuntimeError if there has been none with this joint set)"""
+        step_jointed (n_joints, 3); RuntimeError if there has been none with this joint set).  A set given through
+        set_joint_kinds -> (gap, phi, theta (n_joints,)): the gap rows of a lock or axis joint hold its angular gap e."""
         return self.ctx.joint_state()
 
     def interaction_forces(self):

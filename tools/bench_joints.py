@@ -18,10 +18,17 @@
                   over the first and over the second half of the steps, or the error that ended the run.  The largest dt at
                   which the gap does not grow (no error, second half at most twice the first) is reported for both.
 
+  (d) hinges      the solve of (a) at cfg 3 (or --configs) with a chain of hinges through the bodies in index order, the same axes and
+                  points both times: as two ball joints half a unit either side of the point on the axis (one redundant row a
+                  hinge, given an eigenvalue in the preconditioner) and as a ball joint and an axis joint (five rows, set_joint_kinds).
+                  Iterations, ms per solve and per iteration, and the shares of (a).
+  (e) ball        the ball-only cases of (a) on THIS build against the parent's (--parent-root), alternated visit by visit as in
+                  (b); the verdict per case compares the medians against the PARENT's own window spread.
+
 Every window is timed by the host clock around its work and ends in a device synchronise; every line carries its windows and
 their spread (max - min) / median.  One JSON line per measurement, appended to --out.
 
-    python tools/bench_joints.py [--parent-root DIR] [--kinds solve,off,spring] [--rounds 5] [--visits 2] [--out profiles/joints.jsonl]
+    python tools/bench_joints.py [--parent-root DIR] [--kinds solve,off,spring,hinges,ball] [--rounds 5] [--visits 2] [--out profiles/joints.jsonl]
 """
 import argparse
 import json
@@ -49,6 +56,26 @@ def pivots(X, seed=4):
     rng = np.random.default_rng(seed)
     return (np.array([[i, -1] for i in range(n)]),
             np.concatenate([0.3 * rng.standard_normal((n, 3)), X + 0.3 * rng.standard_normal((n, 3))], axis=1))
+
+
+def hinge_chain(X, Q, five, seed=6):
+    """a hinge between the bodies i and i + 1 for every i, at a point near the middle of the two centres about a random axis ->
+    the keyword arguments of set_joint_kinds: five rows a hinge (ball + axis joint) or two ball joints half a unit either side
+    of the point on the axis"""
+    from rigid_body_light_amd import _lib as lib
+    rng = np.random.default_rng(seed)
+    rows = []
+    for i in range(X.shape[0] - 1):
+        p = 0.5 * (X[i] + X[i + 1]) + 0.2 * rng.standard_normal(3)
+        ax = rng.standard_normal(3)
+        ax /= np.linalg.norm(ax)
+        if five:
+            rows.append(lib.hinge(X, Q, i, i + 1, p, ax))
+        else:
+            for s in (0.5, -0.5):
+                r = lib.hinge(X, Q, i, i + 1, p + s * ax, ax)
+                rows.append({k: v[:1] for k, v in r.items()})             # its ball joint alone
+    return lib.joint_rows(*rows)
 
 
 def joint_sets(name, X):
@@ -90,7 +117,7 @@ def worker(args):
         print("JSON " + json.dumps(d), flush=True)
 
     for kind in args.kinds.split(","):
-        if kind == "solve":
+        if kind in ("solve", "hinges"):
             for name in args.configs.split(","):
                 nb, nblb, wall = CONFIGS[name]
                 c = make_config(nb, nblb, wall)
@@ -106,8 +133,16 @@ def worker(args):
                 def jointed(m=200, rt=args.rtol):
                     its["last"] = rb.solve_jointed(F, max_iter=m, rtol=rt)[3]
                 out = {}
-                for case, fn, body, anchor in [("plain", plain, None, None)] + [(n_, jointed, b_, a_) for n_, b_, a_ in joint_sets(name, c["X"])]:
-                    if body is not None:
+                if kind == "hinges":
+                    Qn = c["Q"] / np.linalg.norm(c["Q"], axis=1, keepdims=True)
+                    sets = [(n_, hinge_chain(c["X"], Qn, five)) for n_, five in (("hinges_two_ball", False), ("hinges_five_row", True))]
+                    sets = [(n_, r["body"], r) for n_, r in sets]
+                else:
+                    sets = [(n_, b_, a_) for n_, b_, a_ in joint_sets(name, c["X"])]
+                for case, fn, body, anchor in [("plain", plain, None, None)] + [(n_, jointed, b_, a_) for n_, b_, a_ in sets]:
+                    if isinstance(anchor, dict):
+                        rb.set_joint_kinds(**anchor)
+                    elif body is not None:
                         rb.set_joints(body, anchor[:, :3], anchor[:, 3:])
                     fn()                                     # warm-up: code loading, factors, workspaces
                     ts = windows(fn, args.rounds, sync)
@@ -117,7 +152,7 @@ def worker(args):
                     t_hi = float(np.median(windows(lambda: fn(hi, 0.0), args.rounds, sync)))
                     slope = (t_hi - t_lo) / (hi - lo)
                     out[case] = dict(its=used, slope=slope, joints=0 if body is None else int(body.shape[0]))
-                    line("solve", name, ts, "solve", case=case, joints=out[case]["joints"], rtol=args.rtol, iterations=used,
+                    line(kind, name, ts, "solve", case=case, joints=out[case]["joints"], rtol=args.rtol, iterations=used,
                          ms_per_iteration=round(1e3 * slope, 4), ms_outside_iterations=round(1e3 * (t_lo - lo * slope), 4))
                 # one application of the same preconditioner alone, on device vectors (a context of its own)
                 ctx = DeviceContext(c["a"], c["eta"], wall, cfg=c["cfg"], dt=c["dt"], stream_ptr=torch.cuda.current_stream().cuda_stream)
@@ -270,17 +305,23 @@ def main():
             f.write(json.dumps(d) + "\n")
 
     kinds = args.kinds.split(",")
-    for kind in ("solve", "spring"):
+    for kind in ("solve", "spring", "hinges"):
         if kind in kinds:
             for d in visit(HERE, "this", kind):
                 emit(d)
-    if "off" in kinds:
+    for against in ("off", "ball"):
+        if against not in kinds:
+            continue
         pooled = {}                                           # parent, this, parent, this, ...
         builds = ([("parent", os.path.abspath(args.parent_root))] if args.parent_root else []) + [("this", HERE)]
         for v in range(args.visits):
             for label, root in builds:
-                for d in visit(root, label, "off"):
+                for d in visit(root, label, "off" if against == "off" else "solve"):
+                    if "windows_ms" not in d:
+                        continue                              # (the shares of a solve visit: not timed windows)
                     d["visit"] = v
+                    if against == "ball":
+                        d["mode"] = "ball_solve_" + d["case"]
                     emit(d)
                     pooled.setdefault((d["mode"], d["workload"]), {}).setdefault(label, []).extend(d["windows_ms"])
         for (mode, workload), w in pooled.items():
