@@ -759,7 +759,55 @@ int rbl_interaction_stats(rbl_ctx *ctx, int64_t *body_pairs, int64_t *blob_pairs
  *                             replica give bitwise rbl_ensemble_step_brownian_mixed.  kBT <= 1e-10: rbl_ensemble_step_mixed_dof.
  *                             A mask with a partly prescribed rotation is RBL_ERR_ARG before the device is touched; the message
  *                             names the replica and the body.  The other refusals are rbl_ensemble_step_brownian_mixed's.
- * A Brownian RUN with prescribed_per = 6 stays refused (below): it is the follow-up and needs only this kernel in its sequence. */
+ * A Brownian RUN with prescribed_per = 6 stays refused (below): it is the follow-up and needs only this kernel in its sequence.
+ *
+ * With hard joints (section 9): the jointed saddle solve and the jointed deterministic step of every replica, ONE solver launch
+ * whatever R is (k_gmres_small_jt: the one-kernel solver with the joints' rows, their Schur complement S = J N~^-1 J^T assembled,
+ * factored, pivot-tested and inverted in LDS, and section 9's exact right preconditioner with the diagonal M~).  The joint set is
+ * the one rbl_set_joints / rbl_set_joint_kinds stored: topology, kinds, anchors, axes and q_rel are shared by all replicas, body
+ * indices are local to a replica (checked against the ensemble's N_bod at these calls); the motors' rates and angles are the
+ * replica's own.
+ *   rbl_ensemble_set_joint_rates   rate[sets n_joints], sets = 1 (every replica alike) or R; only a lock joint takes a non-zero rate.
+ *   rbl_ensemble_set_joint_angles  theta[sets n_joints]: a sweep of stroke phases, or a restart.  Both are zero for a new joint set
+ *                             and after rbl_ensemble_set_config with another R or another N_bod (a new ensemble: the joint table
+ *                             on the device is made again for its shape, and the phi of the last solve is dropped); a call
+ *                             with the same R and N_bod keeps them.
+ *   rbl_ensemble_solve_jointed     rbl_solve_jointed at every replica's configuration; nothing moves, the force model is not
+ *                             evaluated.  F_body[R 6 N_bod]; slip[R n3] or NULL; joint_rhs[R 3 n_joints] or NULL (zero);
+ *                             lambda[R n3], U[R 6 N_bod], phi[R 3 n_joints] may be NULL; iters[R], resid[R].
+ *   rbl_ensemble_step_jointed      rbl_step_jointed for every replica: the force model's loads and the flow model's term at q^n as
+ *                             in rbl_ensemble_step_deterministic, c = -(gamma / dt) gap + joint_velocity - rate ah (a lock's
+ *                             rows) formed inside the solver launch, the solve, evolve_X_Q(U).  The first failing replica names
+ *                             the error and nothing commits; when the step commits, and only then, theta_j += rate_j dt per replica
+ *                             (product and sum rounded one after the other).  A fixed number of launches whatever R is.
+ *   rbl_ensemble_joint_state       gap[R 3 n_joints] at the current configurations (an angular joint's rows: e, or P e), phi of the
+ *                             last jointed ensemble solve or step with this set, theta[R n_joints]; any may be NULL.
+ * Joints switched off or never set: the step is bitwise rbl_ensemble_step_deterministic and the solve is the unjointed one-kernel
+ * solve on [slip ; -F_body] at the current configuration (phi untouched).  Replica r of R is bitwise the R = 1 call on its data.
+ * Capacity: rbl_gmres_small_fits' limits with, for n_j joints, 3 n_j more doubles in each of the three vectors and in every basis
+ * vector kept in LDS, and 16 n_j + 18 n_j^2 + (7 n_j + N_bod + 2) / 2 doubles of joint data (lever arms, redundant rows, gaps,
+ * sigmas and S's diagonal; S's factor and S^-1; the integer tables), all within the solver's 150 KB: 10 x 12 blobs with 11 joints
+ * or 9 x 12 blobs with 16 joints at max_iter = 100; about 22 joints at the most.  A set that does not fit is RBL_ERR_SIZE, the
+ * message telling a shape that is beyond the solver anyway from one that only the joints' LDS pushes out.
+ * Refused before any device work: NULL F_body, gamma outside [0, 1], dt <= 0 (a step), max_iter outside 1 .. 255, rtol < 0
+ * (RBL_ERR_ARG); sets other than 1 or R, a non-zero rate on a joint that is no lock, a non-finite value (RBL_ERR_ARG); a
+ * communicator (RBL_ERR_ARG); no ensemble configuration, a joint that names a body >= N_bod (RBL_ERR_STATE); RBL_ERR_SIZE above.
+ * A redundant loop of joints in some replica is RBL_ERR_NOT_SPD with "redundant" and the first failing replica in the message;
+ * nothing moved, no motor's angle advanced, and the context serves a valid set afterwards.  (The lost pivot of S has an error
+ * bit of its own: a body's 6 x 6 preconditioner block that fails its Cholesky is RBL_ERR_NOT_SPD with the unjointed solver's message.)
+ * Not offered with joints: prescribed masks, Brownian steps, rbl_ensemble_run (per-replica angles and rates are kept so that a
+ * run can advance them on the device), lock-step right-hand sides.  Every other entry point of this section ignores the joints. */
+int rbl_ensemble_set_joint_rates(rbl_ctx *ctx, const double *rate, int sets);
+int rbl_ensemble_set_joint_angles(rbl_ctx *ctx, const double *theta, int sets);
+int rbl_ensemble_solve_jointed(rbl_ctx *ctx, const double *F_body, const double *slip, const double *joint_rhs, int max_iter, double rtol,
+                               double *lambda, double *U, double *phi, int *iters, double *resid);
+int rbl_ensemble_step_jointed(rbl_ctx *ctx, const double *F_body, const double *slip, const double *joint_velocity, double gamma,
+                              int max_iter, double rtol, double *phi, int *iters, double *resid);
+int rbl_ensemble_joint_state(rbl_ctx *ctx, double *gap, double *phi, double *theta);
+/* The capacity rule above as a query without a context: 1 when N_bod bodies of N_blb blobs with n_joints joints fit the jointed
+ * one-kernel solver at max_iter, 0 otherwise; *lds_bytes (may be NULL) the bytes its vectors and joint data take of the 153600.
+ * n_joints = 0: the rule of the unjointed ensembles. */
+int rbl_ensemble_joints_fit(int N_blb, int N_bod, int max_iter, int n_joints, int64_t *lds_bytes);
 int rbl_ensemble_set_config(rbl_ctx *ctx, int R, int N_bod, const double *X, const double *Q);
 int rbl_ensemble_get_config(rbl_ctx *ctx, double *X, double *Q);
 int rbl_ensemble_info(const rbl_ctx *ctx, int *R, int *N_bod);
@@ -1257,8 +1305,10 @@ int rbl_ensemble_step_moments(rbl_ctx *ctx, double *D);
  * rbl_solve_jointed is the plain solve (rbl_gmres_saddle_dev on [slip; -F_body], cold start; joint_rhs and phi are not touched)
  * and rbl_step_jointed is rbl_step_deterministic with a cold start.
  *
- * Not offered, each refused before any device work: contexts with a communicator (RBL_ERR_ARG); contexts that hold an ensemble
- * (RBL_ERR_STATE; the ensemble entry points of section 5 ignore the joints like every other); and, having no entry point at
+ * Not offered, each refused before any device work: contexts with a communicator (RBL_ERR_ARG); the calls of THIS section on a
+ * context that holds an ensemble (RBL_ERR_STATE) -- an ensemble's jointed solve and step are section 5's
+ * rbl_ensemble_solve_jointed / rbl_ensemble_step_jointed, which read the joint set stored here; the other ensemble entry points
+ * ignore the joints like every other, and rbl_ensemble_run has no jointed form --; and, having no entry point at
  * all: the jointed solve together with prescribed masks (section 7), lock-step right-hand sides, Brownian steps (the drift of a
  * constrained suspension has not been derived here), joint kinds other than those below (no slider, no universal joint).
  *

@@ -136,6 +136,11 @@ def lib(path=None):
         L.rbl_ensemble_step_mixed_dof.argtypes = L.rbl_ensemble_step_mixed.argtypes
         L.rbl_ensemble_step_brownian_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, dbl, C.c_int, dbl, vp, vp, vp]
         L.rbl_ensemble_run.argtypes = [vp, C.POINTER(RunOpts), C.POINTER(RunOut)]
+        L.rbl_ensemble_set_joint_rates.argtypes = L.rbl_ensemble_set_joint_angles.argtypes = [vp, vp, C.c_int]
+        L.rbl_ensemble_solve_jointed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, vp, vp]
+        L.rbl_ensemble_step_jointed.argtypes = [vp, vp, vp, vp, dbl, C.c_int, dbl, vp, vp, vp]
+        L.rbl_ensemble_joint_state.argtypes = [vp, vp, vp, vp]
+        L.rbl_ensemble_joints_fit.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(i64)]
         L.rbl_velocity_field.argtypes = [vp, vp, i64, vp, vp, i64, vp]
         L.rbl_velocity_field_dev.argtypes = [vp, vp, i64, vp, vp, i64, vp]
         L.rbl_velocity_field_info.argtypes = [vp, i64, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
@@ -1297,6 +1302,73 @@ class DeviceContext:
         iterations[R], residual estimates[R]); W as ensemble_step_brownian"""
         return self._ens_step_brownian_mixed("ensemble_step_brownian_mixed_dof", 6, prescribed6, body_in, W, seed, split_rand, delta,
                                              max_iter, rtol, slip)
+
+    # -- hard joints of an ensemble (include/rbl.h section 5; the set is set_joints' / set_joint_kinds') ------------------------
+    def _ens_joint_count(self):
+        n = C.c_int(0)
+        self._chk(self.L.rbl_get_joints(self.h, C.byref(n), None, None, None))
+        return n.value
+
+    def _ens_joint_values(self, who, v):
+        """(n_joints,) -- every replica alike -- or (R, n_joints) -> (contiguous array, sets)"""
+        import numpy as np
+        R, n = self.ensemble_info()[0], self._ens_joint_count()
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if not n or v.shape not in ((n,), (R, n)):
+            raise ValueError("%s: one value per stored joint, shape (%d,) or (%d, %d); got %s" % (who, n, R, n, v.shape))
+        return v, (1 if v.ndim == 1 else R)
+
+    def ensemble_set_joint_rates(self, rates):
+        """the motors' rates: (n_joints,) for every replica, or (R, n_joints); non-zero on lock joints only"""
+        r, sets = self._ens_joint_values("ensemble_set_joint_rates", rates)
+        self._chk(self.L.rbl_ensemble_set_joint_rates(self.h, r.ctypes.data, sets))
+
+    def ensemble_set_joint_angles(self, theta):
+        """the motors' angles: (n_joints,) for every replica, or (R, n_joints) -- a sweep of stroke phases, or a restart"""
+        t, sets = self._ens_joint_values("ensemble_set_joint_angles", theta)
+        self._chk(self.L.rbl_ensemble_set_joint_angles(self.h, t.ctypes.data, sets))
+
+    def _ens_jointed_args(self, F_body, slip, jv, jname):
+        R, nb = self.ensemble_info()
+        nj = self._joints_active()
+        F = self._ens_vec(F_body, 6 * nb, "F_body")
+        sl = None if slip is None else self._ens_vec(slip, 3 * nb * self._sizes()[1], "slip")
+        jr = None if jv is None or not nj else self._ens_vec(jv, 3 * nj, jname)
+        return R, nb, nj, F, sl, jr
+
+    def ensemble_solve_jointed(self, F_body, slip=None, joint_rhs=None, max_iter=100, rtol=1.0e-8):
+        """solve_jointed at every replica's configuration (nothing moves) -> (lambda (R, n3), U (R, 6 N_bod), phi (R, 3 n_joints),
+        iterations[R], residual estimates[R]).  Joints off or never set: the unjointed solve, phi empty"""
+        import numpy as np
+        R, nb, nj, F, sl, jr = self._ens_jointed_args(F_body, slip, joint_rhs, "joint_rhs")
+        lam, U, phi = np.zeros((R, 3 * nb * self._sizes()[1])), np.zeros((R, 6 * nb)), np.zeros((R, 3 * nj))
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(self.L.rbl_ensemble_solve_jointed(self.h, F.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                    None if jr is None else jr.ctypes.data, int(max_iter), float(rtol or 0.0),
+                                                    lam.ctypes.data, U.ctypes.data, phi.ctypes.data if nj else None, it.ctypes.data,
+                                                    res.ctypes.data))
+        return lam, U, phi, it, res
+
+    def ensemble_step_jointed(self, F_body, slip=None, joint_velocity=None, gamma=1.0, max_iter=50, rtol=1.0e-8):
+        """one deterministic step of every replica with the joints: J U = -(gamma / dt) gap + joint_velocity -> (phi (R, 3 n_joints),
+        iterations[R], residual estimates[R])"""
+        import numpy as np
+        R, nb, nj, F, sl, jr = self._ens_jointed_args(F_body, slip, joint_velocity, "joint_velocity")
+        phi = np.zeros((R, 3 * nj))
+        it, res = np.zeros(R, dtype=np.int32), np.zeros(R)
+        self._chk(self.L.rbl_ensemble_step_jointed(self.h, F.ctypes.data, None if sl is None else sl.ctypes.data,
+                                                   None if jr is None else jr.ctypes.data, float(gamma), int(max_iter), float(rtol or 0.0),
+                                                   phi.ctypes.data if nj else None, it.ctypes.data, res.ctypes.data))
+        return phi, it, res
+
+    def ensemble_joint_state(self, phi=True):
+        """-> (gap (R, n_joints, 3) at the replicas' configurations, phi (R, n_joints, 3) of the last jointed ensemble solve or
+        step, theta (R, n_joints)).  phi=False: before any jointed solve has succeeded with this set -> (gap, None, theta)"""
+        import numpy as np
+        R, n = self.ensemble_info()[0], self._ens_joint_count()
+        gap, ph, theta = np.zeros((R, max(n, 1), 3)), np.zeros((R, max(n, 1), 3)), np.zeros((R, max(n, 1)))
+        self._chk(self.L.rbl_ensemble_joint_state(self.h, gap.ctypes.data, ph.ctypes.data if phi else None, theta.ctypes.data))
+        return gap[:, :n], (ph[:, :n] if phi else None), theta[:, :n]
 
     def ensemble_run(self, n_steps, F_body=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error=RUN_STOP,
                      check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8, per=1):

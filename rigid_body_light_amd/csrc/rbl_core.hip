@@ -34,6 +34,9 @@ int rbl_flags_to_status(rbl_ctx *c, unsigned f)
     return rbl_fail(c, RBL_ERR_OVERLAP, "ERROR: TWO BLOBS ARE OVERLAPPING OR TOO CLOSELY POSITIONED.");
   if (f & RBL_FLAG_NOT_SPD)
     return rbl_fail(c, RBL_ERR_NOT_SPD, "Cholesky: matrix is not positive definite");
+  if (f & RBL_FLAG_REDUNDANT)
+    return rbl_fail(c, RBL_ERR_NOT_SPD, "the joints are redundant: their Schur complement J N^-1 J^T is not positive definite (a loop of "
+                                        "joints constrains a relative coordinate twice)");
   if (f & RBL_FLAG_CAPACITY)
     return rbl_fail(c, RBL_ERR_CAPACITY, "interactions: a body has more neighbours within 2 R_body + r_cut than its list holds");
   if (f & RBL_FLAG_INTERNAL)
@@ -157,6 +160,8 @@ static const RblBufRow kDevBufs[] = {
     {&rbl_ctx::d_jtS, RBL_BUF_SCRATCH},           // joint Schur complement and its inverse: reserved once per jointed solve, before it is assembled
     {&rbl_ctx::d_jtw, RBL_BUF_SCRATCH},           // jointed solve's vectors: reserved once, at the start of each section 9 entry point
     {&rbl_ctx::d_jtphi, RBL_BUF_PERSIST},         // joint forces of the last jointed solve (jt_phi_valid)
+    {&rbl_ctx::d_ens_jt, RBL_BUF_PERSIST},        // an ensemble's joint table with every replica's angles and rates (ens_jt_valid)
+    {&rbl_ctx::d_ens_jtw, RBL_BUF_SCRATCH},       // jointed ensemble solve: reserved once, at the start of each jointed section 5 entry point
 };
 
 // the poison pattern, on the context's stream; nothing while the stream is being captured into a graph (a capture may not

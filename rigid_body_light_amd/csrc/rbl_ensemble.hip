@@ -945,6 +945,219 @@ int ens_mx_step_bd(rbl_ctx *c, const char *who, int per, const uint8_t *prescrib
   return ens_step_bd(c, prescribed, body_in, slip, W, seed, split_rand, delta, max_iter, rtol, F, iters, resid, per);
 }
 
+// ---- hard joints (include/rbl.h sections 5 and 9): the jointed solve and step of every replica --------------------------------
+// The joint set is the context's (rbl_set_joints / rbl_set_joint_kinds), shared by the replicas; the motor angles and rates are
+// the replica's own and live here.  One launch of k_gmres_small_jt (rbl_small_joints.hip) solves every replica's jointed system.
+
+bool ens_jt_active(const rbl_ctx *c) { return c->jt_on && c->jt_n > 0; }
+
+// angles and rates of the stored set for the ensemble's R replicas of N_bod bodies: zeros, and the device table stale, when the
+// set, R or N_bod changed since they were made
+void ens_jt_sync(rbl_ctx *c)
+{
+  const size_t n = (size_t)c->ens_R * (size_t)c->jt_n;
+  if (c->ens_jt_gen == c->jt_gen && c->ens_jt_R == c->ens_R && c->ens_jt_Nb == c->ens_Nb && c->ens_jt_theta.size() == n) return;
+  c->ens_jt_theta.assign(n, 0.0);
+  c->ens_jt_rate.assign(n, 0.0);
+  c->ens_jt_gen = c->jt_gen; c->ens_jt_R = c->ens_R; c->ens_jt_Nb = c->ens_Nb;   // (the device table's layout holds N_bod + 1 row starts)
+  c->ens_jt_valid = false; c->ens_jt_phi_valid = false;
+}
+
+// what every jointed ensemble call asks before it touches a device (the style of ens_mx_check)
+int ens_jt_check(rbl_ctx *c, const char *who, const double *F_body, int max_iter, double rtol)
+{
+  const std::string w(who);
+  if (!F_body) return rbl_fail(c, RBL_ERR_ARG, w + ": F_body is NULL");
+  if (max_iter < 1 || max_iter > 255) return rbl_fail(c, RBL_ERR_ARG, w + ": max_iter must lie in 1 .. 255 (no restart)");
+  if (!(rtol >= 0.0)) return rbl_fail(c, RBL_ERR_ARG, w + ": rtol must be >= 0");
+  int rc = need_params(c); if (rc) return rc;
+  if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, w + ": ensemble: not on a context with a communicator (run one ensemble per process)");
+  if (!c->ens_R) return rbl_fail(c, RBL_ERR_STATE, w + ": ensemble: no ensemble configuration (rbl_ensemble_set_config)");
+  if (c->S.N_blb != c->ens_Nblb) return rbl_fail(c, RBL_ERR_STATE, w + ": ensemble: the structure changed since rbl_ensemble_set_config");
+  const bool on = ens_jt_active(c);
+  if (on && c->jt_top >= c->ens_Nb)
+    for (int j = 0; j < c->jt_n; ++j) {
+      const int m = std::max(c->jt_body[2 * (size_t)j], c->jt_body[2 * (size_t)j + 1]);
+      if (m >= c->ens_Nb)
+        return rbl_fail(c, RBL_ERR_STATE, w + ": joint " + std::to_string(j) + " names body " + std::to_string(m) + ", a replica has " +
+                                              std::to_string(c->ens_Nb) + " bodies (indices are local to a replica)");
+    }
+  if (!rbl_gmres_small_jt_fits(c->S.N_blb, c->ens_Nb, max_iter, on ? c->jt_n : 0))
+    return rbl_fail(c, RBL_ERR_SIZE,
+                    rbl_gmres_small_fits(c->S.N_blb, c->ens_Nb, max_iter, false)
+                        ? w + ": this shape fits the one-kernel solver without joints, but not with the LDS of " + std::to_string(c->jt_n) +
+                              " joints (" + std::to_string(rbl_gmres_small_jt_lds_bytes(c->S.N_blb, c->ens_Nb, max_iter, c->jt_n)) + " of 153600 bytes)"
+                        : w + ": ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)");
+  return RBL_OK;
+}
+
+// the joint table on the device (RblEnsJoints): once per set, and again after every change of an angle or a rate
+int ens_jt_upload(rbl_ctx *c, RblEnsJoints *T)
+{
+  ens_jt_sync(c);
+  const int nj = c->jt_n, nb = c->ens_Nb;
+  const size_t ne = c->jt_ends.size() / 2, Rn = (size_t)c->ens_R * nj;
+  const size_t ndbl = 13 * (size_t)nj + 2 * Rn, nint = 5 * (size_t)nj + (size_t)nb + 1 + 2 * ne;
+  int rc = rbl_dev_reserve(c, c->d_ens_jt, sizeof(double) * ndbl + sizeof(int) * nint); if (rc) return rc;
+  double *d = (double *)c->d_ens_jt.p;
+  int *di = (int *)(d + ndbl);
+  T->anchor = d; T->ang = d + 6 * (size_t)nj; T->theta = d + 13 * (size_t)nj; T->rate = T->theta + Rn;
+  T->body = di; T->mate = di + 2 * (size_t)nj; T->kind = di + 4 * (size_t)nj; T->ptr = di + 5 * (size_t)nj; T->ends = T->ptr + nb + 1;
+  T->n = nj; T->n_ends = (int)ne;
+  if (c->ens_jt_valid) return RBL_OK;
+  std::vector<double> hd(ndbl);
+  std::copy(c->jt_anchor.begin(), c->jt_anchor.end(), hd.begin());
+  std::copy(c->jt_ang.begin(), c->jt_ang.end(), hd.begin() + 6 * (size_t)nj);
+  std::copy(c->ens_jt_theta.begin(), c->ens_jt_theta.end(), hd.begin() + 13 * (size_t)nj);
+  std::copy(c->ens_jt_rate.begin(), c->ens_jt_rate.end(), hd.begin() + 13 * (size_t)nj + Rn);
+  std::vector<int> hi(nint);
+  std::copy(c->jt_body.begin(), c->jt_body.end(), hi.begin());
+  std::copy(c->jt_mate.begin(), c->jt_mate.end(), hi.begin() + 2 * (size_t)nj);
+  std::copy(c->jt_kind.begin(), c->jt_kind.end(), hi.begin() + 4 * (size_t)nj);
+  int *ptr = hi.data() + 5 * (size_t)nj;                // the CSR of joint ends with a row for EVERY body of a replica
+  {                                                     // (jt_rows is in increasing body order: a body without a joint gets an empty row)
+    std::vector<char> has((size_t)nb, 0);
+    for (size_t i = 0; i < c->jt_rows.size(); ++i) { has[c->jt_rows[i]] = 1; ptr[c->jt_rows[i]] = c->jt_ptr[i]; }
+    int next = (int)ne;
+    ptr[nb] = next;
+    for (int b = nb - 1; b >= 0; --b) {
+      if (has[b]) next = ptr[b];
+      else ptr[b] = next;
+    }
+  }
+  std::copy(c->jt_ends.begin(), c->jt_ends.end(), hi.begin() + 5 * (size_t)nj + nb + 1);
+  if ((rc = copy_h2d(c, d, hd.data(), sizeof(double) * ndbl))) return rc;
+  if ((rc = copy_h2d(c, di, hi.data(), sizeof(int) * nint))) return rc;
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  c->ens_jt_valid = true;
+  return RBL_OK;
+}
+
+// rhs of every replica: [slip (or 0) ; -(F - FT) ; jr (or 0)], k_ens_rhs_det with the joint rows behind
+__global__ __launch_bounds__(ET) void k_ens_rhs_jt(int R, int n3, int nb6, int nj3, const double *__restrict__ slip, const double *__restrict__ F,
+                                                   const double *__restrict__ FT, const double *__restrict__ jr, double *__restrict__ rhs)
+{
+  const long nsys = (long)n3 + nb6 + nj3, idx = (long)blockIdx.x * ET + threadIdx.x;
+  if (idx >= (long)R * nsys) return;
+  const long r = idx / nsys, e = idx - r * nsys;
+  if (e < n3) { rhs[idx] = slip ? slip[r * n3 + e] : 0.0; return; }
+  if (e >= n3 + nb6) { rhs[idx] = jr ? jr[r * nj3 + e - n3 - nb6] : 0.0; return; }
+  double f = F[r * nb6 + e - n3];
+  if (FT) f = 1.0 * f + -1.0 * FT[r * nb6 + e - n3];
+  rhs[idx] = -1.0 * f + 0.0;
+}
+
+// joints switched off or never set: the unjointed one-kernel solve on [slip ; -F] at the current configuration
+int ens_jt_plain_solve(rbl_ctx *c, const double *F_body, const double *slip, int max_iter, double rtol, double *lambda, double *U, int *iters,
+                       double *resid)
+{
+  EnsWork w;
+  int rc;
+  if ((rc = ens_work(c, max_iter, &w))) return rc;
+  EnsStepIn in;
+  in.F_body = F_body; in.slip = slip;
+  if ((rc = ens_enqueue_det(c, w, in, max_iter, rtol, false))) return rc;
+  const int R = c->ens_R;
+  const size_t n3 = (size_t)3 * c->ens_Nb * c->S.N_blb, nb6 = (size_t)6 * c->ens_Nb;
+  std::vector<double> x((size_t)R * (n3 + nb6));
+  if ((rc = copy_d2h(c, x.data(), w.x, sizeof(double) * x.size()))) return rc;
+  if ((rc = ens_finish(c, w, R, iters, resid, false))) return rc;
+  for (int r = 0; r < R; ++r) {
+    if (lambda) std::memcpy(lambda + (size_t)r * n3, x.data() + (size_t)r * (n3 + nb6), sizeof(double) * n3);
+    if (U) std::memcpy(U + (size_t)r * nb6, x.data() + (size_t)r * (n3 + nb6) + n3, sizeof(double) * nb6);
+  }
+  return RBL_OK;
+}
+
+// the jointed solve of every replica at the current configuration; move: a time step -- the force model's loads and the flow
+// model's slip at q^n (ens_begin), c formed in the kernel from the gaps (coef = -gamma / dt), k_ens_evolve, and on success the
+// commit and the motors' angles
+int ens_jt_solve(rbl_ctx *c, const char *who, const double *F_body, const double *slip, const double *jr, bool move, double coef, int max_iter,
+                 double rtol, double *lambda, double *U, double *phi, int *iters, double *resid)
+{
+  const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb, nj = c->jt_n;
+  const size_t n3 = (size_t)3 * Nb * nbl, nb6 = (size_t)6 * Nb, nj3 = (size_t)3 * nj, nsys = n3 + nb6 + nj3, Rz = (size_t)R;
+  c->ens_jt_phi_valid = false;
+  EnsWork w;
+  int rc;
+  if ((rc = ens_work(c, max_iter, &w))) return rc;
+  RblEnsJoints T;
+  if ((rc = ens_jt_upload(c, &T))) return rc;
+  const size_t wd = rbl_gmres_small_jt_work_doubles(nbl, Nb, max_iter, nj);
+  if ((rc = rbl_dev_reserve(c, c->d_ens_jtw, sizeof(double) * Rz * (2 * nsys + nj3 + wd)))) return rc;
+  double *rhs = (double *)c->d_ens_jtw.p, *x = rhs + Rz * nsys, *djr = x + Rz * nsys, *gm = djr + Rz * nj3;
+  if (jr && (rc = copy_h2d(c, djr, jr, sizeof(double) * Rz * nj3))) return rc;
+  const double *FT, *SL;
+  if ((rc = ens_begin(c, w, F_body, slip, &FT, &SL, move))) return rc;
+  const long tot = (long)R * (long)nsys;
+  hipLaunchKernelGGL(k_ens_rhs_jt, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, (int)n3, (int)nb6, (int)nj3, SL,
+                     (const double *)w.F, FT, jr ? (const double *)djr : nullptr, rhs);
+  const RblParams P = rbl_make_params(c->S.a, c->S.eta);
+  const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
+  rc = rbl_launch_gmres_small_ens_jt(c->stream, P, c->S.wall, X, Q, ens_cfg(c), nbl, Nb, R, rhs, x, max_iter, rtol, gm, w.iters, w.resid,
+                                     w.rerr, T, move ? 1 : 0, coef);
+  if (rc) return rbl_fail(c, rc, std::string(who) + ": the one-kernel jointed solver does not fit this device's LDS");
+  if (move) {
+    const int nbod = R * Nb;
+    if (c->record_mom) {                                 // RBL_OPT_RECORD_MOMENTS, as ens_solve_evolve
+      c->ens_mom_R = 0;
+      if ((rc = rbl_dev_reserve(c, c->d_ens_mom, sizeof(double) * 9 * (size_t)nbod))) return rc;
+      flow_launch_moments(c, nullptr, Q, ens_cfg(c), x, Nb, nbod, (int64_t)nsys, (double *)c->d_ens_mom.p);
+    }
+    hipLaunchKernelGGL(k_ens_evolve, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, (long)nsys, (long)n3, c->S.dt,
+                       (const double *)x, X, Q, ens_X(c, c->ens_cur ^ 1), ens_Q(c, c->ens_cur ^ 1), w.rerr);
+  }
+  std::vector<double> hx(Rz * nsys);
+  if ((rc = copy_d2h(c, hx.data(), x, sizeof(double) * hx.size()))) return rc;
+  // a redundant joint set: RBL_FLAG_REDUNDANT in the replica's word, which ens_finish turns into RBL_ERR_NOT_SPD with the replica named
+  if ((rc = ens_finish(c, w, R, iters, resid, move))) return rc;
+  c->ens_jt_phi.resize(Rz * nj3);
+  for (int r = 0; r < R; ++r) {
+    const double *xr = hx.data() + (size_t)r * nsys;
+    if (lambda) std::memcpy(lambda + (size_t)r * n3, xr, sizeof(double) * n3);
+    if (U) std::memcpy(U + (size_t)r * nb6, xr + n3, sizeof(double) * nb6);
+    if (phi) std::memcpy(phi + (size_t)r * nj3, xr + n3 + nb6, sizeof(double) * nj3);
+    std::memcpy(c->ens_jt_phi.data() + (size_t)r * nj3, xr + n3 + nb6, sizeof(double) * nj3);
+  }
+  c->ens_jt_phi_valid = true;
+  if (move) {                                            // the step committed: theta_j += rate_j dt, product and sum rounded one after the other
+    bool moved = false;
+    for (size_t i = 0; i < c->ens_jt_rate.size(); ++i)
+      if (c->ens_jt_rate[i] != 0.0) {
+        volatile double d = c->ens_jt_rate[i] * c->S.dt;
+        c->ens_jt_theta[i] += d;
+        moved = true;
+      }
+    if (moved) c->ens_jt_valid = false;
+  }
+  return RBL_OK;
+}
+
+// [sets n_joints] values, sets = 1 (every replica alike) or R, into the ensemble's [R n_joints]
+int ens_jt_set_values(rbl_ctx *c, const char *who, const double *v, int sets, bool rates)
+{
+  if (!c) return RBL_ERR_ARG;
+  const std::string w(who);
+  if (!c->ens_R) return rbl_fail(c, RBL_ERR_STATE, w + ": ensemble: no ensemble configuration (rbl_ensemble_set_config)");
+  if (c->jt_n < 1) return rbl_fail(c, RBL_ERR_STATE, w + ": no joints have been set (rbl_set_joint_kinds)");
+  if (!v) return rbl_fail(c, RBL_ERR_ARG, w + ": the array is NULL");
+  if (sets != 1 && sets != c->ens_R) return rbl_fail(c, RBL_ERR_ARG, w + ": sets must be 1 or R = " + std::to_string(c->ens_R));
+  for (int s = 0; s < sets; ++s)
+    for (int j = 0; j < c->jt_n; ++j) {
+      const double x = v[(size_t)s * c->jt_n + j];
+      const std::string at = w + ": set " + std::to_string(s) + ", joint " + std::to_string(j) + ": ";
+      if (!std::isfinite(x)) return rbl_fail(c, RBL_ERR_ARG, at + "the value must be finite");
+      if (rates && x != 0.0 && c->jt_kind[j] != RBL_JOINT_LOCK)
+        return rbl_fail(c, RBL_ERR_ARG, at + "only a lock joint (RBL_JOINT_LOCK) takes a rate; it must be 0 here");
+    }
+  ens_jt_sync(c);
+  std::vector<double> &dst = rates ? c->ens_jt_rate : c->ens_jt_theta;
+  for (int r = 0; r < c->ens_R; ++r)
+    std::copy(v + (size_t)(sets == 1 ? 0 : r) * c->jt_n, v + (size_t)(sets == 1 ? 0 : r) * c->jt_n + c->jt_n, dst.begin() + (size_t)r * c->jt_n);
+  c->ens_jt_valid = false;
+  return RBL_OK;
+}
+
 }  // namespace
 
 // ---- C ABI (include/rbl.h section 5) --------------------------------------------------------------------------------
@@ -975,6 +1188,7 @@ int rbl_ensemble_set_config(rbl_ctx *c, int R, int N_bod, const double *X, const
   // two configuration sets (committed, written by a step) and the reference configuration
   if ((rc = rbl_dev_reserve(c, c->d_ens, sizeof(double) * (2 * (nx + nq) + 3 * (size_t)c->S.N_blb)))) return rc;
   c->ens_R = R; c->ens_Nb = N_bod; c->ens_Nblb = c->S.N_blb; c->ens_cur = 0;
+  c->ens_jt_valid = false; c->ens_jt_phi_valid = false;  // a joint table on the device, and the last phi, belonged to the ensemble before
   c->ens_cfg_host.clear();
   if ((rc = copy_h2d(c, ens_X(c, 0), X, sizeof(double) * nx))) { c->ens_R = 0; return rc; }
   if ((rc = copy_h2d(c, ens_Q(c, 0), Qn.data(), sizeof(double) * nq))) { c->ens_R = 0; return rc; }
@@ -1180,4 +1394,80 @@ int rbl_ensemble_flow_slip(rbl_ctx *c, double *out)
   if ((rc = copy_d2h(c, out, w.slip, vb))) return rc;
   RBL_HIP(c, hipStreamSynchronize(c->stream));
   return RBL_OK;
+}
+
+// ---- hard joints of an ensemble (include/rbl.h section 5; the joint set is section 9's, rbl_set_joints / rbl_set_joint_kinds) ----
+
+int rbl_ensemble_set_joint_rates(rbl_ctx *c, const double *rate, int sets)
+{
+  return ens_jt_set_values(c, "ensemble_set_joint_rates", rate, sets, true);
+}
+
+int rbl_ensemble_set_joint_angles(rbl_ctx *c, const double *theta, int sets)
+{
+  return ens_jt_set_values(c, "ensemble_set_joint_angles", theta, sets, false);
+}
+
+int rbl_ensemble_solve_jointed(rbl_ctx *c, const double *F_body, const double *slip, const double *joint_rhs, int max_iter, double rtol,
+                               double *lambda, double *U, double *phi, int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_solve_jointed");
+  int rc = ens_jt_check(c, "ensemble_solve_jointed", F_body, max_iter, rtol); if (rc) return rc;
+  if ((rc = ens_ready(c))) return rc;
+  if (!ens_jt_active(c)) return ens_jt_plain_solve(c, F_body, slip, max_iter, rtol, lambda, U, iters, resid);
+  return ens_jt_solve(c, "ensemble_solve_jointed", F_body, slip, joint_rhs, false, 0.0, max_iter, rtol, lambda, U, phi, iters, resid);
+}
+
+int rbl_ensemble_step_jointed(rbl_ctx *c, const double *F_body, const double *slip, const double *joint_velocity, double gamma, int max_iter,
+                              double rtol, double *phi, int *iters, double *resid)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_step_jointed");
+  if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_jointed: F_body is NULL");
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_jointed: gamma must lie in [0, 1]");
+  if (ens_jt_active(c) && !(c->S.dt > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_jointed: dt must be positive");
+  int rc = ens_jt_check(c, "ensemble_step_jointed", F_body, max_iter, rtol); if (rc) return rc;
+  if (!ens_jt_active(c)) return rbl_ensemble_step_deterministic(c, F_body, slip, max_iter, rtol, iters, resid);
+  if ((rc = ens_flow_check(c))) return rc;
+  if ((rc = ens_ready(c))) return rc;
+  return ens_jt_solve(c, "ensemble_step_jointed", F_body, slip, joint_velocity, true, -gamma / c->S.dt, max_iter, rtol, nullptr, nullptr, phi,
+                      iters, resid);
+}
+
+// gaps [R 3 n_joints] of the stored joints (on or off) at every replica's configuration -- an angular joint's rows hold e, or P e --,
+// phi [R 3 n_joints] of the last jointed ensemble solve or step with this set, theta [R n_joints]; any may be NULL
+int rbl_ensemble_joint_state(rbl_ctx *c, double *gap, double *phi, double *theta)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (periodic_on(c)) return periodic_refuse(c, "ensemble_joint_state");
+  if (!c->ens_R) return ens_fail_state(c);
+  if (c->jt_n < 1) return rbl_fail(c, RBL_ERR_STATE, "ensemble_joint_state: no joints have been set (rbl_set_joint_kinds)");
+  if (c->jt_top >= c->ens_Nb) return rbl_fail(c, RBL_ERR_STATE, "ensemble_joint_state: a joint names a body beyond the replica's " + std::to_string(c->ens_Nb));
+  ens_jt_sync(c);
+  if (phi && !c->ens_jt_phi_valid)
+    return rbl_fail(c, RBL_ERR_STATE, "ensemble_joint_state: no jointed ensemble solve or step has succeeded with this joint set");
+  const size_t Rn = (size_t)c->ens_R * c->jt_n;
+  if (gap) {
+    int rc = ens_ready(c); if (rc) return rc;
+    RblEnsJoints T;
+    if ((rc = ens_jt_upload(c, &T))) return rc;
+    if ((rc = rbl_dev_reserve(c, c->d_ens_jtw, sizeof(double) * 9 * Rn))) return rc;
+    double *d_lev = (double *)c->d_ens_jtw.p, *d_gap = d_lev + 6 * Rn;
+    rbl_launch_ens_jt_geom(c->stream, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), c->ens_Nb, c->ens_R, T, d_lev, d_gap);
+    if ((rc = copy_d2h(c, gap, d_gap, sizeof(double) * 3 * Rn))) return rc;
+    RBL_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  if (phi) std::memcpy(phi, c->ens_jt_phi.data(), sizeof(double) * 3 * Rn);
+  if (theta) std::memcpy(theta, c->ens_jt_theta.data(), sizeof(double) * Rn);
+  return RBL_OK;
+}
+
+// does a jointed ensemble of this shape fit the one-kernel solver?  1 or 0; *lds_bytes (may be NULL): what its vectors and joint
+// data take of the solver's 153600 bytes (without the Krylov basis, which goes to global memory when it does not fit beside them).
+// No context: a caller asks before it builds anything
+int rbl_ensemble_joints_fit(int N_blb, int N_bod, int max_iter, int n_joints, int64_t *lds_bytes)
+{
+  if (lds_bytes) *lds_bytes = N_blb > 0 && N_bod > 0 && max_iter > 0 && n_joints >= 0 ? (int64_t)rbl_gmres_small_jt_lds_bytes(N_blb, N_bod, max_iter, n_joints) : 0;
+  return rbl_gmres_small_jt_fits(N_blb, N_bod, max_iter, n_joints) ? 1 : 0;
 }

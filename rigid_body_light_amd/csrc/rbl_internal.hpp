@@ -283,6 +283,15 @@ struct rbl_ctx {
   RblDevBuf d_jtw;                                  // a jointed solve's vectors: rhs | x | (0, J^T phi) | its preconditioned image | lever arms and gaps
   RblDevBuf d_jtphi;                                // phi of the last jointed solve or step (jt_phi_valid), the state query's gaps
   bool jt_phi_valid = false;
+  // the joints of an ensemble (rbl_ensemble.hip; include/rbl.h section 5): the set above, shared by the replicas, with motor angles
+  // and rates of the replica's own
+  int jt_gen = 0;                                   // counts the joint sets stored (rbl_set_joints / rbl_set_joint_kinds)
+  int ens_jt_gen = -1, ens_jt_R = 0, ens_jt_Nb = 0;  // the set, the replica count and N_bod that ens_jt_theta / ens_jt_rate and the device table belong to
+  std::vector<double> ens_jt_theta, ens_jt_rate;    // R n_joints each, replica-major
+  std::vector<double> ens_jt_phi;                   // R 3 n_joints: phi of the last jointed ensemble solve or step (ens_jt_phi_valid)
+  bool ens_jt_valid = false, ens_jt_phi_valid = false;   // d_ens_jt holds the table with the current angles and rates
+  RblDevBuf d_ens_jt;                               // anchors | axes and q_rel | theta | rates | bodies | mates | kinds | row starts by body | ends
+  RblDevBuf d_ens_jtw;                              // a jointed ensemble solve's rhs | x | joint rows given | solver workspace
   // periodic cell in x and y (rbl_periodic.hip; include/rbl.h section 10): explicit image sums of the wall-corrected product,
   // minimum image in the pair forces.  A length of 0: that axis is open (its image count is stored as 0)
   bool per_on = false;
@@ -453,6 +462,28 @@ int rbl_launch_gmres_small_ens_mixed(hipStream_t st, const RblParams &P, bool wa
                                      const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_UFx, int max_iter,
                                      double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err,
                                      const unsigned char *d_mask, const double *d_body_in, int per);
+// the jointed solve of the replicas (rbl_small_joints.hip; include/rbl.h sections 5 and 9).  The joint table on the device, shared
+// by the replicas: anchor 6, ang 7 (axis | q_rel) per joint; theta, rate: n per REPLICA; body 2, mate 2, kind 1 per joint; ptr: the
+// row starts of the joint ends by body (N_bod + 1); ends: (joint, end) per entry, n_ends of them
+struct RblEnsJoints {
+  const double *anchor, *ang, *theta, *rate;
+  const int *body, *mate, *kind, *ptr, *ends;
+  int n, n_ends;
+};
+// rbl_gmres_small_fits' limits with the joint data's LDS: 3 n_joints more in every vector, 16 n_joints + 18 n_joints^2 doubles and
+// (7 n_joints + N_bod + 2) / 2 for the integers.  n_joints = 0: the plain predicate
+bool rbl_gmres_small_jt_fits(int N_blb, int N_bod, int max_iter, int n_joints);
+size_t rbl_gmres_small_jt_lds_bytes(int N_blb, int N_bod, int max_iter, int n_joints);   // without the Krylov basis
+size_t rbl_gmres_small_jt_work_doubles(int N_blb, int N_bod, int max_iter, int n_joints);
+// rhs / x: 3 N + 6 N_bod + 3 n_joints per replica ([slip ; -F ; c], [lambda ; U ; phi]); step != 0: the joint rows of rhs hold
+// joint_velocity and the kernel forms c = coef gap + joint_velocity - rate ah (a lock's rows)
+int rbl_launch_gmres_small_ens_jt(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
+                                  int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter, double rtol,
+                                  double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err, const RblEnsJoints &T, int step,
+                                  double coef);
+// lever arms (reps x 6 n) and gaps (reps x 3 n) of every replica's joints
+void rbl_launch_ens_jt_geom(hipStream_t st, const double *dX, const double *dQ, int N_bod, int reps, const RblEnsJoints &T, double *d_lev,
+                            double *d_gap);
 
 // per-body geometric operators on the device (rbl_body_dev.hip)
 void rbl_launch_body_geom(hipStream_t st, const double *dX, const double *dQ, const double *dcfg,

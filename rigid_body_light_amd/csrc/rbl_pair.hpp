@@ -23,6 +23,7 @@
 #define RBL_FLAG_NOT_SPD 8
 #define RBL_FLAG_INTERNAL 16   // a bounded wait between workgroups ran out (rbl_tilechol.hip): never expected, never a hang
 #define RBL_FLAG_CAPACITY 32   // an interaction neighbour list overflowed its cap (rbl_forces.hip): reported, never truncated silently
+#define RBL_FLAG_REDUNDANT 64  // a pivot of the joints' Schur complement was lost inside the one-kernel jointed solve (rbl_small_solve.hpp): a redundant joint set
 
 struct RblParams {
   double a;        // blob radius

@@ -13,7 +13,8 @@ vectors within 150 KB of LDS, about 75 N_blobs + 60 N_bod doubles: 49 tetrahedra
 """
 import numpy as np
 
-from ._lib import RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError, blob_anchor, bond_args, check_brownian_mask6
+from ._lib import (JOINT_BALL, RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError, blob_anchor, bond_args, check_brownian_mask6,
+                   default_q_rel, hinge, joint_kind_args, motor, weld)
 
 
 def _fail(message):
@@ -334,9 +335,108 @@ class Ensemble:
         return self.ctx.bonds()
 
     def set_joints(self, *args, **kwargs):
-        """hard joints (RigidBody.set_joints) are not offered for ensembles: the one-kernel solver of the replicas has no joint
-        rows.  Hold replicas together with set_bonds"""
-        raise ValueError("set_joints: hard joints are not offered for ensembles (include/rbl.h section 9); bonds are (set_bonds)")
+        """RigidBody.set_joints is not offered for ensembles under that name: an ensemble's hard joints of every kind, ball joints
+        included, are stored by set_joint_kinds (kind=None: all ball joints) and act in solve_jointed / step_jointed"""
+        raise ValueError("set_joints: not offered for ensembles (include/rbl.h section 5): use set_joint_kinds -- kind=None stores ball "
+                         "joints -- with solve_jointed / step_jointed")
+
+    # ------------------------------------------------------------------ hard joints (include/rbl.h sections 5 and 9)
+    def set_joint_kinds(self, body, kind, anchor_a=None, anchor_b=None, axis=None, q_rel=None, on=True):
+        """the joints of RigidBody.set_joint_kinds for every replica: topology, kinds, anchors, axes and q_rel are shared, body
+        indices are local to a replica.  kind=None: all ball joints.  q_rel=None: Q_A^-1 Q_B of replica 0's configuration.
+        They act in solve_jointed / step_jointed only.  body=None with on=False only switches them off"""
+        if body is None:
+            if on:
+                _fail("set_joint_kinds: body is None: that only switches the stored joints off, with on=False")
+            return self.ctx.set_joint_kinds(None, None, on=False)
+        if kind is None:
+            kind = np.zeros(np.asarray(body).reshape(-1, 2).shape[0], dtype=np.int32)
+        b, k, anchor, ax, qr = joint_kind_args("set_joint_kinds", body, kind, anchor_a, anchor_b, axis, q_rel)
+        if b.max() >= self.N_bodies:
+            _fail("set_joint_kinds: body indices are local to a replica and must lie below %d" % self.N_bodies)
+        if q_rel is None and (k != JOINT_BALL).any():
+            default_q_rel("set_joint_kinds", b, k, qr, self.get_config()[1][0])
+        self.ctx.set_joint_kinds(b, k, anchor[:, :3], anchor[:, 3:], axis=ax, q_rel=qr, on=on)
+
+    def joint_kinds(self):
+        """{on, by_kinds, body, anchor_a, anchor_b, kind, axis, q_rel, theta (R, n_joints)} of the stored joints.  The motors' rates
+        are not among them: an ensemble's are per replica and the library does not hand them back (keep what set_joint_rates got)"""
+        d = self.ctx.joint_kinds()
+        d.pop("rate")                                      # (the single context's own rates, which an ensemble does not use)
+        d["theta"] = self.ctx.ensemble_joint_state(phi=False)[2] if d["kind"].shape[0] else np.zeros((self.R, 0))
+        return d
+
+    def _joint_values(self, who, v):
+        n = self.ctx.joints()["body"].shape[0]           # (a host-side query: the stored set is the context's, whoever stored it)
+        v = np.asarray(v, dtype=np.float64)
+        if not n or v.shape not in ((n,), (self.R, n)):
+            _fail("%s: one value per stored joint, shape (%d,) or (%d, %d); got %s" % (who, n, self.R, n, v.shape))
+        return v
+
+    def set_joint_rates(self, rates):
+        """the motors' rates: (n_joints,) shared by the replicas, or (R, n_joints), one set per replica; non-zero on lock joints only"""
+        rates = self._joint_values("set_joint_rates", rates)
+        self.ctx.ensemble_set_joint_rates(rates)
+
+    def set_joint_angles(self, theta):
+        """the motors' angles: (n_joints,) or (R, n_joints): a sweep of stroke phases, or a restart"""
+        theta = self._joint_values("set_joint_angles", theta)
+        self.ctx.ensemble_set_joint_angles(theta)
+
+    def _joint_rows_in(self, who, v, n):
+        """joint_rhs / joint_velocity: (3 n,), (n, 3), or either with a leading R -> (R, 3 n) or (3 n,)"""
+        if v is None:
+            return None
+        v = np.asarray(v, dtype=np.float64)
+        if v.shape in ((3 * n,), (n, 3)):
+            return v.reshape(3 * n)
+        if v.shape in ((self.R, 3 * n), (self.R, n, 3)):
+            return np.ascontiguousarray(v.reshape(self.R, 3 * n))
+        _fail("%s must have shape (%d,), (%d, 3), (%d, %d) or (%d, %d, 3); got %s" % (who, 3 * n, n, self.R, 3 * n, self.R, n, v.shape))
+
+    def _joints_on(self):
+        d = self.ctx.joints()                              # (a host-side query: the stored set is the context's, whoever stored it)
+        return d["body"].shape[0] if d["on"] else 0
+
+    def solve_jointed(self, F, slip=None, joint_rhs=None, max_iter=100, rtol=1e-8):
+        """RigidBody.solve_jointed at every replica's configuration in one solver launch; nothing moves -> (lambda (R, n3),
+        U (R, 6 N_bod), phi (R, 3 n_joints), iterations (R,), residual estimates (R,)).  Joints off or never set: the unjointed
+        solve, phi empty"""
+        F, s = self._forces(F), self._slip(slip)
+        jr = self._joint_rows_in("joint_rhs", joint_rhs, self._joints_on())
+        return self.ctx.ensemble_solve_jointed(F, slip=s, joint_rhs=jr, max_iter=max_iter, rtol=rtol)
+
+    def step_jointed(self, F, slip=None, joint_velocity=None, gamma=1.0, max_iter=50, rtol=1e-8):
+        """one deterministic step of every replica with the joints, J U = -(gamma / dt) gap + joint_velocity - rate ah (a motor's
+        rows), in one solver launch -> (phi (R, 3 n_joints), iterations (R,), residual estimates (R,)).  The first failing replica
+        raises and nothing moves; every motor's angle advances by rate dt when the step commits"""
+        F, s = self._forces(F), self._slip(slip)
+        jv = self._joint_rows_in("joint_velocity", joint_velocity, self._joints_on())
+        return self.ctx.ensemble_step_jointed(F, slip=s, joint_velocity=jv, gamma=gamma, max_iter=max_iter, rtol=rtol)
+
+    def joint_state(self, phi=True):
+        """-> (gap (R, n_joints, 3) at the current configurations, phi (R, n_joints, 3) of the last jointed solve or step,
+        theta (R, n_joints)).  phi=False leaves phi out (None): the query then also serves before any jointed solve"""
+        return self.ctx.ensemble_joint_state(phi=phi)
+
+    def _replica_config(self, replica):
+        X, Q = self.get_config()
+        if not 0 <= int(replica) < self.R:
+            _fail("replica must lie in [0, %d); got %r" % (self.R, replica))
+        return X[int(replica)], Q[int(replica)]
+
+    def hinge(self, a, b, point, axis, replica=0):
+        """rows of a five-row hinge (ball + axis joint) for joint_rows / set_joint_kinds: point and axis in the lab frame, the
+        body-frame anchors, axis and q_rel taken from the named replica's configuration"""
+        return hinge(*self._replica_config(replica), a, b, point, axis)
+
+    def weld(self, a, b, point, replica=0):
+        """rows of a weld (ball + lock joint) at the named replica's configuration"""
+        return weld(*self._replica_config(replica), a, b, point)
+
+    def motor(self, a, b, point, axis, replica=0):
+        """rows of a motor (ball + lock joint, driven by set_joint_rates) at the named replica's configuration"""
+        return motor(*self._replica_config(replica), a, b, point, axis)
 
     def set_periodic(self, *args, **kwargs):
         """a periodic cell (RigidBody.set_periodic) is not offered for ensembles: the one-kernel solver of the replicas has no
