@@ -7,7 +7,11 @@ code.  TEST INFRASTRUCTURE: a pair costs about 40 microseconds per image, so the
     M_per[i,j] = sum_{|p| <= nx} sum_{|q| <= ny} B(d0 + (p Lx, q Ly, 0); z_i, z_j)
 
 with the reference's roles: the block of (lower index, higher index) is evaluated, h = z of the higher index, and the mirror block is
-its transpose.  The (p, q) != 0 terms of i = j are a blob's own images: ordinary pairs of two DIFFERENT blobs at equal height."""
+its transpose.  The (p, q) != 0 terms of i = j are a blob's own images: ordinary pairs of two DIFFERENT blobs at equal height.
+
+The force model's double loops (pair_forces, dipole_pairs) are the definition; pair_forces_v and dipole_pairs_v at the end of the
+module are the same terms broadcast over rows of blobs, for systems the loops are too slow for, and count the pairs inside the
+cutoff by whether their minimum image is the direct displacement or one through a boundary."""
 import numpy as np
 
 
@@ -193,3 +197,141 @@ def dipole_pairs(X, m_lab, c_dd, r_core, r_cut, L):
             FT[i, 3:] += np.cross(mi, h)
             E += 0.5 * c_dd * (mm / s ** 3 - 3.0 * a_ * b_ / s ** 5)
     return FT.reshape(-1), E
+
+
+# ---- the same pair terms broadcast over rows of blobs: what the GPU tests beyond a few dozen blobs compare with.  The double loops
+# above stay the definition; tests/test_periodic_shapes_cpu.py holds each form below against its loop -----------------------------
+def _folds(d, L):
+    """True where the minimum image of the displacements d (..., 3) is NOT the direct displacement (a fold on either axis)"""
+    out = np.zeros(d.shape[:-1], dtype=bool)
+    for k in (0, 1):
+        if L[k] > 0.0:
+            out |= np.rint(d[..., k] / L[k]) != 0.0
+    return out
+
+
+def hermite_v(U, dU, lo, hi, x):
+    """hermite() on an array of lo <= x <= hi"""
+    U, dU = np.asarray(U, dtype=np.float64), np.asarray(dU, dtype=np.float64)
+    n = len(U)
+    h = (hi - lo) / (n - 1)
+    s = (x - lo) / h
+    k = np.minimum(s.astype(np.int64), n - 2)
+    t = s - k
+    D0, D1 = h * dU[k], h * dU[k + 1]
+    c0, c1 = U[k], D0
+    c2 = 3.0 * (U[k + 1] - U[k]) - 2.0 * D0 - D1
+    c3 = 2.0 * (U[k] - U[k + 1]) + D0 + D1
+    return c0 + t * (c1 + t * (c2 + t * c3)), (c1 + t * (2.0 * c2 + 3.0 * c3 * t)) / h
+
+
+def pair_forces_v(r, n_blb, a, L, steric=None, table=None, rows=128):
+    """pair_forces() in blocks of `rows` row blobs against all column blobs -> (f (N, 3), energy, n_direct, n_through): the ordered
+    pairs of blobs of different bodies inside the cutoff of a term that is on, by whether their minimum image is the direct
+    displacement or one through a boundary (n_direct + n_through is what rbl_interaction_stats counts)"""
+    r = np.asarray(r, dtype=np.float64).reshape(-1, 3)
+    N = r.shape[0]
+    body = np.arange(N) // n_blb
+    f = np.zeros((N, 3))
+    E = 0.0
+    count = [0, 0]
+    for i0 in range(0, N, rows):
+        raw = r[i0:i0 + rows, None, :] - r[None, :, :]
+        d = nearest(raw, L)
+        x = np.sqrt((d * d).sum(axis=2))
+        other = body[i0:i0 + rows, None] != body[None, :]
+        g = np.zeros_like(x)                                           # -U'(x) / x
+        inside = np.zeros_like(other)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            if steric is not None:
+                eps, b, rc = steric
+                m = other & (x <= rc)
+                far = x >= 2.0 * a
+                Uf = eps * (2.0 * a / x) * np.exp(-(x - 2.0 * a) / b)
+                slope = eps * (1.0 / (2.0 * a) + 1.0 / b)
+                U = np.where(far, Uf, eps + slope * (2.0 * a - x))
+                g += np.where(m, np.where(far, Uf * (1.0 / x + 1.0 / b) / x, slope / x), 0.0)
+                E += 0.5 * U[m].sum()
+                inside |= m
+            if table is not None:
+                Ut, dUt, lo, hi = table
+                m = other & (x <= hi)
+                T, dT = hermite_v(Ut, dUt, lo, hi, np.clip(x, lo, hi))
+                below = x < lo
+                T = np.where(below, Ut[0] + dUt[0] * (x - lo), T)
+                dT = np.where(below, dUt[0], dT)
+                g -= np.where(m, dT / x, 0.0)
+                E += 0.5 * T[m].sum()
+                inside |= m
+        f[i0:i0 + rows] = (g[:, :, None] * d).sum(axis=1)
+        through = _folds(raw, L)
+        count[0] += int((inside & ~through).sum())
+        count[1] += int((inside & through).sum())
+    return f, E, count[0], count[1]
+
+
+def dipole_pairs_v(X, m_lab, c_dd, r_core, r_cut, L):
+    """dipole_pairs() with every partner of a body at once -> (FT (6 N_bod,), energy, n_direct, n_through), the counts as in
+    pair_forces_v over the ordered pairs of bodies inside r_cut"""
+    X = np.asarray(X, dtype=np.float64).reshape(-1, 3)
+    m_lab = np.asarray(m_lab, dtype=np.float64).reshape(-1, 3)
+    nb = X.shape[0]
+    FT = np.zeros((nb, 6))
+    E = 0.0
+    count = [0, 0]
+    for i in range(nb):
+        raw = X[i] - X
+        r = nearest(raw, L)
+        d = np.sqrt((r * r).sum(axis=1))
+        m = d <= r_cut
+        m[i] = False
+        r, d, mj, raw = r[m], d[m], m_lab[m], raw[m]
+        mi = m_lab[i]
+        core = d < r_core
+        s = np.where(core, r_core, d)
+        a_, b_, mm = r @ mi, (mj * r).sum(axis=1), mj @ mi
+        k5 = 3.0 * c_dd / s ** 5
+        kr = np.where(core, 0.0, mm - 5.0 * a_ * b_ / s ** 2)
+        FT[i, :3] = (k5[:, None] * (a_[:, None] * mj + b_[:, None] * mi + kr[:, None] * r)).sum(axis=0)
+        h = (k5 * b_)[:, None] * r - (c_dd / s ** 3)[:, None] * mj     # the partners' fields at i
+        FT[i, 3:] = np.cross(mi, h).sum(axis=0)
+        E += 0.5 * c_dd * (mm / s ** 3 - 3.0 * a_ * b_ / s ** 5).sum()
+        through = _folds(raw, L)
+        count[0] += int((~through).sum())
+        count[1] += int(through.sum())
+    return FT.reshape(-1), E, count[0], count[1]
+
+
+def one_body_terms(r, X, n_blb, a, wall, builtin=None, height=None, traps=None):
+    """weight, wall repulsion, height table and traps: they do not see the cell, so they are the open-system oracle's
+    (tests/table_oracle.py) with every pair term off.  builtin: dict(w, eps_wall, b_wall) -> (f (N, 3), FT (6 N_bod,), energy)"""
+    import table_oracle as to
+    r = np.asarray(r, dtype=np.float64).reshape(-1, 3)
+    X = np.asarray(X, dtype=np.float64).reshape(-1, 3)
+    bi = None if builtin is None else dict(w=builtin["w"], eps_wall=builtin["eps_wall"], b_wall=builtin["b_wall"], eps_blob=0.0,
+                                           b_blob=1.0, r_cut=-1.0)      # no pair lies inside a negative cutoff
+    # the blob terms as ONE body of all the blobs (no pair loop at all), K^T f about the real centres by KT(); the traps act on
+    # the centres alone: the bodies as single blobs, no other term on
+    f, _, E, npairs = to.interactions(r, np.zeros((1, 3)), r.shape[0], a, wall, builtin=bi, height=height)
+    assert npairs == 0
+    nb = X.shape[0]
+    FT = KT(f.reshape(nb, n_blb, 3), r.reshape(nb, n_blb, 3) - X[:, None, :])
+    if traps is not None:
+        _, FTt, Et, npairs = to.interactions(X, X, 1, a, False, builtin=dict(w=0.0, eps_wall=0.0, b_wall=1.0, eps_blob=0.0, b_blob=1.0, r_cut=-1.0),
+                                             traps=traps)
+        assert npairs == 0
+        FT = FT + FTt
+        E += Et
+    return f, FT, E
+
+
+def force_model(r, X, n_blb, a, L, wall=True, builtin=None, steric=None, table=None, height=None, traps=None):
+    """the whole blob force model in the cell: the minimum-image pair terms and the one-body terms added
+    -> dict(f (N, 3), FT (6 N_bod,), E, direct, through)"""
+    r = np.asarray(r, dtype=np.float64).reshape(-1, 3)
+    X = np.asarray(X, dtype=np.float64).reshape(-1, 3)
+    nb = X.shape[0]
+    fp, Ep, nd, nt = pair_forces_v(r, n_blb, a, L, steric=steric, table=table)
+    f1, FT1, E1 = one_body_terms(r, X, n_blb, a, wall, builtin=builtin, height=height, traps=traps)
+    FT = KT(fp.reshape(nb, n_blb, 3), r.reshape(nb, n_blb, 3) - X[:, None, :]) + FT1
+    return dict(f=fp + f1, FT=FT, E=Ep + E1, direct=nd, through=nt)
