@@ -808,6 +808,32 @@ int rbl_ensemble_joint_state(rbl_ctx *ctx, double *gap, double *phi, double *the
  * one-kernel solver at max_iter, 0 otherwise; *lds_bytes (may be NULL) the bytes its vectors and joint data take of the 153600.
  * n_joints = 0: the rule of the unjointed ensembles. */
 int rbl_ensemble_joints_fit(int N_blb, int N_bod, int max_iter, int n_joints, int64_t *lds_bytes);
+/* In a periodic cell (section 10's cell for ensembles): ONE cell in x and y shared by all replicas, state of its own beside the
+ * single context's -- rbl_set_periodic still refuses a context that holds an ensemble, rbl_get_periodic reports that cell, and the
+ * refusals of section 10 keep their meaning.  With it on, the operator of the one-kernel solver is B M_per B of section 10: its
+ * pair sweep evaluates every unordered pair once per image (the image folded into the sweep's step index, so the
+ * (2 nx + 1)(2 ny + 1)-fold work spreads over the sixteen waves; d0 formed as the single context's kernel forms it) and takes in
+ * every blob's own images; the drift kernel's two products are the same sweep, and the dense matrix of the Brownian root is
+ * summed image by image in the reference's order (k_build_M_per).  The preconditioner stays the image-free diagonal one, so expect
+ * more iterations than in the open system.  Fixed summation order: two calls agree bitwise, and replica r of R with the R = 1 call.
+ * Everything of this section takes the cell -- the deterministic and Brownian steps, the masked solves and steps with their _dof
+ * forms, rbl_ensemble_run with both policies and frames, rbl_ensemble_interaction_forces (the minimum-image kernels, with
+ * section 10's bounds on the cutoffs; replicas still never interact), the resistance matrix through the masked solve -- except the
+ * jointed calls: rbl_ensemble_solve_jointed, rbl_ensemble_step_jointed and rbl_ensemble_joint_state are RBL_ERR_STATE with
+ * "periodic" in the message, before any device work, while the cell is on.  Coordinates stay unwrapped (rbl_ensemble_get_config,
+ * frames, bond states).  The truncated sum's positivity is observed, not proven: a replica whose dense factor fails is
+ * RBL_ERR_NOT_SPD naming it.
+ *   rbl_ensemble_set_periodic  the checks, in this order, and nothing stored unless all pass: the argument checks of
+ *                              rbl_set_periodic (RBL_ERR_ARG: a non-finite or negative length; 0 < L <= 4a once the parameters
+ *                              are set; n outside 1 .. 16 on a periodic axis, n stored as 0 on an open one; both lengths 0 with on
+ *                              set); a communicator (RBL_ERR_ARG); a context that holds no ensemble configuration
+ *                              (RBL_ERR_STATE).  rbl_ensemble_set_config with a new R keeps the cell.  At use: RBL_ERR_STATE when
+ *                              the wall term is off ("periodic cell: the wall term is off") or the parameters have outgrown a
+ *                              length ("no longer exceeds 4a").
+ *   rbl_ensemble_get_periodic  reads it back; any pointer may be NULL.
+ * With the cell off or never set every call of this section launches what it launched before and returns the same bits. */
+int rbl_ensemble_set_periodic(rbl_ctx *ctx, double Lx, double Ly, int nx, int ny, int on);
+int rbl_ensemble_get_periodic(const rbl_ctx *ctx, double *Lx, double *Ly, int *nx, int *ny, int *on);
 int rbl_ensemble_set_config(rbl_ctx *ctx, int R, int N_bod, const double *X, const double *Q);
 int rbl_ensemble_get_config(rbl_ctx *ctx, double *X, double *Q);
 int rbl_ensemble_info(const rbl_ctx *ctx, int *R, int *N_bod);
@@ -1423,7 +1449,7 @@ int rbl_joint_state_kinds(rbl_ctx *ctx, double *gap, double *phi, double *theta)
  * Not offered, each refused with RBL_ERR_STATE and "periodic" in rbl_last_error before any device work while the cell is on: the
  * dense build and the dense Cholesky root (rbl_rotne_prager_tensor[_dev], rbl_M_half_W* with RBL_MHALF_CHOLESKY); the
  * explicit-kernel products rbl_apply_M_sym_dev and rbl_apply_M_sym_multi_dev; rbl_velocity_field[_dev]; every rbl_ensemble_*
- * entry point; attaching a communicator.  And, having no entry point at all: free-space periodicity; an analytic tail correction
+ * entry point (an ensemble's cell is its own: rbl_ensemble_set_periodic, section 5); attaching a communicator.  And, having no entry point at all: free-space periodicity; an analytic tail correction
  * or an Ewald split; the relaxed single-precision products; wrapped coordinates; bonds or joints across the boundary by minimum
  * image; a periodic z. */
 int rbl_set_periodic(rbl_ctx *ctx, double Lx, double Ly, int nx, int ny, int on);

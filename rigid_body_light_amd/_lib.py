@@ -119,6 +119,8 @@ def lib(path=None):
         L.rbl_joint_state_kinds.argtypes = [vp, vp, vp, vp]
         L.rbl_set_periodic.argtypes = [vp, dbl, dbl, C.c_int, C.c_int, C.c_int]
         L.rbl_get_periodic.argtypes = [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.rbl_ensemble_set_periodic.argtypes = L.rbl_set_periodic.argtypes
+        L.rbl_ensemble_get_periodic.argtypes = L.rbl_get_periodic.argtypes
         L.rbl_interaction_forces_dev.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_forces.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
@@ -983,6 +985,19 @@ class DeviceContext:
         """{on, Lx, Ly, images (nx, ny)} (both lengths 0: never set)"""
         Lx, Ly, nx, ny, on = C.c_double(0.0), C.c_double(0.0), C.c_int(0), C.c_int(0), C.c_int(0)
         self._chk(self.L.rbl_get_periodic(self.h, C.byref(Lx), C.byref(Ly), C.byref(nx), C.byref(ny), C.byref(on)))
+        return dict(on=bool(on.value), Lx=Lx.value, Ly=Ly.value, images=(nx.value, ny.value))
+
+    # -- the cell of an ensemble (include/rbl.h section 5): state of its own beside the one above --------------------------------------
+    def ensemble_set_periodic(self, Lx, Ly, images=(1, 1), on=True):
+        """one periodic cell shared by the replicas of the context's ensemble (Lx, Ly, images as set_periodic takes them): the
+        one-kernel solver, the drift and the dense Brownian root sum over the images, the pair forces use the minimum image"""
+        Lx, Ly, nx, ny = periodic_args("ensemble_set_periodic", Lx, Ly, images)
+        self._chk(self.L.rbl_ensemble_set_periodic(self.h, Lx, Ly, nx, ny, int(bool(on))))
+
+    def ensemble_periodic(self):
+        """{on, Lx, Ly, images (nx, ny)} of the ensemble's cell (both lengths 0: never set)"""
+        Lx, Ly, nx, ny, on = C.c_double(0.0), C.c_double(0.0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_ensemble_get_periodic(self.h, C.byref(Lx), C.byref(Ly), C.byref(nx), C.byref(ny), C.byref(on)))
         return dict(on=bool(on.value), Lx=Lx.value, Ly=Ly.value, images=(nx.value, ny.value))
 
     def set_bond_table(self, U, dU, r_min, r_cut, on=True):

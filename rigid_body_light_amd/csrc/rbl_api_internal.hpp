@@ -191,5 +191,8 @@ int flow_record_moments(rbl_ctx *c, const double *d_lambda);
 bool periodic_on(const rbl_ctx *c);           // a cell is set and switched on
 // RBL_ERR_STATE "<who>: not offered with a periodic cell ..." while the cell is on, RBL_OK otherwise; touches no device
 int periodic_refuse(rbl_ctx *c, const char *who);
+// the checks a cell meets at use, shared by the single context's product and the ensembles' steps: RBL_ERR_STATE "periodic cell: the
+// wall term is off ..." / "... no longer exceeds 4a ... (call <setter> again)"; L: the cell's two lengths
+int periodic_use_check(rbl_ctx *c, bool wall, const double *L, const char *setter);
 
 #pragma GCC visibility pop

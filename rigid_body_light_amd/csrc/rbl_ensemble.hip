@@ -45,10 +45,16 @@
 //   k_ens_commit              per replica, a second launch (so `stopped` is final without any wait between workgroups): commit, or
 //                             q^n copied into the new buffer; counters, sums over accepted steps, the frame
 // The host swaps the two configuration buffers after every step without a synchronisation and reads back once at the end.
+//
+// In a periodic cell (rbl_ensemble_set_periodic; the cell's state and checks are in rbl_periodic.hip): the same launches with the
+// cell's instantiations -- k_gmres_small_per (rbl_small_per.hip) and k_ens_rfd_rhs<true, true> (the image sum inside rbl_small_pair_sweep),
+// k_build_M_per for the dense root, the minimum-image force kernels (ia_eval_batch passes the ensemble's cell).  The jointed calls
+// are refused with the cell on.  Cell off: nothing here launches anything else than before.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "rbl_api_internal.hpp"
@@ -213,7 +219,10 @@ __global__ __launch_bounds__(ET) void k_ens_midpoint_masked(int nbod, int Nb, in
 // B M B W_rfd at each, (1/delta) difference) and the right-hand side of the stochastic step (rbl_RHS_and_Midpoint_dev):
 //   top = slip - kBT M_RFD - c2 M^1/2 W1 (+ c2 M^1/2 W2 with split_rand),  bottom = -(F - FT).
 // Also checks the replica's dense factor: a diagonal entry that is not positive and finite is RBL_FLAG_NOT_SPD.
-template <bool WALL>
+// PER (the ensemble's periodic cell, wall only): both products are the cell's -- the pair sweep sums over the images and takes in
+// every blob's own; the cell is one more kernel argument (an empty one otherwise: the two open instantiations keep their code).
+struct EnsNoCell {};
+template <bool WALL, bool PER = false>
 __global__ __launch_bounds__(RBL_SG_THREADS) void k_ens_rfd_rhs(RblParams P, int Nb, int nbl, const double *__restrict__ X,
                                                                 const double *__restrict__ Q, const double *__restrict__ cfg,
                                                                 const double *__restrict__ dq, double delta,
@@ -221,7 +230,8 @@ __global__ __launch_bounds__(RBL_SG_THREADS) void k_ens_rfd_rhs(RblParams P, int
                                                                 const double *__restrict__ Lm, const double *__restrict__ slip,
                                                                 const double *__restrict__ F, const double *__restrict__ FT,
                                                                 double kBT, double c2, int split, double *__restrict__ rhs,
-                                                                unsigned *__restrict__ rerr)
+                                                                unsigned *__restrict__ rerr,
+                                                                std::conditional_t<PER, RblSmallCell, EnsNoCell> C = {})
 {
   extern __shared__ double sm[];
   const int r = blockIdx.x, t = threadIdx.x;
@@ -269,7 +279,8 @@ __global__ __launch_bounds__(RBL_SG_THREADS) void k_ens_rfd_rhs(RblParams P, int
                                        di * vin[3 * t], di * vin[3 * t + 1], di * vin[3 * t + 2], true, ux, uy, uz, flags);
       su[3 * t] = ux; su[3 * t + 1] = uy; su[3 * t + 2] = uz;
     }
-    rbl_small_pair_sweep<WALL>(Pu, pos, dmp, vin, N, part, flags);
+    if constexpr (PER) rbl_small_pair_sweep<WALL, true>(Pu, pos, dmp, vin, N, part, flags, C);
+    else rbl_small_pair_sweep<WALL>(Pu, pos, dmp, vin, N, part, flags);
     for (int e = t; e < n3; e += RBL_SG_THREADS) {
       double s = su[e];
       for (int w = 0; w < EW; ++w) s += part[(size_t)w * n3 + e];
@@ -486,6 +497,17 @@ int ens_flow_check(rbl_ctx *c) { return c->ens_R ? flow_check(c, c->ens_Nb) : RB
 
 int ens_fail_state(rbl_ctx *c) { return rbl_fail(c, RBL_ERR_STATE, "ensemble: no ensemble configuration (rbl_ensemble_set_config)"); }
 
+// the ensemble's periodic cell (rbl_ensemble_set_periodic; include/rbl.h section 5): on, and as the one-workgroup kernels take it
+bool ens_cell_on(const rbl_ctx *c) { return c->ens_per_on; }
+RblSmallCell ens_cell(const rbl_ctx *c) { return rbl_small_cell(c->S.a, c->ens_per_L, c->ens_per_n); }
+
+// what is not offered with the ensemble's cell on: RBL_ERR_STATE before any device work
+int ens_cell_refuse(rbl_ctx *c, const char *who)
+{
+  if (!ens_cell_on(c)) return RBL_OK;
+  return rbl_fail(c, RBL_ERR_STATE, std::string(who) + ": not offered with the ensemble's periodic cell (rbl_ensemble_set_periodic; switch the cell off first)");
+}
+
 double *ens_X(rbl_ctx *c, int which) { return (double *)c->d_ens.p + (size_t)which * 7 * c->ens_R * c->ens_Nb; }
 double *ens_Q(rbl_ctx *c, int which) { return ens_X(c, which) + (size_t)3 * c->ens_R * c->ens_Nb; }
 double *ens_cfg(rbl_ctx *c) { return ens_X(c, 2); }
@@ -592,10 +614,17 @@ int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const doubl
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
   const long n3 = 3L * Nb * nbl, nsys = n3 + 6L * Nb;
   const RblParams P = rbl_make_params(c->S.a, c->S.eta);
-  int rc = mixed ? rbl_launch_gmres_small_ens_mixed(c->stream, P, c->S.wall, Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.U, max_iter, rtol,
-                                                    w.gm, w.iters, w.resid, w.rerr, w.mask, w.F, per)
-                 : rbl_launch_gmres_small_ens(c->stream, P, c->S.wall, Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.x, max_iter, rtol, w.gm,
-                                              w.iters, w.resid, w.rerr);
+  int rc;
+  if (ens_cell_on(c))                                    // the cell on (the wall is: the callers' periodic_use_check): k_gmres_small_per
+    rc = mixed ? rbl_launch_gmres_small_ens_mixed_per(c->stream, P, ens_cell(c), Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.U, max_iter, rtol,
+                                                      w.gm, w.iters, w.resid, w.rerr, w.mask, w.F, per)
+               : rbl_launch_gmres_small_ens_per(c->stream, P, ens_cell(c), Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.x, max_iter, rtol, w.gm,
+                                                w.iters, w.resid, w.rerr);
+  else
+    rc = mixed ? rbl_launch_gmres_small_ens_mixed(c->stream, P, c->S.wall, Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.U, max_iter, rtol,
+                                                  w.gm, w.iters, w.resid, w.rerr, w.mask, w.F, per)
+               : rbl_launch_gmres_small_ens(c->stream, P, c->S.wall, Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.x, max_iter, rtol, w.gm,
+                                            w.iters, w.resid, w.rerr);
   if (rc) return rbl_fail(c, rc, "ensemble step: the one-kernel solver does not fit this device's LDS");
   if (!evolve) return RBL_OK;
   const int nbod = R * Nb;
@@ -664,6 +693,7 @@ int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_i
   const bool mixed = in.prescribed != nullptr;
   const double *FT, *SL;
   int rc;
+  if (ens_cell_on(c) && (rc = periodic_use_check(c, c->S.wall, c->ens_per_L, "rbl_ensemble_set_periodic"))) return rc;
   if (mixed && !in.resident && (rc = ens_upload_mask(c, w, in.prescribed, in.per))) return rc;
   if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, move, in.resident, in.accepted))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb;
@@ -706,8 +736,9 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
                    double rtol)
 {
   const RblBodyState &S = c->S;
-  const bool mixed = in.prescribed != nullptr;
+  const bool mixed = in.prescribed != nullptr, per_cell = ens_cell_on(c);
   int rc;
+  if (per_cell && (rc = periodic_use_check(c, S.wall, c->ens_per_L, "rbl_ensemble_set_periodic"))) return rc;
   if (mixed && !in.resident && (rc = ens_upload_mask(c, w, in.prescribed, in.per))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = S.N_blb, N = Nb * nbl;
   const int64_t n3 = 3 * (int64_t)N;
@@ -718,7 +749,11 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
   const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
   // dense root of every replica: B M B (:667-669), lower Cholesky (:670-671), L W1 and L W2 (:672)
   const RblParams P = rbl_make_params(S.a, S.eta);
-  rbl_launch_build_M_batched(c->stream, P, S.wall, true, w.pos, N, R, w.Lm, n3 * n3, w.rerr, 0, 1);
+  if (per_cell)
+    rbl_launch_build_M_per_batched(c->stream, P, true, w.pos, N, R, w.Lm, n3 * n3, w.rerr, 1, c->ens_per_L[0], c->ens_per_L[1],
+                                   c->ens_per_n[0], c->ens_per_n[1]);
+  else
+    rbl_launch_build_M_batched(c->stream, P, S.wall, true, w.pos, N, R, w.Lm, n3 * n3, w.rerr, 0, 1);
   if ((rc = rbl_launch_cholesky_batched(c->stream, w.Lm, n3, R, n3 * n3, in.chol_err ? w.rerr : w.gerr, w.Linv, in.chol_err)))
     return rbl_fail(c, rc, "ensemble: batched Cholesky launch failed");
   const int split = split_rand ? 1 : 0;
@@ -735,19 +770,23 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
                        (const unsigned char *)w.mask, in.per, (const double *)w.F, (const double *)w.MW, 0.5 * S.dt * c1, 0.5 * S.dt, w.dq,
                        w.Xh, w.Qh);
   const size_t lds = rfd_lds_bytes(Nb, nbl);
-  const void *fn = S.wall ? (const void *)k_ens_rfd_rhs<true> : (const void *)k_ens_rfd_rhs<false>;
+  const void *fn = per_cell ? (const void *)k_ens_rfd_rhs<true, true> : S.wall ? (const void *)k_ens_rfd_rhs<true> : (const void *)k_ens_rfd_rhs<false>;
   if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
     (void)hipGetLastError();
     return rbl_fail(c, RBL_ERR_SIZE, "ensemble: the RFD product does not fit this device's LDS");
   }
-  if (S.wall)
+  if (per_cell)
+    hipLaunchKernelGGL((k_ens_rfd_rhs<true, true>), dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
+                       (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
+                       SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr, ens_cell(c));
+  else if (S.wall)
     hipLaunchKernelGGL(k_ens_rfd_rhs<true>, dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
                        (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
-                       SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
+                       SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr, EnsNoCell{});
   else
     hipLaunchKernelGGL(k_ens_rfd_rhs<false>, dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
                        (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
-                       SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr);
+                       SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr, EnsNoCell{});
   // saddle solve at q^{n+1/2}, update from q^n
   return ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol, mixed, true, !in.resident, in.per);
 }
@@ -1413,6 +1452,7 @@ int rbl_ensemble_solve_jointed(rbl_ctx *c, const double *F_body, const double *s
 {
   if (!c) return RBL_ERR_ARG;
   if (periodic_on(c)) return periodic_refuse(c, "ensemble_solve_jointed");
+  if (ens_cell_on(c)) return ens_cell_refuse(c, "ensemble_solve_jointed");
   int rc = ens_jt_check(c, "ensemble_solve_jointed", F_body, max_iter, rtol); if (rc) return rc;
   if ((rc = ens_ready(c))) return rc;
   if (!ens_jt_active(c)) return ens_jt_plain_solve(c, F_body, slip, max_iter, rtol, lambda, U, iters, resid);
@@ -1424,6 +1464,7 @@ int rbl_ensemble_step_jointed(rbl_ctx *c, const double *F_body, const double *sl
 {
   if (!c) return RBL_ERR_ARG;
   if (periodic_on(c)) return periodic_refuse(c, "ensemble_step_jointed");
+  if (ens_cell_on(c)) return ens_cell_refuse(c, "ensemble_step_jointed");
   if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_jointed: F_body is NULL");
   if (!(gamma >= 0.0 && gamma <= 1.0)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_jointed: gamma must lie in [0, 1]");
   if (ens_jt_active(c) && !(c->S.dt > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_step_jointed: dt must be positive");
@@ -1441,6 +1482,7 @@ int rbl_ensemble_joint_state(rbl_ctx *c, double *gap, double *phi, double *theta
 {
   if (!c) return RBL_ERR_ARG;
   if (periodic_on(c)) return periodic_refuse(c, "ensemble_joint_state");
+  if (ens_cell_on(c)) return ens_cell_refuse(c, "ensemble_joint_state");
   if (!c->ens_R) return ens_fail_state(c);
   if (c->jt_n < 1) return rbl_fail(c, RBL_ERR_STATE, "ensemble_joint_state: no joints have been set (rbl_set_joint_kinds)");
   if (c->jt_top >= c->ens_Nb) return rbl_fail(c, RBL_ERR_STATE, "ensemble_joint_state: a joint names a body beyond the replica's " + std::to_string(c->ens_Nb));

@@ -739,9 +739,9 @@ static IaBonds ia_bond_args(const rbl_ctx *c, int n_win)
 // the model over n_win windows of win bodies each (resident X of the body centres, blob positions and lever arms): neighbour
 // lists inside each window, the pair kernel, K^T f.  d_f (3 N) is required here; d_FT (6 N_bod total) and d_e may be NULL.
 // d_Q: the orientations beside d_X (the dipoles); d_accepted: a run's per-replica step counters, the field's clock (NULL: the
-// field time as set)
+// field time as set).  ens: called for an ensemble -- the cell is the ensemble's (rbl_ensemble_set_periodic), not the single context's
 static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const double *d_pos, const double *d_lever, int win, int n_win,
-                     double *d_cl, double *d_f, double *d_FT, double *d_e, unsigned *d_err, const int *d_accepted = nullptr)
+                     double *d_cl, double *d_f, double *d_FT, double *d_e, unsigned *d_err, const int *d_accepted = nullptr, bool ens = false)
 {
   const RblBodyState &S = c->S;
   if (c->ia_on && !(c->ia_r_cut >= 2.0 * S.a))           // the built-in term's own check: a context with only a table on has r_cut = 0
@@ -763,7 +763,9 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   // The convention is unique only while no pair inside a cutoff has a second image inside it: blobs of two bodies lie within
   // 2 R_body + r_cut of each other's centres, dipoles sit on the centres themselves
   IaCell C = {};
-  if (periodic_on(c)) {
+  const bool per = ens ? c->ens_per_on : periodic_on(c);
+  const double *per_L = ens ? c->ens_per_L : c->per_L;
+  if (per) {
     double R2b = 0.0;
     for (int k = 0; k < S.N_blb; ++k) {
       const double *q = &S.ref_cfg[3 * (size_t)k];
@@ -773,7 +775,7 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
     const double need_pair = (c->ia_on || c->ia_pt.on) ? 2.0 * std::sqrt(R2b) + rc_pair : 0.0;
     const double need_dp = dp_pairs ? c->ia_dp_rcut : 0.0;
     for (int k = 0; k < 2; ++k) {
-      const double Lk = c->per_L[k];
+      const double Lk = per_L[k];
       if (!(Lk > 0.0)) continue;
       const std::string Ln = std::string("L") + (k ? "y" : "x") + " = " + std::to_string(Lk);
       if (need_pair > 0.5 * Lk)
@@ -783,7 +785,7 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
         return rbl_fail(c, RBL_ERR_ARG, "interactions: periodic cell too small: " + Ln + " needs the dipole r_cut = " + std::to_string(need_dp) +
                                             " <= L / 2 = " + std::to_string(0.5 * Lk) + " for a unique minimum image");
     }
-    C.Lx = c->per_L[0]; C.Ly = c->per_L[1];
+    C.Lx = per_L[0]; C.Ly = per_L[1];
     C.px = C.Lx > 0.0 ? 1 : 0; C.py = C.Ly > 0.0 ? 1 : 0;
     C.iLx = C.px ? 1.0 / C.Lx : 0.0; C.iLy = C.py ? 1.0 / C.Ly : 0.0;
   }
@@ -801,7 +803,6 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   // distances: it can only add candidates, whose pairs beyond the cutoffs are then skipped one by one
   const double rc_max = std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0);
   const double cut = (2.0 * std::sqrt(R2) + rc_max) * (1.0 + 1e-12) + 1e-12;
-  const bool per = periodic_on(c);
   if (per)
     hipLaunchKernelGGL(k_body_neighbours_per, dim3(nbod), dim3(64), 0, c->stream, d_X, nbod, win, cut * cut, c->ia_cull ? 1 : 0, cap,
                        C, L.cnt, L.list, d_err);
@@ -893,7 +894,7 @@ int ia_eval_batch(rbl_ctx *c, const double *d_X, const double *d_Q, const double
 {
   IaLayout L = ia_layout(d_work, N_bod * reps, c->S.N_blb, ia_cap(N_bod));
   *d_f = L.f;
-  return ia_launch(c, d_X, d_Q, d_pos, d_lever, N_bod, reps, (double *)d_work, L.f, d_FT, d_e, d_err, d_accepted);
+  return ia_launch(c, d_X, d_Q, d_pos, d_lever, N_bod, reps, (double *)d_work, L.f, d_FT, d_e, d_err, d_accepted, true);
 }
 
 int ia_add_to_step_force(rbl_ctx *c, double *d_force)

@@ -297,6 +297,11 @@ struct rbl_ctx {
   bool per_on = false;
   double per_L[2] = {0.0, 0.0};
   int per_n[2] = {0, 0};
+  // the cell of an ensemble (rbl_ensemble_set_periodic; include/rbl.h section 5): one cell shared by the replicas, state of its own
+  // beside the single context's above -- periodic_on() and every periodic_refuse keep meaning that one
+  bool ens_per_on = false;
+  double ens_per_L[2] = {0.0, 0.0};
+  int ens_per_n[2] = {0, 0};
   // lanczos
   int lanczos_max_iter = 100;
   bool lanczos_out_norm = true;  // preconditioned root: final stopping test in the Euclidean norm of the increment (RBL_OPT_LANCZOS_EUCLID_NORM)
@@ -450,6 +455,21 @@ size_t rbl_gmres_small_work_doubles(int N_blb, int N_bod, int max_iter);
 int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
                            int N_blb, int N_bod, const double *d_rhs, const double *d_x0, double *d_x, int max_iter, double rtol,
                            double fsign, double *d_work, double *d_scal, unsigned *d_err);
+// The periodic cell of an ensemble as the one-workgroup kernels take it, by value as a kernel argument (scalar registers): lengths
+// and reciprocals in units of the blob radius, 0 on an open axis (whose reduction then leaves the displacement alone: no separate
+// instantiation), and the image counts
+struct RblSmallCell {
+  double Lx, Ly, iLx, iLy;
+  int nx, ny;
+};
+inline RblSmallCell rbl_small_cell(double a, const double *L, const int *n)
+{
+  RblSmallCell C;
+  C.Lx = L[0] / a; C.Ly = L[1] / a;
+  C.iLx = L[0] > 0.0 ? 1.0 / C.Lx : 0.0; C.iLy = L[1] > 0.0 ? 1.0 / C.Ly : 0.0;
+  C.nx = L[0] > 0.0 ? n[0] : 0; C.ny = L[1] > 0.0 ? n[1] : 0;
+  return C;
+}
 // the same solve for `reps` replicas of one system shape, one workgroup each (rbl_ensemble.hip): X, Q replica-major (3 N_bod,
 // 4 N_bod per replica), rhs / x nsys per replica, d_work reps x rbl_gmres_small_work_doubles, one iteration count, residual and
 // error word per replica; diagonal preconditioner with the force block's sign restored (fsign = +1), cold start
@@ -462,6 +482,14 @@ int rbl_launch_gmres_small_ens_mixed(hipStream_t st, const RblParams &P, bool wa
                                      const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_UFx, int max_iter,
                                      double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err,
                                      const unsigned char *d_mask, const double *d_body_in, int per);
+// both in a periodic cell (rbl_small_per.hip: k_gmres_small_per; wall only): the operator sums every pair over the cell's images
+int rbl_launch_gmres_small_ens_per(hipStream_t st, const RblParams &P, const RblSmallCell &C, const double *dX, const double *dQ,
+                                   const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter,
+                                   double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err);
+int rbl_launch_gmres_small_ens_mixed_per(hipStream_t st, const RblParams &P, const RblSmallCell &C, const double *dX, const double *dQ,
+                                         const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_UFx,
+                                         int max_iter, double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err,
+                                         const unsigned char *d_mask, const double *d_body_in, int per);
 // the jointed solve of the replicas (rbl_small_joints.hip; include/rbl.h sections 5 and 9).  The joint table on the device, shared
 // by the replicas: anchor 6, ang 7 (axis | q_rel) per joint; theta, rate: n per REPLICA; body 2, mate 2, kind 1 per joint; ptr: the
 // row starts of the joint ends by body (N_bod + 1); ends: (joint, end) per entry, n_ends of them
@@ -531,6 +559,10 @@ void rbl_launch_tl_addq(hipStream_t st, const double *d_Q, int64_t n3, int N_blb
 void rbl_launch_build_M_batched(hipStream_t st, const RblParams &P, bool wall, bool scale_damp, const double *d_r,
                                 int64_t n_blobs, int batch, double *d_M, int64_t strideM, unsigned *d_err, int lower_tiles = 0,
                                 int err_stride = 0);
+// the same matrices in a periodic cell (wall only; k_build_M_per): every block the sum over the cell's images of the reference-order
+// block.  Lx, Ly in physical units (0: that axis is open, its n is 0)
+void rbl_launch_build_M_per_batched(hipStream_t st, const RblParams &P, bool scale_damp, const double *d_r, int64_t n_blobs, int batch,
+                                    double *d_M, int64_t strideM, unsigned *d_err, int err_stride, double Lx, double Ly, int nx, int ny);
 
 // ---- ONE wave-wide sum of doubles, in ONE order --------------------------------------------------------------------------------
 // The bitwise-equal-everywhere claims of the fused reductions (RblNormFold: every wave of every workgroup must get the SAME |w| from

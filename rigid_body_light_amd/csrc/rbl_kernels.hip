@@ -1422,6 +1422,87 @@ __global__ __launch_bounds__(256) void k_build_M(const double *__restrict__ r,
   if (flags) atomicOr(err, flags);
 }
 
+// The same matrix in a periodic cell (include/rbl.h sections 5 and 10; wall only), batched as k_build_M is: every 3x3 block is the
+// sum over the cell's images of the reference-order block, p outer and q inner starting from the first term, with the (lower index,
+// higher index) roles -- d0 = r_lo - r_hi reduced to the nearest image in physical units, the block of (d0 + (p Lx, q Ly), z_lo)
+// against (0, 0, z_hi) -- and the transpose below the diagonal; a blob's own images (p, q) != (0, 0) are pairs of two different
+// blobs, the self block is (0, 0) of equal indices alone.  Then nf and the damping as k_build_M applies them.  An open axis has
+// L = 0 and n = 0: one term, nothing reduced.
+struct PerCellPhys {
+  double Lx, Ly;
+  int nx, ny;
+};
+
+__global__ __launch_bounds__(256) void k_build_M_per(const double *__restrict__ r, double *__restrict__ M, long N, int scale_damp,
+                                                     RblParams P, PerCellPhys C, unsigned *err, long strideR, long strideM,
+                                                     int err_stride)
+{
+  r += (size_t)blockIdx.z * (size_t)strideR;
+  M += (size_t)blockIdx.z * (size_t)strideM;
+  err += (size_t)blockIdx.z * (size_t)err_stride;
+  __shared__ double col[3][768];
+  const int t = threadIdx.x;
+  const long i0 = (long)blockIdx.x * 256;
+  const long i = i0 + t;
+  const bool valid = i < N;
+  const long ic = valid ? i : N - 1;
+  const long n3 = 3 * N;
+  const double xi = r[3 * ic], yi = r[3 * ic + 1], zi = r[3 * ic + 2];
+  const double di = scale_damp ? damp_of(P, zi) : 1.0;
+  const long nrow_blk = ((N - i0) < 256 ? (N - i0) : 256) * 3;
+  unsigned flags = 0;
+  const long jb0 = (long)blockIdx.y * JB;
+  for (int jj = 0; jj < JB; ++jj) {
+    const long j = jb0 + jj;
+    if (j >= N) break;  // block-uniform
+    const double xj = r[3 * j], yj = r[3 * j + 1], zj = r[3 * j + 2];
+    const bool lower = ic <= j;                  // our blob has the lower index: the stored block; otherwise its transpose
+    const double zl = lower ? zi : zj, zh = lower ? zj : zi;
+    double s[9];
+    {
+#pragma clang fp contract(off)
+      double dx = lower ? xi - xj : xj - xi, dy = lower ? yi - yj : yj - yi;
+      if (C.Lx > 0.0) dx = dx - C.Lx * rint(dx / C.Lx);
+      if (C.Ly > 0.0) dy = dy - C.Ly * rint(dy / C.Ly);
+      bool first = true;
+      for (int p = -C.nx; p <= C.nx; ++p)
+        for (int q = -C.ny; q <= C.ny; ++q) {
+          double bt[9];
+          rbl_block_ref(P, true, dx + p * C.Lx, dy + q * C.Ly, zl, 0.0, 0.0, zh, ic == j && p == 0 && q == 0, bt, flags);
+          for (int k = 0; k < 9; ++k) s[k] = first ? bt[k] : s[k] + bt[k];
+          first = false;
+        }
+    }
+    double b[9];
+    if (lower) {
+      for (int k = 0; k < 9; ++k) b[k] = s[k];
+    } else {
+      b[0] = s[0]; b[1] = s[3]; b[2] = s[6];
+      b[3] = s[1]; b[4] = s[4]; b[5] = s[7];
+      b[6] = s[2]; b[7] = s[5]; b[8] = s[8];
+    }
+    const double dj = scale_damp ? damp_of(P, zj) : 1.0;
+    {
+#pragma clang fp contract(off)
+      for (int k = 0; k < 9; ++k) {
+        double v = b[k] * P.nf;
+        if (scale_damp) v = (di * v) * dj;
+        b[k] = v;
+      }
+    }
+    __syncthreads();
+    for (int q = 0; q < 3; ++q)
+      for (int p = 0; p < 3; ++p) col[q][3 * t + p] = b[3 * p + q];
+    __syncthreads();
+    for (int q = 0; q < 3; ++q) {
+      double *dst = M + (size_t)(3 * j + q) * (size_t)n3 + (size_t)(3 * i0);
+      for (int e = t; e < nrow_blk; e += 256) dst[e] = col[q][e];
+    }
+  }
+  if (!valid) flags &= ~RBL_FLAG_OVERLAP;
+  if (flags) atomicOr(err, flags);
+}
+
 // ---------------------------------------------------------------------------
 __global__ void k_blob_positions(const double *__restrict__ X, const double *__restrict__ Q,
                                  const double *__restrict__ cfg, int N_blb, int body_begin,
@@ -2395,6 +2476,16 @@ void rbl_launch_build_M_batched(hipStream_t st, const RblParams &P, bool wall, b
   else
     hipLaunchKernelGGL(k_build_M<false>, grid, block, 0, st, d_r, d_M, (long)n_blobs, scale_damp ? 1 : 0, P, d_err,
                        (long)(3 * n_blobs), (long)strideM, lower_tiles, err_stride);
+}
+
+void rbl_launch_build_M_per_batched(hipStream_t st, const RblParams &P, bool scale_damp, const double *d_r, int64_t n_blobs, int batch,
+                                    double *d_M, int64_t strideM, unsigned *d_err, int err_stride, double Lx, double Ly, int nx, int ny)
+{
+  if (n_blobs <= 0 || batch <= 0) return;
+  dim3 grid((unsigned)((n_blobs + 255) / 256), (unsigned)((n_blobs + JB - 1) / JB), (unsigned)batch), block(256);
+  const PerCellPhys C = {Lx, Ly, Lx > 0.0 ? nx : 0, Ly > 0.0 ? ny : 0};
+  hipLaunchKernelGGL(k_build_M_per, grid, block, 0, st, d_r, d_M, (long)n_blobs, scale_damp ? 1 : 0, P, C, d_err, (long)(3 * n_blobs),
+                     (long)strideM, err_stride);
 }
 
 void rbl_launch_pair_blocks(hipStream_t st, const RblParams &P, bool wall, int mode,

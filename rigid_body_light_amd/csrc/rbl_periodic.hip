@@ -1,7 +1,9 @@
 // rbl_periodic.hip -- the periodic cell in x and y (include/rbl.h section 10): its state and the refusals of what it is not
 // offered with.  The cell itself acts in two places: apply_M_enqueue / apply_M_multi_enqueue (rbl_products.hip) route every
 // mobility product to k_apply_M_per (rbl_kernels.hip), and ia_launch (rbl_forces.hip) selects the minimum-image instantiations
-// of the pair-force kernels.  Nothing here touches a device.
+// of the pair-force kernels.  The cell of an ensemble (rbl_ensemble_set_periodic, section 5) is state of its own beside it: it acts in
+// the one-kernel solver's pair sweep, the drift kernel and the dense build of rbl_ensemble.hip, and ia_launch takes it when it is
+// called for an ensemble.  Nothing here touches a device.
 #include <cmath>
 #include <string>
 
@@ -15,6 +17,39 @@ int periodic_refuse(rbl_ctx *c, const char *who)
   return rbl_fail(c, RBL_ERR_STATE, std::string(who) + ": not offered with a periodic cell (rbl_set_periodic; switch the cell off first)");
 }
 
+// what a product or a step asks of a cell at use (the single context's and the ensembles'): the wall term, and lengths the current
+// parameters have not outgrown.  L: the cell's two lengths; setter: the call that stores them, named in the message
+int periodic_use_check(rbl_ctx *c, bool wall, const double *L, const char *setter)
+{
+  if (!wall) return rbl_fail(c, RBL_ERR_STATE, "periodic cell: the wall term is off, and the free-space lattice sum diverges (rbl_set_wall_pc)");
+  for (int k = 0; k < 2; ++k)
+    if (L[k] > 0.0 && !(L[k] > 4.0 * c->S.a))
+      return rbl_fail(c, RBL_ERR_STATE, std::string("periodic cell: L") + (k ? "y" : "x") + " = " + std::to_string(L[k]) +
+                                            " no longer exceeds 4a of the current parameters (call " + setter + " again)");
+  return RBL_OK;
+}
+
+// the argument checks of rbl_set_periodic and rbl_ensemble_set_periodic (who: the name in the messages); n of an open axis -> 0
+static int cell_args(rbl_ctx *c, const std::string &who, const double *L, int *n, int on)
+{
+  const char *axis[2] = {"x", "y"};
+  for (int k = 0; k < 2; ++k) {
+    const std::string Ln = std::string("L") + axis[k], nn = std::string("n") + axis[k];
+    if (!std::isfinite(L[k]) || L[k] < 0.0)
+      return rbl_fail(c, RBL_ERR_ARG, who + ": " + Ln + " = " + std::to_string(L[k]) + " must be finite and >= 0 (0: that axis is open)");
+    if (L[k] > 0.0 && c->S.params_set && !(L[k] > 4.0 * c->S.a))
+      return rbl_fail(c, RBL_ERR_ARG, who + ": " + Ln + " = " + std::to_string(L[k]) + " must exceed 4a = " + std::to_string(4.0 * c->S.a) +
+                                          " (a blob must not overlap its own image)");
+    if (L[k] > 0.0 && (n[k] < 1 || n[k] > 16))
+      return rbl_fail(c, RBL_ERR_ARG, who + ": " + nn + " = " + std::to_string(n[k]) + " must lie in [1, 16] on a periodic axis (the nearest image "
+                                          "alone is not positive definite)");
+    if (L[k] == 0.0) n[k] = 0;
+  }
+  if (on && L[0] == 0.0 && L[1] == 0.0)
+    return rbl_fail(c, RBL_ERR_ARG, who + ": Lx = 0 and Ly = 0 with on set: a cell that is switched on needs a periodic axis");
+  return RBL_OK;
+}
+
 // ---- the C ABI (include/rbl.h section 10) ------------------------------------------------------------------------------------------
 
 // the cell: checks first, nothing is stored unless every one passes
@@ -23,21 +58,7 @@ int rbl_set_periodic(rbl_ctx *c, double Lx, double Ly, int nx, int ny, int on)
   if (!c) return RBL_ERR_ARG;
   const double L[2] = {Lx, Ly};
   int n[2] = {nx, ny};
-  const char *axis[2] = {"x", "y"};
-  for (int k = 0; k < 2; ++k) {
-    const std::string Ln = std::string("L") + axis[k], nn = std::string("n") + axis[k];
-    if (!std::isfinite(L[k]) || L[k] < 0.0)
-      return rbl_fail(c, RBL_ERR_ARG, "set_periodic: " + Ln + " = " + std::to_string(L[k]) + " must be finite and >= 0 (0: that axis is open)");
-    if (L[k] > 0.0 && c->S.params_set && !(L[k] > 4.0 * c->S.a))
-      return rbl_fail(c, RBL_ERR_ARG, "set_periodic: " + Ln + " = " + std::to_string(L[k]) + " must exceed 4a = " + std::to_string(4.0 * c->S.a) +
-                                          " (a blob must not overlap its own image)");
-    if (L[k] > 0.0 && (n[k] < 1 || n[k] > 16))
-      return rbl_fail(c, RBL_ERR_ARG, "set_periodic: " + nn + " = " + std::to_string(n[k]) + " must lie in [1, 16] on a periodic axis (the nearest image "
-                                          "alone is not positive definite)");
-    if (L[k] == 0.0) n[k] = 0;
-  }
-  if (on && L[0] == 0.0 && L[1] == 0.0)
-    return rbl_fail(c, RBL_ERR_ARG, "set_periodic: Lx = 0 and Ly = 0 with on set: a cell that is switched on needs a periodic axis");
+  int rc = cell_args(c, "set_periodic", L, n, on); if (rc) return rc;
   if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, "set_periodic: not on a context with a communicator");
   if (c->ens_R) return rbl_fail(c, RBL_ERR_STATE, "set_periodic: not offered for ensembles (the context holds an ensemble configuration)");
   c->per_L[0] = L[0]; c->per_L[1] = L[1];
@@ -55,5 +76,35 @@ int rbl_get_periodic(const rbl_ctx *c, double *Lx, double *Ly, int *nx, int *ny,
   if (nx) *nx = c->per_n[0];
   if (ny) *ny = c->per_n[1];
   if (on) *on = c->per_on ? 1 : 0;
+  return RBL_OK;
+}
+
+// ---- the cell of an ensemble (include/rbl.h section 5): state of its own, one cell shared by the replicas -----------------------------
+// The argument checks stand first (they need no device and no ensemble), then the communicator, then the ensemble
+
+int rbl_ensemble_set_periodic(rbl_ctx *c, double Lx, double Ly, int nx, int ny, int on)
+{
+  if (!c) return RBL_ERR_ARG;
+  const double L[2] = {Lx, Ly};
+  int n[2] = {nx, ny};
+  int rc = cell_args(c, "ensemble_set_periodic", L, n, on); if (rc) return rc;
+  if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_set_periodic: not on a context with a communicator");
+  if (!c->ens_R)
+    return rbl_fail(c, RBL_ERR_STATE, "ensemble_set_periodic: the context holds no ensemble configuration (rbl_ensemble_set_config; a single "
+                                      "context's cell is rbl_set_periodic)");
+  c->ens_per_L[0] = L[0]; c->ens_per_L[1] = L[1];
+  c->ens_per_n[0] = n[0]; c->ens_per_n[1] = n[1];
+  c->ens_per_on = on != 0;
+  return RBL_OK;
+}
+
+int rbl_ensemble_get_periodic(const rbl_ctx *c, double *Lx, double *Ly, int *nx, int *ny, int *on)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (Lx) *Lx = c->ens_per_L[0];
+  if (Ly) *Ly = c->ens_per_L[1];
+  if (nx) *nx = c->ens_per_n[0];
+  if (ny) *ny = c->ens_per_n[1];
+  if (on) *on = c->ens_per_on ? 1 : 0;
   return RBL_OK;
 }

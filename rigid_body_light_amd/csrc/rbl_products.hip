@@ -30,12 +30,8 @@ static RblSymTune launch_tune(const rbl_ctx *c, const RblProductReq &rq)
 static int apply_M_per_enqueue(rbl_ctx *c, bool wall, const double *d_F, const double *d_r, int64_t nbl, int64_t row_begin,
                                int64_t row_end, double *d_out, const RblProductReq &rq)
 {
-  if (!wall) return rbl_fail(c, RBL_ERR_STATE, "periodic cell: the wall term is off, and the free-space lattice sum diverges (rbl_set_wall_pc)");
-  for (int k = 0; k < 2; ++k)
-    if (c->per_L[k] > 0.0 && !(c->per_L[k] > 4.0 * c->S.a))
-      return rbl_fail(c, RBL_ERR_STATE, std::string("periodic cell: L") + (k ? "y" : "x") + " = " + std::to_string(c->per_L[k]) +
-                                            " no longer exceeds 4a of the current parameters (call rbl_set_periodic again)");
   int js = 1, rc;
+  if ((rc = periodic_use_check(c, wall, c->per_L, "rbl_set_periodic"))) return rc;
   const size_t pb = rbl_apply_M_part_bytes(nbl, row_end - row_begin, c->n_cu, c->tune_jsplit, &js);
   if ((rc = rbl_dev_reserve(c, c->d_part, pb))) return rc;
   RblPhase ph(c, RBL_T_PRODUCT);

@@ -31,16 +31,72 @@ __device__ __forceinline__ void rbl_quat_rot9(const double *q, double *R)
 // steps are dealt round-robin to the wavefronts, each adding into its OWN accumulator set part[wave][3N] (fixed order inside
 // a wave).  The caller adds the sets in wave order.  pos: positions / a (3N), dmp: wall damping per blob (WALL only), in: 3N.
 // Every thread of the workgroup calls it (it contains barriers); part holds NW x 3N doubles and is zeroed here.
-template <bool WALL>
+//
+// PER (a periodic cell, include/rbl.h sections 5 and 10; wall only): every unordered pair once per image,
+//     U_i += sum_{|p| <= nx} sum_{|q| <= ny} B(d0 + (p Lx, q Ly, 0); z_i, z_j) F_j      and the transpose into U_j,
+// d0 the nearest-image displacement formed as sweep_tile_per forms it (rbl_kernels.hip): M_ji = M_ij^T holds image by image
+// because the image set is symmetric and rint is odd.  The image is folded into the step index: a wave's step is (offset s, row
+// block, image k = (p + nx)(2 ny + 1) + (q + ny)), dealt round-robin as before, so the (2 nx + 1)(2 ny + 1)-fold sweep spreads
+// evenly over the waves and nothing but the step's three scalars is live across the pair call; the reduction is redone per step.
+// A blob's own images (p, q) != (0, 0) are ordinary pairs of two different blobs at one height: the steps behind the pairs',
+// offset 0, take the half set k > k(0, 0) -- (p, q) and (-p, -q) are each other's transpose, so ui + uj of one evaluation is both.
+// The step index comes through readfirstlane: the decoding below is scalar arithmetic.  C arrives as a kernel argument (SGPRs).
+template <bool WALL, bool PER = false>
 __device__ __forceinline__ void rbl_small_pair_sweep(const RblParams &Pu, const double *pos, const double *dmp, const double *in,
-                                                     int N, double *part, unsigned &flags)
+                                                     int N, double *part, unsigned &flags, const RblSmallCell &C = RblSmallCell{})
 {
+  static_assert(WALL || !PER, "the free-space lattice sum diverges: a cell needs the wall");
   constexpr int NW = RBL_SG_THREADS / 64;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, n3 = 3 * N;
   for (int idx = t; idx < NW * n3; idx += RBL_SG_THREADS) part[idx] = 0.0;
   __syncthreads();
   const int RB = (N + 63) / 64, nsteps = (N / 2) * RB;
   double *acc = part + (size_t)wave * n3;
+  if constexpr (PER) {
+    const int W = 2 * C.ny + 1, kc = C.nx * W + C.ny, NI = 2 * kc + 1;
+    const int npair = nsteps * NI, nall = npair + RB * kc;
+    for (int q = __builtin_amdgcn_readfirstlane(wave); q < nall; q += NW) {
+      int s_, rb, k;
+      if (q < npair) {                                 // a pair's image: image innermost, then the row block, then the offset
+        const int u = q / NI;
+        k = q - u * NI;
+        s_ = u / RB + 1;
+        rb = u - (s_ - 1) * RB;
+      } else {                                         // a blob's own image, k(0, 0) < k < NI
+        const int u = q - npair, kk = u / RB;
+        k = kc + 1 + kk;
+        rb = u - kk * RB;
+        s_ = 0;
+      }
+      const int kp = k / W;
+      const double pd = (double)(kp - C.nx), qd = (double)(k - kp * W - C.ny);
+      const int i = rb * 64 + lane;
+      if (i < N && (2 * s_ != N || 2 * i < N)) {
+        int j = i + s_;
+        if (j >= N) j -= N;
+        const double di = dmp[i], dj = dmp[j];
+        const RblV3 Fi[1] = {{di * in[3 * i], di * in[3 * i + 1], di * in[3 * i + 2]}}, Fj[1] = {{dj * in[3 * j], dj * in[3 * j + 1], dj * in[3 * j + 2]}};
+        RblV3 ui[1] = {{0.0, 0.0, 0.0}}, uj[1] = {{0.0, 0.0, 0.0}};
+        double dx = pos[3 * i] - pos[3 * j], dy = pos[3 * i + 1] - pos[3 * j + 1];
+        dx = __builtin_fma(-C.Lx, rint(dx * C.iLx), dx);   // 1 / L is 0 on an open axis: rint(0) = 0 leaves d alone
+        dy = __builtin_fma(-C.Ly, rint(dy * C.iLy), dy);
+        rbl_pair_symv<true, true, true>(Pu, __builtin_fma(pd, C.Lx, dx), __builtin_fma(qd, C.Ly, dy), pos[3 * i + 2], Fi, 0.0, 0.0, pos[3 * j + 2], Fj, ui, uj, flags);
+        if (s_ == 0) {                                 // wave-uniform: j = i, image and mirror image in one
+          ui[0].x += uj[0].x; ui[0].y += uj[0].y; ui[0].z += uj[0].z;
+        }
+        __hip_atomic_fetch_add(&acc[3 * i], ui[0].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&acc[3 * i + 1], ui[0].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&acc[3 * i + 2], ui[0].z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (s_ != 0) {
+          __hip_atomic_fetch_add(&acc[3 * j], uj[0].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_fetch_add(&acc[3 * j + 1], uj[0].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_fetch_add(&acc[3 * j + 2], uj[0].z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      }
+    }
+    __syncthreads();
+    return;
+  }
   for (int q = wave; q < nsteps; q += NW) {
     const int s_ = q / RB + 1, i = (q - (s_ - 1) * RB) * 64 + lane;
     if (i < N && (2 * s_ != N || 2 * i < N)) {

@@ -43,6 +43,9 @@ struct SmallArgsMixed : SmallArgs {
   int reps;                        // the grid
   int per;                         // mask entries per body: 1 or 6 (read in the prologue only: the flags in LDS serve afterwards)
 };
+// PER: the cell, behind everything the open system's kernels take
+struct SmallArgsPer : SmallArgs { RblSmallCell C; };
+struct SmallArgsMixedPer : SmallArgsMixed { RblSmallCell C; };
 // The jointed variant (JOINTS): rhs and x hold 3 n_joints more per replica, [slip ; -F ; c] and [lambda ; U ; phi].  The joint
 // table is shared by the replicas; J.ptr holds the row starts of the joint ends BY BODY (N_bod + 1 entries: a body without a
 // joint has an empty row; J.rows is unused), J.theta and J.rate hold n_joints values per replica, replica r's r n_joints further.
@@ -121,9 +124,14 @@ __device__ __forceinline__ double wave_sum(double v)
   return ((lane_value(v, 0) + lane_value(v, 16)) + lane_value(v, 32)) + lane_value(v, 48);
 }
 
-template <bool WALL, bool VLDS, bool MIXED, bool JOINTS, class Args>
+// PER (the ensembles in a periodic cell, include/rbl.h sections 5 and 10): the operator's pair sweep sums every pair over the cell's
+// images and takes in every blob's own images (rbl_small_pair_sweep<WALL, true>); the cell is A.C of SmallArgsPer / SmallArgsMixedPer,
+// a kernel argument.  The self block, the preconditioner (image-free, diagonal) and everything else are the open system's: with
+// PER = false the function is unchanged.
+template <bool WALL, bool VLDS, bool MIXED, bool JOINTS, bool PER = false, class Args>
 __device__ __forceinline__ void rbl_small_solve(Args A)
 {
+  static_assert(!(PER && JOINTS), "the jointed solve has no image sum");
   extern __shared__ double sm[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   constexpr int NW = SGT / 64;
@@ -469,7 +477,8 @@ __device__ __forceinline__ void rbl_small_solve(Args A)
       kt[t] = v0; kt[N + t] = v1; kt[2 * N + t] = v2;
       kt[3 * N + t] = l1 * v2 - l2 * v1; kt[4 * N + t] = l2 * v0 - l0 * v2; kt[5 * N + t] = l0 * v1 - l1 * v0;
     }
-    rbl_small_pair_sweep<WALL>(Pu, pos, dmp, in, N, part, flags);   // one accumulator set per wave in part (rbl_small_dev.hpp)
+    if constexpr (PER) rbl_small_pair_sweep<WALL, true>(Pu, pos, dmp, in, N, part, flags, A.C);
+    else rbl_small_pair_sweep<WALL>(Pu, pos, dmp, in, N, part, flags);   // one accumulator set per wave in part (rbl_small_dev.hpp)
     if (t < n3) {                            // U_i = nf d_i (self + sum over the waves' sets) - (K U)_i
       double s = su[t];
       for (int w = 0; w < NW; ++w) s += part[(size_t)w * n3 + t];

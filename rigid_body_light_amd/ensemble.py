@@ -14,7 +14,7 @@ vectors within 150 KB of LDS, about 75 N_blobs + 60 N_bod doubles: 49 tetrahedra
 import numpy as np
 
 from ._lib import (JOINT_BALL, RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError, blob_anchor, bond_args, check_brownian_mask6,
-                   default_q_rel, hinge, joint_kind_args, motor, weld)
+                   default_q_rel, hinge, joint_kind_args, motor, periodic_args, weld)
 
 
 def _fail(message):
@@ -439,9 +439,24 @@ class Ensemble:
         return motor(*self._replica_config(replica), a, b, point, axis)
 
     def set_periodic(self, *args, **kwargs):
-        """a periodic cell (RigidBody.set_periodic) is not offered for ensembles: the one-kernel solver of the replicas has no
-        image sum"""
-        raise ValueError("set_periodic: a periodic cell is not offered for ensembles (include/rbl.h section 10)")
+        """the single context's cell (RigidBody.set_periodic) is not offered for ensembles under that name: an ensemble's cell is
+        state of its own, stored by set_cell"""
+        raise ValueError("set_periodic: a periodic cell is not offered for ensembles under this name (include/rbl.h section 10): "
+                         "use set_cell (rbl_ensemble_set_periodic, section 5)")
+
+    # ------------------------------------------------------------------ periodic cell in x and y (include/rbl.h sections 5 and 10)
+    def set_cell(self, Lx, Ly, images=(1, 1), on=True):
+        """One periodic cell of lengths Lx, Ly (0: that axis stays open) shared by all replicas: the one-kernel solver's operator,
+        the drift and the dense Brownian root sum every pair over images = (nx, ny) periodic images on either side of its nearest
+        one (1 <= n <= 16 on a periodic axis), a blob's own images included, and the pair forces use the minimum image.  Needs
+        the wall; L must exceed 4a.  Coordinates stay unwrapped.  Every step, solve and run takes the cell; solve_jointed,
+        step_jointed and joint_state are refused (RblError, "periodic") while it is on.  on=False stores it switched off."""
+        Lx, Ly, nx, ny = periodic_args("set_cell", Lx, Ly, images)
+        self.ctx.ensemble_set_periodic(Lx, Ly, images=(nx, ny), on=bool(on))
+
+    def cell(self):
+        """-> {Lx, Ly, images, on} of the ensemble's cell"""
+        return self.ctx.ensemble_periodic()
 
     def set_bond_table(self, U, dU, r_min, r_cut, on=True):
         """the potential of the kind-1 bonds of RigidBody.set_bond_table, one for all replicas"""
