@@ -795,8 +795,9 @@ int rbl_interaction_stats(rbl_ctx *ctx, int64_t *body_pairs, int64_t *blob_pairs
  * A redundant loop of joints in some replica is RBL_ERR_NOT_SPD with "redundant" and the first failing replica in the message;
  * nothing moved, no motor's angle advanced, and the context serves a valid set afterwards.  (The lost pivot of S has an error
  * bit of its own: a body's 6 x 6 preconditioner block that fails its Cholesky is RBL_ERR_NOT_SPD with the unjointed solver's message.)
- * Not offered with joints: prescribed masks, Brownian steps, rbl_ensemble_run (per-replica angles and rates are kept so that a
- * run can advance them on the device), lock-step right-hand sides.  Every other entry point of this section ignores the joints. */
+ * Not offered with joints: prescribed masks, Brownian steps, lock-step right-hand sides.  Many steps in one call are
+ * rbl_ensemble_run_jointed (below, after rbl_ensemble_run), which advances the per-replica angles and a motor schedule on the
+ * device.  Every other entry point of this section ignores the joints. */
 int rbl_ensemble_set_joint_rates(rbl_ctx *ctx, const double *rate, int sets);
 int rbl_ensemble_set_joint_angles(rbl_ctx *ctx, const double *theta, int sets);
 int rbl_ensemble_solve_jointed(rbl_ctx *ctx, const double *F_body, const double *slip, const double *joint_rhs, int max_iter, double rtol,
@@ -819,7 +820,7 @@ int rbl_ensemble_joints_fit(int N_blb, int N_bod, int max_iter, int n_joints, in
  * Everything of this section takes the cell -- the deterministic and Brownian steps, the masked solves and steps with their _dof
  * forms, rbl_ensemble_run with both policies and frames, rbl_ensemble_interaction_forces (the minimum-image kernels, with
  * section 10's bounds on the cutoffs; replicas still never interact), the resistance matrix through the masked solve -- except the
- * jointed calls: rbl_ensemble_solve_jointed, rbl_ensemble_step_jointed and rbl_ensemble_joint_state are RBL_ERR_STATE with
+ * jointed calls: rbl_ensemble_solve_jointed, rbl_ensemble_step_jointed, rbl_ensemble_run_jointed and rbl_ensemble_joint_state are RBL_ERR_STATE with
  * "periodic" in the message, before any device work, while the cell is on.  Coordinates stay unwrapped (rbl_ensemble_get_config,
  * frames, bond states).  The truncated sum's positivity is observed, not proven: a replica whose dense factor fails is
  * RBL_ERR_NOT_SPD naming it.
@@ -950,6 +951,75 @@ typedef struct rbl_run_out {
   int32_t steps_done, stopped_at, stop_replica, reserved;   /* written by the call */
 } rbl_run_out;
 int rbl_ensemble_run(rbl_ctx *ctx, const rbl_run_opts *opts, rbl_run_out *out);
+
+/* A run with hard joints: n_steps steps of rbl_ensemble_step_jointed in ONE call.  Each step enqueues that call's launch sequence
+ * (force and flow models at q^n, the right-hand side, one k_gmres_small_jt, the moments kernel while RBL_OPT_RECORD_MOMENTS is
+ * on, the update), then the run's verdict and commit and ONE small launch for the joints (k_ens_jt_run, one thread per replica
+ * and joint), which for the replicas that commit advances theta -- d = rate dt, theta += d, product and sum rounded one after
+ * the other, only where rate != 0: the one-step call's bits --, advances the replica's position in the motor schedule, adds the
+ * step's phi to phi_sum, and for every replica writes the rates of its next step into the joint table the solver reads.  The
+ * joint table, F_body, slip, joint_velocity and the schedule go up once; the host synchronises at the check_every polls and at the
+ * one read-back that ends the run.  A run that records frames launches k_ens_jt_geom once more on the recording steps.
+ *
+ * opts: n_steps, max_iter, rtol, stride, on_error, check_every, F_body and slip are read as rbl_ensemble_run reads them; both
+ * error policies are that call's (RBL_RUN_STOP: the failing step commits nothing and turns no motor, nor does any later one;
+ * RBL_RUN_REJECT: a failing replica keeps q^n, theta and its position in the cycle and tries again, and the new configuration is
+ * validated before it commits).  prescribed, body_in and prescribed_per outside {0, 1} are RBL_ERR_ARG (joints with masks are
+ * not offered); brownian != 0 while kBT > 1e-10 is RBL_ERR_ARG (the drift of a constrained suspension has not been derived;
+ * brownian is ignored at kBT <= 1e-10); seed, split_rand and delta are not read.
+ *
+ * jopts: gamma and joint_velocity[R 3 n_joints] (or NULL) as in rbl_ensemble_step_jointed, constant over the run, and the motor
+ * schedule, the one input that moves: a cycle of n_phases >= 0 phases, phase k lasting phase_steps[k] >= 1 steps with the rates
+ * phase_rates[k][s][j] (s < rate_sets, 1: every replica alike, or R; finite, non-zero on RBL_JOINT_LOCK joints only:
+ * rbl_ensemble_set_joint_rates' rule, the message naming phase, set and joint).  A replica at cycle position p steps with the
+ * rates of the phase whose half-open range [cum_k, cum_k+1) of the prefix sums of phase_steps holds p; p advances by one, modulo
+ * the cycle's length (which must fit 31 bits), when the replica commits -- a rejected replica's schedule waits for it, like its
+ * field clock.  cycle_start[start_sets], start_sets 0 (every replica at 0), 1 or R: the positions at the run's first step,
+ * 0 <= value < the cycle's length.  n_phases = 0: the rates rbl_ensemble_set_joint_rates stored, constant.  The schedule is an
+ * argument, never state: after the run the stored rates are what rbl_ensemble_set_joint_rates last gave.
+ *
+ * jout (any pointer may be NULL): theta[R n_joints], the angles the run leaves (rbl_ensemble_joint_state returns the same);
+ * cycle_pos[R], the positions at the run's end, so that a next run continues the stroke; phi_sum[R 3 n_joints], the sum over the
+ * replica's ACCEPTED steps of the phi the one-step call returns, added in step order by one thread per entry: its mean over a
+ * motor's lock rows is the motor's torque.  With stride > 0 the frames frame_theta[n_frames R n_joints], frame_phi and
+ * frame_gap[n_frames R 3 n_joints]: phi is that step's, or the replica's last accepted one where it was rejected in that step
+ * (zeros before any); the gap is k_ens_jt_geom's at the committed configuration and angles, the bits of rbl_ensemble_joint_state.
+ * After a run that did not stop rbl_ensemble_joint_state returns every replica's last accepted phi; after a stopped run phi is
+ * invalid, as after a failed step.  rbl_ensemble_step_moments is RBL_ERR_STATE after the run.
+ *
+ * Joints switched off or never set: the call is rbl_ensemble_run with brownian = 0, bit for bit; the schedule must then be empty
+ * (RBL_ERR_STATE otherwise), cycle_pos is zeros and the other arrays of jout are left alone.
+ * Refused before any device work: NULL structs or wrong sizes, the refusals above, those of rbl_ensemble_run for the fields that
+ * are read, those of rbl_ensemble_step_jointed (gamma, dt, max_iter outside 1 .. 255, a joint naming a body >= N_bod, the size
+ * refusals with the LDS message), n_phases < 0, rate_sets outside {1, R} or start_sets outside {0, 1, R}, NULL schedule arrays
+ * while n_phases > 0, a phase_steps entry < 1, a cycle_start outside the cycle (RBL_ERR_ARG), a periodic cell that is on
+ * (RBL_ERR_STATE, "periodic"), a communicator. */
+typedef struct rbl_run_joint_opts {
+  int64_t size;                 /* sizeof(rbl_run_joint_opts) */
+  double gamma;                 /* in [0, 1] */
+  const double *joint_velocity; /* [R 3 n_joints] or NULL */
+  int32_t n_phases;             /* >= 0; 0: the stored rates, constant */
+  int32_t rate_sets;            /* 1 or R (read while n_phases > 0) */
+  int32_t start_sets;           /* 0, 1 or R */
+  int32_t reserved;
+  const int32_t *phase_steps;   /* [n_phases], each >= 1 */
+  const double *phase_rates;    /* [n_phases rate_sets n_joints] */
+  const int32_t *cycle_start;   /* [start_sets] */
+} rbl_run_joint_opts;
+typedef struct rbl_run_joint_out {
+  int64_t size;                 /* sizeof(rbl_run_joint_out) */
+  double *theta;                /* [R n_joints] */
+  int32_t *cycle_pos;           /* [R] */
+  double *phi_sum;              /* [R 3 n_joints] */
+  double *frame_theta;          /* [n_frames R n_joints] */
+  double *frame_phi, *frame_gap; /* [n_frames R 3 n_joints] */
+} rbl_run_joint_out;
+int rbl_ensemble_run_jointed(rbl_ctx *ctx, const rbl_run_opts *opts, const rbl_run_joint_opts *jopts, rbl_run_out *out,
+                             rbl_run_joint_out *jout);
+/* The schedule's map from a cycle position to its phase, as the run's kernel evaluates it (one __host__ __device__ function):
+ * the k with cum_k <= pos < cum_k+1, or -1 for n_phases < 1, a NULL array, a phase_steps entry < 1 or pos outside the cycle.
+ * No context. */
+int rbl_run_schedule_phase(const int32_t *phase_steps, int n_phases, int64_t pos);
 
 /* ===================================================================== */
 /* 6. Fluid velocity at arbitrary points (rigid_body_light_amd/csrc/rbl_field.hip) */
@@ -1333,8 +1403,8 @@ int rbl_ensemble_step_moments(rbl_ctx *ctx, double *D);
  *
  * Not offered, each refused before any device work: contexts with a communicator (RBL_ERR_ARG); the calls of THIS section on a
  * context that holds an ensemble (RBL_ERR_STATE) -- an ensemble's jointed solve and step are section 5's
- * rbl_ensemble_solve_jointed / rbl_ensemble_step_jointed, which read the joint set stored here; the other ensemble entry points
- * ignore the joints like every other, and rbl_ensemble_run has no jointed form --; and, having no entry point at
+ * rbl_ensemble_solve_jointed / rbl_ensemble_step_jointed / rbl_ensemble_run_jointed, which read the joint set stored here; the
+ * other ensemble entry points, rbl_ensemble_run among them, ignore the joints like every other --; and, having no entry point at
  * all: the jointed solve together with prescribed masks (section 7), lock-step right-hand sides, Brownian steps (the drift of a
  * constrained suspension has not been derived here), joint kinds other than those below (no slider, no universal joint).
  *

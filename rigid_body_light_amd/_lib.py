@@ -138,6 +138,8 @@ def lib(path=None):
         L.rbl_ensemble_step_mixed_dof.argtypes = L.rbl_ensemble_step_mixed.argtypes
         L.rbl_ensemble_step_brownian_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, dbl, C.c_int, dbl, vp, vp, vp]
         L.rbl_ensemble_run.argtypes = [vp, C.POINTER(RunOpts), C.POINTER(RunOut)]
+        L.rbl_ensemble_run_jointed.argtypes = [vp, C.POINTER(RunOpts), C.POINTER(RunJointOpts), C.POINTER(RunOut), C.POINTER(RunJointOut)]
+        L.rbl_run_schedule_phase.argtypes = [vp, C.c_int, i64]
         L.rbl_ensemble_set_joint_rates.argtypes = L.rbl_ensemble_set_joint_angles.argtypes = [vp, vp, C.c_int]
         L.rbl_ensemble_solve_jointed.argtypes = [vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp, vp, vp]
         L.rbl_ensemble_step_jointed.argtypes = [vp, vp, vp, vp, dbl, C.c_int, dbl, vp, vp, vp]
@@ -468,6 +470,19 @@ class RunOut(C.Structure):
                 ("steps_done", C.c_int32), ("stopped_at", C.c_int32), ("stop_replica", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RunJointOpts(C.Structure):
+    """rbl_run_joint_opts (include/rbl.h section 5)"""
+    _fields_ = [("size", C.c_int64), ("gamma", C.c_double), ("joint_velocity", C.c_void_p), ("n_phases", C.c_int32),
+                ("rate_sets", C.c_int32), ("start_sets", C.c_int32), ("reserved", C.c_int32), ("phase_steps", C.c_void_p),
+                ("phase_rates", C.c_void_p), ("cycle_start", C.c_void_p)]
+
+
+class RunJointOut(C.Structure):
+    """rbl_run_joint_out (include/rbl.h section 5)"""
+    _fields_ = [("size", C.c_int64), ("theta", C.c_void_p), ("cycle_pos", C.c_void_p), ("phi_sum", C.c_void_p),
+                ("frame_theta", C.c_void_p), ("frame_phi", C.c_void_p), ("frame_gap", C.c_void_p)]
+
+
 RUN_STOP, RUN_REJECT, RUN_CHECK_DEFAULT = 0, 1, 64
 
 
@@ -477,7 +492,12 @@ class RunResult:
     the accepted steps; F_sum and F_mean (R, 6 N_bod) for runs with prescribed bodies (F_mean = F_sum / accepted, NaN where nothing
     was accepted), else None; steps_done, stopped_at (-1: never), stop_replica; the frames X (n_frames, R, N_bod, 3), Q (n_frames,
     R, N_bod, 4), accepted_at (n_frames, R) and, with prescribed bodies, F (n_frames, R, 6 N_bod); status and error: the call's
-    status code and message (0, None for a run that did not stop)"""
+    status code and message (0, None for a run that did not stop).
+    A run with hard joints (DeviceContext.ensemble_run_jointed, Ensemble.run_jointed) adds theta (R, n_joints), the angles it
+    leaves, cycle_pos (R,), the positions in the motor schedule at its end, phi_sum and phi_mean (R, n_joints, 3) over the accepted
+    steps (phi_mean NaN where nothing was accepted) and the frames theta (n_frames, R, n_joints), phi and gap (n_frames, R,
+    n_joints, 3), here as frame_theta, frame_phi and frame_gap; all of them None for other runs"""
+    theta = cycle_pos = phi_sum = phi_mean = frame_theta = frame_phi = frame_gap = None
 
     def __repr__(self):
         return "RunResult(steps_done=%d, stopped_at=%d, accepted=%d..%d, rejected=%d)" % (
@@ -1449,6 +1469,83 @@ class DeviceContext:
         if masked:
             with np.errstate(divide="ignore", invalid="ignore"):
                 res.F_mean = np.where(res.accepted[:, None] > 0, res.F_sum / res.accepted[:, None], np.nan)
+        return res, rc
+
+    def ensemble_run_jointed(self, n_steps, F_body, slip=None, joint_velocity=None, gamma=1.0, phase_steps=None, phase_rates=None,
+                             cycle_start=None, stride=0, on_error=RUN_STOP, check_every=RUN_CHECK_DEFAULT, max_iter=50, rtol=1.0e-8,
+                             brownian=False, prescribed=None, per=0):
+        """n_steps jointed steps of every replica in one call (rbl_ensemble_run_jointed) -> (RunResult, status), as ensemble_run
+        returns them, with the joints' records (theta, cycle_pos, phi_sum, phi_mean, frame_theta / frame_phi / frame_gap).
+        The motor schedule: phase_steps (n_phases,) integers and phase_rates (n_phases, n_joints) or (n_phases, R, n_joints), both
+        None for the stored rates; cycle_start None, an integer or (R,) integers.  brownian, prescribed and per exist so that the
+        library's refusals can be reached; nothing else is offered through them"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        if R == 0:
+            self._chk(self.L.rbl_ensemble_get_config(self.h, None, None))       # the state error, as every ensemble call gives it
+        n_steps, stride = int(n_steps), int(stride)
+        if n_steps < 1 or stride < 0:
+            raise ValueError("ensemble_run_jointed: need n_steps >= 1 and stride >= 0; got %d and %d" % (n_steps, stride))
+        if (phase_steps is None) != (phase_rates is None):
+            raise ValueError("ensemble_run_jointed: phase_steps and phase_rates go together")
+        _, _, nj, F, sl, jv = self._ens_jointed_args(F_body, slip, joint_velocity, "joint_velocity")
+        nst = self._ens_joint_count()                     # the stored joints, on or off: what a schedule is measured against
+        jo = RunJointOpts()
+        jo.size, jo.gamma = C.sizeof(RunJointOpts), float(gamma)
+        jo.joint_velocity = None if jv is None else jv.ctypes.data
+        ps = pr = cs = None
+        if phase_steps is not None:
+            ps = np.ascontiguousarray(phase_steps, dtype=np.int32).reshape(-1)
+            pr = np.ascontiguousarray(phase_rates, dtype=np.float64)
+            if pr.shape not in ((ps.size, nst), (ps.size, R, nst)):
+                raise ValueError("ensemble_run_jointed: phase_rates must have shape (%d, %d) or (%d, %d, %d); got %s"
+                                 % (ps.size, nst, ps.size, R, nst, pr.shape))
+            jo.n_phases, jo.rate_sets = ps.size, (1 if pr.ndim == 2 else R)
+            jo.phase_steps, jo.phase_rates = ps.ctypes.data, pr.ctypes.data
+        if cycle_start is not None:
+            cs = np.ascontiguousarray(cycle_start, dtype=np.int32).reshape(-1)
+            if cs.size not in (1, R):
+                raise ValueError("ensemble_run_jointed: cycle_start must be one integer or %d; got %d" % (R, cs.size))
+            jo.start_sets, jo.cycle_start = cs.size, cs.ctypes.data
+        pm = None if prescribed is None else np.ascontiguousarray(prescribed, dtype=np.uint8)
+        o = RunOpts()
+        o.size = C.sizeof(RunOpts)
+        o.n_steps, o.brownian, o.max_iter, o.stride = n_steps, int(bool(brownian)), int(max_iter), stride
+        o.on_error, o.check_every, o.rtol, o.prescribed_per = int(on_error), int(check_every), float(rtol or 0.0), int(per)
+        o.F_body = F.ctypes.data
+        o.slip = None if sl is None else sl.ctypes.data
+        o.prescribed = None if pm is None else pm.ctypes.data
+        nf = n_steps // stride if stride > 0 else 0
+        res = RunResult()
+        res.accepted, res.rejected = np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32)
+        res.first_flags, res.first_status = np.zeros(R, dtype=np.uint32), np.zeros(R, dtype=np.int32)
+        res.iters_sum, res.resid_max = np.zeros(R, dtype=np.int64), np.zeros(R)
+        res.F_sum = res.F = res.F_mean = None
+        res.X, res.Q = np.zeros((nf, R, nb, 3)), np.zeros((nf, R, nb, 4))
+        res.accepted_at = np.zeros((nf, R), dtype=np.int32)
+        res.theta, res.cycle_pos, res.phi_sum = np.zeros((R, nj)), np.zeros(R, dtype=np.int32), np.zeros((R, nj, 3))
+        res.frame_theta, res.frame_phi, res.frame_gap = np.zeros((nf, R, nj)), np.zeros((nf, R, nj, 3)), np.zeros((nf, R, nj, 3))
+        out = RunOut()
+        out.size = C.sizeof(RunOut)
+        out.accepted, out.rejected = res.accepted.ctypes.data, res.rejected.ctypes.data
+        out.first_flags, out.first_status = res.first_flags.ctypes.data, res.first_status.ctypes.data
+        out.iters_sum, out.resid_max = res.iters_sum.ctypes.data, res.resid_max.ctypes.data
+        out.frame_X, out.frame_Q, out.frame_accepted_at = res.X.ctypes.data, res.Q.ctypes.data, res.accepted_at.ctypes.data
+        out.stopped_at = out.stop_replica = -1       # a refused call leaves them so
+        jout = RunJointOut()
+        jout.size = C.sizeof(RunJointOut)
+        jout.theta, jout.cycle_pos, jout.phi_sum = res.theta.ctypes.data, res.cycle_pos.ctypes.data, res.phi_sum.ctypes.data
+        jout.frame_theta, jout.frame_phi, jout.frame_gap = res.frame_theta.ctypes.data, res.frame_phi.ctypes.data, res.frame_gap.ctypes.data
+        rc = self.L.rbl_ensemble_run_jointed(self.h, C.byref(o), C.byref(jo), C.byref(out), C.byref(jout))
+        res.steps_done, res.stopped_at, res.stop_replica = out.steps_done, out.stopped_at, out.stop_replica
+        res.status, res.error = rc, None
+        if rc != 0:
+            res.error = "%s [rbl status %d]" % (self.L.rbl_last_error(self.h).decode(), rc)
+            if out.stopped_at < 0:                    # refused, or failed outside the steps: there is no result
+                raise RblError(res.error)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            res.phi_mean = np.where(res.accepted[:, None, None] > 0, res.phi_sum / res.accepted[:, None, None], np.nan)
+        res.phi, res.gap = res.frame_phi, res.frame_gap
         return res, rc
 
     def _sizes(self):

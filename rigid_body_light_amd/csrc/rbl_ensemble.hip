@@ -45,6 +45,11 @@
 //   k_ens_commit              per replica, a second launch (so `stopped` is final without any wait between workgroups): commit, or
 //                             q^n copied into the new buffer; counters, sums over accepted steps, the frame
 // The host swaps the two configuration buffers after every step without a synchronisation and reads back once at the end.
+// With hard joints (rbl_ensemble_run_jointed): the same loop around the jointed step (ens_jt_enqueue, the enqueueing part of
+// rbl_ensemble_step_jointed), and one more small launch per step after the commit:
+//   k_ens_jt_run              per replica and joint: theta += rate dt where the replica committed, its position in the motor
+//                             schedule, the sum of phi, the next step's rates into the joint table; the frame's theta and phi
+// (k_ens_jt_rates before the first step; k_ens_jt_geom for the gaps of a recording step).
 //
 // In a periodic cell (rbl_ensemble_set_periodic; the cell's state and checks are in rbl_periodic.hip): the same launches with the
 // cell's instantiations -- k_gmres_small_per (rbl_small_per.hip) and k_ens_rfd_rhs<true, true> (the image sum inside rbl_small_pair_sweep),
@@ -59,6 +64,7 @@
 
 #include "rbl_api_internal.hpp"
 #include "rbl_body_dev.hpp"
+#include "rbl_schedule.hpp"
 #include "rbl_small_dev.hpp"
 
 namespace {
@@ -837,10 +843,18 @@ EnsRunBuf ens_run_carve(void *base, int R, int Nb, int nbl, bool slip, bool mixe
   return b;
 }
 
+// what a run with hard joints (rbl_ensemble_run_jointed) adds to the loop below; the hard-joints part of this file defines them
+struct EnsJtRun;
+size_t ens_jt_run_bytes(const rbl_ctx *c, const EnsJtRun &J, size_t n_frames);
+int ens_jt_run_begin(rbl_ctx *c, EnsJtRun &J, void *base, size_t n_frames, int max_iter, const EnsRunBuf &b);
+int ens_jt_run_enqueue(rbl_ctx *c, const EnsWork &w, EnsJtRun &J, const EnsStepIn &in, int max_iter, double rtol);
+void ens_jt_run_after(rbl_ctx *c, EnsJtRun &J, long frame);
+int ens_jt_run_end(rbl_ctx *c, EnsJtRun &J, size_t nfr, bool stopped);
+
 // n_steps steps of every replica (checks and ens_ready done by the caller; per: the mask's entries per body): the inputs go up
 // once, every step is the one-step calls' enqueue sequence followed by the verdict and the commit, the buffers flip on the host,
-// ONE read-back ends it
-int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_out *out)
+// ONE read-back ends it.  J (rbl_ensemble_run_jointed): the step is the jointed one and one launch for the joints follows the commit
+int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_out *out, EnsJtRun *J = nullptr)
 {
   const RblBodyState &S = c->S;
   const bool mixed = o.prescribed != nullptr, reject = o.on_error == RBL_RUN_REJECT;
@@ -852,7 +866,7 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
   if ((rc = ens_work(c, o.max_iter, &w))) return rc;
   size_t bytes = 0;
   ens_run_carve(nullptr, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
-  if ((rc = rbl_dev_reserve(c, c->d_ens_run, bytes))) return rc;
+  if ((rc = rbl_dev_reserve(c, c->d_ens_run, bytes + (J ? ens_jt_run_bytes(c, *J, n_frames) : 0)))) return rc;   // the joints' part behind
   const EnsRunBuf b = ens_run_carve(c->d_ens_run.p, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
   // the uploads, once
   if (mixed && (rc = ens_upload_mask(c, w, o.prescribed, per))) return rc;
@@ -860,6 +874,7 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
   if (o.slip && (rc = copy_h2d(c, b.slip, o.slip, sizeof(double) * n3 * Rz))) return rc;
   RBL_HIP(c, hipMemsetAsync(b.st, 0, b.rb_bytes, c->stream));
   if (mixed) RBL_HIP(c, hipMemsetAsync(b.F_last, 0, sizeof(double) * nb6 * Rz, c->stream));
+  if (J && (rc = ens_jt_run_begin(c, *J, (char *)c->d_ens_run.p + bytes, n_frames, o.max_iter, b))) return rc;
   EnsStepIn in;
   in.prescribed = o.prescribed; in.per = per;
   in.slip = o.slip ? b.slip : nullptr; in.resident = true; in.chol_err = 1;
@@ -867,8 +882,9 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
   EnsRunStatus hs = {0, 0, 0u, 0};
   int enq = 0;
   for (int n = 0; n < o.n_steps; ++n) {
-    rc = brownian ? ens_enqueue_bd(c, w, in, o.seed + (uint64_t)n, o.split_rand, o.delta, o.max_iter, o.rtol)
-                  : ens_enqueue_det(c, w, in, o.max_iter, o.rtol, true);
+    rc = J          ? ens_jt_run_enqueue(c, w, *J, in, o.max_iter, o.rtol)
+         : brownian ? ens_enqueue_bd(c, w, in, o.seed + (uint64_t)n, o.split_rand, o.delta, o.max_iter, o.rtol)
+                    : ens_enqueue_det(c, w, in, o.max_iter, o.rtol, true);
     if (rc) return rc;
     const int cur = c->ens_cur;
     if (S.wall)
@@ -892,6 +908,7 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
     }
     hipLaunchKernelGGL(k_ens_commit, dim3((unsigned)R), dim3(ET), 0, c->stream, R, Nb, n, D);
     c->ens_cur ^= 1;                                     // the new buffer holds every replica's configuration, moved or not
+    if (J) ens_jt_run_after(c, *J, D.fX ? (long)((n + 1) / o.stride - 1) : -1L);
     ++enq;
     if (o.check_every > 0 && enq % o.check_every == 0 && n + 1 < o.n_steps) {
       if ((rc = read_back(c, &hs, b.st, sizeof(hs)))) return rc;
@@ -923,6 +940,7 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
     if (mixed && (rc = copy_d2h(c, out->frame_F, b.fF, sizeof(double) * nfr * Rz * nb6))) return rc;
     RBL_HIP(c, hipStreamSynchronize(c->stream));
   }
+  if (J && (rc = ens_jt_run_end(c, *J, nfr, hs.stopped != 0))) return rc;
   out->stopped_at = hs.stopped ? hs.stopped - 1 : -1;
   out->steps_done = hs.stopped ? hs.stopped - 1 : o.n_steps;
   out->stop_replica = hs.stopped && hs.stop_rep ? R - hs.stop_rep : -1;
@@ -1111,29 +1129,36 @@ int ens_jt_plain_solve(rbl_ctx *c, const double *F_body, const double *slip, int
 // the jointed solve of every replica at the current configuration; move: a time step -- the force model's loads and the flow
 // model's slip at q^n (ens_begin), c formed in the kernel from the gaps (coef = -gamma / dt), k_ens_evolve, and on success the
 // commit and the motors' angles
-int ens_jt_solve(rbl_ctx *c, const char *who, const double *F_body, const double *slip, const double *jr, bool move, double coef, int max_iter,
-                 double rtol, double *lambda, double *U, double *phi, int *iters, double *resid)
+// the jointed solve's own vectors in d_ens_jtw: rhs | x (nsys per replica each) | the joint rows given (3 n_joints) | solver workspace
+struct EnsJtVec { double *rhs, *x, *djr, *gm; };
+
+int ens_jt_vectors(rbl_ctx *c, int max_iter, EnsJtVec *V)
+{
+  const int Nb = c->ens_Nb, nbl = c->S.N_blb, nj = c->jt_n;
+  const size_t nj3 = (size_t)3 * nj, nsys = (size_t)3 * Nb * nbl + (size_t)6 * Nb + nj3, Rz = (size_t)c->ens_R;
+  const size_t wd = rbl_gmres_small_jt_work_doubles(nbl, Nb, max_iter, nj);
+  int rc = rbl_dev_reserve(c, c->d_ens_jtw, sizeof(double) * Rz * (2 * nsys + nj3 + wd)); if (rc) return rc;
+  V->rhs = (double *)c->d_ens_jtw.p; V->x = V->rhs + Rz * nsys; V->djr = V->x + Rz * nsys; V->gm = V->djr + Rz * nj3;
+  return RBL_OK;
+}
+
+// everything the jointed solve or step enqueues, from ens_begin's uploads to the update: the one-step calls and the run
+// (rbl_ensemble_run_jointed, in.resident) share it.  have_jr: V.djr holds the joint rows the caller gave
+int ens_jt_enqueue(rbl_ctx *c, const char *who, const EnsWork &w, const RblEnsJoints &T, const EnsJtVec &V, const EnsStepIn &in, bool have_jr,
+                   bool move, double coef, int max_iter, double rtol)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb, nj = c->jt_n;
-  const size_t n3 = (size_t)3 * Nb * nbl, nb6 = (size_t)6 * Nb, nj3 = (size_t)3 * nj, nsys = n3 + nb6 + nj3, Rz = (size_t)R;
-  c->ens_jt_phi_valid = false;
-  EnsWork w;
+  const size_t n3 = (size_t)3 * Nb * nbl, nb6 = (size_t)6 * Nb, nj3 = (size_t)3 * nj, nsys = n3 + nb6 + nj3;
+  double *rhs = V.rhs, *x = V.x;
   int rc;
-  if ((rc = ens_work(c, max_iter, &w))) return rc;
-  RblEnsJoints T;
-  if ((rc = ens_jt_upload(c, &T))) return rc;
-  const size_t wd = rbl_gmres_small_jt_work_doubles(nbl, Nb, max_iter, nj);
-  if ((rc = rbl_dev_reserve(c, c->d_ens_jtw, sizeof(double) * Rz * (2 * nsys + nj3 + wd)))) return rc;
-  double *rhs = (double *)c->d_ens_jtw.p, *x = rhs + Rz * nsys, *djr = x + Rz * nsys, *gm = djr + Rz * nj3;
-  if (jr && (rc = copy_h2d(c, djr, jr, sizeof(double) * Rz * nj3))) return rc;
   const double *FT, *SL;
-  if ((rc = ens_begin(c, w, F_body, slip, &FT, &SL, move))) return rc;
+  if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, move, in.resident, in.accepted))) return rc;
   const long tot = (long)R * (long)nsys;
   hipLaunchKernelGGL(k_ens_rhs_jt, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, (int)n3, (int)nb6, (int)nj3, SL,
-                     (const double *)w.F, FT, jr ? (const double *)djr : nullptr, rhs);
+                     (const double *)w.F, FT, have_jr ? (const double *)V.djr : nullptr, rhs);
   const RblParams P = rbl_make_params(c->S.a, c->S.eta);
   const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
-  rc = rbl_launch_gmres_small_ens_jt(c->stream, P, c->S.wall, X, Q, ens_cfg(c), nbl, Nb, R, rhs, x, max_iter, rtol, gm, w.iters, w.resid,
+  rc = rbl_launch_gmres_small_ens_jt(c->stream, P, c->S.wall, X, Q, ens_cfg(c), nbl, Nb, R, rhs, x, max_iter, rtol, V.gm, w.iters, w.resid,
                                      w.rerr, T, move ? 1 : 0, coef);
   if (rc) return rbl_fail(c, rc, std::string(who) + ": the one-kernel jointed solver does not fit this device's LDS");
   if (move) {
@@ -1146,6 +1171,27 @@ int ens_jt_solve(rbl_ctx *c, const char *who, const double *F_body, const double
     hipLaunchKernelGGL(k_ens_evolve, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, (long)nsys, (long)n3, c->S.dt,
                        (const double *)x, X, Q, ens_X(c, c->ens_cur ^ 1), ens_Q(c, c->ens_cur ^ 1), w.rerr);
   }
+  return RBL_OK;
+}
+
+int ens_jt_solve(rbl_ctx *c, const char *who, const double *F_body, const double *slip, const double *jr, bool move, double coef, int max_iter,
+                 double rtol, double *lambda, double *U, double *phi, int *iters, double *resid)
+{
+  const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb, nj = c->jt_n;
+  const size_t n3 = (size_t)3 * Nb * nbl, nb6 = (size_t)6 * Nb, nj3 = (size_t)3 * nj, nsys = n3 + nb6 + nj3, Rz = (size_t)R;
+  c->ens_jt_phi_valid = false;
+  EnsWork w;
+  int rc;
+  if ((rc = ens_work(c, max_iter, &w))) return rc;
+  RblEnsJoints T;
+  if ((rc = ens_jt_upload(c, &T))) return rc;
+  EnsJtVec V;
+  if ((rc = ens_jt_vectors(c, max_iter, &V))) return rc;
+  if (jr && (rc = copy_h2d(c, V.djr, jr, sizeof(double) * Rz * nj3))) return rc;
+  EnsStepIn in;
+  in.F_body = F_body; in.slip = slip;
+  if ((rc = ens_jt_enqueue(c, who, w, T, V, in, jr != nullptr, move, coef, max_iter, rtol))) return rc;
+  const double *x = V.x;
   std::vector<double> hx(Rz * nsys);
   if ((rc = copy_d2h(c, hx.data(), x, sizeof(double) * hx.size()))) return rc;
   // a redundant joint set: RBL_FLAG_REDUNDANT in the replica's word, which ens_finish turns into RBL_ERR_NOT_SPD with the replica named
@@ -1194,6 +1240,240 @@ int ens_jt_set_values(rbl_ctx *c, const char *who, const double *v, int sets, bo
   for (int r = 0; r < c->ens_R; ++r)
     std::copy(v + (size_t)(sets == 1 ? 0 : r) * c->jt_n, v + (size_t)(sets == 1 ? 0 : r) * c->jt_n + c->jt_n, dst.begin() + (size_t)r * c->jt_n);
   c->ens_jt_valid = false;
+  return RBL_OK;
+}
+
+// ---- a run with hard joints (rbl_ensemble_run_jointed): ens_run's loop with the jointed step, and the joints' own launch ----
+// What moves during such a run besides the configurations lives on the device: the angles and rates in the joint table
+// (RblEnsJoints::theta / rate, which the solver and k_ens_jt_geom read per replica), every replica's position in the motor
+// schedule, the sums and the last accepted value of phi.
+
+// what k_ens_jt_run reads and writes (device pointers; the frame slots are NULL in a step that records none)
+struct EnsJtRunDev {
+  const EnsRunStatus *st; const unsigned *vflag;   // the run's status and this step's verdicts, as k_ens_commit read them
+  double *theta, *rate;                            // the joint table's [R n_joints] arrays
+  const double *x; long nsys, off;                 // this step's solutions: phi of replica r at x + r nsys + off
+  const int *pos_in; int *pos_out;                 // cycle positions [R], read and written: two buffers, since a replica's threads
+                                                   // may sit in two workgroups and nobody waits for anybody
+  const int *cum; const double *rates;             // the schedule: prefix sums (n_phases + 1), rates [n_phases rate_sets n_joints]
+  int n_phases, rate_sets;
+  double dt;
+  double *phi_sum, *phi_last;                      // [R 3 n_joints]
+  double *fT, *fP;                                 // the frame's theta [R n_joints] and phi [R 3 n_joints]
+};
+
+// the scheduled rate of joint j of replica r at cycle position p
+__device__ __forceinline__ double ens_jt_sched_rate(const int *cum, const double *rates, int n_phases, int rate_sets, int nj, int r, int j,
+                                                    int p)
+{
+  const int k = rbl_schedule_phase(cum, n_phases, p);
+  return rates[((size_t)k * rate_sets + (rate_sets == 1 ? 0 : r)) * nj + j];
+}
+
+// One thread per replica and joint, after k_ens_commit (st->stopped and vflag are final for this step): where the replica
+// committed, theta += rate dt with the product and the sum rounded one after the other and only where rate != 0 -- the statements
+// of the one-step call's host loop, so its bits --, the cycle position moves on by one and the step's phi is kept and added to
+// phi_sum (every entry by one thread, in step order).  Then, committed or not, the rates of the replica's next step go into the
+// table, and the frame is written: the angles as they stand, the last accepted phi
+__global__ __launch_bounds__(64) void k_ens_jt_run(int R, int nj, EnsJtRunDev D)
+{
+  const long g = (long)blockIdx.x * 64 + threadIdx.x;
+  if (g >= (long)R * nj) return;
+  const int r = (int)(g / nj), j = (int)(g - (long)r * nj);
+  const bool ok = D.st->stopped == 0 && D.vflag[r] == 0;
+  const size_t e = 3 * (size_t)g;
+  int p = D.n_phases ? D.pos_in[r] : 0;
+  double th = D.theta[g], ph[3] = {D.phi_last[e], D.phi_last[e + 1], D.phi_last[e + 2]};
+  if (ok) {
+    const double rate = D.rate[g];
+    if (rate != 0.0) {
+#pragma clang fp contract(off)
+      const double d = rate * D.dt;
+      th = th + d;
+      D.theta[g] = th;
+    }
+    if (D.n_phases) p = rbl_schedule_next(D.cum, D.n_phases, p);
+    const double *phi = D.x + (size_t)r * D.nsys + D.off + 3 * j;
+    for (int q = 0; q < 3; ++q) {
+      ph[q] = phi[q];
+      D.phi_last[e + q] = ph[q];
+      D.phi_sum[e + q] += ph[q];
+    }
+  }
+  if (D.n_phases) {
+    D.rate[g] = ens_jt_sched_rate(D.cum, D.rates, D.n_phases, D.rate_sets, nj, r, j, p);
+    if (j == 0) D.pos_out[r] = p;
+  }
+  if (D.fT) {
+    D.fT[g] = th;
+    for (int q = 0; q < 3; ++q) D.fP[e + q] = ph[q];
+  }
+}
+
+// before the first step: the rates of every replica's starting position into the table
+__global__ __launch_bounds__(64) void k_ens_jt_rates(int R, int nj, const int *__restrict__ pos, const int *__restrict__ cum,
+                                                     const double *__restrict__ rates, int n_phases, int rate_sets, double *__restrict__ rate)
+{
+  const long g = (long)blockIdx.x * 64 + threadIdx.x;
+  if (g >= (long)R * nj) return;
+  const int r = (int)(g / nj), j = (int)(g - (long)r * nj);
+  rate[g] = ens_jt_sched_rate(cum, rates, n_phases, rate_sets, nj, r, j, pos[r]);
+}
+
+struct EnsJtRun {
+  const rbl_run_joint_opts *o; rbl_run_joint_out *out;
+  double coef;                                     // -gamma / dt
+  std::vector<int> cum, start;                     // host: the prefix sums (n_phases + 1, or empty), the starting positions [R]
+  RblEnsJoints T; EnsJtVec V;
+  const EnsRunStatus *st; const unsigned *vflag;
+  int *pos[2]; int cur;                            // device: positions, which of the two is current
+  int *cum_d; double *rates_d, *phi_sum, *phi_last, *lev, *fT, *fP, *fG;
+};
+
+void ens_jt_run_carve(EnsJtRun &J, void *base, int R, int nj, size_t n_frames, size_t *bytes)
+{
+  const size_t Rn = (size_t)R * nj, np = (size_t)J.o->n_phases;
+  Carve C{(char *)base};
+  J.pos[0] = C.take<int>(R); J.pos[1] = C.take<int>(R);
+  J.cum_d = C.take<int>(np + 1);
+  J.rates_d = C.take<double>(np * (size_t)J.o->rate_sets * nj);
+  J.phi_sum = C.take<double>(6 * Rn);              // phi_sum | phi_last, cleared in one piece
+  J.phi_last = J.phi_sum ? J.phi_sum + 3 * Rn : nullptr;
+  J.lev = C.take<double>(6 * Rn);
+  J.fT = C.take<double>(n_frames * Rn); J.fP = C.take<double>(n_frames * 3 * Rn); J.fG = C.take<double>(n_frames * 3 * Rn);
+  *bytes = C.off;
+}
+
+size_t ens_jt_run_bytes(const rbl_ctx *c, const EnsJtRun &J, size_t n_frames)
+{
+  EnsJtRun t = J;
+  size_t bytes = 0;
+  ens_jt_run_carve(t, nullptr, c->ens_R, c->jt_n, n_frames, &bytes);
+  return bytes;
+}
+
+// the joint table (with the stored angles and rates), the solver's vectors, joint_velocity and the schedule go up, once; the first
+// step's rates are written.  From here on the device table is ahead of the host's copy: it is marked stale whatever follows
+int ens_jt_run_begin(rbl_ctx *c, EnsJtRun &J, void *base, size_t n_frames, int max_iter, const EnsRunBuf &b)
+{
+  const int R = c->ens_R, nj = c->jt_n, np = J.o->n_phases;
+  const size_t Rn = (size_t)R * nj;
+  int rc;
+  if ((rc = ens_jt_upload(c, &J.T))) return rc;
+  if ((rc = ens_jt_vectors(c, max_iter, &J.V))) return rc;
+  size_t bytes = 0;
+  ens_jt_run_carve(J, base, R, nj, n_frames, &bytes);
+  J.st = b.st; J.vflag = b.vflag; J.cur = 0;
+  c->ens_jt_valid = false; c->ens_jt_phi_valid = false;
+  if (J.o->joint_velocity && (rc = copy_h2d(c, J.V.djr, J.o->joint_velocity, sizeof(double) * 3 * Rn))) return rc;
+  RBL_HIP(c, hipMemsetAsync(J.phi_sum, 0, sizeof(double) * 6 * Rn, c->stream));
+  if (np) {
+    if ((rc = copy_h2d(c, J.cum_d, J.cum.data(), sizeof(int) * ((size_t)np + 1)))) return rc;
+    if ((rc = copy_h2d(c, J.rates_d, J.o->phase_rates, sizeof(double) * (size_t)np * J.o->rate_sets * nj))) return rc;
+    if ((rc = copy_h2d(c, J.pos[0], J.start.data(), sizeof(int) * (size_t)R))) return rc;
+    hipLaunchKernelGGL(k_ens_jt_rates, dim3((unsigned)((Rn + 63) / 64)), dim3(64), 0, c->stream, R, nj, (const int *)J.pos[0],
+                       (const int *)J.cum_d, (const double *)J.rates_d, np, (int)J.o->rate_sets, (double *)J.T.rate);
+  }
+  return RBL_OK;
+}
+
+int ens_jt_run_enqueue(rbl_ctx *c, const EnsWork &w, EnsJtRun &J, const EnsStepIn &in, int max_iter, double rtol)
+{
+  return ens_jt_enqueue(c, "ensemble_run_jointed", w, J.T, J.V, in, J.o->joint_velocity != nullptr, true, J.coef, max_iter, rtol);
+}
+
+// after the step's commit and the host's flip: the joints' launch and, in a recording step (frame >= 0), the gaps at the committed
+// configuration and angles by k_ens_jt_geom itself
+void ens_jt_run_after(rbl_ctx *c, EnsJtRun &J, long frame)
+{
+  const int R = c->ens_R, Nb = c->ens_Nb, nj = c->jt_n, np = J.o->n_phases;
+  const size_t Rn = (size_t)R * nj, n3 = (size_t)3 * Nb * c->S.N_blb, nb6 = (size_t)6 * Nb;
+  EnsJtRunDev D;
+  D.st = J.st; D.vflag = J.vflag;
+  D.theta = (double *)J.T.theta; D.rate = (double *)J.T.rate;
+  D.x = J.V.x; D.nsys = (long)(n3 + nb6 + 3 * (size_t)nj); D.off = (long)(n3 + nb6);
+  D.pos_in = J.pos[J.cur]; D.pos_out = J.pos[J.cur ^ 1];
+  D.cum = J.cum_d; D.rates = J.rates_d; D.n_phases = np; D.rate_sets = J.o->rate_sets;
+  D.dt = c->S.dt;
+  D.phi_sum = J.phi_sum; D.phi_last = J.phi_last;
+  D.fT = D.fP = nullptr;
+  if (frame >= 0) { D.fT = J.fT + (size_t)frame * Rn; D.fP = J.fP + (size_t)frame * 3 * Rn; }
+  hipLaunchKernelGGL(k_ens_jt_run, dim3((unsigned)((Rn + 63) / 64)), dim3(64), 0, c->stream, R, nj, D);
+  if (np) J.cur ^= 1;
+  if (frame >= 0)
+    rbl_launch_ens_jt_geom(c->stream, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), Nb, R, J.T, J.lev, J.fG + (size_t)frame * 3 * Rn);
+}
+
+// the joints' share of the read-back: the angles become the ensemble's, the last accepted phi the one rbl_ensemble_joint_state
+// returns (not after a stop: that phi is invalid, as after a failed step); nfr: the frames of the steps that were enqueued
+int ens_jt_run_end(rbl_ctx *c, EnsJtRun &J, size_t nfr, bool stopped)
+{
+  const int R = c->ens_R, nj = c->jt_n;
+  const size_t Rn = (size_t)R * nj;
+  rbl_run_joint_out *out = J.out;
+  int rc;
+  c->ens_jt_phi.resize(3 * Rn);
+  if ((rc = copy_d2h(c, c->ens_jt_theta.data(), J.T.theta, sizeof(double) * Rn))) return rc;
+  if ((rc = copy_d2h(c, c->ens_jt_phi.data(), J.phi_last, sizeof(double) * 3 * Rn))) return rc;
+  if (out->phi_sum && (rc = copy_d2h(c, out->phi_sum, J.phi_sum, sizeof(double) * 3 * Rn))) return rc;
+  if (out->cycle_pos) {
+    if (!J.o->n_phases) std::memset(out->cycle_pos, 0, sizeof(int32_t) * (size_t)R);
+    else if ((rc = copy_d2h(c, out->cycle_pos, J.pos[J.cur], sizeof(int32_t) * (size_t)R))) return rc;
+  }
+  if (nfr) {
+    if (out->frame_theta && (rc = copy_d2h(c, out->frame_theta, J.fT, sizeof(double) * nfr * Rn))) return rc;
+    if (out->frame_phi && (rc = copy_d2h(c, out->frame_phi, J.fP, sizeof(double) * nfr * 3 * Rn))) return rc;
+    if (out->frame_gap && (rc = copy_d2h(c, out->frame_gap, J.fG, sizeof(double) * nfr * 3 * Rn))) return rc;
+  }
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  if (out->theta) std::memcpy(out->theta, c->ens_jt_theta.data(), sizeof(double) * Rn);
+  c->ens_jt_phi_valid = !stopped;
+  return RBL_OK;
+}
+
+// the schedule's own refusals (include/rbl.h section 5), none needing a device; fills J.cum and J.start
+int ens_jt_schedule_check(rbl_ctx *c, const char *who, const rbl_run_joint_opts &jo, EnsJtRun &J)
+{
+  const std::string w(who);
+  const int R = c->ens_R, nj = c->jt_n;
+  if (jo.n_phases < 0) return rbl_fail(c, RBL_ERR_ARG, w + ": n_phases must be >= 0");
+  if (jo.start_sets != 0 && jo.start_sets != 1 && jo.start_sets != R)
+    return rbl_fail(c, RBL_ERR_ARG, w + ": start_sets must be 0, 1 or R = " + std::to_string(R));
+  if (jo.start_sets && !jo.cycle_start) return rbl_fail(c, RBL_ERR_ARG, w + ": cycle_start is NULL while start_sets > 0");
+  J.cum.clear();
+  long long len = 0;
+  if (jo.n_phases) {
+    if (!ens_jt_active(c))
+      return rbl_fail(c, RBL_ERR_STATE, w + ": a motor schedule was given, but the joints are switched off or were never set (rbl_set_joint_kinds)");
+    if (!jo.phase_steps || !jo.phase_rates) return rbl_fail(c, RBL_ERR_ARG, w + ": phase_steps or phase_rates is NULL while n_phases > 0");
+    if (jo.rate_sets != 1 && jo.rate_sets != R) return rbl_fail(c, RBL_ERR_ARG, w + ": rate_sets must be 1 or R = " + std::to_string(R));
+    J.cum.push_back(0);
+    for (int k = 0; k < jo.n_phases; ++k) {
+      if (jo.phase_steps[k] < 1)
+        return rbl_fail(c, RBL_ERR_ARG, w + ": phase_steps[" + std::to_string(k) + "] = " + std::to_string(jo.phase_steps[k]) + ": every phase lasts at least one step");
+      len += jo.phase_steps[k];
+      if (len > 0x7fffffffLL) return rbl_fail(c, RBL_ERR_ARG, w + ": the cycle's length (the sum of phase_steps) must fit 31 bits");
+      J.cum.push_back((int)len);
+    }
+    for (int k = 0; k < jo.n_phases; ++k)
+      for (int s = 0; s < jo.rate_sets; ++s)
+        for (int j = 0; j < nj; ++j) {
+          const double x = jo.phase_rates[((size_t)k * jo.rate_sets + s) * nj + j];
+          const std::string at = w + ": phase " + std::to_string(k) + ", set " + std::to_string(s) + ", joint " + std::to_string(j) + ": ";
+          if (!std::isfinite(x)) return rbl_fail(c, RBL_ERR_ARG, at + "the value must be finite");
+          if (x != 0.0 && c->jt_kind[j] != RBL_JOINT_LOCK)
+            return rbl_fail(c, RBL_ERR_ARG, at + "only a lock joint (RBL_JOINT_LOCK) takes a rate; it must be 0 here");
+        }
+  }
+  J.start.assign((size_t)R, 0);
+  for (int s = 0; s < jo.start_sets; ++s) {
+    const long long p = jo.cycle_start[s];
+    if (p < 0 || p >= std::max(len, 1LL))
+      return rbl_fail(c, RBL_ERR_ARG, w + ": cycle_start[" + std::to_string(s) + "] = " + std::to_string(p) + " lies outside the cycle, 0 <= value < " +
+                                          std::to_string(std::max(len, 1LL)) + (len ? "" : " (no schedule: only 0)"));
+    if (jo.start_sets == 1) J.start.assign((size_t)R, (int)p);
+    else J.start[(size_t)s] = (int)p;
+  }
   return RBL_OK;
 }
 
@@ -1381,6 +1661,67 @@ int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)
   if ((rc = ens_flow_check(c))) return rc;
   if ((rc = ens_ready(c))) return rc;
   return ens_run(c, *o, per, brownian, out);
+}
+
+// n_steps jointed steps in one call: rbl_ensemble_step_jointed's checks and rbl_ensemble_run's, the schedule's own, then ens_run
+// with the jointed step; joints off or never set: rbl_ensemble_run's deterministic run itself
+int rbl_ensemble_run_jointed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, rbl_run_out *out, rbl_run_joint_out *jout)
+{
+  const char *who = "ensemble_run_jointed";
+  const std::string w(who);
+  if (!c) return RBL_ERR_ARG;
+  if (!o || !jo || !out || !jout) return rbl_fail(c, RBL_ERR_ARG, w + ": opts, jopts, out or jout is NULL");
+  if (o->size != (int64_t)sizeof(rbl_run_opts)) return rbl_fail(c, RBL_ERR_ARG, w + ": opts.size is not sizeof(rbl_run_opts)");
+  if (jo->size != (int64_t)sizeof(rbl_run_joint_opts)) return rbl_fail(c, RBL_ERR_ARG, w + ": jopts.size is not sizeof(rbl_run_joint_opts)");
+  if (out->size != (int64_t)sizeof(rbl_run_out)) return rbl_fail(c, RBL_ERR_ARG, w + ": out.size is not sizeof(rbl_run_out)");
+  if (jout->size != (int64_t)sizeof(rbl_run_joint_out)) return rbl_fail(c, RBL_ERR_ARG, w + ": jout.size is not sizeof(rbl_run_joint_out)");
+  out->steps_done = 0; out->stopped_at = -1; out->stop_replica = -1; out->reserved = 0;   // what a refused call leaves
+  if (periodic_on(c)) return periodic_refuse(c, who);
+  if (ens_cell_on(c)) return ens_cell_refuse(c, who);
+  if (o->n_steps < 1) return rbl_fail(c, RBL_ERR_ARG, w + ": n_steps must be >= 1");
+  if (o->stride < 0) return rbl_fail(c, RBL_ERR_ARG, w + ": stride must be >= 0");
+  if (o->check_every < 0) return rbl_fail(c, RBL_ERR_ARG, w + ": check_every must be >= 0");
+  if (o->on_error != RBL_RUN_STOP && o->on_error != RBL_RUN_REJECT)
+    return rbl_fail(c, RBL_ERR_ARG, w + ": on_error must be RBL_RUN_STOP (0) or RBL_RUN_REJECT (1)");
+  if (o->prescribed || o->body_in)
+    return rbl_fail(c, RBL_ERR_ARG, w + ": prescribed and body_in must be NULL: joints together with prescribed masks are not offered");
+  if (o->prescribed_per != 0 && o->prescribed_per != 1)
+    return rbl_fail(c, RBL_ERR_ARG, w + ": prescribed_per must be 0 or 1: joints together with prescribed masks are not offered");
+  if (o->brownian && c->S.kBT > 1e-10)                   // kBT <= 1e-10: brownian is ignored, as in a plain run
+    return rbl_fail(c, RBL_ERR_ARG, w + ": brownian != 0 with kBT > 1e-10: Brownian jointed steps are not offered, the drift of a constrained "
+                                        "suspension has not been derived");
+  if (!(jo->gamma >= 0.0 && jo->gamma <= 1.0)) return rbl_fail(c, RBL_ERR_ARG, w + ": gamma must lie in [0, 1]");
+  const bool on = ens_jt_active(c);
+  if (on && !(c->S.dt > 0.0)) return rbl_fail(c, RBL_ERR_ARG, w + ": dt must be positive");
+  int rc = ens_jt_check(c, who, o->F_body, o->max_iter, o->rtol); if (rc) return rc;
+  const size_t n_frames = o->stride > 0 ? (size_t)(o->n_steps / o->stride) : 0;
+  if (n_frames && (!out->frame_X || !out->frame_Q || !out->frame_accepted_at))
+    return rbl_fail(c, RBL_ERR_ARG, w + ": frame_X, frame_Q and frame_accepted_at must not be NULL while stride > 0 records frames");
+  EnsJtRun J = {};
+  J.o = jo; J.out = jout;
+  if ((rc = ens_jt_schedule_check(c, who, *jo, J))) return rc;
+  rbl_run_opts od = *o;                                  // the deterministic run's options
+  od.brownian = 0; od.prescribed_per = 0;
+  if (!on) {
+    if ((rc = rbl_ensemble_run(c, &od, out)) && out->stopped_at < 0) return rc;
+    if (jout->cycle_pos) std::memset(jout->cycle_pos, 0, sizeof(int32_t) * (size_t)c->ens_R);
+    return rc;
+  }
+  if ((rc = ens_flow_check(c))) return rc;
+  if ((rc = ens_ready(c))) return rc;
+  J.coef = -jo->gamma / c->S.dt;
+  return ens_run(c, od, 1, false, out, &J);
+}
+
+int rbl_run_schedule_phase(const int32_t *phase_steps, int n_phases, int64_t pos)
+{
+  if (!phase_steps || n_phases < 1 || pos < 0) return -1;
+  std::vector<int> cum(1, 0);
+  for (int k = 0; k < n_phases; ++k) {
+    if (phase_steps[k] < 1 || (int64_t)cum.back() + phase_steps[k] > 0x7fffffffLL) return -1;
+    cum.push_back(cum.back() + phase_steps[k]);
+  }
+  return pos < cum.back() ? rbl_schedule_phase(cum.data(), n_phases, (int)pos) : -1;
 }
 
 int rbl_ensemble_interaction_forces(rbl_ctx *c, double *FT_body, double *energy)

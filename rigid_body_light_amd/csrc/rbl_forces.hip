@@ -319,12 +319,19 @@ struct IaMag {
 };
 
 // B at replica r's field time t = t0 + dt * n, n = the replica's accepted steps so far inside a run (accepted == NULL, the
-// one-step calls: 0).  The product and the sum are rounded separately, as the host's t0 + dt * n is: a run is bitwise the loop
+// one-step calls: 0).  The product and the sum are rounded separately, as the host's t0 + dt * n is: a run is bitwise the loop.
+// Contraction is switched off for the two statements: __dmul_rn and __dadd_rn are the plain operators here, and the compiler fused
+// them into one fma, which rounds differently for some n (t0 = 0.37, dt = 0.01: first at n = 9)
 __device__ __forceinline__ void ia_field_B(const IaMag &M, const double *__restrict__ tf, const int *__restrict__ accepted, int r,
                                            double (&B)[3])
 {
   const double n = accepted ? (double)accepted[r] : 0.0;
-  const double t = __dadd_rn(tf[M.per_t == 1 ? 0 : r], __dmul_rn(M.dt, n));
+  double t;
+  {
+#pragma clang fp contract(off)
+    const double s = M.dt * n;
+    t = tf[M.per_t == 1 ? 0 : r] + s;
+  }
   double sn, cs;
   sincos(__dmul_rn(M.omega, t), &sn, &cs);
 #pragma unroll

@@ -414,6 +414,77 @@ class Ensemble:
         jv = self._joint_rows_in("joint_velocity", joint_velocity, self._joints_on())
         return self.ctx.ensemble_step_jointed(F, slip=s, joint_velocity=jv, gamma=gamma, max_iter=max_iter, rtol=rtol)
 
+    def _schedule(self, schedule, cycle_start):
+        """(phase_steps, phase_rates) and the starting positions as run_jointed takes them -> (int32 (n_phases,), float64
+        (n_phases, n_joints) or (n_phases, R, n_joints), int32 (1,) or (R,)), each None where not given; ValueError before the
+        library is called"""
+        ps = pr = cs = None
+        length = 0
+        if schedule is not None:
+            n = self.ctx.joints()["body"].shape[0]
+            try:
+                ps, pr = schedule
+            except (TypeError, ValueError):
+                _fail("run_jointed: schedule must be a pair (phase_steps, phase_rates)")
+            ps, pr = np.asarray(ps), np.asarray(pr, dtype=np.float64)
+            if ps.ndim != 1 or not ps.size or not np.issubdtype(ps.dtype, np.integer):
+                _fail("run_jointed: phase_steps must be a non-empty list of integers; got shape %s, dtype %s" % (ps.shape, ps.dtype))
+            if (ps < 1).any():
+                _fail("run_jointed: phase_steps[%d] = %d: every phase lasts at least one step" % (int(np.flatnonzero(ps < 1)[0]), int(ps[ps < 1][0])))
+            length = int(ps.astype(np.int64).sum())
+            if length > 2**31 - 1:
+                _fail("run_jointed: the cycle's length (the sum of phase_steps) must fit 31 bits")
+            if not n or pr.shape not in ((ps.size, n), (ps.size, self.R, n)):
+                _fail("run_jointed: phase_rates: one rate per phase and stored joint, shape (%d, %d) or (%d, %d, %d); got %s"
+                      % (ps.size, n, ps.size, self.R, n, pr.shape))
+            if not np.isfinite(pr).all():
+                _fail("run_jointed: phase_rates must be finite")
+            ps = ps.astype(np.int32)
+        if cycle_start is not None:
+            cs = np.asarray(cycle_start)
+            if cs.shape not in ((), (1,), (self.R,)) or not np.issubdtype(cs.dtype, np.integer):
+                _fail("run_jointed: cycle_start must be an integer or %d integers; got shape %s, dtype %s" % (self.R, cs.shape, cs.dtype))
+            cs = cs.reshape(-1)
+            if (cs < 0).any() or (cs >= max(length, 1)).any():
+                _fail("run_jointed: cycle_start must lie in the cycle, 0 <= value < %d; got %s" % (max(length, 1), cs.tolist()))
+            cs = cs.astype(np.int32)
+        return ps, pr, cs
+
+    def run_jointed(self, n_steps, F, slip=None, joint_velocity=None, gamma=1.0, schedule=None, cycle_start=None, stride=0,
+                    on_error="stop", check_every=RUN_CHECK_DEFAULT, max_iter=50, rtol=1e-8):
+        """n_steps steps of step_jointed in ONE call (rbl_ensemble_run_jointed): the joint table, F, slip and joint_velocity go to
+        the device once, the motors' angles advance there, one read-back ends the run -> RunResult, with theta (R, n_joints) and
+        cycle_pos (R,) as the run leaves them, phi_sum / phi_mean (R, n_joints, 3) over the accepted steps (a motor's mean torque
+        is phi_mean of its lock rows) and, with stride > 0, the frames X, Q, accepted_at, frame_theta, frame_phi (the step's phi,
+        or the last accepted one) and frame_gap (joint_state's gaps at the committed configuration).
+        schedule = (phase_steps, phase_rates): a periodic, piecewise-constant motor schedule, phase k lasting phase_steps[k] steps
+        with the rates phase_rates[k] -- (n_phases, n_joints), or (n_phases, R, n_joints) for rates per replica; non-zero on motors
+        only --, evaluated on each replica's own position in the cycle, which starts at cycle_start (an integer or (R,); 0 when
+        None) and moves on when the replica commits.  cycle_start=res.cycle_pos continues a stroke.  schedule=None: the rates of
+        set_joint_rates, constant; set_joint_rates' rates are untouched by a schedule.  on_error and check_every as in run; a
+        stopped run raises RblError and leaves the partial result on self.last_run.  Joints off or never set: run(brownian=False)"""
+        modes = {"stop": RUN_STOP, "reject": RUN_REJECT}
+        if on_error not in modes:
+            _fail("on_error must be 'stop' or 'reject'; got %r" % (on_error,))
+        n_steps, stride, check_every = int(n_steps), int(stride), int(check_every)
+        if n_steps < 1:
+            _fail("n_steps must be >= 1; got %d" % n_steps)
+        if stride < 0 or check_every < 0:
+            _fail("stride and check_every must be >= 0; got %d and %d" % (stride, check_every))
+        if not 0.0 <= float(gamma) <= 1.0:
+            _fail("gamma must lie in [0, 1]; got %r" % (gamma,))
+        F, s = self._forces(F), self._slip(slip)
+        jv = self._joint_rows_in("joint_velocity", joint_velocity, self._joints_on())
+        ps, pr, cs = self._schedule(schedule, cycle_start)
+        self.last_run = None
+        res, rc = self.ctx.ensemble_run_jointed(n_steps, F, slip=s, joint_velocity=jv, gamma=gamma, phase_steps=ps, phase_rates=pr,
+                                                cycle_start=cs, stride=stride, on_error=modes[on_error], check_every=check_every,
+                                                max_iter=max_iter, rtol=rtol)
+        self.last_run = res
+        if rc != 0:
+            raise RblError(res.error)
+        return res
+
     def joint_state(self, phi=True):
         """-> (gap (R, n_joints, 3) at the current configurations, phi (R, n_joints, 3) of the last jointed solve or step,
         theta (R, n_joints)).  phi=False leaves phi out (None): the query then also serves before any jointed solve"""
@@ -450,7 +521,7 @@ class Ensemble:
         the drift and the dense Brownian root sum every pair over images = (nx, ny) periodic images on either side of its nearest
         one (1 <= n <= 16 on a periodic axis), a blob's own images included, and the pair forces use the minimum image.  Needs
         the wall; L must exceed 4a.  Coordinates stay unwrapped.  Every step, solve and run takes the cell; solve_jointed,
-        step_jointed and joint_state are refused (RblError, "periodic") while it is on.  on=False stores it switched off."""
+        step_jointed, run_jointed and joint_state are refused (RblError, "periodic") while it is on.  on=False stores it switched off."""
         Lx, Ly, nx, ny = periodic_args("set_cell", Lx, Ly, images)
         self.ctx.ensemble_set_periodic(Lx, Ly, images=(nx, ny), on=bool(on))
 
