@@ -161,7 +161,6 @@ static const RblBufRow kDevBufs[] = {
     {&rbl_ctx::d_jtw, RBL_BUF_SCRATCH},           // jointed solve's vectors: reserved once, at the start of each section 9 entry point
     {&rbl_ctx::d_jtphi, RBL_BUF_PERSIST},         // joint forces of the last jointed solve (jt_phi_valid)
     {&rbl_ctx::d_ens_jt, RBL_BUF_PERSIST},        // an ensemble's joint table with every replica's angles and rates (ens_jt_valid)
-    {&rbl_ctx::d_ens_jtw, RBL_BUF_SCRATCH},       // jointed ensemble solve: reserved once, at the start of each jointed section 5 entry point
 };
 
 // the poison pattern, on the context's stream; nothing while the stream is being captured into a graph (a capture may not

@@ -45,8 +45,8 @@
 //   k_ens_commit              per replica, a second launch (so `stopped` is final without any wait between workgroups): commit, or
 //                             q^n copied into the new buffer; counters, sums over accepted steps, the frame
 // The host swaps the two configuration buffers after every step without a synchronisation and reads back once at the end.
-// With hard joints (rbl_ensemble_run_jointed): the same loop around the jointed step (ens_jt_enqueue, the enqueueing part of
-// rbl_ensemble_step_jointed), and one more small launch per step after the commit:
+// With hard joints (rbl_ensemble_run_jointed): the same loop around the jointed step (ens_enqueue_det with an EnsJtStep, the
+// enqueueing part of rbl_ensemble_step_jointed), and one more small launch per step after the commit:
 //   k_ens_jt_run              per replica and joint: theta += rate dt where the replica committed, its position in the motor
 //                             schedule, the sum of phi, the next step's rates into the joint table; the frame's theta and phi
 // (k_ens_jt_rates before the first step; k_ens_jt_geom for the gaps of a recording step).
@@ -134,15 +134,16 @@ __device__ void ens_kinv_body(const double *R, const double *cfg, int nbl, const
   for (int p = 0; p < 3; ++p) out[3 + p] = (S[3 * p] * f[3] + S[3 * p + 1] * f[4]) + S[3 * p + 2] * f[5];
 }
 
-// right-hand side of the deterministic step: [slip (or 0) ; -(F - FT)] per replica (FT: the model's K^T f_phys, or NULL)
-__global__ __launch_bounds__(ET) void k_ens_rhs_det(int R, int n3, int nb6, const double *__restrict__ slip,
-                                                    const double *__restrict__ F, const double *__restrict__ FT,
-                                                    double *__restrict__ rhs)
+// right-hand side of the deterministic step: [slip (or 0) ; -(F - FT) ; jr (or 0)] per replica (FT: the model's K^T f_phys, or
+// NULL; the nj3 = 3 n_joints joint rows of the jointed step, none otherwise)
+__global__ __launch_bounds__(ET) void k_ens_rhs_jt(int R, int n3, int nb6, int nj3, const double *__restrict__ slip, const double *__restrict__ F,
+                                                   const double *__restrict__ FT, const double *__restrict__ jr, double *__restrict__ rhs)
 {
-  const long nsys = n3 + nb6, idx = (long)blockIdx.x * ET + threadIdx.x;
+  const long nsys = (long)n3 + nb6 + nj3, idx = (long)blockIdx.x * ET + threadIdx.x;
   if (idx >= (long)R * nsys) return;
   const long r = idx / nsys, e = idx - r * nsys;
   if (e < n3) { rhs[idx] = slip ? slip[r * n3 + e] : 0.0; return; }
+  if (e >= n3 + nb6) { rhs[idx] = jr ? jr[r * nj3 + e - n3 - nb6] : 0.0; return; }
   double f = F[r * nb6 + e - n3];
   if (FT) f = 1.0 * f + -1.0 * FT[r * nb6 + e - n3];                 // F_body - K^T f_phys (include/rbl.h section 4)
   rhs[idx] = -1.0 * f + 0.0;                                           // Force *= -1 (:972)
@@ -458,19 +459,21 @@ struct Carve {
 
 struct EnsWork {
   double *lever, *pos, *F, *FT, *slip, *W, *Lm, *Linv, *MW, *dq, *Xh, *Qh, *rhs, *x, *gm, *e;
+  double *jr;                                // the jointed step: the joint rows the caller gave (joint_rhs / joint_velocity), 3 n_joints per replica
   void *ia;
   // read-back block: residuals | iterations | error word per replica | one error word for the batch
   double *resid; int *iters; unsigned *rerr, *gerr;
   size_t rb_bytes;
   // prescribed bodies: U and F of the masked solve follow the read-back block (rb_mx_bytes reaches their end) and stand in front
-  // of x in one piece [U | F | x], as rbl_launch_gmres_small_ens_mixed wants them; body_in is uploaded where F_body goes (F)
+  // of x in one piece [U | F | x], as the masked rbl_launch_gmres_small_ens wants them; body_in is uploaded where F_body goes (F)
   double *U, *Fo; unsigned char *mask;
   size_t rb_mx_bytes;
 };
 
-EnsWork ens_carve(void *base, int R, int Nb, int nbl, int max_iter, size_t *bytes)
+// nj: the joints of a jointed solve, whose rhs, x and solver workspace hold 3 nj more per replica (0: the sizes of the unjointed one)
+EnsWork ens_carve(void *base, int R, int Nb, int nbl, int max_iter, int nj, size_t *bytes)
 {
-  const size_t N = (size_t)Nb * nbl, n3 = 3 * N, nb6 = 6 * (size_t)Nb, nsys = n3 + nb6, Rz = (size_t)R;
+  const size_t N = (size_t)Nb * nbl, n3 = 3 * N, nb6 = 6 * (size_t)Nb, nsys = n3 + nb6 + 3 * (size_t)nj, Rz = (size_t)R;
   Carve C{(char *)base};
   EnsWork w;
   w.resid = C.take<double>(Rz);                        // the read-back block first, contiguous
@@ -490,7 +493,8 @@ EnsWork ens_carve(void *base, int R, int Nb, int nbl, int max_iter, size_t *byte
   w.dq = C.take<double>(Rz * nb6); w.Xh = C.take<double>(Rz * 3 * Nb); w.Qh = C.take<double>(Rz * 4 * Nb);
   w.rhs = C.take<double>(Rz * nsys);
   w.mask = C.take<unsigned char>(Rz * nb6);             // room for one entry per velocity component (whole bodies use Rz * Nb of it)
-  w.gm = C.take<double>(Rz * rbl_gmres_small_work_doubles(nbl, Nb, max_iter));
+  w.gm = C.take<double>(Rz * rbl_gmres_small_work_doubles(nbl, Nb, max_iter, nj));
+  w.jr = C.take<double>(Rz * 3 * (size_t)nj);
   w.e = C.take<double>(Rz * N);
   w.ia = C.take<char>(ia_batch_bytes(Nb, nbl, R));
   *bytes = C.off;
@@ -501,7 +505,27 @@ EnsWork ens_carve(void *base, int R, int Nb, int nbl, int max_iter, size_t *byte
 // and the query before ens_ready touches the device; without an ensemble there is nothing to check (ens_ready says so)
 int ens_flow_check(rbl_ctx *c) { return c->ens_R ? flow_check(c, c->ens_Nb) : RBL_OK; }
 
-int ens_fail_state(rbl_ctx *c) { return rbl_fail(c, RBL_ERR_STATE, "ensemble: no ensemble configuration (rbl_ensemble_set_config)"); }
+// pre: the caller's name with ": " behind it, or nothing
+int ens_fail_state(rbl_ctx *c, const std::string &pre = "")
+{
+  return rbl_fail(c, RBL_ERR_STATE, pre + "ensemble: no ensemble configuration (rbl_ensemble_set_config)");
+}
+
+std::string ens_beyond(const std::string &pre = "")
+{
+  return pre + "ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)";
+}
+
+// the refusals that look at the context's state alone, before any device work: a communicator, no ensemble, a structure changed
+// since.  comm_last: ens_ready's order, which looks for the ensemble first
+int ens_state_check(rbl_ctx *c, const std::string &pre, bool comm_last = false)
+{
+  auto comm = [&] { return rbl_fail(c, RBL_ERR_ARG, pre + "ensemble: not on a context with a communicator (run one ensemble per process)"); };
+  if (comm_on(c) && !comm_last) return comm();
+  if (!c->ens_R) return ens_fail_state(c, pre);
+  if (c->S.N_blb != c->ens_Nblb) return rbl_fail(c, RBL_ERR_STATE, pre + "ensemble: the structure changed since rbl_ensemble_set_config");
+  return comm_on(c) ? comm() : RBL_OK;
+}
 
 // the ensemble's periodic cell (rbl_ensemble_set_periodic; include/rbl.h section 5): on, and as the one-workgroup kernels take it
 bool ens_cell_on(const rbl_ctx *c) { return c->ens_per_on; }
@@ -522,9 +546,7 @@ double *ens_cfg(rbl_ctx *c) { return ens_X(c, 2); }
 int ens_ready(rbl_ctx *c)
 {
   int rc = need_params(c); if (rc) return rc;
-  if (!c->ens_R) return ens_fail_state(c);
-  if (c->S.N_blb != c->ens_Nblb) return rbl_fail(c, RBL_ERR_STATE, "ensemble: the structure changed since rbl_ensemble_set_config");
-  if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, "ensemble: not on a context with a communicator (run one ensemble per process)");
+  if ((rc = ens_state_check(c, "", true))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (c->ens_cfg_host != c->S.ref_cfg) {
     if ((rc = copy_h2d(c, ens_cfg(c), c->S.ref_cfg.data(), sizeof(double) * c->S.ref_cfg.size()))) return rc;
@@ -563,6 +585,29 @@ int ens_finish(rbl_ctx *c, const EnsWork &w, int R, int *iters, double *resid, b
   return RBL_OK;
 }
 
+// ens_finish of a one-step call that returns pieces of the solution: x of every replica (3 N + 6 N_bod + nj3 each) is read back
+// in front of it and cut into whichever of lambda, U and phi (the nj3 joint rows) were asked for once the step has succeeded
+int ens_finish_x(rbl_ctx *c, const EnsWork &w, size_t nj3, int *iters, double *resid, bool commit, double *lambda, double *U, double *phi,
+                 double *U_mx = nullptr, double *F_mx = nullptr)
+{
+  const int R = c->ens_R;
+  const size_t n3 = (size_t)3 * c->ens_Nb * c->S.N_blb, nb6 = (size_t)6 * c->ens_Nb, nsys = n3 + nb6 + nj3;
+  std::vector<double> x;
+  int rc;
+  if (lambda || U || phi) {
+    x.resize((size_t)R * nsys);
+    if ((rc = copy_d2h(c, x.data(), w.x, sizeof(double) * x.size()))) return rc;
+  }
+  if ((rc = ens_finish(c, w, R, iters, resid, commit, U_mx, F_mx))) return rc;
+  for (int r = 0; r < R && !x.empty(); ++r) {
+    const double *xr = x.data() + (size_t)r * nsys;
+    if (lambda) std::memcpy(lambda + (size_t)r * n3, xr, sizeof(double) * n3);
+    if (U) std::memcpy(U + (size_t)r * nb6, xr + n3, sizeof(double) * nb6);
+    if (phi) std::memcpy(phi + (size_t)r * nj3, xr + n3 + nb6, sizeof(double) * nj3);
+  }
+  return RBL_OK;
+}
+
 // upload F (R 6 N_bod) and slip (R n3 or NULL), clear the read-back block, evaluate the force model at q^n when it is on and
 // the caller wants its loads (model): *FT -> K^T f_phys of every replica (NULL otherwise).  The flow model (include/rbl.h
 // section 8) goes the same way: one launch adds its term at q^n to every replica's slip.  *SL -> the slip the right-hand side
@@ -595,12 +640,17 @@ int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *
   return RBL_OK;
 }
 
-int ens_work(rbl_ctx *c, int max_iter, EnsWork *w)
+// hard joints switched on (include/rbl.h section 9's set, shared by the replicas)
+bool ens_jt_active(const rbl_ctx *c) { return c->jt_on && c->jt_n > 0; }
+
+// nj < 0: the joints of the active set, none when they are off
+int ens_work(rbl_ctx *c, int max_iter, EnsWork *w, int nj = -1)
 {
+  if (nj < 0) nj = ens_jt_active(c) ? c->jt_n : 0;
   size_t bytes = 0;
-  ens_carve(nullptr, c->ens_R, c->ens_Nb, c->S.N_blb, max_iter, &bytes);
+  ens_carve(nullptr, c->ens_R, c->ens_Nb, c->S.N_blb, max_iter, nj, &bytes);
   int rc = rbl_dev_reserve(c, c->d_ens_w, bytes); if (rc) return rc;
-  *w = ens_carve(c->d_ens_w.p, c->ens_R, c->ens_Nb, c->S.N_blb, max_iter, &bytes);
+  *w = ens_carve(c->d_ens_w.p, c->ens_R, c->ens_Nb, c->S.N_blb, max_iter, nj, &bytes);
   return RBL_OK;
 }
 
@@ -608,30 +658,32 @@ int ens_check_solver(rbl_ctx *c, int max_iter)
 {
   if (max_iter < 1) return rbl_fail(c, RBL_ERR_ARG, "ensemble step: max_iter must be >= 1");
   if (!rbl_gmres_small_fits(c->S.N_blb, c->ens_Nb, max_iter, false))
-    return rbl_fail(c, RBL_ERR_SIZE, "ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)");
+    return rbl_fail(c, RBL_ERR_SIZE, ens_beyond());
   return RBL_OK;
 }
 
-// mixed: the masked solve (w.mask, body_in in w.F); the update then reads the U it wrote (a prescribed body: dt U_p exactly).
-// evolve = false: the solve alone
+// the jointed variant of a step (hard joints, further down): the joint table on the device, coef = -gamma / dt of a time step,
+// whether w.jr holds joint rows the caller gave, and the caller's name for a refusal
+struct EnsJtStep { const char *who; RblEnsJoints T; double coef; bool have_jr; };
+
+// The solve of every replica at (Xs, Qs) and the update from q^n: the one place that launches the one-kernel solver.  The variant
+// is chosen once -- mixed: the masked solve (w.mask, body_in in w.F); the update then reads the U it wrote (a prescribed body:
+// dt U_p exactly); the ensemble's cell on (the wall is: the callers' periodic_use_check): k_gmres_small_per; jt: the jointed
+// solve, rhs and x with the joint rows behind.  evolve = false: the solve alone
 int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const double *Qs, int max_iter, double rtol, bool mixed = false,
-                     bool evolve = true, bool record = true, int per = 1)
+                     bool evolve = true, bool record = true, int per = 1, const EnsJtStep *jt = nullptr)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
-  const long n3 = 3L * Nb * nbl, nsys = n3 + 6L * Nb;
+  const long n3 = 3L * Nb * nbl, nsys = n3 + 6L * Nb + (jt ? 3L * jt->T.n : 0L);
   const RblParams P = rbl_make_params(c->S.a, c->S.eta);
-  int rc;
-  if (ens_cell_on(c))                                    // the cell on (the wall is: the callers' periodic_use_check): k_gmres_small_per
-    rc = mixed ? rbl_launch_gmres_small_ens_mixed_per(c->stream, P, ens_cell(c), Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.U, max_iter, rtol,
-                                                      w.gm, w.iters, w.resid, w.rerr, w.mask, w.F, per)
-               : rbl_launch_gmres_small_ens_per(c->stream, P, ens_cell(c), Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.x, max_iter, rtol, w.gm,
-                                                w.iters, w.resid, w.rerr);
-  else
-    rc = mixed ? rbl_launch_gmres_small_ens_mixed(c->stream, P, c->S.wall, Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.U, max_iter, rtol,
-                                                  w.gm, w.iters, w.resid, w.rerr, w.mask, w.F, per)
-               : rbl_launch_gmres_small_ens(c->stream, P, c->S.wall, Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.x, max_iter, rtol, w.gm,
-                                            w.iters, w.resid, w.rerr);
-  if (rc) return rbl_fail(c, rc, "ensemble step: the one-kernel solver does not fit this device's LDS");
+  const RblSmallEns S = {Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.x, max_iter, rtol, w.gm, w.iters, w.resid, w.rerr};
+  const unsigned char *mask = mixed ? w.mask : nullptr;
+  int rc = jt               ? rbl_launch_gmres_small_ens_jt(c->stream, P, c->S.wall, S, jt->T, evolve ? 1 : 0, jt->coef)
+           : ens_cell_on(c) ? rbl_launch_gmres_small_ens_per(c->stream, P, ens_cell(c), S, mask, w.F, per)
+                            : rbl_launch_gmres_small_ens(c->stream, P, c->S.wall, S, mask, w.F, per);
+  if (rc)
+    return rbl_fail(c, rc, jt ? std::string(jt->who) + ": the one-kernel jointed solver does not fit this device's LDS"
+                              : std::string("ensemble step: the one-kernel solver does not fit this device's LDS"));
   if (!evolve) return RBL_OK;
   const int nbod = R * Nb;
   if (c->record_mom) c->ens_mom_R = 0;                   // valid once a step committed; a run (record = false) leaves nothing to read
@@ -655,11 +707,9 @@ int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const d
   const char *pn = per == 6 ? "prescribed6" : "prescribed";
   if (!prescribed || !body_in) return rbl_fail(c, RBL_ERR_ARG, w + ": " + pn + " or body_in is NULL");
   if (max_iter < 1 || !(rtol >= 0.0)) return rbl_fail(c, RBL_ERR_ARG, w + ": need max_iter >= 1 and rtol >= 0");
-  const std::string beyond = w + ": ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)";
+  const std::string beyond = ens_beyond(w + ": ");
   if (max_iter > 255) return rbl_fail(c, RBL_ERR_SIZE, beyond);
-  if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, w + ": ensemble: not on a context with a communicator (run one ensemble per process)");
-  if (!c->ens_R) return rbl_fail(c, RBL_ERR_STATE, w + ": ensemble: no ensemble configuration (rbl_ensemble_set_config)");
-  if (c->S.N_blb != c->ens_Nblb) return rbl_fail(c, RBL_ERR_STATE, w + ": ensemble: the structure changed since rbl_ensemble_set_config");
+  if ((rc = ens_state_check(c, w + ": "))) return rc;
   const size_t nent = (size_t)c->ens_R * c->ens_Nb * (size_t)per;
   for (size_t g = 0; g < nent; ++g)
     if (prescribed[g] > 1)
@@ -694,7 +744,8 @@ int ens_upload_mask(rbl_ctx *c, const EnsWork &w, const uint8_t *prescribed, int
 }
 
 // everything the deterministic step enqueues, from the uploads to the update: the one-step calls and the run share it
-int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_iter, double rtol, bool move)
+// jt: the jointed solve or step (move: c of a time step is formed in the solver from the gaps)
+int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_iter, double rtol, bool move, const EnsJtStep *jt = nullptr)
 {
   const bool mixed = in.prescribed != nullptr;
   const double *FT, *SL;
@@ -703,11 +754,12 @@ int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_i
   if (mixed && !in.resident && (rc = ens_upload_mask(c, w, in.prescribed, in.per))) return rc;
   if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, move, in.resident, in.accepted))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb;
-  const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb;
-  const long tot = (long)R * (n3 + nb6);
-  hipLaunchKernelGGL(k_ens_rhs_det, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, n3, nb6, SL,
-                     (const double *)w.F, FT, w.rhs);
-  return ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, mixed, move, !in.resident, in.per);
+  const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb, nj3 = jt ? 3 * jt->T.n : 0;
+  const long tot = (long)R * (n3 + nb6 + nj3);
+  hipLaunchKernelGGL(k_ens_rhs_jt, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, n3, nb6, nj3, SL,
+                     (const double *)w.F, FT, jt && jt->have_jr ? (const double *)w.jr : nullptr, w.rhs);
+  // a jointed step records its moments in a run too, as it always did
+  return ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, mixed, move, jt || !in.resident, in.per, jt);
 }
 
 int ens_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, int max_iter, double rtol, bool move,
@@ -720,19 +772,10 @@ int ens_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, co
   EnsStepIn in;
   in.prescribed = prescribed; in.per = per; in.F_body = F_body; in.slip = slip;
   if ((rc = ens_enqueue_det(c, w, in, max_iter, rtol, move))) return rc;
-  const int R = c->ens_R, Nb = c->ens_Nb;
-  const int n3 = 3 * Nb * c->S.N_blb, nb6 = 6 * Nb;
-  std::vector<double> x;
-  if (lambda) {                                          // the blob forces: the top of every replica's solution
-    x.resize((size_t)R * (n3 + nb6));
-    if ((rc = copy_d2h(c, x.data(), w.x, sizeof(double) * x.size()))) return rc;
-  }
   std::vector<double> Ft;
-  if (mixed && !F) { Ft.resize((size_t)R * nb6); F = Ft.data(); }         // the masked read-back is chosen by U or F
-  if ((rc = ens_finish(c, w, R, iters, resid, move, mixed ? U : nullptr, mixed ? F : nullptr))) return rc;
-  if (lambda)
-    for (int r = 0; r < R; ++r) std::memcpy(lambda + (size_t)r * n3, x.data() + (size_t)r * (n3 + nb6), sizeof(double) * n3);
-  return RBL_OK;
+  if (mixed && !F) { Ft.resize((size_t)c->ens_R * 6 * c->ens_Nb); F = Ft.data(); }   // the masked read-back is chosen by U or F
+  // lambda, the blob forces: the top of every replica's solution; U (unmasked: rbl_ensemble_solve_jointed with the joints off): below it
+  return ens_finish_x(c, w, 0, iters, resid, move, lambda, mixed ? nullptr : U, nullptr, mixed ? U : nullptr, mixed ? F : nullptr);
 }
 
 // the stochastic midpoint step of every replica (checks done by the caller).  prescribed == NULL: rbl_ensemble_step_brownian;
@@ -776,23 +819,21 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
                        (const unsigned char *)w.mask, in.per, (const double *)w.F, (const double *)w.MW, 0.5 * S.dt * c1, 0.5 * S.dt, w.dq,
                        w.Xh, w.Qh);
   const size_t lds = rfd_lds_bytes(Nb, nbl);
-  const void *fn = per_cell ? (const void *)k_ens_rfd_rhs<true, true> : S.wall ? (const void *)k_ens_rfd_rhs<true> : (const void *)k_ens_rfd_rhs<false>;
-  if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return rbl_fail(c, RBL_ERR_SIZE, "ensemble: the RFD product does not fit this device's LDS");
-  }
-  if (per_cell)
-    hipLaunchKernelGGL((k_ens_rfd_rhs<true, true>), dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
+  // the instantiation (the cell's, the wall's, the open one) is chosen once; its last argument is the cell or its empty stand-in
+  auto rfd_rhs = [&](auto kern, auto cell) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+      (void)hipGetLastError();
+      return rbl_fail(c, RBL_ERR_SIZE, "ensemble: the RFD product does not fit this device's LDS");
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
                        (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
-                       SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr, ens_cell(c));
-  else if (S.wall)
-    hipLaunchKernelGGL(k_ens_rfd_rhs<true>, dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
-                       (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
-                       SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr, EnsNoCell{});
-  else
-    hipLaunchKernelGGL(k_ens_rfd_rhs<false>, dim3((unsigned)R), dim3(RBL_SG_THREADS), lds, c->stream, P, Nb, nbl, X, Q, ens_cfg(c),
-                       (const double *)w.dq, delta, (const double *)w.W, (const double *)w.MW, (const double *)w.Lm,
-                       SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr, EnsNoCell{});
+                       SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr, cell);
+    return (int)RBL_OK;
+  };
+  if ((rc = per_cell ? rfd_rhs(k_ens_rfd_rhs<true, true>, ens_cell(c))
+            : S.wall ? rfd_rhs(k_ens_rfd_rhs<true>, EnsNoCell{})
+                     : rfd_rhs(k_ens_rfd_rhs<false>, EnsNoCell{})))
+    return rc;
   // saddle solve at q^{n+1/2}, update from q^n
   return ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol, mixed, true, !in.resident, in.per);
 }
@@ -811,149 +852,6 @@ int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, con
   std::vector<double> Ft;
   if (mixed && !F_out) { Ft.resize((size_t)R * 6 * Nb); F_out = Ft.data(); }   // the masked read-back is chosen by F
   return ens_finish(c, w, R, iters, resid, true, nullptr, mixed ? F_out : nullptr);
-}
-
-// the run's own device buffer: [slip copy] | read-back block (status, counters, sums) | verdict words, last loads | frames
-struct EnsRunBuf {
-  double *slip;
-  EnsRunStatus *st; int *accepted, *rejected; unsigned *first_flags; long long *iters_sum; double *resid_max, *F_sum;
-  size_t rb_off, rb_bytes;                 // the read-back block: from st to the end of F_sum
-  unsigned *vflag; double *F_last;
-  double *fX, *fQ; int *fA; double *fF;
-};
-
-EnsRunBuf ens_run_carve(void *base, int R, int Nb, int nbl, bool slip, bool mixed, size_t n_frames, size_t *bytes)
-{
-  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, n3 = (size_t)3 * Nb * nbl;
-  Carve C{(char *)base};
-  EnsRunBuf b;
-  b.slip = C.take<double>(slip ? Rz * n3 : 0);
-  b.rb_off = C.off;
-  b.st = C.take<EnsRunStatus>(1);
-  b.accepted = C.take<int>(Rz); b.rejected = C.take<int>(Rz); b.first_flags = C.take<unsigned>(Rz);
-  b.iters_sum = C.take<long long>(Rz); b.resid_max = C.take<double>(Rz);
-  b.F_sum = C.take<double>(mixed ? Rz * nb6 : 0);
-  b.rb_bytes = C.off - b.rb_off;
-  b.vflag = C.take<unsigned>(Rz);
-  b.F_last = C.take<double>(mixed ? Rz * nb6 : 0);
-  b.fX = C.take<double>(n_frames * Rz * 3 * Nb); b.fQ = C.take<double>(n_frames * Rz * 4 * Nb);
-  b.fA = C.take<int>(n_frames * Rz);
-  b.fF = C.take<double>(mixed ? n_frames * Rz * nb6 : 0);
-  *bytes = C.off;
-  return b;
-}
-
-// what a run with hard joints (rbl_ensemble_run_jointed) adds to the loop below; the hard-joints part of this file defines them
-struct EnsJtRun;
-size_t ens_jt_run_bytes(const rbl_ctx *c, const EnsJtRun &J, size_t n_frames);
-int ens_jt_run_begin(rbl_ctx *c, EnsJtRun &J, void *base, size_t n_frames, int max_iter, const EnsRunBuf &b);
-int ens_jt_run_enqueue(rbl_ctx *c, const EnsWork &w, EnsJtRun &J, const EnsStepIn &in, int max_iter, double rtol);
-void ens_jt_run_after(rbl_ctx *c, EnsJtRun &J, long frame);
-int ens_jt_run_end(rbl_ctx *c, EnsJtRun &J, size_t nfr, bool stopped);
-
-// n_steps steps of every replica (checks and ens_ready done by the caller; per: the mask's entries per body): the inputs go up
-// once, every step is the one-step calls' enqueue sequence followed by the verdict and the commit, the buffers flip on the host,
-// ONE read-back ends it.  J (rbl_ensemble_run_jointed): the step is the jointed one and one launch for the joints follows the commit
-int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_out *out, EnsJtRun *J = nullptr)
-{
-  const RblBodyState &S = c->S;
-  const bool mixed = o.prescribed != nullptr, reject = o.on_error == RBL_RUN_REJECT;
-  const int R = c->ens_R, Nb = c->ens_Nb, nbl = S.N_blb;
-  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, n3 = (size_t)3 * Nb * nbl;
-  const size_t n_frames = o.stride > 0 ? (size_t)(o.n_steps / o.stride) : 0;
-  int rc;
-  EnsWork w;
-  if ((rc = ens_work(c, o.max_iter, &w))) return rc;
-  size_t bytes = 0;
-  ens_run_carve(nullptr, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
-  if ((rc = rbl_dev_reserve(c, c->d_ens_run, bytes + (J ? ens_jt_run_bytes(c, *J, n_frames) : 0)))) return rc;   // the joints' part behind
-  const EnsRunBuf b = ens_run_carve(c->d_ens_run.p, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
-  // the uploads, once
-  if (mixed && (rc = ens_upload_mask(c, w, o.prescribed, per))) return rc;
-  if ((rc = copy_h2d(c, w.F, mixed ? o.body_in : o.F_body, sizeof(double) * nb6 * Rz))) return rc;
-  if (o.slip && (rc = copy_h2d(c, b.slip, o.slip, sizeof(double) * n3 * Rz))) return rc;
-  RBL_HIP(c, hipMemsetAsync(b.st, 0, b.rb_bytes, c->stream));
-  if (mixed) RBL_HIP(c, hipMemsetAsync(b.F_last, 0, sizeof(double) * nb6 * Rz, c->stream));
-  if (J && (rc = ens_jt_run_begin(c, *J, (char *)c->d_ens_run.p + bytes, n_frames, o.max_iter, b))) return rc;
-  EnsStepIn in;
-  in.prescribed = o.prescribed; in.per = per;
-  in.slip = o.slip ? b.slip : nullptr; in.resident = true; in.chol_err = 1;
-  in.accepted = b.accepted;
-  EnsRunStatus hs = {0, 0, 0u, 0};
-  int enq = 0;
-  for (int n = 0; n < o.n_steps; ++n) {
-    rc = J          ? ens_jt_run_enqueue(c, w, *J, in, o.max_iter, o.rtol)
-         : brownian ? ens_enqueue_bd(c, w, in, o.seed + (uint64_t)n, o.split_rand, o.delta, o.max_iter, o.rtol)
-                    : ens_enqueue_det(c, w, in, o.max_iter, o.rtol, true);
-    if (rc) return rc;
-    const int cur = c->ens_cur;
-    if (S.wall)
-      hipLaunchKernelGGL(k_ens_verdict<true>, dim3((unsigned)R), dim3(ET), 0, c->stream, Nb, nbl, n, reject ? 1 : 0,
-                         (const double *)ens_X(c, cur ^ 1), (const double *)ens_Q(c, cur ^ 1), (const double *)ens_cfg(c),
-                         (const unsigned *)w.rerr, (const unsigned *)w.gerr, b.vflag, b.st);
-    else
-      hipLaunchKernelGGL(k_ens_verdict<false>, dim3((unsigned)R), dim3(ET), 0, c->stream, Nb, nbl, n, reject ? 1 : 0,
-                         (const double *)ens_X(c, cur ^ 1), (const double *)ens_Q(c, cur ^ 1), (const double *)ens_cfg(c),
-                         (const unsigned *)w.rerr, (const unsigned *)w.gerr, b.vflag, b.st);
-    EnsRunDev D;
-    D.Xo = ens_X(c, cur); D.Qo = ens_Q(c, cur); D.Xn = ens_X(c, cur ^ 1); D.Qn = ens_Q(c, cur ^ 1);
-    D.vflag = b.vflag; D.gerr = w.gerr; D.iters = w.iters; D.resid = w.resid; D.Fo = mixed ? w.Fo : nullptr; D.st = b.st;
-    D.accepted = b.accepted; D.rejected = b.rejected; D.first_flags = b.first_flags; D.iters_sum = b.iters_sum;
-    D.resid_max = b.resid_max; D.F_sum = b.F_sum; D.F_last = b.F_last;
-    D.fX = D.fQ = D.fF = nullptr; D.fA = nullptr;
-    if (o.stride > 0 && (n + 1) % o.stride == 0) {
-      const size_t k = (size_t)((n + 1) / o.stride - 1);
-      D.fX = b.fX + k * Rz * 3 * Nb; D.fQ = b.fQ + k * Rz * 4 * Nb; D.fA = b.fA + k * Rz;
-      if (mixed) D.fF = b.fF + k * Rz * nb6;
-    }
-    hipLaunchKernelGGL(k_ens_commit, dim3((unsigned)R), dim3(ET), 0, c->stream, R, Nb, n, D);
-    c->ens_cur ^= 1;                                     // the new buffer holds every replica's configuration, moved or not
-    if (J) ens_jt_run_after(c, *J, D.fX ? (long)((n + 1) / o.stride - 1) : -1L);
-    ++enq;
-    if (o.check_every > 0 && enq % o.check_every == 0 && n + 1 < o.n_steps) {
-      if ((rc = read_back(c, &hs, b.st, sizeof(hs)))) return rc;
-      if (hs.stopped) break;
-    }
-  }
-  RBL_HIP(c, hipGetLastError());
-  // the one read-back: status, counters, sums; then the frames the run completed, straight into the caller's arrays
-  std::vector<char> h(b.rb_bytes);
-  if ((rc = copy_d2h(c, h.data(), b.st, b.rb_bytes))) return rc;
-  RBL_HIP(c, hipStreamSynchronize(c->stream));
-  auto at = [&](const void *p) { return h.data() + ((const char *)p - (const char *)b.st); };
-  std::memcpy(&hs, at(b.st), sizeof(hs));
-  const int *hacc = (const int *)at(b.accepted), *hrej = (const int *)at(b.rejected);
-  const unsigned *hff = (const unsigned *)at(b.first_flags);
-  if (out->accepted) std::memcpy(out->accepted, hacc, sizeof(int) * Rz);
-  if (out->rejected) std::memcpy(out->rejected, hrej, sizeof(int) * Rz);
-  if (out->first_flags) std::memcpy(out->first_flags, hff, sizeof(unsigned) * Rz);
-  if (out->first_status)
-    for (int r = 0; r < R; ++r) out->first_status[r] = hrej[r] ? rbl_flags_to_status(c, hff[r]) : RBL_OK;
-  if (out->iters_sum) std::memcpy(out->iters_sum, at(b.iters_sum), sizeof(int64_t) * Rz);
-  if (out->resid_max) std::memcpy(out->resid_max, at(b.resid_max), sizeof(double) * Rz);
-  if (mixed && out->F_sum) std::memcpy(out->F_sum, at(b.F_sum), sizeof(double) * nb6 * Rz);
-  const size_t nfr = o.stride > 0 ? (size_t)(enq / o.stride) : 0;   // frames of the steps that were enqueued (a polled stop: fewer)
-  if (nfr) {
-    if ((rc = copy_d2h(c, out->frame_X, b.fX, sizeof(double) * nfr * Rz * 3 * Nb))) return rc;
-    if ((rc = copy_d2h(c, out->frame_Q, b.fQ, sizeof(double) * nfr * Rz * 4 * Nb))) return rc;
-    if ((rc = copy_d2h(c, out->frame_accepted_at, b.fA, sizeof(int) * nfr * Rz))) return rc;
-    if (mixed && (rc = copy_d2h(c, out->frame_F, b.fF, sizeof(double) * nfr * Rz * nb6))) return rc;
-    RBL_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  if (J && (rc = ens_jt_run_end(c, *J, nfr, hs.stopped != 0))) return rc;
-  out->stopped_at = hs.stopped ? hs.stopped - 1 : -1;
-  out->steps_done = hs.stopped ? hs.stopped - 1 : o.n_steps;
-  out->stop_replica = hs.stopped && hs.stop_rep ? R - hs.stop_rep : -1;
-  if (!hs.stopped) return RBL_OK;
-  const std::string at_step = "ensemble_run step " + std::to_string(hs.stopped - 1);
-  if (hs.stop_rep) {
-    rc = rbl_flags_to_status(c, hff[R - hs.stop_rep]);
-    c->last_error = at_step + ", replica " + std::to_string(R - hs.stop_rep) + ": " + c->last_error;
-  } else {
-    rc = rbl_flags_to_status(c, hs.batch);
-    c->last_error = at_step + ": " + c->last_error;
-  }
-  return rc;
 }
 
 // ---- the entry points with a mask: one worker per operation, per decided by the exported function (1: whole bodies, who's plain
@@ -1006,8 +904,6 @@ int ens_mx_step_bd(rbl_ctx *c, const char *who, int per, const uint8_t *prescrib
 // The joint set is the context's (rbl_set_joints / rbl_set_joint_kinds), shared by the replicas; the motor angles and rates are
 // the replica's own and live here.  One launch of k_gmres_small_jt (rbl_small_joints.hip) solves every replica's jointed system.
 
-bool ens_jt_active(const rbl_ctx *c) { return c->jt_on && c->jt_n > 0; }
-
 // angles and rates of the stored set for the ensemble's R replicas of N_bod bodies: zeros, and the device table stale, when the
 // set, R or N_bod changed since they were made
 void ens_jt_sync(rbl_ctx *c)
@@ -1028,9 +924,7 @@ int ens_jt_check(rbl_ctx *c, const char *who, const double *F_body, int max_iter
   if (max_iter < 1 || max_iter > 255) return rbl_fail(c, RBL_ERR_ARG, w + ": max_iter must lie in 1 .. 255 (no restart)");
   if (!(rtol >= 0.0)) return rbl_fail(c, RBL_ERR_ARG, w + ": rtol must be >= 0");
   int rc = need_params(c); if (rc) return rc;
-  if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, w + ": ensemble: not on a context with a communicator (run one ensemble per process)");
-  if (!c->ens_R) return rbl_fail(c, RBL_ERR_STATE, w + ": ensemble: no ensemble configuration (rbl_ensemble_set_config)");
-  if (c->S.N_blb != c->ens_Nblb) return rbl_fail(c, RBL_ERR_STATE, w + ": ensemble: the structure changed since rbl_ensemble_set_config");
+  if ((rc = ens_state_check(c, w + ": "))) return rc;
   const bool on = ens_jt_active(c);
   if (on && c->jt_top >= c->ens_Nb)
     for (int j = 0; j < c->jt_n; ++j) {
@@ -1044,7 +938,7 @@ int ens_jt_check(rbl_ctx *c, const char *who, const double *F_body, int max_iter
                     rbl_gmres_small_fits(c->S.N_blb, c->ens_Nb, max_iter, false)
                         ? w + ": this shape fits the one-kernel solver without joints, but not with the LDS of " + std::to_string(c->jt_n) +
                               " joints (" + std::to_string(rbl_gmres_small_jt_lds_bytes(c->S.N_blb, c->ens_Nb, max_iter, c->jt_n)) + " of 153600 bytes)"
-                        : w + ": ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)");
+                        : ens_beyond(w + ": "));
   return RBL_OK;
 }
 
@@ -1090,120 +984,27 @@ int ens_jt_upload(rbl_ctx *c, RblEnsJoints *T)
   return RBL_OK;
 }
 
-// rhs of every replica: [slip (or 0) ; -(F - FT) ; jr (or 0)], k_ens_rhs_det with the joint rows behind
-__global__ __launch_bounds__(ET) void k_ens_rhs_jt(int R, int n3, int nb6, int nj3, const double *__restrict__ slip, const double *__restrict__ F,
-                                                   const double *__restrict__ FT, const double *__restrict__ jr, double *__restrict__ rhs)
-{
-  const long nsys = (long)n3 + nb6 + nj3, idx = (long)blockIdx.x * ET + threadIdx.x;
-  if (idx >= (long)R * nsys) return;
-  const long r = idx / nsys, e = idx - r * nsys;
-  if (e < n3) { rhs[idx] = slip ? slip[r * n3 + e] : 0.0; return; }
-  if (e >= n3 + nb6) { rhs[idx] = jr ? jr[r * nj3 + e - n3 - nb6] : 0.0; return; }
-  double f = F[r * nb6 + e - n3];
-  if (FT) f = 1.0 * f + -1.0 * FT[r * nb6 + e - n3];
-  rhs[idx] = -1.0 * f + 0.0;
-}
-
-// joints switched off or never set: the unjointed one-kernel solve on [slip ; -F] at the current configuration
-int ens_jt_plain_solve(rbl_ctx *c, const double *F_body, const double *slip, int max_iter, double rtol, double *lambda, double *U, int *iters,
-                       double *resid)
-{
-  EnsWork w;
-  int rc;
-  if ((rc = ens_work(c, max_iter, &w))) return rc;
-  EnsStepIn in;
-  in.F_body = F_body; in.slip = slip;
-  if ((rc = ens_enqueue_det(c, w, in, max_iter, rtol, false))) return rc;
-  const int R = c->ens_R;
-  const size_t n3 = (size_t)3 * c->ens_Nb * c->S.N_blb, nb6 = (size_t)6 * c->ens_Nb;
-  std::vector<double> x((size_t)R * (n3 + nb6));
-  if ((rc = copy_d2h(c, x.data(), w.x, sizeof(double) * x.size()))) return rc;
-  if ((rc = ens_finish(c, w, R, iters, resid, false))) return rc;
-  for (int r = 0; r < R; ++r) {
-    if (lambda) std::memcpy(lambda + (size_t)r * n3, x.data() + (size_t)r * (n3 + nb6), sizeof(double) * n3);
-    if (U) std::memcpy(U + (size_t)r * nb6, x.data() + (size_t)r * (n3 + nb6) + n3, sizeof(double) * nb6);
-  }
-  return RBL_OK;
-}
-
 // the jointed solve of every replica at the current configuration; move: a time step -- the force model's loads and the flow
 // model's slip at q^n (ens_begin), c formed in the kernel from the gaps (coef = -gamma / dt), k_ens_evolve, and on success the
-// commit and the motors' angles
-// the jointed solve's own vectors in d_ens_jtw: rhs | x (nsys per replica each) | the joint rows given (3 n_joints) | solver workspace
-struct EnsJtVec { double *rhs, *x, *djr, *gm; };
-
-int ens_jt_vectors(rbl_ctx *c, int max_iter, EnsJtVec *V)
-{
-  const int Nb = c->ens_Nb, nbl = c->S.N_blb, nj = c->jt_n;
-  const size_t nj3 = (size_t)3 * nj, nsys = (size_t)3 * Nb * nbl + (size_t)6 * Nb + nj3, Rz = (size_t)c->ens_R;
-  const size_t wd = rbl_gmres_small_jt_work_doubles(nbl, Nb, max_iter, nj);
-  int rc = rbl_dev_reserve(c, c->d_ens_jtw, sizeof(double) * Rz * (2 * nsys + nj3 + wd)); if (rc) return rc;
-  V->rhs = (double *)c->d_ens_jtw.p; V->x = V->rhs + Rz * nsys; V->djr = V->x + Rz * nsys; V->gm = V->djr + Rz * nj3;
-  return RBL_OK;
-}
-
-// everything the jointed solve or step enqueues, from ens_begin's uploads to the update: the one-step calls and the run
-// (rbl_ensemble_run_jointed, in.resident) share it.  have_jr: V.djr holds the joint rows the caller gave
-int ens_jt_enqueue(rbl_ctx *c, const char *who, const EnsWork &w, const RblEnsJoints &T, const EnsJtVec &V, const EnsStepIn &in, bool have_jr,
-                   bool move, double coef, int max_iter, double rtol)
-{
-  const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb, nj = c->jt_n;
-  const size_t n3 = (size_t)3 * Nb * nbl, nb6 = (size_t)6 * Nb, nj3 = (size_t)3 * nj, nsys = n3 + nb6 + nj3;
-  double *rhs = V.rhs, *x = V.x;
-  int rc;
-  const double *FT, *SL;
-  if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, move, in.resident, in.accepted))) return rc;
-  const long tot = (long)R * (long)nsys;
-  hipLaunchKernelGGL(k_ens_rhs_jt, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, (int)n3, (int)nb6, (int)nj3, SL,
-                     (const double *)w.F, FT, have_jr ? (const double *)V.djr : nullptr, rhs);
-  const RblParams P = rbl_make_params(c->S.a, c->S.eta);
-  const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
-  rc = rbl_launch_gmres_small_ens_jt(c->stream, P, c->S.wall, X, Q, ens_cfg(c), nbl, Nb, R, rhs, x, max_iter, rtol, V.gm, w.iters, w.resid,
-                                     w.rerr, T, move ? 1 : 0, coef);
-  if (rc) return rbl_fail(c, rc, std::string(who) + ": the one-kernel jointed solver does not fit this device's LDS");
-  if (move) {
-    const int nbod = R * Nb;
-    if (c->record_mom) {                                 // RBL_OPT_RECORD_MOMENTS, as ens_solve_evolve
-      c->ens_mom_R = 0;
-      if ((rc = rbl_dev_reserve(c, c->d_ens_mom, sizeof(double) * 9 * (size_t)nbod))) return rc;
-      flow_launch_moments(c, nullptr, Q, ens_cfg(c), x, Nb, nbod, (int64_t)nsys, (double *)c->d_ens_mom.p);
-    }
-    hipLaunchKernelGGL(k_ens_evolve, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, (long)nsys, (long)n3, c->S.dt,
-                       (const double *)x, X, Q, ens_X(c, c->ens_cur ^ 1), ens_Q(c, c->ens_cur ^ 1), w.rerr);
-  }
-  return RBL_OK;
-}
-
+// commit and the motors' angles.  What it enqueues is ens_enqueue_det's sequence with the jointed variant (EnsJtStep)
 int ens_jt_solve(rbl_ctx *c, const char *who, const double *F_body, const double *slip, const double *jr, bool move, double coef, int max_iter,
                  double rtol, double *lambda, double *U, double *phi, int *iters, double *resid)
 {
-  const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb, nj = c->jt_n;
-  const size_t n3 = (size_t)3 * Nb * nbl, nb6 = (size_t)6 * Nb, nj3 = (size_t)3 * nj, nsys = n3 + nb6 + nj3, Rz = (size_t)R;
+  const size_t nj3 = (size_t)3 * c->jt_n, Rz = (size_t)c->ens_R;
   c->ens_jt_phi_valid = false;
   EnsWork w;
   int rc;
   if ((rc = ens_work(c, max_iter, &w))) return rc;
-  RblEnsJoints T;
-  if ((rc = ens_jt_upload(c, &T))) return rc;
-  EnsJtVec V;
-  if ((rc = ens_jt_vectors(c, max_iter, &V))) return rc;
-  if (jr && (rc = copy_h2d(c, V.djr, jr, sizeof(double) * Rz * nj3))) return rc;
+  EnsJtStep jt = {who, {}, coef, jr != nullptr};
+  if ((rc = ens_jt_upload(c, &jt.T))) return rc;
+  if (jr && (rc = copy_h2d(c, w.jr, jr, sizeof(double) * Rz * nj3))) return rc;
   EnsStepIn in;
   in.F_body = F_body; in.slip = slip;
-  if ((rc = ens_jt_enqueue(c, who, w, T, V, in, jr != nullptr, move, coef, max_iter, rtol))) return rc;
-  const double *x = V.x;
-  std::vector<double> hx(Rz * nsys);
-  if ((rc = copy_d2h(c, hx.data(), x, sizeof(double) * hx.size()))) return rc;
+  if ((rc = ens_enqueue_det(c, w, in, max_iter, rtol, move, &jt))) return rc;
   // a redundant joint set: RBL_FLAG_REDUNDANT in the replica's word, which ens_finish turns into RBL_ERR_NOT_SPD with the replica named
-  if ((rc = ens_finish(c, w, R, iters, resid, move))) return rc;
   c->ens_jt_phi.resize(Rz * nj3);
-  for (int r = 0; r < R; ++r) {
-    const double *xr = hx.data() + (size_t)r * nsys;
-    if (lambda) std::memcpy(lambda + (size_t)r * n3, xr, sizeof(double) * n3);
-    if (U) std::memcpy(U + (size_t)r * nb6, xr + n3, sizeof(double) * nb6);
-    if (phi) std::memcpy(phi + (size_t)r * nj3, xr + n3 + nb6, sizeof(double) * nj3);
-    std::memcpy(c->ens_jt_phi.data() + (size_t)r * nj3, xr + n3 + nb6, sizeof(double) * nj3);
-  }
+  if ((rc = ens_finish_x(c, w, nj3, iters, resid, move, lambda, U, c->ens_jt_phi.data()))) return rc;
+  if (phi) std::memcpy(phi, c->ens_jt_phi.data(), sizeof(double) * Rz * nj3);
   c->ens_jt_phi_valid = true;
   if (move) {                                            // the step committed: theta_j += rate_j dt, product and sum rounded one after the other
     bool moved = false;
@@ -1223,7 +1024,7 @@ int ens_jt_set_values(rbl_ctx *c, const char *who, const double *v, int sets, bo
 {
   if (!c) return RBL_ERR_ARG;
   const std::string w(who);
-  if (!c->ens_R) return rbl_fail(c, RBL_ERR_STATE, w + ": ensemble: no ensemble configuration (rbl_ensemble_set_config)");
+  if (!c->ens_R) return ens_fail_state(c, w + ": ");
   if (c->jt_n < 1) return rbl_fail(c, RBL_ERR_STATE, w + ": no joints have been set (rbl_set_joint_kinds)");
   if (!v) return rbl_fail(c, RBL_ERR_ARG, w + ": the array is NULL");
   if (sets != 1 && sets != c->ens_R) return rbl_fail(c, RBL_ERR_ARG, w + ": sets must be 1 or R = " + std::to_string(c->ens_R));
@@ -1322,9 +1123,9 @@ __global__ __launch_bounds__(64) void k_ens_jt_rates(int R, int nj, const int *_
 
 struct EnsJtRun {
   const rbl_run_joint_opts *o; rbl_run_joint_out *out;
-  double coef;                                     // -gamma / dt
   std::vector<int> cum, start;                     // host: the prefix sums (n_phases + 1, or empty), the starting positions [R]
-  RblEnsJoints T; EnsJtVec V;
+  EnsJtStep step;                                  // the jointed variant of every step: the joint table, -gamma / dt
+  const double *x;                                 // the solutions of a step (EnsWork::x)
   const EnsRunStatus *st; const unsigned *vflag;
   int *pos[2]; int cur;                            // device: positions, which of the two is current
   int *cum_d; double *rates_d, *phi_sum, *phi_last, *lev, *fT, *fP, *fG;
@@ -1352,34 +1153,29 @@ size_t ens_jt_run_bytes(const rbl_ctx *c, const EnsJtRun &J, size_t n_frames)
   return bytes;
 }
 
-// the joint table (with the stored angles and rates), the solver's vectors, joint_velocity and the schedule go up, once; the first
-// step's rates are written.  From here on the device table is ahead of the host's copy: it is marked stale whatever follows
-int ens_jt_run_begin(rbl_ctx *c, EnsJtRun &J, void *base, size_t n_frames, int max_iter, const EnsRunBuf &b)
+// the joint table (with the stored angles and rates), joint_velocity and the schedule go up, once; the first step's rates are
+// written.  From here on the device table is ahead of the host's copy: it is marked stale whatever follows.  st, vflag: the run's
+// status and verdict words
+int ens_jt_run_begin(rbl_ctx *c, EnsJtRun &J, void *base, size_t n_frames, const EnsWork &w, const EnsRunStatus *st, const unsigned *vflag)
 {
   const int R = c->ens_R, nj = c->jt_n, np = J.o->n_phases;
   const size_t Rn = (size_t)R * nj;
   int rc;
-  if ((rc = ens_jt_upload(c, &J.T))) return rc;
-  if ((rc = ens_jt_vectors(c, max_iter, &J.V))) return rc;
+  if ((rc = ens_jt_upload(c, &J.step.T))) return rc;
   size_t bytes = 0;
   ens_jt_run_carve(J, base, R, nj, n_frames, &bytes);
-  J.st = b.st; J.vflag = b.vflag; J.cur = 0;
+  J.st = st; J.vflag = vflag; J.x = w.x; J.cur = 0;
   c->ens_jt_valid = false; c->ens_jt_phi_valid = false;
-  if (J.o->joint_velocity && (rc = copy_h2d(c, J.V.djr, J.o->joint_velocity, sizeof(double) * 3 * Rn))) return rc;
+  if (J.o->joint_velocity && (rc = copy_h2d(c, w.jr, J.o->joint_velocity, sizeof(double) * 3 * Rn))) return rc;
   RBL_HIP(c, hipMemsetAsync(J.phi_sum, 0, sizeof(double) * 6 * Rn, c->stream));
   if (np) {
     if ((rc = copy_h2d(c, J.cum_d, J.cum.data(), sizeof(int) * ((size_t)np + 1)))) return rc;
     if ((rc = copy_h2d(c, J.rates_d, J.o->phase_rates, sizeof(double) * (size_t)np * J.o->rate_sets * nj))) return rc;
     if ((rc = copy_h2d(c, J.pos[0], J.start.data(), sizeof(int) * (size_t)R))) return rc;
     hipLaunchKernelGGL(k_ens_jt_rates, dim3((unsigned)((Rn + 63) / 64)), dim3(64), 0, c->stream, R, nj, (const int *)J.pos[0],
-                       (const int *)J.cum_d, (const double *)J.rates_d, np, (int)J.o->rate_sets, (double *)J.T.rate);
+                       (const int *)J.cum_d, (const double *)J.rates_d, np, (int)J.o->rate_sets, (double *)J.step.T.rate);
   }
   return RBL_OK;
-}
-
-int ens_jt_run_enqueue(rbl_ctx *c, const EnsWork &w, EnsJtRun &J, const EnsStepIn &in, int max_iter, double rtol)
-{
-  return ens_jt_enqueue(c, "ensemble_run_jointed", w, J.T, J.V, in, J.o->joint_velocity != nullptr, true, J.coef, max_iter, rtol);
 }
 
 // after the step's commit and the host's flip: the joints' launch and, in a recording step (frame >= 0), the gaps at the committed
@@ -1390,8 +1186,8 @@ void ens_jt_run_after(rbl_ctx *c, EnsJtRun &J, long frame)
   const size_t Rn = (size_t)R * nj, n3 = (size_t)3 * Nb * c->S.N_blb, nb6 = (size_t)6 * Nb;
   EnsJtRunDev D;
   D.st = J.st; D.vflag = J.vflag;
-  D.theta = (double *)J.T.theta; D.rate = (double *)J.T.rate;
-  D.x = J.V.x; D.nsys = (long)(n3 + nb6 + 3 * (size_t)nj); D.off = (long)(n3 + nb6);
+  D.theta = (double *)J.step.T.theta; D.rate = (double *)J.step.T.rate;
+  D.x = J.x; D.nsys = (long)(n3 + nb6 + 3 * (size_t)nj); D.off = (long)(n3 + nb6);
   D.pos_in = J.pos[J.cur]; D.pos_out = J.pos[J.cur ^ 1];
   D.cum = J.cum_d; D.rates = J.rates_d; D.n_phases = np; D.rate_sets = J.o->rate_sets;
   D.dt = c->S.dt;
@@ -1401,7 +1197,7 @@ void ens_jt_run_after(rbl_ctx *c, EnsJtRun &J, long frame)
   hipLaunchKernelGGL(k_ens_jt_run, dim3((unsigned)((Rn + 63) / 64)), dim3(64), 0, c->stream, R, nj, D);
   if (np) J.cur ^= 1;
   if (frame >= 0)
-    rbl_launch_ens_jt_geom(c->stream, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), Nb, R, J.T, J.lev, J.fG + (size_t)frame * 3 * Rn);
+    rbl_launch_ens_jt_geom(c->stream, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), Nb, R, J.step.T, J.lev, J.fG + (size_t)frame * 3 * Rn);
 }
 
 // the joints' share of the read-back: the angles become the ensemble's, the last accepted phi the one rbl_ensemble_joint_state
@@ -1413,7 +1209,7 @@ int ens_jt_run_end(rbl_ctx *c, EnsJtRun &J, size_t nfr, bool stopped)
   rbl_run_joint_out *out = J.out;
   int rc;
   c->ens_jt_phi.resize(3 * Rn);
-  if ((rc = copy_d2h(c, c->ens_jt_theta.data(), J.T.theta, sizeof(double) * Rn))) return rc;
+  if ((rc = copy_d2h(c, c->ens_jt_theta.data(), J.step.T.theta, sizeof(double) * Rn))) return rc;
   if ((rc = copy_d2h(c, c->ens_jt_phi.data(), J.phi_last, sizeof(double) * 3 * Rn))) return rc;
   if (out->phi_sum && (rc = copy_d2h(c, out->phi_sum, J.phi_sum, sizeof(double) * 3 * Rn))) return rc;
   if (out->cycle_pos) {
@@ -1429,6 +1225,136 @@ int ens_jt_run_end(rbl_ctx *c, EnsJtRun &J, size_t nfr, bool stopped)
   if (out->theta) std::memcpy(out->theta, c->ens_jt_theta.data(), sizeof(double) * Rn);
   c->ens_jt_phi_valid = !stopped;
   return RBL_OK;
+}
+
+// the run's own device buffer: [slip copy] | read-back block (status, counters, sums) | verdict words, last loads | frames
+struct EnsRunBuf {
+  double *slip;
+  EnsRunStatus *st; int *accepted, *rejected; unsigned *first_flags; long long *iters_sum; double *resid_max, *F_sum;
+  size_t rb_off, rb_bytes;                 // the read-back block: from st to the end of F_sum
+  unsigned *vflag; double *F_last;
+  double *fX, *fQ; int *fA; double *fF;
+};
+
+EnsRunBuf ens_run_carve(void *base, int R, int Nb, int nbl, bool slip, bool mixed, size_t n_frames, size_t *bytes)
+{
+  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, n3 = (size_t)3 * Nb * nbl;
+  Carve C{(char *)base};
+  EnsRunBuf b;
+  b.slip = C.take<double>(slip ? Rz * n3 : 0);
+  b.rb_off = C.off;
+  b.st = C.take<EnsRunStatus>(1);
+  b.accepted = C.take<int>(Rz); b.rejected = C.take<int>(Rz); b.first_flags = C.take<unsigned>(Rz);
+  b.iters_sum = C.take<long long>(Rz); b.resid_max = C.take<double>(Rz);
+  b.F_sum = C.take<double>(mixed ? Rz * nb6 : 0);
+  b.rb_bytes = C.off - b.rb_off;
+  b.vflag = C.take<unsigned>(Rz);
+  b.F_last = C.take<double>(mixed ? Rz * nb6 : 0);
+  b.fX = C.take<double>(n_frames * Rz * 3 * Nb); b.fQ = C.take<double>(n_frames * Rz * 4 * Nb);
+  b.fA = C.take<int>(n_frames * Rz);
+  b.fF = C.take<double>(mixed ? n_frames * Rz * nb6 : 0);
+  *bytes = C.off;
+  return b;
+}
+
+// n_steps steps of every replica (checks and ens_ready done by the caller; per: the mask's entries per body): the inputs go up
+// once, every step is the one-step calls' enqueue sequence followed by the verdict and the commit, the buffers flip on the host,
+// ONE read-back ends it.  J (rbl_ensemble_run_jointed): the step is the jointed one and one launch for the joints follows the commit
+int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_out *out, EnsJtRun *J)
+{
+  const RblBodyState &S = c->S;
+  const bool mixed = o.prescribed != nullptr, reject = o.on_error == RBL_RUN_REJECT;
+  const int R = c->ens_R, Nb = c->ens_Nb, nbl = S.N_blb;
+  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, n3 = (size_t)3 * Nb * nbl;
+  const size_t n_frames = o.stride > 0 ? (size_t)(o.n_steps / o.stride) : 0;
+  int rc;
+  EnsWork w;
+  if ((rc = ens_work(c, o.max_iter, &w))) return rc;
+  size_t bytes = 0;
+  ens_run_carve(nullptr, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
+  if ((rc = rbl_dev_reserve(c, c->d_ens_run, bytes + (J ? ens_jt_run_bytes(c, *J, n_frames) : 0)))) return rc;   // the joints' part behind
+  const EnsRunBuf b = ens_run_carve(c->d_ens_run.p, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
+  // the uploads, once
+  if (mixed && (rc = ens_upload_mask(c, w, o.prescribed, per))) return rc;
+  if ((rc = copy_h2d(c, w.F, mixed ? o.body_in : o.F_body, sizeof(double) * nb6 * Rz))) return rc;
+  if (o.slip && (rc = copy_h2d(c, b.slip, o.slip, sizeof(double) * n3 * Rz))) return rc;
+  RBL_HIP(c, hipMemsetAsync(b.st, 0, b.rb_bytes, c->stream));
+  if (mixed) RBL_HIP(c, hipMemsetAsync(b.F_last, 0, sizeof(double) * nb6 * Rz, c->stream));
+  if (J && (rc = ens_jt_run_begin(c, *J, (char *)c->d_ens_run.p + bytes, n_frames, w, b.st, b.vflag))) return rc;
+  EnsStepIn in;
+  in.prescribed = o.prescribed; in.per = per;
+  in.slip = o.slip ? b.slip : nullptr; in.resident = true; in.chol_err = 1;
+  in.accepted = b.accepted;
+  EnsRunStatus hs = {0, 0, 0u, 0};
+  int enq = 0;
+  const auto verdict = S.wall ? k_ens_verdict<true> : k_ens_verdict<false>;
+  for (int n = 0; n < o.n_steps; ++n) {
+    rc = brownian ? ens_enqueue_bd(c, w, in, o.seed + (uint64_t)n, o.split_rand, o.delta, o.max_iter, o.rtol)
+                  : ens_enqueue_det(c, w, in, o.max_iter, o.rtol, true, J ? &J->step : nullptr);
+    if (rc) return rc;
+    const int cur = c->ens_cur;
+    hipLaunchKernelGGL(verdict, dim3((unsigned)R), dim3(ET), 0, c->stream, Nb, nbl, n, reject ? 1 : 0,
+                       (const double *)ens_X(c, cur ^ 1), (const double *)ens_Q(c, cur ^ 1), (const double *)ens_cfg(c),
+                       (const unsigned *)w.rerr, (const unsigned *)w.gerr, b.vflag, b.st);
+    EnsRunDev D;
+    D.Xo = ens_X(c, cur); D.Qo = ens_Q(c, cur); D.Xn = ens_X(c, cur ^ 1); D.Qn = ens_Q(c, cur ^ 1);
+    D.vflag = b.vflag; D.gerr = w.gerr; D.iters = w.iters; D.resid = w.resid; D.Fo = mixed ? w.Fo : nullptr; D.st = b.st;
+    D.accepted = b.accepted; D.rejected = b.rejected; D.first_flags = b.first_flags; D.iters_sum = b.iters_sum;
+    D.resid_max = b.resid_max; D.F_sum = b.F_sum; D.F_last = b.F_last;
+    D.fX = D.fQ = D.fF = nullptr; D.fA = nullptr;
+    if (o.stride > 0 && (n + 1) % o.stride == 0) {
+      const size_t k = (size_t)((n + 1) / o.stride - 1);
+      D.fX = b.fX + k * Rz * 3 * Nb; D.fQ = b.fQ + k * Rz * 4 * Nb; D.fA = b.fA + k * Rz;
+      if (mixed) D.fF = b.fF + k * Rz * nb6;
+    }
+    hipLaunchKernelGGL(k_ens_commit, dim3((unsigned)R), dim3(ET), 0, c->stream, R, Nb, n, D);
+    c->ens_cur ^= 1;                                     // the new buffer holds every replica's configuration, moved or not
+    if (J) ens_jt_run_after(c, *J, D.fX ? (long)((n + 1) / o.stride - 1) : -1L);
+    ++enq;
+    if (o.check_every > 0 && enq % o.check_every == 0 && n + 1 < o.n_steps) {
+      if ((rc = read_back(c, &hs, b.st, sizeof(hs)))) return rc;
+      if (hs.stopped) break;
+    }
+  }
+  RBL_HIP(c, hipGetLastError());
+  // the one read-back: status, counters, sums; then the frames the run completed, straight into the caller's arrays
+  std::vector<char> h(b.rb_bytes);
+  if ((rc = copy_d2h(c, h.data(), b.st, b.rb_bytes))) return rc;
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  auto at = [&](const void *p) { return h.data() + ((const char *)p - (const char *)b.st); };
+  std::memcpy(&hs, at(b.st), sizeof(hs));
+  const int *hacc = (const int *)at(b.accepted), *hrej = (const int *)at(b.rejected);
+  const unsigned *hff = (const unsigned *)at(b.first_flags);
+  if (out->accepted) std::memcpy(out->accepted, hacc, sizeof(int) * Rz);
+  if (out->rejected) std::memcpy(out->rejected, hrej, sizeof(int) * Rz);
+  if (out->first_flags) std::memcpy(out->first_flags, hff, sizeof(unsigned) * Rz);
+  if (out->first_status)
+    for (int r = 0; r < R; ++r) out->first_status[r] = hrej[r] ? rbl_flags_to_status(c, hff[r]) : RBL_OK;
+  if (out->iters_sum) std::memcpy(out->iters_sum, at(b.iters_sum), sizeof(int64_t) * Rz);
+  if (out->resid_max) std::memcpy(out->resid_max, at(b.resid_max), sizeof(double) * Rz);
+  if (mixed && out->F_sum) std::memcpy(out->F_sum, at(b.F_sum), sizeof(double) * nb6 * Rz);
+  const size_t nfr = o.stride > 0 ? (size_t)(enq / o.stride) : 0;   // frames of the steps that were enqueued (a polled stop: fewer)
+  if (nfr) {
+    if ((rc = copy_d2h(c, out->frame_X, b.fX, sizeof(double) * nfr * Rz * 3 * Nb))) return rc;
+    if ((rc = copy_d2h(c, out->frame_Q, b.fQ, sizeof(double) * nfr * Rz * 4 * Nb))) return rc;
+    if ((rc = copy_d2h(c, out->frame_accepted_at, b.fA, sizeof(int) * nfr * Rz))) return rc;
+    if (mixed && (rc = copy_d2h(c, out->frame_F, b.fF, sizeof(double) * nfr * Rz * nb6))) return rc;
+    RBL_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  if (J && (rc = ens_jt_run_end(c, *J, nfr, hs.stopped != 0))) return rc;
+  out->stopped_at = hs.stopped ? hs.stopped - 1 : -1;
+  out->steps_done = hs.stopped ? hs.stopped - 1 : o.n_steps;
+  out->stop_replica = hs.stopped && hs.stop_rep ? R - hs.stop_rep : -1;
+  if (!hs.stopped) return RBL_OK;
+  const std::string at_step = "ensemble_run step " + std::to_string(hs.stopped - 1);
+  if (hs.stop_rep) {
+    rc = rbl_flags_to_status(c, hff[R - hs.stop_rep]);
+    c->last_error = at_step + ", replica " + std::to_string(R - hs.stop_rep) + ": " + c->last_error;
+  } else {
+    rc = rbl_flags_to_status(c, hs.batch);
+    c->last_error = at_step + ": " + c->last_error;
+  }
+  return rc;
 }
 
 // the schedule's own refusals (include/rbl.h section 5), none needing a device; fills J.cum and J.start
@@ -1649,18 +1575,15 @@ int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)
     if ((rc = ens_mx_check(c, "ensemble_run", o->prescribed, o->body_in, o->max_iter, o->rtol, per))) return rc;
   } else {
     if ((rc = need_params(c))) return rc;
-    if (o->max_iter > 255)
-      return rbl_fail(c, RBL_ERR_SIZE, "ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)");
-    if (comm_on(c)) return rbl_fail(c, RBL_ERR_ARG, "ensemble: not on a context with a communicator (run one ensemble per process)");
-    if (!c->ens_R) return ens_fail_state(c);
-    if (c->S.N_blb != c->ens_Nblb) return rbl_fail(c, RBL_ERR_STATE, "ensemble: the structure changed since rbl_ensemble_set_config");
+    if (o->max_iter > 255) return rbl_fail(c, RBL_ERR_SIZE, ens_beyond());
+    if ((rc = ens_state_check(c, ""))) return rc;
     if ((rc = ens_check_solver(c, o->max_iter))) return rc;
   }
   const bool brownian = o->brownian && c->S.kBT > 1e-10;   // no Brownian terms (:967-970): the deterministic step
   if (brownian && (!(c->S.dt > 0.0) || !(o->delta > 0.0))) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: dt and delta must be positive");
   if ((rc = ens_flow_check(c))) return rc;
   if ((rc = ens_ready(c))) return rc;
-  return ens_run(c, *o, per, brownian, out);
+  return ens_run(c, *o, per, brownian, out, nullptr);
 }
 
 // n_steps jointed steps in one call: rbl_ensemble_step_jointed's checks and rbl_ensemble_run's, the schedule's own, then ens_run
@@ -1709,7 +1632,7 @@ int rbl_ensemble_run_jointed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_jo
   }
   if ((rc = ens_flow_check(c))) return rc;
   if ((rc = ens_ready(c))) return rc;
-  J.coef = -jo->gamma / c->S.dt;
+  J.step = {who, {}, -jo->gamma / c->S.dt, jo->joint_velocity != nullptr};
   return ens_run(c, od, 1, false, out, &J);
 }
 
@@ -1796,7 +1719,8 @@ int rbl_ensemble_solve_jointed(rbl_ctx *c, const double *F_body, const double *s
   if (ens_cell_on(c)) return ens_cell_refuse(c, "ensemble_solve_jointed");
   int rc = ens_jt_check(c, "ensemble_solve_jointed", F_body, max_iter, rtol); if (rc) return rc;
   if ((rc = ens_ready(c))) return rc;
-  if (!ens_jt_active(c)) return ens_jt_plain_solve(c, F_body, slip, max_iter, rtol, lambda, U, iters, resid);
+  if (!ens_jt_active(c))                               // switched off or never set: the unjointed solve on [slip ; -F]
+    return ens_step_det(c, nullptr, F_body, slip, max_iter, rtol, false, lambda, U, nullptr, iters, resid);
   return ens_jt_solve(c, "ensemble_solve_jointed", F_body, slip, joint_rhs, false, 0.0, max_iter, rtol, lambda, U, phi, iters, resid);
 }
 
@@ -1835,8 +1759,11 @@ int rbl_ensemble_joint_state(rbl_ctx *c, double *gap, double *phi, double *theta
     int rc = ens_ready(c); if (rc) return rc;
     RblEnsJoints T;
     if ((rc = ens_jt_upload(c, &T))) return rc;
-    if ((rc = rbl_dev_reserve(c, c->d_ens_jtw, sizeof(double) * 9 * Rn))) return rc;
-    double *d_lev = (double *)c->d_ens_jtw.p, *d_gap = d_lev + 6 * Rn;
+    // the stored set, on or off: the gaps go where a jointed step's joint rows go, the lever arms (6 per joint) into the solver's
+    // workspace, which holds more than two vectors of 3 N + 6 N_bod + 3 n_joints per replica
+    EnsWork w;
+    if ((rc = ens_work(c, 1, &w, c->jt_n))) return rc;
+    double *d_lev = w.gm, *d_gap = w.jr;
     rbl_launch_ens_jt_geom(c->stream, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), c->ens_Nb, c->ens_R, T, d_lev, d_gap);
     if ((rc = copy_d2h(c, gap, d_gap, sizeof(double) * 3 * Rn))) return rc;
     RBL_HIP(c, hipStreamSynchronize(c->stream));

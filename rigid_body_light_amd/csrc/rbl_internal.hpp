@@ -291,7 +291,6 @@ struct rbl_ctx {
   std::vector<double> ens_jt_phi;                   // R 3 n_joints: phi of the last jointed ensemble solve or step (ens_jt_phi_valid)
   bool ens_jt_valid = false, ens_jt_phi_valid = false;   // d_ens_jt holds the table with the current angles and rates
   RblDevBuf d_ens_jt;                               // anchors | axes and q_rel | theta | rates | bodies | mates | kinds | row starts by body | ends
-  RblDevBuf d_ens_jtw;                              // a jointed ensemble solve's rhs | x | joint rows given | solver workspace
   // periodic cell in x and y (rbl_periodic.hip; include/rbl.h section 10): explicit image sums of the wall-corrected product,
   // minimum image in the pair forces.  A length of 0: that axis is open (its image count is stored as 0)
   bool per_on = false;
@@ -451,7 +450,7 @@ void rbl_launch_scale_by_damp(hipStream_t st, const RblParams &P, const double *
 
 // whole GMRES solve of a small system in one kernel (rbl_small.hip)
 bool rbl_gmres_small_fits(int N_blb, int N_bod, int max_iter, bool block_pc, bool mixed = false);   // mixed: the masked variant
-size_t rbl_gmres_small_work_doubles(int N_blb, int N_bod, int max_iter);
+size_t rbl_gmres_small_work_doubles(int N_blb, int N_bod, int max_iter, int n_joints = 0);   // n_joints: the jointed variant (below)
 int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
                            int N_blb, int N_bod, const double *d_rhs, const double *d_x0, double *d_x, int max_iter, double rtol,
                            double fsign, double *d_work, double *d_scal, unsigned *d_err);
@@ -471,25 +470,29 @@ inline RblSmallCell rbl_small_cell(double a, const double *L, const int *n)
   return C;
 }
 // the same solve for `reps` replicas of one system shape, one workgroup each (rbl_ensemble.hip): X, Q replica-major (3 N_bod,
-// 4 N_bod per replica), rhs / x nsys per replica, d_work reps x rbl_gmres_small_work_doubles, one iteration count, residual and
-// error word per replica; diagonal preconditioner with the force block's sign restored (fsign = +1), cold start
-int rbl_launch_gmres_small_ens(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
-                               int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter, double rtol,
-                               double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err);
-// the same with a 0/1 mask per body (per = 1) or per velocity component (per = 6) and replica (include/rbl.h section 7's system): d_rhs is the all-free right-hand side
-// [slip ; -body_in]; the launch adds K_p U_p, solves and splits.  d_UFx: ONE block [U reps x 6 N_bod | F reps x 6 N_bod | x reps x nsys]
-int rbl_launch_gmres_small_ens_mixed(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ,
-                                     const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_UFx, int max_iter,
-                                     double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err,
-                                     const unsigned char *d_mask, const double *d_body_in, int per);
-// both in a periodic cell (rbl_small_per.hip: k_gmres_small_per; wall only): the operator sums every pair over the cell's images
-int rbl_launch_gmres_small_ens_per(hipStream_t st, const RblParams &P, const RblSmallCell &C, const double *dX, const double *dQ,
-                                   const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter,
-                                   double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err);
-int rbl_launch_gmres_small_ens_mixed_per(hipStream_t st, const RblParams &P, const RblSmallCell &C, const double *dX, const double *dQ,
-                                         const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_UFx,
-                                         int max_iter, double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err,
-                                         const unsigned char *d_mask, const double *d_body_in, int per);
+// 4 N_bod per replica), rhs / x nsys per replica, work reps x rbl_gmres_small_work_doubles, one iteration count, residual and
+// error word per replica; diagonal preconditioner with the force block's sign restored (fsign = +1), cold start.  What every
+// variant's launch takes (device pointers):
+struct RblSmallEns {
+  const double *X, *Q, *cfg;
+  int N_blb, N_bod, reps;
+  const double *rhs;
+  double *x;
+  int max_iter;
+  double rtol;
+  double *work;
+  int *iters;
+  double *resid;
+  unsigned *err;
+};
+// open or above the wall.  d_mask != NULL: a 0/1 mask per body (per = 1) or per velocity component (per = 6) and replica (include/rbl.h
+// section 7's system) -- rhs is the all-free right-hand side [slip ; -body_in]; the launch adds K_p U_p, solves and splits, and x
+// is the last piece of ONE block [U reps x 6 N_bod | F reps x 6 N_bod | x reps x nsys]: U and F are found from x
+int rbl_launch_gmres_small_ens(hipStream_t st, const RblParams &P, bool wall, const RblSmallEns &S, const unsigned char *d_mask = nullptr,
+                               const double *d_body_in = nullptr, int per = 1);
+// the same in a periodic cell (rbl_small_per.hip: k_gmres_small_per; wall only): the operator sums every pair over the cell's images
+int rbl_launch_gmres_small_ens_per(hipStream_t st, const RblParams &P, const RblSmallCell &C, const RblSmallEns &S,
+                                   const unsigned char *d_mask = nullptr, const double *d_body_in = nullptr, int per = 1);
 // the jointed solve of the replicas (rbl_small_joints.hip; include/rbl.h sections 5 and 9).  The joint table on the device, shared
 // by the replicas: anchor 6, ang 7 (axis | q_rel) per joint; theta, rate: n per REPLICA; body 2, mate 2, kind 1 per joint; ptr: the
 // row starts of the joint ends by body (N_bod + 1); ends: (joint, end) per entry, n_ends of them
@@ -502,12 +505,9 @@ struct RblEnsJoints {
 // (7 n_joints + N_bod + 2) / 2 for the integers.  n_joints = 0: the plain predicate
 bool rbl_gmres_small_jt_fits(int N_blb, int N_bod, int max_iter, int n_joints);
 size_t rbl_gmres_small_jt_lds_bytes(int N_blb, int N_bod, int max_iter, int n_joints);   // without the Krylov basis
-size_t rbl_gmres_small_jt_work_doubles(int N_blb, int N_bod, int max_iter, int n_joints);
 // rhs / x: 3 N + 6 N_bod + 3 n_joints per replica ([slip ; -F ; c], [lambda ; U ; phi]); step != 0: the joint rows of rhs hold
 // joint_velocity and the kernel forms c = coef gap + joint_velocity - rate ah (a lock's rows)
-int rbl_launch_gmres_small_ens_jt(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
-                                  int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter, double rtol,
-                                  double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err, const RblEnsJoints &T, int step,
+int rbl_launch_gmres_small_ens_jt(hipStream_t st, const RblParams &P, bool wall, const RblSmallEns &S, const RblEnsJoints &T, int step,
                                   double coef);
 // lever arms (reps x 6 n) and gaps (reps x 3 n) of every replica's joints
 void rbl_launch_ens_jt_geom(hipStream_t st, const double *dX, const double *dQ, int N_bod, int reps, const RblEnsJoints &T, double *d_lev,

@@ -60,84 +60,35 @@ bool rbl_gmres_small_fits(int N_blb, int N_bod, int max_iter, bool block_pc, boo
   return small_lds_base_bytes(N_blb, N_bod, max_iter, mixed) <= SG_LDS_MAX;
 }
 
-size_t rbl_gmres_small_work_doubles(int N_blb, int N_bod, int max_iter)
-{
-  const size_t nsys = (size_t)3 * N_blb * N_bod + (size_t)6 * N_bod;
-  return (size_t)(max_iter + 1) * nsys + (size_t)max_iter * (max_iter + 1) / 2 + 8;
-}
+size_t rbl_gmres_small_work_doubles(int N_blb, int N_bod, int max_iter, int n_joints) { return small_work_doubles(N_blb, N_bod, max_iter, n_joints); }
 
-// one workgroup per replica: reps systems of the same shape, replica r's X, Q, rhs, x0, x, workspace, iterations, residual and
-// error word lie r strides further (rbl_launch_gmres_small is the grid of one).  MIXED: mask, body_in and reps of A are set by
-// the caller (replica r's r N_bod / 6 N_bod further), d_x is the x of a block [U | F | x]
+// the launcher is small_launch (rbl_small_solve.hpp); the kernels of this file for one wall flag, [vlds]
 template <bool MIXED>
-static int launch_small(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
-                        int N_blb, int N_bod, const double *d_rhs, const double *d_x0, double *d_x, int max_iter, double rtol,
-                        double fsign, double *d_work, int *d_iters, double *d_resid, unsigned *d_err, int reps, int err_stride,
-                        std::conditional_t<MIXED, SmallArgsMixed, SmallArgs> A = {})
+static auto small_row(bool wall)
 {
-  if (!rbl_gmres_small_fits(N_blb, N_bod, max_iter, false, MIXED)) return RBL_ERR_SIZE;
-  const size_t nsys = (size_t)3 * N_blb * N_bod + (size_t)6 * N_bod;
-  size_t lds = small_lds_base_bytes(N_blb, N_bod, max_iter, MIXED);
-  bool vlds = lds + small_basis_bytes(N_blb, N_bod, max_iter) <= SG_LDS_MAX;     // the Krylov basis beside the vectors in LDS?
-  A.X = dX; A.Q = dQ; A.cfg = dcfg; A.rhs = d_rhs; A.x0 = d_x0; A.x = d_x;
-  A.V = d_work; A.H = d_work + (size_t)(max_iter + 1) * nsys;
-  A.iters_out = d_iters; A.resid_out = d_resid; A.err = d_err;
-  A.work_stride = rbl_gmres_small_work_doubles(N_blb, N_bod, max_iter); A.err_stride = err_stride;
-  A.P = P; A.N_blb = N_blb; A.N_bod = N_bod; A.max_iter = max_iter; A.rtol = rtol; A.fsign = fsign;
-  // more than 64 KB of dynamic LDS needs the attribute (gfx950: 160 KB per CU).  If the runtime refuses the basis goes to
-  // global memory; if even the vectors do not fit the caller falls back to the general solver (RBL_ERR_SIZE).
-  auto allow = [&](bool v, size_t bytes) {
-    if (bytes <= 64 * 1024) return true;
-    const void *fn = wall ? (v ? (const void *)k_gmres_small<true, true, MIXED> : (const void *)k_gmres_small<true, false, MIXED>)
-                          : (v ? (const void *)k_gmres_small<false, true, MIXED> : (const void *)k_gmres_small<false, false, MIXED>);
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return true;
-    (void)hipGetLastError();
-    return false;
-  };
-  if (vlds && allow(true, lds + small_basis_bytes(N_blb, N_bod, max_iter))) lds += small_basis_bytes(N_blb, N_bod, max_iter);
-  else {
-    vlds = false;
-    if (!allow(false, lds)) return RBL_ERR_SIZE;
-  }
-  const dim3 grid((unsigned)reps);
-  if (vlds) {
-    if (wall) hipLaunchKernelGGL((k_gmres_small<true, true, MIXED>), grid, dim3(SGT), lds, st, A);
-    else hipLaunchKernelGGL((k_gmres_small<false, true, MIXED>), grid, dim3(SGT), lds, st, A);
-  } else {
-    if (wall) hipLaunchKernelGGL((k_gmres_small<true, false, MIXED>), grid, dim3(SGT), lds, st, A);
-    else hipLaunchKernelGGL((k_gmres_small<false, false, MIXED>), grid, dim3(SGT), lds, st, A);
-  }
-  return RBL_OK;
+  static void (*const tab[2][2])(std::conditional_t<MIXED, SmallArgsMixed, SmallArgs>) = {
+      {k_gmres_small<false, false, MIXED>, k_gmres_small<false, true, MIXED>}, {k_gmres_small<true, false, MIXED>, k_gmres_small<true, true, MIXED>}};
+  return tab[wall];
 }
 
-// d_work: rbl_gmres_small_work_doubles(...) doubles; d_scal: 2 doubles (iterations as an int in the first, residual in the second)
+// the grid of one.  d_work: rbl_gmres_small_work_doubles(...) doubles; d_scal: 2 doubles (iterations as an int in the first,
+// residual in the second)
 int rbl_launch_gmres_small(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
                            int N_blb, int N_bod, const double *d_rhs, const double *d_x0, double *d_x, int max_iter, double rtol,
                            double fsign, double *d_work, double *d_scal, unsigned *d_err)
 {
-  return launch_small<false>(st, P, wall, dX, dQ, dcfg, N_blb, N_bod, d_rhs, d_x0, d_x, max_iter, rtol, fsign, d_work, (int *)d_scal,
-                             d_scal + 1, d_err, 1, 0);
+  const RblSmallEns S = {dX, dQ, dcfg, N_blb, N_bod, 1, d_rhs, d_x, max_iter, rtol, d_work, (int *)d_scal, d_scal + 1, d_err};
+  return small_launch(st, P, S, SmallArgs{}, small_row<false>(wall), false, 0, d_x0, fsign, 0);
 }
 
-int rbl_launch_gmres_small_ens(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
-                               int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter, double rtol,
-                               double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err)
+// every replica of an ensemble.  d_mask: the masked solve (MIXED above) -- S.rhs is the all-free right-hand side [slip ; -body_in]
+// (the loads of the free components), d_mask reps x per N_bod bytes (per = 1: one per body, 6: one per velocity component),
+// d_body_in reps x 6 N_bod (the prescribed components' velocities are read)
+int rbl_launch_gmres_small_ens(hipStream_t st, const RblParams &P, bool wall, const RblSmallEns &S, const unsigned char *d_mask,
+                               const double *d_body_in, int per)
 {
-  return launch_small<false>(st, P, wall, dX, dQ, dcfg, N_blb, N_bod, d_rhs, nullptr, d_x, max_iter, rtol, 1.0, d_work, d_iters, d_resid,
-                             d_rep_err, reps, 1);
-}
-
-// the masked solve (MIXED above) of every replica: d_rhs is the all-free right-hand side [slip ; -body_in] (the loads of the free
-// components), d_mask reps x per N_bod bytes (per = 1: one per body, 6: one per velocity component), d_body_in reps x 6 N_bod (the prescribed components'
-// velocities are read); d_UFx is ONE block
-// [U: reps x 6 N_bod | F: reps x 6 N_bod | x: reps x nsys]
-int rbl_launch_gmres_small_ens_mixed(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ,
-                                     const double *dcfg, int N_blb, int N_bod, int reps, const double *d_rhs, double *d_UFx, int max_iter,
-                                     double rtol, double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err,
-                                     const unsigned char *d_mask, const double *d_body_in, int per)
-{
+  if (!d_mask) return small_launch(st, P, S, SmallArgs{}, small_row<false>(wall));
   SmallArgsMixed A = {};
-  A.mask = d_mask; A.body_in = d_body_in; A.reps = reps; A.per = per;
-  return launch_small<true>(st, P, wall, dX, dQ, dcfg, N_blb, N_bod, d_rhs, nullptr, d_UFx + (size_t)2 * reps * 6 * N_bod, max_iter, rtol,
-                            1.0, d_work, d_iters, d_resid, d_rep_err, reps, 1, A);
+  A.mask = d_mask; A.body_in = d_body_in; A.reps = S.reps; A.per = per;
+  return small_launch(st, P, S, A, small_row<true>(wall), true);
 }

@@ -60,54 +60,17 @@ size_t rbl_gmres_small_jt_lds_bytes(int N_blb, int N_bod, int max_iter, int n_jo
   return small_lds_base_bytes(N_blb, N_bod, max_iter, false, n_joints);
 }
 
-size_t rbl_gmres_small_jt_work_doubles(int N_blb, int N_bod, int max_iter, int n_joints)
-{
-  const size_t nsys = (size_t)3 * N_blb * N_bod + (size_t)6 * N_bod + 3 * (size_t)n_joints;
-  return (size_t)(max_iter + 1) * nsys + (size_t)max_iter * (max_iter + 1) / 2 + 8;
-}
-
-// one workgroup per replica; d_rhs and d_x hold 3 N + 6 N_bod + 3 n_joints doubles per replica, d_work
-// rbl_gmres_small_jt_work_doubles per replica.  step: the joint rows of d_rhs hold joint_velocity and c = coef gap + them
-// (- rate ah on a lock's rows) is formed in the kernel
-int rbl_launch_gmres_small_ens_jt(hipStream_t st, const RblParams &P, bool wall, const double *dX, const double *dQ, const double *dcfg,
-                                  int N_blb, int N_bod, int reps, const double *d_rhs, double *d_x, int max_iter, double rtol,
-                                  double *d_work, int *d_iters, double *d_resid, unsigned *d_rep_err, const RblEnsJoints &T, int step,
+// one workgroup per replica; S.rhs and S.x hold 3 N + 6 N_bod + 3 n_joints doubles per replica, S.work
+// rbl_gmres_small_work_doubles(.., n_joints) per replica.  step: the joint rows of S.rhs hold joint_velocity and
+// c = coef gap + them (- rate ah on a lock's rows) is formed in the kernel.  The launcher is small_launch (rbl_small_solve.hpp)
+int rbl_launch_gmres_small_ens_jt(hipStream_t st, const RblParams &P, bool wall, const RblSmallEns &S, const RblEnsJoints &T, int step,
                                   double coef)
 {
-  if (!rbl_gmres_small_jt_fits(N_blb, N_bod, max_iter, T.n)) return RBL_ERR_SIZE;
-  const size_t nsys = (size_t)3 * N_blb * N_bod + (size_t)6 * N_bod + 3 * (size_t)T.n;
-  size_t lds = small_lds_base_bytes(N_blb, N_bod, max_iter, false, T.n);
-  const size_t basis = small_basis_bytes(N_blb, N_bod, max_iter, T.n);
-  bool vlds = lds + basis <= SG_LDS_MAX;                   // the Krylov basis beside the vectors in LDS?
+  static void (*const tab[2][2])(SmallArgsJt) = {{k_gmres_small_jt<false, false>, k_gmres_small_jt<false, true>},
+                                                 {k_gmres_small_jt<true, false>, k_gmres_small_jt<true, true>}};
   SmallArgsJt A = {};
-  A.X = dX; A.Q = dQ; A.cfg = dcfg; A.rhs = d_rhs; A.x0 = nullptr; A.x = d_x;
-  A.V = d_work; A.H = d_work + (size_t)(max_iter + 1) * nsys;
-  A.iters_out = d_iters; A.resid_out = d_resid; A.err = d_rep_err;
-  A.work_stride = rbl_gmres_small_jt_work_doubles(N_blb, N_bod, max_iter, T.n); A.err_stride = 1;
-  A.P = P; A.N_blb = N_blb; A.N_bod = N_bod; A.max_iter = max_iter; A.rtol = rtol; A.fsign = 1.0;
   A.J = jt_table(T); A.n_ends = T.n_ends; A.jstep = step; A.jcoef = coef;
-  auto allow = [&](bool v, size_t bytes) {                 // as rbl_small.hip's launcher: beyond 64 KB the attribute is needed
-    if (bytes <= 64 * 1024) return true;
-    const void *fn = wall ? (v ? (const void *)k_gmres_small_jt<true, true> : (const void *)k_gmres_small_jt<true, false>)
-                          : (v ? (const void *)k_gmres_small_jt<false, true> : (const void *)k_gmres_small_jt<false, false>);
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return true;
-    (void)hipGetLastError();
-    return false;
-  };
-  if (vlds && allow(true, lds + basis)) lds += basis;
-  else {
-    vlds = false;
-    if (!allow(false, lds)) return RBL_ERR_SIZE;
-  }
-  const dim3 grid((unsigned)reps);
-  if (vlds) {
-    if (wall) hipLaunchKernelGGL((k_gmres_small_jt<true, true>), grid, dim3(SGT), lds, st, A);
-    else hipLaunchKernelGGL((k_gmres_small_jt<false, true>), grid, dim3(SGT), lds, st, A);
-  } else {
-    if (wall) hipLaunchKernelGGL((k_gmres_small_jt<true, false>), grid, dim3(SGT), lds, st, A);
-    else hipLaunchKernelGGL((k_gmres_small_jt<false, false>), grid, dim3(SGT), lds, st, A);
-  }
-  return RBL_OK;
+  return small_launch(st, P, S, A, tab[wall], false, T.n);
 }
 
 // d_lev: reps x 6 n_joints, d_gap: reps x 3 n_joints

@@ -2,7 +2,8 @@
 // function template that the kernels of rbl_small.hip (JOINTS = false: the unmasked and the masked solve) and of
 // rbl_small_joints.hip (JOINTS = true: the jointed solve of the ensembles, include/rbl.h sections 5 and 9) instantiate.  Every
 // jointed statement is behind `if constexpr (JOINTS)` and the jointed arguments exist in SmallArgsJt only: with JOINTS = false
-// the function is the kernel body rbl_small.hip had.
+// the function is the kernel body rbl_small.hip had.  Behind it, the host side of every variant: the sizes and small_launch, the
+// one launcher, which rbl_small.hip, rbl_small_per.hip and rbl_small_joints.hip call with their kernels.
 #pragma once
 #include <type_traits>
 
@@ -568,7 +569,7 @@ __device__ __forceinline__ void rbl_small_solve(Args A)
             v += c == 0 ? u[0] + l2 * u[4] - l1 * u[5] : c == 1 ? u[1] + l0 * u[5] - l2 * u[3] : u[2] + l1 * u[3] - l0 * u[4];
           }
         } else {                             // what is echoed is written here: rhs and body_in are not needed again
-          // U and F of this replica: the launcher's ONE block [U | F | x] (rbl_launch_gmres_small_ens_mixed: reps x 6 N_bod each,
+          // U and F of this replica: the launcher's ONE block [U | F | x] (the masked rbl_launch_gmres_small_ens: reps x 6 N_bod,
           // then reps x nsys), found from A.x, which the prologue moved on by blockIdx.x * nsys; the split at the end forms the
           // same two addresses -- change the layout there and in both places here together
           double *Uo = A.x - (size_t)blockIdx.x * nsys - 2 * (size_t)A.reps * nb6 + (size_t)blockIdx.x * nb6, *Fo = Uo + (size_t)A.reps * nb6;
@@ -754,7 +755,7 @@ __device__ __forceinline__ void rbl_small_solve(Args A)
       const double *p = kt + (size_t)c * N + (size_t)b * nbl;
       double f = 0.0;
       for (int k = 0; k < nbl; ++k) f += p[k];
-      // [U | F | x] of rbl_launch_gmres_small_ens_mixed, as where the right-hand side is loaded above
+      // [U | F | x] of the masked rbl_launch_gmres_small_ens, as where the right-hand side is loaded above
       double *Uo = A.x - (size_t)blockIdx.x * nsys - 2 * (size_t)A.reps * nb6 + (size_t)blockIdx.x * nb6, *Fo = Uo + (size_t)A.reps * nb6;
       if (NLs[NS * b + RS * c + 6] != 0.0) Fo[t] = -f;
       else Uo[t] = vz[n3 + t];
@@ -770,23 +771,65 @@ __device__ __forceinline__ void rbl_small_solve(Args A)
 
 }  // namespace
 
-// LDS of the vectors beside the Krylov basis, and of the basis: what the launchers and the fits predicates add up
+// LDS of the vectors beside the Krylov basis, and of the basis: what the launcher and the fits predicates add up (constexpr: the
+// CPU tests hold them against their restatement at compile time)
 // n_joints > 0 (the jointed solve): every vector is 3 n_joints longer, and the joint data stand behind them -- 16 n_joints doubles
 // of lever arms, redundant rows, gaps, sigmas and the diagonal of S, 2 (3 n_joints)^2 for S's factor and S^-1, and the integers
 // (2 + 1 per joint, N_bod + 1 row starts, at most 4 per joint for the joint ends) two to a double
-static size_t small_jt_doubles(int N_bod, int n_joints)
+constexpr size_t small_jt_doubles(int N_bod, int n_joints)
 {
   const size_t nj = (size_t)n_joints;
   return n_joints > 0 ? 16 * nj + 18 * nj * nj + (7 * nj + (size_t)N_bod + 2) / 2 : 0;
 }
-static size_t small_lds_base_bytes(int N_blb, int N_bod, int max_iter, bool mixed = false, int n_joints = 0)
+constexpr size_t small_lds_base_bytes(int N_blb, int N_bod, int max_iter, bool mixed = false, int n_joints = 0)
 {
   const size_t N = (size_t)N_blb * N_bod, n3 = 3 * N, nb6 = 6 * (size_t)N_bod, nsys = n3 + nb6 + 3 * (size_t)n_joints, m = (size_t)max_iter;
   return sizeof(double) * (2 * n3 + 2 * N + N + 36 * (size_t)N_bod + 3 * nsys + nb6 + 3 * (m + 2) + 2 * m + 8 + (SGT / 64) * n3 + n3 + 6 * N +
                            (max_iter <= SG_RLDS ? m * (m + 1) / 2 : 0) + (mixed ? nb6 : 0) +    // mixed: the mask, one flag per row of NLs
                            small_jt_doubles(N_bod, n_joints));
 }
-static size_t small_basis_bytes(int N_blb, int N_bod, int max_iter, int n_joints = 0)
+constexpr size_t small_basis_bytes(int N_blb, int N_bod, int max_iter, int n_joints = 0)
 {
   return sizeof(double) * (size_t)(max_iter + 1) * ((size_t)3 * N_blb * N_bod + (size_t)6 * N_bod + 3 * (size_t)n_joints);
+}
+// the global workspace of one replica (rbl_gmres_small_work_doubles): the Krylov basis, the packed triangular factor behind it, 8 spare
+constexpr size_t small_work_doubles(int N_blb, int N_bod, int max_iter, int n_joints = 0)
+{
+  return small_basis_bytes(N_blb, N_bod, max_iter, n_joints) / sizeof(double) + (size_t)max_iter * (max_iter + 1) / 2 + 8;
+}
+
+// ---- the launcher of every variant ---------------------------------------------------------------------------------------------
+// One workgroup per replica: S.reps systems of the same shape, replica r's X, Q, rhs, x0, x, workspace, iterations, residual and
+// error word r strides further (err_stride = 0, S.reps = 1: the grid of one).  A arrives with what is the variant's own (mask,
+// body_in, reps, per; the cell; the joint table) and gets everything else here; row: the variant's kernels for this wall flag,
+// [0] with the Krylov basis in global memory, [1] with it in LDS.  n_joints > 0 (the jointed variant): rhs, x and every vector of the
+// workspace hold 3 n_joints more per replica.  mixed: S.x is the x of ONE block [U | F | x] (rbl_internal.hpp: RblSmallEns)
+template <class Args>
+static int small_launch(hipStream_t st, const RblParams &P, const RblSmallEns &S, Args A, void (*const *row)(Args), bool mixed = false,
+                        int n_joints = 0, const double *d_x0 = nullptr, double fsign = 1.0, int err_stride = 1)
+{
+  size_t lds = small_lds_base_bytes(S.N_blb, S.N_bod, S.max_iter, mixed, n_joints);
+  if (!rbl_gmres_small_fits(S.N_blb, S.N_bod, S.max_iter, false) || 3 * (size_t)n_joints > (size_t)SGT || lds > SG_LDS_MAX) return RBL_ERR_SIZE;
+  const size_t basis = small_basis_bytes(S.N_blb, S.N_bod, S.max_iter, n_joints);
+  bool vlds = lds + basis <= SG_LDS_MAX;                   // the Krylov basis beside the vectors in LDS?
+  A.X = S.X; A.Q = S.Q; A.cfg = S.cfg; A.rhs = S.rhs; A.x0 = d_x0; A.x = S.x;
+  A.V = S.work; A.H = S.work + basis / sizeof(double);
+  A.iters_out = S.iters; A.resid_out = S.resid; A.err = S.err;
+  A.work_stride = small_work_doubles(S.N_blb, S.N_bod, S.max_iter, n_joints); A.err_stride = err_stride;
+  A.P = P; A.N_blb = S.N_blb; A.N_bod = S.N_bod; A.max_iter = S.max_iter; A.rtol = S.rtol; A.fsign = fsign;
+  // more than 64 KB of dynamic LDS needs the attribute (gfx950: 160 KB per CU).  If the runtime refuses the basis goes to
+  // global memory; if even the vectors do not fit the caller falls back to the general solver (RBL_ERR_SIZE).
+  auto allow = [&](bool v, size_t bytes) {
+    if (bytes <= 64 * 1024) return true;
+    if (hipFuncSetAttribute((const void *)row[v], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+  };
+  if (vlds && allow(true, lds + basis)) lds += basis;
+  else {
+    vlds = false;
+    if (!allow(false, lds)) return RBL_ERR_SIZE;
+  }
+  hipLaunchKernelGGL(row[vlds], dim3((unsigned)S.reps), dim3(SGT), lds, st, A);
+  return RBL_OK;
 }

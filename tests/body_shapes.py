@@ -175,6 +175,16 @@ def small_lds_bytes(nblb, nb, max_iter, mixed=False):
                 (m * (m + 1) // 2 if m <= 64 else 0) + (nb6 if mixed else 0))
 
 
+def small_basis_bytes(nblb, nb, max_iter):
+    """the Krylov basis: max_iter + 1 vectors; in LDS when it fits beside small_lds_bytes, else in the global workspace"""
+    return 8 * (max_iter + 1) * (3 * nblb * nb + 6 * nb)
+
+
+def small_work_doubles(nblb, nb, max_iter):
+    """the global workspace of one replica (rbl_gmres_small_work_doubles): the basis | the packed triangular factor | 8 spare"""
+    return (max_iter + 1) * (3 * nblb * nb + 6 * nb) + max_iter * (max_iter + 1) // 2 + 8
+
+
 def small_fits(nblb, nb, max_iter, mixed=False):
     return nblb * nb <= 256 and nb <= 64 and 1 <= max_iter <= 255 and small_lds_bytes(nblb, nb, max_iter, mixed) <= SMALL_LDS_MAX
 

@@ -127,3 +127,45 @@ def test_which_cases_the_one_kernel_solver_takes():
     assert fits("E2", 255) and not bs.small_fits(239, 1, 255)
     assert fits("E3", 255) and not bs.small_fits(7, 31, 255)
     assert fits("E4", 100) and fits("E4", 100, True) and not bs.small_fits(4, 52, 100)
+
+
+def test_the_launchers_size_arithmetic_is_the_restated_one(tmp_path):
+    """The one launcher of the one-kernel solver (small_launch, rbl_small_solve.hpp) takes its LDS bytes, its Krylov basis bytes and
+    the workspace of a replica from constexpr functions of the same header.  Without joints they are body_shapes' restatement --
+    what the launcher's three predecessors computed, each for itself -- and the placement that follows from them (basis in LDS
+    under 64 KB, in LDS with the attribute, in global memory) is the one the GPU tests count on at 2 bodies of 12 blobs.  Checked
+    by the compiler: one static_assert per shape, host side only, nothing is run.  The C ABI's own figure (rbl_ensemble_joints_fit
+    with no joints) is the same number"""
+    import ctypes
+    import os
+    import subprocess
+    from rigid_body_light_amd import build as B
+    shapes = [(12, 2, 40), (12, 2, 100), (12, 2, 255), (12, 10, 64), (12, 10, 65), (3, 63, 38), (3, 64, 189), (238, 1, 255), (4, 49, 255),
+              (7, 30, 1), (1, 1, 1), (12, 3, 100)]
+    lines = ['#include "rbl_small_solve.hpp"']
+    for nblb, nb, m in shapes:
+        args = "%d, %d, %d" % (nblb, nb, m)
+        lines.append('static_assert(small_work_doubles(%s) == %dull && small_work_doubles(%s, 0) == %dull, "workspace %s");'
+                     % (args, bs.small_work_doubles(nblb, nb, m), args, bs.small_work_doubles(nblb, nb, m), args))
+        for mixed in (False, True):
+            lines.append('static_assert(small_lds_base_bytes(%s, %s) == %dull && small_lds_base_bytes(%s, %s, 0) == %dull, "LDS %s");'
+                         % (args, str(mixed).lower(), bs.small_lds_bytes(nblb, nb, m, mixed), args, str(mixed).lower(),
+                            bs.small_lds_bytes(nblb, nb, m, mixed), args))
+        lines.append('static_assert(small_basis_bytes(%s) == %dull && small_basis_bytes(%s, 0) == %dull, "basis %s");'
+                     % (args, bs.small_basis_bytes(nblb, nb, m), args, bs.small_basis_bytes(nblb, nb, m), args))
+    # the jointed variant's vectors are 3 n_joints longer: the workspace and the basis grow by exactly that
+    lines.append('static_assert(small_work_doubles(12, 3, 100, 4) == %dull + 101 * 12 && small_basis_bytes(12, 3, 100, 4) == %dull + 8 * 101 * 12, "joints");'
+                 % (bs.small_work_doubles(12, 3, 100), bs.small_basis_bytes(12, 3, 100)))
+    src = tmp_path / "sizes.hip"
+    src.write_text("\n".join(lines) + "\n")
+    p = subprocess.run([B.HIPCC, "-std=c++17", "-x", "hip", "--offload-host-only", "-fsyntax-only", "-I" + B.CSRC, str(src)],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    # the three placements of the 2-body, 12-blob shape: the basis beside the vectors under 64 KB, above it, and not at all
+    total = {m: bs.small_lds_bytes(12, 2, m) + bs.small_basis_bytes(12, 2, m) for m in (40, 100, 255)}
+    assert total[40] <= 64 * 1024 < total[100] <= bs.SMALL_LDS_MAX < total[255] and bs.small_fits(12, 2, 255, True)
+    L = ctypes.CDLL(os.path.join(os.path.dirname(B.CSRC), "librbl.so"))
+    for nblb, nb, m in shapes:
+        lds = ctypes.c_int64(0)
+        fit = L.rbl_ensemble_joints_fit(nblb, nb, m, 0, ctypes.byref(lds))
+        assert lds.value == bs.small_lds_bytes(nblb, nb, m) and bool(fit) == bs.small_fits(nblb, nb, m), (nblb, nb, m)

@@ -78,7 +78,7 @@ def _single_dof(s, which, P, body_in, slip, max_iter, rtol, nb):
     return F, it.value, res.value
 
 
-# ---- the solver's placement rule, restated (rbl_launch_gmres_small, small_lds_base_bytes of rbl_small.hip) --------------------------
+# ---- the solver's placement rule, restated (small_launch, small_lds_base_bytes of rbl_small_solve.hpp) --------------------------
 def _basis_in_lds(nb, max_iter, nbl=NBLB):
     """the masked solve keeps the Krylov basis in LDS when its vectors, the mask's flags and (max_iter + 1) basis vectors fit in
     150 KB: the launcher's own rule"""

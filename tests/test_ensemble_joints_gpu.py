@@ -103,6 +103,32 @@ def test_a_weld(orc, wall):
     _solve_and_compare(orc, c, ens, r, wall, 11, "weld wall=%s" % wall, table="weld")
 
 
+@pytest.mark.parametrize("wall", [False, True])
+def test_a_weld_keeps_its_bits_where_the_basis_crosses_64_kb_of_lds(wall):
+    """the weld's solve with max_iter = 40 and with 100: vectors, joint data and Krylov basis take 54 200 bytes of LDS at 40 and
+    93 240 at 100, under and over the 64 KB a kernel gets without hipFuncAttributeMaxDynamicSharedMemorySize (the bytes from
+    rbl_ensemble_joints_fit, the basis max_iter + 1 vectors of 3 N + 6 N_bod + 3 n_joints).  The solve converges to 1e-10 below
+    both caps -- REF_ITERS: the numpy GMRES takes 29 / 30 iterations -- so lambda, U, phi, the counts and the residuals are the
+    same bits"""
+    import ctypes
+    X, Q, r = jk.case_weld()
+    _, ens = _ens(X, Q, wall)
+    ens.set_joint_kinds(**r)
+    caps, total = (40, MAXIT), []
+    for m in caps:
+        lds = ctypes.c_int64(0)
+        assert ens.ctx.L.rbl_ensemble_joints_fit(12, 2, m, 2, ctypes.byref(lds)) == 1
+        total.append(lds.value + 8 * (m + 1) * (72 + 12 + 6))
+    assert total == [54200, 93240] and total[0] <= 64 * 1024 < total[1] <= 153600
+    F, slip, crhs = _inputs(2, 2, 11)
+    got = [ens.solve_jointed(F, slip=slip, joint_rhs=crhs, max_iter=m, rtol=RTOL) for m in caps]
+    its, res = int(got[0][3][0]), float(got[0][4][0])
+    print("weld wall=%s, max_iter 40 and 100: %d iterations (reference %d), residual %.2e" % (wall, its, REF_ITERS["weld"][wall], res))
+    assert 0 < its < caps[0] and abs(its - REF_ITERS["weld"][wall]) <= 1 and res < RTOL
+    for p, q in zip(*got):
+        assert np.asarray(p).tobytes() == np.asarray(q).tobytes()
+
+
 @pytest.mark.parametrize("max_iter", [60, 100])
 @pytest.mark.parametrize("wall", [False, True])
 def test_a_five_row_hinge_with_the_factor_in_lds_and_in_global_memory(orc, wall, max_iter):

@@ -227,6 +227,38 @@ def test_deterministic_step_equals_the_single_context_step_in_its_cell(name):
         assert moved_X > 1e-4 and np.abs(Xe[r] - Xs).max() <= 1e-7 * moved_X and np.abs(Qe[r] - Qs).max() <= 1e-7 * moved_Q
 
 
+def test_the_unmasked_step_keeps_its_bits_where_the_basis_crosses_64_kb_of_lds():
+    """2 x shell_N_12 in a cell, three replicas, the unmasked k_gmres_small_per: with max_iter = 40 the vectors and the Krylov basis
+    take 51 184 bytes of LDS, with max_iter = 100 87 344 (body_shapes' restatement of the launcher's arithmetic), more than the
+    64 KB a kernel gets without hipFuncAttributeMaxDynamicSharedMemorySize and less than the solver's 153 600.  The step converges
+    to 1e-10 below both caps -- the numpy GMRES with the diagonal preconditioner on B M_per B (joint_oracle.gmres_right_pc) takes 28
+    iterations for each of the three replicas -- so both calls do the same arithmetic: iteration counts, residuals and the new
+    configurations are the same bits"""
+    import body_shapes as bs
+    from rigid_body_light_amd.synth import make_config
+    c = make_config(2, 12, True)
+    s = pc.spacing(c["a"])
+    rng = np.random.default_rng(71)
+    R, caps = 3, (40, 100)
+    X = np.stack([c["X"]] + [c["X"] + rng.uniform(-0.05, 0.05, c["X"].shape) for _ in range(R - 1)])
+    F, slip = rng.standard_normal((R, 12)), 0.1 * rng.standard_normal((R, 72))
+    total = [bs.small_lds_bytes(12, 2, m) + bs.small_basis_bytes(12, 2, m) for m in caps]
+    assert total == [51184, 87344] and total[0] <= 64 * 1024 < total[1] <= bs.SMALL_LDS_MAX
+    got = []
+    for m in caps:
+        ens = _ens(c["cfg"], c["a"], X, np.stack([c["Q"]] * R))
+        ens.set_cell(2.0 * s, s + 0.7, images=(1, 1))
+        its, res = ens.step_deterministic(F, slip=slip, max_iter=m, rtol=1e-10)
+        got.append((its, res) + tuple(ens.get_config()))
+        ens.close()
+    its, res = got[0][:2]
+    print("2 bodies in a cell, max_iter 40 and 100: %s iterations, residual estimates <= %.1e" % (its.tolist(), res.max()))
+    assert (its > 0).all() and (its < caps[0]).all() and (res < 1e-10).all()
+    for p, q in zip(*got):
+        assert np.asarray(p).tobytes() == np.asarray(q).tobytes()
+    assert np.abs(got[0][2] - X).max() > 1e-4                  # the replicas moved
+
+
 # ------------------------------------------------------------------------------------------------------ 4: the Brownian step
 def _np_brownian_step(orc, cfg, X, Qn, a, L, images, dt, kBT, P6, body_in, slip, W, split_rand, delta=1e-4):
     """the stochastic midpoint step of rbl_ensemble.hip restated on the oracle's matrices of the cell: the root from
