@@ -56,6 +56,14 @@ int upload_coef(rbl_ctx *c, double *d_dst, const double *src, int count, int slo
 int copy_h2d(rbl_ctx *c, void *dst, const void *src, size_t bytes);   // synchronous for large pageable sources
 int copy_d2h(rbl_ctx *c, void *dst, const void *src, size_t bytes);
 int read_back(rbl_ctx *c, void *dst, const void *d_src, size_t bytes);   // small device -> host read the host needs NOW
+// the context's pinned buffer behind read_back (allocated at first use); NULL: `bytes` does not fit it
+int pin_buffer(rbl_ctx *c, size_t bytes, void **h_pin);
+// Which side the caller's arrays of a call live on.  An entry point's host form and its _dev form are one core that moves the
+// caller's data with these two: Host is copy_h2d / copy_d2h (pageable arrays, synchronous above 64 KB), Device an asynchronous
+// device-to-device copy on the context's stream.  d_dst of xfer_in and d_src of xfer_out are the library's own workspace
+enum class RblSide { Host, Device };
+int xfer_in(rbl_ctx *c, RblSide side, void *d_dst, const void *src, size_t bytes);
+int xfer_out(rbl_ctx *c, RblSide side, void *dst, const void *d_src, size_t bytes);
 int finish_and_check(rbl_ctx *c);             // drain the stream, read + clear the latched device flags
 RblParams ctx_params(const rbl_ctx *c, bool force_no_damp);   // undamped when RBL_OPT_NO_DAMP or the caller asks
 
@@ -133,6 +141,25 @@ int gmres_multi_with_ops(rbl_ctx *c, const RblMultiOps *ops, const double *d_rhs
                          int *iters_out, double *resid_out);
 
 // ---- rbl_steps.hip ------------------------------------------------------------------------------------------------
+// the lengths the context's configuration gives every vector: blobs, 3 N, 6 N_bod, and the saddle system's 3 N + 6 N_bod
+struct RblSizes { size_t N, n3, nb6, nsys; };
+RblSizes sizes_of(const rbl_ctx *c);
+// The stages every whole-step entry point of a single context shares (rbl_step_deterministic, rbl_step_brownian, rbl_step_jointed,
+// the steps of rbl_mixed.hip).  A model that enters every step has these places to go:
+// step_begin: the flow model's checks, the device, then RBL_ERR_ARG with `missing` when the caller names a required argument that
+// is NULL (the refusal's place in the order, behind the device), then the previous record of moments is dropped
+int step_begin(rbl_ctx *c, const char *missing = nullptr);
+// the slip of a call into d_slip (3 N): the caller's (either side; NULL: none) and, with `model`, the flow model's term at q^n
+// added.  *have_slip: d_slip holds something (nothing is written otherwise)
+int step_slip(rbl_ctx *c, RblSide side, const double *slip, double *d_slip, bool model, bool *have_slip);
+// the inputs of a step at q^n from host arrays: d_slip (3 N) = slip (NULL: zero) + the flow model's term, then d_force (6 N_bod) =
+// F_body - K^T f_phys of the force model (which ends in a drain and a check of the latched flags while it is on)
+int step_inputs(rbl_ctx *c, const double *F_body, const double *slip, double *d_force, double *d_slip);
+// the end of a step's solve: RBL_OPT_RECORD_MOMENTS of d_lambda at the configuration the context is at, U (6 N_bod, from d_U) and,
+// when `more` is not NULL, n_more doubles from d_more to the host, then the stream drained -- by finish_and_check when
+// `check_flags`, by a plain synchronisation otherwise
+int step_commit(rbl_ctx *c, const double *d_lambda, const double *d_U, double *U, const double *d_more, double *more, size_t n_more,
+                bool check_flags);
 // The stochastic midpoint scheme, once for rbl_step_brownian and rbl_step_brownian_mixed (rbl_mixed.hip): the all-free step is the
 // mixed one with no mask (h_mask, d_mask, d_body_in all NULL).  d_s = slip - kBT M_RFD - BI may alias d_slip; d_slip NULL: zero.
 // per: mask entries per body, 1 or 6 (a mask per velocity component whose rotation entries are all equal within a body)

@@ -345,17 +345,37 @@ int copy_d2h(rbl_ctx *c, void *dst, const void *src, size_t bytes)
 // a stream drain -- 11.6 us on MI355X; with a pageable target the runtime stages the copy itself and the same read costs
 // 21 us (tools/launch_costs.hip).
 constexpr size_t RBL_PIN_BYTES = (size_t)1 << 20;
+int pin_buffer(rbl_ctx *c, size_t bytes, void **h_pin)
+{
+  *h_pin = nullptr;
+  if (bytes > RBL_PIN_BYTES) return RBL_OK;
+  if (!c->h_pin) RBL_HIP(c, hipHostMalloc(&c->h_pin, RBL_PIN_BYTES, hipHostMallocDefault));
+  *h_pin = c->h_pin;
+  return RBL_OK;
+}
+
 int read_back(rbl_ctx *c, void *dst, const void *d_src, size_t bytes)
 {
-  if (bytes <= RBL_PIN_BYTES) {
-    if (!c->h_pin) RBL_HIP(c, hipHostMalloc(&c->h_pin, RBL_PIN_BYTES, hipHostMallocDefault));
-    RBL_HIP(c, hipMemcpyAsync(c->h_pin, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
-    RBL_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(dst, c->h_pin, bytes);
-    return RBL_OK;
-  }
-  RBL_HIP(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
+  void *pin;
+  int rc = pin_buffer(c, bytes, &pin); if (rc) return rc;
+  RBL_HIP(c, hipMemcpyAsync(pin ? pin : dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
   RBL_HIP(c, hipStreamSynchronize(c->stream));
+  if (pin) std::memcpy(dst, pin, bytes);
+  return RBL_OK;
+}
+
+// The caller's arrays of an entry point in and out, whichever side they live on (RblSide, rbl_api_internal.hpp)
+int xfer_in(rbl_ctx *c, RblSide side, void *d_dst, const void *src, size_t bytes)
+{
+  if (side == RblSide::Host) return copy_h2d(c, d_dst, src, bytes);
+  RBL_HIP(c, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+  return RBL_OK;
+}
+
+int xfer_out(rbl_ctx *c, RblSide side, void *dst, const void *d_src, size_t bytes)
+{
+  if (side == RblSide::Host) return copy_d2h(c, dst, d_src, bytes);
+  RBL_HIP(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToDevice, c->stream));
   return RBL_OK;
 }
 

@@ -434,7 +434,7 @@ struct JtBuf {             // the one workspace of a section 9 entry point (rbl_
 
 int jt_reserve(rbl_ctx *c, JtBuf &B)
 {
-  const size_t nj3 = 3 * (size_t)c->jt_n, nsys = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb + 6 * (size_t)c->S.N_bod, n = nsys + nj3;
+  const size_t nj3 = 3 * (size_t)c->jt_n, nsys = sizes_of(c).nsys, n = nsys + nj3;
   const int rc = rbl_dev_reserve(c, c->d_jtw, sizeof(double) * (2 * n + 2 * nsys + 6 * nj3));
   if (rc) return rc;
   B.rhs = (double *)c->d_jtw.p; B.x = B.rhs + n; B.v = B.x + n; B.w = B.v + nsys; B.t = B.w + nsys; B.lev = B.t + nj3;
@@ -549,7 +549,7 @@ void jt_launch_tail(rbl_ctx *c, const JtSolve *m, const double *phi, int add, do
 int jt_op(rbl_ctx *c, void *user, const double *d_x, double *d_out)
 {
   const JtSolve *m = (const JtSolve *)user;
-  const long n3 = 3L * c->S.N_bod * c->S.N_blb, nsys = n3 + 6L * c->S.N_bod;
+  const long n3 = (long)sizes_of(c).n3, nsys = (long)sizes_of(c).nsys;
   const int rc = rbl_apply_saddle_dev(c, d_x, d_out); if (rc) return rc;
   jt_launch_tail(c, m, d_x + nsys, 1, d_out + n3, d_x + n3, nullptr, d_out + nsys);
   return RBL_OK;
@@ -559,7 +559,7 @@ int jt_pc(rbl_ctx *c, void *user, const double *d_in, double *d_out)
 {
   const JtSolve *m = (const JtSolve *)user;
   const JtBuf &B = *m->B;
-  const long n3 = 3L * c->S.N_bod * c->S.N_blb, nsys = n3 + 6L * c->S.N_bod;
+  const long n3 = (long)sizes_of(c).n3, nsys = (long)sizes_of(c).nsys;
   const int nj3 = 3 * m->J.n;
   RblPcReq rq;
   rq.fsign = 1.0;
@@ -625,7 +625,7 @@ int jt_solve(rbl_ctx *c, const char *who, const JtBuf &B, int max_iter, double r
   RblPhase ph_total(c, RBL_T_TOTAL);
   c->jt_phi_valid = false;
   int rc = rbl_prepare_dev(c); if (rc) return rc;                        // resident geometry, the preconditioner of this configuration
-  const size_t n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nsys = n3 + 6 * (size_t)c->S.N_bod, nj3 = 3 * (size_t)c->jt_n;
+  const size_t nsys = sizes_of(c).nsys, nj3 = 3 * (size_t)c->jt_n;
   JtSolve m{&B, jt_args(c), nullptr, jt_np(c)};
   if ((rc = jt_factor(c, who, B, &m.Sinv, &m.J.ninv))) return rc;
   RBL_HIP(c, hipMemsetAsync(B.v, 0, sizeof(double) * nsys, c->stream));
@@ -643,40 +643,58 @@ int jt_solve(rbl_ctx *c, const char *who, const JtBuf &B, int max_iter, double r
 }
 
 // rhs = [slip (or zero) ; -F ; c (or zero)] from device vectors; d_F may be B.v
-void jt_rhs(rbl_ctx *c, const JtBuf &B, const double *d_F, bool have_slip, const double *d_c)
+int jt_rhs(rbl_ctx *c, const JtBuf &B, const double *d_F, bool have_slip, const double *d_c)
 {
-  const size_t n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nb6 = 6 * (size_t)c->S.N_bod, nj3 = 3 * (size_t)c->jt_n;
-  if (!have_slip) (void)hipMemsetAsync(B.rhs, 0, sizeof(double) * n3, c->stream);
-  rbl_launch_axpby(c->stream, (int64_t)nb6, -1.0, d_F, 0.0, nullptr, B.rhs + n3);
-  if (d_c) (void)hipMemcpyAsync(B.rhs + n3 + nb6, d_c, sizeof(double) * nj3, hipMemcpyDeviceToDevice, c->stream);
-  else (void)hipMemsetAsync(B.rhs + n3 + nb6, 0, sizeof(double) * nj3, c->stream);
+  const RblSizes z = sizes_of(c);
+  const size_t nj3 = 3 * (size_t)c->jt_n;
+  if (!have_slip) RBL_HIP(c, hipMemsetAsync(B.rhs, 0, sizeof(double) * z.n3, c->stream));
+  rbl_launch_axpby(c->stream, (int64_t)z.nb6, -1.0, d_F, 0.0, nullptr, B.rhs + z.n3);
+  if (d_c) RBL_HIP(c, hipMemcpyAsync(B.rhs + z.nsys, d_c, sizeof(double) * nj3, hipMemcpyDeviceToDevice, c->stream));
+  else RBL_HIP(c, hipMemsetAsync(B.rhs + z.nsys, 0, sizeof(double) * nj3, c->stream));
+  return RBL_OK;
 }
 
-// joints switched off or never set: the plain saddle solve on [slip ; -F]
-int jt_plain_solve(rbl_ctx *c, const double *F_body, const double *slip, bool host, int max_iter, double rtol, double *lambda, double *U,
+// joints switched off or never set: the plain saddle solve on [slip ; -F], the caller's arrays on either side
+int jt_plain_solve(rbl_ctx *c, RblSide side, const double *F_body, const double *slip, int max_iter, double rtol, double *lambda, double *U,
                    int *iters, double *resid)
 {
-  const size_t n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nb6 = 6 * (size_t)c->S.N_bod, nsys = n3 + nb6;
-  int rc = rbl_dev_reserve(c, c->d_jtw, sizeof(double) * (2 * nsys + nb6)); if (rc) return rc;
-  double *x = (double *)c->d_jtw.p, *rhs = x + nsys, *f = rhs + nsys;
-  if (host) {
-    if (slip && (rc = copy_h2d(c, rhs, slip, sizeof(double) * n3))) return rc;
-    if ((rc = copy_h2d(c, f, F_body, sizeof(double) * nb6))) return rc;
-  } else {
-    if (slip) RBL_HIP(c, hipMemcpyAsync(rhs, slip, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
-    RBL_HIP(c, hipMemcpyAsync(f, F_body, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
-  }
-  if (!slip) RBL_HIP(c, hipMemsetAsync(rhs, 0, sizeof(double) * n3, c->stream));
-  rbl_launch_axpby(c->stream, (int64_t)nb6, -1.0, f, 0.0, nullptr, rhs + n3);
+  const RblSizes z = sizes_of(c);
+  int rc = rbl_dev_reserve(c, c->d_jtw, sizeof(double) * (2 * z.nsys + z.nb6)); if (rc) return rc;
+  double *x = (double *)c->d_jtw.p, *rhs = x + z.nsys, *f = rhs + z.nsys;
+  if (slip && (rc = xfer_in(c, side, rhs, slip, sizeof(double) * z.n3))) return rc;
+  if ((rc = xfer_in(c, side, f, F_body, sizeof(double) * z.nb6))) return rc;
+  if (!slip) RBL_HIP(c, hipMemsetAsync(rhs, 0, sizeof(double) * z.n3, c->stream));
+  rbl_launch_axpby(c->stream, (int64_t)z.nb6, -1.0, f, 0.0, nullptr, rhs + z.n3);
   if ((rc = rbl_gmres_saddle_dev(c, rhs, max_iter, rtol, x, 0, iters, resid))) return rc;
-  if (host) {
-    if (lambda && (rc = copy_d2h(c, lambda, x, sizeof(double) * n3))) return rc;
-    if (U && (rc = copy_d2h(c, U, x + n3, sizeof(double) * nb6))) return rc;
-  } else {
-    if (lambda) RBL_HIP(c, hipMemcpyAsync(lambda, x, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
-    RBL_HIP(c, hipMemcpyAsync(U, x + n3, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
-  }
+  if (lambda && (rc = xfer_out(c, side, lambda, x, sizeof(double) * z.n3))) return rc;
+  if (U && (rc = xfer_out(c, side, U, x + z.n3, sizeof(double) * z.nb6))) return rc;
   return finish_and_check(c);
+}
+
+// The jointed solve, the checks done and the device up: the caller's arrays (either side) in, the solve, lambda, U and phi out
+// where they are not NULL.  A host caller's loads and joint right-hand side go up into the workspace; a device caller's are read
+// where they are.  Nothing is drained beyond the solver's convergence tests
+int jt_solve_core(rbl_ctx *c, const char *who, RblSide side, const double *F_body, const double *slip, const double *joint_rhs, int max_iter,
+                  double rtol, double *lambda, double *U, double *phi, int *iters, double *resid)
+{
+  const RblSizes z = sizes_of(c);
+  const size_t nj3 = 3 * (size_t)c->jt_n;
+  JtBuf B;
+  int rc = jt_reserve(c, B); if (rc) return rc;
+  if ((rc = jt_geom(c, B.lev, B.gap, B.gau))) return rc;
+  if (slip && (rc = xfer_in(c, side, B.rhs, slip, sizeof(double) * z.n3))) return rc;
+  if (side == RblSide::Host) {
+    if ((rc = copy_h2d(c, B.v, F_body, sizeof(double) * z.nb6))) return rc;
+    if (joint_rhs && (rc = copy_h2d(c, B.c, joint_rhs, sizeof(double) * nj3))) return rc;
+    F_body = B.v;
+    if (joint_rhs) joint_rhs = B.c;
+  }
+  if ((rc = jt_rhs(c, B, F_body, slip != nullptr, joint_rhs))) return rc;
+  if ((rc = jt_solve(c, who, B, max_iter, rtol, iters, resid))) return rc;
+  if (lambda && (rc = xfer_out(c, side, lambda, B.x, sizeof(double) * z.n3))) return rc;
+  if (U && (rc = xfer_out(c, side, U, B.x + z.n3, sizeof(double) * z.nb6))) return rc;
+  if (phi && (rc = xfer_out(c, side, phi, B.x + z.nsys, sizeof(double) * nj3))) return rc;
+  return RBL_OK;
 }
 
 }   // namespace
@@ -886,19 +904,8 @@ int rbl_solve_jointed(rbl_ctx *c, const double *F_body, const double *slip, cons
   if ((rc = need_K(c))) return rc;
   if (jt_active(c) && (rc = jt_range(c, "solve_jointed"))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
-  if (!jt_active(c)) return jt_plain_solve(c, F_body, slip, true, max_iter, rtol, lambda, U, iters, resid);
-  const size_t n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nb6 = 6 * (size_t)c->S.N_bod, nsys = n3 + nb6, nj3 = 3 * (size_t)c->jt_n;
-  JtBuf B;
-  if ((rc = jt_reserve(c, B))) return rc;
-  if ((rc = jt_geom(c, B.lev, B.gap, B.gau))) return rc;
-  if (slip && (rc = copy_h2d(c, B.rhs, slip, sizeof(double) * n3))) return rc;
-  if ((rc = copy_h2d(c, B.v, F_body, sizeof(double) * nb6))) return rc;
-  if (joint_rhs && (rc = copy_h2d(c, B.c, joint_rhs, sizeof(double) * nj3))) return rc;
-  jt_rhs(c, B, B.v, slip != nullptr, joint_rhs ? B.c : nullptr);
-  if ((rc = jt_solve(c, "solve_jointed", B, max_iter, rtol, iters, resid))) return rc;
-  if (lambda && (rc = copy_d2h(c, lambda, B.x, sizeof(double) * n3))) return rc;
-  if (U && (rc = copy_d2h(c, U, B.x + n3, sizeof(double) * nb6))) return rc;
-  if (phi && (rc = copy_d2h(c, phi, B.x + nsys, sizeof(double) * nj3))) return rc;
+  if (!jt_active(c)) return jt_plain_solve(c, RblSide::Host, F_body, slip, max_iter, rtol, lambda, U, iters, resid);
+  if ((rc = jt_solve_core(c, "solve_jointed", RblSide::Host, F_body, slip, joint_rhs, max_iter, rtol, lambda, U, phi, iters, resid))) return rc;
   return finish_and_check(c);
 }
 
@@ -911,19 +918,10 @@ int rbl_solve_jointed_dev(rbl_ctx *c, const double *d_F_body, const double *d_sl
   if ((rc = need_config(c))) return rc;
   if (jt_active(c) && (rc = jt_range(c, "solve_jointed_dev"))) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
-  if (!jt_active(c)) return jt_plain_solve(c, d_F_body, d_slip, false, max_iter, rtol, d_lambda, d_U, iters, resid);
+  if (!jt_active(c)) return jt_plain_solve(c, RblSide::Device, d_F_body, d_slip, max_iter, rtol, d_lambda, d_U, iters, resid);
   if (!d_phi) return rbl_fail(c, RBL_ERR_ARG, "solve_jointed_dev: phi is NULL");
-  const size_t n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nb6 = 6 * (size_t)c->S.N_bod, nsys = n3 + nb6, nj3 = 3 * (size_t)c->jt_n;
-  JtBuf B;
-  if ((rc = jt_reserve(c, B))) return rc;
-  if ((rc = jt_geom(c, B.lev, B.gap, B.gau))) return rc;
-  if (d_slip) RBL_HIP(c, hipMemcpyAsync(B.rhs, d_slip, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
-  jt_rhs(c, B, d_F_body, d_slip != nullptr, d_joint_rhs);
-  if ((rc = jt_solve(c, "solve_jointed_dev", B, max_iter, rtol, iters, resid))) return rc;
-  if (d_lambda) RBL_HIP(c, hipMemcpyAsync(d_lambda, B.x, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
-  RBL_HIP(c, hipMemcpyAsync(d_U, B.x + n3, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
-  RBL_HIP(c, hipMemcpyAsync(d_phi, B.x + nsys, sizeof(double) * nj3, hipMemcpyDeviceToDevice, c->stream));
-  return RBL_OK;
+  return jt_solve_core(c, "solve_jointed_dev", RblSide::Device, d_F_body, d_slip, d_joint_rhs, max_iter, rtol, d_lambda, d_U, d_phi, iters,
+                       resid);
 }
 
 // One deterministic time step with hard joints: the force model's loads and the flow model's slip at q^n as in
@@ -943,18 +941,13 @@ int rbl_step_jointed(rbl_ctx *c, const double *F_body, const double *slip, const
     return rc;
   }
   if (!(c->S.dt > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "step_jointed: dt must be positive");
-  if ((rc = flow_check(c, c->S.N_bod))) return rc;
-  if ((rc = rbl_dev_init(c))) return rc;
-  flow_begin_step(c);
-  const size_t n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nb6 = 6 * (size_t)c->S.N_bod, nsys = n3 + nb6, nj3 = 3 * (size_t)c->jt_n;
+  if ((rc = step_begin(c))) return rc;
+  const RblSizes z = sizes_of(c);
+  const size_t nj3 = 3 * (size_t)c->jt_n;
   JtBuf B;
   if ((rc = jt_reserve(c, B))) return rc;
   if ((rc = jt_geom(c, B.lev, B.gap, B.gau))) return rc;
-  bool have_slip = slip != nullptr;
-  if (slip && (rc = copy_h2d(c, B.rhs, slip, sizeof(double) * n3))) return rc;
-  if ((rc = flow_add_to_step_slip(c, B.rhs, &have_slip))) return rc;     // imposed flow and body slip at q^n (include/rbl.h section 8)
-  if ((rc = copy_h2d(c, B.v, F_body, sizeof(double) * nb6))) return rc;
-  if ((rc = ia_add_to_step_force(c, B.v))) return rc;                   // the force model at q^n, bonds included (section 4)
+  if ((rc = step_inputs(c, F_body, slip, B.v, B.rhs))) return rc;       // the models at q^n as in rbl_step_deterministic, bonds included
   if (joint_velocity && (rc = copy_h2d(c, B.t, joint_velocity, sizeof(double) * nj3))) return rc;
   if (c->jt_angular)
     hipLaunchKernelGGL(k_jt_step_rhs_kinds, dim3((unsigned)((nj3 + 255) / 256)), dim3(256), 0, c->stream, (const double *)B.gap,
@@ -962,14 +955,11 @@ int rbl_step_jointed(rbl_ctx *c, const double *F_body, const double *slip, const
   else
     hipLaunchKernelGGL(k_jt_step_rhs, dim3((unsigned)((nj3 + 255) / 256)), dim3(256), 0, c->stream, (const double *)B.gap,
                        joint_velocity ? (const double *)B.t : nullptr, -gamma / c->S.dt, (int)nj3, B.c);
-  jt_rhs(c, B, B.v, have_slip, B.c);
+  if ((rc = jt_rhs(c, B, B.v, true, B.c))) return rc;
   c->step_hist_n = 0;                                    // the warm starts of rbl_step_deterministic extrapolate over ITS steps only
   if ((rc = jt_solve(c, "step_jointed", B, max_iter, rtol, iters, resid))) return rc;
-  if ((rc = flow_record_moments(c, B.x))) return rc;                    // RBL_OPT_RECORD_MOMENTS: lever arms of q^n
-  std::vector<double> U(nb6);
-  if ((rc = copy_d2h(c, U.data(), B.x + n3, sizeof(double) * nb6))) return rc;
-  if (phi && (rc = copy_d2h(c, phi, B.x + nsys, sizeof(double) * nj3))) return rc;
-  if ((rc = finish_and_check(c))) return rc;
+  std::vector<double> U(z.nb6);
+  if ((rc = step_commit(c, B.x, B.x + z.n3, U.data(), B.x + z.nsys, phi, nj3, true))) return rc;   // moments: lever arms of q^n
   if ((rc = rbl_evolve_X_Q(c, U.data()))) return rc;
   // the step is accepted: every motor's angle advances, theta_j += rate_j dt (product and sum rounded one after the other)
   bool moved = false;

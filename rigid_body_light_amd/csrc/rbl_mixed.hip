@@ -379,7 +379,7 @@ struct MxBuf {           // the one workspace of a section 7 entry point (rbl_ct
 
 int mx_reserve(rbl_ctx *c, MxBuf &B)
 {
-  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nsys = n3 + nb6;
+  const size_t nb6 = sizes_of(c).nb6, n3 = sizes_of(c).n3, nsys = n3 + nb6;
   const size_t nlm = B.per == 6 ? 6 * nb6 : 0;           // the masked factors: solves with a mask per component only
   const size_t k = (size_t)B.k;                          // (y1, model, the factors and the mask are shared by the columns)
   const int rc = rbl_dev_reserve(c, c->d_mx, sizeof(double) * (k * (2 * nsys + n3 + 3 * nb6) + n3 + nb6 + nlm) + (size_t)B.per * (size_t)c->S.N_bod);
@@ -399,7 +399,7 @@ int mx_op(rbl_ctx *c, void *user, const double *d_x, double *d_out)
 {
   const MxSolve *m = (const MxSolve *)user;
   const RblBodyState &S = c->S;
-  const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N;
+  const int64_t N = (int64_t)sizes_of(c).N, n3 = 3 * N;
   int rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3); if (rc) return rc;
   if ((rc = apply_M_enqueue(c, S.wall, d_x, (const double *)c->d_pos.p, N, 0, N, (double *)c->d_sad.p))) return rc;
   hipLaunchKernelGGL(k_mx_op_tail, dim3((unsigned)S.N_bod), dim3(MT), 0, c->stream, (const double *)c->d_lever.p,
@@ -412,7 +412,7 @@ int mx_op_multi(rbl_ctx *c, void *user, const double *d_x, double *d_out, int k,
 {
   const MxSolve *m = (const MxSolve *)user;
   const RblBodyState &S = c->S;
-  const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N;
+  const int64_t N = (int64_t)sizes_of(c).N, n3 = 3 * N;
   int rc = rbl_dev_reserve(c, c->d_sad, sizeof(double) * (size_t)n3 * (size_t)k); if (rc) return rc;
   if ((rc = apply_M_multi_enqueue(c, S.wall, d_x, (const double *)c->d_pos.p, N, k, (double *)c->d_sad.p, pitch, n3))) return rc;
   hipLaunchKernelGGL(k_mx_op_tail, dim3((unsigned)S.N_bod, (unsigned)k), dim3(MT), 0, c->stream, (const double *)c->d_lever.p,
@@ -434,7 +434,7 @@ const double *bf_table_MK(const rbl_ctx *c)
 int mx_pc_cols(rbl_ctx *c, const MxSolve *m, const double *d_in, double *d_out, double *y1, int k, int64_t pitch, unsigned live)
 {
   const RblBodyState &S = c->S;
-  const long n3 = 3 * (long)S.N_bod * S.N_blb;
+  const long n3 = (long)sizes_of(c).n3;
   const double *lev = (const double *)c->d_lever.p;
   const dim3 grid((unsigned)S.N_bod, (unsigned)k), block(MT);
   const int per = m->B->per;
@@ -509,7 +509,7 @@ int mx_solve(rbl_ctx *c, const MxBuf &B, bool have_slip, int n_prescribed, int m
   RblPhase ph_total(c, RBL_T_TOTAL);
   int rc = rbl_prepare_dev(c); if (rc) return rc;                        // resident geometry, the preconditioner of this configuration
   const RblBodyState &S = c->S;
-  const long n3 = 3 * (long)S.N_bod * S.N_blb;
+  const long n3 = (long)sizes_of(c).n3;
   const double *lev = (const double *)c->d_lever.p;
   const dim3 grid((unsigned)S.N_bod), block(MT);
   hipLaunchKernelGGL(k_mx_rhs, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, B.per, (const double *)B.body_in,
@@ -551,7 +551,7 @@ int mx_multi_prepare(rbl_ctx *c, const MxBuf &B)
 int mx_solve_batch(rbl_ctx *c, const MxBuf &B, bool have_slip, int n_prescribed, int kb, int max_iter, double rtol, int *iters, double *resid)
 {
   const RblBodyState &S = c->S;
-  const long nb6 = 6 * (long)S.N_bod, n3 = 3 * (long)S.N_bod * S.N_blb, nsys = n3 + nb6;
+  const long nb6 = (long)sizes_of(c).nb6, n3 = (long)sizes_of(c).n3, nsys = n3 + nb6;
   const double *lev = (const double *)c->d_lever.p;
   const dim3 grid((unsigned)S.N_bod, (unsigned)kb), block(MT);
   hipLaunchKernelGGL(k_mx_rhs, grid, block, 0, c->stream, lev, (const uint8_t *)B.mask, B.per, (const double *)B.body_in,
@@ -566,19 +566,32 @@ int mx_solve_batch(rbl_ctx *c, const MxBuf &B, bool have_slip, int n_prescribed,
   return RBL_OK;
 }
 
-// the workspace with the host's mask (B.per entries per body), body_in and slip in place; model: the force model's loads at the
-// current configuration added to the free slots of body_in and the flow model's term added to the slip (the steps).
-// *have_slip: B.slip holds something (the caller's slip, the term, or their sum)
-int mx_upload(rbl_ctx *c, MxBuf &B, const uint8_t *prescribed, const double *body_in, const double *slip, bool model, int np,
+// the host's mask into the workspace.  Host form: copy_h2d.  Device form: from the context's pinned buffer (idle between the
+// solver's read-backs, which drain the stream): a true asynchronous copy, so the caller's array may go after the call and the
+// stream is not drained for it
+int mx_mask_in(rbl_ctx *c, RblSide side, const MxBuf &B, const uint8_t *prescribed)
+{
+  const size_t nmask = (size_t)B.per * (size_t)c->S.N_bod;
+  if (side == RblSide::Host) return copy_h2d(c, B.mask, prescribed, nmask);
+  void *pin;
+  int rc = pin_buffer(c, nmask, &pin); if (rc) return rc;
+  if (pin) std::memcpy(pin, prescribed, nmask);
+  RBL_HIP(c, hipMemcpyAsync(B.mask, pin ? pin : prescribed, nmask, hipMemcpyHostToDevice, c->stream));
+  if (!pin) RBL_HIP(c, hipStreamSynchronize(c->stream));
+  return RBL_OK;
+}
+
+// the workspace with the host's mask (B.per entries per body) and the caller's body_in and slip (either side) in place; model: the
+// force model's loads at the current configuration added to the free slots of body_in and the flow model's term added to the
+// slip (the steps).  *have_slip: B.slip holds something (the caller's slip, the term, or their sum)
+int mx_upload(rbl_ctx *c, RblSide side, MxBuf &B, const uint8_t *prescribed, const double *body_in, const double *slip, bool model, int np,
               bool *have_slip)
 {
-  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
+  const size_t nb6 = sizes_of(c).nb6;
   int rc = mx_reserve(c, B); if (rc) return rc;
-  if ((rc = copy_h2d(c, B.mask, prescribed, (size_t)B.per * (size_t)c->S.N_bod))) return rc;
-  if ((rc = copy_h2d(c, B.body_in, body_in, sizeof(double) * nb6))) return rc;
-  if (slip && (rc = copy_h2d(c, B.slip, slip, sizeof(double) * n3))) return rc;
-  *have_slip = slip != nullptr;
-  if (model && (rc = flow_add_to_step_slip(c, B.slip, have_slip))) return rc;   // imposed flow and body slip at q^n (section 8)
+  if ((rc = mx_mask_in(c, side, B, prescribed))) return rc;
+  if ((rc = xfer_in(c, side, B.body_in, body_in, sizeof(double) * nb6))) return rc;
+  if ((rc = step_slip(c, side, slip, B.slip, model, have_slip))) return rc;
   if (model && ia_any(c) && np < B.per * c->S.N_bod) {    // -K^T f_phys at q^n, free slots only (none free: nothing feels the model)
     RBL_HIP(c, hipMemsetAsync(B.model, 0, sizeof(double) * nb6, c->stream));
     if ((rc = ia_add_to_step_force(c, B.model))) return rc;
@@ -588,47 +601,36 @@ int mx_upload(rbl_ctx *c, MxBuf &B, const uint8_t *prescribed, const double *bod
   return RBL_OK;
 }
 
-// host arrays in, host arrays out; model: add the force model's loads to the free bodies (the step)
+// One solve, the checks done and the device up: the caller's arrays (either side) in, the solve, lambda (may be NULL), U and F out.
+// model (host arrays only): a step's solve -- the models at q^n go in, the moments are recorded, F may be NULL and lambda is not
+// asked for.  The host form ends in a drain and a check of the latched flags; the device form drains where the solver drains
+int mx_core(rbl_ctx *c, RblSide side, const uint8_t *prescribed, int np, const double *body_in, const double *slip, int max_iter,
+            double rtol, bool model, double *lambda, double *U, double *F, int *iters, double *resid, int per)
+{
+  const RblSizes z = sizes_of(c);
+  MxBuf B;
+  B.per = per;
+  bool have_slip;
+  int rc = mx_upload(c, side, B, prescribed, body_in, slip, model, np, &have_slip); if (rc) return rc;
+  if ((rc = mx_solve(c, B, have_slip, np, max_iter, rtol, iters, resid))) return rc;
+  if (model) return step_commit(c, B.x, B.U, U, B.F, F, z.nb6, true);   // moments: lever arms of q^n
+  if (lambda && (rc = xfer_out(c, side, lambda, B.x, sizeof(double) * z.n3))) return rc;
+  if (U && (rc = xfer_out(c, side, U, B.U, sizeof(double) * z.nb6))) return rc;
+  if (F && (rc = xfer_out(c, side, F, B.F, sizeof(double) * z.nb6))) return rc;
+  return side == RblSide::Host ? finish_and_check(c) : RBL_OK;
+}
+
+// host arrays in, host arrays out; model: the step's solve (see mx_core)
 int mx_host(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter, double rtol,
             bool model, double *lambda, double *U, double *F, int *iters, double *resid, int per = 1)
 {
   int np = 0;
   int rc = mx_check(c, who, prescribed, body_in, max_iter, rtol, true, &np, per); if (rc) return rc;
-  if (model && (rc = flow_check(c, c->S.N_bod))) return rc;
-  if ((rc = rbl_dev_init(c))) return rc;
-  if (model) flow_begin_step(c);
-  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
-  MxBuf B;
-  B.per = per;
-  bool have_slip;
-  if ((rc = mx_upload(c, B, prescribed, body_in, slip, model, np, &have_slip))) return rc;
-  if ((rc = mx_solve(c, B, have_slip, np, max_iter, rtol, iters, resid))) return rc;
-  if (model && (rc = flow_record_moments(c, B.x))) return rc;          // the steps: RBL_OPT_RECORD_MOMENTS, lever arms of q^n
-  if (lambda && (rc = copy_d2h(c, lambda, B.x, sizeof(double) * n3))) return rc;
-  if (U && (rc = copy_d2h(c, U, B.U, sizeof(double) * nb6))) return rc;
-  if (F && (rc = copy_d2h(c, F, B.F, sizeof(double) * nb6))) return rc;
-  return finish_and_check(c);
+  if ((rc = model ? step_begin(c) : rbl_dev_init(c))) return rc;
+  return mx_core(c, RblSide::Host, prescribed, np, body_in, slip, max_iter, rtol, model, lambda, U, F, iters, resid, per);
 }
 
-// the host's mask into the workspace of a _dev form.  It goes up from the context's pinned megabyte (idle between the solver's
-// read-backs, which drain the stream): a true asynchronous copy, so the caller's array may go after the call and the stream is not
-// drained for it
-int mx_mask_async(rbl_ctx *c, const MxBuf &B, const uint8_t *prescribed)
-{
-  const size_t nmask = (size_t)B.per * (size_t)c->S.N_bod;
-  constexpr size_t pin_bytes = (size_t)1 << 20;
-  if (nmask <= pin_bytes) {
-    if (!c->h_pin) RBL_HIP(c, hipHostMalloc(&c->h_pin, pin_bytes, hipHostMallocDefault));
-    std::memcpy(c->h_pin, prescribed, nmask);
-    RBL_HIP(c, hipMemcpyAsync(B.mask, c->h_pin, nmask, hipMemcpyHostToDevice, c->stream));
-  } else {
-    RBL_HIP(c, hipMemcpyAsync(B.mask, prescribed, nmask, hipMemcpyHostToDevice, c->stream));
-    RBL_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return RBL_OK;
-}
-
-// device arrays in, device arrays out, the mask (per entries per body) from the host; the stream is drained where the solver drains it
+// device arrays in, device arrays out, the mask (per entries per body) from the host
 int mx_dev(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *d_body_in, const double *d_slip, int max_iter, double rtol,
            double *d_lambda, double *d_U, double *d_F, int *iters, double *resid, int per)
 {
@@ -636,64 +638,38 @@ int mx_dev(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double 
   int np = 0;
   int rc = mx_check(c, who, prescribed, d_body_in, max_iter, rtol, false, &np, per); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
-  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
-  MxBuf B;
-  B.per = per;
-  if ((rc = mx_reserve(c, B))) return rc;
-  if ((rc = mx_mask_async(c, B, prescribed))) return rc;
-  RBL_HIP(c, hipMemcpyAsync(B.body_in, d_body_in, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
-  if (d_slip) RBL_HIP(c, hipMemcpyAsync(B.slip, d_slip, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
-  if ((rc = mx_solve(c, B, d_slip != nullptr, np, max_iter, rtol, iters, resid))) return rc;
-  if (d_lambda) RBL_HIP(c, hipMemcpyAsync(d_lambda, B.x, sizeof(double) * n3, hipMemcpyDeviceToDevice, c->stream));
-  RBL_HIP(c, hipMemcpyAsync(d_U, B.U, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
-  RBL_HIP(c, hipMemcpyAsync(d_F, B.F, sizeof(double) * nb6, hipMemcpyDeviceToDevice, c->stream));
-  return RBL_OK;
+  return mx_core(c, RblSide::Device, prescribed, np, d_body_in, d_slip, max_iter, rtol, false, d_lambda, d_U, d_F, iters, resid, per);
 }
 
 // ---- nrhs right-hand sides under one mask, in lock step, 16 columns a batch (the workspace holds one batch) -------------------------
 // body_in: nrhs vectors of 6 N_bod, slip: NULL or nrhs vectors of 3 N, one after the other; lambda (may be NULL), U, F likewise
-int mx_multi(rbl_ctx *c, const char *who, bool host_form, const uint8_t *prescribed, int nrhs, const double *body_in, const double *slip,
+int mx_multi(rbl_ctx *c, const char *who, RblSide side, const uint8_t *prescribed, int nrhs, const double *body_in, const double *slip,
              int max_iter, double rtol, double *lambda, double *U, double *F, int *iters, double *resid, int per)
 {
   if (!c) return RBL_ERR_ARG;
   if (!U || !F) return rbl_fail(c, RBL_ERR_ARG, std::string(who) + ": U or F is NULL");
   int np = 0;
-  int rc = mx_check(c, who, prescribed, body_in, max_iter, rtol, host_form, &np, per, nrhs); if (rc) return rc;
+  int rc = mx_check(c, who, prescribed, body_in, max_iter, rtol, side == RblSide::Host, &np, per, nrhs); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
-  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb, nsys = n3 + nb6;
+  const RblSizes z = sizes_of(c);
+  const size_t fb = sizeof(double) * z.nb6, vb = sizeof(double) * z.n3;
   MxBuf B;
   B.per = per;
   B.k = nrhs < 16 ? nrhs : 16;
   if ((rc = mx_reserve(c, B))) return rc;
-  if (host_form) rc = copy_h2d(c, B.mask, prescribed, (size_t)per * (size_t)c->S.N_bod);
-  else rc = mx_mask_async(c, B, prescribed);
-  if (rc) return rc;
+  if ((rc = mx_mask_in(c, side, B, prescribed))) return rc;
   RblPhase ph_total(c, RBL_T_TOTAL);
   if ((rc = mx_multi_prepare(c, B))) return rc;
-  const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
   for (int k0 = 0; k0 < nrhs; k0 += 16) {
-    const int kb = nrhs - k0 < 16 ? nrhs - k0 : 16;
-    const double *bi = body_in + (size_t)k0 * nb6, *sl = slip ? slip + (size_t)k0 * n3 : nullptr;
-    if (host_form) {
-      if ((rc = copy_h2d(c, B.body_in, bi, sizeof(double) * nb6 * (size_t)kb))) return rc;
-      if (sl && (rc = copy_h2d(c, B.slip, sl, sizeof(double) * n3 * (size_t)kb))) return rc;
-    } else {
-      RBL_HIP(c, hipMemcpyAsync(B.body_in, bi, sizeof(double) * nb6 * (size_t)kb, d2d, c->stream));
-      if (sl) RBL_HIP(c, hipMemcpyAsync(B.slip, sl, sizeof(double) * n3 * (size_t)kb, d2d, c->stream));
-    }
-    if ((rc = mx_solve_batch(c, B, slip != nullptr, np, kb, max_iter, rtol, iters ? iters + k0 : nullptr, resid ? resid + k0 : nullptr)))
+    const size_t kb = nrhs - k0 < 16 ? nrhs - k0 : 16;
+    if ((rc = xfer_in(c, side, B.body_in, body_in + (size_t)k0 * z.nb6, fb * kb))) return rc;
+    if (slip && (rc = xfer_in(c, side, B.slip, slip + (size_t)k0 * z.n3, vb * kb))) return rc;
+    if ((rc = mx_solve_batch(c, B, slip != nullptr, np, (int)kb, max_iter, rtol, iters ? iters + k0 : nullptr, resid ? resid + k0 : nullptr)))
       return rc;
-    if (host_form) {
-      for (int col = 0; lambda && col < kb; ++col)
-        if ((rc = copy_d2h(c, lambda + (size_t)(k0 + col) * n3, B.x + (size_t)col * nsys, sizeof(double) * n3))) return rc;
-      if ((rc = copy_d2h(c, U + (size_t)k0 * nb6, B.U, sizeof(double) * nb6 * (size_t)kb))) return rc;
-      if ((rc = copy_d2h(c, F + (size_t)k0 * nb6, B.F, sizeof(double) * nb6 * (size_t)kb))) return rc;
-    } else {
-      for (int col = 0; lambda && col < kb; ++col)
-        RBL_HIP(c, hipMemcpyAsync(lambda + (size_t)(k0 + col) * n3, B.x + (size_t)col * nsys, sizeof(double) * n3, d2d, c->stream));
-      RBL_HIP(c, hipMemcpyAsync(U + (size_t)k0 * nb6, B.U, sizeof(double) * nb6 * (size_t)kb, d2d, c->stream));
-      RBL_HIP(c, hipMemcpyAsync(F + (size_t)k0 * nb6, B.F, sizeof(double) * nb6 * (size_t)kb, d2d, c->stream));
-    }
+    for (size_t col = 0; lambda && col < kb; ++col)
+      if ((rc = xfer_out(c, side, lambda + ((size_t)k0 + col) * z.n3, B.x + col * z.nsys, vb))) return rc;
+    if ((rc = xfer_out(c, side, U + (size_t)k0 * z.nb6, B.U, fb * kb))) return rc;
+    if ((rc = xfer_out(c, side, F + (size_t)k0 * z.nb6, B.F, fb * kb))) return rc;
     if ((rc = finish_and_check(c))) return rc;           // the latched device flags, batch by batch
   }
   return RBL_OK;
@@ -736,7 +712,7 @@ int mx_bd_rhs_dev(rbl_ctx *c, const char *who, const uint8_t *prescribed, int pe
     MxBuf B;
     B.per = per;
     if ((rc = mx_reserve(c, B))) return rc;
-    if ((rc = copy_h2d(c, B.mask, prescribed, (size_t)per * (size_t)c->S.N_bod))) return rc;
+    if ((rc = mx_mask_in(c, RblSide::Host, B, prescribed))) return rc;
     d_mask = B.mask;
   }
   return rhs_and_midpoint_core(c, prescribed, d_mask, d_body_in, d_slip, d_W, seed, method, split_rand, delta, d_s, X_half, Q_half, per);
@@ -750,7 +726,7 @@ int mx_bd_rhs_host(rbl_ctx *c, const char *who, const uint8_t *prescribed, int p
   int np = 0;
   int rc = mx_bd_check(c, who, prescribed, body_in, 1, 0.0, delta, &np, per); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
-  const size_t nb6 = 6 * (size_t)c->S.N_bod, n3 = 3 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
+  const size_t nb6 = sizes_of(c).nb6, n3 = sizes_of(c).n3;
   const size_t vb = sizeof(double) * n3, fb = sizeof(double) * nb6;
   if ((rc = rbl_dev_reserve(c, c->d_bd2, (W ? 4 : 1) * vb + fb))) return rc;
   double *dS = (double *)c->d_bd2.p, *dBody = dS + n3, *dW = dBody + nb6;
@@ -768,16 +744,13 @@ int mx_bd_rhs_host(rbl_ctx *c, const char *who, const uint8_t *prescribed, int p
 int mx_bd_step(rbl_ctx *c, const uint8_t *prescribed, int per, int np, const double *body_in, const double *slip, const double *W,
                uint64_t seed, int method, int split_rand, double delta, int max_iter, double rtol, double *F, int *iters, double *resid)
 {
-  int rc;
-  if ((rc = flow_check(c, c->S.N_bod))) return rc;
-  if ((rc = rbl_dev_init(c))) return rc;
-  flow_begin_step(c);
-  const size_t nb6 = 6 * (size_t)c->S.N_bod;
+  int rc = step_begin(c); if (rc) return rc;
   MxBuf B;
   B.per = per;
   double *dW;
   bool have_slip;
-  if ((rc = mx_upload(c, B, prescribed, body_in, slip, true, np, &have_slip))) return rc;   // the models at q^n; forces: free components only
+  // the models at q^n; forces: free components only
+  if ((rc = mx_upload(c, RblSide::Host, B, prescribed, body_in, slip, true, np, &have_slip))) return rc;
   if ((rc = step_upload_W(c, W, &dW))) return rc;
   return step_midpoint(
       c,
@@ -786,11 +759,8 @@ int mx_bd_step(rbl_ctx *c, const uint8_t *prescribed, int per, int np, const dou
                                      Xh, Qh, per);
       },
       [&](double *U) {
-        int r = mx_solve(c, B, true, np, max_iter, rtol, iters, resid);
-        if (!r) r = flow_record_moments(c, B.x);                          // RBL_OPT_RECORD_MOMENTS: lever arms of q^{n+1/2}
-        if (!r) r = copy_d2h(c, U, B.U, sizeof(double) * nb6);
-        if (!r && F) r = copy_d2h(c, F, B.F, sizeof(double) * nb6);
-        return r ? r : finish_and_check(c);
+        const int r = mx_solve(c, B, true, np, max_iter, rtol, iters, resid);
+        return r ? r : step_commit(c, B.x, B.U, U, B.F, F, sizes_of(c).nb6, true);   // moments: lever arms of q^{n+1/2}
       });
 }
 
@@ -808,7 +778,7 @@ int mx_bd_step_entry(rbl_ctx *c, const char *who, int per, const uint8_t *prescr
     // bits (the masked solve goes through another GMRES driver and would differ from it in the last digits); F: the loads it solved
     // with, echoed.  The whole-body step with nobody prescribed goes through the masked solve, as it always has: its bits stay too
     int r = rbl_step_brownian(c, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, iters, resid);
-    if (!r && F && !(r = copy_d2h(c, F, step_force_dev(c), sizeof(double) * 6 * (size_t)c->S.N_bod))) r = finish_and_check(c);
+    if (!r && F && !(r = copy_d2h(c, F, step_force_dev(c), sizeof(double) * sizes_of(c).nb6))) r = finish_and_check(c);
     return r;
   }
   return mx_bd_step(c, prescribed, per, np, body_in, slip, W, seed, method, split_rand, delta, max_iter, rtol, F, iters, resid);
@@ -882,25 +852,25 @@ int rbl_step_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6, const double *bod
 int rbl_solve_mixed_multi(rbl_ctx *c, const uint8_t *prescribed, int nrhs, const double *body_in, const double *slip, int max_iter,
                           double rtol, double *lambda, double *U, double *F, int *iters, double *resid)
 {
-  return mx_multi(c, "solve_mixed_multi", true, prescribed, nrhs, body_in, slip, max_iter, rtol, lambda, U, F, iters, resid, 1);
+  return mx_multi(c, "solve_mixed_multi", RblSide::Host, prescribed, nrhs, body_in, slip, max_iter, rtol, lambda, U, F, iters, resid, 1);
 }
 
 int rbl_solve_mixed_multi_dev(rbl_ctx *c, const uint8_t *prescribed, int nrhs, const double *d_body_in, const double *d_slip, int max_iter,
                               double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid)
 {
-  return mx_multi(c, "solve_mixed_multi_dev", false, prescribed, nrhs, d_body_in, d_slip, max_iter, rtol, d_lambda, d_U, d_F, iters, resid, 1);
+  return mx_multi(c, "solve_mixed_multi_dev", RblSide::Device, prescribed, nrhs, d_body_in, d_slip, max_iter, rtol, d_lambda, d_U, d_F, iters, resid, 1);
 }
 
 int rbl_solve_mixed_dof_multi(rbl_ctx *c, const uint8_t *prescribed6, int nrhs, const double *body_in, const double *slip, int max_iter,
                               double rtol, double *lambda, double *U, double *F, int *iters, double *resid)
 {
-  return mx_multi(c, "solve_mixed_dof_multi", true, prescribed6, nrhs, body_in, slip, max_iter, rtol, lambda, U, F, iters, resid, 6);
+  return mx_multi(c, "solve_mixed_dof_multi", RblSide::Host, prescribed6, nrhs, body_in, slip, max_iter, rtol, lambda, U, F, iters, resid, 6);
 }
 
 int rbl_solve_mixed_dof_multi_dev(rbl_ctx *c, const uint8_t *prescribed6, int nrhs, const double *d_body_in, const double *d_slip,
                                   int max_iter, double rtol, double *d_lambda, double *d_U, double *d_F, int *iters, double *resid)
 {
-  return mx_multi(c, "solve_mixed_dof_multi_dev", false, prescribed6, nrhs, d_body_in, d_slip, max_iter, rtol, d_lambda, d_U, d_F, iters,
+  return mx_multi(c, "solve_mixed_dof_multi_dev", RblSide::Device, prescribed6, nrhs, d_body_in, d_slip, max_iter, rtol, d_lambda, d_U, d_F, iters,
                   resid, 6);
 }
 

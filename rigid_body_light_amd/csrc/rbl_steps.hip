@@ -17,16 +17,21 @@
 
 // ---- whole time steps in one call (what krylov.py's steppers do, for hosts without a Python driver) ----------
 
-static int step_buffers(rbl_ctx *c, int64_t n3, int64_t nb6, double **rhs, double **x, double **slip, double **force)
+RblSizes sizes_of(const rbl_ctx *c)
 {
-  const int64_t nsys = n3 + nb6;
-  int rc = rbl_dev_reserve(c, c->d_step, sizeof(double) * (size_t)(2 * nsys + n3 + nb6));
+  const size_t N = (size_t)c->S.N_bod * (size_t)c->S.N_blb, nb6 = 6 * (size_t)c->S.N_bod;
+  return {N, 3 * N, nb6, 3 * N + nb6};
+}
+
+static int step_buffers(rbl_ctx *c, const RblSizes &z, double **rhs, double **x, double **slip, double **force)
+{
+  int rc = rbl_dev_reserve(c, c->d_step, sizeof(double) * (2 * z.nsys + z.n3 + z.nb6));
   if (rc) return rc;
-  if (c->step_x_size != nsys) { c->step_hist_n = 0; c->step_x_size = nsys; }
+  if (c->step_x_size != (int64_t)z.nsys) { c->step_hist_n = 0; c->step_x_size = (int64_t)z.nsys; }
   *x = (double *)c->d_step.p;
-  *rhs = *x + nsys;
-  *slip = *rhs + nsys;
-  *force = *slip + n3;
+  *rhs = *x + z.nsys;
+  *slip = *rhs + z.nsys;
+  *force = *slip + z.n3;
   return RBL_OK;
 }
 
@@ -34,8 +39,48 @@ static int step_buffers(rbl_ctx *c, int64_t n3, int64_t nb6, double **rhs, doubl
 // share at q^n): the step with component masks echoes them when nothing is prescribed (rbl_mixed.hip)
 const double *step_force_dev(const rbl_ctx *c)
 {
-  const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb, nsys = n3 + (int64_t)6 * c->S.N_bod;
-  return (const double *)c->d_step.p + 2 * nsys + n3;
+  const RblSizes z = sizes_of(c);
+  return (const double *)c->d_step.p + 2 * z.nsys + z.n3;
+}
+
+// ---- the stages the whole-step entry points share (rbl_api_internal.hpp) ---------------------------------------
+
+int step_begin(rbl_ctx *c, const char *missing)
+{
+  int rc = flow_check(c, c->S.N_bod); if (rc) return rc;
+  if ((rc = rbl_dev_init(c))) return rc;
+  if (missing) return rbl_fail(c, RBL_ERR_ARG, missing);
+  flow_begin_step(c);
+  return RBL_OK;
+}
+
+int step_slip(rbl_ctx *c, RblSide side, const double *slip, double *d_slip, bool model, bool *have_slip)
+{
+  int rc;
+  *have_slip = slip != nullptr;
+  if (slip && (rc = xfer_in(c, side, d_slip, slip, sizeof(double) * sizes_of(c).n3))) return rc;
+  return model ? flow_add_to_step_slip(c, d_slip, have_slip) : RBL_OK;   // imposed flow and body slip at q^n (include/rbl.h section 8)
+}
+
+int step_inputs(rbl_ctx *c, const double *F_body, const double *slip, double *d_force, double *d_slip)
+{
+  const RblSizes z = sizes_of(c);
+  bool have_slip;
+  int rc = step_slip(c, RblSide::Host, slip, d_slip, true, &have_slip); if (rc) return rc;
+  if (!have_slip) RBL_HIP(c, hipMemsetAsync(d_slip, 0, sizeof(double) * z.n3, c->stream));
+  if ((rc = copy_h2d(c, d_force, F_body, sizeof(double) * z.nb6))) return rc;
+  return ia_add_to_step_force(c, d_force);                               // the force model at q^n (include/rbl.h section 4)
+}
+
+int step_commit(rbl_ctx *c, const double *d_lambda, const double *d_U, double *U, const double *d_more, double *more, size_t n_more,
+                bool check_flags)
+{
+  int rc = flow_record_moments(c, d_lambda); if (rc) return rc;
+  if ((rc = copy_d2h(c, U, d_U, sizeof(double) * sizes_of(c).nb6))) return rc;
+  if (more && (rc = copy_d2h(c, more, d_more, sizeof(double) * n_more))) return rc;
+  if (check_flags) return finish_and_check(c);
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  return RBL_OK;
 }
 
 // One deterministic time step on the object's own configuration: solve [M -K; K^T 0][lambda; U] = [slip; -F] by
@@ -48,40 +93,29 @@ int rbl_step_deterministic(rbl_ctx *c, const double *F_body, const double *slip,
                            int warm_start, int *iters, double *resid)
 {
   int rc = need_K(c); if (rc) return rc;
-  if ((rc = flow_check(c, c->S.N_bod))) return rc;
-  if ((rc = rbl_dev_init(c))) return rc;
-  if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "step_deterministic: F_body is NULL");
-  flow_begin_step(c);
-  const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb, nb6 = (int64_t)6 * c->S.N_bod;
+  if ((rc = step_begin(c, F_body ? nullptr : "step_deterministic: F_body is NULL"))) return rc;
+  const RblSizes z = sizes_of(c);
   double *rhs, *x, *dslip, *dforce;
-  if ((rc = step_buffers(c, n3, nb6, &rhs, &x, &dslip, &dforce))) return rc;
-  bool have_slip = slip != nullptr;
-  if (slip && (rc = copy_h2d(c, rhs, slip, sizeof(double) * (size_t)n3))) return rc;
-  if ((rc = flow_add_to_step_slip(c, rhs, &have_slip))) return rc;   // imposed flow and body slip at q^n (include/rbl.h section 8)
-  if (!have_slip) RBL_HIP(c, hipMemsetAsync(rhs, 0, sizeof(double) * (size_t)n3, c->stream));
-  if ((rc = copy_h2d(c, dforce, F_body, sizeof(double) * (size_t)nb6))) return rc;
-  if ((rc = ia_add_to_step_force(c, dforce))) return rc;             // the force model at q^n (include/rbl.h section 4)
-  rbl_launch_axpby(c->stream, nb6, -1.0, dforce, 0.0, nullptr, rhs + n3);
-  const int64_t nsys = n3 + nb6;
-  if ((rc = rbl_dev_reserve(c, c->d_hist, sizeof(double) * (size_t)(3 * nsys)))) return rc;
+  if ((rc = step_buffers(c, z, &rhs, &x, &dslip, &dforce))) return rc;
+  if ((rc = step_inputs(c, F_body, slip, dforce, rhs))) return rc;     // the slip is the right-hand side's top as it stands
+  rbl_launch_axpby(c->stream, (int64_t)z.nb6, -1.0, dforce, 0.0, nullptr, rhs + z.n3);
+  if ((rc = rbl_dev_reserve(c, c->d_hist, sizeof(double) * 3 * z.nsys))) return rc;
   double *H = (double *)c->d_hist.p;
-  auto slot = [&](int age) { return H + (size_t)((c->step_hist_head + age) % 3) * (size_t)nsys; };   // age 0 = newest
+  auto slot = [&](int age) { return H + (size_t)((c->step_hist_head + age) % 3) * z.nsys; };   // age 0 = newest
   int order = warm_start < 0 ? 0 : (warm_start > 3 ? 3 : warm_start);
   if (order > c->step_hist_n) order = c->step_hist_n;
-  if (order == 1) RBL_HIP(c, hipMemcpyAsync(x, slot(0), sizeof(double) * (size_t)nsys, hipMemcpyDeviceToDevice, c->stream));
-  if (order == 2) rbl_launch_axpby(c->stream, nsys, 2.0, slot(0), -1.0, slot(1), x);
+  if (order == 1) RBL_HIP(c, hipMemcpyAsync(x, slot(0), sizeof(double) * z.nsys, hipMemcpyDeviceToDevice, c->stream));
+  if (order == 2) rbl_launch_axpby(c->stream, (int64_t)z.nsys, 2.0, slot(0), -1.0, slot(1), x);
   if (order == 3) {
-    rbl_launch_axpby(c->stream, nsys, 3.0, slot(0), -3.0, slot(1), x);
-    rbl_launch_axpby(c->stream, nsys, 1.0, x, 1.0, slot(2), x);
+    rbl_launch_axpby(c->stream, (int64_t)z.nsys, 3.0, slot(0), -3.0, slot(1), x);
+    rbl_launch_axpby(c->stream, (int64_t)z.nsys, 1.0, x, 1.0, slot(2), x);
   }
   if ((rc = rbl_gmres_saddle_dev(c, rhs, max_iter, rtol, x, order > 0 ? 1 : 0, iters, resid))) { c->step_hist_n = 0; return rc; }
   c->step_hist_head = (c->step_hist_head + 2) % 3;                     // the oldest slot becomes the newest
-  RBL_HIP(c, hipMemcpyAsync(slot(0), x, sizeof(double) * (size_t)nsys, hipMemcpyDeviceToDevice, c->stream));
+  RBL_HIP(c, hipMemcpyAsync(slot(0), x, sizeof(double) * z.nsys, hipMemcpyDeviceToDevice, c->stream));
   if (c->step_hist_n < 3) ++c->step_hist_n;
-  if ((rc = flow_record_moments(c, x))) return rc;                     // RBL_OPT_RECORD_MOMENTS: lever arms of q^n
-  std::vector<double> U((size_t)nb6);
-  if ((rc = copy_d2h(c, U.data(), x + n3, sizeof(double) * (size_t)nb6))) return rc;
-  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  std::vector<double> U(z.nb6);
+  if ((rc = step_commit(c, x, x + z.n3, U.data(), nullptr, nullptr, 0, false))) return rc;   // moments: lever arms of q^n
   return rbl_evolve_X_Q(c, U.data());
 }
 
@@ -91,7 +125,7 @@ int step_upload_W(rbl_ctx *c, const double *W, double **d_W)
 {
   *d_W = nullptr;
   if (!W) return RBL_OK;
-  const size_t bytes = sizeof(double) * 9 * (size_t)c->S.N_bod * (size_t)c->S.N_blb;
+  const size_t bytes = sizeof(double) * 3 * sizes_of(c).n3;
   int rc = rbl_dev_reserve(c, c->d_W, bytes); if (rc) return rc;
   *d_W = (double *)c->d_W.p;
   return copy_h2d(c, *d_W, W, bytes);
@@ -121,29 +155,18 @@ int rbl_step_brownian(rbl_ctx *c, const double *F_body, const double *slip, cons
                       int split_rand, double delta, int max_iter, double rtol, int *iters, double *resid)
 {
   int rc = need_K(c); if (rc) return rc;
-  if ((rc = flow_check(c, c->S.N_bod))) return rc;
-  if ((rc = rbl_dev_init(c))) return rc;
-  if (!F_body) return rbl_fail(c, RBL_ERR_ARG, "step_brownian: F_body is NULL");
-  flow_begin_step(c);
-  const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb, nb6 = (int64_t)6 * c->S.N_bod;
+  if ((rc = step_begin(c, F_body ? nullptr : "step_brownian: F_body is NULL"))) return rc;
+  const RblSizes z = sizes_of(c);
   double *rhs, *x, *dslip, *dforce, *dW;
-  if ((rc = step_buffers(c, n3, nb6, &rhs, &x, &dslip, &dforce))) return rc;
-  bool have_slip = slip != nullptr;
-  if (slip && (rc = copy_h2d(c, dslip, slip, sizeof(double) * (size_t)n3))) return rc;
-  if ((rc = flow_add_to_step_slip(c, dslip, &have_slip))) return rc;   // imposed flow and body slip at q^n, where RHS_and_Midpoint takes its Slip
-  if (!have_slip) RBL_HIP(c, hipMemsetAsync(dslip, 0, sizeof(double) * (size_t)n3, c->stream));
-  if ((rc = copy_h2d(c, dforce, F_body, sizeof(double) * (size_t)nb6))) return rc;
-  if ((rc = ia_add_to_step_force(c, dforce))) return rc;             // the force model at q^n, where RHS_and_Midpoint takes its Force
+  if ((rc = step_buffers(c, z, &rhs, &x, &dslip, &dforce))) return rc;
+  if ((rc = step_inputs(c, F_body, slip, dforce, dslip))) return rc;   // at q^n, where RHS_and_Midpoint takes its Slip and Force
   if ((rc = step_upload_W(c, W, &dW))) return rc;
   return step_midpoint(
       c,
       [&](double *Xh, double *Qh) { return rbl_RHS_and_Midpoint_dev(c, dslip, dforce, dW, seed, method, split_rand, delta, rhs, Xh, Qh); },
       [&](double *U) {
-        int r = rbl_gmres_saddle_dev(c, rhs, max_iter, rtol, x, 0, iters, resid);
-        if (!r) r = flow_record_moments(c, x);                          // RBL_OPT_RECORD_MOMENTS: lever arms of q^{n+1/2}
-        if (!r) r = copy_d2h(c, U, x + n3, sizeof(double) * (size_t)nb6);
-        if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = RBL_ERR_HIP;
-        return r;
+        const int r = rbl_gmres_saddle_dev(c, rhs, max_iter, rtol, x, 0, iters, resid);
+        return r ? r : step_commit(c, x, x + z.n3, U, nullptr, nullptr, 0, false);   // moments: lever arms of q^{n+1/2}
       });
 }
 
@@ -193,7 +216,7 @@ static int on_displaced_copies(rbl_ctx *c, const double *dq, double delta, Fn &&
 static int m_rfd_dir(rbl_ctx *c, const double *d_W, const double *dq, double delta, double *d_out, double *d_r, double *d_work)
 {
   RblPhase ph_total(c, RBL_T_TOTAL);
-  const int64_t N = (int64_t)c->S.N_bod * c->S.N_blb, n3 = 3 * N;
+  const int64_t N = (int64_t)sizes_of(c).N, n3 = 3 * N;
   double *dM[2] = {d_work, d_work + n3};
   const int rc = at_displaced_config(c, dq, delta, [&](int sgn) {
     const int r = positions_dev(c, 0, c->S.N_bod, d_r);
@@ -208,8 +231,7 @@ static int m_rfd_dir(rbl_ctx *c, const double *d_W, const double *dq, double del
 // products on the GPU at the two displaced configurations, the quotient down
 static int m_rfd_host(rbl_ctx *c, const double *W, uint64_t seed, const double *U, double delta, double *out)
 {
-  const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb;
-  const size_t vb = sizeof(double) * (size_t)n3;
+  const size_t n3 = sizes_of(c).n3, vb = sizeof(double) * n3;
   int rc;
   if ((rc = rbl_dev_reserve(c, c->d_W, vb))) return rc;
   if ((rc = rbl_dev_reserve(c, c->d_r, vb))) return rc;
@@ -218,8 +240,8 @@ static int m_rfd_host(rbl_ctx *c, const double *W, uint64_t seed, const double *
   if (W) {
     if ((rc = copy_h2d(c, c->d_W.p, W, vb))) return rc;
   } else {  // rand_vector (:730-741) replaced by the seeded device generator
-    Wh.resize((size_t)n3);
-    rbl_launch_normal(c->stream, seed, 0, n3, (double *)c->d_W.p);
+    Wh.resize(n3);
+    rbl_launch_normal(c->stream, seed, 0, (int64_t)n3, (double *)c->d_W.p);
     if ((rc = copy_d2h(c, Wh.data(), c->d_W.p, vb))) return rc;
     RBL_HIP(c, hipStreamSynchronize(c->stream));
     W = Wh.data();
@@ -273,8 +295,9 @@ int rhs_and_midpoint_core(rbl_ctx *c, const uint8_t *h_mask, const uint8_t *d_ma
                           double *Q_half, int per)
 {
   RblBodyState &S = c->S;
-  const int64_t N = (int64_t)S.N_bod * S.N_blb, n3 = 3 * N, nb6 = (int64_t)6 * S.N_bod;
-  const size_t vb = sizeof(double) * (size_t)n3;
+  const RblSizes z = sizes_of(c);
+  const int64_t N = (int64_t)z.N, n3 = (int64_t)z.n3, nb6 = (int64_t)z.nb6;
+  const size_t vb = sizeof(double) * z.n3;
   int rc;
   if (!d_slip) {
     RBL_HIP(c, hipMemsetAsync(d_s, 0, vb, c->stream));
@@ -337,8 +360,8 @@ int rbl_RHS_and_Midpoint_dev(rbl_ctx *c, const double *d_Slip, const double *d_F
   if ((rc = rbl_dev_init(c))) return rc;
   if (!d_Slip || !d_Force || !d_RHS || !X_half || !Q_half) return rbl_fail(c, RBL_ERR_ARG, "RHS_and_Midpoint: null argument");
   const RblBodyState &S = c->S;
-  const int64_t n3 = (int64_t)3 * S.N_bod * S.N_blb, nb6 = (int64_t)6 * S.N_bod;
-  rbl_launch_axpby(c->stream, nb6, -1.0, d_Force, 0.0, nullptr, d_RHS + n3);          // Force *= -1 (:972)
+  const RblSizes z = sizes_of(c);
+  rbl_launch_axpby(c->stream, (int64_t)z.nb6, -1.0, d_Force, 0.0, nullptr, d_RHS + z.n3);          // Force *= -1 (:972)
   if (S.kBT > 1e-10 && (!(S.dt > 0.0) || !(delta > 0.0)))
     return rbl_fail(c, RBL_ERR_ARG, "RHS_and_Midpoint: dt and delta must be positive");
   return rhs_and_midpoint_core(c, nullptr, nullptr, nullptr, d_Slip, d_W, seed, method, split_rand, delta, d_RHS, X_half, Q_half);
@@ -351,8 +374,7 @@ int rbl_RHS_and_Midpoint(rbl_ctx *c, const double *Slip, const double *Force, co
   int rc = need_K(c); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (!Slip || !Force || !RHS) return rbl_fail(c, RBL_ERR_ARG, "RHS_and_Midpoint: null argument");
-  const int64_t n3 = (int64_t)3 * c->S.N_bod * c->S.N_blb, nb6 = (int64_t)6 * c->S.N_bod;
-  const size_t vb = sizeof(double) * (size_t)n3, fb = sizeof(double) * (size_t)nb6;
+  const size_t n3 = sizes_of(c).n3, nb6 = sizes_of(c).nb6, vb = sizeof(double) * n3, fb = sizeof(double) * nb6;
   if ((rc = rbl_dev_reserve(c, c->d_bd2, (W ? 4 : 1) * vb + 2 * (vb + fb)))) return rc;
   double *dSlip = (double *)c->d_bd2.p, *dForce = dSlip + n3, *dRHS = dForce + nb6, *dW = dRHS + n3 + nb6;
   if ((rc = copy_h2d(c, dSlip, Slip, vb))) return rc;
@@ -369,7 +391,7 @@ int rbl_KTinv_RFD(rbl_ctx *c, const double *W, double delta, double *out)
 {
   int rc = need_K(c); if (rc) return rc;
   if (!W || !(delta > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "KTinv_RFD: need W and delta > 0");
-  const size_t n3 = (size_t)3 * c->S.N_bod * c->S.N_blb;
+  const size_t n3 = sizes_of(c).n3;
   std::vector<double> acc(n3, 0.0), tmp(n3);
   rc = on_displaced_copies(c, W, delta, [&](const RblBodyState &T, double w) {
     rbl_body_KTinv_x_F(T, W, tmp.data());
@@ -395,7 +417,7 @@ int rbl_M_RFD_cfgs(rbl_ctx *c, const double *U, double delta, double *r_plus, do
   int rc = need_config(c); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   if (!U || !r_plus || !r_minus) return rbl_fail(c, RBL_ERR_ARG, "M_RFD_cfgs: null argument");
-  const size_t vb = sizeof(double) * 3 * (size_t)c->S.N_bod * c->S.N_blb;
+  const size_t vb = sizeof(double) * sizes_of(c).n3;
   if ((rc = rbl_dev_reserve(c, c->d_r, vb))) return rc;
   return at_displaced_config(c, U, delta, [&](int sgn) {               // :808, :811
     int r = positions_dev(c, 0, c->S.N_bod, (double *)c->d_r.p);
@@ -410,7 +432,7 @@ int rbl_KT_RFD_from_U(rbl_ctx *c, const double *U, const double *W, double delta
 {
   int rc = need_K(c); if (rc) return rc;
   if (!U || !W || !out || !(delta > 0.0)) return rbl_fail(c, RBL_ERR_ARG, "KT_RFD_from_U: need U, W, out and delta > 0");
-  const size_t nb6 = (size_t)6 * c->S.N_bod;
+  const size_t nb6 = sizes_of(c).nb6;
   std::vector<double> tmp(nb6);
   for (size_t i = 0; i < nb6; ++i) out[i] = 0.0;
   return on_displaced_copies(c, U, delta, [&](const RblBodyState &T, double w) {

@@ -339,44 +339,67 @@ def test_two_calls_give_the_same_bits_and_the_state_query_returns_them(wall, blo
         rb.joint_state()
 
 
+# The second shape, 17 x shell_N_162 = 2754 blobs: a blob vector is 66 096 bytes, the smallest from the shipped structures above the
+# 64 KB at which the host form's copies go through the staging buffer, synchronously; below it (10 x 12) both forms copy
+# asynchronously.  Iterations to 1e-8 there, before the two forms shared their code and since: 24 with the joints, 13 with
+# them off (printed; max_iter 200 is more than twice the larger and below 254).
+def _device_form_gives_the_host_form_s_bits(ctx, c, nb, nblb, max_iter, rtol):
+    import torch
+    body, anchor = jo.chain_set(nb, c["X"], seed=81)
+    ctx.set_joints(body, anchor[:, :3], anchor[:, 3:])
+    j = ctx.joints()
+    assert j["on"] and np.array_equal(j["body"], body) and np.array_equal(j["anchor_b"], anchor[:, 3:])
+    F, slip, crhs = _inputs(nb, nblb, body.shape[0], seed=82)
+    lam, U, phi, its, res = ctx.solve_jointed(F, slip=slip, joint_rhs=crhs, max_iter=max_iter, rtol=rtol)
+    dev = [torch.tensor(v, dtype=torch.float64, device="cuda:0") for v in (F, slip, crhs)]
+    out = [torch.full((n,), float("nan"), dtype=torch.float64, device="cuda:0") for n in (lam.size, U.size, phi.size)]
+    its_d, res_d = ctx.solve_jointed_dev(*(t.data_ptr() for t in dev), max_iter, rtol, *(t.data_ptr() for t in out))
+    ctx.sync_check()
+    torch.cuda.synchronize()
+    print("device form against host form, %d x %d: %d iterations to %.0e, residual %.2e" % (nb, nblb, its, rtol, res))
+    assert (its_d, res_d) == (its, res) and 0 < its < max_iter and res < rtol
+    for host, d in zip((lam, U, phi), out):
+        assert host.tobytes() == d.cpu().numpy().tobytes()
+    gap, phi_s = ctx.joint_state()
+    assert np.array_equal(phi_s.reshape(-1), phi) and np.allclose(gap, jo.geometry(c["X"], c["Q"], body, anchor)[2], rtol=0.0, atol=1e-13)
+    # without slip, joint_rhs and lambda
+    its2, _ = ctx.solve_jointed_dev(dev[0].data_ptr(), None, None, max_iter, rtol, None, out[1].data_ptr(), out[2].data_ptr())
+    ctx.sync_check()
+    assert np.array_equal(out[1].cpu().numpy(), ctx.solve_jointed(F, max_iter=max_iter, rtol=rtol)[1]) and its2 > 0
+    # the joints switched off and a slip given: the plain solve of both forms
+    ctx.set_joints(body, anchor[:, :3], anchor[:, 3:], on=False)
+    lam0, U0, phi0, its0, res0 = ctx.solve_jointed(F, slip=slip, max_iter=max_iter, rtol=rtol)
+    out0 = [torch.full((n,), float("nan"), dtype=torch.float64, device="cuda:0") for n in (lam0.size, U0.size)]
+    its0_d, res0_d = ctx.solve_jointed_dev(dev[0].data_ptr(), dev[1].data_ptr(), None, max_iter, rtol, out0[0].data_ptr(), out0[1].data_ptr(), None)
+    ctx.sync_check()
+    torch.cuda.synchronize()
+    print("   joints off: %d iterations, residual %.2e" % (its0, res0))
+    assert (its0_d, res0_d) == (its0, res0) and 0 < its0 < max_iter and res0 < rtol and phi0.size == 0
+    for host, d in zip((lam0, U0), out0):
+        assert host.tobytes() == d.cpu().numpy().tobytes()
+    return F
+
+
 def test_the_device_form_gives_the_host_form_s_bits_and_an_ensemble_context_is_refused():
     import torch
     from rigid_body_light_amd import make_config
     from rigid_body_light_amd._lib import DeviceContext, RblError
-    nb, nblb = 10, 12
-    c = make_config(nb, nblb, True)
-    ctx = DeviceContext(c["a"], c["eta"], True, cfg=c["cfg"], dt=c["dt"], stream_ptr=torch.cuda.current_stream().cuda_stream)
-    try:
-        ctx._chk(ctx.L.rbl_set_blk_pc(ctx.h, 1))
-        ctx.set_config(c["X"], c["Q"])
-        body, anchor = jo.chain_set(nb, c["X"], seed=81)
-        ctx.set_joints(body, anchor[:, :3], anchor[:, 3:])
-        j = ctx.joints()
-        assert j["on"] and np.array_equal(j["body"], body) and np.array_equal(j["anchor_b"], anchor[:, 3:])
-        F, slip, crhs = _inputs(nb, nblb, body.shape[0], seed=82)
-        lam, U, phi, its, res = ctx.solve_jointed(F, slip=slip, joint_rhs=crhs, max_iter=200, rtol=1e-10)
-        dev = [torch.tensor(v, dtype=torch.float64, device="cuda:0") for v in (F, slip, crhs)]
-        out = [torch.full((n,), float("nan"), dtype=torch.float64, device="cuda:0") for n in (lam.size, U.size, phi.size)]
-        its_d, res_d = ctx.solve_jointed_dev(*(t.data_ptr() for t in dev), 200, 1e-10, *(t.data_ptr() for t in out))
-        ctx.sync_check()
-        torch.cuda.synchronize()
-        assert (its_d, res_d) == (its, res) and 0 < its < 200 and res < 1e-10
-        for host, d in zip((lam, U, phi), out):
-            assert host.tobytes() == d.cpu().numpy().tobytes()
-        gap, phi_s = ctx.joint_state()
-        assert np.array_equal(phi_s.reshape(-1), phi) and np.allclose(gap, jo.geometry(c["X"], c["Q"], body, anchor)[2], rtol=0.0, atol=1e-13)
-        # without slip, joint_rhs and lambda
-        its2, _ = ctx.solve_jointed_dev(dev[0].data_ptr(), None, None, 200, 1e-10, None, out[1].data_ptr(), out[2].data_ptr())
-        ctx.sync_check()
-        assert np.array_equal(out[1].cpu().numpy(), ctx.solve_jointed(F, max_iter=200, rtol=1e-10)[1]) and its2 > 0
-        # a context that holds an ensemble: refused before any work
-        ctx.ensemble_set_config(c["X"][None], c["Q"][None])
-        with pytest.raises(RblError, match="ensemble"):
-            ctx.solve_jointed(F, max_iter=200, rtol=1e-10)
-        with pytest.raises(RblError, match="ensemble"):
-            ctx.step_jointed(F, max_iter=200, rtol=1e-10)
-    finally:
-        ctx.close()
+    for nb, nblb, max_iter, rtol in ((10, 12, 200, 1e-10), (17, 162, 200, 1e-8)):
+        c = make_config(nb, nblb, True)
+        ctx = DeviceContext(c["a"], c["eta"], True, cfg=c["cfg"], dt=c["dt"], stream_ptr=torch.cuda.current_stream().cuda_stream)
+        try:
+            ctx._chk(ctx.L.rbl_set_blk_pc(ctx.h, 1))
+            ctx.set_config(c["X"], c["Q"])
+            F = _device_form_gives_the_host_form_s_bits(ctx, c, nb, nblb, max_iter, rtol)
+            if nb == 10:
+                # a context that holds an ensemble: refused before any work
+                ctx.ensemble_set_config(c["X"][None], c["Q"][None])
+                with pytest.raises(RblError, match="ensemble"):
+                    ctx.solve_jointed(F, max_iter=200, rtol=1e-10)
+                with pytest.raises(RblError, match="ensemble"):
+                    ctx.step_jointed(F, max_iter=200, rtol=1e-10)
+        finally:
+            ctx.close()
 
 
 @pytest.mark.parametrize("wall,block", [(False, True), (True, True), (True, False)])

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """python tools/bench_prescribed.py [--rounds 5] [--cfgs cfg2,cfg3] -- what a solve with prescribed bodies costs next to the
 unconstrained one (include/rbl.h section 7): solve_saddle and solve_mixed with none / a quarter / all of the bodies prescribed, at
-cfg 2 (50 x shell_N_162) and cfg 3 (200 x shell_N_642), wall, block preconditioner, rtol 1e-8, one process, one box.
+cfg 2 (50 x shell_N_162) and cfg 3 (200 x shell_N_642), or with --cfgs cfg1 at cfg 1 (10 x shell_N_12: launch-bound, where added
+host-side work would show); wall, block preconditioner, rtol 1e-8, one process, one box.
 
 Timing: host wall clock around each solve of the host-array entry points (each ends in a stream synchronise), after one untimed
 warm-up solve per case (code loading, the factor build); then `rounds` rounds that alternate the cases.  Per case: iterations,
@@ -12,7 +13,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 import numpy as np
 
-CFGS = {"cfg2": (50, 162), "cfg3": (200, 642)}
+CFGS = {"cfg1": (10, 12), "cfg2": (50, 162), "cfg3": (200, 642)}
 
 
 def main():
