@@ -895,8 +895,9 @@ int rbl_ensemble_step_brownian_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed
  * X[R 3 N_bod], Q[R 4 N_bod], accepted_at[R] (the replica's accepted count then) and, for runs with prescribed bodies, that
  * step's F[R 6 N_bod] (a replica rejected in that very step: its last accepted F, zeros before any).  The frames are written on
  * the device and downloaded once.  Frames after a stop repeat the stopped configuration where their steps were still enqueued;
- * where a status poll ended the enqueuing first, the caller's arrays are left as they were from there on.  Stresslet frames are not recorded, and rbl_ensemble_step_moments is RBL_ERR_STATE after a
- * run until a one-step call has recorded again.
+ * where a status poll ended the enqueuing first, the caller's arrays are left as they were from there on.  Stresslet frames and the flow at probe points are recorded by
+ * rbl_ensemble_run_observed (below), not here, and rbl_ensemble_step_moments is RBL_ERR_STATE after a run until a one-step call has
+ * recorded again.
  *
  * check_every = k > 0: after every k steps the host reads the status block (a few bytes, one stream drain) and stops enqueuing
  * once the run has stopped; 0: never before the end -- a stopped run then still enqueues its remaining steps, which meet the
@@ -1020,6 +1021,79 @@ int rbl_ensemble_run_jointed(rbl_ctx *ctx, const rbl_run_opts *opts, const rbl_r
  * the k with cum_k <= pos < cum_k+1, or -1 for n_phases < 1, a NULL array, a phase_steps entry < 1 or pos outside the cycle.
  * No context. */
 int rbl_run_schedule_phase(const int32_t *phase_steps, int n_phases, int64_t pos);
+
+/* Observers: the flow at probe points and the first moments of lambda, for every replica (rigid_body_light_amd/csrc/rbl_ens_field.hip).
+ *
+ * The field.  For replica r and point p, section 6's definition with the replica's own blobs as sources,
+ *     u_r(x_p) = nf d(z_p) sum_j sum_images M(x_p, r_j + image) d(z_j) lambda_{r,j},
+ * the velocity apply_M would give a force-free blob of radius a at x_p: the same pair block and damping (rbl_set_no_damp is not
+ * read: the ensemble's operator always damps), a point within 1e-12 a of a blob takes the self block, 0 < r < 2a the overlapping
+ * form, with the wall a point at z_p <= 0 gets u = 0 and no error.  With the ensemble's cell on (rbl_ensemble_set_periodic) the
+ * sum runs over the cell's images of every blob: the nearest-image displacement is formed once per (point, blob) as the solver
+ * forms it, the (2 nx + 1)(2 ny + 1) images are the innermost loop, and only the (0, 0) image of a coincident blob is the self
+ * block -- its other images are ordinary pairs.  This is the one flow field the library has in a periodic cell (section 6 refuses
+ * its context's cell).  A blob below the wall is RBL_ERR_BELOW_WALL, a non-finite result RBL_ERR_NONFINITE, both latched in the
+ * replica's own error word: the message names the first failing replica.
+ * One kernel, k_ens_probe: grid (point tiles, R); the replica's N <= 256 blobs are placed from (X, Q, reference configuration)
+ * term for term as k_body_geom places them and staged once per workgroup in LDS (48 B each); one point per lane and register set,
+ * NI sets per lane; every point sums over the blobs in index order, then the images p, then q.  No atomics on doubles: two calls
+ * agree bitwise, replica r of R returns the bits of the R = 1 call, and a point's bits do not depend on the launch geometry.
+ *
+ *   rbl_ensemble_velocity_field      at the ensemble's CURRENT configuration.  points[point_sets 3 P], point_sets 1 (one set for
+ *                                    every replica) or R; lambda[R 3 N] (N = N_bod N_blb; e.g. rbl_ensemble_solve_jointed's);
+ *                                    u[R 3 P].  probe_body = -1: lab points.  probe_body = b >= 0: points are offsets s_p fixed in
+ *                                    body b, placed at X_b + R(Q_b) s_p of the replica's configuration; u stays in lab-frame
+ *                                    components and nothing is subtracted.  Host arrays, synchronous.
+ *   rbl_ensemble_velocity_field_dev  the same with device pointers; the kernel is enqueued on the context's stream and the call
+ *                                    returns once the replicas' error words have been read.
+ *   rbl_ensemble_probe_info          the launch geometry of n_points points on this context's ensemble: points per lane (1, 2 or
+ *                                    4), waves per workgroup (1 .. 4), point tiles.  One function of (n_points, R, CU count).
+ * n_points == 0 does nothing (RBL_OK).  RBL_ERR_ARG: NULL arrays, n_points < 0, point_sets outside {1, R}, probe_body outside
+ * [-1, N_bod), a non-finite coordinate (host form; the message names set and point); RBL_ERR_STATE: no ensemble configuration.
+ *
+ * Observed runs.  rbl_ensemble_run_observed is rbl_ensemble_run (jopts == NULL; jout is then ignored) or rbl_ensemble_run_jointed
+ * with up to two observers evaluated inside every step, on that step's lambda while it lies in the solver's workspace and at the
+ * configuration the solve was taken at -- q^n for deterministic and jointed steps, q^{n+1/2} for the Brownian step, the convention
+ * of RBL_OPT_RECORD_MOMENTS (section 8): the probe kernel when n_probes > 0 (points, point_sets, probe_body as above; body-frame
+ * points follow the body from step to step) and section 8's moments kernel when moments != 0.  Both run just before the update;
+ * the probe kernel's flags go into the replica's error word, so a step with a non-finite field is that replica's failed step.
+ * They enter it (one small launch, k_ens_obs_flags, a thread per replica) only where the step has not failed already: a replica
+ * whose solve has failed -- say, a blob below the wall at the midpoint, which leaves a non-finite lambda -- keeps the word, and
+ * with it first_flags and first_status, that the unobserved run gives it.
+ * One more launch per quantity, k_ens_obs_commit (one thread per entry, after the run's commit), follows the commit's decision
+ * per replica: where the replica committed the step's u and D are added to u_sum / D_sum, in step order, and remembered; on a
+ * recording step the frame takes this step's value, the last accepted one where the replica was rejected in that step, zeros
+ * before any accepted step (frame_F's convention).  Nothing is added from the stopping step on.  The sums divide by accepted[].
+ * A Brownian step's lambda holds the thermal part: u and D are instantaneous values whose MEAN is the measurement, and, as in
+ * section 8, the drift's share of the stress is not added.  The symmetric traceless part of D_sum / accepted is the mean stresslet.
+ * The observers are arguments, never state: rbl_ensemble_step_moments stays RBL_ERR_STATE after a plain run and is untouched
+ * after a jointed one.  With n_probes == 0 and moments == 0 the call is the underlying run, bit for bit and launch for launch.
+ * Refused before any device work, rbl_last_error naming the argument -- RBL_ERR_ARG: NULL obs or oout or a wrong size,
+ * n_probes < 0, points NULL while n_probes > 0, point_sets outside {1, R}, probe_body outside [-1, N_bod), a non-finite
+ * coordinate (set and point named), frame_u (n_probes > 0) or frame_D (moments) NULL while stride > 0 records frames; then
+ * everything the underlying run refuses.  u_sum and D_sum may be NULL. */
+typedef struct rbl_run_obs_opts {
+  int64_t size;               /* sizeof(rbl_run_obs_opts) */
+  int32_t n_probes;           /* P >= 0; 0: no field */
+  int32_t point_sets;         /* 1 or R (read while n_probes > 0) */
+  int32_t probe_body;         /* -1: lab points; b >= 0: offsets fixed in body b */
+  int32_t moments;            /* != 0: first moments of every step's lambda */
+  const double *points;       /* [point_sets 3 P] */
+} rbl_run_obs_opts;
+typedef struct rbl_run_obs_out {
+  int64_t size;               /* sizeof(rbl_run_obs_out) */
+  double *u_sum;              /* [R 3 P] */
+  double *D_sum;              /* [R 9 N_bod] */
+  double *frame_u;            /* [n_frames R 3 P] */
+  double *frame_D;            /* [n_frames R 9 N_bod] */
+} rbl_run_obs_out;
+int rbl_ensemble_velocity_field(rbl_ctx *ctx, const double *points, int64_t n_points, int point_sets, int probe_body,
+                                const double *lambda, double *u);
+int rbl_ensemble_velocity_field_dev(rbl_ctx *ctx, const double *d_points, int64_t n_points, int point_sets, int probe_body,
+                                    const double *d_lambda, double *d_u);
+int rbl_ensemble_probe_info(const rbl_ctx *ctx, int64_t n_points, int *ni, int *waves, int64_t *tiles);
+int rbl_ensemble_run_observed(rbl_ctx *ctx, const rbl_run_opts *opts, const rbl_run_joint_opts *jopts, const rbl_run_obs_opts *obs,
+                              rbl_run_out *out, rbl_run_joint_out *jout, rbl_run_obs_out *oout);
 
 /* ===================================================================== */
 /* 6. Fluid velocity at arbitrary points (rigid_body_light_amd/csrc/rbl_field.hip) */

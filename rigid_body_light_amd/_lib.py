@@ -145,6 +145,10 @@ def lib(path=None):
         L.rbl_ensemble_step_jointed.argtypes = [vp, vp, vp, vp, dbl, C.c_int, dbl, vp, vp, vp]
         L.rbl_ensemble_joint_state.argtypes = [vp, vp, vp, vp]
         L.rbl_ensemble_joints_fit.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(i64)]
+        L.rbl_ensemble_run_observed.argtypes = [vp, C.POINTER(RunOpts), C.POINTER(RunJointOpts), C.POINTER(RunObsOpts), C.POINTER(RunOut),
+                                                C.POINTER(RunJointOut), C.POINTER(RunObsOut)]
+        L.rbl_ensemble_velocity_field.argtypes = L.rbl_ensemble_velocity_field_dev.argtypes = [vp, vp, i64, C.c_int, C.c_int, vp, vp]
+        L.rbl_ensemble_probe_info.argtypes = [vp, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
         L.rbl_velocity_field.argtypes = [vp, vp, i64, vp, vp, i64, vp]
         L.rbl_velocity_field_dev.argtypes = [vp, vp, i64, vp, vp, i64, vp]
         L.rbl_velocity_field_info.argtypes = [vp, i64, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
@@ -483,6 +487,17 @@ class RunJointOut(C.Structure):
                 ("frame_theta", C.c_void_p), ("frame_phi", C.c_void_p), ("frame_gap", C.c_void_p)]
 
 
+class RunObsOpts(C.Structure):
+    """rbl_run_obs_opts (include/rbl.h section 5)"""
+    _fields_ = [("size", C.c_int64), ("n_probes", C.c_int32), ("point_sets", C.c_int32), ("probe_body", C.c_int32),
+                ("moments", C.c_int32), ("points", C.c_void_p)]
+
+
+class RunObsOut(C.Structure):
+    """rbl_run_obs_out (include/rbl.h section 5)"""
+    _fields_ = [("size", C.c_int64), ("u_sum", C.c_void_p), ("D_sum", C.c_void_p), ("frame_u", C.c_void_p), ("frame_D", C.c_void_p)]
+
+
 RUN_STOP, RUN_REJECT, RUN_CHECK_DEFAULT = 0, 1, 64
 
 
@@ -496,8 +511,14 @@ class RunResult:
     A run with hard joints (DeviceContext.ensemble_run_jointed, Ensemble.run_jointed) adds theta (R, n_joints), the angles it
     leaves, cycle_pos (R,), the positions in the motor schedule at its end, phi_sum and phi_mean (R, n_joints, 3) over the accepted
     steps (phi_mean NaN where nothing was accepted) and the frames theta (n_frames, R, n_joints), phi and gap (n_frames, R,
-    n_joints, 3), here as frame_theta, frame_phi and frame_gap; all of them None for other runs"""
+    n_joints, 3), here as frame_theta, frame_phi and frame_gap; all of them None for other runs.
+    A run with observers (DeviceContext.ensemble_run_observed; Ensemble.run / run_jointed with probes or moments) adds, for P probe
+    points, u_sum (R, P, 3), the field summed over the replica's accepted steps in step order, u_mean = u_sum / accepted (zeros,
+    not NaN, where nothing was accepted) and the frames frame_u (n_frames, R, P, 3); with moments D_sum, D_mean (R, N_bod, 3, 3),
+    stresslet_mean (the symmetric traceless part of D_mean) and frame_D (n_frames, R, N_bod, 3, 3).  A frame holds its step's value,
+    or the replica's last accepted one where it was rejected in that step (zeros before any).  None for runs without them"""
     theta = cycle_pos = phi_sum = phi_mean = frame_theta = frame_phi = frame_gap = None
+    u_sum = u_mean = frame_u = D_sum = D_mean = stresslet_mean = frame_D = None
 
     def __repr__(self):
         return "RunResult(steps_done=%d, stopped_at=%d, accepted=%d..%d, rejected=%d)" % (
@@ -1412,6 +1433,13 @@ class DeviceContext:
         whose status and message it carries; nothing is raised here for such a run (Ensemble.run does).  F_body (6 N_bod,) or
         (R, 6 N_bod) for free bodies, or prescribed (N_bod,) / (R, N_bod) with body_in -- per=6: a mask per velocity component,
         (N_bod, 6) / (R, N_bod, 6), deterministic runs only --; on_error: RUN_STOP or RUN_REJECT"""
+        return self._ensemble_run(None, n_steps, F_body=F_body, prescribed=prescribed, body_in=body_in, brownian=brownian, seed=seed, stride=stride,
+                                  on_error=on_error, check_every=check_every, slip=slip, split_rand=split_rand, delta=delta, max_iter=max_iter,
+                                  rtol=rtol, per=per)
+
+    def _ensemble_run(self, obs, n_steps, F_body=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error=RUN_STOP,
+                      check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8, per=1):
+        """ensemble_run's body, shared with ensemble_run_observed (obs: its observers, None for the plain run)"""
         import numpy as np
         R, nb = self.ensemble_info()
         if R == 0:
@@ -1458,7 +1486,7 @@ class DeviceContext:
         out.frame_X, out.frame_Q, out.frame_accepted_at = res.X.ctypes.data, res.Q.ctypes.data, res.accepted_at.ctypes.data
         out.frame_F = res.F.ctypes.data if masked else None
         out.stopped_at = out.stop_replica = -1       # a refused call leaves them so
-        rc = self.L.rbl_ensemble_run(self.h, C.byref(o), C.byref(out))
+        rc = self._run_call(o, None, out, None, res, obs)
         res.steps_done, res.stopped_at, res.stop_replica = out.steps_done, out.stopped_at, out.stop_replica
         res.status, res.error = rc, None
         if rc != 0:
@@ -1471,6 +1499,87 @@ class DeviceContext:
                 res.F_mean = np.where(res.accepted[:, None] > 0, res.F_sum / res.accepted[:, None], np.nan)
         return res, rc
 
+    def _run_call(self, o, jo, out, jout, res, obs):
+        """the one place a run enters the library: rbl_ensemble_run / rbl_ensemble_run_jointed as ever, or, with observers (obs:
+        ensemble_run_observed's (points, probe_body, moments)), rbl_ensemble_run_observed, whose records go onto res"""
+        import numpy as np
+        if obs is None:
+            if jo is None:
+                return self.L.rbl_ensemble_run(self.h, C.byref(o), C.byref(out))
+            return self.L.rbl_ensemble_run_jointed(self.h, C.byref(o), C.byref(jo), C.byref(out), C.byref(jout))
+        pts, body, moments = obs
+        R, nb = self.ensemble_info()
+        nf = o.n_steps // o.stride if o.stride > 0 else 0
+        oo, oq = RunObsOpts(), RunObsOut()
+        oo.size, oq.size = C.sizeof(RunObsOpts), C.sizeof(RunObsOut)
+        oo.probe_body, oo.moments = int(body), int(bool(moments))
+        if pts is not None:
+            P = pts.shape[-2]
+            oo.n_probes, oo.point_sets, oo.points = P, (1 if pts.ndim == 2 else pts.shape[0]), pts.ctypes.data
+            if P:
+                res.u_sum, res.frame_u = np.zeros((R, P, 3)), np.zeros((nf, R, P, 3))
+                oq.u_sum, oq.frame_u = res.u_sum.ctypes.data, res.frame_u.ctypes.data
+        if moments:
+            res.D_sum, res.frame_D = np.zeros((R, nb, 3, 3)), np.zeros((nf, R, nb, 3, 3))
+            oq.D_sum, oq.frame_D = res.D_sum.ctypes.data, res.frame_D.ctypes.data
+        return self.L.rbl_ensemble_run_observed(self.h, C.byref(o), None if jo is None else C.byref(jo), C.byref(oo), C.byref(out),
+                                                None if jout is None else C.byref(jout), C.byref(oq))
+
+    def ensemble_run_observed(self, n_steps, probes=None, probe_body=None, moments=False, jointed=False, **run_args):
+        """a run with observers (rbl_ensemble_run_observed) -> (RunResult, status) as ensemble_run returns them: run_args are
+        ensemble_run's keywords, or with jointed=True ensemble_run_jointed's.  probes: (P, 3), one set of points for every replica,
+        or (R, P, 3); probe_body=None: lab points, b: offsets fixed in body b that follow it.  The result gains u_sum, u_mean,
+        frame_u and, with moments, D_sum, D_mean, stresslet_mean, frame_D (RunResult).  Nothing asked for: the underlying run"""
+        import numpy as np
+        pts = None
+        if probes is not None:
+            pts = np.ascontiguousarray(probes, dtype=np.float64)
+            if pts.ndim not in (2, 3) or pts.shape[-1] != 3:
+                raise ValueError("ensemble_run_observed: probes must have shape (P, 3) or (R, P, 3); got %s" % (pts.shape,))
+        obs = (pts, -1 if probe_body is None else int(probe_body), bool(moments))
+        run = self._ensemble_run_jointed if jointed else self._ensemble_run
+        res, rc = run(obs, n_steps, **run_args)
+        acc = res.accepted.astype(np.float64)
+        div = np.where(acc > 0, acc, 1.0)                  # a replica that accepted nothing has zero sums: its means are zeros
+        if res.u_sum is not None:
+            res.u_mean = res.u_sum / div[:, None, None]
+        if res.D_sum is not None:
+            res.D_mean = res.D_sum / div[:, None, None, None]
+            sym = 0.5 * (res.D_mean + np.swapaxes(res.D_mean, -1, -2))
+            res.stresslet_mean = sym - np.trace(sym, axis1=-2, axis2=-1)[..., None, None] * np.eye(3) / 3.0
+        return res, rc
+
+    def ensemble_velocity_field(self, points, lam, body=None):
+        """the flow every replica's blob forces lam (R, 3 N) drive at points (P, 3) -- one set for every replica -- or (R, P, 3), at
+        the ensemble's current configuration and in its cell (rbl_ensemble_velocity_field) -> (R, P, 3).  body=b: the points are
+        offsets fixed in body b of each replica"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        if R == 0:
+            self._chk(self.L.rbl_ensemble_get_config(self.h, None, None))       # the state error, as every ensemble call gives it
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        if pts.ndim not in (2, 3) or pts.shape[-1] != 3:
+            raise ValueError("ensemble_velocity_field: points must have shape (P, 3) or (R, P, 3); got %s" % (pts.shape,))
+        n3 = 3 * nb * self._sizes()[1]
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        if lam.size != R * n3:
+            raise ValueError("ensemble_velocity_field: lam must hold R * 3 N = %d values; got shape %s" % (R * n3, lam.shape))
+        P = pts.shape[-2]
+        u = np.empty((R, P, 3))
+        self._chk(self.L.rbl_ensemble_velocity_field(self.h, pts.ctypes.data, P, 1 if pts.ndim == 2 else pts.shape[0],
+                                                     -1 if body is None else int(body), lam.ctypes.data, u.ctypes.data))
+        return u
+
+    def ensemble_velocity_field_dev(self, d_points, n_points, point_sets, d_lam, d_out, body=None):
+        """the same on device addresses; returns once the replicas' error words have been read"""
+        self._chk(self.L.rbl_ensemble_velocity_field_dev(self.h, d_points, n_points, point_sets, -1 if body is None else int(body), d_lam, d_out))
+
+    def ensemble_probe_info(self, n_points):
+        """(points per lane NI, waves per workgroup, point tiles) of the probe kernel's launch for n_points points per replica"""
+        ni, wv, tl = C.c_int(0), C.c_int(0), C.c_int64(0)
+        self._chk(self.L.rbl_ensemble_probe_info(self.h, n_points, C.byref(ni), C.byref(wv), C.byref(tl)))
+        return ni.value, wv.value, tl.value
+
     def ensemble_run_jointed(self, n_steps, F_body, slip=None, joint_velocity=None, gamma=1.0, phase_steps=None, phase_rates=None,
                              cycle_start=None, stride=0, on_error=RUN_STOP, check_every=RUN_CHECK_DEFAULT, max_iter=50, rtol=1.0e-8,
                              brownian=False, prescribed=None, per=0):
@@ -1479,6 +1588,14 @@ class DeviceContext:
         The motor schedule: phase_steps (n_phases,) integers and phase_rates (n_phases, n_joints) or (n_phases, R, n_joints), both
         None for the stored rates; cycle_start None, an integer or (R,) integers.  brownian, prescribed and per exist so that the
         library's refusals can be reached; nothing else is offered through them"""
+        return self._ensemble_run_jointed(None, n_steps, F_body, slip=slip, joint_velocity=joint_velocity, gamma=gamma, phase_steps=phase_steps,
+                                          phase_rates=phase_rates, cycle_start=cycle_start, stride=stride, on_error=on_error,
+                                          check_every=check_every, max_iter=max_iter, rtol=rtol, brownian=brownian, prescribed=prescribed, per=per)
+
+    def _ensemble_run_jointed(self, obs, n_steps, F_body, slip=None, joint_velocity=None, gamma=1.0, phase_steps=None, phase_rates=None,
+                              cycle_start=None, stride=0, on_error=RUN_STOP, check_every=RUN_CHECK_DEFAULT, max_iter=50, rtol=1.0e-8,
+                              brownian=False, prescribed=None, per=0):
+        """ensemble_run_jointed's body, shared with ensemble_run_observed (obs: its observers, None for the plain run)"""
         import numpy as np
         R, nb = self.ensemble_info()
         if R == 0:
@@ -1536,7 +1653,7 @@ class DeviceContext:
         jout.size = C.sizeof(RunJointOut)
         jout.theta, jout.cycle_pos, jout.phi_sum = res.theta.ctypes.data, res.cycle_pos.ctypes.data, res.phi_sum.ctypes.data
         jout.frame_theta, jout.frame_phi, jout.frame_gap = res.frame_theta.ctypes.data, res.frame_phi.ctypes.data, res.frame_gap.ctypes.data
-        rc = self.L.rbl_ensemble_run_jointed(self.h, C.byref(o), C.byref(jo), C.byref(out), C.byref(jout))
+        rc = self._run_call(o, jo, out, jout, res, obs)
         res.steps_done, res.stopped_at, res.stop_replica = out.steps_done, out.stopped_at, out.stop_replica
         res.status, res.error = rc, None
         if rc != 0:

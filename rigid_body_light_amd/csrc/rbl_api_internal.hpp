@@ -9,6 +9,7 @@
 //   rbl_steps.hip     whole time steps, the stochastic midpoint scheme (free and mixed), random finite differences
 //   rbl_forces.hip    configuration-dependent forces (weight, wall and steric repulsion, tabulated potentials, traps)
 //   rbl_ensemble.hip  ensembles of independent replicas of one small system
+//   rbl_ens_field.hip the flow at probe points of every replica of an ensemble, the observers' share of a run's commit
 //   rbl_field.hip     the fluid velocity at arbitrary points from blob forces
 //   rbl_mixed.hip     prescribed kinematics: held or driven bodies among free ones, the loads that takes; the entry points of their Brownian step
 //   rbl_flow.hip      imposed linear flow and body-frame slip added to every step's slip, first moments of the blob forces
@@ -213,6 +214,44 @@ void flow_launch_moments(rbl_ctx *c, const double *d_lever, const double *d_Q, c
 void flow_begin_step(rbl_ctx *c);
 // RBL_OPT_RECORD_MOMENTS: the moments of d_lambda at the configuration the context is at; no-op while the option is off
 int flow_record_moments(rbl_ctx *c, const double *d_lambda);
+
+// ---- rbl_ensemble.hip / rbl_ens_field.hip ---------------------------------------------------------------------------
+// The ensemble as the one-shot field reads it: the refusals that look at the context's state alone (no ensemble, a changed
+// structure, a communicator; `who` leads the message), then -- the device touched -- the current configuration of all replicas,
+// the reference configuration, the cell (checked as a step checks it at use)
+struct RblEnsView {
+  const double *X, *Q, *cfg;
+  int R, Nb, nbl;
+  bool cell;
+  RblSmallCell C;
+};
+int ens_state_refusals(rbl_ctx *c, const char *who);
+int ens_view(rbl_ctx *c, RblEnsView *v);
+// One launch of the probe kernel (include/rbl.h section 5, observers): u[R 3 P] of P points per replica from the blob forces lam
+// (replica r's at lam + r lam_stride) at the configuration (X, Q) of all R replicas.  pts_stride: 0 for one shared point set,
+// 3 P for one per replica; body >= 0: the points are offsets fixed in that body.  rerr: one error word per replica
+struct RblEnsProbe {
+  const double *X, *Q, *cfg;
+  const double *lam;
+  long lam_stride;
+  const double *pts;
+  long pts_stride;
+  double *u;
+  unsigned *rerr;
+  int Nb, nbl, P, body;
+};
+// a non-finite coordinate of points[sets 3 P] (host) is RBL_ERR_ARG naming `who`, the set and the point
+int ens_points_check(rbl_ctx *c, const char *who, const double *points, int64_t n_points, int sets);
+struct RblEnsProbeGeom { int NI, waves; int64_t tiles; };
+RblEnsProbeGeom ens_probe_geometry(int64_t n_points, int R, int n_cu);
+void ens_probe_launch(hipStream_t st, const RblParams &P, bool wall, const RblSmallCell *cell, const RblEnsProbe &A, int R, int n_cu);
+// a run's step, behind ens_probe_launch with rerr = d_oerr (R words, zero before the run's first step): rerr[r] = oerr[r] where
+// rerr[r] is still clear, oerr cleared again
+void ens_obs_flags_launch(hipStream_t st, unsigned *d_rerr, unsigned *d_oerr, int R);
+// The observers' share of a run's commit, one thread per entry of n = R per_rep: where replica r committed (*stopped == 0 and
+// vflag[r] == 0) last = step and sum += step; frame (may be NULL) = last
+void ens_obs_commit_launch(hipStream_t st, const int *d_stopped, const unsigned *d_vflag, const double *d_step, double *d_last,
+                           double *d_sum, double *d_frame, long per_rep, long n);
 
 // ---- rbl_periodic.hip ---------------------------------------------------------------------------------------------
 bool periodic_on(const rbl_ctx *c);           // a cell is set and switched on

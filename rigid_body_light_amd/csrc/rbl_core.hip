@@ -94,7 +94,9 @@ int rbl_dev_init(rbl_ctx *c)
 //   d_ens_w  ia region                                     as d_ia: ia_eval_batch runs k_body_neighbours first
 //   d_ens_run status block, counters, first error words    hipMemsetAsync at the start of ens_run; the verdict words by
 //                                                          k_ens_verdict before k_ens_commit reads them, every step; frame counts by
-//                                                          k_ens_commit (only the frames of enqueued steps are downloaded)
+//                                                          k_ens_commit (only the frames of enqueued steps are downloaded); the observers'
+//                                                          flag words: hipMemsetAsync at the start of ens_run, cleared again by
+//                                                          k_ens_obs_flags every step
 enum { RBL_BUF_PERSIST = 0, RBL_BUF_SCRATCH = 1 };
 struct RblBufRow { RblDevBuf rbl_ctx::*buf; int kind; };
 static const RblBufRow kDevBufs[] = {
@@ -149,6 +151,7 @@ static const RblBufRow kDevBufs[] = {
     {&rbl_ctx::d_ens, RBL_BUF_PERSIST},           // ensemble configurations
     {&rbl_ctx::d_ens_w, RBL_BUF_SCRATCH},         // ensemble step workspace: reserved at the start of each ensemble entry point
     {&rbl_ctx::d_ens_run, RBL_BUF_SCRATCH},       // ensemble run: inputs, counters and frames, reserved at the start of rbl_ensemble_run
+    {&rbl_ctx::d_ens_obs, RBL_BUF_SCRATCH},       // ensemble velocity field: reserved at its start, within one call (error words: hipMemsetAsync before the launch)
     {&rbl_ctx::d_vf, RBL_BUF_SCRATCH},            // velocity field, host form: reserved at its start, within one call
     {&rbl_ctx::d_vfw, RBL_BUF_SCRATCH},           // velocity field: packed sources and slabs, reserved right before its launches
     {&rbl_ctx::d_mx, RBL_BUF_SCRATCH},            // mixed solve: reserved once, at the start of each section 7 entry point

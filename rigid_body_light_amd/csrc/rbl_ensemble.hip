@@ -51,6 +51,15 @@
 //                             schedule, the sum of phi, the next step's rates into the joint table; the frame's theta and phi
 // (k_ens_jt_rates before the first step; k_ens_jt_geom for the gaps of a recording step).
 //
+// With observers (rbl_ensemble_run_observed; the kernels are in rbl_ens_field.hip): the same loop, and just before k_ens_evolve of
+// every step -- on the step's lambda, the top of every replica's x, at the configuration the solve was taken at --
+//   k_first_moments           (moments) the step's D of every body into the run's buffer
+//   k_ens_probe               (n_probes > 0) the fluid velocity at the probe points of every replica, its flags into words of its own
+//   k_ens_obs_flags           (n_probes > 0) per replica: those flags into rerr, unless the replica's step has failed already
+// and after the commit, once per quantity,
+//   k_ens_obs_commit          per entry: sum += step and last = step where the replica committed; the frame takes last
+// The observers are an argument (EnsObs in EnsStepIn), never context state: without them nothing here launches anything else.
+//
 // In a periodic cell (rbl_ensemble_set_periodic; the cell's state and checks are in rbl_periodic.hip): the same launches with the
 // cell's instantiations -- k_gmres_small_per (rbl_small_per.hip) and k_ens_rfd_rhs<true, true> (the image sum inside rbl_small_pair_sweep),
 // k_build_M_per for the dense root, the minimum-image force kernels (ia_eval_batch passes the ensemble's cell).  The jointed calls
@@ -666,12 +675,23 @@ int ens_check_solver(rbl_ctx *c, int max_iter)
 // whether w.jr holds joint rows the caller gave, and the caller's name for a refusal
 struct EnsJtStep { const char *who; RblEnsJoints T; double coef; bool have_jr; };
 
+// The observers of a run (rbl_ensemble_run_observed), as one step sees them: device pointers into the run's buffer.  P probe
+// points (sets: 1 shared set or R; body >= 0: offsets fixed in that body) whose field goes to u_step, and D_step (moments) for
+// the first moments of the step's lambda.  They travel with the step's inputs (EnsStepIn); nothing of them is context state
+struct EnsObs {
+  int P = 0, sets = 1, body = -1;
+  bool moments = false;
+  const double *pts = nullptr;
+  double *u_step = nullptr, *D_step = nullptr;
+  unsigned *oerr = nullptr;                 // the probe kernel's flags of the step, R words (k_ens_obs_flags passes them on and clears them)
+};
+
 // The solve of every replica at (Xs, Qs) and the update from q^n: the one place that launches the one-kernel solver.  The variant
 // is chosen once -- mixed: the masked solve (w.mask, body_in in w.F); the update then reads the U it wrote (a prescribed body:
 // dt U_p exactly); the ensemble's cell on (the wall is: the callers' periodic_use_check): k_gmres_small_per; jt: the jointed
 // solve, rhs and x with the joint rows behind.  evolve = false: the solve alone
 int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const double *Qs, int max_iter, double rtol, bool mixed = false,
-                     bool evolve = true, bool record = true, int per = 1, const EnsJtStep *jt = nullptr)
+                     bool evolve = true, bool record = true, int per = 1, const EnsJtStep *jt = nullptr, const EnsObs *obs = nullptr)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
   const long n3 = 3L * Nb * nbl, nsys = n3 + 6L * Nb + (jt ? 3L * jt->T.n : 0L);
@@ -691,6 +711,16 @@ int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const doubl
                                                          // arms those of the configuration solved at
     if ((rc = rbl_dev_reserve(c, c->d_ens_mom, sizeof(double) * 9 * (size_t)nbod))) return rc;
     flow_launch_moments(c, nullptr, Qs, ens_cfg(c), w.x, Nb, nbod, nsys, (double *)c->d_ens_mom.p);
+  }
+  if (obs) {                                             // a run's observers: lambda where the solver left it, the configuration solved at
+    if (obs->moments) flow_launch_moments(c, nullptr, Qs, ens_cfg(c), w.x, Nb, nbod, nsys, obs->D_step);
+    if (obs->P > 0) {
+      const RblSmallCell cell = ens_cell(c);
+      const RblEnsProbe A = {Xs, Qs, ens_cfg(c), w.x, nsys, obs->pts, obs->sets == 1 ? 0L : 3L * obs->P, obs->u_step, obs->oerr, Nb, nbl,
+                             obs->P, obs->body};
+      ens_probe_launch(c->stream, P, c->S.wall, ens_cell_on(c) ? &cell : nullptr, A, R, c->n_cu);
+      ens_obs_flags_launch(c->stream, w.rerr, obs->oerr, R);   // into the replica's word, unless its step has failed already
+    }
   }
   hipLaunchKernelGGL(k_ens_evolve, dim3((unsigned)((nbod + ET - 1) / ET)), dim3(ET), 0, c->stream, nbod, Nb, mixed ? 6L * Nb : nsys,
                      mixed ? 0L : n3, c->S.dt, mixed ? (const double *)w.U : (const double *)w.x, (const double *)ens_X(c, c->ens_cur),
@@ -729,6 +759,7 @@ int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const d
 // them once: resident -- prescribed then only says that the step is the masked one (w.mask is filled), F_body is unused (w.F is
 // filled), slip is the run's device copy, W is NULL.  chol_err: the batched Cholesky's error stride (0: the batch word)
 struct EnsStepIn {
+  const EnsObs *obs = nullptr;              // a run with observers: evaluated on the step's lambda just before the update
   const uint8_t *prescribed = nullptr;
   int per = 1;                              // entries of prescribed per body: 1 (whole bodies) or 6 (velocity components)
   const double *F_body = nullptr, *slip = nullptr, *W = nullptr;
@@ -759,7 +790,8 @@ int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_i
   hipLaunchKernelGGL(k_ens_rhs_jt, dim3((unsigned)((tot + ET - 1) / ET)), dim3(ET), 0, c->stream, R, n3, nb6, nj3, SL,
                      (const double *)w.F, FT, jt && jt->have_jr ? (const double *)w.jr : nullptr, w.rhs);
   // a jointed step records its moments in a run too, as it always did
-  return ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, mixed, move, jt || !in.resident, in.per, jt);
+  return ens_solve_evolve(c, w, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), max_iter, rtol, mixed, move, jt || !in.resident, in.per, jt,
+                          in.obs);
 }
 
 int ens_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, int max_iter, double rtol, bool move,
@@ -835,7 +867,7 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
                      : rfd_rhs(k_ens_rfd_rhs<false>, EnsNoCell{})))
     return rc;
   // saddle solve at q^{n+1/2}, update from q^n
-  return ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol, mixed, true, !in.resident, in.per);
+  return ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol, mixed, true, !in.resident, in.per, nullptr, in.obs);
 }
 
 int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, const double *W, uint64_t seed,
@@ -1234,9 +1266,17 @@ struct EnsRunBuf {
   size_t rb_off, rb_bytes;                 // the read-back block: from st to the end of F_sum
   unsigned *vflag; double *F_last;
   double *fX, *fQ; int *fA; double *fF;
+  // the observers' part, behind everything else (nothing of it without them): points | this step's u, the last accepted one, the
+  // sum | the same three of D | frames
+  double *o_pts, *u_step, *u_last, *u_sum, *D_step, *D_last, *D_sum, *fU, *fD;
+  unsigned *o_err;                         // the probe kernel's flags of the current step
 };
 
-EnsRunBuf ens_run_carve(void *base, int R, int Nb, int nbl, bool slip, bool mixed, size_t n_frames, size_t *bytes)
+// what rbl_ensemble_run_observed hands to ens_run: its options and outputs (checked), NULL for a run without observers
+struct EnsRunObs { const rbl_run_obs_opts *o; rbl_run_obs_out *out; };
+
+EnsRunBuf ens_run_carve(void *base, int R, int Nb, int nbl, bool slip, bool mixed, size_t n_frames, size_t *bytes,
+                        const rbl_run_obs_opts *obs = nullptr)
 {
   const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, n3 = (size_t)3 * Nb * nbl;
   Carve C{(char *)base};
@@ -1253,6 +1293,12 @@ EnsRunBuf ens_run_carve(void *base, int R, int Nb, int nbl, bool slip, bool mixe
   b.fX = C.take<double>(n_frames * Rz * 3 * Nb); b.fQ = C.take<double>(n_frames * Rz * 4 * Nb);
   b.fA = C.take<int>(n_frames * Rz);
   b.fF = C.take<double>(mixed ? n_frames * Rz * nb6 : 0);
+  const size_t nu = obs ? Rz * 3 * (size_t)obs->n_probes : 0, nD = obs && obs->moments ? Rz * 9 * (size_t)Nb : 0;
+  b.o_pts = C.take<double>(nu ? 3 * (size_t)obs->n_probes * (size_t)obs->point_sets : 0);
+  b.u_step = C.take<double>(nu); b.u_last = C.take<double>(nu); b.u_sum = C.take<double>(nu);
+  b.D_step = C.take<double>(nD); b.D_last = C.take<double>(nD); b.D_sum = C.take<double>(nD);
+  b.fU = C.take<double>(n_frames * nu); b.fD = C.take<double>(n_frames * nD);
+  b.o_err = C.take<unsigned>(nu ? Rz : 0);
   *bytes = C.off;
   return b;
 }
@@ -1260,7 +1306,7 @@ EnsRunBuf ens_run_carve(void *base, int R, int Nb, int nbl, bool slip, bool mixe
 // n_steps steps of every replica (checks and ens_ready done by the caller; per: the mask's entries per body): the inputs go up
 // once, every step is the one-step calls' enqueue sequence followed by the verdict and the commit, the buffers flip on the host,
 // ONE read-back ends it.  J (rbl_ensemble_run_jointed): the step is the jointed one and one launch for the joints follows the commit
-int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_out *out, EnsJtRun *J)
+int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_out *out, EnsJtRun *J, const EnsRunObs *ob = nullptr)
 {
   const RblBodyState &S = c->S;
   const bool mixed = o.prescribed != nullptr, reject = o.on_error == RBL_RUN_REJECT;
@@ -1271,9 +1317,10 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
   EnsWork w;
   if ((rc = ens_work(c, o.max_iter, &w))) return rc;
   size_t bytes = 0;
-  ens_run_carve(nullptr, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
+  const rbl_run_obs_opts *oo = ob ? ob->o : nullptr;
+  ens_run_carve(nullptr, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes, oo);
   if ((rc = rbl_dev_reserve(c, c->d_ens_run, bytes + (J ? ens_jt_run_bytes(c, *J, n_frames) : 0)))) return rc;   // the joints' part behind
-  const EnsRunBuf b = ens_run_carve(c->d_ens_run.p, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes);
+  const EnsRunBuf b = ens_run_carve(c->d_ens_run.p, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes, oo);
   // the uploads, once
   if (mixed && (rc = ens_upload_mask(c, w, o.prescribed, per))) return rc;
   if ((rc = copy_h2d(c, w.F, mixed ? o.body_in : o.F_body, sizeof(double) * nb6 * Rz))) return rc;
@@ -1281,7 +1328,24 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
   RBL_HIP(c, hipMemsetAsync(b.st, 0, b.rb_bytes, c->stream));
   if (mixed) RBL_HIP(c, hipMemsetAsync(b.F_last, 0, sizeof(double) * nb6 * Rz, c->stream));
   if (J && (rc = ens_jt_run_begin(c, *J, (char *)c->d_ens_run.p + bytes, n_frames, w, b.st, b.vflag))) return rc;
+  EnsObs obs;                                            // the observers: points up once, "last accepted" and the sums start at zero
+  const size_t nu = oo ? Rz * 3 * (size_t)oo->n_probes : 0, nD = oo && oo->moments ? Rz * 9 * (size_t)Nb : 0;
+  if (oo) {
+    obs.P = oo->n_probes; obs.sets = oo->point_sets; obs.body = oo->probe_body; obs.moments = oo->moments != 0;
+    obs.pts = b.o_pts; obs.u_step = b.u_step; obs.D_step = b.D_step; obs.oerr = b.o_err;
+    if (nu) {
+      if ((rc = copy_h2d(c, b.o_pts, oo->points, sizeof(double) * 3 * (size_t)oo->n_probes * (size_t)oo->point_sets))) return rc;
+      RBL_HIP(c, hipMemsetAsync(b.u_last, 0, sizeof(double) * nu, c->stream));
+      RBL_HIP(c, hipMemsetAsync(b.u_sum, 0, sizeof(double) * nu, c->stream));
+      RBL_HIP(c, hipMemsetAsync(b.o_err, 0, sizeof(unsigned) * Rz, c->stream));
+    }
+    if (nD) {
+      RBL_HIP(c, hipMemsetAsync(b.D_last, 0, sizeof(double) * nD, c->stream));
+      RBL_HIP(c, hipMemsetAsync(b.D_sum, 0, sizeof(double) * nD, c->stream));
+    }
+  }
   EnsStepIn in;
+  in.obs = oo ? &obs : nullptr;
   in.prescribed = o.prescribed; in.per = per;
   in.slip = o.slip ? b.slip : nullptr; in.resident = true; in.chol_err = 1;
   in.accepted = b.accepted;
@@ -1308,6 +1372,13 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
       if (mixed) D.fF = b.fF + k * Rz * nb6;
     }
     hipLaunchKernelGGL(k_ens_commit, dim3((unsigned)R), dim3(ET), 0, c->stream, R, Nb, n, D);
+    if (oo) {                                            // the observers follow the commit's decision, replica by replica
+      const size_t k = D.fX ? (size_t)((n + 1) / o.stride - 1) : 0;
+      ens_obs_commit_launch(c->stream, &b.st->stopped, b.vflag, b.u_step, b.u_last, b.u_sum, D.fX ? b.fU + k * nu : nullptr,
+                            3L * oo->n_probes, (long)nu);
+      ens_obs_commit_launch(c->stream, &b.st->stopped, b.vflag, b.D_step, b.D_last, b.D_sum, D.fX ? b.fD + k * nD : nullptr, 9L * Nb,
+                            (long)nD);
+    }
     c->ens_cur ^= 1;                                     // the new buffer holds every replica's configuration, moved or not
     if (J) ens_jt_run_after(c, *J, D.fX ? (long)((n + 1) / o.stride - 1) : -1L);
     ++enq;
@@ -1339,6 +1410,14 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
     if ((rc = copy_d2h(c, out->frame_Q, b.fQ, sizeof(double) * nfr * Rz * 4 * Nb))) return rc;
     if ((rc = copy_d2h(c, out->frame_accepted_at, b.fA, sizeof(int) * nfr * Rz))) return rc;
     if (mixed && (rc = copy_d2h(c, out->frame_F, b.fF, sizeof(double) * nfr * Rz * nb6))) return rc;
+    RBL_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  if (oo) {
+    rbl_run_obs_out *q = ob->out;
+    if (nu && q->u_sum && (rc = copy_d2h(c, q->u_sum, b.u_sum, sizeof(double) * nu))) return rc;
+    if (nD && q->D_sum && (rc = copy_d2h(c, q->D_sum, b.D_sum, sizeof(double) * nD))) return rc;
+    if (nfr && nu && (rc = copy_d2h(c, q->frame_u, b.fU, sizeof(double) * nfr * nu))) return rc;
+    if (nfr && nD && (rc = copy_d2h(c, q->frame_D, b.fD, sizeof(double) * nfr * nD))) return rc;
     RBL_HIP(c, hipStreamSynchronize(c->stream));
   }
   if (J && (rc = ens_jt_run_end(c, *J, nfr, hs.stopped != 0))) return rc;
@@ -1543,7 +1622,8 @@ int rbl_ensemble_step_brownian_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6,
                         iters, resid);
 }
 
-int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)
+// rbl_ensemble_run, and rbl_ensemble_run_observed without joints (ob: its observers, checked there)
+static int ens_run_plain(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out, const EnsRunObs *ob)
 {
   if (!c) return RBL_ERR_ARG;
   if (!o || !out) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: opts or out is NULL");
@@ -1583,12 +1663,15 @@ int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out)
   if (brownian && (!(c->S.dt > 0.0) || !(o->delta > 0.0))) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: dt and delta must be positive");
   if ((rc = ens_flow_check(c))) return rc;
   if ((rc = ens_ready(c))) return rc;
-  return ens_run(c, *o, per, brownian, out, nullptr);
+  return ens_run(c, *o, per, brownian, out, nullptr, ob);
 }
+
+int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out) { return ens_run_plain(c, o, out, nullptr); }
 
 // n_steps jointed steps in one call: rbl_ensemble_step_jointed's checks and rbl_ensemble_run's, the schedule's own, then ens_run
 // with the jointed step; joints off or never set: rbl_ensemble_run's deterministic run itself
-int rbl_ensemble_run_jointed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, rbl_run_out *out, rbl_run_joint_out *jout)
+static int ens_run_jointed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, rbl_run_out *out, rbl_run_joint_out *jout,
+                           const EnsRunObs *ob)
 {
   const char *who = "ensemble_run_jointed";
   const std::string w(who);
@@ -1626,14 +1709,67 @@ int rbl_ensemble_run_jointed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_jo
   rbl_run_opts od = *o;                                  // the deterministic run's options
   od.brownian = 0; od.prescribed_per = 0;
   if (!on) {
-    if ((rc = rbl_ensemble_run(c, &od, out)) && out->stopped_at < 0) return rc;
+    if ((rc = ens_run_plain(c, &od, out, ob)) && out->stopped_at < 0) return rc;
     if (jout->cycle_pos) std::memset(jout->cycle_pos, 0, sizeof(int32_t) * (size_t)c->ens_R);
     return rc;
   }
   if ((rc = ens_flow_check(c))) return rc;
   if ((rc = ens_ready(c))) return rc;
   J.step = {who, {}, -jo->gamma / c->S.dt, jo->joint_velocity != nullptr};
-  return ens_run(c, od, 1, false, out, &J);
+  return ens_run(c, od, 1, false, out, &J, ob);
+}
+
+int rbl_ensemble_run_jointed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, rbl_run_out *out, rbl_run_joint_out *jout)
+{
+  return ens_run_jointed(c, o, jo, out, jout, nullptr);
+}
+
+// the observers' own refusals, none needing a device, then the underlying run with them (or without: nothing asked for)
+int rbl_ensemble_run_observed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, const rbl_run_obs_opts *obs, rbl_run_out *out,
+                              rbl_run_joint_out *jout, rbl_run_obs_out *oout)
+{
+  const char *who = "ensemble_run_observed";
+  const std::string w(who);
+  if (!c) return RBL_ERR_ARG;
+  if (!obs || !oout) return rbl_fail(c, RBL_ERR_ARG, w + ": obs or oout is NULL");
+  if (obs->size != (int64_t)sizeof(rbl_run_obs_opts)) return rbl_fail(c, RBL_ERR_ARG, w + ": obs.size is not sizeof(rbl_run_obs_opts)");
+  if (oout->size != (int64_t)sizeof(rbl_run_obs_out)) return rbl_fail(c, RBL_ERR_ARG, w + ": oout.size is not sizeof(rbl_run_obs_out)");
+  if (obs->n_probes < 0) return rbl_fail(c, RBL_ERR_ARG, w + ": n_probes must be >= 0");
+  if (obs->n_probes > 0) {
+    if (!obs->points) return rbl_fail(c, RBL_ERR_ARG, w + ": points is NULL while n_probes > 0");
+    if (obs->point_sets < 1) return rbl_fail(c, RBL_ERR_ARG, w + ": point_sets must be 1 or R");
+    if (obs->probe_body < -1) return rbl_fail(c, RBL_ERR_ARG, w + ": probe_body must be -1 (lab points) or a body index");
+    if (c->ens_R) {                                      // (no ensemble: the underlying run's RBL_ERR_STATE, below)
+      if (obs->point_sets != 1 && obs->point_sets != c->ens_R)
+        return rbl_fail(c, RBL_ERR_ARG, w + ": point_sets must be 1 or R = " + std::to_string(c->ens_R));
+      if (obs->probe_body >= c->ens_Nb)
+        return rbl_fail(c, RBL_ERR_ARG, w + ": probe_body must be -1 (lab points) or a body index below N_bod = " + std::to_string(c->ens_Nb));
+    }
+    if (c->ens_R || obs->point_sets == 1) {              // (the sets are R sets or one: the array's length is known)
+      int rc = ens_points_check(c, who, obs->points, obs->n_probes, obs->point_sets); if (rc) return rc;
+    }
+  }
+  // (opts of another size are not read: the underlying run refuses them below)
+  const bool frames = o && o->size == (int64_t)sizeof(rbl_run_opts) && o->stride > 0 && o->n_steps / o->stride > 0;
+  if (frames && obs->n_probes > 0 && !oout->frame_u) return rbl_fail(c, RBL_ERR_ARG, w + ": frame_u must not be NULL while stride > 0 records frames of the probes");
+  if (frames && obs->moments && !oout->frame_D) return rbl_fail(c, RBL_ERR_ARG, w + ": frame_D must not be NULL while stride > 0 records frames of the moments");
+  const EnsRunObs ob = {obs, oout};
+  const EnsRunObs *pob = obs->n_probes > 0 || obs->moments ? &ob : nullptr;
+  return jo ? ens_run_jointed(c, o, jo, out, jout, pob) : ens_run_plain(c, o, out, pob);
+}
+
+// ---- what rbl_ens_field.hip reads of the ensemble (rbl_api_internal.hpp) --------------------------------------------
+int ens_state_refusals(rbl_ctx *c, const char *who) { return ens_state_check(c, std::string(who) + ": "); }
+
+int ens_view(rbl_ctx *c, RblEnsView *v)
+{
+  int rc = ens_ready(c); if (rc) return rc;
+  v->cell = ens_cell_on(c);
+  if (v->cell && (rc = periodic_use_check(c, c->S.wall, c->ens_per_L, "rbl_ensemble_set_periodic"))) return rc;
+  v->C = ens_cell(c);
+  v->X = ens_X(c, c->ens_cur); v->Q = ens_Q(c, c->ens_cur); v->cfg = ens_cfg(c);
+  v->R = c->ens_R; v->Nb = c->ens_Nb; v->nbl = c->S.N_blb;
+  return RBL_OK;
 }
 
 int rbl_run_schedule_phase(const int32_t *phase_steps, int n_phases, int64_t pos)

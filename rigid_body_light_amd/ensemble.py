@@ -207,7 +207,8 @@ class Ensemble:
 
     # ------------------------------------------------------------------ a run of steps (include/rbl.h section 5, rbl_ensemble_run)
     def run(self, n_steps, F=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error="stop",
-            check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1e-4, max_iter=50, rtol=1e-8, prescribed_dof=None):
+            check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1e-4, max_iter=50, rtol=1e-8, prescribed_dof=None,
+            probes=None, probe_body=None, moments=False):
         """n_steps steps of every replica in ONE call: the inputs go to the device once, each step's verdict and commit are taken
         per replica on the device, one read-back ends the run -> RunResult (accepted, rejected, first_status, iters_sum, resid_max,
         F_mean for runs with prescribed bodies, steps_done, stopped_at, and with stride > 0 the frames X, Q, accepted_at, F after
@@ -219,7 +220,13 @@ class Ensemble:
         raise it, the partial result stays on self.last_run.  on_error="reject": a failing replica keeps its configuration and
         tries again with the next step's noise (the customary redraw, not an unbiased one: see rejected), the others go on; the
         new configuration is validated before it commits; only a failure of the whole batch raises.  check_every: steps between
-        the host's looks at the run's status (0: none before the end)"""
+        the host's looks at the run's status (0: none before the end).
+        Observers, evaluated inside every step on that step's blob forces, at the configuration the solve was taken at (q^n, or
+        q^{n+1/2} in a Brownian step): probes (P, 3) or (R, P, 3), points at which the fluid velocity is evaluated (velocity_field's
+        definition) -- lab points, or with probe_body=b offsets fixed in body b that follow it -- and moments=True for the first
+        moments D_b of lambda.  The result gains u_sum / u_mean (R, P, 3) and D_sum / D_mean / stresslet_mean (R, N_bod, 3, 3) over
+        the accepted steps and, with stride > 0, frame_u and frame_D.  In a Brownian run these are instantaneous values, thermal
+        part included: the mean is the measurement (the drift's share of the stress is not in it)"""
         modes = {"stop": RUN_STOP, "reject": RUN_REJECT}
         if on_error not in modes:
             _fail("on_error must be 'stop' or 'reject'; got %r" % (on_error,))
@@ -247,14 +254,63 @@ class Ensemble:
         else:
             m, b = self._prescribed_mask(prescribed), self._body_in(body_in)
         s = self._slip(slip)
+        obs = self._observers("run", probes, probe_body, moments)
         self.last_run = None
-        res, rc = self.ctx.ensemble_run(n_steps, F_body=F, prescribed=m, body_in=b, brownian=brownian, seed=seed, stride=stride,
-                                        on_error=modes[on_error], check_every=check_every, slip=s, split_rand=split_rand,
-                                        delta=delta, max_iter=max_iter, rtol=rtol, per=per)
+        args = dict(F_body=F, prescribed=m, body_in=b, brownian=brownian, seed=seed, stride=stride, on_error=modes[on_error],
+                    check_every=check_every, slip=s, split_rand=split_rand, delta=delta, max_iter=max_iter, rtol=rtol, per=per)
+        if obs is None:
+            res, rc = self.ctx.ensemble_run(n_steps, **args)
+        else:
+            res, rc = self.ctx.ensemble_run_observed(n_steps, *obs, **args)
         self.last_run = res
         if rc != 0:
             raise RblError(res.error)
         return res
+
+    # ------------------------------------------------------------------ the flow at probe points, observers (include/rbl.h section 5)
+    def _points(self, who, points):
+        """(P, 3), one set of points for every replica, or (R, P, 3); finite -> a contiguous float64 array; ValueError before the
+        library is called"""
+        p = np.asarray(points, dtype=np.float64)
+        if p.shape[-1:] != (3,) or not (p.ndim == 2 or (p.ndim == 3 and p.shape[0] == self.R)):
+            _fail("%s: points must have shape (P, 3) or (%d, P, 3); got %s" % (who, self.R, p.shape))
+        bad = np.argwhere(~np.isfinite(p).all(axis=-1))
+        if bad.size:
+            _fail("%s: points: %spoint %d has a non-finite coordinate" % (who, "set %d, " % bad[0][0] if p.ndim == 3 else "", bad[0][-1]))
+        return np.ascontiguousarray(p)
+
+    def _probe_body(self, who, body):
+        if body is None:
+            return None
+        if isinstance(body, bool) or int(body) != body or not 0 <= int(body) < self.N_bodies:
+            _fail("%s: the probes' body must be None (lab points) or a body index in [0, %d); got %r" % (who, self.N_bodies, body))
+        return int(body)
+
+    def _observers(self, who, probes, probe_body, moments):
+        """-> None when nothing is observed (the run is then today's call), else (points or None, body or None, moments)"""
+        if probes is None and probe_body is None and not moments:
+            return None
+        if probes is None and probe_body is not None:
+            _fail("%s: probe_body was given without probes" % who)
+        pts = None if probes is None else self._points(who, probes)
+        return pts, self._probe_body(who, probe_body), bool(moments)
+
+    def velocity_field(self, points, lam, body=None):
+        """the fluid velocity every replica's blob forces drive at points, at the ensemble's current configuration and in its cell
+        (set_cell) -> (R, P, 3).  points: (P, 3), shared by the replicas, or (R, P, 3); lam: (R, 3 N), e.g. solve_jointed's or
+        solve_mixed's lambda.  The velocity apply_M would give a force-free blob of radius a placed there: a point on a blob
+        returns that blob's row, with the wall a point at z <= 0 gets 0.  body=b: the points are offsets fixed in body b of each
+        replica, placed at X_b + R(Q_b) s; the velocity stays in lab-frame components"""
+        pts = self._points("velocity_field", points)
+        lam = np.asarray(lam, dtype=np.float64)
+        n3 = 3 * self.N_bodies * self.blobs_per_body
+        if lam.shape != (self.R, n3):
+            _fail("velocity_field: lam must have shape (%d, %d); got %s" % (self.R, n3, lam.shape))
+        return self.ctx.ensemble_velocity_field(pts, lam, body=self._probe_body("velocity_field", body))
+
+    def probe_info(self, n_points):
+        """(points per lane, waves per workgroup, point tiles) of the probe kernel's launch for n_points points per replica"""
+        return self.ctx.ensemble_probe_info(int(n_points))
 
     def body_resistance_matrix(self, max_iter=100, rtol=1e-8):
         """the body resistance matrix of every replica's configuration, (R, 6 N_bod, 6 N_bod): every body prescribed, one ensemble
@@ -451,7 +507,7 @@ class Ensemble:
         return ps, pr, cs
 
     def run_jointed(self, n_steps, F, slip=None, joint_velocity=None, gamma=1.0, schedule=None, cycle_start=None, stride=0,
-                    on_error="stop", check_every=RUN_CHECK_DEFAULT, max_iter=50, rtol=1e-8):
+                    on_error="stop", check_every=RUN_CHECK_DEFAULT, max_iter=50, rtol=1e-8, probes=None, probe_body=None, moments=False):
         """n_steps steps of step_jointed in ONE call (rbl_ensemble_run_jointed): the joint table, F, slip and joint_velocity go to
         the device once, the motors' angles advance there, one read-back ends the run -> RunResult, with theta (R, n_joints) and
         cycle_pos (R,) as the run leaves them, phi_sum / phi_mean (R, n_joints, 3) over the accepted steps (a motor's mean torque
@@ -462,7 +518,9 @@ class Ensemble:
         only --, evaluated on each replica's own position in the cycle, which starts at cycle_start (an integer or (R,); 0 when
         None) and moves on when the replica commits.  cycle_start=res.cycle_pos continues a stroke.  schedule=None: the rates of
         set_joint_rates, constant; set_joint_rates' rates are untouched by a schedule.  on_error and check_every as in run; a
-        stopped run raises RblError and leaves the partial result on self.last_run.  Joints off or never set: run(brownian=False)"""
+        stopped run raises RblError and leaves the partial result on self.last_run.  Joints off or never set: run(brownian=False).
+        probes, probe_body and moments: the observers of run, evaluated at q^n of every step; probes fixed in a link
+        (probe_body) give the flow in the swimmer's frame of reference, still in lab-frame components"""
         modes = {"stop": RUN_STOP, "reject": RUN_REJECT}
         if on_error not in modes:
             _fail("on_error must be 'stop' or 'reject'; got %r" % (on_error,))
@@ -476,10 +534,14 @@ class Ensemble:
         F, s = self._forces(F), self._slip(slip)
         jv = self._joint_rows_in("joint_velocity", joint_velocity, self._joints_on())
         ps, pr, cs = self._schedule(schedule, cycle_start)
+        obs = self._observers("run_jointed", probes, probe_body, moments)
         self.last_run = None
-        res, rc = self.ctx.ensemble_run_jointed(n_steps, F, slip=s, joint_velocity=jv, gamma=gamma, phase_steps=ps, phase_rates=pr,
-                                                cycle_start=cs, stride=stride, on_error=modes[on_error], check_every=check_every,
-                                                max_iter=max_iter, rtol=rtol)
+        args = dict(slip=s, joint_velocity=jv, gamma=gamma, phase_steps=ps, phase_rates=pr, cycle_start=cs, stride=stride,
+                    on_error=modes[on_error], check_every=check_every, max_iter=max_iter, rtol=rtol)
+        if obs is None:
+            res, rc = self.ctx.ensemble_run_jointed(n_steps, F, **args)
+        else:
+            res, rc = self.ctx.ensemble_run_observed(n_steps, *obs, jointed=True, F_body=F, **args)
         self.last_run = res
         if rc != 0:
             raise RblError(res.error)
