@@ -867,7 +867,7 @@ int rbl_ensemble_step_brownian_mixed_dof(rbl_ctx *ctx, const uint8_t *prescribed
  * free) or prescribed with body_in (held or driven bodies, as rbl_ensemble_step_[brownian_]mixed).  prescribed_per = 6 makes the
  * mask one entry per velocity component (prescribed[R 6 N_bod], the steps of rbl_ensemble_step_mixed_dof; 0 and 1: whole bodies);
  * such a run is deterministic only: with brownian != 0 and kBT > 1e-10 it is refused, that step's drift term is not derived.  Everything in the options is
- * constant over the run; the force model (section 4) and the flow model (section 8) enter every step at that step's q^n.
+ * constant over the run (rbl_ensemble_run_driven, below, is the run whose body input follows a drive); the force model (section 4) and the flow model (section 8) enter every step at that step's q^n.
  * The one input that moves is the magnetic field's clock (section 4): replica r evaluates B at its field time + dt accepted[r],
  * and the context's field time itself is left as it was.
  *
@@ -1094,6 +1094,88 @@ int rbl_ensemble_velocity_field_dev(rbl_ctx *ctx, const double *d_points, int64_
 int rbl_ensemble_probe_info(const rbl_ctx *ctx, int64_t n_points, int *ni, int *waves, int64_t *tiles);
 int rbl_ensemble_run_observed(rbl_ctx *ctx, const rbl_run_opts *opts, const rbl_run_joint_opts *jopts, const rbl_run_obs_opts *obs,
                               rbl_run_out *out, rbl_run_joint_out *jout, rbl_run_obs_out *oout);
+
+/* Driven runs: the one body input of a run that moves with time (rigid_body_light_amd/csrc/rbl_ens_drive.hip).
+ *
+ * rbl_ensemble_run keeps everything it is given constant over the run.  rbl_ensemble_run_driven is that run (with observers
+ * when obs is not NULL, as rbl_ensemble_run_observed without joints) whose body input -- F_body of a run with all bodies free,
+ * body_in of a masked run: velocities on prescribed bodies or components, loads on free ones -- is evaluated anew before every
+ * step, per replica.  For replica r at a step that starts with accepted[r] = n and cycle position p_r the 6 N_bod entries are
+ *     in_r = ((A0_r + P_r[phase(p_r)]) + C_r cos(w_r t_r)) + S_r sin(w_r t_r),     t_r = t0_r + dt n.
+ * A0: opts->F_body or opts->body_in, the array a plain run holds constant.  cos_amp (C) and sin_amp (S): [amp_sets 6 N_bod],
+ * amp_sets 1 (every replica alike) or R; either may be NULL: zeros.  omega[omega_sets], omega_sets 1 or R: one frequency per
+ * replica, so R replicas are R points of a spectrum in one call.  t0[t0_sets], t0_sets 0 (t0 = 0), 1 or R.  P: a periodic
+ * piecewise-constant part, n_phases >= 0 phases, phase k lasting phase_steps[k] >= 1 steps with phase_in[k][s][6 N_bod]
+ * (s < phase_sets, 1 or R), read through the schedule map of rbl_ensemble_run_jointed (rbl_run_schedule_phase): the position
+ * starts at cycle_start[start_sets] (start_sets 0: every replica at 0, 1 or R) and moves on by one, modulo the cycle's length,
+ * when the replica commits -- a rejected replica's schedule and clock wait for it.  n_phases = 0: P = 0.
+ * The arithmetic is fixed: dt n and the sum with t0 are two separately rounded operations (the field clock's, section 4),
+ * w t is one rounded product followed by ONE sincos, the products C cs and S sn are rounded, and the three additions are made
+ * in the order written, nothing contracted; absent parts enter as zeros.  So omega = 0 with S = 0 gives the bits of
+ * (A0 + P) + C.  The drive is an argument, never state; the mask, slip, force model and flow model stay constant as before.
+ *
+ * Two launches per step beside the run's own: k_ens_drive before the step's sequence (one thread per entry of [R 6 N_bod];
+ * the evaluated input goes into the buffer the step reads, A0 stays in one of its own; cs, sn per replica into a small table)
+ * and k_ens_drive_commit after the run's commit and the observers' (one thread per entry; it takes the commit's own decision
+ * from the run's status and the replica's verdict word, advances the cycle position and adds the lock-in sums).
+ *
+ * Lock-in sums (lockin != 0): for every step a replica commits, with the step's own cs = cos(w_r t_r), sn = sin(w_r t_r) --
+ * the values the drive was evaluated with --, each entry added by one thread, in step order, product and sum rounded one
+ * after the other:  X_c, X_s [R 3 N_bod] = sum X(q^n) cs / sn with the body centres of the configuration the step started
+ * from;  U_c, U_s [R 6 N_bod] the same of the step's body velocities (what the update reads);  F_c, F_s [R 6 N_bod] the same of
+ * the masked solve's loads (masked runs; left alone otherwise);  norm [R 5] = sum cs, sum sn, sum cs^2, sum sn^2, sum cs sn,
+ * with which amplitude and phase are fitted exactly in discrete time.  Nothing is added from a stopping step on.
+ * cycle_pos[R] and t_end[R] = t0 + dt accepted come back, so that a second run (cycle_start = cycle_pos, t0 = t_end)
+ * continues the first: bit for bit where the clock arithmetic is exact (a dyadic dt and t0), otherwise t_end + dt m and
+ * t0 + dt (n + m) are two roundings of one number.  Any pointer of dout may be NULL.
+ *
+ * Contracts: a driven run is, bit for bit, the loop of rbl_ensemble_drive_eval followed by the one-step call; replica r of R
+ * is the R = 1 run with that replica's inputs; drive == NULL, or a drive with neither C nor S, no phases and lockin == 0, is the
+ * underlying run bit for bit and launch for launch (cycle_pos is then zeros, t_end = t0 + dt accepted, the sums are left alone).
+ *
+ * rbl_ensemble_drive_eval: the same kernel, one launch and a read-back.  base[R 6 N_bod] stands for A0, accepted[R] (NULL:
+ * zeros) and cycle_pos[R] (NULL: cycle_start) for the replicas' counters; in_out[R 6 N_bod] takes the evaluated input and
+ * cs_sn[R 2] (may be NULL) the pair the kernel evaluated it with.  The device's sincos is not the host's: this call is what
+ * lets a loop of one-step calls reproduce a driven run.
+ *
+ * Refused before any device work, rbl_last_error naming the argument -- RBL_ERR_ARG: a wrong struct size, dout NULL with a
+ * non-empty drive, amp_sets or omega_sets outside {1, R}, t0_sets or start_sets outside {0, 1, R}, phase_sets outside {1, R},
+ * n_phases < 0, omega NULL with a harmonic part or lockin, t0, phase_steps, phase_in or cycle_start NULL where its count says
+ * it is read, a non-finite entry of cos_amp, sin_amp, omega, t0 or phase_in (set and entry named), a phase_steps entry < 1, a
+ * cycle longer than 31 bits, a cycle_start outside the cycle, a harmonic part or lockin while dt <= 0; then everything the
+ * underlying run refuses, unchanged (a Brownian run with prescribed_per = 6 and a communicator among them); RBL_ERR_STATE: hard
+ * joints are switched on and the drive is not empty (drives for rbl_ensemble_run_jointed are not offered). */
+typedef struct rbl_run_drive_opts {
+  int64_t size;                 /* sizeof(rbl_run_drive_opts) */
+  int32_t amp_sets;             /* 1 or R (read while cos_amp or sin_amp is given) */
+  int32_t omega_sets;           /* 1 or R (read while omega is given) */
+  int32_t t0_sets;              /* 0, 1 or R */
+  int32_t n_phases;             /* >= 0 */
+  int32_t phase_sets;           /* 1 or R (read while n_phases > 0) */
+  int32_t start_sets;           /* 0, 1 or R */
+  int32_t lockin;               /* != 0: the lock-in sums */
+  int32_t reserved;
+  const double *cos_amp;        /* C [amp_sets 6 N_bod] or NULL */
+  const double *sin_amp;        /* S [amp_sets 6 N_bod] or NULL */
+  const double *omega;          /* [omega_sets]; NULL without a harmonic part and lockin: 0 */
+  const double *t0;             /* [t0_sets] */
+  const int32_t *phase_steps;   /* [n_phases], each >= 1 */
+  const double *phase_in;       /* [n_phases phase_sets 6 N_bod] */
+  const int32_t *cycle_start;   /* [start_sets] */
+} rbl_run_drive_opts;
+typedef struct rbl_run_drive_out {
+  int64_t size;                 /* sizeof(rbl_run_drive_out) */
+  double *X_c, *X_s;            /* [R 3 N_bod] */
+  double *U_c, *U_s;            /* [R 6 N_bod] */
+  double *F_c, *F_s;            /* [R 6 N_bod], masked runs */
+  double *norm;                 /* [R 5] */
+  int32_t *cycle_pos;           /* [R] */
+  double *t_end;                /* [R] */
+} rbl_run_drive_out;
+int rbl_ensemble_run_driven(rbl_ctx *ctx, const rbl_run_opts *opts, const rbl_run_drive_opts *drive, const rbl_run_obs_opts *obs,
+                            rbl_run_out *out, rbl_run_drive_out *dout, rbl_run_obs_out *oout);
+int rbl_ensemble_drive_eval(rbl_ctx *ctx, const rbl_run_drive_opts *drive, const double *base, const int32_t *accepted,
+                            const int32_t *cycle_pos, double *in_out, double *cs_sn);
 
 /* ===================================================================== */
 /* 6. Fluid velocity at arbitrary points (rigid_body_light_amd/csrc/rbl_field.hip) */

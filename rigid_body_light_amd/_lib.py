@@ -147,6 +147,9 @@ def lib(path=None):
         L.rbl_ensemble_joints_fit.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(i64)]
         L.rbl_ensemble_run_observed.argtypes = [vp, C.POINTER(RunOpts), C.POINTER(RunJointOpts), C.POINTER(RunObsOpts), C.POINTER(RunOut),
                                                 C.POINTER(RunJointOut), C.POINTER(RunObsOut)]
+        L.rbl_ensemble_run_driven.argtypes = [vp, C.POINTER(RunOpts), C.POINTER(RunDriveOpts), C.POINTER(RunObsOpts), C.POINTER(RunOut),
+                                              C.POINTER(RunDriveOut), C.POINTER(RunObsOut)]
+        L.rbl_ensemble_drive_eval.argtypes = [vp, C.POINTER(RunDriveOpts), vp, vp, vp, vp, vp]
         L.rbl_ensemble_velocity_field.argtypes = L.rbl_ensemble_velocity_field_dev.argtypes = [vp, vp, i64, C.c_int, C.c_int, vp, vp]
         L.rbl_ensemble_probe_info.argtypes = [vp, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]
         L.rbl_velocity_field.argtypes = [vp, vp, i64, vp, vp, i64, vp]
@@ -498,7 +501,78 @@ class RunObsOut(C.Structure):
     _fields_ = [("size", C.c_int64), ("u_sum", C.c_void_p), ("D_sum", C.c_void_p), ("frame_u", C.c_void_p), ("frame_D", C.c_void_p)]
 
 
+class RunDriveOpts(C.Structure):
+    """rbl_run_drive_opts (include/rbl.h section 5)"""
+    _fields_ = [("size", C.c_int64), ("amp_sets", C.c_int32), ("omega_sets", C.c_int32), ("t0_sets", C.c_int32), ("n_phases", C.c_int32),
+                ("phase_sets", C.c_int32), ("start_sets", C.c_int32), ("lockin", C.c_int32), ("reserved", C.c_int32),
+                ("cos_amp", C.c_void_p), ("sin_amp", C.c_void_p), ("omega", C.c_void_p), ("t0", C.c_void_p), ("phase_steps", C.c_void_p),
+                ("phase_in", C.c_void_p), ("cycle_start", C.c_void_p)]
+
+
+class RunDriveOut(C.Structure):
+    """rbl_run_drive_out (include/rbl.h section 5)"""
+    _fields_ = [("size", C.c_int64), ("X_c", C.c_void_p), ("X_s", C.c_void_p), ("U_c", C.c_void_p), ("U_s", C.c_void_p),
+                ("F_c", C.c_void_p), ("F_s", C.c_void_p), ("norm", C.c_void_p), ("cycle_pos", C.c_void_p), ("t_end", C.c_void_p)]
+
+
 RUN_STOP, RUN_REJECT, RUN_CHECK_DEFAULT = 0, 1, 64
+
+
+def drive_opts(who, nb6, cos=None, sin=None, omega=None, t0=None, phase_steps=None, phase_in=None, cycle_start=None, lockin=False):
+    """rbl_run_drive_opts from arrays -> (RunDriveOpts, the arrays it points into: keep them alive over the call).  cos, sin:
+    (6 N_bod,) or (sets, 6 N_bod); omega, t0: a number or (sets,); phase_steps (n_phases,) with phase_in (n_phases, 6 N_bod) or
+    (n_phases, sets, 6 N_bod); cycle_start: an integer or (sets,).  The set counts go to the library as they are (it refuses
+    what is neither 1 nor R); only what cannot be laid out raises ValueError here"""
+    import numpy as np
+    d = RunDriveOpts()
+    d.size = C.sizeof(RunDriveOpts)
+    keep = []
+
+    def amp(name, a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim == 1:
+            a = a.reshape(1, -1)
+        if a.ndim != 2 or a.shape[1] != nb6:
+            raise ValueError("%s: %s must have shape (%d,) or (sets, %d); got %s" % (who, name, nb6, nb6, a.shape))
+        return a
+    c_, s_ = amp("cos", cos), amp("sin", sin)
+    if c_ is not None and s_ is not None and c_.shape[0] != s_.shape[0]:
+        if 1 not in (c_.shape[0], s_.shape[0]):
+            raise ValueError("%s: cos and sin must hold the same number of sets, or one of them a single set; got %d and %d"
+                             % (who, c_.shape[0], s_.shape[0]))
+        sets = max(c_.shape[0], s_.shape[0])
+        c_, s_ = (np.ascontiguousarray(np.broadcast_to(a, (sets, nb6))) for a in (c_, s_))
+    for a in (c_, s_):
+        if a is not None:
+            d.amp_sets = a.shape[0]
+            keep.append(a)
+    d.cos_amp = None if c_ is None else c_.ctypes.data
+    d.sin_amp = None if s_ is None else s_.ctypes.data
+    if omega is not None:
+        om = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+        d.omega, d.omega_sets = om.ctypes.data, om.size
+        keep.append(om)
+    if t0 is not None:
+        t = np.ascontiguousarray(t0, dtype=np.float64).reshape(-1)
+        d.t0, d.t0_sets = t.ctypes.data, t.size
+        keep.append(t)
+    if phase_steps is not None:
+        ps = np.ascontiguousarray(phase_steps, dtype=np.int32).reshape(-1)
+        pi = np.ascontiguousarray(phase_in, dtype=np.float64)
+        if pi.ndim == 2:
+            pi = pi.reshape(pi.shape[0], 1, pi.shape[1])
+        if pi.ndim != 3 or pi.shape[0] != ps.size or pi.shape[2] != nb6:
+            raise ValueError("%s: phase_in must have shape (%d, %d) or (%d, sets, %d); got %s" % (who, ps.size, nb6, ps.size, nb6, pi.shape))
+        d.n_phases, d.phase_sets, d.phase_steps, d.phase_in = ps.size, pi.shape[1], ps.ctypes.data, pi.ctypes.data
+        keep += [ps, pi]
+    if cycle_start is not None:
+        cs = np.ascontiguousarray(cycle_start, dtype=np.int32).reshape(-1)
+        d.cycle_start, d.start_sets = cs.ctypes.data, cs.size
+        keep.append(cs)
+    d.lockin = int(bool(lockin))
+    return d, keep
 
 
 class RunResult:
@@ -516,9 +590,15 @@ class RunResult:
     points, u_sum (R, P, 3), the field summed over the replica's accepted steps in step order, u_mean = u_sum / accepted (zeros,
     not NaN, where nothing was accepted) and the frames frame_u (n_frames, R, P, 3); with moments D_sum, D_mean (R, N_bod, 3, 3),
     stresslet_mean (the symmetric traceless part of D_mean) and frame_D (n_frames, R, N_bod, 3, 3).  A frame holds its step's value,
-    or the replica's last accepted one where it was rejected in that step (zeros before any).  None for runs without them"""
+    or the replica's last accepted one where it was rejected in that step (zeros before any).  None for runs without them.
+    A driven run (DeviceContext.ensemble_run_driven, Ensemble.run_driven) adds cycle_pos (R,) and t_end (R,), the drive's cycle
+    positions and clocks at its end, and with lockin the sums over the replica's accepted steps, in step order, of the step's
+    value times cs = cos(omega t) / sn = sin(omega t): X_c, X_s (R, N_bod, 3) of the body centres the step started from, U_c,
+    U_s (R, 6 N_bod) of the step's body velocities, F_c, F_s (R, 6 N_bod) of the loads (masked runs) and norm (R, 5) = sum cs,
+    sn, cs^2, sn^2, cs sn"""
     theta = cycle_pos = phi_sum = phi_mean = frame_theta = frame_phi = frame_gap = None
     u_sum = u_mean = frame_u = D_sum = D_mean = stresslet_mean = frame_D = None
+    X_c = X_s = U_c = U_s = F_c = F_s = norm = t_end = None
 
     def __repr__(self):
         return "RunResult(steps_done=%d, stopped_at=%d, accepted=%d..%d, rejected=%d)" % (
@@ -1438,8 +1518,9 @@ class DeviceContext:
                                   rtol=rtol, per=per)
 
     def _ensemble_run(self, obs, n_steps, F_body=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error=RUN_STOP,
-                      check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8, per=1):
-        """ensemble_run's body, shared with ensemble_run_observed (obs: its observers, None for the plain run)"""
+                      check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8, per=1, drive=None):
+        """ensemble_run's body, shared with ensemble_run_observed (obs: its observers, None for the plain run) and
+        ensemble_run_driven (drive: drive_opts' keywords, None for the other two)"""
         import numpy as np
         R, nb = self.ensemble_info()
         if R == 0:
@@ -1486,7 +1567,7 @@ class DeviceContext:
         out.frame_X, out.frame_Q, out.frame_accepted_at = res.X.ctypes.data, res.Q.ctypes.data, res.accepted_at.ctypes.data
         out.frame_F = res.F.ctypes.data if masked else None
         out.stopped_at = out.stop_replica = -1       # a refused call leaves them so
-        rc = self._run_call(o, None, out, None, res, obs)
+        rc = self._run_call(o, None, out, None, res, obs, drive)
         res.steps_done, res.stopped_at, res.stop_replica = out.steps_done, out.stopped_at, out.stop_replica
         res.status, res.error = rc, None
         if rc != 0:
@@ -1499,10 +1580,29 @@ class DeviceContext:
                 res.F_mean = np.where(res.accepted[:, None] > 0, res.F_sum / res.accepted[:, None], np.nan)
         return res, rc
 
-    def _run_call(self, o, jo, out, jout, res, obs):
+    def _run_call(self, o, jo, out, jout, res, obs, drive=None):
         """the one place a run enters the library: rbl_ensemble_run / rbl_ensemble_run_jointed as ever, or, with observers (obs:
-        ensemble_run_observed's (points, probe_body, moments)), rbl_ensemble_run_observed, whose records go onto res"""
+        ensemble_run_observed's (points, probe_body, moments)), rbl_ensemble_run_observed, whose records go onto res; with a drive
+        (drive_opts' keywords) rbl_ensemble_run_driven, with or without observers"""
         import numpy as np
+        dd = dq = None
+        if drive is not None:
+            R, nb = self.ensemble_info()
+            dd, keep = drive_opts("ensemble_run_driven", 6 * nb, **drive)
+            dq = RunDriveOut()
+            dq.size = C.sizeof(RunDriveOut)
+            res.cycle_pos, res.t_end = np.zeros(R, dtype=np.int32), np.zeros(R)
+            dq.cycle_pos, dq.t_end = res.cycle_pos.ctypes.data, res.t_end.ctypes.data
+            if dd.lockin:
+                res.X_c, res.X_s, res.norm = np.zeros((R, nb, 3)), np.zeros((R, nb, 3)), np.zeros((R, 5))
+                res.U_c, res.U_s = np.zeros((R, 6 * nb)), np.zeros((R, 6 * nb))
+                dq.X_c, dq.X_s, dq.norm = res.X_c.ctypes.data, res.X_s.ctypes.data, res.norm.ctypes.data
+                dq.U_c, dq.U_s = res.U_c.ctypes.data, res.U_s.ctypes.data
+                if o.prescribed:
+                    res.F_c, res.F_s = np.zeros((R, 6 * nb)), np.zeros((R, 6 * nb))
+                    dq.F_c, dq.F_s = res.F_c.ctypes.data, res.F_s.ctypes.data
+            if obs is None:
+                return self.L.rbl_ensemble_run_driven(self.h, C.byref(o), C.byref(dd), None, C.byref(out), C.byref(dq), None)
         if obs is None:
             if jo is None:
                 return self.L.rbl_ensemble_run(self.h, C.byref(o), C.byref(out))
@@ -1522,8 +1622,44 @@ class DeviceContext:
         if moments:
             res.D_sum, res.frame_D = np.zeros((R, nb, 3, 3)), np.zeros((nf, R, nb, 3, 3))
             oq.D_sum, oq.frame_D = res.D_sum.ctypes.data, res.frame_D.ctypes.data
+        if dd is not None:
+            return self.L.rbl_ensemble_run_driven(self.h, C.byref(o), C.byref(dd), C.byref(oo), C.byref(out), C.byref(dq), C.byref(oq))
         return self.L.rbl_ensemble_run_observed(self.h, C.byref(o), None if jo is None else C.byref(jo), C.byref(oo), C.byref(out),
                                                 None if jout is None else C.byref(jout), C.byref(oq))
+
+    def ensemble_run_driven(self, n_steps, cos=None, sin=None, omega=None, t0=None, phase_steps=None, phase_in=None, cycle_start=None,
+                            lockin=False, probes=None, probe_body=None, moments=False, **run_args):
+        """a run whose body input follows a drive (rbl_ensemble_run_driven) -> (RunResult, status) as ensemble_run returns them:
+        run_args are ensemble_run's keywords, F_body or body_in standing for the constant part A0.  Before every step replica r
+        steps with ((A0 + P[phase]) + cos * cs) + sin * sn, cs, sn = cos, sin(omega_r t_r), t_r = t0_r + dt * accepted_r; the
+        arrays as drive_opts lays them out.  lockin: the sums X_c ... norm on the result; cycle_pos and t_end always.  probes,
+        probe_body, moments: ensemble_run_observed's.  Nothing given: the underlying run"""
+        drive = dict(cos=cos, sin=sin, omega=omega, t0=t0, phase_steps=phase_steps, phase_in=phase_in, cycle_start=cycle_start, lockin=lockin)
+        if probes is not None or moments:
+            return self.ensemble_run_observed(n_steps, probes=probes, probe_body=probe_body, moments=moments, drive=drive, **run_args)
+        return self._ensemble_run(None, n_steps, drive=drive, **run_args)
+
+    def ensemble_drive_eval(self, base, accepted=None, cycle_pos=None, **drive):
+        """the body input a driven run's step would take (rbl_ensemble_drive_eval: the run's own kernel, one launch) -> (input
+        (R, 6 N_bod), cs_sn (R, 2)).  base (6 N_bod,) or (R, 6 N_bod): A0; accepted (R,) the replicas' step counters (None: 0);
+        cycle_pos (R,) their cycle positions (None: cycle_start); drive: drive_opts' keywords"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        if R == 0:
+            self._chk(self.L.rbl_ensemble_get_config(self.h, None, None))       # the state error, as every ensemble call gives it
+        A0 = self._ens_vec(base, 6 * nb, "base")
+        dd, keep = drive_opts("ensemble_drive_eval", 6 * nb, **drive)
+        ints = []
+        for name, a in (("accepted", accepted), ("cycle_pos", cycle_pos)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.int32)
+                if a.shape != (R,):
+                    raise ValueError("ensemble_drive_eval: %s must have shape (%d,); got %s" % (name, R, a.shape))
+            ints.append(a)
+        out, cs_sn = np.zeros((R, 6 * nb)), np.zeros((R, 2))
+        self._chk(self.L.rbl_ensemble_drive_eval(self.h, C.byref(dd), A0.ctypes.data, None if ints[0] is None else ints[0].ctypes.data,
+                                                 None if ints[1] is None else ints[1].ctypes.data, out.ctypes.data, cs_sn.ctypes.data))
+        return out, cs_sn
 
     def ensemble_run_observed(self, n_steps, probes=None, probe_body=None, moments=False, jointed=False, **run_args):
         """a run with observers (rbl_ensemble_run_observed) -> (RunResult, status) as ensemble_run returns them: run_args are

@@ -10,6 +10,7 @@
 //   rbl_forces.hip    configuration-dependent forces (weight, wall and steric repulsion, tabulated potentials, traps)
 //   rbl_ensemble.hip  ensembles of independent replicas of one small system
 //   rbl_ens_field.hip the flow at probe points of every replica of an ensemble, the observers' share of a run's commit
+//   rbl_ens_drive.hip the time-dependent body input of a driven ensemble run, its lock-in sums
 //   rbl_field.hip     the fluid velocity at arbitrary points from blob forces
 //   rbl_mixed.hip     prescribed kinematics: held or driven bodies among free ones, the loads that takes; the entry points of their Brownian step
 //   rbl_flow.hip      imposed linear flow and body-frame slip added to every step's slip, first moments of the blob forces
@@ -17,6 +18,7 @@
 // None of these symbols is exported from librbl.so.
 #pragma once
 #include <functional>
+#include <vector>
 
 #include "rbl_internal.hpp"
 
@@ -252,6 +254,36 @@ void ens_obs_flags_launch(hipStream_t st, unsigned *d_rerr, unsigned *d_oerr, in
 // vflag[r] == 0) last = step and sum += step; frame (may be NULL) = last
 void ens_obs_commit_launch(hipStream_t st, const int *d_stopped, const unsigned *d_vflag, const double *d_step, double *d_last,
                            double *d_sum, double *d_frame, long per_rep, long n);
+
+// ---- rbl_ens_drive.hip --------------------------------------------------------------------------------------------
+// The drive of rbl_ensemble_run_driven (include/rbl.h section 5) as ens_run carries it through a run: the checked options with
+// the per-replica arrays spread to R on the host, and the device pieces carved behind the run's own buffer
+struct RblEnsDriveRun {
+  const rbl_run_drive_opts *o = nullptr;
+  rbl_run_drive_out *out = nullptr;
+  bool masked = false;                           // the run has a mask: F_c, F_s are kept
+  std::vector<int> cum, start;                   // host: the prefix sums of phase_steps (n_phases + 1, or empty), the starting positions [R]
+  std::vector<double> omega, t0;                 // host: [R] each
+  // device
+  double *A0 = nullptr, *C = nullptr, *S = nullptr, *P = nullptr, *om = nullptr, *t0d = nullptr, *cs_sn = nullptr, *sums = nullptr,
+         *t_end = nullptr;
+  int *cum_d = nullptr, *pos = nullptr;
+};
+// the drive's own refusals, none needing a device (R == 0, no ensemble: the checks that need R are left to the underlying run's
+// RBL_ERR_STATE); *empty: no harmonic part, no phases, no lock-in.  Fills D's host side
+int ens_drive_check(rbl_ctx *c, const char *who, const rbl_run_drive_opts *d, int R, int Nb, bool *empty, RblEnsDriveRun *D);
+size_t ens_drive_bytes(const RblEnsDriveRun &D, int R, int Nb);
+// A0 (host, [R 6 N_bod]) and the drive's arrays go up once, the sums start at zero
+int ens_drive_begin(rbl_ctx *c, RblEnsDriveRun &D, void *base, int R, int Nb, const double *A0);
+// k_ens_drive: the step's input of every replica into d_in, from the replicas' accepted counters and cycle positions
+void ens_drive_step(rbl_ctx *c, const RblEnsDriveRun &D, int R, int Nb, const int *d_accepted, double *d_in);
+// k_ens_drive_commit, after the run's commit: Xo the body centres the step started from, U (replica r's six per body at
+// U + r u_stride) the velocities the update read, Fo the masked solve's loads or NULL
+void ens_drive_after(rbl_ctx *c, const RblEnsDriveRun &D, int R, int Nb, const int *d_stopped, const unsigned *d_vflag,
+                     const int *d_accepted, const double *d_Xo, const double *d_U, long u_stride, const double *d_Fo);
+int ens_drive_end(rbl_ctx *c, const RblEnsDriveRun &D, int R, int Nb);   // the read-back into the caller's arrays (enqueued; the caller drains)
+// out of an empty drive: cycle_pos zeros, t_end = t0 + dt accepted on the host
+void ens_drive_empty_out(const rbl_ctx *c, const RblEnsDriveRun &D, int R, const int *accepted);
 
 // ---- rbl_periodic.hip ---------------------------------------------------------------------------------------------
 bool periodic_on(const rbl_ctx *c);           // a cell is set and switched on

@@ -60,6 +60,12 @@
 //   k_ens_obs_commit          per entry: sum += step and last = step where the replica committed; the frame takes last
 // The observers are an argument (EnsObs in EnsStepIn), never context state: without them nothing here launches anything else.
 //
+// With a drive (rbl_ensemble_run_driven; the kernels are in rbl_ens_drive.hip): the same loop with the body input evaluated per
+// replica before every step and followed up after the commit,
+//   k_ens_drive               before the step's sequence: the step's F_body / body_in into EnsWork::F, which the sequence reads as ever
+//   k_ens_drive_commit        after the commit (and the observers'): cycle positions, the lock-in sums
+// The drive is an argument (RblEnsDriveRun): an empty one is the underlying call itself.
+//
 // In a periodic cell (rbl_ensemble_set_periodic; the cell's state and checks are in rbl_periodic.hip): the same launches with the
 // cell's instantiations -- k_gmres_small_per (rbl_small_per.hip) and k_ens_rfd_rhs<true, true> (the image sum inside rbl_small_pair_sweep),
 // k_build_M_per for the dense root, the minimum-image force kernels (ia_eval_batch passes the ensemble's cell).  The jointed calls
@@ -1306,7 +1312,8 @@ EnsRunBuf ens_run_carve(void *base, int R, int Nb, int nbl, bool slip, bool mixe
 // n_steps steps of every replica (checks and ens_ready done by the caller; per: the mask's entries per body): the inputs go up
 // once, every step is the one-step calls' enqueue sequence followed by the verdict and the commit, the buffers flip on the host,
 // ONE read-back ends it.  J (rbl_ensemble_run_jointed): the step is the jointed one and one launch for the joints follows the commit
-int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_out *out, EnsJtRun *J, const EnsRunObs *ob = nullptr)
+int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_out *out, EnsJtRun *J, const EnsRunObs *ob = nullptr,
+            RblEnsDriveRun *dr = nullptr)
 {
   const RblBodyState &S = c->S;
   const bool mixed = o.prescribed != nullptr, reject = o.on_error == RBL_RUN_REJECT;
@@ -1319,11 +1326,14 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
   size_t bytes = 0;
   const rbl_run_obs_opts *oo = ob ? ob->o : nullptr;
   ens_run_carve(nullptr, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes, oo);
-  if ((rc = rbl_dev_reserve(c, c->d_ens_run, bytes + (J ? ens_jt_run_bytes(c, *J, n_frames) : 0)))) return rc;   // the joints' part behind
+  // the joints' part behind, or the drive's (never both: a drive with joints on is refused)
+  if ((rc = rbl_dev_reserve(c, c->d_ens_run, bytes + (J ? ens_jt_run_bytes(c, *J, n_frames) : dr ? ens_drive_bytes(*dr, R, Nb) : 0)))) return rc;
   const EnsRunBuf b = ens_run_carve(c->d_ens_run.p, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes, oo);
   // the uploads, once
   if (mixed && (rc = ens_upload_mask(c, w, o.prescribed, per))) return rc;
-  if ((rc = copy_h2d(c, w.F, mixed ? o.body_in : o.F_body, sizeof(double) * nb6 * Rz))) return rc;
+  // (a driven run: the body input goes into the drive's own buffer, and k_ens_drive writes w.F before every step)
+  if (dr) { if ((rc = ens_drive_begin(c, *dr, (char *)c->d_ens_run.p + bytes, R, Nb, mixed ? o.body_in : o.F_body))) return rc; }
+  else if ((rc = copy_h2d(c, w.F, mixed ? o.body_in : o.F_body, sizeof(double) * nb6 * Rz))) return rc;
   if (o.slip && (rc = copy_h2d(c, b.slip, o.slip, sizeof(double) * n3 * Rz))) return rc;
   RBL_HIP(c, hipMemsetAsync(b.st, 0, b.rb_bytes, c->stream));
   if (mixed) RBL_HIP(c, hipMemsetAsync(b.F_last, 0, sizeof(double) * nb6 * Rz, c->stream));
@@ -1353,6 +1363,7 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
   int enq = 0;
   const auto verdict = S.wall ? k_ens_verdict<true> : k_ens_verdict<false>;
   for (int n = 0; n < o.n_steps; ++n) {
+    if (dr) ens_drive_step(c, *dr, R, Nb, b.accepted, w.F);   // the step's body input, from the replicas' clocks and cycle positions
     rc = brownian ? ens_enqueue_bd(c, w, in, o.seed + (uint64_t)n, o.split_rand, o.delta, o.max_iter, o.rtol)
                   : ens_enqueue_det(c, w, in, o.max_iter, o.rtol, true, J ? &J->step : nullptr);
     if (rc) return rc;
@@ -1379,6 +1390,9 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
       ens_obs_commit_launch(c->stream, &b.st->stopped, b.vflag, b.D_step, b.D_last, b.D_sum, D.fX ? b.fD + k * nD : nullptr, 9L * Nb,
                             (long)nD);
     }
+    if (dr)                                              // the drive follows it too: cycle positions, lock-in sums (q^n, the U the update read)
+      ens_drive_after(c, *dr, R, Nb, &b.st->stopped, b.vflag, b.accepted, D.Xo, mixed ? (const double *)w.U : (const double *)w.x + n3,
+                      mixed ? (long)nb6 : (long)(n3 + nb6), D.Fo);
     c->ens_cur ^= 1;                                     // the new buffer holds every replica's configuration, moved or not
     if (J) ens_jt_run_after(c, *J, D.fX ? (long)((n + 1) / o.stride - 1) : -1L);
     ++enq;
@@ -1421,6 +1435,7 @@ int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_o
     RBL_HIP(c, hipStreamSynchronize(c->stream));
   }
   if (J && (rc = ens_jt_run_end(c, *J, nfr, hs.stopped != 0))) return rc;
+  if (dr && (rc = ens_drive_end(c, *dr, R, Nb))) return rc;
   out->stopped_at = hs.stopped ? hs.stopped - 1 : -1;
   out->steps_done = hs.stopped ? hs.stopped - 1 : o.n_steps;
   out->stop_replica = hs.stopped && hs.stop_rep ? R - hs.stop_rep : -1;
@@ -1622,8 +1637,9 @@ int rbl_ensemble_step_brownian_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6,
                         iters, resid);
 }
 
-// rbl_ensemble_run, and rbl_ensemble_run_observed without joints (ob: its observers, checked there)
-static int ens_run_plain(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out, const EnsRunObs *ob)
+// rbl_ensemble_run, and rbl_ensemble_run_observed without joints (ob: its observers, checked there); dr: the drive of
+// rbl_ensemble_run_driven, checked there and not empty
+static int ens_run_plain(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out, const EnsRunObs *ob, RblEnsDriveRun *dr = nullptr)
 {
   if (!c) return RBL_ERR_ARG;
   if (!o || !out) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: opts or out is NULL");
@@ -1663,7 +1679,8 @@ static int ens_run_plain(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out, co
   if (brownian && (!(c->S.dt > 0.0) || !(o->delta > 0.0))) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: dt and delta must be positive");
   if ((rc = ens_flow_check(c))) return rc;
   if ((rc = ens_ready(c))) return rc;
-  return ens_run(c, *o, per, brownian, out, nullptr, ob);
+  if (dr) dr->masked = masked;
+  return ens_run(c, *o, per, brownian, out, nullptr, ob, dr);
 }
 
 int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out) { return ens_run_plain(c, o, out, nullptr); }
@@ -1725,8 +1742,8 @@ int rbl_ensemble_run_jointed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_jo
 }
 
 // the observers' own refusals, none needing a device, then the underlying run with them (or without: nothing asked for)
-int rbl_ensemble_run_observed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, const rbl_run_obs_opts *obs, rbl_run_out *out,
-                              rbl_run_joint_out *jout, rbl_run_obs_out *oout)
+static int ens_run_observed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, const rbl_run_obs_opts *obs, rbl_run_out *out,
+                            rbl_run_joint_out *jout, rbl_run_obs_out *oout, RblEnsDriveRun *dr)
 {
   const char *who = "ensemble_run_observed";
   const std::string w(who);
@@ -1755,7 +1772,51 @@ int rbl_ensemble_run_observed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_j
   if (frames && obs->moments && !oout->frame_D) return rbl_fail(c, RBL_ERR_ARG, w + ": frame_D must not be NULL while stride > 0 records frames of the moments");
   const EnsRunObs ob = {obs, oout};
   const EnsRunObs *pob = obs->n_probes > 0 || obs->moments ? &ob : nullptr;
-  return jo ? ens_run_jointed(c, o, jo, out, jout, pob) : ens_run_plain(c, o, out, pob);
+  return jo ? ens_run_jointed(c, o, jo, out, jout, pob) : ens_run_plain(c, o, out, pob, dr);
+}
+
+int rbl_ensemble_run_observed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, const rbl_run_obs_opts *obs, rbl_run_out *out,
+                              rbl_run_joint_out *jout, rbl_run_obs_out *oout)
+{
+  return ens_run_observed(c, o, jo, obs, out, jout, oout, nullptr);
+}
+
+// the drive's own refusals (ens_drive_check, rbl_ens_drive.hip), none needing a device; then the underlying run -- with the drive
+// carried through ens_run, or, the drive empty, the very call of rbl_ensemble_run / rbl_ensemble_run_observed
+int rbl_ensemble_run_driven(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_drive_opts *drive, const rbl_run_obs_opts *obs, rbl_run_out *out,
+                            rbl_run_drive_out *dout, rbl_run_obs_out *oout)
+{
+  const char *who = "ensemble_run_driven";
+  const std::string w(who);
+  if (!c) return RBL_ERR_ARG;
+  RblEnsDriveRun D;
+  bool empty = true;
+  if (dout && dout->size != (int64_t)sizeof(rbl_run_drive_out)) return rbl_fail(c, RBL_ERR_ARG, w + ": dout.size is not sizeof(rbl_run_drive_out)");
+  if (drive) {
+    int rc = ens_drive_check(c, who, drive, c->ens_R, c->ens_Nb, &empty, &D); if (rc) return rc;
+    if (!empty && !dout) return rbl_fail(c, RBL_ERR_ARG, w + ": dout is NULL while a drive is given");
+    if (!empty && ens_jt_active(c))
+      return rbl_fail(c, RBL_ERR_STATE, w + ": hard joints are switched on: a drive together with joints is not offered (run_jointed takes no "
+                                            "drive; switch the joints off, or run without a drive)");
+  }
+  D.out = dout;
+  if (!empty) return obs ? ens_run_observed(c, o, nullptr, obs, out, nullptr, oout, &D) : ens_run_plain(c, o, out, nullptr, &D);
+  // nothing drives: the underlying run itself.  Its accepted counts give t_end; the caller may not have asked for them
+  std::vector<int32_t> acc;
+  rbl_run_out oq;
+  const bool want = drive && dout && c->ens_R && out && out->size == (int64_t)sizeof(rbl_run_out);
+  if (want) {
+    oq = *out;
+    if (!oq.accepted) { acc.assign((size_t)c->ens_R, 0); oq.accepted = acc.data(); }
+  }
+  rbl_run_out *po = want ? &oq : out;
+  const int R0 = c->ens_R;
+  int rc = obs ? rbl_ensemble_run_observed(c, o, nullptr, obs, po, nullptr, oout) : rbl_ensemble_run(c, o, po);
+  if (want) {
+    out->steps_done = oq.steps_done; out->stopped_at = oq.stopped_at; out->stop_replica = oq.stop_replica; out->reserved = oq.reserved;
+    if ((rc == RBL_OK || oq.stopped_at >= 0) && !D.t0.empty()) ens_drive_empty_out(c, D, R0, oq.accepted);
+  }
+  return rc;
 }
 
 // ---- what rbl_ens_field.hip reads of the ensemble (rbl_api_internal.hpp) --------------------------------------------

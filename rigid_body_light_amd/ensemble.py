@@ -227,6 +227,22 @@ class Ensemble:
         moments D_b of lambda.  The result gains u_sum / u_mean (R, P, 3) and D_sum / D_mean / stresslet_mean (R, N_bod, 3, 3) over
         the accepted steps and, with stride > 0, frame_u and frame_D.  In a Brownian run these are instantaneous values, thermal
         part included: the mean is the measurement (the drift's share of the stress is not in it)"""
+        n_steps, args, obs = self._run_inputs("run", n_steps, F, prescribed, body_in, brownian, seed, stride, on_error, check_every, slip,
+                                              split_rand, delta, max_iter, rtol, prescribed_dof, probes, probe_body, moments)
+        self.last_run = None
+        if obs is None:
+            res, rc = self.ctx.ensemble_run(n_steps, **args)
+        else:
+            res, rc = self.ctx.ensemble_run_observed(n_steps, *obs, **args)
+        self.last_run = res
+        if rc != 0:
+            raise RblError(res.error)
+        return res
+
+    def _run_inputs(self, who, n_steps, F, prescribed, body_in, brownian, seed, stride, on_error, check_every, slip, split_rand, delta,
+                    max_iter, rtol, prescribed_dof, probes, probe_body, moments):
+        """the checks run makes before the library is called, shared with run_driven -> (n_steps, DeviceContext.ensemble_run's
+        keywords, the observers or None)"""
         modes = {"stop": RUN_STOP, "reject": RUN_REJECT}
         if on_error not in modes:
             _fail("on_error must be 'stop' or 'reject'; got %r" % (on_error,))
@@ -254,18 +270,118 @@ class Ensemble:
         else:
             m, b = self._prescribed_mask(prescribed), self._body_in(body_in)
         s = self._slip(slip)
-        obs = self._observers("run", probes, probe_body, moments)
-        self.last_run = None
+        obs = self._observers(who, probes, probe_body, moments)
         args = dict(F_body=F, prescribed=m, body_in=b, brownian=brownian, seed=seed, stride=stride, on_error=modes[on_error],
                     check_every=check_every, slip=s, split_rand=split_rand, delta=delta, max_iter=max_iter, rtol=rtol, per=per)
-        if obs is None:
-            res, rc = self.ctx.ensemble_run(n_steps, **args)
-        else:
-            res, rc = self.ctx.ensemble_run_observed(n_steps, *obs, **args)
+        return n_steps, args, obs
+
+    # ------------------------------------------------------------------ driven runs (include/rbl.h section 5, rbl_ensemble_run_driven)
+    def _drive(self, who, cos, sin, omega, t0, schedule, cycle_start, lockin=False):
+        """the drive's arrays as run_driven and drive_eval take them -> DeviceContext.ensemble_run_driven's keywords; ValueError
+        before the library is called.  cos, sin: (6 N_bod,), (N_bod, 6), or either with a leading R; omega, t0: a number or (R,);
+        schedule = (phase_steps, phase_in), phase_in (n_phases, 6 N_bod) or (n_phases, R, 6 N_bod); cycle_start an integer or (R,)"""
+        R, nb6 = self.R, 6 * self.N_bodies
+        d = dict(lockin=bool(lockin))
+        for name, a in (("cos", cos), ("sin", sin)):
+            if a is None:
+                continue
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape in ((nb6,), (self.N_bodies, 6)):
+                a = a.reshape(1, nb6)
+            elif a.shape in ((R, nb6), (R, self.N_bodies, 6)):
+                a = a.reshape(R, nb6)
+            else:
+                _fail("%s: %s must have shape (%d,), (%d, 6), (%d, %d) or (%d, %d, 6); got %s"
+                      % (who, name, nb6, self.N_bodies, R, nb6, R, self.N_bodies, a.shape))
+            if not np.isfinite(a).all():
+                _fail("%s: %s must be finite" % (who, name))
+            d[name] = np.ascontiguousarray(a)
+        harmonic = "cos" in d or "sin" in d
+        for name, a in (("omega", omega), ("t0", t0)):
+            if a is None:
+                continue
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape not in ((), (1,), (R,)):
+                _fail("%s: %s must be a number or have shape (%d,); got %s" % (who, name, R, a.shape))
+            if not np.isfinite(a).all():
+                _fail("%s: %s must be finite" % (who, name))
+            d[name] = a.reshape(-1)
+        if (harmonic or lockin) and "omega" not in d:
+            _fail("%s: omega is needed with cos, sin or lockin" % who)
+        length = 0
+        if schedule is not None:
+            try:
+                ps, pi = schedule
+            except (TypeError, ValueError):
+                _fail("%s: schedule must be a pair (phase_steps, phase_in)" % who)
+            ps, pi = np.asarray(ps), np.asarray(pi, dtype=np.float64)
+            if ps.ndim != 1 or not ps.size or not np.issubdtype(ps.dtype, np.integer):
+                _fail("%s: phase_steps must be a non-empty list of integers; got shape %s, dtype %s" % (who, ps.shape, ps.dtype))
+            if (ps < 1).any():
+                _fail("%s: phase_steps[%d] = %d: every phase lasts at least one step" % (who, int(np.flatnonzero(ps < 1)[0]), int(ps[ps < 1][0])))
+            length = int(ps.astype(np.int64).sum())
+            if length > 2**31 - 1:
+                _fail("%s: the cycle's length (the sum of phase_steps) must fit 31 bits" % who)
+            if pi.shape not in ((ps.size, nb6), (ps.size, R, nb6)):
+                _fail("%s: phase_in: one input per phase, shape (%d, %d) or (%d, %d, %d); got %s" % (who, ps.size, nb6, ps.size, R, nb6, pi.shape))
+            if not np.isfinite(pi).all():
+                _fail("%s: phase_in must be finite" % who)
+            d["phase_steps"], d["phase_in"] = ps.astype(np.int32), np.ascontiguousarray(pi)
+        if cycle_start is not None:
+            cs = np.asarray(cycle_start)
+            if cs.shape not in ((), (1,), (R,)) or not np.issubdtype(cs.dtype, np.integer):
+                _fail("%s: cycle_start must be an integer or %d integers; got shape %s, dtype %s" % (who, R, cs.shape, cs.dtype))
+            cs = cs.reshape(-1)
+            if (cs < 0).any() or (cs >= max(length, 1)).any():
+                _fail("%s: cycle_start must lie in the cycle, 0 <= value < %d; got %s" % (who, max(length, 1), cs.tolist()))
+            d["cycle_start"] = cs.astype(np.int32)
+        return d
+
+    def run_driven(self, n_steps, F=None, prescribed=None, body_in=None, cos=None, sin=None, omega=0.0, t0=None, schedule=None,
+                   cycle_start=None, lockin=False, brownian=True, seed=0, stride=0, on_error="stop", check_every=RUN_CHECK_DEFAULT,
+                   slip=None, split_rand=True, delta=1e-4, max_iter=50, rtol=1e-8, prescribed_dof=None, probes=None, probe_body=None,
+                   moments=False):
+        """run with a body input that follows a drive, in ONE call (rbl_ensemble_run_driven): before every step replica r steps with
+            ((A0 + P[phase(p_r)]) + cos * cs) + sin * sn,    cs, sn = cos, sin(omega_r t_r),    t_r = t0_r + dt * accepted_r
+        where A0 is F (all bodies free) or body_in (with prescribed / prescribed_dof: velocities on prescribed entries, loads on
+        free ones).  cos, sin: amplitudes (6 N_bod,) / (N_bod, 6), or with a leading R one set per replica; omega: a number or
+        (R,) -- one frequency per replica makes the run a spectrum --; t0: a number or (R,), None: 0.  schedule = (phase_steps,
+        phase_in): a periodic piecewise-constant part, phase k lasting phase_steps[k] steps with phase_in[k] ((n_phases, 6 N_bod)
+        or (n_phases, R, 6 N_bod)), on the replica's own cycle position, which starts at cycle_start and moves on when the replica
+        commits; a rejected replica's clock and position wait for it.  lockin=True: the result carries X_c, X_s, U_c, U_s, F_c,
+        F_s and norm (RunResult).  It always carries cycle_pos and t_end: run_driven(..., cycle_start=res.cycle_pos, t0=res.t_end)
+        continues the run.  The run is bit for bit the loop of drive_eval and the one-step method; with no drive it is run().
+        The remaining keywords are run's.  Hard joints switched on: RblError (a drive with joints is not offered)"""
+        n_steps, args, obs = self._run_inputs("run_driven", n_steps, F, prescribed, body_in, brownian, seed, stride, on_error, check_every,
+                                              slip, split_rand, delta, max_iter, rtol, prescribed_dof, probes, probe_body, moments)
+        drive = self._drive("run_driven", cos, sin, omega, t0, schedule, cycle_start, lockin)
+        if obs is not None:
+            args.update(probes=obs[0], probe_body=obs[1], moments=obs[2])
+        self.last_run = None
+        res, rc = self.ctx.ensemble_run_driven(n_steps, **drive, **args)
         self.last_run = res
         if rc != 0:
             raise RblError(res.error)
         return res
+
+    def drive_eval(self, base, accepted=None, cycle_pos=None, cos=None, sin=None, omega=0.0, t0=None, schedule=None, cycle_start=None):
+        """the body input run_driven's kernel gives a step that starts with the counters accepted (R,) (None: zeros) and the cycle
+        positions cycle_pos (R,) (None: cycle_start) -> (input (R, 6 N_bod), cs_sn (R, 2)).  base: A0, as F or body_in.  One
+        launch of the run's own kernel: hand the input to step_deterministic, step_brownian(seed + n), step_mixed, ... and the
+        loop reproduces the run bit for bit (numpy's cos and sin are not the device's)"""
+        A0 = self._body_in(base)
+        drive = self._drive("drive_eval", cos, sin, omega, t0, schedule, cycle_start)
+        drive.pop("lockin")
+        ints = []
+        for name, a in (("accepted", accepted), ("cycle_pos", cycle_pos)):
+            if a is not None:
+                a = np.asarray(a)
+                if a.shape != (self.R,) or not np.issubdtype(a.dtype, np.integer):
+                    _fail("drive_eval: %s must be %d integers; got shape %s, dtype %s" % (name, self.R, a.shape, a.dtype))
+                if (a < 0).any():
+                    _fail("drive_eval: %s must be >= 0" % name)
+            ints.append(a)
+        return self.ctx.ensemble_drive_eval(A0, accepted=ints[0], cycle_pos=ints[1], **drive)
 
     # ------------------------------------------------------------------ the flow at probe points, observers (include/rbl.h section 5)
     def _points(self, who, points):
