@@ -835,6 +835,34 @@ int rbl_ensemble_joints_fit(int N_blb, int N_bod, int max_iter, int n_joints, in
  * With the cell off or never set every call of this section launches what it launched before and returns the same bits. */
 int rbl_ensemble_set_periodic(rbl_ctx *ctx, double Lx, double Ly, int nx, int ny, int on);
 int rbl_ensemble_get_periodic(const rbl_ctx *ctx, double *Lx, double *Ly, int *nx, int *ny, int *on);
+/* A cell PER REPLICA -- an area-fraction sweep, or the truncated sum at several image counts, in one call.  The ensemble's cell is
+ * either the shared one above or one per replica; the later of rbl_ensemble_set_periodic / rbl_ensemble_set_cells replaces the
+ * earlier.  Replica r's cell is (Lx[r], Ly[r]) with (nx[r], ny[r]) images; a replica may keep an axis open (L = 0, its n stored as
+ * 0) while another has it periodic.  The cells live on the device as one table of R records, uploaded when they are set and again
+ * at use when the blob radius has changed since, never per step; every kernel that takes the shared cell by value has a form that
+ * reads its replica's record (a workgroup-uniform index: the record sits in scalar registers as the argument does), with the same
+ * arithmetic per pair and image.  So replica r returns the bits of an R = 1 ensemble with the shared cell (Lx[r], Ly[r], nx[r],
+ * ny[r]), R equal rows return the bits of the shared cell, and everything said above of the shared cell holds per replica: every
+ * step, masked solve, run (observed and driven ones with their probes), rbl_ensemble_interaction_forces and
+ * rbl_ensemble_velocity_field take the cells, the jointed calls stay refused.  A replica with more images runs more steps of the
+ * pair sweep: a launch lasts as long as its slowest replica.
+ *   rbl_ensemble_set_cells     R entries of each array; RBL_ERR_ARG for a NULL array and for an R that is not the ensemble's (R < 1
+ *                              without one), then rbl_ensemble_set_periodic's checks in its order, replica by replica -- the
+ *                              message names the first offending replica, "replica 3: Lx ..." --, then the communicator
+ *                              (RBL_ERR_ARG), then a context without an ensemble (RBL_ERR_STATE).  Nothing is stored unless every
+ *                              replica passes.  on = 0 stores the cells switched off.  At use the checks of the shared cell run
+ *                              per replica and name the first offending one, before any device work: RBL_ERR_STATE "periodic
+ *                              cell: replica 0: Lx ... no longer exceeds 4a", and the force model's bounds for a unique minimum
+ *                              image, RBL_ERR_ARG "interactions: replica 2: periodic cell too small ...".
+ *   rbl_ensemble_get_cells     R entries into each array that is not NULL, in both states: a shared cell (or none: zeros) reads
+ *                              back as R equal rows; *per_replica says which state holds.  RBL_ERR_STATE without an ensemble.
+ *   rbl_ensemble_get_periodic  is RBL_ERR_STATE naming rbl_ensemble_get_cells while cells per replica are stored (on or off): there
+ *                              is no one cell to report.
+ *   rbl_ensemble_set_config    with the same R keeps the cells; with another R it is RBL_ERR_STATE and changes nothing while cells
+ *                              per replica are stored, because the table cannot be mapped: call rbl_ensemble_set_cells or
+ *                              rbl_ensemble_set_periodic first. */
+int rbl_ensemble_set_cells(rbl_ctx *ctx, int R, const double *Lx, const double *Ly, const int *nx, const int *ny, int on);
+int rbl_ensemble_get_cells(const rbl_ctx *ctx, double *Lx, double *Ly, int *nx, int *ny, int *on, int *per_replica);
 int rbl_ensemble_set_config(rbl_ctx *ctx, int R, int N_bod, const double *X, const double *Q);
 int rbl_ensemble_get_config(rbl_ctx *ctx, double *X, double *Q);
 int rbl_ensemble_info(const rbl_ctx *ctx, int *R, int *N_bod);

@@ -121,6 +121,8 @@ def lib(path=None):
         L.rbl_get_periodic.argtypes = [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.rbl_ensemble_set_periodic.argtypes = L.rbl_set_periodic.argtypes
         L.rbl_ensemble_get_periodic.argtypes = L.rbl_get_periodic.argtypes
+        L.rbl_ensemble_set_cells.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int]
+        L.rbl_ensemble_get_cells.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.rbl_interaction_forces_dev.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_forces.argtypes = [vp, vp, vp, C.POINTER(dbl)]
         L.rbl_interaction_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
@@ -605,6 +607,11 @@ class RunResult:
             self.steps_done, self.stopped_at, int(self.accepted.min()), int(self.accepted.max()), int(self.rejected.sum()))
 
 
+def np_contig(a):
+    import numpy as np
+    return np.ascontiguousarray(a)
+
+
 def periodic_args(who, Lx, Ly, images):
     """the checks set_periodic can make before the library is called -> (Lx, Ly, nx, ny)"""
     import numbers
@@ -621,6 +628,51 @@ def periodic_args(who, Lx, Ly, images):
         if isinstance(v, bool) or not isinstance(v, numbers.Integral):
             raise TypeError("%s: images must be integers, got %r" % (who, v))
     return float(Lx), float(Ly), int(n[0]), int(n[1])
+
+
+def cells_args(who, Lx, Ly, images, R=None):
+    """the checks set_cells can make before the library is called: Lx, Ly real scalars or (R,), images (nx, ny) or (R, 2) of
+    integers, scalars broadcast -> (Lx (R,), Ly (R,), n (R, 2) int32).  R=None: the arrays' own common length (1 when all are
+    scalars), for the caller to compare with the ensemble's"""
+    import numbers
+    import numpy as np
+    sizes = {}
+    out = {}
+    for name, v in (("Lx", Lx), ("Ly", Ly)):
+        if isinstance(v, bool) or isinstance(v, (str, bytes)) or v is None:
+            raise TypeError("%s: %s must be a real number or an array of R real numbers, got %r" % (who, name, v))
+        if isinstance(v, numbers.Real):
+            out[name] = float(v)
+            continue
+        try:
+            arr = np.asarray(v)
+        except Exception:
+            raise TypeError("%s: %s must be a real number or an array of R real numbers, got %r" % (who, name, v)) from None
+        if arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
+            raise TypeError("%s: %s must hold real numbers, got dtype %s" % (who, name, arr.dtype))
+        if arr.ndim != 1 or arr.size < 1:
+            raise ValueError("%s: %s must be a real number or have shape (R,), got shape %s" % (who, name, arr.shape))
+        out[name] = arr.astype(np.float64)
+        sizes[name] = arr.size
+    try:
+        narr = np.asarray(images)
+    except Exception:
+        raise TypeError("%s: images must be a pair of integers (nx, ny) or an (R, 2) array of integers, got %r" % (who, images)) from None
+    if narr.dtype == np.bool_ or not np.issubdtype(narr.dtype, np.integer):
+        raise TypeError("%s: images must be integers, got %r" % (who, images))
+    if narr.shape == (2,):
+        pass
+    elif narr.ndim == 2 and narr.shape[1] == 2 and narr.shape[0] >= 1:
+        sizes["images"] = narr.shape[0]
+    else:
+        raise ValueError("%s: images must be a pair (nx, ny) or have shape (R, 2), got shape %s" % (who, narr.shape))
+    if R is None:
+        R = max(sizes.values()) if sizes else 1
+    for name, n in sizes.items():
+        if n != R:
+            raise ValueError("%s: %s has %d entries, the ensemble has R = %d replicas" % (who, name, n, R))
+    L = [np.ascontiguousarray(np.broadcast_to(out[name], (R,)), dtype=np.float64) for name in ("Lx", "Ly")]
+    return L[0], L[1], np.ascontiguousarray(np.broadcast_to(narr, (R, 2)), dtype=np.int32)
 
 
 class DeviceContext:
@@ -1120,6 +1172,30 @@ class DeviceContext:
         Lx, Ly, nx, ny, on = C.c_double(0.0), C.c_double(0.0), C.c_int(0), C.c_int(0), C.c_int(0)
         self._chk(self.L.rbl_ensemble_get_periodic(self.h, C.byref(Lx), C.byref(Ly), C.byref(nx), C.byref(ny), C.byref(on)))
         return dict(on=bool(on.value), Lx=Lx.value, Ly=Ly.value, images=(nx.value, ny.value))
+
+    def ensemble_set_cells(self, Lx, Ly, images=(1, 1), on=True):
+        """a periodic cell PER REPLICA of the context's ensemble: Lx, Ly real scalars or (R,), images (nx, ny) or (R, 2); scalars
+        broadcast.  Replica r sums over its own images in the solver, the drift, the dense Brownian root and the probes, and its pair
+        forces use its own minimum image.  Replaces a shared cell (ensemble_set_periodic), as that replaces this"""
+        args = cells_args("ensemble_set_cells", Lx, Ly, images)       # types and shapes, before the library is called
+        R = self.ensemble_info()[0]
+        if R:                                                # (no ensemble: the library's refusal, behind its argument checks)
+            args = cells_args("ensemble_set_cells", Lx, Ly, images, R)
+        Lx, Ly, n = args
+        nx, ny = np_contig(n[:, 0]), np_contig(n[:, 1])
+        self._chk(self.L.rbl_ensemble_set_cells(self.h, Lx.size, Lx.ctypes.data, Ly.ctypes.data, nx.ctypes.data, ny.ctypes.data,
+                                                int(bool(on))))
+
+    def ensemble_cells(self):
+        """{on, per_replica, Lx (R,), Ly (R,), images (R, 2)} of the ensemble's cell, shared (R equal rows) or per replica"""
+        import numpy as np
+        R = self.ensemble_info()[0]
+        Lx, Ly = np.zeros(R), np.zeros(R)
+        nx, ny = np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32)
+        on, per = C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_ensemble_get_cells(self.h, Lx.ctypes.data, Ly.ctypes.data, nx.ctypes.data, ny.ctypes.data, C.byref(on),
+                                                C.byref(per)))
+        return dict(on=bool(on.value), per_replica=bool(per.value), Lx=Lx, Ly=Ly, images=np.stack([nx, ny], axis=1))
 
     def set_bond_table(self, U, dU, r_min, r_cut, on=True):
         """the potential T(d) of the kind-1 bonds from its values U and derivatives dU = dU/dd on the uniform grid r_min .. r_cut

@@ -226,6 +226,7 @@ struct RblEnsView {
   int R, Nb, nbl;
   bool cell;
   RblSmallCell C;
+  const RblEnsCellRec *cells;                 // a cell per replica: the table on the device (C is then unused); NULL: the shared cell C
 };
 int ens_state_refusals(rbl_ctx *c, const char *who);
 int ens_view(rbl_ctx *c, RblEnsView *v);
@@ -246,7 +247,9 @@ struct RblEnsProbe {
 int ens_points_check(rbl_ctx *c, const char *who, const double *points, int64_t n_points, int sets);
 struct RblEnsProbeGeom { int NI, waves; int64_t tiles; };
 RblEnsProbeGeom ens_probe_geometry(int64_t n_points, int R, int n_cu);
-void ens_probe_launch(hipStream_t st, const RblParams &P, bool wall, const RblSmallCell *cell, const RblEnsProbe &A, int R, int n_cu);
+// cell: the shared cell, or NULL: none; cells (a cell per replica, device): replica r sums over the images of cells[r], cell is unused
+void ens_probe_launch(hipStream_t st, const RblParams &P, bool wall, const RblSmallCell *cell, const RblEnsProbe &A, int R, int n_cu,
+                      const RblEnsCellRec *cells = nullptr);
 // a run's step, behind ens_probe_launch with rerr = d_oerr (R words, zero before the run's first step): rerr[r] = oerr[r] where
 // rerr[r] is still clear, oerr cleared again
 void ens_obs_flags_launch(hipStream_t st, unsigned *d_rerr, unsigned *d_oerr, int R);
@@ -291,6 +294,12 @@ bool periodic_on(const rbl_ctx *c);           // a cell is set and switched on
 int periodic_refuse(rbl_ctx *c, const char *who);
 // the checks a cell meets at use, shared by the single context's product and the ensembles' steps: RBL_ERR_STATE "periodic cell: the
 // wall term is off ..." / "... no longer exceeds 4a ... (call <setter> again)"; L: the cell's two lengths
-int periodic_use_check(rbl_ctx *c, bool wall, const double *L, const char *setter);
+// replica >= 0 (an ensemble with a cell per replica): the message names it, "periodic cell: replica 3: Lx ..."
+int periodic_use_check(rbl_ctx *c, bool wall, const double *L, const char *setter, int replica = -1);
+// an ensemble's cells are stored per replica (rbl_ensemble_set_cells; on or off), not as the one shared cell
+bool ens_cells_stored(const rbl_ctx *c);
+// the table of those cells on the device (rbl_ctx::d_ens_cells), in units of the current blob radius: uploaded when the cells are
+// set, and by the callers at use when a has changed since -- never per step.  Nothing while the table is current
+int ens_cells_upload(rbl_ctx *c);
 
 #pragma GCC visibility pop

@@ -149,6 +149,7 @@ static const RblBufRow kDevBufs[] = {
     {&rbl_ctx::d_iab, RBL_BUF_PERSIST},           // bonds: anchors, parameters, topology (ia_bd_valid)
     {&rbl_ctx::d_iabs, RBL_BUF_SCRATCH},          // bond state queries: reserved at their start, within one call
     {&rbl_ctx::d_ens, RBL_BUF_PERSIST},           // ensemble configurations
+    {&rbl_ctx::d_ens_cells, RBL_BUF_PERSIST},     // an ensemble's cell per replica, R records (ens_cells_valid)
     {&rbl_ctx::d_ens_w, RBL_BUF_SCRATCH},         // ensemble step workspace: reserved at the start of each ensemble entry point
     {&rbl_ctx::d_ens_run, RBL_BUF_SCRATCH},       // ensemble run: inputs, counters and frames, reserved at the start of rbl_ensemble_run
     {&rbl_ctx::d_ens_obs, RBL_BUF_SCRATCH},       // ensemble velocity field: reserved at its start, within one call (error words: hipMemsetAsync before the launch)

@@ -13,6 +13,7 @@
 //                                over the blobs in index order; PER: the nearest-image reduction once per (point, blob), then
 //                                the images p, then q, innermost (sweep_tile_per's order, rbl_kernels.hip); an open axis has a
 //                                zero reciprocal and no images (RblSmallCell), so its reduction leaves the displacement alone.
+//                                CELLS: replica r's own cell, read from the table of rbl_ensemble_set_cells.
 //                                Points fixed in a body (body >= 0) are placed at X_b + R(Q_b) s_p of the same configuration.
 //   k_ens_obs_flags              one thread per replica, behind the probe kernel in a run: its flags enter the replica's error word
 //                                only where the step has not failed already
@@ -59,13 +60,20 @@ __device__ __forceinline__ void ep_place(const double *Rm, const double *X, doub
   p0 = l0 + X[0]; p1 = l1 + X[1]; p2 = l2 + X[2];
 }
 
-template <bool WALL, bool PER, int NI>
+// CELLS (a cell per replica, rbl_ensemble_set_cells): Cin is the table of R records and the workgroup reads its replica's first, a
+// scalar load at a workgroup-uniform index; the sums that follow are those of the launch with that cell by value
+template <bool WALL, bool PER, int NI, bool CELLS = false>
 __global__ __launch_bounds__(64 * EP_WAVES_MAX) void k_ens_probe(RblParams P, RblEnsProbe A,
-                                                                  std::conditional_t<PER, RblSmallCell, EpNoCell> C)
+                                                                  std::conditional_t<CELLS, const RblEnsCellRec *, std::conditional_t<PER, RblSmallCell, EpNoCell>> Cin)
 {
   static_assert(WALL || !PER, "the free-space lattice sum diverges: a cell needs the wall");
+  static_assert(PER || !CELLS, "a table of cells is a periodic launch");
   __shared__ EpBlob sj[EP_N_MAX];
   const int r = blockIdx.y, t = threadIdx.x, nt = blockDim.x;
+  RblSmallCell C = {};
+  if constexpr (CELLS) C = Cin[r].S;
+  else if constexpr (PER) C = Cin;
+  (void)C;
   const int N = A.Nb * A.nbl;
   const double *X = A.X + (size_t)r * 3 * A.Nb, *Q = A.Q + (size_t)r * 4 * A.Nb;
   const double *lam = A.lam + (size_t)r * (size_t)A.lam_stride;
@@ -173,19 +181,23 @@ __global__ __launch_bounds__(256) void k_ens_obs_flags(unsigned *__restrict__ re
 }
 
 template <bool WALL, bool PER, int NI>
-void ep_launch(hipStream_t st, const RblParams &P, const RblSmallCell *cell, const RblEnsProbe &A, int R, const RblEnsProbeGeom &g)
+void ep_launch(hipStream_t st, const RblParams &P, const RblSmallCell *cell, const RblEnsCellRec *cells, const RblEnsProbe &A, int R,
+               const RblEnsProbeGeom &g)
 {
   const dim3 grid((unsigned)g.tiles, (unsigned)R), block((unsigned)(64 * g.waves));
-  if constexpr (PER) hipLaunchKernelGGL((k_ens_probe<WALL, true, NI>), grid, block, 0, st, P, A, *cell);
-  else hipLaunchKernelGGL((k_ens_probe<WALL, false, NI>), grid, block, 0, st, P, A, EpNoCell{});
+  if constexpr (PER) {
+    if (cells) hipLaunchKernelGGL((k_ens_probe<WALL, true, NI, true>), grid, block, 0, st, P, A, cells);
+    else hipLaunchKernelGGL((k_ens_probe<WALL, true, NI>), grid, block, 0, st, P, A, *cell);
+  } else hipLaunchKernelGGL((k_ens_probe<WALL, false, NI>), grid, block, 0, st, P, A, EpNoCell{});
 }
 
 template <bool WALL, bool PER>
-void ep_launch_ni(hipStream_t st, const RblParams &P, const RblSmallCell *cell, const RblEnsProbe &A, int R, const RblEnsProbeGeom &g)
+void ep_launch_ni(hipStream_t st, const RblParams &P, const RblSmallCell *cell, const RblEnsCellRec *cells, const RblEnsProbe &A, int R,
+                  const RblEnsProbeGeom &g)
 {
-  if (g.NI == 4) ep_launch<WALL, PER, 4>(st, P, cell, A, R, g);
-  else if (g.NI == 2) ep_launch<WALL, PER, 2>(st, P, cell, A, R, g);
-  else ep_launch<WALL, PER, 1>(st, P, cell, A, R, g);
+  if (g.NI == 4) ep_launch<WALL, PER, 4>(st, P, cell, cells, A, R, g);
+  else if (g.NI == 2) ep_launch<WALL, PER, 2>(st, P, cell, cells, A, R, g);
+  else ep_launch<WALL, PER, 1>(st, P, cell, cells, A, R, g);
 }
 
 // the one-shot field's argument checks that need no device; *noop: n_points == 0
@@ -223,7 +235,8 @@ int ep_run(rbl_ctx *c, const RblEnsView &v, const double *d_pts, int64_t n_point
                          (int)n_points, probe_body};
   {
     RblPhase ph(c, RBL_T_PRODUCT);
-    ens_probe_launch(c->stream, rbl_make_params(c->S.a, c->S.eta), c->S.wall, v.cell ? &v.C : nullptr, A, R, c->n_cu);
+    ens_probe_launch(c->stream, rbl_make_params(c->S.a, c->S.eta), c->S.wall, v.cell ? &v.C : nullptr, A, R, c->n_cu,
+                     v.cell ? v.cells : nullptr);
     RBL_HIP(c, hipGetLastError());
   }
   std::vector<unsigned> h((size_t)R);
@@ -267,13 +280,14 @@ RblEnsProbeGeom ens_probe_geometry(int64_t n_points, int R, int n_cu)
   return g;
 }
 
-void ens_probe_launch(hipStream_t st, const RblParams &P, bool wall, const RblSmallCell *cell, const RblEnsProbe &A, int R, int n_cu)
+void ens_probe_launch(hipStream_t st, const RblParams &P, bool wall, const RblSmallCell *cell, const RblEnsProbe &A, int R, int n_cu,
+                      const RblEnsCellRec *cells)
 {
   if (A.P <= 0) return;
   const RblEnsProbeGeom g = ens_probe_geometry(A.P, R, n_cu);
-  if (cell) ep_launch_ni<true, true>(st, P, cell, A, R, g);       // (a cell needs the wall: the callers' periodic_use_check)
-  else if (wall) ep_launch_ni<true, false>(st, P, nullptr, A, R, g);
-  else ep_launch_ni<false, false>(st, P, nullptr, A, R, g);
+  if (cell || cells) ep_launch_ni<true, true>(st, P, cell, cells, A, R, g);   // (a cell needs the wall: the callers' periodic_use_check)
+  else if (wall) ep_launch_ni<true, false>(st, P, nullptr, nullptr, A, R, g);
+  else ep_launch_ni<false, false>(st, P, nullptr, nullptr, A, R, g);
 }
 
 void ens_obs_flags_launch(hipStream_t st, unsigned *d_rerr, unsigned *d_oerr, int R)

@@ -70,6 +70,9 @@
 // cell's instantiations -- k_gmres_small_per (rbl_small_per.hip) and k_ens_rfd_rhs<true, true> (the image sum inside rbl_small_pair_sweep),
 // k_build_M_per for the dense root, the minimum-image force kernels (ia_eval_batch passes the ensemble's cell).  The jointed calls
 // are refused with the cell on.  Cell off: nothing here launches anything else than before.
+// With a cell PER REPLICA (rbl_ensemble_set_cells): the same launches again with the forms that read the replica's cell from the
+// table of R records on the device (ens_cell_table) -- k_gmres_small_cells (rbl_small_cells.hip), k_ens_rfd_rhs<true, true, true>,
+// k_build_M_cells, the probe kernel's and the force kernels' table forms.  ens_cell_use is the one check at use, per replica.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -243,8 +246,10 @@ __global__ __launch_bounds__(ET) void k_ens_midpoint_masked(int nbod, int Nb, in
 // Also checks the replica's dense factor: a diagonal entry that is not positive and finite is RBL_FLAG_NOT_SPD.
 // PER (the ensemble's periodic cell, wall only): both products are the cell's -- the pair sweep sums over the images and takes in
 // every blob's own; the cell is one more kernel argument (an empty one otherwise: the two open instantiations keep their code).
+// CELLS (a cell per replica, rbl_ensemble_set_cells): the argument is the table of R records, and the workgroup reads its
+// replica's before anything else -- a scalar load at a workgroup-uniform index, so the cell sits in scalar registers as before.
 struct EnsNoCell {};
-template <bool WALL, bool PER = false>
+template <bool WALL, bool PER = false, bool CELLS = false>
 __global__ __launch_bounds__(RBL_SG_THREADS) void k_ens_rfd_rhs(RblParams P, int Nb, int nbl, const double *__restrict__ X,
                                                                 const double *__restrict__ Q, const double *__restrict__ cfg,
                                                                 const double *__restrict__ dq, double delta,
@@ -253,10 +258,15 @@ __global__ __launch_bounds__(RBL_SG_THREADS) void k_ens_rfd_rhs(RblParams P, int
                                                                 const double *__restrict__ F, const double *__restrict__ FT,
                                                                 double kBT, double c2, int split, double *__restrict__ rhs,
                                                                 unsigned *__restrict__ rerr,
-                                                                std::conditional_t<PER, RblSmallCell, EnsNoCell> C = {})
+                                                                std::conditional_t<CELLS, const RblEnsCellRec *, std::conditional_t<PER, RblSmallCell, EnsNoCell>> C = {})
 {
+  static_assert(PER || !CELLS, "a table of cells is a periodic launch");
   extern __shared__ double sm[];
   const int r = blockIdx.x, t = threadIdx.x;
+  RblSmallCell Cr = {};
+  if constexpr (CELLS) Cr = C[r].S;
+  else if constexpr (PER) Cr = C;
+  (void)Cr;
   const int N = Nb * nbl, n3 = 3 * N, nb6 = 6 * Nb;
   double *pos = sm, *dmp = pos + n3, *su = dmp + N, *vin = su + n3, *acc = vin + n3, *Xs = acc + n3, *Qs = Xs + 3 * Nb,
          *part = Qs + 4 * Nb;
@@ -301,7 +311,7 @@ __global__ __launch_bounds__(RBL_SG_THREADS) void k_ens_rfd_rhs(RblParams P, int
                                        di * vin[3 * t], di * vin[3 * t + 1], di * vin[3 * t + 2], true, ux, uy, uz, flags);
       su[3 * t] = ux; su[3 * t + 1] = uy; su[3 * t + 2] = uz;
     }
-    if constexpr (PER) rbl_small_pair_sweep<WALL, true>(Pu, pos, dmp, vin, N, part, flags, C);
+    if constexpr (PER) rbl_small_pair_sweep<WALL, true>(Pu, pos, dmp, vin, N, part, flags, Cr);
     else rbl_small_pair_sweep<WALL>(Pu, pos, dmp, vin, N, part, flags);
     for (int e = t; e < n3; e += RBL_SG_THREADS) {
       double s = su[e];
@@ -545,6 +555,25 @@ int ens_state_check(rbl_ctx *c, const std::string &pre, bool comm_last = false)
 // the ensemble's periodic cell (rbl_ensemble_set_periodic; include/rbl.h section 5): on, and as the one-workgroup kernels take it
 bool ens_cell_on(const rbl_ctx *c) { return c->ens_per_on; }
 RblSmallCell ens_cell(const rbl_ctx *c) { return rbl_small_cell(c->S.a, c->ens_per_L, c->ens_per_n); }
+// a cell per replica (rbl_ensemble_set_cells): the table on the device, R records -- NULL while the cell is the shared one, and
+// every launch that takes a cell then takes ens_cell(c) by value as it always did
+const RblEnsCellRec *ens_cell_table(const rbl_ctx *c)
+{
+  return ens_cells_stored(c) ? (const RblEnsCellRec *)c->d_ens_cells.p : nullptr;
+}
+
+// what a step, a solve or the one-shot field asks of the ensemble's cell at use, before any device work: the wall term and lengths
+// the current parameters have not outgrown (periodic_use_check) -- replica by replica with a cell per replica, the first offending
+// one named --, then the table in the current parameters' units.  Nothing while the cell is off
+int ens_cell_use(rbl_ctx *c)
+{
+  if (!ens_cell_on(c)) return RBL_OK;
+  if (!ens_cells_stored(c)) return periodic_use_check(c, c->S.wall, c->ens_per_L, "rbl_ensemble_set_periodic");
+  int rc;
+  for (size_t r = 0; 2 * r < c->ens_cells_L.size(); ++r)
+    if ((rc = periodic_use_check(c, c->S.wall, &c->ens_cells_L[2 * r], "rbl_ensemble_set_cells", (int)r))) return rc;
+  return ens_cells_upload(c);
+}
 
 // what is not offered with the ensemble's cell on: RBL_ERR_STATE before any device work
 int ens_cell_refuse(rbl_ctx *c, const char *who)
@@ -705,6 +734,7 @@ int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const doubl
   const RblSmallEns S = {Xs, Qs, ens_cfg(c), nbl, Nb, R, w.rhs, w.x, max_iter, rtol, w.gm, w.iters, w.resid, w.rerr};
   const unsigned char *mask = mixed ? w.mask : nullptr;
   int rc = jt               ? rbl_launch_gmres_small_ens_jt(c->stream, P, c->S.wall, S, jt->T, evolve ? 1 : 0, jt->coef)
+           : ens_cell_table(c) && ens_cell_on(c) ? rbl_launch_gmres_small_ens_cells(c->stream, P, ens_cell_table(c), S, mask, w.F, per)
            : ens_cell_on(c) ? rbl_launch_gmres_small_ens_per(c->stream, P, ens_cell(c), S, mask, w.F, per)
                             : rbl_launch_gmres_small_ens(c->stream, P, c->S.wall, S, mask, w.F, per);
   if (rc)
@@ -724,7 +754,7 @@ int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const doubl
       const RblSmallCell cell = ens_cell(c);
       const RblEnsProbe A = {Xs, Qs, ens_cfg(c), w.x, nsys, obs->pts, obs->sets == 1 ? 0L : 3L * obs->P, obs->u_step, obs->oerr, Nb, nbl,
                              obs->P, obs->body};
-      ens_probe_launch(c->stream, P, c->S.wall, ens_cell_on(c) ? &cell : nullptr, A, R, c->n_cu);
+      ens_probe_launch(c->stream, P, c->S.wall, ens_cell_on(c) ? &cell : nullptr, A, R, c->n_cu, ens_cell_on(c) ? ens_cell_table(c) : nullptr);
       ens_obs_flags_launch(c->stream, w.rerr, obs->oerr, R);   // into the replica's word, unless its step has failed already
     }
   }
@@ -787,7 +817,7 @@ int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_i
   const bool mixed = in.prescribed != nullptr;
   const double *FT, *SL;
   int rc;
-  if (ens_cell_on(c) && (rc = periodic_use_check(c, c->S.wall, c->ens_per_L, "rbl_ensemble_set_periodic"))) return rc;
+  if ((rc = ens_cell_use(c))) return rc;
   if (mixed && !in.resident && (rc = ens_upload_mask(c, w, in.prescribed, in.per))) return rc;
   if ((rc = ens_begin(c, w, in.F_body, in.slip, &FT, &SL, move, in.resident, in.accepted))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb;
@@ -825,7 +855,7 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
   const RblBodyState &S = c->S;
   const bool mixed = in.prescribed != nullptr, per_cell = ens_cell_on(c);
   int rc;
-  if (per_cell && (rc = periodic_use_check(c, S.wall, c->ens_per_L, "rbl_ensemble_set_periodic"))) return rc;
+  if ((rc = ens_cell_use(c))) return rc;
   if (mixed && !in.resident && (rc = ens_upload_mask(c, w, in.prescribed, in.per))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = S.N_blb, N = Nb * nbl;
   const int64_t n3 = 3 * (int64_t)N;
@@ -836,7 +866,9 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
   const double *X = ens_X(c, c->ens_cur), *Q = ens_Q(c, c->ens_cur);
   // dense root of every replica: B M B (:667-669), lower Cholesky (:670-671), L W1 and L W2 (:672)
   const RblParams P = rbl_make_params(S.a, S.eta);
-  if (per_cell)
+  const RblEnsCellRec *cells = per_cell ? ens_cell_table(c) : nullptr;   // a cell per replica: every kernel below reads its replica's
+  if (cells) rbl_launch_build_M_cells_batched(c->stream, P, true, w.pos, N, R, w.Lm, n3 * n3, w.rerr, 1, cells);
+  else if (per_cell)
     rbl_launch_build_M_per_batched(c->stream, P, true, w.pos, N, R, w.Lm, n3 * n3, w.rerr, 1, c->ens_per_L[0], c->ens_per_L[1],
                                    c->ens_per_n[0], c->ens_per_n[1]);
   else
@@ -868,7 +900,8 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
                        SL, (const double *)w.F, FT, S.kBT, c2, split, w.rhs, w.rerr, cell);
     return (int)RBL_OK;
   };
-  if ((rc = per_cell ? rfd_rhs(k_ens_rfd_rhs<true, true>, ens_cell(c))
+  if ((rc = cells    ? rfd_rhs(k_ens_rfd_rhs<true, true, true>, cells)
+            : per_cell ? rfd_rhs(k_ens_rfd_rhs<true, true>, ens_cell(c))
             : S.wall ? rfd_rhs(k_ens_rfd_rhs<true>, EnsNoCell{})
                      : rfd_rhs(k_ens_rfd_rhs<false>, EnsNoCell{})))
     return rc;
@@ -1511,7 +1544,12 @@ int rbl_ensemble_set_config(rbl_ctx *c, int R, int N_bod, const double *X, const
   if (!rbl_gmres_small_fits(c->S.N_blb, N_bod, 1, false))
     return rbl_fail(c, RBL_ERR_SIZE, "ensemble: the system is beyond the one-kernel solver (N_bod * N_blb <= 256, N_bod <= 64 and its vectors within 150 KB of LDS: about 75 N_blobs + 60 N_bod doubles)");
   if (!X || !Q) return rbl_fail(c, RBL_ERR_ARG, "ensemble_set_config: null argument");
-  {                                                    // K^T K of the structure (rotation invariant) must be invertible (:312-316)
+  // a shared cell holds for any R; a table of cells belongs to the R it was given for
+  if (ens_cells_stored(c) && (size_t)R != c->ens_cells_L.size() / 2)
+    return rbl_fail(c, RBL_ERR_STATE, "ensemble_set_config: R = " + std::to_string(R) + ", and cells are stored for " +
+                                          std::to_string(c->ens_cells_L.size() / 2) + " replicas, which cannot be mapped to another R: call "
+                                          "rbl_ensemble_set_cells or rbl_ensemble_set_periodic first");
+  {                                                // K^T K of the structure (rotation invariant) must be invertible (:312-316)
     RblBodyState T = c->S;
     T.N_bod = 1; T.X.assign(3, 0.0); T.Q = {1.0, 0.0, 0.0, 0.0};
     if ((rc = rbl_body_set_K(T, c->last_error))) return rc;
@@ -1826,8 +1864,9 @@ int ens_view(rbl_ctx *c, RblEnsView *v)
 {
   int rc = ens_ready(c); if (rc) return rc;
   v->cell = ens_cell_on(c);
-  if (v->cell && (rc = periodic_use_check(c, c->S.wall, c->ens_per_L, "rbl_ensemble_set_periodic"))) return rc;
+  if ((rc = ens_cell_use(c))) return rc;
   v->C = ens_cell(c);
+  v->cells = ens_cell_table(c);
   v->X = ens_X(c, c->ens_cur); v->Q = ens_Q(c, c->ens_cur); v->cfg = ens_cfg(c);
   v->R = c->ens_R; v->Nb = c->ens_Nb; v->nbl = c->S.N_blb;
   return RBL_OK;

@@ -71,6 +71,14 @@ struct IaCell {
   int px, py;
 };
 
+// replica w's cell from the table of an ensemble with a cell per replica (rbl_ensemble_set_cells): every kernel below that takes
+// the table reads the record of its body's or tile's window first, a workgroup-uniform index into a table that is only read
+__device__ __forceinline__ IaCell ia_cell_of(const RblEnsCellRec *__restrict__ cells, int w)
+{
+  const RblEnsCellRec &R = cells[w];
+  return {R.Lx, R.Ly, R.iLx, R.iLy, R.Lx > 0.0 ? 1 : 0, R.Ly > 0.0 ? 1 : 0};
+}
+
 // minimum-image convention on a displacement: d - L rint(d / L) on every periodic axis
 __device__ __forceinline__ void ia_min_image(const IaCell &C, double &dx, double &dy)
 {
@@ -108,12 +116,12 @@ __global__ __launch_bounds__(64) void k_body_neighbours(const double *__restrict
   }
 }
 
-// the same with the centre distance by minimum image (a periodic cell).  Its own kernel, the body repeated: k_body_neighbours
-// as an instantiation of a shared template came out of the compiler with its registers permuted, and the existing kernels keep
-// their code instruction for instruction
-__global__ __launch_bounds__(64) void k_body_neighbours_per(const double *__restrict__ X, int N_bod, int win, double cut2, int cull,
-                                                            int cap, IaCell C, int *__restrict__ cnt, int *__restrict__ list,
-                                                            unsigned *__restrict__ err)
+// the same with the centre distance by minimum image (a periodic cell).  Its own body, k_body_neighbours' repeated: that kernel
+// as an instantiation of a shared template came out of the compiler with its registers permuted, and it keeps its code instruction
+// for instruction.  The two periodic kernels -- the cell by value, or the cell of the body's window from a table -- share this one
+__device__ __forceinline__ void ia_body_neighbours_per(const double *__restrict__ X, int N_bod, int win, double cut2, int cull, int cap,
+                                                       const IaCell &C, int *__restrict__ cnt, int *__restrict__ list,
+                                                       unsigned *__restrict__ err)
 {
   const int i = blockIdx.x, t = threadIdx.x;
   const double xi = X[3 * (size_t)i], yi = X[3 * (size_t)i + 1], zi = X[3 * (size_t)i + 2];
@@ -140,6 +148,21 @@ __global__ __launch_bounds__(64) void k_body_neighbours_per(const double *__rest
     cnt[i] = base;                                       // may exceed cap: the pair kernel walks min(cnt, cap) and the overflow is reported
     if (base > cap) atomicOr(err, (unsigned)RBL_FLAG_CAPACITY);
   }
+}
+
+__global__ __launch_bounds__(64) void k_body_neighbours_per(const double *__restrict__ X, int N_bod, int win, double cut2, int cull,
+                                                            int cap, IaCell C, int *__restrict__ cnt, int *__restrict__ list,
+                                                            unsigned *__restrict__ err)
+{
+  ia_body_neighbours_per(X, N_bod, win, cut2, cull, cap, C, cnt, list, err);
+}
+
+// ... and in the cell of the body's window, one per replica
+__global__ __launch_bounds__(64) void k_body_neighbours_cells(const double *__restrict__ X, int N_bod, int win, double cut2, int cull,
+                                                              int cap, const RblEnsCellRec *__restrict__ cells, int *__restrict__ cnt,
+                                                              int *__restrict__ list, unsigned *__restrict__ err)
+{
+  ia_body_neighbours_per(X, N_bod, win, cut2, cull, cap, ia_cell_of(cells, blockIdx.x / win), cnt, list, err);
 }
 
 // a tabulated potential on the device: coef[k] = (c0, c1, c2, c3) of interval k, U = c0 + t (c1 + t (c2 + t c3)),
@@ -288,6 +311,19 @@ __global__ __launch_bounds__(IA_BT) void k_blob_interactions_per(const double *_
   static_assert(TAB >= 0 && TAB <= 3, "bit 0: pair table, bit 1: height table");
   __shared__ double s[IA_CHUNK][4];
   ia_blob_interactions<TAB, true>(s, pos, cnt, list, cap, N_blb, tiles, p, PT, HT, f, e, npairs, C);
+}
+
+// ... with a cell per replica: the tile's body i = blockIdx.x / tiles lies in window i / win
+template <int TAB>
+__global__ __launch_bounds__(IA_BT) void k_blob_interactions_cells(const double *__restrict__ pos, const int *__restrict__ cnt,
+                                                                   const int *__restrict__ list, int cap, int N_blb, int tiles, int win,
+                                                                   IaParams p, IaTab PT, IaTab HT, const RblEnsCellRec *__restrict__ cells,
+                                                                   double *__restrict__ f, double *__restrict__ e,
+                                                                   int *__restrict__ npairs)
+{
+  static_assert(TAB >= 0 && TAB <= 3, "bit 0: pair table, bit 1: height table");
+  __shared__ double s[IA_CHUNK][4];
+  ia_blob_interactions<TAB, true>(s, pos, cnt, list, cap, N_blb, tiles, p, PT, HT, f, e, npairs, ia_cell_of(cells, blockIdx.x / tiles / win));
 }
 
 // harmonic traps on the body centres: FT[6 i + c] -= k_c (X_c - X0_c), the energy added to the entry of the body's first blob
@@ -523,15 +559,14 @@ __global__ __launch_bounds__(256) void k_bond_state(const double *__restrict__ X
   out[2 * tot + g] = U;
 }
 
-// the same with the pair displacement by minimum image (a periodic cell): its own kernel for the reason given at
-// k_body_neighbours_per
+// the same with the pair displacement by minimum image (a periodic cell): its own body for the reason given at
+// ia_body_neighbours_per, shared by the kernel that takes the cell by value and the one that reads it from a table
 template <int NT>
-__global__ __launch_bounds__(NT) void k_body_dipoles_per(const double *__restrict__ X, const double *__restrict__ Q,
-                                                     const double *__restrict__ mb, const double *__restrict__ tf,
-                                                     const int *__restrict__ accepted, int win, int N_blb, IaMag M, IaCell C,
-                                                     double *__restrict__ FT, double *__restrict__ e)
+__device__ __forceinline__ void ia_body_dipoles_per(double (*red)[NT], const double *__restrict__ X, const double *__restrict__ Q,
+                                                    const double *__restrict__ mb, const double *__restrict__ tf,
+                                                    const int *__restrict__ accepted, int win, int N_blb, const IaMag &M, const IaCell &C,
+                                                    double *__restrict__ FT, double *__restrict__ e)
 {
-  __shared__ double red[7][NT];
   const int i = blockIdx.x, t = threadIdx.x;
   const int jb = i - i % win;
   double mi[3];
@@ -582,6 +617,28 @@ __global__ __launch_bounds__(NT) void k_body_dipoles_per(const double *__restric
     for (int c = 0; c < 6; ++c) FT[6 * (size_t)i + c] += acc[c];
   }
   if (e) e[(size_t)i * N_blb] += E;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_body_dipoles_per(const double *__restrict__ X, const double *__restrict__ Q,
+                                                     const double *__restrict__ mb, const double *__restrict__ tf,
+                                                     const int *__restrict__ accepted, int win, int N_blb, IaMag M, IaCell C,
+                                                     double *__restrict__ FT, double *__restrict__ e)
+{
+  __shared__ double red[7][NT];
+  ia_body_dipoles_per<NT>(red, X, Q, mb, tf, accepted, win, N_blb, M, C, FT, e);
+}
+
+// ... and in the cell of the body's window, one per replica
+template <int NT>
+__global__ __launch_bounds__(NT) void k_body_dipoles_cells(const double *__restrict__ X, const double *__restrict__ Q,
+                                                           const double *__restrict__ mb, const double *__restrict__ tf,
+                                                           const int *__restrict__ accepted, int win, int N_blb, IaMag M,
+                                                           const RblEnsCellRec *__restrict__ cells, double *__restrict__ FT,
+                                                           double *__restrict__ e)
+{
+  __shared__ double red[7][NT];
+  ia_body_dipoles_per<NT>(red, X, Q, mb, tf, accepted, win, N_blb, M, ia_cell_of(cells, blockIdx.x / win), FT, e);
 }
 
 struct IaLayout {
@@ -769,9 +826,15 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   // a periodic cell (include/rbl.h section 10): minimum image in the neighbour search, the blob pair terms and the dipole pairs.
   // The convention is unique only while no pair inside a cutoff has a second image inside it: blobs of two bodies lie within
   // 2 R_body + r_cut of each other's centres, dipoles sit on the centres themselves
+  // An ensemble with a cell per replica (rbl_ensemble_set_cells): the bounds replica by replica, the first offending one named, and
+  // the kernels read the cell of a body's window from the table
   IaCell C = {};
   const bool per = ens ? c->ens_per_on : periodic_on(c);
-  const double *per_L = ens ? c->ens_per_L : c->per_L;
+  const bool tab_cells = ens && per && ens_cells_stored(c);
+  const int n_cells = tab_cells ? (int)(c->ens_cells_L.size() / 2) : 1;
+  if (tab_cells && n_cells != n_win)
+    return rbl_fail(c, RBL_ERR_STATE, "interactions: the cells are stored for " + std::to_string(n_cells) + " replicas, the evaluation has " +
+                                          std::to_string(n_win) + " (rbl_ensemble_set_cells)");
   if (per) {
     double R2b = 0.0;
     for (int k = 0; k < S.N_blb; ++k) {
@@ -781,21 +844,29 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
     const double rc_pair = std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0);
     const double need_pair = (c->ia_on || c->ia_pt.on) ? 2.0 * std::sqrt(R2b) + rc_pair : 0.0;
     const double need_dp = dp_pairs ? c->ia_dp_rcut : 0.0;
-    for (int k = 0; k < 2; ++k) {
-      const double Lk = per_L[k];
-      if (!(Lk > 0.0)) continue;
-      const std::string Ln = std::string("L") + (k ? "y" : "x") + " = " + std::to_string(Lk);
-      if (need_pair > 0.5 * Lk)
-        return rbl_fail(c, RBL_ERR_ARG, "interactions: periodic cell too small: " + Ln + " needs 2 R_body + r_cut = " + std::to_string(need_pair) +
-                                            " <= L / 2 = " + std::to_string(0.5 * Lk) + " for a unique minimum image");
-      if (need_dp > 0.5 * Lk)
-        return rbl_fail(c, RBL_ERR_ARG, "interactions: periodic cell too small: " + Ln + " needs the dipole r_cut = " + std::to_string(need_dp) +
-                                            " <= L / 2 = " + std::to_string(0.5 * Lk) + " for a unique minimum image");
+    for (int r = 0; r < n_cells; ++r) {
+      const double *per_L = tab_cells ? &c->ens_cells_L[2 * (size_t)r] : ens ? c->ens_per_L : c->per_L;
+      for (int k = 0; k < 2; ++k) {
+        const double Lk = per_L[k];
+        if (!(Lk > 0.0) || (need_pair <= 0.5 * Lk && need_dp <= 0.5 * Lk)) continue;     // (a run checks R cells per step: no strings here)
+        const std::string head = tab_cells ? "interactions: replica " + std::to_string(r) + ": periodic cell too small: "
+                                           : std::string("interactions: periodic cell too small: ");
+        const std::string Ln = std::string("L") + (k ? "y" : "x") + " = " + std::to_string(Lk);
+        if (need_pair > 0.5 * Lk)
+          return rbl_fail(c, RBL_ERR_ARG, head + Ln + " needs 2 R_body + r_cut = " + std::to_string(need_pair) +
+                                              " <= L / 2 = " + std::to_string(0.5 * Lk) + " for a unique minimum image");
+        if (need_dp > 0.5 * Lk)
+          return rbl_fail(c, RBL_ERR_ARG, head + Ln + " needs the dipole r_cut = " + std::to_string(need_dp) +
+                                              " <= L / 2 = " + std::to_string(0.5 * Lk) + " for a unique minimum image");
+      }
+      if (tab_cells) continue;
+      C.Lx = per_L[0]; C.Ly = per_L[1];
+      C.px = C.Lx > 0.0 ? 1 : 0; C.py = C.Ly > 0.0 ? 1 : 0;
+      C.iLx = C.px ? 1.0 / C.Lx : 0.0; C.iLy = C.py ? 1.0 / C.Ly : 0.0;
     }
-    C.Lx = per_L[0]; C.Ly = per_L[1];
-    C.px = C.Lx > 0.0 ? 1 : 0; C.py = C.Ly > 0.0 ? 1 : 0;
-    C.iLx = C.px ? 1.0 / C.Lx : 0.0; C.iLy = C.py ? 1.0 / C.Ly : 0.0;
   }
+  if (tab_cells && (rc = ens_cells_upload(c))) return rc;   // (current already unless the parameters changed since the cells were set)
+  const RblEnsCellRec *cells = tab_cells ? (const RblEnsCellRec *)c->d_ens_cells.p : nullptr;
   if ((rc = ia_upload(c))) return rc;
   if (dp && (rc = ia_mag_upload(c))) return rc;
   if (bonds && (rc = ia_bond_upload(c))) return rc;
@@ -810,7 +881,10 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   // distances: it can only add candidates, whose pairs beyond the cutoffs are then skipped one by one
   const double rc_max = std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0);
   const double cut = (2.0 * std::sqrt(R2) + rc_max) * (1.0 + 1e-12) + 1e-12;
-  if (per)
+  if (cells)
+    hipLaunchKernelGGL(k_body_neighbours_cells, dim3(nbod), dim3(64), 0, c->stream, d_X, nbod, win, cut * cut, c->ia_cull ? 1 : 0, cap,
+                       cells, L.cnt, L.list, d_err);
+  else if (per)
     hipLaunchKernelGGL(k_body_neighbours_per, dim3(nbod), dim3(64), 0, c->stream, d_X, nbod, win, cut * cut, c->ia_cull ? 1 : 0, cap,
                        C, L.cnt, L.list, d_err);
   else
@@ -831,7 +905,15 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
 #define RBL_IA_PER(K)                                                                                                              \
   hipLaunchKernelGGL(k_blob_interactions_per<K>, grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt, (const int *)L.list, cap, \
                      S.N_blb, tiles, P, PT, HT, C, d_f, d_e, L.np)
-  if (per) {
+#define RBL_IA_CELLS(K)                                                                                                              \
+  hipLaunchKernelGGL(k_blob_interactions_cells<K>, grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt, (const int *)L.list, cap, \
+                     S.N_blb, tiles, win, P, PT, HT, cells, d_f, d_e, L.np)
+  if (cells) {
+    if (tab == 0) RBL_IA_CELLS(0);
+    else if (tab == 1) RBL_IA_CELLS(1);
+    else if (tab == 2) RBL_IA_CELLS(2);
+    else RBL_IA_CELLS(3);
+  } else if (per) {
     if (tab == 0) RBL_IA_PER(0);
     else if (tab == 1) RBL_IA_PER(1);
     else if (tab == 2) RBL_IA_PER(2);
@@ -844,6 +926,7 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   else RBL_IA_TAB(3);
 #undef RBL_IA_TAB
 #undef RBL_IA_PER
+#undef RBL_IA_CELLS
   if (d_FT) rbl_launch_KT_x_Lam(c->stream, d_lever, d_f, S.N_blb, nbod, d_FT);
   if (c->ia_tr_on && (d_FT || d_e)) {
     const double *k3 = T + c->ia_pt.coef.size() + c->ia_ht.coef.size() + c->ia_bt.coef.size();
@@ -863,6 +946,12 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
     else if (!per)
       hipLaunchKernelGGL(k_body_dipoles<64>, dim3((unsigned)nbod), dim3(64), 0, c->stream, d_X, d_Q, mb, tf, d_accepted, win,
                          S.N_blb, M, d_FT, d_e);
+    else if (cells && win > 512)
+      hipLaunchKernelGGL(k_body_dipoles_cells<256>, dim3((unsigned)nbod), dim3(256), 0, c->stream, d_X, d_Q, mb, tf, d_accepted, win,
+                         S.N_blb, M, cells, d_FT, d_e);
+    else if (cells)
+      hipLaunchKernelGGL(k_body_dipoles_cells<64>, dim3((unsigned)nbod), dim3(64), 0, c->stream, d_X, d_Q, mb, tf, d_accepted, win,
+                         S.N_blb, M, cells, d_FT, d_e);
     else if (win > 512)
       hipLaunchKernelGGL(k_body_dipoles_per<256>, dim3((unsigned)nbod), dim3(256), 0, c->stream, d_X, d_Q, mb, tf, d_accepted, win,
                          S.N_blb, M, C, d_FT, d_e);

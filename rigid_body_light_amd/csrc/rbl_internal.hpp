@@ -302,6 +302,14 @@ struct rbl_ctx {
   bool ens_per_on = false;
   double ens_per_L[2] = {0.0, 0.0};
   int ens_per_n[2] = {0, 0};
+  // ... or a cell per replica (rbl_ensemble_set_cells): (Lx, Ly) and (nx, ny) of replica r at 2 r, ens_R entries; empty: the cell is
+  // the shared one above.  ens_per_on switches either kind.  d_ens_cells: the R records the kernels read (RblEnsCellRec), scaled
+  // with the blob radius ens_cells_a; uploaded when the cells are set and again at use when a has changed since (ens_cells_valid)
+  std::vector<double> ens_cells_L;
+  std::vector<int> ens_cells_n;
+  RblDevBuf d_ens_cells;
+  double ens_cells_a = 0.0;
+  bool ens_cells_valid = false;
   // lanczos
   int lanczos_max_iter = 100;
   bool lanczos_out_norm = true;  // preconditioned root: final stopping test in the Euclidean norm of the increment (RBL_OPT_LANCZOS_EUCLID_NORM)
@@ -470,6 +478,21 @@ inline RblSmallCell rbl_small_cell(double a, const double *L, const int *n)
   C.nx = L[0] > 0.0 ? n[0] : 0; C.ny = L[1] > 0.0 ? n[1] : 0;
   return C;
 }
+// One replica's cell in the table of an ensemble with a cell per replica (rbl_ensemble_set_cells), in every form a kernel takes:
+// the one-workgroup kernels' and the probes' radius-scaled S (its nx, ny serve the dense build too), and the physical lengths and
+// reciprocals of the dense build and the forces (0 on an open axis).  The kernels only read the table, at a workgroup-uniform index
+struct RblEnsCellRec {
+  RblSmallCell S;
+  double Lx, Ly, iLx, iLy;
+};
+inline RblEnsCellRec rbl_ens_cell_rec(double a, const double *L, const int *n)
+{
+  RblEnsCellRec C;
+  C.S = rbl_small_cell(a, L, n);
+  C.Lx = L[0]; C.Ly = L[1];
+  C.iLx = L[0] > 0.0 ? 1.0 / L[0] : 0.0; C.iLy = L[1] > 0.0 ? 1.0 / L[1] : 0.0;
+  return C;
+}
 // the same solve for `reps` replicas of one system shape, one workgroup each (rbl_ensemble.hip): X, Q replica-major (3 N_bod,
 // 4 N_bod per replica), rhs / x nsys per replica, work reps x rbl_gmres_small_work_doubles, one iteration count, residual and
 // error word per replica; diagonal preconditioner with the force block's sign restored (fsign = +1), cold start.  What every
@@ -494,6 +517,9 @@ int rbl_launch_gmres_small_ens(hipStream_t st, const RblParams &P, bool wall, co
 // the same in a periodic cell (rbl_small_per.hip: k_gmres_small_per; wall only): the operator sums every pair over the cell's images
 int rbl_launch_gmres_small_ens_per(hipStream_t st, const RblParams &P, const RblSmallCell &C, const RblSmallEns &S,
                                    const unsigned char *d_mask = nullptr, const double *d_body_in = nullptr, int per = 1);
+// ... and with a cell per replica (rbl_small_cells.hip: k_gmres_small_cells): replica r sums over the images of d_cells[r]
+int rbl_launch_gmres_small_ens_cells(hipStream_t st, const RblParams &P, const RblEnsCellRec *d_cells, const RblSmallEns &S,
+                                     const unsigned char *d_mask = nullptr, const double *d_body_in = nullptr, int per = 1);
 // the jointed solve of the replicas (rbl_small_joints.hip; include/rbl.h sections 5 and 9).  The joint table on the device, shared
 // by the replicas: anchor 6, ang 7 (axis | q_rel) per joint; theta, rate: n per REPLICA; body 2, mate 2, kind 1 per joint; ptr: the
 // row starts of the joint ends by body (N_bod + 1); ends: (joint, end) per entry, n_ends of them
@@ -564,6 +590,9 @@ void rbl_launch_build_M_batched(hipStream_t st, const RblParams &P, bool wall, b
 // block.  Lx, Ly in physical units (0: that axis is open, its n is 0)
 void rbl_launch_build_M_per_batched(hipStream_t st, const RblParams &P, bool scale_damp, const double *d_r, int64_t n_blobs, int batch,
                                     double *d_M, int64_t strideM, unsigned *d_err, int err_stride, double Lx, double Ly, int nx, int ny);
+// ... and with a cell per matrix (k_build_M_cells): matrix b in the cell d_cells[b]
+void rbl_launch_build_M_cells_batched(hipStream_t st, const RblParams &P, bool scale_damp, const double *d_r, int64_t n_blobs, int batch,
+                                      double *d_M, int64_t strideM, unsigned *d_err, int err_stride, const RblEnsCellRec *d_cells);
 
 // ---- ONE wave-wide sum of doubles, in ONE order --------------------------------------------------------------------------------
 // The bitwise-equal-everywhere claims of the fused reductions (RblNormFold: every wave of every workgroup must get the SAME |w| from

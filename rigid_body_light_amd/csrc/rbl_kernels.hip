@@ -1433,14 +1433,10 @@ struct PerCellPhys {
   int nx, ny;
 };
 
-__global__ __launch_bounds__(256) void k_build_M_per(const double *__restrict__ r, double *__restrict__ M, long N, int scale_damp,
-                                                     RblParams P, PerCellPhys C, unsigned *err, long strideR, long strideM,
-                                                     int err_stride)
+// one matrix of the batch (r, M, err its own) in the cell C: the body of k_build_M_per and k_build_M_cells
+__device__ __forceinline__ void build_M_per_one(const double *__restrict__ r, double *__restrict__ M, long N, int scale_damp,
+                                                const RblParams &P, const PerCellPhys &C, unsigned *err, double (*col)[768])
 {
-  r += (size_t)blockIdx.z * (size_t)strideR;
-  M += (size_t)blockIdx.z * (size_t)strideM;
-  err += (size_t)blockIdx.z * (size_t)err_stride;
-  __shared__ double col[3][768];
   const int t = threadIdx.x;
   const long i0 = (long)blockIdx.x * 256;
   const long i = i0 + t;
@@ -1501,6 +1497,29 @@ __global__ __launch_bounds__(256) void k_build_M_per(const double *__restrict__ 
   }
   if (!valid) flags &= ~RBL_FLAG_OVERLAP;
   if (flags) atomicOr(err, flags);
+}
+
+__global__ __launch_bounds__(256) void k_build_M_per(const double *__restrict__ r, double *__restrict__ M, long N, int scale_damp,
+                                                     RblParams P, PerCellPhys C, unsigned *err, long strideR, long strideM,
+                                                     int err_stride)
+{
+  __shared__ double col[3][768];
+  build_M_per_one(r + (size_t)blockIdx.z * (size_t)strideR, M + (size_t)blockIdx.z * (size_t)strideM, N, scale_damp, P, C,
+                  err + (size_t)blockIdx.z * (size_t)err_stride, col);
+}
+
+// a cell per matrix (an ensemble with a cell per replica, rbl_ensemble_set_cells): matrix blockIdx.z in the cell of record
+// blockIdx.z, read first -- a workgroup-uniform index into a table that is only read, so the cell sits in scalar registers as the
+// by-value one does.  The sum is k_build_M_per's with that cell, term for term
+__global__ __launch_bounds__(256) void k_build_M_cells(const double *__restrict__ r, double *__restrict__ M, long N, int scale_damp,
+                                                       RblParams P, const RblEnsCellRec *__restrict__ cells, unsigned *err, long strideR,
+                                                       long strideM, int err_stride)
+{
+  __shared__ double col[3][768];
+  const RblEnsCellRec &R = cells[blockIdx.z];
+  const PerCellPhys C = {R.Lx, R.Ly, R.S.nx, R.S.ny};
+  build_M_per_one(r + (size_t)blockIdx.z * (size_t)strideR, M + (size_t)blockIdx.z * (size_t)strideM, N, scale_damp, P, C,
+                  err + (size_t)blockIdx.z * (size_t)err_stride, col);
 }
 
 // ---------------------------------------------------------------------------
@@ -2486,6 +2505,15 @@ void rbl_launch_build_M_per_batched(hipStream_t st, const RblParams &P, bool sca
   const PerCellPhys C = {Lx, Ly, Lx > 0.0 ? nx : 0, Ly > 0.0 ? ny : 0};
   hipLaunchKernelGGL(k_build_M_per, grid, block, 0, st, d_r, d_M, (long)n_blobs, scale_damp ? 1 : 0, P, C, d_err, (long)(3 * n_blobs),
                      (long)strideM, err_stride);
+}
+
+void rbl_launch_build_M_cells_batched(hipStream_t st, const RblParams &P, bool scale_damp, const double *d_r, int64_t n_blobs, int batch,
+                                      double *d_M, int64_t strideM, unsigned *d_err, int err_stride, const RblEnsCellRec *d_cells)
+{
+  if (n_blobs <= 0 || batch <= 0) return;
+  dim3 grid((unsigned)((n_blobs + 255) / 256), (unsigned)((n_blobs + JB - 1) / JB), (unsigned)batch), block(256);
+  hipLaunchKernelGGL(k_build_M_cells, grid, block, 0, st, d_r, d_M, (long)n_blobs, scale_damp ? 1 : 0, P, d_cells, d_err,
+                     (long)(3 * n_blobs), (long)strideM, err_stride);
 }
 
 void rbl_launch_pair_blocks(hipStream_t st, const RblParams &P, bool wall, int mode,

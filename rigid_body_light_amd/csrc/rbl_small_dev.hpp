@@ -40,7 +40,9 @@ __device__ __forceinline__ void rbl_quat_rot9(const double *q, double *R)
 // evenly over the waves and nothing but the step's three scalars is live across the pair call; the reduction is redone per step.
 // A blob's own images (p, q) != (0, 0) are ordinary pairs of two different blobs at one height: the steps behind the pairs',
 // offset 0, take the half set k > k(0, 0) -- (p, q) and (-p, -q) are each other's transpose, so ui + uj of one evaluation is both.
-// The step index comes through readfirstlane: the decoding below is scalar arithmetic.  C arrives as a kernel argument (SGPRs).
+// The step index comes through readfirstlane: the decoding below is scalar arithmetic.  C arrives as a kernel argument or, with a
+// cell per replica, from the workgroup's record of a table that is only read (rbl_small_cells.hip): scalar registers either way,
+// and W, kc, NI, npair, nall are then the workgroup's own -- a replica with more images runs more steps.
 template <bool WALL, bool PER = false>
 __device__ __forceinline__ void rbl_small_pair_sweep(const RblParams &Pu, const double *pos, const double *dmp, const double *in,
                                                      int N, double *part, unsigned &flags, const RblSmallCell &C = RblSmallCell{})

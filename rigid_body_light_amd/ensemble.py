@@ -13,7 +13,7 @@ vectors within 150 KB of LDS, about 75 N_blobs + 60 N_bod doubles: 49 tetrahedra
 """
 import numpy as np
 
-from ._lib import (JOINT_BALL, RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError, blob_anchor, bond_args, check_brownian_mask6,
+from ._lib import (JOINT_BALL, RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError, blob_anchor, bond_args, cells_args, check_brownian_mask6,
                    default_q_rel, hinge, joint_kind_args, motor, periodic_args, weld)
 
 
@@ -704,8 +704,36 @@ class Ensemble:
         self.ctx.ensemble_set_periodic(Lx, Ly, images=(nx, ny), on=bool(on))
 
     def cell(self):
-        """-> {Lx, Ly, images, on} of the ensemble's cell"""
-        return self.ctx.ensemble_periodic()
+        """-> {Lx, Ly, images, on} of the ensemble's cell; raises while a cell per replica is stored (see cells)"""
+        try:
+            return self.ctx.ensemble_periodic()
+        except RblError as e:
+            if self.ctx.ensemble_cells()["per_replica"]:
+                raise RblError("cell: the ensemble holds a cell per replica, there is no one cell to report: use cells() (%s)" % e) from None
+            raise
+
+    def set_cells(self, Lx, Ly, images=(1, 1), on=True):
+        """A periodic cell PER REPLICA -- an area-fraction sweep, or a convergence study in the image count, in one call.  Lx, Ly:
+        real scalars or (R,); images: (nx, ny) or (R, 2); scalars broadcast.  Replica r is what an R = 1 ensemble gives after
+        set_cell(Lx[r], Ly[r], images[r]), bit for bit; a replica may keep an axis open (L = 0) while another has it periodic.  A
+        replica with more images runs more steps of the pair sweep, and a launch lasts as long as its slowest replica.  Replaces
+        the shared cell of set_cell, as set_cell replaces this.  The cells belong to this R."""
+        Lx, Ly, n = cells_args("set_cells", Lx, Ly, images, self.R)
+        self.ctx.ensemble_set_cells(Lx, Ly, images=n, on=bool(on))
+
+    def cells(self):
+        """-> {on, per_replica, Lx (R,), Ly (R,), images (R, 2)}: the cell of every replica (a shared cell: R equal rows)"""
+        return self.ctx.ensemble_cells()
+
+    def area_fraction(self, body_area):
+        """(R,) N_bod body_area / (Lx Ly) of every replica, the label of an area-fraction sweep (body_area: the area one body
+        covers, e.g. pi R_h^2); nan for a replica that is not periodic in both axes.  No device work"""
+        c = self.cells()
+        A = c["Lx"] * c["Ly"]
+        out = np.full(self.R, np.nan)
+        ok = (c["Lx"] > 0.0) & (c["Ly"] > 0.0)
+        out[ok] = self.N_bodies * float(body_area) / A[ok]
+        return out
 
     def set_bond_table(self, U, dU, r_min, r_cut, on=True):
         """the potential of the kind-1 bonds of RigidBody.set_bond_table, one for all replicas"""
