@@ -94,7 +94,7 @@ __global__ __launch_bounds__(64 * EP_WAVES_MAX) void k_ens_probe(RblParams P, Rb
   }
   // targets: the lane's NI points, lab points or offsets fixed in a body
   const RblParams Pu = rbl_small_unit_params(P);
-  const RblWallK WK = rbl_wall_k_resident();
+  const RblWallK WK = rbl_wall_k_resident<RBL_UNIT_RADIUS>();
   const long q0 = (long)blockIdx.x * ((long)nt * NI);
   const double *pts = A.pts + (size_t)r * (size_t)A.pts_stride;
   double Rb[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
@@ -127,15 +127,15 @@ __global__ __launch_bounds__(64 * EP_WAVES_MAX) void k_ens_probe(RblParams P, Rb
           for (int q = -C.ny; q <= C.ny; ++q) {
             const double y = __builtin_fma((double)q, C.Ly, dy);
             if (p == 0 && q == 0)   // wave-uniform
-              rbl_pair_accum<true, true, true>(Pu, x, y, zi[k], 0.0, 0.0, bz, fx, fy, fz, coinc, ux[k], uy[k], uz[k], flags, WK);
+              rbl_pair_accum<true, true, RBL_UNIT_RADIUS>(Pu, x, y, zi[k], 0.0, 0.0, bz, fx, fy, fz, coinc, ux[k], uy[k], uz[k], flags, WK);
             else
-              rbl_pair_accum<true, false, true>(Pu, x, y, zi[k], 0.0, 0.0, bz, fx, fy, fz, false, ux[k], uy[k], uz[k], flags, WK);
+              rbl_pair_accum<true, false, RBL_UNIT_RADIUS>(Pu, x, y, zi[k], 0.0, 0.0, bz, fx, fy, fz, false, ux[k], uy[k], uz[k], flags, WK);
           }
         }
       } else {
         const double dx = xi[k] - bx, dy = yi[k] - by, dz = zi[k] - bz;
         const bool coinc = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)) < Pu.tiny2;
-        rbl_pair_accum<WALL, true, true>(Pu, xi[k], yi[k], zi[k], bx, by, bz, fx, fy, fz, coinc, ux[k], uy[k], uz[k], flags, WK);
+        rbl_pair_accum<WALL, true, RBL_UNIT_RADIUS>(Pu, xi[k], yi[k], zi[k], bx, by, bz, fx, fy, fz, coinc, ux[k], uy[k], uz[k], flags, WK);
       }
     }
   }

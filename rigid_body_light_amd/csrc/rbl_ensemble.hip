@@ -307,7 +307,7 @@ __global__ __launch_bounds__(RBL_SG_THREADS) void k_ens_rfd_rhs(RblParams P, int
     if (t < N) {
       const double di = dmp[t];
       double ux = 0.0, uy = 0.0, uz = 0.0;
-      rbl_pair_accum<WALL, true, true>(Pu, pos[3 * t], pos[3 * t + 1], pos[3 * t + 2], pos[3 * t], pos[3 * t + 1], pos[3 * t + 2],
+      rbl_pair_accum<WALL, true, RBL_UNIT_RADIUS>(Pu, pos[3 * t], pos[3 * t + 1], pos[3 * t + 2], pos[3 * t], pos[3 * t + 1], pos[3 * t + 2],
                                        di * vin[3 * t], di * vin[3 * t + 1], di * vin[3 * t + 2], true, ux, uy, uz, flags);
       su[3 * t] = ux; su[3 * t + 1] = uy; su[3 * t + 2] = uz;
     }

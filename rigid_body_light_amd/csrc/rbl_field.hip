@@ -29,16 +29,12 @@ namespace {
 constexpr int VF_TS = 64;   // source tile = wave width
 
 struct __attribute__((aligned(16))) VfBlob {
-  double x, y, z, fx, fy, fz;   // radius-scaled position, damped force: three 16-B LDS broadcasts per source
+  double x, y, z, fx, fy, fz;   // unit-scaled position, damped force: three 16-B LDS broadcasts per source
 };
 
-// (restated from rbl_kernels.hip, where they are file-local)
-__device__ __forceinline__ RblParams vf_unit_params(const RblParams &P)
-{
-  RblParams Pu = P;
-  Pu.a = 1.0; Pu.inv_a = 1.0; Pu.four_a2 = 4.0; Pu.tiny2 = 1e-24; Pu.c_near_A = -0.375; Pu.c_near_B = 0.125;
-  return Pu;
-}
+// the pair arithmetic runs in the length unit rbl_unit_of(WALL) of rbl_pair.hpp, as in rbl_kernels.hip: positions times
+// rbl_unit_pos_scale where they are packed or loaded, rbl_unit_params, sums times rbl_unit_out_scale
+// (restated from rbl_kernels.hip, where it is file-local)
 
 __device__ __forceinline__ double vf_damp_of(const RblParams &P, double z)
 {
@@ -65,7 +61,7 @@ __device__ __forceinline__ double vf_uniform(double v)   // a value all lanes ho
   return __hiloint2double(hi, lo);
 }
 
-// one thread per (padded) source; a wave = one source tile, whose bounding box of the real sources (radius-scaled) goes to
+// one thread per (padded) source; a wave = one source tile, whose bounding box of the real sources (unit-scaled) goes to
 // box[tile][6] = (min x, y, z, max x, y, z) -- the sweep's test whether a point of a unit may coincide with a source of the tile
 template <bool WALL>
 __global__ __launch_bounds__(256) void k_vf_pack(const double *__restrict__ r, const double *__restrict__ lam, long N, long Npad,
@@ -82,7 +78,8 @@ __global__ __launch_bounds__(256) void k_vf_pack(const double *__restrict__ r, c
       if (z < 0.0) atomicOr(err, (unsigned)RBL_FLAG_BELOW_WALL);
       d = vf_damp_of(P, z);
     }
-    b.x = r[3 * j] * P.inv_a; b.y = r[3 * j + 1] * P.inv_a; b.z = z * P.inv_a;
+    const double ps = rbl_unit_pos_scale<rbl_unit_of(WALL)>(P);
+    b.x = r[3 * j] * ps; b.y = r[3 * j + 1] * ps; b.z = z * ps;
     b.fx = d * lam[3 * j]; b.fy = d * lam[3 * j + 1]; b.fz = d * lam[3 * j + 2];
     lo[0] = hi[0] = b.x; lo[1] = hi[1] = b.y; lo[2] = hi[2] = b.z;
   } else {   // padding: zero force, far away, above the wall; not part of the box
@@ -116,7 +113,7 @@ __device__ __forceinline__ void vf_sweep_tile(const RblParams &Pu, const VfBlob 
         const double dx = xi[k] - b.x, dy = yi[k] - b.y, dz = zi[k] - b.z;
         coinc = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)) < Pu.tiny2;
       }
-      rbl_pair_accum<WALL, COINC, true>(Pu, xi[k], yi[k], zi[k], b.x, b.y, b.z, b.fx, b.fy, b.fz, coinc, ux[k], uy[k], uz[k],
+      rbl_pair_accum<WALL, COINC, rbl_unit_of(WALL)>(Pu, xi[k], yi[k], zi[k], b.x, b.y, b.z, b.fx, b.fy, b.fz, coinc, ux[k], uy[k], uz[k],
                                         flags, K);
     }
   }
@@ -132,14 +129,16 @@ __global__ __launch_bounds__(VF_TS, NI == 4 ? 2 : (WALL ? 3 : 4)) void k_vf_swee
   __shared__ VfBlob sj[VF_TS];
   const int t = threadIdx.x;
   const long p0 = (long)blockIdx.x * (VF_TS * NI);
-  const RblParams Pu = vf_unit_params(P);
-  const RblWallK WK = rbl_wall_k_resident();
+  constexpr int kUnit = rbl_unit_of(WALL);
+  const RblParams Pu = rbl_unit_params<kUnit>(P);
+  const RblWallK WK = rbl_wall_k_resident<kUnit>();
+  const double ps = rbl_unit_pos_scale<kUnit>(P);
   double xi[NI], yi[NI], zi[NI], ux[NI], uy[NI], uz[NI];
 #pragma unroll
   for (int k = 0; k < NI; ++k) {
     long p = p0 + t + (long)k * VF_TS;
     if (p >= Pl) p = Pl - 1;          // masked lane: a copy of the last point, never written
-    xi[k] = pts[3 * p] * P.inv_a; yi[k] = pts[3 * p + 1] * P.inv_a; zi[k] = pts[3 * p + 2] * P.inv_a;
+    xi[k] = pts[3 * p] * ps; yi[k] = pts[3 * p + 1] * ps; zi[k] = pts[3 * p + 2] * ps;
     ux[k] = 0.0; uy[k] = 0.0; uz[k] = 0.0;
   }
   // the unit's box (all lanes agree on it: wave-uniform branch per tile below)
@@ -169,7 +168,7 @@ __global__ __launch_bounds__(VF_TS, NI == 4 ? 2 : (WALL ? 3 : 4)) void k_vf_swee
       n0 = sp[0]; n1 = sp[1]; n2 = sp[2]; n3 = sp[3]; n4 = sp[4]; n5 = sp[5];
     }
     const double *tb = box + (long)tile * 6;
-    constexpr double eps = 1e-11;     // (radius-scaled; 10 x the coincidence distance)
+    constexpr double eps = 1e-11 * rbl_unit_l(kUnit);     // (unit-scaled; 10 x the coincidence distance)
     const bool coinc = tb[0] <= bhi[0] + eps && blo[0] <= tb[3] + eps && tb[1] <= bhi[1] + eps && blo[1] <= tb[4] + eps &&
                        tb[2] <= bhi[2] + eps && blo[2] <= tb[5] + eps;
     if (__builtin_amdgcn_readfirstlane((int)coinc))
@@ -183,7 +182,7 @@ __global__ __launch_bounds__(VF_TS, NI == 4 ? 2 : (WALL ? 3 : 4)) void k_vf_swee
     if (p >= Pl) continue;
     if (nch == 1) {
       const double zp = pts[3 * p + 2];   // (the physical height, as apply_M damps with)
-      double sc = P.nf;
+      double sc = rbl_unit_out_scale<kUnit>(P);
       if (WALL) sc *= vf_damp_of(P, zp);
       double vx = sc * ux[k], vy = sc * uy[k], vz = sc * uz[k];
       if (WALL && !(zp > 0.0)) { vx = 0.0; vy = 0.0; vz = 0.0; }   // outside the fluid: u = 0 (d(0) = 0 already)
@@ -205,7 +204,7 @@ __global__ __launch_bounds__(256) void k_vf_reduce(const double *__restrict__ sl
   if (idx >= 3 * Pl) return;
   double s = 0.0;
   for (int k = 0; k < nch; ++k) s += slab[(size_t)k * (size_t)(3 * Pl) + idx];
-  double sc = P.nf;
+  double sc = rbl_unit_out_scale<rbl_unit_of(WALL)>(P);   // (the slabs hold sums of the sweep's unit)
   const double zp = pts[3 * (idx / 3) + 2];
   if (WALL) sc *= vf_damp_of(P, zp);
   double v = sc * s;

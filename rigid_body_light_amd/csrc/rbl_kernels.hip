@@ -39,14 +39,11 @@ struct __attribute__((aligned(16))) JBlob {
   double x, y, z, fx, fy, fz;  // 48 B: three 16-B LDS broadcasts per j
 };
 
-// parameter set of the radius-scaled coordinates (x/a): the mobility entries depend on r/a only, so the
-// matvec kernels scale positions once when they load them and run the pair arithmetic with a = 1
-__device__ __forceinline__ RblParams unit_params(const RblParams &P)
-{
-  RblParams Pu = P;
-  Pu.a = 1.0; Pu.inv_a = 1.0; Pu.four_a2 = 4.0; Pu.tiny2 = 1e-24; Pu.c_near_A = -0.375; Pu.c_near_B = 0.125;
-  return Pu;
-}
+// The mobility entries depend on r/a only, so the matvec kernels scale positions once when they load them and run the pair
+// arithmetic in a unit of their own (rbl_pair.hpp): wall kernels in the shared unit a / lambda (RBL_UNIT_SHARED), free-space kernels
+// in radii -- rbl_unit_of(WALL).  Positions times rbl_unit_pos_scale, the parameter set rbl_unit_params, sums times
+// rbl_unit_out_scale when they leave.  Everything that compares a height or a gap with the blob radius (damp_of, k_tile_bbox /
+// k_tile_far) keeps working in physical lengths or radii.
 
 __device__ __forceinline__ double damp_of(const RblParams &P, double z)
 {
@@ -65,10 +62,11 @@ __device__ __forceinline__ void sweep_tile(const RblParams &P, const JBlob *sj, 
                                            double yi, double zi, int self_jj, double &ux,
                                            double &uy, double &uz, unsigned &flags, const RblWallK &K)
 {
+  constexpr int kUnit = rbl_unit_of(WALL);
 #pragma unroll 4
   for (int jj = 0; jj < TB; ++jj) {
     const JBlob b = sj[jj];
-    rbl_pair_accum<WALL, SELF, true>(P, xi, yi, zi, b.x, b.y, b.z, b.fx, b.fy, b.fz,
+    rbl_pair_accum<WALL, SELF, kUnit>(P, xi, yi, zi, b.x, b.y, b.z, b.fx, b.fy, b.fz,
                                      SELF && (jj == self_jj), ux, uy, uz, flags, K);
   }
 }
@@ -88,9 +86,11 @@ __global__ __launch_bounds__(TB) void k_apply_M(const double *__restrict__ r,
   const bool valid = i < row_end;
   const long ic = valid ? i : row_end - 1;
   const double zi_phys = r[3 * ic + 2];
-  const double xi = r[3 * ic] * P.inv_a, yi = r[3 * ic + 1] * P.inv_a, zi = zi_phys * P.inv_a;   // radius-scaled
-  const RblParams Pu = unit_params(P);
-  const RblWallK WK = rbl_wall_k_resident();
+  constexpr int kUnit = rbl_unit_of(WALL);
+  const double ps = rbl_unit_pos_scale<kUnit>(P);
+  const double xi = r[3 * ic] * ps, yi = r[3 * ic + 1] * ps, zi = zi_phys * ps;   // unit-scaled
+  const RblParams Pu = rbl_unit_params<kUnit>(P);
+  const RblWallK WK = rbl_wall_k_resident<kUnit>();
   unsigned flags = 0;
   if (WALL && zi < 0.0) flags |= RBL_FLAG_BELOW_WALL;
 
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(TB) void k_apply_M(const double *__restrict__ r,
         if (b.z < 0.0) flags |= RBL_FLAG_BELOW_WALL;
         d = damp_of(P, b.z);
       }
-      b.x *= P.inv_a; b.y *= P.inv_a; b.z *= P.inv_a;
+      b.x *= ps; b.y *= ps; b.z *= ps;
       b.fx = d * F[3 * j]; b.fy = d * F[3 * j + 1]; b.fz = d * F[3 * j + 2];
     } else {  // padding: zero force, far away, above the wall
       b.x = 1.0e15; b.y = 1.0e15; b.z = 1.0; b.fx = 0.0; b.fy = 0.0; b.fz = 0.0;
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(TB) void k_apply_M(const double *__restrict__ r,
   if (valid) {
     const long o = 3 * (i - row_begin);
     if (jsplit == 1) {
-      const double sc = WALL ? P.nf * damp_of(P, zi_phys) : P.nf;
+      const double sc = WALL ? rbl_unit_out_scale<kUnit>(P) * damp_of(P, zi_phys) : rbl_unit_out_scale<kUnit>(P);
       out[o] = sc * ux; out[o + 1] = sc * uy; out[o + 2] = sc * uz;
       if (!(isfinite(ux) && isfinite(uy) && isfinite(uz))) flags |= RBL_FLAG_NONFINITE;
     } else {
@@ -155,7 +155,8 @@ __global__ __launch_bounds__(256) void k_reduce_parts(const double *__restrict__
   if (idx >= 3 * nrows) return;
   double s = 0.0;
   for (int k = 0; k < jsplit; ++k) s += part[(size_t)k * (size_t)(3 * nrows) + idx];
-  double sc = P.nf;
+  constexpr int kUnit = rbl_unit_of(WALL);
+  double sc = rbl_unit_out_scale<kUnit>(P);   // (the parts hold sums of the kernels' unit)
   if (WALL) sc *= damp_of(P, r[3 * (row_begin + idx / 3) + 2]);
   out[idx] = sc * s;
   if (!isfinite(s)) atomicOr(err, (unsigned)RBL_FLAG_NONFINITE);
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(256) void k_reduce_parts(const double *__restrict__
 // the cell by the reduction and land on somebody.  One summation order (j, then p, then q), no atomics on doubles.
 // ---------------------------------------------------------------------------
 struct PerCell {
-  double Lx, Ly, iLx, iLy;   // radius-scaled lengths and their reciprocals (0 on an open axis)
+  double Lx, Ly, iLx, iLy;   // unit-scaled lengths (rbl_unit_pos_scale) and their reciprocals (0 on an open axis)
   int nx, ny;
 };
 
@@ -181,6 +182,7 @@ __device__ __forceinline__ void sweep_tile_per(const RblParams &P, const JBlob *
                                                int self_jj, const PerCell &C, double &ux, double &uy, double &uz, unsigned &flags,
                                                const RblWallK &K)
 {
+  constexpr int kUnit = rbl_unit_of(true);
   for (int jj = 0; jj < njj; ++jj) {
     const JBlob b = sj[jj];
     double dx = xi - b.x, dy = yi - b.y;
@@ -191,9 +193,9 @@ __device__ __forceinline__ void sweep_tile_per(const RblParams &P, const JBlob *
       for (int q = -C.ny; q <= C.ny; ++q) {
         const double y = PY ? __builtin_fma((double)q, C.Ly, dy) : dy;
         if (SELF && p == 0 && q == 0)   // wave-uniform
-          rbl_pair_accum<true, true, true>(P, x, y, zi, 0.0, 0.0, b.z, b.fx, b.fy, b.fz, jj == self_jj, ux, uy, uz, flags, K);
+          rbl_pair_accum<true, true, kUnit>(P, x, y, zi, 0.0, 0.0, b.z, b.fx, b.fy, b.fz, jj == self_jj, ux, uy, uz, flags, K);
         else
-          rbl_pair_accum<true, false, true>(P, x, y, zi, 0.0, 0.0, b.z, b.fx, b.fy, b.fz, false, ux, uy, uz, flags, K);
+          rbl_pair_accum<true, false, kUnit>(P, x, y, zi, 0.0, 0.0, b.z, b.fx, b.fy, b.fz, false, ux, uy, uz, flags, K);
       }
     }
   }
@@ -211,9 +213,11 @@ __global__ __launch_bounds__(TB) void k_apply_M_per(const double *__restrict__ r
   const bool valid = i < row_end;
   const long ic = valid ? i : row_end - 1;
   const double zi_phys = r[3 * ic + 2];
-  const double xi = r[3 * ic] * P.inv_a, yi = r[3 * ic + 1] * P.inv_a, zi = zi_phys * P.inv_a;   // radius-scaled
-  const RblParams Pu = unit_params(P);
-  const RblWallK WK = rbl_wall_k_resident();
+  constexpr int kUnit = rbl_unit_of(true);
+  const double ps = rbl_unit_pos_scale<kUnit>(P);
+  const double xi = r[3 * ic] * ps, yi = r[3 * ic + 1] * ps, zi = zi_phys * ps;   // unit-scaled
+  const RblParams Pu = rbl_unit_params<kUnit>(P);
+  const RblWallK WK = rbl_wall_k_resident<kUnit>();
   unsigned flags = 0;
   if (zi < 0.0) flags |= RBL_FLAG_BELOW_WALL;
 
@@ -229,7 +233,7 @@ __global__ __launch_bounds__(TB) void k_apply_M_per(const double *__restrict__ r
       b.x = r[3 * j]; b.y = r[3 * j + 1]; b.z = r[3 * j + 2];
       if (b.z < 0.0) flags |= RBL_FLAG_BELOW_WALL;
       const double d = damp_of(P, b.z);
-      b.x *= P.inv_a; b.y *= P.inv_a; b.z *= P.inv_a;
+      b.x *= ps; b.y *= ps; b.z *= ps;
       b.fx = d * F[3 * j]; b.fy = d * F[3 * j + 1]; b.fz = d * F[3 * j + 2];
     }
     __syncthreads();  // previous tile fully consumed
@@ -248,7 +252,7 @@ __global__ __launch_bounds__(TB) void k_apply_M_per(const double *__restrict__ r
   if (valid) {
     const long o = 3 * (i - row_begin);
     if (jsplit == 1) {
-      const double sc = P.nf * damp_of(P, zi_phys);
+      const double sc = rbl_unit_out_scale<kUnit>(P) * damp_of(P, zi_phys);
       out[o] = sc * ux; out[o + 1] = sc * uy; out[o + 2] = sc * uz;
       if (!(isfinite(ux) && isfinite(uy) && isfinite(uz))) flags |= RBL_FLAG_NONFINITE;
     } else {
@@ -605,7 +609,7 @@ __global__ __launch_bounds__(256) void k_sym_unit_table(SymLayout L, SymSched S,
 }
 
 // ---- pieces both symmetric kernel families share (NV = 1 or 2 force vectors) ------------------------------------------------
-// blob idx as the pair arithmetic wants it: position divided by the blob radius, the NV forces damped (vector v of F at F + 3 N v)
+// blob idx as the pair arithmetic wants it: position in the kernel's length unit (rbl_unit_of(WALL)), the NV forces damped (vector v of F at F + 3 N v)
 template <bool WALL, int NV>
 __device__ __forceinline__ void sym_load_blob(const double *__restrict__ r, const double *__restrict__ F, long N, const RblParams &P,
                                               long idx, double &x, double &y, double &z, RblV3 (&f)[NV], unsigned &flags)
@@ -617,7 +621,9 @@ __device__ __forceinline__ void sym_load_blob(const double *__restrict__ r, cons
       if (z < 0.0) flags |= RBL_FLAG_BELOW_WALL;
       d = damp_of(P, z);
     }
-    x *= P.inv_a; y *= P.inv_a; z *= P.inv_a;
+    constexpr int kUnit = rbl_unit_of(WALL);
+    const double ps = rbl_unit_pos_scale<kUnit>(P);
+    x *= ps; y *= ps; z *= ps;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const double *Fv = F + (size_t)v * (size_t)(3 * N);
@@ -681,9 +687,10 @@ template <bool WALL, int NV>
 __device__ __forceinline__ void sym_diag_pair(const RblParams &Pu, double xi, double yi, double zi, const SymCol<NV> &cj, bool is_self,
                                               RblV3 (&ui)[NV], unsigned &flags)
 {
+  constexpr int kUnit = rbl_unit_of(WALL);
 #pragma unroll
   for (int v = 0; v < NV; ++v)
-    rbl_pair_accum<WALL, true, true>(Pu, xi, yi, zi, cj.x, cj.y, cj.z, cj.f[v].x, cj.f[v].y, cj.f[v].z, is_self, ui[v].x, ui[v].y, ui[v].z, flags);
+    rbl_pair_accum<WALL, true, kUnit>(Pu, xi, yi, zi, cj.x, cj.y, cj.z, cj.f[v].x, cj.f[v].y, cj.f[v].z, is_self, ui[v].x, ui[v].y, ui[v].z, flags);
 }
 
 // a lane's row sums of chunk c into the chunk's slab (row tiles at or beyond T are padding)
@@ -753,10 +760,13 @@ __global__ __launch_bounds__(TS *SW, sym_min_waves(WALL, NI, SW, PREC, NV)) void
   const int T = L.T;
   unsigned flags = 0;
   __shared__ double sO[3];                          // relaxed product: origin of the single-precision coordinates = first blob of the j tile
-  // All pair arithmetic of this kernel runs in coordinates divided by the blob radius (the mobility entries
-  // are functions of r/a only): Pu is the a = 1 parameter set, positions are scaled once when loaded.
-  const RblParams Pu = unit_params(P);
-  const RblWallK WK = rbl_wall_k_resident();
+  // All fp64 pair arithmetic of this kernel runs in the shared length unit (the mobility entries are functions of r/a only): Pu is
+  // that unit's parameter set, positions are scaled once when loaded.  The packed single-precision sweep works in radii (rbl_pair_pk.hpp):
+  // it takes its coordinates and forces times 1 / lambda where they are converted to float, once per tile, so that its sums are the
+  // shared unit's (M F / lambda; the product is linear in F).  Free space: radii throughout, the factor is 1.
+  constexpr int kUnit = rbl_unit_of(WALL);
+  const RblParams Pu = rbl_unit_params<kUnit>(P);
+  const RblWallK WK = rbl_wall_k_resident<kUnit>();
   // Per-NV differences of the sweeps, each one measured:
   constexpr int kSteps = NI > 2 ? 1 : RBL_SYM_UNROLL;   // far sweep, steps per trip (four rows: one, or the 239 VGPRs become 256 + spills)
   constexpr int kDiagSteps = NV == 1 ? 4 : 1;           // diagonal sweep.  Two vectors unrolled by 4: <false,1,1,0> goes from 99 to 171 VGPRs, 4 to 2 waves
@@ -783,9 +793,9 @@ __global__ __launch_bounds__(TS *SW, sym_min_waves(WALL, NI, SW, PREC, NV)) void
   if constexpr (PREC != 0) {
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-      Fi2[v][0] = (rbl_f2){(float)Fi[0][v].x, (float)Fi[NI - 1][v].x};
-      Fi2[v][1] = (rbl_f2){(float)Fi[0][v].y, (float)Fi[NI - 1][v].y};
-      Fi2[v][2] = (rbl_f2){(float)Fi[0][v].z, (float)Fi[NI - 1][v].z};
+      Fi2[v][0] = (rbl_f2){(float)(Fi[0][v].x * rbl_unit_inv_l(kUnit)), (float)(Fi[NI - 1][v].x * rbl_unit_inv_l(kUnit))};
+      Fi2[v][1] = (rbl_f2){(float)(Fi[0][v].y * rbl_unit_inv_l(kUnit)), (float)(Fi[NI - 1][v].y * rbl_unit_inv_l(kUnit))};
+      Fi2[v][2] = (rbl_f2){(float)(Fi[0][v].z * rbl_unit_inv_l(kUnit)), (float)(Fi[NI - 1][v].z * rbl_unit_inv_l(kUnit))};
     }
   }
   // column sums: the 3 NV contributions of this lane's rows to column jj
@@ -815,10 +825,11 @@ __global__ __launch_bounds__(TS *SW, sym_min_waves(WALL, NI, SW, PREC, NV)) void
         // coordinates relative to the tile's first blob: what single precision then rounds is a separation-sized number
         const double ox = sym_first_lane(xj), oy = sym_first_lane(yj), oz = sym_first_lane(zj);
         if (lane == 0) { sO[0] = ox; sO[1] = oy; sO[2] = oz; }
-        sPf[0][lane] = (float)(xj - ox); sPf[1][lane] = (float)(yj - oy); sPf[2][lane] = (float)(zj - oz);
+        constexpr double iL = rbl_unit_inv_l(kUnit);             // shared unit -> radii, forces times 1 / lambda (see Pu above)
+        sPf[0][lane] = (float)((xj - ox) * iL); sPf[1][lane] = (float)((yj - oy) * iL); sPf[2][lane] = (float)((zj - oz) * iL);
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
-          sPf[3 + 3 * v][lane] = (float)Fj[v].x; sPf[4 + 3 * v][lane] = (float)Fj[v].y; sPf[5 + 3 * v][lane] = (float)Fj[v].z;
+          sPf[3 + 3 * v][lane] = (float)(Fj[v].x * iL); sPf[4 + 3 * v][lane] = (float)(Fj[v].y * iL); sPf[5 + 3 * v][lane] = (float)(Fj[v].z * iL);
         }
       }
     }
@@ -833,9 +844,10 @@ __global__ __launch_bounds__(TS *SW, sym_min_waves(WALL, NI, SW, PREC, NV)) void
       if constexpr (PREC != 0) {                              // the coefficients once for all vectors
         const double ox = sO[0], oy = sO[1], oz = sO[2];
         const int a1 = NI - 1;
-        const rbl_f2 xi2 = {(float)(xi[0] - ox), (float)(xi[a1] - ox)}, yi2 = {(float)(yi[0] - oy), (float)(yi[a1] - oy)},
-                     zi2 = {(float)(zi[0] - oz), (float)(zi[a1] - oz)};
-        const float two_z0 = (float)(2.0 * oz);
+        constexpr double iL = rbl_unit_inv_l(kUnit);
+        const rbl_f2 xi2 = {(float)((xi[0] - ox) * iL), (float)((xi[a1] - ox) * iL)}, yi2 = {(float)((yi[0] - oy) * iL), (float)((yi[a1] - oy) * iL)},
+                     zi2 = {(float)((zi[0] - oz) * iL), (float)((zi[a1] - oz) * iL)};
+        const float two_z0 = (float)(2.0 * oz * iL);
         rbl_f2 acc[NV][3];
 #pragma unroll
         for (int v = 0; v < NV; ++v) { acc[v][0] = (rbl_f2){0, 0}; acc[v][1] = (rbl_f2){0, 0}; acc[v][2] = (rbl_f2){0, 0}; }
@@ -882,7 +894,7 @@ __global__ __launch_bounds__(TS *SW, sym_min_waves(WALL, NI, SW, PREC, NV)) void
           for (int v = 0; v < NV; ++v) vj[v] = RblV3{0.0, 0.0, 0.0};
 #pragma unroll
           for (int a = 0; a < NI; ++a)
-            rbl_pair_symv<WALL, true, decltype(nearchk)::value>(Pu, xi[a], yi[a], zi[a], Fi[a], cj.x, cj.y, cj.z, cj.f, ui[a], vj, flags, WK);
+            rbl_pair_symv<WALL, kUnit, decltype(nearchk)::value>(Pu, xi[a], yi[a], zi[a], Fi[a], cj.x, cj.y, cj.z, cj.f, ui[a], vj, flags, WK);
           col_add(jj, vj);
         }
       };
@@ -902,7 +914,7 @@ __global__ __launch_bounds__(TS *SW, sym_min_waves(WALL, NI, SW, PREC, NV)) void
             RblV3 vj[NV];
 #pragma unroll
             for (int v = 0; v < NV; ++v) vj[v] = RblV3{0.0, 0.0, 0.0};
-            rbl_pair_symv<WALL, true, true>(Pu, xi[a], yi[a], zi[a], Fi[a], cj.x, cj.y, cj.z, cj.f, ui[a], vj, flags, WK);
+            rbl_pair_symv<WALL, kUnit, true>(Pu, xi[a], yi[a], zi[a], Fi[a], cj.x, cj.y, cj.z, cj.f, ui[a], vj, flags, WK);
             col_add(jj, vj);
           }
         }
@@ -1051,8 +1063,9 @@ void k_apply_M_symw(const double *__restrict__ r, const double *__restrict__ F, 
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int C = L.C;
   unsigned flags = 0;
-  const RblParams Pu = unit_params(P);
-  const RblWallK WK = rbl_wall_k_resident();
+  constexpr int kUnit = rbl_unit_of(WALL);
+  const RblParams Pu = rbl_unit_params<kUnit>(P);
+  const RblWallK WK = rbl_wall_k_resident<kUnit>();
   // one work unit of this wave (`return` ends the unit)
   auto sweep_unit = [&](const long u) {
   int e, c;
@@ -1105,7 +1118,7 @@ void k_apply_M_symw(const double *__restrict__ r, const double *__restrict__ F, 
         for (int v = 0; v < NV; ++v) vj[v] = acc[v];
 #pragma unroll
         for (int a = 0; a < decltype(nrows)::value; ++a)
-          rbl_pair_symv<WALL, true, true>(Pu, xi[a], yi[a], zi[a], Fi[a], cj.x, cj.y, cj.z, cj.f, ui[a], vj, flags, WK);
+          rbl_pair_symv<WALL, kUnit, true>(Pu, xi[a], yi[a], zi[a], Fi[a], cj.x, cj.y, cj.z, cj.f, ui[a], vj, flags, WK);
 #pragma unroll
         for (int v = 0; v < NV; ++v) acc[v] = RblV3{wave_rol1(vj[v].x), wave_rol1(vj[v].y), wave_rol1(vj[v].z)};
       }
@@ -1189,7 +1202,8 @@ __global__ __launch_bounds__(64 * RG) void k_reduce_sym(const double *__restrict
     double t = sh[0][tx];
 #pragma unroll
     for (int w = 1; w < RG; ++w) t += sh[w][tx];
-    double sc = P.nf;
+    constexpr int kUnit = rbl_unit_of(WALL);
+    double sc = rbl_unit_out_scale<kUnit>(P);       // (the slabs hold sums of the kernels' unit)
     if (WALL) sc *= damp_of(P, r[3 * j + 2]);
     out[idx] = sc * t;
     if (!isfinite(t)) atomicOr(err, (unsigned)RBL_FLAG_NONFINITE);
@@ -1254,7 +1268,7 @@ __device__ __forceinline__ void mrhs_tile(const RblParams &P, const double *sx, 
     const double f0 = fp[0], f1 = fp[MR], f2 = fp[2 * MR];
     fp += (size_t)4 * 3 * MR;
     double m[9];
-    rbl_pair_block_fast<WALL, SELF, true>(P, xi, yi, zi, sx[jj], sy[jj], sz[jj], SELF && (j0 + jj == i), m, flags, K);
+    rbl_pair_block_fast<WALL, SELF, rbl_unit_of(WALL)>(P, xi, yi, zi, sx[jj], sy[jj], sz[jj], SELF && (j0 + jj == i), m, flags, K);
     dx_ = __builtin_amdgcn_mfma_f64_16x16x4f64(m[0], f0, dx_, 0, 0, 0);
     dx_ = __builtin_amdgcn_mfma_f64_16x16x4f64(m[1], f1, dx_, 0, 0, 0);
     dx_ = __builtin_amdgcn_mfma_f64_16x16x4f64(m[2], f2, dx_, 0, 0, 0);
@@ -1279,9 +1293,11 @@ __global__ __launch_bounds__(256) void k_apply_M_mrhs(const double *__restrict__
   const long i_blk0 = (long)blockIdx.x * 64;
   const long i = i_blk0 + wave * 16 + l15;
   const long ic = i < N ? i : N - 1;
-  const double xi = r[3 * ic] * P.inv_a, yi = r[3 * ic + 1] * P.inv_a, zi = r[3 * ic + 2] * P.inv_a;   // radius-scaled
-  const RblParams Pu = unit_params(P);
-  const RblWallK WK = rbl_wall_k_literal();   // (resident constants cost this kernel 1 %: register pressure)
+  constexpr int kUnit = rbl_unit_of(WALL);
+  const double ps = rbl_unit_pos_scale<kUnit>(P);
+  const double xi = r[3 * ic] * ps, yi = r[3 * ic + 1] * ps, zi = r[3 * ic + 2] * ps;   // unit-scaled
+  const RblParams Pu = rbl_unit_params<kUnit>(P);
+  const RblWallK WK = rbl_wall_k_literal<kUnit>();   // (resident constants cost this kernel 1 %: register pressure)
   unsigned flags = 0;
   const long j_begin = (long)blockIdx.y * jchunk;
   const long j_end = (j_begin + jchunk < Npad) ? j_begin + jchunk : Npad;
@@ -1290,7 +1306,7 @@ __global__ __launch_bounds__(256) void k_apply_M_mrhs(const double *__restrict__
     const long j = j0 + t;
     double x, y, z;
     if (j < N) {
-      x = r[3 * j] * P.inv_a; y = r[3 * j + 1] * P.inv_a; z = r[3 * j + 2] * P.inv_a;
+      x = r[3 * j] * ps; y = r[3 * j + 1] * ps; z = r[3 * j + 2] * ps;
       if (WALL && z < 0.0) flags |= RBL_FLAG_BELOW_WALL;
     } else {  // padding (its packed forces are zero)
       x = 1.0e15 * (double)(2 + (j - N)); y = 0.0; z = 1.0;
@@ -1346,7 +1362,7 @@ __global__ void k_unpack_rhs(const double *__restrict__ Up, const double *__rest
   const int n = (int)(idx / (3 * N));
   double s = 0.0;
   for (int k = 0; k < nsplit; ++k) s += Up[(size_t)k * (size_t)Npad * 3 * MR + (size_t)ia * MR + n];
-  double sc = P.nf;
+  double sc = rbl_unit_out_scale<rbl_unit_of(WALL)>(P);   // (k_apply_M_mrhs sums in its unit)
   if (WALL) sc *= damp_of(P, r[3 * (ia / 3) + 2]);
   out[(size_t)n * (size_t)ldO + ia] = sc * s;
   if (!isfinite(s)) atomicOr(err, (unsigned)RBL_FLAG_NONFINITE);
@@ -2063,7 +2079,8 @@ void rbl_launch_apply_M_per(hipStream_t st, const RblParams &P, const double *d_
   const int js_eff = (int)((n_blobs + jchunk - 1) / jchunk);
   const bool px = Lx > 0.0, py = Ly > 0.0;
   PerCell C;
-  C.Lx = px ? Lx * P.inv_a : 0.0; C.Ly = py ? Ly * P.inv_a : 0.0;
+  const double ps = rbl_unit_pos_scale<rbl_unit_of(true)>(P);   // (k_apply_M_per's unit)
+  C.Lx = px ? Lx * ps : 0.0; C.Ly = py ? Ly * ps : 0.0;
   C.iLx = px ? 1.0 / C.Lx : 0.0; C.iLy = py ? 1.0 / C.Ly : 0.0;
   C.nx = px ? nx : 0; C.ny = py ? ny : 0;
   dim3 grid((unsigned)itiles, (unsigned)js_eff), block(TB);

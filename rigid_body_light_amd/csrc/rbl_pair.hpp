@@ -64,27 +64,89 @@ __device__ __forceinline__ double rbl_rsqrt(double x)
 //   T0 = 2g - ez,  T1 = ez { 6gk + u[(2 - 10v) + u(70/3 v - 10)] }
 // Swapping the roles of i and j swaps g <-> k, i.e. T1 -> -T1 only: M_ji = M_ij^T exactly.
 // ---------------------------------------------------------------------------
-// UNIT: the caller works in coordinates already divided by the blob radius (a = 1), which removes the
-// a/R and a/r multiplications from every pair.
-// Three of the polynomial coefficients come in pairs of non-inline constants (fma(v, -10/3, 2/3), ...).
-// A gfx9 VOP3 instruction reads at most one SGPR/constant, so the compiler re-materialises the second one
-// into a VGPR with a v_mov_b64 on EVERY evaluation.  A caller with registers to spare passes them in as
-// opaque VGPR-resident values (RblWallK from rbl_wall_k_resident()) and saves those two issue slots per pair.
+// UNIT: the length unit of the coordinates the caller hands in.
+//   RBL_UNIT_PHYS   (0, = false)  physical lengths; the pair multiplies by a/R and a/r itself
+//   RBL_UNIT_RADIUS (1, = true)   coordinates already divided by the blob radius (a = 1): those multiplications are gone.  The
+//                                 one-workgroup kernels of small systems (rbl_small_dev.hpp) and the host checks of tests/host_pair
+//   RBL_UNIT_SHARED (2)           coordinates divided by a / lambda, lambda^2 = RBL_UNIT_L2 = 3, and every coefficient DIVIDED by
+//                                 lambda: the block the five scalars describe, applied to lambda-scaled displacements, is M / lambda
+//                                 (the epilogues multiply by lambda nf instead of nf: rbl_unit_out_scale).  Every coefficient is
+//                                 w = a/R or s = a/r times a polynomial in w^2, s^2 and ratios of lengths, so the unit only changes
+//                                 the polynomials' constants -- with w' = w / lambda, u' = u / 3:
+//     b1  = -1 - 2gk + u'[(6v - 2)   + u'(6 - 30v)]
+//     b2p =      6gk + u'[(6 - 30v)  + u'(210v - 30)]            Q = 6 - 30v serves both: one instruction less per pair
+//     and, u' being 1 / R'^2 itself, gk = z_i z_j / R^2 = z_i' z_j' u' joins the brackets (no (r/R)^2, no separate constant parts):
+//     b1  = -1 + u'[(6v - 2 - 2 z_i' z_j') + u' Q],    b2p = u'[(Q + 6 z_i' z_j') + u'(210v - 30)]      a second instruction less:
+//     -2 z_i' and 6 z_i' are the row's, formed outside the sweep's loop
+//     T1p = b2p - 60 u'^2,   zz bracket  u'^2 (180v - 24) - v (b2p + 12u'),   A' = s' + 2 s'^3,   Bc' = (s' - 6 s'^3) / r'^2
+//                                 (the brackets coincide because 3 (2 - 10v) = 9 (2/3 - 10/3 v): lambda^2 = 3 and nothing else)
+// A gfx9 VOP3 instruction reads at most one SGPR/constant, so of a bracket's two non-inline constants the compiler re-materialises the
+// second one into a VGPR with a v_mov_b64 on EVERY evaluation.  A caller with registers to spare passes them in as
+// opaque register-resident values (RblWallK from rbl_wall_k_resident()) and saves those issue slots (-30 serves Q and, as the addend,
+// the 210v - 30 bracket).
+#define RBL_UNIT_PHYS 0
+#define RBL_UNIT_RADIUS 1
+#define RBL_UNIT_SHARED 2
+#define RBL_UNIT_L2 3.0                       // lambda^2: the ONE place the shared unit is chosen (the polynomials above assert it)
+#define RBL_UNIT_L 1.7320508075688772         // lambda = sqrt(3)
+#define RBL_UNIT_INV_L 0.57735026918962576    // 1 / lambda
+
+constexpr double rbl_unit_l2(int unit) { return unit == RBL_UNIT_SHARED ? RBL_UNIT_L2 : 1.0; }
+constexpr double rbl_unit_inv_l(int unit) { return unit == RBL_UNIT_SHARED ? RBL_UNIT_INV_L : 1.0; }
+
+constexpr double rbl_unit_l(int unit) { return unit == RBL_UNIT_SHARED ? RBL_UNIT_L : 1.0; }
+// The wall polynomials are what the shared unit pays for; in free space it saves nothing and its -6 (for the -2 of Bc, an inline
+// constant) costs the wave-unit kernels a copy per pair and three instances a few bytes of scratch: free-space kernels keep the radius.
+constexpr int rbl_unit_of(bool wall) { return wall ? RBL_UNIT_SHARED : RBL_UNIT_RADIUS; }
+
+// the kernels' side of a unit (UNIT = RBL_UNIT_RADIUS or RBL_UNIT_SHARED): positions times rbl_unit_pos_scale when loaded, sums times
+// rbl_unit_out_scale when they leave, the pair routines called with rbl_unit_params (the parameter set of a blob of radius 1 or
+// lambda: switch distances and near-branch constants)
+template <int UNIT>
+__host__ __device__ __forceinline__ double rbl_unit_pos_scale(const RblParams &P) { return UNIT == RBL_UNIT_SHARED ? P.inv_a * RBL_UNIT_L : P.inv_a; }
+template <int UNIT>
+__host__ __device__ __forceinline__ double rbl_unit_out_scale(const RblParams &P) { return UNIT == RBL_UNIT_SHARED ? P.nf * RBL_UNIT_L : P.nf; }
+template <int UNIT>
+__host__ __device__ __forceinline__ RblParams rbl_unit_params(const RblParams &P)
+{
+  constexpr double L2 = rbl_unit_l2(UNIT);
+  RblParams Pu = P;
+  Pu.a = rbl_unit_l(UNIT); Pu.inv_a = rbl_unit_inv_l(UNIT);   // the blob radius in the unit
+  Pu.four_a2 = 4.0 * L2; Pu.tiny2 = 1e-24 * L2;
+  Pu.c_near_A = -0.375 / L2; Pu.c_near_B = 0.125 / L2;       // shared: (4/3 - 3/8 r) / lambda = 4/(3 lambda) - r'/8,  1/(8 lambda^2 r') = (1/24) / r'
+  return Pu;
+}
+
+// The shared unit's constants are small integers, and gfx950 encodes such a double (low word zero) as the 32-bit literal of a VOP2
+// v_fmac_f64 -- whose addend is its destination.  Where the addend lives on (fma(v, 210, -30): the resident -30;  T1p = fma(u'^2, -60, b2p):
+// b2p) the compiler takes that form anyway and copies the addend first, a v_mov_b64 per pair each.  So these multipliers are
+// opaque as well, in SCALAR register pairs (a VOP3 v_fma_f64 reads one): 210 (k2), -60 (s1) and the 6 of Q and of 6v - 2 (s2, which the
+// compiler otherwise keeps in a vector pair).  -30 and 180 stay in vector pairs: they share an instruction with 210 and -24.
+// (All of them in vector registers: the same instructions, and k_apply_M_symw<true,2,4,1> spills 12 bytes at its 168 VGPRs.)
 struct RblWallK {
-  double k1, k2, k3, k4;   // -10/3, 70/3, 20, 3/2
+  double k1, k2, k3, k4;   // physical / radius units: -10/3, 70/3, 20, 3/2;  shared unit: -30, 210, 180, (unused)
+  double s1, s2;           // shared unit: -60, 6
 };
-__device__ __forceinline__ RblWallK rbl_wall_k_literal() { return RblWallK{-10.0 / 3.0, 70.0 / 3.0, 20.0, 1.5}; }
+template <int UNIT = RBL_UNIT_PHYS>
+__device__ __forceinline__ RblWallK rbl_wall_k_literal()
+{
+  if constexpr (UNIT == RBL_UNIT_SHARED) return RblWallK{-30.0, 210.0, 180.0, 0.0, -60.0, 6.0};
+  else return RblWallK{-10.0 / 3.0, 70.0 / 3.0, 20.0, 1.5, 0.0, 0.0};
+}
+template <int UNIT>
 __device__ __forceinline__ RblWallK rbl_wall_k_resident()
 {
-  RblWallK K = rbl_wall_k_literal();
-  asm volatile("" : "+v"(K.k1), "+v"(K.k2), "+v"(K.k3), "+v"(K.k4));   // opaque to the optimiser: stays in VGPRs
+  RblWallK K = rbl_wall_k_literal<UNIT>();
+  // opaque to the optimiser: the values stay in the registers they are given
+  if constexpr (UNIT == RBL_UNIT_SHARED) asm volatile("" : "+v"(K.k1), "+v"(K.k3), "+s"(K.k2), "+s"(K.s1), "+s"(K.s2));
+  else asm volatile("" : "+v"(K.k1), "+v"(K.k2), "+v"(K.k3), "+v"(K.k4));
   return K;
 }
 
-template <bool UNIT = false>
+template <int UNIT = RBL_UNIT_PHYS>
 __device__ __forceinline__ void rbl_wall_coeffs(const RblParams &P, double dz, double zi, double zj, double q,
                                                 double r2, double A, double Bc, double &cF, double &beta, double &gxz,
-                                                double &gzx, double &mzz, const RblWallK &K = rbl_wall_k_literal())
+                                                double &gzx, double &mzz, const RblWallK &K = rbl_wall_k_literal<UNIT>())
 {
   // Further identities that take instructions out (84 -> 75 fp64 instructions per unordered pair):
   //   T0 = 2g - ez = (z_j - z_i)/R = -dz/R             (g never formed)
@@ -104,14 +166,27 @@ __device__ __forceinline__ void rbl_wall_coeffs(const RblParams &P, double dz, d
   const double iR2 = invR * invR;
   const double u = w * w;
   const double v = __builtin_fma(-q, iR2, 1.0);
-  const double rr = r2 * iR2;                                                        // (r/R)^2 = 1 - 4 gk
-  const double t1 = __builtin_fma(u, __builtin_fma(v, K.k1, 2.0 / 3.0), __builtin_fma(v, 2.0, -2.0 / 3.0));
-  const double b1 = __builtin_fma(u, t1, __builtin_fma(0.5, rr, -K.k4));             // -1 - 2 gk + u t1
-  const double t2 = __builtin_fma(u, __builtin_fma(v, K.k2, -10.0 / 3.0), __builtin_fma(v, -10.0, 2.0));
-  const double sixgk = __builtin_fma(-rr, K.k4, K.k4);
-  const double b2p = __builtin_fma(u, t2, sixgk);                                    // b2 + 1
+  // (L2 = 1 outside the shared unit: the constants below are then the ones of the header comment's first form)
+  constexpr double L2 = rbl_unit_l2(UNIT);
+  double b1, b2p;
+  if constexpr (UNIT == RBL_UNIT_SHARED) {
+    static_assert(L2 * 2.0 == L2 * L2 * 2.0 / 3.0 && L2 * -10.0 == L2 * L2 * -10.0 / 3.0, "Q is shared only where lambda^2 = 3");
+    // gk = z_i z_j / R^2 = z_i z_j u here (u = 1 / R^2 in the unit), so the constant parts join the Horner brackets:
+    //   b1 = -1 + u [(6v - 2 - 2 z_i z_j) + u Q],   b2p = u [(Q + 6 z_i z_j) + u (210v - 30)]
+    // -2 z_i and 6 z_i belong to the row: a sweep forms them once, outside its loop
+    const double Q = __builtin_fma(v, K.k1, K.s2);                                   // 6 - 30 v
+    const double m = __builtin_fma(-2.0 * zi, zj, -2.0);
+    b1 = __builtin_fma(u, __builtin_fma(u, Q, __builtin_fma(v, K.s2, m)), -1.0);
+    b2p = u * __builtin_fma(u, __builtin_fma(v, K.k2, K.k1), __builtin_fma(6.0 * zi, zj, Q));
+  } else {
+    const double rr = r2 * iR2;                                                      // (r/R)^2 = 1 - 4 gk
+    const double t1 = __builtin_fma(u, __builtin_fma(v, K.k1, 2.0 / 3.0), __builtin_fma(v, 2.0, -2.0 / 3.0));
+    const double t2 = __builtin_fma(u, __builtin_fma(v, K.k2, -10.0 / 3.0), __builtin_fma(v, -10.0, 2.0));
+    b1 = __builtin_fma(u, t1, __builtin_fma(0.5, rr, -K.k4));                        // -1 - 2 gk + u t1
+    b2p = __builtin_fma(u, t2, __builtin_fma(-rr, K.k4, K.k4));                      // b2 + 1 = 6 gk + u t2
+  }
   const double uu = u * u;
-  const double T1p = __builtin_fma(uu, -20.0 / 3.0, b2p);                            // T1 / ez
+  const double T1p = __builtin_fma(uu, UNIT == RBL_UNIT_SHARED ? K.s1 : -20.0 / 3.0, b2p);   // T1 / ez
   const double w3 = w * iR2;                                                         // w / R^2
   const double Bw = Bc - w3;
   cF = __builtin_fma(w, b1, A);
@@ -119,8 +194,8 @@ __device__ __forceinline__ void rbl_wall_coeffs(const RblParams &P, double dz, d
   const double gm = dz * Bw, gdw = Rz * w3;
   gxz = __builtin_fma(-T1p, gdw, gm);                                                // M_xz = dx gxz, M_yz = dy gxz
   gzx = __builtin_fma(T1p, gdw, gm);                                                 // M_zx = dx gzx, M_zy = dy gzx
-  // zz bracket  u d1 - v b2p,  d1 = u (20 v - 8/3) - 4 v:   u^2 (20 v - 8/3) - v (b2p + 4 u)
-  const double c = __builtin_fma(uu, __builtin_fma(v, K.k3, -8.0 / 3.0), -(v * __builtin_fma(4.0, u, b2p)));
+  // zz bracket  u d1 - v b2p,  d1 = u (20 v - 8/3) - 4 v:   u^2 (20 v - 8/3) - v (b2p + 4 u)      (shared unit: 180, 24, 12)
+  const double c = __builtin_fma(uu, __builtin_fma(v, K.k3, -8.0 * L2 * L2 / 3.0), -(v * __builtin_fma(4.0 * L2, u, b2p)));
   mzz = __builtin_fma(w, c, __builtin_fma(gm, dz, cF));
 }
 
@@ -130,12 +205,12 @@ __device__ __forceinline__ void rbl_wall_coeffs(const RblParams &P, double dz, d
 //   SELF: compile-time "this j-tile may contain i" (index-equality self term)
 // Accumulates UNSCALED (units 1/(8 pi eta a)) into ux,uy,uz.
 // ---------------------------------------------------------------------------
-template <bool WALL, bool SELF, bool UNIT = false>
+template <bool WALL, bool SELF, int UNIT = RBL_UNIT_PHYS>
 __device__ __forceinline__ void rbl_pair_accum(const RblParams &P, double xi, double yi,
                                                double zi, double xj, double yj, double zj,
                                                double Fx, double Fy, double Fz, bool is_self,
                                                double &ux, double &uy, double &uz,
-                                               unsigned &flags, const RblWallK &K = rbl_wall_k_literal())
+                                               unsigned &flags, const RblWallK &K = rbl_wall_k_literal<UNIT>())
 {
   const double dx = xi - xj, dy = yi - yj, dz = zi - zj;
   const double q = __builtin_fma(dy, dy, dx * dx);
@@ -146,19 +221,20 @@ __device__ __forceinline__ void rbl_pair_accum(const RblParams &P, double xi, do
   const double invr2 = invr * invr;
   const double s = UNIT ? invr : P.a * invr;         // a/r
   const double t = s * s;                            // (a/r)^2
-  // far:  A = (a/r)(1 + 2/3 (a/r)^2),  Bc = (a/r)(1 - 2 (a/r)^2)/r^2
-  double A = __builtin_fma(s * t, 2.0 / 3.0, s);
-  double Bc = (s * invr2) * __builtin_fma(-2.0, t, 1.0);
+  // far:  A = (a/r)(1 + 2/3 (a/r)^2),  Bc = (a/r)(1 - 2 (a/r)^2)/r^2      (shared unit: s + 2 s^3, (s - 6 s^3)/r^2, all / lambda)
+  constexpr double L2 = rbl_unit_l2(UNIT), iL = rbl_unit_inv_l(UNIT), four3 = (4.0 / 3.0) * iL;
+  double A = __builtin_fma(s * t, 2.0 * L2 / 3.0, s);
+  double Bc = (s * invr2) * __builtin_fma(-2.0 * L2, t, 1.0);
   if (__builtin_expect(__any(r2 < P.four_a2), 0)) {  // wave-uniform: the overlap branch (and i == j) is rare
     // overlap: A = 4/3 - 3/8 r/a,  Bc = (1/8) / (a r)
     const double rr = r2 * invr;                     // r
     const bool far = r2 >= P.four_a2;
-    A = far ? A : __builtin_fma(rr, P.c_near_A, 4.0 / 3.0);
+    A = far ? A : __builtin_fma(rr, P.c_near_A, four3);
     Bc = far ? Bc : invr * P.c_near_B;
     if (r2 < P.tiny2 && !(SELF && is_self)) flags |= RBL_FLAG_OVERLAP;   // :53-58
   }
   if (SELF) {                                        // index equality, :40-46
-    A = is_self ? 4.0 / 3.0 : A;
+    A = is_self ? four3 : A;
     Bc = is_self ? 0.0 : Bc;
   }
   const double q2 = __builtin_fma(dy, Fy, dx * Fx);
@@ -174,11 +250,11 @@ __device__ __forceinline__ void rbl_pair_accum(const RblParams &P, double xi, do
   // ---- single-wall correction (c_rigid_obj.cpp:98-140), ordered pair, h = z_j
   if (SELF && is_self) {
     // self wall term (:98-104): diag only, args (0,0,2h; h = z_i/a)
-    const double iz = (UNIT ? 1.0 : P.a) / zi;       // 1/h  (true division kept: rare path)
+    const double iz = (UNIT == RBL_UNIT_SHARED ? RBL_UNIT_L : UNIT ? 1.0 : P.a) / zi;   // 1/h in radii (true division kept: rare path)
     const double iz3 = iz * iz * iz;
     const double iz5 = iz3 * iz * iz;
-    const double dpar = -(9.0 * iz - 2.0 * iz3 + iz5) / 12.0;
-    const double dper = -(9.0 * iz - 4.0 * iz3 + iz5) / 6.0;
+    const double dpar = -(9.0 * iz - 2.0 * iz3 + iz5) / 12.0 * iL;
+    const double dper = -(9.0 * iz - 4.0 * iz3 + iz5) / 6.0 * iL;
     ux = __builtin_fma(A + dpar, Fx, ux);
     uy = __builtin_fma(A + dpar, Fy, uy);
     uz = __builtin_fma(A + dper, Fz, uz);
@@ -211,10 +287,10 @@ struct RblV3 {
   double x, y, z;
 };
 
-template <bool WALL, bool UNIT = false, bool NEARCHK = true, int NV = 1>
+template <bool WALL, int UNIT = RBL_UNIT_PHYS, bool NEARCHK = true, int NV = 1>
 __device__ __forceinline__ void rbl_pair_symv(const RblParams &P, double xi, double yi, double zi, const RblV3 (&Fi)[NV],
                                               double xj, double yj, double zj, const RblV3 (&Fj)[NV], RblV3 (&ui)[NV],
-                                              RblV3 (&uj)[NV], unsigned &flags, const RblWallK &K = rbl_wall_k_literal())
+                                              RblV3 (&uj)[NV], unsigned &flags, const RblWallK &K = rbl_wall_k_literal<UNIT>())
 {
   const double dx = xi - xj, dy = yi - yj, dz = zi - zj;
   const double q = __builtin_fma(dy, dy, dx * dx);
@@ -223,11 +299,12 @@ __device__ __forceinline__ void rbl_pair_symv(const RblParams &P, double xi, dou
   const double invr2 = invr * invr;
   const double s = UNIT ? invr : P.a * invr;
   const double s3 = (s * s) * s;
-  double A = __builtin_fma(s3, 2.0 / 3.0, s);              // (a/r)(1 + 2/3 (a/r)^2)
-  double Bc = __builtin_fma(s3, -2.0, s) * invr2;          // (a/r)(1 - 2 (a/r)^2) / r^2
+  constexpr double L2 = rbl_unit_l2(UNIT), four3 = (4.0 / 3.0) * rbl_unit_inv_l(UNIT);
+  double A = __builtin_fma(s3, 2.0 * L2 / 3.0, s);         // (a/r)(1 + 2/3 (a/r)^2)            shared unit: s + 2 s^3
+  double Bc = __builtin_fma(s3, -2.0 * L2, s) * invr2;     // (a/r)(1 - 2 (a/r)^2) / r^2                     (s - 6 s^3) / r^2
   if (NEARCHK && __builtin_expect(__any(r2 < P.four_a2), 0)) {   // wave-uniform: overlap branch is rare
     const double rr = r2 * invr;
-    const double A_near = __builtin_fma(rr, P.c_near_A, 4.0 / 3.0);
+    const double A_near = __builtin_fma(rr, P.c_near_A, four3);
     const double B_near = invr * P.c_near_B;
     const bool far = r2 >= P.four_a2;
     A = far ? A : A_near;
@@ -271,11 +348,11 @@ __device__ __forceinline__ void rbl_pair_symv(const RblParams &P, double xi, dou
 // block is the A-operand of fp64 MFMAs:  M = cF I + Bc d d^T + f2 e e^T + f3 e z^T
 // + f4 z e^T + f5 z z^T.
 // ---------------------------------------------------------------------------
-template <bool WALL, bool SELF, bool UNIT = false>
+template <bool WALL, bool SELF, int UNIT = RBL_UNIT_PHYS>
 __device__ __forceinline__ void rbl_pair_block_fast(const RblParams &P, double xi, double yi,
                                                     double zi, double xj, double yj, double zj,
                                                     bool is_self, double *m, unsigned &flags,
-                                                    const RblWallK &K = rbl_wall_k_literal())
+                                                    const RblWallK &K = rbl_wall_k_literal<UNIT>())
 {
   const double dx = xi - xj, dy = yi - yj, dz = zi - zj;
   const double q = __builtin_fma(dy, dy, dx * dx);
@@ -284,17 +361,18 @@ __device__ __forceinline__ void rbl_pair_block_fast(const RblParams &P, double x
   const double invr2 = invr * invr;
   const double s = UNIT ? invr : P.a * invr;
   const double t = s * s;
-  double A = __builtin_fma(s * t, 2.0 / 3.0, s);
-  double Bc = (s * invr2) * __builtin_fma(-2.0, t, 1.0);
+  constexpr double L2 = rbl_unit_l2(UNIT), iL = rbl_unit_inv_l(UNIT), four3 = (4.0 / 3.0) * iL;
+  double A = __builtin_fma(s * t, 2.0 * L2 / 3.0, s);
+  double Bc = (s * invr2) * __builtin_fma(-2.0 * L2, t, 1.0);
   if (__builtin_expect(__any(r2 < P.four_a2), 0)) {
     const double rr = r2 * invr;
     const bool far = r2 >= P.four_a2;
-    A = far ? A : __builtin_fma(rr, P.c_near_A, 4.0 / 3.0);
+    A = far ? A : __builtin_fma(rr, P.c_near_A, four3);
     Bc = far ? Bc : invr * P.c_near_B;
     if (r2 < P.tiny2 && !(SELF && is_self)) flags |= RBL_FLAG_OVERLAP;
   }
   if (SELF) {
-    A = is_self ? 4.0 / 3.0 : A;
+    A = is_self ? four3 : A;
     Bc = is_self ? 0.0 : Bc;
   }
   if (!WALL) {
@@ -305,11 +383,11 @@ __device__ __forceinline__ void rbl_pair_block_fast(const RblParams &P, double x
     return;
   }
   if (SELF && is_self) {  // self wall term (:98-104): diagonal only
-    const double iz = (UNIT ? 1.0 : P.a) / zi;
+    const double iz = (UNIT == RBL_UNIT_SHARED ? RBL_UNIT_L : UNIT ? 1.0 : P.a) / zi;
     const double iz3 = iz * iz * iz;
     const double iz5 = iz3 * iz * iz;
-    const double dpar = -(9.0 * iz - 2.0 * iz3 + iz5) / 12.0;
-    const double dper = -(9.0 * iz - 4.0 * iz3 + iz5) / 6.0;
+    const double dpar = -(9.0 * iz - 2.0 * iz3 + iz5) / 12.0 * iL;
+    const double dper = -(9.0 * iz - 4.0 * iz3 + iz5) / 6.0 * iL;
     m[0] = A + dpar; m[1] = 0.0; m[2] = 0.0;
     m[3] = 0.0; m[4] = A + dpar; m[5] = 0.0;
     m[6] = 0.0; m[7] = 0.0; m[8] = A + dper;

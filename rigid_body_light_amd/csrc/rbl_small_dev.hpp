@@ -7,6 +7,9 @@
 constexpr int RBL_SG_THREADS = 1024;
 
 // the pair kernels' constants for positions given in units of a (rbl_pair_accum / rbl_pair_symv, scaled by nf afterwards)
+// (RBL_UNIT_RADIUS: the one-workgroup kernels keep the radius as their length unit -- their LDS positions and cell tables serve the
+// joints, the forces and the damping in radii as well, and a kernel that waits on barriers and launch latency has no use for the
+// instruction the shared unit of the large products saves)
 __device__ __forceinline__ RblParams rbl_small_unit_params(const RblParams &P)
 {
   return {1.0, 1.0, P.nf, 4.0, 1e-24, -0.375, 0.125, 0};
@@ -82,7 +85,7 @@ __device__ __forceinline__ void rbl_small_pair_sweep(const RblParams &Pu, const 
         double dx = pos[3 * i] - pos[3 * j], dy = pos[3 * i + 1] - pos[3 * j + 1];
         dx = __builtin_fma(-C.Lx, rint(dx * C.iLx), dx);   // 1 / L is 0 on an open axis: rint(0) = 0 leaves d alone
         dy = __builtin_fma(-C.Ly, rint(dy * C.iLy), dy);
-        rbl_pair_symv<true, true, true>(Pu, __builtin_fma(pd, C.Lx, dx), __builtin_fma(qd, C.Ly, dy), pos[3 * i + 2], Fi, 0.0, 0.0, pos[3 * j + 2], Fj, ui, uj, flags);
+        rbl_pair_symv<true, RBL_UNIT_RADIUS, true>(Pu, __builtin_fma(pd, C.Lx, dx), __builtin_fma(qd, C.Ly, dy), pos[3 * i + 2], Fi, 0.0, 0.0, pos[3 * j + 2], Fj, ui, uj, flags);
         if (s_ == 0) {                                 // wave-uniform: j = i, image and mirror image in one
           ui[0].x += uj[0].x; ui[0].y += uj[0].y; ui[0].z += uj[0].z;
         }
@@ -107,7 +110,7 @@ __device__ __forceinline__ void rbl_small_pair_sweep(const RblParams &Pu, const 
       const double di = WALL ? dmp[i] : 1.0, dj = WALL ? dmp[j] : 1.0;
       const RblV3 Fi[1] = {{di * in[3 * i], di * in[3 * i + 1], di * in[3 * i + 2]}}, Fj[1] = {{dj * in[3 * j], dj * in[3 * j + 1], dj * in[3 * j + 2]}};
       RblV3 ui[1] = {{0.0, 0.0, 0.0}}, uj[1] = {{0.0, 0.0, 0.0}};
-      rbl_pair_symv<WALL, true, true>(Pu, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], Fi, pos[3 * j], pos[3 * j + 1], pos[3 * j + 2], Fj, ui, uj, flags);
+      rbl_pair_symv<WALL, RBL_UNIT_RADIUS, true>(Pu, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], Fi, pos[3 * j], pos[3 * j + 1], pos[3 * j + 2], Fj, ui, uj, flags);
       __hip_atomic_fetch_add(&acc[3 * i], ui[0].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       __hip_atomic_fetch_add(&acc[3 * i + 1], ui[0].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       __hip_atomic_fetch_add(&acc[3 * i + 2], ui[0].z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);

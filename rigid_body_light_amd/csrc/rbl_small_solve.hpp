@@ -470,7 +470,7 @@ __device__ __forceinline__ void rbl_small_solve(Args A)
     if (t < N) {                             // self blocks (:40-46, :98-104) and the per-blob terms of K^T lambda
       const double di = WALL ? dmp[t] : 1.0;
       double ux = 0.0, uy = 0.0, uz = 0.0;
-      rbl_pair_accum<WALL, true, true>(Pu, pos[3 * t], pos[3 * t + 1], pos[3 * t + 2], pos[3 * t], pos[3 * t + 1], pos[3 * t + 2],
+      rbl_pair_accum<WALL, true, RBL_UNIT_RADIUS>(Pu, pos[3 * t], pos[3 * t + 1], pos[3 * t + 2], pos[3 * t], pos[3 * t + 1], pos[3 * t + 2],
                                        di * in[3 * t], di * in[3 * t + 1], di * in[3 * t + 2], true, ux, uy, uz, flags);
       su[3 * t] = ux; su[3 * t + 1] = uy; su[3 * t + 2] = uz;
       const double v0 = in[3 * t], v1 = in[3 * t + 1], v2 = in[3 * t + 2];
