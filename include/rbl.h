@@ -679,7 +679,7 @@ int rbl_interaction_forces(rbl_ctx *ctx, double *f_blob, double *FT_body, double
 int rbl_interaction_stats(rbl_ctx *ctx, int64_t *body_pairs, int64_t *blob_pairs);
 
 /* ===================================================================== */
-/* 5. Ensembles of independent replicas (rigid_body_light_amd/csrc/rbl_ensemble.hip) */
+/* 5. Ensembles of independent replicas (rigid_body_light_amd/csrc/rbl_ensemble.hip; runs: rbl_ens_run.hip) */
 /* ===================================================================== */
 /* R independent replicas of one small system, resident on the device: every replica shares the context's structure,
  * parameters (a, eta, dt, kBT), wall flag and force model (section 4) and has its own X (3 N_bod) and Q (4 N_bod); arrays

@@ -1595,8 +1595,7 @@ class DeviceContext:
 
     def _ensemble_run(self, obs, n_steps, F_body=None, prescribed=None, body_in=None, brownian=True, seed=0, stride=0, on_error=RUN_STOP,
                       check_every=RUN_CHECK_DEFAULT, slip=None, split_rand=True, delta=1.0e-4, max_iter=50, rtol=1.0e-8, per=1, drive=None):
-        """ensemble_run's body, shared with ensemble_run_observed (obs: its observers, None for the plain run) and
-        ensemble_run_driven (drive: drive_opts' keywords, None for the other two)"""
+        """ensemble_run's arguments, checked and laid out for _run; obs (ensemble_run_observed) and drive (ensemble_run_driven) pass through"""
         import numpy as np
         R, nb = self.ensemble_info()
         if R == 0:
@@ -1615,17 +1614,23 @@ class DeviceContext:
         else:
             F = self._ens_vec(F_body, 6 * nb, "F_body")
             sl = None if slip is None else self._ens_vec(slip, 3 * nb * self._sizes()[1], "slip")
+        return self._run(masked, dict(n_steps=n_steps, brownian=int(bool(brownian)), split_rand=int(bool(split_rand)), max_iter=int(max_iter),
+                                      stride=stride, on_error=int(on_error), check_every=int(check_every), seed=int(seed), delta=float(delta),
+                                      rtol=float(rtol or 0.0), prescribed_per=int(per), F_body=None if masked else F,
+                                      prescribed=m if masked else None, body_in=bi if masked else None, slip=sl), obs=obs, drive=drive)
+
+    def _run(self, masked, opts, joints=None, obs=None, drive=None):
+        """the one body of a run, and the one place a run enters the library.  opts: the fields of rbl_run_opts (arrays for the
+        pointers); masked: prescribed bodies, so F_sum, F, F_mean.  The optional parts, each with its structs and its records on the
+        result: joints (RunJointOpts, the arrays behind its pointers, the active joints' count), obs (ensemble_run_observed's
+        (points, probe_body, moments)), drive (drive_opts' keywords); they choose the entry point.  -> (RunResult, status)"""
+        import numpy as np
+        R, nb = self.ensemble_info()
         o = RunOpts()
         o.size = C.sizeof(RunOpts)
-        o.n_steps, o.brownian, o.split_rand, o.max_iter = n_steps, int(bool(brownian)), int(bool(split_rand)), int(max_iter)
-        o.stride, o.on_error, o.check_every, o.seed = stride, int(on_error), int(check_every), int(seed)
-        o.delta, o.rtol = float(delta), float(rtol or 0.0)
-        o.prescribed_per = int(per)
-        o.F_body = None if masked else F.ctypes.data
-        o.prescribed = m.ctypes.data if masked else None
-        o.body_in = bi.ctypes.data if masked else None
-        o.slip = None if sl is None else sl.ctypes.data
-        nf = n_steps // stride if stride > 0 else 0
+        for k, v in opts.items():
+            setattr(o, k, v.ctypes.data if isinstance(v, np.ndarray) else v)
+        nf = o.n_steps // o.stride if o.stride > 0 else 0
         res = RunResult()
         res.accepted, res.rejected = np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32)
         res.first_flags, res.first_status = np.zeros(R, dtype=np.uint32), np.zeros(R, dtype=np.int32)
@@ -1634,6 +1639,7 @@ class DeviceContext:
         res.X, res.Q = np.zeros((nf, R, nb, 3)), np.zeros((nf, R, nb, 4))
         res.accepted_at = np.zeros((nf, R), dtype=np.int32)
         res.F = np.zeros((nf, R, 6 * nb)) if masked else None
+        res.F_mean = None
         out = RunOut()
         out.size = C.sizeof(RunOut)
         out.accepted, out.rejected = res.accepted.ctypes.data, res.rejected.ctypes.data
@@ -1643,27 +1649,16 @@ class DeviceContext:
         out.frame_X, out.frame_Q, out.frame_accepted_at = res.X.ctypes.data, res.Q.ctypes.data, res.accepted_at.ctypes.data
         out.frame_F = res.F.ctypes.data if masked else None
         out.stopped_at = out.stop_replica = -1       # a refused call leaves them so
-        rc = self._run_call(o, None, out, None, res, obs, drive)
-        res.steps_done, res.stopped_at, res.stop_replica = out.steps_done, out.stopped_at, out.stop_replica
-        res.status, res.error = rc, None
-        if rc != 0:
-            res.error = "%s [rbl status %d]" % (self.L.rbl_last_error(self.h).decode(), rc)
-            if out.stopped_at < 0:                    # refused, or failed outside the steps: there is no result
-                raise RblError(res.error)
-        res.F_mean = None
-        if masked:
-            with np.errstate(divide="ignore", invalid="ignore"):
-                res.F_mean = np.where(res.accepted[:, None] > 0, res.F_sum / res.accepted[:, None], np.nan)
-        return res, rc
-
-    def _run_call(self, o, jo, out, jout, res, obs, drive=None):
-        """the one place a run enters the library: rbl_ensemble_run / rbl_ensemble_run_jointed as ever, or, with observers (obs:
-        ensemble_run_observed's (points, probe_body, moments)), rbl_ensemble_run_observed, whose records go onto res; with a drive
-        (drive_opts' keywords) rbl_ensemble_run_driven, with or without observers"""
-        import numpy as np
-        dd = dq = None
+        jo = jout = dd = dq = oo = oq = None
+        if joints is not None:
+            jo, keep, nj = joints
+            res.theta, res.cycle_pos, res.phi_sum = np.zeros((R, nj)), np.zeros(R, dtype=np.int32), np.zeros((R, nj, 3))
+            res.frame_theta, res.frame_phi, res.frame_gap = np.zeros((nf, R, nj)), np.zeros((nf, R, nj, 3)), np.zeros((nf, R, nj, 3))
+            jout = RunJointOut()
+            jout.size = C.sizeof(RunJointOut)
+            jout.theta, jout.cycle_pos, jout.phi_sum = res.theta.ctypes.data, res.cycle_pos.ctypes.data, res.phi_sum.ctypes.data
+            jout.frame_theta, jout.frame_phi, jout.frame_gap = res.frame_theta.ctypes.data, res.frame_phi.ctypes.data, res.frame_gap.ctypes.data
         if drive is not None:
-            R, nb = self.ensemble_info()
             dd, keep = drive_opts("ensemble_run_driven", 6 * nb, **drive)
             dq = RunDriveOut()
             dq.size = C.sizeof(RunDriveOut)
@@ -1677,31 +1672,44 @@ class DeviceContext:
                 if o.prescribed:
                     res.F_c, res.F_s = np.zeros((R, 6 * nb)), np.zeros((R, 6 * nb))
                     dq.F_c, dq.F_s = res.F_c.ctypes.data, res.F_s.ctypes.data
-            if obs is None:
-                return self.L.rbl_ensemble_run_driven(self.h, C.byref(o), C.byref(dd), None, C.byref(out), C.byref(dq), None)
-        if obs is None:
-            if jo is None:
-                return self.L.rbl_ensemble_run(self.h, C.byref(o), C.byref(out))
-            return self.L.rbl_ensemble_run_jointed(self.h, C.byref(o), C.byref(jo), C.byref(out), C.byref(jout))
-        pts, body, moments = obs
-        R, nb = self.ensemble_info()
-        nf = o.n_steps // o.stride if o.stride > 0 else 0
-        oo, oq = RunObsOpts(), RunObsOut()
-        oo.size, oq.size = C.sizeof(RunObsOpts), C.sizeof(RunObsOut)
-        oo.probe_body, oo.moments = int(body), int(bool(moments))
-        if pts is not None:
-            P = pts.shape[-2]
-            oo.n_probes, oo.point_sets, oo.points = P, (1 if pts.ndim == 2 else pts.shape[0]), pts.ctypes.data
-            if P:
-                res.u_sum, res.frame_u = np.zeros((R, P, 3)), np.zeros((nf, R, P, 3))
-                oq.u_sum, oq.frame_u = res.u_sum.ctypes.data, res.frame_u.ctypes.data
-        if moments:
-            res.D_sum, res.frame_D = np.zeros((R, nb, 3, 3)), np.zeros((nf, R, nb, 3, 3))
-            oq.D_sum, oq.frame_D = res.D_sum.ctypes.data, res.frame_D.ctypes.data
+        if obs is not None:
+            pts, body, moments = obs
+            oo, oq = RunObsOpts(), RunObsOut()
+            oo.size, oq.size = C.sizeof(RunObsOpts), C.sizeof(RunObsOut)
+            oo.probe_body, oo.moments = int(body), int(bool(moments))
+            if pts is not None:
+                P = pts.shape[-2]
+                oo.n_probes, oo.point_sets, oo.points = P, (1 if pts.ndim == 2 else pts.shape[0]), pts.ctypes.data
+                if P:
+                    res.u_sum, res.frame_u = np.zeros((R, P, 3)), np.zeros((nf, R, P, 3))
+                    oq.u_sum, oq.frame_u = res.u_sum.ctypes.data, res.frame_u.ctypes.data
+            if moments:
+                res.D_sum, res.frame_D = np.zeros((R, nb, 3, 3)), np.zeros((nf, R, nb, 3, 3))
+                oq.D_sum, oq.frame_D = res.D_sum.ctypes.data, res.frame_D.ctypes.data
+
+        def ref(s):
+            return None if s is None else C.byref(s)
         if dd is not None:
-            return self.L.rbl_ensemble_run_driven(self.h, C.byref(o), C.byref(dd), C.byref(oo), C.byref(out), C.byref(dq), C.byref(oq))
-        return self.L.rbl_ensemble_run_observed(self.h, C.byref(o), None if jo is None else C.byref(jo), C.byref(oo), C.byref(out),
-                                                None if jout is None else C.byref(jout), C.byref(oq))
+            rc = self.L.rbl_ensemble_run_driven(self.h, C.byref(o), C.byref(dd), ref(oo), C.byref(out), C.byref(dq), ref(oq))
+        elif oo is not None:
+            rc = self.L.rbl_ensemble_run_observed(self.h, C.byref(o), ref(jo), C.byref(oo), C.byref(out), ref(jout), C.byref(oq))
+        elif jo is not None:
+            rc = self.L.rbl_ensemble_run_jointed(self.h, C.byref(o), C.byref(jo), C.byref(out), C.byref(jout))
+        else:
+            rc = self.L.rbl_ensemble_run(self.h, C.byref(o), C.byref(out))
+        res.steps_done, res.stopped_at, res.stop_replica = out.steps_done, out.stopped_at, out.stop_replica
+        res.status, res.error = rc, None
+        if rc != 0:
+            res.error = "%s [rbl status %d]" % (self.L.rbl_last_error(self.h).decode(), rc)
+            if out.stopped_at < 0:                    # refused, or failed outside the steps: there is no result
+                raise RblError(res.error)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if masked:
+                res.F_mean = np.where(res.accepted[:, None] > 0, res.F_sum / res.accepted[:, None], np.nan)
+            if joints is not None:
+                res.phi_mean = np.where(res.accepted[:, None, None] > 0, res.phi_sum / res.accepted[:, None, None], np.nan)
+                res.phi, res.gap = res.frame_phi, res.frame_gap
+        return res, rc
 
     def ensemble_run_driven(self, n_steps, cos=None, sin=None, omega=None, t0=None, phase_steps=None, phase_in=None, cycle_start=None,
                             lockin=False, probes=None, probe_body=None, moments=False, **run_args):
@@ -1807,7 +1815,7 @@ class DeviceContext:
     def _ensemble_run_jointed(self, obs, n_steps, F_body, slip=None, joint_velocity=None, gamma=1.0, phase_steps=None, phase_rates=None,
                               cycle_start=None, stride=0, on_error=RUN_STOP, check_every=RUN_CHECK_DEFAULT, max_iter=50, rtol=1.0e-8,
                               brownian=False, prescribed=None, per=0):
-        """ensemble_run_jointed's body, shared with ensemble_run_observed (obs: its observers, None for the plain run)"""
+        """ensemble_run_jointed's arguments, checked and laid out for _run; obs (ensemble_run_observed) passes through"""
         import numpy as np
         R, nb = self.ensemble_info()
         if R == 0:
@@ -1837,45 +1845,9 @@ class DeviceContext:
                 raise ValueError("ensemble_run_jointed: cycle_start must be one integer or %d; got %d" % (R, cs.size))
             jo.start_sets, jo.cycle_start = cs.size, cs.ctypes.data
         pm = None if prescribed is None else np.ascontiguousarray(prescribed, dtype=np.uint8)
-        o = RunOpts()
-        o.size = C.sizeof(RunOpts)
-        o.n_steps, o.brownian, o.max_iter, o.stride = n_steps, int(bool(brownian)), int(max_iter), stride
-        o.on_error, o.check_every, o.rtol, o.prescribed_per = int(on_error), int(check_every), float(rtol or 0.0), int(per)
-        o.F_body = F.ctypes.data
-        o.slip = None if sl is None else sl.ctypes.data
-        o.prescribed = None if pm is None else pm.ctypes.data
-        nf = n_steps // stride if stride > 0 else 0
-        res = RunResult()
-        res.accepted, res.rejected = np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32)
-        res.first_flags, res.first_status = np.zeros(R, dtype=np.uint32), np.zeros(R, dtype=np.int32)
-        res.iters_sum, res.resid_max = np.zeros(R, dtype=np.int64), np.zeros(R)
-        res.F_sum = res.F = res.F_mean = None
-        res.X, res.Q = np.zeros((nf, R, nb, 3)), np.zeros((nf, R, nb, 4))
-        res.accepted_at = np.zeros((nf, R), dtype=np.int32)
-        res.theta, res.cycle_pos, res.phi_sum = np.zeros((R, nj)), np.zeros(R, dtype=np.int32), np.zeros((R, nj, 3))
-        res.frame_theta, res.frame_phi, res.frame_gap = np.zeros((nf, R, nj)), np.zeros((nf, R, nj, 3)), np.zeros((nf, R, nj, 3))
-        out = RunOut()
-        out.size = C.sizeof(RunOut)
-        out.accepted, out.rejected = res.accepted.ctypes.data, res.rejected.ctypes.data
-        out.first_flags, out.first_status = res.first_flags.ctypes.data, res.first_status.ctypes.data
-        out.iters_sum, out.resid_max = res.iters_sum.ctypes.data, res.resid_max.ctypes.data
-        out.frame_X, out.frame_Q, out.frame_accepted_at = res.X.ctypes.data, res.Q.ctypes.data, res.accepted_at.ctypes.data
-        out.stopped_at = out.stop_replica = -1       # a refused call leaves them so
-        jout = RunJointOut()
-        jout.size = C.sizeof(RunJointOut)
-        jout.theta, jout.cycle_pos, jout.phi_sum = res.theta.ctypes.data, res.cycle_pos.ctypes.data, res.phi_sum.ctypes.data
-        jout.frame_theta, jout.frame_phi, jout.frame_gap = res.frame_theta.ctypes.data, res.frame_phi.ctypes.data, res.frame_gap.ctypes.data
-        rc = self._run_call(o, jo, out, jout, res, obs)
-        res.steps_done, res.stopped_at, res.stop_replica = out.steps_done, out.stopped_at, out.stop_replica
-        res.status, res.error = rc, None
-        if rc != 0:
-            res.error = "%s [rbl status %d]" % (self.L.rbl_last_error(self.h).decode(), rc)
-            if out.stopped_at < 0:                    # refused, or failed outside the steps: there is no result
-                raise RblError(res.error)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            res.phi_mean = np.where(res.accepted[:, None, None] > 0, res.phi_sum / res.accepted[:, None, None], np.nan)
-        res.phi, res.gap = res.frame_phi, res.frame_gap
-        return res, rc
+        return self._run(False, dict(n_steps=n_steps, brownian=int(bool(brownian)), max_iter=int(max_iter), stride=stride, on_error=int(on_error),
+                                     check_every=int(check_every), rtol=float(rtol or 0.0), prescribed_per=int(per), F_body=F, slip=sl,
+                                     prescribed=pm), joints=(jo, (jv, ps, pr, cs), nj), obs=obs)
 
     def _sizes(self):
         nb, nblb = C.c_int(0), C.c_int(0)

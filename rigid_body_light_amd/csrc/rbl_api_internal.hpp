@@ -8,7 +8,8 @@
 //   rbl_solvers.hip   GMRES on the saddle operator
 //   rbl_steps.hip     whole time steps, the stochastic midpoint scheme (free and mixed), random finite differences
 //   rbl_forces.hip    configuration-dependent forces (weight, wall and steric repulsion, tabulated potentials, traps)
-//   rbl_ensemble.hip  ensembles of independent replicas of one small system
+//   rbl_ensemble.hip  ensembles of independent replicas of one small system: the one-step calls, what every step enqueues
+//   rbl_ens_run.hip   runs of ensemble steps: one request, its plan, the loop with its joints, observers and drive parts
 //   rbl_ens_field.hip the flow at probe points of every replica of an ensemble, the observers' share of a run's commit
 //   rbl_ens_drive.hip the time-dependent body input of a driven ensemble run, its lock-in sums
 //   rbl_field.hip     the fluid velocity at arbitrary points from blob forces
@@ -18,6 +19,7 @@
 // None of these symbols is exported from librbl.so.
 #pragma once
 #include <functional>
+#include <string>
 #include <vector>
 
 #include "rbl_internal.hpp"
@@ -218,9 +220,8 @@ void flow_begin_step(rbl_ctx *c);
 int flow_record_moments(rbl_ctx *c, const double *d_lambda);
 
 // ---- rbl_ensemble.hip / rbl_ens_field.hip ---------------------------------------------------------------------------
-// The ensemble as the one-shot field reads it: the refusals that look at the context's state alone (no ensemble, a changed
-// structure, a communicator; `who` leads the message), then -- the device touched -- the current configuration of all replicas,
-// the reference configuration, the cell (checked as a step checks it at use)
+// The ensemble as the one-shot field reads it (after ens_state_check, the refusals that look at the context's state alone): the
+// device touched, the current configuration of all replicas, the reference configuration, the cell (checked as a step checks it)
 struct RblEnsView {
   const double *X, *Q, *cfg;
   int R, Nb, nbl;
@@ -228,7 +229,6 @@ struct RblEnsView {
   RblSmallCell C;
   const RblEnsCellRec *cells;                 // a cell per replica: the table on the device (C is then unused); NULL: the shared cell C
 };
-int ens_state_refusals(rbl_ctx *c, const char *who);
 int ens_view(rbl_ctx *c, RblEnsView *v);
 // One launch of the probe kernel (include/rbl.h section 5, observers): u[R 3 P] of P points per replica from the blob forces lam
 // (replica r's at lam + r lam_stride) at the configuration (X, Q) of all R replicas.  pts_stride: 0 for one shared point set,
@@ -253,10 +253,94 @@ void ens_probe_launch(hipStream_t st, const RblParams &P, bool wall, const RblSm
 // a run's step, behind ens_probe_launch with rerr = d_oerr (R words, zero before the run's first step): rerr[r] = oerr[r] where
 // rerr[r] is still clear, oerr cleared again
 void ens_obs_flags_launch(hipStream_t st, unsigned *d_rerr, unsigned *d_oerr, int R);
-// The observers' share of a run's commit, one thread per entry of n = R per_rep: where replica r committed (*stopped == 0 and
-// vflag[r] == 0) last = step and sum += step; frame (may be NULL) = last
-void ens_obs_commit_launch(hipStream_t st, const int *d_stopped, const unsigned *d_vflag, const double *d_step, double *d_last,
-                           double *d_sum, double *d_frame, long per_rep, long n);
+
+// ---- rbl_ensemble.hip, as rbl_ens_run.hip reads it: what one step enqueues, and the checks a run makes before it ------------------
+// a bump allocator over one device buffer (256-byte aligned pieces; base NULL: only the sizes)
+struct RblCarve {
+  char *base; size_t off = 0;
+  template <class T> T *take(size_t count)
+  {
+    T *p = (T *)(base ? base + off : nullptr);
+    off += (sizeof(T) * count + 255) & ~(size_t)255;
+    return p;
+  }
+};
+struct EnsWork {
+  double *lever, *pos, *F, *FT, *slip, *W, *Lm, *Linv, *MW, *dq, *Xh, *Qh, *rhs, *x, *gm, *e;
+  double *jr;                                // the jointed step: the joint rows the caller gave (joint_rhs / joint_velocity), 3 n_joints per replica
+  void *ia;
+  // read-back block: residuals | iterations | error word per replica | one error word for the batch
+  double *resid; int *iters; unsigned *rerr, *gerr;
+  size_t rb_bytes;
+  // prescribed bodies: U and F of the masked solve follow the read-back block (rb_mx_bytes reaches their end) and stand in front
+  // of x in one piece [U | F | x], as the masked rbl_launch_gmres_small_ens wants them; body_in is uploaded where F_body goes (F)
+  double *U, *Fo; unsigned char *mask;
+  size_t rb_mx_bytes;
+};
+// the jointed variant of a step (hard joints): the joint table on the device, coef = -gamma / dt of a time step, whether w.jr holds
+// joint rows the caller gave, and the caller's name for a refusal
+struct EnsJtStep { const char *who; RblEnsJoints T; double coef; bool have_jr; };
+// The observers of a run (rbl_ensemble_run_observed), as one step sees them: device pointers into the run's buffer.  P probe
+// points (sets: 1 shared set or R; body >= 0: offsets fixed in that body) whose field goes to u_step, and D_step (moments) for
+// the first moments of the step's lambda.  They travel with the step's inputs (EnsStepIn); nothing of them is context state
+struct EnsObs {
+  int P = 0, sets = 1, body = -1;
+  bool moments = false;
+  const double *pts = nullptr;
+  double *u_step = nullptr, *D_step = nullptr;
+  unsigned *oerr = nullptr;                 // the probe kernel's flags of the step, R words (k_ens_obs_flags passes them on and clears them)
+};
+// What one step reads.  A one-step call passes host arrays, which the enqueueing part uploads; a run (rbl_ensemble_run) has uploaded
+// them once: resident -- prescribed then only says that the step is the masked one (w.mask is filled), F_body is unused (w.F is
+// filled), slip is the run's device copy, W is NULL.  chol_err: the batched Cholesky's error stride (0: the batch word)
+struct EnsStepIn {
+  const EnsObs *obs = nullptr;              // a run with observers: evaluated on the step's lambda just before the update
+  const uint8_t *prescribed = nullptr;
+  int per = 1;                              // entries of prescribed per body: 1 (whole bodies) or 6 (velocity components)
+  const double *F_body = nullptr, *slip = nullptr, *W = nullptr;
+  bool resident = false;
+  int64_t chol_err = 0;
+  const int *accepted = nullptr;            // a run: the device counters of accepted steps, the field's clock (section 4)
+};
+int ens_work(rbl_ctx *c, int max_iter, EnsWork *w, int nj = -1);   // nj < 0: the joints of the active set, none when they are off
+// everything the deterministic / the stochastic step enqueues, from the uploads to the update (jt: the jointed solve or step)
+int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_iter, double rtol, bool move, const EnsJtStep *jt = nullptr);
+int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t seed, int split_rand, double delta, int max_iter,
+                   double rtol);
+int ens_upload_mask(rbl_ctx *c, const EnsWork &w, const uint8_t *prescribed, int per);
+int ens_jt_upload(rbl_ctx *c, RblEnsJoints *T);           // the joint table on the device, uploaded when stale
+// the two configuration buffers (c->ens_cur: the committed one) and, behind them, the reference configuration
+inline double *ens_X(rbl_ctx *c, int which) { return (double *)c->d_ens.p + (size_t)which * 7 * c->ens_R * c->ens_Nb; }
+inline double *ens_Q(rbl_ctx *c, int which) { return ens_X(c, which) + (size_t)3 * c->ens_R * c->ens_Nb; }
+inline double *ens_cfg(rbl_ctx *c) { return ens_X(c, 2); }
+// the state and solver checks; only ens_ready touches a device.  pre: the caller's name with ": " behind it, or nothing; ens_state_check:
+// no ensemble, a changed structure, a communicator
+bool ens_jt_active(const rbl_ctx *c);
+bool ens_cell_on(const rbl_ctx *c);
+int ens_cell_refuse(rbl_ctx *c, const char *who);
+int ens_flow_check(rbl_ctx *c);
+int ens_state_check(rbl_ctx *c, const std::string &pre, bool comm_last = false);
+int ens_ready(rbl_ctx *c);
+std::string ens_beyond(const std::string &pre = "");
+int ens_check_solver(rbl_ctx *c, int max_iter);
+int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *body_in, int max_iter, double rtol, int per = 1);
+int ens_jt_check(rbl_ctx *c, const char *who, const double *F_body, int max_iter, double rtol);
+
+// ---- rbl_ens_field.hip: the observers of a run as ens_run carries them, a part with the life cycle of the joints' and the drive's ----
+struct RblEnsObsRun {
+  const rbl_run_obs_opts *o = nullptr;
+  rbl_run_obs_out *out = nullptr;
+  EnsObs step;                                   // what every step of the run is handed (EnsStepIn::obs)
+  size_t nu = 0, nD = 0;                         // entries of u (R 3 P) and of D (R 9 N_bod, with moments)
+  // device: points | this step's u (step.u_step), the last accepted one, the sum | the same three of D | frames | flags (step.oerr)
+  double *u_last = nullptr, *u_sum = nullptr, *D_last = nullptr, *D_sum = nullptr, *fU = nullptr, *fD = nullptr;
+};
+size_t ens_obs_carve(RblEnsObsRun &O, void *base, int R, int Nb, size_t n_frames);   // as ens_drive_carve
+// the points go up once; last, sum and the flags start at zero
+int ens_obs_begin(rbl_ctx *c, RblEnsObsRun &O, void *base, int R, int Nb, size_t n_frames);
+// after the run's commit, once for u and once for D (frame < 0: a step that records none)
+void ens_obs_after(rbl_ctx *c, const RblEnsObsRun &O, int R, const int *d_stopped, const unsigned *d_vflag, long frame);
+int ens_obs_end(rbl_ctx *c, const RblEnsObsRun &O, size_t nfr);   // the read-back: the sums, the nfr frames the run completed
 
 // ---- rbl_ens_drive.hip --------------------------------------------------------------------------------------------
 // The drive of rbl_ensemble_run_driven (include/rbl.h section 5) as ens_run carries it through a run: the checked options with
@@ -275,7 +359,8 @@ struct RblEnsDriveRun {
 // the drive's own refusals, none needing a device (R == 0, no ensemble: the checks that need R are left to the underlying run's
 // RBL_ERR_STATE); *empty: no harmonic part, no phases, no lock-in.  Fills D's host side
 int ens_drive_check(rbl_ctx *c, const char *who, const rbl_run_drive_opts *d, int R, int Nb, bool *empty, RblEnsDriveRun *D);
-size_t ens_drive_bytes(const RblEnsDriveRun &D, int R, int Nb);
+// D's device pieces from base (NULL: none) -> their bytes
+size_t ens_drive_carve(RblEnsDriveRun &D, void *base, int R, int Nb);
 // A0 (host, [R 6 N_bod]) and the drive's arrays go up once, the sums start at zero
 int ens_drive_begin(rbl_ctx *c, RblEnsDriveRun &D, void *base, int R, int Nb, const double *A0);
 // k_ens_drive: the step's input of every replica into d_in, from the replicas' accepted counters and cycle positions

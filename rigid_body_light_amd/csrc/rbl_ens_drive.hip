@@ -14,7 +14,7 @@
 // Every entry of every sum belongs to one thread and is added to in step order, product and sum rounded one after the other: no
 // atomics on doubles, no scratch, two runs agree bitwise, replica r of R is the R = 1 run.  rbl_ensemble_drive_eval is
 // k_ens_drive alone with a read-back: the device's sincos is not the host's, so this is what a loop of one-step calls
-// reproduces a run with.  The run loop itself is ens_run's (rbl_ensemble.hip); nothing here is context state.
+// reproduces a run with.  The run loop itself is ens_run's (rbl_ens_run.hip); nothing here is context state.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -135,35 +135,7 @@ __global__ __launch_bounds__(DT) void k_ens_drive_commit(int R, int nb6, EnsDriv
   }
 }
 
-// a bump allocator over one device buffer (256-byte aligned pieces)
-struct Carve {
-  char *base; size_t off = 0;
-  template <class T> T *take(size_t count)
-  {
-    T *p = (T *)(base ? base + off : nullptr);
-    off += (sizeof(T) * count + 255) & ~(size_t)255;
-    return p;
-  }
-};
-
 size_t drive_sum_doubles(int R, int Nb) { return (size_t)R * (30 * (size_t)Nb + 5); }
-
-void drive_carve(RblEnsDriveRun &D, void *base, int R, int Nb, size_t *bytes)
-{
-  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, np = (size_t)D.o->n_phases;
-  Carve C{(char *)base};
-  D.A0 = C.take<double>(Rz * nb6);
-  D.C = C.take<double>(D.o->cos_amp ? (size_t)D.o->amp_sets * nb6 : 0);
-  D.S = C.take<double>(D.o->sin_amp ? (size_t)D.o->amp_sets * nb6 : 0);
-  D.P = C.take<double>(np ? np * (size_t)D.o->phase_sets * nb6 : 0);
-  D.om = C.take<double>(Rz); D.t0d = C.take<double>(Rz); D.cs_sn = C.take<double>(2 * Rz);
-  D.sums = C.take<double>(drive_sum_doubles(R, Nb));
-  D.t_end = C.take<double>(Rz);
-  D.cum_d = C.take<int>(np + 1); D.pos = C.take<int>(Rz);
-  if (!D.o->cos_amp) D.C = nullptr;
-  if (!D.o->sin_amp) D.S = nullptr;
-  *bytes = C.off;
-}
 
 // (R == 0, no ensemble: nothing to compare with)
 bool set_count_ok(int sets, int R, bool zero) { return !R || (zero && sets == 0) || sets == 1 || sets == R; }
@@ -245,19 +217,27 @@ int ens_drive_check(rbl_ctx *c, const char *who, const rbl_run_drive_opts *d, in
   return RBL_OK;
 }
 
-size_t ens_drive_bytes(const RblEnsDriveRun &D, int R, int Nb)
+size_t ens_drive_carve(RblEnsDriveRun &D, void *base, int R, int Nb)
 {
-  RblEnsDriveRun t = D;
-  size_t bytes = 0;
-  drive_carve(t, nullptr, R, Nb, &bytes);
-  return bytes;
+  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, np = (size_t)D.o->n_phases;
+  RblCarve C{(char *)base};
+  D.A0 = C.take<double>(Rz * nb6);
+  D.C = C.take<double>(D.o->cos_amp ? (size_t)D.o->amp_sets * nb6 : 0);
+  D.S = C.take<double>(D.o->sin_amp ? (size_t)D.o->amp_sets * nb6 : 0);
+  D.P = C.take<double>(np ? np * (size_t)D.o->phase_sets * nb6 : 0);
+  D.om = C.take<double>(Rz); D.t0d = C.take<double>(Rz); D.cs_sn = C.take<double>(2 * Rz);
+  D.sums = C.take<double>(drive_sum_doubles(R, Nb));
+  D.t_end = C.take<double>(Rz);
+  D.cum_d = C.take<int>(np + 1); D.pos = C.take<int>(Rz);
+  if (!D.o->cos_amp) D.C = nullptr;
+  if (!D.o->sin_amp) D.S = nullptr;
+  return C.off;
 }
 
 int ens_drive_begin(rbl_ctx *c, RblEnsDriveRun &D, void *base, int R, int Nb, const double *A0)
 {
   const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, np = (size_t)D.o->n_phases;
-  size_t bytes = 0;
-  drive_carve(D, base, R, Nb, &bytes);
+  ens_drive_carve(D, base, R, Nb);
   int rc;
   if ((rc = copy_h2d(c, D.A0, A0, sizeof(double) * Rz * nb6))) return rc;
   if (D.C && (rc = copy_h2d(c, D.C, D.o->cos_amp, sizeof(double) * (size_t)D.o->amp_sets * nb6))) return rc;
@@ -335,7 +315,7 @@ int rbl_ensemble_drive_eval(rbl_ctx *c, const rbl_run_drive_opts *d, const doubl
   if (!c) return RBL_ERR_ARG;
   if (!d || !base || !in_out) return rbl_fail(c, RBL_ERR_ARG, w + ": drive, base or in_out is NULL");
   int rc = need_params(c); if (rc) return rc;
-  if ((rc = ens_state_refusals(c, who))) return rc;
+  if ((rc = ens_state_check(c, w + ": "))) return rc;
   const int R = c->ens_R, Nb = c->ens_Nb;
   RblEnsDriveRun D;
   bool empty;
@@ -350,7 +330,7 @@ int rbl_ensemble_drive_eval(rbl_ctx *c, const rbl_run_drive_opts *d, const doubl
   }
   RblEnsView v;
   if ((rc = ens_view(c, &v))) return rc;
-  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, dbytes = ens_drive_bytes(D, R, Nb);
+  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, dbytes = ens_drive_carve(D, nullptr, R, Nb);
   if ((rc = rbl_dev_reserve(c, c->d_ens_obs, dbytes + sizeof(double) * Rz * nb6 + sizeof(int) * Rz))) return rc;
   double *d_in = (double *)((char *)c->d_ens_obs.p + dbytes);
   int *d_acc = (int *)(d_in + Rz * nb6);

@@ -18,7 +18,7 @@
 //   k_ens_obs_flags              one thread per replica, behind the probe kernel in a run: its flags enter the replica's error word
 //                                only where the step has not failed already
 //   k_ens_obs_commit             one thread per entry, after k_ens_commit: where the replica committed, sum += step and
-//                                last = step; the frame slot takes last (frame_F's convention, rbl_ensemble.hip)
+//                                last = step; the frame slot takes last (frame_F's convention, rbl_ens_run.hip)
 //
 // A point's sum does not depend on NI, on the workgroup's size or on R: replica r of R returns the bits of the R = 1 launch, and
 // two launches agree bitwise.  No atomics on doubles, no scratch.  Flags (a blob below the wall, a non-finite result) are ORed
@@ -215,7 +215,7 @@ int ep_check_args(rbl_ctx *c, const char *who, const double *points, int64_t n_p
   if (point_sets < 1) return rbl_fail(c, RBL_ERR_ARG, w + ": point_sets must be 1 or R");
   if (probe_body < -1) return rbl_fail(c, RBL_ERR_ARG, w + ": probe_body must be -1 (lab points) or a body index");
   int rc = need_params(c); if (rc) return rc;
-  if ((rc = ens_state_refusals(c, who))) return rc;
+  if ((rc = ens_state_check(c, std::string(who) + ": "))) return rc;
   if (point_sets != 1 && point_sets != c->ens_R)
     return rbl_fail(c, RBL_ERR_ARG, w + ": point_sets must be 1 or R = " + std::to_string(c->ens_R));
   if (probe_body >= c->ens_Nb)
@@ -295,12 +295,61 @@ void ens_obs_flags_launch(hipStream_t st, unsigned *d_rerr, unsigned *d_oerr, in
   hipLaunchKernelGGL(k_ens_obs_flags, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, d_rerr, d_oerr, R);
 }
 
-void ens_obs_commit_launch(hipStream_t st, const int *d_stopped, const unsigned *d_vflag, const double *d_step, double *d_last,
-                           double *d_sum, double *d_frame, long per_rep, long n)
+// ---- the observers as a part of a run (RblEnsObsRun): bytes, begin, after the commit, end ----------------------------------------
+size_t ens_obs_carve(RblEnsObsRun &O, void *base, int R, int Nb, size_t n_frames)
 {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_ens_obs_commit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_stopped, d_vflag, d_step, d_last, d_sum,
-                     d_frame, per_rep, n);
+  const size_t Rz = (size_t)R;
+  O.nu = Rz * 3 * (size_t)O.o->n_probes;
+  O.nD = O.o->moments ? Rz * 9 * (size_t)Nb : 0;
+  RblCarve C{(char *)base};
+  O.step.pts = C.take<double>(O.nu ? 3 * (size_t)O.o->n_probes * (size_t)O.o->point_sets : 0);
+  O.step.u_step = C.take<double>(O.nu); O.u_last = C.take<double>(O.nu); O.u_sum = C.take<double>(O.nu);
+  O.step.D_step = C.take<double>(O.nD); O.D_last = C.take<double>(O.nD); O.D_sum = C.take<double>(O.nD);
+  O.fU = C.take<double>(n_frames * O.nu); O.fD = C.take<double>(n_frames * O.nD);
+  O.step.oerr = C.take<unsigned>(O.nu ? Rz : 0);
+  return C.off;
+}
+
+int ens_obs_begin(rbl_ctx *c, RblEnsObsRun &O, void *base, int R, int Nb, size_t n_frames)
+{
+  ens_obs_carve(O, base, R, Nb, n_frames);
+  O.step.P = O.o->n_probes; O.step.sets = O.o->point_sets; O.step.body = O.o->probe_body; O.step.moments = O.o->moments != 0;
+  int rc;
+  if (O.nu) {
+    if ((rc = copy_h2d(c, (void *)O.step.pts, O.o->points, sizeof(double) * 3 * (size_t)O.o->n_probes * (size_t)O.o->point_sets))) return rc;
+    RBL_HIP(c, hipMemsetAsync(O.u_last, 0, sizeof(double) * O.nu, c->stream));
+    RBL_HIP(c, hipMemsetAsync(O.u_sum, 0, sizeof(double) * O.nu, c->stream));
+    RBL_HIP(c, hipMemsetAsync(O.step.oerr, 0, sizeof(unsigned) * (size_t)R, c->stream));
+  }
+  if (O.nD) {
+    RBL_HIP(c, hipMemsetAsync(O.D_last, 0, sizeof(double) * O.nD, c->stream));
+    RBL_HIP(c, hipMemsetAsync(O.D_sum, 0, sizeof(double) * O.nD, c->stream));
+  }
+  return RBL_OK;
+}
+
+// k_ens_obs_commit for u and for D, n = R per_rep entries each; frame >= 0: a recording step's slot
+void ens_obs_after(rbl_ctx *c, const RblEnsObsRun &O, int R, const int *d_stopped, const unsigned *d_vflag, long frame)
+{
+  auto commit = [&](const double *step, double *last, double *sum, double *frames, size_t n) {
+    if (n)
+      hipLaunchKernelGGL(k_ens_obs_commit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_stopped, d_vflag, step, last, sum,
+                         frame >= 0 ? frames + (size_t)frame * n : nullptr, (long)(n / (size_t)R), (long)n);
+  };
+  commit(O.step.u_step, O.u_last, O.u_sum, O.fU, O.nu);
+  commit(O.step.D_step, O.D_last, O.D_sum, O.fD, O.nD);
+}
+
+int ens_obs_end(rbl_ctx *c, const RblEnsObsRun &O, size_t nfr)
+{
+  rbl_run_obs_out *q = O.out;
+  int rc;
+  if (O.nu && q->u_sum && (rc = copy_d2h(c, q->u_sum, O.u_sum, sizeof(double) * O.nu))) return rc;
+  if (O.nD && q->D_sum && (rc = copy_d2h(c, q->D_sum, O.D_sum, sizeof(double) * O.nD))) return rc;
+  if (nfr && O.nu && (rc = copy_d2h(c, q->frame_u, O.fU, sizeof(double) * nfr * O.nu))) return rc;
+  if (nfr && O.nD && (rc = copy_d2h(c, q->frame_D, O.fD, sizeof(double) * nfr * O.nD))) return rc;
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  return RBL_OK;
 }
 
 // ---- C ABI (include/rbl.h section 5, observers) ---------------------------------------------------------------------
@@ -343,7 +392,7 @@ int rbl_ensemble_probe_info(const rbl_ctx *cc, int64_t n_points, int *ni, int *w
   rbl_ctx *c = const_cast<rbl_ctx *>(cc);
   if (!c) return RBL_ERR_ARG;
   if (n_points < 0) return rbl_fail(c, RBL_ERR_ARG, "ensemble_probe_info: n_points must be >= 0");
-  int rc = ens_state_refusals(c, "ensemble_probe_info"); if (rc) return rc;
+  int rc = ens_state_check(c, "ensemble_probe_info: "); if (rc) return rc;
   if ((rc = rbl_dev_init(c))) return rc;
   const RblEnsProbeGeom g = ens_probe_geometry(n_points, c->ens_R, c->n_cu);
   if (ni) *ni = g.NI;

@@ -37,34 +37,10 @@
 // by the solver.  U and F follow the error words in the ONE read-back.  A free body's arithmetic and its order are unchanged: with
 // nobody prescribed the configurations and iteration counts are bitwise those of the unmasked steps.
 //
-// A run (rbl_ensemble_run): n steps in one call.  Each step function is an enqueueing part (ens_enqueue_det / ens_enqueue_bd) and
-// a finish (ens_finish: the read-back, the host's verdict, the swap); the one-step calls are the two in a row.  A run uploads its
-// inputs once, enqueues the first part per step with them resident, and lets two kernels of its own stand where the finish stood:
-//   k_ens_verdict             per replica (one workgroup): its error word, and under the reject policy the wall check of q^{n+1};
-//                             one compare-and-swap latches the step that stops the run
-//   k_ens_commit              per replica, a second launch (so `stopped` is final without any wait between workgroups): commit, or
-//                             q^n copied into the new buffer; counters, sums over accepted steps, the frame
-// The host swaps the two configuration buffers after every step without a synchronisation and reads back once at the end.
-// With hard joints (rbl_ensemble_run_jointed): the same loop around the jointed step (ens_enqueue_det with an EnsJtStep, the
-// enqueueing part of rbl_ensemble_step_jointed), and one more small launch per step after the commit:
-//   k_ens_jt_run              per replica and joint: theta += rate dt where the replica committed, its position in the motor
-//                             schedule, the sum of phi, the next step's rates into the joint table; the frame's theta and phi
-// (k_ens_jt_rates before the first step; k_ens_jt_geom for the gaps of a recording step).
-//
-// With observers (rbl_ensemble_run_observed; the kernels are in rbl_ens_field.hip): the same loop, and just before k_ens_evolve of
-// every step -- on the step's lambda, the top of every replica's x, at the configuration the solve was taken at --
-//   k_first_moments           (moments) the step's D of every body into the run's buffer
-//   k_ens_probe               (n_probes > 0) the fluid velocity at the probe points of every replica, its flags into words of its own
-//   k_ens_obs_flags           (n_probes > 0) per replica: those flags into rerr, unless the replica's step has failed already
-// and after the commit, once per quantity,
-//   k_ens_obs_commit          per entry: sum += step and last = step where the replica committed; the frame takes last
-// The observers are an argument (EnsObs in EnsStepIn), never context state: without them nothing here launches anything else.
-//
-// With a drive (rbl_ensemble_run_driven; the kernels are in rbl_ens_drive.hip): the same loop with the body input evaluated per
-// replica before every step and followed up after the commit,
-//   k_ens_drive               before the step's sequence: the step's F_body / body_in into EnsWork::F, which the sequence reads as ever
-//   k_ens_drive_commit        after the commit (and the observers'): cycle positions, the lock-in sums
-// The drive is an argument (RblEnsDriveRun): an empty one is the underlying call itself.
+// Each step function is an enqueueing part (ens_enqueue_det / ens_enqueue_bd) and a finish (ens_finish: the read-back, the host's
+// verdict, the swap); the one-step calls are the two in a row.  A run of n steps in one call (rbl_ensemble_run and its jointed,
+// observed and driven forms) is rbl_ens_run.hip: it enqueues the first part per step with the inputs resident, and its observers
+// reach a step as an argument (EnsObs in EnsStepIn), never as context state: without them nothing here launches anything else.
 //
 // In a periodic cell (rbl_ensemble_set_periodic; the cell's state and checks are in rbl_periodic.hip): the same launches with the
 // cell's instantiations -- k_gmres_small_per (rbl_small_per.hip) and k_ens_rfd_rhs<true, true> (the image sum inside rbl_small_pair_sweep),
@@ -82,7 +58,6 @@
 
 #include "rbl_api_internal.hpp"
 #include "rbl_body_dev.hpp"
-#include "rbl_schedule.hpp"
 #include "rbl_small_dev.hpp"
 
 namespace {
@@ -360,146 +335,22 @@ __global__ __launch_bounds__(ET) void k_ens_evolve(int nbod, int Nb, long nsys, 
   if (!ok) atomicOr(rerr + r, (unsigned)RBL_FLAG_NONFINITE);
 }
 
-// ---- a run of steps (rbl_ensemble_run): the verdict and the commit of every step, per replica, on the device ----------------
-// The few bytes the host polls.  stopped: 1 + the step that stopped the run (0: never; written once, by the first verdict that
-// finds a reason); stop_rep: R - r of the first failing replica r of that step (0: none, a batch-level failure); batch: the batch
-// word of that step
-struct EnsRunStatus { int stopped, stop_rep; unsigned batch; int pad; };
-
-// what the commit kernel reads and writes (device pointers; the frame slots are NULL in a step that records none)
-struct EnsRunDev {
-  const double *Xo, *Qo;                 // q^n
-  double *Xn, *Qn;                       // q^{n+1} as k_ens_evolve left it; q^n again where the replica does not commit
-  const unsigned *vflag, *gerr;
-  const int *iters; const double *resid;
-  const double *Fo;                      // the masked solve's loads (NULL: nobody prescribed)
-  EnsRunStatus *st;
-  int *accepted, *rejected; unsigned *first_flags; long long *iters_sum; double *resid_max, *F_sum, *F_last;
-  double *fX, *fQ; int *fA; double *fF;
-};
-
-// One workgroup per replica: the replica's verdict on step `step`, vflag[r] = its error word as the step's kernels left it and,
-// with reject, the validation of q^{n+1} (Xn, Qn) BEFORE it commits: a blob of the new configuration below the wall is
-// RBL_FLAG_BELOW_WALL, its height computed term for term as k_body_geom does (lever arm with contraction off, then + X), so this
-// is the verdict the next step's k_build_M or pair sweep would reach.  Non-finite components of Xn, Qn are in the word already
-// (k_ens_evolve).  Lanes that find something OR it into one LDS word.  Then the run-level decision: the batch word, or under
-// the stop policy any replica's word, stops the run at this step unless it stopped before -- one compare-and-swap, nobody waits
-template <bool WALL>
-__global__ __launch_bounds__(ET) void k_ens_verdict(int Nb, int nbl, int step, int reject, const double *__restrict__ Xn,
-                                                    const double *__restrict__ Qn, const double *__restrict__ cfg,
-                                                    const unsigned *__restrict__ rerr, const unsigned *__restrict__ gerr,
-                                                    unsigned *__restrict__ vflag, EnsRunStatus *st)
-{
-  __shared__ unsigned s_flags;
-  const int r = blockIdx.x, t = threadIdx.x;
-  if (t == 0) s_flags = rerr[r];
-  __syncthreads();
-  if (WALL && reject && t < Nb * nbl) {
-    const int b = t / nbl, k = t - b * nbl;
-    const size_t g = (size_t)r * Nb + b;
-    double Rm[9];
-    rbl_quat_rot9(Qn + 4 * g, Rm);
-    const double c0 = cfg[3 * k], c1 = cfg[3 * k + 1], c2 = cfg[3 * k + 2];
-    double p2;
-    {
-#pragma clang fp contract(off)
-      const double l2 = c0 * Rm[6] + c1 * Rm[7] + c2 * Rm[8];
-      p2 = l2 + Xn[3 * g + 2];
-    }
-    if (p2 < 0.0) atomicOr(&s_flags, (unsigned)RBL_FLAG_BELOW_WALL);
-  }
-  __syncthreads();
-  if (t == 0) {
-    const unsigned f = s_flags;
-    vflag[r] = f;
-    if (gerr[0] || (!reject && f)) atomicCAS(&st->stopped, 0, step + 1);
-  }
-}
-
-// One workgroup per replica, after k_ens_verdict has finished for all of them (st->stopped is final for this step): the replica
-// commits when the run has not stopped and its word is clear; otherwise q^n is copied into the new buffer, which the host
-// makes the current one without looking.  Counters, the sums over accepted steps and the frame follow the same decision; every
-// entry of F_sum is added to by one thread, in step order.  Nothing counts after the stopping step
-__global__ __launch_bounds__(ET) void k_ens_commit(int R, int Nb, int step, EnsRunDev D)
-{
-  const int r = blockIdx.x, t = threadIdx.x;
-  const int stopped = D.st->stopped;
-  const unsigned f = D.vflag[r];
-  const bool ok = stopped == 0 && f == 0;
-  const int acc = D.accepted[r] + (ok ? 1 : 0);
-  __syncthreads();                                     // every thread has read accepted[r]
-  if (t == 0) {
-    if (ok) {
-      D.accepted[r] = acc;
-      D.iters_sum[r] += D.iters[r];
-      if (D.resid[r] > D.resid_max[r]) D.resid_max[r] = D.resid[r];
-    } else if (f && (stopped == 0 || stopped == step + 1)) {
-      if (D.rejected[r] == 0) D.first_flags[r] = f;
-      D.rejected[r] += 1;
-    }
-    if (stopped == step + 1) {                         // the stopping step names its first failing replica and keeps the batch word
-      if (f) atomicMax(&D.st->stop_rep, R - r);
-      if (r == 0) D.st->batch = D.gerr[0];
-    }
-    if (D.fA) D.fA[r] = acc;
-  }
-  const int nx = 3 * Nb, nq = 4 * Nb, nf = 6 * Nb;
-  for (int j = t; j < nx; j += ET) {
-    const size_t i = (size_t)r * nx + j;
-    double v = D.Xn[i];
-    if (!ok) { v = D.Xo[i]; D.Xn[i] = v; }
-    if (D.fX) D.fX[i] = v;
-  }
-  for (int j = t; j < nq; j += ET) {
-    const size_t i = (size_t)r * nq + j;
-    double v = D.Qn[i];
-    if (!ok) { v = D.Qo[i]; D.Qn[i] = v; }
-    if (D.fQ) D.fQ[i] = v;
-  }
-  if (D.Fo)
-    for (int j = t; j < nf; j += ET) {
-      const size_t i = (size_t)r * nf + j;
-      double v = D.F_last[i];
-      if (ok) { v = D.Fo[i]; D.F_last[i] = v; D.F_sum[i] += v; }
-      if (D.fF) D.fF[i] = v;
-    }
-}
-
 size_t rfd_lds_bytes(int Nb, int nbl)
 {
   const size_t N = (size_t)Nb * nbl;
   return sizeof(double) * (13 * N + 7 * (size_t)Nb + (size_t)EW * 3 * N);
 }
 
-// a bump allocator over one device buffer (256-byte aligned pieces)
-struct Carve {
-  char *base; size_t off = 0;
-  template <class T> T *take(size_t count)
-  {
-    T *p = (T *)(base ? base + off : nullptr);
-    off += (sizeof(T) * count + 255) & ~(size_t)255;
-    return p;
-  }
-};
+}  // namespace
 
-struct EnsWork {
-  double *lever, *pos, *F, *FT, *slip, *W, *Lm, *Linv, *MW, *dq, *Xh, *Qh, *rhs, *x, *gm, *e;
-  double *jr;                                // the jointed step: the joint rows the caller gave (joint_rhs / joint_velocity), 3 n_joints per replica
-  void *ia;
-  // read-back block: residuals | iterations | error word per replica | one error word for the batch
-  double *resid; int *iters; unsigned *rerr, *gerr;
-  size_t rb_bytes;
-  // prescribed bodies: U and F of the masked solve follow the read-back block (rb_mx_bytes reaches their end) and stand in front
-  // of x in one piece [U | F | x], as the masked rbl_launch_gmres_small_ens wants them; body_in is uploaded where F_body goes (F)
-  double *U, *Fo; unsigned char *mask;
-  size_t rb_mx_bytes;
-};
+// ---- the host side.  What rbl_ens_run.hip calls is declared in rbl_api_internal.hpp (EnsWork, EnsStepIn, EnsJtStep, the enqueueing
+// parts, the state and solver checks); everything else is static ----------------------------------------------------------------------
 
 // nj: the joints of a jointed solve, whose rhs, x and solver workspace hold 3 nj more per replica (0: the sizes of the unjointed one)
-EnsWork ens_carve(void *base, int R, int Nb, int nbl, int max_iter, int nj, size_t *bytes)
+static EnsWork ens_carve(void *base, int R, int Nb, int nbl, int max_iter, int nj, size_t *bytes)
 {
   const size_t N = (size_t)Nb * nbl, n3 = 3 * N, nb6 = 6 * (size_t)Nb, nsys = n3 + nb6 + 3 * (size_t)nj, Rz = (size_t)R;
-  Carve C{(char *)base};
+  RblCarve C{(char *)base};
   EnsWork w;
   w.resid = C.take<double>(Rz);                        // the read-back block first, contiguous
   w.iters = C.take<int>(Rz);
@@ -531,19 +382,19 @@ EnsWork ens_carve(void *base, int R, int Nb, int nbl, int max_iter, int nj, size
 int ens_flow_check(rbl_ctx *c) { return c->ens_R ? flow_check(c, c->ens_Nb) : RBL_OK; }
 
 // pre: the caller's name with ": " behind it, or nothing
-int ens_fail_state(rbl_ctx *c, const std::string &pre = "")
+static int ens_fail_state(rbl_ctx *c, const std::string &pre = "")
 {
   return rbl_fail(c, RBL_ERR_STATE, pre + "ensemble: no ensemble configuration (rbl_ensemble_set_config)");
 }
 
-std::string ens_beyond(const std::string &pre = "")
+std::string ens_beyond(const std::string &pre)
 {
   return pre + "ensemble step: the system is beyond the one-kernel solver (<= 256 blobs, <= 64 bodies, max_iter <= 255)";
 }
 
 // the refusals that look at the context's state alone, before any device work: a communicator, no ensemble, a structure changed
 // since.  comm_last: ens_ready's order, which looks for the ensemble first
-int ens_state_check(rbl_ctx *c, const std::string &pre, bool comm_last = false)
+int ens_state_check(rbl_ctx *c, const std::string &pre, bool comm_last)
 {
   auto comm = [&] { return rbl_fail(c, RBL_ERR_ARG, pre + "ensemble: not on a context with a communicator (run one ensemble per process)"); };
   if (comm_on(c) && !comm_last) return comm();
@@ -554,10 +405,10 @@ int ens_state_check(rbl_ctx *c, const std::string &pre, bool comm_last = false)
 
 // the ensemble's periodic cell (rbl_ensemble_set_periodic; include/rbl.h section 5): on, and as the one-workgroup kernels take it
 bool ens_cell_on(const rbl_ctx *c) { return c->ens_per_on; }
-RblSmallCell ens_cell(const rbl_ctx *c) { return rbl_small_cell(c->S.a, c->ens_per_L, c->ens_per_n); }
+static RblSmallCell ens_cell(const rbl_ctx *c) { return rbl_small_cell(c->S.a, c->ens_per_L, c->ens_per_n); }
 // a cell per replica (rbl_ensemble_set_cells): the table on the device, R records -- NULL while the cell is the shared one, and
 // every launch that takes a cell then takes ens_cell(c) by value as it always did
-const RblEnsCellRec *ens_cell_table(const rbl_ctx *c)
+static const RblEnsCellRec *ens_cell_table(const rbl_ctx *c)
 {
   return ens_cells_stored(c) ? (const RblEnsCellRec *)c->d_ens_cells.p : nullptr;
 }
@@ -565,7 +416,7 @@ const RblEnsCellRec *ens_cell_table(const rbl_ctx *c)
 // what a step, a solve or the one-shot field asks of the ensemble's cell at use, before any device work: the wall term and lengths
 // the current parameters have not outgrown (periodic_use_check) -- replica by replica with a cell per replica, the first offending
 // one named --, then the table in the current parameters' units.  Nothing while the cell is off
-int ens_cell_use(rbl_ctx *c)
+static int ens_cell_use(rbl_ctx *c)
 {
   if (!ens_cell_on(c)) return RBL_OK;
   if (!ens_cells_stored(c)) return periodic_use_check(c, c->S.wall, c->ens_per_L, "rbl_ensemble_set_periodic");
@@ -582,10 +433,6 @@ int ens_cell_refuse(rbl_ctx *c, const char *who)
   return rbl_fail(c, RBL_ERR_STATE, std::string(who) + ": not offered with the ensemble's periodic cell (rbl_ensemble_set_periodic; switch the cell off first)");
 }
 
-double *ens_X(rbl_ctx *c, int which) { return (double *)c->d_ens.p + (size_t)which * 7 * c->ens_R * c->ens_Nb; }
-double *ens_Q(rbl_ctx *c, int which) { return ens_X(c, which) + (size_t)3 * c->ens_R * c->ens_Nb; }
-double *ens_cfg(rbl_ctx *c) { return ens_X(c, 2); }
-
 // parameters set, ensemble set for the current structure, single GPU; uploads the reference configuration when it changed
 int ens_ready(rbl_ctx *c)
 {
@@ -600,7 +447,7 @@ int ens_ready(rbl_ctx *c)
 }
 
 // the step's flags: the first failing replica names the error; nothing is committed unless every replica succeeded
-int ens_finish(rbl_ctx *c, const EnsWork &w, int R, int *iters, double *resid, bool commit, double *U = nullptr, double *F = nullptr)
+static int ens_finish(rbl_ctx *c, const EnsWork &w, int R, int *iters, double *resid, bool commit, double *U = nullptr, double *F = nullptr)
 {
   const size_t bytes = (U || F) ? w.rb_mx_bytes : w.rb_bytes;
   std::vector<char> h(bytes);
@@ -631,7 +478,7 @@ int ens_finish(rbl_ctx *c, const EnsWork &w, int R, int *iters, double *resid, b
 
 // ens_finish of a one-step call that returns pieces of the solution: x of every replica (3 N + 6 N_bod + nj3 each) is read back
 // in front of it and cut into whichever of lambda, U and phi (the nj3 joint rows) were asked for once the step has succeeded
-int ens_finish_x(rbl_ctx *c, const EnsWork &w, size_t nj3, int *iters, double *resid, bool commit, double *lambda, double *U, double *phi,
+static int ens_finish_x(rbl_ctx *c, const EnsWork &w, size_t nj3, int *iters, double *resid, bool commit, double *lambda, double *U, double *phi,
                  double *U_mx = nullptr, double *F_mx = nullptr)
 {
   const int R = c->ens_R;
@@ -658,7 +505,7 @@ int ens_finish_x(rbl_ctx *c, const EnsWork &w, size_t nj3, int *iters, double *r
 // takes: the caller's, the term, their sum, or NULL for zero.  resident (a run, rbl_ensemble_run): nothing is uploaded -- w.F
 // holds F_body since the run began and slip is the DEVICE copy made then, which the flow model's term is added to into w.slip
 // (never in place: the copy serves every step).  accepted (a run): the replicas' step counters, the clock of the magnetic field
-int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *slip, const double **FT, const double **SL,
+static int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *slip, const double **FT, const double **SL,
               bool model = true, bool resident = false, const int *accepted = nullptr)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
@@ -688,7 +535,7 @@ int ens_begin(rbl_ctx *c, const EnsWork &w, const double *F_body, const double *
 bool ens_jt_active(const rbl_ctx *c) { return c->jt_on && c->jt_n > 0; }
 
 // nj < 0: the joints of the active set, none when they are off
-int ens_work(rbl_ctx *c, int max_iter, EnsWork *w, int nj = -1)
+int ens_work(rbl_ctx *c, int max_iter, EnsWork *w, int nj)
 {
   if (nj < 0) nj = ens_jt_active(c) ? c->jt_n : 0;
   size_t bytes = 0;
@@ -706,26 +553,11 @@ int ens_check_solver(rbl_ctx *c, int max_iter)
   return RBL_OK;
 }
 
-// the jointed variant of a step (hard joints, further down): the joint table on the device, coef = -gamma / dt of a time step,
-// whether w.jr holds joint rows the caller gave, and the caller's name for a refusal
-struct EnsJtStep { const char *who; RblEnsJoints T; double coef; bool have_jr; };
-
-// The observers of a run (rbl_ensemble_run_observed), as one step sees them: device pointers into the run's buffer.  P probe
-// points (sets: 1 shared set or R; body >= 0: offsets fixed in that body) whose field goes to u_step, and D_step (moments) for
-// the first moments of the step's lambda.  They travel with the step's inputs (EnsStepIn); nothing of them is context state
-struct EnsObs {
-  int P = 0, sets = 1, body = -1;
-  bool moments = false;
-  const double *pts = nullptr;
-  double *u_step = nullptr, *D_step = nullptr;
-  unsigned *oerr = nullptr;                 // the probe kernel's flags of the step, R words (k_ens_obs_flags passes them on and clears them)
-};
-
 // The solve of every replica at (Xs, Qs) and the update from q^n: the one place that launches the one-kernel solver.  The variant
 // is chosen once -- mixed: the masked solve (w.mask, body_in in w.F); the update then reads the U it wrote (a prescribed body:
 // dt U_p exactly); the ensemble's cell on (the wall is: the callers' periodic_use_check): k_gmres_small_per; jt: the jointed
 // solve, rhs and x with the joint rows behind.  evolve = false: the solve alone
-int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const double *Qs, int max_iter, double rtol, bool mixed = false,
+static int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const double *Qs, int max_iter, double rtol, bool mixed = false,
                      bool evolve = true, bool record = true, int per = 1, const EnsJtStep *jt = nullptr, const EnsObs *obs = nullptr)
 {
   const int R = c->ens_R, Nb = c->ens_Nb, nbl = c->S.N_blb;
@@ -766,7 +598,7 @@ int ens_solve_evolve(rbl_ctx *c, const EnsWork &w, const double *Xs, const doubl
 
 // the checks of the entry points with prescribed bodies: none needs a device
 // per: mask entries per body, 1 (whole bodies) or 6 (velocity components, the _dof entry points)
-int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *body_in, int max_iter, double rtol, int per = 1)
+int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const double *body_in, int max_iter, double rtol, int per)
 {
   int rc = need_params(c); if (rc) return rc;
   const std::string w(who);
@@ -791,18 +623,6 @@ int ens_mx_check(rbl_ctx *c, const char *who, const uint8_t *prescribed, const d
 // rbl_ensemble_step_deterministic -- the unmasked solver, lambda, U and F NULL; otherwise body_in stands where F_body stands and
 // the solve is the masked one.  move = false: the solve alone, at the current configuration and without the model's loads
 // (rbl_ensemble_solve_mixed)
-// What one step reads.  A one-step call passes host arrays, which the enqueueing part uploads; a run (rbl_ensemble_run) has uploaded
-// them once: resident -- prescribed then only says that the step is the masked one (w.mask is filled), F_body is unused (w.F is
-// filled), slip is the run's device copy, W is NULL.  chol_err: the batched Cholesky's error stride (0: the batch word)
-struct EnsStepIn {
-  const EnsObs *obs = nullptr;              // a run with observers: evaluated on the step's lambda just before the update
-  const uint8_t *prescribed = nullptr;
-  int per = 1;                              // entries of prescribed per body: 1 (whole bodies) or 6 (velocity components)
-  const double *F_body = nullptr, *slip = nullptr, *W = nullptr;
-  bool resident = false;
-  int64_t chol_err = 0;
-  const int *accepted = nullptr;            // a run: the device counters of accepted steps, the field's clock (section 4)
-};
 
 // the mask as the caller gave it: per entries per body (the solver is told which, k_gmres_small's `per`)
 int ens_upload_mask(rbl_ctx *c, const EnsWork &w, const uint8_t *prescribed, int per)
@@ -812,7 +632,7 @@ int ens_upload_mask(rbl_ctx *c, const EnsWork &w, const uint8_t *prescribed, int
 
 // everything the deterministic step enqueues, from the uploads to the update: the one-step calls and the run share it
 // jt: the jointed solve or step (move: c of a time step is formed in the solver from the gaps)
-int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_iter, double rtol, bool move, const EnsJtStep *jt = nullptr)
+int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_iter, double rtol, bool move, const EnsJtStep *jt)
 {
   const bool mixed = in.prescribed != nullptr;
   const double *FT, *SL;
@@ -830,7 +650,7 @@ int ens_enqueue_det(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, int max_i
                           in.obs);
 }
 
-int ens_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, int max_iter, double rtol, bool move,
+static int ens_step_det(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, int max_iter, double rtol, bool move,
                  double *lambda, double *U, double *F, int *iters, double *resid, int per = 1)
 {
   const bool mixed = prescribed != nullptr;
@@ -909,7 +729,7 @@ int ens_enqueue_bd(rbl_ctx *c, const EnsWork &w, const EnsStepIn &in, uint64_t s
   return ens_solve_evolve(c, w, w.Xh, w.Qh, max_iter, rtol, mixed, true, !in.resident, in.per, nullptr, in.obs);
 }
 
-int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, const double *W, uint64_t seed,
+static int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, const double *slip, const double *W, uint64_t seed,
                 int split_rand, double delta, int max_iter, double rtol, double *F_out, int *iters, double *resid, int per = 1)
 {
   const bool mixed = prescribed != nullptr;
@@ -928,7 +748,7 @@ int ens_step_bd(rbl_ctx *c, const uint8_t *prescribed, const double *F_body, con
 // ---- the entry points with a mask: one worker per operation, per decided by the exported function (1: whole bodies, who's plain
 // name; 6: velocity components, the _dof name) -------------------------------------------------------------------------------------------
 
-int ens_mx_solve(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter,
+static int ens_mx_solve(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter,
                  double rtol, double *lambda, double *U, double *F, int *iters, double *resid)
 {
   if (!c) return RBL_ERR_ARG;
@@ -941,7 +761,7 @@ int ens_mx_solve(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed
   return ens_step_det(c, prescribed, body_in, slip, max_iter, rtol, false, lambda, U, F, iters, resid, per);
 }
 
-int ens_mx_step(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter,
+static int ens_mx_step(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed, const double *body_in, const double *slip, int max_iter,
                 double rtol, double *F, int *iters, double *resid)
 {
   if (!c) return RBL_ERR_ARG;
@@ -954,7 +774,7 @@ int ens_mx_step(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed,
 
 // the Brownian step: the deterministic one's checks and launch sequence plus the predictor's masked kernel.  A mask per velocity
 // component must be in include/rbl.h section 7's admissible class, per replica
-int ens_mx_step_bd(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed, const double *body_in, const double *slip,
+static int ens_mx_step_bd(rbl_ctx *c, const char *who, int per, const uint8_t *prescribed, const double *body_in, const double *slip,
                    const double *W, uint64_t seed, int split_rand, double delta, int max_iter, double rtol, double *F, int *iters,
                    double *resid)
 {
@@ -977,7 +797,7 @@ int ens_mx_step_bd(rbl_ctx *c, const char *who, int per, const uint8_t *prescrib
 
 // angles and rates of the stored set for the ensemble's R replicas of N_bod bodies: zeros, and the device table stale, when the
 // set, R or N_bod changed since they were made
-void ens_jt_sync(rbl_ctx *c)
+static void ens_jt_sync(rbl_ctx *c)
 {
   const size_t n = (size_t)c->ens_R * (size_t)c->jt_n;
   if (c->ens_jt_gen == c->jt_gen && c->ens_jt_R == c->ens_R && c->ens_jt_Nb == c->ens_Nb && c->ens_jt_theta.size() == n) return;
@@ -1058,7 +878,7 @@ int ens_jt_upload(rbl_ctx *c, RblEnsJoints *T)
 // the jointed solve of every replica at the current configuration; move: a time step -- the force model's loads and the flow
 // model's slip at q^n (ens_begin), c formed in the kernel from the gaps (coef = -gamma / dt), k_ens_evolve, and on success the
 // commit and the motors' angles.  What it enqueues is ens_enqueue_det's sequence with the jointed variant (EnsJtStep)
-int ens_jt_solve(rbl_ctx *c, const char *who, const double *F_body, const double *slip, const double *jr, bool move, double coef, int max_iter,
+static int ens_jt_solve(rbl_ctx *c, const char *who, const double *F_body, const double *slip, const double *jr, bool move, double coef, int max_iter,
                  double rtol, double *lambda, double *U, double *phi, int *iters, double *resid)
 {
   const size_t nj3 = (size_t)3 * c->jt_n, Rz = (size_t)c->ens_R;
@@ -1091,7 +911,7 @@ int ens_jt_solve(rbl_ctx *c, const char *who, const double *F_body, const double
 }
 
 // [sets n_joints] values, sets = 1 (every replica alike) or R, into the ensemble's [R n_joints]
-int ens_jt_set_values(rbl_ctx *c, const char *who, const double *v, int sets, bool rates)
+static int ens_jt_set_values(rbl_ctx *c, const char *who, const double *v, int sets, bool rates)
 {
   if (!c) return RBL_ERR_ARG;
   const std::string w(who);
@@ -1115,422 +935,6 @@ int ens_jt_set_values(rbl_ctx *c, const char *who, const double *v, int sets, bo
   return RBL_OK;
 }
 
-// ---- a run with hard joints (rbl_ensemble_run_jointed): ens_run's loop with the jointed step, and the joints' own launch ----
-// What moves during such a run besides the configurations lives on the device: the angles and rates in the joint table
-// (RblEnsJoints::theta / rate, which the solver and k_ens_jt_geom read per replica), every replica's position in the motor
-// schedule, the sums and the last accepted value of phi.
-
-// what k_ens_jt_run reads and writes (device pointers; the frame slots are NULL in a step that records none)
-struct EnsJtRunDev {
-  const EnsRunStatus *st; const unsigned *vflag;   // the run's status and this step's verdicts, as k_ens_commit read them
-  double *theta, *rate;                            // the joint table's [R n_joints] arrays
-  const double *x; long nsys, off;                 // this step's solutions: phi of replica r at x + r nsys + off
-  const int *pos_in; int *pos_out;                 // cycle positions [R], read and written: two buffers, since a replica's threads
-                                                   // may sit in two workgroups and nobody waits for anybody
-  const int *cum; const double *rates;             // the schedule: prefix sums (n_phases + 1), rates [n_phases rate_sets n_joints]
-  int n_phases, rate_sets;
-  double dt;
-  double *phi_sum, *phi_last;                      // [R 3 n_joints]
-  double *fT, *fP;                                 // the frame's theta [R n_joints] and phi [R 3 n_joints]
-};
-
-// the scheduled rate of joint j of replica r at cycle position p
-__device__ __forceinline__ double ens_jt_sched_rate(const int *cum, const double *rates, int n_phases, int rate_sets, int nj, int r, int j,
-                                                    int p)
-{
-  const int k = rbl_schedule_phase(cum, n_phases, p);
-  return rates[((size_t)k * rate_sets + (rate_sets == 1 ? 0 : r)) * nj + j];
-}
-
-// One thread per replica and joint, after k_ens_commit (st->stopped and vflag are final for this step): where the replica
-// committed, theta += rate dt with the product and the sum rounded one after the other and only where rate != 0 -- the statements
-// of the one-step call's host loop, so its bits --, the cycle position moves on by one and the step's phi is kept and added to
-// phi_sum (every entry by one thread, in step order).  Then, committed or not, the rates of the replica's next step go into the
-// table, and the frame is written: the angles as they stand, the last accepted phi
-__global__ __launch_bounds__(64) void k_ens_jt_run(int R, int nj, EnsJtRunDev D)
-{
-  const long g = (long)blockIdx.x * 64 + threadIdx.x;
-  if (g >= (long)R * nj) return;
-  const int r = (int)(g / nj), j = (int)(g - (long)r * nj);
-  const bool ok = D.st->stopped == 0 && D.vflag[r] == 0;
-  const size_t e = 3 * (size_t)g;
-  int p = D.n_phases ? D.pos_in[r] : 0;
-  double th = D.theta[g], ph[3] = {D.phi_last[e], D.phi_last[e + 1], D.phi_last[e + 2]};
-  if (ok) {
-    const double rate = D.rate[g];
-    if (rate != 0.0) {
-#pragma clang fp contract(off)
-      const double d = rate * D.dt;
-      th = th + d;
-      D.theta[g] = th;
-    }
-    if (D.n_phases) p = rbl_schedule_next(D.cum, D.n_phases, p);
-    const double *phi = D.x + (size_t)r * D.nsys + D.off + 3 * j;
-    for (int q = 0; q < 3; ++q) {
-      ph[q] = phi[q];
-      D.phi_last[e + q] = ph[q];
-      D.phi_sum[e + q] += ph[q];
-    }
-  }
-  if (D.n_phases) {
-    D.rate[g] = ens_jt_sched_rate(D.cum, D.rates, D.n_phases, D.rate_sets, nj, r, j, p);
-    if (j == 0) D.pos_out[r] = p;
-  }
-  if (D.fT) {
-    D.fT[g] = th;
-    for (int q = 0; q < 3; ++q) D.fP[e + q] = ph[q];
-  }
-}
-
-// before the first step: the rates of every replica's starting position into the table
-__global__ __launch_bounds__(64) void k_ens_jt_rates(int R, int nj, const int *__restrict__ pos, const int *__restrict__ cum,
-                                                     const double *__restrict__ rates, int n_phases, int rate_sets, double *__restrict__ rate)
-{
-  const long g = (long)blockIdx.x * 64 + threadIdx.x;
-  if (g >= (long)R * nj) return;
-  const int r = (int)(g / nj), j = (int)(g - (long)r * nj);
-  rate[g] = ens_jt_sched_rate(cum, rates, n_phases, rate_sets, nj, r, j, pos[r]);
-}
-
-struct EnsJtRun {
-  const rbl_run_joint_opts *o; rbl_run_joint_out *out;
-  std::vector<int> cum, start;                     // host: the prefix sums (n_phases + 1, or empty), the starting positions [R]
-  EnsJtStep step;                                  // the jointed variant of every step: the joint table, -gamma / dt
-  const double *x;                                 // the solutions of a step (EnsWork::x)
-  const EnsRunStatus *st; const unsigned *vflag;
-  int *pos[2]; int cur;                            // device: positions, which of the two is current
-  int *cum_d; double *rates_d, *phi_sum, *phi_last, *lev, *fT, *fP, *fG;
-};
-
-void ens_jt_run_carve(EnsJtRun &J, void *base, int R, int nj, size_t n_frames, size_t *bytes)
-{
-  const size_t Rn = (size_t)R * nj, np = (size_t)J.o->n_phases;
-  Carve C{(char *)base};
-  J.pos[0] = C.take<int>(R); J.pos[1] = C.take<int>(R);
-  J.cum_d = C.take<int>(np + 1);
-  J.rates_d = C.take<double>(np * (size_t)J.o->rate_sets * nj);
-  J.phi_sum = C.take<double>(6 * Rn);              // phi_sum | phi_last, cleared in one piece
-  J.phi_last = J.phi_sum ? J.phi_sum + 3 * Rn : nullptr;
-  J.lev = C.take<double>(6 * Rn);
-  J.fT = C.take<double>(n_frames * Rn); J.fP = C.take<double>(n_frames * 3 * Rn); J.fG = C.take<double>(n_frames * 3 * Rn);
-  *bytes = C.off;
-}
-
-size_t ens_jt_run_bytes(const rbl_ctx *c, const EnsJtRun &J, size_t n_frames)
-{
-  EnsJtRun t = J;
-  size_t bytes = 0;
-  ens_jt_run_carve(t, nullptr, c->ens_R, c->jt_n, n_frames, &bytes);
-  return bytes;
-}
-
-// the joint table (with the stored angles and rates), joint_velocity and the schedule go up, once; the first step's rates are
-// written.  From here on the device table is ahead of the host's copy: it is marked stale whatever follows.  st, vflag: the run's
-// status and verdict words
-int ens_jt_run_begin(rbl_ctx *c, EnsJtRun &J, void *base, size_t n_frames, const EnsWork &w, const EnsRunStatus *st, const unsigned *vflag)
-{
-  const int R = c->ens_R, nj = c->jt_n, np = J.o->n_phases;
-  const size_t Rn = (size_t)R * nj;
-  int rc;
-  if ((rc = ens_jt_upload(c, &J.step.T))) return rc;
-  size_t bytes = 0;
-  ens_jt_run_carve(J, base, R, nj, n_frames, &bytes);
-  J.st = st; J.vflag = vflag; J.x = w.x; J.cur = 0;
-  c->ens_jt_valid = false; c->ens_jt_phi_valid = false;
-  if (J.o->joint_velocity && (rc = copy_h2d(c, w.jr, J.o->joint_velocity, sizeof(double) * 3 * Rn))) return rc;
-  RBL_HIP(c, hipMemsetAsync(J.phi_sum, 0, sizeof(double) * 6 * Rn, c->stream));
-  if (np) {
-    if ((rc = copy_h2d(c, J.cum_d, J.cum.data(), sizeof(int) * ((size_t)np + 1)))) return rc;
-    if ((rc = copy_h2d(c, J.rates_d, J.o->phase_rates, sizeof(double) * (size_t)np * J.o->rate_sets * nj))) return rc;
-    if ((rc = copy_h2d(c, J.pos[0], J.start.data(), sizeof(int) * (size_t)R))) return rc;
-    hipLaunchKernelGGL(k_ens_jt_rates, dim3((unsigned)((Rn + 63) / 64)), dim3(64), 0, c->stream, R, nj, (const int *)J.pos[0],
-                       (const int *)J.cum_d, (const double *)J.rates_d, np, (int)J.o->rate_sets, (double *)J.step.T.rate);
-  }
-  return RBL_OK;
-}
-
-// after the step's commit and the host's flip: the joints' launch and, in a recording step (frame >= 0), the gaps at the committed
-// configuration and angles by k_ens_jt_geom itself
-void ens_jt_run_after(rbl_ctx *c, EnsJtRun &J, long frame)
-{
-  const int R = c->ens_R, Nb = c->ens_Nb, nj = c->jt_n, np = J.o->n_phases;
-  const size_t Rn = (size_t)R * nj, n3 = (size_t)3 * Nb * c->S.N_blb, nb6 = (size_t)6 * Nb;
-  EnsJtRunDev D;
-  D.st = J.st; D.vflag = J.vflag;
-  D.theta = (double *)J.step.T.theta; D.rate = (double *)J.step.T.rate;
-  D.x = J.x; D.nsys = (long)(n3 + nb6 + 3 * (size_t)nj); D.off = (long)(n3 + nb6);
-  D.pos_in = J.pos[J.cur]; D.pos_out = J.pos[J.cur ^ 1];
-  D.cum = J.cum_d; D.rates = J.rates_d; D.n_phases = np; D.rate_sets = J.o->rate_sets;
-  D.dt = c->S.dt;
-  D.phi_sum = J.phi_sum; D.phi_last = J.phi_last;
-  D.fT = D.fP = nullptr;
-  if (frame >= 0) { D.fT = J.fT + (size_t)frame * Rn; D.fP = J.fP + (size_t)frame * 3 * Rn; }
-  hipLaunchKernelGGL(k_ens_jt_run, dim3((unsigned)((Rn + 63) / 64)), dim3(64), 0, c->stream, R, nj, D);
-  if (np) J.cur ^= 1;
-  if (frame >= 0)
-    rbl_launch_ens_jt_geom(c->stream, ens_X(c, c->ens_cur), ens_Q(c, c->ens_cur), Nb, R, J.step.T, J.lev, J.fG + (size_t)frame * 3 * Rn);
-}
-
-// the joints' share of the read-back: the angles become the ensemble's, the last accepted phi the one rbl_ensemble_joint_state
-// returns (not after a stop: that phi is invalid, as after a failed step); nfr: the frames of the steps that were enqueued
-int ens_jt_run_end(rbl_ctx *c, EnsJtRun &J, size_t nfr, bool stopped)
-{
-  const int R = c->ens_R, nj = c->jt_n;
-  const size_t Rn = (size_t)R * nj;
-  rbl_run_joint_out *out = J.out;
-  int rc;
-  c->ens_jt_phi.resize(3 * Rn);
-  if ((rc = copy_d2h(c, c->ens_jt_theta.data(), J.step.T.theta, sizeof(double) * Rn))) return rc;
-  if ((rc = copy_d2h(c, c->ens_jt_phi.data(), J.phi_last, sizeof(double) * 3 * Rn))) return rc;
-  if (out->phi_sum && (rc = copy_d2h(c, out->phi_sum, J.phi_sum, sizeof(double) * 3 * Rn))) return rc;
-  if (out->cycle_pos) {
-    if (!J.o->n_phases) std::memset(out->cycle_pos, 0, sizeof(int32_t) * (size_t)R);
-    else if ((rc = copy_d2h(c, out->cycle_pos, J.pos[J.cur], sizeof(int32_t) * (size_t)R))) return rc;
-  }
-  if (nfr) {
-    if (out->frame_theta && (rc = copy_d2h(c, out->frame_theta, J.fT, sizeof(double) * nfr * Rn))) return rc;
-    if (out->frame_phi && (rc = copy_d2h(c, out->frame_phi, J.fP, sizeof(double) * nfr * 3 * Rn))) return rc;
-    if (out->frame_gap && (rc = copy_d2h(c, out->frame_gap, J.fG, sizeof(double) * nfr * 3 * Rn))) return rc;
-  }
-  RBL_HIP(c, hipStreamSynchronize(c->stream));
-  if (out->theta) std::memcpy(out->theta, c->ens_jt_theta.data(), sizeof(double) * Rn);
-  c->ens_jt_phi_valid = !stopped;
-  return RBL_OK;
-}
-
-// the run's own device buffer: [slip copy] | read-back block (status, counters, sums) | verdict words, last loads | frames
-struct EnsRunBuf {
-  double *slip;
-  EnsRunStatus *st; int *accepted, *rejected; unsigned *first_flags; long long *iters_sum; double *resid_max, *F_sum;
-  size_t rb_off, rb_bytes;                 // the read-back block: from st to the end of F_sum
-  unsigned *vflag; double *F_last;
-  double *fX, *fQ; int *fA; double *fF;
-  // the observers' part, behind everything else (nothing of it without them): points | this step's u, the last accepted one, the
-  // sum | the same three of D | frames
-  double *o_pts, *u_step, *u_last, *u_sum, *D_step, *D_last, *D_sum, *fU, *fD;
-  unsigned *o_err;                         // the probe kernel's flags of the current step
-};
-
-// what rbl_ensemble_run_observed hands to ens_run: its options and outputs (checked), NULL for a run without observers
-struct EnsRunObs { const rbl_run_obs_opts *o; rbl_run_obs_out *out; };
-
-EnsRunBuf ens_run_carve(void *base, int R, int Nb, int nbl, bool slip, bool mixed, size_t n_frames, size_t *bytes,
-                        const rbl_run_obs_opts *obs = nullptr)
-{
-  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, n3 = (size_t)3 * Nb * nbl;
-  Carve C{(char *)base};
-  EnsRunBuf b;
-  b.slip = C.take<double>(slip ? Rz * n3 : 0);
-  b.rb_off = C.off;
-  b.st = C.take<EnsRunStatus>(1);
-  b.accepted = C.take<int>(Rz); b.rejected = C.take<int>(Rz); b.first_flags = C.take<unsigned>(Rz);
-  b.iters_sum = C.take<long long>(Rz); b.resid_max = C.take<double>(Rz);
-  b.F_sum = C.take<double>(mixed ? Rz * nb6 : 0);
-  b.rb_bytes = C.off - b.rb_off;
-  b.vflag = C.take<unsigned>(Rz);
-  b.F_last = C.take<double>(mixed ? Rz * nb6 : 0);
-  b.fX = C.take<double>(n_frames * Rz * 3 * Nb); b.fQ = C.take<double>(n_frames * Rz * 4 * Nb);
-  b.fA = C.take<int>(n_frames * Rz);
-  b.fF = C.take<double>(mixed ? n_frames * Rz * nb6 : 0);
-  const size_t nu = obs ? Rz * 3 * (size_t)obs->n_probes : 0, nD = obs && obs->moments ? Rz * 9 * (size_t)Nb : 0;
-  b.o_pts = C.take<double>(nu ? 3 * (size_t)obs->n_probes * (size_t)obs->point_sets : 0);
-  b.u_step = C.take<double>(nu); b.u_last = C.take<double>(nu); b.u_sum = C.take<double>(nu);
-  b.D_step = C.take<double>(nD); b.D_last = C.take<double>(nD); b.D_sum = C.take<double>(nD);
-  b.fU = C.take<double>(n_frames * nu); b.fD = C.take<double>(n_frames * nD);
-  b.o_err = C.take<unsigned>(nu ? Rz : 0);
-  *bytes = C.off;
-  return b;
-}
-
-// n_steps steps of every replica (checks and ens_ready done by the caller; per: the mask's entries per body): the inputs go up
-// once, every step is the one-step calls' enqueue sequence followed by the verdict and the commit, the buffers flip on the host,
-// ONE read-back ends it.  J (rbl_ensemble_run_jointed): the step is the jointed one and one launch for the joints follows the commit
-int ens_run(rbl_ctx *c, const rbl_run_opts &o, int per, bool brownian, rbl_run_out *out, EnsJtRun *J, const EnsRunObs *ob = nullptr,
-            RblEnsDriveRun *dr = nullptr)
-{
-  const RblBodyState &S = c->S;
-  const bool mixed = o.prescribed != nullptr, reject = o.on_error == RBL_RUN_REJECT;
-  const int R = c->ens_R, Nb = c->ens_Nb, nbl = S.N_blb;
-  const size_t Rz = (size_t)R, nb6 = 6 * (size_t)Nb, n3 = (size_t)3 * Nb * nbl;
-  const size_t n_frames = o.stride > 0 ? (size_t)(o.n_steps / o.stride) : 0;
-  int rc;
-  EnsWork w;
-  if ((rc = ens_work(c, o.max_iter, &w))) return rc;
-  size_t bytes = 0;
-  const rbl_run_obs_opts *oo = ob ? ob->o : nullptr;
-  ens_run_carve(nullptr, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes, oo);
-  // the joints' part behind, or the drive's (never both: a drive with joints on is refused)
-  if ((rc = rbl_dev_reserve(c, c->d_ens_run, bytes + (J ? ens_jt_run_bytes(c, *J, n_frames) : dr ? ens_drive_bytes(*dr, R, Nb) : 0)))) return rc;
-  const EnsRunBuf b = ens_run_carve(c->d_ens_run.p, R, Nb, nbl, o.slip != nullptr, mixed, n_frames, &bytes, oo);
-  // the uploads, once
-  if (mixed && (rc = ens_upload_mask(c, w, o.prescribed, per))) return rc;
-  // (a driven run: the body input goes into the drive's own buffer, and k_ens_drive writes w.F before every step)
-  if (dr) { if ((rc = ens_drive_begin(c, *dr, (char *)c->d_ens_run.p + bytes, R, Nb, mixed ? o.body_in : o.F_body))) return rc; }
-  else if ((rc = copy_h2d(c, w.F, mixed ? o.body_in : o.F_body, sizeof(double) * nb6 * Rz))) return rc;
-  if (o.slip && (rc = copy_h2d(c, b.slip, o.slip, sizeof(double) * n3 * Rz))) return rc;
-  RBL_HIP(c, hipMemsetAsync(b.st, 0, b.rb_bytes, c->stream));
-  if (mixed) RBL_HIP(c, hipMemsetAsync(b.F_last, 0, sizeof(double) * nb6 * Rz, c->stream));
-  if (J && (rc = ens_jt_run_begin(c, *J, (char *)c->d_ens_run.p + bytes, n_frames, w, b.st, b.vflag))) return rc;
-  EnsObs obs;                                            // the observers: points up once, "last accepted" and the sums start at zero
-  const size_t nu = oo ? Rz * 3 * (size_t)oo->n_probes : 0, nD = oo && oo->moments ? Rz * 9 * (size_t)Nb : 0;
-  if (oo) {
-    obs.P = oo->n_probes; obs.sets = oo->point_sets; obs.body = oo->probe_body; obs.moments = oo->moments != 0;
-    obs.pts = b.o_pts; obs.u_step = b.u_step; obs.D_step = b.D_step; obs.oerr = b.o_err;
-    if (nu) {
-      if ((rc = copy_h2d(c, b.o_pts, oo->points, sizeof(double) * 3 * (size_t)oo->n_probes * (size_t)oo->point_sets))) return rc;
-      RBL_HIP(c, hipMemsetAsync(b.u_last, 0, sizeof(double) * nu, c->stream));
-      RBL_HIP(c, hipMemsetAsync(b.u_sum, 0, sizeof(double) * nu, c->stream));
-      RBL_HIP(c, hipMemsetAsync(b.o_err, 0, sizeof(unsigned) * Rz, c->stream));
-    }
-    if (nD) {
-      RBL_HIP(c, hipMemsetAsync(b.D_last, 0, sizeof(double) * nD, c->stream));
-      RBL_HIP(c, hipMemsetAsync(b.D_sum, 0, sizeof(double) * nD, c->stream));
-    }
-  }
-  EnsStepIn in;
-  in.obs = oo ? &obs : nullptr;
-  in.prescribed = o.prescribed; in.per = per;
-  in.slip = o.slip ? b.slip : nullptr; in.resident = true; in.chol_err = 1;
-  in.accepted = b.accepted;
-  EnsRunStatus hs = {0, 0, 0u, 0};
-  int enq = 0;
-  const auto verdict = S.wall ? k_ens_verdict<true> : k_ens_verdict<false>;
-  for (int n = 0; n < o.n_steps; ++n) {
-    if (dr) ens_drive_step(c, *dr, R, Nb, b.accepted, w.F);   // the step's body input, from the replicas' clocks and cycle positions
-    rc = brownian ? ens_enqueue_bd(c, w, in, o.seed + (uint64_t)n, o.split_rand, o.delta, o.max_iter, o.rtol)
-                  : ens_enqueue_det(c, w, in, o.max_iter, o.rtol, true, J ? &J->step : nullptr);
-    if (rc) return rc;
-    const int cur = c->ens_cur;
-    hipLaunchKernelGGL(verdict, dim3((unsigned)R), dim3(ET), 0, c->stream, Nb, nbl, n, reject ? 1 : 0,
-                       (const double *)ens_X(c, cur ^ 1), (const double *)ens_Q(c, cur ^ 1), (const double *)ens_cfg(c),
-                       (const unsigned *)w.rerr, (const unsigned *)w.gerr, b.vflag, b.st);
-    EnsRunDev D;
-    D.Xo = ens_X(c, cur); D.Qo = ens_Q(c, cur); D.Xn = ens_X(c, cur ^ 1); D.Qn = ens_Q(c, cur ^ 1);
-    D.vflag = b.vflag; D.gerr = w.gerr; D.iters = w.iters; D.resid = w.resid; D.Fo = mixed ? w.Fo : nullptr; D.st = b.st;
-    D.accepted = b.accepted; D.rejected = b.rejected; D.first_flags = b.first_flags; D.iters_sum = b.iters_sum;
-    D.resid_max = b.resid_max; D.F_sum = b.F_sum; D.F_last = b.F_last;
-    D.fX = D.fQ = D.fF = nullptr; D.fA = nullptr;
-    if (o.stride > 0 && (n + 1) % o.stride == 0) {
-      const size_t k = (size_t)((n + 1) / o.stride - 1);
-      D.fX = b.fX + k * Rz * 3 * Nb; D.fQ = b.fQ + k * Rz * 4 * Nb; D.fA = b.fA + k * Rz;
-      if (mixed) D.fF = b.fF + k * Rz * nb6;
-    }
-    hipLaunchKernelGGL(k_ens_commit, dim3((unsigned)R), dim3(ET), 0, c->stream, R, Nb, n, D);
-    if (oo) {                                            // the observers follow the commit's decision, replica by replica
-      const size_t k = D.fX ? (size_t)((n + 1) / o.stride - 1) : 0;
-      ens_obs_commit_launch(c->stream, &b.st->stopped, b.vflag, b.u_step, b.u_last, b.u_sum, D.fX ? b.fU + k * nu : nullptr,
-                            3L * oo->n_probes, (long)nu);
-      ens_obs_commit_launch(c->stream, &b.st->stopped, b.vflag, b.D_step, b.D_last, b.D_sum, D.fX ? b.fD + k * nD : nullptr, 9L * Nb,
-                            (long)nD);
-    }
-    if (dr)                                              // the drive follows it too: cycle positions, lock-in sums (q^n, the U the update read)
-      ens_drive_after(c, *dr, R, Nb, &b.st->stopped, b.vflag, b.accepted, D.Xo, mixed ? (const double *)w.U : (const double *)w.x + n3,
-                      mixed ? (long)nb6 : (long)(n3 + nb6), D.Fo);
-    c->ens_cur ^= 1;                                     // the new buffer holds every replica's configuration, moved or not
-    if (J) ens_jt_run_after(c, *J, D.fX ? (long)((n + 1) / o.stride - 1) : -1L);
-    ++enq;
-    if (o.check_every > 0 && enq % o.check_every == 0 && n + 1 < o.n_steps) {
-      if ((rc = read_back(c, &hs, b.st, sizeof(hs)))) return rc;
-      if (hs.stopped) break;
-    }
-  }
-  RBL_HIP(c, hipGetLastError());
-  // the one read-back: status, counters, sums; then the frames the run completed, straight into the caller's arrays
-  std::vector<char> h(b.rb_bytes);
-  if ((rc = copy_d2h(c, h.data(), b.st, b.rb_bytes))) return rc;
-  RBL_HIP(c, hipStreamSynchronize(c->stream));
-  auto at = [&](const void *p) { return h.data() + ((const char *)p - (const char *)b.st); };
-  std::memcpy(&hs, at(b.st), sizeof(hs));
-  const int *hacc = (const int *)at(b.accepted), *hrej = (const int *)at(b.rejected);
-  const unsigned *hff = (const unsigned *)at(b.first_flags);
-  if (out->accepted) std::memcpy(out->accepted, hacc, sizeof(int) * Rz);
-  if (out->rejected) std::memcpy(out->rejected, hrej, sizeof(int) * Rz);
-  if (out->first_flags) std::memcpy(out->first_flags, hff, sizeof(unsigned) * Rz);
-  if (out->first_status)
-    for (int r = 0; r < R; ++r) out->first_status[r] = hrej[r] ? rbl_flags_to_status(c, hff[r]) : RBL_OK;
-  if (out->iters_sum) std::memcpy(out->iters_sum, at(b.iters_sum), sizeof(int64_t) * Rz);
-  if (out->resid_max) std::memcpy(out->resid_max, at(b.resid_max), sizeof(double) * Rz);
-  if (mixed && out->F_sum) std::memcpy(out->F_sum, at(b.F_sum), sizeof(double) * nb6 * Rz);
-  const size_t nfr = o.stride > 0 ? (size_t)(enq / o.stride) : 0;   // frames of the steps that were enqueued (a polled stop: fewer)
-  if (nfr) {
-    if ((rc = copy_d2h(c, out->frame_X, b.fX, sizeof(double) * nfr * Rz * 3 * Nb))) return rc;
-    if ((rc = copy_d2h(c, out->frame_Q, b.fQ, sizeof(double) * nfr * Rz * 4 * Nb))) return rc;
-    if ((rc = copy_d2h(c, out->frame_accepted_at, b.fA, sizeof(int) * nfr * Rz))) return rc;
-    if (mixed && (rc = copy_d2h(c, out->frame_F, b.fF, sizeof(double) * nfr * Rz * nb6))) return rc;
-    RBL_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  if (oo) {
-    rbl_run_obs_out *q = ob->out;
-    if (nu && q->u_sum && (rc = copy_d2h(c, q->u_sum, b.u_sum, sizeof(double) * nu))) return rc;
-    if (nD && q->D_sum && (rc = copy_d2h(c, q->D_sum, b.D_sum, sizeof(double) * nD))) return rc;
-    if (nfr && nu && (rc = copy_d2h(c, q->frame_u, b.fU, sizeof(double) * nfr * nu))) return rc;
-    if (nfr && nD && (rc = copy_d2h(c, q->frame_D, b.fD, sizeof(double) * nfr * nD))) return rc;
-    RBL_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  if (J && (rc = ens_jt_run_end(c, *J, nfr, hs.stopped != 0))) return rc;
-  if (dr && (rc = ens_drive_end(c, *dr, R, Nb))) return rc;
-  out->stopped_at = hs.stopped ? hs.stopped - 1 : -1;
-  out->steps_done = hs.stopped ? hs.stopped - 1 : o.n_steps;
-  out->stop_replica = hs.stopped && hs.stop_rep ? R - hs.stop_rep : -1;
-  if (!hs.stopped) return RBL_OK;
-  const std::string at_step = "ensemble_run step " + std::to_string(hs.stopped - 1);
-  if (hs.stop_rep) {
-    rc = rbl_flags_to_status(c, hff[R - hs.stop_rep]);
-    c->last_error = at_step + ", replica " + std::to_string(R - hs.stop_rep) + ": " + c->last_error;
-  } else {
-    rc = rbl_flags_to_status(c, hs.batch);
-    c->last_error = at_step + ": " + c->last_error;
-  }
-  return rc;
-}
-
-// the schedule's own refusals (include/rbl.h section 5), none needing a device; fills J.cum and J.start
-int ens_jt_schedule_check(rbl_ctx *c, const char *who, const rbl_run_joint_opts &jo, EnsJtRun &J)
-{
-  const std::string w(who);
-  const int R = c->ens_R, nj = c->jt_n;
-  if (jo.n_phases < 0) return rbl_fail(c, RBL_ERR_ARG, w + ": n_phases must be >= 0");
-  if (jo.start_sets != 0 && jo.start_sets != 1 && jo.start_sets != R)
-    return rbl_fail(c, RBL_ERR_ARG, w + ": start_sets must be 0, 1 or R = " + std::to_string(R));
-  if (jo.start_sets && !jo.cycle_start) return rbl_fail(c, RBL_ERR_ARG, w + ": cycle_start is NULL while start_sets > 0");
-  J.cum.clear();
-  long long len = 0;
-  if (jo.n_phases) {
-    if (!ens_jt_active(c))
-      return rbl_fail(c, RBL_ERR_STATE, w + ": a motor schedule was given, but the joints are switched off or were never set (rbl_set_joint_kinds)");
-    if (!jo.phase_steps || !jo.phase_rates) return rbl_fail(c, RBL_ERR_ARG, w + ": phase_steps or phase_rates is NULL while n_phases > 0");
-    if (jo.rate_sets != 1 && jo.rate_sets != R) return rbl_fail(c, RBL_ERR_ARG, w + ": rate_sets must be 1 or R = " + std::to_string(R));
-    J.cum.push_back(0);
-    for (int k = 0; k < jo.n_phases; ++k) {
-      if (jo.phase_steps[k] < 1)
-        return rbl_fail(c, RBL_ERR_ARG, w + ": phase_steps[" + std::to_string(k) + "] = " + std::to_string(jo.phase_steps[k]) + ": every phase lasts at least one step");
-      len += jo.phase_steps[k];
-      if (len > 0x7fffffffLL) return rbl_fail(c, RBL_ERR_ARG, w + ": the cycle's length (the sum of phase_steps) must fit 31 bits");
-      J.cum.push_back((int)len);
-    }
-    for (int k = 0; k < jo.n_phases; ++k)
-      for (int s = 0; s < jo.rate_sets; ++s)
-        for (int j = 0; j < nj; ++j) {
-          const double x = jo.phase_rates[((size_t)k * jo.rate_sets + s) * nj + j];
-          const std::string at = w + ": phase " + std::to_string(k) + ", set " + std::to_string(s) + ", joint " + std::to_string(j) + ": ";
-          if (!std::isfinite(x)) return rbl_fail(c, RBL_ERR_ARG, at + "the value must be finite");
-          if (x != 0.0 && c->jt_kind[j] != RBL_JOINT_LOCK)
-            return rbl_fail(c, RBL_ERR_ARG, at + "only a lock joint (RBL_JOINT_LOCK) takes a rate; it must be 0 here");
-        }
-  }
-  J.start.assign((size_t)R, 0);
-  for (int s = 0; s < jo.start_sets; ++s) {
-    const long long p = jo.cycle_start[s];
-    if (p < 0 || p >= std::max(len, 1LL))
-      return rbl_fail(c, RBL_ERR_ARG, w + ": cycle_start[" + std::to_string(s) + "] = " + std::to_string(p) + " lies outside the cycle, 0 <= value < " +
-                                          std::to_string(std::max(len, 1LL)) + (len ? "" : " (no schedule: only 0)"));
-    if (jo.start_sets == 1) J.start.assign((size_t)R, (int)p);
-    else J.start[(size_t)s] = (int)p;
-  }
-  return RBL_OK;
-}
-
-}  // namespace
 
 // ---- C ABI (include/rbl.h section 5) --------------------------------------------------------------------------------
 
@@ -1675,191 +1079,7 @@ int rbl_ensemble_step_brownian_mixed_dof(rbl_ctx *c, const uint8_t *prescribed6,
                         iters, resid);
 }
 
-// rbl_ensemble_run, and rbl_ensemble_run_observed without joints (ob: its observers, checked there); dr: the drive of
-// rbl_ensemble_run_driven, checked there and not empty
-static int ens_run_plain(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out, const EnsRunObs *ob, RblEnsDriveRun *dr = nullptr)
-{
-  if (!c) return RBL_ERR_ARG;
-  if (!o || !out) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: opts or out is NULL");
-  if (o->size != (int64_t)sizeof(rbl_run_opts)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: opts.size is not sizeof(rbl_run_opts)");
-  if (out->size != (int64_t)sizeof(rbl_run_out)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: out.size is not sizeof(rbl_run_out)");
-  out->steps_done = 0; out->stopped_at = -1; out->stop_replica = -1; out->reserved = 0;   // what a refused call leaves
-  if (periodic_on(c)) return periodic_refuse(c, "ensemble_run");
-  if (o->n_steps < 1) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: n_steps must be >= 1");
-  if (o->stride < 0) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: stride must be >= 0");
-  if (o->check_every < 0) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: check_every must be >= 0");
-  if (o->on_error != RBL_RUN_STOP && o->on_error != RBL_RUN_REJECT)
-    return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: on_error must be RBL_RUN_STOP (0) or RBL_RUN_REJECT (1)");
-  if (o->prescribed_per != 0 && o->prescribed_per != 1 && o->prescribed_per != 6)
-    return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: prescribed_per must be 0 or 1 (a mask entry per body) or 6 (one per velocity component)");
-  const int per = o->prescribed_per == 6 ? 6 : 1;
-  const bool free_run = o->F_body != nullptr, masked = o->prescribed || o->body_in;
-  if (free_run == masked)
-    return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: give either F_body or prescribed with body_in (both or neither were given)");
-  if (masked && per == 6 && o->brownian && c->S.kBT > 1e-10)   // kBT <= 1e-10 runs the deterministic step, as elsewhere
-    return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: the Brownian step takes whole-body masks only (prescribed_per = 6 with brownian != 0 and "
-                                    "kBT > 1e-10): the drift term of a partly prescribed body has not been derived");
-  if (o->max_iter < 1) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: max_iter must be >= 1");
-  if (!(o->rtol >= 0.0)) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: rtol must be >= 0");
-  const size_t n_frames = o->stride > 0 ? (size_t)(o->n_steps / o->stride) : 0;
-  if (n_frames && (!out->frame_X || !out->frame_Q || !out->frame_accepted_at || (masked && !out->frame_F)))
-    return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: frame_X, frame_Q, frame_accepted_at (and frame_F with prescribed bodies) must not be NULL while stride > 0 records frames");
-  int rc;
-  if (masked) {                                        // NULL halves, max_iter > 255, communicator, state, entries, the LDS
-    if ((rc = ens_mx_check(c, "ensemble_run", o->prescribed, o->body_in, o->max_iter, o->rtol, per))) return rc;
-  } else {
-    if ((rc = need_params(c))) return rc;
-    if (o->max_iter > 255) return rbl_fail(c, RBL_ERR_SIZE, ens_beyond());
-    if ((rc = ens_state_check(c, ""))) return rc;
-    if ((rc = ens_check_solver(c, o->max_iter))) return rc;
-  }
-  const bool brownian = o->brownian && c->S.kBT > 1e-10;   // no Brownian terms (:967-970): the deterministic step
-  if (brownian && (!(c->S.dt > 0.0) || !(o->delta > 0.0))) return rbl_fail(c, RBL_ERR_ARG, "ensemble_run: dt and delta must be positive");
-  if ((rc = ens_flow_check(c))) return rc;
-  if ((rc = ens_ready(c))) return rc;
-  if (dr) dr->masked = masked;
-  return ens_run(c, *o, per, brownian, out, nullptr, ob, dr);
-}
-
-int rbl_ensemble_run(rbl_ctx *c, const rbl_run_opts *o, rbl_run_out *out) { return ens_run_plain(c, o, out, nullptr); }
-
-// n_steps jointed steps in one call: rbl_ensemble_step_jointed's checks and rbl_ensemble_run's, the schedule's own, then ens_run
-// with the jointed step; joints off or never set: rbl_ensemble_run's deterministic run itself
-static int ens_run_jointed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, rbl_run_out *out, rbl_run_joint_out *jout,
-                           const EnsRunObs *ob)
-{
-  const char *who = "ensemble_run_jointed";
-  const std::string w(who);
-  if (!c) return RBL_ERR_ARG;
-  if (!o || !jo || !out || !jout) return rbl_fail(c, RBL_ERR_ARG, w + ": opts, jopts, out or jout is NULL");
-  if (o->size != (int64_t)sizeof(rbl_run_opts)) return rbl_fail(c, RBL_ERR_ARG, w + ": opts.size is not sizeof(rbl_run_opts)");
-  if (jo->size != (int64_t)sizeof(rbl_run_joint_opts)) return rbl_fail(c, RBL_ERR_ARG, w + ": jopts.size is not sizeof(rbl_run_joint_opts)");
-  if (out->size != (int64_t)sizeof(rbl_run_out)) return rbl_fail(c, RBL_ERR_ARG, w + ": out.size is not sizeof(rbl_run_out)");
-  if (jout->size != (int64_t)sizeof(rbl_run_joint_out)) return rbl_fail(c, RBL_ERR_ARG, w + ": jout.size is not sizeof(rbl_run_joint_out)");
-  out->steps_done = 0; out->stopped_at = -1; out->stop_replica = -1; out->reserved = 0;   // what a refused call leaves
-  if (periodic_on(c)) return periodic_refuse(c, who);
-  if (ens_cell_on(c)) return ens_cell_refuse(c, who);
-  if (o->n_steps < 1) return rbl_fail(c, RBL_ERR_ARG, w + ": n_steps must be >= 1");
-  if (o->stride < 0) return rbl_fail(c, RBL_ERR_ARG, w + ": stride must be >= 0");
-  if (o->check_every < 0) return rbl_fail(c, RBL_ERR_ARG, w + ": check_every must be >= 0");
-  if (o->on_error != RBL_RUN_STOP && o->on_error != RBL_RUN_REJECT)
-    return rbl_fail(c, RBL_ERR_ARG, w + ": on_error must be RBL_RUN_STOP (0) or RBL_RUN_REJECT (1)");
-  if (o->prescribed || o->body_in)
-    return rbl_fail(c, RBL_ERR_ARG, w + ": prescribed and body_in must be NULL: joints together with prescribed masks are not offered");
-  if (o->prescribed_per != 0 && o->prescribed_per != 1)
-    return rbl_fail(c, RBL_ERR_ARG, w + ": prescribed_per must be 0 or 1: joints together with prescribed masks are not offered");
-  if (o->brownian && c->S.kBT > 1e-10)                   // kBT <= 1e-10: brownian is ignored, as in a plain run
-    return rbl_fail(c, RBL_ERR_ARG, w + ": brownian != 0 with kBT > 1e-10: Brownian jointed steps are not offered, the drift of a constrained "
-                                        "suspension has not been derived");
-  if (!(jo->gamma >= 0.0 && jo->gamma <= 1.0)) return rbl_fail(c, RBL_ERR_ARG, w + ": gamma must lie in [0, 1]");
-  const bool on = ens_jt_active(c);
-  if (on && !(c->S.dt > 0.0)) return rbl_fail(c, RBL_ERR_ARG, w + ": dt must be positive");
-  int rc = ens_jt_check(c, who, o->F_body, o->max_iter, o->rtol); if (rc) return rc;
-  const size_t n_frames = o->stride > 0 ? (size_t)(o->n_steps / o->stride) : 0;
-  if (n_frames && (!out->frame_X || !out->frame_Q || !out->frame_accepted_at))
-    return rbl_fail(c, RBL_ERR_ARG, w + ": frame_X, frame_Q and frame_accepted_at must not be NULL while stride > 0 records frames");
-  EnsJtRun J = {};
-  J.o = jo; J.out = jout;
-  if ((rc = ens_jt_schedule_check(c, who, *jo, J))) return rc;
-  rbl_run_opts od = *o;                                  // the deterministic run's options
-  od.brownian = 0; od.prescribed_per = 0;
-  if (!on) {
-    if ((rc = ens_run_plain(c, &od, out, ob)) && out->stopped_at < 0) return rc;
-    if (jout->cycle_pos) std::memset(jout->cycle_pos, 0, sizeof(int32_t) * (size_t)c->ens_R);
-    return rc;
-  }
-  if ((rc = ens_flow_check(c))) return rc;
-  if ((rc = ens_ready(c))) return rc;
-  J.step = {who, {}, -jo->gamma / c->S.dt, jo->joint_velocity != nullptr};
-  return ens_run(c, od, 1, false, out, &J, ob);
-}
-
-int rbl_ensemble_run_jointed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, rbl_run_out *out, rbl_run_joint_out *jout)
-{
-  return ens_run_jointed(c, o, jo, out, jout, nullptr);
-}
-
-// the observers' own refusals, none needing a device, then the underlying run with them (or without: nothing asked for)
-static int ens_run_observed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, const rbl_run_obs_opts *obs, rbl_run_out *out,
-                            rbl_run_joint_out *jout, rbl_run_obs_out *oout, RblEnsDriveRun *dr)
-{
-  const char *who = "ensemble_run_observed";
-  const std::string w(who);
-  if (!c) return RBL_ERR_ARG;
-  if (!obs || !oout) return rbl_fail(c, RBL_ERR_ARG, w + ": obs or oout is NULL");
-  if (obs->size != (int64_t)sizeof(rbl_run_obs_opts)) return rbl_fail(c, RBL_ERR_ARG, w + ": obs.size is not sizeof(rbl_run_obs_opts)");
-  if (oout->size != (int64_t)sizeof(rbl_run_obs_out)) return rbl_fail(c, RBL_ERR_ARG, w + ": oout.size is not sizeof(rbl_run_obs_out)");
-  if (obs->n_probes < 0) return rbl_fail(c, RBL_ERR_ARG, w + ": n_probes must be >= 0");
-  if (obs->n_probes > 0) {
-    if (!obs->points) return rbl_fail(c, RBL_ERR_ARG, w + ": points is NULL while n_probes > 0");
-    if (obs->point_sets < 1) return rbl_fail(c, RBL_ERR_ARG, w + ": point_sets must be 1 or R");
-    if (obs->probe_body < -1) return rbl_fail(c, RBL_ERR_ARG, w + ": probe_body must be -1 (lab points) or a body index");
-    if (c->ens_R) {                                      // (no ensemble: the underlying run's RBL_ERR_STATE, below)
-      if (obs->point_sets != 1 && obs->point_sets != c->ens_R)
-        return rbl_fail(c, RBL_ERR_ARG, w + ": point_sets must be 1 or R = " + std::to_string(c->ens_R));
-      if (obs->probe_body >= c->ens_Nb)
-        return rbl_fail(c, RBL_ERR_ARG, w + ": probe_body must be -1 (lab points) or a body index below N_bod = " + std::to_string(c->ens_Nb));
-    }
-    if (c->ens_R || obs->point_sets == 1) {              // (the sets are R sets or one: the array's length is known)
-      int rc = ens_points_check(c, who, obs->points, obs->n_probes, obs->point_sets); if (rc) return rc;
-    }
-  }
-  // (opts of another size are not read: the underlying run refuses them below)
-  const bool frames = o && o->size == (int64_t)sizeof(rbl_run_opts) && o->stride > 0 && o->n_steps / o->stride > 0;
-  if (frames && obs->n_probes > 0 && !oout->frame_u) return rbl_fail(c, RBL_ERR_ARG, w + ": frame_u must not be NULL while stride > 0 records frames of the probes");
-  if (frames && obs->moments && !oout->frame_D) return rbl_fail(c, RBL_ERR_ARG, w + ": frame_D must not be NULL while stride > 0 records frames of the moments");
-  const EnsRunObs ob = {obs, oout};
-  const EnsRunObs *pob = obs->n_probes > 0 || obs->moments ? &ob : nullptr;
-  return jo ? ens_run_jointed(c, o, jo, out, jout, pob) : ens_run_plain(c, o, out, pob, dr);
-}
-
-int rbl_ensemble_run_observed(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_joint_opts *jo, const rbl_run_obs_opts *obs, rbl_run_out *out,
-                              rbl_run_joint_out *jout, rbl_run_obs_out *oout)
-{
-  return ens_run_observed(c, o, jo, obs, out, jout, oout, nullptr);
-}
-
-// the drive's own refusals (ens_drive_check, rbl_ens_drive.hip), none needing a device; then the underlying run -- with the drive
-// carried through ens_run, or, the drive empty, the very call of rbl_ensemble_run / rbl_ensemble_run_observed
-int rbl_ensemble_run_driven(rbl_ctx *c, const rbl_run_opts *o, const rbl_run_drive_opts *drive, const rbl_run_obs_opts *obs, rbl_run_out *out,
-                            rbl_run_drive_out *dout, rbl_run_obs_out *oout)
-{
-  const char *who = "ensemble_run_driven";
-  const std::string w(who);
-  if (!c) return RBL_ERR_ARG;
-  RblEnsDriveRun D;
-  bool empty = true;
-  if (dout && dout->size != (int64_t)sizeof(rbl_run_drive_out)) return rbl_fail(c, RBL_ERR_ARG, w + ": dout.size is not sizeof(rbl_run_drive_out)");
-  if (drive) {
-    int rc = ens_drive_check(c, who, drive, c->ens_R, c->ens_Nb, &empty, &D); if (rc) return rc;
-    if (!empty && !dout) return rbl_fail(c, RBL_ERR_ARG, w + ": dout is NULL while a drive is given");
-    if (!empty && ens_jt_active(c))
-      return rbl_fail(c, RBL_ERR_STATE, w + ": hard joints are switched on: a drive together with joints is not offered (run_jointed takes no "
-                                            "drive; switch the joints off, or run without a drive)");
-  }
-  D.out = dout;
-  if (!empty) return obs ? ens_run_observed(c, o, nullptr, obs, out, nullptr, oout, &D) : ens_run_plain(c, o, out, nullptr, &D);
-  // nothing drives: the underlying run itself.  Its accepted counts give t_end; the caller may not have asked for them
-  std::vector<int32_t> acc;
-  rbl_run_out oq;
-  const bool want = drive && dout && c->ens_R && out && out->size == (int64_t)sizeof(rbl_run_out);
-  if (want) {
-    oq = *out;
-    if (!oq.accepted) { acc.assign((size_t)c->ens_R, 0); oq.accepted = acc.data(); }
-  }
-  rbl_run_out *po = want ? &oq : out;
-  const int R0 = c->ens_R;
-  int rc = obs ? rbl_ensemble_run_observed(c, o, nullptr, obs, po, nullptr, oout) : rbl_ensemble_run(c, o, po);
-  if (want) {
-    out->steps_done = oq.steps_done; out->stopped_at = oq.stopped_at; out->stop_replica = oq.stop_replica; out->reserved = oq.reserved;
-    if ((rc == RBL_OK || oq.stopped_at >= 0) && !D.t0.empty()) ens_drive_empty_out(c, D, R0, oq.accepted);
-  }
-  return rc;
-}
-
 // ---- what rbl_ens_field.hip reads of the ensemble (rbl_api_internal.hpp) --------------------------------------------
-int ens_state_refusals(rbl_ctx *c, const char *who) { return ens_state_check(c, std::string(who) + ": "); }
-
 int ens_view(rbl_ctx *c, RblEnsView *v)
 {
   int rc = ens_ready(c); if (rc) return rc;
@@ -1870,17 +1090,6 @@ int ens_view(rbl_ctx *c, RblEnsView *v)
   v->X = ens_X(c, c->ens_cur); v->Q = ens_Q(c, c->ens_cur); v->cfg = ens_cfg(c);
   v->R = c->ens_R; v->Nb = c->ens_Nb; v->nbl = c->S.N_blb;
   return RBL_OK;
-}
-
-int rbl_run_schedule_phase(const int32_t *phase_steps, int n_phases, int64_t pos)
-{
-  if (!phase_steps || n_phases < 1 || pos < 0) return -1;
-  std::vector<int> cum(1, 0);
-  for (int k = 0; k < n_phases; ++k) {
-    if (phase_steps[k] < 1 || (int64_t)cum.back() + phase_steps[k] > 0x7fffffffLL) return -1;
-    cum.push_back(cum.back() + phase_steps[k]);
-  }
-  return pos < cum.back() ? rbl_schedule_phase(cum.data(), n_phases, (int)pos) : -1;
 }
 
 int rbl_ensemble_interaction_forces(rbl_ctx *c, double *FT_body, double *energy)
