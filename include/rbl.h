@@ -621,6 +621,24 @@ int rbl_option_key(const char *name);
  * rbl_get_bonds takes NULL for what is not wanted.  rbl_bond_state / rbl_ensemble_bond_state: length d, tension dU/dd and
  * energy U of every stored bond (on or off) at the context's / every replica's configuration, n_bonds / R n_bonds doubles
  * each (replica-major), host arrays, any may be NULL; synchronous.  RBL_ERR_STATE before any bonds were set.
+ * Blob types with one pair table per unordered type pair (their own switch, nothing changes while they are off): every blob
+ * carries a type in [0, n_types), 1 <= n_types <= 8, and the pair of types (s, t) may own a TYPE TABLE T_st = T_ts with the
+ * construction, limits and coefficient layout of the pair table.  For blobs i (type s) and j (type t) of DIFFERENT bodies of
+ * one system with r <= r_cut(s, t), and T_st set and on, the pair gets T_st(r) IN ADDITION to the built-in steric term and the
+ * untyped pair table; each of the three keeps its own cutoff, a type pair without a table adds nothing, r = 0 exerts no force
+ * and each blob carries half of a pair's energy.  The term enters f_blob.  A type on a patch of a body's surface makes a pair
+ * potential depend on the bodies' orientations without any angular term (Janus and patchy particles, sticky caps, selective
+ * binding).  In a periodic cell (section 10) the largest type cutoff that is on joins r_cut of the cell's check.
+ * rbl_set_blob_types: type[n], n = N_blb (every body alike: blob k of any body has type[k]) or N_bod N_blb (one entry per
+ * blob of the system, body-major; in an ensemble the system of ONE replica, shared by all replicas: body i reads row
+ * i % N_bod).  An n that fits neither is found when the model is evaluated with the term active (RBL_ERR_STATE).  RBL_ERR_ARG,
+ * the previous types in place: type = NULL with on != 0, n < 1, n_types outside [1, 8], a value outside [0, n_types) (the
+ * message names the first offending index and its value).  type = NULL with on = 0 only switches the stored types off.
+ * rbl_set_type_table(ta, tb, ...): the arguments and refusals of rbl_set_pair_table for the table of the unordered pair
+ * (ta, tb) -- (tb, ta) names the same table --, and ta or tb outside [0, 8): RBL_ERR_ARG.  A table whose type is >= the current
+ * n_types is stored and ignored.  rbl_clear_type_tables forgets every type table (the types stay).  Bit 7 of
+ * rbl_interactions_active: types on and at least one table on whose two types are < n_types; only then is the term evaluated.
+ * The cap of 8 types: the 36 table descriptors of 64 bytes sit in LDS beside the pair kernel's 16 KB position chunk.
  * Body force / torque about the body centre = K^T f_blob (+ the traps, the dipole pairs, the field torque and the bonds).  The
  * evaluation is deterministic (ordered pairs, no atomics): the same configuration gives bitwise the same forces on every
  * call and every rank (multi-GPU contexts evaluate the whole model, replicated -- the dipole terms included).
@@ -649,8 +667,8 @@ int rbl_get_interactions(const rbl_ctx *ctx, double *params6, int *on);
  * NULL (k = X0 = NULL) with on = 0 only switches it off.  rbl_set_parameters is not needed first.  The getters take NULL for
  * what is not wanted; coef: 4 (n - 1) doubles (c0 c1 c2 c3 per interval), k3 / X0: 3 n_bodies each; n = 0: never set.
  * rbl_get_interactions keeps reporting the built-in term only; rbl_interactions_active: bit 0 built-in term, bit 1 pair
- * table, bit 2 height table, bit 3 traps, bit 4 dipole pairs, bit 5 field torque, bit 6 bonds.  The steps, the queries below
- * and the ensembles evaluate every term that is on. */
+ * table, bit 2 height table, bit 3 traps, bit 4 dipole pairs, bit 5 field torque, bit 6 bonds, bit 7 typed pair
+ * tables.  The steps, the queries below and the ensembles evaluate every term that is on. */
 int rbl_set_pair_table(rbl_ctx *ctx, const double *U, const double *dU, int n, double r_min, double r_cut, int on);
 int rbl_get_pair_table(const rbl_ctx *ctx, int *n, double *r_min, double *r_cut, int *on, double *coef);
 int rbl_set_height_table(rbl_ctx *ctx, const double *U, const double *dU, int n, double h_min, double h_cut, int on);
@@ -670,6 +688,11 @@ int rbl_set_bond_table(rbl_ctx *ctx, const double *U, const double *dU, int n, d
 int rbl_get_bond_table(const rbl_ctx *ctx, int *n, double *r_min, double *r_cut, int *on, double *coef);
 int rbl_bond_state(rbl_ctx *ctx, double *length, double *tension, double *energy);
 int rbl_ensemble_bond_state(rbl_ctx *ctx, double *length, double *tension, double *energy);
+int rbl_set_blob_types(rbl_ctx *ctx, const int *type, int n, int n_types, int on);
+int rbl_get_blob_types(const rbl_ctx *ctx, int *n, int *n_types, int *on, int *type);
+int rbl_set_type_table(rbl_ctx *ctx, int ta, int tb, const double *U, const double *dU, int n, double r_min, double r_cut, int on);
+int rbl_get_type_table(const rbl_ctx *ctx, int ta, int tb, int *n, double *r_min, double *r_cut, int *on, double *coef);
+int rbl_clear_type_tables(rbl_ctx *ctx);
 int rbl_interactions_active(const rbl_ctx *ctx, int *mask);
 int rbl_interaction_forces_dev(rbl_ctx *ctx, double *d_f_blob, double *d_FT_body, double *energy);
 int rbl_interaction_forces(rbl_ctx *ctx, double *f_blob, double *FT_body, double *energy);

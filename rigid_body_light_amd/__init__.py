@@ -35,6 +35,6 @@ except ImportError as _e:  # fail loudly: the product has no Python/CPU path
 from .rigid_body import RigidBody  # noqa: E402,F401
 from .ensemble import Ensemble  # noqa: E402,F401
 from .synth import load_structure, make_config, STRUCT_DIR  # noqa: E402,F401
-from ._lib import tabulate  # noqa: E402,F401
+from ._lib import patch_types, tabulate  # noqa: E402,F401
 
-__all__ = ["RigidBody", "Ensemble", "c_rigid", "load_structure", "make_config", "STRUCT_DIR", "tabulate"]
+__all__ = ["RigidBody", "Ensemble", "c_rigid", "load_structure", "make_config", "STRUCT_DIR", "tabulate", "patch_types"]

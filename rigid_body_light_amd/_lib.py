@@ -96,6 +96,11 @@ def lib(path=None):
         L.rbl_set_traps.argtypes = [vp, vp, vp, C.c_int, C.c_int]
         L.rbl_get_traps.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp]
         L.rbl_interactions_active.argtypes = [vp, C.POINTER(C.c_int)]
+        L.rbl_set_blob_types.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
+        L.rbl_get_blob_types.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
+        L.rbl_set_type_table.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, dbl, dbl, C.c_int]
+        L.rbl_get_type_table.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int), vp]
+        L.rbl_clear_type_tables.argtypes = [vp]
         L.rbl_set_dipoles.argtypes = [vp, vp, C.c_int, dbl, dbl, dbl, C.c_int]
         L.rbl_get_dipoles.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int), vp]
         L.rbl_set_magnetic_field.argtypes = [vp, vp, vp, vp, dbl, C.c_int]
@@ -446,6 +451,51 @@ def table_arrays(who, U, dU):
     if U.ndim != 1 or U.shape != dU.shape:
         raise ValueError("%s: U and dU must be one-dimensional and of one length; got %s and %s" % (who, U.shape, dU.shape))
     return U, dU
+
+
+MAX_BLOB_TYPES = 8   # include/rbl.h section 4: the descriptors of the 36 type pairs sit in LDS
+
+
+def blob_type_args(who, types, n_types):
+    """the checks set_blob_types can make before the library is called -> contiguous int32 types (flattened), n_types.
+    types: integers of shape (N_blb,) -- every body alike -- or (N_bod, N_blb); n_types None: the largest type + 1"""
+    import numpy as np
+    t = np.asarray(types)
+    if t.ndim not in (1, 2) or not t.size:
+        raise ValueError("%s: types must have shape (N_blb,) or (N_bod, N_blb); got %s" % (who, t.shape))
+    if not np.issubdtype(t.dtype, np.integer):
+        raise ValueError("%s: types must be integers; got dtype %s" % (who, t.dtype))
+    if n_types is None:
+        n_types = int(t.max()) + 1
+    return np.ascontiguousarray(t.reshape(-1), dtype=np.int32), int(n_types)
+
+
+def type_pair_args(who, ta, tb):
+    """two type indices as Python integers (a float or a bool is a ValueError, the range is the library's to refuse)"""
+    import numpy as np
+    for name, v in (("ta", ta), ("tb", tb)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s: %s must be an integer; got %r" % (who, name, v))
+    return int(ta), int(tb)
+
+
+def patch_types(ref_config, axis, cos_half_angle=0.0):
+    """blob types of a patchy particle: type 1 for the blobs of the structure `ref_config` (N_blb, 3) whose direction from the
+    structure's mean lies within the cap about the body-frame `axis`, n . axis >= cos_half_angle |n| |axis|, else type 0.
+    cos_half_angle = 0: a hemisphere, a Janus particle.  A blob at the mean itself is type 0.  -> int32 (N_blb,)"""
+    import numpy as np
+    cfg = np.asarray(ref_config, dtype=np.float64)
+    ax = np.asarray(axis, dtype=np.float64)
+    if cfg.ndim != 2 or cfg.shape[1] != 3 or not cfg.shape[0]:
+        raise ValueError("patch_types: ref_config must have shape (N_blb, 3); got %s" % (cfg.shape,))
+    if ax.shape != (3,) or not np.isfinite(ax).all() or not np.linalg.norm(ax) > 0.0:
+        raise ValueError("patch_types: axis must be a finite non-zero vector of 3; got %r" % (axis,))
+    if not -1.0 <= float(cos_half_angle) <= 1.0:
+        raise ValueError("patch_types: cos_half_angle must lie in [-1, 1]; got %r" % (cos_half_angle,))
+    n = cfg - cfg.mean(axis=0)
+    ln = np.linalg.norm(n, axis=1)
+    inside = (ln > 0.0) & (n @ (ax / np.linalg.norm(ax)) >= float(cos_half_angle) * ln)
+    return inside.astype(np.int32)
 
 
 def check_brownian_mask6(who, mask6, n_bod, replicas=1):
@@ -865,7 +915,7 @@ class DeviceContext:
 
     def interactions_active(self):
         """bit 0 built-in terms, bit 1 pair table, bit 2 height table, bit 3 traps, bit 4 dipole pairs, bit 5 field torque,
-        bit 6 bonds"""
+        bit 6 bonds, bit 7 typed pair tables (types on and a usable type table on)"""
         m = C.c_int(0)
         self._chk(self.L.rbl_interactions_active(self.h, C.byref(m)))
         return m.value
@@ -899,6 +949,45 @@ class DeviceContext:
     def pair_table(self):
         """{n, lo, hi, on, coef (n - 1, 4)} of the pair table (n = 0: never set)"""
         return self._get_table(self.L.rbl_get_pair_table)
+
+    def set_blob_types(self, types, n_types=None, on=True):
+        """a type per blob, integers in [0, n_types), n_types <= 8 (None: the largest type + 1): shape (N_blb,) -- every body
+        alike -- or (N_bod, N_blb), one row per body of the system (of ONE replica of an ensemble, shared by all).  With
+        set_type_table a pair of blobs of different bodies gets the table of its two types on top of the steric term and the
+        untyped pair table: a patch of another type makes the pair potential depend on orientation (`patch_types`).
+        types=None with on=False only switches the stored types off."""
+        if types is None and not on:
+            return self._chk(self.L.rbl_set_blob_types(self.h, None, 0, 0, 0))
+        t, n_types = blob_type_args("set_blob_types", types, n_types)
+        self._chk(self.L.rbl_set_blob_types(self.h, t.ctypes.data, t.size, n_types, int(bool(on))))
+
+    def blob_types(self):
+        """{on, n_types, types (n,) int32} (n = 0: never set)"""
+        import numpy as np
+        n, nt, on = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.L.rbl_get_blob_types(self.h, C.byref(n), C.byref(nt), C.byref(on), None))
+        t = np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            self._chk(self.L.rbl_get_blob_types(self.h, None, None, None, t.ctypes.data))
+        return dict(on=bool(on.value), n_types=nt.value, types=t)
+
+    def set_type_table(self, ta, tb, U, dU, r_min, r_cut, on=True):
+        """the pair table of set_pair_table for blobs of the types ta and tb (one table per unordered pair: (tb, ta) names the
+        same one).  U = dU = None with on=False only switches the stored table off."""
+        ta, tb = type_pair_args("set_type_table", ta, tb)
+        if U is None and dU is None and not on:
+            return self._chk(self.L.rbl_set_type_table(self.h, ta, tb, None, None, 0, 0.0, 0.0, 0))
+        U, dU = table_arrays("set_type_table", U, dU)
+        self._chk(self.L.rbl_set_type_table(self.h, ta, tb, U.ctypes.data, dU.ctypes.data, U.size, float(r_min), float(r_cut), int(bool(on))))
+
+    def type_table(self, ta, tb):
+        """{n, lo, hi, on, coef (n - 1, 4)} of the table of the type pair (ta, tb) (n = 0: never set)"""
+        ta, tb = type_pair_args("type_table", ta, tb)
+        return self._get_table(lambda h, *a: self.L.rbl_get_type_table(h, ta, tb, *a))
+
+    def clear_type_tables(self):
+        """forget every type table; the types stay"""
+        self._chk(self.L.rbl_clear_type_tables(self.h))
 
     def height_table(self):
         return self._get_table(self.L.rbl_get_height_table)

@@ -145,6 +145,7 @@ static const RblBufRow kDevBufs[] = {
     {&rbl_ctx::d_hist, RBL_BUF_PERSIST},          // warm-start history ring
     {&rbl_ctx::d_ia, RBL_BUF_PERSIST},            // force-model lists and forces of the last evaluation (ia_nb, ia_cap)
     {&rbl_ctx::d_iat, RBL_BUF_PERSIST},           // force-model tables and traps (ia_tab_valid)
+    {&rbl_ctx::d_iaty, RBL_BUF_PERSIST},          // blob types, the type tables and their descriptors (ia_ty_valid)
     {&rbl_ctx::d_iam, RBL_BUF_PERSIST},           // dipole moments and field times (ia_mag_valid, ia_ft_valid)
     {&rbl_ctx::d_iab, RBL_BUF_PERSIST},           // bonds: anchors, parameters, topology (ia_bd_valid)
     {&rbl_ctx::d_iabs, RBL_BUF_SCRATCH},          // bond state queries: reserved at their start, within one call

@@ -21,6 +21,9 @@
 //                        would fit beside the position chunk at all (the largest table is 2 MB).  An LDS-staged variant has
 //                        not been built.  k_blob_interactions itself is the TAB = 0 instantiation with the argument list it
 //                        always had.
+//   k_blob_interactions_typed<TAB, CELL>  the pair kernel with blob types and one table per unordered type pair, launched only while
+//                        types and a usable type table are on: the same grid, chunking and summation order; the neighbour's type
+//                        rides in the fourth slot of the staged position, the 36 table descriptors sit in LDS (see the kernel).
 //   k_body_traps         harmonic traps on the body centres, after K^T f: one lane per body.
 //   k_body_dipoles<NT>   permanent dipoles fixed in the bodies, after the traps: one workgroup of NT lanes per body i (one wave
 //                        for windows of up to 512 bodies, four beyond).  Lane t takes the partners j = t, t + NT, ... of i's
@@ -324,6 +327,135 @@ __global__ __launch_bounds__(IA_BT) void k_blob_interactions_cells(const double 
   static_assert(TAB >= 0 && TAB <= 3, "bit 0: pair table, bit 1: height table");
   __shared__ double s[IA_CHUNK][4];
   ia_blob_interactions<TAB, true>(s, pos, cnt, list, cap, N_blb, tiles, p, PT, HT, f, e, npairs, ia_cell_of(cells, blockIdx.x / tiles / win));
+}
+
+// ---- blob types: one pair table per unordered type pair (include/rbl.h section 4) --------------------------------------------
+constexpr int IA_TY_PAIRS = rbl_ctx::IA_TY_PAIRS;
+
+// the typed term as the kernel takes it (by value).  desc: one IaTab per unordered type pair (hi = hi2 = -1: no table, nothing is
+// inside it); type: rows of N_blb entries -- body i reads row 0 (per_row = 0: every body alike) or row i % win
+struct IaTyped {
+  const IaTab *desc;
+  const int *type;
+  double cmax2;                                          // the largest cutoff^2 of every pair term that is on (built-in, untyped, typed)
+  int per_row;
+};
+
+// a descriptor in LDS, padded to 72 bytes: a lane's descriptor follows ITS type, so the 32 lanes of a ds_read_b64 group read
+// up to 8 different descriptors.  At 64 bytes the descriptors 4 apart share their banks ((a / 4) % 64); at 18 dwords the first
+// 32 all start on different even banks
+struct IaTabLds {
+  IaTab T;
+  double pad;
+};
+
+__device__ __forceinline__ int ia_type_pair(int s, int t) { const int hi = max(s, t); return hi * (hi + 1) / 2 + min(s, t); }
+
+// the pair kernel with blob types: the grid, the chunking and the summation order of ia_blob_interactions (its own body: that one's
+// kernels keep their code instruction for instruction).  The fourth slot of a staged blob carries its type; the neighbour's type
+// is the same for every lane at every step of the inner loop (an LDS broadcast), the lane's own type is not, so the descriptor of
+// (own, neighbour) is read from LDS by a per-lane address, and only by the pairs inside the largest cutoff.
+// CELL: 0 open, 1 the cell C, 2 the cell of the tile's window from the table
+template <int TAB, int CELL>
+__global__ __launch_bounds__(IA_BT) void k_blob_interactions_typed(const double *__restrict__ pos, const int *__restrict__ cnt,
+                                                                   const int *__restrict__ list, int cap, int N_blb, int tiles, int win,
+                                                                   IaParams p, IaTab PT, IaTab HT, IaTyped Y, IaCell Cv,
+                                                                   const RblEnsCellRec *__restrict__ cells, double *__restrict__ f,
+                                                                   double *__restrict__ e, int *__restrict__ npairs)
+{
+  static_assert(TAB >= 0 && TAB <= 3 && CELL >= 0 && CELL <= 2, "TAB bit 0: pair table, bit 1: height table; CELL 0 open, 1 by value, 2 table");
+  __shared__ double s[IA_CHUNK][4];
+  __shared__ IaTabLds sd[IA_TY_PAIRS];
+  for (int u = threadIdx.x; u < IA_TY_PAIRS; u += blockDim.x) sd[u].T = Y.desc[u];   // (the first barrier of the loop orders it)
+  const int i = blockIdx.x / tiles, k = (blockIdx.x - i * tiles) * blockDim.x + threadIdx.x;
+  IaCell C = Cv;
+  if constexpr (CELL == 2) C = ia_cell_of(cells, i / win);
+  const bool own = k < N_blb;
+  const size_t gi = (size_t)i * N_blb + (own ? k : 0);
+  const double xi = pos[3 * gi], yi = pos[3 * gi + 1], zi = pos[3 * gi + 2];
+  const int ti = Y.type[(size_t)(Y.per_row ? i % win : 0) * N_blb + (own ? k : 0)];
+  double fx = 0.0, fy = 0.0, fz = 0.0, en = 0.0;
+  int np = 0;
+  const int nn = min(cnt[i], cap);
+  for (int q = 0; q < nn; ++q) {
+    const int j = list[(size_t)i * cap + q];
+    const double *pj = pos + 3 * (size_t)j * N_blb;
+    const int *tj = Y.type + (size_t)(Y.per_row ? j % win : 0) * N_blb;
+    for (int c0 = 0; c0 < N_blb; c0 += IA_CHUNK) {
+      const int m = min(IA_CHUNK, N_blb - c0);
+      __syncthreads();                                   // the previous chunk has been read by every lane
+      for (int u = threadIdx.x; u < m; u += blockDim.x) {
+        s[u][0] = pj[3 * (size_t)(c0 + u)];
+        s[u][1] = pj[3 * (size_t)(c0 + u) + 1];
+        s[u][2] = pj[3 * (size_t)(c0 + u) + 2];
+        s[u][3] = __hiloint2double(0, tj[c0 + u]);       // the type in the low word of the fourth slot
+      }
+      __syncthreads();
+      if (!own) continue;
+      for (int u = 0; u < m; ++u) {
+        double dx = xi - s[u][0], dy = yi - s[u][1];
+        const double dz = zi - s[u][2];
+        if constexpr (CELL != 0) ia_min_image(C, dx, dy);
+        const double r2 = dx * dx + dy * dy + dz * dz;
+        if (r2 > Y.cmax2) continue;                      // beyond every cutoff that is on: skipped, not multiplied by zero
+        const double r = sqrt(r2);
+        const IaTab &TT = sd[ia_type_pair(ti, __double2loint(s[u][3]))].T;
+        const bool in_b = r2 <= p.rc2;                   // each term has its own cutoff
+        const bool in_t = (TAB & 1) && r <= PT.hi;
+        const bool in_y = r <= TT.hi;
+        if (!(in_b || in_t || in_y)) continue;
+        double U = 0.0, g = 0.0;                         // energy of the pair, -U'(r) / r
+        if (in_b) {
+          if (r >= p.two_a) {
+            U = p.eps_b * (p.two_a / r) * exp(-(r - p.two_a) * p.inv_bb);
+            g = U * (1.0 / r + p.inv_bb) / r;
+          } else {                                       // the tangent at r = 2a continued inwards
+            const double slope = p.eps_b * (1.0 / p.two_a + p.inv_bb);
+            U = p.eps_b + slope * (p.two_a - r);
+            g = r > 0.0 ? slope / r : 0.0;
+          }
+        }
+        if constexpr (TAB & 1) {
+          if (in_t) {
+            double Ut, dUt;
+            ia_tab_eval(PT, r, Ut, dUt);
+            U += Ut;
+            if (r > 0.0) g -= dUt / r;                   // coincident blobs exert no force
+          }
+        }
+        if (in_y) {
+          double Ut, dUt;
+          ia_tab_eval(TT, r, Ut, dUt);
+          U += Ut;
+          if (r > 0.0) g -= dUt / r;
+        }
+        fx += g * dx; fy += g * dy; fz += g * dz;
+        en += 0.5 * U;
+        ++np;
+      }
+    }
+  }
+  if (!own) return;
+  fz -= p.w;                                             // weight
+  en += p.w * zi;
+  if (p.wall) {                                          // wall repulsion, tangent continued below h = a
+    double Fw, Uw;
+    if (zi >= p.a) { Uw = p.eps_w * exp(-(zi - p.a) * p.inv_bw); Fw = Uw * p.inv_bw; }
+    else { Fw = p.eps_w * p.inv_bw; Uw = p.eps_w + Fw * (p.a - zi); }
+    fz += Fw;
+    en += Uw;
+  }
+  if constexpr (TAB & 2) {
+    if (zi <= HT.hi) {                                   // with or without the wall; nothing above h_cut
+      double Uh, dUh;
+      ia_tab_eval(HT, zi, Uh, dUh);
+      fz -= dUh;
+      en += Uh;
+    }
+  }
+  f[3 * gi] = fx; f[3 * gi + 1] = fy; f[3 * gi + 2] = fz;
+  if (e) e[gi] = en;
+  npairs[gi] = np;
 }
 
 // harmonic traps on the body centres: FT[6 i + c] -= k_c (X_c - X0_c), the energy added to the entry of the body's first blob
@@ -682,10 +814,22 @@ int ia_reserve(rbl_ctx *c, IaLayout &L)
 static bool ia_dp_pairs(const rbl_ctx *c) { return c->ia_dp_on && c->ia_dp_c > 0.0; }
 static bool ia_dp_field(const rbl_ctx *c) { return c->ia_dp_on && c->ia_mf_on; }
 static bool ia_bonds(const rbl_ctx *c) { return c->ia_bd_on && c->ia_bd_n > 0; }
+// the type tables that can be reached: both types below n_types (the entries of an unordered pair are ordered by the larger type)
+static int ia_ty_usable(const rbl_ctx *c) { return c->ia_ty_nt * (c->ia_ty_nt + 1) / 2; }
+// the largest cutoff of a usable type table that is on, 0: none -- the typed term is evaluated only while this is positive
+static double ia_typed_rcut(const rbl_ctx *c)
+{
+  double rc = 0.0;
+  if (c->ia_ty_on)
+    for (int q = 0; q < ia_ty_usable(c); ++q)
+      if (c->ia_tt[q].on) rc = std::max(rc, c->ia_tt[q].hi);
+  return rc;
+}
+static bool ia_typed(const rbl_ctx *c) { return ia_typed_rcut(c) > 0.0; }
 
 bool ia_any(const rbl_ctx *c)
 {
-  return c->ia_on || c->ia_pt.on || c->ia_ht.on || c->ia_tr_on || ia_dp_pairs(c) || ia_dp_field(c) || ia_bonds(c);
+  return c->ia_on || c->ia_pt.on || c->ia_ht.on || c->ia_tr_on || ia_dp_pairs(c) || ia_dp_field(c) || ia_bonds(c) || ia_typed(c);
 }
 
 // the tables' coefficients and the traps on the device (once per rbl_set_pair_table / rbl_set_height_table / rbl_set_bond_table /
@@ -738,6 +882,49 @@ static IaTab ia_tab_args(const rbl_ctx::IaTable &t, const double *d_coef)
   T.hi2 = t.hi * t.hi * (1.0 + 1e-15);
   T.last = t.n - 2;
   return T;
+}
+
+// the typed term on the device, once per rbl_set_blob_types / rbl_set_type_table / rbl_clear_type_tables: one descriptor per
+// unordered type pair (no usable table that is on: hi = hi2 = -1, no distance is inside it) | the coefficients of the usable
+// tables that are on | the types.  The descriptors hold device addresses of this buffer, so they are built here
+static int ia_ty_upload(rbl_ctx *c)
+{
+  if (c->ia_ty_valid) return RBL_OK;
+  size_t ncoef = 0;
+  for (int q = 0; q < ia_ty_usable(c); ++q)
+    if (c->ia_tt[q].on) ncoef += c->ia_tt[q].coef.size();
+  int rc = rbl_dev_reserve(c, c->d_iaty, sizeof(IaTab) * IA_TY_PAIRS + sizeof(double) * ncoef + sizeof(int) * c->ia_ty.size());
+  if (rc) return rc;
+  IaTab desc[IA_TY_PAIRS];
+  double *d = (double *)((IaTab *)c->d_iaty.p + IA_TY_PAIRS);
+  for (int q = 0; q < IA_TY_PAIRS; ++q) {
+    const rbl_ctx::IaTable &t = c->ia_tt[q];
+    desc[q] = IaTab{};
+    desc[q].hi = desc[q].hi2 = -1.0;
+    if (q >= ia_ty_usable(c) || !t.on) continue;
+    desc[q] = ia_tab_args(t, d);
+    if ((rc = copy_h2d(c, d, t.coef.data(), sizeof(double) * t.coef.size()))) return rc;
+    d += t.coef.size();
+  }
+  if ((rc = copy_h2d(c, c->d_iaty.p, desc, sizeof(desc)))) return rc;
+  if (!c->ia_ty.empty() && (rc = copy_h2d(c, d, c->ia_ty.data(), sizeof(int) * c->ia_ty.size()))) return rc;
+  RBL_HIP(c, hipStreamSynchronize(c->stream));
+  c->ia_ty_valid = true;
+  return RBL_OK;
+}
+
+// after ia_ty_upload
+static IaTyped ia_typed_args(const rbl_ctx *c, double cmax2, bool per_row)
+{
+  size_t ncoef = 0;
+  for (int q = 0; q < ia_ty_usable(c); ++q)
+    if (c->ia_tt[q].on) ncoef += c->ia_tt[q].coef.size();
+  IaTyped Y;
+  Y.desc = (const IaTab *)c->d_iaty.p;
+  Y.type = (const int *)((const double *)(Y.desc + IA_TY_PAIRS) + ncoef);
+  Y.cmax2 = cmax2;
+  Y.per_row = per_row ? 1 : 0;
+  return Y;
 }
 
 // what an evaluation over windows of `win` bodies needs of the bonds (no device touched)
@@ -823,6 +1010,11 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   const bool bonds = ia_bonds(c);
   int rc;
   if (bonds && (rc = ia_bond_check(c, "interactions", win, n_win))) return rc;
+  const double rc_typed = ia_typed_rcut(c);
+  const bool typed = rc_typed > 0.0;
+  const size_t nty = c->ia_ty.size();
+  if (typed && nty != (size_t)S.N_blb && nty != (size_t)win * S.N_blb)
+    return rbl_fail(c, RBL_ERR_STATE, "interactions: the blob types hold neither one entry per blob of a body nor one per blob of the system (rbl_set_blob_types)");
   // a periodic cell (include/rbl.h section 10): minimum image in the neighbour search, the blob pair terms and the dipole pairs.
   // The convention is unique only while no pair inside a cutoff has a second image inside it: blobs of two bodies lie within
   // 2 R_body + r_cut of each other's centres, dipoles sit on the centres themselves
@@ -841,8 +1033,8 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
       const double *q = &S.ref_cfg[3 * (size_t)k];
       R2b = std::max(R2b, q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
     }
-    const double rc_pair = std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0);
-    const double need_pair = (c->ia_on || c->ia_pt.on) ? 2.0 * std::sqrt(R2b) + rc_pair : 0.0;
+    const double rc_pair = std::max(std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0), rc_typed);
+    const double need_pair = (c->ia_on || c->ia_pt.on || typed) ? 2.0 * std::sqrt(R2b) + rc_pair : 0.0;
     const double need_dp = dp_pairs ? c->ia_dp_rcut : 0.0;
     for (int r = 0; r < n_cells; ++r) {
       const double *per_L = tab_cells ? &c->ens_cells_L[2 * (size_t)r] : ens ? c->ens_per_L : c->per_L;
@@ -870,6 +1062,7 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   if ((rc = ia_upload(c))) return rc;
   if (dp && (rc = ia_mag_upload(c))) return rc;
   if (bonds && (rc = ia_bond_upload(c))) return rc;
+  if (typed && (rc = ia_ty_upload(c))) return rc;
   RblPhase ph(c, RBL_T_FORCES);
   IaLayout L = ia_layout(d_cl, nbod, S.N_blb, cap);
   double R2 = 0.0;                                       // R_body: largest blob distance from the centre, body frame (mean removed)
@@ -879,7 +1072,7 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   }
   // the larger cutoff of the pair terms that are on.  A hair of slack for the rounding of the rotated lever arms and of the
   // distances: it can only add candidates, whose pairs beyond the cutoffs are then skipped one by one
-  const double rc_max = std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0);
+  const double rc_max = std::max(std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0), rc_typed);
   const double cut = (2.0 * std::sqrt(R2) + rc_max) * (1.0 + 1e-12) + 1e-12;
   if (cells)
     hipLaunchKernelGGL(k_body_neighbours_cells, dim3(nbod), dim3(64), 0, c->stream, d_X, nbod, win, cut * cut, c->ia_cull ? 1 : 0, cap,
@@ -908,7 +1101,26 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
 #define RBL_IA_CELLS(K)                                                                                                              \
   hipLaunchKernelGGL(k_blob_interactions_cells<K>, grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt, (const int *)L.list, cap, \
                      S.N_blb, tiles, win, P, PT, HT, cells, d_f, d_e, L.np)
-  if (cells) {
+  if (typed) {
+    // the largest cutoff^2 of the pair terms that are on, each rounded as its own test takes it (rc2; hi^2 a hair up)
+    const double cmax2 = std::max(std::max(P.rc2, c->ia_pt.on ? PT.hi2 : -1.0), rc_typed * rc_typed * (1.0 + 1e-15));
+    const IaTyped Y = ia_typed_args(c, cmax2, nty != (size_t)S.N_blb);
+#define RBL_IA_TYPED(K, CELL)                                                                                                        \
+  hipLaunchKernelGGL((k_blob_interactions_typed<K, CELL>), grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt,                 \
+                     (const int *)L.list, cap, S.N_blb, tiles, win, P, PT, HT, Y, C, cells, d_f, d_e, L.np)
+#define RBL_IA_TYPED_TAB(CELL)                                                                                                       \
+  do {                                                                                                                               \
+    if (tab == 0) RBL_IA_TYPED(0, CELL);                                                                                             \
+    else if (tab == 1) RBL_IA_TYPED(1, CELL);                                                                                        \
+    else if (tab == 2) RBL_IA_TYPED(2, CELL);                                                                                        \
+    else RBL_IA_TYPED(3, CELL);                                                                                                      \
+  } while (0)
+    if (cells) RBL_IA_TYPED_TAB(2);
+    else if (per) RBL_IA_TYPED_TAB(1);
+    else RBL_IA_TYPED_TAB(0);
+#undef RBL_IA_TYPED_TAB
+#undef RBL_IA_TYPED
+  } else if (cells) {
     if (tab == 0) RBL_IA_CELLS(0);
     else if (tab == 1) RBL_IA_CELLS(1);
     else if (tab == 2) RBL_IA_CELLS(2);
@@ -1093,6 +1305,74 @@ int rbl_get_height_table(const rbl_ctx *c, int *n, double *h_min, double *h_cut,
 {
   if (!c) return RBL_ERR_ARG;
   return ia_get_table(c->ia_ht, n, h_min, h_cut, on, coef);
+}
+
+// a type table's slot: the unordered pair (ta, tb); NULL outside [0, 8)
+static rbl_ctx::IaTable *ia_type_slot(rbl_ctx *c, int ta, int tb)
+{
+  if (ta < 0 || ta >= rbl_ctx::IA_TY_MAX || tb < 0 || tb >= rbl_ctx::IA_TY_MAX) return nullptr;
+  const int hi = std::max(ta, tb);
+  return &c->ia_tt[hi * (hi + 1) / 2 + std::min(ta, tb)];
+}
+
+int rbl_set_type_table(rbl_ctx *c, int ta, int tb, const double *U, const double *dU, int n, double r_min, double r_cut, int on)
+{
+  if (!c) return RBL_ERR_ARG;
+  rbl_ctx::IaTable *t = ia_type_slot(c, ta, tb);
+  if (!t)
+    return rbl_fail(c, RBL_ERR_ARG, "set_type_table: ta = " + std::to_string(ta) + ", tb = " + std::to_string(tb) + ": both types must lie in [0, " +
+                                        std::to_string(rbl_ctx::IA_TY_MAX) + ")");
+  const bool untyped_valid = c->ia_tab_valid;            // (ia_set_table speaks for the buffer of the untyped tables)
+  const int rc = ia_set_table(c, "set_type_table", *t, U, dU, n, r_min, r_cut, true, on);
+  c->ia_tab_valid = untyped_valid;
+  if (rc == RBL_OK) c->ia_ty_valid = false;
+  return rc;
+}
+
+int rbl_get_type_table(const rbl_ctx *c, int ta, int tb, int *n, double *r_min, double *r_cut, int *on, double *coef)
+{
+  if (!c) return RBL_ERR_ARG;
+  const rbl_ctx::IaTable *t = ia_type_slot(const_cast<rbl_ctx *>(c), ta, tb);
+  if (!t) return RBL_ERR_ARG;
+  return ia_get_table(*t, n, r_min, r_cut, on, coef);
+}
+
+int rbl_clear_type_tables(rbl_ctx *c)
+{
+  if (!c) return RBL_ERR_ARG;
+  for (rbl_ctx::IaTable &t : c->ia_tt) t = rbl_ctx::IaTable{};
+  c->ia_ty_valid = false;
+  return RBL_OK;
+}
+
+// the blob types: checks first, nothing is stored unless every one passes (include/rbl.h section 4)
+int rbl_set_blob_types(rbl_ctx *c, const int *type, int n, int n_types, int on)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (!type && !on) { c->ia_ty_on = false; return RBL_OK; }
+  if (!type) return rbl_fail(c, RBL_ERR_ARG, "set_blob_types: type must not be NULL");
+  if (n < 1) return rbl_fail(c, RBL_ERR_ARG, "set_blob_types: n must be >= 1");
+  if (n_types < 1 || n_types > rbl_ctx::IA_TY_MAX)
+    return rbl_fail(c, RBL_ERR_ARG, "set_blob_types: n_types = " + std::to_string(n_types) + " must lie in [1, " + std::to_string(rbl_ctx::IA_TY_MAX) + "]");
+  for (int k = 0; k < n; ++k)
+    if (type[k] < 0 || type[k] >= n_types)
+      return rbl_fail(c, RBL_ERR_ARG, "set_blob_types: type[" + std::to_string(k) + "] = " + std::to_string(type[k]) + " must lie in [0, " +
+                                          std::to_string(n_types) + ")");
+  c->ia_ty.assign(type, type + n);
+  c->ia_ty_nt = n_types;
+  c->ia_ty_on = on != 0;
+  c->ia_ty_valid = false;
+  return RBL_OK;
+}
+
+int rbl_get_blob_types(const rbl_ctx *c, int *n, int *n_types, int *on, int *type)
+{
+  if (!c) return RBL_ERR_ARG;
+  if (n) *n = (int)c->ia_ty.size();
+  if (n_types) *n_types = c->ia_ty_nt;
+  if (on) *on = c->ia_ty_on ? 1 : 0;
+  if (type && !c->ia_ty.empty()) std::memcpy(type, c->ia_ty.data(), sizeof(int) * c->ia_ty.size());
+  return RBL_OK;
 }
 
 int rbl_set_traps(rbl_ctx *c, const double *k3, const double *X0, int n_bodies, int on)
@@ -1329,7 +1609,7 @@ int rbl_interactions_active(const rbl_ctx *c, int *mask)
 {
   if (!c || !mask) return RBL_ERR_ARG;
   *mask = (c->ia_on ? 1 : 0) | (c->ia_pt.on ? 2 : 0) | (c->ia_ht.on ? 4 : 0) | (c->ia_tr_on ? 8 : 0) |
-          (ia_dp_pairs(c) ? 16 : 0) | (ia_dp_field(c) ? 32 : 0) | (ia_bonds(c) ? 64 : 0);
+          (ia_dp_pairs(c) ? 16 : 0) | (ia_dp_field(c) ? 32 : 0) | (ia_bonds(c) ? 64 : 0) | (ia_typed(c) ? 128 : 0);
   return RBL_OK;
 }
 

@@ -219,6 +219,14 @@ struct rbl_ctx {
   std::vector<double> ia_tr_k, ia_tr_X0;            // 3 per body, ia_tr_k.size() / 3 bodies
   RblDevBuf d_iat;                                  // pair | height | bond coefficients | trap k | trap X0 (ia_tab_valid)
   bool ia_tab_valid = false;
+  // blob types and one pair table per unordered type pair (ta <= tb: entry tb (tb + 1) / 2 + ta)
+  static constexpr int IA_TY_MAX = 8, IA_TY_PAIRS = IA_TY_MAX * (IA_TY_MAX + 1) / 2;
+  bool ia_ty_on = false;
+  int ia_ty_nt = 0;                                 // n_types (0: never set)
+  std::vector<int> ia_ty;                           // N_blb entries (every body alike) or N_bod N_blb (one per blob of the system)
+  IaTable ia_tt[IA_TY_PAIRS];
+  RblDevBuf d_iaty;                                 // descriptors [IA_TY_PAIRS] | coefficients of the usable tables | types (ia_ty_valid)
+  bool ia_ty_valid = false;
   // permanent dipoles fixed in the bodies, a uniform field B(t) = B0 + B1 cos(omega t) + B2 sin(omega t) and its clock
   bool ia_dp_on = false;
   std::vector<double> ia_dp_m;                      // body-frame moments, 3 per entry (1, N_bod or R N_bod entries)

@@ -453,6 +453,29 @@ class Ensemble:
         """the tabulated potential in the blob height of RigidBody.set_height_table, for every replica"""
         self.ctx.set_height_table(U, dU, h_min, h_cut, on=on)
 
+    def set_blob_types(self, types, n_types=None, on=True):
+        """the blob types of RigidBody.set_blob_types: (N_blb,) -- every body alike -- or (N_bod, N_blb), the system of ONE
+        replica, shared by every replica"""
+        if types is None and not on:
+            return self.ctx.set_blob_types(None, on=False)
+        t = np.asarray(types)
+        if t.shape not in ((self.blobs_per_body,), (self.N_bodies, self.blobs_per_body)):
+            _fail("types must have shape (%d,) or (%d, %d); got %s" % (self.blobs_per_body, self.N_bodies, self.blobs_per_body, t.shape))
+        self.ctx.set_blob_types(t, n_types=n_types, on=on)
+
+    def blob_types(self):
+        return self.ctx.blob_types()
+
+    def set_type_table(self, ta, tb, U, dU, r_min, r_cut, on=True):
+        """the table of the type pair (ta, tb) of RigidBody.set_type_table, for every replica (pairs only inside a replica)"""
+        self.ctx.set_type_table(ta, tb, U, dU, r_min, r_cut, on=on)
+
+    def type_table(self, ta, tb):
+        return self.ctx.type_table(ta, tb)
+
+    def clear_type_tables(self):
+        self.ctx.clear_type_tables()
+
     def set_traps(self, k, X0, on=True):
         """harmonic traps on the body centres: k and X0 of shape (N_bod, 3), shared by every replica, or (R, N_bod, 3)"""
         k, X0 = np.asarray(k, dtype=np.float64), np.asarray(X0, dtype=np.float64)

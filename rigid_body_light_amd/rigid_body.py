@@ -22,7 +22,7 @@ and an imposed flow, a body-frame slip and stresslets (`set_background_flow`, `s
 import numpy as np
 
 from . import c_rigid as _ext
-from ._lib import JOINT_AXIS, JOINT_BALL, JOINT_LOCK, DeviceContext, default_q_rel, hinge, joint_kind_args, joint_rows, motor, weld, blob_anchor, bond_args, check_brownian_mask6, dipole_args, field_args, joint_args, periodic_args, table_arrays, tabulate  # noqa: F401
+from ._lib import JOINT_AXIS, JOINT_BALL, JOINT_LOCK, DeviceContext, default_q_rel, hinge, joint_kind_args, joint_rows, motor, weld, blob_anchor, bond_args, check_brownian_mask6, blob_type_args, dipole_args, field_args, joint_args, patch_types, periodic_args, table_arrays, tabulate  # noqa: F401
 
 _KBT_IN_WRAPPER = 1.0   # the reference wrapper passes kBT = 1 whatever the caller wants (src/Rigid.py:23)
 
@@ -235,6 +235,33 @@ class RigidBody:
         """The same construction in the blob height z over h_min .. h_cut, with or without the wall."""
         U, dU = table_arrays("set_height_table", U, dU)
         self.ctx.set_height_table(U, dU, h_min, h_cut, on)
+
+    def set_blob_types(self, types, n_types=None, on=True):
+        """A type per blob (include/rbl.h section 4): integers in [0, n_types), n_types <= 8, of shape (N_blobs_per_body,) --
+        every body alike -- or (N_bodies, N_blobs_per_body).  With set_type_table a pair of blobs of different bodies gets the
+        table of its two types on top of the steric term and the pair table; `patch_types` types a cap of the structure."""
+        if types is None and not on:
+            return self.ctx.set_blob_types(None, on=False)
+        t, n_types = blob_type_args("set_blob_types", types, n_types)
+        if t.size not in (self.blobs_per_body, self.N_bodies * self.blobs_per_body):
+            raise ValueError(f"set_blob_types: types must have shape ({self.blobs_per_body},) or ({self.N_bodies}, {self.blobs_per_body}). "
+                             f"Got shape: {np.shape(types)}")
+        self.ctx.set_blob_types(t, n_types, on)
+
+    def blob_types(self):
+        """{on, n_types, types}"""
+        return self.ctx.blob_types()
+
+    def set_type_table(self, ta, tb, U, dU, r_min, r_cut, on=True):
+        """The pair table of set_pair_table for blobs of the types ta and tb; (tb, ta) names the same table."""
+        self.ctx.set_type_table(ta, tb, U, dU, r_min, r_cut, on)
+
+    def type_table(self, ta, tb):
+        """{n, lo, hi, on, coef (n - 1, 4)}"""
+        return self.ctx.type_table(ta, tb)
+
+    def clear_type_tables(self):
+        self.ctx.clear_type_tables()
 
     def set_traps(self, k, X0, on=True):
         """Harmonic traps on the body centres: k and X0 of shape (N_bodies, 3), lab frame; a component of k that is 0 leaves
