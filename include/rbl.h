@@ -520,7 +520,11 @@ enum {
   RBL_OPT_RECORD_MOMENTS = 37,     /* [0] every whole-step entry point also leaves the first moments D_b = sum (r_i - X_b) lambda_i^T of its
                                       solve's blob forces on the device (section 8: rbl_step_moments, rbl_ensemble_step_moments); one small
                                       launch per step.  Setting the option (to either value) discards what was recorded              */
-  RBL_OPT_COUNT = 38
+  RBL_OPT_MC_SWEEPS_PER_LAUNCH = 38, /* [128] rbl_ensemble_mc (section 5): sweeps of one kernel launch, 1 .. 65536; a chain of n_sweeps is
+                                      ceil(n_sweeps / this) launches.  Results do not depend on it.  The default keeps a launch in the tens of
+                                      milliseconds at the measured 4.3 - 6.4 us per trial (profiles/ensemble_mc.jsonl): 12 ms for 19 shells,
+                                      about 31 ms for 53 tetrahedra (53 trials a sweep; not timed)                                  */
+  RBL_OPT_COUNT = 39
 };
 int rbl_set_option(rbl_ctx *ctx, int option, int64_t value);
 int rbl_get_option(const rbl_ctx *ctx, int option, int64_t *value);
@@ -1227,6 +1231,85 @@ int rbl_ensemble_run_driven(rbl_ctx *ctx, const rbl_run_opts *opts, const rbl_ru
                             rbl_run_out *out, rbl_run_drive_out *dout, rbl_run_obs_out *oout);
 int rbl_ensemble_drive_eval(rbl_ctx *ctx, const rbl_run_drive_opts *drive, const double *base, const int32_t *accepted,
                             const int32_t *cycle_pos, double *in_out, double *cs_sn);
+
+/* Metropolis sampling of the force model (rigid_body_light_amd/csrc/rbl_ens_mc.hip): rbl_ensemble_mc runs n_sweeps Metropolis
+ * sweeps on every replica of the ensemble's current configuration and leaves the result as the current configuration, from
+ * which every step family continues as from rbl_ensemble_set_config of the same numbers -- up to that call's own normalisation of
+ * the quaternions, which the chain's result does not go through again: where set_config would move the last bit of a quaternion
+ * the chain left (it divides by a norm that is 1 only to rounding), the two continuations differ by that bit's consequence and are
+ * bitwise equal otherwise.  No mobility is involved: the chain
+ * samples exp(-E / kBT) of the total energy E that rbl_ensemble_interaction_forces reports, for equilibrated starting
+ * configurations and as the reference of the stationary distribution of the Brownian steps.
+ *
+ * Sweeps and trials.  One sweep is N_bod trials, body b = 0 .. N_bod - 1 in that order.  A fixed order preserves the stationary
+ * distribution (every trial does); it is NOT detailed balance of the sweep, nor a random-scan chain.  The trial of body b in
+ * replica r at the global sweep index S = sweep_start + s draws 7 uniforms from Philox-4x32-10, the generator of the steps'
+ * noise, with the key (k0, k1) = (low, high word of seed) and the two counters
+ *     c = { low word of S, high word of S, replica_base + r, 0x4D430000 | j << 8 | b },  j = 0, 1
+ * (b < 64; the steps' normals use c[3] = 0, so the streams never meet): block j = 0 gives the words w0..w3, block j = 1 the
+ * words w4..w6 (its fourth word is unused).  A word becomes u = (w + 0.5) 2^-32, 0 < u < 1.  The counter depends on
+ * (replica_base + r, S, b) and on nothing else -- not on R, on the launch split, or on what other bodies did.
+ * Proposal: dX = step_x (2 u_{0,1,2} - 1), a rotation vector phi = step_theta (2 u_{3,4,5} - 1) in the lab frame, and
+ * q' = update_X_Q(q, (dX, phi)): the library's own body update (the rotation quaternion of phi multiplied from the left, then
+ * normalised).  The proposal density is symmetric under (dX, phi) -> -(dX, phi): no Hastings factor.  u_6 decides: the trial is
+ * accepted iff dE <= 0 or u_6 < exp(-dE / kBT_r).  kBT: kBT_sets = 0 the context's, 1 one value, R one value per replica (a
+ * temperature sweep in one call); every value finite and > 0.
+ * Energy.  dE is the change of the total energy of section 4 restricted to what body b takes part in: weight, wall repulsion
+ * and height table of b's blobs; steric term, pair table and type tables between b's blobs and the blobs of the replica's other
+ * bodies, each inside its own cutoff; b's trap; the bonds and tethers that end on b -- bits 0, 1, 2, 3, 6 and 7 of
+ * rbl_interactions_active, with the definitions of section 4 (tangent continuations, unshifted cutoffs, the r = 0 rules), the
+ * kernels sharing the force kernels' expressions.  Replica-indexed inputs are read as the force evaluation reads them (trap
+ * sets, bond parameter sets, a cell per replica).  With the ensemble's cell on, shared or per replica, pair displacements take
+ * the minimum image and bonds stay unwrapped, as in the force kernels.  Dipole pairs and the field torque (bits 4, 5) are not
+ * offered: RBL_ERR_STATE, the term named, while either is active.  Nor are hard joints (constrained sampling), moves of more
+ * than one body, cluster or swap moves, replica exchange, or a single context without an ensemble.
+ * Domain.  With the wall on (rbl_set_wall_pc) a trial that puts any blob of b at z < 0 is rejected without an energy
+ * evaluation and counted in wall_rejected (the mobility is undefined there); a starting configuration with a blob below the
+ * wall is RBL_ERR_BELOW_WALL, the replica named, and nothing moves.
+ * frozen: an optional byte mask, frozen_sets = 1 (N_bod entries) or R (R N_bod): a frozen body is never tried, keeps its bits
+ * and still acts on the others.
+ * Sizes: a replica is what rbl_ensemble_set_config accepts, the one-kernel solver's size rule (about 75 N_blobs + 60 N_bod doubles
+ * within 150 KB of LDS): at most 19 shells of 12 blobs, 53 tetrahedra, or one body of 238 blobs.  The kernel's arrays are sized for
+ * the layout's bound of 256 blobs and 64 bodies, which no ensemble reaches; the call asks the size rule again (RBL_ERR_SIZE).
+ * Outputs, host arrays, any may be NULL; the flags, counters and energies come back in one read-back, frames and trace follow
+ * once the call has succeeded (a refused call leaves the caller's arrays alone): tried, accepted, wall_rejected [R] (int64);
+ * energy_start [R], the energy of rbl_ensemble_interaction_forces at the start (that evaluation, summed in its order);
+ * energy_end [R] = energy_start plus the accepted dE in trial order; with stride > 0 the n_sweeps / stride frames after every
+ * stride-th sweep of the call, frame_X [n_frames R 3 N_bod], frame_Q [n_frames R 4 N_bod], frame_E [n_frames R] (all three
+ * required then); with n_trace > 0 the first n_trace trials of every replica, trace [R n_trace 10]: body, dX (3), phi (3),
+ * dE, u_6, verdict (0 rejected, 1 accepted, 2 rejected at the wall: dE = 0, not evaluated; rows beyond the trials made: -1).
+ * Contracts: the call is bitwise reproducible (one workgroup per replica, one summation order, no atomics on doubles); n1 + n2
+ * sweeps give the configuration and the counters of n1 sweeps followed by n2 sweeps with sweep_start = n1 (energy_end agrees to
+ * rounding: the second call starts from its own evaluation); replica r of R is the R = 1 ensemble of that replica with
+ * replica_base = r; the host splits a chain into ceil(n_sweeps / RBL_OPT_MC_SWEEPS_PER_LAUNCH) launches, invisible in every bit.
+ * Refused before any device work, RBL_ERR_ARG with the argument named: NULL structs or a wrong size, n_sweeps < 1, step_x or
+ * step_theta negative or non-finite, a kBT <= 0 or non-finite (kBT NULL with kBT_sets > 0), kBT_sets or frozen_sets negative
+ * or neither 1 nor R, stride < 0, n_trace < 0, sweep_start < 0, replica_base < 0 or replica_base + R > 2^31, frame arrays NULL
+ * with n_frames > 0, trace NULL with n_trace > 0, a context with a communicator; RBL_ERR_STATE: hard joints switched on, a
+ * dipole term active, no term of the force model on, no ensemble configuration.  On any error nothing moves. */
+typedef struct rbl_mc_opts {
+  int64_t size;               /* sizeof(rbl_mc_opts) */
+  int64_t n_sweeps;           /* >= 1 */
+  int64_t sweep_start;        /* >= 0: the global index of the call's first sweep */
+  uint64_t seed;
+  double step_x, step_theta;  /* >= 0 */
+  int32_t replica_base;       /* >= 0 */
+  int32_t kBT_sets;           /* 0 (the context's kBT), 1 or R */
+  int32_t frozen_sets;        /* 0 (none frozen), 1 or R */
+  int32_t stride;             /* >= 0; 0 records no frames */
+  int32_t n_trace;            /* >= 0 */
+  int32_t reserved;
+  const double *kBT;          /* [kBT_sets] */
+  const uint8_t *frozen;      /* [frozen_sets N_bod] */
+} rbl_mc_opts;
+typedef struct rbl_mc_out {
+  int64_t size;               /* sizeof(rbl_mc_out) */
+  int64_t *tried, *accepted, *wall_rejected;   /* [R] */
+  double *energy_start, *energy_end;           /* [R] */
+  double *frame_X, *frame_Q, *frame_E;         /* [n_frames R 3 N_bod], [n_frames R 4 N_bod], [n_frames R] */
+  double *trace;                               /* [R n_trace 10] */
+} rbl_mc_out;
+int rbl_ensemble_mc(rbl_ctx *ctx, const rbl_mc_opts *opts, rbl_mc_out *out);
 
 /* ===================================================================== */
 /* 6. Fluid velocity at arbitrary points (rigid_body_light_amd/csrc/rbl_field.hip) */

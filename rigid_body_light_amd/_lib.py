@@ -145,6 +145,7 @@ def lib(path=None):
         L.rbl_ensemble_step_mixed_dof.argtypes = L.rbl_ensemble_step_mixed.argtypes
         L.rbl_ensemble_step_brownian_mixed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, dbl, C.c_int, dbl, vp, vp, vp]
         L.rbl_ensemble_run.argtypes = [vp, C.POINTER(RunOpts), C.POINTER(RunOut)]
+        L.rbl_ensemble_mc.argtypes = [vp, C.POINTER(McOpts), C.POINTER(McOut)]
         L.rbl_ensemble_run_jointed.argtypes = [vp, C.POINTER(RunOpts), C.POINTER(RunJointOpts), C.POINTER(RunOut), C.POINTER(RunJointOut)]
         L.rbl_run_schedule_phase.argtypes = [vp, C.c_int, i64]
         L.rbl_ensemble_set_joint_rates.argtypes = L.rbl_ensemble_set_joint_angles.argtypes = [vp, vp, C.c_int]
@@ -527,6 +528,64 @@ class RunOut(C.Structure):
                 ("first_status", C.c_void_p), ("iters_sum", C.c_void_p), ("resid_max", C.c_void_p), ("F_sum", C.c_void_p),
                 ("frame_X", C.c_void_p), ("frame_Q", C.c_void_p), ("frame_accepted_at", C.c_void_p), ("frame_F", C.c_void_p),
                 ("steps_done", C.c_int32), ("stopped_at", C.c_int32), ("stop_replica", C.c_int32), ("reserved", C.c_int32)]
+
+
+class McOpts(C.Structure):
+    """rbl_mc_opts (include/rbl.h section 5)"""
+    _fields_ = [("size", C.c_int64), ("n_sweeps", C.c_int64), ("sweep_start", C.c_int64), ("seed", C.c_uint64), ("step_x", C.c_double),
+                ("step_theta", C.c_double), ("replica_base", C.c_int32), ("kBT_sets", C.c_int32), ("frozen_sets", C.c_int32),
+                ("stride", C.c_int32), ("n_trace", C.c_int32), ("reserved", C.c_int32), ("kBT", C.c_void_p), ("frozen", C.c_void_p)]
+
+
+class McOut(C.Structure):
+    """rbl_mc_out (include/rbl.h section 5)"""
+    _fields_ = [("size", C.c_int64), ("tried", C.c_void_p), ("accepted", C.c_void_p), ("wall_rejected", C.c_void_p),
+                ("energy_start", C.c_void_p), ("energy_end", C.c_void_p), ("frame_X", C.c_void_p), ("frame_Q", C.c_void_p),
+                ("frame_E", C.c_void_p), ("trace", C.c_void_p)]
+
+
+class McResult:
+    """what a Metropolis chain returns (DeviceContext.ensemble_mc, Ensemble.metropolis): tried, accepted, wall_rejected (R,) int64;
+    acceptance = accepted / tried (nan where nothing was tried); energy_start, energy_end (R,); with stride > 0 the frames X
+    (n_frames, R, N_bod, 3), Q (n_frames, R, N_bod, 4), E (n_frames, R), else None; with trace > 0 the first trials of every replica,
+    trace (R, n_trace, 10): body, dX (3), phi (3), dE, u_6, verdict (0 rejected, 1 accepted, 2 rejected at the wall), else None"""
+
+    def __init__(self, tried, accepted, wall_rejected, energy_start, energy_end, X=None, Q=None, E=None, trace=None):
+        import numpy as np
+        self.tried, self.accepted, self.wall_rejected = tried, accepted, wall_rejected
+        self.energy_start, self.energy_end = energy_start, energy_end
+        self.X, self.Q, self.E, self.trace = X, Q, E, trace
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.acceptance = accepted / tried.astype(np.float64)
+
+
+def mc_args(who, R, n_bod, n_sweeps, step_x, step_theta, kBT, frozen, stride, trace, sweep_start, replica_base):
+    """the argument checks of a Metropolis chain, before the library is called (ValueError) -> (n_sweeps, kBT array or None,
+    frozen (sets, N_bod) uint8 or None, stride, trace, sweep_start, replica_base)"""
+    import numpy as np
+    n_sweeps, stride, trace, sweep_start, replica_base = int(n_sweeps), int(stride), int(trace), int(sweep_start), int(replica_base)
+    if n_sweeps < 1:
+        raise ValueError("%s: n_sweeps must be >= 1; got %d" % (who, n_sweeps))
+    for name, v in (("step_x", step_x), ("step_theta", step_theta)):
+        if not np.isfinite(v) or v < 0.0:
+            raise ValueError("%s: %s must be finite and >= 0; got %r" % (who, name, v))
+    if stride < 0 or trace < 0 or sweep_start < 0 or replica_base < 0:
+        raise ValueError("%s: stride, trace, sweep_start and replica_base must be >= 0; got %d, %d, %d, %d"
+                         % (who, stride, trace, sweep_start, replica_base))
+    if kBT is not None:
+        kBT = np.ascontiguousarray(np.atleast_1d(np.asarray(kBT, dtype=np.float64)))
+        if kBT.ndim != 1 or kBT.size not in (1, R):
+            raise ValueError("%s: kBT must be one value or one per replica (%d); got shape %s" % (who, R, kBT.shape))
+        if not np.all(np.isfinite(kBT)) or not np.all(kBT > 0.0):
+            raise ValueError("%s: every kBT must be finite and > 0" % who)
+    if frozen is not None:
+        frozen = np.asarray(frozen)
+        if frozen.shape == (n_bod,):
+            frozen = frozen.reshape(1, n_bod)
+        if frozen.shape not in ((1, n_bod), (R, n_bod)):
+            raise ValueError("%s: frozen must have shape (%d,) or (%d, %d); got %s" % (who, n_bod, R, n_bod, frozen.shape))
+        frozen = np.ascontiguousarray(frozen != 0, dtype=np.uint8)
+    return n_sweeps, kBT, frozen, stride, trace, sweep_start, replica_base
 
 
 class RunJointOpts(C.Structure):
@@ -1514,6 +1573,35 @@ class DeviceContext:
         FT, E = np.zeros((R, 6 * nb)), np.zeros(R)
         self._chk(self.L.rbl_ensemble_interaction_forces(self.h, FT.ctypes.data, E.ctypes.data))
         return FT, E
+
+    def ensemble_mc(self, n_sweeps, step_x, step_theta, seed=0, kBT=None, frozen=None, stride=0, trace=0, sweep_start=0, replica_base=0):
+        """n_sweeps Metropolis sweeps of every replica on the force model (include/rbl.h section 5, rbl_ensemble_mc) -> McResult;
+        the result is the ensemble's configuration.  kBT: None (the context's), one value or (R,); frozen: None, (N_bod,) or
+        (R, N_bod), bodies that are never tried.  Shape and value errors raise ValueError before the library is called"""
+        import numpy as np
+        R, nb = self.ensemble_info()
+        n_sweeps, kBT, frozen, stride, trace, sweep_start, replica_base = mc_args(
+            "ensemble_mc", R, nb, n_sweeps, step_x, step_theta, kBT, frozen, stride, trace, sweep_start, replica_base)
+        o, out = McOpts(), McOut()
+        o.size, out.size = C.sizeof(McOpts), C.sizeof(McOut)
+        o.n_sweeps, o.sweep_start, o.seed, o.step_x, o.step_theta = n_sweeps, sweep_start, int(seed), float(step_x), float(step_theta)
+        o.replica_base, o.stride, o.n_trace = replica_base, stride, trace
+        o.kBT_sets, o.kBT = (0, None) if kBT is None else (kBT.size, kBT.ctypes.data)
+        o.frozen_sets, o.frozen = (0, None) if frozen is None else (frozen.shape[0], frozen.ctypes.data)
+        tried, acc, wr = (np.zeros(R, dtype=np.int64) for _ in range(3))
+        E0, E1 = np.zeros(R), np.zeros(R)
+        out.tried, out.accepted, out.wall_rejected = tried.ctypes.data, acc.ctypes.data, wr.ctypes.data
+        out.energy_start, out.energy_end = E0.ctypes.data, E1.ctypes.data
+        nf = n_sweeps // stride if stride > 0 else 0
+        fX = fQ = fE = tr = None
+        if nf:
+            fX, fQ, fE = np.zeros((nf, R, nb, 3)), np.zeros((nf, R, nb, 4)), np.zeros((nf, R))
+            out.frame_X, out.frame_Q, out.frame_E = fX.ctypes.data, fQ.ctypes.data, fE.ctypes.data
+        if trace:
+            tr = np.zeros((R, trace, 10))
+            out.trace = tr.ctypes.data
+        self._chk(self.L.rbl_ensemble_mc(self.h, C.byref(o), C.byref(out)))
+        return McResult(tried, acc, wr, E0, E1, fX, fQ, fE, tr)
 
     def _ens_mixed_args(self, who, prescribed, body_in, slip, per=1):
         """mask (R, N_bod) uint8 -- (N_bod,) is broadcast over the replicas --, body_in (R, 6 N_bod), slip (R, n3) or None.

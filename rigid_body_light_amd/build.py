@@ -19,9 +19,9 @@ ARCH = os.environ.get("RBL_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 HIP_SOURCES = ["rbl_kernels.hip", "rbl_dense.hip", "rbl_tilechol.hip", "rbl_body_dev.hip", "rbl_small.hip", "rbl_small_joints.hip", "rbl_small_per.hip", "rbl_small_cells.hip", "rbl_core.hip", "rbl_options.hip", "rbl_comm.hip",
-               "rbl_products.hip", "rbl_bodies.hip", "rbl_roots.hip", "rbl_solvers.hip", "rbl_steps.hip", "rbl_forces.hip", "rbl_ensemble.hip", "rbl_ens_run.hip", "rbl_ens_field.hip", "rbl_ens_drive.hip", "rbl_field.hip", "rbl_mixed.hip", "rbl_flow.hip", "rbl_joints.hip", "rbl_periodic.hip",
+               "rbl_products.hip", "rbl_bodies.hip", "rbl_roots.hip", "rbl_solvers.hip", "rbl_steps.hip", "rbl_forces.hip", "rbl_ensemble.hip", "rbl_ens_run.hip", "rbl_ens_field.hip", "rbl_ens_drive.hip", "rbl_ens_mc.hip", "rbl_field.hip", "rbl_mixed.hip", "rbl_flow.hip", "rbl_joints.hip", "rbl_periodic.hip",
                "rbl_host.cpp"]
-HEADERS = ["rbl_internal.hpp", "rbl_api_internal.hpp", "rbl_small_dev.hpp", "rbl_small_solve.hpp", "rbl_joints_dev.hpp", "rbl_pair.hpp", "rbl_pair_pk.hpp", "rbl_dense_dev.hpp", "rbl_body_dev.hpp", "rbl_schedule.hpp", os.path.join("..", "..", "include", "rbl.h")]
+HEADERS = ["rbl_internal.hpp", "rbl_api_internal.hpp", "rbl_small_dev.hpp", "rbl_small_solve.hpp", "rbl_joints_dev.hpp", "rbl_pair.hpp", "rbl_pair_pk.hpp", "rbl_dense_dev.hpp", "rbl_body_dev.hpp", "rbl_schedule.hpp", "rbl_forces_dev.hpp", "rbl_philox.hpp", os.path.join("..", "..", "include", "rbl.h")]
 
 
 def lib_path():

@@ -153,6 +153,7 @@ static const RblBufRow kDevBufs[] = {
     {&rbl_ctx::d_ens_cells, RBL_BUF_PERSIST},     // an ensemble's cell per replica, R records (ens_cells_valid)
     {&rbl_ctx::d_ens_w, RBL_BUF_SCRATCH},         // ensemble step workspace: reserved at the start of each ensemble entry point
     {&rbl_ctx::d_ens_run, RBL_BUF_SCRATCH},       // ensemble run: inputs, counters and frames, reserved at the start of rbl_ensemble_run
+    {&rbl_ctx::d_ens_mc, RBL_BUF_SCRATCH},        // Metropolis chain: reserved at the start of rbl_ensemble_mc (counters, energies, flags: hipMemsetAsync before the first launch)
     {&rbl_ctx::d_ens_obs, RBL_BUF_SCRATCH},       // ensemble velocity field: reserved at its start, within one call (error words: hipMemsetAsync before the launch)
     {&rbl_ctx::d_vf, RBL_BUF_SCRATCH},            // velocity field, host form: reserved at its start, within one call
     {&rbl_ctx::d_vfw, RBL_BUF_SCRATCH},           // velocity field: packed sources and slabs, reserved right before its launches

@@ -66,26 +66,7 @@ constexpr int ET = 256;          // threads of the per-body / per-entry kernels
 constexpr int EW = RBL_SG_THREADS / 64;
 constexpr int ENS_R_MAX = 65535;
 
-// update_X_Q of one body, c_rigid_obj.cpp:679-710 (the device restatement of rbl_body_update_X_Q): U displacement units
-__device__ __forceinline__ void ens_update_body(const double *X, const double *Q, const double *U, double *Xo, double *Qo)
-{
-  const double *om = U + 3;
-  const double nrm = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
-  double qw = cos(nrm / 2.0), qx = 0.0, qy = 0.0, qz = 0.0;          // :681-683
-  if (nrm > 1.0e-10) {                                                 // :684-686
-    const double s = sin(nrm / 2.0) / nrm;
-    qx = s * om[0]; qy = s * om[1]; qz = s * om[2];
-  }
-  double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);             // :687
-  qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-  const double rw = qw * Q[0] - qx * Q[1] - qy * Q[2] - qz * Q[3];    // Q_rot * Q  (:704)
-  const double rx = qw * Q[1] + qx * Q[0] + qy * Q[3] - qz * Q[2];
-  const double ry = qw * Q[2] + qy * Q[0] + qz * Q[1] - qx * Q[3];
-  const double rz = qw * Q[3] + qz * Q[0] + qx * Q[2] - qy * Q[1];
-  qn = sqrt(rw * rw + rx * rx + ry * ry + rz * rz);                   // :705
-  Qo[0] = rw / qn; Qo[1] = rx / qn; Qo[2] = ry / qn; Qo[3] = rz / qn;
-  for (int c = 0; c < 3; ++c) Xo[c] = X[c] + U[c];                    // :706
-}
+// (ens_update_body, update_X_Q of one body: rbl_body_dev.hpp, shared with the Metropolis sampler)
 
 // Kinv V = (K^T K)^-1 K^T V of one body (:390, :406): the K^T sums over its blobs in blob order, then the 6 x 6 blocks of
 // (K^T K)^-1 = diag(1/N_blb I, (sum |c|^2 I - R MOI R^T)^-1) (:302-326; the reference configuration has its mean removed)

@@ -55,39 +55,13 @@
 
 #include "rbl_api_internal.hpp"
 #include "rbl_body_dev.hpp"
+#include "rbl_forces_dev.hpp"   // the argument structs and the energy expressions, shared with the sampler (rbl_ens_mc.hip)
 
 namespace {
 
 constexpr int IA_CAP_MAX = 1024;      // neighbour-list length per body (beyond it: RBL_ERR_CAPACITY)
 constexpr int IA_CHUNK = 512;         // neighbour blobs staged per pass (x, y, z, pad: 16 KB of LDS)
 constexpr int IA_BT = 256;            // lanes per workgroup of the pair kernel for bodies of more than 128 blobs
-
-struct IaParams {
-  double w, a, eps_w, inv_bw, eps_b, inv_bb, two_a, rc2;
-  int wall;
-};
-
-// the periodic cell of include/rbl.h section 10 as the minimum-image kernels take it (by value): lengths and reciprocals, 0 on an
-// open axis, whose reduction is then skipped (no 1 / 0)
-struct IaCell {
-  double Lx, Ly, iLx, iLy;
-  int px, py;
-};
-
-// replica w's cell from the table of an ensemble with a cell per replica (rbl_ensemble_set_cells): every kernel below that takes
-// the table reads the record of its body's or tile's window first, a workgroup-uniform index into a table that is only read
-__device__ __forceinline__ IaCell ia_cell_of(const RblEnsCellRec *__restrict__ cells, int w)
-{
-  const RblEnsCellRec &R = cells[w];
-  return {R.Lx, R.Ly, R.iLx, R.iLy, R.Lx > 0.0 ? 1 : 0, R.Ly > 0.0 ? 1 : 0};
-}
-
-// minimum-image convention on a displacement: d - L rint(d / L) on every periodic axis
-__device__ __forceinline__ void ia_min_image(const IaCell &C, double &dx, double &dy)
-{
-  if (C.px) dx = __builtin_fma(-C.Lx, rint(dx * C.iLx), dx);
-  if (C.py) dy = __builtin_fma(-C.Ly, rint(dy * C.iLy), dy);
-}
 
 // win: bodies per window -- body i only sees the bodies [i - i % win, i - i % win + win) (the replicas of an ensemble do not
 // interact); win = N_bod: every body
@@ -168,30 +142,6 @@ __global__ __launch_bounds__(64) void k_body_neighbours_cells(const double *__re
   ia_body_neighbours_per(X, N_bod, win, cut2, cull, cap, ia_cell_of(cells, blockIdx.x / win), cnt, list, err);
 }
 
-// a tabulated potential on the device: coef[k] = (c0, c1, c2, c3) of interval k, U = c0 + t (c1 + t (c2 + t c3)),
-// dU/dx = (c1 + t (2 c2 + 3 c3 t)) / h with t = (x - lo) / h - k
-struct IaTab {
-  const double4 *coef;
-  double lo, hi, inv_h, U0, dU0, hi2;                    // U0, dU0: value and slope at lo (the tangent below it); hi2: hi^2 rounded up
-  int last;                                              // n - 2, the last interval
-};
-
-// (U, dU/dx) at x <= T.hi
-__device__ __forceinline__ void ia_tab_eval(const IaTab &T, double x, double &U, double &dU)
-{
-  if (x >= T.lo) {
-    const double sx = (x - T.lo) * T.inv_h;
-    const int k = min((int)sx, T.last);
-    const double t = sx - (double)k;
-    const double4 c = T.coef[k];
-    U = c.x + t * (c.y + t * (c.z + t * c.w));
-    dU = (c.y + t * (2.0 * c.z + 3.0 * c.w * t)) * T.inv_h;
-  } else {                                               // the tangent at lo continued downwards
-    U = T.U0 + T.dU0 * (x - T.lo);
-    dU = T.dU0;
-  }
-}
-
 // TAB: bit 0 pair table PT, bit 1 height table HT (both ignored in the TAB = 0 instantiation, the model of weight, wall and
 // steric repulsion alone).  A pair is counted once when it lies inside the cutoff of a pair term that is on; the built-in
 // term is switched off by p.rc2 < 0
@@ -238,13 +188,8 @@ __device__ __forceinline__ void ia_blob_interactions(double (*s)[4], const doubl
         if ((TAB & 1) && r2 > p.rc2) {                   // only the table can reach this far
           if (!in_t) continue;
           U = 0.0; g = 0.0;
-        } else if (r >= p.two_a) {
-          U = p.eps_b * (p.two_a / r) * exp(-(r - p.two_a) * p.inv_bb);
-          g = U * (1.0 / r + p.inv_bb) / r;
-        } else {                                         // the tangent at r = 2a continued inwards
-          const double slope = p.eps_b * (1.0 / p.two_a + p.inv_bb);
-          U = p.eps_b + slope * (p.two_a - r);
-          g = r > 0.0 ? slope / r : 0.0;
+        } else {
+          ia_steric(p, r, U, g);
         }
         if constexpr (TAB & 1) {
           if (in_t) {
@@ -265,8 +210,7 @@ __device__ __forceinline__ void ia_blob_interactions(double (*s)[4], const doubl
   en += p.w * zi;
   if (p.wall) {                                          // wall repulsion, tangent continued below h = a
     double Fw, Uw;
-    if (zi >= p.a) { Uw = p.eps_w * exp(-(zi - p.a) * p.inv_bw); Fw = Uw * p.inv_bw; }
-    else { Fw = p.eps_w * p.inv_bw; Uw = p.eps_w + Fw * (p.a - zi); }
+    ia_wall(p, zi, Uw, Fw);
     fz += Fw;
     en += Uw;
   }
@@ -329,28 +273,7 @@ __global__ __launch_bounds__(IA_BT) void k_blob_interactions_cells(const double 
   ia_blob_interactions<TAB, true>(s, pos, cnt, list, cap, N_blb, tiles, p, PT, HT, f, e, npairs, ia_cell_of(cells, blockIdx.x / tiles / win));
 }
 
-// ---- blob types: one pair table per unordered type pair (include/rbl.h section 4) --------------------------------------------
-constexpr int IA_TY_PAIRS = rbl_ctx::IA_TY_PAIRS;
-
-// the typed term as the kernel takes it (by value).  desc: one IaTab per unordered type pair (hi = hi2 = -1: no table, nothing is
-// inside it); type: rows of N_blb entries -- body i reads row 0 (per_row = 0: every body alike) or row i % win
-struct IaTyped {
-  const IaTab *desc;
-  const int *type;
-  double cmax2;                                          // the largest cutoff^2 of every pair term that is on (built-in, untyped, typed)
-  int per_row;
-};
-
-// a descriptor in LDS, padded to 72 bytes: a lane's descriptor follows ITS type, so the 32 lanes of a ds_read_b64 group read
-// up to 8 different descriptors.  At 64 bytes the descriptors 4 apart share their banks ((a / 4) % 64); at 18 dwords the first
-// 32 all start on different even banks
-struct IaTabLds {
-  IaTab T;
-  double pad;
-};
-
-__device__ __forceinline__ int ia_type_pair(int s, int t) { const int hi = max(s, t); return hi * (hi + 1) / 2 + min(s, t); }
-
+// ---- blob types: one pair table per unordered type pair (include/rbl.h section 4; IaTyped, IaTabLds: rbl_forces_dev.hpp) ------
 // the pair kernel with blob types: the grid, the chunking and the summation order of ia_blob_interactions (its own body: that one's
 // kernels keep their code instruction for instruction).  The fourth slot of a staged blob carries its type; the neighbour's type
 // is the same for every lane at every step of the inner loop (an LDS broadcast), the lane's own type is not, so the descriptor of
@@ -405,16 +328,7 @@ __global__ __launch_bounds__(IA_BT) void k_blob_interactions_typed(const double 
         const bool in_y = r <= TT.hi;
         if (!(in_b || in_t || in_y)) continue;
         double U = 0.0, g = 0.0;                         // energy of the pair, -U'(r) / r
-        if (in_b) {
-          if (r >= p.two_a) {
-            U = p.eps_b * (p.two_a / r) * exp(-(r - p.two_a) * p.inv_bb);
-            g = U * (1.0 / r + p.inv_bb) / r;
-          } else {                                       // the tangent at r = 2a continued inwards
-            const double slope = p.eps_b * (1.0 / p.two_a + p.inv_bb);
-            U = p.eps_b + slope * (p.two_a - r);
-            g = r > 0.0 ? slope / r : 0.0;
-          }
-        }
+        if (in_b) ia_steric(p, r, U, g);
         if constexpr (TAB & 1) {
           if (in_t) {
             double Ut, dUt;
@@ -440,8 +354,7 @@ __global__ __launch_bounds__(IA_BT) void k_blob_interactions_typed(const double 
   en += p.w * zi;
   if (p.wall) {                                          // wall repulsion, tangent continued below h = a
     double Fw, Uw;
-    if (zi >= p.a) { Uw = p.eps_w * exp(-(zi - p.a) * p.inv_bw); Fw = Uw * p.inv_bw; }
-    else { Fw = p.eps_w * p.inv_bw; Uw = p.eps_w + Fw * (p.a - zi); }
+    ia_wall(p, zi, Uw, Fw);
     fz += Fw;
     en += Uw;
   }
@@ -576,71 +489,7 @@ __global__ __launch_bounds__(NT) void k_body_dipoles(const double *__restrict__ 
   if (e) e[(size_t)i * N_blb] += E;
 }
 
-// the bond table on the device: the pair table's construction, continued along its tangent above hi as well as below lo
-struct IaBondTab {
-  IaTab T;
-  double U1, dU1;                                        // value and slope at hi
-};
-
-// the bonds as the kernels take them (by value).  anchor: s_A | s_B (or the lab point P) per bond; param: (k, l0) per bond,
-// set-major; ends: (partner or -1, bond, which end) per entry of the CSR
-struct IaBonds {
-  const double *anchor, *param;
-  const int *kind, *body, *rows, *ptr, *ends;
-  IaBondTab BT;
-  int n, n_rows, per_set;                                // per_set: window w reads parameter set w (0: every window reads set 0)
-};
-
-// R(Q_b) s
-__device__ __forceinline__ void ia_lab_anchor(const double *__restrict__ Q, const double *__restrict__ s, int b, double (&l)[3])
-{
-  double R[9];
-  quat_rot(Q + 4 * (size_t)b, R);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) l[c] = R[3 * c] * s[0] + R[3 * c + 1] * s[1] + R[3 * c + 2] * s[2];
-}
-
-// bond b of window w between the bodies ia and ib (global indices; ib < 0: the lab point): the lever arms of both ends,
-// r = p_A - p_B, its length, the energy U(d) and the tension dU/dd.  ONE sequence of operations for both ends of a bond and
-// for the state query
-__device__ __forceinline__ void ia_bond_eval(const IaBonds &B, const double *__restrict__ X, const double *__restrict__ Q, int b,
-                                             int w, int ia, int ib, double (&lA)[3], double (&lB)[3], double (&r)[3], double &d,
-                                             double &U, double &dU)
-{
-  const double *s = B.anchor + 6 * (size_t)b;
-  ia_lab_anchor(Q, s, ia, lA);
-  double pB[3];
-  if (ib >= 0) {
-    ia_lab_anchor(Q, s + 3, ib, lB);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) pB[c] = X[3 * (size_t)ib + c] + lB[c];
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { lB[c] = 0.0; pB[c] = s[3 + c]; }
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) r[c] = (X[3 * (size_t)ia + c] + lA[c]) - pB[c];
-  d = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-  const double *q = B.param + 2 * ((size_t)(B.per_set ? w : 0) * B.n + b);
-  const double k = q[0], l0 = q[1];
-  if (B.kind[b] == 0) {
-    const double x = d - l0;
-    dU = k * x;
-    U = 0.5 * k * x * x;
-  } else {
-    double Ut, dUt;
-    if (d > B.BT.T.hi) {                                 // a bond never breaks: the tangent at hi continued upwards
-      Ut = B.BT.U1 + B.BT.dU1 * (d - B.BT.T.hi);
-      dUt = B.BT.dU1;
-    } else {
-      ia_tab_eval(B.BT.T, d, Ut, dUt);
-    }
-    U = k * Ut;
-    dU = k * dUt;
-  }
-}
-
-// bonds and tethers (include/rbl.h section 4), added to FT and to the energy entry of the body's first blob after the dipoles on
+// bonds and tethers (include/rbl.h section 4; IaBonds, ia_bond_eval: rbl_forces_dev.hpp), added to FT and to the energy entry of the body's first blob after the dipoles on
 // the same stream: one order.  One wave per (bonded body, window): blockIdx.x = window * n_rows + row
 __global__ __launch_bounds__(64) void k_body_bonds(const double *__restrict__ X, const double *__restrict__ Q, int win, int N_blb,
                                                    IaBonds B, double *__restrict__ FT, double *__restrict__ e)
@@ -987,6 +836,55 @@ static IaBonds ia_bond_args(const rbl_ctx *c, int n_win)
   return B;
 }
 
+// ---- the pieces of the model's kernel arguments that ia_launch and ia_mc_model (the Metropolis sampler's) both take: ONE builder each
+// the built-in terms (switched off: no weight, no wall term, no pair inside a negative cutoff)
+static IaParams ia_params(const rbl_ctx *c)
+{
+  const RblBodyState &S = c->S;
+  IaParams P;
+  P.w = c->ia_w; P.a = S.a; P.eps_w = c->ia_eps_wall; P.inv_bw = 1.0 / c->ia_b_wall; P.eps_b = c->ia_eps_blob;
+  P.inv_bb = 1.0 / c->ia_b_blob; P.two_a = 2.0 * S.a; P.rc2 = c->ia_r_cut * c->ia_r_cut; P.wall = S.wall ? 1 : 0;
+  if (!c->ia_on) { P.w = 0.0; P.wall = 0; P.eps_b = 0.0; P.rc2 = -1.0; }   // no pair is inside a negative cutoff
+  return P;
+}
+// R_body^2: largest blob distance from the centre, body frame (mean removed)
+static double ia_body_R2(const rbl_ctx *c)
+{
+  double R2 = 0.0;
+  for (int k = 0; k < c->S.N_blb; ++k) {
+    const double *q = &c->S.ref_cfg[3 * (size_t)k];
+    R2 = std::max(R2, q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+  }
+  return R2;
+}
+// the larger cutoff of the pair terms that are on
+static double ia_rc_max(const rbl_ctx *c, double rc_typed)
+{
+  return std::max(std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0), rc_typed);
+}
+// the body-level cull's radius.  A hair of slack for the rounding of the rotated lever arms and of the distances: it can only add
+// candidates, whose pairs beyond the cutoffs are then skipped one by one
+static double ia_cull_cut(const rbl_ctx *c, double rc_typed)
+{
+  return (2.0 * std::sqrt(ia_body_R2(c)) + ia_rc_max(c, rc_typed)) * (1.0 + 1e-12) + 1e-12;
+}
+// the largest cutoff^2 of the pair terms that are on, each rounded as its own test takes it (rc2; hi^2 a hair up)
+static double ia_cmax2(const rbl_ctx *c, const IaParams &P, const IaTab &PT, double rc_typed)
+{
+  return std::max(std::max(P.rc2, c->ia_pt.on ? PT.hi2 : -1.0), rc_typed > 0.0 ? rc_typed * rc_typed * (1.0 + 1e-15) : -1.0);
+}
+static IaCell ia_cell_value(const double *per_L)
+{
+  IaCell C = {};
+  C.Lx = per_L[0]; C.Ly = per_L[1];
+  C.px = C.Lx > 0.0 ? 1 : 0; C.py = C.Ly > 0.0 ? 1 : 0;
+  C.iLx = C.px ? 1.0 / C.Lx : 0.0; C.iLy = C.py ? 1.0 / C.Ly : 0.0;
+  return C;
+}
+// the tables in d_iat (ia_upload's order): pair | height | bond coefficients | trap k | trap X0
+static const double *ia_height_coef(const rbl_ctx *c) { return (const double *)c->d_iat.p + c->ia_pt.coef.size(); }
+static const double *ia_trap_k(const rbl_ctx *c) { return ia_height_coef(c) + c->ia_ht.coef.size() + c->ia_bt.coef.size(); }
+
 // the model over n_win windows of win bodies each (resident X of the body centres, blob positions and lever arms): neighbour
 // lists inside each window, the pair kernel, K^T f.  d_f (3 N) is required here; d_FT (6 N_bod total) and d_e may be NULL.
 // d_Q: the orientations beside d_X (the dipoles); d_accepted: a run's per-replica step counters, the field's clock (NULL: the
@@ -1028,12 +926,7 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
     return rbl_fail(c, RBL_ERR_STATE, "interactions: the cells are stored for " + std::to_string(n_cells) + " replicas, the evaluation has " +
                                           std::to_string(n_win) + " (rbl_ensemble_set_cells)");
   if (per) {
-    double R2b = 0.0;
-    for (int k = 0; k < S.N_blb; ++k) {
-      const double *q = &S.ref_cfg[3 * (size_t)k];
-      R2b = std::max(R2b, q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
-    }
-    const double rc_pair = std::max(std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0), rc_typed);
+    const double R2b = ia_body_R2(c), rc_pair = ia_rc_max(c, rc_typed);
     const double need_pair = (c->ia_on || c->ia_pt.on || typed) ? 2.0 * std::sqrt(R2b) + rc_pair : 0.0;
     const double need_dp = dp_pairs ? c->ia_dp_rcut : 0.0;
     for (int r = 0; r < n_cells; ++r) {
@@ -1052,9 +945,7 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
                                               " <= L / 2 = " + std::to_string(0.5 * Lk) + " for a unique minimum image");
       }
       if (tab_cells) continue;
-      C.Lx = per_L[0]; C.Ly = per_L[1];
-      C.px = C.Lx > 0.0 ? 1 : 0; C.py = C.Ly > 0.0 ? 1 : 0;
-      C.iLx = C.px ? 1.0 / C.Lx : 0.0; C.iLy = C.py ? 1.0 / C.Ly : 0.0;
+      C = ia_cell_value(per_L);
     }
   }
   if (tab_cells && (rc = ens_cells_upload(c))) return rc;   // (current already unless the parameters changed since the cells were set)
@@ -1065,15 +956,7 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   if (typed && (rc = ia_ty_upload(c))) return rc;
   RblPhase ph(c, RBL_T_FORCES);
   IaLayout L = ia_layout(d_cl, nbod, S.N_blb, cap);
-  double R2 = 0.0;                                       // R_body: largest blob distance from the centre, body frame (mean removed)
-  for (int k = 0; k < S.N_blb; ++k) {
-    const double *q = &S.ref_cfg[3 * (size_t)k];
-    R2 = std::max(R2, q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
-  }
-  // the larger cutoff of the pair terms that are on.  A hair of slack for the rounding of the rotated lever arms and of the
-  // distances: it can only add candidates, whose pairs beyond the cutoffs are then skipped one by one
-  const double rc_max = std::max(std::max(c->ia_on ? c->ia_r_cut : 0.0, c->ia_pt.on ? c->ia_pt.hi : 0.0), rc_typed);
-  const double cut = (2.0 * std::sqrt(R2) + rc_max) * (1.0 + 1e-12) + 1e-12;
+  const double cut = ia_cull_cut(c, rc_typed);
   if (cells)
     hipLaunchKernelGGL(k_body_neighbours_cells, dim3(nbod), dim3(64), 0, c->stream, d_X, nbod, win, cut * cut, c->ia_cull ? 1 : 0, cap,
                        cells, L.cnt, L.list, d_err);
@@ -1083,15 +966,12 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   else
     hipLaunchKernelGGL(k_body_neighbours, dim3(nbod), dim3(64), 0, c->stream, d_X, nbod, win, cut * cut, c->ia_cull ? 1 : 0, cap,
                        L.cnt, L.list, d_err);
-  IaParams P;
-  P.w = c->ia_w; P.a = S.a; P.eps_w = c->ia_eps_wall; P.inv_bw = 1.0 / c->ia_b_wall; P.eps_b = c->ia_eps_blob;
-  P.inv_bb = 1.0 / c->ia_b_blob; P.two_a = 2.0 * S.a; P.rc2 = c->ia_r_cut * c->ia_r_cut; P.wall = S.wall ? 1 : 0;
-  if (!c->ia_on) { P.w = 0.0; P.wall = 0; P.eps_b = 0.0; P.rc2 = -1.0; }   // no pair is inside a negative cutoff
+  const IaParams P = ia_params(c);
   const int bt = S.N_blb > 128 ? IA_BT : (S.N_blb + 63) / 64 * 64, tiles = (S.N_blb + bt - 1) / bt;
   const dim3 grid((unsigned)(tiles * nbod));
   const int tab = (c->ia_pt.on ? 1 : 0) | (c->ia_ht.on ? 2 : 0);
   const double *T = (const double *)c->d_iat.p;
-  const IaTab PT = ia_tab_args(c->ia_pt, T), HT = ia_tab_args(c->ia_ht, T + c->ia_pt.coef.size());
+  const IaTab PT = ia_tab_args(c->ia_pt, T), HT = ia_tab_args(c->ia_ht, ia_height_coef(c));
 #define RBL_IA_TAB(K)                                                                                                              \
   hipLaunchKernelGGL(k_blob_interactions_tab<K>, grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt, (const int *)L.list, cap, \
                      S.N_blb, tiles, P, PT, HT, d_f, d_e, L.np)
@@ -1102,8 +982,7 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
   hipLaunchKernelGGL(k_blob_interactions_cells<K>, grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt, (const int *)L.list, cap, \
                      S.N_blb, tiles, win, P, PT, HT, cells, d_f, d_e, L.np)
   if (typed) {
-    // the largest cutoff^2 of the pair terms that are on, each rounded as its own test takes it (rc2; hi^2 a hair up)
-    const double cmax2 = std::max(std::max(P.rc2, c->ia_pt.on ? PT.hi2 : -1.0), rc_typed * rc_typed * (1.0 + 1e-15));
+    const double cmax2 = ia_cmax2(c, P, PT, rc_typed);
     const IaTyped Y = ia_typed_args(c, cmax2, nty != (size_t)S.N_blb);
 #define RBL_IA_TYPED(K, CELL)                                                                                                        \
   hipLaunchKernelGGL((k_blob_interactions_typed<K, CELL>), grid, dim3(bt), 0, c->stream, d_pos, (const int *)L.cnt,                 \
@@ -1141,7 +1020,7 @@ static int ia_launch(rbl_ctx *c, const double *d_X, const double *d_Q, const dou
 #undef RBL_IA_CELLS
   if (d_FT) rbl_launch_KT_x_Lam(c->stream, d_lever, d_f, S.N_blb, nbod, d_FT);
   if (c->ia_tr_on && (d_FT || d_e)) {
-    const double *k3 = T + c->ia_pt.coef.size() + c->ia_ht.coef.size() + c->ia_bt.coef.size();
+    const double *k3 = ia_trap_k(c);
     hipLaunchKernelGGL(k_body_traps, dim3((unsigned)((nbod + 255) / 256)), dim3(256), 0, c->stream, d_X, k3, k3 + 3 * ntr, nbod,
                        (int)ntr, S.N_blb, d_FT, d_e);
   }
@@ -1203,6 +1082,36 @@ int ia_eval_batch(rbl_ctx *c, const double *d_X, const double *d_Q, const double
   IaLayout L = ia_layout(d_work, N_bod * reps, c->S.N_blb, ia_cap(N_bod));
   *d_f = L.f;
   return ia_launch(c, d_X, d_Q, d_pos, d_lever, N_bod, reps, (double *)d_work, L.f, d_FT, d_e, d_err, d_accepted, true);
+}
+
+// the model as the Metropolis kernel takes it (rbl_forces_dev.hpp): ia_launch's own arguments, from the same builders, for an
+// ensemble of n_win replicas.  The caller has just evaluated the model on the same ensemble (ia_eval_batch), which made every check
+// and upload; the dipole terms are the caller's to refuse
+IaMcModel ia_mc_model(const rbl_ctx *c, int n_win)
+{
+  IaMcModel M = {};
+  M.p = ia_params(c);
+  M.tab = (c->ia_pt.on ? 1 : 0) | (c->ia_ht.on ? 2 : 0);
+  M.PT = ia_tab_args(c->ia_pt, (const double *)c->d_iat.p);
+  M.HT = ia_tab_args(c->ia_ht, ia_height_coef(c));
+  const double rc_typed = ia_typed_rcut(c);
+  M.typed = rc_typed > 0.0 ? 1 : 0;
+  const double cmax2 = ia_cmax2(c, M.p, M.PT, rc_typed);
+  if (M.typed) M.Y = ia_typed_args(c, cmax2, c->ia_ty.size() != (size_t)c->S.N_blb);
+  M.Y.cmax2 = cmax2;
+  M.bonds = ia_bonds(c) ? 1 : 0;
+  if (M.bonds) M.B = ia_bond_args(c, n_win);
+  M.per = !c->ens_per_on ? 0 : ens_cells_stored(c) ? 2 : 1;
+  if (M.per == 1) M.C = ia_cell_value(c->ens_per_L);
+  M.cells = M.per == 2 ? (const RblEnsCellRec *)c->d_ens_cells.p : nullptr;
+  const size_t ntr = c->ia_tr_k.size() / 3;
+  M.tr_per = c->ia_tr_on ? (int)ntr : 0;
+  M.tr_k = ia_trap_k(c);
+  M.tr_X0 = M.tr_k + 3 * ntr;
+  const double cut = ia_cull_cut(c, rc_typed);
+  M.cull2 = cut * cut;
+  M.cull = c->ia_cull ? 1 : 0;
+  return M;
 }
 
 int ia_add_to_step_force(rbl_ctx *c, double *d_force)

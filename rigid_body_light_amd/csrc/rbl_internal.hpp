@@ -255,6 +255,8 @@ struct rbl_ctx {
   RblDevBuf d_ens;                                  // [X | Q] x 2 (R 7 N_bod each) | reference configuration
   RblDevBuf d_ens_w;                                // step workspace
   RblDevBuf d_ens_run;                              // rbl_ensemble_run: resident inputs, counters, status block, frames
+  RblDevBuf d_ens_mc;                               // rbl_ensemble_mc: kBT, frozen mask, counters and running energies, frames, trace
+  int mc_sweeps_per_launch = 128;                   // RBL_OPT_MC_SWEEPS_PER_LAUNCH
   RblDevBuf d_ens_obs;                              // rbl_ensemble_velocity_field: points | lambda | u | one error word per replica
   // velocity field (rbl_field.hip; include/rbl.h section 6)
   RblDevBuf d_vf;                                   // host form's staging: points | u | lambda | r

@@ -21,6 +21,7 @@
 // global memory anywhere: every sum has a fixed order, results are bitwise reproducible.
 #include "rbl_internal.hpp"
 #include "rbl_pair_pk.hpp"
+#include "rbl_philox.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -1604,21 +1605,8 @@ __global__ void k_pair_blocks(const double *__restrict__ ri, const double *__res
 // ---------------------------------------------------------------------------
 // Counter-based normal generator: Philox-4x32-10 -> Box-Muller, two doubles
 // from each 128-bit block.  Reproducible for (seed, offset) on any grid.
+// (philox4x32_10: rbl_philox.hpp, shared with the Metropolis sampler)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
 
 __global__ void k_normal(uint64_t seed, uint64_t offset, long n, double *__restrict__ out)
 {

@@ -95,6 +95,8 @@ const OptRow kOptions[] = {
      [](rbl_ctx *c, int64_t v) { c->fused_krylov = v != 0; }},
     {RBL_OPT_RECORD_MOMENTS, "record_moments", 0, 1, 0, [](const rbl_ctx *c) -> int64_t { return c->record_mom; },
      [](rbl_ctx *c, int64_t v) { c->record_mom = v != 0; c->mom_nb = 0; c->ens_mom_R = 0; }},
+    {RBL_OPT_MC_SWEEPS_PER_LAUNCH, "mc_sweeps_per_launch", 1, 65536, 128, [](const rbl_ctx *c) -> int64_t { return c->mc_sweeps_per_launch; },
+     [](rbl_ctx *c, int64_t v) { c->mc_sweeps_per_launch = (int)v; }},
 };
 
 const OptRow *find_option(int key)

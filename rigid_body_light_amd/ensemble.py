@@ -13,7 +13,8 @@ vectors within 150 KB of LDS, about 75 N_blobs + 60 N_bod doubles: 49 tetrahedra
 """
 import numpy as np
 
-from ._lib import (JOINT_BALL, RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError, blob_anchor, bond_args, cells_args, check_brownian_mask6,
+from ._lib import (McResult,  # noqa: F401  (what metropolis returns)
+                   JOINT_BALL, RUN_CHECK_DEFAULT, RUN_REJECT, RUN_STOP, DeviceContext, RblError, blob_anchor, bond_args, cells_args, check_brownian_mask6,
                    default_q_rel, hinge, joint_kind_args, motor, periodic_args, weld)
 
 
@@ -274,6 +275,37 @@ class Ensemble:
         args = dict(F_body=F, prescribed=m, body_in=b, brownian=brownian, seed=seed, stride=stride, on_error=modes[on_error],
                     check_every=check_every, slip=s, split_rand=split_rand, delta=delta, max_iter=max_iter, rtol=rtol, per=per)
         return n_steps, args, obs
+
+    # ------------------------------------------------------------------ Metropolis sampling (include/rbl.h section 5, rbl_ensemble_mc)
+    def metropolis(self, n_sweeps, step_x, step_theta, seed=0, kBT=None, frozen=None, stride=0, trace=0, sweep_start=0, replica_base=0):
+        """n_sweeps Metropolis sweeps of every replica on the total energy of the force model (the one interaction_energy reports),
+        in one call: a sweep tries every body once, in order, with a uniform displacement in [-step_x, step_x]^3 and a rotation
+        vector in [-step_theta, step_theta]^3 -> McResult (tried, accepted, acceptance, wall_rejected, energy_start, energy_end, and
+        with stride > 0 the frames X, Q, E after every stride-th sweep, with trace > 0 the first trials of every replica).  The result
+        is the ensemble's configuration: every step continues from it.  kBT: None (the ensemble's), one value, or (R,) for a
+        temperature sweep; frozen: (N_bod,) or (R, N_bod), bodies that never move and still act on the others.  The draws depend on
+        (seed, replica_base + r, sweep_start + s, b) alone: n1 + n2 sweeps are n1 sweeps followed by n2 with sweep_start=n1, and
+        replica r is a one-replica ensemble with replica_base=r.  Not offered: dipole terms, hard joints, moves of several bodies,
+        cluster or swap moves, replica exchange (RblError names the term)"""
+        return self.ctx.ensemble_mc(n_sweeps, step_x, step_theta, seed=seed, kBT=kBT, frozen=frozen, stride=stride, trace=trace,
+                                    sweep_start=sweep_start, replica_base=replica_base)   # (the binding owns the argument checks)
+
+    def metropolis_tune(self, target=0.4, n_sweeps=20, rounds=8, step_x=0.1, step_theta=0.1, seed=0, kBT=None, frozen=None):
+        """a host loop that scales BOTH step sizes by one common factor towards the acceptance `target` (mean over the replicas):
+        `rounds` chains of n_sweeps sweeps, each followed by factor = clip(acceptance / target, 0.5, 2) -> (step_x, step_theta).
+        The chains move the ensemble (a burn-in).  Adapting the steps while sampling would bias the chain: tune first, then
+        sample with the returned steps held fixed"""
+        if not 0.0 < target < 1.0:
+            _fail("metropolis_tune: target must lie in (0, 1); got %r" % (target,))
+        if int(rounds) < 1:
+            _fail("metropolis_tune: rounds must be >= 1; got %r" % (rounds,))
+        sx, st = float(step_x), float(step_theta)
+        for k in range(int(rounds)):
+            res = self.metropolis(n_sweeps, sx, st, seed=seed, kBT=kBT, frozen=frozen, sweep_start=k * int(n_sweeps))
+            acc = float(res.accepted.sum()) / max(1, int(res.tried.sum()))
+            f = min(2.0, max(0.5, acc / target))
+            sx, st = sx * f, st * f
+        return sx, st
 
     # ------------------------------------------------------------------ driven runs (include/rbl.h section 5, rbl_ensemble_run_driven)
     def _drive(self, who, cos, sin, omega, t0, schedule, cycle_start, lockin=False):
