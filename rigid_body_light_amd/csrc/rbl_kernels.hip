@@ -889,7 +889,6 @@ __global__ __launch_bounds__(TS *SW, sym_min_waves(WALL, NI, SW, PREC, NV)) void
         for (int s = 0; s < TS; ++s) {
           const SymCol<NV> cj = sym_read_col<NV>(sP, off16);
           const int jj = (int)(off16 >> 4);
-          off16 = (off16 + 16u) & (unsigned)(TS * 16 - 16);
           RblV3 vj[NV];
 #pragma unroll
           for (int v = 0; v < NV; ++v) vj[v] = RblV3{0.0, 0.0, 0.0};
@@ -897,6 +896,7 @@ __global__ __launch_bounds__(TS *SW, sym_min_waves(WALL, NI, SW, PREC, NV)) void
           for (int a = 0; a < NI; ++a)
             rbl_pair_symv<WALL, kUnit, decltype(nearchk)::value>(Pu, xi[a], yi[a], zi[a], Fi[a], cj.x, cj.y, cj.z, cj.f, ui[a], vj, flags, WK);
           col_add(jj, vj);
+          off16 = (off16 + 16u) & (unsigned)(TS * 16 - 16);   // advanced last: old and new value never live together (no copy)
         }
       };
       if (far_tile) sweep(std::false_type{});   // no pair can overlap: sweep without the per-pair test

@@ -80,6 +80,11 @@ __device__ __forceinline__ double rbl_rsqrt(double x)
 //     -2 z_i' and 6 z_i' are the row's, formed outside the sweep's loop
 //     T1p = b2p - 60 u'^2,   zz bracket  u'^2 (180v - 24) - v (b2p + 12u'),   A' = s' + 2 s'^3,   Bc' = (s' - 6 s'^3) / r'^2
 //                                 (the brackets coincide because 3 (2 - 10v) = 9 (2/3 - 10/3 v): lambda^2 = 3 and nothing else)
+//     and, w' u' being w'^3, the brackets X = (6v - 2 - 2 z_i' z_j') + u' Q and Y = (Q + 6 z_i' z_j') + u'(210v - 30) are used as they
+//     stand (b1 = -1 + u' X, b2p = u' Y are never formed): their factor u' rides on the odd powers w'^3, w'^5 = w'^3 u' that the five
+//     scalars are multiplied by anyway --
+//     cF = (A - w') + w'^3 X,  beta = Bw + w'^5 Y,  gxz, gzx = gm -+ (Y - 60u') Rz w'^5,  mzz = cF + gm dz + w'^3 [u'(180v - 24) - v (Y + 12)]
+//     u'^2 and u' Y go, w'^5 comes: a third instruction less (70 fp64 per unordered pair, 62 per ordered one; profiles/wall_brackets.md)
 // A gfx9 VOP3 instruction reads at most one SGPR/constant, so of a bracket's two non-inline constants the compiler re-materialises the
 // second one into a VGPR with a v_mov_b64 on EVERY evaluation.  A caller with registers to spare passes them in as
 // opaque register-resident values (RblWallK from rbl_wall_k_resident()) and saves those issue slots (-30 serves Q and, as the addend,
@@ -118,19 +123,20 @@ __host__ __device__ __forceinline__ RblParams rbl_unit_params(const RblParams &P
 }
 
 // The shared unit's constants are small integers, and gfx950 encodes such a double (low word zero) as the 32-bit literal of a VOP2
-// v_fmac_f64 -- whose addend is its destination.  Where the addend lives on (fma(v, 210, -30): the resident -30;  T1p = fma(u'^2, -60, b2p):
-// b2p) the compiler takes that form anyway and copies the addend first, a v_mov_b64 per pair each.  So these multipliers are
+// v_fmac_f64 -- whose addend is its destination.  Where the addend lives on (fma(v, 210, -30): the resident -30;  fma(u', -60, Y): Y)
+// the compiler takes that form anyway and copies the addend first, a v_mov_b64 per pair each.  So these multipliers are
 // opaque as well, in SCALAR register pairs (a VOP3 v_fma_f64 reads one): 210 (k2), -60 (s1) and the 6 of Q and of 6v - 2 (s2, which the
 // compiler otherwise keeps in a vector pair).  -30 and 180 stay in vector pairs: they share an instruction with 210 and -24.
+// The 12 of Y + 12 (k4) is a scalar pair too: v_add_f64 exists as VOP3 only and takes no literal at all.
 // (All of them in vector registers: the same instructions, and k_apply_M_symw<true,2,4,1> spills 12 bytes at its 168 VGPRs.)
 struct RblWallK {
-  double k1, k2, k3, k4;   // physical / radius units: -10/3, 70/3, 20, 3/2;  shared unit: -30, 210, 180, (unused)
+  double k1, k2, k3, k4;   // physical / radius units: -10/3, 70/3, 20, 3/2;  shared unit: -30, 210, 180, 12
   double s1, s2;           // shared unit: -60, 6
 };
 template <int UNIT = RBL_UNIT_PHYS>
 __device__ __forceinline__ RblWallK rbl_wall_k_literal()
 {
-  if constexpr (UNIT == RBL_UNIT_SHARED) return RblWallK{-30.0, 210.0, 180.0, 0.0, -60.0, 6.0};
+  if constexpr (UNIT == RBL_UNIT_SHARED) return RblWallK{-30.0, 210.0, 180.0, 12.0, -60.0, 6.0};
   else return RblWallK{-10.0 / 3.0, 70.0 / 3.0, 20.0, 1.5, 0.0, 0.0};
 }
 template <int UNIT>
@@ -138,7 +144,7 @@ __device__ __forceinline__ RblWallK rbl_wall_k_resident()
 {
   RblWallK K = rbl_wall_k_literal<UNIT>();
   // opaque to the optimiser: the values stay in the registers they are given
-  if constexpr (UNIT == RBL_UNIT_SHARED) asm volatile("" : "+v"(K.k1), "+v"(K.k3), "+s"(K.k2), "+s"(K.s1), "+s"(K.s2));
+  if constexpr (UNIT == RBL_UNIT_SHARED) asm volatile("" : "+v"(K.k1), "+v"(K.k3), "+s"(K.k2), "+s"(K.k4), "+s"(K.s1), "+s"(K.s2));
   else asm volatile("" : "+v"(K.k1), "+v"(K.k2), "+v"(K.k3), "+v"(K.k4));
   return K;
 }
@@ -148,7 +154,8 @@ __device__ __forceinline__ void rbl_wall_coeffs(const RblParams &P, double dz, d
                                                 double r2, double A, double Bc, double &cF, double &beta, double &gxz,
                                                 double &gzx, double &mzz, const RblWallK &K = rbl_wall_k_literal<UNIT>())
 {
-  // Further identities that take instructions out (84 -> 75 fp64 instructions per unordered pair):
+  // Further identities that take instructions out (84 -> 75 fp64 instructions per unordered pair when they came in; 70 today, see the
+  // header comment):
   //   T0 = 2g - ez = (z_j - z_i)/R = -dz/R             (g never formed)
   //   gk = z_i z_j / R^2 = (1 - r^2/R^2) / 4           (R^2 - r^2 = 4 z_i z_j)
   //   v = ez^2 = 1 - q/R^2                             (ez itself is only needed as Rz/R inside Rz w/R^2)
@@ -166,37 +173,54 @@ __device__ __forceinline__ void rbl_wall_coeffs(const RblParams &P, double dz, d
   const double iR2 = invR * invR;
   const double u = w * w;
   const double v = __builtin_fma(-q, iR2, 1.0);
-  // (L2 = 1 outside the shared unit: the constants below are then the ones of the header comment's first form)
-  constexpr double L2 = rbl_unit_l2(UNIT);
-  double b1, b2p;
   if constexpr (UNIT == RBL_UNIT_SHARED) {
+    constexpr double L2 = rbl_unit_l2(UNIT);
     static_assert(L2 * 2.0 == L2 * L2 * 2.0 / 3.0 && L2 * -10.0 == L2 * L2 * -10.0 / 3.0, "Q is shared only where lambda^2 = 3");
     // gk = z_i z_j / R^2 = z_i z_j u here (u = 1 / R^2 in the unit), so the constant parts join the Horner brackets:
-    //   b1 = -1 + u [(6v - 2 - 2 z_i z_j) + u Q],   b2p = u [(Q + 6 z_i z_j) + u (210v - 30)]
-    // -2 z_i and 6 z_i belong to the row: a sweep forms them once, outside its loop
+    //   b1 = -1 + u X,  X = (6v - 2 - 2 z_i z_j) + u Q;      b2p = u Y,  Y = (Q + 6 z_i z_j) + u (210v - 30)
+    // -2 z_i and 6 z_i belong to the row: a sweep forms them once, outside its loop.
+    // The brackets stay un-multiplied: every use of b1 and b2p goes on to a multiplication by w or w^3 = w u (u is 1 / R^2 here), so
+    // the factor u moves into the odd powers w^3, w^5 = w^3 u, which all uses share:
+    //   cF   = A + w b1         = (A - w) + w^3 X
+    //   beta = Bw + w^3 b2p     = Bw + w^5 Y
+    //   T1p  = b2p - 60 u^2     = u (Y - 60 u) =: u T1Y,      gxz, gzx = gm -+ T1p Rz w^3 = gm -+ T1Y Rz w^5
+    //   mzz  = ... + w [u^2 (180v - 24) - v (b2p + 12 u)] = ... + w^3 [u (180v - 24) - v (Y + 12)]
+    // u^2 and the product u Y are never formed, w^5 is: one instruction less per pair.  (12: an opaque scalar pair where the caller
+    // keeps its constants resident -- v_add_f64 takes no literal.)
     const double Q = __builtin_fma(v, K.k1, K.s2);                                   // 6 - 30 v
     const double m = __builtin_fma(-2.0 * zi, zj, -2.0);
-    b1 = __builtin_fma(u, __builtin_fma(u, Q, __builtin_fma(v, K.s2, m)), -1.0);
-    b2p = u * __builtin_fma(u, __builtin_fma(v, K.k2, K.k1), __builtin_fma(6.0 * zi, zj, Q));
+    const double X = __builtin_fma(u, Q, __builtin_fma(v, K.s2, m));
+    const double Y = __builtin_fma(u, __builtin_fma(v, K.k2, K.k1), __builtin_fma(6.0 * zi, zj, Q));
+    const double w3 = w * u, w5 = w3 * u;
+    const double Bw = Bc - w3;
+    cF = __builtin_fma(w3, X, A - w);
+    beta = __builtin_fma(Y, w5, Bw);                                                 // lateral dyad: (Bc + fact2/R^2) dl dl^T
+    const double T1Y = __builtin_fma(u, K.s1, Y);                                    // T1 / (ez u)
+    const double gm = dz * Bw, gd5 = Rz * w5;
+    gxz = __builtin_fma(-T1Y, gd5, gm);                                              // M_xz = dx gxz, M_yz = dy gxz
+    gzx = __builtin_fma(T1Y, gd5, gm);                                               // M_zx = dx gzx, M_zy = dy gzx
+    const double c = __builtin_fma(u, __builtin_fma(v, K.k3, -24.0), -(v * (Y + K.k4)));
+    mzz = __builtin_fma(w3, c, __builtin_fma(gm, dz, cF));
   } else {
+    // physical lengths and radii (w^3 = w / R^2 is not w u in physical lengths): the header comment's first form
     const double rr = r2 * iR2;                                                      // (r/R)^2 = 1 - 4 gk
     const double t1 = __builtin_fma(u, __builtin_fma(v, K.k1, 2.0 / 3.0), __builtin_fma(v, 2.0, -2.0 / 3.0));
     const double t2 = __builtin_fma(u, __builtin_fma(v, K.k2, -10.0 / 3.0), __builtin_fma(v, -10.0, 2.0));
-    b1 = __builtin_fma(u, t1, __builtin_fma(0.5, rr, -K.k4));                        // -1 - 2 gk + u t1
-    b2p = __builtin_fma(u, t2, __builtin_fma(-rr, K.k4, K.k4));                      // b2 + 1 = 6 gk + u t2
+    const double b1 = __builtin_fma(u, t1, __builtin_fma(0.5, rr, -K.k4));           // -1 - 2 gk + u t1
+    const double b2p = __builtin_fma(u, t2, __builtin_fma(-rr, K.k4, K.k4));         // b2 + 1 = 6 gk + u t2
+    const double uu = u * u;
+    const double T1p = __builtin_fma(uu, -20.0 / 3.0, b2p);                          // T1 / ez
+    const double w3 = w * iR2;                                                       // w / R^2
+    const double Bw = Bc - w3;
+    cF = __builtin_fma(w, b1, A);
+    beta = __builtin_fma(b2p, w3, Bw);                                               // lateral dyad: (Bc + fact2/R^2) dl dl^T
+    const double gm = dz * Bw, gdw = Rz * w3;
+    gxz = __builtin_fma(-T1p, gdw, gm);                                              // M_xz = dx gxz, M_yz = dy gxz
+    gzx = __builtin_fma(T1p, gdw, gm);                                               // M_zx = dx gzx, M_zy = dy gzx
+    // zz bracket  u d1 - v b2p,  d1 = u (20 v - 8/3) - 4 v:   u^2 (20 v - 8/3) - v (b2p + 4 u)
+    const double c = __builtin_fma(uu, __builtin_fma(v, K.k3, -8.0 / 3.0), -(v * __builtin_fma(4.0, u, b2p)));
+    mzz = __builtin_fma(w, c, __builtin_fma(gm, dz, cF));
   }
-  const double uu = u * u;
-  const double T1p = __builtin_fma(uu, UNIT == RBL_UNIT_SHARED ? K.s1 : -20.0 / 3.0, b2p);   // T1 / ez
-  const double w3 = w * iR2;                                                         // w / R^2
-  const double Bw = Bc - w3;
-  cF = __builtin_fma(w, b1, A);
-  beta = __builtin_fma(b2p, w3, Bw);                                                 // lateral dyad: (Bc + fact2/R^2) dl dl^T
-  const double gm = dz * Bw, gdw = Rz * w3;
-  gxz = __builtin_fma(-T1p, gdw, gm);                                                // M_xz = dx gxz, M_yz = dy gxz
-  gzx = __builtin_fma(T1p, gdw, gm);                                                 // M_zx = dx gzx, M_zy = dy gzx
-  // zz bracket  u d1 - v b2p,  d1 = u (20 v - 8/3) - 4 v:   u^2 (20 v - 8/3) - v (b2p + 4 u)      (shared unit: 180, 24, 12)
-  const double c = __builtin_fma(uu, __builtin_fma(v, K.k3, -8.0 * L2 * L2 / 3.0), -(v * __builtin_fma(4.0 * L2, u, b2p)));
-  mzz = __builtin_fma(w, c, __builtin_fma(gm, dz, cF));
 }
 
 // ---------------------------------------------------------------------------
@@ -275,11 +299,10 @@ __device__ __forceinline__ void rbl_pair_accum(const RblParams &P, double xi, do
 //     U_j[v] += M_ji F_i[v]      (accumulated into uj[v]; caller adds it to j)
 // M_ji = M_ij^T holds exactly for the RPY part and, for the wall part, through the
 // role swap g <-> k (h = z_i instead of z_j): fact1, fact2, the e_z-part of fact3
-// and the h-free part of fact5 are shared.  ~78 fp64 instructions per unordered wall pair
-// (measured in the ISA of k_apply_M_sym<true,2>) vs 2 x ~68 for two ordered evaluations.
-// NV = 2: the coefficients (~60 of the ~84 fp64 instructions of a wall pair) are shared, only the 20-FMA application
-// is repeated.  Used for the two Brownian increments of the stochastic step (lock-step Lanczos) and for 2-3
-// simultaneous vectors in general.
+// and the h-free part of fact5 are shared.  70 fp64 instructions per unordered wall pair in the shared unit
+// (the far sweep of k_apply_M_sym<true,4> and <true,2>, librbl.isa.json) vs 2 x 62 for two ordered evaluations (k_apply_M<true>).
+// NV = 2: the coefficients (50 of the 70) are shared, only the 20-FMA application is repeated: 90 per pair.
+// Used for the two Brownian increments of the stochastic step (lock-step Lanczos) and for 2-3 simultaneous vectors in general.
 // ---------------------------------------------------------------------------
 // NEARCHK = false: the caller has proved (tile bounding boxes) that no pair of this sweep is closer than 2a,
 // the overlap branch and its per-pair compare are compiled out.
